@@ -14,7 +14,9 @@ HIP streams (default: what the product's labelling loops keep -- 2, or 3 with `-
 its own workspace and pinned host buffer, so that many batches are in flight per GPU (every step is still a complete pass over its
 own batch, and all K steps are inside the timed, fenced region).
 
-Besides the contract fields the JSON line carries
+A plain run sets up, warms up, times the K steps, writes the last step's outputs if `--dump-outputs DIR` is given (ids, argmax,
+maxprob, offsets of the TagBatch a caller of `label` receives, as float32 .npy; the inputs are seeded, so two builds compare output
+for output) and prints the JSON line (`roofline` null).  Everything else it measures runs only with `--full`, where the line also carries
   roofline        the dominant kernel family (bf16 MFMA GEMMs): algorithmic FLOPs / HIP-event time per launch, measured on the
                   launch stream in a second pass over the same K steps (one batch at a time, so nothing else shares the GPU with
                   the kernel being timed), against the 2.5 PFLOP/s dense bf16 MFMA peak; `breakdown_ms_per_step` gives the same
@@ -25,6 +27,8 @@ Besides the contract fields the JSON line carries
   cpu_baseline    the oracle (pure-torch fp32 CPU restatement of the reference forward, kind "port") timed on this box's host
                   cores on a bounded sample of the same workload, at B = 1 per call (the reference's own loop, infer.py:261)
                   and batched (rank 0, N = 1 only)
+  precision_high  a second timed leg with `model.precision: high` (default workload only), and the committed parity record
+The `--no-*` switches below turn single legs of a `--full` run off.
 """
 import argparse
 import json
@@ -83,6 +87,12 @@ def parse():
                     help="walk the launcher and the N-rank host path on CPU (gloo, no GPU, no kernels): shard plan, barrier, one gather "
                          "of fake packed tags, max-reduce of the clock; prints the JSON line with value null")
     ap.add_argument("--master-port", type=int, default=0, help="rendezvous port of the self-launched ranks (default: a free one)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beyond the headline: with-H2D, per-launch HIP-event roofline, precision high + parity "
+                         "record, CPU baseline (each can be turned off by its --no-* switch)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write rank 0's last-step TagBatch (ids, argmax, maxprob, offsets) as float32 "
+                         "DIR/<name>.npy (at most 64 MB: a seeded sample of clips beyond that)")
     return ap.parse_args()
 
 
@@ -257,6 +267,24 @@ def cpu_baseline(cfg, labels, sd_np, clips, calls, clip_seconds):
     }
 
 
+DUMP_LIMIT_BYTES = 63 * 10 ** 6          # --dump-outputs: below 64 MB with the .npy headers
+
+
+def dump_outputs(out, path):
+    """The arrays of one TagBatch as float32 .npy files (ids / argmax < 2^24, exact).  Over DUMP_LIMIT_BYTES, a fixed seeded sample of
+    clips (rows) is written instead, the same rows for every array."""
+    arrays = {"ids": out.ids, "argmax": out.argmax, "maxprob": out.maxprob, "offsets": out.offsets}
+    arrays = {k: v.float().cpu().numpy() for k, v in arrays.items()}
+    B = arrays["ids"].shape[0]
+    per_row = sum(a.nbytes for a in arrays.values()) // B
+    if per_row * B > DUMP_LIMIT_BYTES:
+        rows = np.sort(np.random.default_rng(0).choice(B, max(1, DUMP_LIMIT_BYTES // per_row), replace=False))
+        arrays = {k: a[rows] for k, a in arrays.items()}
+    os.makedirs(path, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(path, k + ".npy"), np.ascontiguousarray(a))
+
+
 def main():
     args = parse()
     rank = int(os.environ.get("RANK", "0"))
@@ -315,6 +343,7 @@ def main():
     host_bufs = [torch.zeros((world if (rank == 0 and gather_on) else 1), words, dtype=torch.int32).pin_memory() for _ in range(nfl)]
     streams = [torch.cuda.current_stream(dev)] + [torch.cuda.Stream(dev) for _ in range(nfl - 1)]
     step_no = [0]
+    last_out = [None]                                     # the TagBatch of the latest step (--dump-outputs)
     # the optional gather leg (--gather); WFL_BENCH_FAKE_WORLD walks its code path on one rank
     multi = (world > 1 and args.gather) or bool(os.environ.get("WFL_BENCH_FAKE_WORLD"))
     comm_stream = [torch.cuda.Stream(dev)] if multi else [None]
@@ -328,6 +357,7 @@ def main():
         host_tags = host_bufs[slot]
         with torch.cuda.stream(streams[slot]):
             out = (mdl or model).label(wav if x is None else x, lang, threshold=0.5, graph=graph, slot=slot)
+            last_out[0] = out
             if not multi:
                 if not os.environ.get("WFL_BENCH_NO_D2H"):        # (diagnostic: how much the tag copy's blit kernel costs the step)
                     host_tags[0].copy_(out.packed, non_blocking=True)
@@ -369,10 +399,12 @@ def main():
     fence()
     elapsed = time.perf_counter() - t0
     check_status()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(last_out[0], args.dump_outputs)
 
     # ---- with-H2D leg: the same K steps, each on a batch that crosses PCIe inside the step
     h2d = None
-    if not args.no_h2d:
+    if args.full and not args.no_h2d:
         n_rot = 8
         pinned = [torch.from_numpy(np.roll(wav_host, j, axis=0).copy()).pin_memory() for j in range(n_rot)]
         dev_in = [torch.empty(B, L, dtype=torch.float32, device=dev) for _ in range(nfl + 1)]
@@ -415,7 +447,7 @@ def main():
 
     # Roofline pass: the same K steps again, launched eagerly with a HIP-event pair around every GEMM / attention / LSTM /
     # log-mel / LayerNorm launch on the launch stream (events cannot live inside a replayed graph; kernels and inputs are identical).
-    use_events = not args.no_kernel_events
+    use_events = args.full and not args.no_kernel_events
     prof = []
     if use_events:
         step(graph=False, single=True)
@@ -437,7 +469,7 @@ def main():
     # ---- second timed leg: the same workload with `model.precision: high` -- the mode whose tag indices are the reference's (the
     # parity record below); same batch, same fences, every rank, max over ranks.  The headline `value` stays the default build's.
     high = None
-    if (args.config_index == 1 and not args.full_head and args.precision == "default" and not args.no_precision_high
+    if (args.full and args.config_index == 1 and not args.full_head and args.precision == "default" and not args.no_precision_high
             and str(cfg["model"].get("weight_dtype", "bf16")) != "fp8"):
         import copy
         cfg_h = copy.deepcopy(cfg)
@@ -560,10 +592,10 @@ def main():
             result.update(h2d)
         if high:
             result["precision_high"] = high
-        par = parity_record()
+        par = parity_record() if args.full else None
         if par and args.config_index == 1 and not args.full_head:
             result["parity"] = par
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             clips = args.cpu_clips or (16 if (args.config_index == 1 and not args.full_head) else 4)
             result["cpu_baseline"] = cpu_baseline(cfg, labels, sd_np, clips, args.cpu_calls, clip_seconds)
             result["speedup_vs_cpu_baseline"] = result["value"] / result["cpu_baseline"]["value"]

@@ -162,7 +162,8 @@ def test_three_batches_in_flight_label_like_one(workdir, monkeypatch):
 def test_bench_emits_one_json_line_with_the_contract_keys():
     """bench.py is what the driver times: a short run must print exactly one JSON line with the contract's keys (roofline and
     cpu_baseline objects included) and a status-clean forward."""
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--cpu-calls", "1", "--cpu-clips", "1"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "3", "--warmup", "1", "--cpu-calls", "1",
+                        "--cpu-clips", "1"],
                        capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.strip().startswith("{")]
@@ -175,3 +176,28 @@ def test_bench_emits_one_json_line_with_the_contract_keys():
     assert set(("bound", "achieved", "peak", "unit", "frac", "traffic")) <= set(d["roofline"])
     assert set(("value", "unit", "cores", "kind", "sample")) <= set(d["cpu_baseline"])
     assert "workload" in d["config"]
+
+
+def test_plain_bench_run_times_only_the_steps_and_dumps_the_last_outputs(tmp_path):
+    """A plain bench.py run (no --full) prints the headline line without the extra legs and, with --dump-outputs, writes the last
+    timed step's TagBatch as float32 .npy files of the workload's shape."""
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--dump-outputs", str(tmp_path)],
+                       capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [l for l in r.stdout.splitlines() if l.strip().startswith("{")]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in d, k
+    assert d["steps"] == 2 and d["value"] > 0 and d["ms_per_step"] > 0 and d["roofline"] is None
+    for k in ("cpu_baseline", "precision_high", "value_with_h2d", "parity"):
+        assert k not in d, k
+    B, T = d["config"]["clips_per_gpu"], d["config"]["frames_per_clip"]
+    got = {n: np.load(tmp_path / (n + ".npy")) for n in ("ids", "argmax", "maxprob", "offsets")}
+    assert sorted(os.listdir(tmp_path)) == sorted(n + ".npy" for n in got)
+    assert all(a.dtype == np.float32 for a in got.values())
+    assert got["ids"].shape == got["argmax"].shape == got["maxprob"].shape == (B, T) and got["offsets"].shape == (B, T, 2)
+    assert sum(a.nbytes for a in got.values()) <= 64e6
+    ids = got["ids"]
+    assert np.array_equal(ids, np.round(ids)) and ids.min() >= 0 and ids.max() < d["config"]["tags"]
+    assert np.isfinite(got["maxprob"]).all() and got["maxprob"].min() >= 0 and got["maxprob"].max() <= 1

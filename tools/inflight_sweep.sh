@@ -6,7 +6,7 @@ what=${1:-fullhead}
 out=gpurun_out/inflight_sweep_$what.jsonl
 mkdir -p gpurun_out
 : > $out
-common="--steps 24 --warmup 3 --no-cpu-baseline --no-kernel-events --no-h2d"
+common="--full --steps 24 --warmup 3 --no-cpu-baseline --no-kernel-events --no-h2d"
 if [ $what = fullhead ]; then
   for b in 16 64; do
     for n in 1 2 3 4 5 6; do

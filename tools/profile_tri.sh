@@ -3,7 +3,7 @@ ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$ROOT/gpurun_out/r4d
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-B="python3 $ROOT/bench.py"
+B="python3 $ROOT/bench.py --full"
 timeout -k 10 400 $B > $OUT/bench_cfg2.json 2> $OUT/bench_cfg2.err || exit 1
 timeout -k 10 300 $B --precision high --steps 10 --warmup 2 --no-cpu-baseline > $OUT/bench_cfg2_precision_high.json 2>> $OUT/bench.err || exit 1
 WFL_TRI=0 timeout -k 10 300 $B --precision high --steps 10 --warmup 2 --no-cpu-baseline --no-kernel-events --no-h2d > $OUT/bench_cfg2_precision_high_tri0.json 2>> $OUT/bench.err || exit 1
