@@ -70,8 +70,9 @@ typedef struct wfl_arch {
   int32_t wavlm_do_normalize;
   int32_t fp8_weights;               /* 1: the Whisper encoder layers' q|k|v, out_proj, fc1, fc2 weights are kept as OCP e4m3 with one
                                         fp32 scale per output channel (BASELINE configs[4]); 0: bf16 */
-  int32_t mel_hop;                   /* WFL_ENC_NONE: hop of the mel front-end = int(frame_duration * sample_rate) (model.py:88);
-                                        d_model = n_mels = the hidden width (model.py:91); 160 and 320 are built */
+  int32_t mel_hop;                   /* WFL_ENC_NONE: hop of the mel front-end = int(frame_duration * sample_rate) (model.py:88): 160 or
+                                        320 when mel_sample_rate is 0, any hop >= 1 when it is set (160 and 320 have kernels of their own,
+                                        every other hop runs the general one); d_model = n_mels = the hidden width (model.py:91) */
   int32_t precision;                 /* 0: bf16 operands (default).  1 ("model.precision: high", round 3): every GEMM, the attention's two
                                         products and the BiLSTM recurrence (hidden size <= 256 per direction) run as three bf16 MFMA passes
                                         over split operands -- A_hi W_hi + A_hi W_lo + A_lo W_hi, summed in fp32 -- with every activation
@@ -87,7 +88,11 @@ typedef struct wfl_arch {
                                         2: ONE e4m3 value per activation on the same MFMA: the fastest form, and 5-9 % of the raw tag
                                            decisions then differ from that reference (three mantissa bits) -- an explicit opt-in;
                                         1: round 3's form of 2 on the non-scaled fp8 MFMA (kept for A/B runs). */
-  int32_t reserved[6];
+  int32_t mel_sample_rate;           /* WFL_ENC_NONE: data.sample_rate of the model, 8000 .. 192000 Hz, with any mel_hop >= 1.  0 (a caller
+                                        that predates the field): 16 kHz, mel_hop 160 or 320 only, as before.  The HTK mel bank spans
+                                        0 .. rate // 2 Hz over the 201 STFT bins, as torchaudio's MelSpectrogram defaults; the caller feeds
+                                        audio at this rate (wfl_forward's wav) */
+  int32_t reserved[5];
 } wfl_arch;
 
 const char* wfl_last_error(void);
@@ -127,7 +132,7 @@ int64_t wfl_workspace_bytes(const wfl_model* m, int32_t B, int32_t L);
 
 /* Replaces BIOPhonemeTagger.forward (model.py:148-194) + decode_predictions (196-198) + the softmax/threshold
  * half of suppress_low_confidence (infer.py:86-96) for a batch of clips.
- *   wav        [B][ldw] fp32 16 kHz samples, L valid columns; lens (optional, [B] int32) marks shorter clips
+ *   wav        [B][ldw] fp32 samples (16 kHz; WFL_ENC_NONE: mel_sample_rate), L valid columns; lens (optional, [B] int32) marks shorter clips
  *   ids        [B][T] int32  argmax class, or o_id where max prob < threshold
  *   argmax     [B][T] int32  raw argmax                      (optional)
  *   maxprob    [B][T] fp32   max softmax probability

@@ -87,11 +87,13 @@ def _suffix(name: str, prefix: str) -> str:
     return base.lstrip("-_")
 
 
-def resolve_encoder_arch(model_cfg: dict, data_cfg: dict | None = None):
+def resolve_encoder_arch(model_cfg: dict, data_cfg: dict | None = None, any_rate: bool = False):
     """config["model"] (+ config["data"]) -> ("whisper", WhisperArch) | ("wavlm", WavLMArch) | ("none", MelArch).
 
     Mirrors the selection at /root/reference/model.py:57-93.  `encoder_type: none` reads sample_rate, frame_duration and n_mels
-    from config["data"] (model.py:85-90).
+    from config["data"] (model.py:85-90).  any_rate=False keeps this function's original contract for `none`: 16 kHz only (the hop
+    is checked by the library: 160 or 320).  any_rate=True takes any positive sample_rate and any frame_duration whose hop
+    int(frame_duration * sample_rate) is at least 1, as the reference does; BIOPhonemeTagger(any_rate=True) and Labeler use it.
     """
     enc = str(model_cfg["encoder_type"]).lower()
     override = dict(model_cfg.get("encoder_arch") or {})
@@ -105,10 +107,18 @@ def resolve_encoder_arch(model_cfg: dict, data_cfg: dict | None = None):
         if data_cfg is None:
             raise ValueError("encoder_type 'none' needs config['data'] (sample_rate, frame_duration, n_mels)")
         sr = int(data_cfg["sample_rate"])
-        if sr != 16000:
-            raise ValueError("encoder_type 'none': the mel front-end is built for 16 kHz input (config.data.sample_rate)")
+        if not any_rate and sr != 16000:
+            raise ValueError("encoder_type 'none': the mel front-end is built for 16 kHz input (config.data.sample_rate); "
+                             "any_rate=True takes other rates")
+        if sr <= 0:
+            raise ValueError(f"encoder_type 'none': config.data.sample_rate must be positive (got {sr})")
         n_mels = int(data_cfg.get("n_mels", 80))
-        arch = MelArch(n_mels, n_mels, int(data_cfg.get("frame_duration", 0.02) * sr), 400, sr)
+        frame_duration = data_cfg.get("frame_duration", 0.02)
+        hop = int(frame_duration * sr)                 # model.py:88, Python's float truncation (0.01 * 22050 -> 220)
+        if any_rate and hop < 1:
+            raise ValueError(f"encoder_type 'none': config.data.frame_duration {frame_duration} s at {sr} Hz gives a hop of "
+                             f"{hop} samples (int(frame_duration * sample_rate) must be at least 1)")
+        arch = MelArch(n_mels, n_mels, hop, 400, sr)
         if override:
             raise ValueError("model.encoder_arch does not apply to encoder_type 'none'")
         return "none", arch

@@ -155,6 +155,7 @@ struct LogmelArgs {
   const int* mel_lo; const int* mel_cnt; const float* mel_w; int mel_maxw;
   float* raw;                       // [B][n_frames][n_mels] log10 mel
   unsigned* clipmax;                // [B] ordered-uint max of raw (zeroed by the caller)
+  int hop;                          // frame hop of the general mel-power kernel (logmel.hip, HOP = 0); the others fix it at compile time
 #ifdef WFL_LOGMEL_STAMPS
   unsigned long long* stamps;       // diagnostic build (tools/micro/logmel_bench.hip): [blocks][8] 100 MHz phase stamps
 #endif

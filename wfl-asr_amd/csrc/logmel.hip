@@ -17,7 +17,16 @@
 // 149-150: torchaudio.transforms.MelSpectrogram(sample_rate, n_fft=400, hop_length=frame_duration * sample_rate, n_mels), i.e.
 // periodic Hann, centred / reflect-padded frames, power 2, HTK mel triangles without normalisation, NO log): frames
 // 1 + L / hop, the plain mel power goes out as fp32 [B][frames][n_mels] (the hidden states themselves) and kernel 2' rounds it
-// into the head's bf16 frame rows.  Hop 160 and 320 are instantiated (frame_duration 0.01 / 0.02 s at 16 kHz).
+// into the head's bf16 frame rows.  Hop 160 and 320 (frame_duration 0.01 / 0.02 s at 16 kHz) keep their Toeplitz instantiations.
+//
+// Every other hop (any sample rate, any frame_duration) runs the general instantiation HOP = 0 with the hop a runtime argument
+// (LogmelArgs::hop).  The Toeplitz segment cannot serve it: its skew arithmetic assumes 2 HOP > 200 and 3 HOP > 400, and the
+// segment (FT - 1) HOP + 400 grows with the hop (hop 882: 111 KB of LDS, more than half of it never read once frames stop
+// overlapping).  Instead each of the workgroup's FT frames is staged as its own LDS row of 400 samples at an odd pitch of 401
+// words, so the 32 frames one fragment read touches still fall in 32 different banks; reflection and per-clip lengths are
+// resolved while staging.  The DFT (same tables, same 100 K-steps in the same order, same twiddle ring) and the mel projection
+// are the specialised kernels' own code, so at hop 160 / 320 the general kernel equals them bit for bit (WFL_MEL_GENERAL=1
+// forces it at every hop: the A/B switch).  LDS: 32 x 401 x 4 B + the 28.8 KB power tile = 80 KB, two workgroups per CU.
 #include "common.h"
 
 #define NFFT 400
@@ -29,9 +38,14 @@
                          // instead of 147 -- no gain, reverted (tools/micro/logmel_bench.hip prints the phases)
 #define RT (FT / 32)     // 32-frame MFMA row tiles per workgroup
 #define PPITCH 225
+#define RPITCH 401        // general kernel: words per staged frame row (odd: frame r of a fragment read sits in bank (17 r + j) mod 32)
 template <int HOP> struct Seg {
   static constexpr int SEG = (FT - 1) * HOP + NFFT;         // hop 160: 5360 samples
   static constexpr int SEG_LDS = SEG + SEG / HOP + 2;       // skewed
+};
+template <> struct Seg<0> {                                 // general kernel: FT rows of 400 samples, one per frame
+  static constexpr int SEG = FT * NFFT;
+  static constexpr int SEG_LDS = FT * RPITCH;
 };
 #ifdef WFL_LOGMEL_STAMPS
 #define LSTAMP(k) do { if (threadIdx.x == 0 && p.stamps) p.stamps[((long)blockIdx.y * gridDim.x + blockIdx.x) * 8 + (k)] = __builtin_amdgcn_s_memrealtime(); } while (0)
@@ -49,9 +63,13 @@ static __device__ __forceinline__ float ord2f(unsigned k) {
   return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
 }
 
+// HOP = 0: the general form (hop = p.hop, frame rows instead of the Toeplitz segment; POWER only)
 template <int HOP, bool POWER>
 __global__ __launch_bounds__(256) void logmel_power_kernel(LogmelArgs p) {
   constexpr int SEG = Seg<HOP>::SEG, SEG_LDS = Seg<HOP>::SEG_LDS;
+  constexpr bool GEN = HOP == 0;
+  static_assert(!GEN || POWER, "the general kernel is the mel-power front-end");
+  const int hop = GEN ? p.hop : HOP;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   float* seg = (float*)smem;
   float* pw = seg + ((SEG_LDS + 3) & ~3);
@@ -61,30 +79,50 @@ __global__ __launch_bounds__(256) void logmel_power_kernel(LogmelArgs p) {
   // POWER with per-clip lengths: the clip is reflected about ITS last sample and has 1 + len / HOP frames (a clip labelled alone);
   // the frames up to the batch-wide count are written as zeros
   const int nsamp = (POWER && p.lens) ? len : p.n_samples;
-  const int nfr = (POWER && p.lens) ? (len > NFFT / 2 ? 1 + len / HOP : 0) : p.n_frames;
+  const int nfr = (POWER && p.lens) ? (len > NFFT / 2 ? 1 + len / hop : 0) : p.n_frames;
   const float* w = p.wav + (long)b * p.ldw;
   LSTAMP(0);
 
   // ---- stage the signal segment: sample index i = 160*f0 - 200 + j, reflect about 0 and n_samples-1
   // All 41 loads of a thread are issued before the first LDS write (unconditional, index clamped, value selected afterwards):
   // a load-then-store loop serialises 41 HBM round trips per workgroup (it was 2/3 of this kernel's time).
-  const int s0 = f0 * HOP - NFFT / 2;
+  const int s0 = f0 * hop - NFFT / 2;
   constexpr int NIT = (SEG + 255) / 256;
   float sv[NIT];
+  if constexpr (GEN) {
+    // general kernel: element j = 400 fr + n of the workgroup's frame rows is sample hop (f0 + fr) - 200 + n (64-bit: any hop)
 #pragma unroll
-  for (int it = 0; it < NIT; ++it) {
-    int i = s0 + tid + 256 * it;
-    if (i < 0) i = -i;
-    if (i >= nsamp) i = 2 * (nsamp - 1) - i;
-    const bool ok = i >= 0 && i < len;
-    const int ic = min(max(i, 0), p.L - 1);
-    const float v = w[ic];
-    sv[it] = ok ? v : 0.f;
-  }
+    for (int it = 0; it < NIT; ++it) {
+      const int j = tid + 256 * it, fr = j / NFFT;
+      long i = (long)s0 + (long)fr * hop + (j - fr * NFFT);
+      if (i < 0) i = -i;
+      if (i >= nsamp) i = 2l * (nsamp - 1) - i;
+      const bool ok = i >= 0 && i < len;
+      const int ic = (int)min(max(i, 0l), (long)p.L - 1);
+      const float v = w[ic];
+      sv[it] = ok ? v : 0.f;
+    }
 #pragma unroll
-  for (int it = 0; it < NIT; ++it) {
-    const int j = tid + 256 * it;
-    if (j < SEG) seg[j + j / HOP] = sv[it];
+    for (int it = 0; it < NIT; ++it) {
+      const int j = tid + 256 * it, fr = j / NFFT;
+      if (j < SEG) seg[fr * RPITCH + (j - fr * NFFT)] = sv[it];
+    }
+  } else {
+#pragma unroll
+    for (int it = 0; it < NIT; ++it) {
+      int i = s0 + tid + 256 * it;
+      if (i < 0) i = -i;
+      if (i >= nsamp) i = 2 * (nsamp - 1) - i;
+      const bool ok = i >= 0 && i < len;
+      const int ic = min(max(i, 0), p.L - 1);
+      const float v = w[ic];
+      sv[it] = ok ? v : 0.f;
+    }
+#pragma unroll
+    for (int it = 0; it < NIT; ++it) {
+      const int j = tid + 256 * it;
+      if (j < SEG) seg[j + j / HOP] = sv[it];
+    }
   }
   __syncthreads();
   LSTAMP(1);
@@ -104,7 +142,8 @@ __global__ __launch_bounds__(256) void logmel_power_kernel(LogmelArgs p) {
     for (int rt = 0; rt < RT; ++rt)
 #pragma unroll
       for (int e = 0; e < 16; ++e) { re[rt][e] = 0.f; im[rt][e] = 0.f; }
-    const float* fa = seg + (HOP + 1) * r;                   // frame r of row tile 0 (skewed: + n + n/HOP); tile rt at + (HOP+1)*32*rt
+    constexpr int FP = GEN ? RPITCH : HOP + 1;               // words between consecutive frames
+    const float* fa = seg + FP * r;                          // frame r of row tile 0 (Toeplitz: skewed, + n + n/HOP); tile rt at + FP*32*rt
     const float* bc = p.Wc + (long)kh * NBIN_PAD + ct * 32 + r;   // row j-1 of the folded tables, j = 1 + 2*step + kh
     const float* bs = p.Ws + (long)kh * NBIN_PAD + ct * 32 + r;
     float wcv[PD], wsv[PD];
@@ -114,10 +153,10 @@ __global__ __launch_bounds__(256) void logmel_power_kernel(LogmelArgs p) {
     auto ldx = [&](int step, float (&xa)[RT], float (&xb)[RT]) __attribute__((always_inline)) {
       const int j = 1 + 2 * step + kh;                       // 1..200
       const int n2 = NFFT - j;                               // 200..399
-      const int a1 = j + (j >= HOP ? 1 : 0);                 // (j <= 200 < 2 HOP)
-      const int a2 = n2 + (n2 >= 2 * HOP ? 2 : (n2 >= HOP ? 1 : 0));
+      const int a1 = GEN ? j : j + (j >= HOP ? 1 : 0);       // (Toeplitz: j <= 200 < 2 HOP)
+      const int a2 = GEN ? n2 : n2 + (n2 >= 2 * HOP ? 2 : (n2 >= HOP ? 1 : 0));
 #pragma unroll
-      for (int rt = 0; rt < RT; ++rt) { xa[rt] = fa[(HOP + 1) * 32 * rt + a1]; xb[rt] = fa[(HOP + 1) * 32 * rt + a2]; }
+      for (int rt = 0; rt < RT; ++rt) { xa[rt] = fa[FP * 32 * rt + a1]; xb[rt] = fa[FP * 32 * rt + a2]; }
     };
     float na[RT], nb[RT];
     ldx(0, na, nb);
@@ -236,12 +275,18 @@ static int launch_power(const LogmelArgs& a, hipStream_t s) {
 
 // encoder_type none: a.raw receives the mel power (= the hidden states, fp32 [B][frames][n_mels]); a.n_samples = a.L > 200; with
 // a.lens every clip is reflected about its own last sample and has its own 1 + len / hop frames (zeros behind them).
+// Hop 160 / 320: the Toeplitz instantiations; any other hop >= 1: the general kernel (WFL_MEL_GENERAL=1: at every hop -- A/B runs).
 int wfl_launch_melpower(const LogmelArgs& a, int hop, bf16_t* out, long ldo, long lead, int P, int split, int shift, hipStream_t s) {
-  if (a.n_samples != a.L || a.L <= NFFT / 2 || a.n_frames != 1 + a.L / hop || a.n_mels <= 0 || a.B <= 0) return -1;
+  if (hop < 1 || a.n_samples != a.L || a.L <= NFFT / 2 || a.n_frames != 1 + a.L / hop || a.n_mels <= 0 || a.B <= 0) return -1;
+  static const bool general_only = [] { const char* e = std::getenv("WFL_MEL_GENERAL"); return e && std::atoi(e) != 0; }();
   int r;
-  if (hop == 160) r = launch_power<160, true>(a, s);
-  else if (hop == 320) r = launch_power<320, true>(a, s);
-  else return -1;
+  if (hop == 160 && !general_only) r = launch_power<160, true>(a, s);
+  else if (hop == 320 && !general_only) r = launch_power<320, true>(a, s);
+  else {
+    LogmelArgs g = a;
+    g.hop = hop;
+    r = launch_power<0, true>(g, s);
+  }
   if (r) return r;
   const long total = (long)a.B * a.n_frames * a.n_mels;
   long blocks = (total + 255) / 256;

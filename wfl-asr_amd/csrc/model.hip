@@ -178,7 +178,15 @@ int32_t wfl_create(const wfl_arch* arch, wfl_model** out) {
   if (none) {
     // model.py:82-91: hidden_size = n_mels; the head runs at that width
     if (a.n_mels <= 0 || a.d_model != a.n_mels) return fail(-1, "encoder_type none: d_model must equal n_mels");
-    if (a.mel_hop != 160 && a.mel_hop != 320) return fail(-1, "encoder_type none: the mel front-end is built for hop 160 and 320 (frame_duration 0.01 / 0.02 s at 16 kHz)");
+    if (a.mel_sample_rate == 0) {          // a caller that names no rate: 16 kHz with the two Toeplitz hops, as before the field existed
+      if (a.mel_hop != 160 && a.mel_hop != 320)
+        return fail(-1, "encoder_type none: without mel_sample_rate the mel front-end is built for hop 160 and 320 (frame_duration 0.01 / "
+                        "0.02 s at 16 kHz); set mel_sample_rate for any other hop");
+    } else {
+      if (a.mel_sample_rate < 8000 || a.mel_sample_rate > 192000)
+        return fail(-1, "encoder_type none: mel_sample_rate must be 8000 .. 192000 Hz (or 0: 16 kHz, hop 160 / 320)");
+      if (a.mel_hop < 1) return fail(-1, "encoder_type none: mel_hop must be >= 1 (int(frame_duration * sample_rate))");
+    }
     if (a.d_model % 2 && a.enable_bilstm) return fail(-1, "encoder_type none: odd n_mels with a BiLSTM");
     if (a.n_conformer > 0) {
       if (a.conformer_heads <= 0 || a.d_model % a.conformer_heads) return fail(-1, "bad conformer_heads");
@@ -1013,7 +1021,10 @@ int32_t wfl_finalize(wfl_model* m) {
   if (m->a.encoder_type == WFL_ENC_WHISPER) finalize_whisper(m, P);
   else if (m->a.encoder_type == WFL_ENC_WAVLM) finalize_wavlm(m, P);
   else {
-    build_frontend_tables(m, P, true, 8000.0);      // MelSpectrogram(f_min = 0, f_max = sample_rate / 2): 16 kHz input, like the rest of the path
+    // MelSpectrogram(f_min = 0, f_max = float(sample_rate // 2)): torchaudio's default f_max and melscale_fbanks' bin grid
+    // linspace(0, sample_rate // 2, 201) both use the integer half
+    const int sr = m->a.mel_sample_rate ? m->a.mel_sample_rate : 16000;
+    build_frontend_tables(m, P, true, (double)(sr / 2));
     pad_head_state(m, P);
   }
   if (P.err.empty()) finalize_head(m, P);

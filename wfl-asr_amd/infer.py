@@ -29,7 +29,7 @@ from .tagger import BIOPhonemeTagger, raise_on_status
 
 frame_duration = pp.FRAME_DURATION
 MAX_SEGMENT_DURATION = pp.MAX_SEGMENT_DURATION
-CHUNK_SAMPLES = int(MAX_SEGMENT_DURATION * 16000)
+CHUNK_SAMPLES = int(MAX_SEGMENT_DURATION * 16000)     # at 16 kHz; a Labeler's own work-item length is `chunk_samples` (its config's rate)
 
 
 def load_config(config_path="config.yaml"):
@@ -60,15 +60,19 @@ class Labeler:
         self.device = pick_device(device)
         torch.cuda.set_device(self.device)       # weights, workspaces, streams and pinned staging all belong to this device
         self.sr = int(self.config["data"]["sample_rate"])
-        if self.sr != 16000:
+        enc = str(self.config["model"]["encoder_type"]).lower()
+        if self.sr != 16000 and enc not in ("none", "null"):
             raise ValueError("both encoders are 16 kHz models (config data.sample_rate must be 16000)")
+        # every file is resampled to the config's rate and cut into 30 s work items (infer.py:19-28, 218-220); the mel front-end of
+        # `encoder_type: none` runs at that rate (its hop is int(frame_duration * sample_rate))
+        self.chunk_samples = int(MAX_SEGMENT_DURATION * self.sr)
         save_dir = self.config["output"]["save_dir"]
         self.labels = pp.load_phoneme_list(os.path.join(save_dir, "phonemes.txt"))
         langs_path = os.path.join(save_dir, "langs.txt")
         self.lang2id = pp.load_langs(langs_path) if os.path.exists(langs_path) else {}
         mm_path = os.path.join(save_dir, "phoneme_merge_map.json")
         self.merge_map = pp.load_phoneme_merge_map(mm_path) if os.path.exists(mm_path) else None
-        self.model = BIOPhonemeTagger(self.config, self.labels, device=self.device)
+        self.model = BIOPhonemeTagger(self.config, self.labels, device=self.device, any_rate=True)   # (`none`: the config's own rate)
         if isinstance(checkpoint_path, dict):
             state_dict = checkpoint_path
         else:
@@ -97,7 +101,7 @@ class Labeler:
             return self._forward_items_by_length(items, lang_id, threshold)
         out = [None] * len(items)
         Bs = self.batch_size
-        L = CHUNK_SAMPLES
+        L = self.chunk_samples
 
         def fill(k, host):
             chunk = items[k * Bs:(k + 1) * Bs]
@@ -126,7 +130,7 @@ class Labeler:
         the end-to-end rate of a folder of 30 s files was 82 k audio-s/s against 123 k for batches already resident."""
         from concurrent.futures import ThreadPoolExecutor
         Bs = self.batch_size
-        L = CHUNK_SAMPLES
+        L = self.chunk_samples
         T = self.model.num_frames(L)
         NS = self.n_inflight
         NI = NS + 1
@@ -340,7 +344,7 @@ class Labeler:
         batches run.  Returns {file index: [(start_s, end_s, phoneme)]} (before forced alignment); every other file is left to the
         general path."""
         from concurrent.futures import ThreadPoolExecutor
-        Bs, L = self.batch_size, CHUNK_SAMPLES
+        Bs, L = self.batch_size, self.chunk_samples
         done = {}
         meta = {}
         self._names_for(lang_name)                       # (build the cache on this thread)
@@ -396,7 +400,7 @@ class Labeler:
 
         from . import _lib
         lib = _lib.load()
-        Bs, L = self.batch_size, CHUNK_SAMPLES
+        Bs, L = self.batch_size, self.chunk_samples
         NI = self.n_inflight + 1
         cap_in = 2 * (int(math.ceil(L * src_sr / self.sr)) + 2)          # interleaved int16 values of a 30 s two-channel file
         key = (src_sr, Bs)
@@ -492,7 +496,7 @@ class Labeler:
                     tag, ch, sr, bits, nbytes = h
                     if tag == 1 and bits == 16 and ch in (1, 2) and sr != self.sr and sr > 0:
                         frames = nbytes // (2 * ch)
-                        if 0 < frames and int(math.ceil(frames * self.sr / sr)) <= CHUNK_SAMPLES:
+                        if 0 < frames and int(math.ceil(frames * self.sr / sr)) <= self.chunk_samples:
                             by_rate.setdefault(sr, []).append(fi)
                 for sr, fis in by_rate.items():
                     got = self._label_resampled([audio_paths[fi] for fi in fis], sr, lang_id, confidence_threshold, lang_name)

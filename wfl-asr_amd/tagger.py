@@ -56,12 +56,14 @@ def raise_on_status(word: int):
 
 
 class BIOPhonemeTagger:
-    def __init__(self, config: dict, label_list, device=None):
+    def __init__(self, config: dict, label_list, device=None, any_rate: bool = False):
         """device: the HIP device the weights will live on (default: the current one when load_state_dict runs).  Every
-        kernel launch of this object happens with that device current."""
+        kernel launch of this object happens with that device current.
+        any_rate: `encoder_type: none` at any data.sample_rate / frame_duration (the library's general mel front-end, wfl_arch::
+        mel_sample_rate set).  Off, the model keeps its original 16 kHz, frame_duration 0.01 / 0.02 s contract.  Labeler turns it on."""
         self.config = config
         self.device = _resolve_device(device) if device is not None else None
-        self.encoder_type, self.arch = resolve_encoder_arch(config["model"], config.get("data"))
+        self.encoder_type, self.arch = resolve_encoder_arch(config["model"], config.get("data"), any_rate=any_rate)
         self.head_cfg = head_config(config["model"])
         self.label_list = list(label_list)
         self.label2id = {label: i for i, label in enumerate(self.label_list)}
@@ -82,6 +84,7 @@ class BIOPhonemeTagger:
         a.d_model, a.enc_layers, a.enc_heads, a.enc_ffn = self.arch.d_model, self.arch.layers, self.arch.heads, self.arch.ffn
         if isinstance(self.arch, MelArch):
             a.n_mels, a.mel_hop = self.arch.n_mels, self.arch.hop
+            a.mel_sample_rate = self.arch.sample_rate if any_rate else 0
         elif isinstance(self.arch, WhisperArch):
             a.n_mels, a.max_positions = self.arch.n_mels, self.arch.max_positions
             a.fp8_weights = int(str(config["model"].get("weight_dtype", "bf16")).lower() in ("fp8", "e4m3", "float8_e4m3fn"))
