@@ -307,6 +307,28 @@ int64_t wfl_boundary_workspace_bytes(int32_t B, int32_t L);
 int32_t wfl_boundary_features(const float* wav, int64_t ldw, const int32_t* lens, int32_t B, int32_t L, const float* mel_w,
                               const float* dct, float* flux, float* mfcc, void* workspace, int64_t workspace_bytes, void* stream);
 
+/* ---- Viterbi forced alignment on the GPU (`postprocess.align: viterbi`; wfl-asr_amd/align.py).  Replaces, for files that come with a
+ * transcript, the greedy in-order string match of /root/reference/infer.py:30-60 over the freely decoded segments (read at 193, 210-215;
+ * applied at 312-319) by a search over the frame logits that spells exactly the transcript, in order, one contiguous run per token.
+ * Clip b has T = n_frames_host[b] logits rows (row frame_off_host[b] + t, ld ldl, C <= 1024 fp32 columns) and N = n_tok_host[b] tokens
+ * (tok_cls rows tok_off_host[b] ..).  Emissions e_t(c) = z[t][c] - logsumexp z[t][.];  token k has 1..4 alternatives (B_j, I_j)
+ * (tok_cls[k][j][0..1], -1 -1 = unused), EB_t(k) = max_j e_t(B_j), EI_t(k) = max_j e_t(I_j); EG_t = max over gap_cls[b][0..7] (-1 = unused,
+ * at least one).  States G_0, B_0, I_0, G_1, ..., B_{N-1}, I_{N-1}, G_N (G_k = 3k, B_k = 3k + 1, I_k = 3k + 2):
+ *     G_k <- {G_k, I_{k-1}, B_{k-1}}    B_k <- {G_k, I_{k-1}, B_{k-1}}    I_k <- {I_k, B_k}        (the first listed wins an exact tie)
+ *     start G_0 | B_0, end G_N | I_{N-1} | B_{N-1} (in that order of preference): every token gets >= 1 frame, gaps may be empty.
+ * Outputs (device): ids[t] the class on the path (a B frame: the B_j of its arg-max alternative, an I frame: the I_j of its arg-max
+ * alternative, a gap frame: o_id), tok[t] = k on B_k / I_k frames and -1 in gaps (same rows as the logits); score[b] the path's sum of
+ * e_t (fp32; the search itself decides on the raw logits); status[b]: 0 ok, 1 infeasible (T < N), 2 N above 4096, 4 a class id out of
+ * range or no gap class.  A clip with status != 0 gets ids = o_id, tok = -1, score 0.  Clips are independent (one workgroup each): a
+ * clip aligned alone equals the same clip inside any batch, bit for bit.  Arguments are checked on the host (negative return): C in
+ * 1 .. 1024, o_id in range, ldl >= C, counts and offsets >= 0, non-null pointers, workspace large enough.
+ * Workspace: 2-bit backpointers, per clip round_up(T * words(N), 64) 4-byte words, words(N) = 64 (N <= 127), 256 (N <= 1023),
+ * 512 (N <= 2047), 1024 (N <= 4096); 0 for a clip with T < N or N > 4096.  wfl_align_workspace_bytes returns that sum in bytes. */
+int64_t wfl_align_workspace_bytes(const int32_t* n_frames_host, const int32_t* n_tok_host, int32_t n_clips);
+int32_t wfl_align(const float* logits, int64_t ldl, int32_t C, int32_t o_id, const int64_t* frame_off_host, const int32_t* n_frames_host,
+                  const int32_t* tok_off_host, const int32_t* n_tok_host, const int32_t* tok_cls, const int32_t* gap_cls, int32_t n_clips,
+                  void* workspace, int64_t workspace_bytes, int32_t* ids, int32_t* tok, float* score, int32_t* status, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -71,6 +71,8 @@ SIGNATURES = {
     "wfl_resample_pcm16": (_I, [_P, _L, _P, _P, _I, _I, _I, _P, _L, _I, _P, _L, _P]),
     "wfl_boundary_workspace_bytes": (_L, [_I, _I]),
     "wfl_boundary_features": (_I, [_P, _L, _P, _I, _I, _P, _P, _P, _P, _P, _L, _P]),
+    "wfl_align_workspace_bytes": (_L, [_P, _P, _I]),
+    "wfl_align": (_I, [_P, _L, _I, _I, _P, _P, _P, _P, _P, _P, _I, _P, _L, _P, _P, _P, _P, _P]),
     "wfl_gemm_profile_enable": (_I, [_P, _I]),
     "wfl_gemm_profile_read": (_I, [_P, _I, _P, _P, _P, _P, _P, _I]),
 }

@@ -1,0 +1,197 @@
+"""Viterbi forced alignment of a transcript over the model's frame logits (`postprocess.align: viterbi`).
+
+The reference aligns a `{audio}.txt` phoneme list by a greedy in-order string match over the freely decoded segments
+(/root/reference/infer.py:30-60, applied at 312-319; restated in postprocess.align_phoneme_list).  That match never looks at the
+posteriors: a missed, inserted or mislabelled phoneme shifts every later token onto the wrong segment.  This module instead searches
+the frame logits for the best path that spells exactly the transcript, in order (csrc/align.hip, include/wfl_asr.h `wfl_align`): every
+token gets one contiguous, time-ordered run of frames, none is dropped.
+
+  viterbi_align         the C ABI on CUDA tensors: a ragged batch of clips in one call
+  token_alternatives    transcript tokens -> (B, I) class pairs of every phoneme whose output name is the token
+  gap_classes           the classes a gap between tokens may take (O, and SP / AP unless the transcript spells them)
+  path_segments         the path's ids / tokens, chunk by chunk, -> exactly one (start, end, token) per transcript token
+"""
+from __future__ import annotations
+
+import ctypes as C
+
+import numpy as np
+import torch
+
+from . import _lib
+from . import native_post as npost
+
+MAX_TOKENS = 4096          # wfl_align's token cap per clip (status 2 above it)
+MAX_ALTERNATIVES = 4       # (B, I) pairs per token
+MAX_GAP = 8                # gap classes per clip
+PAUSES = ("SP", "AP")
+
+STATUS_OK, STATUS_INFEASIBLE, STATUS_OVER_CAP, STATUS_BAD_CLASS = 0, 1, 2, 4
+
+
+def _ptr(t):
+    return C.c_void_p(t.data_ptr()) if t is not None else None
+
+
+def workspace_bytes(n_frames, n_tokens) -> int:
+    lib = _lib.load()
+    T = np.ascontiguousarray(n_frames, np.int32)
+    N = np.ascontiguousarray(n_tokens, np.int32)
+    n = int(lib.wfl_align_workspace_bytes(T.ctypes.data_as(C.c_void_p), N.ctypes.data_as(C.c_void_p), T.size))
+    if n < 0:
+        raise _lib.WflError("wfl_align_workspace_bytes: negative frame or token count")
+    return n
+
+
+def viterbi_align(logits, n_frames, token_classes, gap_classes, o_id, frame_offsets=None, stream=None):
+    """Forced alignment of a ragged batch of clips on the GPU.
+
+    logits         [rows, C] float32 CUDA tensor (rows contiguous in C; clip b = rows frame_offsets[b] .. + n_frames[b]).  With
+                   `lang_id=None` these are the language-averaged logits the forward returns, and the search runs on those.
+    n_frames       frames per clip (host ints)
+    token_classes  per clip, per token: 1..4 (B, I) class pairs (token_alternatives)
+    gap_classes    per clip: 1..8 class ids a gap frame may take (gap_classes)
+    frame_offsets  first row of each clip (default: the clips back to back)
+    -> (ids [rows] int32, tok [rows] int32, score [clips] float32, status [clips] int32), CUDA tensors on `stream`'s device."""
+    lib = _lib.load()
+    if not logits.is_cuda or logits.dim() != 2 or logits.dtype != torch.float32 or logits.stride(1) != 1:
+        raise ValueError("logits must be a [rows, C] float32 CUDA tensor with contiguous rows")
+    nb = len(n_frames)
+    if len(token_classes) != nb or len(gap_classes) != nb:
+        raise ValueError("n_frames, token_classes and gap_classes need one entry per clip")
+    dev = logits.device
+    T = np.asarray(n_frames, np.int32).reshape(nb)
+    N = np.array([len(t) for t in token_classes], np.int32)
+    if frame_offsets is None:
+        frame_offsets = np.concatenate([[0], np.cumsum(T.astype(np.int64))[:-1]]) if nb else np.zeros(0, np.int64)
+    F0 = np.ascontiguousarray(frame_offsets, np.int64).reshape(nb)
+    K0 = np.concatenate([[0], np.cumsum(N.astype(np.int64))[:-1]]).astype(np.int32) if nb else np.zeros(0, np.int32)
+    flat = [a for toks in token_classes for a in toks]
+    if any(not 1 <= len(a) <= MAX_ALTERNATIVES for a in flat):
+        raise ValueError(f"a token needs 1 to {MAX_ALTERNATIVES} (B, I) class pairs")
+    pad = [(-1, -1)] * MAX_ALTERNATIVES
+    tc = np.array([list(a) + pad[len(a):] for a in flat] or [pad], np.int32).reshape(-1, MAX_ALTERNATIVES, 2)
+    gc = np.full((max(nb, 1), MAX_GAP), -1, np.int32)
+    for b, g in enumerate(gap_classes):
+        if not 1 <= len(g) <= MAX_GAP:
+            raise ValueError(f"a clip needs 1 to {MAX_GAP} gap classes, got {len(g)}")
+        gc[b, :len(g)] = g
+    rows = logits.shape[0]
+    if nb and int((F0 + T).max()) > rows:
+        raise ValueError("a clip's frames run past the logits rows")
+    d_tc = torch.from_numpy(tc).to(dev)
+    d_gc = torch.from_numpy(gc).to(dev)
+    ws_n = workspace_bytes(T, N)
+    ws = torch.empty(max(ws_n, 1), dtype=torch.uint8, device=dev)
+    ids = torch.empty(rows, dtype=torch.int32, device=dev)
+    tok = torch.empty(rows, dtype=torch.int32, device=dev)
+    score = torch.empty(max(nb, 1), dtype=torch.float32, device=dev)
+    status = torch.empty(max(nb, 1), dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        st = stream if stream is not None else torch.cuda.current_stream(dev)
+        hp = lambda a: a.ctypes.data_as(C.c_void_p)      # noqa: E731
+        rc = lib.wfl_align(_ptr(logits), logits.stride(0), logits.shape[1], int(o_id), hp(F0), hp(T), hp(K0), hp(N), _ptr(d_tc), _ptr(d_gc),
+                           nb, _ptr(ws), ws_n, _ptr(ids), _ptr(tok), _ptr(score), _ptr(status), C.c_void_p(st.cuda_stream))
+        _lib.check(rc, "wfl_align")
+        for t in (d_tc, d_gc, ws):
+            t.record_stream(st)
+    return ids, tok, score[:nb], status[:nb]
+
+
+# ---------------------------------------------------------------------------------------------------------------- host helpers
+def class_pairs(label_list):
+    """phoneme name (as in the label set) -> (B class, I class), for the phonemes that have both tags."""
+    b, i = {}, {}
+    for c, tag in enumerate(label_list):
+        if tag.startswith("B-"):
+            b[tag[2:]] = c
+        elif tag.startswith("I-"):
+            i[tag[2:]] = c
+    return {ph: (b[ph], i[ph]) for ph in b if ph in i}
+
+
+def token_alternatives(transcript, table: npost.LabelTable, remap, names, label_list):
+    """Per transcript token, the (B, I) class pairs of every phoneme whose OUTPUT name (the merge-map back-mapping `remap` / `names`
+    that Labeler._names_for builds) equals the token.  -> (alternatives, None), or (None, reason) when a token matches no phoneme
+    or more than MAX_ALTERNATIVES of them."""
+    pairs = class_pairs(label_list)
+    by_name = {}
+    for p, ph in enumerate(table.names):
+        if ph in pairs:
+            by_name.setdefault(names[int(remap[p])], []).append(pairs[ph])
+    out = []
+    for tokn in transcript:
+        alts = by_name.get(tokn)
+        if not alts:
+            return None, f"token {tokn!r} matches no phoneme of the label set"
+        if len(alts) > MAX_ALTERNATIVES:
+            return None, f"token {tokn!r} matches {len(alts)} phonemes (at most {MAX_ALTERNATIVES})"
+        out.append(alts)
+    return out, None
+
+
+def gap_classes(label_list, transcript):
+    """O, plus B- / I- of SP and of AP when the label set has them and the transcript does not spell them (silence and breaths go
+    into gaps instead of stretching the neighbouring tokens)."""
+    g = [label_list.index("O")]
+    for ph in PAUSES:
+        if ph in transcript:
+            continue
+        for tag in ("B-" + ph, "I-" + ph):
+            if tag in label_list:
+                g.append(label_list.index(tag))
+    return g
+
+
+def path_segments(ids, tok, chunk_frames, chunk_offsets, chunk_clock, table: npost.LabelTable, alternatives, transcript,
+                  frame_duration):
+    """A path over a file's chunks (ids / tok concatenated, chunk_frames[c] valid frames each) -> [(start_s, end_s, token)], exactly
+    one per transcript token, in transcript order.
+
+    Each chunk goes through the native BIO decoder (no median filter) with that chunk's offsets and is shifted by its clock offset,
+    as the free decode of Labeler.label_files.  Within a token the ids are first mapped to the token's first alternative (all of
+    them share the token's output name), so the decoder sees one phoneme per run; a run that crosses a chunk seam (the next chunk
+    begins with I-x of the same token) is joined into one segment.  Equal neighbouring tokens stay separate segments.  A segment's
+    end is capped at the next segment's start, so the segments never overlap, and is never before its own start."""
+    ids = np.asarray(ids, np.int32)
+    tok = np.asarray(tok, np.int32)
+    b0 = np.array([a[0][0] for a in alternatives] or [0], np.int32)
+    i0 = np.array([a[0][1] for a in alternatives] or [0], np.int32)
+    segs = []                                            # [start, end, token index]
+    pos = 0
+    for Tc, offs, t0 in zip(chunk_frames, chunk_offsets, chunk_clock):
+        idc = ids[pos:pos + Tc]
+        tkc = tok[pos:pos + Tc]
+        pos += Tc
+        on = tkc >= 0
+        is_b = table.kind[idc] == 1
+        canon = idc.copy()
+        canon[on] = np.where(is_b[on], b0[tkc[on]], i0[tkc[on]])
+        s, e, _ = npost.decode_bio_ids(canon, table, frame_duration, offs, median=0)
+        prev = np.concatenate([[-1], tkc[:-1]])
+        starts = np.nonzero(on & (is_b | (prev != tkc)))[0]
+        if len(starts) != len(s):
+            raise RuntimeError(f"path decode: {len(s)} segments for {len(starts)} token runs")
+        for j, f in enumerate(starts):
+            k = int(tkc[f])
+            if f == 0 and segs and segs[-1][2] == k:     # the token's run continues from the previous chunk
+                segs[-1][1] = float(e[j]) + t0
+            else:
+                segs.append([float(s[j]) + t0, float(e[j]) + t0, k])
+    if [g[2] for g in segs] != list(range(len(transcript))):
+        raise RuntimeError("the path does not spell the transcript")
+    for j, g in enumerate(segs):
+        if j + 1 < len(segs):                            # the decoder closes a run at the NEXT run's first frame (its end offset):
+            g[1] = min(g[1], segs[j + 1][0])             # keep the segments from overlapping
+        g[1] = max(g[1], g[0])                           # a one-frame run at a chunk's end closes on its own frame's end offset
+    return [(a, b, transcript[k]) for a, b, k in segs]
+
+
+def with_end_pauses(free_segments, aligned, transcript):
+    """The reference's rule for the ends (/root/reference/infer.py:312-319): without SP / AP in the transcript, the freely decoded
+    SP / AP segments that end at or before the first aligned start or begin at or after the last aligned end are kept."""
+    if "SP" not in transcript and "AP" not in transcript and aligned:
+        before = [s for s in free_segments if s[2] in PAUSES and s[1] <= aligned[0][0]]
+        after = [s for s in free_segments if s[2] in PAUSES and s[0] >= aligned[-1][1]]
+        return before + aligned + after
+    return aligned

@@ -282,6 +282,7 @@ struct WflOncePerDevice {
   }
 };
 
+int wfl_fail(int code, const char* msg);         // model.hip: set the text wfl_last_error() returns, return `code`
 // host-side launchers (one per .hip translation unit)
 int wfl_launch_gemm(const GemmArgs& a, hipStream_t s);
 // which kernel the last wfl_launch_gemm used (profiling labels): 1 gemm_stream<.,6>, 2 gemm256<.,6>, 3 gemm256<.,8>, 4 gemm_bf16 (128 tile), 5 gemm_stream<.,8>, 6 gemm_stream conv mode

@@ -53,6 +53,7 @@ static int fail(int code, const std::string& msg) {
   g_err = msg;
   return code;
 }
+int wfl_fail(int code, const char* msg) { return fail(code, msg); }   // (common.h: other translation units' ABI errors)
 #define HIPCHK(x)                                                                            \
   do {                                                                                       \
     hipError_t e_ = (x);                                                                     \

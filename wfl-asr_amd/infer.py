@@ -29,6 +29,7 @@ from .tagger import BIOPhonemeTagger, raise_on_status
 
 frame_duration = pp.FRAME_DURATION
 MAX_SEGMENT_DURATION = pp.MAX_SEGMENT_DURATION
+ALIGN_MODES = ("greedy", "viterbi")
 CHUNK_SAMPLES = int(MAX_SEGMENT_DURATION * 16000)     # at 16 kHz; a Labeler's own work-item length is `chunk_samples` (its config's rate)
 
 
@@ -470,11 +471,40 @@ class Labeler:
             post.shutdown(wait=True)
         return done
 
-    def label_files(self, audio_paths, lang_id=None, confidence_threshold=0.0, verbose=True):
-        """-> list (per file) of [(start_s, end_s, phoneme)] after merge + forced alignment."""
+    def align_mode(self, align=None) -> str:
+        """"greedy" (the reference's string match, the default) or "viterbi"; None: config postprocess.align, else greedy."""
+        mode = self.config.get("postprocess", {}).get("align", "greedy") if align is None else align
+        if mode not in ALIGN_MODES:
+            raise ValueError(f"align must be one of {ALIGN_MODES}, got {mode!r}")
+        return mode
+
+    def label_files(self, audio_paths, lang_id=None, confidence_threshold=0.0, verbose=True, align=None):
+        """-> list (per file) of [(start_s, end_s, phoneme)] after merge + forced alignment.
+
+        align: "greedy" -- a `{audio}.txt` transcript is matched onto the freely decoded segments (infer.py:30-60, 312-319);
+        "viterbi" -- files with a transcript are aligned by a search over their frame logits on the GPU (align.py: one segment
+        per token, in order, none dropped); files without one take the greedy path unchanged.  None: config postprocess.align."""
         if lang_id is not None and self.lang2id and lang_id > max(self.lang2id.values()):
             raise ValueError(f"Error: Language ID ({lang_id}) is higher than the latest ID ({max(self.lang2id.values())}) "
                              f"of this model.\n Languages and Codes available: {self.lang2id}")
+        if self.align_mode(align) == "viterbi":
+            forced = {fi: _read_forced(p, verbose) for fi, p in enumerate(audio_paths)}
+            with_t = [fi for fi in range(len(audio_paths)) if forced[fi] is not None]
+            if with_t:
+                rest = [fi for fi in range(len(audio_paths)) if forced[fi] is None]
+                final = [None] * len(audio_paths)
+                if rest:
+                    for fi, segs in zip(rest, self._label_files_greedy([audio_paths[fi] for fi in rest], lang_id, confidence_threshold,
+                                                                        verbose)):
+                        final[fi] = segs
+                got = self._label_viterbi([audio_paths[fi] for fi in with_t], [forced[fi] for fi in with_t], lang_id,
+                                          confidence_threshold, verbose)
+                for fi, segs in zip(with_t, got):
+                    final[fi] = segs
+                return final
+        return self._label_files_greedy(audio_paths, lang_id, confidence_threshold, verbose)
+
+    def _label_files_greedy(self, audio_paths, lang_id, confidence_threshold, verbose):
         lang_name = self._lang_name(lang_id)
         decided_fast = {}                                 # file index -> segments of its one <= 30 s item, natively loaded
         if self.model.encoder_type == "whisper" and len(audio_paths) > 0:
@@ -503,13 +533,7 @@ class Labeler:
                     decided_fast.update({fis[j]: seg for j, seg in got.items()})
         items, owner = [], []
         chunk_lens = []
-
-        def load_one(path):
-            chunks = A.load_items(path, self.sr)            # native: decode, resample, normalise, 30 s chunks (csrc/hostpost.hip)
-            if chunks is None:                              # an encoding the native decoder does not take: the Python restatement
-                audio = A.load_clip(path, self.sr)
-                chunks = A.chunk_clip(audio, self.sr)
-            return chunks
+        load_one = self._load_chunks
 
         slow = [fi for fi in range(len(audio_paths)) if fi not in decided_fast]
         # The native loader releases the GIL: files decode / resample on worker threads, all submitted at once; the items are
@@ -575,6 +599,140 @@ class Labeler:
         return final
 
 
+    def _load_chunks(self, path):
+        chunks = A.load_items(path, self.sr)            # native: decode, resample, normalise, 30 s chunks (csrc/hostpost.hip)
+        if chunks is None:                              # an encoding the native decoder does not take: the Python restatement
+            audio = A.load_clip(path, self.sr)
+            chunks = A.chunk_clip(audio, self.sr)
+        return chunks
+
+    def _valid_frames(self, n, T):
+        """Frames of a chunk of n samples in a forward of T frames: Whisper's window always has T frames, of which
+        ceil(n T / chunk_samples) hold audio (min(1500, ceil(n / 320)) at 16 kHz); WavLM and the mel front-end: num_frames(n)."""
+        if self.model.encoder_type == "whisper":
+            return min(T, -(-n * T // self.chunk_samples))
+        return self.model.num_frames(n)
+
+    def _label_viterbi(self, audio_paths, transcripts, lang_id, threshold, verbose):
+        """Files with a transcript, align="viterbi".  Their chunks are forwarded with logits (kept on the device); the free decode of
+        the same forward gives the greedy result, which the pause rule at the ends needs and which a file falls back to (with a
+        message) when its transcript cannot be aligned.  Each file's chunks' valid logits rows are concatenated on the device, so
+        one search covers the whole file; the files of a wave go to wfl_align as one ragged batch and only ids / tok / score / status
+        come back to the host."""
+        from . import align as AL
+        lang_name = self._lang_name(lang_id)
+        remap, names = self._names_for(lang_name)
+        mode = self.config["postprocess"]["merge_segments"]
+        Bs = self.batch_size
+        whisper = self.model.encoder_type == "whisper"
+        results = []
+        wave = getattr(self, "_wave_items", None) or max(8 * Bs, 64)
+        from concurrent.futures import ThreadPoolExecutor
+        pool = ThreadPoolExecutor(max_workers=max(1, min(16, os.cpu_count() or 1, len(audio_paths))))
+        loads = [pool.submit(self._load_chunks, p) for p in audio_paths]      # (the native loader releases the GIL)
+        pool.shutdown(wait=False)
+        files = list(range(len(audio_paths)))
+        while files:
+            # a wave of files: their chunks are forwarded and aligned together
+            sel, chunks = [], []
+            while files and (not sel or len(chunks) < wave):
+                fi = files.pop(0)
+                cs = loads[fi].result()
+                loads[fi] = None
+                if verbose and len(cs) > 1:
+                    print(f"Audio is too long ({sum(len(c) for c in cs)/self.sr:.1f}s), splitting...")
+                sel.append(fi)
+                chunks.extend((fi, c) for c in cs)
+            free = {}                                         # (file, chunk) -> (ids, offsets) of the free decode
+            rows = {}                                         # (file, chunk) -> device logits rows of the chunk's valid frames
+            by_file = {}
+            for fi, c in chunks:
+                by_file.setdefault(fi, []).append(c)
+            order = [(fi, ci) for fi in sel for ci in range(len(by_file[fi]))]
+            if not whisper:
+                order.sort(key=lambda k: -len(by_file[k[0]][k[1]]))
+            for s0 in range(0, len(order), Bs):
+                part = order[s0:s0 + Bs]
+                xs = [by_file[fi][ci] for fi, ci in part]
+                L = self.chunk_samples if whisper else max(len(x) for x in xs)
+                host = np.zeros((len(xs) if not whisper else Bs, L), np.float32)
+                lens = np.zeros(host.shape[0], np.int32)
+                for r, x in enumerate(xs):
+                    n = min(len(x), L)
+                    host[r, :n] = x[:n]
+                    lens[r] = n
+                same = (not whisper) and all(len(x) == L for x in xs)
+                res = self.model.label(torch.from_numpy(host).to(self.device), None if lang_id is None else [lang_id] * host.shape[0],
+                                       threshold=threshold, lens=None if same else lens, average_languages=lang_id is None,
+                                       want_logits=True)
+                raise_on_status(int(res.status.item()))
+                T = res.ids.shape[1]
+                ids_h, offs_h = res.ids.cpu().numpy(), res.offsets.cpu().numpy()
+                for r, (fi, ci) in enumerate(part):
+                    tv = self._valid_frames(len(xs[r]), T)
+                    keep = T if whisper else tv                # what the greedy loop decodes (_forward_items)
+                    free[(fi, ci)] = (ids_h[r, :keep].copy(), offs_h[r, :keep].copy())
+                    rows[(fi, ci)] = (res.logits[r, :tv], offs_h[r, :tv].copy())
+            # the greedy result of every file (free decode, merge, string match), as _label_files_greedy computes it
+            greedy, free_segs, plans = {}, {}, {}
+            for j, fi in enumerate(sel):
+                parts, clock = [], 0.0
+                for ci, x in enumerate(by_file[fi]):
+                    ids_c, offs_c = free[(fi, ci)]
+                    s, e, ph = self._segments_of_item(ids_c, offs_c, lang_name)
+                    parts.append((s + clock, e + clock, ph))
+                    clock += len(x) / self.sr
+                s = np.concatenate([p[0] for p in parts])
+                e = np.concatenate([p[1] for p in parts])
+                ph = np.concatenate([p[2] for p in parts]).astype(np.int32)
+                if mode != "none" and s.size:
+                    s, e, ph = npost.merge_segments(s, e, ph, mode)
+                segs = npost.to_tuples(s, e, ph, names)
+                free_segs[fi] = segs
+                tr = transcripts[fi]
+                greedy[fi] = AL.with_end_pauses(segs, pp.align_phoneme_list(segs, tr), tr)
+                if not tr:
+                    continue
+                alts, why = AL.token_alternatives(tr, self._table, remap, names, self.labels)
+                if alts is None:
+                    print(f"{audio_paths[fi]}: viterbi alignment not possible ({why}); using the greedy alignment")
+                    continue
+                plans[fi] = alts
+            # one ragged search over the files that can be aligned
+            aligned = {}
+            run = [fi for fi in sel if fi in plans]
+            if run:
+                frames = [sum(rows[(fi, ci)][0].shape[0] for ci in range(len(by_file[fi]))) for fi in run]
+                lg = torch.cat([rows[(fi, ci)][0] for fi in run for ci in range(len(by_file[fi]))])   # device-to-device
+                gaps = [AL.gap_classes(self.labels, transcripts[fi]) for fi in run]
+                d_ids, d_tok, _, d_st = AL.viterbi_align(lg, frames, [plans[fi] for fi in run], gaps, self.labels.index("O"))
+                ids_all, tok_all, st_all = d_ids.cpu().numpy(), d_tok.cpu().numpy(), d_st.cpu().numpy()
+                pos = 0
+                for b, fi in enumerate(run):
+                    n = frames[b]
+                    tr = transcripts[fi]
+                    if st_all[b] != AL.STATUS_OK:
+                        why = {AL.STATUS_INFEASIBLE: f"{len(tr)} tokens for {n} frames",
+                               AL.STATUS_OVER_CAP: f"{len(tr)} tokens, over the cap of {AL.MAX_TOKENS}"}.get(int(st_all[b]),
+                                                                                                           f"status {int(st_all[b])}")
+                        print(f"{audio_paths[fi]}: viterbi alignment not possible ({why}); using the greedy alignment")
+                    else:
+                        cf, co, cc, clock = [], [], [], 0.0
+                        for ci, x in enumerate(by_file[fi]):
+                            r, offs = rows[(fi, ci)]
+                            cf.append(r.shape[0])
+                            co.append(offs)
+                            cc.append(clock)
+                            clock += len(x) / self.sr
+                        segs = AL.path_segments(ids_all[pos:pos + n], tok_all[pos:pos + n], cf, co, cc, self._table, plans[fi], tr,
+                                                frame_duration)
+                        aligned[fi] = AL.with_end_pauses(free_segs[fi], segs, tr)
+                    pos += n
+            for fi in sel:
+                results.append(aligned.get(fi, greedy[fi]))
+        return results
+
+
 def _read_forced(audio_path, verbose):
     """`{audio}.txt` forced phoneme list (infer.py:193, 210-215)."""
     txt = audio_path.replace(".wav", ".txt")
@@ -590,6 +748,11 @@ def _read_forced(audio_path, verbose):
 
 
 _LABELERS = {}
+
+
+def _check_align(align):
+    if align is not None and align not in ALIGN_MODES:
+        raise ValueError(f"align must be one of {ALIGN_MODES}, got {align!r}")
 
 
 def _labeler(config_path, checkpoint_path, device):
@@ -610,9 +773,12 @@ def _write_lab(path, segments):
 
 
 def infer_audio(audio_path, config_path="config.yaml", checkpoint_path="best_model.pt", output_lab_path=None, device="cuda",
-                lang_id=None, sample=False, top_k=0, top_p=0.0, temperature=1.0, confidence_threshold=0.0):
+                lang_id=None, sample=False, top_k=0, top_p=0.0, temperature=1.0, confidence_threshold=0.0, align=None):
+    """align: "greedy" | "viterbi" | None (config postprocess.align, else greedy): how a `{audio}.txt` transcript is aligned
+    (Labeler.label_files)."""
+    _check_align(align)
     lab = _labeler(config_path, checkpoint_path, device)
-    segments = lab.label_files([audio_path], lang_id=lang_id, confidence_threshold=confidence_threshold)[0]
+    segments = lab.label_files([audio_path], lang_id=lang_id, confidence_threshold=confidence_threshold, align=align)[0]
     if output_lab_path:
         if os.path.abspath(output_lab_path) == os.path.abspath(audio_path):
             # the reference would truncate the input WAV here (infer.py:410-411 + utils.py:77)
@@ -623,7 +789,8 @@ def infer_audio(audio_path, config_path="config.yaml", checkpoint_path="best_mod
 
 def infer_folder(folder_path: str, config_path: str = "config.yaml", checkpoint_path: str = "best_model.pt",
                  output_dir: str = "outputs", device: str = "cuda", lang_id: int = None, sample=False, top_k=0, top_p=0.0,
-                 temperature=1.0, confidence_threshold=0.0):
+                 temperature=1.0, confidence_threshold=0.0, align=None):
+    _check_align(align)
     wav_files = sorted(f for f in os.listdir(folder_path) if f.lower().endswith(".wav"))
     os.makedirs(output_dir, exist_ok=True)
     # one process per GPU: every rank labels its own share of the files and writes its own .lab files (no collective)
@@ -634,7 +801,7 @@ def infer_folder(folder_path: str, config_path: str = "config.yaml", checkpoint_
         wav_files = [wav_files[i] for i in shard_items(sizes, world)[rank]]
     lab = _labeler(config_path, checkpoint_path, device)
     paths = [os.path.join(folder_path, f) for f in wav_files]
-    all_segments = lab.label_files(paths, lang_id=lang_id, confidence_threshold=confidence_threshold) if paths else []
+    all_segments = lab.label_files(paths, lang_id=lang_id, confidence_threshold=confidence_threshold, align=align) if paths else []
     for wav_file, segments in zip(wav_files, all_segments):
         print(f"\nInferencing: {wav_file}")
         _write_lab(os.path.join(output_dir, os.path.splitext(wav_file)[0] + ".lab"), segments)
@@ -661,7 +828,10 @@ def main(argv=None):
     @click.option("--device", "-d", type=str, default="auto", help='Device to use: "cuda", "cuda:0". Auto-detects if not specified.')
     @click.option("--confidence-threshold", "-ct", type=float, default=None,
                   help="Suppress predictions with low confidence. Set 0 to disable.")
-    def cli(path, checkpoint, config, output, lang_id, sample, top_k, top_p, temperature, device, confidence_threshold):
+    @click.option("--align", "-a", type=click.Choice(ALIGN_MODES), default=None,
+                  help="How a {audio}.txt transcript is aligned: greedy (string match) or viterbi (search over the logits, GPU). "
+                       "Default: config postprocess.align, else greedy.")
+    def cli(path, checkpoint, config, output, lang_id, sample, top_k, top_p, temperature, device, confidence_threshold, align):
         if sample:
             if top_k <= 0 and top_p <= 0.0:
                 print("Sampling is enabled but neither --top-k nor --top-p is set.")
@@ -688,6 +858,8 @@ def main(argv=None):
         cfg = load_config(Path(config))
         if confidence_threshold is None:
             confidence_threshold = cfg["postprocess"].get("confidence_threshold", 0.0)
+        if align is None:
+            align = cfg["postprocess"].get("align", "greedy")
         output_path = inf_path if output == "." else output
         if not inf_path.exists():
             print(f"Unable to locate folder {str(inf_path)}")
@@ -695,7 +867,7 @@ def main(argv=None):
         if lang_id is not None and lang_id <= -1:
             lang_id = None
         kw = dict(config_path=str(config), checkpoint_path=str(checkpoint), device=device, lang_id=lang_id, sample=sample,
-                  top_k=top_k, top_p=top_p, temperature=temperature, confidence_threshold=confidence_threshold)
+                  top_k=top_k, top_p=top_p, temperature=temperature, confidence_threshold=confidence_threshold, align=align)
         if inf_path.is_dir():
             infer_folder(folder_path=str(inf_path), output_dir=str(output_path), **kw)
         else:
