@@ -329,6 +329,36 @@ int32_t wfl_align(const float* logits, int64_t ldl, int32_t C, int32_t o_id, con
                   const int32_t* tok_off_host, const int32_t* n_tok_host, const int32_t* tok_cls, const int32_t* gap_cls, int32_t n_clips,
                   void* workspace, int64_t workspace_bytes, int32_t* ids, int32_t* tok, float* score, int32_t* status, void* stream);
 
+/* ---- Posteriors of a Viterbi alignment by forward-backward on the GPU (`postprocess.align_scores`; wfl-asr_amd/align.py).  No
+ * counterpart in the reference, which reports no confidence for its string match.  The lattice, emissions EB / EI / EG, start and end
+ * states, caps (C <= 1024, N <= 4096) and argument conventions are wfl_align's.  The weight of a path is exp(sum_t e_t(state_t));
+ * alpha_t(s) / beta_t(s) are the log-sums of the weights of the path prefixes ending in / suffixes leaving s at frame t over wfl_align's
+ * transitions:
+ *     logZ = log sum over all accepted paths,        gamma_t(s) = exp(alpha_t(s) + beta_t(s) - logZ).
+ * tok (device) is wfl_align's output for the same clips (row frame_off_host[b] + t).  Outputs (device):
+ *   logz[b]        logZ of the clip (fp32);
+ *   tok_post[k]    (rows tok_off_host[b] + k) the mean over the frames t with tok[t] == k of gamma_t(B_k) + gamma_t(I_k): the posterior
+ *                  occupancy of the run Viterbi chose, in [0, 1] (clamped to 1 from above);
+ *   start_mean[k], start_sd[k]   mean and standard deviation, in frames, of the token's start frame: a path visits B_k in exactly one
+ *                  frame, so gamma_.(B_k) is that frame's posterior distribution (sum_t gamma_t(B_k) = 1; the moments are divided by the
+ *                  computed sum, which is 1 up to rounding).  start_mean is relative to the first frame with tok[t] == k (Viterbi's
+ *                  start); the moments are accumulated about that frame, in double;
+ *   status[b]      wfl_align's codes (0 ok, 1 infeasible, 2 N above 4096, 4 a class id out of range or no gap class), and 8: tok does not
+ *                  contain every token 0 .. N - 1 or holds a value outside -1 .. N - 1 (not a path of this lattice).  A clip with
+ *                  status != 0 gets logz = 0 and tok_post = start_mean = start_sd = 0.
+ * One workgroup per clip: a clip scored alone equals the same clip inside any batch, bit for bit.  fp32 log-domain states, renormalised
+ * every 16 frames (offsets in double).  Arguments are checked on the host as wfl_align checks its own (negative return).
+ * Workspace: the alpha lattice is not stored.  Per clip, in 4-byte words, round_up_64 of
+ *     round_up_64(T) + round_up_64(2 nblk) + (nblk + 128) * 3 * slots(N),   nblk = ceil(T / 128),
+ * (the frames' log-sum-exp, alpha checkpoints every 128 frames with their offsets, one recomputed 128-frame block of alpha);
+ * slots(N) = 128 (N <= 127), 512 (N <= 511), 1024 (N <= 1023), 2048 (N <= 2047), 4608 (above); 0 for T = 0.  13.7 MB at T = 15000,
+ * N = 4096.  wfl_align_posterior_workspace_bytes returns the sum in bytes. */
+int64_t wfl_align_posterior_workspace_bytes(const int32_t* n_frames_host, const int32_t* n_tok_host, int32_t n_clips);
+int32_t wfl_align_posterior(const float* logits, int64_t ldl, int32_t C, int32_t o_id, const int64_t* frame_off_host,
+                            const int32_t* n_frames_host, const int32_t* tok_off_host, const int32_t* n_tok_host, const int32_t* tok_cls,
+                            const int32_t* gap_cls, int32_t n_clips, const int32_t* tok, void* workspace, int64_t workspace_bytes,
+                            float* logz, float* tok_post, float* start_mean, float* start_sd, int32_t* status, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -3,6 +3,10 @@
 
   --op    one wfl_align launch for 16 and 64 clips x 1500 frames x N = 300 tokens, C = 141 (seeded random logits, resident): the
           median of --reps launches timed with device events (run it under `rocprofv3 --kernel-trace --stats` for the kernel alone)
+  --posterior   the same shape through viterbi_align and then alignment_posteriors (wfl_align_posterior), both timed in the same run;
+          the ratio of the two calls.  With --check also the kernel's maximum deviations from the float64 reference on the shapes
+          of tests/test_gpu_align_posterior.py, beside the float32 restatement's.  With --e2e the end-to-end rate of viterbi with
+          and without align_scores.  The result goes to --out (profiles/align_posterior_bench.json)
   --e2e   Labeler.label_files over a folder of 30 s 16 kHz files (BASELINE config 2 model, synthetic weights), the same files with
           a transcript each (align="viterbi") and without one, alternated, --rounds times each; prints audio-s/s of both"""
 import argparse
@@ -51,7 +55,54 @@ def op_bench(reps):
     print(json.dumps({"align_launch": out, "T": T, "N": N, "C": C, "reps": reps}))
 
 
-def e2e_bench(files, rounds):
+def _timed(fn, reps):
+    for _ in range(3):
+        fn()
+    torch.cuda.synchronize()
+    ms = []
+    for _ in range(reps):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        fn()
+        b.record()
+        b.synchronize()
+        ms.append(a.elapsed_time(b))
+    return {"ms_median": float(np.median(ms)), "ms_min": float(np.min(ms))}
+
+
+def posterior_bench(reps):
+    rng = np.random.default_rng(0)
+    C, T, N = 141, 1500, 300
+    out = {"T": T, "N": N, "C": C, "reps": reps}
+    for nb in (16, 64):
+        z = torch.from_numpy(rng.standard_normal((nb * T, C)).astype(np.float32) * 3).cuda()
+        toks = [[[(int(2 * p - 1), int(2 * p))] for p in rng.integers(1, 70, N)] for _ in range(nb)]
+        gaps = [[0, 139, 140]] * nb
+        args = (z, [T] * nb, toks, gaps, 0)
+        tok = AL.viterbi_align(*args)[1]
+        vit = _timed(lambda: AL.viterbi_align(*args), reps)
+        post = _timed(lambda: AL.alignment_posteriors(*args, tok), reps)
+        st = AL.alignment_posteriors(*args, tok)[4]
+        assert int(st.max()) == 0
+        out[f"clips{nb}"] = {"viterbi_align": vit, "alignment_posteriors": post,
+                             "ratio_posterior_to_viterbi": post["ms_median"] / vit["ms_median"],
+                             "workspace_bytes": AL.posterior_workspace_bytes([T] * nb, [N] * nb)}
+    return out
+
+
+def posterior_check():
+    """The kernel's and the float32 restatement's maximum deviations from float64 on the operator test's own clips (its builders)."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import test_gpu_align_posterior as tp
+    out = {}
+    for name, clips, scattered in [("ragged", tp.ragged_clips(), True), ("multi_wave_2500_1000", tp.multi_wave_clips(2500, 1000), False),
+                                   ("multi_wave_4400_4096", tp.multi_wave_clips(4400, 4096), False), ("cap_15000_4096", tp.cap_clips(), False),
+                                   ("T_equals_N", tp.t_equals_n_clips(), False), ("batch_of_16", tp.batch16_clips(), False)]:
+        out[name] = tp._check_case(name, clips, tp._run(clips, scattered=scattered))
+    return out
+
+
+def e2e_bench(files, rounds, scores=False):
     d = tempfile.mkdtemp(prefix="wfl_align_")
     try:
         cfg = synth.baseline_config(1)
@@ -77,19 +128,25 @@ def e2e_bench(files, rounds):
                 f.write(" ".join(rng.choice(phs, size=300)))
         lists = {k: sorted(os.path.join(f, n) for n in os.listdir(f) if n.endswith(".wav")) for k, f in (("greedy", plain),
                                                                                                       ("viterbi", withtr))}
-        for k in lists:                                        # warm-up (allocations, kernels)
-            lab.label_files(lists[k][:4], confidence_threshold=0.5, verbose=False, align=k)
-        rates = {"greedy": [], "viterbi": []}
+        legs = {"greedy": ("greedy", "greedy", None), "viterbi": ("viterbi", "viterbi", None)}
+        if scores:
+            legs["viterbi_scores"] = ("viterbi", "viterbi", True)
+        for folder, mode, sc in legs.values():                 # warm-up (allocations, kernels)
+            lab.label_files(lists[folder][:4], confidence_threshold=0.5, verbose=False, align=mode, align_scores=sc)
+        rates = {k: [] for k in legs}
         for _ in range(rounds):
-            for k in ("greedy", "viterbi"):
+            for k, (folder, mode, sc) in legs.items():
                 torch.cuda.synchronize()
                 t0 = time.perf_counter()
-                lab.label_files(lists[k], confidence_threshold=0.5, verbose=False, align=k)
+                lab.label_files(lists[folder], confidence_threshold=0.5, verbose=False, align=mode, align_scores=sc)
                 torch.cuda.synchronize()
                 rates[k].append(files * 30.0 / (time.perf_counter() - t0))
-        print(json.dumps({"e2e_audio_s_per_s": {k: [round(r, 1) for r in v] for k, v in rates.items()},
-                          "median": {k: round(float(np.median(v)), 1) for k, v in rates.items()}, "files": files,
-                          "note": "greedy = the folder without transcripts, viterbi = the same files with a 300-token transcript each"}))
+        res = {"e2e_audio_s_per_s": {k: [round(r, 1) for r in v] for k, v in rates.items()},
+               "median": {k: round(float(np.median(v)), 1) for k, v in rates.items()}, "files": files,
+               "note": "greedy = the folder without transcripts, viterbi = the same files with a 300-token transcript each"
+                       + (", viterbi_scores = viterbi with align_scores" if scores else "")}
+        print(json.dumps(res))
+        return res
     finally:
         shutil.rmtree(d, ignore_errors=True)
 
@@ -98,13 +155,28 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--op", action="store_true")
     ap.add_argument("--e2e", action="store_true")
+    ap.add_argument("--posterior", action="store_true")
+    ap.add_argument("--check", action="store_true")
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "align_posterior_bench.json"))
     ap.add_argument("--reps", type=int, default=50)
     ap.add_argument("--files", type=int, default=64)
     ap.add_argument("--rounds", type=int, default=3)
     a = ap.parse_args()
     if a.op:
         op_bench(a.reps)
-    if a.e2e:
+    if a.posterior:
+        res = {"tool": "tools/align_bench.py " + " ".join(sys.argv[1:]), "gpu": torch.cuda.get_device_name(0),
+               "calls_device_events": posterior_bench(a.reps)}
+        if a.check:
+            res["max_deviation_from_float64"] = posterior_check()
+        if a.e2e:
+            res["e2e"] = e2e_bench(a.files, a.rounds, scores=True)
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            json.dump(res, f, indent=1)
+            f.write("\n")
+        print(json.dumps(res["calls_device_events"]))
+    elif a.e2e:
         e2e_bench(a.files, a.rounds)
 
 

@@ -7,6 +7,9 @@ the frame logits for the best path that spells exactly the transcript, in order 
 token gets one contiguous, time-ordered run of frames, none is dropped.
 
   viterbi_align         the C ABI on CUDA tensors: a ragged batch of clips in one call
+  alignment_posteriors  forward-backward over the same lattice (csrc/align_posterior.hip, `wfl_align_posterior`): logZ, and per token
+                        the posterior of the run Viterbi chose and the spread of its start (`postprocess.align_scores`)
+  file_score            those outputs + viterbi_align's score -> FileScore / TokenScore records
   token_alternatives    transcript tokens -> (B, I) class pairs of every phoneme whose output name is the token
   gap_classes           the classes a gap between tokens may take (O, and SP / AP unless the transcript spells them)
   path_segments         the path's ids / tokens, chunk by chunk, -> exactly one (start, end, token) per transcript token
@@ -14,6 +17,7 @@ token gets one contiguous, time-ordered run of frames, none is dropped.
 from __future__ import annotations
 
 import ctypes as C
+from typing import List, NamedTuple
 
 import numpy as np
 import torch
@@ -27,6 +31,7 @@ MAX_GAP = 8                # gap classes per clip
 PAUSES = ("SP", "AP")
 
 STATUS_OK, STATUS_INFEASIBLE, STATUS_OVER_CAP, STATUS_BAD_CLASS = 0, 1, 2, 4
+STATUS_NOT_A_PATH = 8      # wfl_align_posterior alone: `tok` is not a path of the clip's lattice
 
 
 def _ptr(t):
@@ -43,23 +48,13 @@ def workspace_bytes(n_frames, n_tokens) -> int:
     return n
 
 
-def viterbi_align(logits, n_frames, token_classes, gap_classes, o_id, frame_offsets=None, stream=None):
-    """Forced alignment of a ragged batch of clips on the GPU.
-
-    logits         [rows, C] float32 CUDA tensor (rows contiguous in C; clip b = rows frame_offsets[b] .. + n_frames[b]).  With
-                   `lang_id=None` these are the language-averaged logits the forward returns, and the search runs on those.
-    n_frames       frames per clip (host ints)
-    token_classes  per clip, per token: 1..4 (B, I) class pairs (token_alternatives)
-    gap_classes    per clip: 1..8 class ids a gap frame may take (gap_classes)
-    frame_offsets  first row of each clip (default: the clips back to back)
-    -> (ids [rows] int32, tok [rows] int32, score [clips] float32, status [clips] int32), CUDA tensors on `stream`'s device."""
-    lib = _lib.load()
+def _pack_clips(logits, n_frames, token_classes, gap_classes, frame_offsets):
+    """The validation and host-side packing that viterbi_align and alignment_posteriors share -> (nb, T, N, F0, K0, tc, gc)."""
     if not logits.is_cuda or logits.dim() != 2 or logits.dtype != torch.float32 or logits.stride(1) != 1:
         raise ValueError("logits must be a [rows, C] float32 CUDA tensor with contiguous rows")
     nb = len(n_frames)
     if len(token_classes) != nb or len(gap_classes) != nb:
         raise ValueError("n_frames, token_classes and gap_classes need one entry per clip")
-    dev = logits.device
     T = np.asarray(n_frames, np.int32).reshape(nb)
     N = np.array([len(t) for t in token_classes], np.int32)
     if frame_offsets is None:
@@ -76,11 +71,45 @@ def viterbi_align(logits, n_frames, token_classes, gap_classes, o_id, frame_offs
         if not 1 <= len(g) <= MAX_GAP:
             raise ValueError(f"a clip needs 1 to {MAX_GAP} gap classes, got {len(g)}")
         gc[b, :len(g)] = g
-    rows = logits.shape[0]
-    if nb and int((F0 + T).max()) > rows:
+    if nb and int((F0 + T).max()) > logits.shape[0]:
         raise ValueError("a clip's frames run past the logits rows")
-    d_tc = torch.from_numpy(tc).to(dev)
-    d_gc = torch.from_numpy(gc).to(dev)
+    return nb, T, N, F0, K0, tc, gc
+
+
+class PackedClips(NamedTuple):
+    """pack_clips' result: the host arrays and the uploaded token / gap tables of a ragged batch."""
+    nb: int
+    T: np.ndarray
+    N: np.ndarray
+    F0: np.ndarray
+    K0: np.ndarray
+    d_tc: torch.Tensor
+    d_gc: torch.Tensor
+
+
+def pack_clips(logits, n_frames, token_classes, gap_classes, frame_offsets=None) -> PackedClips:
+    """Validate a ragged batch and upload its token and gap tables once; pass the result as `packed=` to viterbi_align and to
+    alignment_posteriors of the same batch (the packing is host work that grows with the token count)."""
+    nb, T, N, F0, K0, tc, gc = _pack_clips(logits, n_frames, token_classes, gap_classes, frame_offsets)
+    return PackedClips(nb, T, N, F0, K0, torch.from_numpy(tc).to(logits.device), torch.from_numpy(gc).to(logits.device))
+
+
+def viterbi_align(logits, n_frames, token_classes, gap_classes, o_id, frame_offsets=None, stream=None, packed=None):
+    """Forced alignment of a ragged batch of clips on the GPU.
+
+    logits         [rows, C] float32 CUDA tensor (rows contiguous in C; clip b = rows frame_offsets[b] .. + n_frames[b]).  With
+                   `lang_id=None` these are the language-averaged logits the forward returns, and the search runs on those.
+    n_frames       frames per clip (host ints)
+    token_classes  per clip, per token: 1..4 (B, I) class pairs (token_alternatives)
+    gap_classes    per clip: 1..8 class ids a gap frame may take (gap_classes)
+    frame_offsets  first row of each clip (default: the clips back to back)
+    packed         pack_clips(...) of these same arguments, to share the packing with alignment_posteriors (default: packed here)
+    -> (ids [rows] int32, tok [rows] int32, score [clips] float32, status [clips] int32), CUDA tensors on `stream`'s device."""
+    lib = _lib.load()
+    nb, T, N, F0, K0, d_tc, d_gc = packed if packed is not None else pack_clips(logits, n_frames, token_classes, gap_classes,
+                                                                                frame_offsets)
+    dev = logits.device
+    rows = logits.shape[0]
     ws_n = workspace_bytes(T, N)
     ws = torch.empty(max(ws_n, 1), dtype=torch.uint8, device=dev)
     ids = torch.empty(rows, dtype=torch.int32, device=dev)
@@ -96,6 +125,51 @@ def viterbi_align(logits, n_frames, token_classes, gap_classes, o_id, frame_offs
         for t in (d_tc, d_gc, ws):
             t.record_stream(st)
     return ids, tok, score[:nb], status[:nb]
+
+
+def posterior_workspace_bytes(n_frames, n_tokens) -> int:
+    lib = _lib.load()
+    T = np.ascontiguousarray(n_frames, np.int32)
+    N = np.ascontiguousarray(n_tokens, np.int32)
+    n = int(lib.wfl_align_posterior_workspace_bytes(T.ctypes.data_as(C.c_void_p), N.ctypes.data_as(C.c_void_p), T.size))
+    if n < 0:
+        raise _lib.WflError("wfl_align_posterior_workspace_bytes: negative frame or token count")
+    return n
+
+
+def alignment_posteriors(logits, n_frames, token_classes, gap_classes, o_id, tok, frame_offsets=None, stream=None, packed=None):
+    """Forward-backward over the lattice of viterbi_align, for the same ragged batch of clips (same arguments), given its `tok`.
+
+    tok     [rows] int32 CUDA tensor: viterbi_align's output for these clips (row frame_offsets[b] + t)
+    packed  the pack_clips(...) result that viterbi_align ran on, when the batch is the same (default: packed here)
+    -> (logz [clips], tok_post [tokens], start_mean [tokens], start_sd [tokens], status [clips]): float32 / int32 CUDA tensors, the
+    per-token ones in the order of the clips' tokens.  logz: log of the summed weight of every path that spells the transcript;
+    tok_post: the posterior occupancy of the run Viterbi gave the token, in [0, 1]; start_mean / start_sd: mean (relative to
+    Viterbi's start) and standard deviation of the token's start, in frames.  A clip with status != 0 gets zeros
+    (STATUS_NOT_A_PATH: `tok` does not hold every token of the clip)."""
+    lib = _lib.load()
+    nb, T, N, F0, K0, d_tc, d_gc = packed if packed is not None else pack_clips(logits, n_frames, token_classes, gap_classes,
+                                                                                frame_offsets)
+    dev = logits.device
+    if not tok.is_cuda or tok.device != dev or tok.dtype != torch.int32 or tok.dim() != 1 or tok.stride(0) != 1 \
+            or tok.shape[0] != logits.shape[0]:
+        raise ValueError("tok must be viterbi_align's [rows] int32 CUDA tensor for these logits")
+    ntok = int(N.sum())
+    ws_n = posterior_workspace_bytes(T, N)
+    ws = torch.empty(max(ws_n, 1), dtype=torch.uint8, device=dev)
+    logz = torch.empty(max(nb, 1), dtype=torch.float32, device=dev)
+    per_tok = torch.empty((3, max(ntok, 1)), dtype=torch.float32, device=dev)
+    status = torch.empty(max(nb, 1), dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        st = stream if stream is not None else torch.cuda.current_stream(dev)
+        hp = lambda a: a.ctypes.data_as(C.c_void_p)      # noqa: E731
+        rc = lib.wfl_align_posterior(_ptr(logits), logits.stride(0), logits.shape[1], int(o_id), hp(F0), hp(T), hp(K0), hp(N),
+                                     _ptr(d_tc), _ptr(d_gc), nb, _ptr(tok), _ptr(ws), ws_n, _ptr(logz), _ptr(per_tok[0]),
+                                     _ptr(per_tok[1]), _ptr(per_tok[2]), _ptr(status), C.c_void_p(st.cuda_stream))
+        _lib.check(rc, "wfl_align_posterior")
+        for t in (d_tc, d_gc, ws):
+            t.record_stream(st)
+    return logz[:nb], per_tok[0, :ntok], per_tok[1, :ntok], per_tok[2, :ntok], status[:nb]
 
 
 # ---------------------------------------------------------------------------------------------------------------- host helpers
@@ -195,3 +269,34 @@ def with_end_pauses(free_segments, aligned, transcript):
         after = [s for s in free_segments if s[2] in PAUSES and s[0] >= aligned[-1][1]]
         return before + aligned + after
     return aligned
+
+
+# ------------------------------------------------------------------------------------------------------------- alignment scores
+class TokenScore(NamedTuple):
+    token: str
+    start_s: float          # the token's segment, as in the .lab
+    end_s: float
+    posterior: float        # posterior occupancy of the frames Viterbi gave the token (alignment_posteriors' tok_post)
+    start_sd_s: float       # posterior standard deviation of the token's start, seconds on the .lab clock
+    start_shift_s: float    # posterior mean of the start minus Viterbi's start, seconds on the .lab clock
+
+
+class FileScore(NamedTuple):
+    path_log_posterior: float    # score - logz, <= 0; 0 means "the only plausible path"
+    mean_frame_logprob: float    # score / n_frames
+    mean_frame_logz: float       # logz / n_frames: comparable between transcripts of one file (the better transcript is higher)
+    min_posterior: float         # the weakest token's posterior (1 for an empty transcript)
+    tokens: List[TokenScore]
+
+
+def file_score(score, logz, n_frames, tok_post, start_mean, start_sd, segments, frame_duration):
+    """One file's FileScore from viterbi_align's score, alignment_posteriors' outputs for the file (host values) and the file's
+    aligned segments [(start_s, end_s, token)], one per transcript token in order (path_segments).  frame_duration: the .lab clock
+    (postprocess.FRAME_DURATION) that turns the frame figures into seconds."""
+    tok_post, start_mean, start_sd = (np.asarray(a, np.float64).reshape(-1) for a in (tok_post, start_mean, start_sd))
+    if not len(tok_post) == len(start_mean) == len(start_sd) == len(segments):
+        raise ValueError("one posterior, start mean and start deviation per aligned segment")
+    score, logz, n = float(score), float(logz), max(int(n_frames), 1)
+    toks = [TokenScore(str(ph), float(s), float(e), float(p), float(sd) * frame_duration, float(mu) * frame_duration)
+            for (s, e, ph), p, mu, sd in zip(segments, tok_post, start_mean, start_sd)]
+    return FileScore(score - logz, score / n, logz / n, float(tok_post.min()) if len(tok_post) else 1.0, toks)

@@ -1,0 +1,666 @@
+// Forward-backward over the forced-alignment lattice of wfl_align: per-token posteriors of a Viterbi path (wfl_align_posterior,
+// include/wfl_asr.h).  The sum-product twin of csrc/align.hip; the reference has no counterpart (it reports no confidence for its
+// string match).
+//
+// Lattice, emissions, start / end states and caps are wfl_align's (states G_k = 3k, B_k = 3k + 1, I_k = 3k + 2):
+//   alpha_t(G_k) = EG_t + lse(alpha_{t-1}(G_k), alpha_{t-1}(I_{k-1}), alpha_{t-1}(B_{k-1}))      alpha_t(B_k): the same sum + EB_t(k)
+//   alpha_t(I_k) = EI_t(k) + lse(alpha_{t-1}(I_k), alpha_{t-1}(B_k))
+//   beta_{t-1}(G_k) = lse(beta_t(G_k) + EG_t, beta_t(B_k) + EB_t(k))
+//   beta_{t-1}(B_k) = beta_{t-1}(I_k) = lse(beta_t(I_k) + EI_t(k), beta_t(G_{k+1}) + EG_t, beta_t(B_{k+1}) + EB_t(k+1))
+//   logZ = lse(alpha_{T-1}(G_N), alpha_{T-1}(I_{N-1}), alpha_{T-1}(B_{N-1})),   gamma_t(s) = exp(alpha_t(s) + beta_t(s) - logZ).
+// beta of B_k and I_k are equal (same successors), so the backward sweep carries two values per token.
+//
+// One workgroup per clip, configurations and slot ownership as align_kernel: thread i owns the token slots i R .. i R + R - 1 in
+// registers.  Per frame one float2 crosses between neighbouring threads through LDS, one barrier per frame: the forward sweep takes
+// (alpha(B), alpha(I)) of the last slot of thread i - 1, the backward sweep (beta(G), beta(B)) of the first slot of thread i + 1 (the
+// emission of that slot's B state is gathered by thread i itself, from the staged row).  Every per-token output is accumulated by
+// the thread that owns the token; no reduction over the block per frame.  Every 16 frames the block's maximum is subtracted from the
+// states (alpha and beta separately) and added to a double, so the fp32 log-domain values never grow with T.
+//
+// Memory: the alpha lattice is never stored.  Sweep 1 runs forward over the clip and keeps a checkpoint of the registers every
+// POST_W frames; then, block by block from the last one, sweep 2 recomputes the block's POST_W frames of alpha from its checkpoint
+// into a block buffer and sweep 3 walks beta down the block, combining.  Every thread reads back only what it wrote itself.
+// Workspace per clip: lse[T] | checkpoints' offsets | checkpoints | one block (wfl_align_posterior_workspace_bytes).
+//
+// The per-frame log-sum-exp of the logits is computed once (double, expf), stored in fp32 and subtracted from the gathered logits;
+// what the fp32 rounding of it loses is summed in double and given back to logZ (it is common to every path).
+#include "common.h"
+#include "wfl_asr.h"
+
+#include <limits.h>
+#include <math.h>
+
+#include <algorithm>
+#include <vector>
+
+namespace {
+
+constexpr int POST_MAX_TOKENS = 4096;
+constexpr int POST_MAX_CLASSES = 1024;
+constexpr int POST_W = 128;                // frames per recomputed block (a multiple of the renormalisation period)
+constexpr int POST_RENORM = 16;
+constexpr int POST_CLIPS_PER_LAUNCH = 64;  // the clip table travels in the kernel arguments
+constexpr int POST_NGAP = 8;
+constexpr int POST_FMAX = 32;              // staged rows per stage, at most
+static_assert(POST_W % POST_RENORM == 0, "a block ends on a renormalisation");
+
+struct PostClip {
+  long frame_off;  // first logits row of the clip
+  long ws_off;     // the clip's workspace, in floats
+  int T, tok_off, N, clip;
+};
+
+struct PostLaunch {
+  const float* logits;
+  long ldl;
+  int C;
+  const int* tok_cls;  // [total tokens][4][2]
+  const int* gap_cls;  // [n_clips][8]
+  const int* tok;      // wfl_align's output, same rows as the logits
+  float* ws;
+  float* logz;
+  float* tok_post;
+  float* start_mean;
+  float* start_sd;
+  int* status;
+  int n;
+  PostClip clip[POST_CLIPS_PER_LAUNCH];
+};
+
+__host__ __device__ constexpr long round64(long x) { return (x + 63) / 64 * 64; }
+
+// a clip's workspace in floats: [lse: round64(T)] [checkpoint offsets: round64(2 nblk)] [checkpoints: nblk S] [block: POST_W S]
+struct PostLayout {
+  long ckacc, ckpt, blk, total;
+  int nblk;
+  __host__ __device__ PostLayout(int T, long S) {
+    nblk = (T + POST_W - 1) / POST_W;
+    ckacc = round64(T);
+    ckpt = ckacc + round64(2L * nblk);
+    blk = ckpt + (long)nblk * S;
+    total = blk + (long)POST_W * S;
+  }
+};
+
+template <int NT, int R>
+struct PCfg {
+  static constexpr int PR = NT >= 512 ? 8 : 16;          // staged logits values per thread
+  static constexpr int NW = NT / 64;
+  static constexpr long S = (long)NT * R * 3;            // floats of one frame's alpha (and of one checkpoint)
+  static constexpr int OFF_ALT = 2 * NT * PR * 4;                  // ring: two stages of NT PR floats
+  static constexpr int OFF_FIRST = OFF_ALT + NT * R * 16;          // alternatives: one int4 (B | I << 16, -1 unused) per slot
+  static constexpr int OFF_XF = OFF_FIRST + NT * R * 4;            // first frame of every token's Viterbi run
+  static constexpr int OFF_XB = OFF_XF + 2 * NT * 8;               // forward neighbour exchange: [2][NT] float2
+  static constexpr int OFF_WMAX = OFF_XB + 2 * NT * 8;             // backward neighbour exchange
+  static constexpr int OFF_RED = OFF_WMAX + 64;                    // per-wave maxima (renormalisation)
+  static constexpr int OFF_OFFA = OFF_RED + 8 * 16;                // per-wave double sums, logZ
+  static constexpr int OFF_LRING = OFF_OFFA + POST_W * 8;          // alpha's offset of every frame of the block (double)
+  static constexpr int OFF_TRING = OFF_LRING + 2 * POST_FMAX * 4;  // staged rows' log-sum-exp
+  static constexpr int OFF_MISC = OFF_TRING + 2 * POST_FMAX * 4;   // staged rows' Viterbi token
+  static constexpr int LDS = OFF_MISC + 64;
+};
+
+__device__ __forceinline__ float wave_max(float v) {
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
+  return v;
+}
+
+__device__ __forceinline__ double wave_sum(double v) {
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o);
+  return v;
+}
+
+// log(exp a + exp b [+ exp c]); -inf in, -inf out (v_exp_f32 / v_log_f32)
+__device__ __forceinline__ float lae2(float a, float b) {
+  const float m = fmaxf(a, b);
+  const float ms = m == -INFINITY ? 0.f : m;
+  return ms + __logf(__expf(a - ms) + __expf(b - ms));
+}
+
+__device__ __forceinline__ float lae3(float a, float b, float c) {
+  const float m = fmaxf(a, fmaxf(b, c));
+  const float ms = m == -INFINITY ? 0.f : m;
+  return ms + __logf(__expf(a - ms) + __expf(b - ms) + __expf(c - ms));
+}
+
+template <int NT, int R>
+__global__ __launch_bounds__(NT) void post_kernel(PostLaunch a) {
+  using K = PCfg<NT, R>;
+  extern __shared__ __attribute__((aligned(16))) char lds[];
+  float* ring = (float*)lds;
+  int4* alt = (int4*)(lds + K::OFF_ALT);
+  int* first = (int*)(lds + K::OFF_FIRST);
+  float2* xf = (float2*)(lds + K::OFF_XF);
+  float2* xb = (float2*)(lds + K::OFF_XB);
+  float* wmax = (float*)(lds + K::OFF_WMAX);
+  double* red = (double*)(lds + K::OFF_RED);
+  double* offa = (double*)(lds + K::OFF_OFFA);
+  float* lring = (float*)(lds + K::OFF_LRING);
+  int* tring = (int*)(lds + K::OFF_TRING);
+  int* misc = (int*)(lds + K::OFF_MISC);
+  float* fin = (float*)(misc + 4);
+
+  const PostClip cl = a.clip[blockIdx.x];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int T = cl.T, N = cl.N, C = a.C;
+  const float* Z = a.logits + cl.frame_off * a.ldl;
+  const int* tokp = a.tok + cl.frame_off;
+  const float NEG = -INFINITY;
+
+  int st = 0;
+  if (N > NT * R - 1 || N > POST_MAX_TOKENS) st = 2;
+  else if (T < N) st = 1;
+  int g[POST_NGAP];
+  if (st == 0) {
+    if (tid == 0) misc[0] = 0;
+    __syncthreads();
+    bool bad = false;
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+      const int k = tid * R + r;
+      int4 v = make_int4(-1, -1, -1, -1);          // the used alternatives first
+      if (k < N) {
+        const int* tc = a.tok_cls + (long)(cl.tok_off + k) * 8;
+        int n = 0;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const int b = tc[2 * j], i = tc[2 * j + 1];
+          if (b == -1 && i == -1) continue;                        // an unused alternative
+          if (b < 0 || b >= C || i < 0 || i >= C) { bad = true; continue; }
+          const int pk = b | (i << 16);
+          if (n == 0) v.x = pk; else if (n == 1) v.y = pk; else if (n == 2) v.z = pk; else v.w = pk;
+          ++n;
+        }
+        if (n == 0) bad = true;
+      }
+      alt[k] = v;
+      first[k] = INT_MAX;
+    }
+    int ng = 0;
+#pragma unroll
+    for (int j = 0; j < POST_NGAP; ++j) {
+      g[j] = a.gap_cls[(long)cl.clip * POST_NGAP + j];
+      if (g[j] == -1) continue;
+      if (g[j] < 0 || g[j] >= C) { bad = true; g[j] = -1; }
+      else ++ng;
+    }
+    if (ng == 0) bad = true;
+    if (bad) misc[0] = 1;
+    __syncthreads();
+    if (misc[0]) st = 4;
+    __syncthreads();                           // every thread has read the flag before the next phase may raise it again
+  }
+  if (st == 0 && T > 0) {
+    // the first frame of every token's Viterbi run; a tok that is not a path of this lattice (a token missing, a value out of range)
+    bool bad = false;
+    for (int t = tid; t < T; t += NT) {
+      const int k = tokp[t];
+      if (k < -1 || k >= N) bad = true;
+      else if (k >= 0 && (t == 0 || tokp[t - 1] != k)) atomicMin(&first[k], t);
+    }
+    if (bad) misc[0] = 1;
+    __syncthreads();
+#pragma unroll
+    for (int r = 0; r < R; ++r)
+      if (tid * R + r < N && first[tid * R + r] == INT_MAX) misc[0] = 1;
+    __syncthreads();
+    if (misc[0]) st = 8;
+  }
+  if (st != 0 || T == 0) {
+    for (int k = tid; k < N; k += NT) {
+      a.tok_post[cl.tok_off + k] = 0.f;
+      a.start_mean[cl.tok_off + k] = 0.f;
+      a.start_sd[cl.tok_off + k] = 0.f;
+    }
+    if (tid == 0) { a.logz[cl.clip] = 0.f; a.status[cl.clip] = st; }
+    return;
+  }
+
+  const PostLayout lay(T, K::S);
+  float* ws = a.ws + cl.ws_off;
+  float* lse = ws;
+  double* ckacc = (double*)(ws + lay.ckacc);
+  float* ckpt = ws + lay.ckpt;
+  float* blk = ws + lay.blk;
+
+  // ---- the per-frame log-sum-exp, in fp32 for the sweeps; what its rounding loses, in double for logZ
+  double lres = 0.0;
+  // (a thread per row; a wave per row with coalesced loads and wave reductions was measured 4 % slower for the whole kernel)
+  for (int t = tid; t < T; t += NT) {
+    const float* z = Z + (long)t * a.ldl;
+    float m = z[0];
+    for (int q = 1; q < C; ++q) m = fmaxf(m, z[q]);
+    double se = 0.0;
+    for (int q = 0; q < C; ++q) se += (double)expf(z[q] - m);
+    const double ld = (double)m + log(se);
+    const float lf = (float)ld;
+    lse[t] = lf;
+    lres += ld - (double)lf;
+  }
+  lres = wave_sum(lres);
+  if (lane == 0) red[wave] = lres;
+  __syncthreads();                             // (and the block sees lse[])
+  lres = 0.0;
+#pragma unroll
+  for (int w = 0; w < K::NW; ++w) lres += red[w];
+
+  // ---- staging of the logits rows (with their log-sum-exp and Viterbi token): stage c = rows c F .. c F + F - 1
+  const int F = min(POST_FMAX, NT * K::PR / C);       // rows per stage (C <= POST_MAX_CLASSES <= NT PR: F >= 1)
+  const int SE = F * C;
+  int rc[K::PR];                               // (row << 16 | column) of this thread's staged values inside a stage, -1 none
+#pragma unroll
+  for (int i = 0; i < K::PR; ++i) {
+    const int e = tid + i * NT;
+    rc[i] = e < SE ? ((e / C) << 16) | (e % C) : -1;
+  }
+  float pre[K::PR];
+  float pre_l = 0.f;
+  int pre_t = -1;
+  auto load_stage = [&](int c) {
+    const int t0 = c * F;
+#pragma unroll
+    for (int i = 0; i < K::PR; ++i) {
+      const int row = t0 + (rc[i] >> 16);
+      pre[i] = (rc[i] >= 0 && c >= 0 && row < T) ? Z[(long)row * a.ldl + (rc[i] & 0xffff)] : 0.f;
+    }
+    const bool in = tid < F && c >= 0 && t0 + tid < T;
+    pre_l = in ? lse[t0 + tid] : 0.f;
+    pre_t = in ? tokp[t0 + tid] : -1;
+  };
+  auto store_stage = [&](int c) {
+    float* h = ring + (c & 1) * NT * K::PR;
+#pragma unroll
+    for (int i = 0; i < K::PR; ++i)
+      if (rc[i] >= 0) h[tid + i * NT] = pre[i];
+    if (tid < F) {
+      lring[(c & 1) * POST_FMAX + tid] = pre_l;
+      tring[(c & 1) * POST_FMAX + tid] = pre_t;
+    }
+  };
+
+  int4 av[R];                                   // this thread's slots' alternatives
+#pragma unroll
+  for (int r = 0; r < R; ++r) av[r] = alt[tid * R + r];
+  const int4 avn = tid + 1 < NT ? alt[(tid + 1) * R] : make_int4(-1, -1, -1, -1);   // the next thread's first slot
+  auto gap_emission = [&](const float* row) {
+    float eg = NEG;
+#pragma unroll
+    for (int j = 0; j < POST_NGAP; ++j)
+      if (g[j] >= 0) eg = fmaxf(eg, row[g[j]]);
+    return eg;
+  };
+  auto tok_emission = [&](const float* row, const int4& v, float& eb, float& ei) {
+    const int p[4] = {v.x, v.y, v.z, v.w};
+    eb = NEG;
+    ei = NEG;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      if (p[j] < 0) break;
+      eb = fmaxf(eb, row[p[j] & 0xffff]);
+      ei = fmaxf(ei, row[p[j] >> 16]);
+    }
+  };
+
+  // ---- the forward sweep over frames t0 .. t1 - 1, from the clip's start (t0 = 0) or from checkpoint t0 / POST_W
+  float G[R], B[R], I[R];
+  double acc = 0.0;                            // what alpha's renormalisations subtracted
+  auto forward = [&](int t0, int t1, bool keep) {
+    if (t0 == 0) {
+#pragma unroll
+      for (int r = 0; r < R; ++r) G[r] = B[r] = I[r] = NEG;
+      if (tid == 0) G[0] = 0.f;                // a virtual frame -1 in G_0: frame 0 starts in G_0 or B_0
+      acc = 0.0;
+    } else {
+      const float* ck = ckpt + (long)(t0 / POST_W) * K::S;
+#pragma unroll
+      for (int r = 0; r < R; ++r) {
+        G[r] = ck[(r * 3 + 0) * NT + tid];
+        B[r] = ck[(r * 3 + 1) * NT + tid];
+        I[r] = ck[(r * 3 + 2) * NT + tid];
+      }
+      acc = ckacc[t0 / POST_W];
+    }
+    xf[((t0 + 1) & 1) * NT + tid] = make_float2(B[R - 1], I[R - 1]);
+    float sub = 0.f;
+    int c = t0 / F, tin = t0 - c * F;
+    __syncthreads();                           // the ring's last readers are done
+    load_stage(c);
+    store_stage(c);
+    load_stage(c + 1);
+    __syncthreads();
+    for (int t = t0; t < t1; ++t, ++tin) {
+      if (tin == F) {
+        ++c;
+        tin = 0;
+        store_stage(c);
+        __syncthreads();
+        load_stage(c + 1);
+      }
+      const float* row = ring + (c & 1) * NT * K::PR + tin * C;
+      const float l = lring[(c & 1) * POST_FMAX + tin];
+      const float eg = gap_emission(row) - l;
+      float2 nb = tid > 0 ? xf[((t + 1) & 1) * NT + tid - 1] : make_float2(NEG, NEG);
+      nb.x -= sub;
+      nb.y -= sub;
+#pragma unroll
+      for (int r = R - 1; r >= 0; --r) {       // descending: slot r - 1's previous-frame values are still in place
+        const int k = tid * R + r;
+        const float pB1 = r ? B[r > 0 ? r - 1 : 0] : nb.x;
+        const float pI1 = r ? I[r > 0 ? r - 1 : 0] : nb.y;
+        const float in = lae3(G[r], pI1, pB1);
+        const float ii = lae2(I[r], B[r]);
+        float eb = NEG, ei = NEG;
+        if (k < N) {
+          tok_emission(row, av[r], eb, ei);
+          eb -= l;
+          ei -= l;
+        }
+        G[r] = k <= N ? in + eg : NEG;
+        B[r] = in + eb;
+        I[r] = ii + ei;
+      }
+      xf[(t & 1) * NT + tid] = make_float2(B[R - 1], I[R - 1]);
+      const bool renorm = (t & (POST_RENORM - 1)) == POST_RENORM - 1;
+      if (renorm) {
+        float lm = NEG;
+#pragma unroll
+        for (int r = 0; r < R; ++r) lm = fmaxf(lm, fmaxf(G[r], fmaxf(B[r], I[r])));
+        lm = wave_max(lm);
+        if (lane == 0) wmax[wave] = lm;
+      }
+      __syncthreads();
+      sub = 0.f;
+      if (renorm) {
+        float M = wmax[0];
+#pragma unroll
+        for (int w = 1; w < K::NW; ++w) M = fmaxf(M, wmax[w]);
+        if (!(M > NEG)) M = 0.f;
+#pragma unroll
+        for (int r = 0; r < R; ++r) { G[r] -= M; B[r] -= M; I[r] -= M; }
+        sub = M;
+        acc += (double)M;
+      }
+      if (keep) {                              // the block's alpha, for the backward sweep of the same thread
+        float* o = blk + (long)(t - t0) * K::S;
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+          o[(r * 3 + 0) * NT + tid] = G[r];
+          o[(r * 3 + 1) * NT + tid] = B[r];
+          o[(r * 3 + 2) * NT + tid] = I[r];
+        }
+        if (tid == 0) offa[t - t0] = acc;
+      } else if ((t + 1) % POST_W == 0 && t + 1 < T) {   // (a block ends on a renormalisation: sub is spent)
+        float* o = ckpt + (long)((t + 1) / POST_W) * K::S;
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+          o[(r * 3 + 0) * NT + tid] = G[r];
+          o[(r * 3 + 1) * NT + tid] = B[r];
+          o[(r * 3 + 2) * NT + tid] = I[r];
+        }
+        if (tid == 0) ckacc[(t + 1) / POST_W] = acc;
+      }
+    }
+  };
+
+  // ---- sweep 1: alpha over the whole clip, checkpoints, logZ
+  forward(0, T, false);
+#pragma unroll
+  for (int r = 0; r < R; ++r) {
+    const int k = tid * R + r;
+    if (k == N) fin[0] = G[r];
+    if (k == N - 1) { fin[1] = I[r]; fin[2] = B[r]; }
+  }
+  __syncthreads();
+  if (tid == 0) {
+    const int ne = N >= 1 ? 3 : 1;
+    double m = -INFINITY;
+    for (int i = 0; i < ne; ++i) m = fmax(m, (double)fin[i]);
+    double s = 0.0;
+    for (int i = 0; i < ne; ++i) s += exp((double)fin[i] - m);
+    red[0] = m + log(s) + acc;
+  }
+  __syncthreads();                             // (ckacc[] of thread 0 is visible to the block as well)
+  const double logZ = red[0];                  // on the fp32 log-sum-exps; the clip's logZ is logZ - lres
+
+  // ---- sweeps 2 and 3, block by block from the end
+  float bG[R], bX[R];                          // beta(G_k), beta(B_k) = beta(I_k)
+  int f0[R], cnt[R];
+  double occ[R], m0[R], m1[R], m2[R];
+#pragma unroll
+  for (int r = 0; r < R; ++r) {
+    const int k = tid * R + r;
+    bG[r] = k == N ? 0.f : NEG;
+    bX[r] = k == N - 1 ? 0.f : NEG;
+    f0[r] = k < N ? first[k] : 0;
+    cnt[r] = 0;
+    occ[r] = m0[r] = m1[r] = m2[r] = 0.0;
+  }
+  xb[(T & 1) * NT + tid] = make_float2(bG[0], bX[0]);
+  double accb = 0.0;                           // what beta's renormalisations subtracted
+  float subb = 0.f;
+  for (int j = lay.nblk - 1; j >= 0; --j) {
+    const int t_lo = j * POST_W, t_hi = min(T, t_lo + POST_W) - 1;
+    forward(t_lo, t_hi + 1, true);
+    int c = t_hi / F, tin = t_hi - c * F;
+    __syncthreads();
+    load_stage(c);
+    store_stage(c);
+    load_stage(c - 1);
+    __syncthreads();
+    float an[R][3], ac[R][3];
+    auto load_alpha = [&](int f) {
+      const float* o = blk + (long)f * K::S;
+#pragma unroll
+      for (int r = 0; r < R; ++r) {
+        an[r][0] = o[(r * 3 + 0) * NT + tid];
+        an[r][1] = o[(r * 3 + 1) * NT + tid];
+        an[r][2] = o[(r * 3 + 2) * NT + tid];
+      }
+    };
+    load_alpha(t_hi - t_lo);
+    for (int t = t_hi; t >= t_lo; --t, --tin) {
+      if (tin < 0) {
+        --c;
+        tin = F - 1;
+        store_stage(c);
+        __syncthreads();
+        load_stage(c - 1);
+      }
+      const float* row = ring + (c & 1) * NT * K::PR + tin * C;
+      const float l = lring[(c & 1) * POST_FMAX + tin];
+      const int tk = tring[(c & 1) * POST_FMAX + tin];
+#pragma unroll
+      for (int r = 0; r < R; ++r) { ac[r][0] = an[r][0]; ac[r][1] = an[r][1]; ac[r][2] = an[r][2]; }
+      if (t > t_lo) load_alpha(t - 1 - t_lo);  // one frame ahead of its use
+      // gamma_t of this thread's tokens
+      const double cst = offa[t - t_lo] + accb - logZ;
+#pragma unroll
+      for (int r = 0; r < R; ++r) {
+        const int k = tid * R + r;
+        if (k < N) {
+          const float gb = __expf((float)((double)ac[r][1] + (double)bX[r] + cst));
+          const float gi = __expf((float)((double)ac[r][2] + (double)bX[r] + cst));
+          const double d = (double)(t - f0[r]);
+          m0[r] += (double)gb;
+          m1[r] += (double)gb * d;
+          m2[r] += (double)gb * d * d;
+          if (tk == k) { occ[r] += (double)gb + (double)gi; ++cnt[r]; }
+        }
+      }
+      if (t == 0) break;
+      // beta_{t-1}
+      const float eg = gap_emission(row) - l;
+      float eb[R], ei[R];
+#pragma unroll
+      for (int r = 0; r < R; ++r) {
+        eb[r] = ei[r] = NEG;
+        if (tid * R + r < N) {
+          tok_emission(row, av[r], eb[r], ei[r]);
+          eb[r] -= l;
+          ei[r] -= l;
+        }
+      }
+      float ebn = NEG;
+      if ((tid + 1) * R < N && tid + 1 < NT) {
+        float ein;
+        tok_emission(row, avn, ebn, ein);
+        ebn -= l;
+      }
+      float2 nb = tid + 1 < NT ? xb[((t + 1) & 1) * NT + tid + 1] : make_float2(NEG, NEG);
+      nb.x -= subb;
+      nb.y -= subb;
+#pragma unroll
+      for (int r = 0; r < R; ++r) {            // ascending: slot r + 1's values of frame t are still in place
+        const int k = tid * R + r;
+        const float nG = r + 1 < R ? bG[r + 1 < R ? r + 1 : 0] : nb.x;
+        const float nX = r + 1 < R ? bX[r + 1 < R ? r + 1 : 0] : nb.y;
+        const float nE = r + 1 < R ? eb[r + 1 < R ? r + 1 : 0] : ebn;
+        const float x = lae3(bX[r] + ei[r], nG + eg, nX + nE);
+        const float y = lae2(bG[r] + eg, bX[r] + eb[r]);
+        bG[r] = k <= N ? y : NEG;
+        bX[r] = k < N ? x : NEG;
+      }
+      xb[(t & 1) * NT + tid] = make_float2(bG[0], bX[0]);
+      const bool renorm = (t & (POST_RENORM - 1)) == 0;
+      if (renorm) {
+        float lm = NEG;
+#pragma unroll
+        for (int r = 0; r < R; ++r) lm = fmaxf(lm, fmaxf(bG[r], bX[r]));
+        lm = wave_max(lm);
+        if (lane == 0) wmax[wave] = lm;
+      }
+      __syncthreads();
+      subb = 0.f;
+      if (renorm) {
+        float M = wmax[0];
+#pragma unroll
+        for (int w = 1; w < K::NW; ++w) M = fmaxf(M, wmax[w]);
+        if (!(M > NEG)) M = 0.f;
+#pragma unroll
+        for (int r = 0; r < R; ++r) { bG[r] -= M; bX[r] -= M; }
+        subb = M;
+        accb += (double)M;
+      }
+    }
+  }
+
+  // ---- per-token outputs, by the thread that owns the token
+#pragma unroll
+  for (int r = 0; r < R; ++r) {
+    const int k = tid * R + r;
+    if (k < N) {
+      const double mean = m0[r] > 0.0 ? m1[r] / m0[r] : 0.0;
+      const double var = m0[r] > 0.0 ? m2[r] / m0[r] - mean * mean : 0.0;
+      a.tok_post[cl.tok_off + k] = cnt[r] > 0 ? fminf((float)(occ[r] / (double)cnt[r]), 1.f) : 0.f;
+      a.start_mean[cl.tok_off + k] = (float)mean;
+      a.start_sd[cl.tok_off + k] = (float)sqrt(fmax(var, 0.0));
+    }
+  }
+  if (tid == 0) {
+    a.logz[cl.clip] = (float)(logZ - lres);
+    a.status[cl.clip] = 0;
+  }
+}
+
+// configuration by token count: (threads, slots per thread); NT R - 1 >= N  (align_kernel's)
+constexpr int kCfgMaxN[5] = {127, 511, 1023, 2047, POST_MAX_TOKENS};
+constexpr long kCfgS[5] = {PCfg<64, 2>::S, PCfg<256, 2>::S, PCfg<256, 4>::S, PCfg<256, 8>::S, PCfg<512, 9>::S};
+static_assert(64 * 2 - 1 >= 127 && 256 * 2 - 1 >= 511 && 256 * 4 - 1 >= 1023 && 256 * 8 - 1 >= 2047 && 512 * 9 - 1 >= 4096, "slots");
+
+int cfg_of(int N) {
+  for (int c = 0; c < 5; ++c)
+    if (N <= kCfgMaxN[c]) return c;
+  return 4;                                     // over the cap: the kernel reports status 2; sized as the cap, so the need is monotone
+}
+
+long clip_floats(int T, int N) {
+  if (T <= 0) return 0;
+  return round64(PostLayout(T, kCfgS[cfg_of(N)]).total);     // (256-byte aligned)
+}
+
+template <int NT, int R>
+int launch_cfg(const PostLaunch& a, hipStream_t s) {
+  auto k = post_kernel<NT, R>;
+  constexpr int lds = PCfg<NT, R>::LDS;
+  static_assert(lds <= 160 * 1024, "LDS");
+  static WflOncePerDevice attr_once;
+  if (attr_once.need()) {
+    if (hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess)
+      return wfl_fail(-2, "wfl_align_posterior: cannot reserve the kernel's LDS");
+  }
+  hipLaunchKernelGGL(k, dim3(a.n), dim3(NT), lds, s, a);
+  return hipGetLastError() == hipSuccess ? 0 : wfl_fail(-3, "wfl_align_posterior: launch failed");
+}
+
+int launch(int cfg, const PostLaunch& a, hipStream_t s) {
+  switch (cfg) {
+    case 0: return launch_cfg<64, 2>(a, s);
+    case 1: return launch_cfg<256, 2>(a, s);
+    case 2: return launch_cfg<256, 4>(a, s);
+    case 3: return launch_cfg<256, 8>(a, s);
+    default: return launch_cfg<512, 9>(a, s);
+  }
+}
+
+}  // namespace
+
+extern "C" {
+
+int64_t wfl_align_posterior_workspace_bytes(const int32_t* n_frames_host, const int32_t* n_tok_host, int32_t n_clips) {
+  if (n_clips < 0 || (n_clips > 0 && (!n_frames_host || !n_tok_host))) return -1;
+  int64_t words = 0;
+  for (int b = 0; b < n_clips; ++b) {
+    if (n_frames_host[b] < 0 || n_tok_host[b] < 0) return -1;
+    words += clip_floats(n_frames_host[b], n_tok_host[b]);
+  }
+  return words * 4;
+}
+
+int32_t wfl_align_posterior(const float* logits, int64_t ldl, int32_t C, int32_t o_id, const int64_t* frame_off_host,
+                            const int32_t* n_frames_host, const int32_t* tok_off_host, const int32_t* n_tok_host, const int32_t* tok_cls,
+                            const int32_t* gap_cls, int32_t n_clips, const int32_t* tok, void* workspace, int64_t workspace_bytes,
+                            float* logz, float* tok_post, float* start_mean, float* start_sd, int32_t* status, void* stream) {
+  if (C < 1 || C > POST_MAX_CLASSES) return wfl_fail(-1, "wfl_align_posterior: C must be 1 .. 1024");
+  if (o_id < 0 || o_id >= C) return wfl_fail(-1, "wfl_align_posterior: o_id out of range");
+  if (ldl < C) return wfl_fail(-1, "wfl_align_posterior: ldl < C");
+  if (n_clips < 0) return wfl_fail(-1, "wfl_align_posterior: n_clips < 0");
+  if (n_clips == 0) return 0;
+  if (!frame_off_host || !n_frames_host || !tok_off_host || !n_tok_host)
+    return wfl_fail(-1, "wfl_align_posterior: null host array");
+  const int64_t need = wfl_align_posterior_workspace_bytes(n_frames_host, n_tok_host, n_clips);
+  if (need < 0) return wfl_fail(-1, "wfl_align_posterior: negative frame or token count");
+  bool any_tok = false, any_frame = false;
+  for (int b = 0; b < n_clips; ++b) {
+    if (frame_off_host[b] < 0 || tok_off_host[b] < 0) return wfl_fail(-1, "wfl_align_posterior: negative offset");
+    any_tok |= n_tok_host[b] > 0;
+    any_frame |= n_frames_host[b] > 0;
+  }
+  if (!logz || !status || !gap_cls || (any_tok && (!tok_cls || !tok_post || !start_mean || !start_sd)) || (any_frame && (!logits || !tok)))
+    return wfl_fail(-1, "wfl_align_posterior: null device pointer");
+  if (workspace_bytes < need || (need > 0 && !workspace))
+    return wfl_fail(-1, "wfl_align_posterior: workspace too small (wfl_align_posterior_workspace_bytes)");
+  hipStream_t s = (hipStream_t)stream;
+  PostLaunch a{};
+  a.logits = logits; a.ldl = ldl; a.C = C; a.tok_cls = tok_cls; a.gap_cls = gap_cls; a.tok = tok;
+  a.ws = (float*)workspace; a.logz = logz; a.tok_post = tok_post; a.start_mean = start_mean; a.start_sd = start_sd; a.status = status;
+  long off = 0;
+  std::vector<PostClip> by_cfg[5];
+  for (int b = 0; b < n_clips; ++b) {
+    const int T = n_frames_host[b], N = n_tok_host[b];
+    by_cfg[cfg_of(N)].push_back(PostClip{(long)frame_off_host[b], off, T, tok_off_host[b], N, b});
+    off += clip_floats(T, N);
+  }
+  for (int cfg = 0; cfg < 5; ++cfg) {
+    for (size_t i = 0; i < by_cfg[cfg].size(); i += POST_CLIPS_PER_LAUNCH) {
+      a.n = (int)std::min<size_t>(POST_CLIPS_PER_LAUNCH, by_cfg[cfg].size() - i);
+      for (int j = 0; j < a.n; ++j) a.clip[j] = by_cfg[cfg][i + j];
+      const int rc = launch(cfg, a, s);
+      if (rc) return rc;
+    }
+  }
+  return 0;
+}
+
+}  // extern "C"

@@ -478,12 +478,27 @@ class Labeler:
             raise ValueError(f"align must be one of {ALIGN_MODES}, got {mode!r}")
         return mode
 
-    def label_files(self, audio_paths, lang_id=None, confidence_threshold=0.0, verbose=True, align=None):
-        """-> list (per file) of [(start_s, end_s, phoneme)] after merge + forced alignment.
+    def align_scores_on(self, align_scores=None, align=None) -> bool:
+        """Whether alignment scores are asked for (None: config postprocess.align_scores, else off).  They score a Viterbi
+        alignment: with align "greedy" the request is an error."""
+        on = bool(self.config.get("postprocess", {}).get("align_scores", False) if align_scores is None else align_scores)
+        if on and self.align_mode(align) != "viterbi":
+            raise ValueError("align_scores needs align='viterbi' (postprocess.align: viterbi): the greedy match has no lattice to score")
+        return on
+
+    def label_files(self, audio_paths, lang_id=None, confidence_threshold=0.0, verbose=True, align=None, align_scores=None):
+        """-> list (per file) of [(start_s, end_s, phoneme)] after merge + forced alignment; with align_scores, (that list, scores).
 
         align: "greedy" -- a `{audio}.txt` transcript is matched onto the freely decoded segments (infer.py:30-60, 312-319);
         "viterbi" -- files with a transcript are aligned by a search over their frame logits on the GPU (align.py: one segment
-        per token, in order, none dropped); files without one take the greedy path unchanged.  None: config postprocess.align."""
+        per token, in order, none dropped); files without one take the greedy path unchanged.  None: config postprocess.align.
+
+        align_scores (with "viterbi" only; None: config postprocess.align_scores, else off): also return scores[i], an
+        align.FileScore from a forward-backward pass over the file's alignment lattice (per token the posterior of the run it got
+        and the spread of its start), or None for a file without a transcript or one that fell back to the greedy alignment (and,
+        with a message, for an aligned file whose path wfl_align_posterior does not accept: status 8, not expected from wfl_align's
+        own output).  The segments are the same with and without."""
+        want_scores = self.align_scores_on(align_scores, align)
         if lang_id is not None and self.lang2id and lang_id > max(self.lang2id.values()):
             raise ValueError(f"Error: Language ID ({lang_id}) is higher than the latest ID ({max(self.lang2id.values())}) "
                              f"of this model.\n Languages and Codes available: {self.lang2id}")
@@ -493,16 +508,22 @@ class Labeler:
             if with_t:
                 rest = [fi for fi in range(len(audio_paths)) if forced[fi] is None]
                 final = [None] * len(audio_paths)
+                scores = [None] * len(audio_paths)
                 if rest:
                     for fi, segs in zip(rest, self._label_files_greedy([audio_paths[fi] for fi in rest], lang_id, confidence_threshold,
                                                                         verbose)):
                         final[fi] = segs
                 got = self._label_viterbi([audio_paths[fi] for fi in with_t], [forced[fi] for fi in with_t], lang_id,
-                                          confidence_threshold, verbose)
+                                          confidence_threshold, verbose, want_scores)
+                if want_scores:
+                    got, got_scores = got
+                    for fi, sc in zip(with_t, got_scores):
+                        scores[fi] = sc
                 for fi, segs in zip(with_t, got):
                     final[fi] = segs
-                return final
-        return self._label_files_greedy(audio_paths, lang_id, confidence_threshold, verbose)
+                return (final, scores) if want_scores else final
+        final = self._label_files_greedy(audio_paths, lang_id, confidence_threshold, verbose)
+        return (final, [None] * len(final)) if want_scores else final
 
     def _label_files_greedy(self, audio_paths, lang_id, confidence_threshold, verbose):
         lang_name = self._lang_name(lang_id)
@@ -613,19 +634,20 @@ class Labeler:
             return min(T, -(-n * T // self.chunk_samples))
         return self.model.num_frames(n)
 
-    def _label_viterbi(self, audio_paths, transcripts, lang_id, threshold, verbose):
+    def _label_viterbi(self, audio_paths, transcripts, lang_id, threshold, verbose, want_scores=False):
         """Files with a transcript, align="viterbi".  Their chunks are forwarded with logits (kept on the device); the free decode of
         the same forward gives the greedy result, which the pause rule at the ends needs and which a file falls back to (with a
         message) when its transcript cannot be aligned.  Each file's chunks' valid logits rows are concatenated on the device, so
         one search covers the whole file; the files of a wave go to wfl_align as one ragged batch and only ids / tok / score / status
-        come back to the host."""
+        come back to the host.  want_scores: right after the search, one wfl_align_posterior call per wave over the clips it
+        aligned (same logits, the device `tok`), one more small copy to the host -> (results, [FileScore or None per file])."""
         from . import align as AL
         lang_name = self._lang_name(lang_id)
         remap, names = self._names_for(lang_name)
         mode = self.config["postprocess"]["merge_segments"]
         Bs = self.batch_size
         whisper = self.model.encoder_type == "whisper"
-        results = []
+        results, scores = [], []
         wave = getattr(self, "_wave_items", None) or max(8 * Bs, 64)
         from concurrent.futures import ThreadPoolExecutor
         pool = ThreadPoolExecutor(max_workers=max(1, min(16, os.cpu_count() or 1, len(audio_paths))))
@@ -700,13 +722,38 @@ class Labeler:
                 plans[fi] = alts
             # one ragged search over the files that can be aligned
             aligned = {}
+            post = {}                                         # file -> its FileScore (want_scores)
             run = [fi for fi in sel if fi in plans]
             if run:
                 frames = [sum(rows[(fi, ci)][0].shape[0] for ci in range(len(by_file[fi]))) for fi in run]
                 lg = torch.cat([rows[(fi, ci)][0] for fi in run for ci in range(len(by_file[fi]))])   # device-to-device
                 gaps = [AL.gap_classes(self.labels, transcripts[fi]) for fi in run]
-                d_ids, d_tok, _, d_st = AL.viterbi_align(lg, frames, [plans[fi] for fi in run], gaps, self.labels.index("O"))
+                packed = AL.pack_clips(lg, frames, [plans[fi] for fi in run], gaps) if want_scores else None
+                d_ids, d_tok, d_score, d_st = AL.viterbi_align(lg, frames, [plans[fi] for fi in run], gaps, self.labels.index("O"),
+                                                               packed=packed)
                 ids_all, tok_all, st_all = d_ids.cpu().numpy(), d_tok.cpu().numpy(), d_st.cpu().numpy()
+                raw = {}                                      # file -> (score, logz, tok_post, start_mean, start_sd)
+                bad_post = {}
+                ok = [b for b in range(len(run)) if st_all[b] == AL.STATUS_OK]
+                if want_scores and ok:
+                    f0 = np.concatenate([[0], np.cumsum(np.asarray(frames, np.int64))[:-1]])
+                    # (only the clips the search aligned; when that is all of them, on the tables the search was given)
+                    d_post = AL.alignment_posteriors(lg, [frames[b] for b in ok], [plans[run[b]] for b in ok], [gaps[b] for b in ok],
+                                                     self.labels.index("O"), d_tok, frame_offsets=f0[ok],
+                                                     packed=packed if len(ok) == len(run) else None)
+                    nt = sum(len(plans[run[b]]) for b in ok)
+                    h = torch.cat([d_score[ok], *d_post[:4], d_post[4].to(torch.float32)]).cpu().numpy()      # one copy
+                    n_ok = len(ok)
+                    h_score, h_logz, h_st = h[:n_ok], h[n_ok:2 * n_ok], h[2 * n_ok + 3 * nt:]
+                    k0 = 0
+                    for j, b in enumerate(ok):
+                        n = len(plans[run[b]])
+                        if h_st[j] != AL.STATUS_OK:
+                            bad_post[run[b]] = int(h_st[j])
+                        else:
+                            raw[run[b]] = (h_score[j], h_logz[j]) + tuple(h[2 * n_ok + q * nt + k0:2 * n_ok + q * nt + k0 + n]
+                                                                          for q in range(3))
+                        k0 += n
                 pos = 0
                 for b, fi in enumerate(run):
                     n = frames[b]
@@ -727,10 +774,15 @@ class Labeler:
                         segs = AL.path_segments(ids_all[pos:pos + n], tok_all[pos:pos + n], cf, co, cc, self._table, plans[fi], tr,
                                                 frame_duration)
                         aligned[fi] = AL.with_end_pauses(free_segs[fi], segs, tr)
+                        if fi in raw:
+                            post[fi] = AL.file_score(raw[fi][0], raw[fi][1], n, *raw[fi][2:], segs, frame_duration)
+                        elif want_scores:                     # (wfl_align_posterior refused the path wfl_align gave it)
+                            print(f"{audio_paths[fi]}: no alignment scores (wfl_align_posterior status {bad_post.get(fi)})")
                     pos += n
             for fi in sel:
                 results.append(aligned.get(fi, greedy[fi]))
-        return results
+                scores.append(post.get(fi))
+        return (results, scores) if want_scores else results
 
 
 def _read_forced(audio_path, verbose):
@@ -772,25 +824,83 @@ def _write_lab(path, segments):
     print(f"Predictions saved to: {path}")
 
 
+def _check_align_scores(align, align_scores):
+    if align_scores and align == "greedy":
+        raise ValueError("align_scores needs align='viterbi': the greedy match has no lattice to score")
+
+
+def _lab_int(t):
+    """The integer a .lab line carries for a time (the native formatter's truncating int(t * 1e7))."""
+    return int(npost.format_lab_tuples([(t, t, "x")]).split()[0])
+
+
+def format_scores_tsv(score) -> str:
+    """`{stem}.scores.tsv` of one Viterbi-aligned file (align.FileScore): a `#` header line with the file's figures, then one line
+    per transcript token, `start end token posterior start_sd_s start_shift_s`, start / end being the integers of the token's .lab
+    line."""
+    lines = [f"# path_log_posterior={score.path_log_posterior:.4f}\tmean_frame_logprob={score.mean_frame_logprob:.6f}\t"
+             f"mean_frame_logz={score.mean_frame_logz:.6f}\tmin_posterior={score.min_posterior:.6f}"]
+    for t in score.tokens:
+        lines.append(f"{_lab_int(t.start_s)}\t{_lab_int(t.end_s)}\t{t.token}\t{t.posterior:.6f}\t{t.start_sd_s:.4f}\t"
+                     f"{t.start_shift_s:+.4f}")
+    return "\n".join(lines) + "\n"
+
+
+def format_review_tsv(named_scores) -> str:
+    """`alignment_scores.tsv` of a folder: [(file name, FileScore)] -> one line per aligned file, the weakest first (ascending
+    min_posterior; ties by name): the review list."""
+    rows = sorted(named_scores, key=lambda r: (r[1].min_posterior, r[0]))
+    lines = ["# file\tmin_posterior\tpath_log_posterior\tmean_frame_logprob\tmean_frame_logz\ttokens"]
+    for name, sc in rows:
+        lines.append(f"{name}\t{sc.min_posterior:.6f}\t{sc.path_log_posterior:.4f}\t{sc.mean_frame_logprob:.6f}\t"
+                     f"{sc.mean_frame_logz:.6f}\t{len(sc.tokens)}")
+    return "\n".join(lines) + "\n"
+
+
+def _write_text(path, text, what):
+    d = os.path.dirname(path)
+    if d:
+        os.makedirs(d, exist_ok=True)
+    with open(path, "w", encoding="utf-8") as f:
+        f.write(text)
+    print(f"{what} saved to: {path}")
+
+
+def scores_path(lab_path):
+    return os.path.splitext(lab_path)[0] + ".scores.tsv"
+
+
 def infer_audio(audio_path, config_path="config.yaml", checkpoint_path="best_model.pt", output_lab_path=None, device="cuda",
-                lang_id=None, sample=False, top_k=0, top_p=0.0, temperature=1.0, confidence_threshold=0.0, align=None):
+                lang_id=None, sample=False, top_k=0, top_p=0.0, temperature=1.0, confidence_threshold=0.0, align=None,
+                align_scores=None):
     """align: "greedy" | "viterbi" | None (config postprocess.align, else greedy): how a `{audio}.txt` transcript is aligned
-    (Labeler.label_files)."""
+    (Labeler.label_files).  align_scores (viterbi only; None: config postprocess.align_scores): also write `{stem}.scores.tsv`
+    beside the .lab when the file was Viterbi-aligned (format_scores_tsv)."""
     _check_align(align)
+    _check_align_scores(align, align_scores)
     lab = _labeler(config_path, checkpoint_path, device)
-    segments = lab.label_files([audio_path], lang_id=lang_id, confidence_threshold=confidence_threshold, align=align)[0]
+    score = None
+    if lab.align_scores_on(align_scores, align):
+        segments, scores = lab.label_files([audio_path], lang_id=lang_id, confidence_threshold=confidence_threshold, align=align,
+                                           align_scores=True)
+        segments, score = segments[0], scores[0]
+    else:
+        segments = lab.label_files([audio_path], lang_id=lang_id, confidence_threshold=confidence_threshold, align=align)[0]
     if output_lab_path:
         if os.path.abspath(output_lab_path) == os.path.abspath(audio_path):
             # the reference would truncate the input WAV here (infer.py:410-411 + utils.py:77)
             output_lab_path = os.path.splitext(audio_path)[0] + ".lab"
         _write_lab(output_lab_path, segments)
+        if score is not None:
+            _write_text(scores_path(output_lab_path), format_scores_tsv(score), "Alignment scores")
     return segments
 
 
 def infer_folder(folder_path: str, config_path: str = "config.yaml", checkpoint_path: str = "best_model.pt",
                  output_dir: str = "outputs", device: str = "cuda", lang_id: int = None, sample=False, top_k=0, top_p=0.0,
-                 temperature=1.0, confidence_threshold=0.0, align=None):
+                 temperature=1.0, confidence_threshold=0.0, align=None, align_scores=None):
     _check_align(align)
+    _check_align_scores(align, align_scores)
     wav_files = sorted(f for f in os.listdir(folder_path) if f.lower().endswith(".wav"))
     os.makedirs(output_dir, exist_ok=True)
     # one process per GPU: every rank labels its own share of the files and writes its own .lab files (no collective)
@@ -801,13 +911,26 @@ def infer_folder(folder_path: str, config_path: str = "config.yaml", checkpoint_
         wav_files = [wav_files[i] for i in shard_items(sizes, world)[rank]]
     lab = _labeler(config_path, checkpoint_path, device)
     paths = [os.path.join(folder_path, f) for f in wav_files]
-    all_segments = lab.label_files(paths, lang_id=lang_id, confidence_threshold=confidence_threshold, align=align) if paths else []
-    for wav_file, segments in zip(wav_files, all_segments):
+    want_scores = lab.align_scores_on(align_scores, align)
+    all_scores = [None] * len(paths)
+    if want_scores and paths:
+        all_segments, all_scores = lab.label_files(paths, lang_id=lang_id, confidence_threshold=confidence_threshold, align=align,
+                                                   align_scores=True)
+    else:
+        all_segments = lab.label_files(paths, lang_id=lang_id, confidence_threshold=confidence_threshold, align=align) if paths else []
+    for wav_file, segments, score in zip(wav_files, all_segments, all_scores):
         print(f"\nInferencing: {wav_file}")
-        _write_lab(os.path.join(output_dir, os.path.splitext(wav_file)[0] + ".lab"), segments)
+        lab_path = os.path.join(output_dir, os.path.splitext(wav_file)[0] + ".lab")
+        _write_lab(lab_path, segments)
+        if score is not None:
+            _write_text(scores_path(lab_path), format_scores_tsv(score), "Alignment scores")
         print("Predicted segments:")
         for start, end, ph in segments:
             print(f"({round(start, 2)}, {round(end, 2)}, {ph})")
+    if want_scores:
+        name = "alignment_scores.tsv" if world == 1 else f"alignment_scores.rank{rank}.tsv"
+        _write_text(os.path.join(output_dir, name), format_review_tsv([(f, sc) for f, sc in zip(wav_files, all_scores) if sc is not None]),
+                    "Review list")
     return all_segments
 
 
@@ -831,7 +954,11 @@ def main(argv=None):
     @click.option("--align", "-a", type=click.Choice(ALIGN_MODES), default=None,
                   help="How a {audio}.txt transcript is aligned: greedy (string match) or viterbi (search over the logits, GPU). "
                        "Default: config postprocess.align, else greedy.")
-    def cli(path, checkpoint, config, output, lang_id, sample, top_k, top_p, temperature, device, confidence_threshold, align):
+    @click.option("--align-scores", "align_scores", is_flag=True, default=None,
+                  help="With viterbi: also write {stem}.scores.tsv beside each aligned .lab (per-token posteriors by forward-backward "
+                       "on the GPU) and, for a folder, alignment_scores.tsv. Default: config postprocess.align_scores, else off.")
+    def cli(path, checkpoint, config, output, lang_id, sample, top_k, top_p, temperature, device, confidence_threshold, align,
+            align_scores):
         if sample:
             if top_k <= 0 and top_p <= 0.0:
                 print("Sampling is enabled but neither --top-k nor --top-p is set.")
@@ -860,6 +987,10 @@ def main(argv=None):
             confidence_threshold = cfg["postprocess"].get("confidence_threshold", 0.0)
         if align is None:
             align = cfg["postprocess"].get("align", "greedy")
+        if align_scores is None:
+            align_scores = bool(cfg["postprocess"].get("align_scores", False))
+        if align_scores and align != "viterbi":
+            raise click.UsageError("--align-scores (postprocess.align_scores) needs --align viterbi")
         output_path = inf_path if output == "." else output
         if not inf_path.exists():
             print(f"Unable to locate folder {str(inf_path)}")
@@ -867,7 +998,8 @@ def main(argv=None):
         if lang_id is not None and lang_id <= -1:
             lang_id = None
         kw = dict(config_path=str(config), checkpoint_path=str(checkpoint), device=device, lang_id=lang_id, sample=sample,
-                  top_k=top_k, top_p=top_p, temperature=temperature, confidence_threshold=confidence_threshold, align=align)
+                  top_k=top_k, top_p=top_p, temperature=temperature, confidence_threshold=confidence_threshold, align=align,
+                  align_scores=align_scores)
         if inf_path.is_dir():
             infer_folder(folder_path=str(inf_path), output_dir=str(output_path), **kw)
         else:
