@@ -359,6 +359,31 @@ int32_t wfl_align_posterior(const float* logits, int64_t ldl, int32_t C, int32_t
                             const int32_t* gap_cls, int32_t n_clips, const int32_t* tok, void* workspace, int64_t workspace_bytes,
                             float* logz, float* tok_post, float* start_mean, float* start_sd, int32_t* status, void* stream);
 
+/* ---- BIO-grammar Viterbi decode of clips WITHOUT a transcript on the GPU (`postprocess.decode: viterbi`; wfl-asr_amd/decode.py).
+ * Stands beside the reference's free decode, infer.py:86-96, 164-174, 293-302 (per-frame argmax, confidence threshold, median filter
+ * over the ids, then the BIO decoder), which knows nothing of the grammar it decodes.  Clip b has T = n_frames_host[b] logits rows (row
+ * frame_off_host[b] + t, ld ldl, C fp32 columns).  pairs (device) holds n_pairs phonemes as (B class, I class or -1); o_id is the O
+ * class; every other class is never chosen.  A legal path is a class per frame with every I-p directly preceded by B-p or I-p; B-* and
+ * O may follow anything; the clip starts after a virtual O frame.  The path maximises
+ *     sum_t z[t][c_t] - lambda * (runs opened),     a run is opened by every B-p frame and by every O frame whose predecessor is not O.
+ * With d the previous frame's state scores, a = argmax d (the lowest class id wins a tie) and best = d[a]:
+ *     O   : z + (d[O] >= best - lambda ? d[O] : best - lambda)      B-p : z + best - lambda
+ *     I-p : z + (d[I-p] >= d[B-p] ? d[I-p] : d[B-p])                end state: the argmax of the last frame, lowest id on a tie.
+ * threshold > 0: a frame whose largest softmax probability (fp32) is below it can only be O.  lambda >= 0 is in nats.
+ * Outputs (device): ids[t] the path's class (same rows as the logits); score[b] the path's objective minus sum_t logsumexp z[t][.]
+ * (fp32; the search decides on the raw logits); status[b]: 0 ok, 2 C above 1024, 4 a class id of `pairs` outside [0, C) or a class used
+ * twice (o_id included).  A clip with status != 0 gets ids = o_id and score 0; T = 0 is ok and writes no ids.  One wave per clip: a clip
+ * decoded alone equals the same clip inside any batch, bit for bit.  fp32 state scores, renormalised every 16 frames (offset in double).
+ * Arguments are checked on the host (negative return): C >= 1, o_id in range, ldl >= C, counts and offsets >= 0, lambda and threshold
+ * >= 0, non-null pointers, workspace large enough.
+ * Workspace, per clip with T > 0, in 4-byte words: round_up_64(T (2 S + 1)) + 2 round_up_64(T)  (backpointers: 2 S words of I-p bits
+ * and one word a | O's bit << 16 per frame; the frames' log-sum-exp; their forced flags), S = 2 (n_pairs <= 128), 4 (<= 256),
+ * 8 (<= 512), 16 (<= 1024); 0 above.  wfl_decode_workspace_bytes returns the sum in bytes (28 bytes per frame at n_pairs <= 128). */
+int64_t wfl_decode_workspace_bytes(const int32_t* n_frames_host, int32_t n_clips, int32_t n_pairs);
+int32_t wfl_decode(const float* logits, int64_t ldl, int32_t C, int32_t o_id, const int64_t* frame_off_host, const int32_t* n_frames_host,
+                   int32_t n_clips, const int32_t* pairs, int32_t n_pairs, float lambda, float threshold, void* workspace,
+                   int64_t workspace_bytes, int32_t* ids, float* score, int32_t* status, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

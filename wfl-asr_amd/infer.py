@@ -30,6 +30,7 @@ from .tagger import BIOPhonemeTagger, raise_on_status
 frame_duration = pp.FRAME_DURATION
 MAX_SEGMENT_DURATION = pp.MAX_SEGMENT_DURATION
 ALIGN_MODES = ("greedy", "viterbi")
+DECODE_MODES = ("argmax", "viterbi")
 CHUNK_SAMPLES = int(MAX_SEGMENT_DURATION * 16000)     # at 16 kHz; a Labeler's own work-item length is `chunk_samples` (its config's rate)
 
 
@@ -486,7 +487,19 @@ class Labeler:
             raise ValueError("align_scores needs align='viterbi' (postprocess.align: viterbi): the greedy match has no lattice to score")
         return on
 
-    def label_files(self, audio_paths, lang_id=None, confidence_threshold=0.0, verbose=True, align=None, align_scores=None):
+    def decode_options(self, decode=None, switch_penalty=None):
+        """-> (mode, switch penalty in nats).  mode: "argmax" (the reference's free decode, the default) or "viterbi" (the BIO-grammar
+        search over the frame logits, decode.py); None: config postprocess.decode, else argmax.  switch_penalty: a number >= 0, used
+        with "viterbi" only; None: config postprocess.switch_penalty, else 0."""
+        from .decode import check_options
+        post = self.config.get("postprocess", {})
+        mode = post.get("decode", "argmax") if decode is None else decode
+        lam = post.get("switch_penalty", 0.0) if switch_penalty is None else switch_penalty
+        check_options(mode, lam)
+        return mode, float(lam)
+
+    def label_files(self, audio_paths, lang_id=None, confidence_threshold=0.0, verbose=True, align=None, align_scores=None,
+                    decode=None, switch_penalty=None):
         """-> list (per file) of [(start_s, end_s, phoneme)] after merge + forced alignment; with align_scores, (that list, scores).
 
         align: "greedy" -- a `{audio}.txt` transcript is matched onto the freely decoded segments (infer.py:30-60, 312-319);
@@ -497,8 +510,17 @@ class Labeler:
         align.FileScore from a forward-backward pass over the file's alignment lattice (per token the posterior of the run it got
         and the spread of its start), or None for a file without a transcript or one that fell back to the greedy alignment (and,
         with a message, for an aligned file whose path wfl_align_posterior does not accept: status 8, not expected from wfl_align's
-        own output).  The segments are the same with and without."""
+        own output).  The segments are the same with and without.
+
+        decode: "argmax" -- the free decode is the reference's (per-frame argmax, confidence threshold, median filter, BIO decoder);
+        "viterbi" -- every file whose segments come from the free decode (no transcript, or one under align "greedy", which is then
+        matched over the new segments) is decoded by the BIO-grammar search over its frame logits on the GPU (decode.py), each opened
+        run costing `switch_penalty` nats; postprocess.median_filter is not applied to those files.  None: config postprocess.decode /
+        postprocess.switch_penalty, else argmax / 0."""
         want_scores = self.align_scores_on(align_scores, align)
+        free = self.decode_options(decode, switch_penalty)
+        if free[0] == "viterbi" and int(self.config["postprocess"].get("median_filter", 0)) > 1:
+            print("decode: viterbi -- postprocess.median_filter is not applied (the switch penalty takes its place)")
         if lang_id is not None and self.lang2id and lang_id > max(self.lang2id.values()):
             raise ValueError(f"Error: Language ID ({lang_id}) is higher than the latest ID ({max(self.lang2id.values())}) "
                              f"of this model.\n Languages and Codes available: {self.lang2id}")
@@ -511,7 +533,7 @@ class Labeler:
                 scores = [None] * len(audio_paths)
                 if rest:
                     for fi, segs in zip(rest, self._label_files_greedy([audio_paths[fi] for fi in rest], lang_id, confidence_threshold,
-                                                                        verbose)):
+                                                                        verbose, *free)):
                         final[fi] = segs
                 got = self._label_viterbi([audio_paths[fi] for fi in with_t], [forced[fi] for fi in with_t], lang_id,
                                           confidence_threshold, verbose, want_scores)
@@ -522,10 +544,22 @@ class Labeler:
                 for fi, segs in zip(with_t, got):
                     final[fi] = segs
                 return (final, scores) if want_scores else final
-        final = self._label_files_greedy(audio_paths, lang_id, confidence_threshold, verbose)
+        final = self._label_files_greedy(audio_paths, lang_id, confidence_threshold, verbose, *free)
         return (final, [None] * len(final)) if want_scores else final
 
-    def _label_files_greedy(self, audio_paths, lang_id, confidence_threshold, verbose):
+    def _label_files_greedy(self, audio_paths, lang_id, confidence_threshold, verbose, decode="argmax", switch_penalty=0.0):
+        if decode == "viterbi":
+            # the free decode by the grammar search; a file it could not decode (with a message) takes the argmax decode below
+            got = self._decode_viterbi(audio_paths, lang_id, confidence_threshold, verbose, switch_penalty)
+            rest = [fi for fi in range(len(audio_paths)) if fi not in got]
+            final = [None] * len(audio_paths)
+            if rest:
+                for fi, segs in zip(rest, self._label_files_greedy([audio_paths[fi] for fi in rest], lang_id, confidence_threshold,
+                                                                    verbose)):
+                    final[fi] = segs
+            for fi, segs in got.items():
+                final[fi] = self._match_forced(audio_paths[fi], segs, verbose)
+            return final
         lang_name = self._lang_name(lang_id)
         decided_fast = {}                                 # file index -> segments of its one <= 30 s item, natively loaded
         if self.model.encoder_type == "whisper" and len(audio_paths) > 0:
@@ -607,18 +641,23 @@ class Labeler:
                 if mode != "none" and s.size:
                     s, e, ph = npost.merge_segments(s, e, ph, mode)
                 segs = npost.to_tuples(s, e, ph, names)
-            forced = _read_forced(path, verbose)
-            if forced is not None:
-                aligned = pp.align_phoneme_list(segs, forced)
-                if "SP" not in forced and "AP" not in forced and aligned:
-                    before = [s for s in segs if s[2] in ("SP", "AP") and s[1] <= aligned[0][0]]
-                    after = [s for s in segs if s[2] in ("SP", "AP") and s[0] >= aligned[-1][1]]
-                    segs = before + aligned + after
-                else:
-                    segs = aligned
-            final.append(segs)
+            final.append(self._match_forced(path, segs, verbose))
         return final
 
+    @staticmethod
+    def _match_forced(path, segs, verbose):
+        """The greedy string match of a `{audio}.txt` transcript onto freely decoded segments and the pause rule for the ends
+        (infer.py:30-60, 312-319); a file without a transcript keeps its segments."""
+        forced = _read_forced(path, verbose)
+        if forced is not None:
+            aligned = pp.align_phoneme_list(segs, forced)
+            if "SP" not in forced and "AP" not in forced and aligned:
+                before = [s for s in segs if s[2] in ("SP", "AP") and s[1] <= aligned[0][0]]
+                after = [s for s in segs if s[2] in ("SP", "AP") and s[0] >= aligned[-1][1]]
+                segs = before + aligned + after
+            else:
+                segs = aligned
+        return segs
 
     def _load_chunks(self, path):
         chunks = A.load_items(path, self.sr)            # native: decode, resample, normalise, 30 s chunks (csrc/hostpost.hip)
@@ -634,6 +673,105 @@ class Labeler:
             return min(T, -(-n * T // self.chunk_samples))
         return self.model.num_frames(n)
 
+    def _forward_with_logits(self, sel, by_file, lang_id, threshold):
+        """Forward the chunks of a wave of files (by_file[fi]: the file's chunks) with the logits kept on the device ->
+        (free, rows): (file, chunk) -> (ids, offsets) of the argmax decode as _forward_items returns them, and
+        (file, chunk) -> (device logits rows of the chunk's valid frames, their offsets)."""
+        Bs = self.batch_size
+        whisper = self.model.encoder_type == "whisper"
+        free, rows = {}, {}
+        order = [(fi, ci) for fi in sel for ci in range(len(by_file[fi]))]
+        if not whisper:
+            order.sort(key=lambda k: -len(by_file[k[0]][k[1]]))
+        for s0 in range(0, len(order), Bs):
+            part = order[s0:s0 + Bs]
+            xs = [by_file[fi][ci] for fi, ci in part]
+            L = self.chunk_samples if whisper else max(len(x) for x in xs)
+            host = np.zeros((len(xs) if not whisper else Bs, L), np.float32)
+            lens = np.zeros(host.shape[0], np.int32)
+            for r, x in enumerate(xs):
+                n = min(len(x), L)
+                host[r, :n] = x[:n]
+                lens[r] = n
+            same = (not whisper) and all(len(x) == L for x in xs)
+            res = self.model.label(torch.from_numpy(host).to(self.device), None if lang_id is None else [lang_id] * host.shape[0],
+                                   threshold=threshold, lens=None if same else lens, average_languages=lang_id is None,
+                                   want_logits=True)
+            raise_on_status(int(res.status.item()))
+            T = res.ids.shape[1]
+            ids_h, offs_h = res.ids.cpu().numpy(), res.offsets.cpu().numpy()
+            for r, (fi, ci) in enumerate(part):
+                tv = self._valid_frames(len(xs[r]), T)
+                keep = T if whisper else tv                # what the greedy loop decodes (_forward_items)
+                free[(fi, ci)] = (ids_h[r, :keep].copy(), offs_h[r, :keep].copy())
+                rows[(fi, ci)] = (res.logits[r, :tv], offs_h[r, :tv].copy())
+        return free, rows
+
+    def _decode_viterbi(self, audio_paths, lang_id, threshold, verbose, switch_penalty):
+        """decode="viterbi": the free decode of files by the BIO-grammar search (decode.py, wfl_decode) -> {file index: segments
+        [(start_s, end_s, phoneme)] after the merge-map names and merge_segments, before any string match}.  The files' chunks are
+        forwarded with logits (kept on the device); each file's chunks' valid logits rows are concatenated on the device, so one
+        search covers the whole file and a run may cross a chunk seam; the files of a wave go to wfl_decode as one ragged batch and
+        only ids / status come back to the host.  A file whose status is not 0 is left out (with a message): the caller decodes it
+        by argmax."""
+        from . import decode as DC
+        lang_name = self._lang_name(lang_id)
+        remap, names = self._names_for(lang_name)
+        mode = self.config["postprocess"]["merge_segments"]
+        table = getattr(self, "_decode_table", None)
+        if table is None:
+            table = self._decode_table = DC.class_table(self.labels)
+        wave = getattr(self, "_wave_items", None) or max(8 * self.batch_size, 64)
+        out = {}
+        if not audio_paths:
+            return out
+        from concurrent.futures import ThreadPoolExecutor
+        pool = ThreadPoolExecutor(max_workers=max(1, min(16, os.cpu_count() or 1, len(audio_paths))))
+        loads = [pool.submit(self._load_chunks, p) for p in audio_paths]      # (the native loader releases the GIL)
+        pool.shutdown(wait=False)
+        files = list(range(len(audio_paths)))
+        while files:
+            sel, by_file, n_chunks = [], {}, 0
+            while files and (not sel or n_chunks < wave):
+                fi = files.pop(0)
+                cs = loads[fi].result()
+                loads[fi] = None
+                if verbose and len(cs) > 1:
+                    print(f"Audio is too long ({sum(len(c) for c in cs)/self.sr:.1f}s), splitting...")
+                if not cs:                                    # no audio: no segments
+                    out[fi] = []
+                    continue
+                sel.append(fi)
+                by_file[fi] = list(cs)
+                n_chunks += len(cs)
+            if not sel:
+                continue
+            _, rows = self._forward_with_logits(sel, by_file, lang_id, threshold)
+            frames = [sum(rows[(fi, ci)][0].shape[0] for ci in range(len(by_file[fi]))) for fi in sel]
+            lg = torch.cat([rows[(fi, ci)][0] for fi in sel for ci in range(len(by_file[fi]))])       # device-to-device
+            d_ids, _, d_st = DC.bio_viterbi(lg, frames, table, switch_penalty, threshold)
+            ids_all, st_all = d_ids.cpu().numpy(), d_st.cpu().numpy()
+            pos = 0
+            for b, fi in enumerate(sel):
+                n = frames[b]
+                if st_all[b] != DC.STATUS_OK:
+                    print(f"{audio_paths[fi]}: viterbi decode not possible (wfl_decode status {int(st_all[b])}); using the argmax decode")
+                else:
+                    cf, co, cc, clock = [], [], [], 0.0
+                    for ci, x in enumerate(by_file[fi]):
+                        r, offs = rows[(fi, ci)]
+                        cf.append(r.shape[0])
+                        co.append(offs)
+                        cc.append(clock)
+                        clock += len(x) / self.sr
+                    s, e, ph = DC.path_segments_free(ids_all[pos:pos + n], cf, co, cc, self._table, frame_duration)
+                    ph = remap[ph] if ph.size else ph
+                    if mode != "none" and s.size:
+                        s, e, ph = npost.merge_segments(s, e, ph, mode)
+                    out[fi] = npost.to_tuples(s, e, ph, names)
+                pos += n
+        return out
+
     def _label_viterbi(self, audio_paths, transcripts, lang_id, threshold, verbose, want_scores=False):
         """Files with a transcript, align="viterbi".  Their chunks are forwarded with logits (kept on the device); the free decode of
         the same forward gives the greedy result, which the pause rule at the ends needs and which a file falls back to (with a
@@ -646,7 +784,6 @@ class Labeler:
         remap, names = self._names_for(lang_name)
         mode = self.config["postprocess"]["merge_segments"]
         Bs = self.batch_size
-        whisper = self.model.encoder_type == "whisper"
         results, scores = [], []
         wave = getattr(self, "_wave_items", None) or max(8 * Bs, 64)
         from concurrent.futures import ThreadPoolExecutor
@@ -665,36 +802,10 @@ class Labeler:
                     print(f"Audio is too long ({sum(len(c) for c in cs)/self.sr:.1f}s), splitting...")
                 sel.append(fi)
                 chunks.extend((fi, c) for c in cs)
-            free = {}                                         # (file, chunk) -> (ids, offsets) of the free decode
-            rows = {}                                         # (file, chunk) -> device logits rows of the chunk's valid frames
             by_file = {}
             for fi, c in chunks:
                 by_file.setdefault(fi, []).append(c)
-            order = [(fi, ci) for fi in sel for ci in range(len(by_file[fi]))]
-            if not whisper:
-                order.sort(key=lambda k: -len(by_file[k[0]][k[1]]))
-            for s0 in range(0, len(order), Bs):
-                part = order[s0:s0 + Bs]
-                xs = [by_file[fi][ci] for fi, ci in part]
-                L = self.chunk_samples if whisper else max(len(x) for x in xs)
-                host = np.zeros((len(xs) if not whisper else Bs, L), np.float32)
-                lens = np.zeros(host.shape[0], np.int32)
-                for r, x in enumerate(xs):
-                    n = min(len(x), L)
-                    host[r, :n] = x[:n]
-                    lens[r] = n
-                same = (not whisper) and all(len(x) == L for x in xs)
-                res = self.model.label(torch.from_numpy(host).to(self.device), None if lang_id is None else [lang_id] * host.shape[0],
-                                       threshold=threshold, lens=None if same else lens, average_languages=lang_id is None,
-                                       want_logits=True)
-                raise_on_status(int(res.status.item()))
-                T = res.ids.shape[1]
-                ids_h, offs_h = res.ids.cpu().numpy(), res.offsets.cpu().numpy()
-                for r, (fi, ci) in enumerate(part):
-                    tv = self._valid_frames(len(xs[r]), T)
-                    keep = T if whisper else tv                # what the greedy loop decodes (_forward_items)
-                    free[(fi, ci)] = (ids_h[r, :keep].copy(), offs_h[r, :keep].copy())
-                    rows[(fi, ci)] = (res.logits[r, :tv], offs_h[r, :tv].copy())
+            free, rows = self._forward_with_logits(sel, by_file, lang_id, threshold)
             # the greedy result of every file (free decode, merge, string match), as _label_files_greedy computes it
             greedy, free_segs, plans = {}, {}, {}
             for j, fi in enumerate(sel):
@@ -824,6 +935,11 @@ def _write_lab(path, segments):
     print(f"Predictions saved to: {path}")
 
 
+def _check_decode(decode, switch_penalty):
+    from .decode import check_options
+    check_options(decode, switch_penalty)
+
+
 def _check_align_scores(align, align_scores):
     if align_scores and align == "greedy":
         raise ValueError("align_scores needs align='viterbi': the greedy match has no lattice to score")
@@ -872,20 +988,24 @@ def scores_path(lab_path):
 
 def infer_audio(audio_path, config_path="config.yaml", checkpoint_path="best_model.pt", output_lab_path=None, device="cuda",
                 lang_id=None, sample=False, top_k=0, top_p=0.0, temperature=1.0, confidence_threshold=0.0, align=None,
-                align_scores=None):
+                align_scores=None, decode=None, switch_penalty=None):
     """align: "greedy" | "viterbi" | None (config postprocess.align, else greedy): how a `{audio}.txt` transcript is aligned
     (Labeler.label_files).  align_scores (viterbi only; None: config postprocess.align_scores): also write `{stem}.scores.tsv`
-    beside the .lab when the file was Viterbi-aligned (format_scores_tsv)."""
+    beside the .lab when the file was Viterbi-aligned (format_scores_tsv).  decode: "argmax" | "viterbi" | None (config
+    postprocess.decode, else argmax) and switch_penalty (nats, >= 0; None: config postprocess.switch_penalty, else 0): how the free
+    decode is made (Labeler.label_files)."""
     _check_align(align)
     _check_align_scores(align, align_scores)
+    _check_decode(decode, switch_penalty)
     lab = _labeler(config_path, checkpoint_path, device)
     score = None
+    free = dict(decode=decode, switch_penalty=switch_penalty)
     if lab.align_scores_on(align_scores, align):
         segments, scores = lab.label_files([audio_path], lang_id=lang_id, confidence_threshold=confidence_threshold, align=align,
-                                           align_scores=True)
+                                           align_scores=True, **free)
         segments, score = segments[0], scores[0]
     else:
-        segments = lab.label_files([audio_path], lang_id=lang_id, confidence_threshold=confidence_threshold, align=align)[0]
+        segments = lab.label_files([audio_path], lang_id=lang_id, confidence_threshold=confidence_threshold, align=align, **free)[0]
     if output_lab_path:
         if os.path.abspath(output_lab_path) == os.path.abspath(audio_path):
             # the reference would truncate the input WAV here (infer.py:410-411 + utils.py:77)
@@ -898,9 +1018,11 @@ def infer_audio(audio_path, config_path="config.yaml", checkpoint_path="best_mod
 
 def infer_folder(folder_path: str, config_path: str = "config.yaml", checkpoint_path: str = "best_model.pt",
                  output_dir: str = "outputs", device: str = "cuda", lang_id: int = None, sample=False, top_k=0, top_p=0.0,
-                 temperature=1.0, confidence_threshold=0.0, align=None, align_scores=None):
+                 temperature=1.0, confidence_threshold=0.0, align=None, align_scores=None, decode=None, switch_penalty=None):
     _check_align(align)
     _check_align_scores(align, align_scores)
+    _check_decode(decode, switch_penalty)
+    free = dict(decode=decode, switch_penalty=switch_penalty)
     wav_files = sorted(f for f in os.listdir(folder_path) if f.lower().endswith(".wav"))
     os.makedirs(output_dir, exist_ok=True)
     # one process per GPU: every rank labels its own share of the files and writes its own .lab files (no collective)
@@ -915,9 +1037,10 @@ def infer_folder(folder_path: str, config_path: str = "config.yaml", checkpoint_
     all_scores = [None] * len(paths)
     if want_scores and paths:
         all_segments, all_scores = lab.label_files(paths, lang_id=lang_id, confidence_threshold=confidence_threshold, align=align,
-                                                   align_scores=True)
+                                                   align_scores=True, **free)
     else:
-        all_segments = lab.label_files(paths, lang_id=lang_id, confidence_threshold=confidence_threshold, align=align) if paths else []
+        all_segments = lab.label_files(paths, lang_id=lang_id, confidence_threshold=confidence_threshold, align=align,
+                                       **free) if paths else []
     for wav_file, segments, score in zip(wav_files, all_segments, all_scores):
         print(f"\nInferencing: {wav_file}")
         lab_path = os.path.join(output_dir, os.path.splitext(wav_file)[0] + ".lab")
@@ -957,8 +1080,16 @@ def main(argv=None):
     @click.option("--align-scores", "align_scores", is_flag=True, default=None,
                   help="With viterbi: also write {stem}.scores.tsv beside each aligned .lab (per-token posteriors by forward-backward "
                        "on the GPU) and, for a folder, alignment_scores.tsv. Default: config postprocess.align_scores, else off.")
+    @click.option("--decode", "-dec", type=click.Choice(DECODE_MODES), default=None,
+                  help="How files are decoded freely (no transcript, or one under --align greedy): argmax (per-frame argmax and median "
+                       "filter) or viterbi (BIO-grammar search over the logits, GPU). Default: config postprocess.decode, else argmax.")
+    @click.option("--switch-penalty", "switch_penalty", type=float, default=None,
+                  help="With --decode viterbi: cost of every opened run, in nats (>= 0). Default: config postprocess.switch_penalty, "
+                       "else 0.")
     def cli(path, checkpoint, config, output, lang_id, sample, top_k, top_p, temperature, device, confidence_threshold, align,
-            align_scores):
+            align_scores, decode, switch_penalty):
+        if switch_penalty is not None and not switch_penalty >= 0.0:
+            raise click.UsageError("--switch-penalty must be >= 0 (nats)")
         if sample:
             if top_k <= 0 and top_p <= 0.0:
                 print("Sampling is enabled but neither --top-k nor --top-p is set.")
@@ -991,6 +1122,14 @@ def main(argv=None):
             align_scores = bool(cfg["postprocess"].get("align_scores", False))
         if align_scores and align != "viterbi":
             raise click.UsageError("--align-scores (postprocess.align_scores) needs --align viterbi")
+        if decode is None:
+            decode = cfg["postprocess"].get("decode", "argmax")
+        if switch_penalty is None:
+            switch_penalty = cfg["postprocess"].get("switch_penalty", 0.0)
+        try:
+            _check_decode(decode, switch_penalty)
+        except ValueError as err:
+            raise click.UsageError(f"postprocess.decode / postprocess.switch_penalty: {err}")
         output_path = inf_path if output == "." else output
         if not inf_path.exists():
             print(f"Unable to locate folder {str(inf_path)}")
@@ -999,7 +1138,7 @@ def main(argv=None):
             lang_id = None
         kw = dict(config_path=str(config), checkpoint_path=str(checkpoint), device=device, lang_id=lang_id, sample=sample,
                   top_k=top_k, top_p=top_p, temperature=temperature, confidence_threshold=confidence_threshold, align=align,
-                  align_scores=align_scores)
+                  align_scores=align_scores, decode=decode, switch_penalty=switch_penalty)
         if inf_path.is_dir():
             infer_folder(folder_path=str(inf_path), output_dir=str(output_path), **kw)
         else:
