@@ -5,6 +5,8 @@ from __future__ import annotations
 import ctypes as C
 import os
 
+import numpy as np
+
 PKG = os.path.dirname(os.path.abspath(__file__))
 # WFL_LIB_PATH: an alternative build of the same library (A/B runs of compiler flags: tools/build_variant.sh); never a fallback
 LIB_PATH = os.environ.get("WFL_LIB_PATH") or os.path.join(PKG, "libwfl_asr_hip.so")
@@ -106,6 +108,22 @@ def load():
         raise WflError("libwfl_asr_hip.so ABI version mismatch; rebuild")
     _lib = lib
     return lib
+
+
+def ptr(t):
+    """A device tensor's address for the C ABI (None: a null pointer)."""
+    return C.c_void_p(t.data_ptr()) if t is not None else None
+
+
+def host_ptr(a):
+    """A contiguous numpy array's address for the C ABI."""
+    return a.ctypes.data_as(C.c_void_p)
+
+
+def back_to_back(n_frames):
+    """The default `frame_offsets` of a ragged batch: the clips' rows one after the other (int64)."""
+    T = np.asarray(n_frames, np.int64).reshape(-1)
+    return np.concatenate([[0], np.cumsum(T)[:-1]]) if T.size else np.zeros(0, np.int64)
 
 
 def check(rc: int, what: str = ""):

@@ -24,6 +24,7 @@ import torch
 
 from . import _lib
 from . import native_post as npost
+from ._lib import back_to_back, host_ptr as _hp, ptr as _ptr
 
 MAX_TOKENS = 4096          # wfl_align's token cap per clip (status 2 above it)
 MAX_ALTERNATIVES = 4       # (B, I) pairs per token
@@ -34,15 +35,11 @@ STATUS_OK, STATUS_INFEASIBLE, STATUS_OVER_CAP, STATUS_BAD_CLASS = 0, 1, 2, 4
 STATUS_NOT_A_PATH = 8      # wfl_align_posterior alone: `tok` is not a path of the clip's lattice
 
 
-def _ptr(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else None
-
-
 def workspace_bytes(n_frames, n_tokens) -> int:
     lib = _lib.load()
     T = np.ascontiguousarray(n_frames, np.int32)
     N = np.ascontiguousarray(n_tokens, np.int32)
-    n = int(lib.wfl_align_workspace_bytes(T.ctypes.data_as(C.c_void_p), N.ctypes.data_as(C.c_void_p), T.size))
+    n = int(lib.wfl_align_workspace_bytes(_hp(T), _hp(N), T.size))
     if n < 0:
         raise _lib.WflError("wfl_align_workspace_bytes: negative frame or token count")
     return n
@@ -58,7 +55,7 @@ def _pack_clips(logits, n_frames, token_classes, gap_classes, frame_offsets):
     T = np.asarray(n_frames, np.int32).reshape(nb)
     N = np.array([len(t) for t in token_classes], np.int32)
     if frame_offsets is None:
-        frame_offsets = np.concatenate([[0], np.cumsum(T.astype(np.int64))[:-1]]) if nb else np.zeros(0, np.int64)
+        frame_offsets = back_to_back(T)
     F0 = np.ascontiguousarray(frame_offsets, np.int64).reshape(nb)
     K0 = np.concatenate([[0], np.cumsum(N.astype(np.int64))[:-1]]).astype(np.int32) if nb else np.zeros(0, np.int32)
     flat = [a for toks in token_classes for a in toks]
@@ -118,8 +115,7 @@ def viterbi_align(logits, n_frames, token_classes, gap_classes, o_id, frame_offs
     status = torch.empty(max(nb, 1), dtype=torch.int32, device=dev)
     with torch.cuda.device(dev):
         st = stream if stream is not None else torch.cuda.current_stream(dev)
-        hp = lambda a: a.ctypes.data_as(C.c_void_p)      # noqa: E731
-        rc = lib.wfl_align(_ptr(logits), logits.stride(0), logits.shape[1], int(o_id), hp(F0), hp(T), hp(K0), hp(N), _ptr(d_tc), _ptr(d_gc),
+        rc = lib.wfl_align(_ptr(logits), logits.stride(0), logits.shape[1], int(o_id), _hp(F0), _hp(T), _hp(K0), _hp(N), _ptr(d_tc), _ptr(d_gc),
                            nb, _ptr(ws), ws_n, _ptr(ids), _ptr(tok), _ptr(score), _ptr(status), C.c_void_p(st.cuda_stream))
         _lib.check(rc, "wfl_align")
         for t in (d_tc, d_gc, ws):
@@ -131,7 +127,7 @@ def posterior_workspace_bytes(n_frames, n_tokens) -> int:
     lib = _lib.load()
     T = np.ascontiguousarray(n_frames, np.int32)
     N = np.ascontiguousarray(n_tokens, np.int32)
-    n = int(lib.wfl_align_posterior_workspace_bytes(T.ctypes.data_as(C.c_void_p), N.ctypes.data_as(C.c_void_p), T.size))
+    n = int(lib.wfl_align_posterior_workspace_bytes(_hp(T), _hp(N), T.size))
     if n < 0:
         raise _lib.WflError("wfl_align_posterior_workspace_bytes: negative frame or token count")
     return n
@@ -162,8 +158,7 @@ def alignment_posteriors(logits, n_frames, token_classes, gap_classes, o_id, tok
     status = torch.empty(max(nb, 1), dtype=torch.int32, device=dev)
     with torch.cuda.device(dev):
         st = stream if stream is not None else torch.cuda.current_stream(dev)
-        hp = lambda a: a.ctypes.data_as(C.c_void_p)      # noqa: E731
-        rc = lib.wfl_align_posterior(_ptr(logits), logits.stride(0), logits.shape[1], int(o_id), hp(F0), hp(T), hp(K0), hp(N),
+        rc = lib.wfl_align_posterior(_ptr(logits), logits.stride(0), logits.shape[1], int(o_id), _hp(F0), _hp(T), _hp(K0), _hp(N),
                                      _ptr(d_tc), _ptr(d_gc), nb, _ptr(tok), _ptr(ws), ws_n, _ptr(logz), _ptr(per_tok[0]),
                                      _ptr(per_tok[1]), _ptr(per_tok[2]), _ptr(status), C.c_void_p(st.cuda_stream))
         _lib.check(rc, "wfl_align_posterior")

@@ -1,6 +1,6 @@
 // Viterbi forced alignment of a phoneme transcript over the frame logits of a clip (wfl_align, include/wfl_asr.h).
 //
-// Replaces the greedy string match of /root/reference/infer.py:30-60 (run at 193, 210-215, 312-319) when the caller asks for
+// Replaces the greedy string match of the reference's infer.py:30-60 (run at 193, 210-215, 312-319) when the caller asks for
 // `postprocess.align: viterbi`: the search spells exactly the transcript, in order, one contiguous run of frames per token.
 //
 // States of a clip with N tokens: G_0, B_0, I_0, G_1, ..., B_{N-1}, I_{N-1}, G_N  (G_k = 3k, B_k = 3k+1, I_k = 3k+2, G_N = 3N).
@@ -21,27 +21,18 @@
 //   of at most ALIGN_W / R + 2 threads: the block loads such a window into LDS in one go and thread 0 walks ALIGN_W frames out of
 //   LDS, T / ALIGN_W memory round trips in all.  The per-frame states go to `tok`, then every thread turns its frames into
 //   (class id, token) and adds up its frames' log-sum-exp for the score.
-#include "common.h"
+//
+// The lattice itself -- caps, configurations, the shared LDS layout, setup and status codes, the logits stage ring, emissions, the
+// renormalisation halves, and the host side of a ragged batch -- is csrc/lattice.h, shared with csrc/align_posterior.hip.  Here: the
+// max-product recursion, the backpointers and the backtrace.
+#include "lattice.h"
 #include "wfl_asr.h"
-
-#include <math.h>
-
-#include <algorithm>
-#include <vector>
 
 namespace {
 
-constexpr int ALIGN_MAX_TOKENS = 4096;
-constexpr int ALIGN_MAX_CLASSES = 1024;
-constexpr int ALIGN_W = 32;                 // backtrace window, frames
-constexpr int ALIGN_CLIPS_PER_LAUNCH = 64;  // the clip table travels in the kernel arguments
-constexpr int ALIGN_NGAP = 8;
+using namespace lattice;
 
-struct AlignClip {
-  long frame_off;  // first logits row of the clip
-  long bp_off;     // backpointer words of the clip in the workspace
-  int T, tok_off, N, clip;
-};
+constexpr int ALIGN_W = 32;                 // backtrace window, frames
 
 struct AlignLaunch {
   const float* logits;
@@ -49,41 +40,23 @@ struct AlignLaunch {
   int C, o_id;
   const int* tok_cls;  // [total tokens][4][2]
   const int* gap_cls;  // [n_clips][8]
-  unsigned* bp;
+  unsigned* bp;        // LatClip::ws_off: the clip's backpointer words
   int* ids;
   int* tok;
   float* score;
   int* status;
   int n;
-  AlignClip clip[ALIGN_CLIPS_PER_LAUNCH];
+  LatClip clip[CLIPS_PER_LAUNCH];
 };
 
 template <int NT, int R>
-struct Cfg {
+struct Cfg : LdsBase<NT, R, 2 * NT * 8> {                // its own between alt and wmax: the neighbour exchange, [2][NT] float2
   static constexpr int WPT = (6 * R + 31) / 32;          // backpointer words per thread per frame
-  static constexpr int PR = NT >= 512 ? 8 : 16;          // staged logits values per thread
-  static constexpr int NW = NT / 64;
   static constexpr int WIN = ALIGN_W * (ALIGN_W / R + 2) * WPT;
-  static constexpr int OFF_ALT = 2 * NT * PR * 4;                  // ring: two stages of NT PR floats
-  static constexpr int OFF_XCH = OFF_ALT + NT * R * 16;            // alternatives: one int4 (B | I << 16, -1 unused) per slot
-  static constexpr int OFF_WMAX = OFF_XCH + 2 * NT * 8;            // neighbour exchange: [2][NT] float2
-  static constexpr int OFF_RED = OFF_WMAX + 64;                    // per-wave maxima (renormalisation)
-  static constexpr int OFF_WIN = OFF_RED + 8 * 16;                 // per-wave double sums
+  static constexpr int OFF_WIN = Cfg::OFF_OWN;           // the backtrace window
   static constexpr int OFF_MISC = OFF_WIN + WIN * 4;
   static constexpr int LDS = OFF_MISC + 64;
 };
-
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
-  return v;
-}
-
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
 
 template <int NT, int R>
 __global__ __launch_bounds__(NT) void align_kernel(AlignLaunch a) {
@@ -91,14 +64,14 @@ __global__ __launch_bounds__(NT) void align_kernel(AlignLaunch a) {
   extern __shared__ __attribute__((aligned(16))) char lds[];
   float* ring = (float*)lds;
   int4* alt = (int4*)(lds + K::OFF_ALT);
-  float2* xch = (float2*)(lds + K::OFF_XCH);
+  float2* xch = (float2*)(lds + K::OFF_X);
   float* wmax = (float*)(lds + K::OFF_WMAX);
   double* red = (double*)(lds + K::OFF_RED);
   unsigned* win = (unsigned*)(lds + K::OFF_WIN);
   int* misc = (int*)(lds + K::OFF_MISC);
   float* fin = (float*)(misc + 4);
 
-  const AlignClip cl = a.clip[blockIdx.x];
+  const LatClip cl = a.clip[blockIdx.x];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int T = cl.T, N = cl.N, C = a.C;
   const float* Z = a.logits + cl.frame_off * a.ldl;
@@ -106,47 +79,8 @@ __global__ __launch_bounds__(NT) void align_kernel(AlignLaunch a) {
   int* tokp = a.tok + cl.frame_off;
   const float NEG = -INFINITY;
 
-  int st = 0;
-  if (N > NT * R - 1 || N > ALIGN_MAX_TOKENS) st = 2;
-  else if (T < N) st = 1;
-  int g[ALIGN_NGAP];
-  if (st == 0) {
-    if (tid == 0) misc[0] = 0;
-    __syncthreads();
-    bool bad = false;
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-      const int k = tid * R + r;
-      int4 v = make_int4(-1, -1, -1, -1);          // the used alternatives first
-      if (k < N) {
-        const int* tc = a.tok_cls + (long)(cl.tok_off + k) * 8;
-        int n = 0;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          const int b = tc[2 * j], i = tc[2 * j + 1];
-          if (b == -1 && i == -1) continue;                        // an unused alternative
-          if (b < 0 || b >= C || i < 0 || i >= C) { bad = true; continue; }
-          const int pk = b | (i << 16);
-          if (n == 0) v.x = pk; else if (n == 1) v.y = pk; else if (n == 2) v.z = pk; else v.w = pk;
-          ++n;
-        }
-        if (n == 0) bad = true;
-      }
-      alt[k] = v;
-    }
-    int ng = 0;
-#pragma unroll
-    for (int j = 0; j < ALIGN_NGAP; ++j) {
-      g[j] = a.gap_cls[(long)cl.clip * ALIGN_NGAP + j];
-      if (g[j] == -1) continue;
-      if (g[j] < 0 || g[j] >= C) { bad = true; g[j] = -1; }
-      else ++ng;
-    }
-    if (ng == 0) bad = true;
-    if (bad) misc[0] = 1;
-    __syncthreads();
-    if (misc[0]) st = 4;
-  }
+  int g[NGAP];
+  const int st = lattice_setup<NT, R>(cl, C, a.tok_cls, a.gap_cls, alt, misc, g);
   if (st != 0 || T == 0) {
     for (int t = tid; t < T; t += NT) { ids[t] = a.o_id; tokp[t] = -1; }
     if (tid == 0) { a.score[cl.clip] = 0.f; a.status[cl.clip] = st; }
@@ -154,44 +88,23 @@ __global__ __launch_bounds__(NT) void align_kernel(AlignLaunch a) {
   }
 
   // ---- forward pass
-  const int F = min(32, NT * K::PR / C);       // rows per stage (C <= ALIGN_MAX_CLASSES <= NT PR: F >= 1)
-  const int SE = F * C;
-  int rc[K::PR];                               // (row << 16 | column) of this thread's staged values inside a stage, -1 none
-#pragma unroll
-  for (int i = 0; i < K::PR; ++i) {
-    const int e = tid + i * NT;
-    rc[i] = e < SE ? ((e / C) << 16) | (e % C) : -1;
-  }
-  float pre[K::PR];
-  auto load_stage = [&](int c) {
-    const int t0 = c * F;
-#pragma unroll
-    for (int i = 0; i < K::PR; ++i) {
-      const int row = t0 + (rc[i] >> 16);
-      pre[i] = (rc[i] >= 0 && row < T) ? Z[(long)row * a.ldl + (rc[i] & 0xffff)] : 0.f;
-    }
-  };
-  auto store_stage = [&](int c) {
-    float* h = ring + (c & 1) * NT * K::PR;
-#pragma unroll
-    for (int i = 0; i < K::PR; ++i)
-      if (rc[i] >= 0) h[tid + i * NT] = pre[i];
-  };
+  LogitStages<NT, K::PR> stage(Z, a.ldl, T, C, ring);
+  const int F = stage.F;
 
   float G[R], B[R], I[R];
 #pragma unroll
   for (int r = 0; r < R; ++r) G[r] = B[r] = I[r] = NEG;
   if (tid == 0) G[0] = 0.f;                    // a virtual frame -1 in G_0: frame 0 starts in G_0 or B_0
   xch[NT + tid] = make_float2(NEG, NEG);
-  load_stage(0);
-  store_stage(0);
-  load_stage(1);
+  stage.load(0);
+  stage.store(0);
+  stage.load(1);
   __syncthreads();
 
   int4 av[R];                                   // this thread's slots' alternatives, for the whole forward pass
 #pragma unroll
   for (int r = 0; r < R; ++r) av[r] = alt[tid * R + r];
-  unsigned* bp = a.bp + cl.bp_off;
+  unsigned* bp = a.bp + cl.ws_off;
   double acc = 0.0;                            // what the renormalisations subtracted
   float sub = 0.f;
   int c = 0, tin = 0;
@@ -199,15 +112,12 @@ __global__ __launch_bounds__(NT) void align_kernel(AlignLaunch a) {
     if (tin == F) {
       ++c;
       tin = 0;
-      store_stage(c);
+      stage.store(c);
       __syncthreads();
-      load_stage(c + 1);
+      stage.load(c + 1);
     }
-    const float* row = ring + (c & 1) * NT * K::PR + tin * C;
-    float eg = NEG;
-#pragma unroll
-    for (int j = 0; j < ALIGN_NGAP; ++j)
-      if (g[j] >= 0) eg = fmaxf(eg, row[g[j]]);
+    const float* row = stage.row(c, tin);
+    const float eg = gap_emission(row, g);
     float2 nb = tid > 0 ? xch[((t + 1) & 1) * NT + tid - 1] : make_float2(NEG, NEG);
     nb.x -= sub;
     nb.y -= sub;
@@ -227,15 +137,7 @@ __global__ __launch_bounds__(NT) void align_kernel(AlignLaunch a) {
       unsigned ci = 0;
       if (B[r] > mi) { mi = B[r]; ci = 1; }
       float eb = NEG, ei = NEG;
-      if (k < N) {
-        const int p[4] = {av[r].x, av[r].y, av[r].z, av[r].w};
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          if (p[j] < 0) break;
-          eb = fmaxf(eb, row[p[j] & 0xffff]);
-          ei = fmaxf(ei, row[p[j] >> 16]);
-        }
-      }
+      if (k < N) tok_emission(row, av[r], eb, ei);
       G[r] = k <= N ? m + eg : NEG;
       B[r] = m + eb;
       I[r] = mi + ei;
@@ -247,20 +149,17 @@ __global__ __launch_bounds__(NT) void align_kernel(AlignLaunch a) {
     unsigned* bw = bp + ((long)t * NT + tid) * K::WPT;
 #pragma unroll
     for (int w = 0; w < K::WPT; ++w) bw[w] = bits[w];
-    const bool renorm = (t & 15) == 15;
+    const bool renorm = (t & (RENORM - 1)) == RENORM - 1;
     if (renorm) {
       float lm = NEG;
 #pragma unroll
       for (int r = 0; r < R; ++r) lm = fmaxf(lm, fmaxf(G[r], fmaxf(B[r], I[r])));
-      lm = wave_max(lm);
-      if (lane == 0) wmax[wave] = lm;
+      renorm_publish(lm, wmax);
     }
-    __syncthreads();
+    __syncthreads();                           // the neighbour exchange and the renormalisation share it
     sub = 0.f;
     if (renorm) {
-      float M = wmax[0];
-#pragma unroll
-      for (int w = 1; w < K::NW; ++w) M = fmaxf(M, wmax[w]);
+      const float M = renorm_max<K::NW>(wmax);   // (taken as it is; the posterior sweeps replace an M of -inf by 0)
 #pragma unroll
       for (int r = 0; r < R; ++r) { G[r] -= M; B[r] -= M; I[r] -= M; }
       sub = M;
@@ -269,12 +168,7 @@ __global__ __launch_bounds__(NT) void align_kernel(AlignLaunch a) {
   }
 
   // ---- the best end state
-#pragma unroll
-  for (int r = 0; r < R; ++r) {
-    const int k = tid * R + r;
-    if (k == N) fin[0] = G[r];
-    if (k == N - 1) { fin[1] = I[r]; fin[2] = B[r]; }
-  }
+  publish_end_states<R>(N, G, B, I, fin);
   __syncthreads();
   float best = 0.f;
   if (tid == 0) {
@@ -335,16 +229,12 @@ __global__ __launch_bounds__(NT) void align_kernel(AlignLaunch a) {
     const int k = sv / 3, j = sv - 3 * k;
     int id = a.o_id, tk = -1;
     if (j != 0 && k < N) {
-      const int4 v = alt[k];
-      const int p[4] = {v.x, v.y, v.z, v.w};
       float bv = NEG;
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        if (p[q] < 0) break;
-        const int col = j == 2 ? p[q] >> 16 : p[q] & 0xffff;
+      for_each_alt(alt[k], [&](int q, int b, int i) {      // the arg-max alternative's class, the first on a tie
+        const int col = j == 2 ? i : b;
         const float x = z[col];
         if (q == 0 || x > bv) { bv = x; id = col; }
-      }
+      });
       tk = k;
     }
     ids[t] = id;
@@ -361,45 +251,12 @@ __global__ __launch_bounds__(NT) void align_kernel(AlignLaunch a) {
   }
 }
 
-// configuration by token count: (threads, slots per thread); NT R - 1 >= N
-constexpr int kCfgMaxN[5] = {127, 511, 1023, 2047, ALIGN_MAX_TOKENS};
-constexpr int kCfgWords[5] = {64 * Cfg<64, 2>::WPT, 256 * Cfg<256, 2>::WPT, 256 * Cfg<256, 4>::WPT, 256 * Cfg<256, 8>::WPT,
-                              512 * Cfg<512, 9>::WPT};
-static_assert(64 * 2 - 1 >= 127 && 256 * 2 - 1 >= 511 && 256 * 4 - 1 >= 1023 && 256 * 8 - 1 >= 2047 && 512 * 9 - 1 >= 4096, "slots");
-
-int cfg_of(int N) {
-  for (int c = 0; c < 5; ++c)
-    if (N <= kCfgMaxN[c]) return c;
-  return -1;
-}
-
+// backpointer words of a clip.  Over the cap, with fewer frames than tokens or with no frame the kernel stops at its status: no words.
 long clip_words(int T, int N) {
   const int c = cfg_of(N);
-  if (c < 0 || T < N || T <= 0) return 0;
-  return ((long)T * kCfgWords[c] + 63) / 64 * 64;      // (256-byte aligned)
-}
-
-template <int NT, int R>
-int launch_cfg(const AlignLaunch& a, hipStream_t s) {
-  auto k = align_kernel<NT, R>;
-  constexpr int lds = Cfg<NT, R>::LDS;
-  static WflOncePerDevice attr_once;
-  if (attr_once.need()) {
-    if (hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess)
-      return wfl_fail(-2, "wfl_align: cannot reserve the kernel's LDS");
-  }
-  hipLaunchKernelGGL(k, dim3(a.n), dim3(NT), lds, s, a);
-  return hipGetLastError() == hipSuccess ? 0 : wfl_fail(-3, "wfl_align: launch failed");
-}
-
-int launch(int cfg, const AlignLaunch& a, hipStream_t s) {
-  switch (cfg) {
-    case 0: return launch_cfg<64, 2>(a, s);
-    case 1: return launch_cfg<256, 2>(a, s);
-    case 2: return launch_cfg<256, 4>(a, s);
-    case 3: return launch_cfg<256, 8>(a, s);
-    default: return launch_cfg<512, 9>(a, s);
-  }
+  if (c == NCFG || T < N || T <= 0) return 0;
+  const int per_frame = dispatch_cfg(c, [](auto sh) { return decltype(sh)::NT * Cfg<decltype(sh)::NT, decltype(sh)::R>::WPT; });
+  return round64((long)T * per_frame);      // (256-byte aligned)
 }
 
 }  // namespace
@@ -407,59 +264,38 @@ int launch(int cfg, const AlignLaunch& a, hipStream_t s) {
 extern "C" {
 
 int64_t wfl_align_workspace_bytes(const int32_t* n_frames_host, const int32_t* n_tok_host, int32_t n_clips) {
-  if (n_clips < 0 || (n_clips > 0 && (!n_frames_host || !n_tok_host))) return -1;
-  int64_t words = 0;
-  for (int b = 0; b < n_clips; ++b) {
-    if (n_frames_host[b] < 0 || n_tok_host[b] < 0) return -1;
-    words += clip_words(n_frames_host[b], n_tok_host[b]);
-  }
-  return words * 4;
+  return clips_workspace_bytes(n_frames_host, n_tok_host, n_clips, clip_words);
 }
 
 int32_t wfl_align(const float* logits, int64_t ldl, int32_t C, int32_t o_id, const int64_t* frame_off_host, const int32_t* n_frames_host,
                   const int32_t* tok_off_host, const int32_t* n_tok_host, const int32_t* tok_cls, const int32_t* gap_cls, int32_t n_clips,
                   void* workspace, int64_t workspace_bytes, int32_t* ids, int32_t* tok, float* score, int32_t* status, void* stream) {
-  if (C < 1 || C > ALIGN_MAX_CLASSES) return wfl_fail(-1, "wfl_align: C must be 1 .. 1024");
-  if (o_id < 0 || o_id >= C) return wfl_fail(-1, "wfl_align: o_id out of range");
-  if (ldl < C) return wfl_fail(-1, "wfl_align: ldl < C");
-  if (n_clips < 0) return wfl_fail(-1, "wfl_align: n_clips < 0");
-  if (n_clips == 0) return 0;
-  if (!frame_off_host || !n_frames_host || !tok_off_host || !n_tok_host)
-    return wfl_fail(-1, "wfl_align: null host array");
+  const char* fn = "wfl_align";
   const int64_t need = wfl_align_workspace_bytes(n_frames_host, n_tok_host, n_clips);
-  if (need < 0) return wfl_fail(-1, "wfl_align: negative frame or token count");
   bool any_tok = false, any_frame = false;
-  for (int b = 0; b < n_clips; ++b) {
-    if (frame_off_host[b] < 0 || tok_off_host[b] < 0) return wfl_fail(-1, "wfl_align: negative offset");
-    any_tok |= n_tok_host[b] > 0;
-    any_frame |= n_frames_host[b] > 0;
-  }
+  int rc = check_clip_args(fn, C, o_id, ldl, frame_off_host, n_frames_host, tok_off_host, n_tok_host, n_clips, need, any_tok, any_frame);
+  if (rc || n_clips == 0) return rc;
   if (!score || !status || !gap_cls || (any_tok && !tok_cls) || (any_frame && (!logits || !ids || !tok)))
-    return wfl_fail(-1, "wfl_align: null device pointer");
-  if (workspace_bytes < need || (need > 0 && !workspace))
-    return wfl_fail(-1, "wfl_align: workspace too small (wfl_align_workspace_bytes)");
+    return fail(fn, -1, "null device pointer");
+  if ((rc = check_workspace(fn, need, workspace, workspace_bytes))) return rc;
   hipStream_t s = (hipStream_t)stream;
   AlignLaunch a{};
   a.logits = logits; a.ldl = ldl; a.C = C; a.o_id = o_id; a.tok_cls = tok_cls; a.gap_cls = gap_cls;
   a.bp = (unsigned*)workspace; a.ids = ids; a.tok = tok; a.score = score; a.status = status;
-  long off = 0;
-  std::vector<AlignClip> by_cfg[5];
-  for (int b = 0; b < n_clips; ++b) {
-    const int T = n_frames_host[b], N = n_tok_host[b];
-    int cfg = cfg_of(N);
-    if (cfg < 0) cfg = 0;                       // over the cap: the kernel reports status 2
-    by_cfg[cfg].push_back(AlignClip{(long)frame_off_host[b], off, T, tok_off_host[b], N, b});
-    off += clip_words(T, N);
-  }
-  for (int cfg = 0; cfg < 5; ++cfg) {
-    for (size_t i = 0; i < by_cfg[cfg].size(); i += ALIGN_CLIPS_PER_LAUNCH) {
-      a.n = (int)std::min<size_t>(ALIGN_CLIPS_PER_LAUNCH, by_cfg[cfg].size() - i);
-      for (int j = 0; j < a.n; ++j) a.clip[j] = by_cfg[cfg][i + j];
-      const int rc = launch(cfg, a, s);
-      if (rc) return rc;
-    }
-  }
-  return 0;
+  return launch_clips<NCFG>(
+      a, n_clips,
+      [&](int b, long off, LatClip& c, int& cfg) {
+        const int T = n_frames_host[b], N = n_tok_host[b];
+        c = LatClip{(long)frame_off_host[b], off, T, tok_off_host[b], N, b};
+        cfg = cfg_of(N) < NCFG ? cfg_of(N) : 0;   // over the cap: every kernel reports status 2 before it touches the workspace; the smallest
+        return clip_words(T, N);
+      },
+      [&](int cfg, const AlignLaunch& a) {
+        return dispatch_cfg(cfg, [&](auto sh) {
+          constexpr int NT = decltype(sh)::NT, R = decltype(sh)::R;
+          return launch_cfg<align_kernel<NT, R>, NT, Cfg<NT, R>::LDS>(fn, a, s);
+        });
+      });
 }
 
 }  // extern "C"

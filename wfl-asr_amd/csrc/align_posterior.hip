@@ -2,7 +2,10 @@
 // include/wfl_asr.h).  The sum-product twin of csrc/align.hip; the reference has no counterpart (it reports no confidence for its
 // string match).
 //
-// Lattice, emissions, start / end states and caps are wfl_align's (states G_k = 3k, B_k = 3k + 1, I_k = 3k + 2):
+// Lattice, emissions, start / end states and caps are wfl_align's, and so is their code: csrc/lattice.h holds the caps, the
+// configurations, the shared LDS layout, lattice setup with its status codes, the logits stage ring, the emission gathers, the
+// renormalisation halves and the host side of a ragged batch.  Here: the sum-product sweeps, the status-8 check of `tok`, the
+// checkpoint workspace and the per-token outputs.  States G_k = 3k, B_k = 3k + 1, I_k = 3k + 2:
 //   alpha_t(G_k) = EG_t + lse(alpha_{t-1}(G_k), alpha_{t-1}(I_{k-1}), alpha_{t-1}(B_{k-1}))      alpha_t(B_k): the same sum + EB_t(k)
 //   alpha_t(I_k) = EI_t(k) + lse(alpha_{t-1}(I_k), alpha_{t-1}(B_k))
 //   beta_{t-1}(G_k) = lse(beta_t(G_k) + EG_t, beta_t(B_k) + EB_t(k))
@@ -10,7 +13,7 @@
 //   logZ = lse(alpha_{T-1}(G_N), alpha_{T-1}(I_{N-1}), alpha_{T-1}(B_{N-1})),   gamma_t(s) = exp(alpha_t(s) + beta_t(s) - logZ).
 // beta of B_k and I_k are equal (same successors), so the backward sweep carries two values per token.
 //
-// One workgroup per clip, configurations and slot ownership as align_kernel: thread i owns the token slots i R .. i R + R - 1 in
+// One workgroup per clip, configurations and slot ownership from lattice.h: thread i owns the token slots i R .. i R + R - 1 in
 // registers.  Per frame one float2 crosses between neighbouring threads through LDS, one barrier per frame: the forward sweep takes
 // (alpha(B), alpha(I)) of the last slot of thread i - 1, the backward sweep (beta(G), beta(B)) of the first slot of thread i + 1 (the
 // emission of that slot's B state is gathered by thread i itself, from the staged row).  Every per-token output is accumulated by
@@ -24,31 +27,17 @@
 //
 // The per-frame log-sum-exp of the logits is computed once (double, expf), stored in fp32 and subtracted from the gathered logits;
 // what the fp32 rounding of it loses is summed in double and given back to logZ (it is common to every path).
-#include "common.h"
+#include "lattice.h"
 #include "wfl_asr.h"
 
 #include <limits.h>
-#include <math.h>
-
-#include <algorithm>
-#include <vector>
 
 namespace {
 
-constexpr int POST_MAX_TOKENS = 4096;
-constexpr int POST_MAX_CLASSES = 1024;
-constexpr int POST_W = 128;                // frames per recomputed block (a multiple of the renormalisation period)
-constexpr int POST_RENORM = 16;
-constexpr int POST_CLIPS_PER_LAUNCH = 64;  // the clip table travels in the kernel arguments
-constexpr int POST_NGAP = 8;
-constexpr int POST_FMAX = 32;              // staged rows per stage, at most
-static_assert(POST_W % POST_RENORM == 0, "a block ends on a renormalisation");
+using namespace lattice;
 
-struct PostClip {
-  long frame_off;  // first logits row of the clip
-  long ws_off;     // the clip's workspace, in floats
-  int T, tok_off, N, clip;
-};
+constexpr int POST_W = 128;                // frames per recomputed block (a multiple of the renormalisation period)
+static_assert(POST_W % RENORM == 0, "a block ends on a renormalisation");
 
 struct PostLaunch {
   const float* logits;
@@ -57,17 +46,15 @@ struct PostLaunch {
   const int* tok_cls;  // [total tokens][4][2]
   const int* gap_cls;  // [n_clips][8]
   const int* tok;      // wfl_align's output, same rows as the logits
-  float* ws;
+  float* ws;           // LatClip::ws_off: the clip's workspace, in floats
   float* logz;
   float* tok_post;
   float* start_mean;
   float* start_sd;
   int* status;
   int n;
-  PostClip clip[POST_CLIPS_PER_LAUNCH];
+  LatClip clip[CLIPS_PER_LAUNCH];
 };
-
-__host__ __device__ constexpr long round64(long x) { return (x + 63) / 64 * 64; }
 
 // a clip's workspace in floats: [lse: round64(T)] [checkpoint offsets: round64(2 nblk)] [checkpoints: nblk S] [block: POST_W S]
 struct PostLayout {
@@ -83,34 +70,17 @@ struct PostLayout {
 };
 
 template <int NT, int R>
-struct PCfg {
-  static constexpr int PR = NT >= 512 ? 8 : 16;          // staged logits values per thread
-  static constexpr int NW = NT / 64;
+struct PCfg : LdsBase<NT, R, NT * R * 4 + 2 * 2 * NT * 8> {       // its own between alt and wmax: first[] and the two neighbour exchanges
   static constexpr long S = (long)NT * R * 3;            // floats of one frame's alpha (and of one checkpoint)
-  static constexpr int OFF_ALT = 2 * NT * PR * 4;                  // ring: two stages of NT PR floats
-  static constexpr int OFF_FIRST = OFF_ALT + NT * R * 16;          // alternatives: one int4 (B | I << 16, -1 unused) per slot
-  static constexpr int OFF_XF = OFF_FIRST + NT * R * 4;            // first frame of every token's Viterbi run
-  static constexpr int OFF_XB = OFF_XF + 2 * NT * 8;               // forward neighbour exchange: [2][NT] float2
-  static constexpr int OFF_WMAX = OFF_XB + 2 * NT * 8;             // backward neighbour exchange
-  static constexpr int OFF_RED = OFF_WMAX + 64;                    // per-wave maxima (renormalisation)
-  static constexpr int OFF_OFFA = OFF_RED + 8 * 16;                // per-wave double sums, logZ
-  static constexpr int OFF_LRING = OFF_OFFA + POST_W * 8;          // alpha's offset of every frame of the block (double)
-  static constexpr int OFF_TRING = OFF_LRING + 2 * POST_FMAX * 4;  // staged rows' log-sum-exp
-  static constexpr int OFF_MISC = OFF_TRING + 2 * POST_FMAX * 4;   // staged rows' Viterbi token
+  static constexpr int OFF_FIRST = PCfg::OFF_X;                    // first frame of every token's Viterbi run
+  static constexpr int OFF_XF = OFF_FIRST + NT * R * 4;            // forward neighbour exchange: [2][NT] float2
+  static constexpr int OFF_XB = OFF_XF + 2 * NT * 8;               // backward neighbour exchange
+  static constexpr int OFF_OFFA = PCfg::OFF_OWN;                   // alpha's offset of every frame of the block (double)
+  static constexpr int OFF_LRING = OFF_OFFA + POST_W * 8;          // staged rows' log-sum-exp
+  static constexpr int OFF_TRING = OFF_LRING + 2 * FMAX * 4;       // staged rows' Viterbi token
+  static constexpr int OFF_MISC = OFF_TRING + 2 * FMAX * 4;
   static constexpr int LDS = OFF_MISC + 64;
 };
-
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
-  return v;
-}
-
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
 
 // log(exp a + exp b [+ exp c]); -inf in, -inf out (v_exp_f32 / v_log_f32)
 __device__ __forceinline__ float lae2(float a, float b) {
@@ -142,58 +112,20 @@ __global__ __launch_bounds__(NT) void post_kernel(PostLaunch a) {
   int* misc = (int*)(lds + K::OFF_MISC);
   float* fin = (float*)(misc + 4);
 
-  const PostClip cl = a.clip[blockIdx.x];
+  const LatClip cl = a.clip[blockIdx.x];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int T = cl.T, N = cl.N, C = a.C;
   const float* Z = a.logits + cl.frame_off * a.ldl;
   const int* tokp = a.tok + cl.frame_off;
   const float NEG = -INFINITY;
 
-  int st = 0;
-  if (N > NT * R - 1 || N > POST_MAX_TOKENS) st = 2;
-  else if (T < N) st = 1;
-  int g[POST_NGAP];
-  if (st == 0) {
-    if (tid == 0) misc[0] = 0;
-    __syncthreads();
-    bool bad = false;
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-      const int k = tid * R + r;
-      int4 v = make_int4(-1, -1, -1, -1);          // the used alternatives first
-      if (k < N) {
-        const int* tc = a.tok_cls + (long)(cl.tok_off + k) * 8;
-        int n = 0;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          const int b = tc[2 * j], i = tc[2 * j + 1];
-          if (b == -1 && i == -1) continue;                        // an unused alternative
-          if (b < 0 || b >= C || i < 0 || i >= C) { bad = true; continue; }
-          const int pk = b | (i << 16);
-          if (n == 0) v.x = pk; else if (n == 1) v.y = pk; else if (n == 2) v.z = pk; else v.w = pk;
-          ++n;
-        }
-        if (n == 0) bad = true;
-      }
-      alt[k] = v;
-      first[k] = INT_MAX;
-    }
-    int ng = 0;
-#pragma unroll
-    for (int j = 0; j < POST_NGAP; ++j) {
-      g[j] = a.gap_cls[(long)cl.clip * POST_NGAP + j];
-      if (g[j] == -1) continue;
-      if (g[j] < 0 || g[j] >= C) { bad = true; g[j] = -1; }
-      else ++ng;
-    }
-    if (ng == 0) bad = true;
-    if (bad) misc[0] = 1;
-    __syncthreads();
-    if (misc[0]) st = 4;
-    __syncthreads();                           // every thread has read the flag before the next phase may raise it again
-  }
+  int g[NGAP];
+  int st = lattice_setup<NT, R>(cl, C, a.tok_cls, a.gap_cls, alt, misc, g);
   if (st == 0 && T > 0) {
     // the first frame of every token's Viterbi run; a tok that is not a path of this lattice (a token missing, a value out of range)
+#pragma unroll
+    for (int r = 0; r < R; ++r) first[tid * R + r] = INT_MAX;
+    __syncthreads();                           // (and every thread has read setup's flag before this phase may raise it again)
     bool bad = false;
     for (int t = tid; t < T; t += NT) {
       const int k = tokp[t];
@@ -246,37 +178,22 @@ __global__ __launch_bounds__(NT) void post_kernel(PostLaunch a) {
 #pragma unroll
   for (int w = 0; w < K::NW; ++w) lres += red[w];
 
-  // ---- staging of the logits rows (with their log-sum-exp and Viterbi token): stage c = rows c F .. c F + F - 1
-  const int F = min(POST_FMAX, NT * K::PR / C);       // rows per stage (C <= POST_MAX_CLASSES <= NT PR: F >= 1)
-  const int SE = F * C;
-  int rc[K::PR];                               // (row << 16 | column) of this thread's staged values inside a stage, -1 none
-#pragma unroll
-  for (int i = 0; i < K::PR; ++i) {
-    const int e = tid + i * NT;
-    rc[i] = e < SE ? ((e / C) << 16) | (e % C) : -1;
-  }
-  float pre[K::PR];
+  // ---- staging of the logits rows, with their log-sum-exp and Viterbi token
+  LogitStages<NT, K::PR> stage(Z, a.ldl, T, C, ring);
+  const int F = stage.F;
   float pre_l = 0.f;
   int pre_t = -1;
-  auto load_stage = [&](int c) {
-    const int t0 = c * F;
-#pragma unroll
-    for (int i = 0; i < K::PR; ++i) {
-      const int row = t0 + (rc[i] >> 16);
-      pre[i] = (rc[i] >= 0 && c >= 0 && row < T) ? Z[(long)row * a.ldl + (rc[i] & 0xffff)] : 0.f;
-    }
-    const bool in = tid < F && c >= 0 && t0 + tid < T;
-    pre_l = in ? lse[t0 + tid] : 0.f;
-    pre_t = in ? tokp[t0 + tid] : -1;
+  auto load_stage = [&](int c) {               // (the backward sweep runs one stage ahead as well, down to c = -1)
+    stage.load(c, c >= 0);
+    const bool in = tid < F && c >= 0 && c * F + tid < T;
+    pre_l = in ? lse[c * F + tid] : 0.f;
+    pre_t = in ? tokp[c * F + tid] : -1;
   };
   auto store_stage = [&](int c) {
-    float* h = ring + (c & 1) * NT * K::PR;
-#pragma unroll
-    for (int i = 0; i < K::PR; ++i)
-      if (rc[i] >= 0) h[tid + i * NT] = pre[i];
+    stage.store(c);
     if (tid < F) {
-      lring[(c & 1) * POST_FMAX + tid] = pre_l;
-      tring[(c & 1) * POST_FMAX + tid] = pre_t;
+      lring[(c & 1) * FMAX + tid] = pre_l;
+      tring[(c & 1) * FMAX + tid] = pre_t;
     }
   };
 
@@ -284,24 +201,6 @@ __global__ __launch_bounds__(NT) void post_kernel(PostLaunch a) {
 #pragma unroll
   for (int r = 0; r < R; ++r) av[r] = alt[tid * R + r];
   const int4 avn = tid + 1 < NT ? alt[(tid + 1) * R] : make_int4(-1, -1, -1, -1);   // the next thread's first slot
-  auto gap_emission = [&](const float* row) {
-    float eg = NEG;
-#pragma unroll
-    for (int j = 0; j < POST_NGAP; ++j)
-      if (g[j] >= 0) eg = fmaxf(eg, row[g[j]]);
-    return eg;
-  };
-  auto tok_emission = [&](const float* row, const int4& v, float& eb, float& ei) {
-    const int p[4] = {v.x, v.y, v.z, v.w};
-    eb = NEG;
-    ei = NEG;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      if (p[j] < 0) break;
-      eb = fmaxf(eb, row[p[j] & 0xffff]);
-      ei = fmaxf(ei, row[p[j] >> 16]);
-    }
-  };
 
   // ---- the forward sweep over frames t0 .. t1 - 1, from the clip's start (t0 = 0) or from checkpoint t0 / POST_W
   float G[R], B[R], I[R];
@@ -338,9 +237,9 @@ __global__ __launch_bounds__(NT) void post_kernel(PostLaunch a) {
         __syncthreads();
         load_stage(c + 1);
       }
-      const float* row = ring + (c & 1) * NT * K::PR + tin * C;
-      const float l = lring[(c & 1) * POST_FMAX + tin];
-      const float eg = gap_emission(row) - l;
+      const float* row = stage.row(c, tin);
+      const float l = lring[(c & 1) * FMAX + tin];
+      const float eg = gap_emission(row, g) - l;
       float2 nb = tid > 0 ? xf[((t + 1) & 1) * NT + tid - 1] : make_float2(NEG, NEG);
       nb.x -= sub;
       nb.y -= sub;
@@ -362,21 +261,18 @@ __global__ __launch_bounds__(NT) void post_kernel(PostLaunch a) {
         I[r] = ii + ei;
       }
       xf[(t & 1) * NT + tid] = make_float2(B[R - 1], I[R - 1]);
-      const bool renorm = (t & (POST_RENORM - 1)) == POST_RENORM - 1;
+      const bool renorm = (t & (RENORM - 1)) == RENORM - 1;
       if (renorm) {
         float lm = NEG;
 #pragma unroll
         for (int r = 0; r < R; ++r) lm = fmaxf(lm, fmaxf(G[r], fmaxf(B[r], I[r])));
-        lm = wave_max(lm);
-        if (lane == 0) wmax[wave] = lm;
+        renorm_publish(lm, wmax);
       }
-      __syncthreads();
+      __syncthreads();                         // the neighbour exchange and the renormalisation share it
       sub = 0.f;
       if (renorm) {
-        float M = wmax[0];
-#pragma unroll
-        for (int w = 1; w < K::NW; ++w) M = fmaxf(M, wmax[w]);
-        if (!(M > NEG)) M = 0.f;
+        float M = renorm_max<K::NW>(wmax);
+        if (!(M > NEG)) M = 0.f;               // every state -inf (or a NaN): subtract nothing (wfl_align's search takes M as it is)
 #pragma unroll
         for (int r = 0; r < R; ++r) { G[r] -= M; B[r] -= M; I[r] -= M; }
         sub = M;
@@ -406,12 +302,7 @@ __global__ __launch_bounds__(NT) void post_kernel(PostLaunch a) {
 
   // ---- sweep 1: alpha over the whole clip, checkpoints, logZ
   forward(0, T, false);
-#pragma unroll
-  for (int r = 0; r < R; ++r) {
-    const int k = tid * R + r;
-    if (k == N) fin[0] = G[r];
-    if (k == N - 1) { fin[1] = I[r]; fin[2] = B[r]; }
-  }
+  publish_end_states<R>(N, G, B, I, fin);
   __syncthreads();
   if (tid == 0) {
     const int ne = N >= 1 ? 3 : 1;
@@ -468,9 +359,9 @@ __global__ __launch_bounds__(NT) void post_kernel(PostLaunch a) {
         __syncthreads();
         load_stage(c - 1);
       }
-      const float* row = ring + (c & 1) * NT * K::PR + tin * C;
-      const float l = lring[(c & 1) * POST_FMAX + tin];
-      const int tk = tring[(c & 1) * POST_FMAX + tin];
+      const float* row = stage.row(c, tin);
+      const float l = lring[(c & 1) * FMAX + tin];
+      const int tk = tring[(c & 1) * FMAX + tin];
 #pragma unroll
       for (int r = 0; r < R; ++r) { ac[r][0] = an[r][0]; ac[r][1] = an[r][1]; ac[r][2] = an[r][2]; }
       if (t > t_lo) load_alpha(t - 1 - t_lo);  // one frame ahead of its use
@@ -491,7 +382,7 @@ __global__ __launch_bounds__(NT) void post_kernel(PostLaunch a) {
       }
       if (t == 0) break;
       // beta_{t-1}
-      const float eg = gap_emission(row) - l;
+      const float eg = gap_emission(row, g) - l;
       float eb[R], ei[R];
 #pragma unroll
       for (int r = 0; r < R; ++r) {
@@ -523,20 +414,17 @@ __global__ __launch_bounds__(NT) void post_kernel(PostLaunch a) {
         bX[r] = k < N ? x : NEG;
       }
       xb[(t & 1) * NT + tid] = make_float2(bG[0], bX[0]);
-      const bool renorm = (t & (POST_RENORM - 1)) == 0;
+      const bool renorm = (t & (RENORM - 1)) == 0;
       if (renorm) {
         float lm = NEG;
 #pragma unroll
         for (int r = 0; r < R; ++r) lm = fmaxf(lm, fmaxf(bG[r], bX[r]));
-        lm = wave_max(lm);
-        if (lane == 0) wmax[wave] = lm;
+        renorm_publish(lm, wmax);
       }
       __syncthreads();
       subb = 0.f;
       if (renorm) {
-        float M = wmax[0];
-#pragma unroll
-        for (int w = 1; w < K::NW; ++w) M = fmaxf(M, wmax[w]);
+        float M = renorm_max<K::NW>(wmax);
         if (!(M > NEG)) M = 0.f;
 #pragma unroll
         for (int r = 0; r < R; ++r) { bG[r] -= M; bX[r] -= M; }
@@ -564,44 +452,14 @@ __global__ __launch_bounds__(NT) void post_kernel(PostLaunch a) {
   }
 }
 
-// configuration by token count: (threads, slots per thread); NT R - 1 >= N  (align_kernel's)
-constexpr int kCfgMaxN[5] = {127, 511, 1023, 2047, POST_MAX_TOKENS};
-constexpr long kCfgS[5] = {PCfg<64, 2>::S, PCfg<256, 2>::S, PCfg<256, 4>::S, PCfg<256, 8>::S, PCfg<512, 9>::S};
-static_assert(64 * 2 - 1 >= 127 && 256 * 2 - 1 >= 511 && 256 * 4 - 1 >= 1023 && 256 * 8 - 1 >= 2047 && 512 * 9 - 1 >= 4096, "slots");
-
-int cfg_of(int N) {
-  for (int c = 0; c < 5; ++c)
-    if (N <= kCfgMaxN[c]) return c;
-  return 4;                                     // over the cap: the kernel reports status 2; sized as the cap, so the need is monotone
-}
+// over the cap the kernel reports status 2; such a clip is sized (and launched) as the cap's configuration, so the workspace need is
+// monotone in N -- wfl_align instead gives it no workspace, its words being zero for every clip it does not search
+int post_cfg(int N) { return std::min(cfg_of(N), NCFG - 1); }
 
 long clip_floats(int T, int N) {
   if (T <= 0) return 0;
-  return round64(PostLayout(T, kCfgS[cfg_of(N)]).total);     // (256-byte aligned)
-}
-
-template <int NT, int R>
-int launch_cfg(const PostLaunch& a, hipStream_t s) {
-  auto k = post_kernel<NT, R>;
-  constexpr int lds = PCfg<NT, R>::LDS;
-  static_assert(lds <= 160 * 1024, "LDS");
-  static WflOncePerDevice attr_once;
-  if (attr_once.need()) {
-    if (hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess)
-      return wfl_fail(-2, "wfl_align_posterior: cannot reserve the kernel's LDS");
-  }
-  hipLaunchKernelGGL(k, dim3(a.n), dim3(NT), lds, s, a);
-  return hipGetLastError() == hipSuccess ? 0 : wfl_fail(-3, "wfl_align_posterior: launch failed");
-}
-
-int launch(int cfg, const PostLaunch& a, hipStream_t s) {
-  switch (cfg) {
-    case 0: return launch_cfg<64, 2>(a, s);
-    case 1: return launch_cfg<256, 2>(a, s);
-    case 2: return launch_cfg<256, 4>(a, s);
-    case 3: return launch_cfg<256, 8>(a, s);
-    default: return launch_cfg<512, 9>(a, s);
-  }
+  const long S = dispatch_cfg(post_cfg(N), [](auto sh) { return PCfg<decltype(sh)::NT, decltype(sh)::R>::S; });
+  return round64(PostLayout(T, S).total);     // (256-byte aligned)
 }
 
 }  // namespace
@@ -609,58 +467,39 @@ int launch(int cfg, const PostLaunch& a, hipStream_t s) {
 extern "C" {
 
 int64_t wfl_align_posterior_workspace_bytes(const int32_t* n_frames_host, const int32_t* n_tok_host, int32_t n_clips) {
-  if (n_clips < 0 || (n_clips > 0 && (!n_frames_host || !n_tok_host))) return -1;
-  int64_t words = 0;
-  for (int b = 0; b < n_clips; ++b) {
-    if (n_frames_host[b] < 0 || n_tok_host[b] < 0) return -1;
-    words += clip_floats(n_frames_host[b], n_tok_host[b]);
-  }
-  return words * 4;
+  return clips_workspace_bytes(n_frames_host, n_tok_host, n_clips, clip_floats);
 }
 
 int32_t wfl_align_posterior(const float* logits, int64_t ldl, int32_t C, int32_t o_id, const int64_t* frame_off_host,
                             const int32_t* n_frames_host, const int32_t* tok_off_host, const int32_t* n_tok_host, const int32_t* tok_cls,
                             const int32_t* gap_cls, int32_t n_clips, const int32_t* tok, void* workspace, int64_t workspace_bytes,
                             float* logz, float* tok_post, float* start_mean, float* start_sd, int32_t* status, void* stream) {
-  if (C < 1 || C > POST_MAX_CLASSES) return wfl_fail(-1, "wfl_align_posterior: C must be 1 .. 1024");
-  if (o_id < 0 || o_id >= C) return wfl_fail(-1, "wfl_align_posterior: o_id out of range");
-  if (ldl < C) return wfl_fail(-1, "wfl_align_posterior: ldl < C");
-  if (n_clips < 0) return wfl_fail(-1, "wfl_align_posterior: n_clips < 0");
-  if (n_clips == 0) return 0;
-  if (!frame_off_host || !n_frames_host || !tok_off_host || !n_tok_host)
-    return wfl_fail(-1, "wfl_align_posterior: null host array");
+  const char* fn = "wfl_align_posterior";
   const int64_t need = wfl_align_posterior_workspace_bytes(n_frames_host, n_tok_host, n_clips);
-  if (need < 0) return wfl_fail(-1, "wfl_align_posterior: negative frame or token count");
   bool any_tok = false, any_frame = false;
-  for (int b = 0; b < n_clips; ++b) {
-    if (frame_off_host[b] < 0 || tok_off_host[b] < 0) return wfl_fail(-1, "wfl_align_posterior: negative offset");
-    any_tok |= n_tok_host[b] > 0;
-    any_frame |= n_frames_host[b] > 0;
-  }
+  int rc = check_clip_args(fn, C, o_id, ldl, frame_off_host, n_frames_host, tok_off_host, n_tok_host, n_clips, need, any_tok, any_frame);
+  if (rc || n_clips == 0) return rc;
   if (!logz || !status || !gap_cls || (any_tok && (!tok_cls || !tok_post || !start_mean || !start_sd)) || (any_frame && (!logits || !tok)))
-    return wfl_fail(-1, "wfl_align_posterior: null device pointer");
-  if (workspace_bytes < need || (need > 0 && !workspace))
-    return wfl_fail(-1, "wfl_align_posterior: workspace too small (wfl_align_posterior_workspace_bytes)");
+    return fail(fn, -1, "null device pointer");
+  if ((rc = check_workspace(fn, need, workspace, workspace_bytes))) return rc;
   hipStream_t s = (hipStream_t)stream;
   PostLaunch a{};
   a.logits = logits; a.ldl = ldl; a.C = C; a.tok_cls = tok_cls; a.gap_cls = gap_cls; a.tok = tok;
   a.ws = (float*)workspace; a.logz = logz; a.tok_post = tok_post; a.start_mean = start_mean; a.start_sd = start_sd; a.status = status;
-  long off = 0;
-  std::vector<PostClip> by_cfg[5];
-  for (int b = 0; b < n_clips; ++b) {
-    const int T = n_frames_host[b], N = n_tok_host[b];
-    by_cfg[cfg_of(N)].push_back(PostClip{(long)frame_off_host[b], off, T, tok_off_host[b], N, b});
-    off += clip_floats(T, N);
-  }
-  for (int cfg = 0; cfg < 5; ++cfg) {
-    for (size_t i = 0; i < by_cfg[cfg].size(); i += POST_CLIPS_PER_LAUNCH) {
-      a.n = (int)std::min<size_t>(POST_CLIPS_PER_LAUNCH, by_cfg[cfg].size() - i);
-      for (int j = 0; j < a.n; ++j) a.clip[j] = by_cfg[cfg][i + j];
-      const int rc = launch(cfg, a, s);
-      if (rc) return rc;
-    }
-  }
-  return 0;
+  return launch_clips<NCFG>(
+      a, n_clips,
+      [&](int b, long off, LatClip& c, int& cfg) {
+        const int T = n_frames_host[b], N = n_tok_host[b];
+        c = LatClip{(long)frame_off_host[b], off, T, tok_off_host[b], N, b};
+        cfg = post_cfg(N);
+        return clip_floats(T, N);
+      },
+      [&](int cfg, const PostLaunch& a) {
+        return dispatch_cfg(cfg, [&](auto sh) {
+          constexpr int NT = decltype(sh)::NT, R = decltype(sh)::R;
+          return launch_cfg<post_kernel<NT, R>, NT, PCfg<NT, R>::LDS>(fn, a, s);
+        });
+      });
 }
 
 }  // extern "C"

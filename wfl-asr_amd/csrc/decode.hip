@@ -18,18 +18,18 @@
 // align.hip), so the fp32 scores do not grow with T.
 // Backpointers: per frame 2 S words of I-p bits (one __ballot per slot), and one word a | (O's bit << 16).  Backtrace: lane 0 walks
 // windows of DECODE_W frames that the wave stages into LDS.
-#include "common.h"
+// From csrc/lattice.h (the alignment kernels' header) come only the class cap, the clips-per-launch constant, round64, wave_sum and
+// the host's clip-table batching and workspace check; the kernels here share nothing with the lattice.
+#include "lattice.h"
 #include "wfl_asr.h"
-
-#include <math.h>
-
-#include <algorithm>
 
 namespace {
 
-constexpr int DECODE_MAX_CLASSES = 1024;
+using lattice::CLIPS_PER_LAUNCH;
+using lattice::MAX_CLASSES;
+using lattice::round64;
+
 constexpr int DECODE_W = 32;                 // backtrace window, frames
-constexpr int DECODE_CLIPS_PER_LAUNCH = 64;  // the clip table travels in the kernel arguments
 constexpr int NO_CLASS = 0x7fffffff;
 
 struct DecodeClip {
@@ -50,10 +50,8 @@ struct DecodeLaunch {
   float* score;
   int* status;
   int n, fill_status;
-  DecodeClip clip[DECODE_CLIPS_PER_LAUNCH];
+  DecodeClip clip[CLIPS_PER_LAUNCH];
 };
-
-__host__ __device__ inline long round64(long v) { return (v + 63) / 64 * 64; }
 
 // workspace of a clip, in words: [backpointers T (2 S + 1)] [lse T] [forced T], each rounded up to 64 words
 __host__ __device__ inline long off_lse(int T, int S) { return round64((long)T * (2 * S + 1)); }
@@ -92,12 +90,6 @@ __device__ __forceinline__ void wave_best(float& v, int& c) {
   }
 }
 
-__device__ __forceinline__ double wave_sum_d(double v) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
-
 // ---- per frame: log-sum-exp and the forced-to-O flag.  grid (ceil(max T / 4), clips), 4 waves per block, one wave per frame.
 __global__ __launch_bounds__(256) void decode_pre_kernel(DecodeLaunch a, int S) {
   const DecodeClip cl = a.clip[blockIdx.y];
@@ -131,8 +123,8 @@ __global__ __launch_bounds__(64) void decode_fill_kernel(DecodeLaunch a) {
 template <int S, int D>
 __global__ __launch_bounds__(64) void decode_chain_kernel(DecodeLaunch a) {
   constexpr int WPF = 2 * S + 1;              // backpointer words per frame
-  __shared__ unsigned used[DECODE_MAX_CLASSES / 32];
-  __shared__ int info[DECODE_MAX_CLASSES];    // class -> pair | kind << 16 (kind 0 O, 1 B, 2 I); -1 never chosen
+  __shared__ unsigned used[MAX_CLASSES / 32];
+  __shared__ int info[MAX_CLASSES];    // class -> pair | kind << 16 (kind 0 O, 1 B, 2 I); -1 never chosen
   __shared__ unsigned win[DECODE_W * WPF];
   __shared__ int wout[DECODE_W];
   __shared__ int sh_s;
@@ -144,8 +136,8 @@ __global__ __launch_bounds__(64) void decode_chain_kernel(DecodeLaunch a) {
   int* ids = a.ids + cl.frame_off;
 
   // ---- the class table: every class at most once, all inside [0, C)
-  if (lane < DECODE_MAX_CLASSES / 32) used[lane] = 0;
-  for (int c = lane; c < DECODE_MAX_CLASSES; c += 64) info[c] = -1;
+  if (lane < MAX_CLASSES / 32) used[lane] = 0;
+  for (int c = lane; c < MAX_CLASSES; c += 64) info[c] = -1;
   __syncthreads();
   if (lane == 0) { used[o_id >> 5] = 1u << (o_id & 31); info[o_id] = 0; }
   __syncthreads();
@@ -318,7 +310,7 @@ __global__ __launch_bounds__(64) void decode_chain_kernel(DecodeLaunch a) {
   // ---- the score: the objective minus the frames' log-sum-exp
   double ls = 0.0;
   for (int t = lane; t < T; t += 64) ls += (double)lse[t];
-  ls = wave_sum_d(ls);
+  ls = lattice::wave_sum(ls);
   if (lane == 0) {
     a.score[cl.clip] = (float)((double)best + acc - ls);
     a.status[cl.clip] = 0;
@@ -368,38 +360,33 @@ int32_t wfl_decode(const float* logits, int64_t ldl, int32_t C, int32_t o_id, co
   if (!score || !status || (n_pairs > 0 && !pairs) || (any_frame && (!logits || !ids)))
     return wfl_fail(-1, "wfl_decode: null device pointer");
   // over the class cap: status 2; more pairs than classes (then one is used twice or out of range): status 4
-  const int fill = C > DECODE_MAX_CLASSES ? 2 : (n_pairs > C ? 4 : 0);
+  const int fill = C > MAX_CLASSES ? 2 : (n_pairs > C ? 4 : 0);
   const int S = fill ? 0 : slots_of(n_pairs);
   const int64_t need = fill ? 0 : wfl_decode_workspace_bytes(n_frames_host, n_clips, n_pairs);
-  if (workspace_bytes < need || (need > 0 && !workspace))
-    return wfl_fail(-1, "wfl_decode: workspace too small (wfl_decode_workspace_bytes)");
+  if (const int rc = lattice::check_workspace("wfl_decode", need, workspace, workspace_bytes)) return rc;
   hipStream_t s = (hipStream_t)stream;
   DecodeLaunch a{};
   a.logits = logits; a.ldl = ldl; a.C = C; a.o_id = o_id; a.pairs = pairs; a.n_pairs = n_pairs; a.lambda = lambda;
   a.threshold = threshold; a.ws = (unsigned*)workspace; a.ids = ids; a.score = score; a.status = status; a.fill_status = fill;
-  long off = 0;
-  for (int b0 = 0; b0 < n_clips; b0 += DECODE_CLIPS_PER_LAUNCH) {
-    a.n = std::min(DECODE_CLIPS_PER_LAUNCH, n_clips - b0);
-    int max_t = 0;
-    for (int j = 0; j < a.n; ++j) {
-      const int T = n_frames_host[b0 + j];
-      a.clip[j] = DecodeClip{(long)frame_off_host[b0 + j], off, T, b0 + j};
-      if (!fill) off += clip_words(T, S);
-      max_t = std::max(max_t, T);
-    }
-    if (fill) {
-      hipLaunchKernelGGL(decode_fill_kernel, dim3(a.n), dim3(64), 0, s, a);
-      if (hipGetLastError() != hipSuccess) return wfl_fail(-3, "wfl_decode: launch failed");
-      continue;
-    }
-    if (max_t > 0) {
-      hipLaunchKernelGGL(decode_pre_kernel, dim3((max_t + 3) / 4, a.n), dim3(256), 0, s, a, S);
-      if (hipGetLastError() != hipSuccess) return wfl_fail(-3, "wfl_decode: launch failed");
-    }
-    const int rc = launch_chain(S, a, s);
-    if (rc) return rc;
-  }
-  return 0;
+  return lattice::launch_clips<1>(           // one group: the clips in their order
+      a, n_clips,
+      [&](int b, long off, DecodeClip& c, int&) {
+        c = DecodeClip{(long)frame_off_host[b], off, n_frames_host[b], b};
+        return fill ? 0 : clip_words(c.T, S);
+      },
+      [&](int, const DecodeLaunch& a) {
+        if (fill) {
+          hipLaunchKernelGGL(decode_fill_kernel, dim3(a.n), dim3(64), 0, s, a);
+          return hipGetLastError() == hipSuccess ? 0 : wfl_fail(-3, "wfl_decode: launch failed");
+        }
+        int max_t = 0;
+        for (int j = 0; j < a.n; ++j) max_t = std::max(max_t, a.clip[j].T);
+        if (max_t > 0) {
+          hipLaunchKernelGGL(decode_pre_kernel, dim3((max_t + 3) / 4, a.n), dim3(256), 0, s, a, S);
+          if (hipGetLastError() != hipSuccess) return wfl_fail(-3, "wfl_decode: launch failed");
+        }
+        return launch_chain(S, a, s);
+      });
 }
 
 }  // extern "C"

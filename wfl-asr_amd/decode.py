@@ -21,6 +21,7 @@ import torch
 
 from . import _lib
 from . import native_post as npost
+from ._lib import back_to_back, host_ptr as _hp, ptr as _ptr
 from .align import class_pairs
 
 DECODE_MODES = ("argmax", "viterbi")
@@ -58,14 +59,10 @@ def check_options(decode, switch_penalty):
             raise ValueError(f"switch_penalty must be a number >= 0 (nats), got {switch_penalty!r}")
 
 
-def _ptr(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else None
-
-
 def workspace_bytes(n_frames, n_pairs) -> int:
     lib = _lib.load()
     T = np.ascontiguousarray(n_frames, np.int32)
-    n = int(lib.wfl_decode_workspace_bytes(T.ctypes.data_as(C.c_void_p), T.size, int(n_pairs)))
+    n = int(lib.wfl_decode_workspace_bytes(_hp(T), T.size, int(n_pairs)))
     if n < 0:
         raise _lib.WflError("wfl_decode_workspace_bytes: negative frame or pair count")
     return n
@@ -98,7 +95,7 @@ def bio_viterbi(logits, n_frames, table, switch_penalty, threshold, frame_offset
     if nb and int(T.min()) < 0:
         raise ValueError("a clip has a negative frame count")
     if frame_offsets is None:
-        frame_offsets = np.concatenate([[0], np.cumsum(T.astype(np.int64))[:-1]]) if nb else np.zeros(0, np.int64)
+        frame_offsets = back_to_back(T)
     F0 = np.ascontiguousarray(frame_offsets, np.int64).reshape(nb)
     if nb and (int(F0.min()) < 0 or int((F0 + T).max()) > logits.shape[0]):
         raise ValueError("a clip's frames run past the logits rows")
@@ -113,9 +110,8 @@ def bio_viterbi(logits, n_frames, table, switch_penalty, threshold, frame_offset
     status = torch.empty(max(nb, 1), dtype=torch.int32, device=dev)
     with torch.cuda.device(dev):
         st = stream if stream is not None else torch.cuda.current_stream(dev)
-        hp = lambda a: a.ctypes.data_as(C.c_void_p)      # noqa: E731
         ldl = logits.stride(0) if logits.numel() else logits.shape[1]      # (an empty tensor's strides say nothing)
-        rc = lib.wfl_decode(_ptr(logits), ldl, logits.shape[1], int(o_id), hp(F0), hp(T), nb, _ptr(d_pairs), len(pairs),
+        rc = lib.wfl_decode(_ptr(logits), ldl, logits.shape[1], int(o_id), _hp(F0), _hp(T), nb, _ptr(d_pairs), len(pairs),
                             float(switch_penalty), float(threshold), _ptr(ws), ws_n, _ptr(ids), _ptr(score), _ptr(status),
                             C.c_void_p(st.cuda_stream))
         _lib.check(rc, "wfl_decode")

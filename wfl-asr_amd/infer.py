@@ -707,6 +707,49 @@ class Labeler:
                 rows[(fi, ci)] = (res.logits[r, :tv], offs_h[r, :tv].copy())
         return free, rows
 
+    def _file_waves(self, audio_paths, verbose):
+        """The files of a whole-file search (_decode_viterbi, _label_viterbi) in waves whose chunks are forwarded together: yields
+        (files, by_file), the wave's file indices in order and {file: its chunks} for those that hold audio.  A pool loads the files
+        ahead; a wave closes once it holds `wave` chunks."""
+        if not audio_paths:
+            return
+        wave = getattr(self, "_wave_items", None) or max(8 * self.batch_size, 64)
+        from concurrent.futures import ThreadPoolExecutor
+        pool = ThreadPoolExecutor(max_workers=max(1, min(16, os.cpu_count() or 1, len(audio_paths))))
+        loads = [pool.submit(self._load_chunks, p) for p in audio_paths]      # (the native loader releases the GIL)
+        pool.shutdown(wait=False)
+        files = list(range(len(audio_paths)))
+        while files:
+            sel, by_file, n_chunks = [], {}, 0
+            while files and n_chunks < wave:
+                fi = files.pop(0)
+                cs = loads[fi].result()
+                loads[fi] = None
+                if verbose and len(cs) > 1:
+                    print(f"Audio is too long ({sum(len(c) for c in cs)/self.sr:.1f}s), splitting...")
+                sel.append(fi)
+                if cs:
+                    by_file[fi] = list(cs)
+                n_chunks += len(cs)
+            yield sel, by_file
+
+    @staticmethod
+    def _file_rows(rows, by_file, sel):
+        """-> (frames per file of `sel`, those files' valid logits rows concatenated on the device): one clip per file."""
+        frames = [sum(rows[(fi, ci)][0].shape[0] for ci in range(len(by_file[fi]))) for fi in sel]
+        return frames, torch.cat([rows[(fi, ci)][0] for fi in sel for ci in range(len(by_file[fi]))])       # device-to-device
+
+    def _chunk_plan(self, rows, chunks, fi):
+        """-> (chunk_frames, chunk_offsets, chunk_clock) of file fi for path_segments / path_segments_free."""
+        cf, co, cc, clock = [], [], [], 0.0
+        for ci, x in enumerate(chunks):
+            r, offs = rows[(fi, ci)]
+            cf.append(r.shape[0])
+            co.append(offs)
+            cc.append(clock)
+            clock += len(x) / self.sr
+        return cf, co, cc
+
     def _decode_viterbi(self, audio_paths, lang_id, threshold, verbose, switch_penalty):
         """decode="viterbi": the free decode of files by the BIO-grammar search (decode.py, wfl_decode) -> {file index: segments
         [(start_s, end_s, phoneme)] after the merge-map names and merge_segments, before any string match}.  The files' chunks are
@@ -721,34 +764,14 @@ class Labeler:
         table = getattr(self, "_decode_table", None)
         if table is None:
             table = self._decode_table = DC.class_table(self.labels)
-        wave = getattr(self, "_wave_items", None) or max(8 * self.batch_size, 64)
         out = {}
-        if not audio_paths:
-            return out
-        from concurrent.futures import ThreadPoolExecutor
-        pool = ThreadPoolExecutor(max_workers=max(1, min(16, os.cpu_count() or 1, len(audio_paths))))
-        loads = [pool.submit(self._load_chunks, p) for p in audio_paths]      # (the native loader releases the GIL)
-        pool.shutdown(wait=False)
-        files = list(range(len(audio_paths)))
-        while files:
-            sel, by_file, n_chunks = [], {}, 0
-            while files and (not sel or n_chunks < wave):
-                fi = files.pop(0)
-                cs = loads[fi].result()
-                loads[fi] = None
-                if verbose and len(cs) > 1:
-                    print(f"Audio is too long ({sum(len(c) for c in cs)/self.sr:.1f}s), splitting...")
-                if not cs:                                    # no audio: no segments
-                    out[fi] = []
-                    continue
-                sel.append(fi)
-                by_file[fi] = list(cs)
-                n_chunks += len(cs)
+        for files, by_file in self._file_waves(audio_paths, verbose):
+            sel = [fi for fi in files if fi in by_file]
+            out.update((fi, []) for fi in files if fi not in by_file)      # no audio: no segments
             if not sel:
                 continue
             _, rows = self._forward_with_logits(sel, by_file, lang_id, threshold)
-            frames = [sum(rows[(fi, ci)][0].shape[0] for ci in range(len(by_file[fi]))) for fi in sel]
-            lg = torch.cat([rows[(fi, ci)][0] for fi in sel for ci in range(len(by_file[fi]))])       # device-to-device
+            frames, lg = self._file_rows(rows, by_file, sel)
             d_ids, _, d_st = DC.bio_viterbi(lg, frames, table, switch_penalty, threshold)
             ids_all, st_all = d_ids.cpu().numpy(), d_st.cpu().numpy()
             pos = 0
@@ -757,14 +780,8 @@ class Labeler:
                 if st_all[b] != DC.STATUS_OK:
                     print(f"{audio_paths[fi]}: viterbi decode not possible (wfl_decode status {int(st_all[b])}); using the argmax decode")
                 else:
-                    cf, co, cc, clock = [], [], [], 0.0
-                    for ci, x in enumerate(by_file[fi]):
-                        r, offs = rows[(fi, ci)]
-                        cf.append(r.shape[0])
-                        co.append(offs)
-                        cc.append(clock)
-                        clock += len(x) / self.sr
-                    s, e, ph = DC.path_segments_free(ids_all[pos:pos + n], cf, co, cc, self._table, frame_duration)
+                    s, e, ph = DC.path_segments_free(ids_all[pos:pos + n], *self._chunk_plan(rows, by_file[fi], fi), self._table,
+                                                     frame_duration)
                     ph = remap[ph] if ph.size else ph
                     if mode != "none" and s.size:
                         s, e, ph = npost.merge_segments(s, e, ph, mode)
@@ -783,28 +800,8 @@ class Labeler:
         lang_name = self._lang_name(lang_id)
         remap, names = self._names_for(lang_name)
         mode = self.config["postprocess"]["merge_segments"]
-        Bs = self.batch_size
         results, scores = [], []
-        wave = getattr(self, "_wave_items", None) or max(8 * Bs, 64)
-        from concurrent.futures import ThreadPoolExecutor
-        pool = ThreadPoolExecutor(max_workers=max(1, min(16, os.cpu_count() or 1, len(audio_paths))))
-        loads = [pool.submit(self._load_chunks, p) for p in audio_paths]      # (the native loader releases the GIL)
-        pool.shutdown(wait=False)
-        files = list(range(len(audio_paths)))
-        while files:
-            # a wave of files: their chunks are forwarded and aligned together
-            sel, chunks = [], []
-            while files and (not sel or len(chunks) < wave):
-                fi = files.pop(0)
-                cs = loads[fi].result()
-                loads[fi] = None
-                if verbose and len(cs) > 1:
-                    print(f"Audio is too long ({sum(len(c) for c in cs)/self.sr:.1f}s), splitting...")
-                sel.append(fi)
-                chunks.extend((fi, c) for c in cs)
-            by_file = {}
-            for fi, c in chunks:
-                by_file.setdefault(fi, []).append(c)
+        for sel, by_file in self._file_waves(audio_paths, verbose):     # a wave's chunks are forwarded and aligned together
             free, rows = self._forward_with_logits(sel, by_file, lang_id, threshold)
             # the greedy result of every file (free decode, merge, string match), as _label_files_greedy computes it
             greedy, free_segs, plans = {}, {}, {}
@@ -836,8 +833,7 @@ class Labeler:
             post = {}                                         # file -> its FileScore (want_scores)
             run = [fi for fi in sel if fi in plans]
             if run:
-                frames = [sum(rows[(fi, ci)][0].shape[0] for ci in range(len(by_file[fi]))) for fi in run]
-                lg = torch.cat([rows[(fi, ci)][0] for fi in run for ci in range(len(by_file[fi]))])   # device-to-device
+                frames, lg = self._file_rows(rows, by_file, run)
                 gaps = [AL.gap_classes(self.labels, transcripts[fi]) for fi in run]
                 packed = AL.pack_clips(lg, frames, [plans[fi] for fi in run], gaps) if want_scores else None
                 d_ids, d_tok, d_score, d_st = AL.viterbi_align(lg, frames, [plans[fi] for fi in run], gaps, self.labels.index("O"),
@@ -875,15 +871,8 @@ class Labeler:
                                                                                                            f"status {int(st_all[b])}")
                         print(f"{audio_paths[fi]}: viterbi alignment not possible ({why}); using the greedy alignment")
                     else:
-                        cf, co, cc, clock = [], [], [], 0.0
-                        for ci, x in enumerate(by_file[fi]):
-                            r, offs = rows[(fi, ci)]
-                            cf.append(r.shape[0])
-                            co.append(offs)
-                            cc.append(clock)
-                            clock += len(x) / self.sr
-                        segs = AL.path_segments(ids_all[pos:pos + n], tok_all[pos:pos + n], cf, co, cc, self._table, plans[fi], tr,
-                                                frame_duration)
+                        segs = AL.path_segments(ids_all[pos:pos + n], tok_all[pos:pos + n], *self._chunk_plan(rows, by_file[fi], fi),
+                                                self._table, plans[fi], tr, frame_duration)
                         aligned[fi] = AL.with_end_pauses(free_segs[fi], segs, tr)
                         if fi in raw:
                             post[fi] = AL.file_score(raw[fi][0], raw[fi][1], n, *raw[fi][2:], segs, frame_duration)
