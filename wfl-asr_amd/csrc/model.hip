@@ -1064,6 +1064,9 @@ static int check_device(const wfl_model* m, const char* who) {
 // ------------------------------------------------------------------------------------------------ workspace plan
 namespace {
 
+// The bf16 activation buffers "model.precision: high" keeps a low half of (Runner::lo_ok, lo_idx)
+enum Buf { BUF_X, BUF_Y, BUF_ATT, BUF_QK, BUF_FF, BUF_MEL, BUF_C1, BUF_ENC2, BUF_QKP, BUF_ATTP, BUF_FA, BUF_FB, BUF_XG, BUF_COUNT };
+
 struct Plan {
   int B, L, T, P, lead, tail;
   int T2, P2, lead2;            // whisper stem input rows (mel frames)
@@ -1080,6 +1083,7 @@ struct Plan {
   long lo_delta, hp32;          // "model.precision: high": every activation buffer has its low half lo_delta bytes further on (a twin of
   long hp32_floats;             //   the whole activation area); hp32 = the fp32 sums of the three passes, [rows][columns]
   int da;                       // Conformer attention width (wfl_model::conf_da); QKp / ATTp exist when it differs from d
+  long buf_off[BUF_COUNT], buf_bytes[BUF_COUNT];   // where make_plan put each of them; 0 bytes: not allocated for this model
 };
 
 static int wavlm_frames(const wfl_arch& a, int L) {
@@ -1109,10 +1113,11 @@ static Plan make_plan(const wfl_model* m, int B, int L, int T_frames = 0) {
   p.ffw = std::max(a.enc_ffn, a.d_model * std::max(a.conformer_ff_expansion, 1));
   long off = 0;
   auto take = [&](long bytes) { long o = off; off = round_up(off + bytes, 256); return o; };
+  auto take_buf = [&](Buf b, long bytes) { p.buf_bytes[b] = bytes; return p.buf_off[b] = take(bytes); };
   if (T_frames > 0) {
   } else if (whisper) {
-    p.mel = take(p.R2 * a.n_mels * 2 + 1024);
-    p.c1 = take(p.R2 * p.d * 2);
+    p.mel = take_buf(BUF_MEL, p.R2 * a.n_mels * 2 + 1024);
+    p.c1 = take_buf(BUF_C1, p.R2 * p.d * 2);
     p.raw = take((long)B * p.T2 * a.n_mels * 4);
   } else if (none) {
     p.raw = take((long)B * p.T * a.n_mels * 4);        // the mel power = the hidden states, fp32 [B][T][n_mels]
@@ -1129,26 +1134,26 @@ static Plan make_plan(const wfl_model* m, int B, int L, int T_frames = 0) {
       p.leadl[i] = i == n - 1 ? p.lead : 8;
       p.Rl[i] = p.leadl[i] + (long)B * p.Pl[i] + p.tail;
     }
-    p.FA = take(p.Rl[0] * C * 2);                     // levels 0, 2, 4, 6
-    p.FB = take(p.Rl[1] * C * 2);                     // levels 1, 3, 5
-    p.XG = take((long)a.wavlm_pos_conv_groups * p.R * 64 * 2);
+    p.FA = take_buf(BUF_FA, p.Rl[0] * C * 2);                     // levels 0, 2, 4, 6
+    p.FB = take_buf(BUF_FB, p.Rl[1] * C * 2);                     // levels 1, 3, 5
+    p.XG = take_buf(BUF_XG, (long)a.wavlm_pos_conv_groups * p.R * 64 * 2);
     p.gate = take((long)B * a.enc_heads * p.T * 4);
     p.rtab = take((long)a.enc_heads * (2L * p.T + 1) * 4);
     p.wstats = take((long)B * 2 * 8);
     p.cstats = take((long)B * C * 2 * 8);
     p.cpart = take(a.wavlm_group_norm ? (long)B * ((p.Tl[0] + 511) / 512) * C * 2 * 4 : 16);   // GroupNorm partials per 512-step block
   }
-  p.X = take(p.R * p.d * 2);
-  p.Y = take(p.R * p.d * 2);
+  p.X = take_buf(BUF_X, p.R * p.d * 2);
+  p.Y = take_buf(BUF_Y, p.R * p.d * 2);
   p.Xlo = take(p.R * p.d * 2);                          // low halves of the residual stream (GemmArgs::res_lo)
   p.Ylo = take(p.R * p.d * 2);
-  p.ATT = take(p.R * p.d * 2);
-  p.QK = take(p.R * 3 * p.d * 2);                   // packed q | k | v rows
-  p.FF = take(p.R * p.ffw * 2);
+  p.ATT = take_buf(BUF_ATT, p.R * p.d * 2);
+  p.QK = take_buf(BUF_QK, p.R * 3 * p.d * 2);                   // packed q | k | v rows
+  p.FF = take_buf(BUF_FF, p.R * p.ffw * 2);
   p.da = m->conf_da > 0 ? m->conf_da : p.d;
   if (p.da != p.d) {
-    p.QKp = take(p.R * 3 * p.da * 2);
-    p.ATTp = take(p.R * p.da * 2);
+    p.QKp = take_buf(BUF_QKP, p.R * 3 * p.da * 2);
+    p.ATTp = take_buf(BUF_ATTP, p.R * p.da * 2);
   }
   if (a.fp8_weights && T_frames <= 0) {
     p.X8 = take(p.R * (long)p.d);
@@ -1158,7 +1163,7 @@ static Plan make_plan(const wfl_model* m, int B, int L, int T_frames = 0) {
     p.FF8lo = take(p.R * (long)p.ffw);
   }
   p.stats = take(p.R * 4L * 2 * 4);                     // per row, per 256-column tile (<= 4): (sum, sum of squares)
-  p.enc2 = take(p.R * p.d * 2);
+  p.enc2 = take_buf(BUF_ENC2, p.R * p.d * 2);
   p.clipmax = take((long)B * 4);
   p.logits = take((long)B * p.T * round_up(a.num_classes, 4) * 4);      // (rows of a multiple of four floats when the caller does not ask for them)
   p.logits2 = take((long)B * p.T * a.num_classes * 4);
@@ -1199,6 +1204,45 @@ int64_t wfl_workspace_bytes(const wfl_model* m, int32_t B, int32_t L) {
 // ------------------------------------------------------------------------------------------------ forward
 namespace {
 
+// Keys of the non-GEMM kernel families in the launch profile (wfl_gemm_profile_read; GEMM variants have keys below 2040)
+enum { PROF_ATTENTION = 2040, PROF_LSTM = 2041, PROF_LOGMEL = 2042, PROF_LAYERNORM = 2043, PROF_POSCONV = 2044 };
+
+// One Runner::gemm() call: C = epilogue(A W^T + b) over the rows, with the options the caller names.
+struct GemmRows { int M, P, T; };                              // M = B * P rows; the first T of every P are a clip's frames
+struct GemmOut { void* C; long ldc, c_lead; int c_pitch; };    // row b * P + t of the product goes to row c_lead + b * c_pitch + t of C
+struct GemmOpts {
+  int act = WFL_ACT_NONE;
+  const bf16_t* res = nullptr;  // residual: C = res + alpha * act(A W^T + b)
+  long ldres = 0;
+  float alpha = 1.f;
+  int cin = 0;                  // > 0: K holds K / cin taps of cin channels, tap_stride elements apart (GemmArgs::cin)
+  long tap_stride = 0;
+  bool glu = false;
+  bool out_f32 = false;
+  const bf16_t* pos = nullptr;  // positional table [T][ldpos], added after the activation
+  long ldpos = 0;
+  const float* clip_bias = nullptr;   // per-clip bias rows clip_bias[clip_idx[b] * clip_ld + n]
+  const int* clip_idx = nullptr;
+  int clip_ld = 0;
+  bool want_stats = false;      // a residual launch that feeds a LayerNorm-folded GEMM: emit the row statistics if this launch can
+  bool lo_out = false;          // the output is a residual-stream tensor: keep its low half
+  bool acc_f32 = false;         // (fp32 output) add to what is there
+  double flops = -1.0;          // >= 0: algorithmic FLOPs to book instead of 2 M N K
+  int tap_wrap = 0;             // K holds three tap segments (GemmArgs::tap_wrap / seg_off)
+  long seg_off = 0;
+  // fp8 activations (GemmArgs::a8): the A operand is e4m3 bytes with these scales ...
+  int a8 = 0;                   // 0 off, 1 gemm_stream A8, 2 / 3 gemm_mx single / pair
+  const float* a8_scale = nullptr;
+  float a8_static = 1.f;
+  const unsigned char* a8_lo = nullptr;     // pair input (a8 == 3)
+  // ... and the output goes out as e4m3 too (gemm_mx.hip: c8_lo for a pair)
+  unsigned char* c8 = nullptr;
+  unsigned char* c8_lo = nullptr;
+  long ldc8 = 0;
+  float c8_inv = 1.f;
+  bool stats_in = false;        // (ln_gemm) a folded operand reads the statistics the last residual launch left behind
+};
+
 struct Runner {
   wfl_model* m;
   Plan p;
@@ -1222,158 +1266,104 @@ struct Runner {
   // Residual stream hi + lo (common.h, GemmArgs::res_lo): X and Y have low halves; lo_ok says whether the low half of the
   // tensor currently held in X / Y is valid (a kernel that writes only the high half invalidates it).
   // "model.precision: high" (precise.hip): EVERY activation buffer has a low half, lo_delta bytes further on, and lo_ok tracks the
-  // buffers whose producer wrote it (X, Y, ATT, QK, FF, mel, c1, enc2, QKp, ATTp, and WavLM's FA, FB, XG: indices 0 .. 12; any pointer
-  // inside the buffer counts)
+  // buffers whose producer wrote it (one flag per Buf; any pointer inside the buffer counts)
   bool precise() const { return m->a.precision != 0 && p.lo_delta > 0; }
-  bool lo_ok[13] = {false, false, false, false, false, false, false, false, false, false, false, false, false};
-  int lo_idx(const void* ptr) const {               // default mode -- 0: inside X's first row (a column offset is allowed), 1: Y, else -1
-    if (precise()) {
-      const long o = (const char*)ptr - ws;
-      const bool wavlm = m->a.encoder_type == WFL_ENC_WAVLM;
-      const long C0 = wavlm ? m->a.wavlm_conv_dim[0] : 0;
-      const long st[13] = {p.X, p.Y, p.ATT, p.QK, p.FF, p.mel, p.c1, p.enc2, p.QKp, p.ATTp, p.FA, p.FB, p.XG};
-      const long sz[13] = {p.R * p.d * 2, p.R * p.d * 2, p.R * p.d * 2, p.R * 3L * p.d * 2, p.R * (long)p.ffw * 2, p.mel > 0 || m->a.encoder_type == WFL_ENC_WHISPER ? p.R2 * m->a.n_mels * 2 + 1024 : 0,
-                           m->a.encoder_type == WFL_ENC_WHISPER ? p.R2 * (long)p.d * 2 : 0, p.R * p.d * 2, p.da != p.d ? p.R * 3L * p.da * 2 : 0, p.da != p.d ? p.R * (long)p.da * 2 : 0,
-                           wavlm ? p.Rl[0] * C0 * 2 : 0, wavlm ? p.Rl[1] * C0 * 2 : 0, wavlm ? (long)m->a.wavlm_pos_conv_groups * p.R * 64 * 2 : 0};
-      for (int i = 0; i < 13; ++i)
-        if (sz[i] > 0 && o >= st[i] && o < st[i] + sz[i]) return i;
-      return -1;
+  bool lo_ok[BUF_COUNT] = {};
+  int lo_idx(const void* ptr) const {               // the buffer `ptr` lies in, or -1
+    const long o = (const char*)ptr - ws;
+    // default mode: only X and Y have low halves, and only a pointer inside their first row (a column offset is allowed) names them
+    const int n = precise() ? BUF_COUNT : BUF_Y + 1;
+    for (int i = 0; i < n; ++i) {
+      const long bytes = precise() ? p.buf_bytes[i] : (long)p.d * 2;
+      if (o >= p.buf_off[i] && o < p.buf_off[i] + bytes) return i;
     }
-    const long dx = (const char*)ptr - (ws + p.X), dy = (const char*)ptr - (ws + p.Y);
-    if (dx >= 0 && dx < (long)p.d * 2) return 0;
-    if (dy >= 0 && dy < (long)p.d * 2) return 1;
     return -1;
   }
   bf16_t* lo_of(const void* ptr) const {
     const int i = lo_idx(ptr);
     if (i < 0) return nullptr;
     if (precise()) return (bf16_t*)((char*)ptr + p.lo_delta);
-    return (bf16_t*)(ws + (i == 0 ? p.Xlo : p.Ylo) + ((const char*)ptr - (ws + (i == 0 ? p.X : p.Y))));
+    return (bf16_t*)(ws + (i == BUF_X ? p.Xlo : p.Ylo) + ((const char*)ptr - (ws + (i == BUF_X ? p.X : p.Y))));
   }
   const bf16_t* lo_in(const void* ptr) const { const int i = lo_idx(ptr); return (i >= 0 && lo_ok[i]) ? lo_of(ptr) : nullptr; }
-  bool next_stats = false;      // the next gemm() (a residual launch) feeds a LayerNorm-folded GEMM: have it emit the row statistics
-  bool next_lo_out = false;     // the next gemm() produces a residual-stream tensor: keep its low half
-  bool next_acc_f32 = false;    // the next gemm() (fp32 output) adds to what is there
-  double next_flops = -1.0;     // >= 0: algorithmic FLOPs to book for the next gemm() instead of 2 M N K
-  int next_tap_wrap = 0;        // the next gemm()'s K holds three tap segments (GemmArgs::tap_wrap / seg_off)
-  long next_seg_off = 0;
-  // fp8 activations (GemmArgs::a8): the next gemm()'s A operand is e4m3 bytes with these scales / its output goes out as e4m3
-  bool next_a8 = false;
-  const float* next_a8_scale = nullptr;
-  float next_a8_static = 1.f;
-  unsigned char* next_c8 = nullptr;
-  unsigned char* next_c8_lo = nullptr;            // gemm_mx.hip: e4m3 pair output
-  const unsigned char* next_a8_lo = nullptr;      //   and pair input (next_a8_mode == 3)
-  int next_a8_mode = 1;                           // GemmArgs::a8 of the next launch: 1 gemm_stream A8, 2 / 3 gemm_mx single / pair
-  long next_ldc8 = 0;
-  float next_c8_inv = 1.f;
   // LayerNorm statistics left behind by the last residual GEMM (gemm_stream.hip, STATS): valid for the rows of `stats_for`
   const void* stats_for = nullptr;
   int stats_nsl = 0;
-  bool stats_in_next = false;   // the next gemm() call (a folded operand) reads them
 
-  void gemm(const bf16_t* A, long lda, const Lin& W, int M, int P, int T, void* C, long ldc, long c_lead, int c_pitch,
-            int act = WFL_ACT_NONE, const bf16_t* res = nullptr, long ldres = 0, float alpha = 1.f, int cin = 0,
-            long tap_stride = 0, bool glu = false, bool out_f32 = false,
-            const bf16_t* pos = nullptr, long ldpos = 0, const float* clip_bias = nullptr, const int* clip_idx = nullptr,
-            int clip_ld = 0) {
+  GemmOut out(void* C, long ldc) const { return {C, ldc, p.lead, p.P}; }        // rows in the main geometry
+
+  // What every launch of a Linear / Conv-as-GEMM has in common; the callers below set what differs (operand halves, W_lo / W3, the
+  // fp32 accumulator, the fp8 and LayerNorm-fold fields)
+  GemmArgs gemm_args(const bf16_t* A, long lda, const Lin& W, const GemmRows& r, const GemmOut& c, const GemmOpts& o) const {
+    GemmArgs g{};
+    g.A = A; g.lda = lda;
+    g.cin = o.cin > 0 ? o.cin : W.K; g.tap_stride = o.tap_stride;
+    g.W = W.W; g.M = r.M; g.N = W.N; g.K = W.K; g.n_valid = W.n_valid;
+    g.P = r.P; g.T = r.T; g.clip_T = clip_T_for(r.P);
+    g.C = c.C; g.ldc = c.ldc; g.c_lead = c.c_lead; g.c_pitch = c.c_pitch;
+    g.bias = W.bias; g.clip_bias = o.clip_bias; g.clip_idx = o.clip_idx; g.clip_ld = o.clip_ld;
+    g.res = o.res; g.ldres = o.ldres; g.alpha = o.alpha;
+    g.pos = o.pos; g.ldpos = o.ldpos;
+    g.act = o.act; g.glu = o.glu ? 1 : 0; g.out_f32 = o.out_f32 ? 1 : 0;
+    g.ln_eps = 1e-5f;
+    return g;
+  }
+  // One pass of a product summed in fp32: A W^T alone -- no bias, no epilogue -- of the same taps
+  static GemmOpts partial_product(const GemmOpts& o) { return {.cin = o.cin, .tap_stride = o.tap_stride, .out_f32 = true}; }
+
+  void gemm(const bf16_t* A, long lda, const Lin& W, const GemmRows& r, const GemmOut& c, const GemmOpts& o = {}) {
     if (rc) return;
-    if (precise() && !out_f32 && !W.w8 && !next_a8 && W.W_lo) {
-      gemm_precise(A, lda, W, M, P, T, C, ldc, c_lead, c_pitch, act, res, ldres, alpha, cin, tap_stride, glu, pos, ldpos, clip_bias, clip_idx,
-                   clip_ld);
+    if (precise() && !o.out_f32 && !W.w8 && !o.a8 && W.W_lo) {
+      gemm_precise(A, lda, W, r, c, o);
       return;
     }
-    if (precise() && out_f32 && !next_acc_f32 && act == WFL_ACT_NONE && W.W_lo && !W.w8 && !glu && !res && !pos && !clip_bias && !W.ln_s &&
-        next_tap_wrap == 0) {
+    bool acc_f32 = o.acc_f32;
+    if (precise() && o.out_f32 && !acc_f32 && o.act == WFL_ACT_NONE && W.W_lo && !W.w8 && !o.glu && !o.res && !o.pos && !o.clip_bias &&
+        !W.ln_s && o.tap_wrap == 0) {
       // fp32 output (the BiLSTM's input projection): the two correction passes first -- A_hi W_lo^T, then A_lo W_hi^T added to it, no
-      // bias -- and the plain launch below adds A_hi W_hi^T + b to them
+      // bias -- and the plain launch below adds A_hi W_hi^T + b to them (which books the product: these two are not timed)
       const bf16_t* A_lo = lo_in(A);
       for (int pass = 0; pass < 2; ++pass) {
         if (pass == 1 && !A_lo) break;
-        GemmArgs g{};
-        g.A = pass == 1 ? A_lo : A; g.lda = lda;
-        g.cin = cin > 0 ? cin : W.K; g.tap_stride = tap_stride;
-        g.W = pass == 0 ? W.W_lo : W.W; g.M = M; g.N = W.N; g.K = W.K; g.n_valid = W.n_valid;
-        g.P = P; g.T = T; g.clip_T = clip_T_for(P);
-        g.C = C; g.ldc = ldc; g.c_lead = c_lead; g.c_pitch = c_pitch;
-        g.alpha = 1.f; g.act = WFL_ACT_NONE; g.out_f32 = 1; g.acc_f32 = pass;
-        const int r = wfl_launch_gemm(g, s);
-        if (r) { rc = fail(r, "gemm launch failed (precision high, fp32 output, pass " + std::to_string(pass) + ")"); return; }
+        GemmArgs g = gemm_args(pass == 1 ? A_lo : A, lda, W, r, c, partial_product(o));
+        g.W = pass == 0 ? W.W_lo : W.W; g.bias = nullptr; g.acc_f32 = pass;
+        const int e = wfl_launch_gemm(g, s);
+        if (e) { rc = fail(e, "gemm launch failed (precision high, fp32 output, pass " + std::to_string(pass) + ")"); return; }
       }
-      next_acc_f32 = true;
+      acc_f32 = true;
     }
-    GemmArgs g{};
-    g.ln_s = W.ln_s; g.ln_eps = 1e-5f;
+    GemmArgs g = gemm_args(A, lda, W, r, c, o);
+    g.ln_s = W.ln_s;
     g.w8_scale = W.w8;
-    if (W.ln_s && stats_in_next) { g.stats_in = (const float*)(ws + p.stats); g.stats_nsl = stats_nsl; g.stats_lead = p.lead; }
-    stats_in_next = false;
-    g.A = A; g.lda = lda;
-    g.cin = cin > 0 ? cin : W.K; g.tap_stride = tap_stride;
-    g.tap_wrap = next_tap_wrap; g.seg_off = next_seg_off;
-    next_tap_wrap = 0; next_seg_off = 0;
-    g.W = W.W; g.M = M; g.N = W.N; g.K = W.K; g.n_valid = W.n_valid;
-    g.P = P; g.T = T;
-    g.clip_T = clip_T_for(P);
-    g.C = C; g.ldc = ldc; g.c_lead = c_lead; g.c_pitch = c_pitch;
-    g.bias = W.bias; g.clip_bias = clip_bias; g.clip_idx = clip_idx; g.clip_ld = clip_ld;
-    g.res = res; g.ldres = ldres; g.alpha = alpha;
-    g.pos = pos; g.ldpos = ldpos;
-    g.act = act; g.glu = glu ? 1 : 0; g.out_f32 = out_f32 ? 1 : 0;
-    g.acc_f32 = (out_f32 && next_acc_f32) ? 1 : 0;
-    if (next_a8) {
-      g.a8 = next_a8_mode; g.a8_lo = next_a8_lo; g.a8_scale = next_a8_scale; g.a8_lead = p.lead; g.a8_static = next_a8_static;
-      g.c8 = next_c8; g.c8_lo = next_c8_lo; g.ldc8 = next_ldc8; g.c8_inv_scale = next_c8_inv;
+    if (W.ln_s && o.stats_in) { g.stats_in = (const float*)(ws + p.stats); g.stats_nsl = stats_nsl; g.stats_lead = p.lead; }
+    g.tap_wrap = o.tap_wrap; g.seg_off = o.seg_off;
+    g.acc_f32 = (o.out_f32 && acc_f32) ? 1 : 0;
+    if (o.a8) {
+      g.a8 = o.a8; g.a8_lo = o.a8_lo; g.a8_scale = o.a8_scale; g.a8_lead = p.lead; g.a8_static = o.a8_static;
+      g.c8 = o.c8; g.c8_lo = o.c8_lo; g.ldc8 = o.ldc8; g.c8_inv_scale = o.c8_inv;
       g.err = (unsigned*)(ws + p.err);
-      next_a8 = false; next_a8_scale = nullptr; next_c8 = nullptr; next_a8_lo = nullptr; next_c8_lo = nullptr;
     }
-    if (!out_f32 && !glu && (res || next_lo_out)) g.c_lo = lo_of(C);
-    if (res) g.res_lo = lo_in(res);
-    { const int ci = out_f32 ? -1 : lo_idx(C); if (ci >= 0) lo_ok[ci] = g.c_lo != nullptr; }
-    const double flops_booked = next_flops;
-    next_lo_out = next_acc_f32 = false;
-    next_flops = -1.0;
-    if (C == stats_for) stats_for = nullptr;                       // the rows they describe are being overwritten
-    const bool want_stats = next_stats;
-    next_stats = false;
-    if (want_stats && res && !out_f32 && !glu && act == WFL_ACT_NONE && ldc == p.d && W.n_valid == p.d && c_lead == p.lead &&
-        c_pitch == p.P && P == p.P && ln_fold_mode() == 1 && !W.w8) {
+    if (!o.out_f32 && !o.glu && (o.res || o.lo_out)) g.c_lo = lo_of(c.C);
+    if (o.res) g.res_lo = lo_in(o.res);
+    { const int ci = o.out_f32 ? -1 : lo_idx(c.C); if (ci >= 0) lo_ok[ci] = g.c_lo != nullptr; }
+    if (c.C == stats_for) stats_for = nullptr;                     // the rows they describe are being overwritten
+    // want_stats is a request: a launch that cannot emit the statistics runs without them, and the consumer's LayerNorm stays a kernel
+    if (o.want_stats && o.res && !o.out_f32 && !o.glu && o.act == WFL_ACT_NONE && c.ldc == p.d && W.n_valid == p.d && c.c_lead == p.lead &&
+        c.c_pitch == p.P && r.P == p.P && ln_fold_mode() == 1 && !W.w8) {
       g.stats_out = (float*)(ws + p.stats);
-      if (wfl_gemm_stream_takes(g)) { stats_for = C; stats_nsl = W.N / 256; }
+      if (wfl_gemm_stream_takes(g)) { stats_for = c.C; stats_nsl = W.N / 256; }
       else g.stats_out = nullptr;
     }
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (m->prof_on) {
-      if (m->prof_used >= m->prof.ev.size()) {
-        hipEvent_t a_, b_;
-        if (hipEventCreate(&a_) != hipSuccess || hipEventCreate(&b_) != hipSuccess) { rc = fail(-10, "hipEventCreate"); return; }
-        m->prof.ev.push_back({a_, b_});
-      }
-      e0 = m->prof.ev[m->prof_used].first; e1 = m->prof.ev[m->prof_used].second;
-      ++m->prof_used;
-      (void)hipEventRecord(e0, s);
-    }
-    const int r = wfl_launch_gemm(g, s);
-    if (m->prof_on) {
-      (void)hipEventRecord(e1, s);
-      const int key = (act & 3) | (glu ? 4 : 0) | (out_f32 ? 8 : 0) | (res ? 16 : 0) | ((g_wfl_gemm_kernel_id & 7) << 5) |
-                      ((g.ln_s ? (g.stats_in ? 2 : 1) : 0) << 8) | (g.stats_out ? 1024 : 0);
-      m->prof.key.push_back(key);
-      m->prof.launches[key] += 1;
-      m->prof.flops[key] += flops_booked >= 0.0 ? flops_booked : 2.0 * (double)(M / P) * T * (double)W.n_valid * (double)W.K;
-    }
-    if (r) rc = fail(r, "gemm launch failed (" + std::to_string(r) + ")");
+    launch_timed(g, o.flops >= 0.0 ? o.flops : 2.0 * (double)(r.M / r.P) * r.T * (double)W.n_valid * (double)W.K, "");
   }
 
   // "model.precision: high": the same Linear / Conv1d as three bf16 passes over split operands, summed in fp32, then the layer's
-  // epilogue as its own kernel (precise.hip).  A's low half is used when its producer wrote it (lo_ok).
-  void gemm_precise(const bf16_t* A, long lda, const Lin& W, int M, int P, int T, void* C, long ldc, long c_lead, int c_pitch, int act,
-                    const bf16_t* res, long ldres, float alpha, int cin, long tap_stride, bool glu, const bf16_t* pos, long ldpos,
-                    const float* clip_bias, const int* clip_idx, int clip_ld) {
-    next_lo_out = next_acc_f32 = next_stats = false;
-    next_flops = -1.0;
-    stats_in_next = false;
+  // epilogue as its own kernel (precise.hip).  A's low half is used when its producer wrote it (lo_ok).  Both halves of the output are
+  // always kept and the FLOPs of the passes are booked as they are: o.want_stats, o.lo_out and o.flops are not read.
+  void gemm_precise(const bf16_t* A, long lda, const Lin& W, const GemmRows& r, const GemmOut& c, const GemmOpts& o) {
+    void* const C = c.C;
     if (C == stats_for) stats_for = nullptr;
-    const int B = M / P;
+    const int B = r.M / r.P;
     const bf16_t* A_lo = lo_in(A);
     // One launch instead of three + the finish kernel, whenever the operand has its low half and the fused epilogues can do what the
     // layer needs: K' = 3 K with the weights packed [W_hi | W_hi | W_lo] against the taps [A_hi | A_lo | A_hi] (GemmArgs::tap_wrap; the
@@ -1381,94 +1371,46 @@ struct Runner {
     // keeps the three-launch form (A/B runs); the positional-table launch (the Whisper stem's conv2) joined it in round 4 (below).
     static int fused_on = -1;
     if (fused_on < 0) { const char* e = getenv("WFL_PRECISE_FUSED"); fused_on = e ? atoi(e) : 1; }
-    GemmArgs g{};
+    static int pos_fused = -1;                          // WFL_PRECISE_POS_FUSED=0: the table launch in the three-launch form (A/B runs)
+    if (pos_fused < 0) { const char* e = getenv("WFL_PRECISE_POS_FUSED"); pos_fused = e ? atoi(e) : 1; }
     if (fused_on && W.W3 && A_lo && lo_of(C)) {
-      g.A = A; g.lda = lda;
-      g.cin = cin > 0 ? cin : W.K; g.tap_stride = tap_stride;
+      GemmArgs g = gemm_args(A, lda, W, r, c, o);
       g.tap_wrap = W.K / g.cin; g.seg_off = (long)(A_lo - A);
-      g.W = W.W3; g.M = M; g.N = W.N; g.K = 3 * W.K; g.n_valid = W.n_valid;
-      g.P = P; g.T = T; g.clip_T = clip_T_for(P);
-      g.C = C; g.ldc = ldc; g.c_lead = c_lead; g.c_pitch = c_pitch;
-      g.bias = W.bias; g.clip_bias = clip_bias; g.clip_idx = clip_idx; g.clip_ld = clip_ld;
-      g.res = res; g.ldres = ldres; g.alpha = alpha; g.res_lo = res ? lo_in(res) : nullptr;
-      g.act = act; g.glu = glu ? 1 : 0; g.ln_eps = 1e-5f;
+      g.W = W.W3; g.K = 3 * W.K;
+      g.res_lo = o.res ? lo_in(o.res) : nullptr;
       g.c_lo = lo_of(C);
       // the positional-table launch (the Whisper stem's conv2): one launch too when the slice-by-slice walk takes it -- its epilogue adds
       // the table as a pair; any other kernel would drop the low half, so those shapes keep the three-launch form below
-      if (pos) { g.pos = pos; g.ldpos = ldpos; g.pos_lo = (pos == m->pos) ? m->pos_lo : nullptr; }
-    }
-    static int pos_fused = -1;                          // WFL_PRECISE_POS_FUSED=0: the table launch in the three-launch form (A/B runs)
-    if (pos_fused < 0) { const char* e = getenv("WFL_PRECISE_POS_FUSED"); pos_fused = e ? atoi(e) : 1; }
-    if (g.W && (!pos || (pos_fused && g.pos_lo && !glu && wfl_gemm256_tri_takes(g) && !wfl_gemm_stream_takes(g)))) {
-      { const int ci = lo_idx(C); if (ci >= 0) lo_ok[ci] = true; }
-      hipEvent_t e0 = nullptr, e1 = nullptr;
-      if (m->prof_on) {
-        if (m->prof_used >= m->prof.ev.size()) {
-          hipEvent_t a_, b_;
-          if (hipEventCreate(&a_) != hipSuccess || hipEventCreate(&b_) != hipSuccess) { rc = fail(-10, "hipEventCreate"); return; }
-          m->prof.ev.push_back({a_, b_});
-        }
-        e0 = m->prof.ev[m->prof_used].first; e1 = m->prof.ev[m->prof_used].second;
-        ++m->prof_used;
-        (void)hipEventRecord(e0, s);
+      if (o.pos) g.pos_lo = (o.pos == m->pos) ? m->pos_lo : nullptr;
+      if (!o.pos || (pos_fused && g.pos_lo && !o.glu && wfl_gemm256_tri_takes(g) && !wfl_gemm_stream_takes(g))) {
+        { const int ci = lo_idx(C); if (ci >= 0) lo_ok[ci] = true; }
+        launch_timed(g, 3.0 * 2.0 * (double)B * r.T * (double)W.n_valid * (double)W.K, "precision high, one-launch form: ");
+        return;
       }
-      const int r = wfl_launch_gemm(g, s);
-      if (m->prof_on) {
-        (void)hipEventRecord(e1, s);
-        const int key = (act & 3) | (glu ? 4 : 0) | (res ? 16 : 0) | ((g_wfl_gemm_kernel_id & 7) << 5);
-        m->prof.key.push_back(key);
-        m->prof.launches[key] += 1;
-        m->prof.flops[key] += 3.0 * 2.0 * (double)B * T * (double)W.n_valid * (double)W.K;
-      }
-      if (r) rc = fail(r, "gemm launch failed (precision high, one-launch form: " + std::to_string(r) + ")");
-      return;
     }
-    if ((long)M * W.N > p.hp32_floats) { rc = fail(-1, "precision high: the fp32 accumulator is too small for this launch"); return; }
+    if ((long)r.M * W.N > p.hp32_floats) { rc = fail(-1, "precision high: the fp32 accumulator is too small for this launch"); return; }
     float* acc = (float*)(ws + p.hp32);
     for (int pass = 0; pass < 3; ++pass) {
       if (pass == 2 && !A_lo) break;
-      GemmArgs g{};
-      g.A = pass == 2 ? A_lo : A; g.lda = lda;
-      g.cin = cin > 0 ? cin : W.K; g.tap_stride = tap_stride;
-      g.W = pass == 1 ? W.W_lo : W.W; g.M = M; g.N = W.N; g.K = W.K; g.n_valid = W.N;
-      g.P = P; g.T = T; g.clip_T = clip_T_for(P);
-      g.C = acc; g.ldc = W.N; g.c_lead = 0; g.c_pitch = P;
-      g.alpha = 1.f; g.act = WFL_ACT_NONE; g.out_f32 = 1; g.acc_f32 = pass > 0 ? 1 : 0;
-      hipEvent_t e0 = nullptr, e1 = nullptr;
-      if (m->prof_on) {
-        if (m->prof_used >= m->prof.ev.size()) {
-          hipEvent_t a_, b_;
-          if (hipEventCreate(&a_) != hipSuccess || hipEventCreate(&b_) != hipSuccess) { rc = fail(-10, "hipEventCreate"); return; }
-          m->prof.ev.push_back({a_, b_});
-        }
-        e0 = m->prof.ev[m->prof_used].first; e1 = m->prof.ev[m->prof_used].second;
-        ++m->prof_used;
-        (void)hipEventRecord(e0, s);
-      }
-      const int r = wfl_launch_gemm(g, s);
-      if (m->prof_on) {
-        (void)hipEventRecord(e1, s);
-        const int key = 8 | ((g_wfl_gemm_kernel_id & 7) << 5);
-        m->prof.key.push_back(key);
-        m->prof.launches[key] += 1;
-        m->prof.flops[key] += 2.0 * (double)B * T * (double)W.n_valid * (double)W.K;
-      }
-      if (r) { rc = fail(r, "gemm launch failed (precision high, pass " + std::to_string(pass) + ": " + std::to_string(r) + ")"); return; }
+      GemmArgs g = gemm_args(pass == 2 ? A_lo : A, lda, W, r, {acc, W.N, 0, r.P}, partial_product(o));
+      g.W = pass == 1 ? W.W_lo : W.W; g.n_valid = W.N; g.bias = nullptr; g.acc_f32 = pass > 0 ? 1 : 0;
+      if (!launch_timed(g, 2.0 * (double)B * r.T * (double)W.n_valid * (double)W.K, "precision high, pass " + std::to_string(pass) + ": "))
+        return;
     }
     PreciseFinishArgs f{};
-    f.acc = acc; f.ld_acc = W.N; f.B = B; f.P = P; f.T = T;
-    f.glu = glu ? 1 : 0;
-    f.n_out = glu ? W.n_valid / 2 : W.n_valid;
-    f.bias = W.bias; f.clip_bias = clip_bias; f.clip_idx = clip_idx; f.clip_ld = clip_ld;
-    f.act = act; f.alpha = alpha; f.pos = pos; f.ldpos = ldpos;
-    f.pos_lo = (pos && pos == m->pos) ? m->pos_lo : nullptr;
-    f.res = res; f.res_lo = res ? lo_in(res) : nullptr; f.ldres = ldres;
-    f.out = (bf16_t*)C; f.out_lo = lo_of(C); f.ldc = ldc; f.c_lead = c_lead; f.c_pitch = c_pitch;
-    f.clip_T = clip_T_for(P);
+    f.acc = acc; f.ld_acc = W.N; f.B = B; f.P = r.P; f.T = r.T;
+    f.glu = o.glu ? 1 : 0;
+    f.n_out = o.glu ? W.n_valid / 2 : W.n_valid;
+    f.bias = W.bias; f.clip_bias = o.clip_bias; f.clip_idx = o.clip_idx; f.clip_ld = o.clip_ld;
+    f.act = o.act; f.alpha = o.alpha; f.pos = o.pos; f.ldpos = o.ldpos;
+    f.pos_lo = (o.pos && o.pos == m->pos) ? m->pos_lo : nullptr;
+    f.res = o.res; f.res_lo = o.res ? lo_in(o.res) : nullptr; f.ldres = o.ldres;
+    f.out = (bf16_t*)C; f.out_lo = lo_of(C); f.ldc = c.ldc; f.c_lead = c.c_lead; f.c_pitch = c.c_pitch;
+    f.clip_T = clip_T_for(r.P);
     { const int ci = lo_idx(C); if (ci >= 0) lo_ok[ci] = f.out_lo != nullptr; }
     if (f.n_out % 8) { rc = fail(-1, "precision high: output width must be a multiple of 8"); return; }
-    const int r = wfl_launch_precise_finish(f, s);
-    if (r) rc = fail(r, "precise_finish launch failed");
+    const int e = wfl_launch_precise_finish(f, s);
+    if (e) rc = fail(e, "precise_finish launch failed");
   }
 
   // WFL_LN_FOLD: 1 (default) fold a LayerNorm into the GEMM that consumes it whenever the GEMM that produced its input left
@@ -1490,13 +1432,12 @@ struct Runner {
       g.M = M; g.N = folded.N; g.K = folded.K; g.cin = folded.K; g.n_valid = folded.n_valid; g.act = act; g.ln_s = folded.ln_s;
       if (mode == 1) { g.stats_in = (const float*)(ws + p.stats); g.stats_nsl = stats_nsl; }
       if (wfl_gemm_stream_takes(g)) {
-        stats_in_next = mode == 1;
-        gemm(x + (long)p.lead * p.d, p.d, folded, M, p.P, p.T, C, ldc, p.lead, p.P, act);
+        gemm(x + (long)p.lead * p.d, p.d, folded, {M, p.P, p.T}, out(C, ldc), {.act = act, .stats_in = mode == 1});
         return;
       }
     }
     ln(x, scratch, w);
-    gemm(scratch + (long)p.lead * p.d, p.d, plain, M, p.P, p.T, C, ldc, p.lead, p.P, act);
+    gemm(scratch + (long)p.lead * p.d, p.d, plain, {M, p.P, p.T}, out(C, ldc), {.act = act});
   }
 
   // lo_out: the output is (or may become) a residual-stream tensor -- keep its low half; the input's low half is read when valid
@@ -1508,11 +1449,12 @@ struct Runner {
     { const int yi = lo_idx(y); if (yi >= 0) lo_ok[yi] = y_lo != nullptr; }
     prof_begin();
     const int r = wfl_launch_layernorm_act(x, p.d, y, p.d, w.g, w.b, 1e-5f, p.lead, p.B, p.P, p.T, p.d, 0, s, x_lo, y_lo, m->dv, clipT);
-    prof_end(2043, 0.0);
+    prof_end(PROF_LAYERNORM, 0.0);
     if (r) rc = fail(r, "layernorm launch failed");
   }
 
-  // Timing hook for the non-GEMM kernel families (keys 2040 attention, 2041 BiLSTM recurrence, 2042 log-mel, 2043 LayerNorm)
+  // Timing hook: prof_begin() takes the next event pair (created on demand) and records its first event, prof_end() records the second
+  // and books the launch under its key -- a GEMM variant's (launch_timed) or a PROF_* family's
   hipEvent_t prof_e1 = nullptr;
   void prof_begin() {
     prof_e1 = nullptr;
@@ -1533,6 +1475,16 @@ struct Runner {
     m->prof.launches[key] += 1;
     m->prof.flops[key] += flops;
     prof_e1 = nullptr;
+  }
+  // wfl_launch_gemm, timed and booked under the key of the kernel variant that took it (GemmProf); false, and rc set, when it failed
+  bool launch_timed(const GemmArgs& g, double flops, const std::string& what) {
+    prof_begin();
+    if (rc) return false;
+    const int e = wfl_launch_gemm(g, s);
+    prof_end((g.act & 3) | (g.glu ? 4 : 0) | (g.out_f32 ? 8 : 0) | (g.res ? 16 : 0) | ((g_wfl_gemm_kernel_id & 7) << 5) |
+             ((g.ln_s ? (g.stats_in ? 2 : 1) : 0) << 8) | (g.stats_out ? 1024 : 0), flops);
+    if (e) rc = fail(e, "gemm launch failed (" + what + std::to_string(e) + ")");
+    return !e;
   }
 
   // padded: the Conformer attention at width p.da != p.d (head size rounded up to a built one): q | k | v rows in QKp, context in ATTp
@@ -1559,7 +1511,7 @@ struct Runner {
     a.clip_T = clipT;
     prof_begin();
     const int r = wfl_launch_attention(a, s);
-    prof_end(2040, 4.0 * (double)p.B * p.T * (double)p.T * (double)p.d);
+    prof_end(PROF_ATTENTION, 4.0 * (double)p.B * p.T * (double)p.T * (double)p.d);
     if (r) rc = fail(r, "attention launch failed (" + std::to_string(r) + "; head_dim " + std::to_string(w / heads) + ")");
   }
 
@@ -1687,22 +1639,22 @@ static int run_encoder(Runner& R, const float* wav, int64_t ldw, const int32_t* 
   const Plan& p = R.p;
   const int B = p.B, L = p.L, d = p.d;
   const long Mrows = (long)B * p.P;
+  const GemmRows rows{(int)Mrows, p.P, p.T};
   bf16_t *X = R.buf(p.X), *Y = R.buf(p.Y), *ATT = R.buf(p.ATT), *QK = R.buf(p.QK), *FF = R.buf(p.FF);
   if (a.encoder_type == WFL_ENC_WHISPER) {
     // ---- Whisper encoder (HF modeling_whisper.py:618-642)
     R.prof_begin();
     const int r = run_logmel(m, p, R.ws, wav, ldw, lens, nullptr, R.s);
-    R.prof_end(2042, 0.96e9 * (double)B * (a.n_mels / 80.0));
+    R.prof_end(PROF_LOGMEL, 0.96e9 * (double)B * (a.n_mels / 80.0));
     if (r) return fail(r, "logmel launch failed");
-    if (R.precise()) R.lo_ok[5] = true;                // (the log-mel kernel wrote the features' low half)
+    if (R.precise()) R.lo_ok[BUF_MEL] = true;                // (the log-mel kernel wrote the features' low half)
     bf16_t* mel = R.buf(p.mel);
     bf16_t* c1 = R.buf(p.c1);
     // conv1 k3 p1: frame t reads mel rows t-1..t+1 = 3*n_mels contiguous channels
-    R.gemm(mel + (long)(p.lead2 - 1) * a.n_mels, a.n_mels, m->conv1, B * p.P2, p.P2, p.T2, c1, d, p.lead2, p.P2, WFL_ACT_GELU);
+    R.gemm(mel + (long)(p.lead2 - 1) * a.n_mels, a.n_mels, m->conv1, {B * p.P2, p.P2, p.T2}, {c1, d, p.lead2, p.P2}, {.act = WFL_ACT_GELU});
     // conv2 k3 s2 p1: frame t reads c1 rows 2t-1..2t+1; pitch(c1) = 2 * pitch(X) makes it one flat GEMM with lda = 2d
-    R.next_lo_out = true;                            // the residual stream starts here
-    R.gemm(c1 + (long)(p.lead2 - 1) * d, 2 * d, m->conv2, (int)Mrows, p.P, p.T, X, d, p.lead, p.P, WFL_ACT_GELU, nullptr, 0,
-           1.f, 0, 0, false, false, m->pos, d);
+    // (lo_out: the residual stream starts here)
+    R.gemm(c1 + (long)(p.lead2 - 1) * d, 2 * d, m->conv2, rows, R.out(X, d), {.act = WFL_ACT_GELU, .pos = m->pos, .ldpos = d, .lo_out = true});
     // fp8 x fp8 (BASELINE configs[4]; WFL_FP8_ACT=0: fp8 weights with bf16 activations, round 2's form): every GEMM operand of a layer
     // is e4m3 -- LayerNorm outputs and the attention context with one scale per row (norm.hip), fc1's GELU output straight from its
     // epilogue with a fixed scale -- and the four GEMMs run on v_mfma_f32_16x16x32_fp8_fp8 (gemm_stream.hip, A8)
@@ -1734,42 +1686,47 @@ static int run_encoder(Runner& R, const float* wav, int64_t ldw, const int32_t* 
         if (R.rc) return;
         R.prof_begin();
         const int r = wfl_launch_rows_fp8(x, d, x_lo, w ? w->g : nullptr, w ? w->b : nullptr, 1e-5f, p.lead, B, p.P, p.T, d, X8, d, rs8, R.s, X8lo);
-        R.prof_end(2043, 0.0);
+        R.prof_end(PROF_LAYERNORM, 0.0);
         if (r) R.rc = fail(r, "rows_fp8 launch failed");
       };
-      auto next_in = [&](const float* row_scale, float stat, const unsigned char* lo_plane) {
-        R.next_a8 = true; R.next_a8_mode = a8_mode; R.next_a8_scale = row_scale; R.next_a8_static = stat; R.next_a8_lo = lo_plane;
+      // the e4m3 operand of the next launch: one scale per row (rows8) or a fixed one, and the plane of the pairs' low halves
+      auto in8 = [&](const float* row_scale, float stat, const unsigned char* lo_plane) {
+        return GemmOpts{.a8 = a8_mode, .a8_scale = row_scale, .a8_static = stat, .a8_lo = lo_plane};
       };
+      const unsigned char* X8lo_rows = X8lo ? X8lo + (long)p.lead * d : nullptr;
+      const bf16_t* X8_rows = (const bf16_t*)(X8 + (long)p.lead * d);
       rows8(X, R.lo_in(X), &L_.ln1);
-      next_in(rs8, 1.f, X8lo ? X8lo + (long)p.lead * d : nullptr);
-      R.gemm((const bf16_t*)(X8 + (long)p.lead * d), d, L_.qkv, (int)Mrows, p.P, p.T, QK, 3 * d, p.lead, p.P, WFL_ACT_NONE);
+      R.gemm(X8_rows, d, L_.qkv, rows, R.out(QK, 3 * d), in8(rs8, 1.f, X8lo_rows));
       // the attention context leaves the attention kernel as e4m3 (a pair in mode 3) with a fixed scale (head_dim 64; other head sizes:
       // bf16, then quantised per row): a context row is a convex combination of value rows, |x| <= max |v|
+      GemmOpts o;
       if (d / a.enc_heads == 64) {
         R.attn(a.enc_heads, nullptr, nullptr, false, X8, d, att_scale, X8lo);
-        next_in(nullptr, 1.0f / att_scale, X8lo ? X8lo + (long)p.lead * d : nullptr);
+        o = in8(nullptr, 1.0f / att_scale, X8lo_rows);
       } else {
         R.attn(a.enc_heads);
         rows8(ATT, nullptr, nullptr);
-        next_in(rs8, 1.f, X8lo ? X8lo + (long)p.lead * d : nullptr);
+        o = in8(rs8, 1.f, X8lo_rows);
       }
-      R.gemm((const bf16_t*)(X8 + (long)p.lead * d), d, L_.out, (int)Mrows, p.P, p.T, X, d, p.lead, p.P, WFL_ACT_NONE, X, d, 1.f);
+      o.res = X; o.ldres = d;
+      R.gemm(X8_rows, d, L_.out, rows, R.out(X, d), o);
       rows8(X, R.lo_in(X), &L_.ln2);
-      next_in(rs8, 1.f, X8lo ? X8lo + (long)p.lead * d : nullptr);
-      R.next_c8 = FF8; R.next_c8_lo = FF8lo; R.next_ldc8 = p.ffw; R.next_c8_inv = ff_scale;
-      R.gemm((const bf16_t*)(X8 + (long)p.lead * d), d, L_.fc1, (int)Mrows, p.P, p.T, FF, p.ffw, p.lead, p.P, WFL_ACT_GELU);
-      next_in(nullptr, 1.0f / ff_scale, FF8lo ? FF8lo + (long)p.lead * p.ffw : nullptr);
-      R.gemm((const bf16_t*)(FF8 + (long)p.lead * p.ffw), p.ffw, L_.fc2, (int)Mrows, p.P, p.T, X, d, p.lead, p.P, WFL_ACT_NONE, X, d, 1.f);
+      o = in8(rs8, 1.f, X8lo_rows);
+      o.act = WFL_ACT_GELU;
+      o.c8 = FF8; o.c8_lo = FF8lo; o.ldc8 = p.ffw; o.c8_inv = ff_scale;
+      R.gemm(X8_rows, d, L_.fc1, rows, R.out(FF, p.ffw), o);
+      o = in8(nullptr, 1.0f / ff_scale, FF8lo ? FF8lo + (long)p.lead * p.ffw : nullptr);
+      o.res = X; o.ldres = d;
+      R.gemm((const bf16_t*)(FF8 + (long)p.lead * p.ffw), p.ffw, L_.fc2, rows, R.out(X, d), o);
     }
     for (int i = 0; !act8 && i < a.enc_layers; ++i) {
       const EncLayer& L_ = m->enc[i];
       R.ln_gemm(X, Y, L_.ln1, L_.qkv, L_.qkv_ln, (int)Mrows, QK, 3 * d, WFL_ACT_NONE);
       R.attn(a.enc_heads);
-      R.next_stats = true;                                            // (consumed by the folded fc1)
-      R.gemm(ATT + (long)p.lead * d, d, L_.out, (int)Mrows, p.P, p.T, X, d, p.lead, p.P, WFL_ACT_NONE, X, d, 1.f);
+      // want_stats: for the folded fc1, then for the next layer's folded q|k|v (the final LayerNorm is a kernel)
+      R.gemm(ATT + (long)p.lead * d, d, L_.out, rows, R.out(X, d), {.res = X, .ldres = d, .want_stats = true});
       R.ln_gemm(X, Y, L_.ln2, L_.fc1, L_.fc1_ln, (int)Mrows, FF, p.ffw, WFL_ACT_GELU);
-      R.next_stats = i + 1 < a.enc_layers;                            // (the next layer's folded q|k|v; the final LayerNorm is a kernel)
-      R.gemm(FF + (long)p.lead * p.ffw, p.ffw, L_.fc2, (int)Mrows, p.P, p.T, X, d, p.lead, p.P, WFL_ACT_NONE, X, d, 1.f);
+      R.gemm(FF + (long)p.lead * p.ffw, p.ffw, L_.fc2, rows, R.out(X, d), {.res = X, .ldres = d, .want_stats = i + 1 < a.enc_layers});
     }
     R.ln(X, Y, m->enc_ln, true);   // encoder output in Y (with lang_id None it is the head's residual stream)
   } else if (a.encoder_type == WFL_ENC_NONE) {
@@ -1791,13 +1748,13 @@ static int run_encoder(Runner& R, const float* wav, int64_t ldw, const int32_t* 
     la.raw = (float*)(R.ws + p.raw); la.clipmax = nullptr;
     R.prof_begin();
     const int r = wfl_launch_melpower(la, a.mel_hop, Y, d, p.lead, p.P, m->pad_split(), m->pad_shift(), R.s);
-    R.prof_end(2042, 0.0);
+    R.prof_end(PROF_LOGMEL, 0.0);
     if (r) return fail(r, "mel launch failed");
-    R.lo_ok[1] = false;
+    R.lo_ok[BUF_Y] = false;
     if (R.precise()) {                                 // the fp32 mel power once more, as hi + lo rows
       const int r2 = wfl_launch_f32_to_rows(la.raw, Y, d, p.lead, B, p.P, p.T, a.n_mels, R.s, m->pad_split(), m->pad_shift(), R.lo_of(Y));
       if (r2) return fail(r2, "f32_to_rows launch failed");
-      R.lo_ok[1] = true;
+      R.lo_ok[BUF_Y] = true;
     }
   } else {
     // ---- WavLM (HF modeling_wavlm.py:1032-1088).  The reference never pads WavLM input: with `lens` every clip keeps its own sample
@@ -1827,7 +1784,7 @@ static int run_encoder(Runner& R, const float* wav, int64_t ldw, const int32_t* 
     if (R.rc) return R.rc;
     {
       Conv0Args c{};
-      if (D) { c.out_lo = R.lo_of(F[0]); R.lo_ok[10] = c.out_lo != nullptr; }
+      if (D) { c.out_lo = R.lo_of(F[0]); R.lo_ok[BUF_FA] = c.out_lo != nullptr; }
       c.wav = wav; c.ldw = ldw; c.L = L; c.wstats = wstats; c.w = m->conv0_w; c.bias = m->conv0_b;
       c.gamma = m->conv0_norm.g; c.beta = m->conv0_norm.b; c.B = B; c.T0 = p.Tl[0]; c.C = C; c.lens = lens;
       c.cstats = (double*)(R.ws + p.cstats); c.cpart = (float*)(R.ws + p.cpart); c.out = F[0]; c.lead = p.leadl[0]; c.P = p.Pl[0];
@@ -1841,7 +1798,8 @@ static int run_encoder(Runner& R, const float* wav, int64_t ldw, const int32_t* 
       const bool group = a.wavlm_group_norm != 0;
       R.zero((i & 1) ? p.FB : p.FA, C, p.leadl[i], p.Pl[i], p.Tl[i], p.tail);
       if (D) R.zero(((i & 1) ? p.FB : p.FA) + D, C, p.leadl[i], p.Pl[i], p.Tl[i], p.tail);
-      R.gemm(in, 2 * C, m->fconv[i - 1], B * p.Pl[i], p.Pl[i], p.Tl[i], out, C, p.leadl[i], p.Pl[i], group ? WFL_ACT_GELU : WFL_ACT_NONE);
+      R.gemm(in, 2 * C, m->fconv[i - 1], {B * p.Pl[i], p.Pl[i], p.Tl[i]}, {out, C, p.leadl[i], p.Pl[i]},
+             {.act = group ? WFL_ACT_GELU : WFL_ACT_NONE});
       if (!group && !R.rc) {
         const int r = wfl_launch_layernorm_act(out, C, out, C, m->fconv_ln[i - 1].g, m->fconv_ln[i - 1].b, 1e-5f, p.leadl[i], B,
                                                p.Pl[i], p.Tl[i], C, 1, R.s, R.lo_in(out), D ? R.lo_of(out) : nullptr, 0, R.levelT[i]);
@@ -1855,18 +1813,17 @@ static int run_encoder(Runner& R, const float* wav, int64_t ldw, const int32_t* 
                                              D ? R.lo_of(feats) : nullptr, 0, R.clipT);
       if (r) return fail(r, "layernorm launch failed");
     }
-    R.next_lo_out = true;
-    R.gemm(feats + (long)p.lead * C, C, m->fp_proj, (int)Mrows, p.P, p.T, X, d, p.lead, p.P);
+    R.gemm(feats + (long)p.lead * C, C, m->fp_proj, rows, R.out(X, d), {.lo_out = true});
     // positional conv: x + GELU(grouped conv k, pad k/2, last step dropped), one contiguous-tap GEMM per group
     {
       const int G = a.wavlm_pos_conv_groups, cpg = d / G, K = a.wavlm_pos_conv_kernel;
       bf16_t* XG = R.buf(p.XG);
       if (!R.rc) {
         int r = wfl_launch_regroup(X, d, G, cpg, p.R, p.lead, B, p.P, p.T, XG, R.s, R.clipT);
-        R.lo_ok[12] = false;
+        R.lo_ok[BUF_XG] = false;
         if (!r && D && R.lo_in(X)) {                 // the low halves in the same layout: the per-group GEMMs' third pass
           r = wfl_launch_regroup(R.lo_in(X), d, G, cpg, p.R, p.lead, B, p.P, p.T, R.lo_of(XG), R.s, R.clipT);
-          R.lo_ok[12] = true;
+          R.lo_ok[BUF_XG] = true;
         }
         if (r) return fail(r, "regroup launch failed");
       }
@@ -1883,13 +1840,13 @@ static int run_encoder(Runner& R, const float* wav, int64_t ldw, const int32_t* 
         pc.clip_T = R.clipT;
         R.prof_begin();
         taken = wfl_launch_posconv(pc, R.s);
-        R.prof_end(2044, 2.0 * (double)B * p.T * (double)d * (double)cpg * (double)K);
+        R.prof_end(PROF_POSCONV, 2.0 * (double)B * p.T * (double)d * (double)cpg * (double)K);
         if (taken < 0) return fail(taken, "posconv launch failed");
-        if (taken == 0) { R.lo_ok[1] = true; R.stats_for = nullptr; }
+        if (taken == 0) { R.lo_ok[BUF_Y] = true; R.stats_for = nullptr; }
       }
       for (int gi = 0; gi < G && taken == 1; ++gi)
-        R.gemm(XG + ((long)gi * p.R + p.lead - K / 2) * 64, 64, m->posconv[gi], (int)Mrows, p.P, p.T, Y + gi * cpg, d, p.lead, p.P,
-               WFL_ACT_GELU, X + gi * cpg, d, 1.f);
+        R.gemm(XG + ((long)gi * p.R + p.lead - K / 2) * 64, 64, m->posconv[gi], rows, R.out(Y + gi * cpg, d),
+               {.act = WFL_ACT_GELU, .res = X + gi * cpg, .ldres = d});
     }
     bf16_t *H = Y, *S = X;                             // current hidden states / scratch
     const bool stable = a.wavlm_stable_layer_norm != 0;
@@ -1908,20 +1865,19 @@ static int run_encoder(Runner& R, const float* wav, int64_t ldw, const int32_t* 
       if (R.rc) break;
       int r = wfl_launch_relpos_gate(A_in, d, p.lead, B, p.P, p.T, a.enc_heads, hd, L_.w8, L_.b8, L_.cst, gate, R.s, R.lo_in(A_in));
       if (r) return fail(r, "relpos_gate launch failed");
-      R.gemm(A_in + (long)p.lead * d, d, L_.qkv, (int)Mrows, p.P, p.T, QK, 3 * d, p.lead, p.P);
+      R.gemm(A_in + (long)p.lead * d, d, L_.qkv, rows, R.out(QK, 3 * d));
       R.attn(a.enc_heads, rtab, gate);
       if (stable) {
         // x = x + attn; x = x + FFN(LN(x))
-        R.next_stats = L_.fc1_ln.ln_s != nullptr;
-        R.gemm(ATT + (long)p.lead * d, d, L_.out, (int)Mrows, p.P, p.T, H, d, p.lead, p.P, WFL_ACT_NONE, H, d, 1.f);
+        R.gemm(ATT + (long)p.lead * d, d, L_.out, rows, R.out(H, d), {.res = H, .ldres = d, .want_stats = L_.fc1_ln.ln_s != nullptr});
         R.ln_gemm(H, S, L_.ln2, L_.fc1, L_.fc1_ln, (int)Mrows, FF, p.ffw, WFL_ACT_GELU);
-        R.gemm(FF + (long)p.lead * p.ffw, p.ffw, L_.fc2, (int)Mrows, p.P, p.T, H, d, p.lead, p.P, WFL_ACT_NONE, H, d, 1.f);
+        R.gemm(FF + (long)p.lead * p.ffw, p.ffw, L_.fc2, rows, R.out(H, d), {.res = H, .ldres = d});
       } else {
         // x = LN(x + attn); x = LN_final(x + FFN(x))
-        R.gemm(ATT + (long)p.lead * d, d, L_.out, (int)Mrows, p.P, p.T, S, d, p.lead, p.P, WFL_ACT_NONE, H, d, 1.f);
+        R.gemm(ATT + (long)p.lead * d, d, L_.out, rows, R.out(S, d), {.res = H, .ldres = d});
         R.ln(S, H, L_.ln1, true);
-        R.gemm(H + (long)p.lead * d, d, L_.fc1, (int)Mrows, p.P, p.T, FF, p.ffw, p.lead, p.P, WFL_ACT_GELU);
-        R.gemm(FF + (long)p.lead * p.ffw, p.ffw, L_.fc2, (int)Mrows, p.P, p.T, S, d, p.lead, p.P, WFL_ACT_NONE, H, d, 1.f);
+        R.gemm(H + (long)p.lead * d, d, L_.fc1, rows, R.out(FF, p.ffw), {.act = WFL_ACT_GELU});
+        R.gemm(FF + (long)p.lead * p.ffw, p.ffw, L_.fc2, rows, R.out(S, d), {.res = H, .ldres = d});
         R.ln(S, H, L_.ln2, true);
       }
     }
@@ -1930,7 +1886,7 @@ static int run_encoder(Runner& R, const float* wav, int64_t ldw, const int32_t* 
       R.stats_for = nullptr;
       if (wfl_launch_copy16(Y, H, p.R * d * 2, R.s)) return fail(-3, "copy launch failed");
       if (R.lo_in(H) && wfl_launch_copy16(R.lo_of(Y), R.lo_of(H), p.R * d * 2, R.s)) return fail(-3, "copy launch failed");
-      R.lo_ok[1] = R.lo_in(H) != nullptr;
+      R.lo_ok[BUF_Y] = R.lo_in(H) != nullptr;
     }
   }
   return R.rc;
@@ -1956,6 +1912,7 @@ static int run_head(Runner& R, const int32_t* lang_id, int32_t lang_mode, float 
   const Plan& p = R.p;
   const int B = p.B, d = p.d;
   const long Mrows = (long)B * p.P;
+  const GemmRows rows{(int)Mrows, p.P, p.T};
   bf16_t *X = R.buf(p.X), *Y = R.buf(p.Y), *ATT = R.buf(p.ATT), *QK = R.buf(p.QK), *FF = R.buf(p.FF);
   // ---- head (model.py:176-194); with WFL_LANG_AVERAGE it runs once per language on the same encoder output
   const int n_pass = lang_mode == WFL_LANG_AVERAGE ? (int)m->avg_langs.size() : 1;
@@ -1987,17 +1944,15 @@ static int run_head(Runner& R, const int32_t* lang_id, int32_t lang_mode, float 
         if (fr) return fail(fr, "fill launch failed");
         idx = lang_dev;
       }
-      R.next_lo_out = true;
-      R.gemm(ENC + (long)p.lead * d, d, m->lang, (int)Mrows, p.P, p.T, X, d, p.lead, p.P, WFL_ACT_NONE, nullptr, 0, 1.f, 0, 0,
-             false, false, nullptr, 0, m->lang_table, idx, d);
+      R.gemm(ENC + (long)p.lead * d, d, m->lang, rows, R.out(X, d),
+             {.clip_bias = m->lang_table, .clip_idx = idx, .clip_ld = d, .lo_out = true});
       H = X; S = Y;
     }
     if (a.enable_bilstm) {
       const int Hh = d / 2;
       float* GX = (float*)(R.ws + p.gx);
       for (int layer = 0; layer < a.bilstm_layers; ++layer) {
-        R.gemm(H + (long)p.lead * d, d, m->lstm_in[layer], (int)Mrows, p.P, p.T, GX, 8 * Hh, p.lead, p.P, WFL_ACT_NONE, nullptr, 0,
-               1.f, 0, 0, false, true);
+        R.gemm(H + (long)p.lead * d, d, m->lstm_in[layer], rows, R.out(GX, 8 * Hh), {.out_f32 = true});
         if (R.rc) return R.rc;
         LstmArgs la{};
         la.gx = GX; la.ldgx = 8 * Hh; la.whh = m->lstm_whh[layer]; la.out = S; la.ldo = d; la.lead = p.lead;
@@ -2011,7 +1966,7 @@ static int run_head(Runner& R, const int32_t* lang_id, int32_t lang_mode, float 
         { const int si = R.lo_idx(S); if (si >= 0) R.lo_ok[si] = split; }
         R.prof_begin();
         const int lr = wfl_launch_lstm(la, R.ws + p.lstm_x, R.s);
-        R.prof_end(2041, 2.0 * (double)B * p.T * 2.0 * 4.0 * (double)Hh * (double)Hh);
+        R.prof_end(PROF_LSTM, 2.0 * (double)B * p.T * 2.0 * 4.0 * (double)Hh * (double)Hh);
         if (lr) return fail(lr, lr == -5 ? "BiLSTM: hidden size too large (more than 64 slice workgroups per direction)"
                                           : "lstm launch failed (" + std::to_string(lr) + ")");
         std::swap(H, S);
@@ -2021,36 +1976,35 @@ static int run_head(Runner& R, const int32_t* lang_id, int32_t lang_mode, float 
       const ConfLayer& C = m->conf[i];
       // x = x + 0.5 * FF1(x)
       R.ln_gemm(H, S, C.ff1_ln, C.ff1_a, C.ff1_a_ln, (int)Mrows, FF, p.ffw, WFL_ACT_GELU);
-      R.gemm(FF + (long)p.lead * p.ffw, p.ffw, C.ff1_b, (int)Mrows, p.P, p.T, H, d, p.lead, p.P, WFL_ACT_NONE, H, d, 0.5f);
+      R.gemm(FF + (long)p.lead * p.ffw, p.ffw, C.ff1_b, rows, R.out(H, d), {.res = H, .ldres = d, .alpha = 0.5f});
       // x = LN1(x + MHA(x))
       if (p.da == d) {
-        R.gemm(H + (long)p.lead * d, d, C.qkv, (int)Mrows, p.P, p.T, QK, 3 * d, p.lead, p.P);
+        R.gemm(H + (long)p.lead * d, d, C.qkv, rows, R.out(QK, 3 * d));
         R.attn(a.conformer_heads);
-        R.gemm(ATT + (long)p.lead * d, d, C.out, (int)Mrows, p.P, p.T, S, d, p.lead, p.P, WFL_ACT_NONE, H, d, 1.f);
+        R.gemm(ATT + (long)p.lead * d, d, C.out, rows, R.out(S, d), {.res = H, .ldres = d});
       } else {
-        R.gemm(H + (long)p.lead * d, d, C.qkv, (int)Mrows, p.P, p.T, R.buf(p.QKp), 3 * p.da, p.lead, p.P);
+        R.gemm(H + (long)p.lead * d, d, C.qkv, rows, R.out(R.buf(p.QKp), 3 * p.da));
         R.attn(a.conformer_heads, nullptr, nullptr, true);
-        R.gemm(R.buf(p.ATTp) + (long)p.lead * p.da, p.da, C.out, (int)Mrows, p.P, p.T, S, d, p.lead, p.P, WFL_ACT_NONE, H, d, 1.f);
+        R.gemm(R.buf(p.ATTp) + (long)p.lead * p.da, p.da, C.out, rows, R.out(S, d), {.res = H, .ldres = d});
       }
       R.ln(S, H, C.ln1, true);
       // x = x + pw2(GELU(BN(conv_k(GLU(pw1(LN2(x)))))))
       R.ln(H, S, C.ln2);
-      R.gemm(S + (long)p.lead * d, d, C.pw1, (int)Mrows, p.P, p.T, ATT, d, p.lead, p.P, WFL_ACT_NONE, nullptr, 0, 1.f, 0, 0, true);
+      R.gemm(S + (long)p.lead * d, d, C.pw1, rows, R.out(ATT, d), {.glu = true});
       // dense k-tap conv: taps are adjacent rows (cin = d, tap stride = one row) -> the streaming GEMM's tap-stationary mode
-      R.gemm(ATT + (long)(p.lead - a.conformer_kernel / 2) * d, d, C.conv, (int)Mrows, p.P, p.T, S, d, p.lead, p.P, WFL_ACT_GELU,
-             nullptr, 0, 1.f, d, d);
-      R.next_stats = true;                                            // (consumed by the folded ff2)
-      R.gemm(S + (long)p.lead * d, d, C.pw2, (int)Mrows, p.P, p.T, H, d, p.lead, p.P, WFL_ACT_NONE, H, d, 1.f);
+      R.gemm(ATT + (long)(p.lead - a.conformer_kernel / 2) * d, d, C.conv, rows, R.out(S, d),
+             {.act = WFL_ACT_GELU, .cin = d, .tap_stride = d});
+      // want_stats: for the folded ff2, then for the next block's folded ff1
+      R.gemm(S + (long)p.lead * d, d, C.pw2, rows, R.out(H, d), {.res = H, .ldres = d, .want_stats = true});
       // x = x + 0.5 * FF2(x)
       R.ln_gemm(H, S, C.ff2_ln, C.ff2_a, C.ff2_a_ln, (int)Mrows, FF, p.ffw, WFL_ACT_GELU);
-      R.next_stats = i + 1 < a.n_conformer;                           // (the next block's folded ff1)
-      R.gemm(FF + (long)p.lead * p.ffw, p.ffw, C.ff2_b, (int)Mrows, p.P, p.T, H, d, p.lead, p.P, WFL_ACT_NONE, H, d, 0.5f);
+      R.gemm(FF + (long)p.lead * p.ffw, p.ffw, C.ff2_b, rows, R.out(H, d),
+             {.res = H, .ldres = d, .alpha = 0.5f, .want_stats = i + 1 < a.n_conformer});
     }
     if (a.enable_dilated) {
       for (int i = 0; i < a.dilated_depth; ++i) {
         const int dil = 1 << i, pad = dil * (a.dilated_kernel - 1) / 2;
-        R.gemm(H + (long)(p.lead - pad) * d, d, m->dil[i], (int)Mrows, p.P, p.T, S, d, p.lead, p.P, WFL_ACT_RELU, nullptr, 0, 1.f,
-               d, (long)dil * d);
+        R.gemm(H + (long)(p.lead - pad) * d, d, m->dil[i], rows, R.out(S, d), {.act = WFL_ACT_RELU, .cin = d, .tap_stride = (long)dil * d});
         std::swap(H, S);
       }
     }
@@ -2062,27 +2016,22 @@ static int run_head(Runner& R, const int32_t* lang_id, int32_t lang_mode, float 
     // input halves are taps one buffer apart; without a valid low half the second pass is the plain K = d one)
     static const bool cls_one = std::getenv("WFL_CLS_TWO_LAUNCHES") == nullptr;       // (A/B hook: rounds 2-3's two-launch form)
     const bf16_t* hlo = R.lo_in(H);
+    const bf16_t* Hrows = H + (long)p.lead * d;
+    const GemmOut lg_out{lg_pass, ldlg, 0, p.T};                    // compact rows: no halo
+    const double cls_flops = 2.0 * (double)B * p.T * (double)a.num_classes * (double)d;
     if (hlo && m->cls3.W && cls_one) {
       // one launch (round 3): K' = 3 d over the tap segments [h_hi | h_lo | h_hi] against [W_hi | W_hi | W_lo], bias once, the sum never
       // leaves the accumulators
-      R.next_flops = 2.0 * (double)B * p.T * (double)a.num_classes * (double)d;
-      R.next_tap_wrap = 1;
-      R.next_seg_off = (long)(hlo - H);
-      R.gemm(H + (long)p.lead * d, d, m->cls3, (int)Mrows, p.P, p.T, lg_pass, ldlg, 0, p.T, WFL_ACT_NONE, nullptr, 0, 1.f, d, 0, false, true);
+      R.gemm(Hrows, d, m->cls3, rows, lg_out, {.cin = d, .out_f32 = true, .flops = cls_flops, .tap_wrap = 1, .seg_off = (long)(hlo - H)});
     } else {
-      R.next_flops = 0.0;
-      R.gemm(H + (long)p.lead * d, d, m->cls_lo, (int)Mrows, p.P, p.T, lg_pass, ldlg, 0, p.T, WFL_ACT_NONE, nullptr, 0, 1.f,
-             0, 0, false, true);
-      R.next_acc_f32 = true;
-      R.next_flops = 2.0 * (double)B * p.T * (double)a.num_classes * (double)d;
+      R.gemm(Hrows, d, m->cls_lo, rows, lg_out, {.out_f32 = true, .flops = 0.0});       // (the product is booked once, below)
       if (hlo)
-        R.gemm(H + (long)p.lead * d, d, m->cls_hi2, (int)Mrows, p.P, p.T, lg_pass, ldlg, 0, p.T, WFL_ACT_NONE, nullptr, 0,
-               1.f, d, (long)(hlo - H), false, true);
+        R.gemm(Hrows, d, m->cls_hi2, rows, lg_out,
+               {.cin = d, .tap_stride = (long)(hlo - H), .out_f32 = true, .acc_f32 = true, .flops = cls_flops});
       else
-        R.gemm(H + (long)p.lead * d, d, m->cls, (int)Mrows, p.P, p.T, lg_pass, ldlg, 0, p.T, WFL_ACT_NONE, nullptr, 0, 1.f,
-               0, 0, false, true);
+        R.gemm(Hrows, d, m->cls, rows, lg_out, {.out_f32 = true, .acc_f32 = true, .flops = cls_flops});
     }
-    R.gemm(H + (long)(p.lead - 1) * d, d, m->off1, (int)Mrows, p.P, p.T, S, d, p.lead, p.P, WFL_ACT_GELU, nullptr, 0, 1.f, d, d);
+    R.gemm(H + (long)(p.lead - 1) * d, d, m->off1, rows, R.out(S, d), {.act = WFL_ACT_GELU, .cin = d, .tap_stride = d});
     if (R.rc) return R.rc;
     TagArgs t{};
     t.rows = B * p.T; t.C = a.num_classes; t.threshold = threshold; t.o_id = a.o_id;
@@ -2189,7 +2138,7 @@ int32_t wfl_head(wfl_model* m, const float* hidden, int32_t B, int32_t T, const 
   const int r = wfl_launch_f32_to_rows(hidden, R.buf(p.Y), p.d, p.lead, B, p.P, p.T, m->dv, R.s, m->pad_split(), m->pad_shift(),
                                        R.precise() ? R.lo_of(R.buf(p.Y)) : nullptr);
   if (r) return fail(r, "f32_to_rows launch failed");
-  if (R.precise()) R.lo_ok[1] = true;
+  if (R.precise()) R.lo_ok[BUF_Y] = true;
   return run_head(R, lang_id, lang_mode, threshold, ids, argmax, maxprob, offsets, logits, status);
 }
 
