@@ -30,7 +30,7 @@ def main():
     ap.add_argument("--rate", type=int, default=16000, help="sample rate of the files on disk (other than 16000: every file takes the "
                     "general ingest path -- decode, resample, chunk -- and the end-to-end rate is printed alone)")
     ap.add_argument("--wavlm", action="store_true", help="BASELINE configs[2] (WavLM-large + 2-layer BiLSTM + dilated stack) on files of "
-                    "6-10 s: the ragged by-length loop (Labeler._forward_items_by_length); prints the end-to-end rate only")
+                    "6-10 s: the ragged by-length batches (Labeler._forward_items_by_length) on the pipelined loop (Labeler._pipeline); prints the end-to-end rate only")
     args = ap.parse_args()
     d = tempfile.mkdtemp(prefix="wfl_e2e_")
     cfg = synth.baseline_config(2) if args.wavlm else (synth.base_config("whisper") if args.full_head else synth.baseline_config(1))

@@ -2,7 +2,7 @@
 """Diagnostic (not product): what the waveforms' PCIe crossing costs the cfg2 step, and which part of it -- the copy itself beside the
 forwards, the events that order it, or the stream it is issued from.  Same model / batch / loop as bench.py's with-H2D leg.
 modes: resident | copy_unused (copies run, forwards read the resident batch) | events_only | copy_stream (bench.py's leg) |
-       same_stream (copy on the forward's own stream, as Labeler._run_batches does) | copy_stream_ahead2 (ring of nfl + 2 device buffers)"""
+       same_stream (copy on the forward's own stream, as Labeler._pipeline does) | copy_stream_ahead2 (ring of nfl + 2 device buffers)"""
 import os
 import sys
 import time

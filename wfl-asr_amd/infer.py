@@ -17,12 +17,15 @@ from __future__ import annotations
 import math
 import os
 import sys
+from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 import torch
 import yaml
 
+from . import align as AL
 from . import audio as A
+from . import decode as DC
 from . import native_post as npost
 from . import postprocess as pp
 from .tagger import BIOPhonemeTagger, raise_on_status
@@ -37,6 +40,11 @@ CHUNK_SAMPLES = int(MAX_SEGMENT_DURATION * 16000)     # at 16 kHz; a Labeler's o
 def load_config(config_path="config.yaml"):
     with open(config_path, "r") as f:
         return yaml.safe_load(f)
+
+
+def _worker_threads(n_tasks=16):
+    """Threads of a pool of host workers (the native loaders release the GIL)."""
+    return max(1, min(16, os.cpu_count() or 1, n_tasks))
 
 
 def pick_device(device="cuda") -> torch.device:
@@ -91,216 +99,164 @@ class Labeler:
             batch_size = int(os.environ.get("WFL_BATCH_SIZE", "64" if self.model.head_cfg["enable_bilstm"] else "16"))
         self.batch_size = int(batch_size)
         self.use_graph = bool(use_graph)
-        self._pinned = None
         self.n_inflight = self.model.batches_in_flight()   # batches on the GPU at once: stream + workspace slot each
         self._table = npost.LabelTable(self.labels)          # native BIO decode works on ids (csrc/hostpost.hip)
         self._streams = None
+        self._pinned = {}                                    # dtype -> ring of flat pinned staging buffers (_pinned_ring)
+        self._names_cache = {}                               # _names_for
+        self._decode_table = None                            # decode.class_table(labels), built by the first grammar decode
+        self._wave_items = None                              # chunks per wave of files; None: _wave()
 
     # ------------------------------------------------------------------ the batched loop
     def _forward_items(self, items, lang_id, threshold):
-        """items: list of float32 arrays (<= 480000 samples each) -> list of (ids[T], offsets[T,2]) numpy."""
+        """items: list of float32 arrays (<= 480000 samples each) -> list of (ids[T], offsets[T,2]) numpy, in item order."""
         if self.model.encoder_type != "whisper":
             return self._forward_items_by_length(items, lang_id, threshold)
         out = [None] * len(items)
-        Bs = self.batch_size
-        L = self.chunk_samples
+        Bs, L = self.batch_size, self.chunk_samples
 
         def fill(k, host):
-            chunk = items[k * Bs:(k + 1) * Bs]
             lens = np.zeros(Bs, dtype=np.int32)
             rows = host.numpy()                  # (a numpy row assignment is a plain memcpy, 0.2 ms per 30 s item; the same through
-            for i, x in enumerate(chunk):        #  torch's indexing was measured at 1-18 ms)
+            for i, x in enumerate(items[k * Bs:(k + 1) * Bs]):   # torch's indexing was measured at 1-18 ms)
                 n = min(len(x), L)
                 rows[i, :n] = x[:n]
                 lens[i] = n
-            return lens, len(chunk)
+            return lens
 
-        def take(k, n, ids, offs):
-            for i in range(n):
+        def take(k, ids, offs):
+            for i in range(min(Bs, len(items) - k * Bs)):
                 out[k * Bs + i] = (ids[i].copy(), offs[i].copy())
 
-        self._run_batches((len(items) + Bs - 1) // Bs, fill, take, lang_id, threshold)
+        self._pipeline([(Bs, L, self.model.num_frames(L))] * -(-len(items) // Bs), fill, take, lang_id, threshold, graph=self.use_graph)
         return out
 
-    def _run_batches(self, n_batches, fill, take, lang_id, threshold, pinned_in=None, upload=None):
-        """The pipelined hot loop.  NS = `n_inflight` batches in flight on the GPU (two, or three for a BiLSTM behind a small
-        encoder -- tagger.batches_in_flight; stream and workspace slot k % NS, own pinned output buffer), one more being filled:
-        `fill(k, pinned_rows) -> (lens, rows used)` runs on a worker thread one batch ahead of the launches (the native loader
-        releases the GIL), into a ring of NS + 1 pinned input buffers, each guarded by the event of its last host-to-device
-        copy; the main thread launches batch k and unpacks batch k - NS (`take(k, rows, ids[B, T], offsets[B, T, 2])`, views
-        into pinned memory: copy what you keep).  With everything on one thread (round 2's first half)
-        the end-to-end rate of a folder of 30 s files was 82 k audio-s/s against 123 k for batches already resident."""
-        from concurrent.futures import ThreadPoolExecutor
-        Bs = self.batch_size
-        L = self.chunk_samples
-        T = self.model.num_frames(L)
+    def _pinned_ring(self, n, dtype, capacity):
+        """n flat pinned buffers of `dtype` with at least `capacity` elements each: the cached ones while they still fit (pinning
+        costs milliseconds; the loops view them per batch)."""
+        ring = self._pinned.get(dtype)
+        if ring is None or len(ring) != n or ring[0].numel() < capacity:
+            ring = self._pinned[dtype] = [torch.zeros(capacity, dtype=dtype).pin_memory() for _ in range(n)]
+        return ring
+
+    def _pipeline(self, jobs, fill, take, lang_id, threshold, dtype=torch.float32, upload=None, graph=False):
+        """The pipelined hot loop, for every encoder.  jobs[k] = (rows of forward k, values per staged row, frames per row): constant
+        for Whisper (`batch_size` rows of `chunk_samples`, unused rows at lens 0), per batch for the by-length path.
+
+        NS = `n_inflight` batches in flight on the GPU (two, or three for a BiLSTM behind a small encoder -- tagger.batches_in_flight;
+        stream and workspace slot k % NS, own pinned output buffer), one more being filled: `fill(k, host[rows, values]) -> lens` (None:
+        every row is full) runs on a worker thread one batch ahead of the launches (the native loader releases the GIL), into a ring of
+        NS + 1 pinned input buffers of `dtype`, each guarded by the event of its last host-to-device copy; the main thread launches batch
+        k and unpacks batch k - NS.  With everything on one thread (round 2's first half) the end-to-end rate of a folder of 30 s files
+        was 82 k audio-s/s against 123 k for batches already resident.  The staging is flat pinned memory sized for the largest job and
+        viewed per job (_pinned_ring).
+
+        upload(host, lens, slot, stream) -> (device batch, lens): another staging format, run inside the slot's stream context (the GPU
+        ingest path: int16 PCM rows, resampled on the device -- _label_resampled); default: float32 waveform rows copied as they are.
+        graph: captured forwards (Whisper only), one slot, on the current stream.
+
+        What callers rely on: `fill` of batch k + 1 runs while batch k is launched; `take(k, ids[rows, T], offsets[rows, T, 2])` is
+        called in ascending k, after the forward's device-side status word (it rides behind the tags) went through raise_on_status,
+        with views into pinned memory that are valid only until it returns: copy what you keep.
+
+        (Two WavLM-base forwards in flight used to disturb each other now and then: a packed-f32 instruction form in the group-norm
+        conv0 kernel that is unsafe beside another wave's MFMAs -- DESIGN.md section 7; the form is gone and the build refuses it;
+        `test_two_wavlm_forwards_in_flight_do_not_disturb_each_other` guards the loop.)"""
+        if not jobs:
+            return
         NS = self.n_inflight
         NI = NS + 1
-        # pinned_in / upload: another staging format (the GPU ingest path: int16 PCM rows, resampled on the device -- _label_resampled);
-        # default: float32 waveform rows copied as they are
-        if pinned_in is None and (self._pinned is None or len(self._pinned) != NI or self._pinned[0].shape[0] != Bs):
-            self._pinned = [torch.zeros(Bs, L, dtype=torch.float32).pin_memory() for _ in range(NI)]
-        if getattr(self, "_pinned_out", None) is None or len(self._pinned_out) != NS or self._pinned_out[0].numel() != Bs * T * 4 + 1:
-            self._pinned_out = [torch.empty(Bs * T * 4 + 1, dtype=torch.int32).pin_memory() for _ in range(NS)]
-        pin = pinned_in if pinned_in is not None else self._pinned
-        assert len(pin) == NI
-        self._ensure_streams()
-        use_pipe = not self.use_graph
+        pin_in = self._pinned_ring(NI, dtype, max(rows * width for rows, width, _ in jobs))
+        pin_out = self._pinned_ring(NS, torch.int32, max(rows * T * 4 + 1 for rows, _, T in jobs))
+        if self._streams is None or len(self._streams) != NS:
+            self._streams = [torch.cuda.Stream(self.device) for _ in range(NS)]
         pending = [None] * NS
         copied = [None] * NI                               # event behind the last H2D copy out of input buffer i
 
-        def finish(slot):
-            job = pending[slot]
-            if job is None:
-                return
-            k, n, ev = job
-            ev.synchronize()
-            blob = self._pinned_out[slot].numpy()
-            nn = Bs * T
-            raise_on_status(int(blob[4 * nn]))             # the forward's device-side error word rides behind the tags
-            take(k, n, blob[0:nn].reshape(Bs, T), blob[2 * nn:4 * nn].view(np.float32).reshape(Bs, T, 2))
-            pending[slot] = None
+        def staged(k):
+            rows, width, _ = jobs[k]
+            return pin_in[k % NI][:rows * width].view(rows, width)
 
         def fill_job(k):
-            ib = k % NI
-            if copied[ib] is not None:
-                copied[ib].synchronize()                   # (NS + 1 batches back: long done)
-            return fill(k, pin[ib])
+            if copied[k % NI] is not None:
+                copied[k % NI].synchronize()               # (NS + 1 batches back: long done)
+            return fill(k, staged(k))
 
-        if n_batches <= 0:
-            return
+        def finish(slot):
+            if pending[slot] is None:
+                return
+            k, ev = pending[slot]
+            ev.synchronize()
+            rows, _, T = jobs[k]
+            nn = rows * T
+            blob = pin_out[slot].numpy()
+            raise_on_status(int(blob[4 * nn]))
+            take(k, blob[0:nn].reshape(rows, T), blob[2 * nn:4 * nn].view(np.float32).reshape(rows, T, 2))
+            pending[slot] = None
+
         with ThreadPoolExecutor(max_workers=1) as pool:
             fut = pool.submit(fill_job, 0)
-            for k in range(n_batches):
-                lens, n = fut.result()
-                if k + 1 < n_batches:
+            for k, (rows, _, T) in enumerate(jobs):
+                lens = fut.result()
+                if k + 1 < len(jobs):
                     fut = pool.submit(fill_job, k + 1)
-                slot = k % NS if use_pipe else 0
+                slot = 0 if graph else k % NS
                 finish(slot)                               # the output buffer and workspace of this slot are free again
-                host = pin[k % NI]
-                stream = self._streams[slot] if use_pipe else torch.cuda.current_stream(self.device)
+                stream = torch.cuda.current_stream(self.device) if graph else self._streams[slot]
                 with torch.cuda.stream(stream):
                     if upload is None:
-                        dev_wav = host.to(self.device, non_blocking=True)
+                        dev_wav = staged(k).to(self.device, non_blocking=True)
                     else:
-                        dev_wav, lens = upload(host, lens, slot, stream)
-                    ev_in = torch.cuda.Event()
-                    ev_in.record(stream)
-                    copied[k % NI] = ev_in
-                    res = self.model.label(dev_wav, None if lang_id is None else [lang_id] * Bs, threshold=threshold, lens=lens,
-                                           average_languages=lang_id is None, graph=self.use_graph, slot=slot)
-                    self._pinned_out[slot].copy_(res.packed, non_blocking=True)
+                        dev_wav, lens = upload(staged(k), lens, slot, stream)
+                    copied[k % NI] = torch.cuda.Event()
+                    copied[k % NI].record(stream)
+                    res = self.model.label(dev_wav, None if lang_id is None else [lang_id] * rows, threshold=threshold, lens=lens,
+                                           average_languages=lang_id is None, graph=graph, slot=slot)
+                    pin_out[slot][:rows * T * 4 + 1].copy_(res.packed, non_blocking=True)
                     ev = torch.cuda.Event()
                     ev.record(stream)
-                pending[slot] = (k, n, ev)
-            for k in range(max(0, n_batches - NS), n_batches):   # what is still in flight, oldest first
-                finish(k % NS if use_pipe else 0)
-
-    def _ensure_streams(self):
-        if self._streams is None or len(self._streams) != self.n_inflight:
-            self._streams = [torch.cuda.Stream(self.device) for _ in range(self.n_inflight)]
+                pending[slot] = (k, ev)
+            for k in range(max(0, len(jobs) - NS), len(jobs)):   # what is still in flight, oldest first
+                finish(0 if graph else k % NS)
 
     def _forward_items_by_length(self, items, lang_id, threshold):
         """WavLM and the mel front-end: the frame count follows the clip length and the reference never pads their input (padding
         would change the waveform / GroupNorm statistics, the unmasked attention and where the backward LSTM starts).  A batch may
         still hold clips of different lengths: the library takes per-clip sample counts (`lens`) and carries every clip's own frame
         count through the whole forward, so each row comes out as if labelled alone (csrc/model.hip, Runner::clipT).  Clips are
-        sorted by length so that a batch wastes little on its shorter rows; `WFL_RAGGED=0` goes back to one length per batch.
-        Same pipeline as `_run_batches`: `n_inflight` batches in flight on their streams / workspace slots, pinned staging both ways, the
-        status word read with the tags.  (Two WavLM-base forwards in flight used to disturb each other now and then: a packed-f32
-        instruction form in the group-norm conv0 kernel that is unsafe beside another wave's MFMAs -- DESIGN.md section 7; the form is
-        gone and the build refuses it; `test_two_wavlm_forwards_in_flight_do_not_disturb_each_other` guards the loop.)"""
+        sorted by length so that a batch wastes little on its shorter rows; `WFL_RAGGED=0` goes back to one length per batch."""
         out = [None] * len(items)
         Bs = self.batch_size
-        ragged = os.environ.get("WFL_RAGGED", "1") != "0"
         frames = [self.model.num_frames(len(x)) for x in items]
         for i, t in enumerate(frames):
             if t <= 0:
                 raise ValueError(f"clip {i} is too short for the {self.model.encoder_type} front-end ({len(items[i])} samples)")
-        if ragged:
+        if os.environ.get("WFL_RAGGED", "1") != "0":
             order = sorted(range(len(items)), key=lambda i: -len(items[i]))
-            jobs = [order[s:s + Bs] for s in range(0, len(order), Bs)]
+            batches = [order[s:s + Bs] for s in range(0, len(order), Bs)]
         else:
             by_len = {}
             for i, x in enumerate(items):
                 by_len.setdefault(len(x), []).append(i)
-            jobs = [idxs[s:s + Bs] for n, idxs in by_len.items() for s in range(0, len(idxs), Bs)]
-        self._ensure_streams()
-        NS = self.n_inflight
-        NI = NS + 1
-        if not jobs:
-            return out
-        # pinned staging sized once for the largest batch (round 2 grew the buffers lazily inside the loop): NS + 1 input buffers, so that
-        # a worker thread fills batch k + 1 while the main thread launches batch k (the same pipeline as _run_batches), NS output buffers
-        geom = []
-        for sel in jobs:
+            batches = [idxs[s:s + Bs] for n, idxs in by_len.items() for s in range(0, len(idxs), Bs)]
+        jobs = []
+        for sel in batches:
             n = max(len(items[i]) for i in sel)
-            geom.append((n, self.model.num_frames(n), all(len(items[i]) == n for i in sel)))
-        need_in = max(len(sel) * g[0] for sel, g in zip(jobs, geom))
-        need_out = max(len(sel) * g[1] * 4 + 1 for sel, g in zip(jobs, geom))
-        cache = getattr(self, "_pinned_ragged", None)
-        if cache is None or len(cache[0]) != NI or cache[0][0].numel() < need_in or len(cache[1]) != NS or cache[1][0].numel() < need_out:
-            cache = ([torch.empty(need_in, dtype=torch.float32).pin_memory() for _ in range(NI)],
-                     [torch.empty(need_out, dtype=torch.int32).pin_memory() for _ in range(NS)])
-            self._pinned_ragged = cache
-        pin_in, pin_out = cache
-        pending = [None] * NS
-        copied = [None] * NI                               # event behind the last H2D copy out of input buffer i
+            jobs.append((len(sel), n, self.model.num_frames(n)))
 
-        def finish(slot):
-            job = pending[slot]
-            if job is None:
-                return
-            sel, T, ev = job
-            ev.synchronize()
-            nn = len(sel) * T
-            blob = pin_out[slot].numpy()
-            raise_on_status(int(blob[4 * nn]))
-            ids = blob[0:nn].reshape(len(sel), T)
-            offs = blob[2 * nn:4 * nn].view(np.float32).reshape(len(sel), T, 2)
-            for j, i in enumerate(sel):
-                out[i] = (ids[j, :frames[i]].copy(), offs[j, :frames[i]].copy())
-            pending[slot] = None
-
-        def fill_job(k):
-            sel = jobs[k]
-            n, T, same = geom[k]
-            ib = k % NI
-            if copied[ib] is not None:
-                copied[ib].synchronize()                   # (NS + 1 batches back: long done)
-            host = pin_in[ib][:len(sel) * n].view(len(sel), n)
+        def fill(k, host):
             rows = host.numpy()
-            for j, i in enumerate(sel):
-                m = len(items[i])
-                rows[j, :m] = items[i]
-                if m < n:
-                    rows[j, m:] = 0.0                      # (behind a shorter clip: never read -- `lens` -- but keep the buffer defined)
-            return host, (None if same else np.array([len(items[i]) for i in sel], np.int32))
+            lens = np.array([len(items[i]) for i in batches[k]], np.int32)
+            for j, i in enumerate(batches[k]):
+                rows[j, :lens[j]] = items[i]
+                rows[j, lens[j]:] = 0.0                    # (behind a shorter clip: never read -- `lens` -- but keep the buffer defined)
+            return None if (lens == host.shape[1]).all() else lens
 
-        from concurrent.futures import ThreadPoolExecutor
-        with ThreadPoolExecutor(max_workers=1) as pool:
-            fut = pool.submit(fill_job, 0)
-            for k, sel in enumerate(jobs):
-                host, lens = fut.result()
-                if k + 1 < len(jobs):
-                    fut = pool.submit(fill_job, k + 1)
-                slot = k % NS
-                finish(slot)
-                n, T, same = geom[k]
-                need_o = len(sel) * T * 4 + 1
-                with torch.cuda.stream(self._streams[slot]):
-                    wav = host.to(self.device, non_blocking=True)
-                    ev_in = torch.cuda.Event()
-                    ev_in.record(self._streams[slot])
-                    copied[k % NI] = ev_in
-                    res = self.model.label(wav, None if lang_id is None else [lang_id] * len(sel), threshold=threshold, lens=lens,
-                                           average_languages=lang_id is None, slot=slot)
-                    pin_out[slot][:need_o].copy_(res.packed, non_blocking=True)
-                    ev = torch.cuda.Event()
-                    ev.record(self._streams[slot])
-                pending[slot] = (sel, T, ev)
-            for k in range(max(0, len(jobs) - NS), len(jobs)):
-                finish(k % NS)
+        def take(k, ids, offs):
+            for j, i in enumerate(batches[k]):
+                out[i] = (ids[j, :frames[i]].copy(), offs[j, :frames[i]].copy())
+
+        self._pipeline(jobs, fill, take, lang_id, threshold)
         return out
 
     def _lang_name(self, lang_id):
@@ -316,9 +272,7 @@ class Labeler:
         the phoneme table once instead of to every segment; phonemes that map to the same string share an index, so the
         equal-neighbour merge compares exactly what the reference's string comparison compares."""
         key = lang_name if (self.merge_map and lang_name) else None
-        cache = getattr(self, "_names_cache", None)
-        if cache is None:
-            cache = self._names_cache = {}
+        cache = self._names_cache
         if key not in cache:
             mapped = [pp.canonical_to_lang(ph, key, self.merge_map) if key else ph for ph in self._table.names]
             uniq, remap = [], np.empty(max(len(mapped), 1), np.int32)
@@ -339,57 +293,68 @@ class Labeler:
         remap, _ = self._names_for(lang_name)
         return s, e, remap[ph] if ph.size else ph
 
-    def _label_fast(self, audio_paths, lang_id, threshold, lang_name):
-        """Files the native loader takes whole (16 kHz, <= 30 s, <= 2 channels, PCM / float WAV): decoded, normalised and
-        converted by worker threads straight into the pinned batch rows (audio.load_wavs_into), one file per row; a finished
-        batch's tags go to a second worker thread for the native median filter + BIO decode + segment merge while the next
-        batches run.  Returns {file index: [(start_s, end_s, phoneme)]} (before forced alignment); every other file is left to the
-        general path."""
-        from concurrent.futures import ThreadPoolExecutor
-        Bs, L = self.batch_size, self.chunk_samples
-        done = {}
-        meta = {}
+    def _merged_tuples(self, s, e, ph, lang_name):
+        """A file's segments (name indices of _names_for) -> merge_segments unless "none" -> [(start_s, end_s, phoneme)]."""
+        mode = self.config["postprocess"]["merge_segments"]
+        ph = ph.astype(np.int32)
+        if mode != "none" and s.size:
+            s, e, ph = npost.merge_segments(s, e, ph, mode)
+        return npost.to_tuples(s, e, ph, self._names_for(lang_name)[1])
+
+    def _file_segments(self, parts, lang_name):
+        """A file's free decode: parts = [(ids, offsets, clock_s)] of its chunks in order (one for a file of at most 30 s) ->
+        [(start_s, end_s, phoneme)] on the file's clock, merged and named."""
+        if not parts:
+            return self._merged_tuples(np.empty(0), np.empty(0), np.empty(0, np.int32), lang_name)
+        segs = [self._segments_of_item(ids, offs, lang_name) for ids, offs, _ in parts]
+        s, e = (np.concatenate([seg[c] + p[2] for seg, p in zip(segs, parts)]) for c in (0, 1))
+        return self._merged_tuples(s, e, np.concatenate([seg[2] for seg in segs]), lang_name)
+
+    def _label_rows(self, n_files, width, fill, lang_id, threshold, lang_name, dtype=torch.float32, upload=None):
+        """One file per row of a Whisper batch, files k * batch_size ... in batch k: `fill(those file indices, host rows of `width`
+        values) -> (lens for the pipeline, [(row, file index)] of the rows it accepted)`; a finished batch's accepted tags go to a
+        second worker thread for the native median filter + BIO decode + segment merge while the next batches run.
+        -> {file index: [(start_s, end_s, phoneme)]} (before forced alignment)."""
+        Bs = self.batch_size
+        meta, futures = {}, []
         self._names_for(lang_name)                       # (build the cache on this thread)
         post = ThreadPoolExecutor(max_workers=1)
-        futures = []
-        threads = max(1, min(16, (os.cpu_count() or 1)))
 
-        def fill(k, host):
-            sel = list(range(k * Bs, min((k + 1) * Bs, len(audio_paths))))
+        def fill_batch(k, host):
+            lens, meta[k] = fill(list(range(k * Bs, min((k + 1) * Bs, n_files))), host)
+            return lens
+
+        def segments(rows):
+            return [(fi, self._file_segments([(ids, offs, 0.0)], lang_name)) for fi, ids, offs in rows]
+
+        def take(k, ids, offs):
+            futures.append(post.submit(segments, [(fi, ids[r].copy(), offs[r].copy()) for r, fi in meta.pop(k)]))
+
+        try:
+            self._pipeline([(Bs, width, self.model.num_frames(self.chunk_samples))] * -(-n_files // Bs), fill_batch, take, lang_id,
+                           threshold, dtype, upload, graph=self.use_graph)
+            return {fi: seg for f in futures for fi, seg in f.result()}
+        finally:
+            post.shutdown(wait=True)
+
+    def _label_fast(self, audio_paths, lang_id, threshold, lang_name):
+        """Files the native loader takes whole (16 kHz, <= 30 s, <= 2 channels, PCM / float WAV): decoded, normalised and
+        converted by worker threads straight into the pinned batch rows (audio.load_wavs_into), one file per row (_label_rows).
+        Returns {file index: [(start_s, end_s, phoneme)]} (before forced alignment); every other file is left to the general path."""
+        L = self.chunk_samples
+        threads = _worker_threads()
+
+        def fill(sel, host):
             ns, srs, st = A.load_wavs_into([audio_paths[i] for i in sel], host, L, threads)
-            lens = np.zeros(Bs, dtype=np.int32)
+            lens = np.zeros(self.batch_size, dtype=np.int32)
             ok = []
             for r, fi in enumerate(sel):
                 if st[r] == 0 and srs[r] == self.sr and ns[r] > 0:
                     lens[r] = ns[r]
-                    ok.append((r, fi, int(ns[r])))
-            meta[k] = ok
-            return lens, len(sel)
+                    ok.append((r, fi))
+            return lens, ok
 
-        mode = self.config["postprocess"]["merge_segments"]
-        names = self._names_for(lang_name)[1]
-
-        def segments(rows):
-            res = []
-            for fi, ids, offs in rows:
-                s, e, ph = self._segments_of_item(ids, offs, lang_name)
-                ph = ph.astype(np.int32)
-                if mode != "none" and s.size:
-                    s, e, ph = npost.merge_segments(s, e, ph, mode)
-                res.append((fi, npost.to_tuples(s, e, ph, names)))
-            return res
-
-        def take(k, n, ids, offs):
-            futures.append(post.submit(segments, [(fi, ids[r].copy(), offs[r].copy()) for r, fi, ns in meta.pop(k)]))
-
-        try:
-            self._run_batches((len(audio_paths) + Bs - 1) // Bs, fill, take, lang_id, threshold)
-            for f in futures:
-                for fi, seg in f.result():
-                    done[fi] = seg
-        finally:
-            post.shutdown(wait=True)
-        return done
+        return self._label_rows(len(audio_paths), L, fill, lang_id, threshold, lang_name)
 
     def _label_resampled(self, audio_paths, src_sr, lang_id, threshold, lang_name):
         """Files of ONE sample rate other than the model's, 16-bit PCM, at most 30 s: their samples go to the GPU as they are (the native
@@ -398,28 +363,16 @@ class Labeler:
         cores no longer bound a 44.1 kHz folder (48 k audio-s/s with the host resampler).  Same pipeline, post-
         processing and result as _label_fast."""
         import ctypes as C
-        from concurrent.futures import ThreadPoolExecutor
 
         from . import _lib
         lib = _lib.load()
         Bs, L = self.batch_size, self.chunk_samples
-        NI = self.n_inflight + 1
         cap_in = 2 * (int(math.ceil(L * src_sr / self.sr)) + 2)          # interleaved int16 values of a 30 s two-channel file
-        key = (src_sr, Bs)
-        cache = getattr(self, "_pinned_pcm", None)
-        if cache is None or cache[0] != key or len(cache[1]) != NI:
-            cache = (key, [torch.zeros(Bs, cap_in, dtype=torch.int16).pin_memory() for _ in range(NI)])
-            self._pinned_pcm = cache
-        pin = cache[1]
         ws_bytes = int(lib.wfl_resample_workspace_bytes(Bs, L))
         dev_out, dev_ws = {}, {}
-        meta, done, futures = {}, {}, []
-        self._names_for(lang_name)
-        post = ThreadPoolExecutor(max_workers=1)
-        threads = max(1, min(16, (os.cpu_count() or 1)))
+        threads = _worker_threads()
 
-        def fill(k, host):
-            sel = list(range(k * Bs, min((k + 1) * Bs, len(audio_paths))))
+        def fill(sel, host):
             nf, ch, srs, st = A.read_pcm16_into([audio_paths[i] for i in sel], host, cap_in, threads)
             frames = np.zeros(Bs, np.int32)
             chans = np.ones(Bs, np.int32)
@@ -428,8 +381,7 @@ class Labeler:
                 if st[r] == 0 and srs[r] == src_sr and nf[r] > 0 and int(math.ceil(int(nf[r]) * self.sr / src_sr)) <= L:
                     frames[r], chans[r] = nf[r], ch[r]
                     ok.append((r, fi))
-            meta[k] = ok
-            return (frames, chans), len(sel)
+            return (frames, chans), ok
 
         def upload(host, fc, slot, stream):
             frames, chans = fc
@@ -447,30 +399,7 @@ class Labeler:
             lens = np.minimum(np.ceil(frames.astype(np.float64) * self.sr / src_sr), L).astype(np.int32)
             return dev_out[slot], lens
 
-        mode = self.config["postprocess"]["merge_segments"]
-        names = self._names_for(lang_name)[1]
-
-        def segments(rows):
-            res = []
-            for fi, ids, offs in rows:
-                s, e, ph = self._segments_of_item(ids, offs, lang_name)
-                ph = ph.astype(np.int32)
-                if mode != "none" and s.size:
-                    s, e, ph = npost.merge_segments(s, e, ph, mode)
-                res.append((fi, npost.to_tuples(s, e, ph, names)))
-            return res
-
-        def take(k, n, ids, offs):
-            futures.append(post.submit(segments, [(fi, ids[r].copy(), offs[r].copy()) for r, fi in meta.pop(k)]))
-
-        try:
-            self._run_batches((len(audio_paths) + Bs - 1) // Bs, fill, take, lang_id, threshold, pinned_in=pin, upload=upload)
-            for f in futures:
-                for fi, seg in f.result():
-                    done[fi] = seg
-        finally:
-            post.shutdown(wait=True)
-        return done
+        return self._label_rows(len(audio_paths), cap_in, fill, lang_id, threshold, lang_name, torch.int16, upload)
 
     def align_mode(self, align=None) -> str:
         """"greedy" (the reference's string match, the default) or "viterbi"; None: config postprocess.align, else greedy."""
@@ -517,49 +446,49 @@ class Labeler:
         matched over the new segments) is decoded by the BIO-grammar search over its frame logits on the GPU (decode.py), each opened
         run costing `switch_penalty` nats; postprocess.median_filter is not applied to those files.  None: config postprocess.decode /
         postprocess.switch_penalty, else argmax / 0."""
+        final, scores = self._label_scored(audio_paths, lang_id, confidence_threshold, verbose, align, align_scores, decode,
+                                           switch_penalty)
+        return (final, scores) if self.align_scores_on(align_scores, align) else final
+
+    def _label_scored(self, audio_paths, lang_id=None, confidence_threshold=0.0, verbose=True, align=None, align_scores=None,
+                      decode=None, switch_penalty=None):
+        """label_files, always -> (segments, scores): the files are split once into those a transcript is Viterbi-aligned to, those the
+        grammar search decodes and those left to the argmax decode, and each subset's results go back to its files' places."""
         want_scores = self.align_scores_on(align_scores, align)
-        free = self.decode_options(decode, switch_penalty)
-        if free[0] == "viterbi" and int(self.config["postprocess"].get("median_filter", 0)) > 1:
+        mode, lam = self.decode_options(decode, switch_penalty)
+        if mode == "viterbi" and int(self.config["postprocess"].get("median_filter", 0)) > 1:
             print("decode: viterbi -- postprocess.median_filter is not applied (the switch penalty takes its place)")
         if lang_id is not None and self.lang2id and lang_id > max(self.lang2id.values()):
             raise ValueError(f"Error: Language ID ({lang_id}) is higher than the latest ID ({max(self.lang2id.values())}) "
                              f"of this model.\n Languages and Codes available: {self.lang2id}")
+        final, scores = [None] * len(audio_paths), [None] * len(audio_paths)
+        free, with_t = list(range(len(audio_paths))), []
         if self.align_mode(align) == "viterbi":
-            forced = {fi: _read_forced(p, verbose) for fi, p in enumerate(audio_paths)}
-            with_t = [fi for fi in range(len(audio_paths)) if forced[fi] is not None]
-            if with_t:
-                rest = [fi for fi in range(len(audio_paths)) if forced[fi] is None]
-                final = [None] * len(audio_paths)
-                scores = [None] * len(audio_paths)
-                if rest:
-                    for fi, segs in zip(rest, self._label_files_greedy([audio_paths[fi] for fi in rest], lang_id, confidence_threshold,
-                                                                        verbose, *free)):
-                        final[fi] = segs
-                got = self._label_viterbi([audio_paths[fi] for fi in with_t], [forced[fi] for fi in with_t], lang_id,
-                                          confidence_threshold, verbose, want_scores)
-                if want_scores:
-                    got, got_scores = got
-                    for fi, sc in zip(with_t, got_scores):
-                        scores[fi] = sc
-                for fi, segs in zip(with_t, got):
-                    final[fi] = segs
-                return (final, scores) if want_scores else final
-        final = self._label_files_greedy(audio_paths, lang_id, confidence_threshold, verbose, *free)
-        return (final, [None] * len(final)) if want_scores else final
+            forced = [_read_forced(p, verbose) for p in audio_paths]
+            with_t = [fi for fi in free if forced[fi] is not None]
+            free = [fi for fi in free if forced[fi] is None]
 
-    def _label_files_greedy(self, audio_paths, lang_id, confidence_threshold, verbose, decode="argmax", switch_penalty=0.0):
-        if decode == "viterbi":
-            # the free decode by the grammar search; a file it could not decode (with a message) takes the argmax decode below
-            got = self._decode_viterbi(audio_paths, lang_id, confidence_threshold, verbose, switch_penalty)
-            rest = [fi for fi in range(len(audio_paths)) if fi not in got]
-            final = [None] * len(audio_paths)
-            if rest:
-                for fi, segs in zip(rest, self._label_files_greedy([audio_paths[fi] for fi in rest], lang_id, confidence_threshold,
-                                                                    verbose)):
-                    final[fi] = segs
-            for fi, segs in got.items():
-                final[fi] = self._match_forced(audio_paths[fi], segs, verbose)
-            return final
+        def paths(idx):
+            return [audio_paths[fi] for fi in idx]
+
+        searched = {}
+        if mode == "viterbi":
+            # the free decode by the grammar search; a file it could not decode (with a message) takes the argmax decode
+            got = self._decode_viterbi(paths(free), lang_id, confidence_threshold, verbose, lam)
+            searched = {free[j]: segs for j, segs in got.items()}
+        argmax = [fi for fi in free if fi not in searched]
+        for fi, segs in zip(argmax, self._label_files_greedy(paths(argmax), lang_id, confidence_threshold, verbose)):
+            final[fi] = segs
+        for fi, segs in searched.items():
+            final[fi] = self._match_forced(audio_paths[fi], segs, verbose)
+        if with_t:
+            got = self._label_viterbi(paths(with_t), [forced[fi] for fi in with_t], lang_id, confidence_threshold, verbose, want_scores)
+            for fi, segs, sc in zip(with_t, *got):
+                final[fi], scores[fi] = segs, sc
+        return final, scores
+
+    def _label_files_greedy(self, audio_paths, lang_id, confidence_threshold, verbose):
+        """The argmax free decode of every file, then the greedy match of its transcript, if it has one (_match_forced)."""
         lang_name = self._lang_name(lang_id)
         decided_fast = {}                                 # file index -> segments of its one <= 30 s item, natively loaded
         if self.model.encoder_type == "whisper" and len(audio_paths) > 0:
@@ -586,8 +515,8 @@ class Labeler:
                 for sr, fis in by_rate.items():
                     got = self._label_resampled([audio_paths[fi] for fi in fis], sr, lang_id, confidence_threshold, lang_name)
                     decided_fast.update({fis[j]: seg for j, seg in got.items()})
-        items, owner = [], []
-        chunk_lens = []
+        items, owner, clocks = [], [], []
+        clock = [0.0] * len(audio_paths)
         load_one = self._load_chunks
 
         slow = [fi for fi in range(len(audio_paths)) if fi not in decided_fast]
@@ -597,21 +526,19 @@ class Labeler:
         pool = None
         try:
             if len(slow) > 1:
-                from concurrent.futures import ThreadPoolExecutor
-                pool = ThreadPoolExecutor(max_workers=max(1, min(16, os.cpu_count() or 1, len(slow))))
+                pool = ThreadPoolExecutor(max_workers=_worker_threads(len(slow)))
                 futs = [pool.submit(load_one, audio_paths[fi]) for fi in slow]
-            wave = getattr(self, "_wave_items", None) or max(8 * self.batch_size, 64)   # items per wave: enough batches to fill
-                                                                                        # the pipeline's slots (tests set a small one)
+            wave = self._wave()                           # items per wave: enough batches to fill the pipeline's slots
             start = 0
             for j, fi in enumerate(slow):
                 chunks = futs[j].result() if pool is not None else load_one(audio_paths[fi])
-                lens = [len(c) for c in chunks]
                 if verbose and len(chunks) > 1:
-                    print(f"Audio is too long ({sum(lens)/self.sr:.1f}s), splitting...")
-                for c, n in zip(chunks, lens):
+                    print(f"Audio is too long ({sum(len(c) for c in chunks)/self.sr:.1f}s), splitting...")
+                for c in chunks:
                     items.append(c)
                     owner.append(fi)
-                    chunk_lens.append(n)
+                    clocks.append(clock[fi])
+                    clock[fi] += len(c) / self.sr
                 if len(items) - start >= wave and j + 1 < len(slow):
                     decided.extend(self._forward_items(items[start:], lang_id, confidence_threshold))
                     start = len(items)
@@ -620,44 +547,25 @@ class Labeler:
         finally:
             if pool is not None:
                 pool.shutdown(wait=True, cancel_futures=True)
-        results = [[] for _ in audio_paths]
-        clock = [0.0] * len(audio_paths)
-        for (ids, offs), fi, n in zip(decided, owner, chunk_lens):
-            s, e, ph = self._segments_of_item(ids, offs, lang_name)
-            t0 = clock[fi]
-            results[fi].append((s + t0, e + t0, ph))
-            clock[fi] += n / self.sr
-        names = self._names_for(lang_name)[1]
-        final = []
-        for fi, path in enumerate(audio_paths):
-            if fi in decided_fast:                        # one <= 30 s item: decoded and merged by the post worker already
-                segs = decided_fast[fi]
-            else:
-                parts = results[fi]
-                s = np.concatenate([p[0] for p in parts]) if parts else np.empty(0)
-                e = np.concatenate([p[1] for p in parts]) if parts else np.empty(0)
-                ph = np.concatenate([p[2] for p in parts]).astype(np.int32) if parts else np.empty(0, np.int32)
-                mode = self.config["postprocess"]["merge_segments"]
-                if mode != "none" and s.size:
-                    s, e, ph = npost.merge_segments(s, e, ph, mode)
-                segs = npost.to_tuples(s, e, ph, names)
-            final.append(self._match_forced(path, segs, verbose))
-        return final
+        parts = [[] for _ in audio_paths]
+        for (ids, offs), fi, t0 in zip(decided, owner, clocks):
+            parts[fi].append((ids, offs, t0))
+        # (a file of decided_fast: one <= 30 s item, decoded and merged by the post worker already)
+        return [self._match_forced(path, decided_fast[fi] if fi in decided_fast else self._file_segments(parts[fi], lang_name), verbose)
+                for fi, path in enumerate(audio_paths)]
 
     @staticmethod
     def _match_forced(path, segs, verbose):
         """The greedy string match of a `{audio}.txt` transcript onto freely decoded segments and the pause rule for the ends
         (infer.py:30-60, 312-319); a file without a transcript keeps its segments."""
         forced = _read_forced(path, verbose)
-        if forced is not None:
-            aligned = pp.align_phoneme_list(segs, forced)
-            if "SP" not in forced and "AP" not in forced and aligned:
-                before = [s for s in segs if s[2] in ("SP", "AP") and s[1] <= aligned[0][0]]
-                after = [s for s in segs if s[2] in ("SP", "AP") and s[0] >= aligned[-1][1]]
-                segs = before + aligned + after
-            else:
-                segs = aligned
-        return segs
+        if forced is None:
+            return segs
+        return AL.with_end_pauses(segs, pp.align_phoneme_list(segs, forced), forced)
+
+    def _wave(self):
+        """Chunks per wave of files: enough batches to fill the pipeline's slots (a test sets a small `_wave_items`)."""
+        return self._wave_items or max(8 * self.batch_size, 64)
 
     def _load_chunks(self, path):
         chunks = A.load_items(path, self.sr)            # native: decode, resample, normalise, 30 s chunks (csrc/hostpost.hip)
@@ -713,9 +621,8 @@ class Labeler:
         ahead; a wave closes once it holds `wave` chunks."""
         if not audio_paths:
             return
-        wave = getattr(self, "_wave_items", None) or max(8 * self.batch_size, 64)
-        from concurrent.futures import ThreadPoolExecutor
-        pool = ThreadPoolExecutor(max_workers=max(1, min(16, os.cpu_count() or 1, len(audio_paths))))
+        wave = self._wave()
+        pool = ThreadPoolExecutor(max_workers=_worker_threads(len(audio_paths)))
         loads = [pool.submit(self._load_chunks, p) for p in audio_paths]      # (the native loader releases the GIL)
         pool.shutdown(wait=False)
         files = list(range(len(audio_paths)))
@@ -757,13 +664,11 @@ class Labeler:
         search covers the whole file and a run may cross a chunk seam; the files of a wave go to wfl_decode as one ragged batch and
         only ids / status come back to the host.  A file whose status is not 0 is left out (with a message): the caller decodes it
         by argmax."""
-        from . import decode as DC
         lang_name = self._lang_name(lang_id)
-        remap, names = self._names_for(lang_name)
-        mode = self.config["postprocess"]["merge_segments"]
-        table = getattr(self, "_decode_table", None)
-        if table is None:
-            table = self._decode_table = DC.class_table(self.labels)
+        remap, _ = self._names_for(lang_name)
+        if self._decode_table is None:
+            self._decode_table = DC.class_table(self.labels)
+        table = self._decode_table
         out = {}
         for files, by_file in self._file_waves(audio_paths, verbose):
             sel = [fi for fi in files if fi in by_file]
@@ -782,10 +687,7 @@ class Labeler:
                 else:
                     s, e, ph = DC.path_segments_free(ids_all[pos:pos + n], *self._chunk_plan(rows, by_file[fi], fi), self._table,
                                                      frame_duration)
-                    ph = remap[ph] if ph.size else ph
-                    if mode != "none" and s.size:
-                        s, e, ph = npost.merge_segments(s, e, ph, mode)
-                    out[fi] = npost.to_tuples(s, e, ph, names)
+                    out[fi] = self._merged_tuples(s, e, remap[ph] if ph.size else ph, lang_name)
                 pos += n
         return out
 
@@ -794,12 +696,11 @@ class Labeler:
         the same forward gives the greedy result, which the pause rule at the ends needs and which a file falls back to (with a
         message) when its transcript cannot be aligned.  Each file's chunks' valid logits rows are concatenated on the device, so
         one search covers the whole file; the files of a wave go to wfl_align as one ragged batch and only ids / tok / score / status
-        come back to the host.  want_scores: right after the search, one wfl_align_posterior call per wave over the clips it
-        aligned (same logits, the device `tok`), one more small copy to the host -> (results, [FileScore or None per file])."""
-        from . import align as AL
+        come back to the host.  -> (results, [FileScore or None per file]); want_scores: right after the search, one
+        wfl_align_posterior call per wave over the clips it aligned (same logits, the device `tok`), one more small copy to the host;
+        without, every score is None."""
         lang_name = self._lang_name(lang_id)
         remap, names = self._names_for(lang_name)
-        mode = self.config["postprocess"]["merge_segments"]
         results, scores = [], []
         for sel, by_file in self._file_waves(audio_paths, verbose):     # a wave's chunks are forwarded and aligned together
             free, rows = self._forward_with_logits(sel, by_file, lang_id, threshold)
@@ -808,17 +709,9 @@ class Labeler:
             for j, fi in enumerate(sel):
                 parts, clock = [], 0.0
                 for ci, x in enumerate(by_file[fi]):
-                    ids_c, offs_c = free[(fi, ci)]
-                    s, e, ph = self._segments_of_item(ids_c, offs_c, lang_name)
-                    parts.append((s + clock, e + clock, ph))
+                    parts.append((*free[(fi, ci)], clock))
                     clock += len(x) / self.sr
-                s = np.concatenate([p[0] for p in parts])
-                e = np.concatenate([p[1] for p in parts])
-                ph = np.concatenate([p[2] for p in parts]).astype(np.int32)
-                if mode != "none" and s.size:
-                    s, e, ph = npost.merge_segments(s, e, ph, mode)
-                segs = npost.to_tuples(s, e, ph, names)
-                free_segs[fi] = segs
+                segs = free_segs[fi] = self._file_segments(parts, lang_name)
                 tr = transcripts[fi]
                 greedy[fi] = AL.with_end_pauses(segs, pp.align_phoneme_list(segs, tr), tr)
                 if not tr:
@@ -882,7 +775,7 @@ class Labeler:
             for fi in sel:
                 results.append(aligned.get(fi, greedy[fi]))
                 scores.append(post.get(fi))
-        return (results, scores) if want_scores else results
+        return results, scores
 
 
 def _read_forced(audio_path, verbose):
@@ -987,14 +880,8 @@ def infer_audio(audio_path, config_path="config.yaml", checkpoint_path="best_mod
     _check_align_scores(align, align_scores)
     _check_decode(decode, switch_penalty)
     lab = _labeler(config_path, checkpoint_path, device)
-    score = None
-    free = dict(decode=decode, switch_penalty=switch_penalty)
-    if lab.align_scores_on(align_scores, align):
-        segments, scores = lab.label_files([audio_path], lang_id=lang_id, confidence_threshold=confidence_threshold, align=align,
-                                           align_scores=True, **free)
-        segments, score = segments[0], scores[0]
-    else:
-        segments = lab.label_files([audio_path], lang_id=lang_id, confidence_threshold=confidence_threshold, align=align, **free)[0]
+    (segments,), (score,) = lab._label_scored([audio_path], lang_id=lang_id, confidence_threshold=confidence_threshold, align=align,
+                                              align_scores=align_scores, decode=decode, switch_penalty=switch_penalty)
     if output_lab_path:
         if os.path.abspath(output_lab_path) == os.path.abspath(audio_path):
             # the reference would truncate the input WAV here (infer.py:410-411 + utils.py:77)
@@ -1011,7 +898,6 @@ def infer_folder(folder_path: str, config_path: str = "config.yaml", checkpoint_
     _check_align(align)
     _check_align_scores(align, align_scores)
     _check_decode(decode, switch_penalty)
-    free = dict(decode=decode, switch_penalty=switch_penalty)
     wav_files = sorted(f for f in os.listdir(folder_path) if f.lower().endswith(".wav"))
     os.makedirs(output_dir, exist_ok=True)
     # one process per GPU: every rank labels its own share of the files and writes its own .lab files (no collective)
@@ -1023,13 +909,8 @@ def infer_folder(folder_path: str, config_path: str = "config.yaml", checkpoint_
     lab = _labeler(config_path, checkpoint_path, device)
     paths = [os.path.join(folder_path, f) for f in wav_files]
     want_scores = lab.align_scores_on(align_scores, align)
-    all_scores = [None] * len(paths)
-    if want_scores and paths:
-        all_segments, all_scores = lab.label_files(paths, lang_id=lang_id, confidence_threshold=confidence_threshold, align=align,
-                                                   align_scores=True, **free)
-    else:
-        all_segments = lab.label_files(paths, lang_id=lang_id, confidence_threshold=confidence_threshold, align=align,
-                                       **free) if paths else []
+    all_segments, all_scores = lab._label_scored(paths, lang_id=lang_id, confidence_threshold=confidence_threshold, align=align,
+                                                 align_scores=align_scores, decode=decode, switch_penalty=switch_penalty) if paths else ([], [])
     for wav_file, segments, score in zip(wav_files, all_segments, all_scores):
         print(f"\nInferencing: {wav_file}")
         lab_path = os.path.join(output_dir, os.path.splitext(wav_file)[0] + ".lab")
