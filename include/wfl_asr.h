@@ -384,6 +384,41 @@ int32_t wfl_decode(const float* logits, int64_t ldl, int32_t C, int32_t o_id, co
                    int32_t n_clips, const int32_t* pairs, int32_t n_pairs, float lambda, float threshold, void* workspace,
                    int64_t workspace_bytes, int32_t* ids, float* score, int32_t* status, void* stream);
 
+/* ---- Posteriors of a BIO-grammar decode by forward-backward on the GPU (`postprocess.decode_scores`; wfl-asr_amd/decode.py).  No
+ * counterpart in the reference, which reports no confidence for its free decode.  Classes, virtual start, forced frames, caps and
+ * argument conventions are wfl_decode's: the states are O, B-p, I-p of `pairs` (every other class is never on a path), the clip follows
+ * a virtual O frame, a frame whose largest softmax probability (fp32, the same pre-pass arithmetic) is below threshold > 0 can only be O,
+ * any state may end the clip.  The weight of a legal path is exp(sum_t z[t][c_t] - lambda * runs opened), the runs counted as wfl_decode
+ * counts them; as transitions:  into O from O: 0;  into O from anything else: -lambda;  into any B-q from anything: -lambda;  into I-p
+ * from B-p or I-p only: 0.  Then
+ *     logZ = log sum of the weights of all legal paths,      gamma_t(c) = posterior that the path is in class c at frame t.
+ * ids (device) is the path wfl_decode returned for the same clips and rows.  Outputs (device, fp32):
+ *   logz[b]       logZ of the clip;
+ *   post[t]       (same rows as the logits) for ids[t] in {B-p, I-p}: gamma_t(B-p) + gamma_t(I-p), the posterior that frame t belongs to
+ *                 phoneme p at all; for ids[t] == O: gamma_t(O).  In [0, 1], clamped to 1 from above;
+ *   cls_post[t]   gamma_t(ids[t]), the posterior of the exact class: on the first frame of a run, that a run of p opens exactly here.
+ *                 cls_post[t] <= post[t];
+ *   status[b]     wfl_decode's codes (0 ok, 2 C above 1024, 4 a class id of `pairs` outside [0, C) or a class used twice), and 8: ids
+ *                 holds a class that is never chosen, an I-p that does not follow B-p / I-p, or a non-O class on a forced frame (not a
+ *                 path of this grammar).  A clip with status != 0 gets logz = 0 and post = cls_post = 0; T = 0 is ok, logz 0, and
+ *                 writes nothing per frame.
+ * One wave per clip: a clip scored alone equals the same clip inside any batch, bit for bit.  Scaled linear-domain fp32 states
+ * (emissions exp(z - row maximum), every frame rescaled by a power of two, the exponents summed in an integer); a posterior that
+ * underflows fp32 is reported as 0.  An O emission counts as at least 2^-60 of its frame's largest (the row maximum over all C
+ * classes) and lambda as at most 60 ln 2 (41.6 nats), which keeps every sum inside fp32's exponent range.  Neither moves a posterior by
+ * more than 1e-18 while the frame's largest logit belongs to a class that carries mass there or O lies within 41.6 nats of it; on a
+ * frame whose largest logit is a class outside the grammar, or an I-q no path can reach, more than 41.6 nats above O, O is lifted
+ * against the B / I states and the frame's posterior leans towards O.  Arguments are checked on the host as wfl_decode checks its own
+ * (negative return).
+ * Workspace: the alpha lattice is not stored.  Per clip with T > 0, in 4-byte words: round_up_64(3 T) + 3 round_up_64(T)  (per frame
+ * alpha on the path's own phoneme and the scale exponent; the path's (pair, kind); the row maximum; the forced flag), whatever n_pairs
+ * <= 1024; 0 above.  wfl_decode_posterior_workspace_bytes returns the sum in bytes (24 bytes per frame). */
+int64_t wfl_decode_posterior_workspace_bytes(const int32_t* n_frames_host, int32_t n_clips, int32_t n_pairs);
+int32_t wfl_decode_posterior(const float* logits, int64_t ldl, int32_t C, int32_t o_id, const int64_t* frame_off_host,
+                             const int32_t* n_frames_host, int32_t n_clips, const int32_t* pairs, int32_t n_pairs, float lambda,
+                             float threshold, const int32_t* ids, void* workspace, int64_t workspace_bytes, float* logz, float* post,
+                             float* cls_post, int32_t* status, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

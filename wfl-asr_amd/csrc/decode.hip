@@ -18,9 +18,11 @@
 // align.hip), so the fp32 scores do not grow with T.
 // Backpointers: per frame 2 S words of I-p bits (one __ballot per slot), and one word a | (O's bit << 16).  Backtrace: lane 0 walks
 // windows of DECODE_W frames that the wave stages into LDS.
-// From csrc/lattice.h (the alignment kernels' header) come only the class cap, the clips-per-launch constant, round64, wave_sum and
-// the host's clip-table batching and workspace check; the kernels here share nothing with the lattice.
-#include "lattice.h"
+// What wfl_decode_posterior (csrc/decode_posterior.hip) scores this search's paths with lives in csrc/bio_grammar.h: the clip record,
+// the slot configurations, the pre-pass arithmetic, the class table and its validation, the host's argument checks.  From
+// csrc/lattice.h (the alignment kernels' header) come only the class cap, the clips-per-launch constant, round64, wave_sum and the
+// host's clip-table batching and workspace check; the kernels here share nothing with the lattice.
+#include "bio_grammar.h"
 #include "wfl_asr.h"
 
 namespace {
@@ -29,14 +31,11 @@ using lattice::CLIPS_PER_LAUNCH;
 using lattice::MAX_CLASSES;
 using lattice::round64;
 
-constexpr int DECODE_W = 32;                 // backtrace window, frames
-constexpr int NO_CLASS = 0x7fffffff;
+using bio::NO_CLASS;
+using bio::slots_of;
+using DecodeClip = bio::Clip;
 
-struct DecodeClip {
-  long frame_off;  // first logits row of the clip
-  long ws_off;     // the clip's words in the workspace
-  int T, clip;
-};
+constexpr int DECODE_W = 32;                 // backtrace window, frames
 
 struct DecodeLaunch {
   const float* logits;
@@ -57,12 +56,6 @@ struct DecodeLaunch {
 __host__ __device__ inline long off_lse(int T, int S) { return round64((long)T * (2 * S + 1)); }
 __host__ __device__ inline long off_forced(int T, int S) { return off_lse(T, S) + round64(T); }
 inline long clip_words(int T, int S) { return T > 0 ? off_forced(T, S) + round64(T) : 0; }
-
-int slots_of(int n_pairs) {
-  for (int s = 2; s <= 16; s *= 2)
-    if (n_pairs <= 64 * s) return s;
-  return 0;
-}
 
 // (value, class) ordered by value, then by the LOWER class id: max-combine of one lane's pair with another's
 __device__ __forceinline__ void take_better(float& v, int& c, float ov, int oc) {
@@ -97,18 +90,12 @@ __global__ __launch_bounds__(256) void decode_pre_kernel(DecodeLaunch a, int S) 
   const int t = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (t >= cl.T) return;
   const float* z = a.logits + (cl.frame_off + t) * a.ldl;
-  float m = -INFINITY;
-  for (int c = lane; c < a.C; c += 64) m = fmaxf(m, z[c]);
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
-  float se = 0.f;
-  for (int c = lane; c < a.C; c += 64) se += expf(z[c] - m);
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) se += __shfl_xor(se, o);
+  float m, se;
+  bio::frame_stats(z, a.C, lane, m, se);
   if (lane == 0) {
     unsigned* w = a.ws + cl.ws_off;
     ((float*)(w + off_lse(cl.T, S)))[t] = m + logf(se);
-    w[off_forced(cl.T, S) + t] = (a.threshold > 0.f && 1.f / se < a.threshold) ? 1u : 0u;   // max probability = exp(m - lse) = 1 / se
+    w[off_forced(cl.T, S) + t] = bio::forced_to_o(se, a.threshold);
   }
 }
 
@@ -136,31 +123,8 @@ __global__ __launch_bounds__(64) void decode_chain_kernel(DecodeLaunch a) {
   int* ids = a.ids + cl.frame_off;
 
   // ---- the class table: every class at most once, all inside [0, C)
-  if (lane < MAX_CLASSES / 32) used[lane] = 0;
-  for (int c = lane; c < MAX_CLASSES; c += 64) info[c] = -1;
-  __syncthreads();
-  if (lane == 0) { used[o_id >> 5] = 1u << (o_id & 31); info[o_id] = 0; }
-  __syncthreads();
   int clsB[S], clsI[S];
-  bool bad = false;
-#pragma unroll
-  for (int s = 0; s < S; ++s) {
-    const int p = lane + 64 * s;
-    clsB[s] = clsI[s] = NO_CLASS;
-    if (p < a.n_pairs) {
-      const int b = a.pairs[2 * p], i = a.pairs[2 * p + 1];
-      if (b < 0 || b >= C) bad = true;
-      else if (atomicOr(&used[b >> 5], 1u << (b & 31)) & (1u << (b & 31))) bad = true;
-      else { clsB[s] = b; info[b] = p | (1 << 16); }
-      if (i != -1) {
-        if (i < 0 || i >= C) bad = true;
-        else if (atomicOr(&used[i >> 5], 1u << (i & 31)) & (1u << (i & 31))) bad = true;
-        else { clsI[s] = i; info[i] = p | (2 << 16); }
-      }
-    }
-  }
-  __syncthreads();
-  if (__any(bad)) {
+  if (bio::class_table<S>(a.pairs, a.n_pairs, C, o_id, used, info, clsB, clsI)) {
     for (int t = lane; t < T; t += 64) ids[t] = o_id;
     if (lane == 0) { a.score[cl.clip] = 0.f; a.status[cl.clip] = 4; }
     return;
@@ -345,22 +309,14 @@ int64_t wfl_decode_workspace_bytes(const int32_t* n_frames_host, int32_t n_clips
 int32_t wfl_decode(const float* logits, int64_t ldl, int32_t C, int32_t o_id, const int64_t* frame_off_host, const int32_t* n_frames_host,
                    int32_t n_clips, const int32_t* pairs, int32_t n_pairs, float lambda, float threshold, void* workspace,
                    int64_t workspace_bytes, int32_t* ids, float* score, int32_t* status, void* stream) {
-  if (C < 1) return wfl_fail(-1, "wfl_decode: C < 1");
-  if (o_id < 0 || o_id >= C) return wfl_fail(-1, "wfl_decode: o_id out of range");
-  if (ldl < C) return wfl_fail(-1, "wfl_decode: ldl < C");
-  if (n_clips < 0 || n_pairs < 0) return wfl_fail(-1, "wfl_decode: negative count");
-  if (!(lambda >= 0.f) || !(threshold >= 0.f)) return wfl_fail(-1, "wfl_decode: lambda and threshold must be >= 0");
+  bool any_frame;
+  if (const int rc = bio::check_args("wfl_decode", C, o_id, ldl, frame_off_host, n_frames_host, n_clips, n_pairs, lambda, threshold, any_frame))
+    return rc;
   if (n_clips == 0) return 0;
-  if (!frame_off_host || !n_frames_host) return wfl_fail(-1, "wfl_decode: null host array");
-  bool any_frame = false;
-  for (int b = 0; b < n_clips; ++b) {
-    if (frame_off_host[b] < 0 || n_frames_host[b] < 0) return wfl_fail(-1, "wfl_decode: negative offset or frame count");
-    any_frame |= n_frames_host[b] > 0;
-  }
   if (!score || !status || (n_pairs > 0 && !pairs) || (any_frame && (!logits || !ids)))
     return wfl_fail(-1, "wfl_decode: null device pointer");
   // over the class cap: status 2; more pairs than classes (then one is used twice or out of range): status 4
-  const int fill = C > MAX_CLASSES ? 2 : (n_pairs > C ? 4 : 0);
+  const int fill = bio::refused_status(C, n_pairs);
   const int S = fill ? 0 : slots_of(n_pairs);
   const int64_t need = fill ? 0 : wfl_decode_workspace_bytes(n_frames_host, n_clips, n_pairs);
   if (const int rc = lattice::check_workspace("wfl_decode", need, workspace, workspace_bytes)) return rc;

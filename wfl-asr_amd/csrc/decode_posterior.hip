@@ -1,0 +1,451 @@
+// Forward-backward over the BIO grammar of wfl_decode: per-frame posteriors of a decoded path (wfl_decode_posterior, include/wfl_asr.h).
+//
+// The sum-product counterpart of csrc/decode.hip over the same states (the classes O, B-p, I-p of `pairs`; every other class is never on
+// a path), the same virtual O frame in front of the clip, the same forced frames (largest softmax probability below the threshold: only
+// O) and the same penalty.  The weight of a legal path is exp(sum_t z[t][c_t] - lambda * runs opened); in transition terms, with
+// w = exp(-lambda):   into O from O: 1    into O from anything else: w    into any B-q from anything: w    into I-p from B-p / I-p: 1.
+// Any state may end the clip.
+//     logZ = log sum of the weights of all legal paths,      gamma_t(c) = posterior that the path is in class c at frame t.
+// With e the frame's emissions, tot the sum of all states of the previous frame (alpha) and primes for the next frame (beta):
+//     forward    O'   = e(O) (O + w (tot - O))          B-p' = e(B-p) w tot          I-p' = e(I-p) (I-p + B-p)
+//     backward   SB = sum_q e'(B-q) beta'(B-q),  wO = e'(O) beta'(O)
+//                beta(O) = wO + w SB          beta(B-p) = beta(I-p) = w (wO + SB) + e'(I-p) beta'(I-p)          beta at T - 1 = 1
+// Outputs per frame, for the class ids[t] of the path wfl_decode returned: post = gamma(B-p) + gamma(I-p) of the path's phoneme (gamma(O)
+// on an O frame), cls_post = gamma(ids[t]).
+//
+// Execution shape of the search: decode_post_pre_kernel, one wave per frame, fully parallel (the row maximum and the forced flag, by
+// the search's own pre-pass arithmetic); decode_post_chain_kernel, ONE WAVE per clip, lane l owning the phonemes l, l + 64, ... (S slots,
+// both states of each in registers), so the I-p update is lane-local and the only cross-lane work of a frame is ONE wave sum in each
+// direction (DPP inside a row of 16, the four row sums through v_readlane).  No LDS exchange, no barrier in the frame loops.
+//
+// Arithmetic: scaled linear domain.  e = exp(z - row maximum) is formed when a group of D frames is loaded, one group ahead of the chain,
+// so the chain holds no transcendental: a frame is a handful of multiply-adds, the wave sum and a rescale by a power of two taken from the
+// exponent of that sum (exact; the exponents add up in an integer, so the scale costs no rounding however long the clip).  On a forced
+// frame every path is in O, so O's emission is factored out (taken as 1, its logit added to logZ).  Two guards keep the sums inside
+// fp32's exponent range whatever the logits: an O emission is at least 2^-60 of its frame's maximum and w at least 2^-60 (41.6 nats).
+// The maximum is the row's, over ALL C classes.  While it belongs to a class that carries mass at that frame, or O lies within 41.6 nats
+// of it, the floors move no posterior by more than 1e-18.  On a frame whose largest logit is a class outside the grammar (or an I-q no
+// path can reach there) AND stands more than 41.6 nats above O, O is lifted against the B / I states, which keep their true size: that
+// frame's posterior leans towards O.  A state smaller than 2^-126 of its frame's sum underflows: its posterior is reported 0.
+//
+// The alpha lattice is not stored.  The outputs need alpha only on the path's own phoneme: the forward sweep's owning lane writes
+// (alpha(B-p), alpha(I-p), scale exponent) -- (alpha(O), 0, exponent) on an O frame -- three words per frame; the backward sweep reads them
+// a group ahead and the owning lane multiplies them with its beta (in double, with logZ's mantissa and the three exponents).
+// Before the sweeps the wave checks in parallel that ids is a path of the grammar (status 8) and leaves class -> (pair, kind) per frame.
+// Workspace per clip, in words: [alpha records 3 T] [pair | kind << 16 per frame T] [row maxima T] [forced flags T], each rounded up to 64.
+#include "bio_grammar.h"
+#include "wfl_asr.h"
+
+namespace {
+
+using bio::NO_CLASS;
+using bio::slots_of;
+using lattice::CLIPS_PER_LAUNCH;
+using lattice::MAX_CLASSES;
+using lattice::round64;
+
+struct PostLaunch {
+  const float* logits;
+  long ldl;
+  int C, o_id;
+  const int* pairs;  // [n_pairs][2]: B class, I class or -1
+  int n_pairs;
+  float lambda, threshold;
+  const int* ids;
+  unsigned* ws;
+  float *logz, *post, *cls_post;
+  int* status;
+  int n, fill_status;
+  bio::Clip clip[CLIPS_PER_LAUNCH];
+};
+
+__host__ __device__ inline long off_sel(int T) { return round64(3L * T); }
+__host__ __device__ inline long off_max(int T) { return off_sel(T) + round64(T); }
+__host__ __device__ inline long off_forced(int T) { return off_max(T) + round64(T); }
+inline long clip_words(int T) { return T > 0 ? off_forced(T) + round64(T) : 0; }
+
+constexpr float TINY = 0x1p-60f;   // floor of an O emission and of exp(-lambda)
+
+// ---- every lane gets the wave's sum.  Each DPP step adds two groups that already agree inside themselves (a + b == b + a bit for bit),
+// so the 16 lanes of a row end with the same row sum; the four row sums are read through SGPRs.
+template <int CTRL>
+__device__ __forceinline__ float dpp_add(float v) {
+  return v + __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xf, 0xf, false));
+}
+
+__device__ __forceinline__ float wave_total(float v) {
+  v = dpp_add<0xB1>(v);    // quad_perm [1,0,3,2]
+  v = dpp_add<0x4E>(v);    // quad_perm [2,3,0,1]
+  v = dpp_add<0x141>(v);   // row_half_mirror: the other quad of the 8
+  v = dpp_add<0x140>(v);   // row_mirror: the other 8 of the 16
+  const int b = __float_as_int(v);
+  const float r0 = __int_as_float(__builtin_amdgcn_readlane(b, 0)), r1 = __int_as_float(__builtin_amdgcn_readlane(b, 16));
+  const float r2 = __int_as_float(__builtin_amdgcn_readlane(b, 32)), r3 = __int_as_float(__builtin_amdgcn_readlane(b, 48));
+  return (r0 + r1) + (r2 + r3);
+}
+
+// x = f 2^e, f in [1, 2): e into `ex`, -> 2^-e (x is positive and normal, see the guards in the header comment)
+__device__ __forceinline__ float unscale(float x, int& ex) {
+  const int be = __builtin_amdgcn_readfirstlane((__float_as_int(x) >> 23) & 0xff);
+  ex = be - 127;
+  return __int_as_float((254 - be) << 23);
+}
+
+// ---- per frame: the row maximum and the forced-to-O flag.  grid (ceil(max T / 4), clips), 4 waves per block, one wave per frame.
+__global__ __launch_bounds__(256) void decode_post_pre_kernel(PostLaunch a) {
+  const bio::Clip cl = a.clip[blockIdx.y];
+  const int lane = threadIdx.x & 63;
+  const int t = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (t >= cl.T) return;
+  float m, se;
+  bio::frame_stats(a.logits + (cl.frame_off + t) * a.ldl, a.C, lane, m, se);
+  if (lane == 0) {
+    unsigned* w = a.ws + cl.ws_off;
+    ((float*)(w + off_max(cl.T)))[t] = m;
+    w[off_forced(cl.T) + t] = bio::forced_to_o(se, a.threshold);
+  }
+}
+
+// ---- clips that cannot be scored (C over the cap, more pairs than classes): zeros, the status
+__global__ __launch_bounds__(64) void decode_post_fill_kernel(PostLaunch a) {
+  const bio::Clip cl = a.clip[blockIdx.x];
+  for (int t = threadIdx.x; t < cl.T; t += 64) a.post[cl.frame_off + t] = a.cls_post[cl.frame_off + t] = 0.f;
+  if (threadIdx.x == 0) { a.logz[cl.clip] = 0.f; a.status[cl.clip] = a.fill_status; }
+}
+
+template <int S, int D>
+__global__ __launch_bounds__(64) void decode_post_chain_kernel(PostLaunch a) {
+  __shared__ unsigned used[MAX_CLASSES / 32];
+  __shared__ int info[MAX_CLASSES];    // class -> pair | kind << 16 (kind 0 O, 1 B, 2 I); -1 never chosen
+
+  const bio::Clip cl = a.clip[blockIdx.x];
+  const int lane = threadIdx.x;
+  const int T = cl.T, C = a.C, o_id = a.o_id;
+  const int* ids = a.ids + cl.frame_off;
+  float* post = a.post + cl.frame_off;
+  float* cls_post = a.cls_post + cl.frame_off;
+  auto refuse = [&](int st) {
+    for (int t = lane; t < T; t += 64) post[t] = cls_post[t] = 0.f;
+    if (lane == 0) { a.logz[cl.clip] = 0.f; a.status[cl.clip] = st; }
+  };
+
+  int clsB[S], clsI[S];
+  if (bio::class_table<S>(a.pairs, a.n_pairs, C, o_id, used, info, clsB, clsI)) { refuse(4); return; }
+  if (T == 0) {
+    if (lane == 0) { a.logz[cl.clip] = 0.f; a.status[cl.clip] = 0; }
+    return;
+  }
+
+  unsigned* w0 = a.ws + cl.ws_off;
+  float* rec = (float*)w0;                                     // [T][3]: alpha(B-p) or alpha(O), alpha(I-p) or 0, scale exponent
+  int* sel = (int*)(w0 + off_sel(T));
+  const float* rowmax = (const float*)(w0 + off_max(T));
+  const unsigned* forced = w0 + off_forced(T);
+  const float* Z = a.logits + cl.frame_off * a.ldl;
+
+  // ---- is ids a path of this grammar?  Every frame on its own: a class of the table, I-p only after B-p / I-p, O on a forced frame.
+  bool bad = false;
+  for (int t = lane; t < T; t += 64) {
+    const int c = ids[t];
+    const int in = (c >= 0 && c < C) ? info[c] : -1;
+    if (in < 0) bad = true;
+    else if ((in >> 16) == 2) {
+      const int pc = t ? ids[t - 1] : o_id;
+      const int pin = (pc >= 0 && pc < C) ? info[pc] : -1;
+      if (pin < 0 || (pin >> 16) == 0 || (pin & 0xffff) != (in & 0xffff)) bad = true;
+    }
+    if (in > 0 && forced[t]) bad = true;                       // (in == 0 is O)
+    sel[t] = in < 0 ? 0 : in;
+  }
+  if (__any(bad)) { refuse(8); return; }
+  __threadfence_block();
+  __syncthreads();                                             // sel[] is read back by every lane below
+
+  int colB[S], colI[S];                                        // a state that does not exist reads O's column and gets emission 0
+  unsigned hasB = 0, hasI = 0;
+#pragma unroll
+  for (int s = 0; s < S; ++s) {
+    colB[s] = clsB[s] != NO_CLASS ? clsB[s] : o_id;
+    colI[s] = clsI[s] != NO_CLASS ? clsI[s] : o_id;
+    if (clsB[s] != NO_CLASS) hasB |= 1u << s;
+    if (clsI[s] != NO_CLASS) hasI |= 1u << s;
+  }
+  const float w = fmaxf(expf(-a.lambda), TINY);
+
+  // a group of D frames from t0 on: the raw logits, the row maxima, the forced flags, the path's (pair, kind)
+  auto load_group = [&](int t0, float (&ob)[D][S], float (&oi)[D][S], float (&oo)[D], float (&om)[D], unsigned (&of)[D], int (&os)[D]) {
+#pragma unroll
+    for (int f = 0; f < D; ++f) {
+      const int t = min(t0 + f, T - 1);        // (the tail of the last group re-reads the last row; it is never used)
+      const float* z = Z + (long)t * a.ldl;
+      oo[f] = z[o_id];
+      om[f] = rowmax[t];
+      of[f] = forced[t];
+      os[f] = sel[t];
+#pragma unroll
+      for (int s = 0; s < S; ++s) { ob[f][s] = z[colB[s]]; oi[f][s] = z[colI[s]]; }
+    }
+  };
+  // ... turned into emissions in place, off the chain
+  auto to_emissions = [&](float (&ob)[D][S], float (&oi)[D][S], float (&oo)[D], const float (&om)[D], const unsigned (&of)[D]) {
+#pragma unroll
+    for (int f = 0; f < D; ++f) {
+      const bool frc = of[f] != 0;
+      oo[f] = frc ? 1.f : fmaxf(expf(oo[f] - om[f]), TINY);
+#pragma unroll
+      for (int s = 0; s < S; ++s) {
+        ob[f][s] = (frc || !((hasB >> s) & 1u)) ? 0.f : expf(ob[f][s] - om[f]);
+        oi[f][s] = (frc || !((hasI >> s) & 1u)) ? 0.f : expf(oi[f][s] - om[f]);
+      }
+    }
+  };
+
+  float eb[D][S], ei[D][S], eo[D], mx[D];
+  unsigned fc[D];
+  int sl[D];
+
+  // ================================================================================================================ forward sweep
+  float aO = 1.f, aB[S], aI[S];                // the virtual O frame
+#pragma unroll
+  for (int s = 0; s < S; ++s) aB[s] = aI[s] = 0.f;
+  long KA = 0;                                 // true alpha = a 2^KA
+  load_group(0, eb, ei, eo, mx, fc, sl);
+  to_emissions(eb, ei, eo, mx, fc);
+  for (int t0 = 0; t0 < T; t0 += D) {
+    float nb[D][S], ni[D][S], no[D], nm[D];
+    unsigned nf[D];
+    int ns[D];
+    const bool more = t0 + D < T;
+    if (more) load_group(t0 + D, nb, ni, no, nm, nf, ns);
+#pragma unroll
+    for (int f = 0; f < D; ++f) {
+      const int t = t0 + f;
+      if (t < T) {                             // (uniform)
+        float both[S], part[S];                // both: what I-p continues from
+#pragma unroll
+        for (int s = 0; s < S; ++s) part[s] = both[s] = aB[s] + aI[s];
+#pragma unroll
+        for (int h = S / 2; h >= 1; h >>= 1)
+#pragma unroll
+          for (int s = 0; s < h; ++s) part[s] += part[s + h];
+        const float tot = aO + wave_total(part[0]);
+        int ex;
+        const float sc = unscale(tot, ex);
+        KA += ex;
+        const float wts = w * tot * sc;
+        aO = eo[f] * ((aO + w * (tot - aO)) * sc);
+#pragma unroll
+        for (int s = 0; s < S; ++s) {
+          aI[s] = (ei[f][s] * both[s]) * sc;
+          aB[s] = eb[f][s] * wts;
+        }
+        // the path's own phoneme, by the lane that owns it
+        const int se = __builtin_amdgcn_readfirstlane(sl[f]);
+        const int slot = (se & 0xffff) >> 6;
+        float x0 = aO, x1 = 0.f;
+        if (se >> 16) {
+#pragma unroll
+          for (int s = 0; s < S; ++s)
+            if (slot == s) { x0 = aB[s]; x1 = aI[s]; }
+        }
+        if (lane == (se & 63)) {
+          float* r = rec + 3L * t;
+          r[0] = x0;
+          r[1] = x1;
+          r[2] = __int_as_float((int)KA);      // (the low 32 bits: the backward sweep needs only differences of exponents)
+        }
+      }
+    }
+    if (more) {
+      to_emissions(nb, ni, no, nm, nf);
+#pragma unroll
+      for (int f = 0; f < D; ++f) {
+        eo[f] = no[f];
+        sl[f] = ns[f];
+#pragma unroll
+        for (int s = 0; s < S; ++s) { eb[f][s] = nb[f][s]; ei[f][s] = ni[f][s]; }
+      }
+    }
+  }
+  // Z = Zm 2^KA, every state may end the clip
+  float zsum = 0.f;
+  {
+    float part[S];
+#pragma unroll
+    for (int s = 0; s < S; ++s) part[s] = aB[s] + aI[s];
+#pragma unroll
+    for (int h = S / 2; h >= 1; h >>= 1)
+#pragma unroll
+      for (int s = 0; s < h; ++s) part[s] += part[s + h];
+    zsum = aO + wave_total(part[0]);
+  }
+  const double inv_zm = 1.0 / (double)zsum;
+  const int ka_end = (int)KA;
+  __threadfence_block();
+  __syncthreads();                             // the records this wave wrote are read back below
+
+  // =============================================================================================================== backward sweep
+  float bO = 1.f, bX[S];                       // beta(B-p) = beta(I-p): the same successors
+#pragma unroll
+  for (int s = 0; s < S; ++s) bX[s] = 1.f;
+  int KB = 0;                                  // true beta = b 2^KB (low 32 bits)
+  float r0[D], r1[D], r2[D];
+  auto load_rec = [&](int t0, float (&o0)[D], float (&o1)[D], float (&o2)[D]) {
+#pragma unroll
+    for (int f = 0; f < D; ++f) {
+      const float* r = rec + 3L * min(t0 + f, T - 1);
+      o0[f] = r[0];
+      o1[f] = r[1];
+      o2[f] = r[2];
+    }
+  };
+  const int tl = (T - 1) / D * D;              // the last group
+  load_group(tl, eb, ei, eo, mx, fc, sl);
+  load_rec(tl, r0, r1, r2);
+  to_emissions(eb, ei, eo, mx, fc);
+  for (int t0 = tl; t0 >= 0; t0 -= D) {
+    float nb[D][S], ni[D][S], no[D], nm[D], n0[D], n1[D], n2[D];
+    unsigned nf[D];
+    int ns[D];
+    const bool more = t0 > 0;
+    if (more) {
+      load_group(t0 - D, nb, ni, no, nm, nf, ns);
+      load_rec(t0 - D, n0, n1, n2);
+    }
+#pragma unroll
+    for (int f = D - 1; f >= 0; --f) {
+      const int t = t0 + f;
+      if (t < T) {                             // (uniform)
+        // gamma of the path's class at t, by the owning lane
+        const int se = __builtin_amdgcn_readfirstlane(sl[f]);
+        const int slot = (se & 0xffff) >> 6, kind = se >> 16;
+        float bs = bO;
+        if (kind) {
+#pragma unroll
+          for (int s = 0; s < S; ++s)
+            if (slot == s) bs = bX[s];
+        }
+        if (lane == (se & 63)) {
+          const int sh = __float_as_int(r2[f]) + KB - ka_end;          // (wraps to the true, small difference)
+          const double k = ldexp((double)bs * inv_zm, sh);
+          double gp = (double)(r0[f] + r1[f]) * k, gc = (double)(kind == 2 ? r1[f] : r0[f]) * k;
+          gp = gp >= 0.0 ? fmin(gp, 1.0) : 0.0;                        // (a NaN of an overflowed clip is reported as 0)
+          gc = gc >= 0.0 ? fmin(gc, 1.0) : 0.0;
+          post[t] = (float)gp;
+          cls_post[t] = (float)gc;
+        }
+        if (t > 0) {
+          float part[S], pI[S];
+#pragma unroll
+          for (int s = 0; s < S; ++s) {
+            part[s] = eb[f][s] * bX[s];
+            pI[s] = ei[f][s] * bX[s];
+          }
+#pragma unroll
+          for (int h = S / 2; h >= 1; h >>= 1)
+#pragma unroll
+            for (int s = 0; s < h; ++s) part[s] += part[s + h];
+          const float SB = wave_total(part[0]);
+          const float wO = eo[f] * bO;
+          const float cm = wO + SB;
+          int ex;
+          const float sc = unscale(cm, ex);
+          KB += ex;
+          bO = (wO + w * SB) * sc;
+          const float base = w * cm * sc;
+#pragma unroll
+          for (int s = 0; s < S; ++s) bX[s] = base + pI[s] * sc;
+        }
+      }
+    }
+    if (more) {
+      to_emissions(nb, ni, no, nm, nf);
+#pragma unroll
+      for (int f = 0; f < D; ++f) {
+        eo[f] = no[f];
+        sl[f] = ns[f];
+        r0[f] = n0[f];
+        r1[f] = n1[f];
+        r2[f] = n2[f];
+#pragma unroll
+        for (int s = 0; s < S; ++s) { eb[f][s] = nb[f][s]; ei[f][s] = ni[f][s]; }
+      }
+    }
+  }
+
+  // ---- logZ: the mantissa, the exponents, and what the emissions left out (the row maxima; O's logit on a forced frame)
+  double ls = 0.0;
+  for (int t = lane; t < T; t += 64) ls += forced[t] ? (double)Z[(long)t * a.ldl + o_id] : (double)rowmax[t];
+  ls = lattice::wave_sum(ls);
+  if (lane == 0) {
+    a.logz[cl.clip] = (float)(log((double)zsum) + (double)KA * 0.69314718055994530942 + ls);
+    a.status[cl.clip] = 0;
+  }
+}
+
+int launch_chain(int S, const PostLaunch& a, hipStream_t s) {
+  switch (S) {
+    case 2: hipLaunchKernelGGL((decode_post_chain_kernel<2, 16>), dim3(a.n), dim3(64), 0, s, a); break;
+    case 4: hipLaunchKernelGGL((decode_post_chain_kernel<4, 8>), dim3(a.n), dim3(64), 0, s, a); break;
+    case 8: hipLaunchKernelGGL((decode_post_chain_kernel<8, 4>), dim3(a.n), dim3(64), 0, s, a); break;
+    default: hipLaunchKernelGGL((decode_post_chain_kernel<16, 2>), dim3(a.n), dim3(64), 0, s, a); break;
+  }
+  return hipGetLastError() == hipSuccess ? 0 : wfl_fail(-3, "wfl_decode_posterior: launch failed");
+}
+
+}  // namespace
+
+extern "C" {
+
+int64_t wfl_decode_posterior_workspace_bytes(const int32_t* n_frames_host, int32_t n_clips, int32_t n_pairs) {
+  if (n_clips < 0 || n_pairs < 0 || (n_clips > 0 && !n_frames_host)) return -1;
+  const int S = slots_of(n_pairs);
+  int64_t words = 0;
+  for (int b = 0; b < n_clips; ++b) {
+    if (n_frames_host[b] < 0) return -1;
+    if (S) words += clip_words(n_frames_host[b]);
+  }
+  return words * 4;
+}
+
+int32_t wfl_decode_posterior(const float* logits, int64_t ldl, int32_t C, int32_t o_id, const int64_t* frame_off_host,
+                             const int32_t* n_frames_host, int32_t n_clips, const int32_t* pairs, int32_t n_pairs, float lambda,
+                             float threshold, const int32_t* ids, void* workspace, int64_t workspace_bytes, float* logz, float* post,
+                             float* cls_post, int32_t* status, void* stream) {
+  const char* fn = "wfl_decode_posterior";
+  bool any_frame;
+  if (const int rc = bio::check_args(fn, C, o_id, ldl, frame_off_host, n_frames_host, n_clips, n_pairs, lambda, threshold, any_frame)) return rc;
+  if (n_clips == 0) return 0;
+  if (!logz || !status || (n_pairs > 0 && !pairs) || (any_frame && (!logits || !ids || !post || !cls_post)))
+    return lattice::fail(fn, -1, "null device pointer");
+  const int fill = bio::refused_status(C, n_pairs);
+  const int S = fill ? 0 : slots_of(n_pairs);
+  const int64_t need = fill ? 0 : wfl_decode_posterior_workspace_bytes(n_frames_host, n_clips, n_pairs);
+  if (const int rc = lattice::check_workspace(fn, need, workspace, workspace_bytes)) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  PostLaunch a{};
+  a.logits = logits; a.ldl = ldl; a.C = C; a.o_id = o_id; a.pairs = pairs; a.n_pairs = n_pairs; a.lambda = lambda;
+  a.threshold = threshold; a.ids = ids; a.ws = (unsigned*)workspace; a.logz = logz; a.post = post; a.cls_post = cls_post;
+  a.status = status; a.fill_status = fill;
+  return lattice::launch_clips<1>(           // one group: the clips in their order
+      a, n_clips,
+      [&](int b, long off, bio::Clip& c, int&) {
+        c = bio::Clip{(long)frame_off_host[b], off, n_frames_host[b], b};
+        return fill ? 0 : clip_words(c.T);
+      },
+      [&](int, const PostLaunch& a) {
+        if (fill) {
+          hipLaunchKernelGGL(decode_post_fill_kernel, dim3(a.n), dim3(64), 0, s, a);
+          return hipGetLastError() == hipSuccess ? 0 : lattice::fail(fn, -3, "launch failed");
+        }
+        int max_t = 0;
+        for (int j = 0; j < a.n; ++j) max_t = std::max(max_t, a.clip[j].T);
+        if (max_t > 0) {
+          hipLaunchKernelGGL(decode_post_pre_kernel, dim3((max_t + 3) / 4, a.n), dim3(256), 0, s, a);
+          if (hipGetLastError() != hipSuccess) return lattice::fail(fn, -3, "launch failed");
+        }
+        return launch_chain(S, a, s);
+      });
+}
+
+}  // extern "C"

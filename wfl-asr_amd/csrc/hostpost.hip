@@ -83,6 +83,7 @@ int32_t wfl_host_decode_bio(const int32_t* ids, int32_t T, const float* offsets,
       if (open_ph >= 0) close(i, false);
       open_ph = phon[id]; open_idx = i;
     } else if (k == 2) {                // "I-x": continues x, or closes the open run and opens one for x
+      // (wfl-asr_amd/decode.py:_run_frames restates when a run opens and closes, for the frames of each segment: keep the two in step)
       const int ph = phon[id];
       if (ph != open_ph) {
         if (open_ph >= 0) close(i, false);

@@ -9,12 +9,15 @@ follows `B-p` or `I-p`, and every run that is opened costs `switch_penalty` nats
 
   class_table         label set -> (O class, (B class, I class or -1) per phoneme); every other class is never chosen
   bio_viterbi         the C ABI on CUDA tensors: a ragged batch of clips in one call
+  decode_posteriors   forward-backward over the same grammar (csrc/decode_posterior.hip, `wfl_decode_posterior`): logZ, and per frame
+                      the posterior of the phoneme and of the exact class the path chose (`postprocess.decode_scores`)
   path_segments_free  the path's ids of a file, chunk by chunk, -> segments; a run that crosses a chunk seam is one segment
+  free_score          those outputs + bio_viterbi's score -> FreeScore / RunScore records, run j being segment j of the path
 """
 from __future__ import annotations
 
 import ctypes as C
-from typing import NamedTuple
+from typing import List, NamedTuple
 
 import numpy as np
 import torch
@@ -27,6 +30,7 @@ from .align import class_pairs
 DECODE_MODES = ("argmax", "viterbi")
 MAX_CLASSES = 1024         # wfl_decode's class cap (status 2 above it)
 STATUS_OK, STATUS_OVER_CAP, STATUS_BAD_CLASS = 0, 2, 4
+STATUS_NOT_A_PATH = 8      # wfl_decode_posterior alone: `ids` is not a path of the grammar
 
 
 class ClassTable(NamedTuple):
@@ -68,18 +72,8 @@ def workspace_bytes(n_frames, n_pairs) -> int:
     return n
 
 
-def bio_viterbi(logits, n_frames, table, switch_penalty, threshold, frame_offsets=None, stream=None):
-    """BIO-grammar Viterbi decode of a ragged batch of clips on the GPU.
-
-    logits          [rows, C] float32 CUDA tensor (rows contiguous in C; clip b = rows frame_offsets[b] .. + n_frames[b]).  With
-                    `lang_id=None` these are the language-averaged logits the forward returns, and the search runs on those.
-    n_frames        frames per clip (host ints)
-    table           class_table(label_list), or any (o_id, [(B class, I class or -1), ...])
-    switch_penalty  lambda >= 0, nats per opened run
-    threshold       a frame whose largest softmax probability is below it can only be O (0: no frame is forced)
-    frame_offsets   first row of each clip (default: the clips back to back)
-    -> (ids [rows] int32, score [clips] float32, status [clips] int32), CUDA tensors on `stream`'s device.  A clip with status != 0
-    (STATUS_OVER_CAP: C > 1024; STATUS_BAD_CLASS: a class of the table out of range or used twice) is O everywhere, score 0."""
+def _check_clips(logits, n_frames, table, switch_penalty, threshold, frame_offsets):
+    """The validation bio_viterbi and decode_posteriors share -> (o_id, pairs, nb, T, F0)."""
     if not logits.is_cuda or logits.dim() != 2 or logits.dtype != torch.float32 or (logits.numel() and logits.stride(1) != 1):
         raise ValueError("logits must be a [rows, C] float32 CUDA tensor with contiguous rows")
     o_id, pairs = table
@@ -99,6 +93,22 @@ def bio_viterbi(logits, n_frames, table, switch_penalty, threshold, frame_offset
     F0 = np.ascontiguousarray(frame_offsets, np.int64).reshape(nb)
     if nb and (int(F0.min()) < 0 or int((F0 + T).max()) > logits.shape[0]):
         raise ValueError("a clip's frames run past the logits rows")
+    return int(o_id), pairs, nb, T, F0
+
+
+def bio_viterbi(logits, n_frames, table, switch_penalty, threshold, frame_offsets=None, stream=None):
+    """BIO-grammar Viterbi decode of a ragged batch of clips on the GPU.
+
+    logits          [rows, C] float32 CUDA tensor (rows contiguous in C; clip b = rows frame_offsets[b] .. + n_frames[b]).  With
+                    `lang_id=None` these are the language-averaged logits the forward returns, and the search runs on those.
+    n_frames        frames per clip (host ints)
+    table           class_table(label_list), or any (o_id, [(B class, I class or -1), ...])
+    switch_penalty  lambda >= 0, nats per opened run
+    threshold       a frame whose largest softmax probability is below it can only be O (0: no frame is forced)
+    frame_offsets   first row of each clip (default: the clips back to back)
+    -> (ids [rows] int32, score [clips] float32, status [clips] int32), CUDA tensors on `stream`'s device.  A clip with status != 0
+    (STATUS_OVER_CAP: C > 1024; STATUS_BAD_CLASS: a class of the table out of range or used twice) is O everywhere, score 0."""
+    o_id, pairs, nb, T, F0 = _check_clips(logits, n_frames, table, switch_penalty, threshold, frame_offsets)
     lib = _lib.load()
     dev = logits.device
     rows = logits.shape[0]
@@ -120,6 +130,49 @@ def bio_viterbi(logits, n_frames, table, switch_penalty, threshold, frame_offset
     return ids, score[:nb], status[:nb]
 
 
+def posterior_workspace_bytes(n_frames, n_pairs) -> int:
+    lib = _lib.load()
+    T = np.ascontiguousarray(n_frames, np.int32)
+    n = int(lib.wfl_decode_posterior_workspace_bytes(_hp(T), T.size, int(n_pairs)))
+    if n < 0:
+        raise _lib.WflError("wfl_decode_posterior_workspace_bytes: negative frame or pair count")
+    return n
+
+
+def decode_posteriors(logits, n_frames, table, switch_penalty, threshold, ids, frame_offsets=None, stream=None):
+    """Forward-backward over the grammar of bio_viterbi, for the same ragged batch of clips (same arguments), given its `ids`.
+
+    ids  [rows] int32 CUDA tensor: bio_viterbi's output for these clips (row frame_offsets[b] + t)
+    -> (logz [clips], post [rows], cls_post [rows], status [clips]): float32 / int32 CUDA tensors.  logz: log of the summed weight
+    exp(sum of the logits on the path - switch_penalty * runs opened) of every legal path; post: the posterior that the frame belongs
+    to the phoneme the path gives it (B-p or I-p; to O on an O frame), in [0, 1]; cls_post: the posterior of the exact class, so on a
+    run's first frame that the run opens exactly there; cls_post <= post.  Rows outside the clips are not written.  A clip with
+    status != 0 gets zeros (STATUS_NOT_A_PATH: `ids` is not a legal path of these clips)."""
+    o_id, pairs, nb, T, F0 = _check_clips(logits, n_frames, table, switch_penalty, threshold, frame_offsets)
+    dev = logits.device
+    if not isinstance(ids, torch.Tensor) or not ids.is_cuda or ids.device != dev or ids.dtype != torch.int32 or ids.dim() != 1 \
+            or (ids.numel() and ids.stride(0) != 1) or ids.shape[0] != logits.shape[0]:
+        raise ValueError("ids must be bio_viterbi's [rows] int32 CUDA tensor for these logits")
+    lib = _lib.load()
+    rows = logits.shape[0]
+    ws_n = posterior_workspace_bytes(T, len(pairs)) if logits.shape[1] <= MAX_CLASSES else 0
+    ws = torch.empty(max(ws_n, 1), dtype=torch.uint8, device=dev)
+    d_pairs = torch.from_numpy(pairs if len(pairs) else np.full((1, 2), -1, np.int32)).to(dev)
+    per_frame = torch.empty((2, max(rows, 1)), dtype=torch.float32, device=dev)
+    logz = torch.empty(max(nb, 1), dtype=torch.float32, device=dev)
+    status = torch.empty(max(nb, 1), dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        st = stream if stream is not None else torch.cuda.current_stream(dev)
+        ldl = logits.stride(0) if logits.numel() else logits.shape[1]      # (an empty tensor's strides say nothing)
+        rc = lib.wfl_decode_posterior(_ptr(logits), ldl, logits.shape[1], o_id, _hp(F0), _hp(T), nb, _ptr(d_pairs), len(pairs),
+                                      float(switch_penalty), float(threshold), _ptr(ids), _ptr(ws), ws_n, _ptr(logz),
+                                      _ptr(per_frame[0]), _ptr(per_frame[1]), _ptr(status), C.c_void_p(st.cuda_stream))
+        _lib.check(rc, "wfl_decode_posterior")
+        for t in (d_pairs, ws):
+            t.record_stream(st)
+    return logz[:nb], per_frame[0, :rows], per_frame[1, :rows], status[:nb]
+
+
 def path_segments_free(ids, chunk_frames, chunk_offsets, chunk_clock, table: npost.LabelTable, frame_duration):
     """A legal path over a file's chunks (ids concatenated, chunk_frames[c] valid frames each) -> (start_s [n], end_s [n],
     phoneme index [n]) arrays, the phoneme index being table.names'.
@@ -129,12 +182,36 @@ def path_segments_free(ids, chunk_frames, chunk_offsets, chunk_clock, table: npo
     seam (the next chunk begins with I-p of the phoneme the previous chunk ended in) is joined into one segment.  `B-p` directly after
     `B-p` or `I-p` of the same phoneme starts a new segment.  A segment's end is capped at the next segment's start, so the segments
     never overlap, and is never before its own start."""
+    segs, _ = _walk_runs(ids, chunk_frames, chunk_offsets, chunk_clock, table, frame_duration)
+    return (np.array([g[0] for g in segs], np.float64), np.array([g[1] for g in segs], np.float64),
+            np.array([g[2] for g in segs], np.int32))
+
+
+def _run_frames(idc, table: npost.LabelTable):
+    """(first, end) frame of every run of one chunk's ids, as the native BIO decoder (wfl_host_decode_bio) opens and closes them: B-x
+    opens a run; I-x continues an open run of x and otherwise opens one; O, the next opening and the chunk's end close it; any other
+    tag is passed over."""
+    rel = np.nonzero(table.kind[idc] != 3)[0]
+    k, p = table.kind[idc[rel]], table.phon[idc[rel]]
+    prev_k, prev_p = np.concatenate([[0], k[:-1]]), np.concatenate([[-1], p[:-1]])
+    opens = (k == 1) | ((k == 2) & ((prev_k == 0) | (prev_p != p)))
+    events = np.nonzero(opens | (k == 0))[0]
+    at = np.nonzero(opens)[0]
+    closes = np.concatenate([rel[events], [len(idc)]])           # the frame of every event, then the chunk's end
+    return rel[at], closes[np.searchsorted(events, at, side="right")]
+
+
+def _walk_runs(ids, chunk_frames, chunk_offsets, chunk_clock, table: npost.LabelTable, frame_duration, want_frames=False):
+    """The one walk over a path's runs that path_segments_free and free_score share -> (segments [[start_s, end_s, phoneme]], frames):
+    frames[j] holds the (first, end) frame ranges, in the file's concatenated frames, that make up segment j (two or more when the run
+    crosses a chunk seam; only with want_frames)."""
     ids = np.asarray(ids, np.int32)
-    segs = []                                            # [start, end, phoneme]
+    segs, frames = [], []
     pos = 0
     last = -1                                            # the class of the previous chunk's last frame
     for Tc, offs, t0 in zip(chunk_frames, chunk_offsets, chunk_clock):
         idc = ids[pos:pos + Tc]
+        base = pos
         pos += Tc
         if Tc == 0:
             continue
@@ -142,15 +219,59 @@ def path_segments_free(ids, chunk_frames, chunk_offsets, chunk_clock, table: npo
         first = int(idc[0])
         joined = bool(len(s) and segs and last >= 0 and table.kind[first] == 2 and table.kind[last] in (1, 2)
                       and table.phon[first] == table.phon[last] and segs[-1][2] == int(ph[0]))
+        if want_frames:
+            starts, ends = _run_frames(idc, table)
+            if len(starts) != len(s):
+                raise RuntimeError(f"path decode: {len(s)} segments for {len(starts)} runs")
         for j in range(len(s)):
+            f0, f1 = (int(starts[j]), int(ends[j])) if want_frames else (0, 0)
             if j == 0 and joined:                        # the run continues from the previous chunk
                 segs[-1][1] = float(e[0]) + t0
+                frames[-1].append((base + f0, base + f1))
             else:
                 segs.append([float(s[j]) + t0, float(e[j]) + t0, int(ph[j])])
+                frames.append([(base + f0, base + f1)])
         last = int(idc[-1])
     for j, g in enumerate(segs):
         if j + 1 < len(segs):                            # the decoder closes a run at the NEXT run's first frame (its end offset):
             g[1] = min(g[1], segs[j + 1][0])             # keep the segments from overlapping
         g[1] = max(g[1], g[0])
-    return (np.array([g[0] for g in segs], np.float64), np.array([g[1] for g in segs], np.float64),
-            np.array([g[2] for g in segs], np.int32))
+    return segs, frames
+
+
+# ---------------------------------------------------------------------------------------------------------------- decode scores
+class RunScore(NamedTuple):
+    start_s: float              # the run's segment, as path_segments_free gives it
+    end_s: float
+    phoneme: str
+    posterior: float            # mean over the run's frames of decode_posteriors' post: that the frame belongs to this phoneme
+    start_posterior: float      # cls_post at the run's first frame: that a run of this phoneme opens exactly there
+    min_frame_posterior: float  # the run's weakest frame
+
+
+class FreeScore(NamedTuple):
+    path_log_posterior: float        # score + sum lse - logz, <= 0: log probability of the chosen path among the legal ones
+    mean_frame_logprob: float        # score / n_frames
+    legal_log_mass_per_frame: float  # (logz - sum lse) / n_frames, <= 0: how much of the frames' probability the grammar keeps
+    min_posterior: float             # the weakest run's posterior (1 for a path without runs)
+    runs: List[RunScore]
+
+
+def free_score(score, logz, sum_lse, post, cls_post, ids, chunk_frames, chunk_offsets, chunk_clock, table: npost.LabelTable,
+               frame_duration, names=None):
+    """One file's FreeScore from bio_viterbi's score and ids, decode_posteriors' logz / post / cls_post for the file (host values;
+    per-frame arrays over the file's concatenated frames) and the sum of the frames' log-sum-exp.  The runs are walked exactly as
+    path_segments_free walks them (seam joins included), so run j is segment j of the path.  names: phoneme index -> the name to
+    report (default table.names)."""
+    post, cls_post = np.asarray(post, np.float64).reshape(-1), np.asarray(cls_post, np.float64).reshape(-1)
+    ids = np.asarray(ids, np.int32).reshape(-1)
+    if not len(post) == len(cls_post) == len(ids) == int(sum(chunk_frames)):
+        raise ValueError("one post, cls_post and id per frame of the chunk plan")
+    segs, frames = _walk_runs(ids, chunk_frames, chunk_offsets, chunk_clock, table, frame_duration, want_frames=True)
+    names = table.names if names is None else names
+    runs = []
+    for (s, e, ph), parts in zip(segs, frames):
+        p = np.concatenate([post[a:b] for a, b in parts])
+        runs.append(RunScore(float(s), float(e), str(names[ph]), float(p.mean()), float(cls_post[parts[0][0]]), float(p.min())))
+    score, logz, sum_lse, n = float(score), float(logz), float(sum_lse), max(len(ids), 1)
+    return FreeScore(score + sum_lse - logz, score / n, (logz - sum_lse) / n, min((r.posterior for r in runs), default=1.0), runs)

@@ -416,6 +416,14 @@ class Labeler:
             raise ValueError("align_scores needs align='viterbi' (postprocess.align: viterbi): the greedy match has no lattice to score")
         return on
 
+    def decode_scores_on(self, decode_scores=None, decode=None) -> bool:
+        """Whether decode scores are asked for (None: config postprocess.decode_scores, else off).  They score the grammar search's
+        path: with decode "argmax" the request is an error."""
+        on = bool(self.config.get("postprocess", {}).get("decode_scores", False) if decode_scores is None else decode_scores)
+        if on and self.decode_options(decode)[0] != "viterbi":
+            raise ValueError("decode_scores needs decode='viterbi' (postprocess.decode: viterbi): the argmax decode has no lattice to score")
+        return on
+
     def decode_options(self, decode=None, switch_penalty=None):
         """-> (mode, switch penalty in nats).  mode: "argmax" (the reference's free decode, the default) or "viterbi" (the BIO-grammar
         search over the frame logits, decode.py); None: config postprocess.decode, else argmax.  switch_penalty: a number >= 0, used
@@ -428,8 +436,9 @@ class Labeler:
         return mode, float(lam)
 
     def label_files(self, audio_paths, lang_id=None, confidence_threshold=0.0, verbose=True, align=None, align_scores=None,
-                    decode=None, switch_penalty=None):
-        """-> list (per file) of [(start_s, end_s, phoneme)] after merge + forced alignment; with align_scores, (that list, scores).
+                    decode=None, switch_penalty=None, decode_scores=None):
+        """-> list (per file) of [(start_s, end_s, phoneme)] after merge + forced alignment; with align_scores or decode_scores, (that
+        list, scores).
 
         align: "greedy" -- a `{audio}.txt` transcript is matched onto the freely decoded segments (infer.py:30-60, 312-319);
         "viterbi" -- files with a transcript are aligned by a search over their frame logits on the GPU (align.py: one segment
@@ -445,17 +454,24 @@ class Labeler:
         "viterbi" -- every file whose segments come from the free decode (no transcript, or one under align "greedy", which is then
         matched over the new segments) is decoded by the BIO-grammar search over its frame logits on the GPU (decode.py), each opened
         run costing `switch_penalty` nats; postprocess.median_filter is not applied to those files.  None: config postprocess.decode /
-        postprocess.switch_penalty, else argmax / 0."""
+        postprocess.switch_penalty, else argmax / 0.
+
+        decode_scores (with decode "viterbi" only; None: config postprocess.decode_scores, else off): also return scores[i], a
+        decode.FreeScore from a forward-backward pass over the grammar for a file the grammar search decoded (per run of the path, before
+        merge_segments and any string match, the posterior of its phoneme, of its opening frame and of its weakest frame), or None for a
+        file that fell back to the argmax decode (and, with a message, for one whose path wfl_decode_posterior does not accept).  With
+        both kinds of scores on, each file gets its own kind.  The segments are the same with and without."""
         final, scores = self._label_scored(audio_paths, lang_id, confidence_threshold, verbose, align, align_scores, decode,
-                                           switch_penalty)
-        return (final, scores) if self.align_scores_on(align_scores, align) else final
+                                           switch_penalty, decode_scores)
+        return (final, scores) if self.align_scores_on(align_scores, align) or self.decode_scores_on(decode_scores, decode) else final
 
     def _label_scored(self, audio_paths, lang_id=None, confidence_threshold=0.0, verbose=True, align=None, align_scores=None,
-                      decode=None, switch_penalty=None):
+                      decode=None, switch_penalty=None, decode_scores=None):
         """label_files, always -> (segments, scores): the files are split once into those a transcript is Viterbi-aligned to, those the
         grammar search decodes and those left to the argmax decode, and each subset's results go back to its files' places."""
         want_scores = self.align_scores_on(align_scores, align)
         mode, lam = self.decode_options(decode, switch_penalty)
+        want_free = self.decode_scores_on(decode_scores, decode)
         if mode == "viterbi" and int(self.config["postprocess"].get("median_filter", 0)) > 1:
             print("decode: viterbi -- postprocess.median_filter is not applied (the switch penalty takes its place)")
         if lang_id is not None and self.lang2id and lang_id > max(self.lang2id.values()):
@@ -474,8 +490,10 @@ class Labeler:
         searched = {}
         if mode == "viterbi":
             # the free decode by the grammar search; a file it could not decode (with a message) takes the argmax decode
-            got = self._decode_viterbi(paths(free), lang_id, confidence_threshold, verbose, lam)
+            got, free_scores = self._decode_viterbi(paths(free), lang_id, confidence_threshold, verbose, lam, want_free)
             searched = {free[j]: segs for j, segs in got.items()}
+            for j, sc in free_scores.items():
+                scores[free[j]] = sc
         argmax = [fi for fi in free if fi not in searched]
         for fi, segs in zip(argmax, self._label_files_greedy(paths(argmax), lang_id, confidence_threshold, verbose)):
             final[fi] = segs
@@ -657,19 +675,21 @@ class Labeler:
             clock += len(x) / self.sr
         return cf, co, cc
 
-    def _decode_viterbi(self, audio_paths, lang_id, threshold, verbose, switch_penalty):
-        """decode="viterbi": the free decode of files by the BIO-grammar search (decode.py, wfl_decode) -> {file index: segments
-        [(start_s, end_s, phoneme)] after the merge-map names and merge_segments, before any string match}.  The files' chunks are
+    def _decode_viterbi(self, audio_paths, lang_id, threshold, verbose, switch_penalty, want_scores=False):
+        """decode="viterbi": the free decode of files by the BIO-grammar search (decode.py, wfl_decode) -> ({file index: segments
+        [(start_s, end_s, phoneme)] after the merge-map names and merge_segments, before any string match}, {file index: FreeScore}).  The files' chunks are
         forwarded with logits (kept on the device); each file's chunks' valid logits rows are concatenated on the device, so one
         search covers the whole file and a run may cross a chunk seam; the files of a wave go to wfl_decode as one ragged batch and
         only ids / status come back to the host.  A file whose status is not 0 is left out (with a message): the caller decodes it
-        by argmax."""
+        by argmax.  want_scores: right after the search, one wfl_decode_posterior call per wave over the clips it decoded (same
+        logits, the device `ids`) and one log-sum-exp reduction over the wave's logits, the per-frame arrays back in one more copy; without, the second dict stays empty and the calls are
+        the search's alone."""
         lang_name = self._lang_name(lang_id)
-        remap, _ = self._names_for(lang_name)
+        remap, names = self._names_for(lang_name)
         if self._decode_table is None:
             self._decode_table = DC.class_table(self.labels)
         table = self._decode_table
-        out = {}
+        out, scored = {}, {}
         for files, by_file in self._file_waves(audio_paths, verbose):
             sel = [fi for fi in files if fi in by_file]
             out.update((fi, []) for fi in files if fi not in by_file)      # no audio: no segments
@@ -677,19 +697,41 @@ class Labeler:
                 continue
             _, rows = self._forward_with_logits(sel, by_file, lang_id, threshold)
             frames, lg = self._file_rows(rows, by_file, sel)
-            d_ids, _, d_st = DC.bio_viterbi(lg, frames, table, switch_penalty, threshold)
+            d_ids, d_score, d_st = DC.bio_viterbi(lg, frames, table, switch_penalty, threshold)
             ids_all, st_all = d_ids.cpu().numpy(), d_st.cpu().numpy()
+            f0 = np.concatenate([[0], np.cumsum(np.asarray(frames, np.int64))[:-1]])
+            raw = {}                                          # clip -> (score, logz, sum lse, post, cls_post, posterior status)
+            ok = [b for b in range(len(sel)) if st_all[b] == DC.STATUS_OK]
+            if want_scores and ok:
+                d_logz, d_post, d_cls, d_pst = DC.decode_posteriors(lg, [frames[b] for b in ok], table, switch_penalty, threshold, d_ids,
+                                                                    frame_offsets=f0[ok])
+                # (the files' sums of log-sum-exp, path_log_posterior's third term, which the ABI has no output for: one fp32
+                # reduction over the wave's logits, then differences of one running sum in double)
+                run = torch.cat([lg.new_zeros(1, dtype=torch.float64), torch.logsumexp(lg, dim=1).double().cumsum(0)])
+                ends = torch.from_numpy(f0[ok] + np.asarray(frames, np.int64)[ok]).to(lg.device)
+                d_lse = run[ends] - run[torch.from_numpy(f0[ok]).to(lg.device)]
+                n_ok, nr = len(ok), lg.shape[0]
+                h = torch.cat([d_score[ok].double(), d_logz.double(), d_lse, d_pst.double(), d_post.double(), d_cls.double()]).cpu().numpy()
+                for j, b in enumerate(ok):                    # one copy
+                    a, z = int(f0[b]), int(f0[b]) + frames[b]
+                    raw[b] = (h[j], h[n_ok + j], h[2 * n_ok + j], h[4 * n_ok + a:4 * n_ok + z], h[4 * n_ok + nr + a:4 * n_ok + nr + z],
+                              int(h[3 * n_ok + j]))
             pos = 0
             for b, fi in enumerate(sel):
                 n = frames[b]
                 if st_all[b] != DC.STATUS_OK:
                     print(f"{audio_paths[fi]}: viterbi decode not possible (wfl_decode status {int(st_all[b])}); using the argmax decode")
                 else:
-                    s, e, ph = DC.path_segments_free(ids_all[pos:pos + n], *self._chunk_plan(rows, by_file[fi], fi), self._table,
-                                                     frame_duration)
+                    plan = self._chunk_plan(rows, by_file[fi], fi)
+                    s, e, ph = DC.path_segments_free(ids_all[pos:pos + n], *plan, self._table, frame_duration)
                     out[fi] = self._merged_tuples(s, e, remap[ph] if ph.size else ph, lang_name)
+                    if b in raw and raw[b][5] == DC.STATUS_OK:
+                        scored[fi] = DC.free_score(*raw[b][:5], ids_all[pos:pos + n], *plan, self._table, frame_duration,
+                                                   names=[names[int(r)] for r in remap[:len(self._table.names)]])
+                    elif want_scores:                         # (wfl_decode_posterior refused the path wfl_decode gave it)
+                        print(f"{audio_paths[fi]}: no decode scores (wfl_decode_posterior status {raw[b][5] if b in raw else None})")
                 pos += n
-        return out
+        return out, scored
 
     def _label_viterbi(self, audio_paths, transcripts, lang_id, threshold, verbose, want_scores=False):
         """Files with a transcript, align="viterbi".  Their chunks are forwarded with logits (kept on the device); the free decode of
@@ -827,6 +869,11 @@ def _check_align_scores(align, align_scores):
         raise ValueError("align_scores needs align='viterbi': the greedy match has no lattice to score")
 
 
+def _check_decode_scores(decode, decode_scores):
+    if decode_scores and decode == "argmax":
+        raise ValueError("decode_scores needs decode='viterbi': the argmax decode has no lattice to score")
+
+
 def _lab_int(t):
     """The integer a .lab line carries for a time (the native formatter's truncating int(t * 1e7))."""
     return int(npost.format_lab_tuples([(t, t, "x")]).split()[0])
@@ -855,6 +902,34 @@ def format_review_tsv(named_scores) -> str:
     return "\n".join(lines) + "\n"
 
 
+DECODE_SCORES_NOTE = "runs are the path's runs before merge_segments and any transcript match"
+
+
+def format_decode_scores_tsv(score, lab_lines) -> str:
+    """`{stem}.decode_scores.tsv` of one file the grammar search decoded (decode.FreeScore): a `#` header line with the file's four
+    figures, the number of runs beside the number of lines of the .lab, and the note that the two may differ; then one line per run of
+    the path, `start end phoneme posterior start_posterior min_frame_posterior`, start / end being the integers a .lab line carries
+    for the run's times."""
+    lines = [f"# path_log_posterior={score.path_log_posterior:.4f}\tmean_frame_logprob={score.mean_frame_logprob:.6f}\t"
+             f"legal_log_mass_per_frame={score.legal_log_mass_per_frame:.6f}\tmin_posterior={score.min_posterior:.6f}\t"
+             f"runs={len(score.runs)} lab_lines={int(lab_lines)}\t{DECODE_SCORES_NOTE}"]
+    for r in score.runs:
+        lines.append(f"{_lab_int(r.start_s)}\t{_lab_int(r.end_s)}\t{r.phoneme}\t{r.posterior:.6f}\t{r.start_posterior:.6f}\t"
+                     f"{r.min_frame_posterior:.6f}")
+    return "\n".join(lines) + "\n"
+
+
+def format_decode_review_tsv(named_scores) -> str:
+    """`decode_scores.tsv` of a folder: [(file name, FreeScore)] -> one line per scored file, the weakest first (ascending
+    min_posterior; ties by name): the review list."""
+    rows = sorted(named_scores, key=lambda r: (r[1].min_posterior, r[0]))
+    lines = ["# file\tmin_posterior\tpath_log_posterior\tmean_frame_logprob\tlegal_log_mass_per_frame\truns"]
+    for name, sc in rows:
+        lines.append(f"{name}\t{sc.min_posterior:.6f}\t{sc.path_log_posterior:.4f}\t{sc.mean_frame_logprob:.6f}\t"
+                     f"{sc.legal_log_mass_per_frame:.6f}\t{len(sc.runs)}")
+    return "\n".join(lines) + "\n"
+
+
 def _write_text(path, text, what):
     d = os.path.dirname(path)
     if d:
@@ -868,36 +943,52 @@ def scores_path(lab_path):
     return os.path.splitext(lab_path)[0] + ".scores.tsv"
 
 
+def decode_scores_path(lab_path):
+    return os.path.splitext(lab_path)[0] + ".decode_scores.tsv"
+
+
+def _write_score(lab_path, segments, score):
+    """The scores file of one labelled file beside its .lab, by the kind of its score (None: no file)."""
+    if isinstance(score, DC.FreeScore):
+        _write_text(decode_scores_path(lab_path), format_decode_scores_tsv(score, len(segments)), "Decode scores")
+    elif score is not None:
+        _write_text(scores_path(lab_path), format_scores_tsv(score), "Alignment scores")
+
+
 def infer_audio(audio_path, config_path="config.yaml", checkpoint_path="best_model.pt", output_lab_path=None, device="cuda",
                 lang_id=None, sample=False, top_k=0, top_p=0.0, temperature=1.0, confidence_threshold=0.0, align=None,
-                align_scores=None, decode=None, switch_penalty=None):
+                align_scores=None, decode=None, switch_penalty=None, decode_scores=None):
     """align: "greedy" | "viterbi" | None (config postprocess.align, else greedy): how a `{audio}.txt` transcript is aligned
     (Labeler.label_files).  align_scores (viterbi only; None: config postprocess.align_scores): also write `{stem}.scores.tsv`
     beside the .lab when the file was Viterbi-aligned (format_scores_tsv).  decode: "argmax" | "viterbi" | None (config
     postprocess.decode, else argmax) and switch_penalty (nats, >= 0; None: config postprocess.switch_penalty, else 0): how the free
-    decode is made (Labeler.label_files)."""
+    decode is made (Labeler.label_files).  decode_scores (decode viterbi only; None: config postprocess.decode_scores): also write
+    `{stem}.decode_scores.tsv` beside the .lab when the grammar search decoded the file (format_decode_scores_tsv)."""
     _check_align(align)
     _check_align_scores(align, align_scores)
     _check_decode(decode, switch_penalty)
+    _check_decode_scores(decode, decode_scores)
     lab = _labeler(config_path, checkpoint_path, device)
     (segments,), (score,) = lab._label_scored([audio_path], lang_id=lang_id, confidence_threshold=confidence_threshold, align=align,
-                                              align_scores=align_scores, decode=decode, switch_penalty=switch_penalty)
+                                              align_scores=align_scores, decode=decode, switch_penalty=switch_penalty,
+                                              decode_scores=decode_scores)
     if output_lab_path:
         if os.path.abspath(output_lab_path) == os.path.abspath(audio_path):
             # the reference would truncate the input WAV here (infer.py:410-411 + utils.py:77)
             output_lab_path = os.path.splitext(audio_path)[0] + ".lab"
         _write_lab(output_lab_path, segments)
-        if score is not None:
-            _write_text(scores_path(output_lab_path), format_scores_tsv(score), "Alignment scores")
+        _write_score(output_lab_path, segments, score)
     return segments
 
 
 def infer_folder(folder_path: str, config_path: str = "config.yaml", checkpoint_path: str = "best_model.pt",
                  output_dir: str = "outputs", device: str = "cuda", lang_id: int = None, sample=False, top_k=0, top_p=0.0,
-                 temperature=1.0, confidence_threshold=0.0, align=None, align_scores=None, decode=None, switch_penalty=None):
+                 temperature=1.0, confidence_threshold=0.0, align=None, align_scores=None, decode=None, switch_penalty=None,
+                 decode_scores=None):
     _check_align(align)
     _check_align_scores(align, align_scores)
     _check_decode(decode, switch_penalty)
+    _check_decode_scores(decode, decode_scores)
     wav_files = sorted(f for f in os.listdir(folder_path) if f.lower().endswith(".wav"))
     os.makedirs(output_dir, exist_ok=True)
     # one process per GPU: every rank labels its own share of the files and writes its own .lab files (no collective)
@@ -909,21 +1000,27 @@ def infer_folder(folder_path: str, config_path: str = "config.yaml", checkpoint_
     lab = _labeler(config_path, checkpoint_path, device)
     paths = [os.path.join(folder_path, f) for f in wav_files]
     want_scores = lab.align_scores_on(align_scores, align)
+    want_free = lab.decode_scores_on(decode_scores, decode)
     all_segments, all_scores = lab._label_scored(paths, lang_id=lang_id, confidence_threshold=confidence_threshold, align=align,
-                                                 align_scores=align_scores, decode=decode, switch_penalty=switch_penalty) if paths else ([], [])
+                                                 align_scores=align_scores, decode=decode, switch_penalty=switch_penalty,
+                                                 decode_scores=decode_scores) if paths else ([], [])
     for wav_file, segments, score in zip(wav_files, all_segments, all_scores):
         print(f"\nInferencing: {wav_file}")
         lab_path = os.path.join(output_dir, os.path.splitext(wav_file)[0] + ".lab")
         _write_lab(lab_path, segments)
-        if score is not None:
-            _write_text(scores_path(lab_path), format_scores_tsv(score), "Alignment scores")
+        _write_score(lab_path, segments, score)
         print("Predicted segments:")
         for start, end, ph in segments:
             print(f"({round(start, 2)}, {round(end, 2)}, {ph})")
     if want_scores:
         name = "alignment_scores.tsv" if world == 1 else f"alignment_scores.rank{rank}.tsv"
-        _write_text(os.path.join(output_dir, name), format_review_tsv([(f, sc) for f, sc in zip(wav_files, all_scores) if sc is not None]),
-                    "Review list")
+        _write_text(os.path.join(output_dir, name),
+                    format_review_tsv([(f, sc) for f, sc in zip(wav_files, all_scores) if isinstance(sc, AL.FileScore)]), "Review list")
+    if want_free:
+        name = "decode_scores.tsv" if world == 1 else f"decode_scores.rank{rank}.tsv"
+        _write_text(os.path.join(output_dir, name),
+                    format_decode_review_tsv([(f, sc) for f, sc in zip(wav_files, all_scores) if isinstance(sc, DC.FreeScore)]),
+                    "Decode review list")
     return all_segments
 
 
@@ -956,8 +1053,12 @@ def main(argv=None):
     @click.option("--switch-penalty", "switch_penalty", type=float, default=None,
                   help="With --decode viterbi: cost of every opened run, in nats (>= 0). Default: config postprocess.switch_penalty, "
                        "else 0.")
+    @click.option("--decode-scores", "decode_scores", is_flag=True, default=None,
+                  help="With --decode viterbi: also write {stem}.decode_scores.tsv beside each searched .lab (per-run posteriors by "
+                       "forward-backward over the grammar on the GPU) and, for a folder, decode_scores.tsv. Default: config "
+                       "postprocess.decode_scores, else off.")
     def cli(path, checkpoint, config, output, lang_id, sample, top_k, top_p, temperature, device, confidence_threshold, align,
-            align_scores, decode, switch_penalty):
+            align_scores, decode, switch_penalty, decode_scores):
         if switch_penalty is not None and not switch_penalty >= 0.0:
             raise click.UsageError("--switch-penalty must be >= 0 (nats)")
         if sample:
@@ -1000,6 +1101,10 @@ def main(argv=None):
             _check_decode(decode, switch_penalty)
         except ValueError as err:
             raise click.UsageError(f"postprocess.decode / postprocess.switch_penalty: {err}")
+        if decode_scores is None:
+            decode_scores = bool(cfg["postprocess"].get("decode_scores", False))
+        if decode_scores and decode != "viterbi":
+            raise click.UsageError("--decode-scores (postprocess.decode_scores) needs --decode viterbi")
         output_path = inf_path if output == "." else output
         if not inf_path.exists():
             print(f"Unable to locate folder {str(inf_path)}")
@@ -1008,7 +1113,7 @@ def main(argv=None):
             lang_id = None
         kw = dict(config_path=str(config), checkpoint_path=str(checkpoint), device=device, lang_id=lang_id, sample=sample,
                   top_k=top_k, top_p=top_p, temperature=temperature, confidence_threshold=confidence_threshold, align=align,
-                  align_scores=align_scores, decode=decode, switch_penalty=switch_penalty)
+                  align_scores=align_scores, decode=decode, switch_penalty=switch_penalty, decode_scores=decode_scores)
         if inf_path.is_dir():
             infer_folder(folder_path=str(inf_path), output_dir=str(output_path), **kw)
         else:
