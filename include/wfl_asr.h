@@ -419,6 +419,31 @@ int32_t wfl_decode_posterior(const float* logits, int64_t ldl, int32_t C, int32_
                              float threshold, const int32_t* ids, void* workspace, int64_t workspace_bytes, float* logz, float* post,
                              float* cls_post, int32_t* status, void* stream);
 
+/* ---- BIO-grammar Viterbi decode with a phone-bigram prior on the GPU (`postprocess.phoneme_bigram`; wfl-asr_amd/decode.py,
+ * wfl-asr_amd/phonotactics.py).  No counterpart in the reference.  Clips, logits, pairs, o_id, threshold, ids, score and the argument
+ * checks are wfl_decode's; so are the states, the legality rule, the forced-to-O rule and the virtual O frame before frame 0.  Symbols:
+ * 0 is O, 1 + p is phoneme p of `pairs`; N = n_pairs + 1.  trans (device) is an [N][N] fp32 table, rows the PREVIOUS symbol, entries
+ * finite or -inf (a forbidden succession), never NaN or +inf, every trans[p][O] finite (so every clip has a path); trans[O][O] is never
+ * read.  The path maximises
+ *     sum_t z[t][c_t] + sum over opened runs trans[previous symbol][opened symbol],
+ * a run being opened by every B-q frame and by every O frame whose predecessor is not O; the previous symbol of a frame in B-p or I-p is
+ * p, of a frame in O it is O; O after O and I-q after B-q / I-q cost nothing.  With end[O] = d[O], end[p] = max(d[B-p], d[I-p]):
+ *     B-q : z + max_s (end[s] + trans[s][q])     O : z + max(d[O], max_{p != O} (end[p] + trans[p][O]))     I-q : z + max(d[I-q], d[B-q])
+ * The lowest predecessor symbol wins a tie; of a symbol's two states I-p wins a tie against B-p; the end state is the best symbol of the
+ * last frame, the lowest on a tie.  With trans identically -lambda the objective is wfl_decode's.
+ * status[b]: 0 ok; 2 C above 1024 or N above WFL_DECODE_BIGRAM_MAX_SYMBOLS (O + 191 phonemes: the table, 144 KiB of fp32 at the cap,
+ * stays in one CU's LDS for the whole clip); 4 a bad class table, as wfl_decode.  A clip with status != 0 gets ids = o_id and score 0.
+ * One workgroup per clip: a clip decoded alone equals the same clip inside any batch, bit for bit.  fp32 state scores, renormalised every
+ * 16 frames (offset in double).
+ * Workspace, per clip with T > 0, in 4-byte words: round_up_64(T ceil(N / 2)) + 2 round_up_64(T)  (per frame and symbol 16 bits: the
+ * winning predecessor symbol | the I bit << 8 | O's bit << 9; the frames' log-sum-exp; their forced flags); 0 above the symbol cap. */
+#define WFL_DECODE_BIGRAM_MAX_SYMBOLS 192
+int64_t wfl_decode_bigram_workspace_bytes(const int32_t* n_frames_host, int32_t n_clips, int32_t n_pairs);
+int32_t wfl_decode_bigram(const float* logits, int64_t ldl, int32_t C, int32_t o_id, const int64_t* frame_off_host,
+                          const int32_t* n_frames_host, int32_t n_clips, const int32_t* pairs, int32_t n_pairs, const float* trans,
+                          float threshold, void* workspace, int64_t workspace_bytes, int32_t* ids, float* score, int32_t* status,
+                          void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -9,6 +9,8 @@ follows `B-p` or `I-p`, and every run that is opened costs `switch_penalty` nats
 
   class_table         label set -> (O class, (B class, I class or -1) per phoneme); every other class is never chosen
   bio_viterbi         the C ABI on CUDA tensors: a ragged batch of clips in one call
+  bio_viterbi_bigram  the same search with a phone-bigram prior: a table of transition weights per (previous symbol, opened symbol)
+                      in place of the flat switch penalty (csrc/decode_bigram.hip, `wfl_decode_bigram`; phonotactics.py makes the table)
   decode_posteriors   forward-backward over the same grammar (csrc/decode_posterior.hip, `wfl_decode_posterior`): logZ, and per frame
                       the posterior of the phoneme and of the exact class the path chose (`postprocess.decode_scores`)
   path_segments_free  the path's ids of a file, chunk by chunk, -> segments; a run that crosses a chunk seam is one segment
@@ -29,6 +31,7 @@ from .align import class_pairs
 
 DECODE_MODES = ("argmax", "viterbi")
 MAX_CLASSES = 1024         # wfl_decode's class cap (status 2 above it)
+MAX_BIGRAM_SYMBOLS = 192   # wfl_decode_bigram's symbol cap, O + 191 phonemes (WFL_DECODE_BIGRAM_MAX_SYMBOLS; status 2 above it)
 STATUS_OK, STATUS_OVER_CAP, STATUS_BAD_CLASS = 0, 2, 4
 STATUS_NOT_A_PATH = 8      # wfl_decode_posterior alone: `ids` is not a path of the grammar
 
@@ -126,6 +129,70 @@ def bio_viterbi(logits, n_frames, table, switch_penalty, threshold, frame_offset
                             C.c_void_p(st.cuda_stream))
         _lib.check(rc, "wfl_decode")
         for t in (d_pairs, ws):
+            t.record_stream(st)
+    return ids, score[:nb], status[:nb]
+
+
+def bigram_workspace_bytes(n_frames, n_pairs) -> int:
+    lib = _lib.load()
+    T = np.ascontiguousarray(n_frames, np.int32)
+    n = int(lib.wfl_decode_bigram_workspace_bytes(_hp(T), T.size, int(n_pairs)))
+    if n < 0:
+        raise _lib.WflError("wfl_decode_bigram_workspace_bytes: negative frame or pair count")
+    return n
+
+
+def check_transitions(trans, n_pairs) -> np.ndarray:
+    """A table of transition weights for bio_viterbi_bigram -> contiguous float32 [n_pairs + 1, n_pairs + 1].  Symbol 0 is O, symbol
+    1 + p is phoneme p of the class table; rows are the previous symbol.  Entries are finite or -inf (a forbidden succession): never
+    NaN, never +inf, and every [p][O] finite, so every clip has a path (a forced frame can only be O); [O][O] is never read and not
+    checked."""
+    if isinstance(trans, torch.Tensor):
+        trans = trans.detach().cpu().numpy()
+    w = np.asarray(trans)
+    n = int(n_pairs) + 1
+    if w.dtype != np.float32:
+        raise ValueError(f"trans must be float32, got {w.dtype}")
+    if w.shape != (n, n):
+        raise ValueError(f"trans must be a [{n}, {n}] table (O and the {n - 1} phonemes of the class table), got {list(w.shape)}")
+    w = np.array(w, np.float32, order="C")            # (a copy)
+    w[0, 0] = 0.0                                     # [O][O] is never read (O after O costs nothing): whatever it holds is fine
+    if np.isnan(w).any():
+        raise ValueError("trans holds a NaN")
+    if np.isposinf(w).any():
+        raise ValueError("trans holds +inf (entries are finite, or -inf for a forbidden succession)")
+    if not np.isfinite(w[:, 0]).all():
+        raise ValueError("every trans[p][O] must be finite: a frame forced to O needs a way in")
+    return w
+
+
+def bio_viterbi_bigram(logits, n_frames, table, trans, threshold, frame_offsets=None, stream=None):
+    """bio_viterbi with a phone-bigram prior: every opened run costs trans[previous symbol][opened symbol] (natural-log weights, <= 0
+    for a prior) instead of one flat switch penalty.  Arguments and results are bio_viterbi's, but:
+
+    trans  float32 [n + 1, n + 1] over O (symbol 0) and the n phonemes of `table` in its order (check_transitions;
+           phonotactics.transition_table builds it from a phoneme_bigram.json); -inf forbids a succession.
+    A label set with more than 191 phonemes is over the kernel's cap (MAX_BIGRAM_SYMBOLS): STATUS_OVER_CAP, O everywhere, score 0."""
+    o_id, pairs, nb, T, F0 = _check_clips(logits, n_frames, table, 0.0, threshold, frame_offsets)
+    w = check_transitions(trans, len(pairs))
+    lib = _lib.load()
+    dev = logits.device
+    rows = logits.shape[0]
+    ws_n = bigram_workspace_bytes(T, len(pairs)) if logits.shape[1] <= MAX_CLASSES else 0
+    ws = torch.empty(max(ws_n, 1), dtype=torch.uint8, device=dev)
+    d_pairs = torch.from_numpy(pairs if len(pairs) else np.full((1, 2), -1, np.int32)).to(dev)
+    d_trans = torch.from_numpy(w).to(dev)
+    ids = torch.empty(rows, dtype=torch.int32, device=dev)
+    score = torch.empty(max(nb, 1), dtype=torch.float32, device=dev)
+    status = torch.empty(max(nb, 1), dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        st = stream if stream is not None else torch.cuda.current_stream(dev)
+        ldl = logits.stride(0) if logits.numel() else logits.shape[1]      # (an empty tensor's strides say nothing)
+        rc = lib.wfl_decode_bigram(_ptr(logits), ldl, logits.shape[1], int(o_id), _hp(F0), _hp(T), nb, _ptr(d_pairs), len(pairs),
+                                   _ptr(d_trans), float(threshold), _ptr(ws), ws_n, _ptr(ids), _ptr(score), _ptr(status),
+                                   C.c_void_p(st.cuda_stream))
+        _lib.check(rc, "wfl_decode_bigram")
+        for t in (d_pairs, d_trans, ws):
             t.record_stream(st)
     return ids, score[:nb], status[:nb]
 

@@ -105,6 +105,7 @@ class Labeler:
         self._pinned = {}                                    # dtype -> ring of flat pinned staging buffers (_pinned_ring)
         self._names_cache = {}                               # _names_for
         self._decode_table = None                            # decode.class_table(labels), built by the first grammar decode
+        self._bigram_cache = {}                              # (path, switch penalty, weight) -> transition table (_bigram_table)
         self._wave_items = None                              # chunks per wave of files; None: _wave()
 
     # ------------------------------------------------------------------ the batched loop
@@ -435,8 +436,31 @@ class Labeler:
         check_options(mode, lam)
         return mode, float(lam)
 
+    def bigram_options(self, phoneme_bigram=None, bigram_weight=None, decode=None, decode_scores=None):
+        """-> (path of the phoneme bigram file or None, its weight).  None: config postprocess.phoneme_bigram /
+        postprocess.bigram_weight, else no bigram / 1.  Both belong to decode "viterbi" alone (ValueError otherwise); the weight is a
+        number >= 0; decode_scores with a bigram is refused: the posterior must score the grammar the search ran on, and the
+        forward-backward pass knows the flat switch penalty only."""
+        post = self.config.get("postprocess", {})
+        path = post.get("phoneme_bigram") if phoneme_bigram is None else phoneme_bigram
+        given = post.get("bigram_weight") if bigram_weight is None else bigram_weight
+        _check_bigram(self.decode_options(decode)[0], path, given)
+        if path and self.decode_scores_on(decode_scores, decode):
+            raise ValueError(BIGRAM_SCORES_ERROR)
+        return (str(path) if path else None), float(1.0 if given is None else given)
+
+    def _bigram_table(self, path, switch_penalty, weight):
+        """The search's transition table for the bigram file `path` (absolute, or relative to the working directory)."""
+        from . import phonotactics as PH
+        key = (os.path.abspath(path), float(switch_penalty), float(weight))
+        if key not in self._bigram_cache:
+            if self._decode_table is None:
+                self._decode_table = DC.class_table(self.labels)
+            self._bigram_cache[key] = PH.transition_table(PH.load(key[0]), self._decode_table, self.labels, switch_penalty, weight)
+        return self._bigram_cache[key]
+
     def label_files(self, audio_paths, lang_id=None, confidence_threshold=0.0, verbose=True, align=None, align_scores=None,
-                    decode=None, switch_penalty=None, decode_scores=None):
+                    decode=None, switch_penalty=None, decode_scores=None, phoneme_bigram=None, bigram_weight=None):
         """-> list (per file) of [(start_s, end_s, phoneme)] after merge + forced alignment; with align_scores or decode_scores, (that
         list, scores).
 
@@ -456,22 +480,29 @@ class Labeler:
         run costing `switch_penalty` nats; postprocess.median_filter is not applied to those files.  None: config postprocess.decode /
         postprocess.switch_penalty, else argmax / 0.
 
+        phoneme_bigram (with decode "viterbi" only; None: config postprocess.phoneme_bigram, else none): a phoneme_bigram.json
+        (phonotactics.py); the search then pays  bigram_weight * log P(opened symbol | previous symbol) - switch_penalty  for every
+        opened run instead of the flat penalty (decode.bio_viterbi_bigram).  bigram_weight: a number >= 0 (None: config
+        postprocess.bigram_weight, else 1).  decode_scores cannot be combined with a bigram.
+
         decode_scores (with decode "viterbi" only; None: config postprocess.decode_scores, else off): also return scores[i], a
         decode.FreeScore from a forward-backward pass over the grammar for a file the grammar search decoded (per run of the path, before
         merge_segments and any string match, the posterior of its phoneme, of its opening frame and of its weakest frame), or None for a
         file that fell back to the argmax decode (and, with a message, for one whose path wfl_decode_posterior does not accept).  With
         both kinds of scores on, each file gets its own kind.  The segments are the same with and without."""
         final, scores = self._label_scored(audio_paths, lang_id, confidence_threshold, verbose, align, align_scores, decode,
-                                           switch_penalty, decode_scores)
+                                           switch_penalty, decode_scores, phoneme_bigram, bigram_weight)
         return (final, scores) if self.align_scores_on(align_scores, align) or self.decode_scores_on(decode_scores, decode) else final
 
     def _label_scored(self, audio_paths, lang_id=None, confidence_threshold=0.0, verbose=True, align=None, align_scores=None,
-                      decode=None, switch_penalty=None, decode_scores=None):
+                      decode=None, switch_penalty=None, decode_scores=None, phoneme_bigram=None, bigram_weight=None):
         """label_files, always -> (segments, scores): the files are split once into those a transcript is Viterbi-aligned to, those the
         grammar search decodes and those left to the argmax decode, and each subset's results go back to its files' places."""
         want_scores = self.align_scores_on(align_scores, align)
         mode, lam = self.decode_options(decode, switch_penalty)
         want_free = self.decode_scores_on(decode_scores, decode)
+        bigram, bigram_w = self.bigram_options(phoneme_bigram, bigram_weight, decode, decode_scores)
+        trans = self._bigram_table(bigram, lam, bigram_w) if bigram else None
         if mode == "viterbi" and int(self.config["postprocess"].get("median_filter", 0)) > 1:
             print("decode: viterbi -- postprocess.median_filter is not applied (the switch penalty takes its place)")
         if lang_id is not None and self.lang2id and lang_id > max(self.lang2id.values()):
@@ -490,7 +521,7 @@ class Labeler:
         searched = {}
         if mode == "viterbi":
             # the free decode by the grammar search; a file it could not decode (with a message) takes the argmax decode
-            got, free_scores = self._decode_viterbi(paths(free), lang_id, confidence_threshold, verbose, lam, want_free)
+            got, free_scores = self._decode_viterbi(paths(free), lang_id, confidence_threshold, verbose, lam, want_free, trans)
             searched = {free[j]: segs for j, segs in got.items()}
             for j, sc in free_scores.items():
                 scores[free[j]] = sc
@@ -675,7 +706,7 @@ class Labeler:
             clock += len(x) / self.sr
         return cf, co, cc
 
-    def _decode_viterbi(self, audio_paths, lang_id, threshold, verbose, switch_penalty, want_scores=False):
+    def _decode_viterbi(self, audio_paths, lang_id, threshold, verbose, switch_penalty, want_scores=False, trans=None):
         """decode="viterbi": the free decode of files by the BIO-grammar search (decode.py, wfl_decode) -> ({file index: segments
         [(start_s, end_s, phoneme)] after the merge-map names and merge_segments, before any string match}, {file index: FreeScore}).  The files' chunks are
         forwarded with logits (kept on the device); each file's chunks' valid logits rows are concatenated on the device, so one
@@ -683,7 +714,8 @@ class Labeler:
         only ids / status come back to the host.  A file whose status is not 0 is left out (with a message): the caller decodes it
         by argmax.  want_scores: right after the search, one wfl_decode_posterior call per wave over the clips it decoded (same
         logits, the device `ids`) and one log-sum-exp reduction over the wave's logits, the per-frame arrays back in one more copy; without, the second dict stays empty and the calls are
-        the search's alone."""
+        the search's alone.  trans: the transition table of a phoneme bigram (_bigram_table); the search is then wfl_decode_bigram's,
+        everything around it the same."""
         lang_name = self._lang_name(lang_id)
         remap, names = self._names_for(lang_name)
         if self._decode_table is None:
@@ -697,7 +729,10 @@ class Labeler:
                 continue
             _, rows = self._forward_with_logits(sel, by_file, lang_id, threshold)
             frames, lg = self._file_rows(rows, by_file, sel)
-            d_ids, d_score, d_st = DC.bio_viterbi(lg, frames, table, switch_penalty, threshold)
+            if trans is None:
+                d_ids, d_score, d_st = DC.bio_viterbi(lg, frames, table, switch_penalty, threshold)
+            else:
+                d_ids, d_score, d_st = DC.bio_viterbi_bigram(lg, frames, table, trans, threshold)
             ids_all, st_all = d_ids.cpu().numpy(), d_st.cpu().numpy()
             f0 = np.concatenate([[0], np.cumsum(np.asarray(frames, np.int64))[:-1]])
             raw = {}                                          # clip -> (score, logz, sum lse, post, cls_post, posterior status)
@@ -720,7 +755,8 @@ class Labeler:
             for b, fi in enumerate(sel):
                 n = frames[b]
                 if st_all[b] != DC.STATUS_OK:
-                    print(f"{audio_paths[fi]}: viterbi decode not possible (wfl_decode status {int(st_all[b])}); using the argmax decode")
+                    fn = "wfl_decode" if trans is None else "wfl_decode_bigram"
+                    print(f"{audio_paths[fi]}: viterbi decode not possible ({fn} status {int(st_all[b])}); using the argmax decode")
                 else:
                     plan = self._chunk_plan(rows, by_file[fi], fi)
                     s, e, ph = DC.path_segments_free(ids_all[pos:pos + n], *plan, self._table, frame_duration)
@@ -864,6 +900,24 @@ def _check_decode(decode, switch_penalty):
     check_options(decode, switch_penalty)
 
 
+BIGRAM_SCORES_ERROR = ("decode_scores cannot be combined with a phoneme bigram: the forward-backward pass scores the flat switch "
+                       "penalty, not the bigram the search ran on")
+
+
+def _check_bigram(decode, phoneme_bigram, bigram_weight):
+    """phoneme_bigram / bigram_weight (None = not given) belong to decode "viterbi"; the weight is a number >= 0."""
+    if bigram_weight is not None:
+        try:
+            ok = float(bigram_weight) >= 0.0 and not isinstance(bigram_weight, bool)
+        except (TypeError, ValueError):
+            ok = False
+        if not ok:
+            raise ValueError(f"bigram_weight must be a number >= 0, got {bigram_weight!r}")
+    if (phoneme_bigram or bigram_weight is not None) and decode != "viterbi":
+        raise ValueError("phoneme_bigram / bigram_weight need decode='viterbi' (postprocess.decode: viterbi): the argmax decode has no "
+                         "search to weigh")
+
+
 def _check_align_scores(align, align_scores):
     if align_scores and align == "greedy":
         raise ValueError("align_scores needs align='viterbi': the greedy match has no lattice to score")
@@ -957,21 +1011,25 @@ def _write_score(lab_path, segments, score):
 
 def infer_audio(audio_path, config_path="config.yaml", checkpoint_path="best_model.pt", output_lab_path=None, device="cuda",
                 lang_id=None, sample=False, top_k=0, top_p=0.0, temperature=1.0, confidence_threshold=0.0, align=None,
-                align_scores=None, decode=None, switch_penalty=None, decode_scores=None):
+                align_scores=None, decode=None, switch_penalty=None, decode_scores=None, phoneme_bigram=None, bigram_weight=None):
     """align: "greedy" | "viterbi" | None (config postprocess.align, else greedy): how a `{audio}.txt` transcript is aligned
     (Labeler.label_files).  align_scores (viterbi only; None: config postprocess.align_scores): also write `{stem}.scores.tsv`
     beside the .lab when the file was Viterbi-aligned (format_scores_tsv).  decode: "argmax" | "viterbi" | None (config
     postprocess.decode, else argmax) and switch_penalty (nats, >= 0; None: config postprocess.switch_penalty, else 0): how the free
     decode is made (Labeler.label_files).  decode_scores (decode viterbi only; None: config postprocess.decode_scores): also write
-    `{stem}.decode_scores.tsv` beside the .lab when the grammar search decoded the file (format_decode_scores_tsv)."""
+    `{stem}.decode_scores.tsv` beside the .lab when the grammar search decoded the file (format_decode_scores_tsv).  phoneme_bigram /
+    bigram_weight (decode viterbi only; None: config postprocess.phoneme_bigram / postprocess.bigram_weight): the phone-bigram prior
+    of the search (Labeler.label_files)."""
     _check_align(align)
     _check_align_scores(align, align_scores)
     _check_decode(decode, switch_penalty)
     _check_decode_scores(decode, decode_scores)
+    if decode is not None:
+        _check_bigram(decode, phoneme_bigram, bigram_weight)
     lab = _labeler(config_path, checkpoint_path, device)
     (segments,), (score,) = lab._label_scored([audio_path], lang_id=lang_id, confidence_threshold=confidence_threshold, align=align,
                                               align_scores=align_scores, decode=decode, switch_penalty=switch_penalty,
-                                              decode_scores=decode_scores)
+                                              decode_scores=decode_scores, phoneme_bigram=phoneme_bigram, bigram_weight=bigram_weight)
     if output_lab_path:
         if os.path.abspath(output_lab_path) == os.path.abspath(audio_path):
             # the reference would truncate the input WAV here (infer.py:410-411 + utils.py:77)
@@ -984,11 +1042,13 @@ def infer_audio(audio_path, config_path="config.yaml", checkpoint_path="best_mod
 def infer_folder(folder_path: str, config_path: str = "config.yaml", checkpoint_path: str = "best_model.pt",
                  output_dir: str = "outputs", device: str = "cuda", lang_id: int = None, sample=False, top_k=0, top_p=0.0,
                  temperature=1.0, confidence_threshold=0.0, align=None, align_scores=None, decode=None, switch_penalty=None,
-                 decode_scores=None):
+                 decode_scores=None, phoneme_bigram=None, bigram_weight=None):
     _check_align(align)
     _check_align_scores(align, align_scores)
     _check_decode(decode, switch_penalty)
     _check_decode_scores(decode, decode_scores)
+    if decode is not None:
+        _check_bigram(decode, phoneme_bigram, bigram_weight)
     wav_files = sorted(f for f in os.listdir(folder_path) if f.lower().endswith(".wav"))
     os.makedirs(output_dir, exist_ok=True)
     # one process per GPU: every rank labels its own share of the files and writes its own .lab files (no collective)
@@ -1001,9 +1061,11 @@ def infer_folder(folder_path: str, config_path: str = "config.yaml", checkpoint_
     paths = [os.path.join(folder_path, f) for f in wav_files]
     want_scores = lab.align_scores_on(align_scores, align)
     want_free = lab.decode_scores_on(decode_scores, decode)
+    lab.bigram_options(phoneme_bigram, bigram_weight, decode, decode_scores)
     all_segments, all_scores = lab._label_scored(paths, lang_id=lang_id, confidence_threshold=confidence_threshold, align=align,
                                                  align_scores=align_scores, decode=decode, switch_penalty=switch_penalty,
-                                                 decode_scores=decode_scores) if paths else ([], [])
+                                                 decode_scores=decode_scores, phoneme_bigram=phoneme_bigram,
+                                                 bigram_weight=bigram_weight) if paths else ([], [])
     for wav_file, segments, score in zip(wav_files, all_segments, all_scores):
         print(f"\nInferencing: {wav_file}")
         lab_path = os.path.join(output_dir, os.path.splitext(wav_file)[0] + ".lab")
@@ -1057,8 +1119,15 @@ def main(argv=None):
                   help="With --decode viterbi: also write {stem}.decode_scores.tsv beside each searched .lab (per-run posteriors by "
                        "forward-backward over the grammar on the GPU) and, for a folder, decode_scores.tsv. Default: config "
                        "postprocess.decode_scores, else off.")
+    @click.option("--phoneme-bigram", "phoneme_bigram", type=str, default=None,
+                  help="With --decode viterbi: a phoneme_bigram.json (python -m wfl_asr_amd.phonotactics); every opened run then costs "
+                       "bigram_weight * log P(symbol | previous symbol) - switch_penalty. Default: config postprocess.phoneme_bigram, "
+                       "else none.")
+    @click.option("--bigram-weight", "bigram_weight", type=float, default=None,
+                  help="With --phoneme-bigram: the weight of the bigram's log probabilities (>= 0). Default: config "
+                       "postprocess.bigram_weight, else 1.")
     def cli(path, checkpoint, config, output, lang_id, sample, top_k, top_p, temperature, device, confidence_threshold, align,
-            align_scores, decode, switch_penalty, decode_scores):
+            align_scores, decode, switch_penalty, decode_scores, phoneme_bigram, bigram_weight):
         if switch_penalty is not None and not switch_penalty >= 0.0:
             raise click.UsageError("--switch-penalty must be >= 0 (nats)")
         if sample:
@@ -1105,6 +1174,16 @@ def main(argv=None):
             decode_scores = bool(cfg["postprocess"].get("decode_scores", False))
         if decode_scores and decode != "viterbi":
             raise click.UsageError("--decode-scores (postprocess.decode_scores) needs --decode viterbi")
+        if phoneme_bigram is None:
+            phoneme_bigram = cfg["postprocess"].get("phoneme_bigram")
+        if bigram_weight is None:
+            bigram_weight = cfg["postprocess"].get("bigram_weight")
+        try:
+            _check_bigram(decode, phoneme_bigram, bigram_weight)
+        except ValueError as err:
+            raise click.UsageError(f"--phoneme-bigram / --bigram-weight (postprocess.phoneme_bigram, postprocess.bigram_weight): {err}")
+        if phoneme_bigram and decode_scores:
+            raise click.UsageError(BIGRAM_SCORES_ERROR)
         output_path = inf_path if output == "." else output
         if not inf_path.exists():
             print(f"Unable to locate folder {str(inf_path)}")
@@ -1113,7 +1192,8 @@ def main(argv=None):
             lang_id = None
         kw = dict(config_path=str(config), checkpoint_path=str(checkpoint), device=device, lang_id=lang_id, sample=sample,
                   top_k=top_k, top_p=top_p, temperature=temperature, confidence_threshold=confidence_threshold, align=align,
-                  align_scores=align_scores, decode=decode, switch_penalty=switch_penalty, decode_scores=decode_scores)
+                  align_scores=align_scores, decode=decode, switch_penalty=switch_penalty, decode_scores=decode_scores,
+                  phoneme_bigram=phoneme_bigram, bigram_weight=bigram_weight)
         if inf_path.is_dir():
             infer_folder(folder_path=str(inf_path), output_dir=str(output_path), **kw)
         else:
