@@ -241,3 +241,54 @@ def test_abi_entries_and_the_symbol_cap():
     assert DC.bigram_workspace_bytes(T, 70) == 4 * ((384 + 128) + (256 + 128))
     assert DC.bigram_workspace_bytes(T, 191) == 4 * ((960 + 128) + (704 + 128))
     assert DC.bigram_workspace_bytes(T, 192) == 0                       # over the cap: nothing is searched
+
+
+def test_decode_bigram_validates_its_arguments_without_gpu():
+    """wfl_decode_bigram's host side: the bad arguments of test_decode_cpu.py's list that the entry has (it takes no lambda), a null
+    `trans` with frames present, and the workspace rule in full."""
+    import ctypes
+    import __graft_entry__ as g
+    g.build()
+    from wfl_asr_amd import _lib
+    lib = _lib.load()
+    P = ctypes.c_void_p
+    buf = (ctypes.c_char * 64)()
+    d = ctypes.cast(buf, P)                        # never dereferenced: every call below fails on the host
+    fo = np.zeros(1, np.int64)
+    T = np.array([10], np.int32)
+    h = lambda a: a.ctypes.data_as(P)              # noqa: E731
+
+    def call(C=141, o_id=0, ldl=141, fo_=fo, T_=T, ws=None, ws_bytes=0, logits=d, n=1, ids=d, pairs=d, n_pairs=70, trans=d, thr=0.0,
+             score=d, status=d):
+        return lib.wfl_decode_bigram(logits, ldl, C, o_id, h(fo_) if fo_ is not None else None, h(T_), n, pairs, n_pairs, trans, thr, ws,
+                                     ws_bytes, ids, score, status, None)
+
+    need = lib.wfl_decode_bigram_workspace_bytes(h(T), 1, 70)
+    assert need > 0
+    for kw, word in ((dict(C=0), b"C < 1"), (dict(o_id=141), b"o_id"), (dict(o_id=-1), b"o_id"), (dict(ldl=100), b"ldl"),
+                     (dict(n=-1), b"negative count"), (dict(n_pairs=-1), b"negative count"), (dict(thr=-0.1), b"threshold"),
+                     (dict(thr=float("nan")), b"threshold"), (dict(fo_=None, ws=d, ws_bytes=need), b"null host"),
+                     (dict(T_=np.array([-2], np.int32), ws=d, ws_bytes=need), b"negative"),
+                     (dict(fo_=np.array([-1], np.int64), ws=d, ws_bytes=need), b"negative offset"),
+                     (dict(logits=None, ws=d, ws_bytes=need), b"null device"), (dict(ids=None, ws=d, ws_bytes=need), b"null device"),
+                     (dict(score=None, ws=d, ws_bytes=need), b"null device"), (dict(status=None, ws=d, ws_bytes=need), b"null device"),
+                     (dict(pairs=None, ws=d, ws_bytes=need), b"null device"), (dict(trans=None, ws=d, ws_bytes=need), b"null device"),
+                     (dict(ws=d, ws_bytes=need - 1), b"workspace"), (dict(ws=None, ws_bytes=need), b"workspace")):
+        assert call(**kw) != 0, kw
+        err = lib.wfl_last_error()
+        assert b"wfl_decode_bigram" in err and word in err, (kw, err)
+    assert call(n=0) == 0                          # nothing to do
+
+    # per clip with T > 0: round_up_64(T ceil(N / 2)) + 2 round_up_64(T) words, N = n_pairs + 1; nothing is searched over the cap
+    r64 = lambda v: (v + 63) // 64 * 64            # noqa: E731
+    Ts = [1500, 1, 0, 63, 64, 65]
+    Tn = np.array(Ts, np.int32)
+    size = lib.wfl_decode_bigram_workspace_bytes
+    for n_pairs in (0, 1, 70, 190, 191):
+        want = sum(4 * (r64(t * ((n_pairs + 2) // 2)) + 2 * r64(t)) for t in Ts if t > 0)
+        assert size(h(Tn), len(Ts), n_pairs) == want, n_pairs
+    assert size(h(Tn), len(Ts), 192) == 0
+    assert size(h(Tn), -1, 70) < 0 and size(h(Tn), 1, -1) < 0
+    assert size(h(np.array([-1], np.int32)), 1, 70) < 0
+    assert size(None, 1, 70) < 0
+    assert size(None, 0, 70) == 0

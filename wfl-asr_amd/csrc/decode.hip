@@ -9,8 +9,8 @@
 // Frame 0 follows a virtual O frame (d[O] = 0, every other state -inf).  A frame whose largest softmax probability is below the
 // threshold can only be O (every other emission is -inf there).
 //
-// Two kernels.  decode_pre_kernel, one wave per frame, fully parallel: the frame's log-sum-exp and its forced-to-O flag, so no
-// transcendental sits on the serial chain.  decode_chain_kernel, ONE WAVE per clip: lane l owns the phonemes l, l + 64, ... (S slots,
+// Two kernels.  bio::pre_kernel (csrc/bio_grammar.h), one wave per frame, fully parallel: the frame's log-sum-exp and its forced-to-O
+// flag, so no transcendental sits on the serial chain.  decode_chain_kernel, ONE WAVE per clip: lane l owns the phonemes l, l + 64, ... (S slots,
 // both states of each in registers), so the I-p update is lane-local, and the only cross-lane work of a frame is one
 // max-with-index reduction over the 64 lanes (DPP inside a row of 16, two __shfl_xor across rows); its result feeds O and every B-p.
 // There is no LDS exchange and no barrier in the frame loop.  The logits are gathered through the per-lane class ids one group of D
@@ -18,44 +18,33 @@
 // align.hip), so the fp32 scores do not grow with T.
 // Backpointers: per frame 2 S words of I-p bits (one __ballot per slot), and one word a | (O's bit << 16).  Backtrace: lane 0 walks
 // windows of DECODE_W frames that the wave stages into LDS.
-// What wfl_decode_posterior (csrc/decode_posterior.hip) scores this search's paths with lives in csrc/bio_grammar.h: the clip record,
-// the slot configurations, the pre-pass arithmetic, the class table and its validation, the host's argument checks.  From
-// csrc/lattice.h (the alignment kernels' header) come only the class cap, the clips-per-launch constant, round64, wave_sum and the
-// host's clip-table batching and workspace check; the kernels here share nothing with the lattice.
+// This file holds the chain kernel, its backpointer words (the head of a clip's workspace) and the entry's own pointer checks.
+// Everything wfl_decode shares with wfl_decode_bigram and wfl_decode_posterior lives in csrc/bio_grammar.h: the clip record and the
+// common launch fields, the workspace tail, the pre-pass and fill kernels, the class table, the slot dispatch, the argument checks and
+// the host driver of an entry.
 #include "bio_grammar.h"
 #include "wfl_asr.h"
 
 namespace {
 
-using lattice::CLIPS_PER_LAUNCH;
 using lattice::MAX_CLASSES;
-using lattice::round64;
 
 using bio::NO_CLASS;
-using bio::slots_of;
 using DecodeClip = bio::Clip;
 
 constexpr int DECODE_W = 32;                 // backtrace window, frames
 
-struct DecodeLaunch {
-  const float* logits;
-  long ldl;
-  int C, o_id;
-  const int* pairs;  // [n_pairs][2]: B class, I class or -1
-  int n_pairs;
-  float lambda, threshold;
-  unsigned* ws;
+struct DecodeLaunch : bio::Launch {
+  float lambda;
   int* ids;
   float* score;
-  int* status;
-  int n, fill_status;
-  DecodeClip clip[CLIPS_PER_LAUNCH];
 };
 
-// workspace of a clip, in words: [backpointers T (2 S + 1)] [lse T] [forced T], each rounded up to 64 words
-__host__ __device__ inline long off_lse(int T, int S) { return round64((long)T * (2 * S + 1)); }
-__host__ __device__ inline long off_forced(int T, int S) { return off_lse(T, S) + round64(T); }
-inline long clip_words(int T, int S) { return T > 0 ? off_forced(T, S) + round64(T) : 0; }
+// head of a clip's workspace, in words: the backpointers, 2 S + 1 per frame
+struct BpWords {
+  int S;
+  __host__ __device__ long operator()(int T) const { return lattice::round64((long)T * (2 * S + 1)); }
+};
 
 // (value, class) ordered by value, then by the LOWER class id: max-combine of one lane's pair with another's
 __device__ __forceinline__ void take_better(float& v, int& c, float ov, int oc) {
@@ -83,30 +72,6 @@ __device__ __forceinline__ void wave_best(float& v, int& c) {
   }
 }
 
-// ---- per frame: log-sum-exp and the forced-to-O flag.  grid (ceil(max T / 4), clips), 4 waves per block, one wave per frame.
-__global__ __launch_bounds__(256) void decode_pre_kernel(DecodeLaunch a, int S) {
-  const DecodeClip cl = a.clip[blockIdx.y];
-  const int lane = threadIdx.x & 63;
-  const int t = blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (t >= cl.T) return;
-  const float* z = a.logits + (cl.frame_off + t) * a.ldl;
-  float m, se;
-  bio::frame_stats(z, a.C, lane, m, se);
-  if (lane == 0) {
-    unsigned* w = a.ws + cl.ws_off;
-    ((float*)(w + off_lse(cl.T, S)))[t] = m + logf(se);
-    w[off_forced(cl.T, S) + t] = bio::forced_to_o(se, a.threshold);
-  }
-}
-
-// ---- clips that cannot be decoded (C over the cap, more pairs than classes): O everywhere, score 0, the status
-__global__ __launch_bounds__(64) void decode_fill_kernel(DecodeLaunch a) {
-  const DecodeClip cl = a.clip[blockIdx.x];
-  int* ids = a.ids + cl.frame_off;
-  for (int t = threadIdx.x; t < cl.T; t += 64) ids[t] = a.o_id;
-  if (threadIdx.x == 0) { a.score[cl.clip] = 0.f; a.status[cl.clip] = a.fill_status; }
-}
-
 template <int S, int D>
 __global__ __launch_bounds__(64) void decode_chain_kernel(DecodeLaunch a) {
   constexpr int WPF = 2 * S + 1;              // backpointer words per frame
@@ -124,19 +89,15 @@ __global__ __launch_bounds__(64) void decode_chain_kernel(DecodeLaunch a) {
 
   // ---- the class table: every class at most once, all inside [0, C)
   int clsB[S], clsI[S];
-  if (bio::class_table<S>(a.pairs, a.n_pairs, C, o_id, used, info, clsB, clsI)) {
-    for (int t = lane; t < T; t += 64) ids[t] = o_id;
-    if (lane == 0) { a.score[cl.clip] = 0.f; a.status[cl.clip] = 4; }
-    return;
-  }
+  if (bio::class_table<S, 64>(a.pairs, a.n_pairs, C, o_id, used, info, clsB, clsI)) { bio::refuse<64>(a, cl, 4); return; }
   if (T == 0) {
     if (lane == 0) { a.score[cl.clip] = 0.f; a.status[cl.clip] = 0; }
     return;
   }
 
   unsigned* bp = a.ws + cl.ws_off;
-  const float* lse = (const float*)(bp + off_lse(T, S));
-  const unsigned* forced = bp + off_forced(T, S);
+  const float* lse = (const float*)(bp + bio::tail_stat(BpWords{S}(T)));
+  const unsigned* forced = bp + bio::tail_forced(BpWords{S}(T), T);
   const float* Z = a.logits + cl.frame_off * a.ldl;
   int colB[S], colI[S];                        // a state that does not exist reads O's column and is masked to -inf
 #pragma unroll
@@ -281,68 +242,34 @@ __global__ __launch_bounds__(64) void decode_chain_kernel(DecodeLaunch a) {
   }
 }
 
-int launch_chain(int S, const DecodeLaunch& a, hipStream_t s) {
-  switch (S) {
-    case 2: hipLaunchKernelGGL((decode_chain_kernel<2, 16>), dim3(a.n), dim3(64), 0, s, a); break;
-    case 4: hipLaunchKernelGGL((decode_chain_kernel<4, 8>), dim3(a.n), dim3(64), 0, s, a); break;
-    case 8: hipLaunchKernelGGL((decode_chain_kernel<8, 4>), dim3(a.n), dim3(64), 0, s, a); break;
-    default: hipLaunchKernelGGL((decode_chain_kernel<16, 2>), dim3(a.n), dim3(64), 0, s, a); break;
-  }
-  return hipGetLastError() == hipSuccess ? 0 : wfl_fail(-3, "wfl_decode: launch failed");
-}
-
 }  // namespace
 
 extern "C" {
 
 int64_t wfl_decode_workspace_bytes(const int32_t* n_frames_host, int32_t n_clips, int32_t n_pairs) {
-  if (n_clips < 0 || n_pairs < 0 || (n_clips > 0 && !n_frames_host)) return -1;
-  const int S = slots_of(n_pairs);
-  int64_t words = 0;
-  for (int b = 0; b < n_clips; ++b) {
-    if (n_frames_host[b] < 0) return -1;
-    if (S) words += clip_words(n_frames_host[b], S);
-  }
-  return words * 4;
+  const int S = bio::slots_of(n_pairs);
+  return bio::workspace_bytes(n_frames_host, n_clips, n_pairs, S == 0, BpWords{S});
 }
 
 int32_t wfl_decode(const float* logits, int64_t ldl, int32_t C, int32_t o_id, const int64_t* frame_off_host, const int32_t* n_frames_host,
                    int32_t n_clips, const int32_t* pairs, int32_t n_pairs, float lambda, float threshold, void* workspace,
                    int64_t workspace_bytes, int32_t* ids, float* score, int32_t* status, void* stream) {
+  const char* fn = "wfl_decode";
   bool any_frame;
-  if (const int rc = bio::check_args("wfl_decode", C, o_id, ldl, frame_off_host, n_frames_host, n_clips, n_pairs, lambda, threshold, any_frame))
-    return rc;
+  if (const int rc = bio::check_args(fn, C, o_id, ldl, frame_off_host, n_frames_host, n_clips, n_pairs, lambda, threshold, any_frame)) return rc;
   if (n_clips == 0) return 0;
-  if (!score || !status || (n_pairs > 0 && !pairs) || (any_frame && (!logits || !ids)))
-    return wfl_fail(-1, "wfl_decode: null device pointer");
-  // over the class cap: status 2; more pairs than classes (then one is used twice or out of range): status 4
-  const int fill = bio::refused_status(C, n_pairs);
-  const int S = fill ? 0 : slots_of(n_pairs);
-  const int64_t need = fill ? 0 : wfl_decode_workspace_bytes(n_frames_host, n_clips, n_pairs);
-  if (const int rc = lattice::check_workspace("wfl_decode", need, workspace, workspace_bytes)) return rc;
-  hipStream_t s = (hipStream_t)stream;
+  if (!score || !status || (n_pairs > 0 && !pairs) || (any_frame && (!logits || !ids))) return lattice::fail(fn, -1, "null device pointer");
   DecodeLaunch a{};
-  a.logits = logits; a.ldl = ldl; a.C = C; a.o_id = o_id; a.pairs = pairs; a.n_pairs = n_pairs; a.lambda = lambda;
-  a.threshold = threshold; a.ws = (unsigned*)workspace; a.ids = ids; a.score = score; a.status = status; a.fill_status = fill;
-  return lattice::launch_clips<1>(           // one group: the clips in their order
-      a, n_clips,
-      [&](int b, long off, DecodeClip& c, int&) {
-        c = DecodeClip{(long)frame_off_host[b], off, n_frames_host[b], b};
-        return fill ? 0 : clip_words(c.T, S);
-      },
-      [&](int, const DecodeLaunch& a) {
-        if (fill) {
-          hipLaunchKernelGGL(decode_fill_kernel, dim3(a.n), dim3(64), 0, s, a);
-          return hipGetLastError() == hipSuccess ? 0 : wfl_fail(-3, "wfl_decode: launch failed");
-        }
-        int max_t = 0;
-        for (int j = 0; j < a.n; ++j) max_t = std::max(max_t, a.clip[j].T);
-        if (max_t > 0) {
-          hipLaunchKernelGGL(decode_pre_kernel, dim3((max_t + 3) / 4, a.n), dim3(256), 0, s, a, S);
-          if (hipGetLastError() != hipSuccess) return wfl_fail(-3, "wfl_decode: launch failed");
-        }
-        return launch_chain(S, a, s);
-      });
+  a.logits = logits; a.ldl = ldl; a.C = C; a.o_id = o_id; a.pairs = pairs; a.n_pairs = n_pairs; a.threshold = threshold; a.status = status;
+  a.lambda = lambda; a.ids = ids; a.score = score;
+  const int S = bio::slots_of(n_pairs);
+  return bio::run<true>(fn, a, false, frame_off_host, n_frames_host, n_clips, workspace, workspace_bytes, stream, BpWords{S},
+                        [&](const DecodeLaunch& a, hipStream_t s) {
+                          bio::dispatch_slots(S, [&](auto c) {
+                            hipLaunchKernelGGL((decode_chain_kernel<decltype(c)::S, decltype(c)::D>), dim3(a.n), dim3(64), 0, s, a);
+                          });
+                          return 0;
+                        });
 }
 
 }  // extern "C"

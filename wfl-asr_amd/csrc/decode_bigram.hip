@@ -4,8 +4,9 @@
 //     B-q : z + max_s (end[s] + W[s][q])      O : z + max(d[O], max_{p != O} (end[p] + W[p][O]))      I-q : z + max(d[I-q], d[B-q])
 // so a frame is a max-plus product of the N x N table with end[]: decode_chain_kernel's one wave-wide maximum does not carry over.
 //
-// Two kernels.  bigram_pre_kernel: the frames' log-sum-exp and forced-to-O flags (bio_grammar.h's arithmetic, this file's workspace
-// layout).  bigram_chain_kernel, ONE WORKGROUP of 256 threads per clip:
+// Two kernels.  bio::pre_kernel: the frames' log-sum-exp and forced-to-O flags (csrc/bio_grammar.h, as everything this entry shares with
+// wfl_decode and wfl_decode_posterior; this file holds the chain kernel, its backpointer words and LDS layout, and the entry's own
+// checks).  bigram_chain_kernel, ONE WORKGROUP of 256 threads per clip:
 //   - the table lives in LDS for the whole clip (N N floats, 144 KiB at the cap), row = previous symbol, so the 64 lanes of a wave read
 //     consecutive words of one row: no bank conflict; W[O][O] is stored as -inf (O after O costs nothing and is decided apart)
 //   - wave w takes the predecessors [w NS, (w + 1) NS), NS = ceil(N / 4); lane l the targets l, l + 64, l + 128.  Ascending s and a strict
@@ -21,9 +22,7 @@
 
 namespace {
 
-using lattice::CLIPS_PER_LAUNCH;
 using lattice::MAX_CLASSES;
-using lattice::round64;
 
 using bio::NO_CLASS;
 using BigramClip = bio::Clip;
@@ -36,27 +35,18 @@ constexpr int D = 8;                         // frames per emission group
 constexpr int BIGRAM_W = 32;                 // backtrace window, frames
 static_assert(MAX_SYMBOLS <= NT && MAX_SYMBOLS <= 256, "one owner thread per symbol, 8-bit predecessors");
 
-struct BigramLaunch {
-  const float* logits;
-  long ldl;
-  int C, o_id;
-  const int* pairs;    // [n_pairs][2]: B class, I class or -1
-  int n_pairs;
+struct BigramLaunch : bio::Launch {
   const float* trans;  // [N][N], rows the previous symbol
-  float threshold;
-  unsigned* ws;
   int* ids;
   float* score;
-  int* status;
-  int n, fill_status;
-  BigramClip clip[CLIPS_PER_LAUNCH];
 };
 
-// workspace of a clip, in words: [backpointers T ceil(N / 2)] [lse T] [forced T], each rounded up to 64 words
+// head of a clip's workspace, in words: the backpointers, 16 bits per symbol and frame
 __host__ __device__ inline int bp_words(int N) { return (N + 1) / 2; }
-__host__ __device__ inline long off_lse(int T, int N) { return round64((long)T * bp_words(N)); }
-__host__ __device__ inline long off_forced(int T, int N) { return off_lse(T, N) + round64(T); }
-inline long clip_words(int T, int N) { return T > 0 ? off_forced(T, N) + round64(T) : 0; }
+struct BpWords {
+  int N;
+  __host__ __device__ long operator()(int T) const { return lattice::round64((long)T * bp_words(N)); }
+};
 
 // dynamic LDS, in bytes: [table N N floats, later the backtrace window] [partial values NW x MAX_SYMBOLS] [partial predecessors, same]
 // [end MAX_SYMBOLS] [B class, I class per symbol]
@@ -68,30 +58,6 @@ constexpr int FIXED_BYTES = (2 * NW + 3) * MAX_SYMBOLS * 4;
 inline int lds_bytes(int N) { return table_bytes(N) + FIXED_BYTES; }
 constexpr int MAX_LDS = (MAX_SYMBOLS * MAX_SYMBOLS + (2 * NW + 3) * MAX_SYMBOLS) * 4;
 static_assert(MAX_LDS + (MAX_CLASSES + MAX_CLASSES / 32 + BIGRAM_W + 16) * 4 <= 160 * 1024, "LDS of one CU");
-
-// ---- per frame: log-sum-exp and the forced-to-O flag.  grid (ceil(max T / 4), clips), 4 waves per block, one wave per frame.
-__global__ __launch_bounds__(256) void bigram_pre_kernel(BigramLaunch a, int N) {
-  const BigramClip cl = a.clip[blockIdx.y];
-  const int lane = threadIdx.x & 63;
-  const int t = blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (t >= cl.T) return;
-  const float* z = a.logits + (cl.frame_off + t) * a.ldl;
-  float m, se;
-  bio::frame_stats(z, a.C, lane, m, se);
-  if (lane == 0) {
-    unsigned* w = a.ws + cl.ws_off;
-    ((float*)(w + off_lse(cl.T, N)))[t] = m + logf(se);
-    w[off_forced(cl.T, N) + t] = bio::forced_to_o(se, a.threshold);
-  }
-}
-
-// ---- clips that cannot be decoded (over a cap, more pairs than classes): O everywhere, score 0, the status
-__global__ __launch_bounds__(64) void bigram_fill_kernel(BigramLaunch a) {
-  const BigramClip cl = a.clip[blockIdx.x];
-  int* ids = a.ids + cl.frame_off;
-  for (int t = threadIdx.x; t < cl.T; t += 64) ids[t] = a.o_id;
-  if (threadIdx.x == 0) { a.score[cl.clip] = 0.f; a.status[cl.clip] = a.fill_status; }
-}
 
 __global__ __launch_bounds__(NT) void bigram_chain_kernel(BigramLaunch a) {
   extern __shared__ __align__(16) unsigned char lds[];
@@ -114,14 +80,9 @@ __global__ __launch_bounds__(NT) void bigram_chain_kernel(BigramLaunch a) {
   int* symB = (int*)(endv + MAX_SYMBOLS);
   int* symI = symB + MAX_SYMBOLS;
 
-  // ---- the class table: thread p owns phoneme p here (bio::class_table with one slot per lane); a bad one is status 4
+  // ---- the class table: thread p owns phoneme p here (one slot per thread); a bad one is status 4
   int cB[1], cI[1];
-  const bool bad_wave = bio::class_table<1>(a.pairs, a.n_pairs, C, o_id, used, info, cB, cI);
-  if (__syncthreads_or(bad_wave ? 1 : 0)) {
-    for (int t = tid; t < T; t += NT) ids[t] = o_id;
-    if (tid == 0) { a.score[cl.clip] = 0.f; a.status[cl.clip] = 4; }
-    return;
-  }
+  if (bio::class_table<1, NT>(a.pairs, a.n_pairs, C, o_id, used, info, cB, cI)) { bio::refuse<NT>(a, cl, 4); return; }
   if (T == 0) {
     if (tid == 0) { a.score[cl.clip] = 0.f; a.status[cl.clip] = 0; }
     return;
@@ -141,8 +102,8 @@ __global__ __launch_bounds__(NT) void bigram_chain_kernel(BigramLaunch a) {
 
   unsigned* bpw = a.ws + cl.ws_off;
   unsigned short* bp = (unsigned short*)bpw;
-  const float* lse = (const float*)(bpw + off_lse(T, N));
-  const unsigned* forced = bpw + off_forced(T, N);
+  const float* lse = (const float*)(bpw + bio::tail_stat(BpWords{N}(T)));
+  const unsigned* forced = bpw + bio::tail_forced(BpWords{N}(T), T);
   const float* Z = a.logits + cl.frame_off * a.ldl;
 
   float z0[D], z1[D];
@@ -302,72 +263,36 @@ __global__ __launch_bounds__(NT) void bigram_chain_kernel(BigramLaunch a) {
   }
 }
 
-int launch_chain(const BigramLaunch& a, int N, hipStream_t s) {
-  static WflOncePerDevice attr_once;
-  if (attr_once.need()) {
-    if (hipFuncSetAttribute((const void*)bigram_chain_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, MAX_LDS) != hipSuccess)
-      return wfl_fail(-2, "wfl_decode_bigram: cannot reserve the kernel's LDS");
-  }
-  hipLaunchKernelGGL(bigram_chain_kernel, dim3(a.n), dim3(NT), lds_bytes(N), s, a);
-  return hipGetLastError() == hipSuccess ? 0 : wfl_fail(-3, "wfl_decode_bigram: launch failed");
-}
-
 }  // namespace
 
 extern "C" {
 
 int64_t wfl_decode_bigram_workspace_bytes(const int32_t* n_frames_host, int32_t n_clips, int32_t n_pairs) {
-  if (n_clips < 0 || n_pairs < 0 || (n_clips > 0 && !n_frames_host)) return -1;
-  const bool over = n_pairs + 1 > MAX_SYMBOLS;
-  int64_t words = 0;
-  for (int b = 0; b < n_clips; ++b) {
-    if (n_frames_host[b] < 0) return -1;
-    if (!over) words += clip_words(n_frames_host[b], n_pairs + 1);
-  }
-  return words * 4;
+  return bio::workspace_bytes(n_frames_host, n_clips, n_pairs, n_pairs + 1 > MAX_SYMBOLS, BpWords{n_pairs + 1});
 }
 
 int32_t wfl_decode_bigram(const float* logits, int64_t ldl, int32_t C, int32_t o_id, const int64_t* frame_off_host,
                           const int32_t* n_frames_host, int32_t n_clips, const int32_t* pairs, int32_t n_pairs, const float* trans,
                           float threshold, void* workspace, int64_t workspace_bytes, int32_t* ids, float* score, int32_t* status,
                           void* stream) {
+  const char* fn = "wfl_decode_bigram";
   bool any_frame;
-  if (const int rc = bio::check_args("wfl_decode_bigram", C, o_id, ldl, frame_off_host, n_frames_host, n_clips, n_pairs, 0.f, threshold,
-                                     any_frame))
-    return rc;
+  if (const int rc = bio::check_args(fn, C, o_id, ldl, frame_off_host, n_frames_host, n_clips, n_pairs, 0.f, threshold, any_frame)) return rc;
   if (n_clips == 0) return 0;
-  if (!score || !status || (n_pairs > 0 && !pairs) || (any_frame && (!logits || !ids)))
-    return wfl_fail(-1, "wfl_decode_bigram: null device pointer");
-  // over the class cap or the symbol cap: status 2; more pairs than classes (then one is used twice or out of range): status 4
-  int fill = bio::refused_status(C, n_pairs);
-  if (!fill && n_pairs + 1 > MAX_SYMBOLS) fill = 2;
-  if (!fill && any_frame && !trans) return wfl_fail(-1, "wfl_decode_bigram: null device pointer");
+  if (!score || !status || (n_pairs > 0 && !pairs) || (any_frame && (!logits || !ids))) return lattice::fail(fn, -1, "null device pointer");
+  // over the symbol cap: status 2, as over the class cap; the table is read only when the clips are searched
   const int N = n_pairs + 1;
-  const int64_t need = fill ? 0 : wfl_decode_bigram_workspace_bytes(n_frames_host, n_clips, n_pairs);
-  if (const int rc = lattice::check_workspace("wfl_decode_bigram", need, workspace, workspace_bytes)) return rc;
-  hipStream_t s = (hipStream_t)stream;
+  const bool over = N > MAX_SYMBOLS;
+  if (any_frame && !trans && !bio::refused_status(C, n_pairs, over)) return lattice::fail(fn, -1, "null device pointer");
   BigramLaunch a{};
-  a.logits = logits; a.ldl = ldl; a.C = C; a.o_id = o_id; a.pairs = pairs; a.n_pairs = n_pairs; a.trans = trans;
-  a.threshold = threshold; a.ws = (unsigned*)workspace; a.ids = ids; a.score = score; a.status = status; a.fill_status = fill;
-  return lattice::launch_clips<1>(           // one group: the clips in their order
-      a, n_clips,
-      [&](int b, long off, BigramClip& c, int&) {
-        c = BigramClip{(long)frame_off_host[b], off, n_frames_host[b], b};
-        return fill ? 0 : clip_words(c.T, N);
-      },
-      [&](int, const BigramLaunch& a) {
-        if (fill) {
-          hipLaunchKernelGGL(bigram_fill_kernel, dim3(a.n), dim3(64), 0, s, a);
-          return hipGetLastError() == hipSuccess ? 0 : wfl_fail(-3, "wfl_decode_bigram: launch failed");
-        }
-        int max_t = 0;
-        for (int j = 0; j < a.n; ++j) max_t = std::max(max_t, a.clip[j].T);
-        if (max_t > 0) {
-          hipLaunchKernelGGL(bigram_pre_kernel, dim3((max_t + 3) / 4, a.n), dim3(256), 0, s, a, N);
-          if (hipGetLastError() != hipSuccess) return wfl_fail(-3, "wfl_decode_bigram: launch failed");
-        }
-        return launch_chain(a, N, s);
-      });
+  a.logits = logits; a.ldl = ldl; a.C = C; a.o_id = o_id; a.pairs = pairs; a.n_pairs = n_pairs; a.threshold = threshold; a.status = status;
+  a.trans = trans; a.ids = ids; a.score = score;
+  return bio::run<true>(fn, a, over, frame_off_host, n_frames_host, n_clips, workspace, workspace_bytes, stream, BpWords{N},
+                        [&](const BigramLaunch& a, hipStream_t s) {
+                          if (const int rc = lattice::reserve_lds<bigram_chain_kernel, MAX_LDS>(fn)) return rc;
+                          hipLaunchKernelGGL(bigram_chain_kernel, dim3(a.n), dim3(NT), lds_bytes(N), s, a);
+                          return 0;
+                        });
 }
 
 }  // extern "C"

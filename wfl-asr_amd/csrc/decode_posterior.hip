@@ -13,8 +13,8 @@
 // Outputs per frame, for the class ids[t] of the path wfl_decode returned: post = gamma(B-p) + gamma(I-p) of the path's phoneme (gamma(O)
 // on an O frame), cls_post = gamma(ids[t]).
 //
-// Execution shape of the search: decode_post_pre_kernel, one wave per frame, fully parallel (the row maximum and the forced flag, by
-// the search's own pre-pass arithmetic); decode_post_chain_kernel, ONE WAVE per clip, lane l owning the phonemes l, l + 64, ... (S slots,
+// Execution shape of the search: bio::pre_kernel (csrc/bio_grammar.h, the search's own pre-pass, here leaving the row maximum in place
+// of the log-sum-exp), one wave per frame, fully parallel; decode_post_chain_kernel, ONE WAVE per clip, lane l owning the phonemes l, l + 64, ... (S slots,
 // both states of each in registers), so the I-p update is lane-local and the only cross-lane work of a frame is ONE wave sum in each
 // direction (DPP inside a row of 16, the four row sums through v_readlane).  No LDS exchange, no barrier in the frame loops.
 //
@@ -32,37 +32,29 @@
 // (alpha(B-p), alpha(I-p), scale exponent) -- (alpha(O), 0, exponent) on an O frame -- three words per frame; the backward sweep reads them
 // a group ahead and the owning lane multiplies them with its beta (in double, with logZ's mantissa and the three exponents).
 // Before the sweeps the wave checks in parallel that ids is a path of the grammar (status 8) and leaves class -> (pair, kind) per frame.
-// Workspace per clip, in words: [alpha records 3 T] [pair | kind << 16 per frame T] [row maxima T] [forced flags T], each rounded up to 64.
+// Workspace per clip, in words: [alpha records 3 T] [pair | kind << 16 per frame T] [row maxima T] [forced flags T], each rounded up to 64;
+// the first two are this file's head, the last two the tail of csrc/bio_grammar.h.  That header holds everything this entry shares with
+// wfl_decode and wfl_decode_bigram; this file holds the chain kernel and the entry's own pointer checks.
 #include "bio_grammar.h"
 #include "wfl_asr.h"
 
 namespace {
 
 using bio::NO_CLASS;
-using bio::slots_of;
-using lattice::CLIPS_PER_LAUNCH;
 using lattice::MAX_CLASSES;
 using lattice::round64;
 
-struct PostLaunch {
-  const float* logits;
-  long ldl;
-  int C, o_id;
-  const int* pairs;  // [n_pairs][2]: B class, I class or -1
-  int n_pairs;
-  float lambda, threshold;
+struct PostLaunch : bio::Launch {
+  float lambda;
   const int* ids;
-  unsigned* ws;
   float *logz, *post, *cls_post;
-  int* status;
-  int n, fill_status;
-  bio::Clip clip[CLIPS_PER_LAUNCH];
 };
 
+// head of a clip's workspace, in words: the alpha records, then the path's (pair, kind) per frame
 __host__ __device__ inline long off_sel(int T) { return round64(3L * T); }
-__host__ __device__ inline long off_max(int T) { return off_sel(T) + round64(T); }
-__host__ __device__ inline long off_forced(int T) { return off_max(T) + round64(T); }
-inline long clip_words(int T) { return T > 0 ? off_forced(T) + round64(T) : 0; }
+struct HeadWords {
+  __host__ __device__ long operator()(int T) const { return off_sel(T) + round64(T); }
+};
 
 constexpr float TINY = 0x1p-60f;   // floor of an O emission and of exp(-lambda)
 
@@ -91,28 +83,6 @@ __device__ __forceinline__ float unscale(float x, int& ex) {
   return __int_as_float((254 - be) << 23);
 }
 
-// ---- per frame: the row maximum and the forced-to-O flag.  grid (ceil(max T / 4), clips), 4 waves per block, one wave per frame.
-__global__ __launch_bounds__(256) void decode_post_pre_kernel(PostLaunch a) {
-  const bio::Clip cl = a.clip[blockIdx.y];
-  const int lane = threadIdx.x & 63;
-  const int t = blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (t >= cl.T) return;
-  float m, se;
-  bio::frame_stats(a.logits + (cl.frame_off + t) * a.ldl, a.C, lane, m, se);
-  if (lane == 0) {
-    unsigned* w = a.ws + cl.ws_off;
-    ((float*)(w + off_max(cl.T)))[t] = m;
-    w[off_forced(cl.T) + t] = bio::forced_to_o(se, a.threshold);
-  }
-}
-
-// ---- clips that cannot be scored (C over the cap, more pairs than classes): zeros, the status
-__global__ __launch_bounds__(64) void decode_post_fill_kernel(PostLaunch a) {
-  const bio::Clip cl = a.clip[blockIdx.x];
-  for (int t = threadIdx.x; t < cl.T; t += 64) a.post[cl.frame_off + t] = a.cls_post[cl.frame_off + t] = 0.f;
-  if (threadIdx.x == 0) { a.logz[cl.clip] = 0.f; a.status[cl.clip] = a.fill_status; }
-}
-
 template <int S, int D>
 __global__ __launch_bounds__(64) void decode_post_chain_kernel(PostLaunch a) {
   __shared__ unsigned used[MAX_CLASSES / 32];
@@ -124,13 +94,9 @@ __global__ __launch_bounds__(64) void decode_post_chain_kernel(PostLaunch a) {
   const int* ids = a.ids + cl.frame_off;
   float* post = a.post + cl.frame_off;
   float* cls_post = a.cls_post + cl.frame_off;
-  auto refuse = [&](int st) {
-    for (int t = lane; t < T; t += 64) post[t] = cls_post[t] = 0.f;
-    if (lane == 0) { a.logz[cl.clip] = 0.f; a.status[cl.clip] = st; }
-  };
 
   int clsB[S], clsI[S];
-  if (bio::class_table<S>(a.pairs, a.n_pairs, C, o_id, used, info, clsB, clsI)) { refuse(4); return; }
+  if (bio::class_table<S, 64>(a.pairs, a.n_pairs, C, o_id, used, info, clsB, clsI)) { bio::refuse<64>(a, cl, 4); return; }
   if (T == 0) {
     if (lane == 0) { a.logz[cl.clip] = 0.f; a.status[cl.clip] = 0; }
     return;
@@ -139,8 +105,8 @@ __global__ __launch_bounds__(64) void decode_post_chain_kernel(PostLaunch a) {
   unsigned* w0 = a.ws + cl.ws_off;
   float* rec = (float*)w0;                                     // [T][3]: alpha(B-p) or alpha(O), alpha(I-p) or 0, scale exponent
   int* sel = (int*)(w0 + off_sel(T));
-  const float* rowmax = (const float*)(w0 + off_max(T));
-  const unsigned* forced = w0 + off_forced(T);
+  const float* rowmax = (const float*)(w0 + bio::tail_stat(HeadWords{}(T)));
+  const unsigned* forced = w0 + bio::tail_forced(HeadWords{}(T), T);
   const float* Z = a.logits + cl.frame_off * a.ldl;
 
   // ---- is ids a path of this grammar?  Every frame on its own: a class of the table, I-p only after B-p / I-p, O on a forced frame.
@@ -157,7 +123,7 @@ __global__ __launch_bounds__(64) void decode_post_chain_kernel(PostLaunch a) {
     if (in > 0 && forced[t]) bad = true;                       // (in == 0 is O)
     sel[t] = in < 0 ? 0 : in;
   }
-  if (__any(bad)) { refuse(8); return; }
+  if (__any(bad)) { bio::refuse<64>(a, cl, 8); return; }
   __threadfence_block();
   __syncthreads();                                             // sel[] is read back by every lane below
 
@@ -383,29 +349,12 @@ __global__ __launch_bounds__(64) void decode_post_chain_kernel(PostLaunch a) {
   }
 }
 
-int launch_chain(int S, const PostLaunch& a, hipStream_t s) {
-  switch (S) {
-    case 2: hipLaunchKernelGGL((decode_post_chain_kernel<2, 16>), dim3(a.n), dim3(64), 0, s, a); break;
-    case 4: hipLaunchKernelGGL((decode_post_chain_kernel<4, 8>), dim3(a.n), dim3(64), 0, s, a); break;
-    case 8: hipLaunchKernelGGL((decode_post_chain_kernel<8, 4>), dim3(a.n), dim3(64), 0, s, a); break;
-    default: hipLaunchKernelGGL((decode_post_chain_kernel<16, 2>), dim3(a.n), dim3(64), 0, s, a); break;
-  }
-  return hipGetLastError() == hipSuccess ? 0 : wfl_fail(-3, "wfl_decode_posterior: launch failed");
-}
-
 }  // namespace
 
 extern "C" {
 
 int64_t wfl_decode_posterior_workspace_bytes(const int32_t* n_frames_host, int32_t n_clips, int32_t n_pairs) {
-  if (n_clips < 0 || n_pairs < 0 || (n_clips > 0 && !n_frames_host)) return -1;
-  const int S = slots_of(n_pairs);
-  int64_t words = 0;
-  for (int b = 0; b < n_clips; ++b) {
-    if (n_frames_host[b] < 0) return -1;
-    if (S) words += clip_words(n_frames_host[b]);
-  }
-  return words * 4;
+  return bio::workspace_bytes(n_frames_host, n_clips, n_pairs, bio::slots_of(n_pairs) == 0, HeadWords{});
 }
 
 int32_t wfl_decode_posterior(const float* logits, int64_t ldl, int32_t C, int32_t o_id, const int64_t* frame_off_host,
@@ -418,34 +367,17 @@ int32_t wfl_decode_posterior(const float* logits, int64_t ldl, int32_t C, int32_
   if (n_clips == 0) return 0;
   if (!logz || !status || (n_pairs > 0 && !pairs) || (any_frame && (!logits || !ids || !post || !cls_post)))
     return lattice::fail(fn, -1, "null device pointer");
-  const int fill = bio::refused_status(C, n_pairs);
-  const int S = fill ? 0 : slots_of(n_pairs);
-  const int64_t need = fill ? 0 : wfl_decode_posterior_workspace_bytes(n_frames_host, n_clips, n_pairs);
-  if (const int rc = lattice::check_workspace(fn, need, workspace, workspace_bytes)) return rc;
-  hipStream_t s = (hipStream_t)stream;
   PostLaunch a{};
-  a.logits = logits; a.ldl = ldl; a.C = C; a.o_id = o_id; a.pairs = pairs; a.n_pairs = n_pairs; a.lambda = lambda;
-  a.threshold = threshold; a.ids = ids; a.ws = (unsigned*)workspace; a.logz = logz; a.post = post; a.cls_post = cls_post;
-  a.status = status; a.fill_status = fill;
-  return lattice::launch_clips<1>(           // one group: the clips in their order
-      a, n_clips,
-      [&](int b, long off, bio::Clip& c, int&) {
-        c = bio::Clip{(long)frame_off_host[b], off, n_frames_host[b], b};
-        return fill ? 0 : clip_words(c.T);
-      },
-      [&](int, const PostLaunch& a) {
-        if (fill) {
-          hipLaunchKernelGGL(decode_post_fill_kernel, dim3(a.n), dim3(64), 0, s, a);
-          return hipGetLastError() == hipSuccess ? 0 : lattice::fail(fn, -3, "launch failed");
-        }
-        int max_t = 0;
-        for (int j = 0; j < a.n; ++j) max_t = std::max(max_t, a.clip[j].T);
-        if (max_t > 0) {
-          hipLaunchKernelGGL(decode_post_pre_kernel, dim3((max_t + 3) / 4, a.n), dim3(256), 0, s, a);
-          if (hipGetLastError() != hipSuccess) return lattice::fail(fn, -3, "launch failed");
-        }
-        return launch_chain(S, a, s);
-      });
+  a.logits = logits; a.ldl = ldl; a.C = C; a.o_id = o_id; a.pairs = pairs; a.n_pairs = n_pairs; a.threshold = threshold; a.status = status;
+  a.lambda = lambda; a.ids = ids; a.logz = logz; a.post = post; a.cls_post = cls_post;
+  const int S = bio::slots_of(n_pairs);
+  return bio::run<false>(fn, a, false, frame_off_host, n_frames_host, n_clips, workspace, workspace_bytes, stream, HeadWords{},
+                         [&](const PostLaunch& a, hipStream_t s) {
+                           bio::dispatch_slots(S, [&](auto c) {
+                             hipLaunchKernelGGL((decode_post_chain_kernel<decltype(c)::S, decltype(c)::D>), dim3(a.n), dim3(64), 0, s, a);
+                           });
+                           return 0;
+                         });
 }
 
 }  // extern "C"

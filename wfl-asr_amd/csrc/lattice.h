@@ -8,8 +8,9 @@
 //   host    the argument checks the ABI entries share, "group the clips by configuration, hand out workspace offsets, launch at most
 //           64 clips at a time", and the launch that reserves a kernel's dynamic LDS once per device
 //
-// csrc/decode.hip is a different search (one wave per clip, the classes as states): it takes the constants, round64, wave_sum and
-// the host helpers, nothing of the lattice.
+// The BIO-grammar decodes (csrc/decode.hip, csrc/decode_bigram.hip, csrc/decode_posterior.hip) are a different search, the classes as
+// states; what they share lives in csrc/bio_grammar.h.  From here that header takes the class cap, the clips-per-launch constant, round64,
+// wave_max / wave_sum and the host's fail, check_workspace, launch_clips and reserve_lds, nothing of the lattice.
 #pragma once
 #include "common.h"
 
@@ -296,15 +297,22 @@ int launch_clips(Launch& a, int n_clips, Make make, Fire fire) {
   return 0;
 }
 
-// one workgroup of NT threads per clip of `a`, LDS bytes of dynamic LDS (reserved once per device and kernel)
-template <auto KERNEL, int NT, int LDS, class Launch>
-int launch_cfg(const char* fn, const Launch& a, hipStream_t s) {
+// LDS bytes of dynamic LDS for KERNEL, reserved once per device
+template <auto KERNEL, int LDS>
+int reserve_lds(const char* fn) {
   static_assert(LDS <= 160 * 1024, "LDS");
   static WflOncePerDevice attr_once;
   if (attr_once.need()) {
     if (hipFuncSetAttribute((const void*)KERNEL, hipFuncAttributeMaxDynamicSharedMemorySize, LDS) != hipSuccess)
       return fail(fn, -2, "cannot reserve the kernel's LDS");
   }
+  return 0;
+}
+
+// one workgroup of NT threads per clip of `a`, LDS bytes of dynamic LDS
+template <auto KERNEL, int NT, int LDS, class Launch>
+int launch_cfg(const char* fn, const Launch& a, hipStream_t s) {
+  if (const int rc = reserve_lds<KERNEL, LDS>(fn)) return rc;
   hipLaunchKernelGGL(KERNEL, dim3(a.n), dim3(NT), LDS, s, a);
   return hipGetLastError() == hipSuccess ? 0 : fail(fn, -3, "launch failed");
 }

@@ -66,17 +66,28 @@ def check_options(decode, switch_penalty):
             raise ValueError(f"switch_penalty must be a number >= 0 (nats), got {switch_penalty!r}")
 
 
-def workspace_bytes(n_frames, n_pairs) -> int:
-    lib = _lib.load()
+def _workspace_bytes(symbol, n_frames, n_pairs) -> int:
     T = np.ascontiguousarray(n_frames, np.int32)
-    n = int(lib.wfl_decode_workspace_bytes(_hp(T), T.size, int(n_pairs)))
+    n = int(getattr(_lib.load(), symbol)(_hp(T), T.size, int(n_pairs)))
     if n < 0:
-        raise _lib.WflError("wfl_decode_workspace_bytes: negative frame or pair count")
+        raise _lib.WflError(f"{symbol}: negative frame or pair count")
     return n
 
 
+def workspace_bytes(n_frames, n_pairs) -> int:
+    return _workspace_bytes("wfl_decode_workspace_bytes", n_frames, n_pairs)
+
+
+def bigram_workspace_bytes(n_frames, n_pairs) -> int:
+    return _workspace_bytes("wfl_decode_bigram_workspace_bytes", n_frames, n_pairs)
+
+
+def posterior_workspace_bytes(n_frames, n_pairs) -> int:
+    return _workspace_bytes("wfl_decode_posterior_workspace_bytes", n_frames, n_pairs)
+
+
 def _check_clips(logits, n_frames, table, switch_penalty, threshold, frame_offsets):
-    """The validation bio_viterbi and decode_posteriors share -> (o_id, pairs, nb, T, F0)."""
+    """The validation the three entries share -> (o_id, pairs, nb, T, F0), _call's clip arguments."""
     if not logits.is_cuda or logits.dim() != 2 or logits.dtype != torch.float32 or (logits.numel() and logits.stride(1) != 1):
         raise ValueError("logits must be a [rows, C] float32 CUDA tensor with contiguous rows")
     o_id, pairs = table
@@ -99,6 +110,33 @@ def _check_clips(logits, n_frames, table, switch_penalty, threshold, frame_offse
     return int(o_id), pairs, nb, T, F0
 
 
+def _call(entry, logits, clips, middle, outputs, stream):
+    """What the three entries share after _check_clips (`clips`: its result): `entry`'s workspace, the class pairs on the device, the
+    call on `stream` (default: the current one) and its check.  middle: the arguments between n_pairs and the workspace, outputs: the
+    tensors after it; a float goes as it is, a tensor as its pointer, a numpy array is uploaded for the call."""
+    o_id, pairs, nb, T, F0 = clips
+    lib = _lib.load()
+    dev = logits.device
+    ws_n = _workspace_bytes(entry + "_workspace_bytes", T, len(pairs)) if logits.shape[1] <= MAX_CLASSES else 0
+    ws = torch.empty(max(ws_n, 1), dtype=torch.uint8, device=dev)
+    d_pairs = torch.from_numpy(pairs if len(pairs) else np.full((1, 2), -1, np.int32)).to(dev)
+    temporaries = [ws, d_pairs]
+    args = []
+    for m in middle:
+        if isinstance(m, np.ndarray):
+            m = torch.from_numpy(m).to(dev)
+            temporaries.append(m)
+        args.append(_ptr(m) if isinstance(m, torch.Tensor) else m)
+    with torch.cuda.device(dev):
+        st = stream if stream is not None else torch.cuda.current_stream(dev)
+        ldl = logits.stride(0) if logits.numel() else logits.shape[1]      # (an empty tensor's strides say nothing)
+        rc = getattr(lib, entry)(_ptr(logits), ldl, logits.shape[1], o_id, _hp(F0), _hp(T), nb, _ptr(d_pairs), len(pairs), *args,
+                                 _ptr(ws), ws_n, *(_ptr(t) for t in outputs), C.c_void_p(st.cuda_stream))
+        _lib.check(rc, entry)
+        for t in temporaries:
+            t.record_stream(st)
+
+
 def bio_viterbi(logits, n_frames, table, switch_penalty, threshold, frame_offsets=None, stream=None):
     """BIO-grammar Viterbi decode of a ragged batch of clips on the GPU.
 
@@ -111,35 +149,13 @@ def bio_viterbi(logits, n_frames, table, switch_penalty, threshold, frame_offset
     frame_offsets   first row of each clip (default: the clips back to back)
     -> (ids [rows] int32, score [clips] float32, status [clips] int32), CUDA tensors on `stream`'s device.  A clip with status != 0
     (STATUS_OVER_CAP: C > 1024; STATUS_BAD_CLASS: a class of the table out of range or used twice) is O everywhere, score 0."""
-    o_id, pairs, nb, T, F0 = _check_clips(logits, n_frames, table, switch_penalty, threshold, frame_offsets)
-    lib = _lib.load()
-    dev = logits.device
-    rows = logits.shape[0]
-    ws_n = workspace_bytes(T, len(pairs)) if logits.shape[1] <= MAX_CLASSES else 0
-    ws = torch.empty(max(ws_n, 1), dtype=torch.uint8, device=dev)
-    d_pairs = torch.from_numpy(pairs if len(pairs) else np.full((1, 2), -1, np.int32)).to(dev)
-    ids = torch.empty(rows, dtype=torch.int32, device=dev)
-    score = torch.empty(max(nb, 1), dtype=torch.float32, device=dev)
-    status = torch.empty(max(nb, 1), dtype=torch.int32, device=dev)
-    with torch.cuda.device(dev):
-        st = stream if stream is not None else torch.cuda.current_stream(dev)
-        ldl = logits.stride(0) if logits.numel() else logits.shape[1]      # (an empty tensor's strides say nothing)
-        rc = lib.wfl_decode(_ptr(logits), ldl, logits.shape[1], int(o_id), _hp(F0), _hp(T), nb, _ptr(d_pairs), len(pairs),
-                            float(switch_penalty), float(threshold), _ptr(ws), ws_n, _ptr(ids), _ptr(score), _ptr(status),
-                            C.c_void_p(st.cuda_stream))
-        _lib.check(rc, "wfl_decode")
-        for t in (d_pairs, ws):
-            t.record_stream(st)
+    clips = _check_clips(logits, n_frames, table, switch_penalty, threshold, frame_offsets)
+    nb = clips[2]
+    ids = torch.empty(logits.shape[0], dtype=torch.int32, device=logits.device)
+    score = torch.empty(max(nb, 1), dtype=torch.float32, device=logits.device)
+    status = torch.empty(max(nb, 1), dtype=torch.int32, device=logits.device)
+    _call("wfl_decode", logits, clips, (float(switch_penalty), float(threshold)), (ids, score, status), stream)
     return ids, score[:nb], status[:nb]
-
-
-def bigram_workspace_bytes(n_frames, n_pairs) -> int:
-    lib = _lib.load()
-    T = np.ascontiguousarray(n_frames, np.int32)
-    n = int(lib.wfl_decode_bigram_workspace_bytes(_hp(T), T.size, int(n_pairs)))
-    if n < 0:
-        raise _lib.WflError("wfl_decode_bigram_workspace_bytes: negative frame or pair count")
-    return n
 
 
 def check_transitions(trans, n_pairs) -> np.ndarray:
@@ -173,37 +189,14 @@ def bio_viterbi_bigram(logits, n_frames, table, trans, threshold, frame_offsets=
     trans  float32 [n + 1, n + 1] over O (symbol 0) and the n phonemes of `table` in its order (check_transitions;
            phonotactics.transition_table builds it from a phoneme_bigram.json); -inf forbids a succession.
     A label set with more than 191 phonemes is over the kernel's cap (MAX_BIGRAM_SYMBOLS): STATUS_OVER_CAP, O everywhere, score 0."""
-    o_id, pairs, nb, T, F0 = _check_clips(logits, n_frames, table, 0.0, threshold, frame_offsets)
-    w = check_transitions(trans, len(pairs))
-    lib = _lib.load()
-    dev = logits.device
-    rows = logits.shape[0]
-    ws_n = bigram_workspace_bytes(T, len(pairs)) if logits.shape[1] <= MAX_CLASSES else 0
-    ws = torch.empty(max(ws_n, 1), dtype=torch.uint8, device=dev)
-    d_pairs = torch.from_numpy(pairs if len(pairs) else np.full((1, 2), -1, np.int32)).to(dev)
-    d_trans = torch.from_numpy(w).to(dev)
-    ids = torch.empty(rows, dtype=torch.int32, device=dev)
-    score = torch.empty(max(nb, 1), dtype=torch.float32, device=dev)
-    status = torch.empty(max(nb, 1), dtype=torch.int32, device=dev)
-    with torch.cuda.device(dev):
-        st = stream if stream is not None else torch.cuda.current_stream(dev)
-        ldl = logits.stride(0) if logits.numel() else logits.shape[1]      # (an empty tensor's strides say nothing)
-        rc = lib.wfl_decode_bigram(_ptr(logits), ldl, logits.shape[1], int(o_id), _hp(F0), _hp(T), nb, _ptr(d_pairs), len(pairs),
-                                   _ptr(d_trans), float(threshold), _ptr(ws), ws_n, _ptr(ids), _ptr(score), _ptr(status),
-                                   C.c_void_p(st.cuda_stream))
-        _lib.check(rc, "wfl_decode_bigram")
-        for t in (d_pairs, d_trans, ws):
-            t.record_stream(st)
+    clips = _check_clips(logits, n_frames, table, 0.0, threshold, frame_offsets)
+    w = check_transitions(trans, len(clips[1]))
+    nb = clips[2]
+    ids = torch.empty(logits.shape[0], dtype=torch.int32, device=logits.device)
+    score = torch.empty(max(nb, 1), dtype=torch.float32, device=logits.device)
+    status = torch.empty(max(nb, 1), dtype=torch.int32, device=logits.device)
+    _call("wfl_decode_bigram", logits, clips, (w, float(threshold)), (ids, score, status), stream)
     return ids, score[:nb], status[:nb]
-
-
-def posterior_workspace_bytes(n_frames, n_pairs) -> int:
-    lib = _lib.load()
-    T = np.ascontiguousarray(n_frames, np.int32)
-    n = int(lib.wfl_decode_posterior_workspace_bytes(_hp(T), T.size, int(n_pairs)))
-    if n < 0:
-        raise _lib.WflError("wfl_decode_posterior_workspace_bytes: negative frame or pair count")
-    return n
 
 
 def decode_posteriors(logits, n_frames, table, switch_penalty, threshold, ids, frame_offsets=None, stream=None):
@@ -215,28 +208,17 @@ def decode_posteriors(logits, n_frames, table, switch_penalty, threshold, ids, f
     to the phoneme the path gives it (B-p or I-p; to O on an O frame), in [0, 1]; cls_post: the posterior of the exact class, so on a
     run's first frame that the run opens exactly there; cls_post <= post.  Rows outside the clips are not written.  A clip with
     status != 0 gets zeros (STATUS_NOT_A_PATH: `ids` is not a legal path of these clips)."""
-    o_id, pairs, nb, T, F0 = _check_clips(logits, n_frames, table, switch_penalty, threshold, frame_offsets)
+    clips = _check_clips(logits, n_frames, table, switch_penalty, threshold, frame_offsets)
     dev = logits.device
     if not isinstance(ids, torch.Tensor) or not ids.is_cuda or ids.device != dev or ids.dtype != torch.int32 or ids.dim() != 1 \
             or (ids.numel() and ids.stride(0) != 1) or ids.shape[0] != logits.shape[0]:
         raise ValueError("ids must be bio_viterbi's [rows] int32 CUDA tensor for these logits")
-    lib = _lib.load()
-    rows = logits.shape[0]
-    ws_n = posterior_workspace_bytes(T, len(pairs)) if logits.shape[1] <= MAX_CLASSES else 0
-    ws = torch.empty(max(ws_n, 1), dtype=torch.uint8, device=dev)
-    d_pairs = torch.from_numpy(pairs if len(pairs) else np.full((1, 2), -1, np.int32)).to(dev)
+    nb, rows = clips[2], logits.shape[0]
     per_frame = torch.empty((2, max(rows, 1)), dtype=torch.float32, device=dev)
     logz = torch.empty(max(nb, 1), dtype=torch.float32, device=dev)
     status = torch.empty(max(nb, 1), dtype=torch.int32, device=dev)
-    with torch.cuda.device(dev):
-        st = stream if stream is not None else torch.cuda.current_stream(dev)
-        ldl = logits.stride(0) if logits.numel() else logits.shape[1]      # (an empty tensor's strides say nothing)
-        rc = lib.wfl_decode_posterior(_ptr(logits), ldl, logits.shape[1], o_id, _hp(F0), _hp(T), nb, _ptr(d_pairs), len(pairs),
-                                      float(switch_penalty), float(threshold), _ptr(ids), _ptr(ws), ws_n, _ptr(logz),
-                                      _ptr(per_frame[0]), _ptr(per_frame[1]), _ptr(status), C.c_void_p(st.cuda_stream))
-        _lib.check(rc, "wfl_decode_posterior")
-        for t in (d_pairs, ws):
-            t.record_stream(st)
+    _call("wfl_decode_posterior", logits, clips, (float(switch_penalty), float(threshold), ids), (logz, per_frame[0], per_frame[1], status),
+          stream)
     return logz[:nb], per_frame[0, :rows], per_frame[1, :rows], status[:nb]
 
 
