@@ -444,6 +444,38 @@ int32_t wfl_decode_bigram(const float* logits, int64_t ldl, int32_t C, int32_t o
                           float threshold, void* workspace, int64_t workspace_bytes, int32_t* ids, float* score, int32_t* status,
                           void* stream);
 
+/* ---- Posteriors of a phone-bigram decode by forward-backward on the GPU (`postprocess.bigram_scores`; wfl-asr_amd/decode.py).  The
+ * sum-product counterpart of wfl_decode_bigram, as wfl_decode_posterior is wfl_decode's.  Clips, logits, pairs, o_id, threshold, trans,
+ * the symbols (0 is O, 1 + p is phoneme p; N = n_pairs + 1), the states, the legality rule, the forced-to-O rule and the virtual O frame
+ * are wfl_decode_bigram's; ids, logz, post, cls_post and what they mean are wfl_decode_posterior's.  The weight of a legal path is
+ *     exp(sum_t z[t][c_t] + sum over opened runs trans[previous symbol][opened symbol]),
+ * the runs counted as wfl_decode_bigram counts them; any state may end the clip.  With W = exp(trans) (-inf -> 0), e a frame's emissions,
+ * end[O] = alpha(O), end[p] = alpha(B-p) + alpha(I-p) of the previous frame, and primes for the next frame:
+ *     forward    B-q' = e(B-q) sum_s end[s] W[s][q]     O' = e(O) (alpha(O) + sum_{p != O} end[p] W[p][O])     I-q' = e(I-q) (alpha(B-q) + alpha(I-q))
+ *     backward   u[O] = e'(O) beta'(O),  u[q] = e'(B-q) beta'(B-q);     beta(O) = u[O] + sum_{q >= 1} W[O][q] u[q];
+ *                beta(B-p) = beta(I-p) = sum_{q >= 0} W[p][q] u[q] + e'(I-p) beta'(I-p);     beta at T - 1 = 1.
+ * With trans identically -lambda every output equals wfl_decode_posterior's at that lambda.
+ * status[b]: 0 ok; 2 C above 1024 or N above WFL_DECODE_BIGRAM_MAX_SYMBOLS; 4 a bad class table, as wfl_decode; 8 ids is not a path of
+ * this grammar: a class that is never chosen, an I-p that does not follow B-p / I-p, a non-O class on a forced frame, or a run opened
+ * through a succession whose trans entry is -inf (wfl_decode_bigram never returns such a path).  A clip with status != 0 gets logz = 0
+ * and post = cls_post = 0; T = 0 is ok, logz 0, and writes nothing per frame.
+ * One workgroup per clip: a clip scored alone equals the same clip inside any batch, bit for bit.  The table stays in one CU's LDS for
+ * the whole clip as linear weights.  Scaled linear-domain fp32 states (emissions exp(z - row maximum), every frame rescaled by a power
+ * of two taken from the previous frame's largest state, the exponents summed in an integer); a posterior that underflows fp32 is
+ * reported as 0.  Guards: an O emission counts as at least 2^-60 of its frame's largest (the row maximum over all C classes), as for
+ * wfl_decode_posterior, with the same consequence on a frame whose largest logit lies outside the grammar more than 41.6 nats above
+ * O; a finite trans entry is clamped to +-60 ln 2 (+-41.6 nats), -inf is exactly weight 0.  Together they keep every sum inside fp32's
+ * exponent range whatever the logits, the table and the clip's length.
+ * Arguments are checked on the host as wfl_decode_bigram checks its own (negative return); trans may be null only when no clip is scored.
+ * Workspace: wfl_decode_posterior's.  Per clip with T > 0, in 4-byte words: round_up_64(3 T) + 3 round_up_64(T)  (per frame alpha on
+ * the path's own phoneme and the scale exponent; the path's (pair, kind); the row maximum; the forced flag); 0 above the symbol cap.
+ * wfl_decode_bigram_posterior_workspace_bytes returns the sum in bytes (24 bytes per frame). */
+int64_t wfl_decode_bigram_posterior_workspace_bytes(const int32_t* n_frames_host, int32_t n_clips, int32_t n_pairs);
+int32_t wfl_decode_bigram_posterior(const float* logits, int64_t ldl, int32_t C, int32_t o_id, const int64_t* frame_off_host,
+                                    const int32_t* n_frames_host, int32_t n_clips, const int32_t* pairs, int32_t n_pairs,
+                                    const float* trans, float threshold, const int32_t* ids, void* workspace, int64_t workspace_bytes,
+                                    float* logz, float* post, float* cls_post, int32_t* status, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,7 +1,8 @@
-// The BIO grammar over the classes themselves, as the three decode entries see it -- wfl_decode (csrc/decode.hip, the max-product search
-// under a flat penalty), wfl_decode_bigram (csrc/decode_bigram.hip, the same search under a phone-bigram table) and wfl_decode_posterior
-// (csrc/decode_posterior.hip, the sum-product sweeps) -- defined ONCE: a change made here reaches all three, so the posterior always
-// scores the grammar and the forced frames the search ran on.  A .hip file keeps its chain kernel, the head of its workspace and its
+// The BIO grammar over the classes themselves, as the four decode entries see it -- wfl_decode (csrc/decode.hip, the max-product search
+// under a flat penalty), wfl_decode_bigram (csrc/decode_bigram.hip, the same search under a phone-bigram table), wfl_decode_posterior
+// (csrc/decode_posterior.hip, the sum-product sweeps under the flat penalty) and wfl_decode_bigram_posterior
+// (csrc/decode_bigram_posterior.hip, the sum-product sweeps under the table) -- defined ONCE: a change made here reaches all four, so a
+// posterior always scores the grammar and the forced frames its search ran on.  A .hip file keeps its chain kernel, the head of its workspace and its
 // own fields of the launch struct; everything else of an entry is here.
 //
 //   device  the per-clip record and the launch fields every kernel takes, a clip's workspace ([the kernel's head] [a statistic per

@@ -13,6 +13,8 @@ follows `B-p` or `I-p`, and every run that is opened costs `switch_penalty` nats
                       in place of the flat switch penalty (csrc/decode_bigram.hip, `wfl_decode_bigram`; phonotactics.py makes the table)
   decode_posteriors   forward-backward over the same grammar (csrc/decode_posterior.hip, `wfl_decode_posterior`): logZ, and per frame
                       the posterior of the phoneme and of the exact class the path chose (`postprocess.decode_scores`)
+  decode_posteriors_bigram  the same over the grammar of bio_viterbi_bigram, the table included (csrc/decode_bigram_posterior.hip,
+                      `wfl_decode_bigram_posterior`; `postprocess.bigram_scores`)
   path_segments_free  the path's ids of a file, chunk by chunk, -> segments; a run that crosses a chunk seam is one segment
   free_score          those outputs + bio_viterbi's score -> FreeScore / RunScore records, run j being segment j of the path
 """
@@ -33,7 +35,7 @@ DECODE_MODES = ("argmax", "viterbi")
 MAX_CLASSES = 1024         # wfl_decode's class cap (status 2 above it)
 MAX_BIGRAM_SYMBOLS = 192   # wfl_decode_bigram's symbol cap, O + 191 phonemes (WFL_DECODE_BIGRAM_MAX_SYMBOLS; status 2 above it)
 STATUS_OK, STATUS_OVER_CAP, STATUS_BAD_CLASS = 0, 2, 4
-STATUS_NOT_A_PATH = 8      # wfl_decode_posterior alone: `ids` is not a path of the grammar
+STATUS_NOT_A_PATH = 8      # the two posterior entries alone: `ids` is not a path of the grammar
 
 
 class ClassTable(NamedTuple):
@@ -84,6 +86,10 @@ def bigram_workspace_bytes(n_frames, n_pairs) -> int:
 
 def posterior_workspace_bytes(n_frames, n_pairs) -> int:
     return _workspace_bytes("wfl_decode_posterior_workspace_bytes", n_frames, n_pairs)
+
+
+def bigram_posterior_workspace_bytes(n_frames, n_pairs) -> int:
+    return _workspace_bytes("wfl_decode_bigram_posterior_workspace_bytes", n_frames, n_pairs)
 
 
 def _check_clips(logits, n_frames, table, switch_penalty, threshold, frame_offsets):
@@ -209,6 +215,11 @@ def decode_posteriors(logits, n_frames, table, switch_penalty, threshold, ids, f
     run's first frame that the run opens exactly there; cls_post <= post.  Rows outside the clips are not written.  A clip with
     status != 0 gets zeros (STATUS_NOT_A_PATH: `ids` is not a legal path of these clips)."""
     clips = _check_clips(logits, n_frames, table, switch_penalty, threshold, frame_offsets)
+    return _posteriors("wfl_decode_posterior", logits, clips, (float(switch_penalty), float(threshold)), ids, stream)
+
+
+def _posteriors(entry, logits, clips, middle, ids, stream):
+    """What the two posterior entries share after their own checks: the check of `ids`, the outputs and the call."""
     dev = logits.device
     if not isinstance(ids, torch.Tensor) or not ids.is_cuda or ids.device != dev or ids.dtype != torch.int32 or ids.dim() != 1 \
             or (ids.numel() and ids.stride(0) != 1) or ids.shape[0] != logits.shape[0]:
@@ -217,9 +228,21 @@ def decode_posteriors(logits, n_frames, table, switch_penalty, threshold, ids, f
     per_frame = torch.empty((2, max(rows, 1)), dtype=torch.float32, device=dev)
     logz = torch.empty(max(nb, 1), dtype=torch.float32, device=dev)
     status = torch.empty(max(nb, 1), dtype=torch.int32, device=dev)
-    _call("wfl_decode_posterior", logits, clips, (float(switch_penalty), float(threshold), ids), (logz, per_frame[0], per_frame[1], status),
-          stream)
+    _call(entry, logits, clips, (*middle, ids), (logz, per_frame[0], per_frame[1], status), stream)
     return logz[:nb], per_frame[0, :rows], per_frame[1, :rows], status[:nb]
+
+
+def decode_posteriors_bigram(logits, n_frames, table, trans, threshold, ids, frame_offsets=None, stream=None):
+    """Forward-backward over the grammar of bio_viterbi_bigram, for the same ragged batch of clips (same arguments), given its `ids`:
+    decode_posteriors with the table `trans` (check_transitions) in place of the flat switch penalty.
+
+    -> (logz [clips], post [rows], cls_post [rows], status [clips]) as decode_posteriors; logz is the log of the summed weight
+    exp(sum of the logits on the path + sum of trans over the runs opened) of every legal path.  A clip with status != 0 gets zeros
+    (STATUS_OVER_CAP also above MAX_BIGRAM_SYMBOLS; STATUS_NOT_A_PATH also for a run opened through a -inf entry of `trans`).  With
+    trans identically -switch_penalty the results are decode_posteriors'."""
+    clips = _check_clips(logits, n_frames, table, 0.0, threshold, frame_offsets)
+    w = check_transitions(trans, len(clips[1]))
+    return _posteriors("wfl_decode_bigram_posterior", logits, clips, (w, float(threshold)), ids, stream)
 
 
 def path_segments_free(ids, chunk_frames, chunk_offsets, chunk_clock, table: npost.LabelTable, frame_duration):

@@ -449,6 +449,17 @@ class Labeler:
             raise ValueError(BIGRAM_SCORES_ERROR)
         return (str(path) if path else None), float(1.0 if given is None else given)
 
+    def bigram_scores_on(self, bigram_scores=None, phoneme_bigram=None, decode=None) -> bool:
+        """Whether the scores of a bigram decode are asked for (None: config postprocess.bigram_scores, else off): decode_scores'
+        records from a forward-backward pass over the grammar WITH the phone-bigram table (decode.decode_posteriors_bigram).  They
+        score the bigram search's path, so they need a phoneme_bigram and with it decode "viterbi" (ValueError otherwise)."""
+        post = self.config.get("postprocess", {})
+        on = bool(post.get("bigram_scores", False) if bigram_scores is None else bigram_scores)
+        if on:
+            _check_bigram_scores(self.decode_options(decode)[0], post.get("phoneme_bigram") if phoneme_bigram is None else phoneme_bigram,
+                                 True)
+        return on
+
     def _bigram_table(self, path, switch_penalty, weight):
         """The search's transition table for the bigram file `path` (absolute, or relative to the working directory)."""
         from . import phonotactics as PH
@@ -460,9 +471,9 @@ class Labeler:
         return self._bigram_cache[key]
 
     def label_files(self, audio_paths, lang_id=None, confidence_threshold=0.0, verbose=True, align=None, align_scores=None,
-                    decode=None, switch_penalty=None, decode_scores=None, phoneme_bigram=None, bigram_weight=None):
-        """-> list (per file) of [(start_s, end_s, phoneme)] after merge + forced alignment; with align_scores or decode_scores, (that
-        list, scores).
+                    decode=None, switch_penalty=None, decode_scores=None, phoneme_bigram=None, bigram_weight=None, bigram_scores=None):
+        """-> list (per file) of [(start_s, end_s, phoneme)] after merge + forced alignment; with align_scores, decode_scores or
+        bigram_scores, (that list, scores).
 
         align: "greedy" -- a `{audio}.txt` transcript is matched onto the freely decoded segments (infer.py:30-60, 312-319);
         "viterbi" -- files with a transcript are aligned by a search over their frame logits on the GPU (align.py: one segment
@@ -483,25 +494,33 @@ class Labeler:
         phoneme_bigram (with decode "viterbi" only; None: config postprocess.phoneme_bigram, else none): a phoneme_bigram.json
         (phonotactics.py); the search then pays  bigram_weight * log P(opened symbol | previous symbol) - switch_penalty  for every
         opened run instead of the flat penalty (decode.bio_viterbi_bigram).  bigram_weight: a number >= 0 (None: config
-        postprocess.bigram_weight, else 1).  decode_scores cannot be combined with a bigram.
+        postprocess.bigram_weight, else 1).  decode_scores cannot be combined with a bigram; bigram_scores is its counterpart there.
 
         decode_scores (with decode "viterbi" only; None: config postprocess.decode_scores, else off): also return scores[i], a
         decode.FreeScore from a forward-backward pass over the grammar for a file the grammar search decoded (per run of the path, before
         merge_segments and any string match, the posterior of its phoneme, of its opening frame and of its weakest frame), or None for a
         file that fell back to the argmax decode (and, with a message, for one whose path wfl_decode_posterior does not accept).  With
-        both kinds of scores on, each file gets its own kind.  The segments are the same with and without."""
+        both kinds of scores on, each file gets its own kind.  The segments are the same with and without.
+
+        bigram_scores (with a phoneme_bigram only; None: config postprocess.bigram_scores, else off): decode_scores for a bigram
+        decode -- the same scores[i] records, from a forward-backward pass over the grammar with the bigram's transition table
+        (decode.decode_posteriors_bigram), so the posterior scores the grammar the search ran on.  The segments are the same with and
+        without."""
         final, scores = self._label_scored(audio_paths, lang_id, confidence_threshold, verbose, align, align_scores, decode,
-                                           switch_penalty, decode_scores, phoneme_bigram, bigram_weight)
-        return (final, scores) if self.align_scores_on(align_scores, align) or self.decode_scores_on(decode_scores, decode) else final
+                                           switch_penalty, decode_scores, phoneme_bigram, bigram_weight, bigram_scores)
+        scored = self.align_scores_on(align_scores, align) or self.decode_scores_on(decode_scores, decode) \
+            or self.bigram_scores_on(bigram_scores, phoneme_bigram, decode)
+        return (final, scores) if scored else final
 
     def _label_scored(self, audio_paths, lang_id=None, confidence_threshold=0.0, verbose=True, align=None, align_scores=None,
-                      decode=None, switch_penalty=None, decode_scores=None, phoneme_bigram=None, bigram_weight=None):
+                      decode=None, switch_penalty=None, decode_scores=None, phoneme_bigram=None, bigram_weight=None, bigram_scores=None):
         """label_files, always -> (segments, scores): the files are split once into those a transcript is Viterbi-aligned to, those the
         grammar search decodes and those left to the argmax decode, and each subset's results go back to its files' places."""
         want_scores = self.align_scores_on(align_scores, align)
         mode, lam = self.decode_options(decode, switch_penalty)
         want_free = self.decode_scores_on(decode_scores, decode)
         bigram, bigram_w = self.bigram_options(phoneme_bigram, bigram_weight, decode, decode_scores)
+        want_free = self.bigram_scores_on(bigram_scores, phoneme_bigram, decode) or want_free
         trans = self._bigram_table(bigram, lam, bigram_w) if bigram else None
         if mode == "viterbi" and int(self.config["postprocess"].get("median_filter", 0)) > 1:
             print("decode: viterbi -- postprocess.median_filter is not applied (the switch penalty takes its place)")
@@ -713,7 +732,7 @@ class Labeler:
         search covers the whole file and a run may cross a chunk seam; the files of a wave go to wfl_decode as one ragged batch and
         only ids / status come back to the host.  A file whose status is not 0 is left out (with a message): the caller decodes it
         by argmax.  want_scores: right after the search, one wfl_decode_posterior call per wave over the clips it decoded (same
-        logits, the device `ids`) and one log-sum-exp reduction over the wave's logits, the per-frame arrays back in one more copy; without, the second dict stays empty and the calls are
+        logits, the device `ids`; wfl_decode_bigram_posterior with the same table when the search was the bigram's) and one log-sum-exp reduction over the wave's logits, the per-frame arrays back in one more copy; without, the second dict stays empty and the calls are
         the search's alone.  trans: the transition table of a phoneme bigram (_bigram_table); the search is then wfl_decode_bigram's,
         everything around it the same."""
         lang_name = self._lang_name(lang_id)
@@ -738,8 +757,12 @@ class Labeler:
             raw = {}                                          # clip -> (score, logz, sum lse, post, cls_post, posterior status)
             ok = [b for b in range(len(sel)) if st_all[b] == DC.STATUS_OK]
             if want_scores and ok:
-                d_logz, d_post, d_cls, d_pst = DC.decode_posteriors(lg, [frames[b] for b in ok], table, switch_penalty, threshold, d_ids,
-                                                                    frame_offsets=f0[ok])
+                if trans is None:
+                    d_logz, d_post, d_cls, d_pst = DC.decode_posteriors(lg, [frames[b] for b in ok], table, switch_penalty, threshold,
+                                                                        d_ids, frame_offsets=f0[ok])
+                else:
+                    d_logz, d_post, d_cls, d_pst = DC.decode_posteriors_bigram(lg, [frames[b] for b in ok], table, trans, threshold,
+                                                                               d_ids, frame_offsets=f0[ok])
                 # (the files' sums of log-sum-exp, path_log_posterior's third term, which the ABI has no output for: one fp32
                 # reduction over the wave's logits, then differences of one running sum in double)
                 run = torch.cat([lg.new_zeros(1, dtype=torch.float64), torch.logsumexp(lg, dim=1).double().cumsum(0)])
@@ -764,8 +787,9 @@ class Labeler:
                     if b in raw and raw[b][5] == DC.STATUS_OK:
                         scored[fi] = DC.free_score(*raw[b][:5], ids_all[pos:pos + n], *plan, self._table, frame_duration,
                                                    names=[names[int(r)] for r in remap[:len(self._table.names)]])
-                    elif want_scores:                         # (wfl_decode_posterior refused the path wfl_decode gave it)
-                        print(f"{audio_paths[fi]}: no decode scores (wfl_decode_posterior status {raw[b][5] if b in raw else None})")
+                    elif want_scores:                         # (the posterior entry refused the path the search gave it)
+                        fn = "wfl_decode_posterior" if trans is None else "wfl_decode_bigram_posterior"
+                        print(f"{audio_paths[fi]}: no decode scores ({fn} status {raw[b][5] if b in raw else None})")
                 pos += n
         return out, scored
 
@@ -901,7 +925,8 @@ def _check_decode(decode, switch_penalty):
 
 
 BIGRAM_SCORES_ERROR = ("decode_scores cannot be combined with a phoneme bigram: the forward-backward pass scores the flat switch "
-                       "penalty, not the bigram the search ran on")
+                       "penalty, not the bigram the search ran on; ask for bigram_scores (postprocess.bigram_scores, --bigram-scores) "
+                       "instead, which scores the bigram's own grammar")
 
 
 def _check_bigram(decode, phoneme_bigram, bigram_weight):
@@ -916,6 +941,25 @@ def _check_bigram(decode, phoneme_bigram, bigram_weight):
     if (phoneme_bigram or bigram_weight is not None) and decode != "viterbi":
         raise ValueError("phoneme_bigram / bigram_weight need decode='viterbi' (postprocess.decode: viterbi): the argmax decode has no "
                          "search to weigh")
+
+
+def _check_bigram_scores(decode, phoneme_bigram, bigram_scores, config_path=None):
+    """bigram_scores scores a bigram decode: it needs a phoneme_bigram and with it decode "viterbi".  What the arguments leave open
+    (None) is looked up in the config file, when one is named and exists, so that a request that cannot be met is refused before any
+    model is loaded."""
+    if not bigram_scores:
+        return
+    post = {}
+    if (decode is None or phoneme_bigram is None) and config_path is not None and os.path.isfile(str(config_path)):
+        post = (load_config(config_path) or {}).get("postprocess") or {}
+    decode = post.get("decode", "argmax") if decode is None else decode
+    phoneme_bigram = post.get("phoneme_bigram") if phoneme_bigram is None else phoneme_bigram
+    if decode != "viterbi":
+        raise ValueError("bigram_scores needs decode='viterbi' (postprocess.decode: viterbi) and a phoneme_bigram: the argmax decode "
+                         "has no lattice to score")
+    if not phoneme_bigram:
+        raise ValueError("bigram_scores needs a phoneme_bigram (postprocess.phoneme_bigram): it scores the bigram search's path; "
+                         "decode_scores scores a search under the flat switch penalty")
 
 
 def _check_align_scores(align, align_scores):
@@ -1011,7 +1055,8 @@ def _write_score(lab_path, segments, score):
 
 def infer_audio(audio_path, config_path="config.yaml", checkpoint_path="best_model.pt", output_lab_path=None, device="cuda",
                 lang_id=None, sample=False, top_k=0, top_p=0.0, temperature=1.0, confidence_threshold=0.0, align=None,
-                align_scores=None, decode=None, switch_penalty=None, decode_scores=None, phoneme_bigram=None, bigram_weight=None):
+                align_scores=None, decode=None, switch_penalty=None, decode_scores=None, phoneme_bigram=None, bigram_weight=None,
+                bigram_scores=None):
     """align: "greedy" | "viterbi" | None (config postprocess.align, else greedy): how a `{audio}.txt` transcript is aligned
     (Labeler.label_files).  align_scores (viterbi only; None: config postprocess.align_scores): also write `{stem}.scores.tsv`
     beside the .lab when the file was Viterbi-aligned (format_scores_tsv).  decode: "argmax" | "viterbi" | None (config
@@ -1019,17 +1064,20 @@ def infer_audio(audio_path, config_path="config.yaml", checkpoint_path="best_mod
     decode is made (Labeler.label_files).  decode_scores (decode viterbi only; None: config postprocess.decode_scores): also write
     `{stem}.decode_scores.tsv` beside the .lab when the grammar search decoded the file (format_decode_scores_tsv).  phoneme_bigram /
     bigram_weight (decode viterbi only; None: config postprocess.phoneme_bigram / postprocess.bigram_weight): the phone-bigram prior
-    of the search (Labeler.label_files)."""
+    of the search (Labeler.label_files).  bigram_scores (with a phoneme_bigram only; None: config postprocess.bigram_scores):
+    decode_scores for a bigram decode, the same `{stem}.decode_scores.tsv`."""
     _check_align(align)
     _check_align_scores(align, align_scores)
     _check_decode(decode, switch_penalty)
     _check_decode_scores(decode, decode_scores)
     if decode is not None:
         _check_bigram(decode, phoneme_bigram, bigram_weight)
+    _check_bigram_scores(decode, phoneme_bigram, bigram_scores, config_path)
     lab = _labeler(config_path, checkpoint_path, device)
     (segments,), (score,) = lab._label_scored([audio_path], lang_id=lang_id, confidence_threshold=confidence_threshold, align=align,
                                               align_scores=align_scores, decode=decode, switch_penalty=switch_penalty,
-                                              decode_scores=decode_scores, phoneme_bigram=phoneme_bigram, bigram_weight=bigram_weight)
+                                              decode_scores=decode_scores, phoneme_bigram=phoneme_bigram, bigram_weight=bigram_weight,
+                                              bigram_scores=bigram_scores)
     if output_lab_path:
         if os.path.abspath(output_lab_path) == os.path.abspath(audio_path):
             # the reference would truncate the input WAV here (infer.py:410-411 + utils.py:77)
@@ -1042,13 +1090,14 @@ def infer_audio(audio_path, config_path="config.yaml", checkpoint_path="best_mod
 def infer_folder(folder_path: str, config_path: str = "config.yaml", checkpoint_path: str = "best_model.pt",
                  output_dir: str = "outputs", device: str = "cuda", lang_id: int = None, sample=False, top_k=0, top_p=0.0,
                  temperature=1.0, confidence_threshold=0.0, align=None, align_scores=None, decode=None, switch_penalty=None,
-                 decode_scores=None, phoneme_bigram=None, bigram_weight=None):
+                 decode_scores=None, phoneme_bigram=None, bigram_weight=None, bigram_scores=None):
     _check_align(align)
     _check_align_scores(align, align_scores)
     _check_decode(decode, switch_penalty)
     _check_decode_scores(decode, decode_scores)
     if decode is not None:
         _check_bigram(decode, phoneme_bigram, bigram_weight)
+    _check_bigram_scores(decode, phoneme_bigram, bigram_scores, config_path)
     wav_files = sorted(f for f in os.listdir(folder_path) if f.lower().endswith(".wav"))
     os.makedirs(output_dir, exist_ok=True)
     # one process per GPU: every rank labels its own share of the files and writes its own .lab files (no collective)
@@ -1062,10 +1111,11 @@ def infer_folder(folder_path: str, config_path: str = "config.yaml", checkpoint_
     want_scores = lab.align_scores_on(align_scores, align)
     want_free = lab.decode_scores_on(decode_scores, decode)
     lab.bigram_options(phoneme_bigram, bigram_weight, decode, decode_scores)
+    want_free = lab.bigram_scores_on(bigram_scores, phoneme_bigram, decode) or want_free
     all_segments, all_scores = lab._label_scored(paths, lang_id=lang_id, confidence_threshold=confidence_threshold, align=align,
                                                  align_scores=align_scores, decode=decode, switch_penalty=switch_penalty,
                                                  decode_scores=decode_scores, phoneme_bigram=phoneme_bigram,
-                                                 bigram_weight=bigram_weight) if paths else ([], [])
+                                                 bigram_weight=bigram_weight, bigram_scores=bigram_scores) if paths else ([], [])
     for wav_file, segments, score in zip(wav_files, all_segments, all_scores):
         print(f"\nInferencing: {wav_file}")
         lab_path = os.path.join(output_dir, os.path.splitext(wav_file)[0] + ".lab")
@@ -1126,8 +1176,12 @@ def main(argv=None):
     @click.option("--bigram-weight", "bigram_weight", type=float, default=None,
                   help="With --phoneme-bigram: the weight of the bigram's log probabilities (>= 0). Default: config "
                        "postprocess.bigram_weight, else 1.")
+    @click.option("--bigram-scores", "bigram_scores", is_flag=True, default=None,
+                  help="With --phoneme-bigram: --decode-scores for the bigram decode; the same {stem}.decode_scores.tsv and "
+                       "decode_scores.tsv, from a forward-backward pass over the grammar with the bigram's table on the GPU. Default: "
+                       "config postprocess.bigram_scores, else off.")
     def cli(path, checkpoint, config, output, lang_id, sample, top_k, top_p, temperature, device, confidence_threshold, align,
-            align_scores, decode, switch_penalty, decode_scores, phoneme_bigram, bigram_weight):
+            align_scores, decode, switch_penalty, decode_scores, phoneme_bigram, bigram_weight, bigram_scores):
         if switch_penalty is not None and not switch_penalty >= 0.0:
             raise click.UsageError("--switch-penalty must be >= 0 (nats)")
         if sample:
@@ -1184,6 +1238,12 @@ def main(argv=None):
             raise click.UsageError(f"--phoneme-bigram / --bigram-weight (postprocess.phoneme_bigram, postprocess.bigram_weight): {err}")
         if phoneme_bigram and decode_scores:
             raise click.UsageError(BIGRAM_SCORES_ERROR)
+        if bigram_scores is None:
+            bigram_scores = bool(cfg["postprocess"].get("bigram_scores", False))
+        try:
+            _check_bigram_scores(decode, phoneme_bigram or "", bigram_scores)
+        except ValueError as err:
+            raise click.UsageError(f"--bigram-scores (postprocess.bigram_scores): {err}")
         output_path = inf_path if output == "." else output
         if not inf_path.exists():
             print(f"Unable to locate folder {str(inf_path)}")
@@ -1193,7 +1253,7 @@ def main(argv=None):
         kw = dict(config_path=str(config), checkpoint_path=str(checkpoint), device=device, lang_id=lang_id, sample=sample,
                   top_k=top_k, top_p=top_p, temperature=temperature, confidence_threshold=confidence_threshold, align=align,
                   align_scores=align_scores, decode=decode, switch_penalty=switch_penalty, decode_scores=decode_scores,
-                  phoneme_bigram=phoneme_bigram, bigram_weight=bigram_weight)
+                  phoneme_bigram=phoneme_bigram, bigram_weight=bigram_weight, bigram_scores=bigram_scores)
         if inf_path.is_dir():
             infer_folder(folder_path=str(inf_path), output_dir=str(output_path), **kw)
         else:
