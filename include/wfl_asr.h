@@ -476,6 +476,29 @@ int32_t wfl_decode_bigram_posterior(const float* logits, int64_t ldl, int32_t C,
                                     const float* trans, float threshold, const int32_t* ids, void* workspace, int64_t workspace_bytes,
                                     float* logz, float* post, float* cls_post, int32_t* status, void* stream);
 
+/* ---- Expected successions of a phone-bigram decode on the GPU: one Baum-Welch E-step over the grammar of wfl_decode_bigram, to adapt
+ * the bigram to audio without labels (`python -m wfl_asr_amd.adapt_bigram`; wfl-asr_amd/decode.py).  Clips, logits, pairs, o_id,
+ * threshold, trans, the symbols, the states, the legality rule, the forced-to-O rule, the virtual O frame, the path weights, W, the
+ * recurrences, the guards and logz are wfl_decode_bigram_posterior's; there is no path argument.  With end_{-1} = (1, 0, ...),
+ * u_t[O] = e_t(O) beta_t(O), u_t[q] = e_t(B-q) beta_t(B-q):
+ *     counts[b][s][q] = (1 / Z) sum_{t = 0 .. T-1} end_{t-1}[s] W[s][q] u_t[q]     for (s, q) != (O, O);     counts[b][O][O] = 0
+ * the expected number of runs of symbol q opened directly after symbol s under the path distribution wfl_decode_bigram maximises over,
+ * the runs counted as the search counts them.  counts (device, fp32) holds one [N][N] table per clip, rows the PREVIOUS symbol; every
+ * entry is >= 0, an entry whose trans is -inf is exactly 0, column q >= 1 sums to sum_t gamma_t(B-q).
+ * status[b]: 0 ok; 2 C above 1024 or N above WFL_DECODE_BIGRAM_MAX_SYMBOLS; 4 a bad class table.  A clip with status != 0 gets logz = 0
+ * and an all-zero table; so does T = 0, with status 0.  logz, counts and status must not be null when n_clips > 0.
+ * One workgroup per clip: a clip alone equals the same clip inside any batch, bit for bit.  The sums are kept in registers for the
+ * whole clip, in fp32 (a frame adds at most 1 to the table).  A frame's share is end W u times the constant 2^(exponents) / Z: that
+ * constant is formed in double, clamped to 2^126 and applied to end first, so no intermediate is inf or NaN whatever the logits and the
+ * table; the clamp acts only where every product of the frame has left fp32's normal range, which reports as 0 as a posterior does.
+ * Workspace, per clip with T > 0, in 4-byte words: round_up_64(T (N + 1)) + 2 round_up_64(T)  (per frame the scaled vector end_{t-1} and
+ * its exponent; the row maximum; the forced flag): 4 (N + 3) bytes per frame, 11.7 MB for 15 000 frames at the cap; 0 above the cap. */
+int64_t wfl_decode_bigram_counts_workspace_bytes(const int32_t* n_frames_host, int32_t n_clips, int32_t n_pairs);
+int32_t wfl_decode_bigram_counts(const float* logits, int64_t ldl, int32_t C, int32_t o_id, const int64_t* frame_off_host,
+                                 const int32_t* n_frames_host, int32_t n_clips, const int32_t* pairs, int32_t n_pairs, const float* trans,
+                                 float threshold, void* workspace, int64_t workspace_bytes, float* logz, float* counts, int32_t* status,
+                                 void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,7 +1,8 @@
-// The BIO grammar over the classes themselves, as the four decode entries see it -- wfl_decode (csrc/decode.hip, the max-product search
+// The BIO grammar over the classes themselves, as the five decode entries see it -- wfl_decode (csrc/decode.hip, the max-product search
 // under a flat penalty), wfl_decode_bigram (csrc/decode_bigram.hip, the same search under a phone-bigram table), wfl_decode_posterior
 // (csrc/decode_posterior.hip, the sum-product sweeps under the flat penalty) and wfl_decode_bigram_posterior
-// (csrc/decode_bigram_posterior.hip, the sum-product sweeps under the table) -- defined ONCE: a change made here reaches all four, so a
+// (csrc/decode_bigram_posterior.hip, the sum-product sweeps under the table); wfl_decode_bigram_counts (csrc/decode_bigram_counts.hip, the
+// same sweeps summed into expected successions) is the fifth -- defined ONCE: a change made here reaches all of them, so a
 // posterior always scores the grammar and the forced frames its search ran on.  A .hip file keeps its chain kernel, the head of its workspace and its
 // own fields of the launch struct; everything else of an entry is here.
 //
@@ -113,7 +114,8 @@ __global__ __launch_bounds__(256) void pre_kernel(L a, Head head) {
 }
 
 // ---- what a clip that is not searched / scored looks like, written by a block of NT threads; the shape is chosen by the outputs the
-// launch struct has.  A search (ids, score): O everywhere, score 0.  A posterior (logz, post, cls_post): zeros.
+// launch struct has.  A search (ids, score): O everywhere, score 0.  A posterior (logz, post, cls_post): zeros.  Expected successions
+// (logz, counts [clips][N][N]): logz 0 and an all-zero table.
 template <int NT, class L>
 static __device__ __forceinline__ auto refuse(const L& a, const Clip& cl, int status) -> decltype((void)a.score) {
   int* ids = a.ids + cl.frame_off;
@@ -122,8 +124,16 @@ static __device__ __forceinline__ auto refuse(const L& a, const Clip& cl, int st
 }
 
 template <int NT, class L>
-static __device__ __forceinline__ auto refuse(const L& a, const Clip& cl, int status) -> decltype((void)a.logz) {
+static __device__ __forceinline__ auto refuse(const L& a, const Clip& cl, int status) -> decltype((void)a.post) {
   for (int t = threadIdx.x; t < cl.T; t += NT) a.post[cl.frame_off + t] = a.cls_post[cl.frame_off + t] = 0.f;
+  if (threadIdx.x == 0) { a.logz[cl.clip] = 0.f; a.status[cl.clip] = status; }
+}
+
+template <int NT, class L>
+static __device__ __forceinline__ auto refuse(const L& a, const Clip& cl, int status) -> decltype((void)a.counts) {
+  const long nn = (long)(a.n_pairs + 1) * (a.n_pairs + 1);
+  float* c = a.counts + cl.clip * nn;
+  for (long e = threadIdx.x; e < nn; e += NT) c[e] = 0.f;
   if (threadIdx.x == 0) { a.logz[cl.clip] = 0.f; a.status[cl.clip] = status; }
 }
 

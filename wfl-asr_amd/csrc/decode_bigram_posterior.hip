@@ -18,7 +18,7 @@
 // path, post = gamma(B-p) + gamma(I-p) of the path's phoneme (gamma(O) on an O frame) and cls_post = gamma(ids[t]).  With trans
 // identically -lambda everything equals wfl_decode_posterior at that lambda.
 //
-// Two kernels.  bio::pre_kernel (csrc/bio_grammar.h, as everything this entry shares with the other three; row maxima, as for
+// Two kernels.  bio::pre_kernel (csrc/bio_grammar.h, as everything this entry shares with the other decode entries; row maxima, as for
 // wfl_decode_posterior).  bigram_post_chain_kernel, ONE WORKGROUP of 256 threads per clip, the shape of the search:
 //   - the table lives in LDS for the whole clip as LINEAR weights, row = previous symbol, ROW STRIDE LD = N | 1 words (odd).  Forward, wave
 //     w takes the predecessors [w NS, (w + 1) NS), NS = ceil(N / 4), lane l the targets l, l + 64, l + 128: the lanes read consecutive
@@ -44,21 +44,16 @@
 // Before the sweeps the workgroup checks in parallel that ids is a path of the grammar (status 8): a class of the table, I-p only after
 // B-p / I-p, O on a forced frame, and no run opened through a succession whose W is 0.  Workspace per clip, in words: [alpha records
 // 3 T] [pair | kind << 16 per frame T] [row maxima T] [forced flags T], each rounded up to 64: wfl_decode_posterior's.
-#include "bio_grammar.h"
-#include "wfl_asr.h"
+#include "bigram_sumproduct.h"
 
 namespace {
 
+using namespace bigram_sp;   // the workgroup's shape, the table in LDS, the scale: shared with csrc/decode_bigram_counts.hip
 using bio::NO_CLASS;
 using lattice::MAX_CLASSES;
 using lattice::round64;
 
-constexpr int MAX_SYMBOLS = WFL_DECODE_BIGRAM_MAX_SYMBOLS;
-constexpr int NT = 256;                      // threads per clip
-constexpr int NW = NT / 64;                  // slices of the summed-over symbols
-constexpr int JT = (MAX_SYMBOLS + 63) / 64;  // output symbols per lane
 constexpr int D = 8;                         // frames per emission group
-static_assert(MAX_SYMBOLS <= NT, "one owner thread per symbol");
 
 struct BigramPostLaunch : bio::Launch {
   const float* trans;  // [N][N], rows the previous symbol
@@ -71,43 +66,6 @@ __host__ __device__ inline long off_sel(int T) { return round64(3L * T); }
 struct HeadWords {
   __host__ __device__ long operator()(int T) const { return off_sel(T) + round64(T); }
 };
-
-constexpr float W_MIN = 0x1p-60f;   // floor of an O emission and of a finite table entry
-constexpr float W_MAX = 0x1p60f;    // ceiling of a table entry
-
-// dynamic LDS, in bytes: [table N rows of LD floats] [partial sums NW x MAX_SYMBOLS] [end / u MAX_SYMBOLS] [B class, I class per symbol]
-__host__ __device__ inline int row_stride(int N) { return N | 1; }
-__host__ __device__ inline int table_bytes(int N) { return (N * row_stride(N) * 4 + 15) / 16 * 16; }
-constexpr int FIXED_BYTES = (NW + 3) * MAX_SYMBOLS * 4;
-inline int lds_bytes(int N) { return table_bytes(N) + FIXED_BYTES; }
-constexpr int MAX_LDS = (MAX_SYMBOLS * (MAX_SYMBOLS | 1) * 4 + 15) / 16 * 16 + FIXED_BYTES;
-static_assert(MAX_LDS + (MAX_CLASSES + MAX_CLASSES / 32 + 16) * 4 <= 160 * 1024, "LDS of one CU");
-
-// ---- every lane gets the wave's maximum: DPP inside a row of 16, the four row maxima through SGPRs
-template <int CTRL>
-__device__ __forceinline__ float dpp_max(float v) {
-  return fmaxf(v, __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xf, 0xf, false)));
-}
-
-__device__ __forceinline__ float wave_largest(float v) {
-  v = dpp_max<0xB1>(v);    // quad_perm [1,0,3,2]
-  v = dpp_max<0x4E>(v);    // quad_perm [2,3,0,1]
-  v = dpp_max<0x141>(v);   // row_half_mirror: the other quad of the 8
-  v = dpp_max<0x140>(v);   // row_mirror: the other 8 of the 16
-  const int b = __float_as_int(v);
-  const float r0 = __int_as_float(__builtin_amdgcn_readlane(b, 0)), r1 = __int_as_float(__builtin_amdgcn_readlane(b, 16));
-  const float r2 = __int_as_float(__builtin_amdgcn_readlane(b, 32)), r3 = __int_as_float(__builtin_amdgcn_readlane(b, 48));
-  return fmaxf(fmaxf(r0, r1), fmaxf(r2, r3));
-}
-
-// x = f 2^e, f in [1, 2): e into `ex`, -> 2^-e.  The exponent is kept inside the normal range, so a vector that is all zero (a table
-// without a finite way into O: refused by the Python layer) stays zero instead of turning into NaN.
-__device__ __forceinline__ float unscale(float x, int& ex) {
-  int be = __builtin_amdgcn_readfirstlane((__float_as_int(x) >> 23) & 0xff);
-  be = min(max(be, 1), 253);
-  ex = be - 127;
-  return __int_as_float((254 - be) << 23);
-}
 
 __global__ __launch_bounds__(NT) void bigram_post_chain_kernel(BigramPostLaunch a) {
   extern __shared__ __align__(16) unsigned char lds[];
@@ -136,12 +94,7 @@ __global__ __launch_bounds__(NT) void bigram_post_chain_kernel(BigramPostLaunch 
   }
   if (tid < a.n_pairs) { symB[tid + 1] = cB[0]; symI[tid + 1] = cI[0]; }
   if (tid == 0) { symB[0] = o_id; symI[0] = NO_CLASS; }
-  // the table as linear weights: -inf is exactly 0, a finite entry is clamped to [2^-60, 2^60], O after O is 1
-  for (int e = tid; e < N * N; e += NT) {
-    const float v = a.trans[e];
-    const float w = e == 0 ? 1.f : (v == -INFINITY ? 0.f : fminf(fmaxf(expf(v), W_MIN), W_MAX));
-    tab[(e / N) * LD + e % N] = w;
-  }
+  stage_table(a.trans, N, tab);
   if (tid < MAX_SYMBOLS) endv[tid] = tid == 0 ? 1.f : 0.f;   // the virtual O frame
   __syncthreads();
 

@@ -15,6 +15,8 @@ follows `B-p` or `I-p`, and every run that is opened costs `switch_penalty` nats
                       the posterior of the phoneme and of the exact class the path chose (`postprocess.decode_scores`)
   decode_posteriors_bigram  the same over the grammar of bio_viterbi_bigram, the table included (csrc/decode_bigram_posterior.hip,
                       `wfl_decode_bigram_posterior`; `postprocess.bigram_scores`)
+  bigram_expected_counts  the expected successions of a batch of clips under bio_viterbi_bigram's path distribution, one [N, N] table
+                      per clip (csrc/decode_bigram_counts.hip, `wfl_decode_bigram_counts`): the E-step of adapt_bigram.py
   path_segments_free  the path's ids of a file, chunk by chunk, -> segments; a run that crosses a chunk seam is one segment
   free_score          those outputs + bio_viterbi's score -> FreeScore / RunScore records, run j being segment j of the path
 """
@@ -90,6 +92,10 @@ def posterior_workspace_bytes(n_frames, n_pairs) -> int:
 
 def bigram_posterior_workspace_bytes(n_frames, n_pairs) -> int:
     return _workspace_bytes("wfl_decode_bigram_posterior_workspace_bytes", n_frames, n_pairs)
+
+
+def bigram_counts_workspace_bytes(n_frames, n_pairs) -> int:
+    return _workspace_bytes("wfl_decode_bigram_counts_workspace_bytes", n_frames, n_pairs)
 
 
 def _check_clips(logits, n_frames, table, switch_penalty, threshold, frame_offsets):
@@ -243,6 +249,26 @@ def decode_posteriors_bigram(logits, n_frames, table, trans, threshold, ids, fra
     clips = _check_clips(logits, n_frames, table, 0.0, threshold, frame_offsets)
     w = check_transitions(trans, len(clips[1]))
     return _posteriors("wfl_decode_bigram_posterior", logits, clips, (w, float(threshold)), ids, stream)
+
+
+def bigram_expected_counts(logits, n_frames, table, trans, threshold, frame_offsets=None, stream=None):
+    """The expected successions of a ragged batch of clips under the grammar of bio_viterbi_bigram (same arguments): one Baum-Welch
+    E-step over the table `trans` (check_transitions).
+
+    -> (logz [clips] float32, counts [clips, N, N] float32, status [clips] int32), CUDA tensors; N = phonemes + 1, symbol 0 is O, rows
+    are the PREVIOUS symbol.  counts[b][s][q] is the expected number of runs of q opened directly after s in clip b, the runs counted
+    as the search counts them (every B-q frame, and every O frame whose predecessor is not O); [O][O] and every entry whose `trans` is
+    -inf are exactly 0.  logz is decode_posteriors_bigram's.  A clip with status != 0 (STATUS_OVER_CAP also above MAX_BIGRAM_SYMBOLS;
+    STATUS_BAD_CLASS) gets logz 0 and an all-zero table; so does an empty clip, with status 0."""
+    clips = _check_clips(logits, n_frames, table, 0.0, threshold, frame_offsets)
+    w = check_transitions(trans, len(clips[1]))
+    nb, n = clips[2], len(clips[1]) + 1
+    dev = logits.device
+    logz = torch.empty(max(nb, 1), dtype=torch.float32, device=dev)
+    counts = torch.empty((max(nb, 1), n, n), dtype=torch.float32, device=dev)
+    status = torch.empty(max(nb, 1), dtype=torch.int32, device=dev)
+    _call("wfl_decode_bigram_counts", logits, clips, (w, float(threshold)), (logz, counts, status), stream)
+    return logz[:nb], counts[:nb], status[:nb]
 
 
 def path_segments_free(ids, chunk_frames, chunk_offsets, chunk_clock, table: npost.LabelTable, frame_duration):

@@ -793,6 +793,45 @@ class Labeler:
                 pos += n
         return out, scored
 
+    def expected_successions(self, audio_paths, trans, lang_id=None, confidence_threshold=0.0, verbose=True):
+        """One Baum-Welch E-step over files without labels, under the grammar and the transition table `trans` ([N, N] float32,
+        phonotactics.transition_table) of the bigram search: -> (counts float64 [N, N]: the expected number of runs of symbol q opened
+        directly after symbol s, summed over the files in float64 on the host; total_logz; total_lse: the frames' summed log-sum-exp;
+        n_frames; skipped: the paths left out).  Symbol 0 is O, symbol 1 + p phoneme p of decode.class_table(labels).  The files are
+        forwarded as _decode_viterbi forwards them: a file is one clip, so a run may cross a 30 s seam; the files of a wave go to
+        wfl_decode_bigram_counts as one ragged batch (decode.bigram_expected_counts), and one log-sum-exp reduction over the wave's
+        logits gives total_lse.  A file whose status is not 0 is skipped with a message."""
+        if self._decode_table is None:
+            self._decode_table = DC.class_table(self.labels)
+        table = self._decode_table
+        n = len(table.pairs) + 1
+        total = np.zeros((n, n), np.float64)
+        total_logz = total_lse = 0.0
+        n_frames, skipped = 0, []
+        for files, by_file in self._file_waves(audio_paths, verbose):
+            sel = [fi for fi in files if fi in by_file]
+            if not sel:
+                continue
+            _, rows = self._forward_with_logits(sel, by_file, lang_id, confidence_threshold)
+            frames, lg = self._file_rows(rows, by_file, sel)
+            d_logz, d_counts, d_st = DC.bigram_expected_counts(lg, frames, table, trans, confidence_threshold)
+            f0 = np.concatenate([[0], np.cumsum(np.asarray(frames, np.int64))[:-1]])
+            run = torch.cat([lg.new_zeros(1, dtype=torch.float64), torch.logsumexp(lg, dim=1).double().cumsum(0)])
+            d_lse = run[torch.from_numpy(f0 + np.asarray(frames, np.int64)).to(lg.device)] - run[torch.from_numpy(f0).to(lg.device)]
+            h = torch.cat([d_logz.double(), d_lse, d_st.double()]).cpu().numpy()
+            h_counts = d_counts.cpu().numpy()
+            nb = len(sel)
+            for b, fi in enumerate(sel):
+                if int(h[2 * nb + b]) != DC.STATUS_OK:
+                    print(f"{audio_paths[fi]}: no expected successions (wfl_decode_bigram_counts status {int(h[2 * nb + b])}); skipped")
+                    skipped.append(audio_paths[fi])
+                    continue
+                total += h_counts[b].astype(np.float64)
+                total_logz += float(h[b])
+                total_lse += float(h[nb + b])
+                n_frames += int(frames[b])
+        return total, total_logz, total_lse, n_frames, skipped
+
     def _label_viterbi(self, audio_paths, transcripts, lang_id, threshold, verbose, want_scores=False):
         """Files with a transcript, align="viterbi".  Their chunks are forwarded with logits (kept on the device); the free decode of
         the same forward gives the greedy result, which the pause rule at the ends needs and which a file falls back to (with a

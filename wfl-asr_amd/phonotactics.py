@@ -5,6 +5,8 @@ Symbols are `O` (silence between segments: no phoneme) and the phonemes.  The mo
 successions the search pays for: every opened phoneme run, and every `O` run after a phoneme.  `O` after `O` is no succession.
 
   estimate          HTK `.lab` files -> Bigram (counts, natural-log conditional probabilities)
+  reestimate        expected succession counts (decode.bigram_expected_counts, summed over unlabelled audio) -> Bigram: the M-step
+                    of adapt_bigram.py, with an optional prior bigram
   save / load       the JSON file {"symbols": ["O", ...], "log_prob": [[...]]}, `null` = a forbidden succession
   transition_table  Bigram + the label set's class table -> the float32 table  weight * log_prob - switch_penalty  of the search
   python -m wfl_asr_amd.phonotactics LAB_DIR... -o phoneme_bigram.json [--phonemes phonemes.txt] [--smoothing K] [--min-gap S]
@@ -24,7 +26,7 @@ O = "O"
 class Bigram(NamedTuple):
     symbols: List[str]                   # "O" first, then the phonemes
     log_prob: np.ndarray                 # [n, n] float64, rows the previous symbol; -inf: forbidden; [O][O] is -inf (never read)
-    counts: Optional[np.ndarray] = None  # [n, n] int64 (estimate only)
+    counts: Optional[np.ndarray] = None  # [n, n] int64 (estimate), float64 (reestimate); not saved
 
 
 def read_lab(path):
@@ -87,6 +89,53 @@ def estimate(lab_paths, symbols=None, smoothing=1.0, min_gap=0.02) -> Bigram:
     with np.errstate(divide="ignore", invalid="ignore"):
         lp = np.where(c > 0, np.log(c / tot), -np.inf)
     return Bigram(syms, lp, counts)
+
+
+def reestimate(counts, symbols, prior: Optional[Bigram] = None, prior_count=0.0, smoothing=0.0) -> Bigram:
+    """Expected succession counts -> Bigram, as `estimate` turns its integer counts into one.
+
+    counts       float64 [n, n] in `symbols`' order ("O" first), rows the previous symbol, entries >= 0
+    prior        a Bigram over the same symbols in the same order: a succession it forbids stays forbidden, whatever the counts and
+                 the smoothing; prior_count pseudo-successions per row are spread as its probabilities
+    smoothing    added to every allowed count of a row
+    Row by row  c = counts + prior_count * exp(prior.log_prob) + smoothing,  normalised over the row; `O` -> `O` is excluded.  A row
+    whose total is 0 keeps the prior's row; without a prior it is uniform over its allowed successions.  ValueError, naming the
+    phoneme, when a [p][O] that the prior allows (every one, without a prior) would come out forbidden: the search needs a way into
+    `O` from every phoneme."""
+    syms = list(symbols)
+    n = len(syms)
+    if n == 0 or syms[0] != O or len(set(syms)) != n:
+        raise ValueError("symbols must be distinct and begin with 'O'")
+    c = np.array(counts, np.float64)
+    if c.shape != (n, n):
+        raise ValueError(f"counts must be a [{n}, {n}] table, got {list(c.shape)}")
+    if not np.isfinite(c).all() or (c < 0).any():
+        raise ValueError("counts must be finite and >= 0")
+    if not float(prior_count) >= 0.0 or not float(smoothing) >= 0.0:
+        raise ValueError("prior_count and smoothing must be >= 0")
+    allowed = np.ones((n, n), bool)
+    pp = np.zeros((n, n))
+    if prior is not None:
+        if list(prior.symbols) != syms:
+            raise ValueError("the prior bigram must hold the same symbols in the same order")
+        lp0 = np.asarray(prior.log_prob, np.float64)
+        allowed = np.isfinite(lp0)
+        pp = np.where(allowed, np.exp(np.where(allowed, lp0, 0.0)), 0.0)
+    allowed[0, 0] = False
+    pp[0, 0] = 0.0
+    c = np.where(allowed, c + (float(prior_count) * pp if float(prior_count) > 0.0 else 0.0) + float(smoothing), 0.0)
+    tot = c.sum(axis=1, keepdims=True)
+    empty = tot[:, 0] == 0
+    if empty.any():                                  # nothing seen from this symbol: the prior's row, else uniform
+        fill = pp if prior is not None else allowed.astype(np.float64)
+        c[empty] = fill[empty]
+        tot = c.sum(axis=1, keepdims=True)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        lp = np.where(c > 0, np.log(c / tot), -np.inf)
+    shut = [syms[p] for p in range(1, n) if allowed[p, 0] and not np.isfinite(lp[p, 0])]
+    if shut:
+        raise ValueError(f"no way into 'O' is left from: {', '.join(shut)} (use smoothing > 0 or a prior_count > 0)")
+    return Bigram(syms, lp, np.array(counts, np.float64))
 
 
 def save(bigram: Bigram, path):
