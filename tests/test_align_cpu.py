@@ -211,17 +211,7 @@ def test_align_option_on_the_public_surface():
         I.infer_audio("x.wav", align="dtw")
     with pytest.raises(ValueError, match="align"):
         I.infer_folder("some_folder", align="dtw")
-
-    class Cfg:
-        def __init__(self, pp):
-            self.config = {"postprocess": pp}
-    assert I.Labeler.align_mode(Cfg({}), None) == "greedy"
-    assert I.Labeler.align_mode(Cfg({"align": "viterbi"}), None) == "viterbi"
-    assert I.Labeler.align_mode(Cfg({"align": "viterbi"}), "greedy") == "greedy"
-    with pytest.raises(ValueError, match="align"):
-        I.Labeler.align_mode(Cfg({}), "nearest")
-    with pytest.raises(ValueError, match="align"):
-        I.Labeler.align_mode(Cfg({"align": "best"}), None)
+    # (how the option is resolved against the config: tests/test_options_cpu.py)
 
 
 def test_cli_takes_align():

@@ -157,20 +157,7 @@ def test_align_scores_option_on_the_public_surface():
         I.infer_audio("x.wav", align="greedy", align_scores=True)
     with pytest.raises(ValueError, match="align_scores"):
         I.infer_folder("some_folder", align="greedy", align_scores=True)
-
-    class Cfg:
-        align_mode = I.Labeler.align_mode
-
-        def __init__(self, pp):
-            self.config = {"postprocess": pp}
-    on = I.Labeler.align_scores_on
-    assert on(Cfg({}), None, None) is False and on(Cfg({"align": "viterbi"}), None, None) is False
-    assert on(Cfg({"align": "viterbi", "align_scores": True}), None, None) is True
-    assert on(Cfg({"align": "viterbi", "align_scores": True}), False, None) is False
-    assert on(Cfg({}), True, "viterbi") is True
-    for cfg, sc, al in ((Cfg({}), True, None), (Cfg({"align": "viterbi"}), True, "greedy"), (Cfg({"align_scores": True}), None, None)):
-        with pytest.raises(ValueError, match="align_scores"):
-            on(cfg, sc, al)
+    # (how the option is resolved against the config: tests/test_options_cpu.py)
 
 
 def test_cli_takes_align_scores(capsys):

@@ -169,36 +169,8 @@ def test_the_command_line_tool_emits_every_phoneme_of_the_label_set(tmp_path):
     assert np.isclose(W[1, 2], np.log(2.5 / 5.5), atol=1e-6)
 
 
-class _Stub:
-    """The Labeler's option methods on a bare config (no model, no GPU)."""
-    def __init__(self, post):
-        self.config = {"postprocess": post}
-
-
-def _options(post, **kw):
-    from wfl_asr_amd.infer import Labeler
-    stub = _Stub(post)
-    for name in ("decode_options", "decode_scores_on", "bigram_options"):
-        setattr(stub, name, getattr(Labeler, name).__get__(stub))
-    return stub.bigram_options(**kw)
-
-
 def test_option_validation():
-    assert _options({}) == (None, 1.0)
-    assert _options({"decode": "viterbi", "phoneme_bigram": "bg.json", "bigram_weight": 0.5}) == ("bg.json", 0.5)
-    assert _options({"decode": "viterbi"}, phoneme_bigram="x.json") == ("x.json", 1.0)
-    with pytest.raises(ValueError, match="need decode='viterbi'"):
-        _options({"phoneme_bigram": "bg.json"})
-    with pytest.raises(ValueError, match="need decode='viterbi'"):
-        _options({"decode": "viterbi"}, phoneme_bigram="bg.json", decode="argmax")
-    with pytest.raises(ValueError, match="need decode='viterbi'"):
-        _options({}, bigram_weight=1.0)
-    with pytest.raises(ValueError, match="bigram_weight must be a number >= 0"):
-        _options({"decode": "viterbi", "phoneme_bigram": "bg.json", "bigram_weight": -0.5})
-    with pytest.raises(ValueError, match="decode_scores cannot be combined"):
-        _options({"decode": "viterbi", "phoneme_bigram": "bg.json", "decode_scores": True})
-    with pytest.raises(ValueError, match="decode_scores cannot be combined"):
-        _options({"decode": "viterbi"}, phoneme_bigram="bg.json", decode_scores=True)
+    """(how the options are resolved against the config, and the rules: tests/test_options_cpu.py)"""
     from wfl_asr_amd.infer import infer_audio
     with pytest.raises(ValueError, match="need decode='viterbi'"):      # refused before any model is loaded
         infer_audio("x.wav", decode="argmax", phoneme_bigram="bg.json")

@@ -135,46 +135,22 @@ def test_parameter_list_of_the_python_entry():
         assert list(params)[-1] == "bigram_scores" and params["bigram_scores"].default is None, f
 
 
-class _Stub:
-    """The Labeler's option methods on a bare config (no model, no GPU)."""
-    def __init__(self, post):
-        self.config = {"postprocess": post}
-
-
-def _stub(post):
-    from wfl_asr_amd.infer import Labeler
-    stub = _Stub(post)
-    for name in ("decode_options", "decode_scores_on", "bigram_options", "bigram_scores_on"):
-        setattr(stub, name, getattr(Labeler, name).__get__(stub))
-    return stub
-
-
 def test_option_validation():
-    assert _stub({}).bigram_scores_on() is False
-    assert _stub({"decode": "viterbi", "phoneme_bigram": "bg.json"}).bigram_scores_on() is False
-    # accepted with a bigram, by the config key as by the argument
-    assert _stub({"decode": "viterbi", "phoneme_bigram": "bg.json", "bigram_scores": True}).bigram_scores_on() is True
-    assert _stub({"decode": "viterbi", "phoneme_bigram": "bg.json"}).bigram_scores_on(True) is True
-    assert _stub({"decode": "viterbi"}).bigram_scores_on(True, "bg.json") is True
-    assert _stub({}).bigram_scores_on(True, "bg.json", "viterbi") is True
-    assert _stub({"decode": "viterbi", "phoneme_bigram": "bg.json", "bigram_scores": True}).bigram_scores_on(False) is False
-    assert _stub({"decode": "viterbi", "phoneme_bigram": "bg.json", "bigram_scores": True}).bigram_options() == ("bg.json", 1.0)
-    # refused without a bigram
+    """The rules and how the options are resolved against a config: tests/test_options_cpu.py.  Here: the Labeler resolves a request
+    against its own config (a bare one: no model, no GPU)."""
+    from wfl_asr_amd.infer import Labeler
+    from wfl_asr_amd.options import PostOptions
+
+    class Stub:
+        config = {"postprocess": {"decode": "viterbi", "phoneme_bigram": "bg.json", "bigram_scores": True}}
+    assert Labeler.options(Stub()) == PostOptions(decode="viterbi", phoneme_bigram="bg.json", bigram_scores=True)
+    assert Labeler.options(Stub(), bigram_scores=False, switch_penalty=2).bigram_scores is False
+    with pytest.raises(ValueError, match="decode_scores cannot be combined with a phoneme bigram.*bigram_scores"):
+        Labeler.options(Stub(), decode_scores=True)
+    Stub.config = {}                                  # no postprocess section: the defaults
+    assert Labeler.options(Stub()) == PostOptions()
     with pytest.raises(ValueError, match="bigram_scores needs a phoneme_bigram"):
-        _stub({"decode": "viterbi", "bigram_scores": True}).bigram_scores_on()
-    with pytest.raises(ValueError, match="bigram_scores needs a phoneme_bigram"):
-        _stub({"decode": "viterbi"}).bigram_scores_on(True)
-    # refused with the argmax decode
-    with pytest.raises(ValueError, match="bigram_scores needs decode='viterbi'"):
-        _stub({"decode": "viterbi", "phoneme_bigram": "bg.json"}).bigram_scores_on(True, decode="argmax")
-    with pytest.raises(ValueError, match="bigram_scores needs decode='viterbi'"):
-        _stub({"bigram_scores": True}).bigram_scores_on(phoneme_bigram="bg.json")
-    # decode_scores with a bigram is still refused, and the message now points at the new key
-    for post, kw in (({"decode": "viterbi", "phoneme_bigram": "bg.json", "decode_scores": True}, {}),
-                     ({"decode": "viterbi"}, dict(phoneme_bigram="bg.json", decode_scores=True)),
-                     ({"decode": "viterbi", "phoneme_bigram": "bg.json", "bigram_scores": True}, dict(decode_scores=True))):
-        with pytest.raises(ValueError, match="decode_scores cannot be combined with a phoneme bigram.*bigram_scores"):
-            _stub(post).bigram_options(**kw)
+        Labeler.options(Stub(), decode="viterbi", bigram_scores=True)
 
 
 def test_refused_before_any_model_is_loaded(tmp_path):

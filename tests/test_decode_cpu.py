@@ -230,23 +230,7 @@ def test_decode_option_on_the_public_surface():
         I.infer_audio("x.wav", decode="viterbi", switch_penalty=-1.0)
     with pytest.raises(ValueError, match="switch_penalty"):
         I.infer_folder("some_folder", switch_penalty="much")
-
-    class Cfg:
-        def __init__(self, pp):
-            self.config = {"postprocess": pp}
-    opts = I.Labeler.decode_options
-    assert opts(Cfg({})) == ("argmax", 0.0)
-    assert opts(Cfg({"decode": "viterbi", "switch_penalty": 2})) == ("viterbi", 2.0)
-    assert opts(Cfg({"decode": "viterbi", "switch_penalty": 2}), "argmax", 0.5) == ("argmax", 0.5)
-    assert opts(Cfg({}), "viterbi", 4) == ("viterbi", 4.0)
-    with pytest.raises(ValueError, match="decode"):
-        opts(Cfg({}), "median")
-    with pytest.raises(ValueError, match="decode"):
-        opts(Cfg({"decode": "best"}))
-    with pytest.raises(ValueError, match="switch_penalty"):
-        opts(Cfg({"switch_penalty": -0.1}))
-    with pytest.raises(ValueError, match="switch_penalty"):
-        opts(Cfg({}), "viterbi", float("nan"))
+    # (how the options are resolved against the config: tests/test_options_cpu.py)
 
 
 def test_cli_takes_decode():

@@ -201,20 +201,7 @@ def test_decode_scores_option_on_the_public_surface():
         I.infer_audio("x.wav", decode="argmax", decode_scores=True)
     with pytest.raises(ValueError, match="decode_scores"):
         I.infer_folder("some_folder", decode="argmax", decode_scores=True)
-
-    class Cfg:
-        decode_options = I.Labeler.decode_options
-
-        def __init__(self, pp):
-            self.config = {"postprocess": pp}
-    on = I.Labeler.decode_scores_on
-    assert on(Cfg({}), None, None) is False and on(Cfg({"decode": "viterbi"}), None, None) is False
-    assert on(Cfg({"decode": "viterbi", "decode_scores": True}), None, None) is True
-    assert on(Cfg({"decode": "viterbi", "decode_scores": True}), False, None) is False
-    assert on(Cfg({}), True, "viterbi") is True
-    for cfg, sc, dec in ((Cfg({}), True, None), (Cfg({"decode": "viterbi"}), True, "argmax"), (Cfg({"decode_scores": True}), None, None)):
-        with pytest.raises(ValueError, match="the argmax decode has no lattice to score"):
-            on(cfg, sc, dec)
+    # (how the option is resolved against the config: tests/test_options_cpu.py)
 
 
 def test_the_texts_of_both_files():

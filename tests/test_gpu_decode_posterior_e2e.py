@@ -173,4 +173,4 @@ def test_both_kinds_of_scores_give_each_file_its_own(world, tmp_path):
     assert [ln.split("\t")[0] for ln in open(tmp_path / "both" / "alignment_scores.tsv").read().split("\n")[1:-1]] == ["a.wav"]
     assert [ln.split("\t")[0] for ln in open(tmp_path / "both" / "decode_scores.tsv").read().split("\n")[1:-1]] == ["plain.wav"]
     r = subprocess.run(base + ["--decode-scores"], capture_output=True, text=True, timeout=300)
-    assert r.returncode != 0 and "needs --decode viterbi" in r.stderr
+    assert r.returncode == 2 and "decode_scores needs decode='viterbi'" in r.stderr      # (a usage error, options.resolve's text)

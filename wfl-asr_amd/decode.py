@@ -32,8 +32,8 @@ from . import _lib
 from . import native_post as npost
 from ._lib import back_to_back, host_ptr as _hp, ptr as _ptr
 from .align import class_pairs
+from .options import DECODE_MODES  # noqa: F401  (decode.DECODE_MODES stays importable)
 
-DECODE_MODES = ("argmax", "viterbi")
 MAX_CLASSES = 1024         # wfl_decode's class cap (status 2 above it)
 MAX_BIGRAM_SYMBOLS = 192   # wfl_decode_bigram's symbol cap, O + 191 phonemes (WFL_DECODE_BIGRAM_MAX_SYMBOLS; status 2 above it)
 STATUS_OK, STATUS_OVER_CAP, STATUS_BAD_CLASS = 0, 2, 4
@@ -55,19 +55,6 @@ def class_table(label_list) -> ClassTable:
     b_only = {tag[2:]: c for c, tag in enumerate(label_list) if tag.startswith("B-") and tag[2:] not in both}
     pairs = sorted(list(both.values()) + [(c, -1) for c in b_only.values()])
     return ClassTable(label_list.index("O"), np.array(pairs, np.int32).reshape(-1, 2))
-
-
-def check_options(decode, switch_penalty):
-    """Validation shared by the Labeler, infer_audio / infer_folder and the CLI (None = not given)."""
-    if decode is not None and decode not in DECODE_MODES:
-        raise ValueError(f"decode must be one of {DECODE_MODES}, got {decode!r}")
-    if switch_penalty is not None:
-        try:
-            ok = float(switch_penalty) >= 0.0 and not isinstance(switch_penalty, bool)
-        except (TypeError, ValueError):
-            ok = False
-        if not ok:
-            raise ValueError(f"switch_penalty must be a number >= 0 (nats), got {switch_penalty!r}")
 
 
 def _workspace_bytes(symbol, n_frames, n_pairs) -> int:

@@ -7,6 +7,8 @@ batched loop over 30 s work items.
                                every clip <= 30 s and every 30 s chunk of a longer file is one batch row; rows of many
                                files share a forward; `lang_id=None` averages logits/offsets over all languages
                                inside the library (encoder runs once; infer.py:146-156, 266-276)
+  options.resolve              the post-processing options of a request (align, decode, the scores, the phone bigram): resolved
+                               once per request into a PostOptions record, and once before any model is loaded (options.py)
   deviations (documented in DESIGN.md): no `.wfl_cache` (infer.py:223-229), `--sample/--top-k/--top-p/--temperature`
   are validated but have no effect (their results are overwritten in the reference too, infer.py:283-297), a single
   file with `-o .` writes `<stem>.lab` instead of overwriting the input WAV (infer.py:410-411, utils.py:77), and
@@ -28,12 +30,11 @@ from . import audio as A
 from . import decode as DC
 from . import native_post as npost
 from . import postprocess as pp
+from .options import ALIGN_MODES, DECODE_MODES, PostOptions, resolve
 from .tagger import BIOPhonemeTagger, raise_on_status
 
 frame_duration = pp.FRAME_DURATION
 MAX_SEGMENT_DURATION = pp.MAX_SEGMENT_DURATION
-ALIGN_MODES = ("greedy", "viterbi")
-DECODE_MODES = ("argmax", "viterbi")
 CHUNK_SAMPLES = int(MAX_SEGMENT_DURATION * 16000)     # at 16 kHz; a Labeler's own work-item length is `chunk_samples` (its config's rate)
 
 
@@ -402,63 +403,10 @@ class Labeler:
 
         return self._label_rows(len(audio_paths), cap_in, fill, lang_id, threshold, lang_name, torch.int16, upload)
 
-    def align_mode(self, align=None) -> str:
-        """"greedy" (the reference's string match, the default) or "viterbi"; None: config postprocess.align, else greedy."""
-        mode = self.config.get("postprocess", {}).get("align", "greedy") if align is None else align
-        if mode not in ALIGN_MODES:
-            raise ValueError(f"align must be one of {ALIGN_MODES}, got {mode!r}")
-        return mode
-
-    def align_scores_on(self, align_scores=None, align=None) -> bool:
-        """Whether alignment scores are asked for (None: config postprocess.align_scores, else off).  They score a Viterbi
-        alignment: with align "greedy" the request is an error."""
-        on = bool(self.config.get("postprocess", {}).get("align_scores", False) if align_scores is None else align_scores)
-        if on and self.align_mode(align) != "viterbi":
-            raise ValueError("align_scores needs align='viterbi' (postprocess.align: viterbi): the greedy match has no lattice to score")
-        return on
-
-    def decode_scores_on(self, decode_scores=None, decode=None) -> bool:
-        """Whether decode scores are asked for (None: config postprocess.decode_scores, else off).  They score the grammar search's
-        path: with decode "argmax" the request is an error."""
-        on = bool(self.config.get("postprocess", {}).get("decode_scores", False) if decode_scores is None else decode_scores)
-        if on and self.decode_options(decode)[0] != "viterbi":
-            raise ValueError("decode_scores needs decode='viterbi' (postprocess.decode: viterbi): the argmax decode has no lattice to score")
-        return on
-
-    def decode_options(self, decode=None, switch_penalty=None):
-        """-> (mode, switch penalty in nats).  mode: "argmax" (the reference's free decode, the default) or "viterbi" (the BIO-grammar
-        search over the frame logits, decode.py); None: config postprocess.decode, else argmax.  switch_penalty: a number >= 0, used
-        with "viterbi" only; None: config postprocess.switch_penalty, else 0."""
-        from .decode import check_options
-        post = self.config.get("postprocess", {})
-        mode = post.get("decode", "argmax") if decode is None else decode
-        lam = post.get("switch_penalty", 0.0) if switch_penalty is None else switch_penalty
-        check_options(mode, lam)
-        return mode, float(lam)
-
-    def bigram_options(self, phoneme_bigram=None, bigram_weight=None, decode=None, decode_scores=None):
-        """-> (path of the phoneme bigram file or None, its weight).  None: config postprocess.phoneme_bigram /
-        postprocess.bigram_weight, else no bigram / 1.  Both belong to decode "viterbi" alone (ValueError otherwise); the weight is a
-        number >= 0; decode_scores with a bigram is refused: the posterior must score the grammar the search ran on, and the
-        forward-backward pass knows the flat switch penalty only."""
-        post = self.config.get("postprocess", {})
-        path = post.get("phoneme_bigram") if phoneme_bigram is None else phoneme_bigram
-        given = post.get("bigram_weight") if bigram_weight is None else bigram_weight
-        _check_bigram(self.decode_options(decode)[0], path, given)
-        if path and self.decode_scores_on(decode_scores, decode):
-            raise ValueError(BIGRAM_SCORES_ERROR)
-        return (str(path) if path else None), float(1.0 if given is None else given)
-
-    def bigram_scores_on(self, bigram_scores=None, phoneme_bigram=None, decode=None) -> bool:
-        """Whether the scores of a bigram decode are asked for (None: config postprocess.bigram_scores, else off): decode_scores'
-        records from a forward-backward pass over the grammar WITH the phone-bigram table (decode.decode_posteriors_bigram).  They
-        score the bigram search's path, so they need a phoneme_bigram and with it decode "viterbi" (ValueError otherwise)."""
-        post = self.config.get("postprocess", {})
-        on = bool(post.get("bigram_scores", False) if bigram_scores is None else bigram_scores)
-        if on:
-            _check_bigram_scores(self.decode_options(decode)[0], post.get("phoneme_bigram") if phoneme_bigram is None else phoneme_bigram,
-                                 True)
-        return on
+    def options(self, **given) -> PostOptions:
+        """The post-processing options of a request (options.resolve): an argument that is given wins, the others come from this
+        Labeler's config `postprocess` section, else the defaults; ValueError for a request the rules between them refuse."""
+        return resolve(self.config.get("postprocess"), **given)
 
     def _bigram_table(self, path, switch_penalty, weight):
         """The search's transition table for the bigram file `path` (absolute, or relative to the working directory)."""
@@ -506,30 +454,25 @@ class Labeler:
         decode -- the same scores[i] records, from a forward-backward pass over the grammar with the bigram's transition table
         (decode.decode_posteriors_bigram), so the posterior scores the grammar the search ran on.  The segments are the same with and
         without."""
-        final, scores = self._label_scored(audio_paths, lang_id, confidence_threshold, verbose, align, align_scores, decode,
-                                           switch_penalty, decode_scores, phoneme_bigram, bigram_weight, bigram_scores)
-        scored = self.align_scores_on(align_scores, align) or self.decode_scores_on(decode_scores, decode) \
-            or self.bigram_scores_on(bigram_scores, phoneme_bigram, decode)
-        return (final, scores) if scored else final
+        opts = self.options(align=align, align_scores=align_scores, decode=decode, switch_penalty=switch_penalty,
+                            decode_scores=decode_scores, phoneme_bigram=phoneme_bigram, bigram_weight=bigram_weight,
+                            bigram_scores=bigram_scores)
+        final, scores = self._label_scored(audio_paths, opts, lang_id, confidence_threshold, verbose)
+        return (final, scores) if opts.scored else final
 
-    def _label_scored(self, audio_paths, lang_id=None, confidence_threshold=0.0, verbose=True, align=None, align_scores=None,
-                      decode=None, switch_penalty=None, decode_scores=None, phoneme_bigram=None, bigram_weight=None, bigram_scores=None):
-        """label_files, always -> (segments, scores): the files are split once into those a transcript is Viterbi-aligned to, those the
-        grammar search decodes and those left to the argmax decode, and each subset's results go back to its files' places."""
-        want_scores = self.align_scores_on(align_scores, align)
-        mode, lam = self.decode_options(decode, switch_penalty)
-        want_free = self.decode_scores_on(decode_scores, decode)
-        bigram, bigram_w = self.bigram_options(phoneme_bigram, bigram_weight, decode, decode_scores)
-        want_free = self.bigram_scores_on(bigram_scores, phoneme_bigram, decode) or want_free
-        trans = self._bigram_table(bigram, lam, bigram_w) if bigram else None
-        if mode == "viterbi" and int(self.config["postprocess"].get("median_filter", 0)) > 1:
+    def _label_scored(self, audio_paths, opts, lang_id, confidence_threshold, verbose):
+        """label_files for the resolved options `opts`, always -> (segments, scores): the files are split once into those a transcript is
+        Viterbi-aligned to, those the grammar search decodes and those left to the argmax decode, and each subset's results go back to
+        its files' places."""
+        trans = self._bigram_table(opts.phoneme_bigram, opts.switch_penalty, opts.bigram_weight) if opts.phoneme_bigram else None
+        if opts.decode == "viterbi" and int(self.config["postprocess"].get("median_filter", 0)) > 1:
             print("decode: viterbi -- postprocess.median_filter is not applied (the switch penalty takes its place)")
         if lang_id is not None and self.lang2id and lang_id > max(self.lang2id.values()):
             raise ValueError(f"Error: Language ID ({lang_id}) is higher than the latest ID ({max(self.lang2id.values())}) "
                              f"of this model.\n Languages and Codes available: {self.lang2id}")
         final, scores = [None] * len(audio_paths), [None] * len(audio_paths)
         free, with_t = list(range(len(audio_paths))), []
-        if self.align_mode(align) == "viterbi":
+        if opts.align == "viterbi":
             forced = [_read_forced(p, verbose) for p in audio_paths]
             with_t = [fi for fi in free if forced[fi] is not None]
             free = [fi for fi in free if forced[fi] is None]
@@ -538,9 +481,10 @@ class Labeler:
             return [audio_paths[fi] for fi in idx]
 
         searched = {}
-        if mode == "viterbi":
+        if opts.decode == "viterbi":
             # the free decode by the grammar search; a file it could not decode (with a message) takes the argmax decode
-            got, free_scores = self._decode_viterbi(paths(free), lang_id, confidence_threshold, verbose, lam, want_free, trans)
+            got, free_scores = self._decode_viterbi(paths(free), lang_id, confidence_threshold, verbose, opts.switch_penalty,
+                                                    opts.free_scores, trans)
             searched = {free[j]: segs for j, segs in got.items()}
             for j, sc in free_scores.items():
                 scores[free[j]] = sc
@@ -550,7 +494,8 @@ class Labeler:
         for fi, segs in searched.items():
             final[fi] = self._match_forced(audio_paths[fi], segs, verbose)
         if with_t:
-            got = self._label_viterbi(paths(with_t), [forced[fi] for fi in with_t], lang_id, confidence_threshold, verbose, want_scores)
+            got = self._label_viterbi(paths(with_t), [forced[fi] for fi in with_t], lang_id, confidence_threshold, verbose,
+                                      opts.align_scores)
             for fi, segs, sc in zip(with_t, *got):
                 final[fi], scores[fi] = segs, sc
         return final, scores
@@ -763,11 +708,7 @@ class Labeler:
                 else:
                     d_logz, d_post, d_cls, d_pst = DC.decode_posteriors_bigram(lg, [frames[b] for b in ok], table, trans, threshold,
                                                                                d_ids, frame_offsets=f0[ok])
-                # (the files' sums of log-sum-exp, path_log_posterior's third term, which the ABI has no output for: one fp32
-                # reduction over the wave's logits, then differences of one running sum in double)
-                run = torch.cat([lg.new_zeros(1, dtype=torch.float64), torch.logsumexp(lg, dim=1).double().cumsum(0)])
-                ends = torch.from_numpy(f0[ok] + np.asarray(frames, np.int64)[ok]).to(lg.device)
-                d_lse = run[ends] - run[torch.from_numpy(f0[ok]).to(lg.device)]
+                d_lse = _clip_lse(lg, f0[ok], f0[ok] + np.asarray(frames, np.int64)[ok])
                 n_ok, nr = len(ok), lg.shape[0]
                 h = torch.cat([d_score[ok].double(), d_logz.double(), d_lse, d_pst.double(), d_post.double(), d_cls.double()]).cpu().numpy()
                 for j, b in enumerate(ok):                    # one copy
@@ -816,8 +757,7 @@ class Labeler:
             frames, lg = self._file_rows(rows, by_file, sel)
             d_logz, d_counts, d_st = DC.bigram_expected_counts(lg, frames, table, trans, confidence_threshold)
             f0 = np.concatenate([[0], np.cumsum(np.asarray(frames, np.int64))[:-1]])
-            run = torch.cat([lg.new_zeros(1, dtype=torch.float64), torch.logsumexp(lg, dim=1).double().cumsum(0)])
-            d_lse = run[torch.from_numpy(f0 + np.asarray(frames, np.int64)).to(lg.device)] - run[torch.from_numpy(f0).to(lg.device)]
+            d_lse = _clip_lse(lg, f0, f0 + np.asarray(frames, np.int64))
             h = torch.cat([d_logz.double(), d_lse, d_st.double()]).cpu().numpy()
             h_counts = d_counts.cpu().numpy()
             nb = len(sel)
@@ -919,6 +859,14 @@ class Labeler:
         return results, scores
 
 
+def _clip_lse(lg, starts, ends):
+    """Per clip the sum of the log-sum-exp of its frames' logits, frames [start, end) of `lg` (int64 host arrays) -> float64 on the
+    device: path_log_posterior's third term, which the ABI has no output for.  One fp32 reduction over the wave's logits, then
+    differences of one running sum in double."""
+    run = torch.cat([lg.new_zeros(1, dtype=torch.float64), torch.logsumexp(lg, dim=1).double().cumsum(0)])
+    return run[torch.from_numpy(ends).to(lg.device)] - run[torch.from_numpy(starts).to(lg.device)]
+
+
 def _read_forced(audio_path, verbose):
     """`{audio}.txt` forced phoneme list (infer.py:193, 210-215)."""
     txt = audio_path.replace(".wav", ".txt")
@@ -934,11 +882,6 @@ def _read_forced(audio_path, verbose):
 
 
 _LABELERS = {}
-
-
-def _check_align(align):
-    if align is not None and align not in ALIGN_MODES:
-        raise ValueError(f"align must be one of {ALIGN_MODES}, got {align!r}")
 
 
 def _labeler(config_path, checkpoint_path, device):
@@ -958,57 +901,12 @@ def _write_lab(path, segments):
     print(f"Predictions saved to: {path}")
 
 
-def _check_decode(decode, switch_penalty):
-    from .decode import check_options
-    check_options(decode, switch_penalty)
-
-
-BIGRAM_SCORES_ERROR = ("decode_scores cannot be combined with a phoneme bigram: the forward-backward pass scores the flat switch "
-                       "penalty, not the bigram the search ran on; ask for bigram_scores (postprocess.bigram_scores, --bigram-scores) "
-                       "instead, which scores the bigram's own grammar")
-
-
-def _check_bigram(decode, phoneme_bigram, bigram_weight):
-    """phoneme_bigram / bigram_weight (None = not given) belong to decode "viterbi"; the weight is a number >= 0."""
-    if bigram_weight is not None:
-        try:
-            ok = float(bigram_weight) >= 0.0 and not isinstance(bigram_weight, bool)
-        except (TypeError, ValueError):
-            ok = False
-        if not ok:
-            raise ValueError(f"bigram_weight must be a number >= 0, got {bigram_weight!r}")
-    if (phoneme_bigram or bigram_weight is not None) and decode != "viterbi":
-        raise ValueError("phoneme_bigram / bigram_weight need decode='viterbi' (postprocess.decode: viterbi): the argmax decode has no "
-                         "search to weigh")
-
-
-def _check_bigram_scores(decode, phoneme_bigram, bigram_scores, config_path=None):
-    """bigram_scores scores a bigram decode: it needs a phoneme_bigram and with it decode "viterbi".  What the arguments leave open
-    (None) is looked up in the config file, when one is named and exists, so that a request that cannot be met is refused before any
-    model is loaded."""
-    if not bigram_scores:
-        return
-    post = {}
-    if (decode is None or phoneme_bigram is None) and config_path is not None and os.path.isfile(str(config_path)):
-        post = (load_config(config_path) or {}).get("postprocess") or {}
-    decode = post.get("decode", "argmax") if decode is None else decode
-    phoneme_bigram = post.get("phoneme_bigram") if phoneme_bigram is None else phoneme_bigram
-    if decode != "viterbi":
-        raise ValueError("bigram_scores needs decode='viterbi' (postprocess.decode: viterbi) and a phoneme_bigram: the argmax decode "
-                         "has no lattice to score")
-    if not phoneme_bigram:
-        raise ValueError("bigram_scores needs a phoneme_bigram (postprocess.phoneme_bigram): it scores the bigram search's path; "
-                         "decode_scores scores a search under the flat switch penalty")
-
-
-def _check_align_scores(align, align_scores):
-    if align_scores and align == "greedy":
-        raise ValueError("align_scores needs align='viterbi': the greedy match has no lattice to score")
-
-
-def _check_decode_scores(decode, decode_scores):
-    if decode_scores and decode == "argmax":
-        raise ValueError("decode_scores needs decode='viterbi': the argmax decode has no lattice to score")
+def _refuse_before_load(config_path, **given):
+    """The refusal before any model is loaded: the request resolved against the `postprocess` section of the config file, when that
+    file exists ({} otherwise; such a call fails at the model load).  The options that labelling uses are the Labeler's own
+    (Labeler.options: a cached Labeler keeps the config it was loaded with)."""
+    cfg = load_config(config_path) if os.path.isfile(str(config_path)) else None
+    resolve((cfg or {}).get("postprocess"), **given)
 
 
 def _lab_int(t):
@@ -1105,18 +1003,11 @@ def infer_audio(audio_path, config_path="config.yaml", checkpoint_path="best_mod
     bigram_weight (decode viterbi only; None: config postprocess.phoneme_bigram / postprocess.bigram_weight): the phone-bigram prior
     of the search (Labeler.label_files).  bigram_scores (with a phoneme_bigram only; None: config postprocess.bigram_scores):
     decode_scores for a bigram decode, the same `{stem}.decode_scores.tsv`."""
-    _check_align(align)
-    _check_align_scores(align, align_scores)
-    _check_decode(decode, switch_penalty)
-    _check_decode_scores(decode, decode_scores)
-    if decode is not None:
-        _check_bigram(decode, phoneme_bigram, bigram_weight)
-    _check_bigram_scores(decode, phoneme_bigram, bigram_scores, config_path)
+    given = dict(align=align, align_scores=align_scores, decode=decode, switch_penalty=switch_penalty, decode_scores=decode_scores,
+                 phoneme_bigram=phoneme_bigram, bigram_weight=bigram_weight, bigram_scores=bigram_scores)
+    _refuse_before_load(config_path, **given)
     lab = _labeler(config_path, checkpoint_path, device)
-    (segments,), (score,) = lab._label_scored([audio_path], lang_id=lang_id, confidence_threshold=confidence_threshold, align=align,
-                                              align_scores=align_scores, decode=decode, switch_penalty=switch_penalty,
-                                              decode_scores=decode_scores, phoneme_bigram=phoneme_bigram, bigram_weight=bigram_weight,
-                                              bigram_scores=bigram_scores)
+    (segments,), (score,) = lab._label_scored([audio_path], lab.options(**given), lang_id, confidence_threshold, True)
     if output_lab_path:
         if os.path.abspath(output_lab_path) == os.path.abspath(audio_path):
             # the reference would truncate the input WAV here (infer.py:410-411 + utils.py:77)
@@ -1130,13 +1021,9 @@ def infer_folder(folder_path: str, config_path: str = "config.yaml", checkpoint_
                  output_dir: str = "outputs", device: str = "cuda", lang_id: int = None, sample=False, top_k=0, top_p=0.0,
                  temperature=1.0, confidence_threshold=0.0, align=None, align_scores=None, decode=None, switch_penalty=None,
                  decode_scores=None, phoneme_bigram=None, bigram_weight=None, bigram_scores=None):
-    _check_align(align)
-    _check_align_scores(align, align_scores)
-    _check_decode(decode, switch_penalty)
-    _check_decode_scores(decode, decode_scores)
-    if decode is not None:
-        _check_bigram(decode, phoneme_bigram, bigram_weight)
-    _check_bigram_scores(decode, phoneme_bigram, bigram_scores, config_path)
+    given = dict(align=align, align_scores=align_scores, decode=decode, switch_penalty=switch_penalty, decode_scores=decode_scores,
+                 phoneme_bigram=phoneme_bigram, bigram_weight=bigram_weight, bigram_scores=bigram_scores)
+    _refuse_before_load(config_path, **given)
     wav_files = sorted(f for f in os.listdir(folder_path) if f.lower().endswith(".wav"))
     os.makedirs(output_dir, exist_ok=True)
     # one process per GPU: every rank labels its own share of the files and writes its own .lab files (no collective)
@@ -1147,14 +1034,8 @@ def infer_folder(folder_path: str, config_path: str = "config.yaml", checkpoint_
         wav_files = [wav_files[i] for i in shard_items(sizes, world)[rank]]
     lab = _labeler(config_path, checkpoint_path, device)
     paths = [os.path.join(folder_path, f) for f in wav_files]
-    want_scores = lab.align_scores_on(align_scores, align)
-    want_free = lab.decode_scores_on(decode_scores, decode)
-    lab.bigram_options(phoneme_bigram, bigram_weight, decode, decode_scores)
-    want_free = lab.bigram_scores_on(bigram_scores, phoneme_bigram, decode) or want_free
-    all_segments, all_scores = lab._label_scored(paths, lang_id=lang_id, confidence_threshold=confidence_threshold, align=align,
-                                                 align_scores=align_scores, decode=decode, switch_penalty=switch_penalty,
-                                                 decode_scores=decode_scores, phoneme_bigram=phoneme_bigram,
-                                                 bigram_weight=bigram_weight, bigram_scores=bigram_scores) if paths else ([], [])
+    opts = lab.options(**given)
+    all_segments, all_scores = lab._label_scored(paths, opts, lang_id, confidence_threshold, True) if paths else ([], [])
     for wav_file, segments, score in zip(wav_files, all_segments, all_scores):
         print(f"\nInferencing: {wav_file}")
         lab_path = os.path.join(output_dir, os.path.splitext(wav_file)[0] + ".lab")
@@ -1163,11 +1044,11 @@ def infer_folder(folder_path: str, config_path: str = "config.yaml", checkpoint_
         print("Predicted segments:")
         for start, end, ph in segments:
             print(f"({round(start, 2)}, {round(end, 2)}, {ph})")
-    if want_scores:
+    if opts.align_scores:
         name = "alignment_scores.tsv" if world == 1 else f"alignment_scores.rank{rank}.tsv"
         _write_text(os.path.join(output_dir, name),
                     format_review_tsv([(f, sc) for f, sc in zip(wav_files, all_scores) if isinstance(sc, AL.FileScore)]), "Review list")
-    if want_free:
+    if opts.free_scores:
         name = "decode_scores.tsv" if world == 1 else f"decode_scores.rank{rank}.tsv"
         _write_text(os.path.join(output_dir, name),
                     format_decode_review_tsv([(f, sc) for f, sc in zip(wav_files, all_scores) if isinstance(sc, DC.FreeScore)]),
@@ -1249,40 +1130,12 @@ def main(argv=None):
         cfg = load_config(Path(config))
         if confidence_threshold is None:
             confidence_threshold = cfg["postprocess"].get("confidence_threshold", 0.0)
-        if align is None:
-            align = cfg["postprocess"].get("align", "greedy")
-        if align_scores is None:
-            align_scores = bool(cfg["postprocess"].get("align_scores", False))
-        if align_scores and align != "viterbi":
-            raise click.UsageError("--align-scores (postprocess.align_scores) needs --align viterbi")
-        if decode is None:
-            decode = cfg["postprocess"].get("decode", "argmax")
-        if switch_penalty is None:
-            switch_penalty = cfg["postprocess"].get("switch_penalty", 0.0)
         try:
-            _check_decode(decode, switch_penalty)
+            opts = resolve(cfg["postprocess"], align=align, align_scores=align_scores, decode=decode, switch_penalty=switch_penalty,
+                           decode_scores=decode_scores, phoneme_bigram=phoneme_bigram, bigram_weight=bigram_weight,
+                           bigram_scores=bigram_scores)
         except ValueError as err:
-            raise click.UsageError(f"postprocess.decode / postprocess.switch_penalty: {err}")
-        if decode_scores is None:
-            decode_scores = bool(cfg["postprocess"].get("decode_scores", False))
-        if decode_scores and decode != "viterbi":
-            raise click.UsageError("--decode-scores (postprocess.decode_scores) needs --decode viterbi")
-        if phoneme_bigram is None:
-            phoneme_bigram = cfg["postprocess"].get("phoneme_bigram")
-        if bigram_weight is None:
-            bigram_weight = cfg["postprocess"].get("bigram_weight")
-        try:
-            _check_bigram(decode, phoneme_bigram, bigram_weight)
-        except ValueError as err:
-            raise click.UsageError(f"--phoneme-bigram / --bigram-weight (postprocess.phoneme_bigram, postprocess.bigram_weight): {err}")
-        if phoneme_bigram and decode_scores:
-            raise click.UsageError(BIGRAM_SCORES_ERROR)
-        if bigram_scores is None:
-            bigram_scores = bool(cfg["postprocess"].get("bigram_scores", False))
-        try:
-            _check_bigram_scores(decode, phoneme_bigram or "", bigram_scores)
-        except ValueError as err:
-            raise click.UsageError(f"--bigram-scores (postprocess.bigram_scores): {err}")
+            raise click.UsageError(str(err))
         output_path = inf_path if output == "." else output
         if not inf_path.exists():
             print(f"Unable to locate folder {str(inf_path)}")
@@ -1290,9 +1143,13 @@ def main(argv=None):
         if lang_id is not None and lang_id <= -1:
             lang_id = None
         kw = dict(config_path=str(config), checkpoint_path=str(checkpoint), device=device, lang_id=lang_id, sample=sample,
-                  top_k=top_k, top_p=top_p, temperature=temperature, confidence_threshold=confidence_threshold, align=align,
-                  align_scores=align_scores, decode=decode, switch_penalty=switch_penalty, decode_scores=decode_scores,
-                  phoneme_bigram=phoneme_bigram, bigram_weight=bigram_weight, bigram_scores=bigram_scores)
+                  top_k=top_k, top_p=top_p, temperature=temperature, confidence_threshold=confidence_threshold, align=opts.align,
+                  align_scores=opts.align_scores, decode=opts.decode, switch_penalty=opts.switch_penalty,
+                  decode_scores=opts.decode_scores, bigram_scores=opts.bigram_scores,
+                  # an argument that is given wins over the config, so "no bigram" travels as an empty path, and a weight only beside
+                  # the search it belongs to (with another decode none was given, or resolve had refused it)
+                  phoneme_bigram=opts.phoneme_bigram or "",
+                  bigram_weight=opts.bigram_weight if opts.decode == "viterbi" else None)
         if inf_path.is_dir():
             infer_folder(folder_path=str(inf_path), output_dir=str(output_path), **kw)
         else:

@@ -1,0 +1,103 @@
+"""The post-processing options of a labelling request, resolved once: argument, else the config's `postprocess.<key>`, else the
+default, then the rules between the options, in one fixed order with one message each.  Pure Python: the Labeler, infer_audio /
+infer_folder (before any model is loaded) and the CLI all call `resolve` and carry the `PostOptions` record it returns.
+
+  option          default   rule (checked in this order; the first broken one is reported)
+  align           greedy    1. one of ALIGN_MODES
+  align_scores    off       2. needs align viterbi
+  decode          argmax    3. one of DECODE_MODES
+  switch_penalty  0         4. a number >= 0 (no bool, no NaN, no string that is not a number)
+  decode_scores   off       5. needs decode viterbi
+  bigram_weight   1         6. when given, a number >= 0 (no bool)
+  phoneme_bigram  none      7. a phoneme_bigram or a given bigram_weight needs decode viterbi
+                            8. decode_scores with a phoneme_bigram is refused (BIGRAM_SCORES_ERROR): a posterior must score the
+                               grammar its search ran on, and decode_scores' pass knows the flat switch penalty only
+  bigram_scores   off       9. needs decode viterbi, and then a phoneme_bigram
+"""
+from __future__ import annotations
+
+from typing import NamedTuple, Optional
+
+ALIGN_MODES = ("greedy", "viterbi")
+DECODE_MODES = ("argmax", "viterbi")
+
+BIGRAM_SCORES_ERROR = ("decode_scores cannot be combined with a phoneme bigram: the forward-backward pass scores the flat switch "
+                       "penalty, not the bigram the search ran on; ask for bigram_scores (postprocess.bigram_scores, --bigram-scores) "
+                       "instead, which scores the bigram's own grammar")
+
+
+class PostOptions(NamedTuple):
+    align: str = "greedy"
+    align_scores: bool = False
+    decode: str = "argmax"
+    switch_penalty: float = 0.0               # nats per opened run (decode viterbi)
+    decode_scores: bool = False
+    phoneme_bigram: Optional[str] = None      # path of a phoneme_bigram.json; an empty path is None
+    bigram_weight: float = 1.0                # (1.0 also stands for "not given")
+    bigram_scores: bool = False
+
+    @property
+    def free_scores(self) -> bool:
+        """Scores of the grammar search's path are asked for, of either kind."""
+        return self.decode_scores or self.bigram_scores
+
+    @property
+    def scored(self) -> bool:
+        return self.align_scores or self.free_scores
+
+
+def _number_ge0(x):
+    """float(x) for a number >= 0; None for anything else (a bool, a NaN, a negative, a string that is no number)."""
+    try:
+        v = float(x)
+    except (TypeError, ValueError):
+        return None
+    return v if v >= 0.0 and not isinstance(x, bool) else None
+
+
+def resolve(post, *, align=None, align_scores=None, decode=None, switch_penalty=None, decode_scores=None, phoneme_bigram=None,
+            bigram_weight=None, bigram_scores=None) -> PostOptions:
+    """post: the config's `postprocess` mapping (None: {}).  Per option the argument wins; None leaves it to `post[<option>]`, and a
+    key that is absent (or None) to the default.  -> PostOptions, or ValueError for the first broken rule of the module's table."""
+    post = post or {}
+
+    def pick(key, arg, default=None):
+        if arg is None:
+            arg = post.get(key)
+        return default if arg is None else arg
+
+    align = pick("align", align, "greedy")
+    if align not in ALIGN_MODES:
+        raise ValueError(f"align must be one of {ALIGN_MODES}, got {align!r}")
+    align_scores = bool(pick("align_scores", align_scores, False))
+    if align_scores and align != "viterbi":
+        raise ValueError("align_scores needs align='viterbi' (postprocess.align: viterbi): the greedy match has no lattice to score")
+    decode = pick("decode", decode, "argmax")
+    if decode not in DECODE_MODES:
+        raise ValueError(f"decode must be one of {DECODE_MODES}, got {decode!r}")
+    given = pick("switch_penalty", switch_penalty, 0.0)
+    switch_penalty = _number_ge0(given)
+    if switch_penalty is None:
+        raise ValueError(f"switch_penalty must be a number >= 0 (nats), got {given!r}")
+    decode_scores = bool(pick("decode_scores", decode_scores, False))
+    if decode_scores and decode != "viterbi":
+        raise ValueError("decode_scores needs decode='viterbi' (postprocess.decode: viterbi): the argmax decode has no lattice to score")
+    given = pick("bigram_weight", bigram_weight)
+    bigram_weight = 1.0 if given is None else _number_ge0(given)
+    if bigram_weight is None:
+        raise ValueError(f"bigram_weight must be a number >= 0, got {given!r}")
+    phoneme_bigram = pick("phoneme_bigram", phoneme_bigram)
+    phoneme_bigram = str(phoneme_bigram) if phoneme_bigram else None
+    if (phoneme_bigram or given is not None) and decode != "viterbi":
+        raise ValueError("phoneme_bigram / bigram_weight need decode='viterbi' (postprocess.decode: viterbi): the argmax decode has no "
+                         "search to weigh")
+    if phoneme_bigram and decode_scores:
+        raise ValueError(BIGRAM_SCORES_ERROR)
+    bigram_scores = bool(pick("bigram_scores", bigram_scores, False))
+    if bigram_scores and decode != "viterbi":
+        raise ValueError("bigram_scores needs decode='viterbi' (postprocess.decode: viterbi) and a phoneme_bigram: the argmax decode "
+                         "has no lattice to score")
+    if bigram_scores and not phoneme_bigram:
+        raise ValueError("bigram_scores needs a phoneme_bigram (postprocess.phoneme_bigram): it scores the bigram search's path; "
+                         "decode_scores scores a search under the flat switch penalty")
+    return PostOptions(align, align_scores, decode, switch_penalty, decode_scores, phoneme_bigram, bigram_weight, bigram_scores)
