@@ -1064,8 +1064,20 @@ static int check_device(const wfl_model* m, const char* who) {
 // ------------------------------------------------------------------------------------------------ workspace plan
 namespace {
 
-// The bf16 activation buffers "model.precision: high" keeps a low half of (Runner::lo_ok, lo_idx)
+// The bf16 activation buffers of the workspace: frame rows [lead | B clips of P rows, the first T of each its frames | tail].
+// make_plan declares each of them once, as an ActBuf of Plan::bufs; the Runner reads offsets, geometry and low halves from there.
 enum Buf { BUF_X, BUF_Y, BUF_ATT, BUF_QK, BUF_FF, BUF_MEL, BUF_C1, BUF_ENC2, BUF_QKP, BUF_ATTP, BUF_FA, BUF_FB, BUF_XG, BUF_COUNT };
+
+struct ActBuf {
+  long off, bytes;      // 0 bytes: not allocated for this model
+  int width;            // elements per row
+  int lead, P, T;       // row geometry (FA / FB: of level 0 / level 1, the first level each of them holds)
+  long tail;            // rows behind the last clip's pitch that the halo kernel clears
+  long lo;              // byte offset of the low half, -1: none.  Default mode: X and Y have one (the residual stream, GemmArgs::res_lo);
+                        // "model.precision: high": every buffer, lo_delta bytes further on
+  long span;            // a pointer less than `span` bytes behind `off` names this buffer (Runner::lo_idx).  Default mode: one row of
+                        // X / Y, i.e. a column offset is allowed and a row offset is not; precision high: the whole buffer
+};
 
 struct Plan {
   int B, L, T, P, lead, tail;
@@ -1075,15 +1087,15 @@ struct Plan {
   // wavlm feature-encoder levels: level i = output of conv layer i (frames T_i, pitch P_i = P * 2^(n-1-i), lead 8)
   int nlev, Tl[8], Pl[8], leadl[8];
   long Rl[8];
-  // byte offsets
-  long mel, c1, X, Y, ATT, QK, FF, stats, raw, clipmax, logits, logits2, offs2, gx, lstm_x, enc2;
-  long FA, FB, XG, gate, rtab, wstats, cstats, cpart, err, Xlo, Ylo, QKp, ATTp, clipT, total;
+  ActBuf bufs[BUF_COUNT];
+  // byte offsets of the single-use slots
+  long stats, raw, clipmax, logits, logits2, offs2, gx, lstm_x;
+  long gate, rtab, wstats, cstats, cpart, err, clipT, total;
   long X8, FF8, rs8;            // fp8 activations (fp8_weights models): e4m3 rows [R][d], [R][ffw], fp32 row scales [R]
   long X8lo, FF8lo;             //   and their lo planes (e4m3 pairs, gemm_mx.hip)
   long lo_delta, hp32;          // "model.precision: high": every activation buffer has its low half lo_delta bytes further on (a twin of
   long hp32_floats;             //   the whole activation area); hp32 = the fp32 sums of the three passes, [rows][columns]
   int da;                       // Conformer attention width (wfl_model::conf_da); QKp / ATTp exist when it differs from d
-  long buf_off[BUF_COUNT], buf_bytes[BUF_COUNT];   // where make_plan put each of them; 0 bytes: not allocated for this model
 };
 
 static int wavlm_frames(const wfl_arch& a, int L) {
@@ -1113,11 +1125,15 @@ static Plan make_plan(const wfl_model* m, int B, int L, int T_frames = 0) {
   p.ffw = std::max(a.enc_ffn, a.d_model * std::max(a.conformer_ff_expansion, 1));
   long off = 0;
   auto take = [&](long bytes) { long o = off; off = round_up(off + bytes, 256); return o; };
-  auto take_buf = [&](Buf b, long bytes) { p.buf_bytes[b] = bytes; return p.buf_off[b] = take(bytes); };
+  // the only writer of Plan::bufs: one call per buffer, in allocation order (lo and span follow below, once the low halves are placed)
+  auto take_buf = [&](Buf b, long bytes, int width, int lead, int P, int T, long tail) {
+    p.bufs[b] = {take(bytes), bytes, width, lead, P, T, tail, -1, 0};
+  };
+  auto take_rows = [&](Buf b, int width) { take_buf(b, p.R * width * 2, width, p.lead, p.P, p.T, p.tail); };   // the main geometry
   if (T_frames > 0) {
   } else if (whisper) {
-    p.mel = take_buf(BUF_MEL, p.R2 * a.n_mels * 2 + 1024);
-    p.c1 = take_buf(BUF_C1, p.R2 * p.d * 2);
+    take_buf(BUF_MEL, p.R2 * a.n_mels * 2 + 1024, a.n_mels, p.lead2, p.P2, p.T2, 2 * p.tail);
+    take_buf(BUF_C1, p.R2 * p.d * 2, p.d, p.lead2, p.P2, p.T2, 2 * p.tail);
     p.raw = take((long)B * p.T2 * a.n_mels * 4);
   } else if (none) {
     p.raw = take((long)B * p.T * a.n_mels * 4);        // the mel power = the hidden states, fp32 [B][T][n_mels]
@@ -1134,26 +1150,26 @@ static Plan make_plan(const wfl_model* m, int B, int L, int T_frames = 0) {
       p.leadl[i] = i == n - 1 ? p.lead : 8;
       p.Rl[i] = p.leadl[i] + (long)B * p.Pl[i] + p.tail;
     }
-    p.FA = take_buf(BUF_FA, p.Rl[0] * C * 2);                     // levels 0, 2, 4, 6
-    p.FB = take_buf(BUF_FB, p.Rl[1] * C * 2);                     // levels 1, 3, 5
-    p.XG = take_buf(BUF_XG, (long)a.wavlm_pos_conv_groups * p.R * 64 * 2);
+    take_buf(BUF_FA, p.Rl[0] * C * 2, C, p.leadl[0], p.Pl[0], p.Tl[0], p.tail);   // levels 0, 2, 4, 6
+    take_buf(BUF_FB, p.Rl[1] * C * 2, C, p.leadl[1], p.Pl[1], p.Tl[1], p.tail);   // levels 1, 3, 5
+    take_buf(BUF_XG, (long)a.wavlm_pos_conv_groups * p.R * 64 * 2, 64, p.lead, p.P, p.T, p.tail);   // per group: R rows of 64 channels
     p.gate = take((long)B * a.enc_heads * p.T * 4);
     p.rtab = take((long)a.enc_heads * (2L * p.T + 1) * 4);
     p.wstats = take((long)B * 2 * 8);
     p.cstats = take((long)B * C * 2 * 8);
     p.cpart = take(a.wavlm_group_norm ? (long)B * ((p.Tl[0] + 511) / 512) * C * 2 * 4 : 16);   // GroupNorm partials per 512-step block
   }
-  p.X = take_buf(BUF_X, p.R * p.d * 2);
-  p.Y = take_buf(BUF_Y, p.R * p.d * 2);
-  p.Xlo = take(p.R * p.d * 2);                          // low halves of the residual stream (GemmArgs::res_lo)
-  p.Ylo = take(p.R * p.d * 2);
-  p.ATT = take_buf(BUF_ATT, p.R * p.d * 2);
-  p.QK = take_buf(BUF_QK, p.R * 3 * p.d * 2);                   // packed q | k | v rows
-  p.FF = take_buf(BUF_FF, p.R * p.ffw * 2);
+  take_rows(BUF_X, p.d);
+  take_rows(BUF_Y, p.d);
+  const long Xlo = take(p.R * p.d * 2);                 // low halves of the residual stream (GemmArgs::res_lo)
+  const long Ylo = take(p.R * p.d * 2);
+  take_rows(BUF_ATT, p.d);
+  take_rows(BUF_QK, 3 * p.d);                           // packed q | k | v rows
+  take_rows(BUF_FF, p.ffw);
   p.da = m->conf_da > 0 ? m->conf_da : p.d;
   if (p.da != p.d) {
-    p.QKp = take_buf(BUF_QKP, p.R * 3 * p.da * 2);
-    p.ATTp = take_buf(BUF_ATTP, p.R * p.da * 2);
+    take_rows(BUF_QKP, 3 * p.da);
+    take_rows(BUF_ATTP, p.da);
   }
   if (a.fp8_weights && T_frames <= 0) {
     p.X8 = take(p.R * (long)p.d);
@@ -1163,7 +1179,7 @@ static Plan make_plan(const wfl_model* m, int B, int L, int T_frames = 0) {
     p.FF8lo = take(p.R * (long)p.ffw);
   }
   p.stats = take(p.R * 4L * 2 * 4);                     // per row, per 256-column tile (<= 4): (sum, sum of squares)
-  p.enc2 = take_buf(BUF_ENC2, p.R * p.d * 2);
+  take_rows(BUF_ENC2, p.d);
   p.clipmax = take((long)B * 4);
   p.logits = take((long)B * p.T * round_up(a.num_classes, 4) * 4);      // (rows of a multiple of four floats when the caller does not ask for them)
   p.logits2 = take((long)B * p.T * a.num_classes * 4);
@@ -1183,6 +1199,12 @@ static Plan make_plan(const wfl_model* m, int B, int L, int T_frames = 0) {
     const long cols = std::max<long>(std::max<long>(3L * std::max(p.d, p.da), 2L * p.ffw), 1024);
     p.hp32_floats = rows * cols;
     p.hp32 = take(p.hp32_floats * 4);
+    for (ActBuf& b : p.bufs)
+      if (b.bytes) { b.lo = b.off + p.lo_delta; b.span = b.bytes; }
+  } else {
+    p.bufs[BUF_X].lo = Xlo;
+    p.bufs[BUF_Y].lo = Ylo;
+    p.bufs[BUF_X].span = p.bufs[BUF_Y].span = (long)p.d * 2;
   }
   p.total = off;
   return p;
@@ -1250,7 +1272,10 @@ struct Runner {
   hipStream_t s;
   int rc = 0;
 
-  bf16_t* buf(long off) const { return (bf16_t*)(ws + off); }
+  bf16_t* act(Buf b) const { return (bf16_t*)(ws + p.bufs[b].off); }
+  // the first frame row of rows `width` elements wide in the main geometry / of a buffer in its own
+  template <class T> T* rows(T* ptr, long width) const { return ptr + (long)p.lead * width; }
+  bf16_t* rows(Buf b) const { return act(b) + (long)p.bufs[b].lead * p.bufs[b].width; }
   // Ragged batches (WavLM / mel front-ends with per-clip lengths): clipT = [B] frames of every clip at the encoder's rate,
   // levelT[i] = the same at level i of the WavLM conv stack (both in the workspace, written by clip_frames_kernel); null otherwise.
   // Every kernel that stores frame rows skips rows t >= clipT[b]; the shared buffers are zeroed whole at the start of the forward,
@@ -1266,26 +1291,21 @@ struct Runner {
   // Residual stream hi + lo (common.h, GemmArgs::res_lo): X and Y have low halves; lo_ok says whether the low half of the
   // tensor currently held in X / Y is valid (a kernel that writes only the high half invalidates it).
   // "model.precision: high" (precise.hip): EVERY activation buffer has a low half, lo_delta bytes further on, and lo_ok tracks the
-  // buffers whose producer wrote it (one flag per Buf; any pointer inside the buffer counts)
+  // buffers whose producer wrote it (one flag per Buf).  Which pointers name a buffer, and where its low half lies: ActBuf::span, lo
   bool precise() const { return m->a.precision != 0 && p.lo_delta > 0; }
   bool lo_ok[BUF_COUNT] = {};
-  int lo_idx(const void* ptr) const {               // the buffer `ptr` lies in, or -1
+  int lo_idx(const void* ptr) const {               // the buffer `ptr` names, or -1 (a buffer without a low half has no span)
     const long o = (const char*)ptr - ws;
-    // default mode: only X and Y have low halves, and only a pointer inside their first row (a column offset is allowed) names them
-    const int n = precise() ? BUF_COUNT : BUF_Y + 1;
-    for (int i = 0; i < n; ++i) {
-      const long bytes = precise() ? p.buf_bytes[i] : (long)p.d * 2;
-      if (o >= p.buf_off[i] && o < p.buf_off[i] + bytes) return i;
-    }
+    for (int i = 0; i < BUF_COUNT; ++i)
+      if (o >= p.bufs[i].off && o < p.bufs[i].off + p.bufs[i].span) return i;
     return -1;
   }
   bf16_t* lo_of(const void* ptr) const {
     const int i = lo_idx(ptr);
-    if (i < 0) return nullptr;
-    if (precise()) return (bf16_t*)((char*)ptr + p.lo_delta);
-    return (bf16_t*)(ws + (i == BUF_X ? p.Xlo : p.Ylo) + ((const char*)ptr - (ws + (i == BUF_X ? p.X : p.Y))));
+    return i < 0 ? nullptr : (bf16_t*)((char*)ptr + (p.bufs[i].lo - p.bufs[i].off));
   }
   const bf16_t* lo_in(const void* ptr) const { const int i = lo_idx(ptr); return (i >= 0 && lo_ok[i]) ? lo_of(ptr) : nullptr; }
+  void mark_lo(const void* ptr, bool valid) { const int i = lo_idx(ptr); if (i >= 0) lo_ok[i] = valid; }   // the producer of `ptr` did / did not write its low half
   // LayerNorm statistics left behind by the last residual GEMM (gemm_stream.hip, STATS): valid for the rows of `stats_for`
   const void* stats_for = nullptr;
   int stats_nsl = 0;
@@ -1345,7 +1365,7 @@ struct Runner {
     }
     if (!o.out_f32 && !o.glu && (o.res || o.lo_out)) g.c_lo = lo_of(c.C);
     if (o.res) g.res_lo = lo_in(o.res);
-    { const int ci = o.out_f32 ? -1 : lo_idx(c.C); if (ci >= 0) lo_ok[ci] = g.c_lo != nullptr; }
+    if (!o.out_f32) mark_lo(c.C, g.c_lo != nullptr);
     if (c.C == stats_for) stats_for = nullptr;                     // the rows they describe are being overwritten
     // want_stats is a request: a launch that cannot emit the statistics runs without them, and the consumer's LayerNorm stays a kernel
     if (o.want_stats && o.res && !o.out_f32 && !o.glu && o.act == WFL_ACT_NONE && c.ldc == p.d && W.n_valid == p.d && c.c_lead == p.lead &&
@@ -1383,7 +1403,7 @@ struct Runner {
       // the table as a pair; any other kernel would drop the low half, so those shapes keep the three-launch form below
       if (o.pos) g.pos_lo = (o.pos == m->pos) ? m->pos_lo : nullptr;
       if (!o.pos || (pos_fused && g.pos_lo && !o.glu && wfl_gemm256_tri_takes(g) && !wfl_gemm_stream_takes(g))) {
-        { const int ci = lo_idx(C); if (ci >= 0) lo_ok[ci] = true; }
+        mark_lo(C, true);
         launch_timed(g, 3.0 * 2.0 * (double)B * r.T * (double)W.n_valid * (double)W.K, "precision high, one-launch form: ");
         return;
       }
@@ -1407,7 +1427,7 @@ struct Runner {
     f.res = o.res; f.res_lo = o.res ? lo_in(o.res) : nullptr; f.ldres = o.ldres;
     f.out = (bf16_t*)C; f.out_lo = lo_of(C); f.ldc = c.ldc; f.c_lead = c.c_lead; f.c_pitch = c.c_pitch;
     f.clip_T = clip_T_for(r.P);
-    { const int ci = lo_idx(C); if (ci >= 0) lo_ok[ci] = f.out_lo != nullptr; }
+    mark_lo(C, f.out_lo != nullptr);
     if (f.n_out % 8) { rc = fail(-1, "precision high: output width must be a multiple of 8"); return; }
     const int e = wfl_launch_precise_finish(f, s);
     if (e) rc = fail(e, "precise_finish launch failed");
@@ -1432,12 +1452,12 @@ struct Runner {
       g.M = M; g.N = folded.N; g.K = folded.K; g.cin = folded.K; g.n_valid = folded.n_valid; g.act = act; g.ln_s = folded.ln_s;
       if (mode == 1) { g.stats_in = (const float*)(ws + p.stats); g.stats_nsl = stats_nsl; }
       if (wfl_gemm_stream_takes(g)) {
-        gemm(x + (long)p.lead * p.d, p.d, folded, {M, p.P, p.T}, out(C, ldc), {.act = act, .stats_in = mode == 1});
+        gemm(rows(x, p.d), p.d, folded, {M, p.P, p.T}, out(C, ldc), {.act = act, .stats_in = mode == 1});
         return;
       }
     }
     ln(x, scratch, w);
-    gemm(scratch + (long)p.lead * p.d, p.d, plain, {M, p.P, p.T}, out(C, ldc), {.act = act});
+    gemm(rows(scratch, p.d), p.d, plain, {M, p.P, p.T}, out(C, ldc), {.act = act});
   }
 
   // lo_out: the output is (or may become) a residual-stream tensor -- keep its low half; the input's low half is read when valid
@@ -1446,7 +1466,7 @@ struct Runner {
     if (y == stats_for) stats_for = nullptr;
     const bf16_t* x_lo = lo_in(x);
     bf16_t* y_lo = (lo_out || precise()) ? lo_of(y) : nullptr;
-    { const int yi = lo_idx(y); if (yi >= 0) lo_ok[yi] = y_lo != nullptr; }
+    mark_lo(y, y_lo != nullptr);
     prof_begin();
     const int r = wfl_launch_layernorm_act(x, p.d, y, p.d, w.g, w.b, 1e-5f, p.lead, p.B, p.P, p.T, p.d, 0, s, x_lo, y_lo, m->dv, clipT);
     prof_end(PROF_LAYERNORM, 0.0);
@@ -1495,18 +1515,17 @@ struct Runner {
     a.bias = bias; a.gate = gate;
     a.O8 = o8; a.O8_lo = o8_lo; a.ldo8 = ldo8; a.o8_scale = o8_scale;
     a.err = (unsigned*)(ws + p.err);
+    bf16_t* ctx = act(padded ? BUF_ATTP : BUF_ATT);
     if (precise() && !o8) {                               // the context's low half for the out-projection's third pass
-      bf16_t* o_hi = buf(padded ? p.ATTp : p.ATT);
-      a.O_lo = lo_of(o_hi);
-      const int oi = lo_idx(o_hi);
-      if (oi >= 0) lo_ok[oi] = a.O_lo != nullptr;
+      a.O_lo = lo_of(ctx);
+      mark_lo(ctx, a.O_lo != nullptr);
     }
     const int w = padded ? p.da : p.d;
-    bf16_t* qk = buf(padded ? p.QKp : p.QK);
+    bf16_t* qk = act(padded ? BUF_QKP : BUF_QK);
     static const bool split_attn = std::getenv("WFL_SPLIT_ATTN") == nullptr;       // (set to anything: bf16 q, k, v, P in precision high -- A/B runs)
     if (precise() && !o8 && split_attn)
       if (const bf16_t* ql = lo_in(qk)) { a.QK_lo = ql; a.V_lo = ql + 2 * w; }     // q | k | v as hi + lo (their projection wrote both halves)
-    a.QK = qk; a.ldqk = 3 * w; a.lead = p.lead; a.V = qk + 2 * w; a.ldv = 3 * w; a.O = buf(padded ? p.ATTp : p.ATT); a.ldo = w;
+    a.QK = qk; a.ldqk = 3 * w; a.lead = p.lead; a.V = qk + 2 * w; a.ldv = 3 * w; a.O = ctx; a.ldo = w;
     a.B = p.B; a.T = p.T; a.P = p.P; a.heads = heads; a.d = w;
     a.clip_T = clipT;
     prof_begin();
@@ -1516,10 +1535,11 @@ struct Runner {
   }
 
   ZeroMulti zm{};
-  void zero_add(long off, long ld_elems, long lead, int P, int T, long tail) {     // queued; zero_flush() launches once
+  void zero_add(Buf b, bool lo_half) {               // the halo rows of a buffer (of its low half); queued, zero_flush() launches once
+    const ActBuf& a = p.bufs[b];
     const int k = zm.n++;
-    zm.buf[k] = ws + off; zm.ld_bytes[k] = ld_elems * 2; zm.lead[k] = lead; zm.P[k] = P; zm.T[k] = T;
-    zm.tail_rows[k] = (long)(P - T) + tail;
+    zm.buf[k] = ws + (lo_half ? a.lo : a.off); zm.ld_bytes[k] = (long)a.width * 2; zm.lead[k] = a.lead; zm.P[k] = a.P; zm.T[k] = a.T;
+    zm.tail_rows[k] = (long)(a.P - a.T) + a.tail;
   }
   void zero_flush() {
     if (rc || zm.n == 0) return;
@@ -1529,10 +1549,10 @@ struct Runner {
     if (r) rc = fail(r, "zero_halo launch failed");
   }
 
-  void zero(long off, long ld_elems, long lead, int P, int T, long tail) {
+  void zero(bf16_t* b, long ld_elems, long lead, int P, int T, long tail) {
     if (rc) return;
     // `tail` = rows behind the last clip's pitch; the kernel counts from the last clip's last valid frame
-    const int r = wfl_launch_zero_halo(buf(off), ld_elems * 2, lead, p.B, P, T, (long)(P - T) + tail, s);
+    const int r = wfl_launch_zero_halo(b, ld_elems * 2, lead, p.B, P, T, (long)(P - T) + tail, s);
     if (r) rc = fail(r, "zero_halo launch failed");
   }
 };
@@ -1546,8 +1566,8 @@ static int run_logmel(wfl_model* m, const Plan& p, char* ws, const float* wav, l
   a.n_frames = p.T2; a.n_samples = p.T2 * 160; a.n_mels = m->a.n_mels;
   a.Wc = m->Wc; a.Ws = m->Ws; a.mel_lo = m->mel_lo; a.mel_cnt = m->mel_cnt; a.mel_w = m->mel_w; a.mel_maxw = m->mel_maxw;
   a.raw = (float*)(ws + p.raw); a.clipmax = (unsigned*)(ws + p.clipmax);
-  bf16_t* mel_lo = (m->a.precision && p.lo_delta > 0) ? (bf16_t*)(ws + p.mel + p.lo_delta) : nullptr;
-  return wfl_launch_logmel(a, (bf16_t*)(ws + p.mel), m->a.n_mels, p.lead2, p.P2, ref_out, s, mel_lo);
+  const ActBuf& mel = p.bufs[BUF_MEL];
+  return wfl_launch_logmel(a, (bf16_t*)(ws + mel.off), mel.width, mel.lead, mel.P, ref_out, s, mel.lo >= 0 ? (bf16_t*)(ws + mel.lo) : nullptr);
 }
 
 int32_t wfl_logmel(wfl_model* m, const float* wav, int64_t ldw, const int32_t* lens, int32_t B, int32_t L, float* out,
@@ -1562,47 +1582,23 @@ int32_t wfl_logmel(wfl_model* m, const float* wav, int64_t ldw, const int32_t* l
   return r ? fail(r, "logmel launch failed") : 0;
 }
 
-// Halo rows of the buffers every stage shares (cheap; keeps the layout invariant independent of the workspace's history) and
-// the forward's error word.
-static int begin_forward(Runner& R, bool with_encoder) {
-  const wfl_arch& a = R.m->a;
+// The opening steps of every forward: the workspace and frame-count checks (`who` = the entry point, for its messages), then the halo
+// rows of the buffers every stage shares (cheap; keeps the layout invariant independent of the workspace's history) and the forward's
+// error word.
+static int begin_forward(Runner& R, const char* who, int64_t workspace_bytes, bool with_encoder) {
   const Plan& p = R.p;
-  const int d = p.d;
-  R.zm.err_word = (unsigned*)(R.ws + p.err);      // cleared by the halo kernel (a kernel, not a memset node: graph replay)
-  R.zero_add(p.X, d, p.lead, p.P, p.T, p.tail);
-  R.zero_add(p.Y, d, p.lead, p.P, p.T, p.tail);
-  R.zero_add(p.ATT, d, p.lead, p.P, p.T, p.tail);
-  R.zero_add(p.QK, 3 * d, p.lead, p.P, p.T, p.tail);
-  R.zero_add(p.FF, p.ffw, p.lead, p.P, p.T, p.tail);
-  if (p.da != d) {
-    R.zero_add(p.QKp, 3 * p.da, p.lead, p.P, p.T, p.tail);
-    R.zero_add(p.ATTp, p.da, p.lead, p.P, p.T, p.tail);
-  }
-  if (with_encoder && a.encoder_type == WFL_ENC_WHISPER) {
-    R.zero_add(p.mel, a.n_mels, p.lead2, p.P2, p.T2, 2 * p.tail);
-    R.zero_add(p.c1, d, p.lead2, p.P2, p.T2, 2 * p.tail);
-  }
-  R.zero_flush();
-  if (R.precise()) {                               // the low halves' halo rows are taps of the split-precision convolutions too
-    const long D = p.lo_delta;
-    R.zero_add(p.X + D, d, p.lead, p.P, p.T, p.tail);
-    R.zero_add(p.Y + D, d, p.lead, p.P, p.T, p.tail);
-    R.zero_add(p.ATT + D, d, p.lead, p.P, p.T, p.tail);
-    R.zero_add(p.QK + D, 3 * d, p.lead, p.P, p.T, p.tail);
-    R.zero_add(p.FF + D, p.ffw, p.lead, p.P, p.T, p.tail);
-    if (p.da != d) {
-      R.zero_add(p.QKp + D, 3 * p.da, p.lead, p.P, p.T, p.tail);
-      R.zero_add(p.ATTp + D, p.da, p.lead, p.P, p.T, p.tail);
-    }
-    if (with_encoder && a.encoder_type == WFL_ENC_WHISPER) {
-      R.zero_add(p.mel + D, a.n_mels, p.lead2, p.P2, p.T2, 2 * p.tail);
-      R.zero_add(p.c1 + D, d, p.lead2, p.P2, p.T2, 2 * p.tail);
-    }
-    R.zm.err_word = nullptr;                       // (cleared by the first flush)
+  if (!R.ws || workspace_bytes < p.total) return fail(-1, std::string(who) + ": workspace too small");
+  if (p.T <= 0) return fail(-1, std::string(who) + ": clip too short for the encoder");
+  // QKp / ATTp: a padded Conformer head size only; mel / c1: the Whisper stem (a head-only plan has neither)
+  for (int lo_half = 0; lo_half <= (R.precise() ? 1 : 0); ++lo_half) {   // the low halves' halo rows are taps of the split-precision convolutions too
+    for (Buf b : {BUF_X, BUF_Y, BUF_ATT, BUF_QK, BUF_FF, BUF_QKP, BUF_ATTP, BUF_MEL, BUF_C1})
+      if (p.bufs[b].bytes && (with_encoder || (b != BUF_MEL && b != BUF_C1))) R.zero_add(b, lo_half != 0);
+    // the first launch clears the error word (a kernel, not a memset node: graph replay)
+    R.zm.err_word = lo_half ? nullptr : (unsigned*)(R.ws + p.err);
     R.zero_flush();
   }
   // a zero-padded width (encoder_type none): the front-end / wfl_head write only the valid columns of the Y rows
-  if (!R.rc && R.m->dv != d && wfl_launch_fill_i32((int*)(R.ws + p.Y), p.R * d / 2, 0, R.s)) return fail(-3, "fill launch failed");
+  if (!R.rc && R.m->dv != p.d && wfl_launch_fill_i32((int*)R.act(BUF_Y), p.bufs[BUF_Y].bytes / 4, 0, R.s)) return fail(-3, "fill launch failed");
   return R.rc;
 }
 
@@ -1611,25 +1607,13 @@ static int begin_forward(Runner& R, bool with_encoder) {
 // conv's padding they are the same zeros the halo rows are.
 static int zero_shared_buffers(Runner& R) {
   const Plan& p = R.p;
-  const long d = p.d;
-  int r = wfl_launch_fill_i32((int*)(R.ws + p.X), p.R * d / 2, 0, R.s);
-  if (!r) r = wfl_launch_fill_i32((int*)(R.ws + p.Y), p.R * d / 2, 0, R.s);
-  if (!r) r = wfl_launch_fill_i32((int*)(R.ws + p.ATT), p.R * d / 2, 0, R.s);
-  if (!r) r = wfl_launch_fill_i32((int*)(R.ws + p.QK), p.R * 3 * d / 2, 0, R.s);
-  if (!r) r = wfl_launch_fill_i32((int*)(R.ws + p.FF), p.R * (long)p.ffw / 2, 0, R.s);
-  if (!r && p.da != p.d) {
-    r = wfl_launch_fill_i32((int*)(R.ws + p.QKp), p.R * 3L * p.da / 2, 0, R.s);
-    if (!r) r = wfl_launch_fill_i32((int*)(R.ws + p.ATTp), p.R * (long)p.da / 2, 0, R.s);
-  }
-  if (!r && R.precise()) {                         // ... and their low halves
-    const long D = p.lo_delta;
-    r = wfl_launch_fill_i32((int*)(R.ws + p.X + D), p.R * d / 2, 0, R.s);
-    if (!r) r = wfl_launch_fill_i32((int*)(R.ws + p.Y + D), p.R * d / 2, 0, R.s);
-    if (!r) r = wfl_launch_fill_i32((int*)(R.ws + p.ATT + D), p.R * d / 2, 0, R.s);
-    if (!r) r = wfl_launch_fill_i32((int*)(R.ws + p.QK + D), p.R * 3 * d / 2, 0, R.s);
-    if (!r) r = wfl_launch_fill_i32((int*)(R.ws + p.FF + D), p.R * (long)p.ffw / 2, 0, R.s);
-  }
-  return r ? fail(r, "fill launch failed") : 0;
+  for (int lo_half = 0; lo_half <= (R.precise() ? 1 : 0); ++lo_half)       // ... and their low halves
+    for (Buf b : {BUF_X, BUF_Y, BUF_ATT, BUF_QK, BUF_FF, BUF_QKP, BUF_ATTP}) {
+      const ActBuf& a = p.bufs[b];
+      if (!a.bytes) continue;
+      if (int r = wfl_launch_fill_i32((int*)(R.ws + (lo_half ? a.lo : a.off)), a.bytes / 4, 0, R.s)) return fail(r, "fill launch failed");
+    }
+  return 0;
 }
 
 // Feature extractor + encoder (model.py:149-161): leaves the encoder output in the Y rows.
@@ -1640,7 +1624,7 @@ static int run_encoder(Runner& R, const float* wav, int64_t ldw, const int32_t* 
   const int B = p.B, L = p.L, d = p.d;
   const long Mrows = (long)B * p.P;
   const GemmRows rows{(int)Mrows, p.P, p.T};
-  bf16_t *X = R.buf(p.X), *Y = R.buf(p.Y), *ATT = R.buf(p.ATT), *QK = R.buf(p.QK), *FF = R.buf(p.FF);
+  bf16_t *X = R.act(BUF_X), *Y = R.act(BUF_Y), *ATT = R.act(BUF_ATT), *QK = R.act(BUF_QK), *FF = R.act(BUF_FF);
   if (a.encoder_type == WFL_ENC_WHISPER) {
     // ---- Whisper encoder (HF modeling_whisper.py:618-642)
     R.prof_begin();
@@ -1648,8 +1632,8 @@ static int run_encoder(Runner& R, const float* wav, int64_t ldw, const int32_t* 
     R.prof_end(PROF_LOGMEL, 0.96e9 * (double)B * (a.n_mels / 80.0));
     if (r) return fail(r, "logmel launch failed");
     if (R.precise()) R.lo_ok[BUF_MEL] = true;                // (the log-mel kernel wrote the features' low half)
-    bf16_t* mel = R.buf(p.mel);
-    bf16_t* c1 = R.buf(p.c1);
+    bf16_t* mel = R.act(BUF_MEL);
+    bf16_t* c1 = R.act(BUF_C1);
     // conv1 k3 p1: frame t reads mel rows t-1..t+1 = 3*n_mels contiguous channels
     R.gemm(mel + (long)(p.lead2 - 1) * a.n_mels, a.n_mels, m->conv1, {B * p.P2, p.P2, p.T2}, {c1, d, p.lead2, p.P2}, {.act = WFL_ACT_GELU});
     // conv2 k3 s2 p1: frame t reads c1 rows 2t-1..2t+1; pitch(c1) = 2 * pitch(X) makes it one flat GEMM with lda = 2d
@@ -1693,8 +1677,8 @@ static int run_encoder(Runner& R, const float* wav, int64_t ldw, const int32_t* 
       auto in8 = [&](const float* row_scale, float stat, const unsigned char* lo_plane) {
         return GemmOpts{.a8 = a8_mode, .a8_scale = row_scale, .a8_static = stat, .a8_lo = lo_plane};
       };
-      const unsigned char* X8lo_rows = X8lo ? X8lo + (long)p.lead * d : nullptr;
-      const bf16_t* X8_rows = (const bf16_t*)(X8 + (long)p.lead * d);
+      const unsigned char* X8lo_rows = X8lo ? R.rows(X8lo, d) : nullptr;
+      const bf16_t* X8_rows = (const bf16_t*)R.rows(X8, d);
       rows8(X, R.lo_in(X), &L_.ln1);
       R.gemm(X8_rows, d, L_.qkv, rows, R.out(QK, 3 * d), in8(rs8, 1.f, X8lo_rows));
       // the attention context leaves the attention kernel as e4m3 (a pair in mode 3) with a fixed scale (head_dim 64; other head sizes:
@@ -1715,18 +1699,18 @@ static int run_encoder(Runner& R, const float* wav, int64_t ldw, const int32_t* 
       o.act = WFL_ACT_GELU;
       o.c8 = FF8; o.c8_lo = FF8lo; o.ldc8 = p.ffw; o.c8_inv = ff_scale;
       R.gemm(X8_rows, d, L_.fc1, rows, R.out(FF, p.ffw), o);
-      o = in8(nullptr, 1.0f / ff_scale, FF8lo ? FF8lo + (long)p.lead * p.ffw : nullptr);
+      o = in8(nullptr, 1.0f / ff_scale, FF8lo ? R.rows(FF8lo, p.ffw) : nullptr);
       o.res = X; o.ldres = d;
-      R.gemm((const bf16_t*)(FF8 + (long)p.lead * p.ffw), p.ffw, L_.fc2, rows, R.out(X, d), o);
+      R.gemm((const bf16_t*)R.rows(FF8, p.ffw), p.ffw, L_.fc2, rows, R.out(X, d), o);
     }
     for (int i = 0; !act8 && i < a.enc_layers; ++i) {
       const EncLayer& L_ = m->enc[i];
       R.ln_gemm(X, Y, L_.ln1, L_.qkv, L_.qkv_ln, (int)Mrows, QK, 3 * d, WFL_ACT_NONE);
       R.attn(a.enc_heads);
       // want_stats: for the folded fc1, then for the next layer's folded q|k|v (the final LayerNorm is a kernel)
-      R.gemm(ATT + (long)p.lead * d, d, L_.out, rows, R.out(X, d), {.res = X, .ldres = d, .want_stats = true});
+      R.gemm(R.rows(ATT, d), d, L_.out, rows, R.out(X, d), {.res = X, .ldres = d, .want_stats = true});
       R.ln_gemm(X, Y, L_.ln2, L_.fc1, L_.fc1_ln, (int)Mrows, FF, p.ffw, WFL_ACT_GELU);
-      R.gemm(FF + (long)p.lead * p.ffw, p.ffw, L_.fc2, rows, R.out(X, d), {.res = X, .ldres = d, .want_stats = i + 1 < a.enc_layers});
+      R.gemm(R.rows(FF, p.ffw), p.ffw, L_.fc2, rows, R.out(X, d), {.res = X, .ldres = d, .want_stats = i + 1 < a.enc_layers});
     }
     R.ln(X, Y, m->enc_ln, true);   // encoder output in Y (with lang_id None it is the head's residual stream)
   } else if (a.encoder_type == WFL_ENC_NONE) {
@@ -1769,7 +1753,7 @@ static int run_encoder(Runner& R, const float* wav, int64_t ldw, const int32_t* 
     }
     if (p.T > WAVLM_MAX_T) return fail(-1, "wfl_forward: clip too long for the WavLM relative-position table");
     const int C = a.wavlm_conv_dim[0], n = p.nlev;
-    bf16_t* F[2] = {R.buf(p.FA), R.buf(p.FB)};
+    bf16_t* F[2] = {R.act(BUF_FA), R.act(BUF_FB)};
     double* wstats = nullptr;
     if (a.wavlm_do_normalize) {
       wstats = (double*)(R.ws + p.wstats);
@@ -1778,13 +1762,13 @@ static int run_encoder(Runner& R, const float* wav, int64_t ldw, const int32_t* 
     }
     // Rows that are not valid frames of a level are zeroed before the level is produced (the two buffers alternate
     // between levels; a K-padded conv GEMM may read a few channels past the last valid frame).
-    const long D = R.precise() ? p.lo_delta : 0;       // precision high: the feature extractor's rows as bf16 pairs too
-    R.zero(p.FA, C, p.leadl[0], p.Pl[0], p.Tl[0], p.tail);
-    if (D) R.zero(p.FA + D, C, p.leadl[0], p.Pl[0], p.Tl[0], p.tail);
+    const bool pairs = R.precise();                    // precision high: the feature extractor's rows as bf16 pairs too
+    R.zero(F[0], C, p.leadl[0], p.Pl[0], p.Tl[0], p.tail);
+    if (pairs) R.zero(R.lo_of(F[0]), C, p.leadl[0], p.Pl[0], p.Tl[0], p.tail);
     if (R.rc) return R.rc;
     {
       Conv0Args c{};
-      if (D) { c.out_lo = R.lo_of(F[0]); R.lo_ok[BUF_FA] = c.out_lo != nullptr; }
+      if (pairs) { c.out_lo = R.lo_of(F[0]); R.lo_ok[BUF_FA] = c.out_lo != nullptr; }
       c.wav = wav; c.ldw = ldw; c.L = L; c.wstats = wstats; c.w = m->conv0_w; c.bias = m->conv0_b;
       c.gamma = m->conv0_norm.g; c.beta = m->conv0_norm.b; c.B = B; c.T0 = p.Tl[0]; c.C = C; c.lens = lens;
       c.cstats = (double*)(R.ws + p.cstats); c.cpart = (float*)(R.ws + p.cpart); c.out = F[0]; c.lead = p.leadl[0]; c.P = p.Pl[0];
@@ -1796,13 +1780,13 @@ static int run_encoder(Runner& R, const float* wav, int64_t ldw, const int32_t* 
       const bf16_t* in = F[(i - 1) & 1] + (long)p.leadl[i - 1] * C;
       bf16_t* out = F[i & 1];
       const bool group = a.wavlm_group_norm != 0;
-      R.zero((i & 1) ? p.FB : p.FA, C, p.leadl[i], p.Pl[i], p.Tl[i], p.tail);
-      if (D) R.zero(((i & 1) ? p.FB : p.FA) + D, C, p.leadl[i], p.Pl[i], p.Tl[i], p.tail);
+      R.zero(out, C, p.leadl[i], p.Pl[i], p.Tl[i], p.tail);
+      if (pairs) R.zero(R.lo_of(out), C, p.leadl[i], p.Pl[i], p.Tl[i], p.tail);
       R.gemm(in, 2 * C, m->fconv[i - 1], {B * p.Pl[i], p.Pl[i], p.Tl[i]}, {out, C, p.leadl[i], p.Pl[i]},
              {.act = group ? WFL_ACT_GELU : WFL_ACT_NONE});
       if (!group && !R.rc) {
         const int r = wfl_launch_layernorm_act(out, C, out, C, m->fconv_ln[i - 1].g, m->fconv_ln[i - 1].b, 1e-5f, p.leadl[i], B,
-                                               p.Pl[i], p.Tl[i], C, 1, R.s, R.lo_in(out), D ? R.lo_of(out) : nullptr, 0, R.levelT[i]);
+                                               p.Pl[i], p.Tl[i], C, 1, R.s, R.lo_in(out), pairs ? R.lo_of(out) : nullptr, 0, R.levelT[i]);
         if (r) return fail(r, "layernorm launch failed");
       }
     }
@@ -1810,18 +1794,18 @@ static int run_encoder(Runner& R, const float* wav, int64_t ldw, const int32_t* 
     bf16_t* feats = F[(n - 1) & 1];                    // level n-1 has the main geometry (lead, P, T)
     {
       const int r = wfl_launch_layernorm_act(feats, C, feats, C, m->fp_ln.g, m->fp_ln.b, 1e-5f, p.lead, B, p.P, p.T, C, 0, R.s, R.lo_in(feats),
-                                             D ? R.lo_of(feats) : nullptr, 0, R.clipT);
+                                             pairs ? R.lo_of(feats) : nullptr, 0, R.clipT);
       if (r) return fail(r, "layernorm launch failed");
     }
-    R.gemm(feats + (long)p.lead * C, C, m->fp_proj, rows, R.out(X, d), {.lo_out = true});
+    R.gemm(R.rows(feats, C), C, m->fp_proj, rows, R.out(X, d), {.lo_out = true});
     // positional conv: x + GELU(grouped conv k, pad k/2, last step dropped), one contiguous-tap GEMM per group
     {
       const int G = a.wavlm_pos_conv_groups, cpg = d / G, K = a.wavlm_pos_conv_kernel;
-      bf16_t* XG = R.buf(p.XG);
+      bf16_t* XG = R.act(BUF_XG);
       if (!R.rc) {
         int r = wfl_launch_regroup(X, d, G, cpg, p.R, p.lead, B, p.P, p.T, XG, R.s, R.clipT);
         R.lo_ok[BUF_XG] = false;
-        if (!r && D && R.lo_in(X)) {                 // the low halves in the same layout: the per-group GEMMs' third pass
+        if (!r && pairs && R.lo_in(X)) {                 // the low halves in the same layout: the per-group GEMMs' third pass
           r = wfl_launch_regroup(R.lo_in(X), d, G, cpg, p.R, p.lead, B, p.P, p.T, R.lo_of(XG), R.s, R.clipT);
           R.lo_ok[BUF_XG] = true;
         }
@@ -1831,7 +1815,7 @@ static int run_encoder(Runner& R, const float* wav, int64_t ldw, const int32_t* 
       static int as_gemm = -1;
       if (as_gemm < 0) { const char* e = getenv("WFL_POSCONV_GEMM"); as_gemm = e && atoi(e) ? 1 : 0; }
       int taken = 1;
-      if (!as_gemm && !D && !R.rc && G <= 16) {      // (precision high: the GEMM per group, three passes each)
+      if (!as_gemm && !pairs && !R.rc && G <= 16) {      // (precision high: the GEMM per group, three passes each)
         PosConvArgs pc{};
         pc.xg = XG; pc.R = p.R; pc.lead = p.lead; pc.B = B; pc.P = p.P; pc.T = p.T; pc.groups = G; pc.cpg = cpg; pc.taps = K;
         for (int gi = 0; gi < G; ++gi) { pc.w[gi] = m->posconv[gi].W; pc.bias[gi] = m->posconv[gi].bias; }
@@ -1865,19 +1849,19 @@ static int run_encoder(Runner& R, const float* wav, int64_t ldw, const int32_t* 
       if (R.rc) break;
       int r = wfl_launch_relpos_gate(A_in, d, p.lead, B, p.P, p.T, a.enc_heads, hd, L_.w8, L_.b8, L_.cst, gate, R.s, R.lo_in(A_in));
       if (r) return fail(r, "relpos_gate launch failed");
-      R.gemm(A_in + (long)p.lead * d, d, L_.qkv, rows, R.out(QK, 3 * d));
+      R.gemm(R.rows(A_in, d), d, L_.qkv, rows, R.out(QK, 3 * d));
       R.attn(a.enc_heads, rtab, gate);
       if (stable) {
         // x = x + attn; x = x + FFN(LN(x))
-        R.gemm(ATT + (long)p.lead * d, d, L_.out, rows, R.out(H, d), {.res = H, .ldres = d, .want_stats = L_.fc1_ln.ln_s != nullptr});
+        R.gemm(R.rows(ATT, d), d, L_.out, rows, R.out(H, d), {.res = H, .ldres = d, .want_stats = L_.fc1_ln.ln_s != nullptr});
         R.ln_gemm(H, S, L_.ln2, L_.fc1, L_.fc1_ln, (int)Mrows, FF, p.ffw, WFL_ACT_GELU);
-        R.gemm(FF + (long)p.lead * p.ffw, p.ffw, L_.fc2, rows, R.out(H, d), {.res = H, .ldres = d});
+        R.gemm(R.rows(FF, p.ffw), p.ffw, L_.fc2, rows, R.out(H, d), {.res = H, .ldres = d});
       } else {
         // x = LN(x + attn); x = LN_final(x + FFN(x))
-        R.gemm(ATT + (long)p.lead * d, d, L_.out, rows, R.out(S, d), {.res = H, .ldres = d});
+        R.gemm(R.rows(ATT, d), d, L_.out, rows, R.out(S, d), {.res = H, .ldres = d});
         R.ln(S, H, L_.ln1, true);
-        R.gemm(H + (long)p.lead * d, d, L_.fc1, rows, R.out(FF, p.ffw), {.act = WFL_ACT_GELU});
-        R.gemm(FF + (long)p.lead * p.ffw, p.ffw, L_.fc2, rows, R.out(S, d), {.res = H, .ldres = d});
+        R.gemm(R.rows(H, d), d, L_.fc1, rows, R.out(FF, p.ffw), {.act = WFL_ACT_GELU});
+        R.gemm(R.rows(FF, p.ffw), p.ffw, L_.fc2, rows, R.out(S, d), {.res = H, .ldres = d});
         R.ln(S, H, L_.ln2, true);
       }
     }
@@ -1900,8 +1884,8 @@ static int emit_hidden(Runner& R, float* hidden) {
     return wfl_launch_axpy(hidden, (const float*)(R.ws + p.raw), (long)p.B * p.T * m->a.n_mels, 1.f, 1, R.s);
   // (the default build hands out the high halves only: wfl_head rounds its input to bf16 again, and bf16(hi + lo) is not always hi --
   //  lo can round up to exactly half a unit of hi -- which would cost wfl_encode + wfl_head == wfl_forward its bit-exactness)
-  return wfl_launch_rows_to_f32(R.buf(p.Y), p.d, p.lead, p.B, p.P, p.T, m->dv, hidden, R.s, m->pad_split(), m->pad_shift(),
-                                R.precise() ? R.lo_in(R.buf(p.Y)) : nullptr);
+  return wfl_launch_rows_to_f32(R.act(BUF_Y), p.d, p.lead, p.B, p.P, p.T, m->dv, hidden, R.s, m->pad_split(), m->pad_shift(),
+                                R.precise() ? R.lo_in(R.act(BUF_Y)) : nullptr);
 }
 
 // Head (model.py:176-194) + tag decision on the encoder output in the Y rows.
@@ -1913,20 +1897,19 @@ static int run_head(Runner& R, const int32_t* lang_id, int32_t lang_mode, float 
   const int B = p.B, d = p.d;
   const long Mrows = (long)B * p.P;
   const GemmRows rows{(int)Mrows, p.P, p.T};
-  bf16_t *X = R.buf(p.X), *Y = R.buf(p.Y), *ATT = R.buf(p.ATT), *QK = R.buf(p.QK), *FF = R.buf(p.FF);
+  bf16_t *X = R.act(BUF_X), *Y = R.act(BUF_Y), *ATT = R.act(BUF_ATT), *QK = R.act(BUF_QK), *FF = R.act(BUF_FF);
   // ---- head (model.py:176-194); with WFL_LANG_AVERAGE it runs once per language on the same encoder output
   const int n_pass = lang_mode == WFL_LANG_AVERAGE ? (int)m->avg_langs.size() : 1;
   float* lg = logits ? logits : (float*)(R.ws + p.logits);
   bf16_t* ENC = Y;
   // the head needs Y as scratch: keep the encoder output in ATT when more than one pass reads it
   if (n_pass > 1) {
-    if (wfl_launch_copy16(R.buf(p.enc2), Y, p.R * d * 2, R.s)) return fail(-3, "copy launch failed");
-    ENC = R.buf(p.enc2);
+    ENC = R.act(BUF_ENC2);
+    if (wfl_launch_copy16(ENC, Y, p.R * d * 2, R.s)) return fail(-3, "copy launch failed");
     if (R.precise()) {                                   // ... and its low half
       const bool have_lo = R.lo_in(Y) != nullptr && R.lo_of(ENC) != nullptr;
       if (have_lo && wfl_launch_copy16(R.lo_of(ENC), R.lo_of(Y), p.R * d * 2, R.s)) return fail(-3, "copy launch failed");
-      const int ei = R.lo_idx(ENC);
-      if (ei >= 0) R.lo_ok[ei] = have_lo;
+      R.mark_lo(ENC, have_lo);
     }
   }
   int* lang_dev = nullptr;
@@ -1944,7 +1927,7 @@ static int run_head(Runner& R, const int32_t* lang_id, int32_t lang_mode, float 
         if (fr) return fail(fr, "fill launch failed");
         idx = lang_dev;
       }
-      R.gemm(ENC + (long)p.lead * d, d, m->lang, rows, R.out(X, d),
+      R.gemm(R.rows(ENC, d), d, m->lang, rows, R.out(X, d),
              {.clip_bias = m->lang_table, .clip_idx = idx, .clip_ld = d, .lo_out = true});
       H = X; S = Y;
     }
@@ -1952,7 +1935,7 @@ static int run_head(Runner& R, const int32_t* lang_id, int32_t lang_mode, float 
       const int Hh = d / 2;
       float* GX = (float*)(R.ws + p.gx);
       for (int layer = 0; layer < a.bilstm_layers; ++layer) {
-        R.gemm(H + (long)p.lead * d, d, m->lstm_in[layer], rows, R.out(GX, 8 * Hh), {.out_f32 = true});
+        R.gemm(R.rows(H, d), d, m->lstm_in[layer], rows, R.out(GX, 8 * Hh), {.out_f32 = true});
         if (R.rc) return R.rc;
         LstmArgs la{};
         la.gx = GX; la.ldgx = 8 * Hh; la.whh = m->lstm_whh[layer]; la.out = S; la.ldo = d; la.lead = p.lead;
@@ -1963,7 +1946,7 @@ static int run_head(Runner& R, const int32_t* lang_id, int32_t lang_mode, float 
         // the recurrence writes plain bf16 rows -- or, precision high with H <= 256, h as a bf16 pair like every other activation
         const bool split = R.precise() && m->lstm_whh_lo[layer] != nullptr && R.lo_of(S) != nullptr;
         if (split) { la.whh_lo = m->lstm_whh_lo[layer]; la.out_lo = R.lo_of(S); }
-        { const int si = R.lo_idx(S); if (si >= 0) R.lo_ok[si] = split; }
+        R.mark_lo(S, split);
         R.prof_begin();
         const int lr = wfl_launch_lstm(la, R.ws + p.lstm_x, R.s);
         R.prof_end(PROF_LSTM, 2.0 * (double)B * p.T * 2.0 * 4.0 * (double)Hh * (double)Hh);
@@ -1976,29 +1959,29 @@ static int run_head(Runner& R, const int32_t* lang_id, int32_t lang_mode, float 
       const ConfLayer& C = m->conf[i];
       // x = x + 0.5 * FF1(x)
       R.ln_gemm(H, S, C.ff1_ln, C.ff1_a, C.ff1_a_ln, (int)Mrows, FF, p.ffw, WFL_ACT_GELU);
-      R.gemm(FF + (long)p.lead * p.ffw, p.ffw, C.ff1_b, rows, R.out(H, d), {.res = H, .ldres = d, .alpha = 0.5f});
+      R.gemm(R.rows(FF, p.ffw), p.ffw, C.ff1_b, rows, R.out(H, d), {.res = H, .ldres = d, .alpha = 0.5f});
       // x = LN1(x + MHA(x))
       if (p.da == d) {
-        R.gemm(H + (long)p.lead * d, d, C.qkv, rows, R.out(QK, 3 * d));
+        R.gemm(R.rows(H, d), d, C.qkv, rows, R.out(QK, 3 * d));
         R.attn(a.conformer_heads);
-        R.gemm(ATT + (long)p.lead * d, d, C.out, rows, R.out(S, d), {.res = H, .ldres = d});
+        R.gemm(R.rows(ATT, d), d, C.out, rows, R.out(S, d), {.res = H, .ldres = d});
       } else {
-        R.gemm(H + (long)p.lead * d, d, C.qkv, rows, R.out(R.buf(p.QKp), 3 * p.da));
+        R.gemm(R.rows(H, d), d, C.qkv, rows, R.out(R.act(BUF_QKP), 3 * p.da));
         R.attn(a.conformer_heads, nullptr, nullptr, true);
-        R.gemm(R.buf(p.ATTp) + (long)p.lead * p.da, p.da, C.out, rows, R.out(S, d), {.res = H, .ldres = d});
+        R.gemm(R.rows(BUF_ATTP), p.da, C.out, rows, R.out(S, d), {.res = H, .ldres = d});
       }
       R.ln(S, H, C.ln1, true);
       // x = x + pw2(GELU(BN(conv_k(GLU(pw1(LN2(x)))))))
       R.ln(H, S, C.ln2);
-      R.gemm(S + (long)p.lead * d, d, C.pw1, rows, R.out(ATT, d), {.glu = true});
+      R.gemm(R.rows(S, d), d, C.pw1, rows, R.out(ATT, d), {.glu = true});
       // dense k-tap conv: taps are adjacent rows (cin = d, tap stride = one row) -> the streaming GEMM's tap-stationary mode
       R.gemm(ATT + (long)(p.lead - a.conformer_kernel / 2) * d, d, C.conv, rows, R.out(S, d),
              {.act = WFL_ACT_GELU, .cin = d, .tap_stride = d});
       // want_stats: for the folded ff2, then for the next block's folded ff1
-      R.gemm(S + (long)p.lead * d, d, C.pw2, rows, R.out(H, d), {.res = H, .ldres = d, .want_stats = true});
+      R.gemm(R.rows(S, d), d, C.pw2, rows, R.out(H, d), {.res = H, .ldres = d, .want_stats = true});
       // x = x + 0.5 * FF2(x)
       R.ln_gemm(H, S, C.ff2_ln, C.ff2_a, C.ff2_a_ln, (int)Mrows, FF, p.ffw, WFL_ACT_GELU);
-      R.gemm(FF + (long)p.lead * p.ffw, p.ffw, C.ff2_b, rows, R.out(H, d),
+      R.gemm(R.rows(FF, p.ffw), p.ffw, C.ff2_b, rows, R.out(H, d),
              {.res = H, .ldres = d, .alpha = 0.5f, .want_stats = i + 1 < a.n_conformer});
     }
     if (a.enable_dilated) {
@@ -2016,7 +1999,7 @@ static int run_head(Runner& R, const int32_t* lang_id, int32_t lang_mode, float 
     // input halves are taps one buffer apart; without a valid low half the second pass is the plain K = d one)
     static const bool cls_one = std::getenv("WFL_CLS_TWO_LAUNCHES") == nullptr;       // (A/B hook: rounds 2-3's two-launch form)
     const bf16_t* hlo = R.lo_in(H);
-    const bf16_t* Hrows = H + (long)p.lead * d;
+    const bf16_t* Hrows = R.rows(H, d);
     const GemmOut lg_out{lg_pass, ldlg, 0, p.T};                    // compact rows: no halo
     const double cls_flops = 2.0 * (double)B * p.T * (double)a.num_classes * (double)d;
     if (hlo && m->cls3.W && cls_one) {
@@ -2092,10 +2075,7 @@ int32_t wfl_forward(wfl_model* m, const float* wav, int64_t ldw, const int32_t* 
   if (int r = check_forward_args(m, "wfl_forward", B, lang_id, lang_mode, ids, maxprob, offsets)) return r;
   if (int r = check_device(m, "wfl_forward")) return r;
   Runner R{m, make_plan(m, B, L), (char*)workspace, (hipStream_t)stream};
-  const Plan& p = R.p;
-  if (!workspace || workspace_bytes < p.total) return fail(-1, "wfl_forward: workspace too small");
-  if (p.T <= 0) return fail(-1, "wfl_forward: clip too short for the encoder");
-  if (int r = begin_forward(R, true)) return r;
+  if (int r = begin_forward(R, "wfl_forward", workspace_bytes, true)) return r;
   if (int r = run_encoder(R, wav, ldw, lens)) return r;
   if (hidden) {
     const int r = emit_hidden(R, hidden);
@@ -2110,10 +2090,7 @@ int32_t wfl_encode(wfl_model* m, const float* wav, int64_t ldw, const int32_t* l
   if (!wav || !hidden || B <= 0 || L <= 0 || ldw < L) return fail(-1, "wfl_encode: bad argument");
   if (int r = check_device(m, "wfl_encode")) return r;
   Runner R{m, make_plan(m, B, L), (char*)workspace, (hipStream_t)stream};
-  const Plan& p = R.p;
-  if (!workspace || workspace_bytes < p.total) return fail(-1, "wfl_encode: workspace too small");
-  if (p.T <= 0) return fail(-1, "wfl_encode: clip too short for the encoder");
-  if (int r = begin_forward(R, true)) return r;
+  if (int r = begin_forward(R, "wfl_encode", workspace_bytes, true)) return r;
   if (int r = run_encoder(R, wav, ldw, lens)) return r;
   const int r = emit_hidden(R, hidden);
   return r ? fail(r, "rows_to_f32 launch failed") : 0;
@@ -2133,10 +2110,9 @@ int32_t wfl_head(wfl_model* m, const float* hidden, int32_t B, int32_t T, const 
   if (int r = check_device(m, "wfl_head")) return r;
   Runner R{m, make_plan(m, B, 0, T), (char*)workspace, (hipStream_t)stream};
   const Plan& p = R.p;
-  if (!workspace || workspace_bytes < p.total) return fail(-1, "wfl_head: workspace too small");
-  if (int r = begin_forward(R, false)) return r;
-  const int r = wfl_launch_f32_to_rows(hidden, R.buf(p.Y), p.d, p.lead, B, p.P, p.T, m->dv, R.s, m->pad_split(), m->pad_shift(),
-                                       R.precise() ? R.lo_of(R.buf(p.Y)) : nullptr);
+  if (int r = begin_forward(R, "wfl_head", workspace_bytes, false)) return r;
+  const int r = wfl_launch_f32_to_rows(hidden, R.act(BUF_Y), p.d, p.lead, B, p.P, p.T, m->dv, R.s, m->pad_split(), m->pad_shift(),
+                                       R.precise() ? R.lo_of(R.act(BUF_Y)) : nullptr);
   if (r) return fail(r, "f32_to_rows launch failed");
   if (R.precise()) R.lo_ok[BUF_Y] = true;
   return run_head(R, lang_id, lang_mode, threshold, ids, argmax, maxprob, offsets, logits, status);
