@@ -329,6 +329,21 @@ int32_t wfl_align(const float* logits, int64_t ldl, int32_t C, int32_t o_id, con
                   const int32_t* tok_off_host, const int32_t* n_tok_host, const int32_t* tok_cls, const int32_t* gap_cls, int32_t n_clips,
                   void* workspace, int64_t workspace_bytes, int32_t* ids, int32_t* tok, float* score, int32_t* status, void* stream);
 
+/* ---- wfl_align inside per-token start windows (`postprocess.align_draft`; wfl-asr_amd/align.py).  wfl_align's arguments plus tok_win
+ * (device), [total tokens][2] int32 = (lo, hi), rows as tok_cls: a path is accepted only if, for every token k, the frame t (0-based
+ * inside the clip) at which it is in B_k -- the frame where the token opens -- satisfies lo_k <= t <= hi_k (inclusive).  That is
+ * EB_t(k) = -inf outside the window; transitions, tie order, start and end states, the other emissions, the renormalisation and the
+ * workspace (wfl_align_workspace_bytes) are wfl_align's, and with every window (0, INT32_MAX) so is every output, bit for bit.  The ends of
+ * tokens carry no window: an end is not a state event of this lattice.
+ * status[b]: wfl_align's codes, 1 now meaning "no path satisfies the windows": T < N, a window with lo > hi, a window at or beyond T,
+ * windows that cannot be met in order (the host rule e_k = max(lo_k, e_{k-1} + 1) <= min(hi_k, T - 1), e_{-1} = -1, predicts it exactly).
+ * Such a clip gets ids = o_id, tok = -1, score 0; its backpointers are never walked.  A null tok_win with any token present is a host-side
+ * -1. */
+int32_t wfl_align_windowed(const float* logits, int64_t ldl, int32_t C, int32_t o_id, const int64_t* frame_off_host,
+                           const int32_t* n_frames_host, const int32_t* tok_off_host, const int32_t* n_tok_host, const int32_t* tok_cls,
+                           const int32_t* tok_win, const int32_t* gap_cls, int32_t n_clips, void* workspace, int64_t workspace_bytes,
+                           int32_t* ids, int32_t* tok, float* score, int32_t* status, void* stream);
+
 /* ---- Posteriors of a Viterbi alignment by forward-backward on the GPU (`postprocess.align_scores`; wfl-asr_amd/align.py).  No
  * counterpart in the reference, which reports no confidence for its string match.  The lattice, emissions EB / EI / EG, start and end
  * states, caps (C <= 1024, N <= 4096) and argument conventions are wfl_align's.  The weight of a path is exp(sum_t e_t(state_t));
@@ -358,6 +373,18 @@ int32_t wfl_align_posterior(const float* logits, int64_t ldl, int32_t C, int32_t
                             const int32_t* n_frames_host, const int32_t* tok_off_host, const int32_t* n_tok_host, const int32_t* tok_cls,
                             const int32_t* gap_cls, int32_t n_clips, const int32_t* tok, void* workspace, int64_t workspace_bytes,
                             float* logz, float* tok_post, float* start_mean, float* start_sd, int32_t* status, void* stream);
+
+/* ---- wfl_align_posterior over the windowed lattice of wfl_align_windowed: the same tok_win (device, [total tokens][2] = (lo, hi)), the
+ * same mask EB_t(k) = -inf outside [lo_k, hi_k] in alpha and in beta, so logZ sums and gamma normalises over exactly the paths the
+ * windowed search chose among.  Workspace and outputs are wfl_align_posterior's (bit for bit with every window open); every token's
+ * start distribution lies inside its window, a token with lo == hi has start_sd 0.  status[b] adds: 8 also when a token's first frame
+ * in tok lies outside its window (such a tok is not a path of this lattice), 1 also when no path satisfies the windows (logZ = -inf).
+ * A null tok_win with any token present is a host-side -1. */
+int32_t wfl_align_posterior_windowed(const float* logits, int64_t ldl, int32_t C, int32_t o_id, const int64_t* frame_off_host,
+                                     const int32_t* n_frames_host, const int32_t* tok_off_host, const int32_t* n_tok_host,
+                                     const int32_t* tok_cls, const int32_t* tok_win, const int32_t* gap_cls, int32_t n_clips,
+                                     const int32_t* tok, void* workspace, int64_t workspace_bytes, float* logz, float* tok_post,
+                                     float* start_mean, float* start_sd, int32_t* status, void* stream);
 
 /* ---- BIO-grammar Viterbi decode of clips WITHOUT a transcript on the GPU (`postprocess.decode: viterbi`; wfl-asr_amd/decode.py).
  * Stands beside the reference's free decode, infer.py:86-96, 164-174, 293-302 (per-frame argmax, confidence threshold, median filter

@@ -7,6 +7,9 @@
           the ratio of the two calls.  With --check also the kernel's maximum deviations from the float64 reference on the shapes
           of tests/test_gpu_align_posterior.py, beside the float32 restatement's.  With --e2e the end-to-end rate of viterbi with
           and without align_scores.  The result goes to --out (profiles/align_posterior_bench.json)
+  --windowed    the --op shape through wfl_align, through wfl_align_windowed with open windows and with windows of +-5 frames around
+          the unwindowed path's starts, and the same three through the posterior entries; the ratios to the unwindowed calls.  The
+          result goes to --out (profiles/align_windowed_bench.json)
   --e2e   Labeler.label_files over a folder of 30 s 16 kHz files (BASELINE config 2 model, synthetic weights), the same files with
           a transcript each (align="viterbi") and without one, alternated, --rounds times each; prints audio-s/s of both"""
 import argparse
@@ -90,6 +93,50 @@ def posterior_bench(reps):
     return out
 
 
+def windowed_bench(reps, shapes=((1500, 300, (16, 64)),)):
+    """shapes: (T, N, clip counts); the first is the --op shape, whose results stay at the top level of the result."""
+    out = {}
+    for T, N, counts in shapes:
+        res = _windowed_shape(reps, T, N, counts)
+        if not out:
+            out = res
+        else:
+            out.setdefault("other_configurations", {})[f"T{T}_N{N}"] = res
+    return out
+
+
+def _windowed_shape(reps, T, N, counts):
+    rng = np.random.default_rng(0)
+    C = 141
+    out = {"T": T, "N": N, "C": C, "reps": reps}
+    for nb in counts:
+        z = torch.from_numpy(rng.standard_normal((nb * T, C)).astype(np.float32) * 3).cuda()
+        toks = [[[(int(2 * p - 1), int(2 * p))] for p in rng.integers(1, 70, N)] for _ in range(nb)]
+        gaps = [[0, 139, 140]] * nb
+        args = (z, [T] * nb, toks, gaps, 0)
+        tok = AL.viterbi_align(*args)[1]
+        h = tok.cpu().numpy().reshape(nb, T)
+        near = []                                     # +-5 frames around every token's start on the unwindowed path
+        for b in range(nb):
+            opens = np.nonzero((h[b] >= 0) & (np.concatenate([[-1], h[b][:-1]]) != h[b]))[0]
+            assert len(opens) == N
+            near.append([(int(t) - 5, int(t) + 5) for t in opens])
+        packs = {"unwindowed": AL.pack_clips(*args[:4]), "open_windows": AL.pack_clips(*args[:4], windows=[None] * nb),
+                 "windows_pm5": AL.pack_clips(*args[:4], windows=near)}
+        res = {}
+        for name, pk in packs.items():
+            st = AL.viterbi_align(*args, packed=pk)[3]
+            pst = AL.alignment_posteriors(*args, tok, packed=pk)[4]
+            assert int(st.max()) == 0 and int(pst.max()) == 0
+            res[name] = {"viterbi_align": _timed(lambda: AL.viterbi_align(*args, packed=pk), reps),
+                         "alignment_posteriors": _timed(lambda: AL.alignment_posteriors(*args, tok, packed=pk), reps)}
+        for name in ("open_windows", "windows_pm5"):
+            for call in ("viterbi_align", "alignment_posteriors"):
+                res[name][call]["ratio_to_unwindowed"] = res[name][call]["ms_median"] / res["unwindowed"][call]["ms_median"]
+        out[f"clips{nb}"] = res
+    return out
+
+
 def posterior_check():
     """The kernel's and the float32 restatement's maximum deviations from float64 on the operator test's own clips (its builders)."""
     sys.path.insert(0, os.path.join(ROOT, "tests"))
@@ -156,14 +203,27 @@ def main():
     ap.add_argument("--op", action="store_true")
     ap.add_argument("--e2e", action="store_true")
     ap.add_argument("--posterior", action="store_true")
+    ap.add_argument("--windowed", action="store_true")
     ap.add_argument("--check", action="store_true")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "align_posterior_bench.json"))
+    ap.add_argument("--out", default=None, help="default: profiles/align_posterior_bench.json (--posterior), "
+                                                 "profiles/align_windowed_bench.json (--windowed)")
     ap.add_argument("--reps", type=int, default=50)
     ap.add_argument("--files", type=int, default=64)
     ap.add_argument("--rounds", type=int, default=3)
     a = ap.parse_args()
     if a.op:
         op_bench(a.reps)
+    if a.windowed:
+        res = {"tool": "tools/align_bench.py " + " ".join(sys.argv[1:]), "gpu": torch.cuda.get_device_name(0),
+               # beside the --op shape (N = 300: 256 threads x 2 slots), the two posterior configurations whose windowed form costs
+               # registers: 256 x 4 (N = 600) and 512 x 9 (N = 2100)
+               "calls_device_events": windowed_bench(a.reps, ((1500, 300, (16, 64)), (1500, 600, (16,)), (3000, 2100, (16,))))}
+        out = a.out or os.path.join(ROOT, "profiles", "align_windowed_bench.json")
+        os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+        with open(out, "w") as f:
+            json.dump(res, f, indent=1)
+            f.write("\n")
+        print(json.dumps(res["calls_device_events"]))
     if a.posterior:
         res = {"tool": "tools/align_bench.py " + " ".join(sys.argv[1:]), "gpu": torch.cuda.get_device_name(0),
                "calls_device_events": posterior_bench(a.reps)}
@@ -171,8 +231,9 @@ def main():
             res["max_deviation_from_float64"] = posterior_check()
         if a.e2e:
             res["e2e"] = e2e_bench(a.files, a.rounds, scores=True)
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "w") as f:
+        out = a.out or os.path.join(ROOT, "profiles", "align_posterior_bench.json")
+        os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+        with open(out, "w") as f:
             json.dump(res, f, indent=1)
             f.write("\n")
         print(json.dumps(res["calls_device_events"]))

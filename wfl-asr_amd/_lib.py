@@ -75,8 +75,10 @@ SIGNATURES = {
     "wfl_boundary_features": (_I, [_P, _L, _P, _I, _I, _P, _P, _P, _P, _P, _L, _P]),
     "wfl_align_workspace_bytes": (_L, [_P, _P, _I]),
     "wfl_align": (_I, [_P, _L, _I, _I, _P, _P, _P, _P, _P, _P, _I, _P, _L, _P, _P, _P, _P, _P]),
+    "wfl_align_windowed": (_I, [_P, _L, _I, _I, _P, _P, _P, _P, _P, _P, _P, _I, _P, _L, _P, _P, _P, _P, _P]),
     "wfl_align_posterior_workspace_bytes": (_L, [_P, _P, _I]),
     "wfl_align_posterior": (_I, [_P, _L, _I, _I, _P, _P, _P, _P, _P, _P, _I, _P, _P, _L, _P, _P, _P, _P, _P, _P]),
+    "wfl_align_posterior_windowed": (_I, [_P, _L, _I, _I, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _L, _P, _P, _P, _P, _P, _P]),
     "wfl_decode_workspace_bytes": (_L, [_P, _I, _I]),
     "wfl_decode": (_I, [_P, _L, _I, _I, _P, _P, _I, _P, _I, _F, _F, _P, _L, _P, _P, _P, _P]),
     "wfl_decode_posterior_workspace_bytes": (_L, [_P, _I, _I]),

@@ -6,13 +6,18 @@ posteriors: a missed, inserted or mislabelled phoneme shifts every later token o
 the frame logits for the best path that spells exactly the transcript, in order (csrc/align.hip, include/wfl_asr.h `wfl_align`): every
 token gets one contiguous, time-ordered run of frames, none is dropped.
 
-  viterbi_align         the C ABI on CUDA tensors: a ragged batch of clips in one call
-  alignment_posteriors  forward-backward over the same lattice (csrc/align_posterior.hip, `wfl_align_posterior`): logZ, and per token
+  viterbi_align         the C ABI on CUDA tensors: a ragged batch of clips in one call; with `windows`, every token may open only
+                        inside its (lo, hi) frame window (`wfl_align_windowed`, `postprocess.align_draft`)
+  alignment_posteriors  forward-backward over the same lattice (csrc/align_posterior.hip, `wfl_align_posterior`; of a batch packed with
+                        windows, `wfl_align_posterior_windowed`): logZ, and per token
                         the posterior of the run Viterbi chose and the spread of its start (`postprocess.align_scores`)
   file_score            those outputs + viterbi_align's score -> FileScore / TokenScore records
   token_alternatives    transcript tokens -> (B, I) class pairs of every phoneme whose output name is the token
   gap_classes           the classes a gap between tokens may take (O, and SP / AP unless the transcript spells them)
   path_segments         the path's ids / tokens, chunk by chunk, -> exactly one (start, end, token) per transcript token
+  windows_feasible      the host rule that predicts the windowed search's status 1
+  draft_windows         a draft's start times -> per-token windows on the file's rows, through the chunk clock
+  read_draft            the draft .lab of a file (phonotactics.read_lab, the HTK reader the bigram estimate uses)
 """
 from __future__ import annotations
 
@@ -33,6 +38,7 @@ PAUSES = ("SP", "AP")
 
 STATUS_OK, STATUS_INFEASIBLE, STATUS_OVER_CAP, STATUS_BAD_CLASS = 0, 1, 2, 4
 STATUS_NOT_A_PATH = 8      # wfl_align_posterior alone: `tok` is not a path of the clip's lattice
+OPEN_WINDOW = (0, 2 ** 31 - 1)   # a token that may open at any frame
 
 
 def workspace_bytes(n_frames, n_tokens) -> int:
@@ -82,16 +88,39 @@ class PackedClips(NamedTuple):
     K0: np.ndarray
     d_tc: torch.Tensor
     d_gc: torch.Tensor
+    d_win: torch.Tensor = None      # [tokens, 2] int32 (lo, hi) start windows; None: the unwindowed entries
 
 
-def pack_clips(logits, n_frames, token_classes, gap_classes, frame_offsets=None) -> PackedClips:
+def _pack_windows(windows, N):
+    """Per clip a list of (lo, hi) per token, or None for open windows -> [max(tokens, 1), 2] int32, rows as the token table's."""
+    if len(windows) != len(N):
+        raise ValueError("windows needs one entry per clip (None: open windows)")
+    out = np.empty((max(int(N.sum()), 1), 2), np.int64)
+    out[:] = OPEN_WINDOW
+    k0 = 0
+    for w, n in zip(windows, N):
+        if w is not None:
+            w = np.asarray(w, np.int64).reshape(-1, 2)
+            if len(w) != n:
+                raise ValueError(f"a clip with {n} tokens needs {n} (lo, hi) windows, got {len(w)}")
+            out[k0:k0 + n] = w
+        k0 += int(n)
+    if out.min() < -2 ** 31 or out.max() > 2 ** 31 - 1:
+        raise ValueError("window bounds are int32")
+    return out.astype(np.int32)
+
+
+def pack_clips(logits, n_frames, token_classes, gap_classes, frame_offsets=None, windows=None) -> PackedClips:
     """Validate a ragged batch and upload its token and gap tables once; pass the result as `packed=` to viterbi_align and to
-    alignment_posteriors of the same batch (the packing is host work that grows with the token count)."""
+    alignment_posteriors of the same batch (the packing is host work that grows with the token count).  windows: per clip a list of
+    (lo, hi) per token -- the frames, inclusive, at which the token may open -- or None for a clip with open windows; None for the
+    whole batch packs for the unwindowed entries."""
     nb, T, N, F0, K0, tc, gc = _pack_clips(logits, n_frames, token_classes, gap_classes, frame_offsets)
-    return PackedClips(nb, T, N, F0, K0, torch.from_numpy(tc).to(logits.device), torch.from_numpy(gc).to(logits.device))
+    d_win = torch.from_numpy(_pack_windows(windows, N)).to(logits.device) if windows is not None else None
+    return PackedClips(nb, T, N, F0, K0, torch.from_numpy(tc).to(logits.device), torch.from_numpy(gc).to(logits.device), d_win)
 
 
-def viterbi_align(logits, n_frames, token_classes, gap_classes, o_id, frame_offsets=None, stream=None, packed=None):
+def viterbi_align(logits, n_frames, token_classes, gap_classes, o_id, frame_offsets=None, stream=None, packed=None, windows=None):
     """Forced alignment of a ragged batch of clips on the GPU.
 
     logits         [rows, C] float32 CUDA tensor (rows contiguous in C; clip b = rows frame_offsets[b] .. + n_frames[b]).  With
@@ -101,10 +130,14 @@ def viterbi_align(logits, n_frames, token_classes, gap_classes, o_id, frame_offs
     gap_classes    per clip: 1..8 class ids a gap frame may take (gap_classes)
     frame_offsets  first row of each clip (default: the clips back to back)
     packed         pack_clips(...) of these same arguments, to share the packing with alignment_posteriors (default: packed here)
+    windows        per clip a list of (lo, hi) per token, or None for a clip without windows: token k may open (be in B_k) only at a
+                   frame lo <= t <= hi of its clip.  None (the default) runs wfl_align; anything else wfl_align_windowed, where a clip
+                   whose windows no path satisfies gets STATUS_INFEASIBLE (windows_feasible predicts it).  With `packed`, the windows
+                   are the ones packed there.
     -> (ids [rows] int32, tok [rows] int32, score [clips] float32, status [clips] int32), CUDA tensors on `stream`'s device."""
     lib = _lib.load()
-    nb, T, N, F0, K0, d_tc, d_gc = packed if packed is not None else pack_clips(logits, n_frames, token_classes, gap_classes,
-                                                                                frame_offsets)
+    nb, T, N, F0, K0, d_tc, d_gc, d_win = packed if packed is not None else pack_clips(logits, n_frames, token_classes, gap_classes,
+                                                                                       frame_offsets, windows)
     dev = logits.device
     rows = logits.shape[0]
     ws_n = workspace_bytes(T, N)
@@ -115,10 +148,13 @@ def viterbi_align(logits, n_frames, token_classes, gap_classes, o_id, frame_offs
     status = torch.empty(max(nb, 1), dtype=torch.int32, device=dev)
     with torch.cuda.device(dev):
         st = stream if stream is not None else torch.cuda.current_stream(dev)
-        rc = lib.wfl_align(_ptr(logits), logits.stride(0), logits.shape[1], int(o_id), _hp(F0), _hp(T), _hp(K0), _hp(N), _ptr(d_tc), _ptr(d_gc),
-                           nb, _ptr(ws), ws_n, _ptr(ids), _ptr(tok), _ptr(score), _ptr(status), C.c_void_p(st.cuda_stream))
-        _lib.check(rc, "wfl_align")
-        for t in (d_tc, d_gc, ws):
+        head = (_ptr(logits), logits.stride(0), logits.shape[1], int(o_id), _hp(F0), _hp(T), _hp(K0), _hp(N), _ptr(d_tc))
+        tail = (_ptr(d_gc), nb, _ptr(ws), ws_n, _ptr(ids), _ptr(tok), _ptr(score), _ptr(status), C.c_void_p(st.cuda_stream))
+        if d_win is None:
+            _lib.check(lib.wfl_align(*head, *tail), "wfl_align")
+        else:
+            _lib.check(lib.wfl_align_windowed(*head, _ptr(d_win), *tail), "wfl_align_windowed")
+        for t in (d_tc, d_gc, ws) + ((d_win,) if d_win is not None else ()):
             t.record_stream(st)
     return ids, tok, score[:nb], status[:nb]
 
@@ -137,15 +173,18 @@ def alignment_posteriors(logits, n_frames, token_classes, gap_classes, o_id, tok
     """Forward-backward over the lattice of viterbi_align, for the same ragged batch of clips (same arguments), given its `tok`.
 
     tok     [rows] int32 CUDA tensor: viterbi_align's output for these clips (row frame_offsets[b] + t)
-    packed  the pack_clips(...) result that viterbi_align ran on, when the batch is the same (default: packed here)
+    packed  the pack_clips(...) result that viterbi_align ran on, when the batch is the same (default: packed here).  Start windows
+            reach this function only through it: a batch packed with `windows` is scored by wfl_align_posterior_windowed, the sums
+            running over the windowed lattice (a `tok` with a token that opens outside its window is STATUS_NOT_A_PATH), so a
+            search and its scores share one lattice by sharing one PackedClips
     -> (logz [clips], tok_post [tokens], start_mean [tokens], start_sd [tokens], status [clips]): float32 / int32 CUDA tensors, the
     per-token ones in the order of the clips' tokens.  logz: log of the summed weight of every path that spells the transcript;
     tok_post: the posterior occupancy of the run Viterbi gave the token, in [0, 1]; start_mean / start_sd: mean (relative to
     Viterbi's start) and standard deviation of the token's start, in frames.  A clip with status != 0 gets zeros
     (STATUS_NOT_A_PATH: `tok` does not hold every token of the clip)."""
     lib = _lib.load()
-    nb, T, N, F0, K0, d_tc, d_gc = packed if packed is not None else pack_clips(logits, n_frames, token_classes, gap_classes,
-                                                                                frame_offsets)
+    nb, T, N, F0, K0, d_tc, d_gc, d_win = packed if packed is not None else pack_clips(logits, n_frames, token_classes, gap_classes,
+                                                                                       frame_offsets)
     dev = logits.device
     if not tok.is_cuda or tok.device != dev or tok.dtype != torch.int32 or tok.dim() != 1 or tok.stride(0) != 1 \
             or tok.shape[0] != logits.shape[0]:
@@ -158,11 +197,14 @@ def alignment_posteriors(logits, n_frames, token_classes, gap_classes, o_id, tok
     status = torch.empty(max(nb, 1), dtype=torch.int32, device=dev)
     with torch.cuda.device(dev):
         st = stream if stream is not None else torch.cuda.current_stream(dev)
-        rc = lib.wfl_align_posterior(_ptr(logits), logits.stride(0), logits.shape[1], int(o_id), _hp(F0), _hp(T), _hp(K0), _hp(N),
-                                     _ptr(d_tc), _ptr(d_gc), nb, _ptr(tok), _ptr(ws), ws_n, _ptr(logz), _ptr(per_tok[0]),
-                                     _ptr(per_tok[1]), _ptr(per_tok[2]), _ptr(status), C.c_void_p(st.cuda_stream))
-        _lib.check(rc, "wfl_align_posterior")
-        for t in (d_tc, d_gc, ws):
+        head = (_ptr(logits), logits.stride(0), logits.shape[1], int(o_id), _hp(F0), _hp(T), _hp(K0), _hp(N), _ptr(d_tc))
+        tail = (_ptr(d_gc), nb, _ptr(tok), _ptr(ws), ws_n, _ptr(logz), _ptr(per_tok[0]), _ptr(per_tok[1]), _ptr(per_tok[2]),
+                _ptr(status), C.c_void_p(st.cuda_stream))
+        if d_win is None:
+            _lib.check(lib.wfl_align_posterior(*head, *tail), "wfl_align_posterior")
+        else:
+            _lib.check(lib.wfl_align_posterior_windowed(*head, _ptr(d_win), *tail), "wfl_align_posterior_windowed")
+        for t in (d_tc, d_gc, ws) + ((d_win,) if d_win is not None else ()):
             t.record_stream(st)
     return logz[:nb], per_tok[0, :ntok], per_tok[1, :ntok], per_tok[2, :ntok], status[:nb]
 
@@ -254,6 +296,52 @@ def path_segments(ids, tok, chunk_frames, chunk_offsets, chunk_clock, table: npo
             g[1] = min(g[1], segs[j + 1][0])             # keep the segments from overlapping
         g[1] = max(g[1], g[0])                           # a one-frame run at a chunk's end closes on its own frame's end offset
     return [(a, b, transcript[k]) for a, b, k in segs]
+
+
+def windows_feasible(T, windows) -> bool:
+    """Whether some path of a T-frame clip opens every token inside its window, i.e. whether the windowed search will NOT report
+    STATUS_INFEASIBLE.  Tokens open at strictly increasing frames and nothing else constrains them (a token may be one frame long,
+    gaps may be empty), so the earliest feasible start of each token decides: e_k = max(lo_k, e_{k-1} + 1) <= min(hi_k, T - 1)."""
+    e = -1
+    for lo, hi in np.asarray(windows, np.int64).reshape(-1, 2):
+        e = max(int(lo), e + 1)
+        if e > min(int(hi), int(T) - 1):
+            return False
+    return True
+
+
+def draft_windows(draft_segments, chunk_frames, chunk_clock, tolerance_s, frame_duration):
+    """Start windows of a draft's tokens on the rows of a file's concatenated logits (chunk c: chunk_frames[c] rows, its first at
+    time chunk_clock[c] of the file) -> [(lo, hi)] per draft segment (start_s, ...).
+
+    A start time goes to a row THROUGH THE CHUNK CLOCK: its chunk is the last one whose clock is at or before the time (the first
+    chunk for an earlier time), the row inside it the nearest frame -- frame f spans [f, f + 1) frame durations from the chunk's
+    clock, as path_segments writes a start at (f + offset) frame durations, so the frame whose centre is nearest is
+    floor((t - clock) / frame_duration) -- kept inside the chunk.  (A .lab carries times truncated to 100 ns; a thousandth of a frame
+    is added before the floor.)  A division of the file time by the frame duration would drift off the rows wherever a chunk's clock
+    is no multiple of it.  lo / hi are the row -+ ceil(tolerance_s / frame_duration), clipped to the file's rows; a tolerance of 0
+    pins the row."""
+    frames = np.asarray(chunk_frames, np.int64).reshape(-1)
+    clock = np.asarray(chunk_clock, np.float64).reshape(-1)
+    if len(frames) != len(clock) or not len(frames):
+        raise ValueError("one clock value per chunk, at least one chunk")
+    first_row = np.concatenate([[0], np.cumsum(frames)[:-1]])
+    T = int(frames.sum())
+    tol = int(np.ceil(float(tolerance_s) / frame_duration - 1e-9))
+    out = []
+    for seg in draft_segments:
+        t = float(seg[0])
+        c = max(int(np.searchsorted(clock, t, side="right")) - 1, 0)
+        f = int(np.floor((t - clock[c]) / frame_duration + 1e-3))
+        row = int(first_row[c]) + min(max(f, 0), max(int(frames[c]) - 1, 0))
+        out.append((max(row - tol, 0), min(row + tol, T - 1)))
+    return out
+
+
+def read_draft(path):
+    """The draft .lab of a file -> [(start_s, end_s, label)]: phonotactics.read_lab, the package's HTK reader."""
+    from .phonotactics import read_lab
+    return read_lab(path)
 
 
 def with_end_pauses(free_segments, aligned, transcript):

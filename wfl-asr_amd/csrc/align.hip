@@ -25,6 +25,10 @@
 // The lattice itself -- caps, configurations, the shared LDS layout, setup and status codes, the logits stage ring, emissions, the
 // renormalisation halves, and the host side of a ragged batch -- is csrc/lattice.h, shared with csrc/align_posterior.hip.  Here: the
 // max-product recursion, the backpointers and the backtrace.
+//
+// wfl_align_windowed is the same kernel instantiated with WIN: every token's EB passes through lattice.h's win_mask (the token may open
+// only inside its window), and a clip whose best end state is -inf -- no path satisfies the windows -- reports status 1 before the
+// backtrace.  The unwindowed instantiation holds none of it.
 #include "lattice.h"
 #include "wfl_asr.h"
 
@@ -47,6 +51,7 @@ struct AlignLaunch {
   int* status;
   int n;
   LatClip clip[CLIPS_PER_LAUNCH];
+  const int* tok_win;  // [total tokens][2] = (lo, hi), the windowed kernels alone (last: the other fields stay where they were)
 };
 
 template <int NT, int R>
@@ -58,7 +63,8 @@ struct Cfg : LdsBase<NT, R, 2 * NT * 8> {                // its own between alt 
   static constexpr int LDS = OFF_MISC + 64;
 };
 
-template <int NT, int R>
+// WIN: the start windows of wfl_align_windowed (lattice.h win_mask); false is wfl_align's kernel, instruction for instruction
+template <int NT, int R, bool WIN>
 __global__ __launch_bounds__(NT) void align_kernel(AlignLaunch a) {
   using K = Cfg<NT, R>;
   extern __shared__ __attribute__((aligned(16))) char lds[];
@@ -104,6 +110,8 @@ __global__ __launch_bounds__(NT) void align_kernel(AlignLaunch a) {
   int4 av[R];                                   // this thread's slots' alternatives, for the whole forward pass
 #pragma unroll
   for (int r = 0; r < R; ++r) av[r] = alt[tid * R + r];
+  int2 wn[WIN ? R : 1];                         // this thread's slots' start windows, in registers
+  if constexpr (WIN) load_windows<R>(a.tok_win, cl.tok_off, N, wn);
   unsigned* bp = a.bp + cl.ws_off;
   double acc = 0.0;                            // what the renormalisations subtracted
   float sub = 0.f;
@@ -138,6 +146,7 @@ __global__ __launch_bounds__(NT) void align_kernel(AlignLaunch a) {
       if (B[r] > mi) { mi = B[r]; ci = 1; }
       float eb = NEG, ei = NEG;
       if (k < N) tok_emission(row, av[r], eb, ei);
+      if constexpr (WIN) eb = win_mask(eb, t, wn[r]);
       G[r] = k <= N ? m + eg : NEG;
       B[r] = m + eb;
       I[r] = mi + ei;
@@ -159,7 +168,9 @@ __global__ __launch_bounds__(NT) void align_kernel(AlignLaunch a) {
     __syncthreads();                           // the neighbour exchange and the renormalisation share it
     sub = 0.f;
     if (renorm) {
-      const float M = renorm_max<K::NW>(wmax);   // (taken as it is; the posterior sweeps replace an M of -inf by 0)
+      // (taken as it is; the posterior sweeps replace an M of -inf by 0.  Windows never make it -inf here: G_0 has no window and a
+      // finite emission at every frame, so it is finite at every frame and M with it)
+      const float M = renorm_max<K::NW>(wmax);
 #pragma unroll
       for (int r = 0; r < R; ++r) { G[r] -= M; B[r] -= M; I[r] -= M; }
       sub = M;
@@ -179,8 +190,16 @@ __global__ __launch_bounds__(NT) void align_kernel(AlignLaunch a) {
       if (fin[2] > best) { best = fin[2]; s = 3 * N - 2; }
     }
     misc[1] = s;
+    if constexpr (WIN) misc[2] = best == NEG;
   }
   __syncthreads();
+  if constexpr (WIN) {
+    if (misc[2]) {                              // no path opens every token inside its window: status 1, the backpointers never walked
+      for (int t = tid; t < T; t += NT) { ids[t] = a.o_id; tokp[t] = -1; }
+      if (tid == 0) { a.score[cl.clip] = 0.f; a.status[cl.clip] = 1; }
+      return;
+    }
+  }
 
   // ---- backtrace, ALIGN_W frames per window
   int s = misc[1];
@@ -267,20 +286,26 @@ int64_t wfl_align_workspace_bytes(const int32_t* n_frames_host, const int32_t* n
   return clips_workspace_bytes(n_frames_host, n_tok_host, n_clips, clip_words);
 }
 
-int32_t wfl_align(const float* logits, int64_t ldl, int32_t C, int32_t o_id, const int64_t* frame_off_host, const int32_t* n_frames_host,
-                  const int32_t* tok_off_host, const int32_t* n_tok_host, const int32_t* tok_cls, const int32_t* gap_cls, int32_t n_clips,
-                  void* workspace, int64_t workspace_bytes, int32_t* ids, int32_t* tok, float* score, int32_t* status, void* stream) {
-  const char* fn = "wfl_align";
+}  // extern "C"
+
+namespace {
+
+// wfl_align (WIN false) and wfl_align_windowed: one host path
+template <bool WIN>
+int align_batch(const char* fn, const float* logits, int64_t ldl, int32_t C, int32_t o_id, const int64_t* frame_off_host,
+                const int32_t* n_frames_host, const int32_t* tok_off_host, const int32_t* n_tok_host, const int32_t* tok_cls,
+                const int32_t* tok_win, const int32_t* gap_cls, int32_t n_clips, void* workspace, int64_t workspace_bytes, int32_t* ids,
+                int32_t* tok, float* score, int32_t* status, void* stream) {
   const int64_t need = wfl_align_workspace_bytes(n_frames_host, n_tok_host, n_clips);
   bool any_tok = false, any_frame = false;
   int rc = check_clip_args(fn, C, o_id, ldl, frame_off_host, n_frames_host, tok_off_host, n_tok_host, n_clips, need, any_tok, any_frame);
   if (rc || n_clips == 0) return rc;
-  if (!score || !status || !gap_cls || (any_tok && !tok_cls) || (any_frame && (!logits || !ids || !tok)))
+  if (!score || !status || !gap_cls || (any_tok && (!tok_cls || (WIN && !tok_win))) || (any_frame && (!logits || !ids || !tok)))
     return fail(fn, -1, "null device pointer");
   if ((rc = check_workspace(fn, need, workspace, workspace_bytes))) return rc;
   hipStream_t s = (hipStream_t)stream;
   AlignLaunch a{};
-  a.logits = logits; a.ldl = ldl; a.C = C; a.o_id = o_id; a.tok_cls = tok_cls; a.gap_cls = gap_cls;
+  a.logits = logits; a.ldl = ldl; a.C = C; a.o_id = o_id; a.tok_cls = tok_cls; a.gap_cls = gap_cls; a.tok_win = tok_win;
   a.bp = (unsigned*)workspace; a.ids = ids; a.tok = tok; a.score = score; a.status = status;
   return launch_clips<NCFG>(
       a, n_clips,
@@ -293,9 +318,28 @@ int32_t wfl_align(const float* logits, int64_t ldl, int32_t C, int32_t o_id, con
       [&](int cfg, const AlignLaunch& a) {
         return dispatch_cfg(cfg, [&](auto sh) {
           constexpr int NT = decltype(sh)::NT, R = decltype(sh)::R;
-          return launch_cfg<align_kernel<NT, R>, NT, Cfg<NT, R>::LDS>(fn, a, s);
+          return launch_cfg<align_kernel<NT, R, WIN>, NT, Cfg<NT, R>::LDS>(fn, a, s);
         });
       });
+}
+
+}  // namespace
+
+extern "C" {
+
+int32_t wfl_align(const float* logits, int64_t ldl, int32_t C, int32_t o_id, const int64_t* frame_off_host, const int32_t* n_frames_host,
+                  const int32_t* tok_off_host, const int32_t* n_tok_host, const int32_t* tok_cls, const int32_t* gap_cls, int32_t n_clips,
+                  void* workspace, int64_t workspace_bytes, int32_t* ids, int32_t* tok, float* score, int32_t* status, void* stream) {
+  return align_batch<false>("wfl_align", logits, ldl, C, o_id, frame_off_host, n_frames_host, tok_off_host, n_tok_host, tok_cls, nullptr,
+                            gap_cls, n_clips, workspace, workspace_bytes, ids, tok, score, status, stream);
+}
+
+int32_t wfl_align_windowed(const float* logits, int64_t ldl, int32_t C, int32_t o_id, const int64_t* frame_off_host,
+                           const int32_t* n_frames_host, const int32_t* tok_off_host, const int32_t* n_tok_host, const int32_t* tok_cls,
+                           const int32_t* tok_win, const int32_t* gap_cls, int32_t n_clips, void* workspace, int64_t workspace_bytes,
+                           int32_t* ids, int32_t* tok, float* score, int32_t* status, void* stream) {
+  return align_batch<true>("wfl_align_windowed", logits, ldl, C, o_id, frame_off_host, n_frames_host, tok_off_host, n_tok_host, tok_cls,
+                           tok_win, gap_cls, n_clips, workspace, workspace_bytes, ids, tok, score, status, stream);
 }
 
 }  // extern "C"

@@ -25,6 +25,10 @@
 // into a block buffer and sweep 3 walks beta down the block, combining.  Every thread reads back only what it wrote itself.
 // Workspace per clip: lse[T] | checkpoints' offsets | checkpoints | one block (wfl_align_posterior_workspace_bytes).
 //
+// wfl_align_posterior_windowed is the same kernel instantiated with WIN: EB passes through lattice.h's win_mask wherever it is gathered --
+// alpha, beta's own slots, and the next thread's first slot (ebn) -- with the windows of a thread's slots (and of that one slot) in
+// registers; a tok that opens a token outside its window is status 8, logZ = -inf status 1.
+//
 // The per-frame log-sum-exp of the logits is computed once (double, expf), stored in fp32 and subtracted from the gathered logits;
 // what the fp32 rounding of it loses is summed in double and given back to logZ (it is common to every path).
 #include "lattice.h"
@@ -54,6 +58,7 @@ struct PostLaunch {
   int* status;
   int n;
   LatClip clip[CLIPS_PER_LAUNCH];
+  const int* tok_win;  // [total tokens][2] = (lo, hi), the windowed kernels alone (last: the other fields stay where they were)
 };
 
 // a clip's workspace in floats: [lse: round64(T)] [checkpoint offsets: round64(2 nblk)] [checkpoints: nblk S] [block: POST_W S]
@@ -95,7 +100,9 @@ __device__ __forceinline__ float lae3(float a, float b, float c) {
   return ms + __logf(__expf(a - ms) + __expf(b - ms) + __expf(c - ms));
 }
 
-template <int NT, int R>
+// WIN: the start windows of wfl_align_posterior_windowed (lattice.h win_mask); false is wfl_align_posterior's kernel, instruction for
+// instruction
+template <int NT, int R, bool WIN>
 __global__ __launch_bounds__(NT) void post_kernel(PostLaunch a) {
   using K = PCfg<NT, R>;
   extern __shared__ __attribute__((aligned(16))) char lds[];
@@ -121,6 +128,14 @@ __global__ __launch_bounds__(NT) void post_kernel(PostLaunch a) {
 
   int g[NGAP];
   int st = lattice_setup<NT, R>(cl, C, a.tok_cls, a.gap_cls, alt, misc, g);
+  int2 wn[WIN ? R : 1];                        // this thread's slots' start windows, in registers, and the next thread's first slot's
+  int2 wnn = make_int2(0, WIN_OPEN_HI);
+  if constexpr (WIN) {
+    if (st == 0) {
+      load_windows<R>(a.tok_win, cl.tok_off, N, wn);
+      wnn = load_window(a.tok_win, cl.tok_off, (tid + 1) * R, N);
+    }
+  }
   if (st == 0 && T > 0) {
     // the first frame of every token's Viterbi run; a tok that is not a path of this lattice (a token missing, a value out of range)
 #pragma unroll
@@ -136,7 +151,13 @@ __global__ __launch_bounds__(NT) void post_kernel(PostLaunch a) {
     __syncthreads();
 #pragma unroll
     for (int r = 0; r < R; ++r)
-      if (tid * R + r < N && first[tid * R + r] == INT_MAX) misc[0] = 1;
+      if (tid * R + r < N) {
+        const int f = first[tid * R + r];
+        if (f == INT_MAX) misc[0] = 1;
+        if constexpr (WIN) {
+          if (f < wn[r].x || f > wn[r].y) misc[0] = 1;   // a token opens outside its window: not a path of this lattice either
+        }
+      }
     __syncthreads();
     if (misc[0]) st = 8;
   }
@@ -255,6 +276,7 @@ __global__ __launch_bounds__(NT) void post_kernel(PostLaunch a) {
           tok_emission(row, av[r], eb, ei);
           eb -= l;
           ei -= l;
+          if constexpr (WIN) eb = win_mask(eb, t, wn[r]);
         }
         G[r] = k <= N ? in + eg : NEG;
         B[r] = in + eb;
@@ -311,9 +333,23 @@ __global__ __launch_bounds__(NT) void post_kernel(PostLaunch a) {
     double s = 0.0;
     for (int i = 0; i < ne; ++i) s += exp((double)fin[i] - m);
     red[0] = m + log(s) + acc;
+    if constexpr (WIN) {
+      if (m == -INFINITY) red[0] = -INFINITY;   // no path opens every token inside its window
+    }
   }
   __syncthreads();                             // (ckacc[] of thread 0 is visible to the block as well)
   const double logZ = red[0];                  // on the fp32 log-sum-exps; the clip's logZ is logZ - lres
+  if constexpr (WIN) {
+    if (logZ == -INFINITY) {                   // status 1 and zeros, as every clip with a status
+      for (int k = tid; k < N; k += NT) {
+        a.tok_post[cl.tok_off + k] = 0.f;
+        a.start_mean[cl.tok_off + k] = 0.f;
+        a.start_sd[cl.tok_off + k] = 0.f;
+      }
+      if (tid == 0) { a.logz[cl.clip] = 0.f; a.status[cl.clip] = 1; }
+      return;
+    }
+  }
 
   // ---- sweeps 2 and 3, block by block from the end
   float bG[R], bX[R];                          // beta(G_k), beta(B_k) = beta(I_k)
@@ -391,6 +427,7 @@ __global__ __launch_bounds__(NT) void post_kernel(PostLaunch a) {
           tok_emission(row, av[r], eb[r], ei[r]);
           eb[r] -= l;
           ei[r] -= l;
+          if constexpr (WIN) eb[r] = win_mask(eb[r], t, wn[r]);
         }
       }
       float ebn = NEG;
@@ -398,6 +435,7 @@ __global__ __launch_bounds__(NT) void post_kernel(PostLaunch a) {
         float ein;
         tok_emission(row, avn, ebn, ein);
         ebn -= l;
+        if constexpr (WIN) ebn = win_mask(ebn, t, wnn);
       }
       float2 nb = tid + 1 < NT ? xb[((t + 1) & 1) * NT + tid + 1] : make_float2(NEG, NEG);
       nb.x -= subb;
@@ -464,27 +502,29 @@ long clip_floats(int T, int N) {
 
 }  // namespace
 
-extern "C" {
-
-int64_t wfl_align_posterior_workspace_bytes(const int32_t* n_frames_host, const int32_t* n_tok_host, int32_t n_clips) {
+extern "C" int64_t wfl_align_posterior_workspace_bytes(const int32_t* n_frames_host, const int32_t* n_tok_host, int32_t n_clips) {
   return clips_workspace_bytes(n_frames_host, n_tok_host, n_clips, clip_floats);
 }
 
-int32_t wfl_align_posterior(const float* logits, int64_t ldl, int32_t C, int32_t o_id, const int64_t* frame_off_host,
-                            const int32_t* n_frames_host, const int32_t* tok_off_host, const int32_t* n_tok_host, const int32_t* tok_cls,
-                            const int32_t* gap_cls, int32_t n_clips, const int32_t* tok, void* workspace, int64_t workspace_bytes,
-                            float* logz, float* tok_post, float* start_mean, float* start_sd, int32_t* status, void* stream) {
-  const char* fn = "wfl_align_posterior";
+namespace {
+
+// wfl_align_posterior (WIN false) and wfl_align_posterior_windowed: one host path
+template <bool WIN>
+int posterior_batch(const char* fn, const float* logits, int64_t ldl, int32_t C, int32_t o_id, const int64_t* frame_off_host,
+                    const int32_t* n_frames_host, const int32_t* tok_off_host, const int32_t* n_tok_host, const int32_t* tok_cls,
+                    const int32_t* tok_win, const int32_t* gap_cls, int32_t n_clips, const int32_t* tok, void* workspace,
+                    int64_t workspace_bytes, float* logz, float* tok_post, float* start_mean, float* start_sd, int32_t* status,
+                    void* stream) {
   const int64_t need = wfl_align_posterior_workspace_bytes(n_frames_host, n_tok_host, n_clips);
   bool any_tok = false, any_frame = false;
   int rc = check_clip_args(fn, C, o_id, ldl, frame_off_host, n_frames_host, tok_off_host, n_tok_host, n_clips, need, any_tok, any_frame);
   if (rc || n_clips == 0) return rc;
-  if (!logz || !status || !gap_cls || (any_tok && (!tok_cls || !tok_post || !start_mean || !start_sd)) || (any_frame && (!logits || !tok)))
+  if (!logz || !status || !gap_cls || (any_tok && (!tok_cls || (WIN && !tok_win) || !tok_post || !start_mean || !start_sd)) || (any_frame && (!logits || !tok)))
     return fail(fn, -1, "null device pointer");
   if ((rc = check_workspace(fn, need, workspace, workspace_bytes))) return rc;
   hipStream_t s = (hipStream_t)stream;
   PostLaunch a{};
-  a.logits = logits; a.ldl = ldl; a.C = C; a.tok_cls = tok_cls; a.gap_cls = gap_cls; a.tok = tok;
+  a.logits = logits; a.ldl = ldl; a.C = C; a.tok_cls = tok_cls; a.gap_cls = gap_cls; a.tok = tok; a.tok_win = tok_win;
   a.ws = (float*)workspace; a.logz = logz; a.tok_post = tok_post; a.start_mean = start_mean; a.start_sd = start_sd; a.status = status;
   return launch_clips<NCFG>(
       a, n_clips,
@@ -497,9 +537,32 @@ int32_t wfl_align_posterior(const float* logits, int64_t ldl, int32_t C, int32_t
       [&](int cfg, const PostLaunch& a) {
         return dispatch_cfg(cfg, [&](auto sh) {
           constexpr int NT = decltype(sh)::NT, R = decltype(sh)::R;
-          return launch_cfg<post_kernel<NT, R>, NT, PCfg<NT, R>::LDS>(fn, a, s);
+          return launch_cfg<post_kernel<NT, R, WIN>, NT, PCfg<NT, R>::LDS>(fn, a, s);
         });
       });
+}
+
+}  // namespace
+
+extern "C" {
+
+int32_t wfl_align_posterior(const float* logits, int64_t ldl, int32_t C, int32_t o_id, const int64_t* frame_off_host,
+                            const int32_t* n_frames_host, const int32_t* tok_off_host, const int32_t* n_tok_host, const int32_t* tok_cls,
+                            const int32_t* gap_cls, int32_t n_clips, const int32_t* tok, void* workspace, int64_t workspace_bytes,
+                            float* logz, float* tok_post, float* start_mean, float* start_sd, int32_t* status, void* stream) {
+  return posterior_batch<false>("wfl_align_posterior", logits, ldl, C, o_id, frame_off_host, n_frames_host, tok_off_host, n_tok_host,
+                                tok_cls, nullptr, gap_cls, n_clips, tok, workspace, workspace_bytes, logz, tok_post, start_mean, start_sd,
+                                status, stream);
+}
+
+int32_t wfl_align_posterior_windowed(const float* logits, int64_t ldl, int32_t C, int32_t o_id, const int64_t* frame_off_host,
+                                     const int32_t* n_frames_host, const int32_t* tok_off_host, const int32_t* n_tok_host,
+                                     const int32_t* tok_cls, const int32_t* tok_win, const int32_t* gap_cls, int32_t n_clips,
+                                     const int32_t* tok, void* workspace, int64_t workspace_bytes, float* logz, float* tok_post,
+                                     float* start_mean, float* start_sd, int32_t* status, void* stream) {
+  return posterior_batch<true>("wfl_align_posterior_windowed", logits, ldl, C, o_id, frame_off_host, n_frames_host, tok_off_host,
+                               n_tok_host, tok_cls, tok_win, gap_cls, n_clips, tok, workspace, workspace_bytes, logz, tok_post, start_mean,
+                               start_sd, status, stream);
 }
 
 }  // extern "C"

@@ -4,7 +4,8 @@
 //
 //   device  caps and constants, the per-clip record, the wave reductions, the (threads, slots per thread) configurations and their
 //           dispatch, the shared part of the LDS layout, lattice setup (status 0 / 1 / 2 / 4, the alternatives in LDS, the gap classes in
-//           registers), the staged logits ring, the emission gathers, the two halves of the block-maximum renormalisation, the end states
+//           registers), the staged logits ring, the emission gathers, the start-window mask of the windowed entries (win_mask: ONE mask
+//           for the search and for both sweeps of the sums), the two halves of the block-maximum renormalisation, the end states
 //   host    the argument checks the ABI entries share, "group the clips by configuration, hand out workspace offsets, launch at most
 //           64 clips at a time", and the launch that reserves a kernel's dynamic LDS once per device
 //
@@ -118,6 +119,26 @@ static __device__ __forceinline__ float gap_emission(const float* row, const int
   for (int j = 0; j < NGAP; ++j)
     if (g[j] >= 0) eg = fmaxf(eg, row[g[j]]);
   return eg;
+}
+
+// ---- start windows (wfl_align_windowed, wfl_align_posterior_windowed): token k may open, i.e. be in B_k, only at a frame lo <= t <= hi
+// (int32, inclusive; lo > hi: never).  That is EB_t(k) = -inf outside the window, and THE mask is win_mask: the max-product step, alpha
+// and both gathers of beta go through it, so the search and the sums run on one lattice.  The table has 36 KB at the cap and the largest
+// posterior configuration has no such LDS left, so every thread keeps the windows of its own R slots in registers (load_windows); the
+// backward sweep takes the next thread's first slot as well (load_window).
+constexpr int WIN_OPEN_HI = 0x7fffffff;
+
+static __device__ __forceinline__ float win_mask(float eb, int t, const int2& w) { return (t >= w.x && t <= w.y) ? eb : -INFINITY; }
+
+static __device__ __forceinline__ int2 load_window(const int* tok_win, int tok_off, int k, int N) {   // slots past the tokens: open
+  const int* p = tok_win + (long)(tok_off + k) * 2;
+  return k < N ? make_int2(p[0], p[1]) : make_int2(0, WIN_OPEN_HI);
+}
+
+template <int R>
+static __device__ __forceinline__ void load_windows(const int* tok_win, int tok_off, int N, int2 (&w)[R]) {
+#pragma unroll
+  for (int r = 0; r < R; ++r) w[r] = load_window(tok_win, tok_off, threadIdx.x * R + r, N);
 }
 
 // ---- lattice setup of a clip -> status: 2 over the cap (of the ABI or of this configuration), 1 fewer frames than tokens, 4 a class id

@@ -7,7 +7,7 @@ batched loop over 30 s work items.
                                every clip <= 30 s and every 30 s chunk of a longer file is one batch row; rows of many
                                files share a forward; `lang_id=None` averages logits/offsets over all languages
                                inside the library (encoder runs once; infer.py:146-156, 266-276)
-  options.resolve              the post-processing options of a request (align, decode, the scores, the phone bigram): resolved
+  options.resolve              the post-processing options of a request (align, decode, the scores, the phone bigram, the draft): resolved
                                once per request into a PostOptions record, and once before any model is loaded (options.py)
   deviations (documented in DESIGN.md): no `.wfl_cache` (infer.py:223-229), `--sample/--top-k/--top-p/--temperature`
   are validated but have no effect (their results are overwritten in the reference too, infer.py:283-297), a single
@@ -20,6 +20,7 @@ import math
 import os
 import sys
 from concurrent.futures import ThreadPoolExecutor
+from typing import NamedTuple
 
 import numpy as np
 import torch
@@ -419,7 +420,8 @@ class Labeler:
         return self._bigram_cache[key]
 
     def label_files(self, audio_paths, lang_id=None, confidence_threshold=0.0, verbose=True, align=None, align_scores=None,
-                    decode=None, switch_penalty=None, decode_scores=None, phoneme_bigram=None, bigram_weight=None, bigram_scores=None):
+                    decode=None, switch_penalty=None, decode_scores=None, phoneme_bigram=None, bigram_weight=None, align_draft=None,
+                    draft_tolerance=None, bigram_scores=None):
         """-> list (per file) of [(start_s, end_s, phoneme)] after merge + forced alignment; with align_scores, decode_scores or
         bigram_scores, (that list, scores).
 
@@ -453,17 +455,25 @@ class Labeler:
         bigram_scores (with a phoneme_bigram only; None: config postprocess.bigram_scores, else off): decode_scores for a bigram
         decode -- the same scores[i] records, from a forward-backward pass over the grammar with the bigram's transition table
         (decode.decode_posteriors_bigram), so the posterior scores the grammar the search ran on.  The segments are the same with and
-        without."""
+        without.
+
+        align_draft (with align "viterbi" only; None: config postprocess.align_draft, else none): a folder of draft .lab files, the
+        draft of X.wav being DIR/X.lab.  A file with a draft is aligned to the draft's label sequence (SP / AP included as tokens, as
+        when a .txt spells them; it wins over a .txt that spells something else, with a message), every token opening within
+        draft_tolerance seconds (>= 0; None: config postprocess.draft_tolerance, else 0.1) of its draft start: the windowed search
+        of align.viterbi_align, and with align_scores the windowed forward-backward over the same lattice.  A draft whose windows no
+        path satisfies (align.windows_feasible) falls back, with a message, to the unwindowed search of the same transcript.  Files
+        without a draft are handled as without the option."""
         opts = self.options(align=align, align_scores=align_scores, decode=decode, switch_penalty=switch_penalty,
                             decode_scores=decode_scores, phoneme_bigram=phoneme_bigram, bigram_weight=bigram_weight,
-                            bigram_scores=bigram_scores)
+                            bigram_scores=bigram_scores, align_draft=align_draft, draft_tolerance=draft_tolerance)
         final, scores = self._label_scored(audio_paths, opts, lang_id, confidence_threshold, verbose)
         return (final, scores) if opts.scored else final
 
-    def _label_scored(self, audio_paths, opts, lang_id, confidence_threshold, verbose):
+    def _label_scored(self, audio_paths, opts, lang_id, confidence_threshold, verbose, moves=None):
         """label_files for the resolved options `opts`, always -> (segments, scores): the files are split once into those a transcript is
         Viterbi-aligned to, those the grammar search decodes and those left to the argmax decode, and each subset's results go back to
-        its files' places."""
+        its files' places.  moves: a dict that takes {file index: [DraftMove]} for the files aligned inside their draft's windows."""
         trans = self._bigram_table(opts.phoneme_bigram, opts.switch_penalty, opts.bigram_weight) if opts.phoneme_bigram else None
         if opts.decode == "viterbi" and int(self.config["postprocess"].get("median_filter", 0)) > 1:
             print("decode: viterbi -- postprocess.median_filter is not applied (the switch penalty takes its place)")
@@ -474,6 +484,8 @@ class Labeler:
         free, with_t = list(range(len(audio_paths))), []
         if opts.align == "viterbi":
             forced = [_read_forced(p, verbose) for p in audio_paths]
+            drafts = [_read_draft(p, opts.align_draft, forced[fi]) if opts.align_draft else None for fi, p in enumerate(audio_paths)]
+            forced = [tr if dr is None else [s[2] for s in dr] for tr, dr in zip(forced, drafts)]
             with_t = [fi for fi in free if forced[fi] is not None]
             free = [fi for fi in free if forced[fi] is None]
 
@@ -494,10 +506,13 @@ class Labeler:
         for fi, segs in searched.items():
             final[fi] = self._match_forced(audio_paths[fi], segs, verbose)
         if with_t:
+            moved = {}
             got = self._label_viterbi(paths(with_t), [forced[fi] for fi in with_t], lang_id, confidence_threshold, verbose,
-                                      opts.align_scores)
+                                      opts.align_scores, [drafts[fi] for fi in with_t], opts.draft_tolerance, moved)
             for fi, segs, sc in zip(with_t, *got):
                 final[fi], scores[fi] = segs, sc
+            if moves is not None:
+                moves.update({with_t[j]: m for j, m in moved.items()})
         return final, scores
 
     def _label_files_greedy(self, audio_paths, lang_id, confidence_threshold, verbose):
@@ -772,14 +787,22 @@ class Labeler:
                 n_frames += int(frames[b])
         return total, total_logz, total_lse, n_frames, skipped
 
-    def _label_viterbi(self, audio_paths, transcripts, lang_id, threshold, verbose, want_scores=False):
+    def _label_viterbi(self, audio_paths, transcripts, lang_id, threshold, verbose, want_scores=False, drafts=None, tolerance=0.0,
+                       moves=None):
         """Files with a transcript, align="viterbi".  Their chunks are forwarded with logits (kept on the device); the free decode of
         the same forward gives the greedy result, which the pause rule at the ends needs and which a file falls back to (with a
         message) when its transcript cannot be aligned.  Each file's chunks' valid logits rows are concatenated on the device, so
         one search covers the whole file; the files of a wave go to wfl_align as one ragged batch and only ids / tok / score / status
         come back to the host.  -> (results, [FileScore or None per file]); want_scores: right after the search, one
         wfl_align_posterior call per wave over the clips it aligned (same logits, the device `tok`), one more small copy to the host;
-        without, every score is None."""
+        without, every score is None.
+
+        drafts: per file its draft segments or None (postprocess.align_draft; the transcript is then the draft's labels).  The start
+        windows of a file with a draft (align.draft_windows, `tolerance` seconds either side) join the same ragged batch, which then
+        goes through the windowed entries: the search, and the posterior over the lattice the search ran on.  A file whose windows
+        no path satisfies is searched without them, with a message: align.windows_feasible finds it before the launch, and a clip the
+        kernel still reports infeasible inside its windows is searched again without them.  moves: a dict that takes
+        {file index: [DraftMove]} for the files aligned inside their windows."""
         lang_name = self._lang_name(lang_id)
         remap, names = self._names_for(lang_name)
         results, scores = [], []
@@ -809,19 +832,46 @@ class Labeler:
             if run:
                 frames, lg = self._file_rows(rows, by_file, run)
                 gaps = [AL.gap_classes(self.labels, transcripts[fi]) for fi in run]
-                packed = AL.pack_clips(lg, frames, [plans[fi] for fi in run], gaps) if want_scores else None
+                wins = [None] * len(run)                      # per clip its tokens' start windows; None: none (open)
+                for b, fi in enumerate(run):
+                    if drafts is not None and drafts[fi] is not None:
+                        cf, _, cc = self._chunk_plan(rows, by_file[fi], fi)
+                        w = AL.draft_windows(drafts[fi], cf, cc, tolerance, frame_duration)
+                        if AL.windows_feasible(frames[b], w):
+                            wins[b] = w
+                        else:
+                            print(f"{audio_paths[fi]}: {DRAFT_INFEASIBLE}")
+                windows = wins if any(w is not None for w in wins) else None      # (no draft in the wave: the unwindowed entries)
+                packed = AL.pack_clips(lg, frames, [plans[fi] for fi in run], gaps, windows=windows) if want_scores else None
                 d_ids, d_tok, d_score, d_st = AL.viterbi_align(lg, frames, [plans[fi] for fi in run], gaps, self.labels.index("O"),
-                                                               packed=packed)
-                ids_all, tok_all, st_all = d_ids.cpu().numpy(), d_tok.cpu().numpy(), d_st.cpu().numpy()
+                                                               packed=packed, windows=windows)
+                st_all = d_st.cpu().numpy()
+                f0 = np.concatenate([[0], np.cumsum(np.asarray(frames, np.int64))[:-1]])
+                again = [b for b in range(len(run)) if wins[b] is not None and st_all[b] == AL.STATUS_INFEASIBLE]
+                if again:                                     # the safety net: the kernel found no path inside the windows
+                    for b in again:
+                        print(f"{audio_paths[run[b]]}: {DRAFT_INFEASIBLE}")
+                        wins[b] = None
+                    r_ids, r_tok, r_score, r_st = AL.viterbi_align(lg, [frames[b] for b in again], [plans[run[b]] for b in again],
+                                                                   [gaps[b] for b in again], self.labels.index("O"),
+                                                                   frame_offsets=f0[again])
+                    for j, b in enumerate(again):
+                        rows_b = slice(int(f0[b]), int(f0[b]) + frames[b])
+                        d_ids[rows_b], d_tok[rows_b] = r_ids[rows_b], r_tok[rows_b]
+                        d_score[b], d_st[b] = r_score[j], r_st[j]
+                    st_all = d_st.cpu().numpy()
+                    windows = wins if any(w is not None for w in wins) else None
+                    packed = None                             # (packed for the windows that were dropped)
+                ids_all, tok_all = d_ids.cpu().numpy(), d_tok.cpu().numpy()
                 raw = {}                                      # file -> (score, logz, tok_post, start_mean, start_sd)
                 bad_post = {}
                 ok = [b for b in range(len(run)) if st_all[b] == AL.STATUS_OK]
                 if want_scores and ok:
-                    f0 = np.concatenate([[0], np.cumsum(np.asarray(frames, np.int64))[:-1]])
                     # (only the clips the search aligned; when that is all of them, on the tables the search was given)
-                    d_post = AL.alignment_posteriors(lg, [frames[b] for b in ok], [plans[run[b]] for b in ok], [gaps[b] for b in ok],
-                                                     self.labels.index("O"), d_tok, frame_offsets=f0[ok],
-                                                     packed=packed if len(ok) == len(run) else None)
+                    sub = ([frames[b] for b in ok], [plans[run[b]] for b in ok], [gaps[b] for b in ok])
+                    if packed is None or len(ok) != len(run):  # (the windows travel in the packed batch: the lattice of the search)
+                        packed = AL.pack_clips(lg, *sub, f0[ok], windows=[wins[b] for b in ok] if windows is not None else None)
+                    d_post = AL.alignment_posteriors(lg, *sub, self.labels.index("O"), d_tok, frame_offsets=f0[ok], packed=packed)
                     nt = sum(len(plans[run[b]]) for b in ok)
                     h = torch.cat([d_score[ok], *d_post[:4], d_post[4].to(torch.float32)]).cpu().numpy()      # one copy
                     n_ok = len(ok)
@@ -848,6 +898,8 @@ class Labeler:
                         segs = AL.path_segments(ids_all[pos:pos + n], tok_all[pos:pos + n], *self._chunk_plan(rows, by_file[fi], fi),
                                                 self._table, plans[fi], tr, frame_duration)
                         aligned[fi] = AL.with_end_pauses(free_segs[fi], segs, tr)
+                        if wins[b] is not None and moves is not None:
+                            moves[fi] = draft_moves(drafts[fi], segs, tok_all[pos:pos + n], wins[b])
                         if fi in raw:
                             post[fi] = AL.file_score(raw[fi][0], raw[fi][1], n, *raw[fi][2:], segs, frame_duration)
                         elif want_scores:                     # (wfl_align_posterior refused the path wfl_align gave it)
@@ -865,6 +917,59 @@ def _clip_lse(lg, starts, ends):
     differences of one running sum in double."""
     run = torch.cat([lg.new_zeros(1, dtype=torch.float64), torch.logsumexp(lg, dim=1).double().cumsum(0)])
     return run[torch.from_numpy(ends).to(lg.device)] - run[torch.from_numpy(starts).to(lg.device)]
+
+
+DRAFT_INFEASIBLE = ("no path opens every token inside its draft window (two starts on one frame, or more tokens than frames in between); "
+                    "aligning the draft's transcript without windows")
+
+
+class DraftMove(NamedTuple):
+    index: int              # the token's place in the transcript
+    token: str
+    draft_start_s: float
+    start_s: float          # the token's start in the new .lab
+    on_edge: bool           # the token opens on the first or the last frame of its window: it wants to be elsewhere
+
+    @property
+    def move_s(self) -> float:
+        return self.start_s - self.draft_start_s
+
+
+def draft_moves(draft, segments, tok, windows):
+    """Per token of a file aligned inside its draft's windows -> [DraftMove]: draft (start_s, end_s, label) and segments
+    (path_segments) one per token in order, tok the file's per-frame token index, windows the (lo, hi) rows the search was held to."""
+    tok = np.asarray(tok)
+    opens = np.nonzero((tok >= 0) & (np.concatenate([[-1], tok[:-1]]) != tok))[0]        # one frame per token, in order
+    first = {int(tok[t]): int(t) for t in opens[::-1]}
+    return [DraftMove(k, str(seg[2]), float(dr[0]), float(seg[0]), first[k] in (int(lo), int(hi)))
+            for k, (dr, seg, (lo, hi)) in enumerate(zip(draft, segments, windows))]
+
+
+def format_draft_moves_tsv(named_moves) -> str:
+    """`draft_moves.tsv` of a folder: [(file name, [DraftMove])] -> one line per token, `file index token draft_start start move_s
+    on_edge`, draft_start / start being the integers a .lab line carries.  on_edge = 1 is the QA list: a token pressed against its
+    window wants to leave the neighbourhood its draft put it in."""
+    lines = ["# file\tindex\ttoken\tdraft_start\tstart\tmove_s\ton_edge"]
+    for name, ms in named_moves:
+        for m in ms:
+            lines.append(f"{name}\t{m.index}\t{m.token}\t{_lab_int(m.draft_start_s)}\t{_lab_int(m.start_s)}\t{m.move_s:+.4f}\t"
+                         f"{int(m.on_edge)}")
+    return "\n".join(lines) + "\n"
+
+
+def _read_draft(audio_path, draft_dir, forced):
+    """The draft of X.wav: DIR/X.lab -> its segments, or None when there is none (no file, or a file without a segment).  forced: the
+    file's `{audio}.txt` transcript or None; one line when it spells something else than the draft, which wins."""
+    lab = os.path.join(draft_dir, os.path.splitext(os.path.basename(audio_path))[0] + ".lab")
+    if not os.path.isfile(lab):
+        return None
+    draft = AL.read_draft(lab)
+    if not draft:
+        print(f"{audio_path}: the draft {lab} holds no segment; the file is handled without it")
+        return None
+    if forced is not None and forced != [s[2] for s in draft]:
+        print(f"{audio_path}: the transcript beside the audio spells something else than the draft {lab}; the draft wins")
+    return draft
 
 
 def _read_forced(audio_path, verbose):
@@ -993,7 +1098,7 @@ def _write_score(lab_path, segments, score):
 def infer_audio(audio_path, config_path="config.yaml", checkpoint_path="best_model.pt", output_lab_path=None, device="cuda",
                 lang_id=None, sample=False, top_k=0, top_p=0.0, temperature=1.0, confidence_threshold=0.0, align=None,
                 align_scores=None, decode=None, switch_penalty=None, decode_scores=None, phoneme_bigram=None, bigram_weight=None,
-                bigram_scores=None):
+                align_draft=None, draft_tolerance=None, bigram_scores=None):
     """align: "greedy" | "viterbi" | None (config postprocess.align, else greedy): how a `{audio}.txt` transcript is aligned
     (Labeler.label_files).  align_scores (viterbi only; None: config postprocess.align_scores): also write `{stem}.scores.tsv`
     beside the .lab when the file was Viterbi-aligned (format_scores_tsv).  decode: "argmax" | "viterbi" | None (config
@@ -1002,9 +1107,12 @@ def infer_audio(audio_path, config_path="config.yaml", checkpoint_path="best_mod
     `{stem}.decode_scores.tsv` beside the .lab when the grammar search decoded the file (format_decode_scores_tsv).  phoneme_bigram /
     bigram_weight (decode viterbi only; None: config postprocess.phoneme_bigram / postprocess.bigram_weight): the phone-bigram prior
     of the search (Labeler.label_files).  bigram_scores (with a phoneme_bigram only; None: config postprocess.bigram_scores):
-    decode_scores for a bigram decode, the same `{stem}.decode_scores.tsv`."""
+    decode_scores for a bigram decode, the same `{stem}.decode_scores.tsv`.  align_draft / draft_tolerance (align viterbi only; None:
+    config postprocess.align_draft / postprocess.draft_tolerance): refine the draft DIR/{stem}.lab inside per-token start windows
+    (Labeler.label_files)."""
     given = dict(align=align, align_scores=align_scores, decode=decode, switch_penalty=switch_penalty, decode_scores=decode_scores,
-                 phoneme_bigram=phoneme_bigram, bigram_weight=bigram_weight, bigram_scores=bigram_scores)
+                 phoneme_bigram=phoneme_bigram, bigram_weight=bigram_weight, bigram_scores=bigram_scores, align_draft=align_draft,
+                 draft_tolerance=draft_tolerance)
     _refuse_before_load(config_path, **given)
     lab = _labeler(config_path, checkpoint_path, device)
     (segments,), (score,) = lab._label_scored([audio_path], lab.options(**given), lang_id, confidence_threshold, True)
@@ -1020,9 +1128,11 @@ def infer_audio(audio_path, config_path="config.yaml", checkpoint_path="best_mod
 def infer_folder(folder_path: str, config_path: str = "config.yaml", checkpoint_path: str = "best_model.pt",
                  output_dir: str = "outputs", device: str = "cuda", lang_id: int = None, sample=False, top_k=0, top_p=0.0,
                  temperature=1.0, confidence_threshold=0.0, align=None, align_scores=None, decode=None, switch_penalty=None,
-                 decode_scores=None, phoneme_bigram=None, bigram_weight=None, bigram_scores=None):
+                 decode_scores=None, phoneme_bigram=None, bigram_weight=None, align_draft=None, draft_tolerance=None,
+                 bigram_scores=None):
     given = dict(align=align, align_scores=align_scores, decode=decode, switch_penalty=switch_penalty, decode_scores=decode_scores,
-                 phoneme_bigram=phoneme_bigram, bigram_weight=bigram_weight, bigram_scores=bigram_scores)
+                 phoneme_bigram=phoneme_bigram, bigram_weight=bigram_weight, bigram_scores=bigram_scores, align_draft=align_draft,
+                 draft_tolerance=draft_tolerance)
     _refuse_before_load(config_path, **given)
     wav_files = sorted(f for f in os.listdir(folder_path) if f.lower().endswith(".wav"))
     os.makedirs(output_dir, exist_ok=True)
@@ -1035,7 +1145,8 @@ def infer_folder(folder_path: str, config_path: str = "config.yaml", checkpoint_
     lab = _labeler(config_path, checkpoint_path, device)
     paths = [os.path.join(folder_path, f) for f in wav_files]
     opts = lab.options(**given)
-    all_segments, all_scores = lab._label_scored(paths, opts, lang_id, confidence_threshold, True) if paths else ([], [])
+    moves = {}
+    all_segments, all_scores = lab._label_scored(paths, opts, lang_id, confidence_threshold, True, moves) if paths else ([], [])
     for wav_file, segments, score in zip(wav_files, all_segments, all_scores):
         print(f"\nInferencing: {wav_file}")
         lab_path = os.path.join(output_dir, os.path.splitext(wav_file)[0] + ".lab")
@@ -1048,6 +1159,10 @@ def infer_folder(folder_path: str, config_path: str = "config.yaml", checkpoint_
         name = "alignment_scores.tsv" if world == 1 else f"alignment_scores.rank{rank}.tsv"
         _write_text(os.path.join(output_dir, name),
                     format_review_tsv([(f, sc) for f, sc in zip(wav_files, all_scores) if isinstance(sc, AL.FileScore)]), "Review list")
+    if opts.align_draft:
+        name = "draft_moves.tsv" if world == 1 else f"draft_moves.rank{rank}.tsv"
+        _write_text(os.path.join(output_dir, name), format_draft_moves_tsv([(wav_files[fi], moves[fi]) for fi in sorted(moves)]),
+                    "Draft moves")
     if opts.free_scores:
         name = "decode_scores.tsv" if world == 1 else f"decode_scores.rank{rank}.tsv"
         _write_text(os.path.join(output_dir, name),
@@ -1100,8 +1215,16 @@ def main(argv=None):
                   help="With --phoneme-bigram: --decode-scores for the bigram decode; the same {stem}.decode_scores.tsv and "
                        "decode_scores.tsv, from a forward-backward pass over the grammar with the bigram's table on the GPU. Default: "
                        "config postprocess.bigram_scores, else off.")
+    @click.option("--align-draft", "align_draft", type=str, default=None,
+                  help="With --align viterbi: a folder of draft .lab files (X.wav -> DIR/X.lab). A file with a draft is aligned to the "
+                       "draft's labels, every token opening within --draft-tolerance of its draft start; for a folder also "
+                       "draft_moves.tsv. Default: config postprocess.align_draft, else none.")
+    @click.option("--draft-tolerance", "draft_tolerance", type=float, default=None,
+                  help="With --align-draft: seconds either side of a draft start in which the token may open (>= 0; 0 pins the "
+                       "frame). Default: config postprocess.draft_tolerance, else 0.1.")
     def cli(path, checkpoint, config, output, lang_id, sample, top_k, top_p, temperature, device, confidence_threshold, align,
-            align_scores, decode, switch_penalty, decode_scores, phoneme_bigram, bigram_weight, bigram_scores):
+            align_scores, decode, switch_penalty, decode_scores, phoneme_bigram, bigram_weight, bigram_scores, align_draft,
+            draft_tolerance):
         if switch_penalty is not None and not switch_penalty >= 0.0:
             raise click.UsageError("--switch-penalty must be >= 0 (nats)")
         if sample:
@@ -1133,7 +1256,7 @@ def main(argv=None):
         try:
             opts = resolve(cfg["postprocess"], align=align, align_scores=align_scores, decode=decode, switch_penalty=switch_penalty,
                            decode_scores=decode_scores, phoneme_bigram=phoneme_bigram, bigram_weight=bigram_weight,
-                           bigram_scores=bigram_scores)
+                           bigram_scores=bigram_scores, align_draft=align_draft, draft_tolerance=draft_tolerance)
         except ValueError as err:
             raise click.UsageError(str(err))
         output_path = inf_path if output == "." else output
@@ -1149,7 +1272,9 @@ def main(argv=None):
                   # an argument that is given wins over the config, so "no bigram" travels as an empty path, and a weight only beside
                   # the search it belongs to (with another decode none was given, or resolve had refused it)
                   phoneme_bigram=opts.phoneme_bigram or "",
-                  bigram_weight=opts.bigram_weight if opts.decode == "viterbi" else None)
+                  bigram_weight=opts.bigram_weight if opts.decode == "viterbi" else None,
+                  # the draft travels the same way: an empty path for "none", a tolerance only beside a draft
+                  align_draft=opts.align_draft or "", draft_tolerance=opts.draft_tolerance if opts.align_draft else None)
         if inf_path.is_dir():
             infer_folder(folder_path=str(inf_path), output_dir=str(output_path), **kw)
         else:

@@ -13,6 +13,8 @@ infer_folder (before any model is loaded) and the CLI all call `resolve` and car
                             8. decode_scores with a phoneme_bigram is refused (BIGRAM_SCORES_ERROR): a posterior must score the
                                grammar its search ran on, and decode_scores' pass knows the flat switch penalty only
   bigram_scores   off       9. needs decode viterbi, and then a phoneme_bigram
+  align_draft     none     10. needs align viterbi (the draft's windows hold that search)
+  draft_tolerance 0.1      11. when given, a number >= 0 (seconds; no bool), and then needs an align_draft
 """
 from __future__ import annotations
 
@@ -21,12 +23,14 @@ from typing import NamedTuple, Optional
 ALIGN_MODES = ("greedy", "viterbi")
 DECODE_MODES = ("argmax", "viterbi")
 
+DEFAULT_DRAFT_TOLERANCE = 0.1     # seconds; a default to start from, not a measured optimum
+
 BIGRAM_SCORES_ERROR = ("decode_scores cannot be combined with a phoneme bigram: the forward-backward pass scores the flat switch "
                        "penalty, not the bigram the search ran on; ask for bigram_scores (postprocess.bigram_scores, --bigram-scores) "
                        "instead, which scores the bigram's own grammar")
 
 
-class PostOptions(NamedTuple):
+class _SearchOptions(NamedTuple):
     align: str = "greedy"
     align_scores: bool = False
     decode: str = "argmax"
@@ -46,6 +50,55 @@ class PostOptions(NamedTuple):
         return self.align_scores or self.free_scores
 
 
+class PostOptions(_SearchOptions):
+    """The record `resolve` returns.  The eight options of the searches are the tuple (positional, `_fields`, as they have been);
+    the draft's two follow them as keyword fields with defaults, read-only like the rest and part of equality, hash and repr:
+
+        align_draft      None   folder of draft .lab files (X.wav -> DIR/X.lab); an empty path is None
+        draft_tolerance  0.1    seconds either side of a draft start (also stands for "not given")"""
+    align_draft: Optional[str] = None
+    draft_tolerance: float = DEFAULT_DRAFT_TOLERANCE
+
+    def __new__(cls, *args, align_draft=None, draft_tolerance=DEFAULT_DRAFT_TOLERANCE, **kw):
+        self = super().__new__(cls, *args, **kw)
+        object.__setattr__(self, "align_draft", align_draft)
+        object.__setattr__(self, "draft_tolerance", draft_tolerance)
+        return self
+
+    def __setattr__(self, name, value):
+        raise AttributeError(f"PostOptions is read-only: cannot set {name!r}")
+
+    def _draft(self):
+        return self.align_draft, self.draft_tolerance
+
+    # the NamedTuple helpers carry the two keyword fields as well (the inherited ones know the tuple alone)
+    @classmethod
+    def _make(cls, iterable, align_draft=None, draft_tolerance=DEFAULT_DRAFT_TOLERANCE):
+        return cls(*iterable, align_draft=align_draft, draft_tolerance=draft_tolerance)
+
+    def _replace(self, **kw):
+        draft = {k: kw.pop(k, getattr(self, k)) for k in ("align_draft", "draft_tolerance")}
+        return type(self)(*super()._replace(**kw), **draft)
+
+    def _asdict(self):
+        return {**super()._asdict(), "align_draft": self.align_draft, "draft_tolerance": self.draft_tolerance}
+
+    def __eq__(self, other):
+        """Equal to another PostOptions with the same ten values; to a plain tuple of the eight only while the draft's two are
+        at their defaults (where a PostOptions of those eight would be equal, too)."""
+        theirs = other._draft() if isinstance(other, PostOptions) else (None, DEFAULT_DRAFT_TOLERANCE)
+        return tuple.__eq__(self, other) is True and self._draft() == theirs
+
+    def __ne__(self, other):
+        return not self == other
+
+    def __hash__(self):     # (equal to a plain tuple only with the default draft fields: then the tuple's own hash)
+        return tuple.__hash__(self) if self._draft() == (None, DEFAULT_DRAFT_TOLERANCE) else hash((tuple(self), self._draft()))
+
+    def __repr__(self):
+        return super().__repr__()[:-1] + f", align_draft={self.align_draft!r}, draft_tolerance={self.draft_tolerance!r})"
+
+
 def _number_ge0(x):
     """float(x) for a number >= 0; None for anything else (a bool, a NaN, a negative, a string that is no number)."""
     try:
@@ -56,7 +109,7 @@ def _number_ge0(x):
 
 
 def resolve(post, *, align=None, align_scores=None, decode=None, switch_penalty=None, decode_scores=None, phoneme_bigram=None,
-            bigram_weight=None, bigram_scores=None) -> PostOptions:
+            bigram_weight=None, bigram_scores=None, align_draft=None, draft_tolerance=None) -> PostOptions:
     """post: the config's `postprocess` mapping (None: {}).  Per option the argument wins; None leaves it to `post[<option>]`, and a
     key that is absent (or None) to the default.  -> PostOptions, or ValueError for the first broken rule of the module's table."""
     post = post or {}
@@ -100,4 +153,16 @@ def resolve(post, *, align=None, align_scores=None, decode=None, switch_penalty=
     if bigram_scores and not phoneme_bigram:
         raise ValueError("bigram_scores needs a phoneme_bigram (postprocess.phoneme_bigram): it scores the bigram search's path; "
                          "decode_scores scores a search under the flat switch penalty")
-    return PostOptions(align, align_scores, decode, switch_penalty, decode_scores, phoneme_bigram, bigram_weight, bigram_scores)
+    align_draft = pick("align_draft", align_draft)
+    align_draft = str(align_draft) if align_draft else None
+    if align_draft and align != "viterbi":
+        raise ValueError("align_draft needs align='viterbi' (postprocess.align: viterbi): the draft's windows hold the Viterbi search, "
+                         "the greedy match has none")
+    given = pick("draft_tolerance", draft_tolerance)
+    draft_tolerance = DEFAULT_DRAFT_TOLERANCE if given is None else _number_ge0(given)
+    if draft_tolerance is None:
+        raise ValueError(f"draft_tolerance must be a number >= 0 (seconds), got {given!r}")
+    if given is not None and not align_draft:
+        raise ValueError("draft_tolerance needs an align_draft (postprocess.align_draft): it is the half-width of the draft's windows")
+    return PostOptions(align, align_scores, decode, switch_penalty, decode_scores, phoneme_bigram, bigram_weight, bigram_scores,
+                       align_draft=align_draft, draft_tolerance=draft_tolerance)
