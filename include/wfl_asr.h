@@ -386,6 +386,34 @@ int32_t wfl_align_posterior_windowed(const float* logits, int64_t ldl, int32_t C
                                      const int32_t* tok, void* workspace, int64_t workspace_bytes, float* logz, float* tok_post,
                                      float* start_mean, float* start_sd, int32_t* status, void* stream);
 
+/* ---- Single-edit scores of an aligned transcript (`postprocess.align_edits`; wfl-asr_amd/align.py, csrc/align_edits.hip).  No
+ * counterpart in the reference.  The arguments are wfl_align_posterior_windowed's without tok; tok_win may be null: the unwindowed
+ * lattice.  sub_cls (device, [n_sub][2] int32 = (B class, I class)) is a table of P = n_sub substitutes, 0 <= P <= 512.  With logZ(.)
+ * what wfl_align_posterior / wfl_align_posterior_windowed return for a transcript, outputs (device):
+ *   logz[b]          logZ of the clip's transcript as written (wfl_align_posterior's logz);
+ *   edits[k][p]      (rows tok_off_host[b] + k, P + 1 fp32 columns) for p < P: logZ(the transcript whose token k has the single alternative
+ *                    sub_cls[p]; everything else, k's window included, unchanged) - logZ(transcript);
+ *   edits[k][P]      logZ(the transcript without token k and without its window) - logZ(transcript).
+ *                    A log likelihood ratio: positive when the edited transcript explains the audio better; -inf when the edited
+ *                    transcript has no path (windows).  If token k has exactly one alternative and it is row p, edits[k][p] is 0 up to
+ *                    rounding;
+ *   status[b]        wfl_align_posterior's codes without 8: 0 ok, 1 infeasible (T < N, or no path satisfies the windows), 2 N above
+ *                    4096, 4 a class id out of range or no gap class -- and 4 for EVERY clip when a class id of sub_cls is out of range.
+ *                    A clip with status != 0 gets logz = 0 and zeros in its edits rows.
+ * The sums run over all boundaries, not Viterbi's: one forward and one backward sweep of the clip (one workgroup per clip, fp32 log
+ * domain renormalised every 16 frames, per-frame offsets in double) leave, per frame and token, the mass that may enter the token, the
+ * mass that follows it and the next token's entry; then one wave per (token, 64 substitutes) runs the N P chains of T steps.  Clips are
+ * independent: a clip scored alone equals the same clip inside any batch, bit for bit.
+ * Workspace per clip, in 4-byte words (every part rounded up to 64; 0 for T = 0), W = round_up_64(min(N, 4096)):
+ *     64 + T + 2 (T + 1) + 2 T + (T + 1) W + 2 T W
+ * about 3 N T floats: 5.3 MB for 1500 frames and 300 tokens, 740 MB at T = 15000, N = 4096.  wfl_align_edits_workspace_bytes returns the
+ * sum in bytes.  Arguments are checked on the host as wfl_align checks its own (negative return). */
+int64_t wfl_align_edits_workspace_bytes(const int32_t* n_frames_host, const int32_t* n_tok_host, int32_t n_clips);
+int32_t wfl_align_edits(const float* logits, int64_t ldl, int32_t C, int32_t o_id, const int64_t* frame_off_host,
+                        const int32_t* n_frames_host, const int32_t* tok_off_host, const int32_t* n_tok_host, const int32_t* tok_cls,
+                        const int32_t* tok_win, const int32_t* gap_cls, int32_t n_clips, const int32_t* sub_cls, int32_t n_sub,
+                        void* workspace, int64_t workspace_bytes, float* logz, float* edits, int32_t* status, void* stream);
+
 /* ---- BIO-grammar Viterbi decode of clips WITHOUT a transcript on the GPU (`postprocess.decode: viterbi`; wfl-asr_amd/decode.py).
  * Stands beside the reference's free decode, infer.py:86-96, 164-174, 293-302 (per-frame argmax, confidence threshold, median filter
  * over the ids, then the BIO decoder), which knows nothing of the grammar it decodes.  Clip b has T = n_frames_host[b] logits rows (row

@@ -11,6 +11,11 @@ token gets one contiguous, time-ordered run of frames, none is dropped.
   alignment_posteriors  forward-backward over the same lattice (csrc/align_posterior.hip, `wfl_align_posterior`; of a batch packed with
                         windows, `wfl_align_posterior_windowed`): logZ, and per token
                         the posterior of the run Viterbi chose and the spread of its start (`postprocess.align_scores`)
+  edit_scores           per token the log likelihood ratio of every single substitution from a table and of the token's deletion
+                        (csrc/align_edits.hip, `wfl_align_edits`; `postprocess.align_edits`), on the same lattice, windows included
+  substitute_table      the (B, I) pairs of a label set, the table edit_scores takes
+  edit_groups           clips -> groups whose edit_scores workspace stays under EDITS_WORKSPACE_LIMIT
+  token_edits / write_edits_tsv / write_folder_edits   one file's rows of {stem}.edits.tsv, the file itself, the folder's list
   file_score            those outputs + viterbi_align's score -> FileScore / TokenScore records
   token_alternatives    transcript tokens -> (B, I) class pairs of every phoneme whose output name is the token
   gap_classes           the classes a gap between tokens may take (O, and SP / AP unless the transcript spells them)
@@ -39,6 +44,10 @@ PAUSES = ("SP", "AP")
 STATUS_OK, STATUS_INFEASIBLE, STATUS_OVER_CAP, STATUS_BAD_CLASS = 0, 1, 2, 4
 STATUS_NOT_A_PATH = 8      # wfl_align_posterior alone: `tok` is not a path of the clip's lattice
 OPEN_WINDOW = (0, 2 ** 31 - 1)   # a token that may open at any frame
+MAX_SUBSTITUTES = 512      # wfl_align_edits' table cap
+# edit_scores keeps about 3 N T floats per clip (5.3 MB for a 30 s clip of 300 tokens, 740 MB at the caps): the Labeler scores the
+# aligned files in groups whose workspace stays under this many bytes (a single clip above it runs alone)
+EDITS_WORKSPACE_LIMIT = 1 << 30
 
 
 def workspace_bytes(n_frames, n_tokens) -> int:
@@ -207,6 +216,80 @@ def alignment_posteriors(logits, n_frames, token_classes, gap_classes, o_id, tok
         for t in (d_tc, d_gc, ws) + ((d_win,) if d_win is not None else ()):
             t.record_stream(st)
     return logz[:nb], per_tok[0, :ntok], per_tok[1, :ntok], per_tok[2, :ntok], status[:nb]
+
+
+def edits_workspace_bytes(n_frames, n_tokens) -> int:
+    lib = _lib.load()
+    T = np.ascontiguousarray(n_frames, np.int32)
+    N = np.ascontiguousarray(n_tokens, np.int32)
+    n = int(lib.wfl_align_edits_workspace_bytes(_hp(T), _hp(N), T.size))
+    if n < 0:
+        raise _lib.WflError("wfl_align_edits_workspace_bytes: negative frame or token count")
+    return n
+
+
+def edit_scores(logits, n_frames, token_classes, gap_classes, o_id, substitutes, frame_offsets=None, stream=None, packed=None):
+    """Single-edit scores of the transcripts of a ragged batch of clips (viterbi_align's arguments), on the lattice of the search.
+
+    substitutes  P (B class, I class) pairs, 0 <= P <= MAX_SUBSTITUTES (substitute_table)
+    packed       the pack_clips(...) result the search ran on; start windows reach this function only through it, as they reach
+                 alignment_posteriors: a batch packed with `windows` is scored on the windowed lattice
+    -> (logz [clips] float32, edits [tokens, P + 1] float32, status [clips] int32), CUDA tensors, the rows in the order of the clips'
+    tokens.  edits[k, p] = logZ(transcript with token k replaced by substitute p alone) - logZ(transcript), edits[k, P] the same for
+    the transcript without token k (and without its window): positive where the edit explains the audio better, -inf where the
+    edited transcript has no path.  logz is alignment_posteriors' logz.  A clip with status != 0 gets zeros; a class id of
+    `substitutes` outside the logits' columns is STATUS_BAD_CLASS for every clip."""
+    lib = _lib.load()
+    nb, T, N, F0, K0, d_tc, d_gc, d_win = packed if packed is not None else pack_clips(logits, n_frames, token_classes, gap_classes,
+                                                                                       frame_offsets)
+    sub = np.asarray(substitutes, np.int64).reshape(-1, 2)
+    P = len(sub)
+    if P > MAX_SUBSTITUTES:
+        raise ValueError(f"at most {MAX_SUBSTITUTES} substitutes, got {P}")
+    if P and (sub.min() < -2 ** 31 or sub.max() > 2 ** 31 - 1):
+        raise ValueError("class ids are int32")
+    dev = logits.device
+    d_sub = torch.from_numpy(np.ascontiguousarray(sub if P else np.zeros((1, 2)), np.int32)).to(dev)
+    ntok = int(N.sum())
+    ws_n = edits_workspace_bytes(T, N)
+    ws = torch.empty(max(ws_n, 1), dtype=torch.uint8, device=dev)
+    logz = torch.empty(max(nb, 1), dtype=torch.float32, device=dev)
+    edits = torch.empty((max(ntok, 1), P + 1), dtype=torch.float32, device=dev)
+    status = torch.empty(max(nb, 1), dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        st = stream if stream is not None else torch.cuda.current_stream(dev)
+        _lib.check(lib.wfl_align_edits(_ptr(logits), logits.stride(0), logits.shape[1], int(o_id), _hp(F0), _hp(T), _hp(K0), _hp(N),
+                                       _ptr(d_tc), _ptr(d_win) if d_win is not None else None, _ptr(d_gc), nb, _ptr(d_sub), P,
+                                       _ptr(ws), ws_n, _ptr(logz), _ptr(edits), _ptr(status), C.c_void_p(st.cuda_stream)),
+                   "wfl_align_edits")
+        for t in (d_tc, d_gc, ws, d_sub) + ((d_win,) if d_win is not None else ()):
+            t.record_stream(st)
+    return logz[:nb], edits[:ntok], status[:nb]
+
+
+def substitute_table(label_list):
+    """-> (names, pairs): every phoneme of the label set that has both tags, in label order (of its B- tag), and its (B class,
+    I class) pair -- the table edit_scores takes."""
+    pairs = class_pairs(label_list)
+    names = [tag[2:] for tag in label_list if tag.startswith("B-") and tag[2:] in pairs]
+    return names, [pairs[ph] for ph in names]
+
+
+def edit_groups(n_frames, n_tokens, limit=None):
+    """Indices of the clips, in order, in groups whose edit_scores workspace stays under `limit` bytes (EDITS_WORKSPACE_LIMIT); a
+    clip that is over it alone is a group of its own."""
+    limit = EDITS_WORKSPACE_LIMIT if limit is None else limit
+    groups, cur, used = [], [], 0
+    for j, (t, n) in enumerate(zip(n_frames, n_tokens)):
+        need = edits_workspace_bytes([t], [n])
+        if cur and used + need > limit:
+            groups.append(cur)
+            cur, used = [], 0
+        cur.append(j)
+        used += need
+    if cur:
+        groups.append(cur)
+    return groups
 
 
 # ---------------------------------------------------------------------------------------------------------------- host helpers
@@ -383,3 +466,80 @@ def file_score(score, logz, n_frames, tok_post, start_mean, start_sd, segments, 
     toks = [TokenScore(str(ph), float(s), float(e), float(p), float(sd) * frame_duration, float(mu) * frame_duration)
             for (s, e, ph), p, mu, sd in zip(segments, tok_post, start_mean, start_sd)]
     return FileScore(score - logz, score / n, logz / n, float(tok_post.min()) if len(tok_post) else 1.0, toks)
+
+
+# ------------------------------------------------------------------------------------------------------------- transcript edits
+class TokenEdit(NamedTuple):
+    index: int
+    token: str
+    start_s: float
+    end_s: float
+    best: str               # output name of the best substitute ("" when the table holds none for this token)
+    best_ratio: float       # its log likelihood ratio against the transcript as written (-inf: none)
+    second: str
+    second_ratio: float
+    deletion_ratio: float   # the same for the transcript without the token
+    flag: int               # 1 when the largest of the three ratios is > 0: an edit explains the audio better
+
+    @property
+    def largest(self) -> float:
+        return max(self.best_ratio, self.second_ratio, self.deletion_ratio)
+
+
+def substitute_output_names(sub_names, table: npost.LabelTable, remap, names):
+    """The output name of every substitute of substitute_table, through the merge-map back-mapping (`remap` / `names` of
+    Labeler._names_for) that token_alternatives uses."""
+    out_of = {ph: names[int(remap[p])] for p, ph in enumerate(table.names)}
+    return [out_of.get(ph, ph) for ph in sub_names]
+
+
+def token_edits(edits, segments, sub_out_names):
+    """One file's TokenEdit rows from its rows of edit_scores' `edits` [tokens, P + 1] (host values) and its aligned segments
+    [(start_s, end_s, token)].  Substitutes whose output name is the token's own are skipped; of several substitutes with one output
+    name (a merge map) the best one stands for the name, so best and second are two different names."""
+    edits = np.asarray(edits, np.float64).reshape(len(segments), -1)
+    if edits.shape[1] != len(sub_out_names) + 1:
+        raise ValueError("one column per substitute and one for the deletion")
+    rows = []
+    for k, (s, e, tokn) in enumerate(segments):
+        by_name = {}
+        for p, name in enumerate(sub_out_names):
+            if name != tokn and edits[k, p] > by_name.get(name, -np.inf):
+                by_name[name] = float(edits[k, p])
+        order = sorted(by_name.items(), key=lambda kv: -kv[1])[:2]      # (stable: the table's order decides a tie)
+        order += [("", -np.inf)] * (2 - len(order))
+        dele = float(edits[k, -1])
+        rows.append(TokenEdit(k, str(tokn), float(s), float(e), order[0][0], order[0][1], order[1][0], order[1][1], dele,
+                              int(max(order[0][1], dele) > 0)))
+    return rows
+
+
+EDITS_HEADER = "index\ttoken\tstart_s\tend_s\tbest\tbest_log_ratio\tsecond\tsecond_log_ratio\tdeletion_log_ratio\tflag"
+
+
+def _edit_cells(r: TokenEdit):
+    return [str(r.index), r.token, f"{r.start_s:.7f}", f"{r.end_s:.7f}", r.best, f"{r.best_ratio:.6g}", r.second,
+            f"{r.second_ratio:.6g}", f"{r.deletion_ratio:.6g}", str(r.flag)]
+
+
+def write_edits_tsv(path, rows):
+    """{stem}.edits.tsv: one line per transcript token."""
+    with open(path, "w", encoding="utf-8") as f:
+        f.write(EDITS_HEADER + "\n")
+        for r in rows:
+            f.write("\t".join(_edit_cells(r)) + "\n")
+
+
+def folder_edit_rows(per_file):
+    """per_file: [(file name, [TokenEdit])] -> every flagged token as (file name, TokenEdit), by its largest ratio, descending (ties
+    keep the files' and the tokens' order)."""
+    flagged = [(name, r) for name, rows in per_file for r in rows if r.flag]
+    return sorted(flagged, key=lambda x: -x[1].largest)
+
+
+def write_folder_edits(path, per_file):
+    """transcript_edits.tsv: folder_edit_rows, the file's name in front of the token's own columns."""
+    with open(path, "w", encoding="utf-8") as f:
+        f.write("file\t" + EDITS_HEADER + "\n")
+        for name, r in folder_edit_rows(per_file):
+            f.write("\t".join([name] + _edit_cells(r)) + "\n")

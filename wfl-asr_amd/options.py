@@ -15,6 +15,7 @@ infer_folder (before any model is loaded) and the CLI all call `resolve` and car
   bigram_scores   off       9. needs decode viterbi, and then a phoneme_bigram
   align_draft     none     10. needs align viterbi (the draft's windows hold that search)
   draft_tolerance 0.1      11. when given, a number >= 0 (seconds; no bool), and then needs an align_draft
+  align_edits     off      12. needs align viterbi (the edits are scored on the lattice of that search)
 """
 from __future__ import annotations
 
@@ -52,51 +53,60 @@ class _SearchOptions(NamedTuple):
 
 class PostOptions(_SearchOptions):
     """The record `resolve` returns.  The eight options of the searches are the tuple (positional, `_fields`, as they have been);
-    the draft's two follow them as keyword fields with defaults, read-only like the rest and part of equality, hash and repr:
+    the later ones follow them as keyword fields with defaults, read-only like the rest and part of equality, hash and repr:
 
         align_draft      None   folder of draft .lab files (X.wav -> DIR/X.lab); an empty path is None
-        draft_tolerance  0.1    seconds either side of a draft start (also stands for "not given")"""
+        draft_tolerance  0.1    seconds either side of a draft start (also stands for "not given")
+        align_edits      False  score single substitutions and deletions of every aligned transcript"""
     align_draft: Optional[str] = None
     draft_tolerance: float = DEFAULT_DRAFT_TOLERANCE
+    align_edits: bool = False
 
-    def __new__(cls, *args, align_draft=None, draft_tolerance=DEFAULT_DRAFT_TOLERANCE, **kw):
+    def __new__(cls, *args, align_draft=None, draft_tolerance=DEFAULT_DRAFT_TOLERANCE, align_edits=False, **kw):
         self = super().__new__(cls, *args, **kw)
         object.__setattr__(self, "align_draft", align_draft)
         object.__setattr__(self, "draft_tolerance", draft_tolerance)
+        object.__setattr__(self, "align_edits", align_edits)
         return self
 
     def __setattr__(self, name, value):
         raise AttributeError(f"PostOptions is read-only: cannot set {name!r}")
 
+    _KEYWORD = ("align_draft", "draft_tolerance", "align_edits")
+    _KEYWORD_DEFAULTS = (None, DEFAULT_DRAFT_TOLERANCE, False)
+
     def _draft(self):
         return self.align_draft, self.draft_tolerance
 
-    # the NamedTuple helpers carry the two keyword fields as well (the inherited ones know the tuple alone)
+    def _later(self):
+        return self.align_draft, self.draft_tolerance, self.align_edits
+
+    # the NamedTuple helpers carry the keyword fields as well (the inherited ones know the tuple alone)
     @classmethod
-    def _make(cls, iterable, align_draft=None, draft_tolerance=DEFAULT_DRAFT_TOLERANCE):
-        return cls(*iterable, align_draft=align_draft, draft_tolerance=draft_tolerance)
+    def _make(cls, iterable, align_draft=None, draft_tolerance=DEFAULT_DRAFT_TOLERANCE, align_edits=False):
+        return cls(*iterable, align_draft=align_draft, draft_tolerance=draft_tolerance, align_edits=align_edits)
 
     def _replace(self, **kw):
-        draft = {k: kw.pop(k, getattr(self, k)) for k in ("align_draft", "draft_tolerance")}
-        return type(self)(*super()._replace(**kw), **draft)
+        later = {k: kw.pop(k, getattr(self, k)) for k in self._KEYWORD}
+        return type(self)(*super()._replace(**kw), **later)
 
     def _asdict(self):
-        return {**super()._asdict(), "align_draft": self.align_draft, "draft_tolerance": self.draft_tolerance}
+        return {**super()._asdict(), **{k: getattr(self, k) for k in self._KEYWORD}}
 
     def __eq__(self, other):
-        """Equal to another PostOptions with the same ten values; to a plain tuple of the eight only while the draft's two are
-        at their defaults (where a PostOptions of those eight would be equal, too)."""
-        theirs = other._draft() if isinstance(other, PostOptions) else (None, DEFAULT_DRAFT_TOLERANCE)
-        return tuple.__eq__(self, other) is True and self._draft() == theirs
+        """Equal to another PostOptions with the same values; to a plain tuple of the eight only while the keyword fields are at
+        their defaults (where a PostOptions of those eight would be equal, too)."""
+        theirs = other._later() if isinstance(other, PostOptions) else self._KEYWORD_DEFAULTS
+        return tuple.__eq__(self, other) is True and self._later() == theirs
 
     def __ne__(self, other):
         return not self == other
 
-    def __hash__(self):     # (equal to a plain tuple only with the default draft fields: then the tuple's own hash)
-        return tuple.__hash__(self) if self._draft() == (None, DEFAULT_DRAFT_TOLERANCE) else hash((tuple(self), self._draft()))
+    def __hash__(self):     # (equal to a plain tuple only with the default keyword fields: then the tuple's own hash)
+        return tuple.__hash__(self) if self._later() == self._KEYWORD_DEFAULTS else hash((tuple(self), self._later()))
 
     def __repr__(self):
-        return super().__repr__()[:-1] + f", align_draft={self.align_draft!r}, draft_tolerance={self.draft_tolerance!r})"
+        return super().__repr__()[:-1] + "".join(f", {k}={getattr(self, k)!r}" for k in self._KEYWORD) + ")"
 
 
 def _number_ge0(x):
@@ -109,7 +119,7 @@ def _number_ge0(x):
 
 
 def resolve(post, *, align=None, align_scores=None, decode=None, switch_penalty=None, decode_scores=None, phoneme_bigram=None,
-            bigram_weight=None, bigram_scores=None, align_draft=None, draft_tolerance=None) -> PostOptions:
+            bigram_weight=None, bigram_scores=None, align_draft=None, draft_tolerance=None, align_edits=None) -> PostOptions:
     """post: the config's `postprocess` mapping (None: {}).  Per option the argument wins; None leaves it to `post[<option>]`, and a
     key that is absent (or None) to the default.  -> PostOptions, or ValueError for the first broken rule of the module's table."""
     post = post or {}
@@ -164,5 +174,9 @@ def resolve(post, *, align=None, align_scores=None, decode=None, switch_penalty=
         raise ValueError(f"draft_tolerance must be a number >= 0 (seconds), got {given!r}")
     if given is not None and not align_draft:
         raise ValueError("draft_tolerance needs an align_draft (postprocess.align_draft): it is the half-width of the draft's windows")
+    align_edits = bool(pick("align_edits", align_edits, False))
+    if align_edits and align != "viterbi":
+        raise ValueError("align_edits needs align='viterbi' (postprocess.align: viterbi): the greedy match has no lattice to score an "
+                         "edit on")
     return PostOptions(align, align_scores, decode, switch_penalty, decode_scores, phoneme_bigram, bigram_weight, bigram_scores,
-                       align_draft=align_draft, draft_tolerance=draft_tolerance)
+                       align_draft=align_draft, draft_tolerance=draft_tolerance, align_edits=align_edits)
