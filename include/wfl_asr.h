@@ -414,6 +414,29 @@ int32_t wfl_align_edits(const float* logits, int64_t ldl, int32_t C, int32_t o_i
                         const int32_t* tok_win, const int32_t* gap_cls, int32_t n_clips, const int32_t* sub_cls, int32_t n_sub,
                         void* workspace, int64_t workspace_bytes, float* logz, float* edits, int32_t* status, void* stream);
 
+/* ---- Single-insertion scores of an aligned transcript (`postprocess.align_insertions`; wfl-asr_amd/align.py, csrc/align_edits.hip):
+ * the third single edit beside wfl_align_edits' substitution and deletion.  No counterpart in the reference.  The arguments are
+ * wfl_align_edits' (tok_win may be null; sub_cls holds P = n_sub substitutes, 0 <= P <= 512).  A clip of N tokens has N + 1 places:
+ * place j lies in front of token j, place N behind the last token; N = 0 is a legal clip with one place.  Outputs (device):
+ *   logz[b]          wfl_align_posterior's (wfl_align_posterior_windowed's) logz of the transcript as written, as wfl_align_edits';
+ *   ins[row][p]      (P fp32 columns) logZ(the transcript with a token whose single alternative is sub_cls[p] inserted at place j, the
+ *                    new token without a window, every other token with its own) - logZ(transcript).  -inf when the longer transcript
+ *                    has no path: every entry of a clip with T = N, and whatever the neighbours' windows leave no frame for;
+ *   status[b]        wfl_align_edits' codes.  A clip with status != 0 gets logz = 0 and zeros in its rows.
+ * Rows: clip b owns the N_b + 1 rows tok_off_host[b] + b + j, j = 0 .. N_b, of a buffer of (total tokens + n_clips) rows.  This rests
+ * on the clips' token ranges lying in clip order (tok_off_host[b + 1] >= tok_off_host[b] + n_tok_host[b]), as pack_clips lays them out.
+ * The sweeps are wfl_align_edits' (the same kernel, instantiated with planes one slot wider); then one wave per (place, 64
+ * substitutes) runs the (N + 1) P chains.  Clips are independent, bit for bit.  N = 4096 is legal.
+ * Workspace per clip, in 4-byte words (every part rounded up to 64; 0 for T = 0), W = round_up_64(min(N, 4096) + 1):
+ *     64 + T + 2 (T + 1) + 2 T + (T + 1) W + T W
+ * wfl_align_insertions_workspace_bytes returns the sum in bytes.  Arguments are checked on the host as wfl_align_edits checks its own;
+ * ins may be null only when n_sub is 0. */
+int64_t wfl_align_insertions_workspace_bytes(const int32_t* n_frames_host, const int32_t* n_tok_host, int32_t n_clips);
+int32_t wfl_align_insertions(const float* logits, int64_t ldl, int32_t C, int32_t o_id, const int64_t* frame_off_host,
+                             const int32_t* n_frames_host, const int32_t* tok_off_host, const int32_t* n_tok_host, const int32_t* tok_cls,
+                             const int32_t* tok_win, const int32_t* gap_cls, int32_t n_clips, const int32_t* sub_cls, int32_t n_sub,
+                             void* workspace, int64_t workspace_bytes, float* logz, float* ins, int32_t* status, void* stream);
+
 /* ---- BIO-grammar Viterbi decode of clips WITHOUT a transcript on the GPU (`postprocess.decode: viterbi`; wfl-asr_amd/decode.py).
  * Stands beside the reference's free decode, infer.py:86-96, 164-174, 293-302 (per-frame argmax, confidence threshold, median filter
  * over the ids, then the BIO decoder), which knows nothing of the grammar it decodes.  Clip b has T = n_frames_host[b] logits rows (row

@@ -81,6 +81,8 @@ SIGNATURES = {
     "wfl_align_posterior_windowed": (_I, [_P, _L, _I, _I, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _L, _P, _P, _P, _P, _P, _P]),
     "wfl_align_edits_workspace_bytes": (_L, [_P, _P, _I]),
     "wfl_align_edits": (_I, [_P, _L, _I, _I, _P, _P, _P, _P, _P, _P, _P, _I, _P, _I, _P, _L, _P, _P, _P, _P]),
+    "wfl_align_insertions_workspace_bytes": (_L, [_P, _P, _I]),
+    "wfl_align_insertions": (_I, [_P, _L, _I, _I, _P, _P, _P, _P, _P, _P, _P, _I, _P, _I, _P, _L, _P, _P, _P, _P]),
     "wfl_decode_workspace_bytes": (_L, [_P, _I, _I]),
     "wfl_decode": (_I, [_P, _L, _I, _I, _P, _P, _I, _P, _I, _F, _F, _P, _L, _P, _P, _P, _P]),
     "wfl_decode_posterior_workspace_bytes": (_L, [_P, _I, _I]),

@@ -16,6 +16,9 @@ token gets one contiguous, time-ordered run of frames, none is dropped.
   substitute_table      the (B, I) pairs of a label set, the table edit_scores takes
   edit_groups           clips -> groups whose edit_scores workspace stays under EDITS_WORKSPACE_LIMIT
   token_edits / write_edits_tsv / write_folder_edits   one file's rows of {stem}.edits.tsv, the file itself, the folder's list
+  insertion_scores      per place (in front of every token, and behind the last) the log likelihood ratio of inserting every phoneme
+                        of a table there (csrc/align_edits.hip, `wfl_align_insertions`; `postprocess.align_insertions`)
+  place_insertions / write_insertions_tsv / write_folder_insertions   the same three for {stem}.insertions.tsv
   file_score            those outputs + viterbi_align's score -> FileScore / TokenScore records
   token_alternatives    transcript tokens -> (B, I) class pairs of every phoneme whose output name is the token
   gap_classes           the classes a gap between tokens may take (O, and SP / AP unless the transcript spells them)
@@ -267,6 +270,56 @@ def edit_scores(logits, n_frames, token_classes, gap_classes, o_id, substitutes,
     return logz[:nb], edits[:ntok], status[:nb]
 
 
+def insertions_workspace_bytes(n_frames, n_tokens) -> int:
+    lib = _lib.load()
+    T = np.ascontiguousarray(n_frames, np.int32)
+    N = np.ascontiguousarray(n_tokens, np.int32)
+    n = int(lib.wfl_align_insertions_workspace_bytes(_hp(T), _hp(N), T.size))
+    if n < 0:
+        raise _lib.WflError("wfl_align_insertions_workspace_bytes: negative frame or token count")
+    return n
+
+
+def insertion_scores(logits, n_frames, token_classes, gap_classes, o_id, substitutes, frame_offsets=None, stream=None, packed=None):
+    """Single-insertion scores of the transcripts of a ragged batch of clips (edit_scores' arguments), on the lattice of the search.
+
+    substitutes  P (B class, I class) pairs, 0 <= P <= MAX_SUBSTITUTES (substitute_table)
+    packed       the pack_clips(...) result the search ran on; start windows reach this function only through it, as they reach
+                 edit_scores.  The inserted token has no window; every other token keeps its own
+    -> (logz [clips] float32, ins [tokens + clips, P] float32, status [clips] int32), CUDA tensors.  A clip of N tokens has N + 1
+    places -- place j in front of token j, place N behind the last token -- and owns the rows (its first token's row + its index in
+    the batch) + j.  ins[row, p] = logZ(transcript with substitute p inserted at the place) - logZ(transcript): positive where the
+    longer transcript explains the audio better, -inf where it has no path (every entry of a clip with as many tokens as frames).
+    logz is alignment_posteriors' logz.  A clip with status != 0 gets zeros; a class id of `substitutes` outside the logits' columns
+    is STATUS_BAD_CLASS for every clip."""
+    lib = _lib.load()
+    nb, T, N, F0, K0, d_tc, d_gc, d_win = packed if packed is not None else pack_clips(logits, n_frames, token_classes, gap_classes,
+                                                                                       frame_offsets)
+    sub = np.asarray(substitutes, np.int64).reshape(-1, 2)
+    P = len(sub)
+    if P > MAX_SUBSTITUTES:
+        raise ValueError(f"at most {MAX_SUBSTITUTES} substitutes, got {P}")
+    if P and (sub.min() < -2 ** 31 or sub.max() > 2 ** 31 - 1):
+        raise ValueError("class ids are int32")
+    dev = logits.device
+    d_sub = torch.from_numpy(np.ascontiguousarray(sub if P else np.zeros((1, 2)), np.int32)).to(dev)
+    rows = int(N.sum()) + nb
+    ws_n = insertions_workspace_bytes(T, N)
+    ws = torch.empty(max(ws_n, 1), dtype=torch.uint8, device=dev)
+    logz = torch.empty(max(nb, 1), dtype=torch.float32, device=dev)
+    ins = torch.empty((max(rows, 1), max(P, 1)), dtype=torch.float32, device=dev)
+    status = torch.empty(max(nb, 1), dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        st = stream if stream is not None else torch.cuda.current_stream(dev)
+        _lib.check(lib.wfl_align_insertions(_ptr(logits), logits.stride(0), logits.shape[1], int(o_id), _hp(F0), _hp(T), _hp(K0),
+                                            _hp(N), _ptr(d_tc), _ptr(d_win) if d_win is not None else None, _ptr(d_gc), nb,
+                                            _ptr(d_sub), P, _ptr(ws), ws_n, _ptr(logz), _ptr(ins), _ptr(status),
+                                            C.c_void_p(st.cuda_stream)), "wfl_align_insertions")
+        for t in (d_tc, d_gc, ws, d_sub) + ((d_win,) if d_win is not None else ()):
+            t.record_stream(st)
+    return logz[:nb], ins[:rows, :P], status[:nb]
+
+
 def substitute_table(label_list):
     """-> (names, pairs): every phoneme of the label set that has both tags, in label order (of its B- tag), and its (B class,
     I class) pair -- the table edit_scores takes."""
@@ -275,13 +328,14 @@ def substitute_table(label_list):
     return names, [pairs[ph] for ph in names]
 
 
-def edit_groups(n_frames, n_tokens, limit=None):
+def edit_groups(n_frames, n_tokens, limit=None, workspace_bytes=edits_workspace_bytes):
     """Indices of the clips, in order, in groups whose edit_scores workspace stays under `limit` bytes (EDITS_WORKSPACE_LIMIT); a
-    clip that is over it alone is a group of its own."""
+    clip that is over it alone is a group of its own.  workspace_bytes: the scoring call's own rule (insertions_workspace_bytes for
+    insertion_scores)."""
     limit = EDITS_WORKSPACE_LIMIT if limit is None else limit
     groups, cur, used = [], [], 0
     for j, (t, n) in enumerate(zip(n_frames, n_tokens)):
-        need = edits_workspace_bytes([t], [n])
+        need = workspace_bytes([t], [n])
         if cur and used + need > limit:
             groups.append(cur)
             cur, used = [], 0
@@ -543,3 +597,69 @@ def write_folder_edits(path, per_file):
         f.write("file\t" + EDITS_HEADER + "\n")
         for name, r in folder_edit_rows(per_file):
             f.write("\t".join([name] + _edit_cells(r)) + "\n")
+
+
+# -------------------------------------------------------------------------------------------------------- transcript insertions
+class PlaceInsertion(NamedTuple):
+    index: int              # the place: 0 .. N, in front of token `index` (N: behind the last token)
+    after: str              # the neighbour tokens' names, "" at the ends
+    before: str
+    at_s: float             # the boundary of the Viterbi path there: the end of token index - 1, for index 0 the start of token 0
+    best: str               # output name of the best phoneme to insert ("" when the table is empty)
+    best_ratio: float       # its log likelihood ratio against the transcript as written (-inf: none, or no path)
+    second: str
+    second_ratio: float
+    flag: int               # 1 when best_ratio > 0: a token inserted here explains the audio better
+
+
+def place_insertions(ins, segments, sub_out_names):
+    """One file's PlaceInsertion rows from its N + 1 rows of insertion_scores' `ins` (host values) and its N aligned segments
+    [(start_s, end_s, token)].  Of several substitutes with one output name (a merge map) the best one stands for the name, so best
+    and second are two different names.  A substitute equal to a neighbour is not skipped: a doubled vowel is a real hypothesis."""
+    n = len(segments)
+    ins = np.asarray(ins, np.float64).reshape(n + 1, -1)
+    if ins.shape[1] != len(sub_out_names):
+        raise ValueError("one column per substitute")
+    rows = []
+    for j in range(n + 1):
+        by_name = {}
+        for p, name in enumerate(sub_out_names):
+            if name not in by_name or ins[j, p] > by_name[name]:
+                by_name[name] = float(ins[j, p])
+        order = sorted(by_name.items(), key=lambda kv: -kv[1])[:2]      # (stable: the table's order decides a tie)
+        order += [("", -np.inf)] * (2 - len(order))
+        at = float(segments[j - 1][1]) if j else (float(segments[0][0]) if n else 0.0)
+        rows.append(PlaceInsertion(j, str(segments[j - 1][2]) if j else "", str(segments[j][2]) if j < n else "", at, order[0][0],
+                                   order[0][1], order[1][0], order[1][1], int(order[0][1] > 0)))
+    return rows
+
+
+INSERTIONS_HEADER = "index\tafter\tbefore\tat_s\tbest\tbest_log_ratio\tsecond\tsecond_log_ratio\tflag"
+
+
+def _insertion_cells(r: PlaceInsertion):
+    return [str(r.index), r.after, r.before, f"{r.at_s:.7f}", r.best, f"{r.best_ratio:.6g}", r.second, f"{r.second_ratio:.6g}",
+            str(r.flag)]
+
+
+def write_insertions_tsv(path, rows):
+    """{stem}.insertions.tsv: one line per place of the transcript."""
+    with open(path, "w", encoding="utf-8") as f:
+        f.write(INSERTIONS_HEADER + "\n")
+        for r in rows:
+            f.write("\t".join(_insertion_cells(r)) + "\n")
+
+
+def folder_insertion_rows(per_file):
+    """per_file: [(file name, [PlaceInsertion])] -> every flagged place as (file name, PlaceInsertion), by its best ratio, descending
+    (ties keep the files' and the places' order)."""
+    flagged = [(name, r) for name, rows in per_file for r in rows if r.flag]
+    return sorted(flagged, key=lambda x: -x[1].best_ratio)
+
+
+def write_folder_insertions(path, per_file):
+    """transcript_insertions.tsv: folder_insertion_rows, the file's name in front of the place's own columns."""
+    with open(path, "w", encoding="utf-8") as f:
+        f.write("file\t" + INSERTIONS_HEADER + "\n")
+        for name, r in folder_insertion_rows(per_file):
+            f.write("\t".join([name] + _insertion_cells(r)) + "\n")

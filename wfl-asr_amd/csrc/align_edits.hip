@@ -25,6 +25,15 @@
 // token's first 64 substitutes also forms the deletion column, lanes over t.  Frames before max(k, lo_k) and after
 // min(T - 1 - (N - 1 - k), hi_{k+1} - 1) contribute exact zeros (A / the window, E) and are skipped; nothing else is.
 // Cost: phase 1 two sweeps of the lattice, phase 2 N P T chain steps (measured: tools/align_edits_bench.py).
+//
+// Single insertions (wfl_align_insertions) are the third edit, from the same two sweeps and the same chain.  Place j = 0 .. N lies in
+// front of token j (j = N: behind the last token); a token [p] inserted there has no window, its neighbours keep theirs:
+//   F_j(t) = beta_t(G_j)                           what follows a token that ends at t in front of token j (E_{j-1}(t) for j >= 1)
+//   insert p at j:  r_p(t) = lse(A_j(t) + EB_t(p), r_p(t-1) + EI_t(p)),   logZ_p(j) = lse_t(r_p(t) + F_j(t))
+// (proved against the definition in tests/test_align_insertions_cpu.py).  Phase 1 is edits_fb_kernel<NT, R, true>: planes
+// round64(N + 1) wide, A with slot N, F = beta(G_k) for k = 0 .. N in E's place, no D.  Phase 2 is insertions_chain_kernel, one wave
+// per (place, 64 substitutes) on the chain of edits_chain_kernel (edit_chain): (N + 1) P chains and no deletion column.  Frames before
+// j and after min(T - 1 - (N - j), hi_j - 1) contribute exact zeros and are skipped; nothing else is.
 #include "lattice.h"
 #include "wfl_asr.h"
 
@@ -47,25 +56,25 @@ struct EditLaunch {
   int P;
   float* ws;           // LatClip::ws_off: the clip's workspace, in floats
   float* logz;
-  float* edits;        // [total tokens][P + 1]
+  float* edits;        // [total tokens][P + 1]; the insertions: [total tokens + n_clips][P], clip b's rows from tok_off + b
   int* status;
   int n;
   LatClip clip[CLIPS_PER_LAUNCH];
 };
 
 // a clip's workspace in floats: [logZ (double) : 64] [lse: round64(T)] [offA (double): T + 1] [offB (double): T] [A: (T + 1) W] [E: T W]
-// [D: T W], every part rounded up to 64
+// [D: T W], every part rounded up to 64.  ins (the insertions): W = round64(N + 1), E holds F (slot k in column k), and there is no D
 struct EditLayout {
   long W, lse, offa, offb, A, E, D, total;
-  __host__ __device__ EditLayout(int T, int N) {
-    W = round64(N);
+  __host__ __device__ EditLayout(int T, int N, bool ins = false) {
+    W = round64(N + (ins ? 1 : 0));
     lse = 64;
     offa = lse + round64(T);
     offb = offa + round64(2L * (T + 1));
     A = offb + round64(2L * T);
     E = A + round64((long)(T + 1) * W);
     D = E + round64((long)T * W);
-    total = D + round64((long)T * W);
+    total = ins ? D : D + round64((long)T * W);
   }
 };
 
@@ -91,8 +100,8 @@ __device__ __forceinline__ float lae3(float a, float b, float c) {
   return ms + __logf(__expf(a - ms) + __expf(b - ms) + __expf(c - ms));
 }
 
-// ---- phase 1: the sweeps of the transcript's own lattice -> A, E, D, the offsets, logZ
-template <int NT, int R>
+// ---- phase 1: the sweeps of the transcript's own lattice -> A, E, D, the offsets, logZ; INS: A with slot N, F in E's place, no D
+template <int NT, int R, bool INS = false>
 __global__ __launch_bounds__(NT) void edits_fb_kernel(EditLaunch a) {
   using K = ECfg<NT, R>;
   extern __shared__ __attribute__((aligned(16))) char lds[];
@@ -130,18 +139,18 @@ __global__ __launch_bounds__(NT) void edits_fb_kernel(EditLaunch a) {
     load_windows<R>(a.tok_win, cl.tok_off, N, wn);
     wnn = load_window(a.tok_win, cl.tok_off, (tid + 1) * R, N);
   }
-  auto refuse = [&](int code) {                // zeros and the status, as every entry of the lattice
-    const long n = (long)N * (P + 1);
-    float* e = a.edits + (long)cl.tok_off * (P + 1);
-    for (long q = tid; q < n; q += NT) e[q] = 0.f;
+  auto refuse = [&](int code, float fill = 0.f) {   // zeros and the status, as every entry of the lattice
+    const long n = INS ? (long)(N + 1) * P : (long)N * (P + 1);
+    float* e = INS ? a.edits + (long)(cl.tok_off + cl.clip) * P : a.edits + (long)cl.tok_off * (P + 1);
+    for (long q = tid; q < n; q += NT) e[q] = fill;
     if (tid == 0) { a.logz[cl.clip] = 0.f; a.status[cl.clip] = code; }
   };
   if (st != 0 || T == 0) {
-    refuse(st);
+    refuse(st, INS && st == 0 ? NEG : 0.f);    // (no frame and no token: a legal clip, and no frame for an inserted token)
     return;
   }
 
-  const EditLayout lay(T, N);
+  const EditLayout lay(T, N, INS);
   const long W = lay.W;
   float* ws = a.ws + cl.ws_off;
   float* lse = ws + lay.lse;
@@ -149,7 +158,7 @@ __global__ __launch_bounds__(NT) void edits_fb_kernel(EditLaunch a) {
   double* offb = (double*)(ws + lay.offb);
   float* pA = ws + lay.A;
   float* pE = ws + lay.E;
-  float* pD = ws + lay.D;
+  [[maybe_unused]] float* pD = ws + lay.D;
 
   // ---- the per-frame log-sum-exp, in fp32 for the sweeps; what its rounding loses, in double for logZ (as post_kernel)
   double lres = 0.0;
@@ -226,6 +235,7 @@ __global__ __launch_bounds__(NT) void edits_fb_kernel(EditLaunch a) {
         const float in = lae3(G[r], pI1, pB1);
         const float ii = lae2(I[r], B[r]);
         float eb = NEG, ei = NEG;
+        if (INS && k == N) pA[(long)t * W + k] = in;
         if (k < N) {
           pA[(long)t * W + k] = in;
           tok_emission(row, av[r], eb, ei);
@@ -256,17 +266,19 @@ __global__ __launch_bounds__(NT) void edits_fb_kernel(EditLaunch a) {
         acc += (double)M;
       }
     }
-    // row T of A: what ends the clip in front of token k (the deletion of the last token reads A_{N-1}(T))
-    float2 nb = tid > 0 ? xf[((T + 1) & 1) * NT + tid - 1] : make_float2(NEG, NEG);
-    nb.x -= sub;
-    nb.y -= sub;
-    if (tid == 0) offa[T] = acc;
+    // row T of A: what ends the clip in front of token k (the deletion of the last token reads A_{N-1}(T)); no insertion reads it
+    if constexpr (!INS) {
+      float2 nb = tid > 0 ? xf[((T + 1) & 1) * NT + tid - 1] : make_float2(NEG, NEG);
+      nb.x -= sub;
+      nb.y -= sub;
+      if (tid == 0) offa[T] = acc;
 #pragma unroll
-    for (int r = 0; r < R; ++r) {
-      const int k = tid * R + r;
-      const float pB1 = r ? B[r > 0 ? r - 1 : 0] : nb.x;
-      const float pI1 = r ? I[r > 0 ? r - 1 : 0] : nb.y;
-      if (k < N) pA[(long)T * W + k] = lae3(G[r], pI1, pB1);
+      for (int r = 0; r < R; ++r) {
+        const int k = tid * R + r;
+        const float pB1 = r ? B[r > 0 ? r - 1 : 0] : nb.x;
+        const float pI1 = r ? I[r > 0 ? r - 1 : 0] : nb.y;
+        if (k < N) pA[(long)T * W + k] = lae3(G[r], pI1, pB1);
+      }
     }
   }
   publish_end_states<R>(N, G, B, I, fin);
@@ -327,9 +339,13 @@ __global__ __launch_bounds__(NT) void edits_fb_kernel(EditLaunch a) {
           eb[r] -= l;
           ei[r] -= l;
           eb[r] = win_mask(eb[r], t, wn[r]);
-          pD[(long)t * W + k] = bX[r] + eb[r];
+          if constexpr (!INS) pD[(long)t * W + k] = bX[r] + eb[r];
         }
-        if (k >= 1 && k <= N) pE[(long)t * W + k - 1] = bG[r];
+        if constexpr (INS) {
+          if (k <= N) pE[(long)t * W + k] = bG[r];
+        } else {
+          if (k >= 1 && k <= N) pE[(long)t * W + k - 1] = bG[r];
+        }
       }
       if (t == 0) break;
       // beta_{t-1}
@@ -396,6 +412,43 @@ struct RunLse {
   __device__ __forceinline__ double value() const { return s > 0.0 ? m + log(s) : -INFINITY; }
 };
 
+// one lane's chain of substitute p over the frames t0 .. t1: r(t) = lse(A(t) + EB_t(p) [the window wk], r(t-1) + EI_t(p)) ->
+// lse_t(r(t) + E(t)), absolute.  pA / pE: the column of the token (edits) or of the place (insertions, wk open), W floats a row.
+__device__ __forceinline__ double edit_chain(const EditLaunch& a, const float* Z, const float* lse, const double* offa, const double* offb,
+                                             const float* pA, const float* pE, long W, int t0, int t1, int2 wk, int p) {
+  const float NEG = -INFINITY;
+  const int cb = a.sub_cls[2 * p], ci = a.sub_cls[2 * p + 1];
+  float r = NEG;
+  double oprev = 0.0;
+  RunLse acc;
+  for (int tb = t0; tb <= t1; tb += CHAIN_U) {
+    float Ak[CHAIN_U], Ek[CHAIN_U], lk[CHAIN_U], zb[CHAIN_U], zi[CHAIN_U];
+    double oa[CHAIN_U], ob[CHAIN_U];
+#pragma unroll
+    for (int u = 0; u < CHAIN_U; ++u) {        // (a group's tail reads frame t1 again, and does not use it)
+      const int t = min(tb + u, t1);
+      Ak[u] = pA[(long)t * W];
+      Ek[u] = pE[(long)t * W];
+      lk[u] = lse[t];
+      oa[u] = offa[t];
+      ob[u] = offb[t];
+      zb[u] = Z[(long)t * a.ldl + cb];
+      zi[u] = Z[(long)t * a.ldl + ci];
+    }
+#pragma unroll
+    for (int u = 0; u < CHAIN_U; ++u) {
+      const int t = tb + u;
+      if (t > t1) break;
+      const float d = (float)(oa[u] - oprev);              // r of frame t - 1 was relative to that frame's offset
+      oprev = oa[u];
+      const float enter = win_mask(Ak[u] + (zb[u] - lk[u]), t, wk);
+      r = lae2(enter, (r - d) + (zi[u] - lk[u]));
+      acc.add((double)(r + Ek[u]) + (oa[u] + ob[u]));
+    }
+  }
+  return acc.value();
+}
+
 __global__ __launch_bounds__(CHAIN_WAVES * 64) void edits_chain_kernel(EditLaunch a) {
   const LatClip cl = a.clip[blockIdx.y];
   const int T = cl.T, N = cl.N, P = a.P;
@@ -430,38 +483,7 @@ __global__ __launch_bounds__(CHAIN_WAVES * 64) void edits_chain_kernel(EditLaunc
   const int t1 = min(T - 1 - (N - 1 - k), k + 1 < N ? max(min(wk1.y, T), 0) - 1 : T - 1);
 
   const int p = chunk * 64 + lane;
-  if (p < P) {
-    const int cb = a.sub_cls[2 * p], ci = a.sub_cls[2 * p + 1];
-    float r = NEG;
-    double oprev = 0.0;
-    RunLse acc;
-    for (int tb = t0; tb <= t1; tb += CHAIN_U) {
-      float Ak[CHAIN_U], Ek[CHAIN_U], lk[CHAIN_U], zb[CHAIN_U], zi[CHAIN_U];
-      double oa[CHAIN_U], ob[CHAIN_U];
-#pragma unroll
-      for (int u = 0; u < CHAIN_U; ++u) {      // (a group's tail reads frame t1 again, and does not use it)
-        const int t = min(tb + u, t1);
-        Ak[u] = pA[(long)t * W];
-        Ek[u] = pE[(long)t * W];
-        lk[u] = lse[t];
-        oa[u] = offa[t];
-        ob[u] = offb[t];
-        zb[u] = Z[(long)t * a.ldl + cb];
-        zi[u] = Z[(long)t * a.ldl + ci];
-      }
-#pragma unroll
-      for (int u = 0; u < CHAIN_U; ++u) {
-        const int t = tb + u;
-        if (t > t1) break;
-        const float d = (float)(oa[u] - oprev);            // r of frame t - 1 was relative to that frame's offset
-        oprev = oa[u];
-        const float enter = win_mask(Ak[u] + (zb[u] - lk[u]), t, wk);
-        r = lae2(enter, (r - d) + (zi[u] - lk[u]));
-        acc.add((double)(r + Ek[u]) + (oa[u] + ob[u]));
-      }
-    }
-    out[p] = (float)(acc.value() - logZ);
-  }
+  if (p < P) out[p] = (float)(edit_chain(a, Z, lse, offa, offb, pA, pE, W, t0, t1, wk, p) - logZ);
 
   if (chunk == 0) {                            // the deletion column, lanes over t
     double v;
@@ -480,12 +502,87 @@ __global__ __launch_bounds__(CHAIN_WAVES * 64) void edits_chain_kernel(EditLaunc
   }
 }
 
+// the insertions' phase 2: one wave per (place j, 64 substitutes); A's column j with F's column j, no window on the entry
+__global__ __launch_bounds__(CHAIN_WAVES * 64) void insertions_chain_kernel(EditLaunch a) {
+  const LatClip cl = a.clip[blockIdx.y];
+  const int T = cl.T, N = cl.N, P = a.P;
+  const int chunks = (P + 63) / 64;
+  const int lane = threadIdx.x & 63;
+  const int w = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * CHAIN_WAVES + (threadIdx.x >> 6)));
+  if (w >= (N + 1) * chunks || a.status[cl.clip] != 0 || T == 0) return;
+  const int j = w / chunks, chunk = w - j * chunks;
+  const EditLayout lay(T, N, true);
+  const float* ws = a.ws + cl.ws_off;
+  const double logZ = *(const double*)ws;
+  // a token needs a frame at or after j (j tokens in front of it); nothing follows it after T - 1 - (N - j) (N - j tokens behind it)
+  // or from token j's last start on: exact zeros
+  int hi = T;
+  if (a.tok_win && j < N) hi = max(min(load_window(a.tok_win, cl.tok_off, j, N).y, T), 0);
+  const int t1 = min(T - 1 - (N - j), hi - 1);
+  const int p = chunk * 64 + lane;
+  if (p < P)
+    a.edits[(long)(cl.tok_off + cl.clip + j) * P + p] =
+        (float)(edit_chain(a, a.logits + cl.frame_off * a.ldl, ws + lay.lse, (const double*)(ws + lay.offa), (const double*)(ws + lay.offb),
+                           ws + lay.A + j, ws + lay.E + j, lay.W, j, t1, make_int2(0, WIN_OPEN_HI), p) - logZ);
+}
+
 // over the cap the kernel reports status 2; such a clip is sized (and launched) as the cap's configuration, as the posterior's
 int edit_cfg(int N) { return std::min(cfg_of(N), NCFG - 1); }
 
 long clip_floats(int T, int N) {
   if (T <= 0) return 0;
   return EditLayout(T, std::min(N, MAX_TOKENS)).total;     // (a multiple of 64: 256-byte aligned)
+}
+
+long clip_floats_ins(int T, int N) {
+  if (T <= 0) return 0;
+  return EditLayout(T, std::min(N, MAX_TOKENS), true).total;
+}
+
+// the two entries: INS false wfl_align_edits, true wfl_align_insertions (`edits`: its ins)
+template <bool INS>
+int run_edits(const char* fn, const float* logits, int64_t ldl, int32_t C, int32_t o_id, const int64_t* frame_off_host,
+              const int32_t* n_frames_host, const int32_t* tok_off_host, const int32_t* n_tok_host, const int32_t* tok_cls,
+              const int32_t* tok_win, const int32_t* gap_cls, int32_t n_clips, const int32_t* sub_cls, int32_t n_sub, void* workspace,
+              int64_t workspace_bytes, float* logz, float* edits, int32_t* status, void* stream) {
+  const int64_t need = clips_workspace_bytes(n_frames_host, n_tok_host, n_clips, INS ? clip_floats_ins : clip_floats);
+  bool any_tok = false, any_frame = false;
+  int rc = check_clip_args(fn, C, o_id, ldl, frame_off_host, n_frames_host, tok_off_host, n_tok_host, n_clips, need, any_tok, any_frame);
+  if (rc) return rc;
+  if (n_sub < 0 || n_sub > MAX_SUB) return fail(fn, -1, "n_sub must be 0 .. 512");
+  if (n_clips == 0) return 0;
+  // (the insertions have a row for every clip, tokens or none, and no column without a substitute)
+  const bool no_out = INS ? (n_sub > 0 && !edits) : (any_tok && !edits);
+  if (!logz || !status || !gap_cls || (n_sub > 0 && !sub_cls) || (any_tok && !tok_cls) || no_out || (any_frame && !logits))
+    return fail(fn, -1, "null device pointer");
+  if ((rc = check_workspace(fn, need, workspace, workspace_bytes))) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  EditLaunch a{};
+  a.logits = logits; a.ldl = ldl; a.C = C; a.tok_cls = tok_cls; a.gap_cls = gap_cls; a.tok_win = tok_win; a.sub_cls = sub_cls;
+  a.P = n_sub; a.ws = (float*)workspace; a.logz = logz; a.edits = edits; a.status = status;
+  return launch_clips<NCFG>(
+      a, n_clips,
+      [&](int b, long off, LatClip& c, int& cfg) {
+        const int T = n_frames_host[b], N = n_tok_host[b];
+        c = LatClip{(long)frame_off_host[b], off, T, tok_off_host[b], N, b};
+        cfg = edit_cfg(N);
+        return INS ? clip_floats_ins(T, N) : clip_floats(T, N);
+      },
+      [&](int cfg, const EditLaunch& a) {
+        const int rc = dispatch_cfg(cfg, [&](auto sh) {
+          constexpr int NT = decltype(sh)::NT, R = decltype(sh)::R;
+          return launch_cfg<edits_fb_kernel<NT, R, INS>, NT, ECfg<NT, R>::LDS>(fn, a, s);
+        });
+        if (rc) return rc;
+        int waves = 0;                         // of the launch's largest transcript; a clip with fewer leaves its surplus at once
+        for (int j = 0; j < a.n; ++j)
+          if (a.clip[j].N <= MAX_TOKENS)
+            waves = std::max(waves, INS ? (a.clip[j].N + 1) * ((a.P + 63) / 64) : a.clip[j].N * std::max(1, (a.P + 63) / 64));
+        if (waves == 0) return 0;
+        hipLaunchKernelGGL(INS ? insertions_chain_kernel : edits_chain_kernel, dim3((waves + CHAIN_WAVES - 1) / CHAIN_WAVES, a.n),
+                           dim3(CHAIN_WAVES * 64), 0, s, a);
+        return hipGetLastError() == hipSuccess ? 0 : fail(fn, -3, "launch failed");
+      });
 }
 
 }  // namespace
@@ -500,41 +597,20 @@ int32_t wfl_align_edits(const float* logits, int64_t ldl, int32_t C, int32_t o_i
                         const int32_t* n_frames_host, const int32_t* tok_off_host, const int32_t* n_tok_host, const int32_t* tok_cls,
                         const int32_t* tok_win, const int32_t* gap_cls, int32_t n_clips, const int32_t* sub_cls, int32_t n_sub,
                         void* workspace, int64_t workspace_bytes, float* logz, float* edits, int32_t* status, void* stream) {
-  const char* fn = "wfl_align_edits";
-  const int64_t need = wfl_align_edits_workspace_bytes(n_frames_host, n_tok_host, n_clips);
-  bool any_tok = false, any_frame = false;
-  int rc = check_clip_args(fn, C, o_id, ldl, frame_off_host, n_frames_host, tok_off_host, n_tok_host, n_clips, need, any_tok, any_frame);
-  if (rc) return rc;
-  if (n_sub < 0 || n_sub > MAX_SUB) return fail(fn, -1, "n_sub must be 0 .. 512");
-  if (n_clips == 0) return 0;
-  if (!logz || !status || !gap_cls || (n_sub > 0 && !sub_cls) || (any_tok && (!tok_cls || !edits)) || (any_frame && !logits))
-    return fail(fn, -1, "null device pointer");
-  if ((rc = check_workspace(fn, need, workspace, workspace_bytes))) return rc;
-  hipStream_t s = (hipStream_t)stream;
-  EditLaunch a{};
-  a.logits = logits; a.ldl = ldl; a.C = C; a.tok_cls = tok_cls; a.gap_cls = gap_cls; a.tok_win = tok_win; a.sub_cls = sub_cls;
-  a.P = n_sub; a.ws = (float*)workspace; a.logz = logz; a.edits = edits; a.status = status;
-  return launch_clips<NCFG>(
-      a, n_clips,
-      [&](int b, long off, LatClip& c, int& cfg) {
-        const int T = n_frames_host[b], N = n_tok_host[b];
-        c = LatClip{(long)frame_off_host[b], off, T, tok_off_host[b], N, b};
-        cfg = edit_cfg(N);
-        return clip_floats(T, N);
-      },
-      [&](int cfg, const EditLaunch& a) {
-        const int rc = dispatch_cfg(cfg, [&](auto sh) {
-          constexpr int NT = decltype(sh)::NT, R = decltype(sh)::R;
-          return launch_cfg<edits_fb_kernel<NT, R>, NT, ECfg<NT, R>::LDS>(fn, a, s);
-        });
-        if (rc) return rc;
-        int waves = 0;                         // of the launch's largest transcript; a clip with fewer leaves its surplus at once
-        for (int j = 0; j < a.n; ++j)
-          if (a.clip[j].N <= MAX_TOKENS) waves = std::max(waves, a.clip[j].N * std::max(1, (a.P + 63) / 64));
-        if (waves == 0) return 0;
-        hipLaunchKernelGGL(edits_chain_kernel, dim3((waves + CHAIN_WAVES - 1) / CHAIN_WAVES, a.n), dim3(CHAIN_WAVES * 64), 0, s, a);
-        return hipGetLastError() == hipSuccess ? 0 : fail(fn, -3, "launch failed");
-      });
+  return run_edits<false>("wfl_align_edits", logits, ldl, C, o_id, frame_off_host, n_frames_host, tok_off_host, n_tok_host, tok_cls, tok_win,
+                          gap_cls, n_clips, sub_cls, n_sub, workspace, workspace_bytes, logz, edits, status, stream);
+}
+
+int64_t wfl_align_insertions_workspace_bytes(const int32_t* n_frames_host, const int32_t* n_tok_host, int32_t n_clips) {
+  return clips_workspace_bytes(n_frames_host, n_tok_host, n_clips, clip_floats_ins);
+}
+
+int32_t wfl_align_insertions(const float* logits, int64_t ldl, int32_t C, int32_t o_id, const int64_t* frame_off_host,
+                             const int32_t* n_frames_host, const int32_t* tok_off_host, const int32_t* n_tok_host, const int32_t* tok_cls,
+                             const int32_t* tok_win, const int32_t* gap_cls, int32_t n_clips, const int32_t* sub_cls, int32_t n_sub,
+                             void* workspace, int64_t workspace_bytes, float* logz, float* ins, int32_t* status, void* stream) {
+  return run_edits<true>("wfl_align_insertions", logits, ldl, C, o_id, frame_off_host, n_frames_host, tok_off_host, n_tok_host, tok_cls,
+                         tok_win, gap_cls, n_clips, sub_cls, n_sub, workspace, workspace_bytes, logz, ins, status, stream);
 }
 
 }  // extern "C"

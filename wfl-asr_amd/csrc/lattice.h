@@ -1,7 +1,8 @@
 // The forced-alignment lattice of wfl_align (csrc/align.hip, the max-product search), wfl_align_posterior (csrc/align_posterior.hip,
 // the sum-product sweeps) and wfl_align_edits (csrc/align_edits.hip: the same sweeps once more, kept per frame, and from them the
-// score of every single substitution and deletion of the transcript), defined ONCE: a change made here reaches all of them, so the
-// posterior and the edit scores always speak of the lattice the search ran on.
+// score of every single substitution and deletion of the transcript, and wfl_align_insertions beside it: of every single insertion),
+// defined ONCE: a change made here reaches all of them, so the posterior and the edit scores always speak of the lattice the search
+// ran on.
 //
 //   device  caps and constants, the per-clip record, the wave reductions, the (threads, slots per thread) configurations and their
 //           dispatch, the shared part of the LDS layout, lattice setup (status 0 / 1 / 2 / 4, the alternatives in LDS, the gap classes in

@@ -421,9 +421,10 @@ class Labeler:
 
     def label_files(self, audio_paths, lang_id=None, confidence_threshold=0.0, verbose=True, align=None, align_scores=None,
                     decode=None, switch_penalty=None, decode_scores=None, phoneme_bigram=None, bigram_weight=None, align_draft=None,
-                    draft_tolerance=None, align_edits=None, bigram_scores=None):
+                    draft_tolerance=None, align_edits=None, align_insertions=None, bigram_scores=None):
         """-> list (per file) of [(start_s, end_s, phoneme)] after merge + forced alignment; with align_scores, decode_scores or
-        bigram_scores, (that list, scores); with align_edits the tuple ends with one more list, edits.
+        bigram_scores, (that list, scores); with align_edits the tuple goes on with one more list, edits, and with align_insertions
+        it ends with one more, insertions.
 
         align: "greedy" -- a `{audio}.txt` transcript is matched onto the freely decoded segments (infer.py:30-60, 312-319);
         "viterbi" -- files with a transcript are aligned by a search over their frame logits on the GPU (align.py: one segment
@@ -470,23 +471,35 @@ class Labeler:
         log likelihood ratio of the transcript so edited against the transcript as written, the same for the transcript without the
         token, and a flag where the largest is > 0 (align.edit_scores: sums over all boundaries of the lattice the search ran on, the
         draft's windows included) -- or None for a file without a transcript or one that fell back to the greedy alignment (with a
-        message).  The segments are the same with and without."""
+        message).  The segments are the same with and without.
+
+        align_insertions (with align "viterbi" only; None: config postprocess.align_insertions, else off): also return
+        insertions[i], for a file that was Viterbi-aligned one align.PlaceInsertion per place of the transcript (in front of every
+        token, and behind the last) -- the best and the second-best phoneme to insert there with the log likelihood ratio of the
+        longer transcript against the transcript as written, and a flag where the best is > 0 (align.insertion_scores: on the same
+        lattice as the edits, the inserted token without a window) -- or None as for align_edits.  The segments and the edits are
+        the same with and without."""
         opts = self.options(align=align, align_scores=align_scores, decode=decode, switch_penalty=switch_penalty,
                             decode_scores=decode_scores, phoneme_bigram=phoneme_bigram, bigram_weight=bigram_weight,
                             bigram_scores=bigram_scores, align_draft=align_draft, draft_tolerance=draft_tolerance,
-                            align_edits=align_edits)
+                            align_edits=align_edits, align_insertions=align_insertions)
         edits = {} if opts.align_edits else None
-        final, scores = self._label_scored(audio_paths, opts, lang_id, confidence_threshold, verbose, edits=edits)
+        insertions = {} if opts.align_insertions else None
+        final, scores = self._label_scored(audio_paths, opts, lang_id, confidence_threshold, verbose, edits=edits,
+                                           insertions=insertions)
         out = (final, scores) if opts.scored else (final,)
         if opts.align_edits:
             out += ([edits.get(fi) for fi in range(len(audio_paths))],)
+        if opts.align_insertions:
+            out += ([insertions.get(fi) for fi in range(len(audio_paths))],)
         return out if len(out) > 1 else final
 
-    def _label_scored(self, audio_paths, opts, lang_id, confidence_threshold, verbose, moves=None, edits=None):
+    def _label_scored(self, audio_paths, opts, lang_id, confidence_threshold, verbose, moves=None, edits=None, insertions=None):
         """label_files for the resolved options `opts`, always -> (segments, scores): the files are split once into those a transcript is
         Viterbi-aligned to, those the grammar search decodes and those left to the argmax decode, and each subset's results go back to
         its files' places.  moves: a dict that takes {file index: [DraftMove]} for the files aligned inside their draft's windows.
-        edits (opts.align_edits): a dict that takes {file index: [TokenEdit]} for the files that were Viterbi-aligned."""
+        edits (opts.align_edits): a dict that takes {file index: [TokenEdit]} for the files that were Viterbi-aligned; insertions
+        (opts.align_insertions): the same with [PlaceInsertion]."""
         trans = self._bigram_table(opts.phoneme_bigram, opts.switch_penalty, opts.bigram_weight) if opts.phoneme_bigram else None
         if opts.decode == "viterbi" and int(self.config["postprocess"].get("median_filter", 0)) > 1:
             print("decode: viterbi -- postprocess.median_filter is not applied (the switch penalty takes its place)")
@@ -521,14 +534,17 @@ class Labeler:
         if with_t:
             moved = {}
             edited = {} if opts.align_edits else None
+            inserted = {} if opts.align_insertions else None
             got = self._label_viterbi(paths(with_t), [forced[fi] for fi in with_t], lang_id, confidence_threshold, verbose,
-                                      opts.align_scores, [drafts[fi] for fi in with_t], opts.draft_tolerance, moved, edited)
+                                      opts.align_scores, [drafts[fi] for fi in with_t], opts.draft_tolerance, moved, edited, inserted)
             for fi, segs, sc in zip(with_t, *got):
                 final[fi], scores[fi] = segs, sc
             if moves is not None:
                 moves.update({with_t[j]: m for j, m in moved.items()})
             if edits is not None and edited is not None:
                 edits.update({with_t[j]: e for j, e in edited.items()})
+            if insertions is not None and inserted is not None:
+                insertions.update({with_t[j]: e for j, e in inserted.items()})
         return final, scores
 
     def _label_files_greedy(self, audio_paths, lang_id, confidence_threshold, verbose):
@@ -804,7 +820,7 @@ class Labeler:
         return total, total_logz, total_lse, n_frames, skipped
 
     def _label_viterbi(self, audio_paths, transcripts, lang_id, threshold, verbose, want_scores=False, drafts=None, tolerance=0.0,
-                       moves=None, edits=None):
+                       moves=None, edits=None, insertions=None):
         """Files with a transcript, align="viterbi".  Their chunks are forwarded with logits (kept on the device); the free decode of
         the same forward gives the greedy result, which the pause rule at the ends needs and which a file falls back to (with a
         message) when its transcript cannot be aligned.  Each file's chunks' valid logits rows are concatenated on the device, so
@@ -823,12 +839,16 @@ class Labeler:
         edits: a dict that takes {file index: [TokenEdit]} (postprocess.align_edits): after the search, align.edit_scores over the
         clips it aligned, on the PackedClips of the search (with a draft: the windowed lattice), with every phoneme of the label set
         as a substitute; the clips go in groups whose workspace stays under align.EDITS_WORKSPACE_LIMIT.  A file that fell back to
-        the greedy alignment gets no entry, and one line says so."""
+        the greedy alignment gets no entry, and one line says so.
+
+        insertions: a dict that takes {file index: [PlaceInsertion]} (postprocess.align_insertions): align.insertion_scores in the
+        same place, on the same PackedClips, with the same table, grouped by its own workspace rule.  With both on, each call runs
+        its own sweeps."""
         lang_name = self._lang_name(lang_id)
         remap, names = self._names_for(lang_name)
         results, scores = [], []
-        want_edits = edits is not None
-        if want_edits:
+        want_edits, want_ins = edits is not None, insertions is not None
+        if want_edits or want_ins:
             sub_names, sub_pairs = AL.substitute_table(self.labels)
             sub_out = AL.substitute_output_names(sub_names, self._table, remap, names)
         for sel, by_file in self._file_waves(audio_paths, verbose):     # a wave's chunks are forwarded and aligned together
@@ -868,7 +888,7 @@ class Labeler:
                             print(f"{audio_paths[fi]}: {DRAFT_INFEASIBLE}")
                 windows = wins if any(w is not None for w in wins) else None      # (no draft in the wave: the unwindowed entries)
                 packed = (AL.pack_clips(lg, frames, [plans[fi] for fi in run], gaps, windows=windows)
-                          if want_scores or want_edits else None)
+                          if want_scores or want_edits or want_ins else None)
                 d_ids, d_tok, d_score, d_st = AL.viterbi_align(lg, frames, [plans[fi] for fi in run], gaps, self.labels.index("O"),
                                                                packed=packed, windows=windows)
                 st_all = d_st.cpu().numpy()
@@ -892,27 +912,38 @@ class Labeler:
                 raw = {}                                      # file -> (score, logz, tok_post, start_mean, start_sd)
                 bad_post = {}
                 ok = [b for b in range(len(run)) if st_all[b] == AL.STATUS_OK]
-                raw_edits = {}                                # file -> its rows of edit_scores' edits
-                if (want_scores or want_edits) and ok:
+                raw_edits, raw_ins = {}, {}                   # file -> its rows of edit_scores' edits / insertion_scores' ins
+                if (want_scores or want_edits or want_ins) and ok:
                     # (only the clips the search aligned; when that is all of them, on the tables the search was given)
                     sub = ([frames[b] for b in ok], [plans[run[b]] for b in ok], [gaps[b] for b in ok])
                     if packed is None or len(ok) != len(run):  # (the windows travel in the packed batch: the lattice of the search)
                         packed = AL.pack_clips(lg, *sub, f0[ok], windows=[wins[b] for b in ok] if windows is not None else None)
-                if want_edits and ok:
+                if (want_edits or want_ins) and ok:
                     n_tok = [len(plans[run[b]]) for b in ok]
-                    for grp in AL.edit_groups(sub[0], n_tok):
-                        gsub = tuple([x[j] for j in grp] for x in sub)
-                        gpack = packed if len(grp) == len(ok) else AL.pack_clips(
-                            lg, *gsub, f0[[ok[j] for j in grp]], windows=[wins[ok[j]] for j in grp] if windows is not None else None)
-                        _, d_ed, d_est = AL.edit_scores(lg, *gsub, self.labels.index("O"), sub_pairs, packed=gpack)
-                        h_ed, h_est = d_ed.cpu().numpy(), d_est.cpu().numpy()
-                        k0 = 0
-                        for q, j in enumerate(grp):
-                            if h_est[q] == AL.STATUS_OK:
-                                raw_edits[run[ok[j]]] = h_ed[k0:k0 + n_tok[j]]
-                            else:
-                                print(f"{audio_paths[run[ok[j]]]}: no transcript edits (wfl_align_edits status {int(h_est[q])})")
-                            k0 += n_tok[j]
+
+                    def scored_rows(scorer, workspace_bytes, extra, what, entry):
+                        """-> {file: its n_tok + extra rows of scorer's table}, the clips in groups under EDITS_WORKSPACE_LIMIT."""
+                        out = {}
+                        for grp in AL.edit_groups(sub[0], n_tok, workspace_bytes=workspace_bytes):
+                            gsub = tuple([x[j] for j in grp] for x in sub)
+                            gpack = packed if len(grp) == len(ok) else AL.pack_clips(
+                                lg, *gsub, f0[[ok[j] for j in grp]],
+                                windows=[wins[ok[j]] for j in grp] if windows is not None else None)
+                            _, d_ed, d_est = scorer(lg, *gsub, self.labels.index("O"), sub_pairs, packed=gpack)
+                            h_ed, h_est = d_ed.cpu().numpy(), d_est.cpu().numpy()
+                            k0 = 0
+                            for q, j in enumerate(grp):
+                                if h_est[q] == AL.STATUS_OK:
+                                    out[run[ok[j]]] = h_ed[k0:k0 + n_tok[j] + extra]
+                                else:
+                                    print(f"{audio_paths[run[ok[j]]]}: no transcript {what} ({entry} status {int(h_est[q])})")
+                                k0 += n_tok[j] + extra
+                        return out
+                    if want_edits:
+                        raw_edits = scored_rows(AL.edit_scores, AL.edits_workspace_bytes, 0, "edits", "wfl_align_edits")
+                    if want_ins:                              # (a clip's N + 1 places: one row more than its tokens)
+                        raw_ins = scored_rows(AL.insertion_scores, AL.insertions_workspace_bytes, 1, "insertions",
+                                              "wfl_align_insertions")
                 if want_scores and ok:
                     d_post = AL.alignment_posteriors(lg, *sub, self.labels.index("O"), d_tok, frame_offsets=f0[ok], packed=packed)
                     nt = sum(len(plans[run[b]]) for b in ok)
@@ -949,12 +980,16 @@ class Labeler:
                             print(f"{audio_paths[fi]}: no alignment scores (wfl_align_posterior status {bad_post.get(fi)})")
                         if fi in raw_edits:
                             edits[fi] = AL.token_edits(raw_edits[fi], segs, sub_out)
+                        if fi in raw_ins:
+                            insertions[fi] = AL.place_insertions(raw_ins[fi], segs, sub_out)
                     pos += n
             for fi in sel:
                 results.append(aligned.get(fi, greedy[fi]))
                 scores.append(post.get(fi))
                 if want_edits and fi not in aligned:
                     print(f"{audio_paths[fi]}: no transcript edits (the file was not Viterbi-aligned)")
+                if want_ins and fi not in aligned:
+                    print(f"{audio_paths[fi]}: no transcript insertions (the file was not Viterbi-aligned)")
         return results, scores
 
 
@@ -1145,6 +1180,17 @@ def _write_edits(lab_path, rows):
         print(f"Transcript edits saved to: {edits_path(lab_path)}")
 
 
+def insertions_path(lab_path):
+    return os.path.splitext(lab_path)[0] + ".insertions.tsv"
+
+
+def _write_insertions(lab_path, rows):
+    """`{stem}.insertions.tsv` beside the .lab of a file that was Viterbi-aligned (None: no file)."""
+    if rows is not None:
+        AL.write_insertions_tsv(insertions_path(lab_path), rows)
+        print(f"Transcript insertions saved to: {insertions_path(lab_path)}")
+
+
 def _write_score(lab_path, segments, score):
     """The scores file of one labelled file beside its .lab, by the kind of its score (None: no file)."""
     if isinstance(score, DC.FreeScore):
@@ -1156,7 +1202,7 @@ def _write_score(lab_path, segments, score):
 def infer_audio(audio_path, config_path="config.yaml", checkpoint_path="best_model.pt", output_lab_path=None, device="cuda",
                 lang_id=None, sample=False, top_k=0, top_p=0.0, temperature=1.0, confidence_threshold=0.0, align=None,
                 align_scores=None, decode=None, switch_penalty=None, decode_scores=None, phoneme_bigram=None, bigram_weight=None,
-                align_draft=None, draft_tolerance=None, align_edits=None, bigram_scores=None):
+                align_draft=None, draft_tolerance=None, align_edits=None, align_insertions=None, bigram_scores=None):
     """align: "greedy" | "viterbi" | None (config postprocess.align, else greedy): how a `{audio}.txt` transcript is aligned
     (Labeler.label_files).  align_scores (viterbi only; None: config postprocess.align_scores): also write `{stem}.scores.tsv`
     beside the .lab when the file was Viterbi-aligned (format_scores_tsv).  decode: "argmax" | "viterbi" | None (config
@@ -1169,15 +1215,19 @@ def infer_audio(audio_path, config_path="config.yaml", checkpoint_path="best_mod
     config postprocess.align_draft / postprocess.draft_tolerance): refine the draft DIR/{stem}.lab inside per-token start windows
     (Labeler.label_files).  align_edits (align viterbi only; None: config postprocess.align_edits): also write `{stem}.edits.tsv`
     beside the .lab when the file was Viterbi-aligned: per token the best and second-best substitute, the deletion, their log
-    likelihood ratios and a flag (align.write_edits_tsv)."""
+    likelihood ratios and a flag (align.write_edits_tsv).  align_insertions (align viterbi only; None: config
+    postprocess.align_insertions): also write `{stem}.insertions.tsv` beside the .lab when the file was Viterbi-aligned: per place of
+    the transcript the best and second-best phoneme to insert, their log likelihood ratios and a flag (align.write_insertions_tsv)."""
     given = dict(align=align, align_scores=align_scores, decode=decode, switch_penalty=switch_penalty, decode_scores=decode_scores,
                  phoneme_bigram=phoneme_bigram, bigram_weight=bigram_weight, bigram_scores=bigram_scores, align_draft=align_draft,
-                 draft_tolerance=draft_tolerance, align_edits=align_edits)
+                 draft_tolerance=draft_tolerance, align_edits=align_edits, align_insertions=align_insertions)
     _refuse_before_load(config_path, **given)
     lab = _labeler(config_path, checkpoint_path, device)
     opts = lab.options(**given)
     edits = {} if opts.align_edits else None
-    (segments,), (score,) = lab._label_scored([audio_path], opts, lang_id, confidence_threshold, True, edits=edits)
+    insertions = {} if opts.align_insertions else None
+    (segments,), (score,) = lab._label_scored([audio_path], opts, lang_id, confidence_threshold, True, edits=edits,
+                                              insertions=insertions)
     if output_lab_path:
         if os.path.abspath(output_lab_path) == os.path.abspath(audio_path):
             # the reference would truncate the input WAV here (infer.py:410-411 + utils.py:77)
@@ -1186,6 +1236,8 @@ def infer_audio(audio_path, config_path="config.yaml", checkpoint_path="best_mod
         _write_score(output_lab_path, segments, score)
         if edits is not None:
             _write_edits(output_lab_path, edits.get(0))
+        if insertions is not None:
+            _write_insertions(output_lab_path, insertions.get(0))
     return segments
 
 
@@ -1193,10 +1245,10 @@ def infer_folder(folder_path: str, config_path: str = "config.yaml", checkpoint_
                  output_dir: str = "outputs", device: str = "cuda", lang_id: int = None, sample=False, top_k=0, top_p=0.0,
                  temperature=1.0, confidence_threshold=0.0, align=None, align_scores=None, decode=None, switch_penalty=None,
                  decode_scores=None, phoneme_bigram=None, bigram_weight=None, align_draft=None, draft_tolerance=None,
-                 align_edits=None, bigram_scores=None):
+                 align_edits=None, align_insertions=None, bigram_scores=None):
     given = dict(align=align, align_scores=align_scores, decode=decode, switch_penalty=switch_penalty, decode_scores=decode_scores,
                  phoneme_bigram=phoneme_bigram, bigram_weight=bigram_weight, bigram_scores=bigram_scores, align_draft=align_draft,
-                 draft_tolerance=draft_tolerance, align_edits=align_edits)
+                 draft_tolerance=draft_tolerance, align_edits=align_edits, align_insertions=align_insertions)
     _refuse_before_load(config_path, **given)
     wav_files = sorted(f for f in os.listdir(folder_path) if f.lower().endswith(".wav"))
     os.makedirs(output_dir, exist_ok=True)
@@ -1211,8 +1263,9 @@ def infer_folder(folder_path: str, config_path: str = "config.yaml", checkpoint_
     opts = lab.options(**given)
     moves = {}
     edits = {} if opts.align_edits else None
-    all_segments, all_scores = (lab._label_scored(paths, opts, lang_id, confidence_threshold, True, moves, edits) if paths
-                                else ([], []))
+    insertions = {} if opts.align_insertions else None
+    all_segments, all_scores = (lab._label_scored(paths, opts, lang_id, confidence_threshold, True, moves, edits, insertions)
+                                if paths else ([], []))
     for fi, (wav_file, segments, score) in enumerate(zip(wav_files, all_segments, all_scores)):
         print(f"\nInferencing: {wav_file}")
         lab_path = os.path.join(output_dir, os.path.splitext(wav_file)[0] + ".lab")
@@ -1220,6 +1273,8 @@ def infer_folder(folder_path: str, config_path: str = "config.yaml", checkpoint_
         _write_score(lab_path, segments, score)
         if edits is not None:
             _write_edits(lab_path, edits.get(fi))
+        if insertions is not None:
+            _write_insertions(lab_path, insertions.get(fi))
         print("Predicted segments:")
         for start, end, ph in segments:
             print(f"({round(start, 2)}, {round(end, 2)}, {ph})")
@@ -1231,6 +1286,10 @@ def infer_folder(folder_path: str, config_path: str = "config.yaml", checkpoint_
         name = "transcript_edits.tsv" if world == 1 else f"transcript_edits.rank{rank}.tsv"
         AL.write_folder_edits(os.path.join(output_dir, name), [(wav_files[fi], edits[fi]) for fi in sorted(edits)])
         print(f"Transcript edits of the folder saved to: {os.path.join(output_dir, name)}")
+    if opts.align_insertions:
+        name = "transcript_insertions.tsv" if world == 1 else f"transcript_insertions.rank{rank}.tsv"
+        AL.write_folder_insertions(os.path.join(output_dir, name), [(wav_files[fi], insertions[fi]) for fi in sorted(insertions)])
+        print(f"Transcript insertions of the folder saved to: {os.path.join(output_dir, name)}")
     if opts.align_draft:
         name = "draft_moves.tsv" if world == 1 else f"draft_moves.rank{rank}.tsv"
         _write_text(os.path.join(output_dir, name), format_draft_moves_tsv([(wav_files[fi], moves[fi]) for fi in sorted(moves)]),
@@ -1299,9 +1358,14 @@ def main(argv=None):
                        "phonemes and the deletion, as log likelihood ratios against the transcript as written, summed over all "
                        "boundaries on the GPU) and, for a folder, transcript_edits.tsv with every token an edit would improve. "
                        "Default: config postprocess.align_edits, else off.")
+    @click.option("--align-insertions", "align_insertions", is_flag=True, default=None,
+                  help="With --align viterbi: also write {stem}.insertions.tsv beside each aligned .lab (per place of the transcript "
+                       "the best phonemes to insert there, as log likelihood ratios against the transcript as written, summed over "
+                       "all boundaries on the GPU) and, for a folder, transcript_insertions.tsv with every place a token seems to be "
+                       "missing. Default: config postprocess.align_insertions, else off.")
     def cli(path, checkpoint, config, output, lang_id, sample, top_k, top_p, temperature, device, confidence_threshold, align,
             align_scores, decode, switch_penalty, decode_scores, phoneme_bigram, bigram_weight, bigram_scores, align_draft,
-            draft_tolerance, align_edits):
+            draft_tolerance, align_edits, align_insertions):
         if switch_penalty is not None and not switch_penalty >= 0.0:
             raise click.UsageError("--switch-penalty must be >= 0 (nats)")
         if sample:
@@ -1334,7 +1398,7 @@ def main(argv=None):
             opts = resolve(cfg["postprocess"], align=align, align_scores=align_scores, decode=decode, switch_penalty=switch_penalty,
                            decode_scores=decode_scores, phoneme_bigram=phoneme_bigram, bigram_weight=bigram_weight,
                            bigram_scores=bigram_scores, align_draft=align_draft, draft_tolerance=draft_tolerance,
-                           align_edits=align_edits)
+                           align_edits=align_edits, align_insertions=align_insertions)
         except ValueError as err:
             raise click.UsageError(str(err))
         output_path = inf_path if output == "." else output
@@ -1353,7 +1417,7 @@ def main(argv=None):
                   bigram_weight=opts.bigram_weight if opts.decode == "viterbi" else None,
                   # the draft travels the same way: an empty path for "none", a tolerance only beside a draft
                   align_draft=opts.align_draft or "", draft_tolerance=opts.draft_tolerance if opts.align_draft else None,
-                  align_edits=opts.align_edits)
+                  align_edits=opts.align_edits, align_insertions=opts.align_insertions)
         if inf_path.is_dir():
             infer_folder(folder_path=str(inf_path), output_dir=str(output_path), **kw)
         else:

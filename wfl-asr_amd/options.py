@@ -16,6 +16,7 @@ infer_folder (before any model is loaded) and the CLI all call `resolve` and car
   align_draft     none     10. needs align viterbi (the draft's windows hold that search)
   draft_tolerance 0.1      11. when given, a number >= 0 (seconds; no bool), and then needs an align_draft
   align_edits     off      12. needs align viterbi (the edits are scored on the lattice of that search)
+  align_insertions off     13. needs align viterbi (the insertions are scored on the lattice of that search)
 """
 from __future__ import annotations
 
@@ -57,34 +58,39 @@ class PostOptions(_SearchOptions):
 
         align_draft      None   folder of draft .lab files (X.wav -> DIR/X.lab); an empty path is None
         draft_tolerance  0.1    seconds either side of a draft start (also stands for "not given")
-        align_edits      False  score single substitutions and deletions of every aligned transcript"""
+        align_edits      False  score single substitutions and deletions of every aligned transcript
+        align_insertions False  score single insertions at every place of every aligned transcript"""
     align_draft: Optional[str] = None
     draft_tolerance: float = DEFAULT_DRAFT_TOLERANCE
     align_edits: bool = False
+    align_insertions: bool = False
 
-    def __new__(cls, *args, align_draft=None, draft_tolerance=DEFAULT_DRAFT_TOLERANCE, align_edits=False, **kw):
+    def __new__(cls, *args, align_draft=None, draft_tolerance=DEFAULT_DRAFT_TOLERANCE, align_edits=False, align_insertions=False,
+                **kw):
         self = super().__new__(cls, *args, **kw)
         object.__setattr__(self, "align_draft", align_draft)
         object.__setattr__(self, "draft_tolerance", draft_tolerance)
         object.__setattr__(self, "align_edits", align_edits)
+        object.__setattr__(self, "align_insertions", align_insertions)
         return self
 
     def __setattr__(self, name, value):
         raise AttributeError(f"PostOptions is read-only: cannot set {name!r}")
 
-    _KEYWORD = ("align_draft", "draft_tolerance", "align_edits")
-    _KEYWORD_DEFAULTS = (None, DEFAULT_DRAFT_TOLERANCE, False)
+    _KEYWORD = ("align_draft", "draft_tolerance", "align_edits", "align_insertions")
+    _KEYWORD_DEFAULTS = (None, DEFAULT_DRAFT_TOLERANCE, False, False)
 
     def _draft(self):
         return self.align_draft, self.draft_tolerance
 
     def _later(self):
-        return self.align_draft, self.draft_tolerance, self.align_edits
+        return self.align_draft, self.draft_tolerance, self.align_edits, self.align_insertions
 
     # the NamedTuple helpers carry the keyword fields as well (the inherited ones know the tuple alone)
     @classmethod
-    def _make(cls, iterable, align_draft=None, draft_tolerance=DEFAULT_DRAFT_TOLERANCE, align_edits=False):
-        return cls(*iterable, align_draft=align_draft, draft_tolerance=draft_tolerance, align_edits=align_edits)
+    def _make(cls, iterable, align_draft=None, draft_tolerance=DEFAULT_DRAFT_TOLERANCE, align_edits=False, align_insertions=False):
+        return cls(*iterable, align_draft=align_draft, draft_tolerance=draft_tolerance, align_edits=align_edits,
+                   align_insertions=align_insertions)
 
     def _replace(self, **kw):
         later = {k: kw.pop(k, getattr(self, k)) for k in self._KEYWORD}
@@ -119,7 +125,8 @@ def _number_ge0(x):
 
 
 def resolve(post, *, align=None, align_scores=None, decode=None, switch_penalty=None, decode_scores=None, phoneme_bigram=None,
-            bigram_weight=None, bigram_scores=None, align_draft=None, draft_tolerance=None, align_edits=None) -> PostOptions:
+            bigram_weight=None, bigram_scores=None, align_draft=None, draft_tolerance=None, align_edits=None,
+            align_insertions=None) -> PostOptions:
     """post: the config's `postprocess` mapping (None: {}).  Per option the argument wins; None leaves it to `post[<option>]`, and a
     key that is absent (or None) to the default.  -> PostOptions, or ValueError for the first broken rule of the module's table."""
     post = post or {}
@@ -178,5 +185,10 @@ def resolve(post, *, align=None, align_scores=None, decode=None, switch_penalty=
     if align_edits and align != "viterbi":
         raise ValueError("align_edits needs align='viterbi' (postprocess.align: viterbi): the greedy match has no lattice to score an "
                          "edit on")
+    align_insertions = bool(pick("align_insertions", align_insertions, False))
+    if align_insertions and align != "viterbi":
+        raise ValueError("align_insertions needs align='viterbi' (postprocess.align: viterbi): the greedy match has no lattice to "
+                         "score an insertion on")
     return PostOptions(align, align_scores, decode, switch_penalty, decode_scores, phoneme_bigram, bigram_weight, bigram_scores,
-                       align_draft=align_draft, draft_tolerance=draft_tolerance, align_edits=align_edits)
+                       align_draft=align_draft, draft_tolerance=draft_tolerance, align_edits=align_edits,
+                       align_insertions=align_insertions)
