@@ -344,6 +344,26 @@ int32_t wfl_align_windowed(const float* logits, int64_t ldl, int32_t C, int32_t 
                            const int32_t* tok_win, const int32_t* gap_cls, int32_t n_clips, void* workspace, int64_t workspace_bytes,
                            int32_t* ids, int32_t* tok, float* score, int32_t* status, void* stream);
 
+/* ---- wfl_align with a minimum duration per token (`postprocess.min_duration`; wfl-asr_amd/align.py).  wfl_align_windowed's arguments
+ * (tok_win may be null: no windows) plus tok_min (device), [total tokens] int32, rows as tok_cls: token k occupies at least D_k =
+ * tok_min[k] frames, 1 <= D_k <= 8 (0.16 s on the 20 ms clock).  A run of token k is frame 1 in B_k, frames 2 .. D_k - 1 in the chain
+ * states H_k^2 .. H_k^{D_k-1}, and every later frame in I_k:
+ *     H_k^2(t) = B_k(t-1) + EI_t(k)
+ *     H_k^j(t) = H_k^{j-1}(t-1) + EI_t(k)
+ *     I_k(t)   = max{ I_k(t-1), X_k(t-1) } + EI_t(k)      X_k = H_k^{D_k-1} for D_k >= 3, B_k for D_k <= 2; I_k first on a tie
+ * The token is left from I_k alone, towards G_{k+1} or B_{k+1}; where D_k == 1 also from B_k, as in wfl_align.  End states G_N | I_{N-1},
+ * and B_{N-1} only when D_{N-1} == 1.  Chain frames emit the token's I classes and are written to ids / tok exactly as I_k frames are, so
+ * the tag string stays BIO-legal and every token keeps one contiguous run, now of at least D_k frames.  G, B, the windows (on EB alone),
+ * the other emissions, the tie order, the renormalisation and the workspace (wfl_align_workspace_bytes: the chain needs no backpointer
+ * bits) are wfl_align_windowed's, and with every D_k == 1 so is every output, bit for bit (of wfl_align with a null tok_win).
+ * status[b]: wfl_align's codes; 1 "no path": T < N, sum of D_k > T, or windows and durations that cannot both be met (the host rule
+ * e_k = max(lo_k, e_{k-1} + D_{k-1}) <= hi_k, e_{N-1} + D_{N-1} <= T predicts it); 4 also for a D_k outside 1 .. 8.  Such a clip gets
+ * ids = o_id, tok = -1, score 0.  A null tok_min with any token present is a host-side -1. */
+int32_t wfl_align_min_duration(const float* logits, int64_t ldl, int32_t C, int32_t o_id, const int64_t* frame_off_host,
+                               const int32_t* n_frames_host, const int32_t* tok_off_host, const int32_t* n_tok_host, const int32_t* tok_cls,
+                               const int32_t* tok_win, const int32_t* tok_min, const int32_t* gap_cls, int32_t n_clips, void* workspace,
+                               int64_t workspace_bytes, int32_t* ids, int32_t* tok, float* score, int32_t* status, void* stream);
+
 /* ---- Posteriors of a Viterbi alignment by forward-backward on the GPU (`postprocess.align_scores`; wfl-asr_amd/align.py).  No
  * counterpart in the reference, which reports no confidence for its string match.  The lattice, emissions EB / EI / EG, start and end
  * states, caps (C <= 1024, N <= 4096) and argument conventions are wfl_align's.  The weight of a path is exp(sum_t e_t(state_t));

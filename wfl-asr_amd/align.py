@@ -7,7 +7,9 @@ the frame logits for the best path that spells exactly the transcript, in order 
 token gets one contiguous, time-ordered run of frames, none is dropped.
 
   viterbi_align         the C ABI on CUDA tensors: a ragged batch of clips in one call; with `windows`, every token may open only
-                        inside its (lo, hi) frame window (`wfl_align_windowed`, `postprocess.align_draft`)
+                        inside its (lo, hi) frame window (`wfl_align_windowed`, `postprocess.align_draft`); with `min_frames`,
+                        every token occupies at least that many frames (`wfl_align_min_duration`, `postprocess.min_duration`)
+  min_frames_for        `postprocess.min_duration` (seconds, or seconds per token name) -> frames per transcript token
   alignment_posteriors  forward-backward over the same lattice (csrc/align_posterior.hip, `wfl_align_posterior`; of a batch packed with
                         windows, `wfl_align_posterior_windowed`): logZ, and per token
                         the posterior of the run Viterbi chose and the spread of its start (`postprocess.align_scores`)
@@ -42,6 +44,7 @@ from ._lib import back_to_back, host_ptr as _hp, ptr as _ptr
 MAX_TOKENS = 4096          # wfl_align's token cap per clip (status 2 above it)
 MAX_ALTERNATIVES = 4       # (B, I) pairs per token
 MAX_GAP = 8                # gap classes per clip
+MAX_MIN_FRAMES = 8         # wfl_align_min_duration's cap on a token's minimum duration, frames (csrc/lattice.h)
 PAUSES = ("SP", "AP")
 
 STATUS_OK, STATUS_INFEASIBLE, STATUS_OVER_CAP, STATUS_BAD_CLASS = 0, 1, 2, 4
@@ -101,6 +104,7 @@ class PackedClips(NamedTuple):
     d_tc: torch.Tensor
     d_gc: torch.Tensor
     d_win: torch.Tensor = None      # [tokens, 2] int32 (lo, hi) start windows; None: the unwindowed entries
+    d_min: torch.Tensor = None      # [tokens] int32 minimum durations in frames; None: the entries without them
 
 
 def _pack_windows(windows, N):
@@ -122,17 +126,42 @@ def _pack_windows(windows, N):
     return out.astype(np.int32)
 
 
-def pack_clips(logits, n_frames, token_classes, gap_classes, frame_offsets=None, windows=None) -> PackedClips:
+def _pack_min_frames(min_frames, N):
+    """Per clip a list of ints per token, or None for all 1 -> [max(tokens, 1)] int32, rows as the token table's.  The values are
+    not judged here: a D outside 1 .. MAX_MIN_FRAMES is the kernel's STATUS_BAD_CLASS for its clip."""
+    if len(min_frames) != len(N):
+        raise ValueError("min_frames needs one entry per clip (None: every token 1)")
+    out = np.ones(max(int(N.sum()), 1), np.int64)
+    k0 = 0
+    for d, n in zip(min_frames, N):
+        if d is not None:
+            if any(isinstance(x, (bool, np.bool_)) or not isinstance(x, (int, np.integer)) for x in d):
+                raise ValueError("min_frames are ints (frames)")
+            d = np.asarray(d, np.int64).reshape(-1)
+            if len(d) != n:
+                raise ValueError(f"a clip with {n} tokens needs {n} minimum durations, got {len(d)}")
+            out[k0:k0 + n] = d
+        k0 += int(n)
+    if out.min() < -2 ** 31 or out.max() > 2 ** 31 - 1:
+        raise ValueError("min_frames are int32")
+    return out.astype(np.int32)
+
+
+def pack_clips(logits, n_frames, token_classes, gap_classes, frame_offsets=None, windows=None, min_frames=None) -> PackedClips:
     """Validate a ragged batch and upload its token and gap tables once; pass the result as `packed=` to viterbi_align and to
     alignment_posteriors of the same batch (the packing is host work that grows with the token count).  windows: per clip a list of
     (lo, hi) per token -- the frames, inclusive, at which the token may open -- or None for a clip with open windows; None for the
-    whole batch packs for the unwindowed entries."""
+    whole batch packs for the unwindowed entries.  min_frames: per clip a list of ints per token -- the frames the token occupies at
+    least, 1 .. MAX_MIN_FRAMES -- or None for a clip of all 1; None for the whole batch packs for the entries without minimum
+    durations."""
     nb, T, N, F0, K0, tc, gc = _pack_clips(logits, n_frames, token_classes, gap_classes, frame_offsets)
     d_win = torch.from_numpy(_pack_windows(windows, N)).to(logits.device) if windows is not None else None
-    return PackedClips(nb, T, N, F0, K0, torch.from_numpy(tc).to(logits.device), torch.from_numpy(gc).to(logits.device), d_win)
+    d_min = torch.from_numpy(_pack_min_frames(min_frames, N)).to(logits.device) if min_frames is not None else None
+    return PackedClips(nb, T, N, F0, K0, torch.from_numpy(tc).to(logits.device), torch.from_numpy(gc).to(logits.device), d_win, d_min)
 
 
-def viterbi_align(logits, n_frames, token_classes, gap_classes, o_id, frame_offsets=None, stream=None, packed=None, windows=None):
+def viterbi_align(logits, n_frames, token_classes, gap_classes, o_id, frame_offsets=None, stream=None, packed=None, windows=None,
+                  min_frames=None):
     """Forced alignment of a ragged batch of clips on the GPU.
 
     logits         [rows, C] float32 CUDA tensor (rows contiguous in C; clip b = rows frame_offsets[b] .. + n_frames[b]).  With
@@ -146,10 +175,16 @@ def viterbi_align(logits, n_frames, token_classes, gap_classes, o_id, frame_offs
                    frame lo <= t <= hi of its clip.  None (the default) runs wfl_align; anything else wfl_align_windowed, where a clip
                    whose windows no path satisfies gets STATUS_INFEASIBLE (windows_feasible predicts it).  With `packed`, the windows
                    are the ones packed there.
+    min_frames     per clip a list of ints per token, or None for a clip of all 1: token k occupies at least that many frames
+                   (1 .. MAX_MIN_FRAMES; min_frames_for).  None (the default) runs exactly the calls above; anything else
+                   wfl_align_min_duration, with the windows if there are any: a clip whose durations (and windows) no path meets gets
+                   STATUS_INFEASIBLE (windows_feasible(T, windows, min_frames) predicts it), a value outside the range
+                   STATUS_BAD_CLASS.  With `packed`, the durations are the ones packed there.
     -> (ids [rows] int32, tok [rows] int32, score [clips] float32, status [clips] int32), CUDA tensors on `stream`'s device."""
     lib = _lib.load()
-    nb, T, N, F0, K0, d_tc, d_gc, d_win = packed if packed is not None else pack_clips(logits, n_frames, token_classes, gap_classes,
-                                                                                       frame_offsets, windows)
+    nb, T, N, F0, K0, d_tc, d_gc, d_win, d_min = packed if packed is not None else pack_clips(logits, n_frames, token_classes,
+                                                                                              gap_classes, frame_offsets, windows,
+                                                                                              min_frames)
     dev = logits.device
     rows = logits.shape[0]
     ws_n = workspace_bytes(T, N)
@@ -162,13 +197,24 @@ def viterbi_align(logits, n_frames, token_classes, gap_classes, o_id, frame_offs
         st = stream if stream is not None else torch.cuda.current_stream(dev)
         head = (_ptr(logits), logits.stride(0), logits.shape[1], int(o_id), _hp(F0), _hp(T), _hp(K0), _hp(N), _ptr(d_tc))
         tail = (_ptr(d_gc), nb, _ptr(ws), ws_n, _ptr(ids), _ptr(tok), _ptr(score), _ptr(status), C.c_void_p(st.cuda_stream))
-        if d_win is None:
+        if d_min is not None:
+            _lib.check(lib.wfl_align_min_duration(*head, _ptr(d_win) if d_win is not None else None, _ptr(d_min), *tail),
+                       "wfl_align_min_duration")
+        elif d_win is None:
             _lib.check(lib.wfl_align(*head, *tail), "wfl_align")
         else:
             _lib.check(lib.wfl_align_windowed(*head, _ptr(d_win), *tail), "wfl_align_windowed")
-        for t in (d_tc, d_gc, ws) + ((d_win,) if d_win is not None else ()):
+        for t in (d_tc, d_gc, ws) + tuple(x for x in (d_win, d_min) if x is not None):
             t.record_stream(st)
     return ids, tok, score[:nb], status[:nb]
+
+
+def _without_min_frames(packed, what):
+    """The sums of alignment_posteriors, edit_scores and insertion_scores run over the lattice WITHOUT minimum durations: a batch
+    packed with them is refused, a score must speak of the lattice its search ran on."""
+    if packed.d_min is not None:
+        raise ValueError(f"{what} scores the lattice without minimum durations: this batch was packed with min_frames")
+    return packed[:8]
 
 
 def posterior_workspace_bytes(n_frames, n_tokens) -> int:
@@ -195,8 +241,8 @@ def alignment_posteriors(logits, n_frames, token_classes, gap_classes, o_id, tok
     Viterbi's start) and standard deviation of the token's start, in frames.  A clip with status != 0 gets zeros
     (STATUS_NOT_A_PATH: `tok` does not hold every token of the clip)."""
     lib = _lib.load()
-    nb, T, N, F0, K0, d_tc, d_gc, d_win = packed if packed is not None else pack_clips(logits, n_frames, token_classes, gap_classes,
-                                                                                       frame_offsets)
+    nb, T, N, F0, K0, d_tc, d_gc, d_win = _without_min_frames(packed if packed is not None else pack_clips(
+        logits, n_frames, token_classes, gap_classes, frame_offsets), "alignment_posteriors")
     dev = logits.device
     if not tok.is_cuda or tok.device != dev or tok.dtype != torch.int32 or tok.dim() != 1 or tok.stride(0) != 1 \
             or tok.shape[0] != logits.shape[0]:
@@ -243,8 +289,8 @@ def edit_scores(logits, n_frames, token_classes, gap_classes, o_id, substitutes,
     edited transcript has no path.  logz is alignment_posteriors' logz.  A clip with status != 0 gets zeros; a class id of
     `substitutes` outside the logits' columns is STATUS_BAD_CLASS for every clip."""
     lib = _lib.load()
-    nb, T, N, F0, K0, d_tc, d_gc, d_win = packed if packed is not None else pack_clips(logits, n_frames, token_classes, gap_classes,
-                                                                                       frame_offsets)
+    nb, T, N, F0, K0, d_tc, d_gc, d_win = _without_min_frames(packed if packed is not None else pack_clips(
+        logits, n_frames, token_classes, gap_classes, frame_offsets), "edit_scores")
     sub = np.asarray(substitutes, np.int64).reshape(-1, 2)
     P = len(sub)
     if P > MAX_SUBSTITUTES:
@@ -293,8 +339,8 @@ def insertion_scores(logits, n_frames, token_classes, gap_classes, o_id, substit
     logz is alignment_posteriors' logz.  A clip with status != 0 gets zeros; a class id of `substitutes` outside the logits' columns
     is STATUS_BAD_CLASS for every clip."""
     lib = _lib.load()
-    nb, T, N, F0, K0, d_tc, d_gc, d_win = packed if packed is not None else pack_clips(logits, n_frames, token_classes, gap_classes,
-                                                                                       frame_offsets)
+    nb, T, N, F0, K0, d_tc, d_gc, d_win = _without_min_frames(packed if packed is not None else pack_clips(
+        logits, n_frames, token_classes, gap_classes, frame_offsets), "insertion_scores")
     sub = np.asarray(substitutes, np.int64).reshape(-1, 2)
     P = len(sub)
     if P > MAX_SUBSTITUTES:
@@ -435,16 +481,42 @@ def path_segments(ids, tok, chunk_frames, chunk_offsets, chunk_clock, table: npo
     return [(a, b, transcript[k]) for a, b, k in segs]
 
 
-def windows_feasible(T, windows) -> bool:
+def windows_feasible(T, windows, min_frames=None) -> bool:
     """Whether some path of a T-frame clip opens every token inside its window, i.e. whether the windowed search will NOT report
     STATUS_INFEASIBLE.  Tokens open at strictly increasing frames and nothing else constrains them (a token may be one frame long,
-    gaps may be empty), so the earliest feasible start of each token decides: e_k = max(lo_k, e_{k-1} + 1) <= min(hi_k, T - 1)."""
-    e = -1
-    for lo, hi in np.asarray(windows, np.int64).reshape(-1, 2):
-        e = max(int(lo), e + 1)
-        if e > min(int(hi), int(T) - 1):
+    gaps may be empty), so the earliest feasible start of each token decides: e_k = max(lo_k, e_{k-1} + 1) <= min(hi_k, T - 1).
+    min_frames (per token; None: all 1): token k occupies at least D_k frames, so e_k = max(lo_k, e_{k-1} + D_{k-1}) <= hi_k and the
+    last run ends inside the clip, e_{N-1} + D_{N-1} <= T -- for every D_k == 1 the rule above."""
+    w = np.asarray(windows, np.int64).reshape(-1, 2)
+    d = np.ones(len(w), np.int64) if min_frames is None else np.asarray(min_frames, np.int64).reshape(-1)
+    if len(d) != len(w):
+        raise ValueError("one minimum duration per window")
+    e, prev = 0, 0                                       # e_{k-1} + D_{k-1}: the first frame the next token may open at
+    for (lo, hi), dk in zip(w, d):
+        e = max(int(lo), e + prev)
+        if e > int(hi) or e + int(dk) > int(T):
             return False
+        prev = int(dk)
     return True
+
+
+def min_frames_for(transcript, spec, frame_duration):
+    """The minimum duration of every transcript token in frames (`postprocess.min_duration`) -> [int] for viterbi_align's
+    min_frames.  spec: a number of seconds for every token, or a mapping {token name: seconds, "default": seconds} (names are the
+    transcript's own tokens, i.e. output names; "default", when absent 0, serves the others).  seconds -> max(1, ceil(seconds /
+    frame_duration - 1e-9)) frames; more than MAX_MIN_FRAMES of them is a ValueError."""
+    if isinstance(spec, (tuple, list)):                  # (the normalised, hashable form PostOptions carries)
+        spec = dict(spec)
+    table = spec if isinstance(spec, dict) else {"default": spec}
+
+    def frames(seconds):
+        n = max(1, int(np.ceil(float(seconds) / frame_duration - 1e-9)))
+        if n > MAX_MIN_FRAMES:
+            raise ValueError(f"a minimum duration of {seconds} s is {n} frames, more than the {MAX_MIN_FRAMES} the search holds")
+        return n
+    by_name = {name: frames(sec) for name, sec in table.items()}
+    default = by_name.get("default", 1)
+    return [by_name[t] if t != "default" and t in by_name else default for t in transcript]
 
 
 def draft_windows(draft_segments, chunk_frames, chunk_clock, tolerance_s, frame_duration):

@@ -29,6 +29,13 @@
 // wfl_align_windowed is the same kernel instantiated with WIN: every token's EB passes through lattice.h's win_mask (the token may open
 // only inside its window), and a clip whose best end state is -inf -- no path satisfies the windows -- reports status 1 before the
 // backtrace.  The unwindowed instantiation holds none of it.
+//
+// wfl_align_min_duration is the kernel instantiated with MIND (with and without WIN): token k occupies at least D_k frames, by the chain
+// states of lattice.h (chain_out / chain_shift), kept in registers beside G, B and I.  A chain frame has one predecessor, so it needs no
+// backpointer: the bits stay 6 per slot and frame, and the I_k bit "entered" now means "from X_k", the chain's last state.  The backtrace
+// then knows the D_k - 2 frames before it to be chain frames of token k (written as I_k frames) and the one before those to be B_k, whose
+// G / B bits it reads there.  The B that a token's successor sees -- inside a thread, through the exchange, and as an end state -- is
+// -inf where D_k > 1: the token is left from I_k alone.
 #include "lattice.h"
 #include "wfl_asr.h"
 
@@ -52,6 +59,7 @@ struct AlignLaunch {
   int n;
   LatClip clip[CLIPS_PER_LAUNCH];
   const int* tok_win;  // [total tokens][2] = (lo, hi), the windowed kernels alone (last: the other fields stay where they were)
+  const int* tok_min;  // [total tokens] D_k, the minimum-duration kernels alone
 };
 
 template <int NT, int R>
@@ -64,7 +72,8 @@ struct Cfg : LdsBase<NT, R, 2 * NT * 8> {                // its own between alt 
 };
 
 // WIN: the start windows of wfl_align_windowed (lattice.h win_mask); false is wfl_align's kernel, instruction for instruction
-template <int NT, int R, bool WIN>
+// MIND: the minimum durations of wfl_align_min_duration (lattice.h chain_*); false leaves the two kernels above as they were
+template <int NT, int R, bool WIN, bool MIND>
 __global__ __launch_bounds__(NT) void align_kernel(AlignLaunch a) {
   using K = Cfg<NT, R>;
   extern __shared__ __attribute__((aligned(16))) char lds[];
@@ -86,7 +95,23 @@ __global__ __launch_bounds__(NT) void align_kernel(AlignLaunch a) {
   const float NEG = -INFINITY;
 
   int g[NGAP];
-  const int st = lattice_setup<NT, R>(cl, C, a.tok_cls, a.gap_cls, alt, misc, g);
+  int st = lattice_setup<NT, R>(cl, C, a.tok_cls, a.gap_cls, alt, misc, g);
+  int dm[MIND ? R : 1];                         // this thread's slots' minimum durations, in registers
+  if constexpr (MIND) {
+    if (st == 0) {                              // (the same in every thread).  A D_k outside 1 .. MAX_MIN_FRAMES: status 4
+      if (tid == 0) misc[3] = 0;
+      __syncthreads();
+      bool bad = false;
+#pragma unroll
+      for (int r = 0; r < R; ++r) {
+        dm[r] = load_min(a.tok_min, cl.tok_off, tid * R + r, N);
+        if (dm[r] < 1 || dm[r] > MAX_MIN_FRAMES) bad = true;
+      }
+      if (bad) misc[3] = 1;
+      __syncthreads();
+      if (misc[3]) st = 4;
+    }
+  }
   if (st != 0 || T == 0) {
     for (int t = tid; t < T; t += NT) { ids[t] = a.o_id; tokp[t] = -1; }
     if (tid == 0) { a.score[cl.clip] = 0.f; a.status[cl.clip] = st; }
@@ -100,6 +125,13 @@ __global__ __launch_bounds__(NT) void align_kernel(AlignLaunch a) {
   float G[R], B[R], I[R];
 #pragma unroll
   for (int r = 0; r < R; ++r) G[r] = B[r] = I[r] = NEG;
+  float H[MIND ? R : 1][CHAIN];                // the chain states H^2 .. H^{MAX_MIN_FRAMES - 1} of every slot
+  if constexpr (MIND) {
+#pragma unroll
+    for (int r = 0; r < R; ++r)
+#pragma unroll
+      for (int j = 0; j < CHAIN; ++j) H[r][j] = NEG;
+  }
   if (tid == 0) G[0] = 0.f;                    // a virtual frame -1 in G_0: frame 0 starts in G_0 or B_0
   xch[NT + tid] = make_float2(NEG, NEG);
   stage.load(0);
@@ -107,9 +139,14 @@ __global__ __launch_bounds__(NT) void align_kernel(AlignLaunch a) {
   stage.load(1);
   __syncthreads();
 
-  int4 av[R];                                   // this thread's slots' alternatives, for the whole forward pass
+  // this thread's slots' alternatives, for the whole forward pass.  (512 x 9 with the chain: 4 R registers too many, it would spill --
+  // that one configuration reads them from LDS every frame)
+  constexpr bool AVR = !(MIND && NT >= 512);
+  int4 av[AVR ? R : 1];
+  if constexpr (AVR) {
 #pragma unroll
-  for (int r = 0; r < R; ++r) av[r] = alt[tid * R + r];
+    for (int r = 0; r < R; ++r) av[r] = alt[tid * R + r];
+  }
   int2 wn[WIN ? R : 1];                         // this thread's slots' start windows, in registers
   if constexpr (WIN) load_windows<R>(a.tok_win, cl.tok_off, N, wn);
   unsigned* bp = a.bp + cl.ws_off;
@@ -135,7 +172,10 @@ __global__ __launch_bounds__(NT) void align_kernel(AlignLaunch a) {
 #pragma unroll
     for (int r = R - 1; r >= 0; --r) {         // descending: slot r - 1's previous-frame values are still in place
       const int k = tid * R + r;
-      const float pB1 = r ? B[r > 0 ? r - 1 : 0] : nb.x;
+      float pB1 = r ? B[r > 0 ? r - 1 : 0] : nb.x;
+      if constexpr (MIND) {                    // the left token is left from its I alone where its D > 1 (nb.x: masked by its owner)
+        if (r && dm[r > 0 ? r - 1 : 0] > 1) pB1 = NEG;
+      }
       const float pI1 = r ? I[r > 0 ? r - 1 : 0] : nb.y;
       float m = G[r];
       unsigned cg = 0;
@@ -143,18 +183,25 @@ __global__ __launch_bounds__(NT) void align_kernel(AlignLaunch a) {
       if (pB1 > m) { m = pB1; cg = 2; }
       float mi = I[r];
       unsigned ci = 0;
-      if (B[r] > mi) { mi = B[r]; ci = 1; }
+      float x = B[r];                          // what I_k is entered from
+      if constexpr (MIND) x = chain_out(B[r], H[r], dm[r]);
+      if (x > mi) { mi = x; ci = 1; }
       float eb = NEG, ei = NEG;
-      if (k < N) tok_emission(row, av[r], eb, ei);
+      if (k < N) {
+        if constexpr (AVR) tok_emission(row, av[r], eb, ei);
+        else tok_emission(row, alt[k], eb, ei);
+      }
       if constexpr (WIN) eb = win_mask(eb, t, wn[r]);
       G[r] = k <= N ? m + eg : NEG;
+      if constexpr (MIND) chain_shift(H[r], B[r], ei, dm[r]);
       B[r] = m + eb;
       I[r] = mi + ei;
       bits[(6 * r) >> 5] |= cg << ((6 * r) & 31);
       bits[(6 * r + 2) >> 5] |= cg << ((6 * r + 2) & 31);
       bits[(6 * r + 4) >> 5] |= ci << ((6 * r + 4) & 31);
     }
-    xch[(t & 1) * NT + tid] = make_float2(B[R - 1], I[R - 1]);
+    if constexpr (MIND) xch[(t & 1) * NT + tid] = make_float2(dm[R - 1] > 1 ? NEG : B[R - 1], I[R - 1]);
+    else xch[(t & 1) * NT + tid] = make_float2(B[R - 1], I[R - 1]);
     unsigned* bw = bp + ((long)t * NT + tid) * K::WPT;
 #pragma unroll
     for (int w = 0; w < K::WPT; ++w) bw[w] = bits[w];
@@ -163,6 +210,12 @@ __global__ __launch_bounds__(NT) void align_kernel(AlignLaunch a) {
       float lm = NEG;
 #pragma unroll
       for (int r = 0; r < R; ++r) lm = fmaxf(lm, fmaxf(G[r], fmaxf(B[r], I[r])));
+      if constexpr (MIND) {
+#pragma unroll
+        for (int r = 0; r < R; ++r)
+#pragma unroll
+          for (int j = 0; j < CHAIN; ++j) lm = fmaxf(lm, H[r][j]);
+      }
       renorm_publish(lm, wmax);
     }
     __syncthreads();                           // the neighbour exchange and the renormalisation share it
@@ -173,6 +226,12 @@ __global__ __launch_bounds__(NT) void align_kernel(AlignLaunch a) {
       const float M = renorm_max<K::NW>(wmax);
 #pragma unroll
       for (int r = 0; r < R; ++r) { G[r] -= M; B[r] -= M; I[r] -= M; }
+      if constexpr (MIND) {
+#pragma unroll
+        for (int r = 0; r < R; ++r)
+#pragma unroll
+          for (int j = 0; j < CHAIN; ++j) H[r][j] -= M;
+      }
       sub = M;
       acc += (double)M;
     }
@@ -180,6 +239,11 @@ __global__ __launch_bounds__(NT) void align_kernel(AlignLaunch a) {
 
   // ---- the best end state
   publish_end_states<R>(N, G, B, I, fin);
+  if constexpr (MIND) {                         // B_{N-1} ends the clip only where D_{N-1} == 1 (the thread that published it)
+#pragma unroll
+    for (int r = 0; r < R; ++r)
+      if (tid * R + r == N - 1 && dm[r] > 1) fin[2] = NEG;
+  }
   __syncthreads();
   float best = 0.f;
   if (tid == 0) {
@@ -190,11 +254,11 @@ __global__ __launch_bounds__(NT) void align_kernel(AlignLaunch a) {
       if (fin[2] > best) { best = fin[2]; s = 3 * N - 2; }
     }
     misc[1] = s;
-    if constexpr (WIN) misc[2] = best == NEG;
+    if constexpr (WIN || MIND) misc[2] = best == NEG;
   }
   __syncthreads();
-  if constexpr (WIN) {
-    if (misc[2]) {                              // no path opens every token inside its window: status 1, the backpointers never walked
+  if constexpr (WIN || MIND) {
+    if (misc[2]) {                              // no path meets every window and duration: status 1, the backpointers never walked
       for (int t = tid; t < T; t += NT) { ids[t] = a.o_id; tokp[t] = -1; }
       if (tid == 0) { a.score[cl.clip] = 0.f; a.status[cl.clip] = 1; }
       return;
@@ -203,6 +267,7 @@ __global__ __launch_bounds__(NT) void align_kernel(AlignLaunch a) {
 
   // ---- backtrace, ALIGN_W frames per window
   int s = misc[1];
+  int chain = 0;                                // thread 0: chain frames of the run still to walk; a run's opening may straddle windows
   for (int thi = T - 1; thi >= 1;) {
     const int tlo = max(1, thi - ALIGN_W + 1);
     const int nf = thi - tlo + 1;
@@ -218,11 +283,23 @@ __global__ __launch_bounds__(NT) void align_kernel(AlignLaunch a) {
     if (tid == 0) {
       for (int t = thi; t >= tlo; --t) {
         tokp[t] = s;
+        if constexpr (MIND) {
+          if (chain > 0) {                      // frame t is a chain frame (written as I_k); the frame before the chain is B_k
+            if (--chain == 0) s -= 1;
+            continue;
+          }
+        }
         const int k = s / 3, j = s - 3 * k;
         const int th = k / R, r = k - th * R;
         const int pos = 2 * (3 * r + j);
         const int wi = (t - tlo) * nw + (th - th_lo) * K::WPT + (pos >> 5);
         const unsigned ch = (wi >= 0 && wi < nf * nw) ? (win[wi] >> (pos & 31)) & 3u : 0u;
+        if constexpr (MIND) {
+          if (j == 2 && ch == 1 && k < N) {     // I_k entered at t: from B_k for D_k <= 2, else through D_k - 2 chain frames
+            const int d = a.tok_min[cl.tok_off + k];
+            if (d >= 3) { chain = d - 2; continue; }
+          }
+        }
         s = j == 2 ? s - (int)ch : 3 * k - (int)ch;
         s = max(s, 0);
       }
@@ -290,22 +367,23 @@ int64_t wfl_align_workspace_bytes(const int32_t* n_frames_host, const int32_t* n
 
 namespace {
 
-// wfl_align (WIN false) and wfl_align_windowed: one host path
-template <bool WIN>
+// wfl_align (WIN false), wfl_align_windowed and wfl_align_min_duration (MIND, with or without windows): one host path
+template <bool WIN, bool MIND>
 int align_batch(const char* fn, const float* logits, int64_t ldl, int32_t C, int32_t o_id, const int64_t* frame_off_host,
                 const int32_t* n_frames_host, const int32_t* tok_off_host, const int32_t* n_tok_host, const int32_t* tok_cls,
-                const int32_t* tok_win, const int32_t* gap_cls, int32_t n_clips, void* workspace, int64_t workspace_bytes, int32_t* ids,
-                int32_t* tok, float* score, int32_t* status, void* stream) {
+                const int32_t* tok_win, const int32_t* tok_min, const int32_t* gap_cls, int32_t n_clips, void* workspace,
+                int64_t workspace_bytes, int32_t* ids, int32_t* tok, float* score, int32_t* status, void* stream) {
   const int64_t need = wfl_align_workspace_bytes(n_frames_host, n_tok_host, n_clips);
   bool any_tok = false, any_frame = false;
   int rc = check_clip_args(fn, C, o_id, ldl, frame_off_host, n_frames_host, tok_off_host, n_tok_host, n_clips, need, any_tok, any_frame);
   if (rc || n_clips == 0) return rc;
-  if (!score || !status || !gap_cls || (any_tok && (!tok_cls || (WIN && !tok_win))) || (any_frame && (!logits || !ids || !tok)))
+  if (!score || !status || !gap_cls || (any_tok && (!tok_cls || (WIN && !tok_win) || (MIND && !tok_min))) ||
+      (any_frame && (!logits || !ids || !tok)))
     return fail(fn, -1, "null device pointer");
   if ((rc = check_workspace(fn, need, workspace, workspace_bytes))) return rc;
   hipStream_t s = (hipStream_t)stream;
   AlignLaunch a{};
-  a.logits = logits; a.ldl = ldl; a.C = C; a.o_id = o_id; a.tok_cls = tok_cls; a.gap_cls = gap_cls; a.tok_win = tok_win;
+  a.logits = logits; a.ldl = ldl; a.C = C; a.o_id = o_id; a.tok_cls = tok_cls; a.gap_cls = gap_cls; a.tok_win = tok_win; a.tok_min = tok_min;
   a.bp = (unsigned*)workspace; a.ids = ids; a.tok = tok; a.score = score; a.status = status;
   return launch_clips<NCFG>(
       a, n_clips,
@@ -318,7 +396,7 @@ int align_batch(const char* fn, const float* logits, int64_t ldl, int32_t C, int
       [&](int cfg, const AlignLaunch& a) {
         return dispatch_cfg(cfg, [&](auto sh) {
           constexpr int NT = decltype(sh)::NT, R = decltype(sh)::R;
-          return launch_cfg<align_kernel<NT, R, WIN>, NT, Cfg<NT, R>::LDS>(fn, a, s);
+          return launch_cfg<align_kernel<NT, R, WIN, MIND>, NT, Cfg<NT, R>::LDS>(fn, a, s);
         });
       });
 }
@@ -330,16 +408,27 @@ extern "C" {
 int32_t wfl_align(const float* logits, int64_t ldl, int32_t C, int32_t o_id, const int64_t* frame_off_host, const int32_t* n_frames_host,
                   const int32_t* tok_off_host, const int32_t* n_tok_host, const int32_t* tok_cls, const int32_t* gap_cls, int32_t n_clips,
                   void* workspace, int64_t workspace_bytes, int32_t* ids, int32_t* tok, float* score, int32_t* status, void* stream) {
-  return align_batch<false>("wfl_align", logits, ldl, C, o_id, frame_off_host, n_frames_host, tok_off_host, n_tok_host, tok_cls, nullptr,
-                            gap_cls, n_clips, workspace, workspace_bytes, ids, tok, score, status, stream);
+  return align_batch<false, false>("wfl_align", logits, ldl, C, o_id, frame_off_host, n_frames_host, tok_off_host, n_tok_host, tok_cls,
+                                   nullptr, nullptr, gap_cls, n_clips, workspace, workspace_bytes, ids, tok, score, status, stream);
 }
 
 int32_t wfl_align_windowed(const float* logits, int64_t ldl, int32_t C, int32_t o_id, const int64_t* frame_off_host,
                            const int32_t* n_frames_host, const int32_t* tok_off_host, const int32_t* n_tok_host, const int32_t* tok_cls,
                            const int32_t* tok_win, const int32_t* gap_cls, int32_t n_clips, void* workspace, int64_t workspace_bytes,
                            int32_t* ids, int32_t* tok, float* score, int32_t* status, void* stream) {
-  return align_batch<true>("wfl_align_windowed", logits, ldl, C, o_id, frame_off_host, n_frames_host, tok_off_host, n_tok_host, tok_cls,
-                           tok_win, gap_cls, n_clips, workspace, workspace_bytes, ids, tok, score, status, stream);
+  return align_batch<true, false>("wfl_align_windowed", logits, ldl, C, o_id, frame_off_host, n_frames_host, tok_off_host, n_tok_host,
+                                  tok_cls, tok_win, nullptr, gap_cls, n_clips, workspace, workspace_bytes, ids, tok, score, status, stream);
+}
+
+int32_t wfl_align_min_duration(const float* logits, int64_t ldl, int32_t C, int32_t o_id, const int64_t* frame_off_host,
+                               const int32_t* n_frames_host, const int32_t* tok_off_host, const int32_t* n_tok_host, const int32_t* tok_cls,
+                               const int32_t* tok_win, const int32_t* tok_min, const int32_t* gap_cls, int32_t n_clips, void* workspace,
+                               int64_t workspace_bytes, int32_t* ids, int32_t* tok, float* score, int32_t* status, void* stream) {
+  const char* fn = "wfl_align_min_duration";
+  return tok_win ? align_batch<true, true>(fn, logits, ldl, C, o_id, frame_off_host, n_frames_host, tok_off_host, n_tok_host, tok_cls, tok_win,
+                                           tok_min, gap_cls, n_clips, workspace, workspace_bytes, ids, tok, score, status, stream)
+                 : align_batch<false, true>(fn, logits, ldl, C, o_id, frame_off_host, n_frames_host, tok_off_host, n_tok_host, tok_cls,
+                                            nullptr, tok_min, gap_cls, n_clips, workspace, workspace_bytes, ids, tok, score, status, stream);
 }
 
 }  // extern "C"

@@ -7,7 +7,8 @@
 //   device  caps and constants, the per-clip record, the wave reductions, the (threads, slots per thread) configurations and their
 //           dispatch, the shared part of the LDS layout, lattice setup (status 0 / 1 / 2 / 4, the alternatives in LDS, the gap classes in
 //           registers), the staged logits ring, the emission gathers, the start-window mask of the windowed entries (win_mask: ONE mask
-//           for the search and for both sweeps of the sums), the two halves of the block-maximum renormalisation, the end states
+//           for the search and for both sweeps of the sums), the minimum-duration chain of wfl_align_min_duration, the two halves of
+//           the block-maximum renormalisation, the end states
 //   host    the argument checks the ABI entries share, "group the clips by configuration, hand out workspace offsets, launch at most
 //           64 clips at a time", and the launch that reserves a kernel's dynamic LDS once per device
 //
@@ -141,6 +142,33 @@ template <int R>
 static __device__ __forceinline__ void load_windows(const int* tok_win, int tok_off, int N, int2 (&w)[R]) {
 #pragma unroll
   for (int r = 0; r < R; ++r) w[r] = load_window(tok_win, tok_off, threadIdx.x * R + r, N);
+}
+
+// ---- minimum durations (wfl_align_min_duration): token k occupies at least D_k frames, 1 <= D_k <= MAX_MIN_FRAMES.  A run is frame 1 in
+// B_k, frames 2 .. D_k - 1 in the chain states H_k^2 .. H_k^{D_k - 1} (which emit EI as I_k does), every later frame in I_k, and the
+// token is left from I_k alone (from B_k as well where D_k == 1).  The chain of a slot is MAX_MIN_FRAMES - 2 floats in registers,
+// h[j] = H^{j + 2}, -inf where the token's D_k has no such state.  Every step is an unrolled select on D_k: no register array is
+// indexed dynamically.
+constexpr int MAX_MIN_FRAMES = 8;
+constexpr int CHAIN = MAX_MIN_FRAMES - 2;
+
+static __device__ __forceinline__ int load_min(const int* tok_min, int tok_off, int k, int N) {   // slots past the tokens: 1
+  return k < N ? tok_min[tok_off + k] : 1;
+}
+
+// X_k of the frame before: what I_k may be entered from, H_k^{D_k - 1} for D_k >= 3, B_k itself for D_k <= 2
+static __device__ __forceinline__ float chain_out(float b, const float (&h)[CHAIN], int d) {
+  float x = b;
+#pragma unroll
+  for (int j = 0; j < CHAIN; ++j) x = d == j + 3 ? h[j] : x;
+  return x;
+}
+
+// one frame: H^2 <- B + EI, H^j <- H^{j-1} + EI (b and h of the frame before), the states D_k does not reach stay -inf
+static __device__ __forceinline__ void chain_shift(float (&h)[CHAIN], float b, float ei, int d) {
+#pragma unroll
+  for (int j = CHAIN - 1; j >= 1; --j) h[j] = j + 3 <= d ? h[j - 1] + ei : -INFINITY;
+  h[0] = 3 <= d ? b + ei : -INFINITY;
 }
 
 // ---- lattice setup of a clip -> status: 2 over the cap (of the ABI or of this configuration), 1 fewer frames than tokens, 4 a class id

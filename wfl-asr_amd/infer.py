@@ -31,7 +31,7 @@ from . import audio as A
 from . import decode as DC
 from . import native_post as npost
 from . import postprocess as pp
-from .options import ALIGN_MODES, DECODE_MODES, PostOptions, resolve
+from .options import ALIGN_MODES, DECODE_MODES, PostOptions, parse_min_duration, resolve
 from .tagger import BIOPhonemeTagger, raise_on_status
 
 frame_duration = pp.FRAME_DURATION
@@ -421,7 +421,7 @@ class Labeler:
 
     def label_files(self, audio_paths, lang_id=None, confidence_threshold=0.0, verbose=True, align=None, align_scores=None,
                     decode=None, switch_penalty=None, decode_scores=None, phoneme_bigram=None, bigram_weight=None, align_draft=None,
-                    draft_tolerance=None, align_edits=None, align_insertions=None, bigram_scores=None):
+                    draft_tolerance=None, align_edits=None, align_insertions=None, min_duration=None, bigram_scores=None):
         """-> list (per file) of [(start_s, end_s, phoneme)] after merge + forced alignment; with align_scores, decode_scores or
         bigram_scores, (that list, scores); with align_edits the tuple goes on with one more list, edits, and with align_insertions
         it ends with one more, insertions.
@@ -478,11 +478,18 @@ class Labeler:
         token, and behind the last) -- the best and the second-best phoneme to insert there with the log likelihood ratio of the
         longer transcript against the transcript as written, and a flag where the best is > 0 (align.insertion_scores: on the same
         lattice as the edits, the inserted token without a window) -- or None as for align_edits.  The segments and the edits are
-        the same with and without."""
+        the same with and without.
+
+        min_duration (with align "viterbi" only; None: config postprocess.min_duration, else none): seconds, or a mapping {token
+        name: seconds, "default": seconds} -- the least time every transcript token (the named ones) occupies, held by the search
+        itself (align.viterbi_align's min_frames, align.min_frames_for: at most 8 frames).  Only transcript tokens are constrained,
+        not the SP / AP of gaps, not the free decode.  It combines with align_draft; align_scores, align_edits and
+        align_insertions beside it are refused (their passes score the lattice without durations).  A file whose durations no path
+        can meet falls back, with a message, to the alignment of the same transcript without them (the draft's windows kept)."""
         opts = self.options(align=align, align_scores=align_scores, decode=decode, switch_penalty=switch_penalty,
                             decode_scores=decode_scores, phoneme_bigram=phoneme_bigram, bigram_weight=bigram_weight,
                             bigram_scores=bigram_scores, align_draft=align_draft, draft_tolerance=draft_tolerance,
-                            align_edits=align_edits, align_insertions=align_insertions)
+                            align_edits=align_edits, align_insertions=align_insertions, min_duration=min_duration)
         edits = {} if opts.align_edits else None
         insertions = {} if opts.align_insertions else None
         final, scores = self._label_scored(audio_paths, opts, lang_id, confidence_threshold, verbose, edits=edits,
@@ -536,7 +543,8 @@ class Labeler:
             edited = {} if opts.align_edits else None
             inserted = {} if opts.align_insertions else None
             got = self._label_viterbi(paths(with_t), [forced[fi] for fi in with_t], lang_id, confidence_threshold, verbose,
-                                      opts.align_scores, [drafts[fi] for fi in with_t], opts.draft_tolerance, moved, edited, inserted)
+                                      opts.align_scores, [drafts[fi] for fi in with_t], opts.draft_tolerance, moved, edited, inserted,
+                                      opts.min_duration)
             for fi, segs, sc in zip(with_t, *got):
                 final[fi], scores[fi] = segs, sc
             if moves is not None:
@@ -820,7 +828,7 @@ class Labeler:
         return total, total_logz, total_lse, n_frames, skipped
 
     def _label_viterbi(self, audio_paths, transcripts, lang_id, threshold, verbose, want_scores=False, drafts=None, tolerance=0.0,
-                       moves=None, edits=None, insertions=None):
+                       moves=None, edits=None, insertions=None, min_duration=None):
         """Files with a transcript, align="viterbi".  Their chunks are forwarded with logits (kept on the device); the free decode of
         the same forward gives the greedy result, which the pause rule at the ends needs and which a file falls back to (with a
         message) when its transcript cannot be aligned.  Each file's chunks' valid logits rows are concatenated on the device, so
@@ -843,7 +851,12 @@ class Labeler:
 
         insertions: a dict that takes {file index: [PlaceInsertion]} (postprocess.align_insertions): align.insertion_scores in the
         same place, on the same PackedClips, with the same table, grouped by its own workspace rule.  With both on, each call runs
-        its own sweeps."""
+        its own sweeps.
+
+        min_duration: PostOptions.min_duration (postprocess.min_duration) or None.  Every transcript token of every file gets its
+        minimum frames (align.min_frames_for) and the batch goes through wfl_align_min_duration, the windows beside them.  A file
+        whose durations no path can meet (align.windows_feasible with them, before the launch; status 1, after it) is searched
+        without them, with a message, its windows kept; the scoring passes never meet a min_duration (options rule 16)."""
         lang_name = self._lang_name(lang_id)
         remap, names = self._names_for(lang_name)
         results, scores = [], []
@@ -886,21 +899,40 @@ class Labeler:
                             wins[b] = w
                         else:
                             print(f"{audio_paths[fi]}: {DRAFT_INFEASIBLE}")
+                mins = [None] * len(run)                      # per clip its tokens' minimum frames; None: none (all 1)
+                if min_duration is not None:
+                    for b, fi in enumerate(run):
+                        d = AL.min_frames_for(transcripts[fi], min_duration, frame_duration)
+                        w = wins[b] if wins[b] is not None else [AL.OPEN_WINDOW] * len(d)
+                        if AL.windows_feasible(frames[b], w, d):
+                            mins[b] = d
+                        elif frames[b] >= len(d):             # (fewer frames than tokens: the search's own status 1, as without)
+                            print(f"{audio_paths[fi]}: {MIN_DURATION_INFEASIBLE}")
                 windows = wins if any(w is not None for w in wins) else None      # (no draft in the wave: the unwindowed entries)
+                min_frames = mins if any(d is not None for d in mins) else None   # (no duration in the wave: the entries without)
                 packed = (AL.pack_clips(lg, frames, [plans[fi] for fi in run], gaps, windows=windows)
                           if want_scores or want_edits or want_ins else None)
                 d_ids, d_tok, d_score, d_st = AL.viterbi_align(lg, frames, [plans[fi] for fi in run], gaps, self.labels.index("O"),
-                                                               packed=packed, windows=windows)
+                                                               packed=packed, windows=windows, min_frames=min_frames)
                 st_all = d_st.cpu().numpy()
                 f0 = np.concatenate([[0], np.cumsum(np.asarray(frames, np.int64))[:-1]])
-                again = [b for b in range(len(run)) if wins[b] is not None and st_all[b] == AL.STATUS_INFEASIBLE]
-                if again:                                     # the safety net: the kernel found no path inside the windows
+                for _ in range(2):                            # the safety net: the kernel found no path inside the durations (dropped
+                    again = [b for b in range(len(run))       # first, the windows kept), then none inside the windows
+                             if (wins[b] is not None or mins[b] is not None) and st_all[b] == AL.STATUS_INFEASIBLE]
+                    if not again:
+                        break
                     for b in again:
-                        print(f"{audio_paths[run[b]]}: {DRAFT_INFEASIBLE}")
-                        wins[b] = None
+                        if mins[b] is not None:
+                            print(f"{audio_paths[run[b]]}: {MIN_DURATION_INFEASIBLE}")
+                            mins[b] = None
+                        else:
+                            print(f"{audio_paths[run[b]]}: {DRAFT_INFEASIBLE}")
+                            wins[b] = None
+                    kept = [wins[b] for b in again]
                     r_ids, r_tok, r_score, r_st = AL.viterbi_align(lg, [frames[b] for b in again], [plans[run[b]] for b in again],
                                                                    [gaps[b] for b in again], self.labels.index("O"),
-                                                                   frame_offsets=f0[again])
+                                                                   frame_offsets=f0[again],
+                                                                   windows=kept if any(w is not None for w in kept) else None)
                     for j, b in enumerate(again):
                         rows_b = slice(int(f0[b]), int(f0[b]) + frames[b])
                         d_ids[rows_b], d_tok[rows_b] = r_ids[rows_b], r_tok[rows_b]
@@ -1001,6 +1033,8 @@ def _clip_lse(lg, starts, ends):
     return run[torch.from_numpy(ends).to(lg.device)] - run[torch.from_numpy(starts).to(lg.device)]
 
 
+MIN_DURATION_INFEASIBLE = ("no path gives every token its minimum duration (postprocess.min_duration: too many tokens for the frames, or "
+                           "for the draft's windows); aligning the transcript without minimum durations")
 DRAFT_INFEASIBLE = ("no path opens every token inside its draft window (two starts on one frame, or more tokens than frames in between); "
                     "aligning the draft's transcript without windows")
 
@@ -1202,7 +1236,8 @@ def _write_score(lab_path, segments, score):
 def infer_audio(audio_path, config_path="config.yaml", checkpoint_path="best_model.pt", output_lab_path=None, device="cuda",
                 lang_id=None, sample=False, top_k=0, top_p=0.0, temperature=1.0, confidence_threshold=0.0, align=None,
                 align_scores=None, decode=None, switch_penalty=None, decode_scores=None, phoneme_bigram=None, bigram_weight=None,
-                align_draft=None, draft_tolerance=None, align_edits=None, align_insertions=None, bigram_scores=None):
+                align_draft=None, draft_tolerance=None, align_edits=None, align_insertions=None, min_duration=None,
+                bigram_scores=None):
     """align: "greedy" | "viterbi" | None (config postprocess.align, else greedy): how a `{audio}.txt` transcript is aligned
     (Labeler.label_files).  align_scores (viterbi only; None: config postprocess.align_scores): also write `{stem}.scores.tsv`
     beside the .lab when the file was Viterbi-aligned (format_scores_tsv).  decode: "argmax" | "viterbi" | None (config
@@ -1217,10 +1252,12 @@ def infer_audio(audio_path, config_path="config.yaml", checkpoint_path="best_mod
     beside the .lab when the file was Viterbi-aligned: per token the best and second-best substitute, the deletion, their log
     likelihood ratios and a flag (align.write_edits_tsv).  align_insertions (align viterbi only; None: config
     postprocess.align_insertions): also write `{stem}.insertions.tsv` beside the .lab when the file was Viterbi-aligned: per place of
-    the transcript the best and second-best phoneme to insert, their log likelihood ratios and a flag (align.write_insertions_tsv)."""
+    the transcript the best and second-best phoneme to insert, their log likelihood ratios and a flag (align.write_insertions_tsv).
+    min_duration (align viterbi only; None: config postprocess.min_duration): seconds, or {token name: seconds, "default": seconds}:
+    the least time a transcript token occupies in the search (Labeler.label_files)."""
     given = dict(align=align, align_scores=align_scores, decode=decode, switch_penalty=switch_penalty, decode_scores=decode_scores,
                  phoneme_bigram=phoneme_bigram, bigram_weight=bigram_weight, bigram_scores=bigram_scores, align_draft=align_draft,
-                 draft_tolerance=draft_tolerance, align_edits=align_edits, align_insertions=align_insertions)
+                 draft_tolerance=draft_tolerance, align_edits=align_edits, align_insertions=align_insertions, min_duration=min_duration)
     _refuse_before_load(config_path, **given)
     lab = _labeler(config_path, checkpoint_path, device)
     opts = lab.options(**given)
@@ -1245,10 +1282,10 @@ def infer_folder(folder_path: str, config_path: str = "config.yaml", checkpoint_
                  output_dir: str = "outputs", device: str = "cuda", lang_id: int = None, sample=False, top_k=0, top_p=0.0,
                  temperature=1.0, confidence_threshold=0.0, align=None, align_scores=None, decode=None, switch_penalty=None,
                  decode_scores=None, phoneme_bigram=None, bigram_weight=None, align_draft=None, draft_tolerance=None,
-                 align_edits=None, align_insertions=None, bigram_scores=None):
+                 align_edits=None, align_insertions=None, min_duration=None, bigram_scores=None):
     given = dict(align=align, align_scores=align_scores, decode=decode, switch_penalty=switch_penalty, decode_scores=decode_scores,
                  phoneme_bigram=phoneme_bigram, bigram_weight=bigram_weight, bigram_scores=bigram_scores, align_draft=align_draft,
-                 draft_tolerance=draft_tolerance, align_edits=align_edits, align_insertions=align_insertions)
+                 draft_tolerance=draft_tolerance, align_edits=align_edits, align_insertions=align_insertions, min_duration=min_duration)
     _refuse_before_load(config_path, **given)
     wav_files = sorted(f for f in os.listdir(folder_path) if f.lower().endswith(".wav"))
     os.makedirs(output_dir, exist_ok=True)
@@ -1363,9 +1400,13 @@ def main(argv=None):
                        "the best phonemes to insert there, as log likelihood ratios against the transcript as written, summed over "
                        "all boundaries on the GPU) and, for a folder, transcript_insertions.tsv with every place a token seems to be "
                        "missing. Default: config postprocess.align_insertions, else off.")
+    @click.option("--min-duration", "min_duration", type=str, multiple=True,
+                  help="With --align viterbi: the least time a transcript token occupies, SECONDS for every token or NAME=SECONDS for "
+                       "the tokens of that name (repeatable; a plain SECONDS beside named ones is their default). At most 0.16 s "
+                       "(8 frames). Default: config postprocess.min_duration, else none.")
     def cli(path, checkpoint, config, output, lang_id, sample, top_k, top_p, temperature, device, confidence_threshold, align,
             align_scores, decode, switch_penalty, decode_scores, phoneme_bigram, bigram_weight, bigram_scores, align_draft,
-            draft_tolerance, align_edits, align_insertions):
+            draft_tolerance, align_edits, align_insertions, min_duration):
         if switch_penalty is not None and not switch_penalty >= 0.0:
             raise click.UsageError("--switch-penalty must be >= 0 (nats)")
         if sample:
@@ -1398,7 +1439,8 @@ def main(argv=None):
             opts = resolve(cfg["postprocess"], align=align, align_scores=align_scores, decode=decode, switch_penalty=switch_penalty,
                            decode_scores=decode_scores, phoneme_bigram=phoneme_bigram, bigram_weight=bigram_weight,
                            bigram_scores=bigram_scores, align_draft=align_draft, draft_tolerance=draft_tolerance,
-                           align_edits=align_edits, align_insertions=align_insertions)
+                           align_edits=align_edits, align_insertions=align_insertions,
+                           min_duration=parse_min_duration(min_duration))
         except ValueError as err:
             raise click.UsageError(str(err))
         output_path = inf_path if output == "." else output
@@ -1417,7 +1459,7 @@ def main(argv=None):
                   bigram_weight=opts.bigram_weight if opts.decode == "viterbi" else None,
                   # the draft travels the same way: an empty path for "none", a tolerance only beside a draft
                   align_draft=opts.align_draft or "", draft_tolerance=opts.draft_tolerance if opts.align_draft else None,
-                  align_edits=opts.align_edits, align_insertions=opts.align_insertions)
+                  align_edits=opts.align_edits, align_insertions=opts.align_insertions, min_duration=opts.min_duration)
         if inf_path.is_dir():
             infer_folder(folder_path=str(inf_path), output_dir=str(output_path), **kw)
         else:

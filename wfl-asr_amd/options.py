@@ -17,10 +17,18 @@ infer_folder (before any model is loaded) and the CLI all call `resolve` and car
   draft_tolerance 0.1      11. when given, a number >= 0 (seconds; no bool), and then needs an align_draft
   align_edits     off      12. needs align viterbi (the edits are scored on the lattice of that search)
   align_insertions off     13. needs align viterbi (the insertions are scored on the lattice of that search)
+  min_duration    none     14. SECONDS or {NAME: SECONDS, default: SECONDS}: every value a number between 0 and
+                               MAX_MIN_FRAMES * FRAME_DURATION (no bool)
+                           15. needs align viterbi (the durations constrain that search)
+                           16. align_scores, align_edits and align_insertions beside a min_duration are refused
+                               (MIN_DURATION_SCORES_ERROR): their passes score the lattice without minimum durations, and a score must
+                               speak of the lattice its search ran on
 """
 from __future__ import annotations
 
 from typing import NamedTuple, Optional
+
+from .postprocess import FRAME_DURATION
 
 ALIGN_MODES = ("greedy", "viterbi")
 DECODE_MODES = ("argmax", "viterbi")
@@ -30,6 +38,57 @@ DEFAULT_DRAFT_TOLERANCE = 0.1     # seconds; a default to start from, not a meas
 BIGRAM_SCORES_ERROR = ("decode_scores cannot be combined with a phoneme bigram: the forward-backward pass scores the flat switch "
                        "penalty, not the bigram the search ran on; ask for bigram_scores (postprocess.bigram_scores, --bigram-scores) "
                        "instead, which scores the bigram's own grammar")
+
+
+MAX_MIN_FRAMES = 8                # the search's cap on a token's minimum duration, frames (csrc/lattice.h, align.MAX_MIN_FRAMES)
+MIN_DURATION_SCORES_ERROR = ("align_scores, align_edits and align_insertions cannot be combined with a min_duration: their passes score "
+                             "the lattice without minimum durations, not the one the search ran on; drop postprocess.min_duration "
+                             "(--min-duration) for the scoring run")
+
+
+def _min_duration(given):
+    """postprocess.min_duration -> its normalised, hashable form: None (absent, or an empty mapping), a float (one value for every
+    token), or a tuple of (name, seconds) pairs sorted by name ("default" among them) -- dict() of it is the mapping again.  A value
+    that breaks rule 14 is a ValueError.  An iterable of pairs (the normalised form itself) is taken as a mapping."""
+    limit = MAX_MIN_FRAMES * FRAME_DURATION
+
+    def seconds(x):
+        v = _number_ge0(x)
+        if v is None or v > limit + 1e-9:
+            raise ValueError(f"min_duration must be a number of seconds between 0 and {limit:g} ({MAX_MIN_FRAMES} frames), or a mapping "
+                             f"of token names (and 'default') to such numbers, got {x!r}")
+        return v
+    if given is None:
+        return None
+    if isinstance(given, (tuple, list)):
+        try:
+            given = dict(given)
+        except (TypeError, ValueError):
+            seconds(given)
+    if isinstance(given, dict):
+        return tuple(sorted((str(k), seconds(v)) for k, v in given.items())) or None
+    return seconds(given)
+
+
+def parse_min_duration(values):
+    """The CLI's repeatable --min-duration values, each SECONDS or NAME=SECONDS -> what `resolve` takes: None (no value), a float (one
+    plain SECONDS) or a mapping, a plain SECONDS among named ones being its "default".  A SECONDS that is no number stays a string
+    for rule 14 to report."""
+    def num(x):
+        try:
+            return float(x)
+        except ValueError:
+            return x
+    values = list(values or ())
+    if not values:
+        return None
+    if len(values) == 1 and "=" not in values[0]:
+        return num(values[0])
+    out = {}
+    for v in values:
+        name, eq, sec = v.rpartition("=")
+        out[name if eq else "default"] = num(sec)
+    return out
 
 
 class _SearchOptions(NamedTuple):
@@ -59,38 +118,42 @@ class PostOptions(_SearchOptions):
         align_draft      None   folder of draft .lab files (X.wav -> DIR/X.lab); an empty path is None
         draft_tolerance  0.1    seconds either side of a draft start (also stands for "not given")
         align_edits      False  score single substitutions and deletions of every aligned transcript
-        align_insertions False  score single insertions at every place of every aligned transcript"""
+        align_insertions False  score single insertions at every place of every aligned transcript
+        min_duration     None   the least time a transcript token occupies: seconds, or ((name, seconds), ...) sorted by name"""
     align_draft: Optional[str] = None
     draft_tolerance: float = DEFAULT_DRAFT_TOLERANCE
     align_edits: bool = False
     align_insertions: bool = False
+    min_duration: object = None
 
     def __new__(cls, *args, align_draft=None, draft_tolerance=DEFAULT_DRAFT_TOLERANCE, align_edits=False, align_insertions=False,
-                **kw):
+                min_duration=None, **kw):
         self = super().__new__(cls, *args, **kw)
         object.__setattr__(self, "align_draft", align_draft)
         object.__setattr__(self, "draft_tolerance", draft_tolerance)
         object.__setattr__(self, "align_edits", align_edits)
         object.__setattr__(self, "align_insertions", align_insertions)
+        object.__setattr__(self, "min_duration", min_duration)
         return self
 
     def __setattr__(self, name, value):
         raise AttributeError(f"PostOptions is read-only: cannot set {name!r}")
 
-    _KEYWORD = ("align_draft", "draft_tolerance", "align_edits", "align_insertions")
-    _KEYWORD_DEFAULTS = (None, DEFAULT_DRAFT_TOLERANCE, False, False)
+    _KEYWORD = ("align_draft", "draft_tolerance", "align_edits", "align_insertions", "min_duration")
+    _KEYWORD_DEFAULTS = (None, DEFAULT_DRAFT_TOLERANCE, False, False, None)
 
     def _draft(self):
         return self.align_draft, self.draft_tolerance
 
     def _later(self):
-        return self.align_draft, self.draft_tolerance, self.align_edits, self.align_insertions
+        return self.align_draft, self.draft_tolerance, self.align_edits, self.align_insertions, self.min_duration
 
     # the NamedTuple helpers carry the keyword fields as well (the inherited ones know the tuple alone)
     @classmethod
-    def _make(cls, iterable, align_draft=None, draft_tolerance=DEFAULT_DRAFT_TOLERANCE, align_edits=False, align_insertions=False):
+    def _make(cls, iterable, align_draft=None, draft_tolerance=DEFAULT_DRAFT_TOLERANCE, align_edits=False, align_insertions=False,
+              min_duration=None):
         return cls(*iterable, align_draft=align_draft, draft_tolerance=draft_tolerance, align_edits=align_edits,
-                   align_insertions=align_insertions)
+                   align_insertions=align_insertions, min_duration=min_duration)
 
     def _replace(self, **kw):
         later = {k: kw.pop(k, getattr(self, k)) for k in self._KEYWORD}
@@ -126,7 +189,7 @@ def _number_ge0(x):
 
 def resolve(post, *, align=None, align_scores=None, decode=None, switch_penalty=None, decode_scores=None, phoneme_bigram=None,
             bigram_weight=None, bigram_scores=None, align_draft=None, draft_tolerance=None, align_edits=None,
-            align_insertions=None) -> PostOptions:
+            align_insertions=None, min_duration=None) -> PostOptions:
     """post: the config's `postprocess` mapping (None: {}).  Per option the argument wins; None leaves it to `post[<option>]`, and a
     key that is absent (or None) to the default.  -> PostOptions, or ValueError for the first broken rule of the module's table."""
     post = post or {}
@@ -189,6 +252,12 @@ def resolve(post, *, align=None, align_scores=None, decode=None, switch_penalty=
     if align_insertions and align != "viterbi":
         raise ValueError("align_insertions needs align='viterbi' (postprocess.align: viterbi): the greedy match has no lattice to "
                          "score an insertion on")
+    min_duration = _min_duration(pick("min_duration", min_duration))
+    if min_duration is not None and align != "viterbi":
+        raise ValueError("min_duration needs align='viterbi' (postprocess.align: viterbi): the durations constrain the Viterbi search, "
+                         "the greedy match has none")
+    if min_duration is not None and (align_scores or align_edits or align_insertions):
+        raise ValueError(MIN_DURATION_SCORES_ERROR)
     return PostOptions(align, align_scores, decode, switch_penalty, decode_scores, phoneme_bigram, bigram_weight, bigram_scores,
                        align_draft=align_draft, draft_tolerance=draft_tolerance, align_edits=align_edits,
-                       align_insertions=align_insertions)
+                       align_insertions=align_insertions, min_duration=min_duration)
