@@ -406,6 +406,33 @@ int32_t wfl_align_posterior_windowed(const float* logits, int64_t ldl, int32_t C
                                      const int32_t* tok, void* workspace, int64_t workspace_bytes, float* logz, float* tok_post,
                                      float* start_mean, float* start_sd, int32_t* status, void* stream);
 
+/* ---- wfl_align_posterior over the minimum-duration lattice of wfl_align_min_duration (`postprocess.duration_scores`;
+ * wfl-asr_amd/align.py duration_posteriors).  wfl_align_posterior_windowed's arguments (tok_win may be null: no windows) plus tok_min
+ * (device, [total tokens] int32, 1 <= D_k <= 8), the table the search was given; tok is wfl_align_min_duration's output.  The sums run
+ * over that search's expanded states, B_k, H_k^2 .. H_k^{D_k-1} (emitting EI) and I_k per token:
+ *     alpha: G_k and B_k are entered from G_k, I_{k-1}, and from B_{k-1} only where D_{k-1} == 1; H_k^2 from B_k, H_k^j from H_k^{j-1};
+ *            I_k from I_k and from X_k (H_k^{D_k-1} for D_k >= 3, B_k for D_k <= 2).  End states G_N | I_{N-1}, B_{N-1} only for D == 1.
+ *     beta:  beta_{t-1}(I_k) = lse(beta_t(I_k) + EI_t(k), beta_t(G_{k+1}) + EG_t, beta_t(B_{k+1}) + EB_t(k+1)); beta_{t-1}(B_k) is that
+ *            value where D_k == 1, beta_t(I_k) + EI_t(k) where D_k == 2, beta_t(H_k^2) + EI_t(k) above; beta_{t-1}(H_k^j) =
+ *            beta_t(H_k^{j+1}) + EI_t(k), the last chain state going to I_k: a delay line per token, the mirror of alpha's chain.
+ * Outputs as wfl_align_posterior's: logz[b] the log weight of every path that meets the durations (and the windows); tok_post[k] the
+ * mean over the frames of Viterbi's run of the posterior of being in ANY state of token k (B_k, its chain, I_k); start_mean / start_sd
+ * from gamma(B_k).  A path in B_k at frame t is in H_k^j at t + j - 1, so gamma_t(H_k^j) = gamma_{t-j+1}(B_k) and the chain's occupancy
+ * is taken from gamma(B_k): the recomputed block holds G, B, I alone, only the checkpoints hold the chain.  With every D_k == 1 the
+ * outputs are wfl_align_posterior's (wfl_align_posterior_windowed's).
+ * status[b]: 2 over the cap; 1 T < N, or no path meets durations and windows (logZ = -inf); 4 a bad class or a D_k outside 1 .. 8;
+ * 8 tok is not a path of this lattice: a token missing, a token opening outside its window, or a run shorter than its D_k.  1 comes
+ * before 8: a clip without any path is status 1 whatever tok holds (wfl_align_min_duration writes tok = -1 for it).  A clip with
+ * status != 0 gets zeros.  A null tok_min with any token present is a host-side -1.
+ * Workspace: wfl_align_posterior's with checkpoints of 9 instead of 3 floats per slot: per clip, in 4-byte words, round_up_64 of
+ *     round_up_64(T) + round_up_64(2 nblk) + (9 nblk + 3 * 128) * slots(N),   nblk = ceil(T / 128). */
+int64_t wfl_align_min_duration_posterior_workspace_bytes(const int32_t* n_frames_host, const int32_t* n_tok_host, int32_t n_clips);
+int32_t wfl_align_min_duration_posterior(const float* logits, int64_t ldl, int32_t C, int32_t o_id, const int64_t* frame_off_host,
+                                         const int32_t* n_frames_host, const int32_t* tok_off_host, const int32_t* n_tok_host,
+                                         const int32_t* tok_cls, const int32_t* tok_win, const int32_t* tok_min, const int32_t* gap_cls,
+                                         int32_t n_clips, const int32_t* tok, void* workspace, int64_t workspace_bytes, float* logz,
+                                         float* tok_post, float* start_mean, float* start_sd, int32_t* status, void* stream);
+
 /* ---- Single-edit scores of an aligned transcript (`postprocess.align_edits`; wfl-asr_amd/align.py, csrc/align_edits.hip).  No
  * counterpart in the reference.  The arguments are wfl_align_posterior_windowed's without tok; tok_win may be null: the unwindowed
  * lattice.  sub_cls (device, [n_sub][2] int32 = (B class, I class)) is a table of P = n_sub substitutes, 0 <= P <= 512.  With logZ(.)

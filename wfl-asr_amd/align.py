@@ -10,9 +10,11 @@ token gets one contiguous, time-ordered run of frames, none is dropped.
                         inside its (lo, hi) frame window (`wfl_align_windowed`, `postprocess.align_draft`); with `min_frames`,
                         every token occupies at least that many frames (`wfl_align_min_duration`, `postprocess.min_duration`)
   min_frames_for        `postprocess.min_duration` (seconds, or seconds per token name) -> frames per transcript token
-  alignment_posteriors  forward-backward over the same lattice (csrc/align_posterior.hip, `wfl_align_posterior`; of a batch packed with
+  alignment_posteriors  forward-backward over the same lattice (csrc/align_posterior.h, `wfl_align_posterior`; of a batch packed with
                         windows, `wfl_align_posterior_windowed`): logZ, and per token
                         the posterior of the run Viterbi chose and the spread of its start (`postprocess.align_scores`)
+  duration_posteriors   the same over the minimum-duration lattice of a batch packed with `min_frames`
+                        (`wfl_align_min_duration_posterior`; `postprocess.duration_scores`)
   edit_scores           per token the log likelihood ratio of every single substitution from a table and of the token's deletion
                         (csrc/align_edits.hip, `wfl_align_edits`; `postprocess.align_edits`), on the same lattice, windows included
   substitute_table      the (B, I) pairs of a label set, the table edit_scores takes
@@ -263,6 +265,62 @@ def alignment_posteriors(logits, n_frames, token_classes, gap_classes, o_id, tok
         else:
             _lib.check(lib.wfl_align_posterior_windowed(*head, _ptr(d_win), *tail), "wfl_align_posterior_windowed")
         for t in (d_tc, d_gc, ws) + ((d_win,) if d_win is not None else ()):
+            t.record_stream(st)
+    return logz[:nb], per_tok[0, :ntok], per_tok[1, :ntok], per_tok[2, :ntok], status[:nb]
+
+
+def _with_min_frames(packed, what):
+    """The sums of duration_posteriors run over the lattice WITH minimum durations: a batch packed without them is refused, a score
+    must speak of the lattice its search ran on."""
+    if packed.d_min is None:
+        raise ValueError(f"{what} scores the lattice with minimum durations: this batch was packed without min_frames")
+    return packed
+
+
+def duration_posterior_workspace_bytes(n_frames, n_tokens) -> int:
+    lib = _lib.load()
+    T = np.ascontiguousarray(n_frames, np.int32)
+    N = np.ascontiguousarray(n_tokens, np.int32)
+    n = int(lib.wfl_align_min_duration_posterior_workspace_bytes(_hp(T), _hp(N), T.size))
+    if n < 0:
+        raise _lib.WflError("wfl_align_min_duration_posterior_workspace_bytes: negative frame or token count")
+    return n
+
+
+def duration_posteriors(logits, n_frames, token_classes, gap_classes, o_id, tok, frame_offsets=None, stream=None, packed=None,
+                        windows=None, min_frames=None):
+    """alignment_posteriors over the minimum-duration lattice of viterbi_align(..., min_frames=...), for the same ragged batch of
+    clips (same arguments), given its `tok` (wfl_align_min_duration_posterior).
+
+    windows, min_frames  as viterbi_align's.  With `packed` -- the PackedClips the search ran on -- the windows and durations are
+                         the ones packed there.  A batch without durations (min_frames None, or packed without them) is refused:
+                         alignment_posteriors scores that lattice
+    -> alignment_posteriors' five tensors.  logz: log of the summed weight of every path that gives every token its minimum
+    duration (and opens it inside its window); tok_post: the posterior of being in any state of the token -- B_k, its chain, I_k --
+    averaged over the run Viterbi gave it; start_mean / start_sd from B_k as there.  STATUS_NOT_A_PATH also for a `tok` with a run
+    shorter than its minimum, STATUS_INFEASIBLE also when no path meets the durations, STATUS_BAD_CLASS also for a duration outside
+    1 .. MAX_MIN_FRAMES."""
+    lib = _lib.load()
+    nb, T, N, F0, K0, d_tc, d_gc, d_win, d_min = _with_min_frames(packed if packed is not None else pack_clips(
+        logits, n_frames, token_classes, gap_classes, frame_offsets, windows, min_frames), "duration_posteriors")
+    dev = logits.device
+    if not tok.is_cuda or tok.device != dev or tok.dtype != torch.int32 or tok.dim() != 1 or tok.stride(0) != 1 \
+            or tok.shape[0] != logits.shape[0]:
+        raise ValueError("tok must be viterbi_align's [rows] int32 CUDA tensor for these logits")
+    ntok = int(N.sum())
+    ws_n = duration_posterior_workspace_bytes(T, N)
+    ws = torch.empty(max(ws_n, 1), dtype=torch.uint8, device=dev)
+    logz = torch.empty(max(nb, 1), dtype=torch.float32, device=dev)
+    per_tok = torch.empty((3, max(ntok, 1)), dtype=torch.float32, device=dev)
+    status = torch.empty(max(nb, 1), dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        st = stream if stream is not None else torch.cuda.current_stream(dev)
+        _lib.check(lib.wfl_align_min_duration_posterior(
+            _ptr(logits), logits.stride(0), logits.shape[1], int(o_id), _hp(F0), _hp(T), _hp(K0), _hp(N), _ptr(d_tc),
+            _ptr(d_win) if d_win is not None else None, _ptr(d_min), _ptr(d_gc), nb, _ptr(tok), _ptr(ws), ws_n, _ptr(logz),
+            _ptr(per_tok[0]), _ptr(per_tok[1]), _ptr(per_tok[2]), _ptr(status), C.c_void_p(st.cuda_stream)),
+            "wfl_align_min_duration_posterior")
+        for t in (d_tc, d_gc, ws, d_min) + ((d_win,) if d_win is not None else ()):
             t.record_stream(st)
     return logz[:nb], per_tok[0, :ntok], per_tok[1, :ntok], per_tok[2, :ntok], status[:nb]
 

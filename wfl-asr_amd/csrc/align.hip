@@ -23,7 +23,7 @@
 //   (class id, token) and adds up its frames' log-sum-exp for the score.
 //
 // The lattice itself -- caps, configurations, the shared LDS layout, setup and status codes, the logits stage ring, emissions, the
-// renormalisation halves, and the host side of a ragged batch -- is csrc/lattice.h, shared with csrc/align_posterior.hip.  Here: the
+// renormalisation halves, and the host side of a ragged batch -- is csrc/lattice.h, shared with csrc/align_posterior.h.  Here: the
 // max-product recursion, the backpointers and the backtrace.
 //
 // wfl_align_windowed is the same kernel instantiated with WIN: every token's EB passes through lattice.h's win_mask (the token may open

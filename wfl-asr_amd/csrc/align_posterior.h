@@ -1,0 +1,699 @@
+// Forward-backward over the forced-alignment lattice of wfl_align: per-token posteriors of a Viterbi path (wfl_align_posterior,
+// include/wfl_asr.h).  The sum-product twin of csrc/align.hip; the reference has no counterpart (it reports no confidence for its
+// string match).
+//
+// Lattice, emissions, start / end states and caps are wfl_align's, and so is their code: csrc/lattice.h holds the caps, the
+// configurations, the shared LDS layout, lattice setup with its status codes, the logits stage ring, the emission gathers, the
+// renormalisation halves and the host side of a ragged batch.  Here: the sum-product sweeps, the status-8 check of `tok`, the
+// checkpoint workspace and the per-token outputs.  States G_k = 3k, B_k = 3k + 1, I_k = 3k + 2:
+//   alpha_t(G_k) = EG_t + lse(alpha_{t-1}(G_k), alpha_{t-1}(I_{k-1}), alpha_{t-1}(B_{k-1}))      alpha_t(B_k): the same sum + EB_t(k)
+//   alpha_t(I_k) = EI_t(k) + lse(alpha_{t-1}(I_k), alpha_{t-1}(B_k))
+//   beta_{t-1}(G_k) = lse(beta_t(G_k) + EG_t, beta_t(B_k) + EB_t(k))
+//   beta_{t-1}(B_k) = beta_{t-1}(I_k) = lse(beta_t(I_k) + EI_t(k), beta_t(G_{k+1}) + EG_t, beta_t(B_{k+1}) + EB_t(k+1))
+//   logZ = lse(alpha_{T-1}(G_N), alpha_{T-1}(I_{N-1}), alpha_{T-1}(B_{N-1})),   gamma_t(s) = exp(alpha_t(s) + beta_t(s) - logZ).
+// beta of B_k and I_k are equal (same successors), so the backward sweep carries two values per token.
+//
+// One workgroup per clip, configurations and slot ownership from lattice.h: thread i owns the token slots i R .. i R + R - 1 in
+// registers.  Per frame one float2 crosses between neighbouring threads through LDS, one barrier per frame: the forward sweep takes
+// (alpha(B), alpha(I)) of the last slot of thread i - 1, the backward sweep (beta(G), beta(B)) of the first slot of thread i + 1 (the
+// emission of that slot's B state is gathered by thread i itself, from the staged row).  Every per-token output is accumulated by
+// the thread that owns the token; no reduction over the block per frame.  Every 16 frames the block's maximum is subtracted from the
+// states (alpha and beta separately) and added to a double, so the fp32 log-domain values never grow with T.
+//
+// Memory: the alpha lattice is never stored.  Sweep 1 runs forward over the clip and keeps a checkpoint of the registers every
+// POST_W frames; then, block by block from the last one, sweep 2 recomputes the block's POST_W frames of alpha from its checkpoint
+// into a block buffer and sweep 3 walks beta down the block, combining.  Every thread reads back only what it wrote itself.
+// Workspace per clip: lse[T] | checkpoints' offsets | checkpoints | one block (wfl_align_posterior_workspace_bytes).
+//
+// wfl_align_posterior_windowed is the same kernel instantiated with WIN: EB passes through lattice.h's win_mask wherever it is gathered --
+// alpha, beta's own slots, and the next thread's first slot (ebn) -- with the windows of a thread's slots (and of that one slot) in
+// registers; a tok that opens a token outside its window is status 8, logZ = -inf status 1.
+//
+// wfl_align_min_duration_posterior is the kernel instantiated with MIND (with and without WIN): the sums over the lattice of
+// wfl_align_min_duration.  Alpha carries lattice.h's chain beside G, B, I (chain_out / chain_shift, as the search), beta a delay line per
+// slot (chain_in / chain_shift_back): beta(B_k) differs from beta(I_k) there, bX is beta(I_k) and beta(B_k) comes out of the line.  The
+// block buffer stays at G, B, I: gamma_t(H_k^j) = gamma_{t-j+1}(B_k), so the chain's share of a run's occupancy is gamma_t(B_k) times
+// the overlap of [t, t + D_k - 2] with the run; only the checkpoints hold the chain (PCfg::SM).  A D_k outside 1 .. 8 is status 4, a run
+// shorter than its D_k status 8, and a clip without any path status 1 before its tok is judged.
+//
+// The per-frame log-sum-exp of the logits is computed once (double, expf), stored in fp32 and subtracted from the gathered logits;
+// what the fp32 rounding of it loses is summed in double and given back to logZ (it is common to every path).
+//
+// This header holds the kernel and the host path every entry shares.  csrc/align_posterior.hip instantiates wfl_align_posterior and
+// wfl_align_posterior_windowed from it, csrc/align_min_duration_posterior.hip the kernels with the minimum-duration chain (MIND) -- a
+// translation unit of its own because those are compiled without the SLP vectoriser (build.py), which must not reach the others.
+// Everything here is in an unnamed namespace: each of the two files has its own copy, and instantiates only its own kernels.
+#pragma once
+#include "lattice.h"
+#include "wfl_asr.h"
+
+#include <limits.h>
+
+namespace {
+
+using namespace lattice;
+
+constexpr int POST_W = 128;                // frames per recomputed block (a multiple of the renormalisation period)
+static_assert(POST_W % RENORM == 0, "a block ends on a renormalisation");
+
+struct PostLaunch {
+  const float* logits;
+  long ldl;
+  int C;
+  const int* tok_cls;  // [total tokens][4][2]
+  const int* gap_cls;  // [n_clips][8]
+  const int* tok;      // wfl_align's output, same rows as the logits
+  float* ws;           // LatClip::ws_off: the clip's workspace, in floats
+  float* logz;
+  float* tok_post;
+  float* start_mean;
+  float* start_sd;
+  int* status;
+  int n;
+  LatClip clip[CLIPS_PER_LAUNCH];
+  const int* tok_win;  // [total tokens][2] = (lo, hi), the windowed kernels alone (last: the other fields stay where they were)
+  const int* tok_min;  // [total tokens] D_k, the minimum-duration kernels alone
+};
+
+// a clip's workspace in floats: [lse: round64(T)] [checkpoint offsets: round64(2 nblk)] [checkpoints: nblk SC] [block: POST_W S]
+// SC: a checkpoint's floats -- S, and with minimum durations the chain states of every slot as well (PCfg::SM)
+struct PostLayout {
+  long ckacc, ckpt, blk, total;
+  int nblk;
+  __host__ __device__ PostLayout(int T, long SC, long S) {
+    nblk = (T + POST_W - 1) / POST_W;
+    ckacc = round64(T);
+    ckpt = ckacc + round64(2L * nblk);
+    blk = ckpt + (long)nblk * SC;
+    total = blk + (long)POST_W * S;
+  }
+};
+
+template <int NT, int R>
+struct PCfg : LdsBase<NT, R, NT * R * 4 + 2 * 2 * NT * 8> {       // its own between alt and wmax: first[] and the two neighbour exchanges
+  static constexpr long S = (long)NT * R * 3;            // floats of one frame's alpha (and of one checkpoint)
+  static constexpr long SM = (long)NT * R * (3 + CHAIN); // floats of one checkpoint with the minimum-duration chain
+  static constexpr int OFF_FIRST = PCfg::OFF_X;                    // first frame of every token's Viterbi run
+  static constexpr int OFF_XF = OFF_FIRST + NT * R * 4;            // forward neighbour exchange: [2][NT] float2
+  static constexpr int OFF_XB = OFF_XF + 2 * NT * 8;               // backward neighbour exchange
+  static constexpr int OFF_OFFA = PCfg::OFF_OWN;                   // alpha's offset of every frame of the block (double)
+  static constexpr int OFF_LRING = OFF_OFFA + POST_W * 8;          // staged rows' log-sum-exp
+  static constexpr int OFF_TRING = OFF_LRING + 2 * FMAX * 4;       // staged rows' Viterbi token
+  static constexpr int OFF_MISC = OFF_TRING + 2 * FMAX * 4;
+  static constexpr int LDS = OFF_MISC + 64;
+};
+
+// log(exp a + exp b [+ exp c]); -inf in, -inf out (v_exp_f32 / v_log_f32)
+__device__ __forceinline__ float lae2(float a, float b) {
+  const float m = fmaxf(a, b);
+  const float ms = m == -INFINITY ? 0.f : m;
+  return ms + __logf(__expf(a - ms) + __expf(b - ms));
+}
+
+__device__ __forceinline__ float lae3(float a, float b, float c) {
+  const float m = fmaxf(a, fmaxf(b, c));
+  const float ms = m == -INFINITY ? 0.f : m;
+  return ms + __logf(__expf(a - ms) + __expf(b - ms) + __expf(c - ms));
+}
+
+// WIN: the start windows of wfl_align_posterior_windowed (lattice.h win_mask); false is wfl_align_posterior's kernel, instruction for
+// instruction
+// MIND: the minimum durations of wfl_align_min_duration_posterior (lattice.h chain_*); false leaves the two kernels above as they were
+template <int NT, int R, bool WIN, bool MIND>
+__global__ __launch_bounds__(NT) void post_kernel(PostLaunch a) {
+  using K = PCfg<NT, R>;
+  extern __shared__ __attribute__((aligned(16))) char lds[];
+  float* ring = (float*)lds;
+  int4* alt = (int4*)(lds + K::OFF_ALT);
+  int* first = (int*)(lds + K::OFF_FIRST);
+  float2* xf = (float2*)(lds + K::OFF_XF);
+  float2* xb = (float2*)(lds + K::OFF_XB);
+  float* wmax = (float*)(lds + K::OFF_WMAX);
+  double* red = (double*)(lds + K::OFF_RED);
+  double* offa = (double*)(lds + K::OFF_OFFA);
+  float* lring = (float*)(lds + K::OFF_LRING);
+  int* tring = (int*)(lds + K::OFF_TRING);
+  int* misc = (int*)(lds + K::OFF_MISC);
+  float* fin = (float*)(misc + 4);
+
+  const LatClip cl = a.clip[blockIdx.x];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int T = cl.T, N = cl.N, C = a.C;
+  const float* Z = a.logits + cl.frame_off * a.ldl;
+  const int* tokp = a.tok + cl.frame_off;
+  const float NEG = -INFINITY;
+
+  int g[NGAP];
+  int st = lattice_setup<NT, R>(cl, C, a.tok_cls, a.gap_cls, alt, misc, g);
+  int2 wn[WIN ? R : 1];                        // this thread's slots' start windows, in registers, and the next thread's first slot's
+  int2 wnn = make_int2(0, WIN_OPEN_HI);
+  if constexpr (WIN) {
+    if (st == 0) {
+      load_windows<R>(a.tok_win, cl.tok_off, N, wn);
+      wnn = load_window(a.tok_win, cl.tok_off, (tid + 1) * R, N);
+    }
+  }
+  int dm[MIND ? R : 1];                        // this thread's slots' minimum durations, in registers
+  int fst[MIND ? R : 1], lst[MIND ? R : 1];    // first and last frame of their Viterbi runs
+  // with durations a tok that is no path is reported only after sweep 1: a clip that has no path at all is status 1 first (the search
+  // writes tok = -1 for such a clip, and its status is the one to pass on)
+  bool notpath = false;
+  if constexpr (MIND) {
+    if (st == 0) {                             // (the same in every thread).  A D_k outside 1 .. MAX_MIN_FRAMES: status 4
+      if (tid == 0) misc[3] = 0;
+      __syncthreads();
+      bool bad = false;
+#pragma unroll
+      for (int r = 0; r < R; ++r) {
+        dm[r] = load_min(a.tok_min, cl.tok_off, tid * R + r, N);
+        if (dm[r] < 1 || dm[r] > MAX_MIN_FRAMES) bad = true;
+      }
+      if (bad) misc[3] = 1;
+      __syncthreads();
+      if (misc[3]) st = 4;
+    }
+  }
+  if (st == 0 && T > 0) {
+    // the first frame of every token's Viterbi run; a tok that is not a path of this lattice (a token missing, a value out of range)
+#pragma unroll
+    for (int r = 0; r < R; ++r) first[tid * R + r] = INT_MAX;
+    __syncthreads();                           // (and every thread has read setup's flag before this phase may raise it again)
+    bool bad = false;
+    for (int t = tid; t < T; t += NT) {
+      const int k = tokp[t];
+      if (k < -1 || k >= N) bad = true;
+      else if (k >= 0 && (t == 0 || tokp[t - 1] != k)) atomicMin(&first[k], t);
+    }
+    if (bad) misc[0] = 1;
+    __syncthreads();
+#pragma unroll
+    for (int r = 0; r < R; ++r)
+      if (tid * R + r < N) {
+        const int f = first[tid * R + r];
+        if (f == INT_MAX) misc[0] = 1;
+        if constexpr (WIN) {
+          if (f < wn[r].x || f > wn[r].y) misc[0] = 1;   // a token opens outside its window: not a path of this lattice either
+        }
+      }
+    __syncthreads();
+    if (misc[0]) {
+      if constexpr (MIND) notpath = true;
+      else st = 8;
+    }
+    if constexpr (MIND) {
+      // the last frame of every run, through the same LDS words (the chain's share of a run's occupancy needs both ends before the
+      // backward sweep reaches the run); a run shorter than its D_k is not a path of this lattice
+      if (st == 0 && !notpath) {               // (the same in every thread; misc[0] is still 0)
+#pragma unroll
+        for (int r = 0; r < R; ++r) fst[r] = tid * R + r < N ? first[tid * R + r] : 0;
+        __syncthreads();
+#pragma unroll
+        for (int r = 0; r < R; ++r) first[tid * R + r] = -1;
+        __syncthreads();
+        for (int t = tid; t < T; t += NT) {
+          const int k = tokp[t];
+          if (k >= 0 && (t == T - 1 || tokp[t + 1] != k)) atomicMax(&first[k], t);
+        }
+        __syncthreads();
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+          lst[r] = tid * R + r < N ? first[tid * R + r] : 0;
+          if (tid * R + r < N && lst[r] - fst[r] + 1 < dm[r]) misc[0] = 1;
+        }
+        __syncthreads();
+        if (misc[0]) notpath = true;
+      }
+    }
+  }
+  if (st != 0 || T == 0) {
+    for (int k = tid; k < N; k += NT) {
+      a.tok_post[cl.tok_off + k] = 0.f;
+      a.start_mean[cl.tok_off + k] = 0.f;
+      a.start_sd[cl.tok_off + k] = 0.f;
+    }
+    if (tid == 0) { a.logz[cl.clip] = 0.f; a.status[cl.clip] = st; }
+    return;
+  }
+
+  const PostLayout lay(T, MIND ? K::SM : K::S, K::S);
+  constexpr long SC = MIND ? K::SM : K::S;     // floats of a checkpoint
+  float* ws = a.ws + cl.ws_off;
+  float* lse = ws;
+  double* ckacc = (double*)(ws + lay.ckacc);
+  float* ckpt = ws + lay.ckpt;
+  float* blk = ws + lay.blk;
+
+  // ---- the per-frame log-sum-exp, in fp32 for the sweeps; what its rounding loses, in double for logZ
+  double lres = 0.0;
+  // (a thread per row; a wave per row with coalesced loads and wave reductions was measured 4 % slower for the whole kernel)
+  for (int t = tid; t < T; t += NT) {
+    const float* z = Z + (long)t * a.ldl;
+    float m = z[0];
+    for (int q = 1; q < C; ++q) m = fmaxf(m, z[q]);
+    double se = 0.0;
+    for (int q = 0; q < C; ++q) se += (double)expf(z[q] - m);
+    const double ld = (double)m + log(se);
+    const float lf = (float)ld;
+    lse[t] = lf;
+    lres += ld - (double)lf;
+  }
+  lres = wave_sum(lres);
+  if (lane == 0) red[wave] = lres;
+  __syncthreads();                             // (and the block sees lse[])
+  lres = 0.0;
+#pragma unroll
+  for (int w = 0; w < K::NW; ++w) lres += red[w];
+
+  // ---- staging of the logits rows, with their log-sum-exp and Viterbi token
+  LogitStages<NT, K::PR> stage(Z, a.ldl, T, C, ring);
+  const int F = stage.F;
+  float pre_l = 0.f;
+  int pre_t = -1;
+  auto load_stage = [&](int c) {               // (the backward sweep runs one stage ahead as well, down to c = -1)
+    stage.load(c, c >= 0);
+    const bool in = tid < F && c >= 0 && c * F + tid < T;
+    pre_l = in ? lse[c * F + tid] : 0.f;
+    pre_t = in ? tokp[c * F + tid] : -1;
+  };
+  auto store_stage = [&](int c) {
+    stage.store(c);
+    if (tid < F) {
+      lring[(c & 1) * FMAX + tid] = pre_l;
+      tring[(c & 1) * FMAX + tid] = pre_t;
+    }
+  };
+
+  int4 av[R];                                   // this thread's slots' alternatives
+#pragma unroll
+  for (int r = 0; r < R; ++r) av[r] = alt[tid * R + r];
+  const int4 avn = tid + 1 < NT ? alt[(tid + 1) * R] : make_int4(-1, -1, -1, -1);   // the next thread's first slot
+
+  // ---- the forward sweep over frames t0 .. t1 - 1, from the clip's start (t0 = 0) or from checkpoint t0 / POST_W
+  float G[R], B[R], I[R];
+  float H[MIND ? R : 1][CHAIN];                // the chain states H^2 .. H^{MAX_MIN_FRAMES - 1} of every slot (alpha)
+  double acc = 0.0;                            // what alpha's renormalisations subtracted
+  auto forward = [&](int t0, int t1, bool keep) {
+    if (t0 == 0) {
+#pragma unroll
+      for (int r = 0; r < R; ++r) G[r] = B[r] = I[r] = NEG;
+      if constexpr (MIND) {
+#pragma unroll
+        for (int r = 0; r < R; ++r)
+#pragma unroll
+          for (int j = 0; j < CHAIN; ++j) H[r][j] = NEG;
+      }
+      if (tid == 0) G[0] = 0.f;                // a virtual frame -1 in G_0: frame 0 starts in G_0 or B_0
+      acc = 0.0;
+    } else {
+      const float* ck = ckpt + (long)(t0 / POST_W) * SC;
+#pragma unroll
+      for (int r = 0; r < R; ++r) {
+        G[r] = ck[(r * 3 + 0) * NT + tid];
+        B[r] = ck[(r * 3 + 1) * NT + tid];
+        I[r] = ck[(r * 3 + 2) * NT + tid];
+      }
+      if constexpr (MIND) {
+#pragma unroll
+        for (int r = 0; r < R; ++r)
+#pragma unroll
+          for (int j = 0; j < CHAIN; ++j) H[r][j] = ck[(R * 3 + r * CHAIN + j) * NT + tid];
+      }
+      acc = ckacc[t0 / POST_W];
+    }
+    // (with durations the left token is left from its I alone where its D > 1: B is masked by its owner, as in csrc/align.hip)
+    if constexpr (MIND) xf[((t0 + 1) & 1) * NT + tid] = make_float2(dm[R - 1] > 1 ? NEG : B[R - 1], I[R - 1]);
+    else xf[((t0 + 1) & 1) * NT + tid] = make_float2(B[R - 1], I[R - 1]);
+    float sub = 0.f;
+    int c = t0 / F, tin = t0 - c * F;
+    __syncthreads();                           // the ring's last readers are done
+    load_stage(c);
+    store_stage(c);
+    load_stage(c + 1);
+    __syncthreads();
+    for (int t = t0; t < t1; ++t, ++tin) {
+      if (tin == F) {
+        ++c;
+        tin = 0;
+        store_stage(c);
+        __syncthreads();
+        load_stage(c + 1);
+      }
+      const float* row = stage.row(c, tin);
+      const float l = lring[(c & 1) * FMAX + tin];
+      const float eg = gap_emission(row, g) - l;
+      float2 nb = tid > 0 ? xf[((t + 1) & 1) * NT + tid - 1] : make_float2(NEG, NEG);
+      nb.x -= sub;
+      nb.y -= sub;
+#pragma unroll
+      for (int r = R - 1; r >= 0; --r) {       // descending: slot r - 1's previous-frame values are still in place
+        const int k = tid * R + r;
+        float pB1 = r ? B[r > 0 ? r - 1 : 0] : nb.x;
+        if constexpr (MIND) {
+          if (r && dm[r > 0 ? r - 1 : 0] > 1) pB1 = NEG;
+        }
+        const float pI1 = r ? I[r > 0 ? r - 1 : 0] : nb.y;
+        const float in = lae3(G[r], pI1, pB1);
+        float x = B[r];                        // what I_k is entered from
+        if constexpr (MIND) x = chain_out(B[r], H[r], dm[r]);
+        const float ii = lae2(I[r], x);
+        float eb = NEG, ei = NEG;
+        if (k < N) {
+          tok_emission(row, av[r], eb, ei);
+          eb -= l;
+          ei -= l;
+          if constexpr (WIN) eb = win_mask(eb, t, wn[r]);
+        }
+        G[r] = k <= N ? in + eg : NEG;
+        if constexpr (MIND) chain_shift(H[r], B[r], ei, dm[r]);
+        B[r] = in + eb;
+        I[r] = ii + ei;
+      }
+      if constexpr (MIND) xf[(t & 1) * NT + tid] = make_float2(dm[R - 1] > 1 ? NEG : B[R - 1], I[R - 1]);
+      else xf[(t & 1) * NT + tid] = make_float2(B[R - 1], I[R - 1]);
+      const bool renorm = (t & (RENORM - 1)) == RENORM - 1;
+      if (renorm) {
+        float lm = NEG;
+#pragma unroll
+        for (int r = 0; r < R; ++r) lm = fmaxf(lm, fmaxf(G[r], fmaxf(B[r], I[r])));
+        renorm_publish(lm, wmax);
+      }
+      __syncthreads();                         // the neighbour exchange and the renormalisation share it
+      sub = 0.f;
+      if (renorm) {
+        float M = renorm_max<K::NW>(wmax);
+        if (!(M > NEG)) M = 0.f;               // every state -inf (or a NaN): subtract nothing (wfl_align's search takes M as it is)
+#pragma unroll
+        for (int r = 0; r < R; ++r) { G[r] -= M; B[r] -= M; I[r] -= M; }
+        if constexpr (MIND) {                  // (the offset is common to every state; the maximum is G's, B's and I's as before)
+#pragma unroll
+          for (int r = 0; r < R; ++r)
+#pragma unroll
+            for (int j = 0; j < CHAIN; ++j) H[r][j] -= M;
+        }
+        sub = M;
+        acc += (double)M;
+      }
+      if (keep) {                              // the block's alpha, for the backward sweep of the same thread
+        float* o = blk + (long)(t - t0) * K::S;
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+          o[(r * 3 + 0) * NT + tid] = G[r];
+          o[(r * 3 + 1) * NT + tid] = B[r];
+          o[(r * 3 + 2) * NT + tid] = I[r];
+        }
+        if (tid == 0) offa[t - t0] = acc;
+      } else if ((t + 1) % POST_W == 0 && t + 1 < T) {   // (a block ends on a renormalisation: sub is spent)
+        float* o = ckpt + (long)((t + 1) / POST_W) * SC;
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+          o[(r * 3 + 0) * NT + tid] = G[r];
+          o[(r * 3 + 1) * NT + tid] = B[r];
+          o[(r * 3 + 2) * NT + tid] = I[r];
+        }
+        if constexpr (MIND) {
+#pragma unroll
+          for (int r = 0; r < R; ++r)
+#pragma unroll
+            for (int j = 0; j < CHAIN; ++j) o[(R * 3 + r * CHAIN + j) * NT + tid] = H[r][j];
+        }
+        if (tid == 0) ckacc[(t + 1) / POST_W] = acc;
+      }
+    }
+  };
+
+  // ---- sweep 1: alpha over the whole clip, checkpoints, logZ
+  forward(0, T, false);
+  publish_end_states<R>(N, G, B, I, fin);
+  if constexpr (MIND) {                         // B_{N-1} ends the clip only where D_{N-1} == 1 (the thread that published it)
+#pragma unroll
+    for (int r = 0; r < R; ++r)
+      if (tid * R + r == N - 1 && dm[r] > 1) fin[2] = NEG;
+  }
+  __syncthreads();
+  if (tid == 0) {
+    const int ne = N >= 1 ? 3 : 1;
+    double m = -INFINITY;
+    for (int i = 0; i < ne; ++i) m = fmax(m, (double)fin[i]);
+    double s = 0.0;
+    for (int i = 0; i < ne; ++i) s += exp((double)fin[i] - m);
+    red[0] = m + log(s) + acc;
+    if constexpr (WIN || MIND) {
+      if (m == -INFINITY) red[0] = -INFINITY;   // no path opens every token inside its window (meets every duration)
+    }
+  }
+  __syncthreads();                             // (ckacc[] of thread 0 is visible to the block as well)
+  const double logZ = red[0];                  // on the fp32 log-sum-exps; the clip's logZ is logZ - lres
+  if constexpr (WIN || MIND) {
+    if (logZ == -INFINITY || (MIND && notpath)) {   // status 1 (with durations 8: paths exist, tok is none of them) and zeros
+      int code = 1;
+      if constexpr (MIND) {
+        if (logZ != -INFINITY) code = 8;
+      }
+      for (int k = tid; k < N; k += NT) {
+        a.tok_post[cl.tok_off + k] = 0.f;
+        a.start_mean[cl.tok_off + k] = 0.f;
+        a.start_sd[cl.tok_off + k] = 0.f;
+      }
+      if (tid == 0) { a.logz[cl.clip] = 0.f; a.status[cl.clip] = code; }
+      return;
+    }
+  }
+
+  // ---- sweeps 2 and 3, block by block from the end
+  float bG[R], bX[R];                          // beta(G_k), beta(B_k) = beta(I_k)
+  // with durations bX is beta(I_k) alone and beta(B_k) comes out of the slot's delay line (lattice.h chain_in): bB, of the frame in hand
+  float bC[MIND ? R : 1][CHAIN_BACK], bB[MIND ? R : 1];
+  int f0[R], cnt[R];
+  double occ[R], m0[R], m1[R], m2[R];
+#pragma unroll
+  for (int r = 0; r < R; ++r) {
+    const int k = tid * R + r;
+    bG[r] = k == N ? 0.f : NEG;
+    bX[r] = k == N - 1 ? 0.f : NEG;
+    if constexpr (MIND) f0[r] = fst[r];
+    else f0[r] = k < N ? first[k] : 0;
+    cnt[r] = 0;
+    occ[r] = m0[r] = m1[r] = m2[r] = 0.0;
+  }
+  if constexpr (MIND) {                         // no chain state ends the clip, and B_{N-1} only where D_{N-1} == 1
+#pragma unroll
+    for (int r = 0; r < R; ++r)
+#pragma unroll
+      for (int j = 0; j < CHAIN_BACK; ++j) bC[r][j] = NEG;
+    xb[(T & 1) * NT + tid] = make_float2(bG[0], chain_in(bX[0], bC[0], dm[0]));
+  } else {
+    xb[(T & 1) * NT + tid] = make_float2(bG[0], bX[0]);
+  }
+  double accb = 0.0;                           // what beta's renormalisations subtracted
+  float subb = 0.f;
+  for (int j = lay.nblk - 1; j >= 0; --j) {
+    const int t_lo = j * POST_W, t_hi = min(T, t_lo + POST_W) - 1;
+    forward(t_lo, t_hi + 1, true);
+    int c = t_hi / F, tin = t_hi - c * F;
+    __syncthreads();
+    load_stage(c);
+    store_stage(c);
+    load_stage(c - 1);
+    __syncthreads();
+    float an[R][3], ac[R][3];
+    auto load_alpha = [&](int f) {
+      const float* o = blk + (long)f * K::S;
+#pragma unroll
+      for (int r = 0; r < R; ++r) {
+        an[r][0] = o[(r * 3 + 0) * NT + tid];
+        an[r][1] = o[(r * 3 + 1) * NT + tid];
+        an[r][2] = o[(r * 3 + 2) * NT + tid];
+      }
+    };
+    load_alpha(t_hi - t_lo);
+    for (int t = t_hi; t >= t_lo; --t, --tin) {
+      if (tin < 0) {
+        --c;
+        tin = F - 1;
+        store_stage(c);
+        __syncthreads();
+        load_stage(c - 1);
+      }
+      const float* row = stage.row(c, tin);
+      const float l = lring[(c & 1) * FMAX + tin];
+      const int tk = tring[(c & 1) * FMAX + tin];
+#pragma unroll
+      for (int r = 0; r < R; ++r) { ac[r][0] = an[r][0]; ac[r][1] = an[r][1]; ac[r][2] = an[r][2]; }
+      if (t > t_lo) load_alpha(t - 1 - t_lo);  // one frame ahead of its use
+      // gamma_t of this thread's tokens
+      const double cst = offa[t - t_lo] + accb - logZ;
+      if constexpr (MIND) {
+#pragma unroll
+        for (int r = 0; r < R; ++r) bB[r] = chain_in(bX[r], bC[r], dm[r]);
+      }
+#pragma unroll
+      for (int r = 0; r < R; ++r) {
+        const int k = tid * R + r;
+        if (k < N) {
+          float bb = bX[r];
+          if constexpr (MIND) bb = bB[r];
+          const float gb = __expf((float)((double)ac[r][1] + (double)bb + cst));
+          const float gi = __expf((float)((double)ac[r][2] + (double)bX[r] + cst));
+          const double d = (double)(t - f0[r]);
+          m0[r] += (double)gb;
+          m1[r] += (double)gb * d;
+          m2[r] += (double)gb * d * d;
+          if constexpr (MIND) {
+            // gamma_t(H_k^j) = gamma_{t-j+1}(B_k): a path in B_k at t is in the token's B / chain states at t .. t + max(D_k - 2, 0),
+            // so gamma_t(B_k) counts once for every such frame inside Viterbi's run -- the block buffer needs no chain
+            const int ov = min(t + max(dm[r] - 2, 0), lst[r]) - max(t, f0[r]) + 1;
+            double add = (double)gb * (double)max(ov, 0);
+            if (tk == k) { add += (double)gi; ++cnt[r]; }
+            occ[r] += add;
+          } else {
+            if (tk == k) { occ[r] += (double)gb + (double)gi; ++cnt[r]; }
+          }
+        }
+      }
+      if (t == 0) break;
+      // beta_{t-1}
+      const float eg = gap_emission(row, g) - l;
+      float eb[R], ei[R];
+#pragma unroll
+      for (int r = 0; r < R; ++r) {
+        eb[r] = ei[r] = NEG;
+        if (tid * R + r < N) {
+          tok_emission(row, av[r], eb[r], ei[r]);
+          eb[r] -= l;
+          ei[r] -= l;
+          if constexpr (WIN) eb[r] = win_mask(eb[r], t, wn[r]);
+        }
+      }
+      float ebn = NEG;
+      if ((tid + 1) * R < N && tid + 1 < NT) {
+        float ein;
+        tok_emission(row, avn, ebn, ein);
+        ebn -= l;
+        if constexpr (WIN) ebn = win_mask(ebn, t, wnn);
+      }
+      float2 nb = tid + 1 < NT ? xb[((t + 1) & 1) * NT + tid + 1] : make_float2(NEG, NEG);
+      nb.x -= subb;
+      nb.y -= subb;
+#pragma unroll
+      for (int r = 0; r < R; ++r) {            // ascending: slot r + 1's values of frame t are still in place
+        const int k = tid * R + r;
+        const float nG = r + 1 < R ? bG[r + 1 < R ? r + 1 : 0] : nb.x;
+        float nX = r + 1 < R ? bX[r + 1 < R ? r + 1 : 0] : nb.y;
+        if constexpr (MIND) nX = r + 1 < R ? bB[r + 1 < R ? r + 1 : 0] : nb.y;   // the next token is entered through its B
+        const float nE = r + 1 < R ? eb[r + 1 < R ? r + 1 : 0] : ebn;
+        const float x = lae3(bX[r] + ei[r], nG + eg, nX + nE);
+        float bb = bX[r];
+        if constexpr (MIND) bb = bB[r];
+        const float y = lae2(bG[r] + eg, bb + eb[r]);
+        if constexpr (MIND) chain_shift_back(bC[r], bX[r], ei[r]);
+        bG[r] = k <= N ? y : NEG;
+        bX[r] = k < N ? x : NEG;
+      }
+      if constexpr (MIND) xb[(t & 1) * NT + tid] = make_float2(bG[0], chain_in(bX[0], bC[0], dm[0]));
+      else xb[(t & 1) * NT + tid] = make_float2(bG[0], bX[0]);
+      const bool renorm = (t & (RENORM - 1)) == 0;
+      if (renorm) {
+        float lm = NEG;
+#pragma unroll
+        for (int r = 0; r < R; ++r) lm = fmaxf(lm, fmaxf(bG[r], bX[r]));
+        renorm_publish(lm, wmax);
+      }
+      __syncthreads();
+      subb = 0.f;
+      if (renorm) {
+        float M = renorm_max<K::NW>(wmax);
+        if (!(M > NEG)) M = 0.f;
+#pragma unroll
+        for (int r = 0; r < R; ++r) { bG[r] -= M; bX[r] -= M; }
+        if constexpr (MIND) {
+#pragma unroll
+          for (int r = 0; r < R; ++r)
+#pragma unroll
+            for (int j = 0; j < CHAIN_BACK; ++j) bC[r][j] -= M;
+        }
+        subb = M;
+        accb += (double)M;
+      }
+    }
+  }
+
+  // ---- per-token outputs, by the thread that owns the token
+#pragma unroll
+  for (int r = 0; r < R; ++r) {
+    const int k = tid * R + r;
+    if (k < N) {
+      const double mean = m0[r] > 0.0 ? m1[r] / m0[r] : 0.0;
+      const double var = m0[r] > 0.0 ? m2[r] / m0[r] - mean * mean : 0.0;
+      a.tok_post[cl.tok_off + k] = cnt[r] > 0 ? fminf((float)(occ[r] / (double)cnt[r]), 1.f) : 0.f;
+      a.start_mean[cl.tok_off + k] = (float)mean;
+      a.start_sd[cl.tok_off + k] = (float)sqrt(fmax(var, 0.0));
+    }
+  }
+  if (tid == 0) {
+    a.logz[cl.clip] = (float)(logZ - lres);
+    a.status[cl.clip] = 0;
+  }
+}
+
+// over the cap the kernel reports status 2; such a clip is sized (and launched) as the cap's configuration, so the workspace need is
+// monotone in N -- wfl_align instead gives it no workspace, its words being zero for every clip it does not search
+int post_cfg(int N) { return std::min(cfg_of(N), NCFG - 1); }
+
+long clip_floats(int T, int N) {
+  if (T <= 0) return 0;
+  const long S = dispatch_cfg(post_cfg(N), [](auto sh) { return PCfg<decltype(sh)::NT, decltype(sh)::R>::S; });
+  return round64(PostLayout(T, S, S).total);  // (256-byte aligned)
+}
+
+// with minimum durations: the checkpoints hold the chain as well, the block does not (post_kernel's note at occ)
+long clip_floats_min(int T, int N) {
+  if (T <= 0) return 0;
+  return dispatch_cfg(post_cfg(N), [T](auto sh) {
+    using K = PCfg<decltype(sh)::NT, decltype(sh)::R>;
+    return round64(PostLayout(T, K::SM, K::S).total);
+  });
+}
+
+}  // namespace
+
+namespace {
+
+// wfl_align_posterior (WIN false), wfl_align_posterior_windowed and wfl_align_min_duration_posterior (MIND, with or without windows): one
+// host path
+template <bool WIN, bool MIND>
+int posterior_batch(const char* fn, const float* logits, int64_t ldl, int32_t C, int32_t o_id, const int64_t* frame_off_host,
+                    const int32_t* n_frames_host, const int32_t* tok_off_host, const int32_t* n_tok_host, const int32_t* tok_cls,
+                    const int32_t* tok_win, const int32_t* tok_min, const int32_t* gap_cls, int32_t n_clips, const int32_t* tok,
+                    void* workspace, int64_t workspace_bytes, float* logz, float* tok_post, float* start_mean, float* start_sd,
+                    int32_t* status, void* stream) {
+  const int64_t need = MIND ? wfl_align_min_duration_posterior_workspace_bytes(n_frames_host, n_tok_host, n_clips)
+                            : wfl_align_posterior_workspace_bytes(n_frames_host, n_tok_host, n_clips);
+  bool any_tok = false, any_frame = false;
+  int rc = check_clip_args(fn, C, o_id, ldl, frame_off_host, n_frames_host, tok_off_host, n_tok_host, n_clips, need, any_tok, any_frame);
+  if (rc || n_clips == 0) return rc;
+  if (!logz || !status || !gap_cls ||
+      (any_tok && (!tok_cls || (WIN && !tok_win) || (MIND && !tok_min) || !tok_post || !start_mean || !start_sd)) ||
+      (any_frame && (!logits || !tok)))
+    return fail(fn, -1, "null device pointer");
+  if ((rc = check_workspace(fn, need, workspace, workspace_bytes))) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  PostLaunch a{};
+  a.logits = logits; a.ldl = ldl; a.C = C; a.tok_cls = tok_cls; a.gap_cls = gap_cls; a.tok = tok; a.tok_win = tok_win; a.tok_min = tok_min;
+  a.ws = (float*)workspace; a.logz = logz; a.tok_post = tok_post; a.start_mean = start_mean; a.start_sd = start_sd; a.status = status;
+  return launch_clips<NCFG>(
+      a, n_clips,
+      [&](int b, long off, LatClip& c, int& cfg) {
+        const int T = n_frames_host[b], N = n_tok_host[b];
+        c = LatClip{(long)frame_off_host[b], off, T, tok_off_host[b], N, b};
+        cfg = post_cfg(N);
+        return MIND ? clip_floats_min(T, N) : clip_floats(T, N);
+      },
+      [&](int cfg, const PostLaunch& a) {
+        return dispatch_cfg(cfg, [&](auto sh) {
+          constexpr int NT = decltype(sh)::NT, R = decltype(sh)::R;
+          return launch_cfg<post_kernel<NT, R, WIN, MIND>, NT, PCfg<NT, R>::LDS>(fn, a, s);
+        });
+      });
+}
+
+}  // namespace

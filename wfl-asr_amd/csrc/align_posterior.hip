@@ -1,548 +1,10 @@
-// Forward-backward over the forced-alignment lattice of wfl_align: per-token posteriors of a Viterbi path (wfl_align_posterior,
-// include/wfl_asr.h).  The sum-product twin of csrc/align.hip; the reference has no counterpart (it reports no confidence for its
-// string match).
-//
-// Lattice, emissions, start / end states and caps are wfl_align's, and so is their code: csrc/lattice.h holds the caps, the
-// configurations, the shared LDS layout, lattice setup with its status codes, the logits stage ring, the emission gathers, the
-// renormalisation halves and the host side of a ragged batch.  Here: the sum-product sweeps, the status-8 check of `tok`, the
-// checkpoint workspace and the per-token outputs.  States G_k = 3k, B_k = 3k + 1, I_k = 3k + 2:
-//   alpha_t(G_k) = EG_t + lse(alpha_{t-1}(G_k), alpha_{t-1}(I_{k-1}), alpha_{t-1}(B_{k-1}))      alpha_t(B_k): the same sum + EB_t(k)
-//   alpha_t(I_k) = EI_t(k) + lse(alpha_{t-1}(I_k), alpha_{t-1}(B_k))
-//   beta_{t-1}(G_k) = lse(beta_t(G_k) + EG_t, beta_t(B_k) + EB_t(k))
-//   beta_{t-1}(B_k) = beta_{t-1}(I_k) = lse(beta_t(I_k) + EI_t(k), beta_t(G_{k+1}) + EG_t, beta_t(B_{k+1}) + EB_t(k+1))
-//   logZ = lse(alpha_{T-1}(G_N), alpha_{T-1}(I_{N-1}), alpha_{T-1}(B_{N-1})),   gamma_t(s) = exp(alpha_t(s) + beta_t(s) - logZ).
-// beta of B_k and I_k are equal (same successors), so the backward sweep carries two values per token.
-//
-// One workgroup per clip, configurations and slot ownership from lattice.h: thread i owns the token slots i R .. i R + R - 1 in
-// registers.  Per frame one float2 crosses between neighbouring threads through LDS, one barrier per frame: the forward sweep takes
-// (alpha(B), alpha(I)) of the last slot of thread i - 1, the backward sweep (beta(G), beta(B)) of the first slot of thread i + 1 (the
-// emission of that slot's B state is gathered by thread i itself, from the staged row).  Every per-token output is accumulated by
-// the thread that owns the token; no reduction over the block per frame.  Every 16 frames the block's maximum is subtracted from the
-// states (alpha and beta separately) and added to a double, so the fp32 log-domain values never grow with T.
-//
-// Memory: the alpha lattice is never stored.  Sweep 1 runs forward over the clip and keeps a checkpoint of the registers every
-// POST_W frames; then, block by block from the last one, sweep 2 recomputes the block's POST_W frames of alpha from its checkpoint
-// into a block buffer and sweep 3 walks beta down the block, combining.  Every thread reads back only what it wrote itself.
-// Workspace per clip: lse[T] | checkpoints' offsets | checkpoints | one block (wfl_align_posterior_workspace_bytes).
-//
-// wfl_align_posterior_windowed is the same kernel instantiated with WIN: EB passes through lattice.h's win_mask wherever it is gathered --
-// alpha, beta's own slots, and the next thread's first slot (ebn) -- with the windows of a thread's slots (and of that one slot) in
-// registers; a tok that opens a token outside its window is status 8, logZ = -inf status 1.
-//
-// The per-frame log-sum-exp of the logits is computed once (double, expf), stored in fp32 and subtracted from the gathered logits;
-// what the fp32 rounding of it loses is summed in double and given back to logZ (it is common to every path).
-#include "lattice.h"
-#include "wfl_asr.h"
-
-#include <limits.h>
-
-namespace {
-
-using namespace lattice;
-
-constexpr int POST_W = 128;                // frames per recomputed block (a multiple of the renormalisation period)
-static_assert(POST_W % RENORM == 0, "a block ends on a renormalisation");
-
-struct PostLaunch {
-  const float* logits;
-  long ldl;
-  int C;
-  const int* tok_cls;  // [total tokens][4][2]
-  const int* gap_cls;  // [n_clips][8]
-  const int* tok;      // wfl_align's output, same rows as the logits
-  float* ws;           // LatClip::ws_off: the clip's workspace, in floats
-  float* logz;
-  float* tok_post;
-  float* start_mean;
-  float* start_sd;
-  int* status;
-  int n;
-  LatClip clip[CLIPS_PER_LAUNCH];
-  const int* tok_win;  // [total tokens][2] = (lo, hi), the windowed kernels alone (last: the other fields stay where they were)
-};
-
-// a clip's workspace in floats: [lse: round64(T)] [checkpoint offsets: round64(2 nblk)] [checkpoints: nblk S] [block: POST_W S]
-struct PostLayout {
-  long ckacc, ckpt, blk, total;
-  int nblk;
-  __host__ __device__ PostLayout(int T, long S) {
-    nblk = (T + POST_W - 1) / POST_W;
-    ckacc = round64(T);
-    ckpt = ckacc + round64(2L * nblk);
-    blk = ckpt + (long)nblk * S;
-    total = blk + (long)POST_W * S;
-  }
-};
-
-template <int NT, int R>
-struct PCfg : LdsBase<NT, R, NT * R * 4 + 2 * 2 * NT * 8> {       // its own between alt and wmax: first[] and the two neighbour exchanges
-  static constexpr long S = (long)NT * R * 3;            // floats of one frame's alpha (and of one checkpoint)
-  static constexpr int OFF_FIRST = PCfg::OFF_X;                    // first frame of every token's Viterbi run
-  static constexpr int OFF_XF = OFF_FIRST + NT * R * 4;            // forward neighbour exchange: [2][NT] float2
-  static constexpr int OFF_XB = OFF_XF + 2 * NT * 8;               // backward neighbour exchange
-  static constexpr int OFF_OFFA = PCfg::OFF_OWN;                   // alpha's offset of every frame of the block (double)
-  static constexpr int OFF_LRING = OFF_OFFA + POST_W * 8;          // staged rows' log-sum-exp
-  static constexpr int OFF_TRING = OFF_LRING + 2 * FMAX * 4;       // staged rows' Viterbi token
-  static constexpr int OFF_MISC = OFF_TRING + 2 * FMAX * 4;
-  static constexpr int LDS = OFF_MISC + 64;
-};
-
-// log(exp a + exp b [+ exp c]); -inf in, -inf out (v_exp_f32 / v_log_f32)
-__device__ __forceinline__ float lae2(float a, float b) {
-  const float m = fmaxf(a, b);
-  const float ms = m == -INFINITY ? 0.f : m;
-  return ms + __logf(__expf(a - ms) + __expf(b - ms));
-}
-
-__device__ __forceinline__ float lae3(float a, float b, float c) {
-  const float m = fmaxf(a, fmaxf(b, c));
-  const float ms = m == -INFINITY ? 0.f : m;
-  return ms + __logf(__expf(a - ms) + __expf(b - ms) + __expf(c - ms));
-}
-
-// WIN: the start windows of wfl_align_posterior_windowed (lattice.h win_mask); false is wfl_align_posterior's kernel, instruction for
-// instruction
-template <int NT, int R, bool WIN>
-__global__ __launch_bounds__(NT) void post_kernel(PostLaunch a) {
-  using K = PCfg<NT, R>;
-  extern __shared__ __attribute__((aligned(16))) char lds[];
-  float* ring = (float*)lds;
-  int4* alt = (int4*)(lds + K::OFF_ALT);
-  int* first = (int*)(lds + K::OFF_FIRST);
-  float2* xf = (float2*)(lds + K::OFF_XF);
-  float2* xb = (float2*)(lds + K::OFF_XB);
-  float* wmax = (float*)(lds + K::OFF_WMAX);
-  double* red = (double*)(lds + K::OFF_RED);
-  double* offa = (double*)(lds + K::OFF_OFFA);
-  float* lring = (float*)(lds + K::OFF_LRING);
-  int* tring = (int*)(lds + K::OFF_TRING);
-  int* misc = (int*)(lds + K::OFF_MISC);
-  float* fin = (float*)(misc + 4);
-
-  const LatClip cl = a.clip[blockIdx.x];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int T = cl.T, N = cl.N, C = a.C;
-  const float* Z = a.logits + cl.frame_off * a.ldl;
-  const int* tokp = a.tok + cl.frame_off;
-  const float NEG = -INFINITY;
-
-  int g[NGAP];
-  int st = lattice_setup<NT, R>(cl, C, a.tok_cls, a.gap_cls, alt, misc, g);
-  int2 wn[WIN ? R : 1];                        // this thread's slots' start windows, in registers, and the next thread's first slot's
-  int2 wnn = make_int2(0, WIN_OPEN_HI);
-  if constexpr (WIN) {
-    if (st == 0) {
-      load_windows<R>(a.tok_win, cl.tok_off, N, wn);
-      wnn = load_window(a.tok_win, cl.tok_off, (tid + 1) * R, N);
-    }
-  }
-  if (st == 0 && T > 0) {
-    // the first frame of every token's Viterbi run; a tok that is not a path of this lattice (a token missing, a value out of range)
-#pragma unroll
-    for (int r = 0; r < R; ++r) first[tid * R + r] = INT_MAX;
-    __syncthreads();                           // (and every thread has read setup's flag before this phase may raise it again)
-    bool bad = false;
-    for (int t = tid; t < T; t += NT) {
-      const int k = tokp[t];
-      if (k < -1 || k >= N) bad = true;
-      else if (k >= 0 && (t == 0 || tokp[t - 1] != k)) atomicMin(&first[k], t);
-    }
-    if (bad) misc[0] = 1;
-    __syncthreads();
-#pragma unroll
-    for (int r = 0; r < R; ++r)
-      if (tid * R + r < N) {
-        const int f = first[tid * R + r];
-        if (f == INT_MAX) misc[0] = 1;
-        if constexpr (WIN) {
-          if (f < wn[r].x || f > wn[r].y) misc[0] = 1;   // a token opens outside its window: not a path of this lattice either
-        }
-      }
-    __syncthreads();
-    if (misc[0]) st = 8;
-  }
-  if (st != 0 || T == 0) {
-    for (int k = tid; k < N; k += NT) {
-      a.tok_post[cl.tok_off + k] = 0.f;
-      a.start_mean[cl.tok_off + k] = 0.f;
-      a.start_sd[cl.tok_off + k] = 0.f;
-    }
-    if (tid == 0) { a.logz[cl.clip] = 0.f; a.status[cl.clip] = st; }
-    return;
-  }
-
-  const PostLayout lay(T, K::S);
-  float* ws = a.ws + cl.ws_off;
-  float* lse = ws;
-  double* ckacc = (double*)(ws + lay.ckacc);
-  float* ckpt = ws + lay.ckpt;
-  float* blk = ws + lay.blk;
-
-  // ---- the per-frame log-sum-exp, in fp32 for the sweeps; what its rounding loses, in double for logZ
-  double lres = 0.0;
-  // (a thread per row; a wave per row with coalesced loads and wave reductions was measured 4 % slower for the whole kernel)
-  for (int t = tid; t < T; t += NT) {
-    const float* z = Z + (long)t * a.ldl;
-    float m = z[0];
-    for (int q = 1; q < C; ++q) m = fmaxf(m, z[q]);
-    double se = 0.0;
-    for (int q = 0; q < C; ++q) se += (double)expf(z[q] - m);
-    const double ld = (double)m + log(se);
-    const float lf = (float)ld;
-    lse[t] = lf;
-    lres += ld - (double)lf;
-  }
-  lres = wave_sum(lres);
-  if (lane == 0) red[wave] = lres;
-  __syncthreads();                             // (and the block sees lse[])
-  lres = 0.0;
-#pragma unroll
-  for (int w = 0; w < K::NW; ++w) lres += red[w];
-
-  // ---- staging of the logits rows, with their log-sum-exp and Viterbi token
-  LogitStages<NT, K::PR> stage(Z, a.ldl, T, C, ring);
-  const int F = stage.F;
-  float pre_l = 0.f;
-  int pre_t = -1;
-  auto load_stage = [&](int c) {               // (the backward sweep runs one stage ahead as well, down to c = -1)
-    stage.load(c, c >= 0);
-    const bool in = tid < F && c >= 0 && c * F + tid < T;
-    pre_l = in ? lse[c * F + tid] : 0.f;
-    pre_t = in ? tokp[c * F + tid] : -1;
-  };
-  auto store_stage = [&](int c) {
-    stage.store(c);
-    if (tid < F) {
-      lring[(c & 1) * FMAX + tid] = pre_l;
-      tring[(c & 1) * FMAX + tid] = pre_t;
-    }
-  };
-
-  int4 av[R];                                   // this thread's slots' alternatives
-#pragma unroll
-  for (int r = 0; r < R; ++r) av[r] = alt[tid * R + r];
-  const int4 avn = tid + 1 < NT ? alt[(tid + 1) * R] : make_int4(-1, -1, -1, -1);   // the next thread's first slot
-
-  // ---- the forward sweep over frames t0 .. t1 - 1, from the clip's start (t0 = 0) or from checkpoint t0 / POST_W
-  float G[R], B[R], I[R];
-  double acc = 0.0;                            // what alpha's renormalisations subtracted
-  auto forward = [&](int t0, int t1, bool keep) {
-    if (t0 == 0) {
-#pragma unroll
-      for (int r = 0; r < R; ++r) G[r] = B[r] = I[r] = NEG;
-      if (tid == 0) G[0] = 0.f;                // a virtual frame -1 in G_0: frame 0 starts in G_0 or B_0
-      acc = 0.0;
-    } else {
-      const float* ck = ckpt + (long)(t0 / POST_W) * K::S;
-#pragma unroll
-      for (int r = 0; r < R; ++r) {
-        G[r] = ck[(r * 3 + 0) * NT + tid];
-        B[r] = ck[(r * 3 + 1) * NT + tid];
-        I[r] = ck[(r * 3 + 2) * NT + tid];
-      }
-      acc = ckacc[t0 / POST_W];
-    }
-    xf[((t0 + 1) & 1) * NT + tid] = make_float2(B[R - 1], I[R - 1]);
-    float sub = 0.f;
-    int c = t0 / F, tin = t0 - c * F;
-    __syncthreads();                           // the ring's last readers are done
-    load_stage(c);
-    store_stage(c);
-    load_stage(c + 1);
-    __syncthreads();
-    for (int t = t0; t < t1; ++t, ++tin) {
-      if (tin == F) {
-        ++c;
-        tin = 0;
-        store_stage(c);
-        __syncthreads();
-        load_stage(c + 1);
-      }
-      const float* row = stage.row(c, tin);
-      const float l = lring[(c & 1) * FMAX + tin];
-      const float eg = gap_emission(row, g) - l;
-      float2 nb = tid > 0 ? xf[((t + 1) & 1) * NT + tid - 1] : make_float2(NEG, NEG);
-      nb.x -= sub;
-      nb.y -= sub;
-#pragma unroll
-      for (int r = R - 1; r >= 0; --r) {       // descending: slot r - 1's previous-frame values are still in place
-        const int k = tid * R + r;
-        const float pB1 = r ? B[r > 0 ? r - 1 : 0] : nb.x;
-        const float pI1 = r ? I[r > 0 ? r - 1 : 0] : nb.y;
-        const float in = lae3(G[r], pI1, pB1);
-        const float ii = lae2(I[r], B[r]);
-        float eb = NEG, ei = NEG;
-        if (k < N) {
-          tok_emission(row, av[r], eb, ei);
-          eb -= l;
-          ei -= l;
-          if constexpr (WIN) eb = win_mask(eb, t, wn[r]);
-        }
-        G[r] = k <= N ? in + eg : NEG;
-        B[r] = in + eb;
-        I[r] = ii + ei;
-      }
-      xf[(t & 1) * NT + tid] = make_float2(B[R - 1], I[R - 1]);
-      const bool renorm = (t & (RENORM - 1)) == RENORM - 1;
-      if (renorm) {
-        float lm = NEG;
-#pragma unroll
-        for (int r = 0; r < R; ++r) lm = fmaxf(lm, fmaxf(G[r], fmaxf(B[r], I[r])));
-        renorm_publish(lm, wmax);
-      }
-      __syncthreads();                         // the neighbour exchange and the renormalisation share it
-      sub = 0.f;
-      if (renorm) {
-        float M = renorm_max<K::NW>(wmax);
-        if (!(M > NEG)) M = 0.f;               // every state -inf (or a NaN): subtract nothing (wfl_align's search takes M as it is)
-#pragma unroll
-        for (int r = 0; r < R; ++r) { G[r] -= M; B[r] -= M; I[r] -= M; }
-        sub = M;
-        acc += (double)M;
-      }
-      if (keep) {                              // the block's alpha, for the backward sweep of the same thread
-        float* o = blk + (long)(t - t0) * K::S;
-#pragma unroll
-        for (int r = 0; r < R; ++r) {
-          o[(r * 3 + 0) * NT + tid] = G[r];
-          o[(r * 3 + 1) * NT + tid] = B[r];
-          o[(r * 3 + 2) * NT + tid] = I[r];
-        }
-        if (tid == 0) offa[t - t0] = acc;
-      } else if ((t + 1) % POST_W == 0 && t + 1 < T) {   // (a block ends on a renormalisation: sub is spent)
-        float* o = ckpt + (long)((t + 1) / POST_W) * K::S;
-#pragma unroll
-        for (int r = 0; r < R; ++r) {
-          o[(r * 3 + 0) * NT + tid] = G[r];
-          o[(r * 3 + 1) * NT + tid] = B[r];
-          o[(r * 3 + 2) * NT + tid] = I[r];
-        }
-        if (tid == 0) ckacc[(t + 1) / POST_W] = acc;
-      }
-    }
-  };
-
-  // ---- sweep 1: alpha over the whole clip, checkpoints, logZ
-  forward(0, T, false);
-  publish_end_states<R>(N, G, B, I, fin);
-  __syncthreads();
-  if (tid == 0) {
-    const int ne = N >= 1 ? 3 : 1;
-    double m = -INFINITY;
-    for (int i = 0; i < ne; ++i) m = fmax(m, (double)fin[i]);
-    double s = 0.0;
-    for (int i = 0; i < ne; ++i) s += exp((double)fin[i] - m);
-    red[0] = m + log(s) + acc;
-    if constexpr (WIN) {
-      if (m == -INFINITY) red[0] = -INFINITY;   // no path opens every token inside its window
-    }
-  }
-  __syncthreads();                             // (ckacc[] of thread 0 is visible to the block as well)
-  const double logZ = red[0];                  // on the fp32 log-sum-exps; the clip's logZ is logZ - lres
-  if constexpr (WIN) {
-    if (logZ == -INFINITY) {                   // status 1 and zeros, as every clip with a status
-      for (int k = tid; k < N; k += NT) {
-        a.tok_post[cl.tok_off + k] = 0.f;
-        a.start_mean[cl.tok_off + k] = 0.f;
-        a.start_sd[cl.tok_off + k] = 0.f;
-      }
-      if (tid == 0) { a.logz[cl.clip] = 0.f; a.status[cl.clip] = 1; }
-      return;
-    }
-  }
-
-  // ---- sweeps 2 and 3, block by block from the end
-  float bG[R], bX[R];                          // beta(G_k), beta(B_k) = beta(I_k)
-  int f0[R], cnt[R];
-  double occ[R], m0[R], m1[R], m2[R];
-#pragma unroll
-  for (int r = 0; r < R; ++r) {
-    const int k = tid * R + r;
-    bG[r] = k == N ? 0.f : NEG;
-    bX[r] = k == N - 1 ? 0.f : NEG;
-    f0[r] = k < N ? first[k] : 0;
-    cnt[r] = 0;
-    occ[r] = m0[r] = m1[r] = m2[r] = 0.0;
-  }
-  xb[(T & 1) * NT + tid] = make_float2(bG[0], bX[0]);
-  double accb = 0.0;                           // what beta's renormalisations subtracted
-  float subb = 0.f;
-  for (int j = lay.nblk - 1; j >= 0; --j) {
-    const int t_lo = j * POST_W, t_hi = min(T, t_lo + POST_W) - 1;
-    forward(t_lo, t_hi + 1, true);
-    int c = t_hi / F, tin = t_hi - c * F;
-    __syncthreads();
-    load_stage(c);
-    store_stage(c);
-    load_stage(c - 1);
-    __syncthreads();
-    float an[R][3], ac[R][3];
-    auto load_alpha = [&](int f) {
-      const float* o = blk + (long)f * K::S;
-#pragma unroll
-      for (int r = 0; r < R; ++r) {
-        an[r][0] = o[(r * 3 + 0) * NT + tid];
-        an[r][1] = o[(r * 3 + 1) * NT + tid];
-        an[r][2] = o[(r * 3 + 2) * NT + tid];
-      }
-    };
-    load_alpha(t_hi - t_lo);
-    for (int t = t_hi; t >= t_lo; --t, --tin) {
-      if (tin < 0) {
-        --c;
-        tin = F - 1;
-        store_stage(c);
-        __syncthreads();
-        load_stage(c - 1);
-      }
-      const float* row = stage.row(c, tin);
-      const float l = lring[(c & 1) * FMAX + tin];
-      const int tk = tring[(c & 1) * FMAX + tin];
-#pragma unroll
-      for (int r = 0; r < R; ++r) { ac[r][0] = an[r][0]; ac[r][1] = an[r][1]; ac[r][2] = an[r][2]; }
-      if (t > t_lo) load_alpha(t - 1 - t_lo);  // one frame ahead of its use
-      // gamma_t of this thread's tokens
-      const double cst = offa[t - t_lo] + accb - logZ;
-#pragma unroll
-      for (int r = 0; r < R; ++r) {
-        const int k = tid * R + r;
-        if (k < N) {
-          const float gb = __expf((float)((double)ac[r][1] + (double)bX[r] + cst));
-          const float gi = __expf((float)((double)ac[r][2] + (double)bX[r] + cst));
-          const double d = (double)(t - f0[r]);
-          m0[r] += (double)gb;
-          m1[r] += (double)gb * d;
-          m2[r] += (double)gb * d * d;
-          if (tk == k) { occ[r] += (double)gb + (double)gi; ++cnt[r]; }
-        }
-      }
-      if (t == 0) break;
-      // beta_{t-1}
-      const float eg = gap_emission(row, g) - l;
-      float eb[R], ei[R];
-#pragma unroll
-      for (int r = 0; r < R; ++r) {
-        eb[r] = ei[r] = NEG;
-        if (tid * R + r < N) {
-          tok_emission(row, av[r], eb[r], ei[r]);
-          eb[r] -= l;
-          ei[r] -= l;
-          if constexpr (WIN) eb[r] = win_mask(eb[r], t, wn[r]);
-        }
-      }
-      float ebn = NEG;
-      if ((tid + 1) * R < N && tid + 1 < NT) {
-        float ein;
-        tok_emission(row, avn, ebn, ein);
-        ebn -= l;
-        if constexpr (WIN) ebn = win_mask(ebn, t, wnn);
-      }
-      float2 nb = tid + 1 < NT ? xb[((t + 1) & 1) * NT + tid + 1] : make_float2(NEG, NEG);
-      nb.x -= subb;
-      nb.y -= subb;
-#pragma unroll
-      for (int r = 0; r < R; ++r) {            // ascending: slot r + 1's values of frame t are still in place
-        const int k = tid * R + r;
-        const float nG = r + 1 < R ? bG[r + 1 < R ? r + 1 : 0] : nb.x;
-        const float nX = r + 1 < R ? bX[r + 1 < R ? r + 1 : 0] : nb.y;
-        const float nE = r + 1 < R ? eb[r + 1 < R ? r + 1 : 0] : ebn;
-        const float x = lae3(bX[r] + ei[r], nG + eg, nX + nE);
-        const float y = lae2(bG[r] + eg, bX[r] + eb[r]);
-        bG[r] = k <= N ? y : NEG;
-        bX[r] = k < N ? x : NEG;
-      }
-      xb[(t & 1) * NT + tid] = make_float2(bG[0], bX[0]);
-      const bool renorm = (t & (RENORM - 1)) == 0;
-      if (renorm) {
-        float lm = NEG;
-#pragma unroll
-        for (int r = 0; r < R; ++r) lm = fmaxf(lm, fmaxf(bG[r], bX[r]));
-        renorm_publish(lm, wmax);
-      }
-      __syncthreads();
-      subb = 0.f;
-      if (renorm) {
-        float M = renorm_max<K::NW>(wmax);
-        if (!(M > NEG)) M = 0.f;
-#pragma unroll
-        for (int r = 0; r < R; ++r) { bG[r] -= M; bX[r] -= M; }
-        subb = M;
-        accb += (double)M;
-      }
-    }
-  }
-
-  // ---- per-token outputs, by the thread that owns the token
-#pragma unroll
-  for (int r = 0; r < R; ++r) {
-    const int k = tid * R + r;
-    if (k < N) {
-      const double mean = m0[r] > 0.0 ? m1[r] / m0[r] : 0.0;
-      const double var = m0[r] > 0.0 ? m2[r] / m0[r] - mean * mean : 0.0;
-      a.tok_post[cl.tok_off + k] = cnt[r] > 0 ? fminf((float)(occ[r] / (double)cnt[r]), 1.f) : 0.f;
-      a.start_mean[cl.tok_off + k] = (float)mean;
-      a.start_sd[cl.tok_off + k] = (float)sqrt(fmax(var, 0.0));
-    }
-  }
-  if (tid == 0) {
-    a.logz[cl.clip] = (float)(logZ - lres);
-    a.status[cl.clip] = 0;
-  }
-}
-
-// over the cap the kernel reports status 2; such a clip is sized (and launched) as the cap's configuration, so the workspace need is
-// monotone in N -- wfl_align instead gives it no workspace, its words being zero for every clip it does not search
-int post_cfg(int N) { return std::min(cfg_of(N), NCFG - 1); }
-
-long clip_floats(int T, int N) {
-  if (T <= 0) return 0;
-  const long S = dispatch_cfg(post_cfg(N), [](auto sh) { return PCfg<decltype(sh)::NT, decltype(sh)::R>::S; });
-  return round64(PostLayout(T, S).total);     // (256-byte aligned)
-}
-
-}  // namespace
+// wfl_align_posterior and wfl_align_posterior_windowed (include/wfl_asr.h): the entries of csrc/align_posterior.h's kernel without
+// minimum durations.  wfl_align_min_duration_posterior is csrc/align_min_duration_posterior.hip.
+#include "align_posterior.h"
 
 extern "C" int64_t wfl_align_posterior_workspace_bytes(const int32_t* n_frames_host, const int32_t* n_tok_host, int32_t n_clips) {
   return clips_workspace_bytes(n_frames_host, n_tok_host, n_clips, clip_floats);
 }
-
-namespace {
-
-// wfl_align_posterior (WIN false) and wfl_align_posterior_windowed: one host path
-template <bool WIN>
-int posterior_batch(const char* fn, const float* logits, int64_t ldl, int32_t C, int32_t o_id, const int64_t* frame_off_host,
-                    const int32_t* n_frames_host, const int32_t* tok_off_host, const int32_t* n_tok_host, const int32_t* tok_cls,
-                    const int32_t* tok_win, const int32_t* gap_cls, int32_t n_clips, const int32_t* tok, void* workspace,
-                    int64_t workspace_bytes, float* logz, float* tok_post, float* start_mean, float* start_sd, int32_t* status,
-                    void* stream) {
-  const int64_t need = wfl_align_posterior_workspace_bytes(n_frames_host, n_tok_host, n_clips);
-  bool any_tok = false, any_frame = false;
-  int rc = check_clip_args(fn, C, o_id, ldl, frame_off_host, n_frames_host, tok_off_host, n_tok_host, n_clips, need, any_tok, any_frame);
-  if (rc || n_clips == 0) return rc;
-  if (!logz || !status || !gap_cls || (any_tok && (!tok_cls || (WIN && !tok_win) || !tok_post || !start_mean || !start_sd)) || (any_frame && (!logits || !tok)))
-    return fail(fn, -1, "null device pointer");
-  if ((rc = check_workspace(fn, need, workspace, workspace_bytes))) return rc;
-  hipStream_t s = (hipStream_t)stream;
-  PostLaunch a{};
-  a.logits = logits; a.ldl = ldl; a.C = C; a.tok_cls = tok_cls; a.gap_cls = gap_cls; a.tok = tok; a.tok_win = tok_win;
-  a.ws = (float*)workspace; a.logz = logz; a.tok_post = tok_post; a.start_mean = start_mean; a.start_sd = start_sd; a.status = status;
-  return launch_clips<NCFG>(
-      a, n_clips,
-      [&](int b, long off, LatClip& c, int& cfg) {
-        const int T = n_frames_host[b], N = n_tok_host[b];
-        c = LatClip{(long)frame_off_host[b], off, T, tok_off_host[b], N, b};
-        cfg = post_cfg(N);
-        return clip_floats(T, N);
-      },
-      [&](int cfg, const PostLaunch& a) {
-        return dispatch_cfg(cfg, [&](auto sh) {
-          constexpr int NT = decltype(sh)::NT, R = decltype(sh)::R;
-          return launch_cfg<post_kernel<NT, R, WIN>, NT, PCfg<NT, R>::LDS>(fn, a, s);
-        });
-      });
-}
-
-}  // namespace
 
 extern "C" {
 
@@ -550,9 +12,9 @@ int32_t wfl_align_posterior(const float* logits, int64_t ldl, int32_t C, int32_t
                             const int32_t* n_frames_host, const int32_t* tok_off_host, const int32_t* n_tok_host, const int32_t* tok_cls,
                             const int32_t* gap_cls, int32_t n_clips, const int32_t* tok, void* workspace, int64_t workspace_bytes,
                             float* logz, float* tok_post, float* start_mean, float* start_sd, int32_t* status, void* stream) {
-  return posterior_batch<false>("wfl_align_posterior", logits, ldl, C, o_id, frame_off_host, n_frames_host, tok_off_host, n_tok_host,
-                                tok_cls, nullptr, gap_cls, n_clips, tok, workspace, workspace_bytes, logz, tok_post, start_mean, start_sd,
-                                status, stream);
+  return posterior_batch<false, false>("wfl_align_posterior", logits, ldl, C, o_id, frame_off_host, n_frames_host, tok_off_host,
+                                       n_tok_host, tok_cls, nullptr, nullptr, gap_cls, n_clips, tok, workspace, workspace_bytes, logz,
+                                       tok_post, start_mean, start_sd, status, stream);
 }
 
 int32_t wfl_align_posterior_windowed(const float* logits, int64_t ldl, int32_t C, int32_t o_id, const int64_t* frame_off_host,
@@ -560,9 +22,9 @@ int32_t wfl_align_posterior_windowed(const float* logits, int64_t ldl, int32_t C
                                      const int32_t* tok_cls, const int32_t* tok_win, const int32_t* gap_cls, int32_t n_clips,
                                      const int32_t* tok, void* workspace, int64_t workspace_bytes, float* logz, float* tok_post,
                                      float* start_mean, float* start_sd, int32_t* status, void* stream) {
-  return posterior_batch<true>("wfl_align_posterior_windowed", logits, ldl, C, o_id, frame_off_host, n_frames_host, tok_off_host,
-                               n_tok_host, tok_cls, tok_win, gap_cls, n_clips, tok, workspace, workspace_bytes, logz, tok_post, start_mean,
-                               start_sd, status, stream);
+  return posterior_batch<true, false>("wfl_align_posterior_windowed", logits, ldl, C, o_id, frame_off_host, n_frames_host, tok_off_host,
+                                      n_tok_host, tok_cls, tok_win, nullptr, gap_cls, n_clips, tok, workspace, workspace_bytes, logz,
+                                      tok_post, start_mean, start_sd, status, stream);
 }
 
 }  // extern "C"

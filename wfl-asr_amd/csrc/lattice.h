@@ -1,4 +1,4 @@
-// The forced-alignment lattice of wfl_align (csrc/align.hip, the max-product search), wfl_align_posterior (csrc/align_posterior.hip,
+// The forced-alignment lattice of wfl_align (csrc/align.hip, the max-product search), wfl_align_posterior (csrc/align_posterior.h,
 // the sum-product sweeps) and wfl_align_edits (csrc/align_edits.hip: the same sweeps once more, kept per frame, and from them the
 // score of every single substitution and deletion of the transcript, and wfl_align_insertions beside it: of every single insertion),
 // defined ONCE: a change made here reaches all of them, so the posterior and the edit scores always speak of the lattice the search
@@ -7,8 +7,9 @@
 //   device  caps and constants, the per-clip record, the wave reductions, the (threads, slots per thread) configurations and their
 //           dispatch, the shared part of the LDS layout, lattice setup (status 0 / 1 / 2 / 4, the alternatives in LDS, the gap classes in
 //           registers), the staged logits ring, the emission gathers, the start-window mask of the windowed entries (win_mask: ONE mask
-//           for the search and for both sweeps of the sums), the minimum-duration chain of wfl_align_min_duration, the two halves of
-//           the block-maximum renormalisation, the end states
+//           for the search and for both sweeps of the sums), the minimum-duration chain of wfl_align_min_duration (chain_out / chain_shift:
+//           the search and alpha) and its mirror for beta (chain_in / chain_shift_back: wfl_align_min_duration_posterior), the two
+//           halves of the block-maximum renormalisation, the end states
 //   host    the argument checks the ABI entries share, "group the clips by configuration, hand out workspace offsets, launch at most
 //           64 clips at a time", and the launch that reserves a kernel's dynamic LDS once per device
 //
@@ -169,6 +170,26 @@ static __device__ __forceinline__ void chain_shift(float (&h)[CHAIN], float b, f
 #pragma unroll
   for (int j = CHAIN - 1; j >= 1; --j) h[j] = j + 3 <= d ? h[j - 1] + ei : -INFINITY;
   h[0] = 3 <= d ? b + ei : -INFINITY;
+}
+
+// ---- the chain seen from behind (wfl_align_min_duration_posterior's beta): a delay line per slot, the mirror of h[].  c[e - 1] is beta of
+// the chain state that is e frames before I_k, e = 1 .. MAX_MIN_FRAMES - 1: H_k^j sits at e = D_k - j, B_k itself at e = D_k - 1.  The
+// shift needs no select on D_k (the entries past D_k - 1 are never read); the one select is chain_in, where B_k is read.
+constexpr int CHAIN_BACK = MAX_MIN_FRAMES - 1;
+
+// beta(B_k) of a frame: beta(I_k) of that frame where D_k == 1 (the same successors), the delay line's entry D_k - 1 elsewhere
+static __device__ __forceinline__ float chain_in(float bi, const float (&c)[CHAIN_BACK], int d) {
+  float b = bi;
+#pragma unroll
+  for (int j = 0; j < CHAIN_BACK; ++j) b = d == j + 2 ? c[j] : b;
+  return b;
+}
+
+// one frame back: beta_{t-1} of the state in front of I_k is beta_t(I_k) + EI_t, of every other chain state beta_t of its successor + EI_t
+static __device__ __forceinline__ void chain_shift_back(float (&c)[CHAIN_BACK], float bi, float ei) {
+#pragma unroll
+  for (int j = CHAIN_BACK - 1; j >= 1; --j) c[j] = c[j - 1] + ei;
+  c[0] = bi + ei;
 }
 
 // ---- lattice setup of a clip -> status: 2 over the cap (of the ABI or of this configuration), 1 fewer frames than tokens, 4 a class id

@@ -421,10 +421,11 @@ class Labeler:
 
     def label_files(self, audio_paths, lang_id=None, confidence_threshold=0.0, verbose=True, align=None, align_scores=None,
                     decode=None, switch_penalty=None, decode_scores=None, phoneme_bigram=None, bigram_weight=None, align_draft=None,
-                    draft_tolerance=None, align_edits=None, align_insertions=None, min_duration=None, bigram_scores=None):
-        """-> list (per file) of [(start_s, end_s, phoneme)] after merge + forced alignment; with align_scores, decode_scores or
-        bigram_scores, (that list, scores); with align_edits the tuple goes on with one more list, edits, and with align_insertions
-        it ends with one more, insertions.
+                    draft_tolerance=None, align_edits=None, align_insertions=None, min_duration=None, duration_scores=None,
+                    bigram_scores=None):
+        """-> list (per file) of [(start_s, end_s, phoneme)] after merge + forced alignment; with align_scores, duration_scores,
+        decode_scores or bigram_scores, (that list, scores); with align_edits the tuple goes on with one more list, edits, and with
+        align_insertions it ends with one more, insertions.
 
         align: "greedy" -- a `{audio}.txt` transcript is matched onto the freely decoded segments (infer.py:30-60, 312-319);
         "viterbi" -- files with a transcript are aligned by a search over their frame logits on the GPU (align.py: one segment
@@ -485,11 +486,17 @@ class Labeler:
         itself (align.viterbi_align's min_frames, align.min_frames_for: at most 8 frames).  Only transcript tokens are constrained,
         not the SP / AP of gaps, not the free decode.  It combines with align_draft; align_scores, align_edits and
         align_insertions beside it are refused (their passes score the lattice without durations).  A file whose durations no path
-        can meet falls back, with a message, to the alignment of the same transcript without them (the draft's windows kept)."""
+        can meet falls back, with a message, to the alignment of the same transcript without them (the draft's windows kept).
+
+        duration_scores (with a min_duration only; None: config postprocess.duration_scores, else off): align_scores for an
+        alignment under minimum durations -- the same scores[i] (align.FileScore), from align.duration_posteriors over the
+        minimum-duration lattice of the search, on the PackedClips it ran on.  A file whose durations were dropped is scored by
+        align.alignment_posteriors, over the lattice without them it was searched on, and one line says so."""
         opts = self.options(align=align, align_scores=align_scores, decode=decode, switch_penalty=switch_penalty,
                             decode_scores=decode_scores, phoneme_bigram=phoneme_bigram, bigram_weight=bigram_weight,
                             bigram_scores=bigram_scores, align_draft=align_draft, draft_tolerance=draft_tolerance,
-                            align_edits=align_edits, align_insertions=align_insertions, min_duration=min_duration)
+                            align_edits=align_edits, align_insertions=align_insertions, min_duration=min_duration,
+                            duration_scores=duration_scores)
         edits = {} if opts.align_edits else None
         insertions = {} if opts.align_insertions else None
         final, scores = self._label_scored(audio_paths, opts, lang_id, confidence_threshold, verbose, edits=edits,
@@ -544,7 +551,7 @@ class Labeler:
             inserted = {} if opts.align_insertions else None
             got = self._label_viterbi(paths(with_t), [forced[fi] for fi in with_t], lang_id, confidence_threshold, verbose,
                                       opts.align_scores, [drafts[fi] for fi in with_t], opts.draft_tolerance, moved, edited, inserted,
-                                      opts.min_duration)
+                                      opts.min_duration, opts.duration_scores)
             for fi, segs, sc in zip(with_t, *got):
                 final[fi], scores[fi] = segs, sc
             if moves is not None:
@@ -828,7 +835,7 @@ class Labeler:
         return total, total_logz, total_lse, n_frames, skipped
 
     def _label_viterbi(self, audio_paths, transcripts, lang_id, threshold, verbose, want_scores=False, drafts=None, tolerance=0.0,
-                       moves=None, edits=None, insertions=None, min_duration=None):
+                       moves=None, edits=None, insertions=None, min_duration=None, duration_scores=False):
         """Files with a transcript, align="viterbi".  Their chunks are forwarded with logits (kept on the device); the free decode of
         the same forward gives the greedy result, which the pause rule at the ends needs and which a file falls back to (with a
         message) when its transcript cannot be aligned.  Each file's chunks' valid logits rows are concatenated on the device, so
@@ -856,7 +863,12 @@ class Labeler:
         min_duration: PostOptions.min_duration (postprocess.min_duration) or None.  Every transcript token of every file gets its
         minimum frames (align.min_frames_for) and the batch goes through wfl_align_min_duration, the windows beside them.  A file
         whose durations no path can meet (align.windows_feasible with them, before the launch; status 1, after it) is searched
-        without them, with a message, its windows kept; the scoring passes never meet a min_duration (options rule 16)."""
+        without them, with a message, its windows kept; the scoring passes above never meet a min_duration (options rule 16).
+
+        duration_scores (postprocess.duration_scores, beside a min_duration): the scores of want_scores for this search.  The clips
+        that kept their durations are scored by align.duration_posteriors (wfl_align_min_duration_posterior) on the PackedClips of
+        the search -- packed again only where clips left the batch -- and the clips whose durations were dropped, which were
+        searched without them, by align.alignment_posteriors with their windows: every file gets the lattice it was searched on."""
         lang_name = self._lang_name(lang_id)
         remap, names = self._names_for(lang_name)
         results, scores = [], []
@@ -910,8 +922,9 @@ class Labeler:
                             print(f"{audio_paths[fi]}: {MIN_DURATION_INFEASIBLE}")
                 windows = wins if any(w is not None for w in wins) else None      # (no draft in the wave: the unwindowed entries)
                 min_frames = mins if any(d is not None for d in mins) else None   # (no duration in the wave: the entries without)
-                packed = (AL.pack_clips(lg, frames, [plans[fi] for fi in run], gaps, windows=windows)
-                          if want_scores or want_edits or want_ins else None)
+                packed = (AL.pack_clips(lg, frames, [plans[fi] for fi in run], gaps, windows=windows,
+                                        min_frames=min_frames if duration_scores else None)
+                          if want_scores or want_edits or want_ins or (duration_scores and min_frames is not None) else None)
                 d_ids, d_tok, d_score, d_st = AL.viterbi_align(lg, frames, [plans[fi] for fi in run], gaps, self.labels.index("O"),
                                                                packed=packed, windows=windows, min_frames=min_frames)
                 st_all = d_st.cpu().numpy()
@@ -976,8 +989,9 @@ class Labeler:
                     if want_ins:                              # (a clip's N + 1 places: one row more than its tokens)
                         raw_ins = scored_rows(AL.insertion_scores, AL.insertions_workspace_bytes, 1, "insertions",
                                               "wfl_align_insertions")
-                if want_scores and ok:
-                    d_post = AL.alignment_posteriors(lg, *sub, self.labels.index("O"), d_tok, frame_offsets=f0[ok], packed=packed)
+
+                def take_posteriors(ok, d_post, entry):
+                    """A scoring call's tensors for the clips `ok` -> raw / bad_post of their files, in one copy to the host."""
                     nt = sum(len(plans[run[b]]) for b in ok)
                     h = torch.cat([d_score[ok], *d_post[:4], d_post[4].to(torch.float32)]).cpu().numpy()      # one copy
                     n_ok = len(ok)
@@ -986,11 +1000,35 @@ class Labeler:
                     for j, b in enumerate(ok):
                         n = len(plans[run[b]])
                         if h_st[j] != AL.STATUS_OK:
-                            bad_post[run[b]] = int(h_st[j])
+                            bad_post[run[b]] = (entry, int(h_st[j]))
                         else:
                             raw[run[b]] = (h_score[j], h_logz[j]) + tuple(h[2 * n_ok + q * nt + k0:2 * n_ok + q * nt + k0 + n]
                                                                           for q in range(3))
                         k0 += n
+                if want_scores and ok:
+                    d_post = AL.alignment_posteriors(lg, *sub, self.labels.index("O"), d_tok, frame_offsets=f0[ok], packed=packed)
+                    take_posteriors(ok, d_post, "wfl_align_posterior")
+                if duration_scores and ok:
+                    # every clip on the lattice it was searched on: with its durations, or -- where they were dropped -- without
+                    for with_min in (True, False):
+                        part = [b for b in ok if (mins[b] is not None) == with_min]
+                        if not part:
+                            continue
+                        psub = ([frames[b] for b in part], [plans[run[b]] for b in part], [gaps[b] for b in part])
+                        pwin = [wins[b] for b in part]
+                        pwin = pwin if any(w is not None for w in pwin) else None
+                        if with_min:
+                            ppack = packed if packed is not None and len(part) == len(run) else AL.pack_clips(
+                                lg, *psub, f0[part], windows=pwin, min_frames=[mins[b] for b in part])
+                            d_post = AL.duration_posteriors(lg, *psub, self.labels.index("O"), d_tok, frame_offsets=f0[part],
+                                                            packed=ppack)
+                            take_posteriors(part, d_post, "wfl_align_min_duration_posterior")
+                        else:
+                            for b in part:
+                                print(f"{audio_paths[run[b]]}: {DURATION_SCORES_PLAIN}")
+                            d_post = AL.alignment_posteriors(lg, *psub, self.labels.index("O"), d_tok, frame_offsets=f0[part],
+                                                             packed=AL.pack_clips(lg, *psub, f0[part], windows=pwin))
+                            take_posteriors(part, d_post, "wfl_align_posterior")
                 pos = 0
                 for b, fi in enumerate(run):
                     n = frames[b]
@@ -1008,8 +1046,9 @@ class Labeler:
                             moves[fi] = draft_moves(drafts[fi], segs, tok_all[pos:pos + n], wins[b])
                         if fi in raw:
                             post[fi] = AL.file_score(raw[fi][0], raw[fi][1], n, *raw[fi][2:], segs, frame_duration)
-                        elif want_scores:                     # (wfl_align_posterior refused the path wfl_align gave it)
-                            print(f"{audio_paths[fi]}: no alignment scores (wfl_align_posterior status {bad_post.get(fi)})")
+                        elif want_scores or duration_scores:  # (the scoring entry refused the path the search gave it)
+                            entry, code = bad_post.get(fi, ("wfl_align_posterior", None))
+                            print(f"{audio_paths[fi]}: no alignment scores ({entry} status {code})")
                         if fi in raw_edits:
                             edits[fi] = AL.token_edits(raw_edits[fi], segs, sub_out)
                         if fi in raw_ins:
@@ -1035,6 +1074,8 @@ def _clip_lse(lg, starts, ends):
 
 MIN_DURATION_INFEASIBLE = ("no path gives every token its minimum duration (postprocess.min_duration: too many tokens for the frames, or "
                            "for the draft's windows); aligning the transcript without minimum durations")
+DURATION_SCORES_PLAIN = ("scored without minimum durations (postprocess.duration_scores: the file was searched without them, and a "
+                         "score speaks of the lattice its search ran on)")
 DRAFT_INFEASIBLE = ("no path opens every token inside its draft window (two starts on one frame, or more tokens than frames in between); "
                     "aligning the draft's transcript without windows")
 
@@ -1237,7 +1278,7 @@ def infer_audio(audio_path, config_path="config.yaml", checkpoint_path="best_mod
                 lang_id=None, sample=False, top_k=0, top_p=0.0, temperature=1.0, confidence_threshold=0.0, align=None,
                 align_scores=None, decode=None, switch_penalty=None, decode_scores=None, phoneme_bigram=None, bigram_weight=None,
                 align_draft=None, draft_tolerance=None, align_edits=None, align_insertions=None, min_duration=None,
-                bigram_scores=None):
+                duration_scores=None, bigram_scores=None):
     """align: "greedy" | "viterbi" | None (config postprocess.align, else greedy): how a `{audio}.txt` transcript is aligned
     (Labeler.label_files).  align_scores (viterbi only; None: config postprocess.align_scores): also write `{stem}.scores.tsv`
     beside the .lab when the file was Viterbi-aligned (format_scores_tsv).  decode: "argmax" | "viterbi" | None (config
@@ -1254,10 +1295,13 @@ def infer_audio(audio_path, config_path="config.yaml", checkpoint_path="best_mod
     postprocess.align_insertions): also write `{stem}.insertions.tsv` beside the .lab when the file was Viterbi-aligned: per place of
     the transcript the best and second-best phoneme to insert, their log likelihood ratios and a flag (align.write_insertions_tsv).
     min_duration (align viterbi only; None: config postprocess.min_duration): seconds, or {token name: seconds, "default": seconds}:
-    the least time a transcript token occupies in the search (Labeler.label_files)."""
+    the least time a transcript token occupies in the search (Labeler.label_files).  duration_scores (with a min_duration only; None:
+    config postprocess.duration_scores): align_scores for that search, the same `{stem}.scores.tsv`, summed over the
+    minimum-duration lattice (align.duration_posteriors)."""
     given = dict(align=align, align_scores=align_scores, decode=decode, switch_penalty=switch_penalty, decode_scores=decode_scores,
                  phoneme_bigram=phoneme_bigram, bigram_weight=bigram_weight, bigram_scores=bigram_scores, align_draft=align_draft,
-                 draft_tolerance=draft_tolerance, align_edits=align_edits, align_insertions=align_insertions, min_duration=min_duration)
+                 draft_tolerance=draft_tolerance, align_edits=align_edits, align_insertions=align_insertions, min_duration=min_duration,
+                 duration_scores=duration_scores)
     _refuse_before_load(config_path, **given)
     lab = _labeler(config_path, checkpoint_path, device)
     opts = lab.options(**given)
@@ -1282,10 +1326,11 @@ def infer_folder(folder_path: str, config_path: str = "config.yaml", checkpoint_
                  output_dir: str = "outputs", device: str = "cuda", lang_id: int = None, sample=False, top_k=0, top_p=0.0,
                  temperature=1.0, confidence_threshold=0.0, align=None, align_scores=None, decode=None, switch_penalty=None,
                  decode_scores=None, phoneme_bigram=None, bigram_weight=None, align_draft=None, draft_tolerance=None,
-                 align_edits=None, align_insertions=None, min_duration=None, bigram_scores=None):
+                 align_edits=None, align_insertions=None, min_duration=None, duration_scores=None, bigram_scores=None):
     given = dict(align=align, align_scores=align_scores, decode=decode, switch_penalty=switch_penalty, decode_scores=decode_scores,
                  phoneme_bigram=phoneme_bigram, bigram_weight=bigram_weight, bigram_scores=bigram_scores, align_draft=align_draft,
-                 draft_tolerance=draft_tolerance, align_edits=align_edits, align_insertions=align_insertions, min_duration=min_duration)
+                 draft_tolerance=draft_tolerance, align_edits=align_edits, align_insertions=align_insertions, min_duration=min_duration,
+                 duration_scores=duration_scores)
     _refuse_before_load(config_path, **given)
     wav_files = sorted(f for f in os.listdir(folder_path) if f.lower().endswith(".wav"))
     os.makedirs(output_dir, exist_ok=True)
@@ -1315,7 +1360,7 @@ def infer_folder(folder_path: str, config_path: str = "config.yaml", checkpoint_
         print("Predicted segments:")
         for start, end, ph in segments:
             print(f"({round(start, 2)}, {round(end, 2)}, {ph})")
-    if opts.align_scores:
+    if opts.align_scores or opts.duration_scores:
         name = "alignment_scores.tsv" if world == 1 else f"alignment_scores.rank{rank}.tsv"
         _write_text(os.path.join(output_dir, name),
                     format_review_tsv([(f, sc) for f, sc in zip(wav_files, all_scores) if isinstance(sc, AL.FileScore)]), "Review list")
@@ -1404,9 +1449,13 @@ def main(argv=None):
                   help="With --align viterbi: the least time a transcript token occupies, SECONDS for every token or NAME=SECONDS for "
                        "the tokens of that name (repeatable; a plain SECONDS beside named ones is their default). At most 0.16 s "
                        "(8 frames). Default: config postprocess.min_duration, else none.")
+    @click.option("--duration-scores", "duration_scores", is_flag=True, default=None,
+                  help="With --min-duration: --align-scores for the alignment under minimum durations; the same {stem}.scores.tsv "
+                       "and alignment_scores.tsv, from a forward-backward pass over the minimum-duration lattice on the GPU. Default: "
+                       "config postprocess.duration_scores, else off.")
     def cli(path, checkpoint, config, output, lang_id, sample, top_k, top_p, temperature, device, confidence_threshold, align,
             align_scores, decode, switch_penalty, decode_scores, phoneme_bigram, bigram_weight, bigram_scores, align_draft,
-            draft_tolerance, align_edits, align_insertions, min_duration):
+            draft_tolerance, align_edits, align_insertions, min_duration, duration_scores):
         if switch_penalty is not None and not switch_penalty >= 0.0:
             raise click.UsageError("--switch-penalty must be >= 0 (nats)")
         if sample:
@@ -1440,7 +1489,7 @@ def main(argv=None):
                            decode_scores=decode_scores, phoneme_bigram=phoneme_bigram, bigram_weight=bigram_weight,
                            bigram_scores=bigram_scores, align_draft=align_draft, draft_tolerance=draft_tolerance,
                            align_edits=align_edits, align_insertions=align_insertions,
-                           min_duration=parse_min_duration(min_duration))
+                           min_duration=parse_min_duration(min_duration), duration_scores=duration_scores)
         except ValueError as err:
             raise click.UsageError(str(err))
         output_path = inf_path if output == "." else output
@@ -1459,7 +1508,8 @@ def main(argv=None):
                   bigram_weight=opts.bigram_weight if opts.decode == "viterbi" else None,
                   # the draft travels the same way: an empty path for "none", a tolerance only beside a draft
                   align_draft=opts.align_draft or "", draft_tolerance=opts.draft_tolerance if opts.align_draft else None,
-                  align_edits=opts.align_edits, align_insertions=opts.align_insertions, min_duration=opts.min_duration)
+                  align_edits=opts.align_edits, align_insertions=opts.align_insertions, min_duration=opts.min_duration,
+                  duration_scores=opts.duration_scores)
         if inf_path.is_dir():
             infer_folder(folder_path=str(inf_path), output_dir=str(output_path), **kw)
         else:

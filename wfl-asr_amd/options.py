@@ -23,6 +23,9 @@ infer_folder (before any model is loaded) and the CLI all call `resolve` and car
                            16. align_scores, align_edits and align_insertions beside a min_duration are refused
                                (MIN_DURATION_SCORES_ERROR): their passes score the lattice without minimum durations, and a score must
                                speak of the lattice its search ran on
+  duration_scores off      17. needs align viterbi
+                           18. needs a min_duration (it scores the minimum-duration lattice; without durations align_scores is the
+                               option to ask for)
 """
 from __future__ import annotations
 
@@ -119,41 +122,48 @@ class PostOptions(_SearchOptions):
         draft_tolerance  0.1    seconds either side of a draft start (also stands for "not given")
         align_edits      False  score single substitutions and deletions of every aligned transcript
         align_insertions False  score single insertions at every place of every aligned transcript
-        min_duration     None   the least time a transcript token occupies: seconds, or ((name, seconds), ...) sorted by name"""
+        min_duration     None   the least time a transcript token occupies: seconds, or ((name, seconds), ...) sorted by name
+        duration_scores  False  score every alignment searched under a min_duration, over the minimum-duration lattice"""
     align_draft: Optional[str] = None
     draft_tolerance: float = DEFAULT_DRAFT_TOLERANCE
     align_edits: bool = False
     align_insertions: bool = False
     min_duration: object = None
+    duration_scores: bool = False
 
     def __new__(cls, *args, align_draft=None, draft_tolerance=DEFAULT_DRAFT_TOLERANCE, align_edits=False, align_insertions=False,
-                min_duration=None, **kw):
+                min_duration=None, duration_scores=False, **kw):
         self = super().__new__(cls, *args, **kw)
         object.__setattr__(self, "align_draft", align_draft)
         object.__setattr__(self, "draft_tolerance", draft_tolerance)
         object.__setattr__(self, "align_edits", align_edits)
         object.__setattr__(self, "align_insertions", align_insertions)
         object.__setattr__(self, "min_duration", min_duration)
+        object.__setattr__(self, "duration_scores", duration_scores)
         return self
 
     def __setattr__(self, name, value):
         raise AttributeError(f"PostOptions is read-only: cannot set {name!r}")
 
-    _KEYWORD = ("align_draft", "draft_tolerance", "align_edits", "align_insertions", "min_duration")
-    _KEYWORD_DEFAULTS = (None, DEFAULT_DRAFT_TOLERANCE, False, False, None)
+    _KEYWORD = ("align_draft", "draft_tolerance", "align_edits", "align_insertions", "min_duration", "duration_scores")
+    _KEYWORD_DEFAULTS = (None, DEFAULT_DRAFT_TOLERANCE, False, False, None, False)
 
     def _draft(self):
         return self.align_draft, self.draft_tolerance
 
+    @property
+    def scored(self) -> bool:
+        return self.align_scores or self.free_scores or self.duration_scores
+
     def _later(self):
-        return self.align_draft, self.draft_tolerance, self.align_edits, self.align_insertions, self.min_duration
+        return self.align_draft, self.draft_tolerance, self.align_edits, self.align_insertions, self.min_duration, self.duration_scores
 
     # the NamedTuple helpers carry the keyword fields as well (the inherited ones know the tuple alone)
     @classmethod
     def _make(cls, iterable, align_draft=None, draft_tolerance=DEFAULT_DRAFT_TOLERANCE, align_edits=False, align_insertions=False,
-              min_duration=None):
+              min_duration=None, duration_scores=False):
         return cls(*iterable, align_draft=align_draft, draft_tolerance=draft_tolerance, align_edits=align_edits,
-                   align_insertions=align_insertions, min_duration=min_duration)
+                   align_insertions=align_insertions, min_duration=min_duration, duration_scores=duration_scores)
 
     def _replace(self, **kw):
         later = {k: kw.pop(k, getattr(self, k)) for k in self._KEYWORD}
@@ -189,7 +199,7 @@ def _number_ge0(x):
 
 def resolve(post, *, align=None, align_scores=None, decode=None, switch_penalty=None, decode_scores=None, phoneme_bigram=None,
             bigram_weight=None, bigram_scores=None, align_draft=None, draft_tolerance=None, align_edits=None,
-            align_insertions=None, min_duration=None) -> PostOptions:
+            align_insertions=None, min_duration=None, duration_scores=None) -> PostOptions:
     """post: the config's `postprocess` mapping (None: {}).  Per option the argument wins; None leaves it to `post[<option>]`, and a
     key that is absent (or None) to the default.  -> PostOptions, or ValueError for the first broken rule of the module's table."""
     post = post or {}
@@ -258,6 +268,13 @@ def resolve(post, *, align=None, align_scores=None, decode=None, switch_penalty=
                          "the greedy match has none")
     if min_duration is not None and (align_scores or align_edits or align_insertions):
         raise ValueError(MIN_DURATION_SCORES_ERROR)
+    duration_scores = bool(pick("duration_scores", duration_scores, False))
+    if duration_scores and align != "viterbi":
+        raise ValueError("duration_scores needs align='viterbi' (postprocess.align: viterbi) and a min_duration: the greedy match has "
+                         "no lattice to score")
+    if duration_scores and min_duration is None:
+        raise ValueError("duration_scores needs a min_duration (postprocess.min_duration): it scores the minimum-duration lattice of "
+                         "that search; without durations align_scores is the option to ask for")
     return PostOptions(align, align_scores, decode, switch_penalty, decode_scores, phoneme_bigram, bigram_weight, bigram_scores,
                        align_draft=align_draft, draft_tolerance=draft_tolerance, align_edits=align_edits,
-                       align_insertions=align_insertions, min_duration=min_duration)
+                       align_insertions=align_insertions, min_duration=min_duration, duration_scores=duration_scores)
