@@ -141,10 +141,14 @@ __global__ __launch_bounds__(256) void attn_kernel(AttnArgs p) {
   // accumulated like an output tile (osum[qt][0] of lanes g == 0), over the same bf16-rounded P as the numerator.
   constexpr float RESCALE_THR = 8.0f;
   f32x4 o[QT][DT], osum[QT];
-  float negm[QT];                        // minus the reference of query tile qt (one value per lane's query: the accumulators start from it)
+  // minus the reference of query tile qt (one value per lane's query), four times over: the C operand of the first score MFMA of every
+  // (qt, kk) of a tile.  An MFMA reads C from any four registers, so the 4 QT score accumulators need no initialising (they used to be
+  // set to -mref on every tile; the steady loop of the head_dim 64, QT = 4 kernel has 99 vector instructions beside its 32 score MFMAs
+  // instead of 111); these registers change only on a rescale.
+  f32x4 negm[QT];
 #pragma unroll
   for (int qt = 0; qt < QT; ++qt) {
-    negm[qt] = 0.f;
+    negm[qt] = (f32x4){0.f, 0.f, 0.f, 0.f};
     osum[qt] = (f32x4){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int dt = 0; dt < DT; ++dt) o[qt][dt] = (f32x4){0.f, 0.f, 0.f, 0.f};
@@ -303,10 +307,6 @@ __global__ __launch_bounds__(256) void attn_kernel(AttnArgs p) {
     // ---- S^T = K . Q^T : st[qt][kk][e] = score(query q0+16qt+c, key 64kt + 16kk + 4g + e)
     f32x4 st[QT][4];
 #pragma unroll
-    for (int qt = 0; qt < QT; ++qt)
-#pragma unroll
-      for (int kk = 0; kk < 4; ++kk) st[qt][kk] = (f32x4){negm[qt], negm[qt], negm[qt], negm[qt]};
-#pragma unroll
     for (int ks = 0; ks < KS; ++ks) {
 #pragma unroll
       for (int kk = 0; kk < 4; ++kk) {
@@ -318,7 +318,7 @@ __global__ __launch_bounds__(256) void attn_kernel(AttnArgs p) {
 #endif
 #pragma unroll
         for (int qt = 0; qt < QT; ++qt)
-          st[qt][kk] = attn_mfma(kf, qf[qt][ks], st[qt][kk]);
+          st[qt][kk] = attn_mfma(kf, qf[qt][ks], ks == 0 ? negm[qt] : st[qt][kk]);     // (ks == 0: the sum starts at -mref)
         if (SPLIT) {
           const bf16x8 kfl = *(const bf16x8*)(Ks + TILE1 + r * (HD * 2) + (((ks * 4 + g) ^ k_swz<HD>(r)) << 4));
 #pragma unroll

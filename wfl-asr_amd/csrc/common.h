@@ -83,6 +83,8 @@ struct GemmArgs {
   int out_f32;
   const float* ln_s;        // LayerNorm folded in front of the GEMM (gemm_stream.hip): s[n] = sum_k W'[n][k], W' = gamma o W,
   float ln_eps;             //   bias = b + W beta;  out = rstd_m * (acc - mean_m * s[n]) + bias[n];  statistics over the K columns
+  int ln_k_pow2;            //   set by the launcher: K is a power of two, and then ln_inv_k = 1 / K exactly (x * ln_inv_k == x / K bit for bit)
+  float ln_inv_k;
   float* stats_out;         // residual launches (gemm_stream.hip): per output row, per 256-column tile, (sum, sum of squares) of
                             //   the bf16-rounded outputs: stats_out[(row * 4 + tile) * 2 + {0, 1}], row = the C row index, N <= 1024
   const float* stats_in;    // with ln_s: take the row statistics from a producer's stats_out (row = A row m + stats_lead)
@@ -255,6 +257,22 @@ static __device__ __forceinline__ float gelu_erf(float x) {
   q = fmaf(q, t, -1.150787711e+00f);
   q = fmaf(q, t, -1.000037670e+00f);
   return fmaxf(x, 0.f) - t * __builtin_amdgcn_exp2f(q);
+}
+// the same value for two arguments at a time, written on a 2-vector so that the FMAs come out as v_pk_fma_f32 (each lane of a packed
+// FMA is the IEEE fma the scalar form issues: bit-identical)
+typedef __attribute__((ext_vector_type(2))) float f32x2;
+static __device__ __forceinline__ f32x2 gelu_erf2(f32x2 x) {
+  const f32x2 t = {fabsf(x[0]), fabsf(x[1])};
+  const f32x2 c5 = -4.732937668e-04f, c4 = 7.084457669e-03f, c3 = -5.182715505e-02f, c2 = -4.599926770e-01f, c1 = -1.150787711e+00f,
+              c0 = -1.000037670e+00f;
+  f32x2 q = __builtin_elementwise_fma(c5, t, c4);
+  q = __builtin_elementwise_fma(q, t, c3);
+  q = __builtin_elementwise_fma(q, t, c2);
+  q = __builtin_elementwise_fma(q, t, c1);
+  q = __builtin_elementwise_fma(q, t, c0);
+  const f32x2 e = {__builtin_amdgcn_exp2f(q[0]), __builtin_amdgcn_exp2f(q[1])};
+  const f32x2 m = {fmaxf(x[0], 0.f), fmaxf(x[1], 0.f)};
+  return __builtin_elementwise_fma(-t, e, m);
 }
 static __device__ __forceinline__ float sigmoidf_(float x) { return 1.0f / (1.0f + __expf(-x)); }
 

@@ -27,6 +27,13 @@
 // The K loop itself is bound by the L2 -> LDS operand DMA (28 KiB per 32-deep step of a 192 x 256 tile; ~65 GB/s per CU) next
 // to 24 MFMAs per wave: tools/gemm_lab.py's ablations give 0.40 us per step for the MFMAs alone, 0.45-0.50 us for the DMA
 // alone and 0.59-0.64 us for the real loop.
+// What the epilogue costs (tools/gemm_lab.py, stamps 3 -> 4: the final copy alone, 16 x 1500 frames; profiles/epilogue_diet_*_gemm_lab.txt;
+// the in-loop copy is the same code at a tile boundary, where the accumulators it reads keep the wave's MFMAs waiting): 3.1 us per tile
+// for bias + GELU (96 outputs per lane, ~1 100 vector instructions, 40 % of them the GELU polynomial), 3.9 us for the conv mode while it
+// also sent an unwanted low half to the scratch line, 8.7-9.9 us for the residual forms, which wait for their residual loads behind the
+// operand DMA.  Trimmed since, every stored value unchanged: the GELU polynomial runs on pairs of outputs (gelu_erf2, v_pk_fma_f32:
+// 2.6 us), 1 / P is one v_rcp_f32, the statistics' divisions by K are products when K is a power of two, and a conv launch without a
+// low-half buffer neither computes nor stores one (template NOLO: 2.5 us).  DESIGN.md section 4, "Vector-ALU work the result does not need".
 #include "common.h"
 #include <cstdlib>
 #include <cstring>
@@ -87,8 +94,11 @@ static __device__ __forceinline__ void wait_vm() { asm volatile("s_waitcnt vmcnt
 //   first form -- 32-byte rows, half-size stages -- kept the 24-MFMA step and its barrier overhead: 0.60 us per 32 k's against 0.79
 //   for W8 and ~0.45 now.)  The scales (per output channel, per frame row) multiply the accumulator in the epilogue.
 //   OUT8: the epilogue writes e4m3 (GemmArgs::c8) instead of bf16 -- fc1's GELU output, the next GEMM's fp8 operand.
-template <int ACT, int MT, bool RES, int LNF, bool STATS, bool CONV, bool W8 = false, bool A8 = false, bool OUT8 = false>
+// NOLO: a CONV launch without a low-half buffer (GemmArgs::c_lo == null: every conv of the default precision) -- the low half is neither
+//   computed nor sent to the scratch line: 12 fewer 16-byte stores per wave and tile, and the second conversion with them.
+template <int ACT, int MT, bool RES, int LNF, bool STATS, bool CONV, bool W8 = false, bool A8 = false, bool OUT8 = false, bool NOLO = false>
 __global__ __launch_bounds__(512) void gemm_stream_kernel(GemmArgs p) {
+  static_assert(!NOLO || CONV, "only the conv mode has an optional low half");
   static_assert(!CONV || (MT == 6 && !RES && LNF == 0 && !STATS), "conv mode: 192-row tiles, plain epilogue");
   static_assert(!W8 || (!CONV && MT == 6), "fp8 weights: plain 192-row mode");
   static_assert(!A8 || (!W8 && !CONV && MT == 6 && LNF == 0 && !STATS), "fp8 x fp8: the plain 192-row mode, no LayerNorm folding");
@@ -103,7 +113,7 @@ __global__ __launch_bounds__(512) void gemm_stream_kernel(GemmArgs p) {
 #endif
   constexpr int AEXT = 224 * SBK * 2;             // CONV: extended frame tile (BMV + up to 32 taps - 1 rows), two of them
   constexpr int AOFF = SNST * STB;
-  constexpr bool LOUT = RES || CONV;                  // epilogues that can write a low half (CONV: "model.precision: high" convs, c_lo without a residual)
+  constexpr bool LOUT = RES || (CONV && !NOLO);       // epilogues that write a low half (CONV: "model.precision: high" convs, c_lo without a residual)
   constexpr int NSTORE = (LOUT ? 4 : 2) * MT + (STATS ? MT : 0);   // epilogue stores per wave (never branched around; a residual
                                                                   // launch always stores the hi and the lo half)
   constexpr int SROW = 4;                             // float2 slots per row of the statistics buffer (one per 256-column tile)
@@ -338,7 +348,9 @@ __global__ __launch_bounds__(512) void gemm_stream_kernel(GemmArgs p) {
     }
     int P_ = p.P, cpitch = p.c_pitch;               // opaque too: 1 / P would otherwise be kept across the K loop
     asm volatile("" : "+s"(P_), "+s"(cpitch));
-    const float invP = 1.0f / (float)P_;
+    // v_rcp_f32 (1 ulp) instead of the IEEE division (a dozen instructions): the quotient below is only a first guess for m / P, put
+    // right by the +-1 corrections, which hold for any reciprocal as long as m * 2^-22 < 1/2 (two million rows)
+    const float invP = __builtin_amdgcn_rcpf((float)P_);
     int orow[MT];                                   // output row index, or -1 for rows that are not stored
 #pragma unroll
     for (int u = 0; u < MT; ++u) {
@@ -410,9 +422,13 @@ __global__ __launch_bounds__(512) void gemm_stream_kernel(GemmArgs p) {
         if (p.stats_nsl > 1) { a1 += sp[u][0][2]; a2 += sp[u][0][3]; }
         if (p.stats_nsl > 2) { a1 += sp[u][1][0]; a2 += sp[u][1][1]; }
         if (p.stats_nsl > 3) { a1 += sp[u][1][2]; a2 += sp[u][1][3]; }
-        const float mean = a1 / (float)p.K;
+        // K a power of two (every model width but Whisper-tiny's and -small's): the product with 1 / K is the quotient, bit for bit,
+        // and replaces two IEEE divisions (two dozen instructions) per 16-frame tile; any other K divides as before
+        float mean, ex2;
+        if (p.ln_k_pow2) { mean = a1 * p.ln_inv_k; ex2 = a2 * p.ln_inv_k; }
+        else { mean = a1 / (float)p.K; ex2 = a2 / (float)p.K; }
         mu[u] = mean;
-        rs[u] = rsqrtf(fmaxf(a2 / (float)p.K - mean * mean, 0.f) + p.ln_eps);
+        rs[u] = rsqrtf(fmaxf(__builtin_fmaf(-mean, mean, ex2), 0.f) + p.ln_eps);
       }
     }
     char* trash = (char*)p.trash + lane * 16;
@@ -437,6 +453,14 @@ __global__ __launch_bounds__(512) void gemm_stream_kernel(GemmArgs p) {
             if (W8 || A8) v *= cj[2 * h + q][e];
             if (A8) v *= sa[u];
             if (LNF) v = (v - mu[u] * sj[2 * h + q][e]) * rs[u];
+            if (ACT == WFL_ACT_GELU) {               // two outputs at a time: gelu_erf2's packed FMAs (a residual never comes with an activation)
+              x[4 * q + e] = v + bj[2 * h + q][e];
+              if (e & 1) {
+                const f32x2 y = gelu_erf2((f32x2){x[4 * q + e - 1], x[4 * q + e]});
+                x[4 * q + e - 1] = y[0]; x[4 * q + e] = y[1];
+              }
+              continue;
+            }
             v = apply_act<ACT>(v + bj[2 * h + q][e]);
             if (RES) v = (bf2f(rr[u % RING][h][4 * q + e]) + lo_scale * bf2f(rl[u % RING][h][4 * q + e])) + p.alpha * v;
             x[4 * q + e] = v;
@@ -700,7 +724,7 @@ __global__ __launch_bounds__(512) void gemm_stream_kernel(GemmArgs p) {
 #undef SSB
 }
 
-template <int ACT, int MT, bool RES, int LNF, bool STATS, bool CONV = false, bool W8 = false, bool A8 = false, bool OUT8 = false>
+template <int ACT, int MT, bool RES, int LNF, bool STATS, bool CONV = false, bool W8 = false, bool A8 = false, bool OUT8 = false, bool NOLO = false>
 static int launch_stream(const GemmArgs& a, hipStream_t s) {
   constexpr int BMV = MT * 32;
 #ifdef WFL_LAB_STB32
@@ -709,7 +733,7 @@ static int launch_stream(const GemmArgs& a, hipStream_t s) {
   constexpr int lds = (CONV ? SNST * 256 * SBK * 2 + 2 * 224 * SBK * 2 : SNST * (BMV * SBK * 2 + 256 * SBK * (W8 ? 1 : 2))) + 8 * (MT * 16) * 2 * 4 + 64;
 #endif
   const int tiles = ((a.M + BMV - 1) / BMV) * (a.N / 256);
-  auto k = gemm_stream_kernel<ACT, MT, RES, LNF, STATS, CONV, W8, A8, OUT8>;
+  auto k = gemm_stream_kernel<ACT, MT, RES, LNF, STATS, CONV, W8, A8, OUT8, NOLO>;
   static WflOncePerDevice attr_once;
   if (attr_once.need()) {
     if (hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess) return -2;
@@ -791,6 +815,8 @@ int wfl_launch_gemm_stream(const GemmArgs& a, hipStream_t s) {
   }
   GemmArgs g = a;
   g.trash = trash[dev];
+  g.ln_k_pow2 = (g.K & (g.K - 1)) == 0;
+  g.ln_inv_k = g.ln_k_pow2 ? 1.0f / (float)g.K : 0.f;
   if (g.a8) {
     // fp8 x fp8 (BASELINE configs[4]): q|k|v (plain), out_proj / fc2 (residual hi + lo), fc1 (GELU, e4m3 out).  The kernel sees both
     // byte matrices as bf16 matrices of half the width (the note at the kernel): K, cin and lda in 2-byte units.
@@ -832,6 +858,14 @@ int wfl_launch_gemm_stream(const GemmArgs& a, hipStream_t s) {
     return 1;
   }
   if (wfl_gemm_stream_conv(g)) {
+    if (!g.c_lo) {                                     // no low half asked for: the instantiation that does not compute one
+      switch (g.act) {
+        case WFL_ACT_NONE: return launch_stream<WFL_ACT_NONE, 6, false, 0, false, true, false, false, false, true>(g, s);
+        case WFL_ACT_GELU: return launch_stream<WFL_ACT_GELU, 6, false, 0, false, true, false, false, false, true>(g, s);
+        case WFL_ACT_RELU: return launch_stream<WFL_ACT_RELU, 6, false, 0, false, true, false, false, false, true>(g, s);
+      }
+      return 1;
+    }
     switch (g.act) {
       case WFL_ACT_NONE: return launch_stream<WFL_ACT_NONE, 6, false, 0, false, true>(g, s);
       case WFL_ACT_GELU: return launch_stream<WFL_ACT_GELU, 6, false, 0, false, true>(g, s);

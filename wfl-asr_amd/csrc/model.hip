@@ -38,6 +38,9 @@ int wfl_launch_relpos_table(const float* rel_emb, const int* bucket_of_delta, in
 int wfl_launch_layernorm_act(const bf16_t* x, long ldx, bf16_t* y, long ldy, const float* g, const float* b, float eps, long lead,
                              int B, int P, int T, int C, int gelu, hipStream_t s, const bf16_t* x_lo = nullptr, bf16_t* y_lo = nullptr,
                              int n_div = 0, const int* clip_T = nullptr);
+int wfl_launch_layernorm_pair(const bf16_t* x, const bf16_t* x_lo, bf16_t* y1, bf16_t* y1_lo, bf16_t* y2, bf16_t* y2_lo, long ld,
+                              const float* g1, const float* b1, const float* g2, const float* b2, float eps, long lead, int B, int P,
+                              int T, int C, int n_div, const int* clip_T, hipStream_t s);
 int wfl_lstm_units_per_wg(int H);
 long wfl_lstm_exchange_bytes(int H, int B);
 bool wfl_lstm_split_precision_supported(int H);
@@ -1473,6 +1476,23 @@ struct Runner {
     if (r) rc = fail(r, "layernorm launch failed");
   }
 
+  // y1 = LN_w1(x) kept as a residual-stream tensor (hi + lo), y2 = LN_w2(y1): what ln(x, y1, w1, true); ln(y1, y2, w2) compute, bit for
+  // bit, in one launch and one pass over the rows (norm.hip, layernorm_pair_kernel).  y2 may be x.
+  void ln_pair(const bf16_t* x, bf16_t* y1, const LNp& w1, bf16_t* y2, const LNp& w2) {
+    if (rc) return;
+    if (y1 == stats_for || y2 == stats_for) stats_for = nullptr;
+    const bf16_t* x_lo = lo_in(x);
+    bf16_t* y1_lo = lo_of(y1);
+    bf16_t* y2_lo = precise() ? lo_of(y2) : nullptr;
+    mark_lo(y1, y1_lo != nullptr);
+    mark_lo(y2, y2_lo != nullptr);
+    prof_begin();
+    const int r = wfl_launch_layernorm_pair(x, x_lo, y1, y1_lo, y2, y2_lo, p.d, w1.g, w1.b, w2.g, w2.b, 1e-5f, p.lead, p.B, p.P, p.T, p.d,
+                                            m->dv, clipT, s);
+    prof_end(PROF_LAYERNORM, 0.0);
+    if (r) rc = fail(r, "layernorm launch failed");
+  }
+
   // Timing hook: prof_begin() takes the next event pair (created on demand) and records its first event, prof_end() records the second
   // and books the launch under its key -- a GEMM variant's (launch_timed) or a PROF_* family's
   hipEvent_t prof_e1 = nullptr;
@@ -1970,9 +1990,8 @@ static int run_head(Runner& R, const int32_t* lang_id, int32_t lang_mode, float 
         R.attn(a.conformer_heads, nullptr, nullptr, true);
         R.gemm(R.rows(BUF_ATTP), p.da, C.out, rows, R.out(S, d), {.res = H, .ldres = d});
       }
-      R.ln(S, H, C.ln1, true);
-      // x = x + pw2(GELU(BN(conv_k(GLU(pw1(LN2(x)))))))
-      R.ln(H, S, C.ln2);
+      // ... and LN2(x) for the conv module in the same pass: x = x + pw2(GELU(BN(conv_k(GLU(pw1(LN2(x)))))))
+      R.ln_pair(S, H, C.ln1, S, C.ln2);
       R.gemm(R.rows(S, d), d, C.pw1, rows, R.out(ATT, d), {.glu = true});
       // dense k-tap conv: taps are adjacent rows (cin = d, tap stride = one row) -> the streaming GEMM's tap-stationary mode
       R.gemm(ATT + (long)(p.lead - a.conformer_kernel / 2) * d, d, C.conv, rows, R.out(S, d),

@@ -105,6 +105,109 @@ int wfl_launch_layernorm_act(const bf16_t* x, long ldx, bf16_t* y, long ldy, con
               : launch_ln<false>(x, ldx, y, ldy, g, b, eps, lead, B, P, T, C, s, x_lo, y_lo, n_div, clip_T);
 }
 
+// Two LayerNorms in a row, y1 = LN1(x) and y2 = LN2(y1), in one pass over the rows (the Conformer block: x = LN1(x + MHA(x)) feeds
+// LN2 in front of the conv module; the reference model.py:27-28).  The second one normalises what the first one STORED -- bf16(y1), plus
+// the low half when one is kept, rebuilt exactly as layernorm_kernel reads them -- with the same order of additions, so y1 and y2 are
+// bit for bit what two launches of layernorm_kernel write; the row is read once and y1 is not read back.  y2 may be x (the block's
+// scratch buffer): a wave has its whole row in registers before it stores anything.
+template <int NCH>
+__global__ __launch_bounds__(256) void layernorm_pair_kernel(const bf16_t* x, const bf16_t* x_lo, bf16_t* y1, bf16_t* y1_lo, bf16_t* y2,
+                                                             bf16_t* y2_lo, long ld, const float* __restrict__ gam1,
+                                                             const float* __restrict__ bet1, const float* __restrict__ gam2,
+                                                             const float* __restrict__ bet2, float eps, long lead, int B, int P, int T,
+                                                             int C, int n_div, const int* __restrict__ clip_T) {
+  const int lane = threadIdx.x & 63;
+  const long r = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (r >= (long)B * T) return;
+  const int b = (int)(r / T), t = (int)(r - (long)b * T);
+  if (clip_T && t >= clip_T[b]) return;
+  const long row = lead + (long)b * P + t;
+  float v[NCH][8];
+  float sum = 0.f;
+#pragma unroll
+  for (int i = 0; i < NCH; ++i) {
+    const int c0 = (i * 64 + lane) * 8;
+    if (c0 < C) {
+      const bf16x8 a = *(const bf16x8*)(x + row * ld + c0);
+      if (x_lo) {
+        const bf16x8 al = *(const bf16x8*)(x_lo + row * ld + c0);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) { v[i][e] = bf2f(a[e]) + bf2f(al[e]); sum += v[i][e]; }
+      } else {
+#pragma unroll
+        for (int e = 0; e < 8; ++e) { v[i][e] = bf2f(a[e]); sum += v[i][e]; }
+      }
+    } else {
+#pragma unroll
+      for (int e = 0; e < 8; ++e) v[i][e] = 0.f;
+    }
+  }
+#pragma unroll
+  for (int pass = 0; pass < 2; ++pass) {
+    const float* gam = pass ? gam2 : gam1;
+    const float* bet = pass ? bet2 : bet1;
+    bf16_t* yp = (pass ? y2 : y1) + row * ld;
+    bf16_t* ylp = pass ? y2_lo : y1_lo;
+#pragma unroll
+    for (int s = 32; s >= 1; s >>= 1) sum += __shfl_xor(sum, s);
+    const float mean = sum / (float)n_div;
+    float sq = 0.f;
+#pragma unroll
+    for (int i = 0; i < NCH; ++i) {
+      const int c0 = (i * 64 + lane) * 8;
+      if (c0 < C) {
+#pragma unroll
+        for (int e = 0; e < 8; ++e) { const float d = v[i][e] - mean; sq += d * d; }
+      }
+    }
+#pragma unroll
+    for (int s = 32; s >= 1; s >>= 1) sq += __shfl_xor(sq, s);
+    if (n_div != C) sq -= (float)(C - n_div) * mean * mean;
+    const float rstd = rsqrtf(fmaxf(sq, 0.f) / (float)n_div + eps);
+    sum = 0.f;
+#pragma unroll
+    for (int i = 0; i < NCH; ++i) {
+      const int c0 = (i * 64 + lane) * 8;
+      if (c0 < C) {
+        const f32x4 g0 = *(const f32x4*)(gam + c0), g1 = *(const f32x4*)(gam + c0 + 4);
+        const f32x4 b0 = *(const f32x4*)(bet + c0), b1 = *(const f32x4*)(bet + c0 + 4);
+        bf16x8 o, ol;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          const float y0 = (v[i][e] - mean) * rstd * g0[e] + b0[e];
+          const float y1v = (v[i][4 + e] - mean) * rstd * g1[e] + b1[e];
+          o[e] = f2bf(y0);
+          o[4 + e] = f2bf(y1v);
+          ol[e] = f2bf(y0 - bf2f(o[e]));
+          ol[4 + e] = f2bf(y1v - bf2f(o[4 + e]));
+        }
+        *(bf16x8*)(yp + c0) = o;
+        if (ylp) *(bf16x8*)(ylp + row * ld + c0) = ol;
+        if (pass == 0) {                     // the second LayerNorm's input: the stored row, summed in layernorm_kernel's order
+#pragma unroll
+          for (int e = 0; e < 8; ++e) { v[i][e] = ylp ? bf2f(o[e]) + bf2f(ol[e]) : bf2f(o[e]); sum += v[i][e]; }
+        }
+      }
+    }
+  }
+}
+
+int wfl_launch_layernorm_pair(const bf16_t* x, const bf16_t* x_lo, bf16_t* y1, bf16_t* y1_lo, bf16_t* y2, bf16_t* y2_lo, long ld,
+                              const float* g1, const float* b1, const float* g2, const float* b2, float eps, long lead, int B, int P,
+                              int T, int C, int n_div, const int* clip_T, hipStream_t s) {
+  if (C % 8 || ld % 8 || C > 2048 || n_div < 0 || n_div > C || y1 == x || y1 == y2 || (y1_lo && (y1_lo == x_lo || y1_lo == y2_lo))) return -1;
+  if (n_div == 0) n_div = C;
+  const long rows = (long)B * T;
+  const dim3 grid((unsigned)((rows + 3) / 4));
+  if (C <= 512)
+    hipLaunchKernelGGL((layernorm_pair_kernel<1>), grid, dim3(256), 0, s, x, x_lo, y1, y1_lo, y2, y2_lo, ld, g1, b1, g2, b2, eps, lead, B, P, T, C, n_div, clip_T);
+  else if (C <= 1024)
+    hipLaunchKernelGGL((layernorm_pair_kernel<2>), grid, dim3(256), 0, s, x, x_lo, y1, y1_lo, y2, y2_lo, ld, g1, b1, g2, b2, eps, lead, B, P, T, C, n_div, clip_T);
+  else
+    hipLaunchKernelGGL((layernorm_pair_kernel<4>), grid, dim3(256), 0, s, x, x_lo, y1, y1_lo, y2, y2_lo, ld, g1, b1, g2, b2, eps, lead, B, P, T, C, n_div, clip_T);
+  return hipGetLastError() == hipSuccess ? 0 : -3;
+}
+
 int wfl_launch_layernorm(const bf16_t* x, long ldx, bf16_t* y, long ldy, const float* g, const float* b, float eps,
                          long lead, int B, int P, int T, int C, hipStream_t s) {
   return wfl_launch_layernorm_act(x, ldx, y, ldy, g, b, eps, lead, B, P, T, C, 0, s, nullptr, nullptr, 0, nullptr);
