@@ -6,6 +6,9 @@ posteriors: a missed, inserted or mislabelled phoneme shifts every later token o
 the frame logits for the best path that spells exactly the transcript, in order (csrc/align.hip, include/wfl_asr.h `wfl_align`): every
 token gets one contiguous, time-ordered run of frames, none is dropped.
 
+  _call                 the one call path of the eight entries below: workspace, argument order, stream, check (as decode._call)
+  AlignBatch            a wave's ragged batch as the Labeler holds it: `windows` / `min_frames`, `select`, `pack`, `args`
+  reuses_packed         whether a scoring call runs on the search's PackedClips or on tables packed again for its clips
   viterbi_align         the C ABI on CUDA tensors: a ragged batch of clips in one call; with `windows`, every token may open only
                         inside its (lo, hi) frame window (`wfl_align_windowed`, `postprocess.align_draft`); with `min_frames`,
                         every token occupies at least that many frames (`wfl_align_min_duration`, `postprocess.min_duration`)
@@ -58,14 +61,33 @@ MAX_SUBSTITUTES = 512      # wfl_align_edits' table cap
 EDITS_WORKSPACE_LIMIT = 1 << 30
 
 
-def workspace_bytes(n_frames, n_tokens) -> int:
-    lib = _lib.load()
+def _workspace_bytes(symbol, n_frames, n_tokens) -> int:
     T = np.ascontiguousarray(n_frames, np.int32)
     N = np.ascontiguousarray(n_tokens, np.int32)
-    n = int(lib.wfl_align_workspace_bytes(_hp(T), _hp(N), T.size))
+    n = int(getattr(_lib.load(), symbol)(_hp(T), _hp(N), T.size))
     if n < 0:
-        raise _lib.WflError("wfl_align_workspace_bytes: negative frame or token count")
+        raise _lib.WflError(f"{symbol}: negative frame or token count")
     return n
+
+
+def workspace_bytes(n_frames, n_tokens) -> int:
+    return _workspace_bytes("wfl_align_workspace_bytes", n_frames, n_tokens)
+
+
+def posterior_workspace_bytes(n_frames, n_tokens) -> int:
+    return _workspace_bytes("wfl_align_posterior_workspace_bytes", n_frames, n_tokens)
+
+
+def duration_posterior_workspace_bytes(n_frames, n_tokens) -> int:
+    return _workspace_bytes("wfl_align_min_duration_posterior_workspace_bytes", n_frames, n_tokens)
+
+
+def edits_workspace_bytes(n_frames, n_tokens) -> int:
+    return _workspace_bytes("wfl_align_edits_workspace_bytes", n_frames, n_tokens)
+
+
+def insertions_workspace_bytes(n_frames, n_tokens) -> int:
+    return _workspace_bytes("wfl_align_insertions_workspace_bytes", n_frames, n_tokens)
 
 
 def _pack_clips(logits, n_frames, token_classes, gap_classes, frame_offsets):
@@ -162,6 +184,121 @@ def pack_clips(logits, n_frames, token_classes, gap_classes, frame_offsets=None,
     return PackedClips(nb, T, N, F0, K0, torch.from_numpy(tc).to(logits.device), torch.from_numpy(gc).to(logits.device), d_win, d_min)
 
 
+def _any_or_none(per_clip):
+    """Per-clip constraints -> the list, its Nones included, or None when no clip has any (the entries without them)."""
+    return per_clip if any(x is not None for x in per_clip) else None
+
+
+def reuses_packed(packed, n_clips, n_selected, with_min) -> bool:
+    """Whether a scoring call over `n_selected` of a batch's `n_clips` clips runs on `packed`, the PackedClips that batch is held in
+    (None: it has none), or on tables packed again for the selection.  with_min: the call is duration_posteriors, over the lattice
+    with minimum durations.  The tables must hold exactly the call's clips and the call's lattice:
+
+      packed             selected    with_min  ->
+      None               any         any       pack again (the search packed for itself, or a fallback round dropped constraints)
+      without durations  every clip  False     reuse      (posteriors, edits, insertions when the search aligned every clip; an edit
+                                                           group that holds every aligned clip)
+      without durations  some clips  False     pack again (clips left the batch with a status, or into another edit group)
+      with durations     every clip  True      reuse      (every clip kept its durations)
+      with durations     some clips  True      pack again
+      with durations     any         False     pack again (clips that lost their durations: alignment_posteriors refuses a d_min)
+      without durations  any         True      pack again (duration_posteriors refuses tables without a d_min)"""
+    return packed is not None and n_selected == n_clips and (packed.d_min is not None) == bool(with_min)
+
+
+class AlignBatch(NamedTuple):
+    """A ragged batch as the Labeler holds it between the stages of a wave: the arguments of viterbi_align and the scoring calls,
+    clip by clip.  Only pack needs the library and a GPU."""
+    lg: object            # the wave's logits [rows, C]
+    frames: list          # frames per clip
+    f0: np.ndarray        # first row of each clip
+    alts: list            # per clip its tokens' alternatives (token_alternatives)
+    gaps: list            # per clip its gap classes
+    wins: list            # per clip its tokens' start windows; None: none (open)
+    mins: list            # per clip its tokens' minimum frames; None: none (all 1)
+    o_id: int
+
+    @classmethod
+    def of(cls, lg, frames, alts, gaps, o_id, wins=None, mins=None):
+        none = [None] * len(frames)                       # (the clips' rows one after the other in `lg`)
+        return cls(lg, list(frames), back_to_back(frames), list(alts), list(gaps), list(wins or none), list(mins or none), o_id)
+
+    @property
+    def windows(self):
+        return _any_or_none(self.wins)
+
+    @property
+    def min_frames(self):
+        return _any_or_none(self.mins)
+
+    def select(self, idx):
+        """The sub-batch of the clips `idx`, in that order, on the same logits."""
+        idx = [int(b) for b in idx]
+        return self._replace(f0=self.f0[idx], **{k: [getattr(self, k)[b] for b in idx] for k in ("frames", "alts", "gaps", "wins", "mins")})
+
+    def pack(self, with_min) -> PackedClips:
+        """pack_clips of the batch; with_min: the minimum durations too (a search or a score over that lattice)."""
+        return pack_clips(self.lg, self.frames, self.alts, self.gaps, self.f0, windows=self.windows,
+                          min_frames=self.min_frames if with_min else None)
+
+    def args(self):                                       # the leading arguments of viterbi_align and of the scoring calls
+        return self.lg, self.frames, self.alts, self.gaps, self.o_id
+
+    def scored_on(self, idx, packed, with_min):
+        """-> (select(idx), the PackedClips its scoring call runs on): `packed`, this batch's own, where reuses_packed allows."""
+        sub = self.select(idx)
+        return sub, packed if reuses_packed(packed, len(self.frames), len(sub.frames), with_min) else sub.pack(with_min)
+
+
+def _check_tok(tok, logits):
+    if not tok.is_cuda or tok.device != logits.device or tok.dtype != torch.int32 or tok.dim() != 1 or tok.stride(0) != 1 \
+            or tok.shape[0] != logits.shape[0]:
+        raise ValueError("tok must be viterbi_align's [rows] int32 CUDA tensor for these logits")
+
+
+def _upload_substitutes(substitutes, dev):
+    """edit_scores' and insertion_scores' table -> (d_sub [max(P, 1), 2] int32 on `dev`, P)."""
+    sub = np.asarray(substitutes, np.int64).reshape(-1, 2)
+    P = len(sub)
+    if P > MAX_SUBSTITUTES:
+        raise ValueError(f"at most {MAX_SUBSTITUTES} substitutes, got {P}")
+    if P and (sub.min() < -2 ** 31 or sub.max() > 2 ** 31 - 1):
+        raise ValueError("class ids are int32")
+    return torch.from_numpy(np.ascontiguousarray(sub if P else np.zeros((1, 2)), np.int32)).to(dev), P
+
+
+# entry -> (the entry whose workspace rule it shares, takes the start windows, takes the minimum durations)
+_ENTRIES = {
+    "wfl_align": ("wfl_align", False, False), "wfl_align_posterior": ("wfl_align_posterior", False, False),
+    "wfl_align_windowed": ("wfl_align", True, False), "wfl_align_posterior_windowed": ("wfl_align_posterior", True, False),
+    "wfl_align_min_duration": ("wfl_align", True, True),
+    "wfl_align_min_duration_posterior": ("wfl_align_min_duration_posterior", True, True),
+    "wfl_align_edits": ("wfl_align_edits", True, False), "wfl_align_insertions": ("wfl_align_insertions", True, False),
+}
+
+
+def _call(entry, logits, o_id, packed, middle, outputs, stream, temporaries=()):
+    """What the entries share after the packing: the workspace, the call on `stream` (default: the current one) and its check.  Every
+    entry takes  logits .. token table, [windows], [minimum durations], gap table, clips, *middle, workspace, its bytes, *outputs,
+    stream  (_ENTRIES; windows that were not packed go as a null pointer).  middle: a tensor goes as its pointer, anything else as
+    it is; temporaries: tensors made for this call alone, kept for the stream beside the workspace and the packed tables."""
+    lib = _lib.load()
+    sized_as, takes_win, takes_min = _ENTRIES[entry]
+    nb, T, N, F0, K0, d_tc, d_gc, d_win, d_min = packed
+    dev = logits.device
+    ws_n = _workspace_bytes(sized_as + "_workspace_bytes", T, N)
+    ws = torch.empty(max(ws_n, 1), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        st = stream if stream is not None else torch.cuda.current_stream(dev)
+        args = [_ptr(logits), logits.stride(0), logits.shape[1], int(o_id), _hp(F0), _hp(T), _hp(K0), _hp(N), _ptr(d_tc)]
+        args += ([_ptr(d_win)] if takes_win else []) + ([_ptr(d_min)] if takes_min else []) + [_ptr(d_gc), nb]
+        args += [_ptr(m) if isinstance(m, torch.Tensor) else m for m in middle] + [_ptr(ws), ws_n] + [_ptr(t) for t in outputs]
+        _lib.check(getattr(lib, entry)(*args, C.c_void_p(st.cuda_stream)), entry)
+        for t in (d_tc, d_gc, ws, d_win, d_min, *temporaries):
+            if t is not None:
+                t.record_stream(st)
+
+
 def viterbi_align(logits, n_frames, token_classes, gap_classes, o_id, frame_offsets=None, stream=None, packed=None, windows=None,
                   min_frames=None):
     """Forced alignment of a ragged batch of clips on the GPU.
@@ -183,31 +320,15 @@ def viterbi_align(logits, n_frames, token_classes, gap_classes, o_id, frame_offs
                    STATUS_INFEASIBLE (windows_feasible(T, windows, min_frames) predicts it), a value outside the range
                    STATUS_BAD_CLASS.  With `packed`, the durations are the ones packed there.
     -> (ids [rows] int32, tok [rows] int32, score [clips] float32, status [clips] int32), CUDA tensors on `stream`'s device."""
-    lib = _lib.load()
-    nb, T, N, F0, K0, d_tc, d_gc, d_win, d_min = packed if packed is not None else pack_clips(logits, n_frames, token_classes,
-                                                                                              gap_classes, frame_offsets, windows,
-                                                                                              min_frames)
-    dev = logits.device
-    rows = logits.shape[0]
-    ws_n = workspace_bytes(T, N)
-    ws = torch.empty(max(ws_n, 1), dtype=torch.uint8, device=dev)
+    if packed is None:
+        packed = pack_clips(logits, n_frames, token_classes, gap_classes, frame_offsets, windows, min_frames)
+    dev, rows, nb = logits.device, logits.shape[0], packed.nb
     ids = torch.empty(rows, dtype=torch.int32, device=dev)
     tok = torch.empty(rows, dtype=torch.int32, device=dev)
     score = torch.empty(max(nb, 1), dtype=torch.float32, device=dev)
     status = torch.empty(max(nb, 1), dtype=torch.int32, device=dev)
-    with torch.cuda.device(dev):
-        st = stream if stream is not None else torch.cuda.current_stream(dev)
-        head = (_ptr(logits), logits.stride(0), logits.shape[1], int(o_id), _hp(F0), _hp(T), _hp(K0), _hp(N), _ptr(d_tc))
-        tail = (_ptr(d_gc), nb, _ptr(ws), ws_n, _ptr(ids), _ptr(tok), _ptr(score), _ptr(status), C.c_void_p(st.cuda_stream))
-        if d_min is not None:
-            _lib.check(lib.wfl_align_min_duration(*head, _ptr(d_win) if d_win is not None else None, _ptr(d_min), *tail),
-                       "wfl_align_min_duration")
-        elif d_win is None:
-            _lib.check(lib.wfl_align(*head, *tail), "wfl_align")
-        else:
-            _lib.check(lib.wfl_align_windowed(*head, _ptr(d_win), *tail), "wfl_align_windowed")
-        for t in (d_tc, d_gc, ws) + tuple(x for x in (d_win, d_min) if x is not None):
-            t.record_stream(st)
+    entry = "wfl_align_min_duration" if packed.d_min is not None else "wfl_align" if packed.d_win is None else "wfl_align_windowed"
+    _call(entry, logits, o_id, packed, (), (ids, tok, score, status), stream)
     return ids, tok, score[:nb], status[:nb]
 
 
@@ -219,14 +340,23 @@ def _without_min_frames(packed, what):
     return packed[:8]
 
 
-def posterior_workspace_bytes(n_frames, n_tokens) -> int:
-    lib = _lib.load()
-    T = np.ascontiguousarray(n_frames, np.int32)
-    N = np.ascontiguousarray(n_tokens, np.int32)
-    n = int(lib.wfl_align_posterior_workspace_bytes(_hp(T), _hp(N), T.size))
-    if n < 0:
-        raise _lib.WflError("wfl_align_posterior_workspace_bytes: negative frame or token count")
-    return n
+def _with_min_frames(packed, what):
+    """The sums of duration_posteriors run over the lattice WITH minimum durations: a batch packed without them is refused, a score
+    must speak of the lattice its search ran on."""
+    if packed.d_min is None:
+        raise ValueError(f"{what} scores the lattice with minimum durations: this batch was packed without min_frames")
+    return packed
+
+
+def _posteriors(entry, logits, o_id, tok, packed, stream):
+    """The forward-backward entries' outputs and call -> alignment_posteriors' five tensors."""
+    _check_tok(tok, logits)
+    nb, ntok, dev = packed.nb, int(packed.N.sum()), logits.device
+    logz = torch.empty(max(nb, 1), dtype=torch.float32, device=dev)
+    per_tok = torch.empty((3, max(ntok, 1)), dtype=torch.float32, device=dev)
+    status = torch.empty(max(nb, 1), dtype=torch.int32, device=dev)
+    _call(entry, logits, o_id, packed, (tok,), (logz, per_tok[0], per_tok[1], per_tok[2], status), stream)
+    return logz[:nb], per_tok[0, :ntok], per_tok[1, :ntok], per_tok[2, :ntok], status[:nb]
 
 
 def alignment_posteriors(logits, n_frames, token_classes, gap_classes, o_id, tok, frame_offsets=None, stream=None, packed=None):
@@ -242,49 +372,11 @@ def alignment_posteriors(logits, n_frames, token_classes, gap_classes, o_id, tok
     tok_post: the posterior occupancy of the run Viterbi gave the token, in [0, 1]; start_mean / start_sd: mean (relative to
     Viterbi's start) and standard deviation of the token's start, in frames.  A clip with status != 0 gets zeros
     (STATUS_NOT_A_PATH: `tok` does not hold every token of the clip)."""
-    lib = _lib.load()
-    nb, T, N, F0, K0, d_tc, d_gc, d_win = _without_min_frames(packed if packed is not None else pack_clips(
-        logits, n_frames, token_classes, gap_classes, frame_offsets), "alignment_posteriors")
-    dev = logits.device
-    if not tok.is_cuda or tok.device != dev or tok.dtype != torch.int32 or tok.dim() != 1 or tok.stride(0) != 1 \
-            or tok.shape[0] != logits.shape[0]:
-        raise ValueError("tok must be viterbi_align's [rows] int32 CUDA tensor for these logits")
-    ntok = int(N.sum())
-    ws_n = posterior_workspace_bytes(T, N)
-    ws = torch.empty(max(ws_n, 1), dtype=torch.uint8, device=dev)
-    logz = torch.empty(max(nb, 1), dtype=torch.float32, device=dev)
-    per_tok = torch.empty((3, max(ntok, 1)), dtype=torch.float32, device=dev)
-    status = torch.empty(max(nb, 1), dtype=torch.int32, device=dev)
-    with torch.cuda.device(dev):
-        st = stream if stream is not None else torch.cuda.current_stream(dev)
-        head = (_ptr(logits), logits.stride(0), logits.shape[1], int(o_id), _hp(F0), _hp(T), _hp(K0), _hp(N), _ptr(d_tc))
-        tail = (_ptr(d_gc), nb, _ptr(tok), _ptr(ws), ws_n, _ptr(logz), _ptr(per_tok[0]), _ptr(per_tok[1]), _ptr(per_tok[2]),
-                _ptr(status), C.c_void_p(st.cuda_stream))
-        if d_win is None:
-            _lib.check(lib.wfl_align_posterior(*head, *tail), "wfl_align_posterior")
-        else:
-            _lib.check(lib.wfl_align_posterior_windowed(*head, _ptr(d_win), *tail), "wfl_align_posterior_windowed")
-        for t in (d_tc, d_gc, ws) + ((d_win,) if d_win is not None else ()):
-            t.record_stream(st)
-    return logz[:nb], per_tok[0, :ntok], per_tok[1, :ntok], per_tok[2, :ntok], status[:nb]
-
-
-def _with_min_frames(packed, what):
-    """The sums of duration_posteriors run over the lattice WITH minimum durations: a batch packed without them is refused, a score
-    must speak of the lattice its search ran on."""
-    if packed.d_min is None:
-        raise ValueError(f"{what} scores the lattice with minimum durations: this batch was packed without min_frames")
-    return packed
-
-
-def duration_posterior_workspace_bytes(n_frames, n_tokens) -> int:
-    lib = _lib.load()
-    T = np.ascontiguousarray(n_frames, np.int32)
-    N = np.ascontiguousarray(n_tokens, np.int32)
-    n = int(lib.wfl_align_min_duration_posterior_workspace_bytes(_hp(T), _hp(N), T.size))
-    if n < 0:
-        raise _lib.WflError("wfl_align_min_duration_posterior_workspace_bytes: negative frame or token count")
-    return n
+    if packed is None:
+        packed = pack_clips(logits, n_frames, token_classes, gap_classes, frame_offsets)
+    _without_min_frames(packed, "alignment_posteriors")
+    entry = "wfl_align_posterior" if packed.d_win is None else "wfl_align_posterior_windowed"
+    return _posteriors(entry, logits, o_id, tok, packed, stream)
 
 
 def duration_posteriors(logits, n_frames, token_classes, gap_classes, o_id, tok, frame_offsets=None, stream=None, packed=None,
@@ -300,39 +392,10 @@ def duration_posteriors(logits, n_frames, token_classes, gap_classes, o_id, tok,
     averaged over the run Viterbi gave it; start_mean / start_sd from B_k as there.  STATUS_NOT_A_PATH also for a `tok` with a run
     shorter than its minimum, STATUS_INFEASIBLE also when no path meets the durations, STATUS_BAD_CLASS also for a duration outside
     1 .. MAX_MIN_FRAMES."""
-    lib = _lib.load()
-    nb, T, N, F0, K0, d_tc, d_gc, d_win, d_min = _with_min_frames(packed if packed is not None else pack_clips(
-        logits, n_frames, token_classes, gap_classes, frame_offsets, windows, min_frames), "duration_posteriors")
-    dev = logits.device
-    if not tok.is_cuda or tok.device != dev or tok.dtype != torch.int32 or tok.dim() != 1 or tok.stride(0) != 1 \
-            or tok.shape[0] != logits.shape[0]:
-        raise ValueError("tok must be viterbi_align's [rows] int32 CUDA tensor for these logits")
-    ntok = int(N.sum())
-    ws_n = duration_posterior_workspace_bytes(T, N)
-    ws = torch.empty(max(ws_n, 1), dtype=torch.uint8, device=dev)
-    logz = torch.empty(max(nb, 1), dtype=torch.float32, device=dev)
-    per_tok = torch.empty((3, max(ntok, 1)), dtype=torch.float32, device=dev)
-    status = torch.empty(max(nb, 1), dtype=torch.int32, device=dev)
-    with torch.cuda.device(dev):
-        st = stream if stream is not None else torch.cuda.current_stream(dev)
-        _lib.check(lib.wfl_align_min_duration_posterior(
-            _ptr(logits), logits.stride(0), logits.shape[1], int(o_id), _hp(F0), _hp(T), _hp(K0), _hp(N), _ptr(d_tc),
-            _ptr(d_win) if d_win is not None else None, _ptr(d_min), _ptr(d_gc), nb, _ptr(tok), _ptr(ws), ws_n, _ptr(logz),
-            _ptr(per_tok[0]), _ptr(per_tok[1]), _ptr(per_tok[2]), _ptr(status), C.c_void_p(st.cuda_stream)),
-            "wfl_align_min_duration_posterior")
-        for t in (d_tc, d_gc, ws, d_min) + ((d_win,) if d_win is not None else ()):
-            t.record_stream(st)
-    return logz[:nb], per_tok[0, :ntok], per_tok[1, :ntok], per_tok[2, :ntok], status[:nb]
-
-
-def edits_workspace_bytes(n_frames, n_tokens) -> int:
-    lib = _lib.load()
-    T = np.ascontiguousarray(n_frames, np.int32)
-    N = np.ascontiguousarray(n_tokens, np.int32)
-    n = int(lib.wfl_align_edits_workspace_bytes(_hp(T), _hp(N), T.size))
-    if n < 0:
-        raise _lib.WflError("wfl_align_edits_workspace_bytes: negative frame or token count")
-    return n
+    if packed is None:
+        packed = pack_clips(logits, n_frames, token_classes, gap_classes, frame_offsets, windows, min_frames)
+    _with_min_frames(packed, "duration_posteriors")
+    return _posteriors("wfl_align_min_duration_posterior", logits, o_id, tok, packed, stream)
 
 
 def edit_scores(logits, n_frames, token_classes, gap_classes, o_id, substitutes, frame_offsets=None, stream=None, packed=None):
@@ -346,42 +409,16 @@ def edit_scores(logits, n_frames, token_classes, gap_classes, o_id, substitutes,
     the transcript without token k (and without its window): positive where the edit explains the audio better, -inf where the
     edited transcript has no path.  logz is alignment_posteriors' logz.  A clip with status != 0 gets zeros; a class id of
     `substitutes` outside the logits' columns is STATUS_BAD_CLASS for every clip."""
-    lib = _lib.load()
-    nb, T, N, F0, K0, d_tc, d_gc, d_win = _without_min_frames(packed if packed is not None else pack_clips(
-        logits, n_frames, token_classes, gap_classes, frame_offsets), "edit_scores")
-    sub = np.asarray(substitutes, np.int64).reshape(-1, 2)
-    P = len(sub)
-    if P > MAX_SUBSTITUTES:
-        raise ValueError(f"at most {MAX_SUBSTITUTES} substitutes, got {P}")
-    if P and (sub.min() < -2 ** 31 or sub.max() > 2 ** 31 - 1):
-        raise ValueError("class ids are int32")
-    dev = logits.device
-    d_sub = torch.from_numpy(np.ascontiguousarray(sub if P else np.zeros((1, 2)), np.int32)).to(dev)
-    ntok = int(N.sum())
-    ws_n = edits_workspace_bytes(T, N)
-    ws = torch.empty(max(ws_n, 1), dtype=torch.uint8, device=dev)
+    if packed is None:
+        packed = pack_clips(logits, n_frames, token_classes, gap_classes, frame_offsets)
+    _without_min_frames(packed, "edit_scores")
+    dev, nb, ntok = logits.device, packed.nb, int(packed.N.sum())
+    d_sub, P = _upload_substitutes(substitutes, dev)
     logz = torch.empty(max(nb, 1), dtype=torch.float32, device=dev)
     edits = torch.empty((max(ntok, 1), P + 1), dtype=torch.float32, device=dev)
     status = torch.empty(max(nb, 1), dtype=torch.int32, device=dev)
-    with torch.cuda.device(dev):
-        st = stream if stream is not None else torch.cuda.current_stream(dev)
-        _lib.check(lib.wfl_align_edits(_ptr(logits), logits.stride(0), logits.shape[1], int(o_id), _hp(F0), _hp(T), _hp(K0), _hp(N),
-                                       _ptr(d_tc), _ptr(d_win) if d_win is not None else None, _ptr(d_gc), nb, _ptr(d_sub), P,
-                                       _ptr(ws), ws_n, _ptr(logz), _ptr(edits), _ptr(status), C.c_void_p(st.cuda_stream)),
-                   "wfl_align_edits")
-        for t in (d_tc, d_gc, ws, d_sub) + ((d_win,) if d_win is not None else ()):
-            t.record_stream(st)
+    _call("wfl_align_edits", logits, o_id, packed, (d_sub, P), (logz, edits, status), stream, temporaries=(d_sub,))
     return logz[:nb], edits[:ntok], status[:nb]
-
-
-def insertions_workspace_bytes(n_frames, n_tokens) -> int:
-    lib = _lib.load()
-    T = np.ascontiguousarray(n_frames, np.int32)
-    N = np.ascontiguousarray(n_tokens, np.int32)
-    n = int(lib.wfl_align_insertions_workspace_bytes(_hp(T), _hp(N), T.size))
-    if n < 0:
-        raise _lib.WflError("wfl_align_insertions_workspace_bytes: negative frame or token count")
-    return n
 
 
 def insertion_scores(logits, n_frames, token_classes, gap_classes, o_id, substitutes, frame_offsets=None, stream=None, packed=None):
@@ -396,32 +433,17 @@ def insertion_scores(logits, n_frames, token_classes, gap_classes, o_id, substit
     longer transcript explains the audio better, -inf where it has no path (every entry of a clip with as many tokens as frames).
     logz is alignment_posteriors' logz.  A clip with status != 0 gets zeros; a class id of `substitutes` outside the logits' columns
     is STATUS_BAD_CLASS for every clip."""
-    lib = _lib.load()
-    nb, T, N, F0, K0, d_tc, d_gc, d_win = _without_min_frames(packed if packed is not None else pack_clips(
-        logits, n_frames, token_classes, gap_classes, frame_offsets), "insertion_scores")
-    sub = np.asarray(substitutes, np.int64).reshape(-1, 2)
-    P = len(sub)
-    if P > MAX_SUBSTITUTES:
-        raise ValueError(f"at most {MAX_SUBSTITUTES} substitutes, got {P}")
-    if P and (sub.min() < -2 ** 31 or sub.max() > 2 ** 31 - 1):
-        raise ValueError("class ids are int32")
-    dev = logits.device
-    d_sub = torch.from_numpy(np.ascontiguousarray(sub if P else np.zeros((1, 2)), np.int32)).to(dev)
-    rows = int(N.sum()) + nb
-    ws_n = insertions_workspace_bytes(T, N)
-    ws = torch.empty(max(ws_n, 1), dtype=torch.uint8, device=dev)
+    if packed is None:
+        packed = pack_clips(logits, n_frames, token_classes, gap_classes, frame_offsets)
+    _without_min_frames(packed, "insertion_scores")
+    dev, nb, rows = logits.device, packed.nb, int(packed.N.sum()) + packed.nb
+    d_sub, P = _upload_substitutes(substitutes, dev)
     logz = torch.empty(max(nb, 1), dtype=torch.float32, device=dev)
     ins = torch.empty((max(rows, 1), max(P, 1)), dtype=torch.float32, device=dev)
     status = torch.empty(max(nb, 1), dtype=torch.int32, device=dev)
-    with torch.cuda.device(dev):
-        st = stream if stream is not None else torch.cuda.current_stream(dev)
-        _lib.check(lib.wfl_align_insertions(_ptr(logits), logits.stride(0), logits.shape[1], int(o_id), _hp(F0), _hp(T), _hp(K0),
-                                            _hp(N), _ptr(d_tc), _ptr(d_win) if d_win is not None else None, _ptr(d_gc), nb,
-                                            _ptr(d_sub), P, _ptr(ws), ws_n, _ptr(logz), _ptr(ins), _ptr(status),
-                                            C.c_void_p(st.cuda_stream)), "wfl_align_insertions")
-        for t in (d_tc, d_gc, ws, d_sub) + ((d_win,) if d_win is not None else ()):
-            t.record_stream(st)
+    _call("wfl_align_insertions", logits, o_id, packed, (d_sub, P), (logz, ins, status), stream, temporaries=(d_sub,))
     return logz[:nb], ins[:rows, :P], status[:nb]
+
 
 
 def substitute_table(label_list):

@@ -31,6 +31,7 @@ from . import audio as A
 from . import decode as DC
 from . import native_post as npost
 from . import postprocess as pp
+from ._lib import back_to_back
 from .options import ALIGN_MODES, DECODE_MODES, PostOptions, parse_min_duration, resolve
 from .tagger import BIOPhonemeTagger, raise_on_status
 
@@ -546,20 +547,13 @@ class Labeler:
         for fi, segs in searched.items():
             final[fi] = self._match_forced(audio_paths[fi], segs, verbose)
         if with_t:
-            moved = {}
-            edited = {} if opts.align_edits else None
-            inserted = {} if opts.align_insertions else None
-            got = self._label_viterbi(paths(with_t), [forced[fi] for fi in with_t], lang_id, confidence_threshold, verbose,
-                                      opts.align_scores, [drafts[fi] for fi in with_t], opts.draft_tolerance, moved, edited, inserted,
-                                      opts.min_duration, opts.duration_scores)
-            for fi, segs, sc in zip(with_t, *got):
-                final[fi], scores[fi] = segs, sc
-            if moves is not None:
-                moves.update({with_t[j]: m for j, m in moved.items()})
-            if edits is not None and edited is not None:
-                edits.update({with_t[j]: e for j, e in edited.items()})
-            if insertions is not None and inserted is not None:
-                insertions.update({with_t[j]: e for j, e in inserted.items()})
+            got = self._label_viterbi(paths(with_t), [forced[fi] for fi in with_t], [drafts[fi] for fi in with_t], opts, lang_id,
+                                      confidence_threshold, verbose)
+            for fi, rec in zip(with_t, got):
+                final[fi], scores[fi] = rec.segments, rec.score
+                for into, value in ((moves, rec.moves), (edits, rec.edits), (insertions, rec.insertions)):
+                    if into is not None and value is not None:
+                        into[fi] = value
         return final, scores
 
     def _label_files_greedy(self, audio_paths, lang_id, confidence_threshold, verbose):
@@ -760,7 +754,7 @@ class Labeler:
             else:
                 d_ids, d_score, d_st = DC.bio_viterbi_bigram(lg, frames, table, trans, threshold)
             ids_all, st_all = d_ids.cpu().numpy(), d_st.cpu().numpy()
-            f0 = np.concatenate([[0], np.cumsum(np.asarray(frames, np.int64))[:-1]])
+            f0 = back_to_back(frames)
             raw = {}                                          # clip -> (score, logz, sum lse, post, cls_post, posterior status)
             ok = [b for b in range(len(sel)) if st_all[b] == DC.STATUS_OK]
             if want_scores and ok:
@@ -818,7 +812,7 @@ class Labeler:
             _, rows = self._forward_with_logits(sel, by_file, lang_id, confidence_threshold)
             frames, lg = self._file_rows(rows, by_file, sel)
             d_logz, d_counts, d_st = DC.bigram_expected_counts(lg, frames, table, trans, confidence_threshold)
-            f0 = np.concatenate([[0], np.cumsum(np.asarray(frames, np.int64))[:-1]])
+            f0 = back_to_back(frames)
             d_lse = _clip_lse(lg, f0, f0 + np.asarray(frames, np.int64))
             h = torch.cat([d_logz.double(), d_lse, d_st.double()]).cpu().numpy()
             h_counts = d_counts.cpu().numpy()
@@ -834,234 +828,244 @@ class Labeler:
                 n_frames += int(frames[b])
         return total, total_logz, total_lse, n_frames, skipped
 
-    def _label_viterbi(self, audio_paths, transcripts, lang_id, threshold, verbose, want_scores=False, drafts=None, tolerance=0.0,
-                       moves=None, edits=None, insertions=None, min_duration=None, duration_scores=False):
-        """Files with a transcript, align="viterbi".  Their chunks are forwarded with logits (kept on the device); the free decode of
-        the same forward gives the greedy result, which the pause rule at the ends needs and which a file falls back to (with a
-        message) when its transcript cannot be aligned.  Each file's chunks' valid logits rows are concatenated on the device, so
-        one search covers the whole file; the files of a wave go to wfl_align as one ragged batch and only ids / tok / score / status
-        come back to the host.  -> (results, [FileScore or None per file]); want_scores: right after the search, one
-        wfl_align_posterior call per wave over the clips it aligned (same logits, the device `tok`), one more small copy to the host;
-        without, every score is None.
-
-        drafts: per file its draft segments or None (postprocess.align_draft; the transcript is then the draft's labels).  The start
-        windows of a file with a draft (align.draft_windows, `tolerance` seconds either side) join the same ragged batch, which then
-        goes through the windowed entries: the search, and the posterior over the lattice the search ran on.  A file whose windows
-        no path satisfies is searched without them, with a message: align.windows_feasible finds it before the launch, and a clip the
-        kernel still reports infeasible inside its windows is searched again without them.  moves: a dict that takes
-        {file index: [DraftMove]} for the files aligned inside their windows.
-
-        edits: a dict that takes {file index: [TokenEdit]} (postprocess.align_edits): after the search, align.edit_scores over the
-        clips it aligned, on the PackedClips of the search (with a draft: the windowed lattice), with every phoneme of the label set
-        as a substitute; the clips go in groups whose workspace stays under align.EDITS_WORKSPACE_LIMIT.  A file that fell back to
-        the greedy alignment gets no entry, and one line says so.
-
-        insertions: a dict that takes {file index: [PlaceInsertion]} (postprocess.align_insertions): align.insertion_scores in the
-        same place, on the same PackedClips, with the same table, grouped by its own workspace rule.  With both on, each call runs
-        its own sweeps.
-
-        min_duration: PostOptions.min_duration (postprocess.min_duration) or None.  Every transcript token of every file gets its
-        minimum frames (align.min_frames_for) and the batch goes through wfl_align_min_duration, the windows beside them.  A file
-        whose durations no path can meet (align.windows_feasible with them, before the launch; status 1, after it) is searched
-        without them, with a message, its windows kept; the scoring passes above never meet a min_duration (options rule 16).
-
-        duration_scores (postprocess.duration_scores, beside a min_duration): the scores of want_scores for this search.  The clips
-        that kept their durations are scored by align.duration_posteriors (wfl_align_min_duration_posterior) on the PackedClips of
-        the search -- packed again only where clips left the batch -- and the clips whose durations were dropped, which were
-        searched without them, by align.alignment_posteriors with their windows: every file gets the lattice it was searched on."""
+    def _label_viterbi(self, audio_paths, transcripts, drafts, opts, lang_id, threshold, verbose):
+        """Files with a transcript, align="viterbi" -> one ViterbiLabel per file.  Their chunks are forwarded with logits (kept on
+        the device); the free decode of the same forward gives the greedy result, which the pause rule at the ends needs and which a
+        file falls back to (with a message) when its transcript cannot be aligned.  Each file's chunks' valid logits rows are
+        concatenated on the device, so one search covers the whole file; the files of a wave are one ragged batch (align.AlignBatch)
+        that goes through the stages -- _greedy_and_plans, _clip_constraints, _search, _score, _clip_label -- and only ids / tok /
+        score / status and the scoring calls' small tables come back to the host.  drafts: per file its draft segments or None
+        (opts.align_draft; the transcript is then the draft's labels)."""
         lang_name = self._lang_name(lang_id)
-        remap, names = self._names_for(lang_name)
-        results, scores = [], []
-        want_edits, want_ins = edits is not None, insertions is not None
-        if want_edits or want_ins:
+        drafts = drafts if drafts is not None else [None] * len(audio_paths)
+        sub_pairs = sub_out = None
+        if opts.align_edits or opts.align_insertions:
             sub_names, sub_pairs = AL.substitute_table(self.labels)
-            sub_out = AL.substitute_output_names(sub_names, self._table, remap, names)
+            sub_out = AL.substitute_output_names(sub_names, self._table, *self._names_for(lang_name))
+        out = []
         for sel, by_file in self._file_waves(audio_paths, verbose):     # a wave's chunks are forwarded and aligned together
             free, rows = self._forward_with_logits(sel, by_file, lang_id, threshold)
-            # the greedy result of every file (free decode, merge, string match), as _label_files_greedy computes it
-            greedy, free_segs, plans = {}, {}, {}
-            for j, fi in enumerate(sel):
-                parts, clock = [], 0.0
-                for ci, x in enumerate(by_file[fi]):
-                    parts.append((*free[(fi, ci)], clock))
-                    clock += len(x) / self.sr
-                segs = free_segs[fi] = self._file_segments(parts, lang_name)
-                tr = transcripts[fi]
-                greedy[fi] = AL.with_end_pauses(segs, pp.align_phoneme_list(segs, tr), tr)
-                if not tr:
-                    continue
-                alts, why = AL.token_alternatives(tr, self._table, remap, names, self.labels)
-                if alts is None:
-                    print(f"{audio_paths[fi]}: viterbi alignment not possible ({why}); using the greedy alignment")
-                    continue
-                plans[fi] = alts
-            # one ragged search over the files that can be aligned
+            greedy, free_segs, plans = self._greedy_and_plans(sel, by_file, free, audio_paths, transcripts, lang_name)
             aligned = {}
-            post = {}                                         # file -> its FileScore (want_scores)
-            run = [fi for fi in sel if fi in plans]
+            run = [fi for fi in sel if fi in plans]          # one ragged search over the files that can be aligned
             if run:
+                paths = [audio_paths[fi] for fi in run]
                 frames, lg = self._file_rows(rows, by_file, run)
-                gaps = [AL.gap_classes(self.labels, transcripts[fi]) for fi in run]
-                wins = [None] * len(run)                      # per clip its tokens' start windows; None: none (open)
+                chunks = [self._chunk_plan(rows, by_file[fi], fi) for fi in run]
+                wins, mins = _clip_constraints(paths, frames, chunks, [transcripts[fi] for fi in run],
+                                               [drafts[fi] for fi in run], opts)
+                batch = AL.AlignBatch.of(lg, frames, [plans[fi] for fi in run], [AL.gap_classes(self.labels, transcripts[fi]) for fi in run],
+                                         self.labels.index("O"), wins, mins)
+                found = _search(batch, paths, opts)
+                scored = _score(found, opts, sub_pairs)
                 for b, fi in enumerate(run):
-                    if drafts is not None and drafts[fi] is not None:
-                        cf, _, cc = self._chunk_plan(rows, by_file[fi], fi)
-                        w = AL.draft_windows(drafts[fi], cf, cc, tolerance, frame_duration)
-                        if AL.windows_feasible(frames[b], w):
-                            wins[b] = w
-                        else:
-                            print(f"{audio_paths[fi]}: {DRAFT_INFEASIBLE}")
-                mins = [None] * len(run)                      # per clip its tokens' minimum frames; None: none (all 1)
-                if min_duration is not None:
-                    for b, fi in enumerate(run):
-                        d = AL.min_frames_for(transcripts[fi], min_duration, frame_duration)
-                        w = wins[b] if wins[b] is not None else [AL.OPEN_WINDOW] * len(d)
-                        if AL.windows_feasible(frames[b], w, d):
-                            mins[b] = d
-                        elif frames[b] >= len(d):             # (fewer frames than tokens: the search's own status 1, as without)
-                            print(f"{audio_paths[fi]}: {MIN_DURATION_INFEASIBLE}")
-                windows = wins if any(w is not None for w in wins) else None      # (no draft in the wave: the unwindowed entries)
-                min_frames = mins if any(d is not None for d in mins) else None   # (no duration in the wave: the entries without)
-                packed = (AL.pack_clips(lg, frames, [plans[fi] for fi in run], gaps, windows=windows,
-                                        min_frames=min_frames if duration_scores else None)
-                          if want_scores or want_edits or want_ins or (duration_scores and min_frames is not None) else None)
-                d_ids, d_tok, d_score, d_st = AL.viterbi_align(lg, frames, [plans[fi] for fi in run], gaps, self.labels.index("O"),
-                                                               packed=packed, windows=windows, min_frames=min_frames)
-                st_all = d_st.cpu().numpy()
-                f0 = np.concatenate([[0], np.cumsum(np.asarray(frames, np.int64))[:-1]])
-                for _ in range(2):                            # the safety net: the kernel found no path inside the durations (dropped
-                    again = [b for b in range(len(run))       # first, the windows kept), then none inside the windows
-                             if (wins[b] is not None or mins[b] is not None) and st_all[b] == AL.STATUS_INFEASIBLE]
-                    if not again:
-                        break
-                    for b in again:
-                        if mins[b] is not None:
-                            print(f"{audio_paths[run[b]]}: {MIN_DURATION_INFEASIBLE}")
-                            mins[b] = None
-                        else:
-                            print(f"{audio_paths[run[b]]}: {DRAFT_INFEASIBLE}")
-                            wins[b] = None
-                    kept = [wins[b] for b in again]
-                    r_ids, r_tok, r_score, r_st = AL.viterbi_align(lg, [frames[b] for b in again], [plans[run[b]] for b in again],
-                                                                   [gaps[b] for b in again], self.labels.index("O"),
-                                                                   frame_offsets=f0[again],
-                                                                   windows=kept if any(w is not None for w in kept) else None)
-                    for j, b in enumerate(again):
-                        rows_b = slice(int(f0[b]), int(f0[b]) + frames[b])
-                        d_ids[rows_b], d_tok[rows_b] = r_ids[rows_b], r_tok[rows_b]
-                        d_score[b], d_st[b] = r_score[j], r_st[j]
-                    st_all = d_st.cpu().numpy()
-                    windows = wins if any(w is not None for w in wins) else None
-                    packed = None                             # (packed for the windows that were dropped)
-                ids_all, tok_all = d_ids.cpu().numpy(), d_tok.cpu().numpy()
-                raw = {}                                      # file -> (score, logz, tok_post, start_mean, start_sd)
-                bad_post = {}
-                ok = [b for b in range(len(run)) if st_all[b] == AL.STATUS_OK]
-                raw_edits, raw_ins = {}, {}                   # file -> its rows of edit_scores' edits / insertion_scores' ins
-                if (want_scores or want_edits or want_ins) and ok:
-                    # (only the clips the search aligned; when that is all of them, on the tables the search was given)
-                    sub = ([frames[b] for b in ok], [plans[run[b]] for b in ok], [gaps[b] for b in ok])
-                    if packed is None or len(ok) != len(run):  # (the windows travel in the packed batch: the lattice of the search)
-                        packed = AL.pack_clips(lg, *sub, f0[ok], windows=[wins[b] for b in ok] if windows is not None else None)
-                if (want_edits or want_ins) and ok:
-                    n_tok = [len(plans[run[b]]) for b in ok]
-
-                    def scored_rows(scorer, workspace_bytes, extra, what, entry):
-                        """-> {file: its n_tok + extra rows of scorer's table}, the clips in groups under EDITS_WORKSPACE_LIMIT."""
-                        out = {}
-                        for grp in AL.edit_groups(sub[0], n_tok, workspace_bytes=workspace_bytes):
-                            gsub = tuple([x[j] for j in grp] for x in sub)
-                            gpack = packed if len(grp) == len(ok) else AL.pack_clips(
-                                lg, *gsub, f0[[ok[j] for j in grp]],
-                                windows=[wins[ok[j]] for j in grp] if windows is not None else None)
-                            _, d_ed, d_est = scorer(lg, *gsub, self.labels.index("O"), sub_pairs, packed=gpack)
-                            h_ed, h_est = d_ed.cpu().numpy(), d_est.cpu().numpy()
-                            k0 = 0
-                            for q, j in enumerate(grp):
-                                if h_est[q] == AL.STATUS_OK:
-                                    out[run[ok[j]]] = h_ed[k0:k0 + n_tok[j] + extra]
-                                else:
-                                    print(f"{audio_paths[run[ok[j]]]}: no transcript {what} ({entry} status {int(h_est[q])})")
-                                k0 += n_tok[j] + extra
-                        return out
-                    if want_edits:
-                        raw_edits = scored_rows(AL.edit_scores, AL.edits_workspace_bytes, 0, "edits", "wfl_align_edits")
-                    if want_ins:                              # (a clip's N + 1 places: one row more than its tokens)
-                        raw_ins = scored_rows(AL.insertion_scores, AL.insertions_workspace_bytes, 1, "insertions",
-                                              "wfl_align_insertions")
-
-                def take_posteriors(ok, d_post, entry):
-                    """A scoring call's tensors for the clips `ok` -> raw / bad_post of their files, in one copy to the host."""
-                    nt = sum(len(plans[run[b]]) for b in ok)
-                    h = torch.cat([d_score[ok], *d_post[:4], d_post[4].to(torch.float32)]).cpu().numpy()      # one copy
-                    n_ok = len(ok)
-                    h_score, h_logz, h_st = h[:n_ok], h[n_ok:2 * n_ok], h[2 * n_ok + 3 * nt:]
-                    k0 = 0
-                    for j, b in enumerate(ok):
-                        n = len(plans[run[b]])
-                        if h_st[j] != AL.STATUS_OK:
-                            bad_post[run[b]] = (entry, int(h_st[j]))
-                        else:
-                            raw[run[b]] = (h_score[j], h_logz[j]) + tuple(h[2 * n_ok + q * nt + k0:2 * n_ok + q * nt + k0 + n]
-                                                                          for q in range(3))
-                        k0 += n
-                if want_scores and ok:
-                    d_post = AL.alignment_posteriors(lg, *sub, self.labels.index("O"), d_tok, frame_offsets=f0[ok], packed=packed)
-                    take_posteriors(ok, d_post, "wfl_align_posterior")
-                if duration_scores and ok:
-                    # every clip on the lattice it was searched on: with its durations, or -- where they were dropped -- without
-                    for with_min in (True, False):
-                        part = [b for b in ok if (mins[b] is not None) == with_min]
-                        if not part:
-                            continue
-                        psub = ([frames[b] for b in part], [plans[run[b]] for b in part], [gaps[b] for b in part])
-                        pwin = [wins[b] for b in part]
-                        pwin = pwin if any(w is not None for w in pwin) else None
-                        if with_min:
-                            ppack = packed if packed is not None and len(part) == len(run) else AL.pack_clips(
-                                lg, *psub, f0[part], windows=pwin, min_frames=[mins[b] for b in part])
-                            d_post = AL.duration_posteriors(lg, *psub, self.labels.index("O"), d_tok, frame_offsets=f0[part],
-                                                            packed=ppack)
-                            take_posteriors(part, d_post, "wfl_align_min_duration_posterior")
-                        else:
-                            for b in part:
-                                print(f"{audio_paths[run[b]]}: {DURATION_SCORES_PLAIN}")
-                            d_post = AL.alignment_posteriors(lg, *psub, self.labels.index("O"), d_tok, frame_offsets=f0[part],
-                                                             packed=AL.pack_clips(lg, *psub, f0[part], windows=pwin))
-                            take_posteriors(part, d_post, "wfl_align_posterior")
-                pos = 0
-                for b, fi in enumerate(run):
-                    n = frames[b]
-                    tr = transcripts[fi]
-                    if st_all[b] != AL.STATUS_OK:
-                        why = {AL.STATUS_INFEASIBLE: f"{len(tr)} tokens for {n} frames",
-                               AL.STATUS_OVER_CAP: f"{len(tr)} tokens, over the cap of {AL.MAX_TOKENS}"}.get(int(st_all[b]),
-                                                                                                           f"status {int(st_all[b])}")
-                        print(f"{audio_paths[fi]}: viterbi alignment not possible ({why}); using the greedy alignment")
-                    else:
-                        segs = AL.path_segments(ids_all[pos:pos + n], tok_all[pos:pos + n], *self._chunk_plan(rows, by_file[fi], fi),
-                                                self._table, plans[fi], tr, frame_duration)
-                        aligned[fi] = AL.with_end_pauses(free_segs[fi], segs, tr)
-                        if wins[b] is not None and moves is not None:
-                            moves[fi] = draft_moves(drafts[fi], segs, tok_all[pos:pos + n], wins[b])
-                        if fi in raw:
-                            post[fi] = AL.file_score(raw[fi][0], raw[fi][1], n, *raw[fi][2:], segs, frame_duration)
-                        elif want_scores or duration_scores:  # (the scoring entry refused the path the search gave it)
-                            entry, code = bad_post.get(fi, ("wfl_align_posterior", None))
-                            print(f"{audio_paths[fi]}: no alignment scores ({entry} status {code})")
-                        if fi in raw_edits:
-                            edits[fi] = AL.token_edits(raw_edits[fi], segs, sub_out)
-                        if fi in raw_ins:
-                            insertions[fi] = AL.place_insertions(raw_ins[fi], segs, sub_out)
-                    pos += n
+                    got = self._clip_label(found, scored, b, chunks[b], transcripts[fi], drafts[fi], free_segs[fi], opts, sub_out)
+                    if got is not None:
+                        aligned[fi] = got
             for fi in sel:
-                results.append(aligned.get(fi, greedy[fi]))
-                scores.append(post.get(fi))
-                if want_edits and fi not in aligned:
+                out.append(aligned.get(fi, ViterbiLabel(greedy[fi])))
+                if opts.align_edits and fi not in aligned:
                     print(f"{audio_paths[fi]}: no transcript edits (the file was not Viterbi-aligned)")
-                if want_ins and fi not in aligned:
+                if opts.align_insertions and fi not in aligned:
                     print(f"{audio_paths[fi]}: no transcript insertions (the file was not Viterbi-aligned)")
-        return results, scores
+        return out
+
+    def _greedy_and_plans(self, sel, by_file, free, audio_paths, transcripts, lang_name):
+        """Stage 1, per file of a wave -> (its greedy result: free decode, merge, string match, as _label_files_greedy computes it;
+        its merged free segments; the token alternatives of a file whose transcript can be aligned, one line for one that cannot)."""
+        remap, names = self._names_for(lang_name)
+        greedy, free_segs, plans = {}, {}, {}
+        for fi in sel:
+            parts, clock = [], 0.0
+            for ci, x in enumerate(by_file[fi]):
+                parts.append((*free[(fi, ci)], clock))
+                clock += len(x) / self.sr
+            segs = free_segs[fi] = self._file_segments(parts, lang_name)
+            tr = transcripts[fi]
+            greedy[fi] = AL.with_end_pauses(segs, pp.align_phoneme_list(segs, tr), tr)
+            alts, why = AL.token_alternatives(tr, self._table, remap, names, self.labels) if tr else (None, None)
+            if alts is not None:
+                plans[fi] = alts
+            elif tr:
+                print(f"{audio_paths[fi]}: viterbi alignment not possible ({why}); using the greedy alignment")
+        return greedy, free_segs, plans
+
+    def _clip_label(self, found, scored, b, chunk_plan, tr, draft, free_segs, opts, sub_out):
+        """Stage 5: clip b of a searched wave -> its file's ViterbiLabel, or None (with a line) for a clip the search did not align."""
+        batch = found.batch
+        n, pos = batch.frames[b], int(batch.f0[b])
+        if found.status[b] != AL.STATUS_OK:
+            why = {AL.STATUS_INFEASIBLE: f"{len(tr)} tokens for {n} frames",
+                   AL.STATUS_OVER_CAP: f"{len(tr)} tokens, over the cap of {AL.MAX_TOKENS}"}.get(int(found.status[b]),
+                                                                                               f"status {int(found.status[b])}")
+            print(f"{found.paths[b]}: viterbi alignment not possible ({why}); using the greedy alignment")
+            return None
+        tok = found.tok[pos:pos + n]
+        segs = AL.path_segments(found.ids[pos:pos + n], tok, *chunk_plan, self._table, batch.alts[b], tr, frame_duration)
+        moves = draft_moves(draft, segs, tok, batch.wins[b]) if batch.wins[b] is not None else None
+        score = None
+        if b in scored.raw:
+            score = AL.file_score(scored.raw[b][0], scored.raw[b][1], n, *scored.raw[b][2:], segs, frame_duration)
+        elif opts.align_scores or opts.duration_scores:      # (the scoring entry refused the path the search gave it)
+            entry, code = scored.refused.get(b, ("wfl_align_posterior", None))
+            print(f"{found.paths[b]}: no alignment scores ({entry} status {code})")
+        return ViterbiLabel(AL.with_end_pauses(free_segs, segs, tr), score, moves,
+                            AL.token_edits(scored.edits[b], segs, sub_out) if b in scored.edits else None,
+                            AL.place_insertions(scored.insertions[b], segs, sub_out) if b in scored.insertions else None)
+
+
+class ViterbiLabel(NamedTuple):
+    """Labeler._label_viterbi's record of one file; what does not apply is None."""
+    segments: list
+    score: AL.FileScore = None      # opts.align_scores / duration_scores, a file that was aligned and scored
+    moves: list = None              # [DraftMove], a file aligned inside its draft's windows
+    edits: list = None              # [TokenEdit] (opts.align_edits), a file that was aligned
+    insertions: list = None         # [PlaceInsertion] (opts.align_insertions), the same
+
+
+class _Searched(NamedTuple):
+    """A wave's batch after the search and its fallbacks (_search)."""
+    batch: AL.AlignBatch            # its wins / mins: what every clip was last searched with
+    paths: list                     # per clip its file's path, for the messages
+    ids: np.ndarray                 # viterbi_align's ids / tok / status on the host ...
+    tok: np.ndarray
+    status: np.ndarray
+    d_tok: torch.Tensor             # ... and tok / score on the device, for the scoring calls
+    d_score: torch.Tensor
+    packed: AL.PackedClips          # what the search ran on; None: packed inside viterbi_align, or a fallback round dropped constraints
+
+    @property
+    def ok(self):
+        return [b for b in range(len(self.paths)) if self.status[b] == AL.STATUS_OK]
+
+
+class _Scored(NamedTuple):
+    """_score's results, by clip."""
+    raw: dict                       # (score, logz, tok_post, start_mean, start_sd) of a clip its scoring entry accepted
+    refused: dict                   # (entry, status) of one it refused
+    edits: dict                     # the clip's rows of edit_scores' edits
+    insertions: dict                # the clip's rows of insertion_scores' ins
+
+
+def _clip_constraints(paths, frames, chunks, transcripts, drafts, opts):
+    """Stage 2 -> (wins, mins): per clip its draft's start windows and its opts.min_duration in frames, each None where there is
+    none or where the host rule align.windows_feasible finds no path (the durations inside the windows), with one line."""
+    wins, mins = [None] * len(paths), [None] * len(paths)
+    for b, draft in enumerate(drafts):
+        if draft is not None:
+            cf, _, cc = chunks[b]
+            w = AL.draft_windows(draft, cf, cc, opts.draft_tolerance, frame_duration)
+            if AL.windows_feasible(frames[b], w):
+                wins[b] = w
+            else:
+                print(f"{paths[b]}: {DRAFT_INFEASIBLE}")
+    if opts.min_duration is not None:
+        for b, tr in enumerate(transcripts):
+            d = AL.min_frames_for(tr, opts.min_duration, frame_duration)
+            w = wins[b] if wins[b] is not None else [AL.OPEN_WINDOW] * len(d)
+            if AL.windows_feasible(frames[b], w, d):
+                mins[b] = d
+            elif frames[b] >= len(d):                     # (fewer frames than tokens: the search's own status 1, as without)
+                print(f"{paths[b]}: {MIN_DURATION_INFEASIBLE}")
+    return wins, mins
+
+
+def _search(batch, paths, opts) -> _Searched:
+    """Stage 3: the search over the whole batch, packed here when scores or edits are to run on the same tables (the durations only
+    with opts.duration_scores; without, they go to viterbi_align beside a PackedClips that has none), then the safety net: a clip
+    the kernel found no path for inside its constraints is searched again, first without its durations, then without its windows."""
+    scoring = opts.align_scores or opts.align_edits or opts.align_insertions
+    packed = batch.pack(opts.duration_scores) if scoring or (opts.duration_scores and batch.min_frames is not None) else None
+    d_ids, d_tok, d_score, d_st = AL.viterbi_align(*batch.args(), packed=packed, windows=batch.windows, min_frames=batch.min_frames)
+    status = d_st.cpu().numpy()
+    for _ in range(2):
+        again = [b for b in range(len(paths))
+                 if (batch.wins[b] is not None or batch.mins[b] is not None) and status[b] == AL.STATUS_INFEASIBLE]
+        if not again:
+            break
+        for b in again:
+            if batch.mins[b] is not None:
+                print(f"{paths[b]}: {MIN_DURATION_INFEASIBLE}")
+                batch.mins[b] = None
+            else:
+                print(f"{paths[b]}: {DRAFT_INFEASIBLE}")
+                batch.wins[b] = None
+        sub = batch.select(again)
+        r_ids, r_tok, r_score, r_st = AL.viterbi_align(*sub.args(), frame_offsets=sub.f0, windows=sub.windows)
+        for j, b in enumerate(again):
+            rows_b = slice(int(batch.f0[b]), int(batch.f0[b]) + batch.frames[b])
+            d_ids[rows_b], d_tok[rows_b] = r_ids[rows_b], r_tok[rows_b]
+            d_score[b], d_st[b] = r_score[j], r_st[j]
+        status = d_st.cpu().numpy()
+        packed = None                                     # (packed for the constraints that were dropped)
+    return _Searched(batch, paths, d_ids.cpu().numpy(), d_tok.cpu().numpy(), status, d_tok, d_score, packed)
+
+
+def _score(found, opts, sub_pairs) -> _Scored:
+    """Stage 4: edits, insertions, posteriors, duration posteriors of the clips the search aligned, each call on a sub-batch and on
+    the lattice its clips were searched on (AlignBatch.scored_on: the search's PackedClips or tables packed again)."""
+    scored = _Scored({}, {}, {}, {})
+    ok = found.ok
+    if not ok:
+        return scored
+    if opts.align_scores or opts.align_edits or opts.align_insertions:
+        sub, packed = found.batch.scored_on(ok, found.packed, False)
+    if opts.align_edits:
+        scored.edits.update(_edit_rows(found, sub, packed, AL.edit_scores, AL.edits_workspace_bytes, 0, "edits", "wfl_align_edits",
+                                       sub_pairs))
+    if opts.align_insertions:                             # (a clip's N + 1 places: one row more than its tokens)
+        scored.insertions.update(_edit_rows(found, sub, packed, AL.insertion_scores, AL.insertions_workspace_bytes, 1, "insertions",
+                                            "wfl_align_insertions", sub_pairs))
+    if opts.align_scores:
+        d_post = AL.alignment_posteriors(*sub.args(), found.d_tok, frame_offsets=sub.f0, packed=packed)
+        _take_posteriors(found, ok, d_post, "wfl_align_posterior", scored)
+    if opts.duration_scores:
+        # every clip on the lattice it was searched on: with its durations, or -- where they were dropped -- without
+        for with_min in (True, False):
+            part = [b for b in ok if (found.batch.mins[b] is not None) == with_min]
+            if not part:
+                continue
+            sub, packed = found.batch.scored_on(part, found.packed, with_min)
+            if not with_min:
+                for b in part:
+                    print(f"{found.paths[b]}: {DURATION_SCORES_PLAIN}")
+            d_post = (AL.duration_posteriors if with_min else AL.alignment_posteriors)(*sub.args(), found.d_tok, frame_offsets=sub.f0,
+                                                                                     packed=packed)
+            _take_posteriors(found, part, d_post, "wfl_align_min_duration_posterior" if with_min else "wfl_align_posterior", scored)
+    return scored
+
+
+def _edit_rows(found, sub, packed, scorer, workspace_bytes, extra, what, entry, sub_pairs):
+    """-> {clip: its n_tok + extra rows of scorer's table} for the aligned clips `sub`, in groups under EDITS_WORKSPACE_LIMIT."""
+    n_tok = [len(a) for a in sub.alts]
+    ok, out = found.ok, {}
+    for grp in AL.edit_groups(sub.frames, n_tok, workspace_bytes=workspace_bytes):
+        gsub, gpack = sub.scored_on(grp, packed, False)
+        _, d_ed, d_est = scorer(*gsub.args(), sub_pairs, packed=gpack)
+        h_ed, h_est = d_ed.cpu().numpy(), d_est.cpu().numpy()
+        k0 = 0
+        for q, j in enumerate(grp):
+            if h_est[q] == AL.STATUS_OK:
+                out[ok[j]] = h_ed[k0:k0 + n_tok[j] + extra]
+            else:
+                print(f"{found.paths[ok[j]]}: no transcript {what} ({entry} status {int(h_est[q])})")
+            k0 += n_tok[j] + extra
+    return out
+
+
+def _take_posteriors(found, clips, d_post, entry, scored):
+    """A scoring call's tensors for `clips` -> scored.raw / scored.refused, in one copy to the host."""
+    n_tok = [len(found.batch.alts[b]) for b in clips]
+    nt, n = sum(n_tok), len(clips)
+    h = torch.cat([found.d_score[clips], *d_post[:4], d_post[4].to(torch.float32)]).cpu().numpy()      # one copy
+    h_score, h_logz, h_st = h[:n], h[n:2 * n], h[2 * n + 3 * nt:]
+    k0 = 0
+    for j, b in enumerate(clips):
+        if h_st[j] != AL.STATUS_OK:
+            scored.refused[b] = (entry, int(h_st[j]))
+        else:
+            scored.raw[b] = (h_score[j], h_logz[j]) + tuple(h[2 * n + q * nt + k0:2 * n + q * nt + k0 + n_tok[j]] for q in range(3))
+        k0 += n_tok[j]
 
 
 def _clip_lse(lg, starts, ends):
