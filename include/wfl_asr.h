@@ -364,6 +364,33 @@ int32_t wfl_align_min_duration(const float* logits, int64_t ldl, int32_t C, int3
                                const int32_t* tok_win, const int32_t* tok_min, const int32_t* gap_cls, int32_t n_clips, void* workspace,
                                int64_t workspace_bytes, int32_t* ids, int32_t* tok, float* score, int32_t* status, void* stream);
 
+/* ---- wfl_align with optional tokens: a path may leave out a token the user marked (`postprocess.optional_tokens`; wfl-asr_amd/align.py).
+ * wfl_align_windowed's arguments (tok_win may be null: no windows) plus tok_opt (device), [total tokens] int32 0 | 1, rows as tok_cls,
+ * and skip_penalty = lambda >= 0 in nats.  The lattice gains skip arcs only, no epsilon moves:
+ *     B_k <- {G_k, I_{k-1}, B_{k-1}, G_{k-1} - lambda, I_{k-2} - lambda, B_{k-2} - lambda}     (the first listed wins an exact tie)
+ * the last three only where tok_opt[k-1] == 1 (I_{k-2}, B_{k-2} also need k >= 2).  G_k and I_k are entered as in wfl_align: a gap in
+ * front of a skipped token k - 1 stays in G_{k-1} until B_k opens, there is no G_{k-1} -> G_k arc, so every labelling is exactly one path
+ * and at most one token is skipped between two kept ones.  Start: the virtual frame -1 sits in G_0, so with tok_opt[0] == 1 and N >= 2
+ * frame 0 may also be B_1, at -lambda.  End: G_N | I_{N-1} | B_{N-1}, and where tok_opt[N-1] == 1 | G_{N-1} - lambda | I_{N-2} - lambda |
+ * B_{N-2} - lambda.  Windows mask EB alone and a skipped token's window is never consulted: an optional token with an empty window
+ * (lo > hi) is a token that must be skipped.  With every flag 0 every output is wfl_align's (null tok_win) or wfl_align_windowed's, bit
+ * for bit, for any lambda.
+ * Outputs: ids, tok as wfl_align's (a skipped token never appears in tok); skipped[k] (device, [total tokens] int32) 1 for a token the
+ * path left out, else 0; score[b] the path's sum of e_t minus lambda times its skipped tokens.  status[b]: wfl_align's codes; 1 "no
+ * path": fewer frames than N minus, over every maximal run of optional tokens, ceil(run / 2) (and T >= 1), or windows that cannot be met;
+ * 4 also for a flag other than 0 | 1.  A clip with status != 0 gets ids = o_id, tok = -1, skipped = 0, score 0; its backpointers are never
+ * walked.  Host-side negative returns as wfl_align's, and: a null tok_opt or skipped with any token present, a negative, infinite or NaN
+ * skip_penalty.
+ * Workspace: wfl_align's words (2 bits G, 3 bits B, 1 bit I per slot and frame: the same 6), but a clip with T < N may have a path here
+ * and keeps its round_up(T * words(N), 64) words.  wfl_align_optional_workspace_bytes returns that sum: wfl_align_workspace_bytes' own
+ * figure for every batch whose clips all have T >= N. */
+int64_t wfl_align_optional_workspace_bytes(const int32_t* n_frames_host, const int32_t* n_tok_host, int32_t n_clips);
+int32_t wfl_align_optional(const float* logits, int64_t ldl, int32_t C, int32_t o_id, const int64_t* frame_off_host,
+                           const int32_t* n_frames_host, const int32_t* tok_off_host, const int32_t* n_tok_host, const int32_t* tok_cls,
+                           const int32_t* tok_win, const int32_t* gap_cls, int32_t n_clips, const int32_t* tok_opt, float skip_penalty,
+                           void* workspace, int64_t workspace_bytes, int32_t* ids, int32_t* tok, float* score, int32_t* skipped,
+                           int32_t* status, void* stream);
+
 /* ---- Posteriors of a Viterbi alignment by forward-backward on the GPU (`postprocess.align_scores`; wfl-asr_amd/align.py).  No
  * counterpart in the reference, which reports no confidence for its string match.  The lattice, emissions EB / EI / EG, start and end
  * states, caps (C <= 1024, N <= 4096) and argument conventions are wfl_align's.  The weight of a path is exp(sum_t e_t(state_t));

@@ -6,12 +6,16 @@ posteriors: a missed, inserted or mislabelled phoneme shifts every later token o
 the frame logits for the best path that spells exactly the transcript, in order (csrc/align.hip, include/wfl_asr.h `wfl_align`): every
 token gets one contiguous, time-ordered run of frames, none is dropped.
 
-  _call                 the one call path of the eight entries below: workspace, argument order, stream, check (as decode._call)
+  _call                 the one call path of the nine entries below: workspace, argument order, stream, check (as decode._call)
   AlignBatch            a wave's ragged batch as the Labeler holds it: `windows` / `min_frames`, `select`, `pack`, `args`
   reuses_packed         whether a scoring call runs on the search's PackedClips or on tables packed again for its clips
   viterbi_align         the C ABI on CUDA tensors: a ragged batch of clips in one call; with `windows`, every token may open only
                         inside its (lo, hi) frame window (`wfl_align_windowed`, `postprocess.align_draft`); with `min_frames`,
                         every token occupies at least that many frames (`wfl_align_min_duration`, `postprocess.min_duration`)
+  viterbi_align_optional  the same search where a path may leave out the tokens the caller marks (`wfl_align_optional`,
+                        `postprocess.optional_tokens`), each at `skip_penalty` nats -> viterbi_align's four and `skipped` per token
+  optional_flags / min_frames_needed   `postprocess.optional_tokens` -> a flag per transcript token; the frames such a transcript needs
+  skipped_tokens / format_skipped_tsv / format_folder_skipped_tsv   one file's SkippedToken rows, {stem}.skipped.tsv, the folder's list
   min_frames_for        `postprocess.min_duration` (seconds, or seconds per token name) -> frames per transcript token
   alignment_posteriors  forward-backward over the same lattice (csrc/align_posterior.h, `wfl_align_posterior`; of a batch packed with
                         windows, `wfl_align_posterior_windowed`): logZ, and per token
@@ -72,6 +76,10 @@ def _workspace_bytes(symbol, n_frames, n_tokens) -> int:
 
 def workspace_bytes(n_frames, n_tokens) -> int:
     return _workspace_bytes("wfl_align_workspace_bytes", n_frames, n_tokens)
+
+
+def optional_workspace_bytes(n_frames, n_tokens) -> int:
+    return _workspace_bytes("wfl_align_optional_workspace_bytes", n_frames, n_tokens)
 
 
 def posterior_workspace_bytes(n_frames, n_tokens) -> int:
@@ -171,6 +179,28 @@ def _pack_min_frames(min_frames, N):
     return out.astype(np.int32)
 
 
+def _pack_optional(optional, N):
+    """Per clip a list of flags per token (bools, or ints 0 | 1), or None for a clip without optional tokens -> [max(tokens, 1)]
+    int32, rows as the token table's.  The values are not judged here: a flag other than 0 | 1 is the kernel's STATUS_BAD_CLASS for
+    its clip."""
+    if len(optional) != len(N):
+        raise ValueError("optional needs one entry per clip (None: no optional token)")
+    out = np.zeros(max(int(N.sum()), 1), np.int64)
+    k0 = 0
+    for f, n in zip(optional, N):
+        if f is not None:
+            if any(not isinstance(x, (bool, np.bool_, int, np.integer)) for x in f):
+                raise ValueError("optional flags are bools")
+            f = np.asarray(f, np.int64).reshape(-1)
+            if len(f) != n:
+                raise ValueError(f"a clip with {n} tokens needs {n} optional flags, got {len(f)}")
+            out[k0:k0 + n] = f
+        k0 += int(n)
+    if out.min() < -2 ** 31 or out.max() > 2 ** 31 - 1:
+        raise ValueError("optional flags are int32")
+    return out.astype(np.int32)
+
+
 def pack_clips(logits, n_frames, token_classes, gap_classes, frame_offsets=None, windows=None, min_frames=None) -> PackedClips:
     """Validate a ragged batch and upload its token and gap tables once; pass the result as `packed=` to viterbi_align and to
     alignment_posteriors of the same batch (the packing is host work that grows with the token count).  windows: per clip a list of
@@ -217,11 +247,13 @@ class AlignBatch(NamedTuple):
     wins: list            # per clip its tokens' start windows; None: none (open)
     mins: list            # per clip its tokens' minimum frames; None: none (all 1)
     o_id: int
+    opts: list = None     # per clip its tokens' optional flags; None (the field or an entry): no token may be skipped
 
     @classmethod
-    def of(cls, lg, frames, alts, gaps, o_id, wins=None, mins=None):
+    def of(cls, lg, frames, alts, gaps, o_id, wins=None, mins=None, opts=None):
         none = [None] * len(frames)                       # (the clips' rows one after the other in `lg`)
-        return cls(lg, list(frames), back_to_back(frames), list(alts), list(gaps), list(wins or none), list(mins or none), o_id)
+        return cls(lg, list(frames), back_to_back(frames), list(alts), list(gaps), list(wins or none), list(mins or none), o_id,
+                   list(opts or none))
 
     @property
     def windows(self):
@@ -231,10 +263,17 @@ class AlignBatch(NamedTuple):
     def min_frames(self):
         return _any_or_none(self.mins)
 
+    @property
+    def optional(self):
+        """The per-clip flags where any clip has a flag set, else None (the entries without skip arcs)."""
+        flags = self.opts or []
+        return list(flags) if any(f is not None and any(f) for f in flags) else None
+
     def select(self, idx):
         """The sub-batch of the clips `idx`, in that order, on the same logits."""
         idx = [int(b) for b in idx]
-        return self._replace(f0=self.f0[idx], **{k: [getattr(self, k)[b] for b in idx] for k in ("frames", "alts", "gaps", "wins", "mins")})
+        fields = ("frames", "alts", "gaps", "wins", "mins") + (("opts",) if self.opts is not None else ())
+        return self._replace(f0=self.f0[idx], **{k: [getattr(self, k)[b] for b in idx] for k in fields})
 
     def pack(self, with_min) -> PackedClips:
         """pack_clips of the batch; with_min: the minimum durations too (a search or a score over that lattice)."""
@@ -271,7 +310,7 @@ def _upload_substitutes(substitutes, dev):
 _ENTRIES = {
     "wfl_align": ("wfl_align", False, False), "wfl_align_posterior": ("wfl_align_posterior", False, False),
     "wfl_align_windowed": ("wfl_align", True, False), "wfl_align_posterior_windowed": ("wfl_align_posterior", True, False),
-    "wfl_align_min_duration": ("wfl_align", True, True),
+    "wfl_align_min_duration": ("wfl_align", True, True), "wfl_align_optional": ("wfl_align_optional", True, False),
     "wfl_align_min_duration_posterior": ("wfl_align_min_duration_posterior", True, True),
     "wfl_align_edits": ("wfl_align_edits", True, False), "wfl_align_insertions": ("wfl_align_insertions", True, False),
 }
@@ -330,6 +369,47 @@ def viterbi_align(logits, n_frames, token_classes, gap_classes, o_id, frame_offs
     entry = "wfl_align_min_duration" if packed.d_min is not None else "wfl_align" if packed.d_win is None else "wfl_align_windowed"
     _call(entry, logits, o_id, packed, (), (ids, tok, score, status), stream)
     return ids, tok, score[:nb], status[:nb]
+
+
+def upload_optional(optional, n_tokens, device):
+    """viterbi_align_optional's flags (per clip a list of bools per token, or None) packed and uploaded once -> [max(tokens, 1)] int32
+    tensor on `device`, for its `optional` argument.  n_tokens: tokens per clip (PackedClips.N)."""
+    return torch.from_numpy(_pack_optional(optional, np.asarray(n_tokens, np.int32).reshape(-1))).to(device)
+
+
+def viterbi_align_optional(logits, n_frames, token_classes, gap_classes, o_id, optional, skip_penalty=0.0, frame_offsets=None,
+                           stream=None, packed=None, windows=None):
+    """viterbi_align where a path may leave out the tokens marked optional (wfl_align_optional): at most one between two kept tokens,
+    each at `skip_penalty` nats.
+
+    optional      per clip a list of bools per token, or None for a clip without optional tokens.  The flags travel beside `packed`,
+                  not in it: the same PackedClips serves viterbi_align and this call.  Or upload_optional(...) of such a list, to
+                  pack and upload the flags of a batch once for several calls
+    skip_penalty  nats >= 0 taken from the path's score per skipped token (0: a token is skipped wherever that is no worse)
+    windows       as viterbi_align's; a skipped token's window is never consulted, so an optional token with an empty window
+                  (lo > hi) is a token that must be skipped.  With `packed`, the windows are the ones packed there
+    -> (ids, tok, score, status, skipped): viterbi_align's four -- a skipped token never appears in `tok`, the score is the path's
+    sum minus skip_penalty per skipped token -- and skipped [tokens] int32, 1 for a token the path left out, in the order of the
+    clips' tokens.  STATUS_INFEASIBLE: fewer frames than min_frames_needed(flags), or windows no path meets; STATUS_BAD_CLASS also
+    for a flag other than 0 | 1.  A clip with status != 0 has skipped = 0.  With no flag set every output is viterbi_align's."""
+    if packed is None:
+        packed = pack_clips(logits, n_frames, token_classes, gap_classes, frame_offsets, windows)
+    if packed.d_min is not None:
+        raise ValueError("viterbi_align_optional has no minimum durations: this batch was packed with min_frames")
+    lam = float(skip_penalty)
+    if not (0.0 <= lam < float("inf")):
+        raise ValueError("skip_penalty must be a number of nats >= 0")
+    dev, rows, nb, ntok = logits.device, logits.shape[0], packed.nb, int(packed.N.sum())
+    d_opt = optional if isinstance(optional, torch.Tensor) else upload_optional(optional, packed.N, dev)
+    if d_opt.device != dev or d_opt.dtype != torch.int32 or d_opt.dim() != 1 or d_opt.stride(0) != 1 or d_opt.shape[0] != max(ntok, 1):
+        raise ValueError("uploaded optional flags must be upload_optional's [tokens] int32 tensor for this batch")
+    ids = torch.empty(rows, dtype=torch.int32, device=dev)
+    tok = torch.empty(rows, dtype=torch.int32, device=dev)
+    score = torch.empty(max(nb, 1), dtype=torch.float32, device=dev)
+    status = torch.empty(max(nb, 1), dtype=torch.int32, device=dev)
+    skipped = torch.empty(max(ntok, 1), dtype=torch.int32, device=dev)
+    _call("wfl_align_optional", logits, o_id, packed, (d_opt, lam), (ids, tok, score, skipped, status), stream, temporaries=(d_opt,))
+    return ids, tok, score[:nb], status[:nb], skipped[:ntok]
 
 
 def _without_min_frames(packed, what):
@@ -518,9 +598,11 @@ def gap_classes(label_list, transcript):
 
 
 def path_segments(ids, tok, chunk_frames, chunk_offsets, chunk_clock, table: npost.LabelTable, alternatives, transcript,
-                  frame_duration):
+                  frame_duration, skipped=None):
     """A path over a file's chunks (ids / tok concatenated, chunk_frames[c] valid frames each) -> [(start_s, end_s, token)], exactly
-    one per transcript token, in transcript order.
+    one per transcript token, in transcript order.  skipped (viterbi_align_optional's flags of this transcript's tokens; None: no
+    token may be missing): the segments are then exactly the tokens whose flag is 0, in order -- a path that lacks a token without
+    the flag, or holds one with it, is the RuntimeError a path that does not spell the transcript always was.
 
     Each chunk goes through the native BIO decoder (no median filter) with that chunk's offsets and is shifted by its clock offset,
     as the free decode of Labeler.label_files.  Within a token the ids are first mapped to the token's first alternative (all of
@@ -552,7 +634,13 @@ def path_segments(ids, tok, chunk_frames, chunk_offsets, chunk_clock, table: npo
                 segs[-1][1] = float(e[j]) + t0
             else:
                 segs.append([float(s[j]) + t0, float(e[j]) + t0, k])
-    if [g[2] for g in segs] != list(range(len(transcript))):
+    if skipped is None:
+        want = list(range(len(transcript)))
+    else:
+        if len(skipped) != len(transcript):
+            raise ValueError("one skipped flag per transcript token")
+        want = [k for k, f in enumerate(skipped) if not int(f)]
+    if [g[2] for g in segs] != want:
         raise RuntimeError("the path does not spell the transcript")
     for j, g in enumerate(segs):
         if j + 1 < len(segs):                            # the decoder closes a run at the NEXT run's first frame (its end offset):
@@ -578,6 +666,31 @@ def windows_feasible(T, windows, min_frames=None) -> bool:
             return False
         prev = int(dk)
     return True
+
+
+def optional_flags(transcript, spec):
+    """`postprocess.optional_tokens` -> a bool per transcript token for viterbi_align_optional.  spec: "*" (every token), or output
+    names -- the transcript's own tokens -- in a list; a name the transcript lacks marks nothing."""
+    if isinstance(spec, str):
+        if spec != "*":
+            raise ValueError("optional_tokens is a list of token names, or '*'")
+        return [True] * len(transcript)
+    names = set(spec)
+    return [t in names for t in transcript]
+
+
+def min_frames_needed(flags) -> int:
+    """The frames a transcript with these optional flags needs to have a path (fewer: STATUS_INFEASIBLE): at most one token is
+    skipped between two kept ones, so a maximal run of r optional tokens can lose ceil(r / 2) of them -- N minus that, summed over
+    the runs, and at least one frame."""
+    need, run = len(flags), 0
+    for f in list(flags) + [False]:
+        if f:
+            run += 1
+        else:
+            need -= (run + 1) // 2
+            run = 0
+    return max(need, 1)
 
 
 def min_frames_for(transcript, spec, frame_duration):
@@ -815,3 +928,53 @@ def write_folder_insertions(path, per_file):
         f.write("file\t" + INSERTIONS_HEADER + "\n")
         for name, r in folder_insertion_rows(per_file):
             f.write("\t".join([name] + _insertion_cells(r)) + "\n")
+
+
+# -------------------------------------------------------------------------------------------------------------- skipped tokens
+class SkippedToken(NamedTuple):
+    index: int              # the token's index in the transcript
+    token: str
+    after: str              # the kept tokens around the place, "" at the ends
+    before: str
+    at_s: float             # the place: the start of the next kept token's segment, the end of the last segment when nothing follows
+
+
+def skipped_tokens(skipped, segments, transcript):
+    """One file's SkippedToken rows from its tokens' `skipped` flags (viterbi_align_optional; host values) and its aligned segments
+    [(start_s, end_s, token)], one per kept token in order (path_segments with the same flags)."""
+    flags = [int(f) for f in skipped]
+    if len(flags) != len(transcript) or len(segments) != flags.count(0):
+        raise ValueError("one flag per transcript token and one segment per kept token")
+    seg_of, j = {}, 0
+    for k, f in enumerate(flags):
+        if not f:
+            seg_of[k] = segments[j]
+            j += 1
+    rows = []
+    for k, f in enumerate(flags):
+        if f:
+            prev = max((q for q in seg_of if q < k), default=None)
+            nxt = min((q for q in seg_of if q > k), default=None)
+            at = float(seg_of[nxt][0]) if nxt is not None else (float(segments[-1][1]) if segments else 0.0)
+            rows.append(SkippedToken(k, str(transcript[k]), str(transcript[prev]) if prev is not None else "",
+                                     str(transcript[nxt]) if nxt is not None else "", at))
+    return rows
+
+
+SKIPPED_HEADER = "index\ttoken\tafter\tbefore\tat_s"
+
+
+def _skipped_cells(r: SkippedToken):
+    return [str(r.index), r.token, r.after, r.before, f"{r.at_s:.7f}"]
+
+
+def format_skipped_tsv(rows) -> str:
+    """{stem}.skipped.tsv: one line per token the path left out."""
+    return "".join("\t".join(c) + "\n" for c in [SKIPPED_HEADER.split("\t")] + [_skipped_cells(r) for r in rows])
+
+
+def format_folder_skipped_tsv(per_file) -> str:
+    """skipped_tokens.tsv: [(file name, [SkippedToken])] -> every skipped token, the file's name in front of the token's own
+    columns, in the files' and the tokens' order."""
+    lines = ["file\t" + SKIPPED_HEADER] + ["\t".join([name] + _skipped_cells(r)) for name, rows in per_file for r in rows]
+    return "".join(line + "\n" for line in lines)

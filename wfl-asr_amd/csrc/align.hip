@@ -36,6 +36,17 @@
 // then knows the D_k - 2 frames before it to be chain frames of token k (written as I_k frames) and the one before those to be B_k, whose
 // G / B bits it reads there.  The B that a token's successor sees -- inside a thread, through the exchange, and as an end state -- is
 // -inf where D_k > 1: the token is left from I_k alone.
+//
+// wfl_align_optional is the kernel instantiated with OPT (with and without WIN, never with MIND): where token k - 1 is optional, B_k is
+// also entered from G_{k-1}, I_{k-2} and B_{k-2}, each minus the skip penalty, after the three arcs above (which win a tie).  G and I are
+// entered as before, so a labelling is one path and at most one token is skipped between two kept ones.  B_k's choice takes 3 bits, I_k's
+// its 1: still 6 per slot and frame (2 G, 3 B, 1 I), the same words.  Slot 0 of a thread needs B, I, G of the left thread's last slot and
+// B, I of the one before it, slot 1 the first two: the exchange carries those five floats per thread (CfgOpt, R >= 2 everywhere), and
+// the renormalisation's `sub` applies to all five.  A frame of the backtrace may step back two tokens, so its LDS window holds the words
+// of 2 ALIGN_W / R + 2 threads.  The ends that skip token N - 1 are G_{N-1}, I_{N-2}, B_{N-2} minus the penalty, after the usual three.
+// `skipped` is filled with 1 for the clip's tokens once a path is known to exist, and the last pass stores 0 from every frame that
+// carries a token.  A clip may now have a path with fewer frames than tokens, so it has backpointer words then too
+// (wfl_align_optional_workspace_bytes; wfl_align's figure wherever T >= N), and "no path" is found as the windowed kernels find it.
 #include "lattice.h"
 #include "wfl_asr.h"
 
@@ -71,11 +82,34 @@ struct Cfg : LdsBase<NT, R, 2 * NT * 8> {                // its own between alt 
   static constexpr int LDS = OFF_MISC + 64;
 };
 
+// wfl_align_optional's layout: the exchange carries XN floats per thread, [2][XN][NT], and a frame of the backtrace may step back two
+// tokens, so ALIGN_W frames need the words of 2 ALIGN_W / R + 2 threads.  The same words per thread: 2 bits G, 3 bits B, 1 bit I.
+constexpr int XN = 5;                       // B, I, G of the thread's last slot, B, I of the one before it
+template <int NT, int R>
+struct CfgOpt : LdsBase<NT, R, 2 * XN * NT * 4> {
+  static_assert(R >= 2, "the widened exchange takes a thread's last TWO slots");
+  static constexpr int WPT = Cfg<NT, R>::WPT;
+  static constexpr int WIN = ALIGN_W * (2 * ALIGN_W / R + 2) * WPT;
+  static constexpr int OFF_WIN = CfgOpt::OFF_OWN;
+  static constexpr int OFF_MISC = OFF_WIN + WIN * 4;
+  static constexpr int LDS = OFF_MISC + 64;
+};
+
+// the kernel arguments of wfl_align_optional: AlignLaunch (which stays the record it was for the other entries) and the optional tokens
+struct AlignLaunchOpt : AlignLaunch {
+  const int* tok_opt;  // [total tokens] 0 | 1
+  int* skipped;        // [total tokens]
+  float lambda;        // the skip penalty, nats
+};
+
 // WIN: the start windows of wfl_align_windowed (lattice.h win_mask); false is wfl_align's kernel, instruction for instruction
 // MIND: the minimum durations of wfl_align_min_duration (lattice.h chain_*); false leaves the two kernels above as they were
-template <int NT, int R, bool WIN, bool MIND>
-__global__ __launch_bounds__(NT) void align_kernel(AlignLaunch a) {
-  using K = Cfg<NT, R>;
+// OPT: the skip arcs of wfl_align_optional (B_k also from G_{k-1}, I_{k-2}, B_{k-2} where token k - 1 is optional); false leaves the
+// kernels above as they were.  Never with MIND.
+template <int NT, int R, bool WIN, bool MIND, bool OPT>
+__global__ __launch_bounds__(NT) void align_kernel(std::conditional_t<OPT, AlignLaunchOpt, AlignLaunch> a) {
+  static_assert(!(OPT && MIND), "no skip arcs in the minimum-duration lattice");
+  using K = std::conditional_t<OPT, CfgOpt<NT, R>, Cfg<NT, R>>;
   extern __shared__ __attribute__((aligned(16))) char lds[];
   float* ring = (float*)lds;
   int4* alt = (int4*)(lds + K::OFF_ALT);
@@ -95,7 +129,37 @@ __global__ __launch_bounds__(NT) void align_kernel(AlignLaunch a) {
   const float NEG = -INFINITY;
 
   int g[NGAP];
-  int st = lattice_setup<NT, R>(cl, C, a.tok_cls, a.gap_cls, alt, misc, g);
+  int st;
+  unsigned om = 0;                              // OPT: bit r = "token k - 1 is optional", k this thread's slot r: B_k has skip arcs
+  if constexpr (OPT) {
+    // the clip's flags, before anything else: a value other than 0 | 1 is status 4; a clip without any flag and with fewer frames than
+    // tokens is wfl_align's status 1, whatever its classes are
+    if (tid == 0) { misc[2] = 0; misc[3] = 0; }
+    __syncthreads();
+    bool any = false, bad = false;
+    for (int k = tid; k < N; k += NT) {
+      const int f = a.tok_opt[cl.tok_off + k];
+      any |= f != 0;
+      bad |= f != 0 && f != 1;
+    }
+    if (any) misc[2] = 1;
+    if (bad) misc[3] = 1;
+    __syncthreads();
+    const bool none = misc[2] == 0, badf = misc[3] != 0;
+    __syncthreads();                            // (lattice_setup writes misc[0]; misc[2] is written again at the end states)
+    if (N <= NT * R - 1 && N <= MAX_TOKENS && T < N && none) st = 1;
+    else st = lattice_setup<NT, R, true>(cl, C, a.tok_cls, a.gap_cls, alt, misc, g);
+    if (st == 0 && badf) st = 4;
+    if (st == 0) {
+#pragma unroll
+      for (int r = 0; r < R; ++r) {
+        const int k1 = tid * R + r - 1;        // (never below 0 or past the tokens: such a slot has no skip arc)
+        if (k1 >= 0 && k1 < N && a.tok_opt[cl.tok_off + k1] != 0) om |= 1u << r;
+      }
+    }
+  } else {
+    st = lattice_setup<NT, R>(cl, C, a.tok_cls, a.gap_cls, alt, misc, g);
+  }
   int dm[MIND ? R : 1];                         // this thread's slots' minimum durations, in registers
   if constexpr (MIND) {
     if (st == 0) {                              // (the same in every thread).  A D_k outside 1 .. MAX_MIN_FRAMES: status 4
@@ -114,6 +178,9 @@ __global__ __launch_bounds__(NT) void align_kernel(AlignLaunch a) {
   }
   if (st != 0 || T == 0) {
     for (int t = tid; t < T; t += NT) { ids[t] = a.o_id; tokp[t] = -1; }
+    if constexpr (OPT) {
+      for (int k = tid; k < N; k += NT) a.skipped[cl.tok_off + k] = 0;
+    }
     if (tid == 0) { a.score[cl.clip] = 0.f; a.status[cl.clip] = st; }
     return;
   }
@@ -132,8 +199,16 @@ __global__ __launch_bounds__(NT) void align_kernel(AlignLaunch a) {
 #pragma unroll
       for (int j = 0; j < CHAIN; ++j) H[r][j] = NEG;
   }
-  if (tid == 0) G[0] = 0.f;                    // a virtual frame -1 in G_0: frame 0 starts in G_0 or B_0
-  xch[NT + tid] = make_float2(NEG, NEG);
+  if (tid == 0) G[0] = 0.f;                    // a virtual frame -1 in G_0: frame 0 starts in G_0 or B_0 (OPT: or, skipping token 0, B_1)
+  float* xo = (float*)xch;                     // OPT: [2][XN][NT]
+  float lam = 0.f;
+  if constexpr (OPT) {
+    lam = a.lambda;
+#pragma unroll
+    for (int j = 0; j < XN; ++j) xo[(XN + j) * NT + tid] = NEG;
+  } else {
+    xch[NT + tid] = make_float2(NEG, NEG);
+  }
   stage.load(0);
   stage.store(0);
   stage.load(1);
@@ -163,7 +238,18 @@ __global__ __launch_bounds__(NT) void align_kernel(AlignLaunch a) {
     }
     const float* row = stage.row(c, tin);
     const float eg = gap_emission(row, g);
-    float2 nb = tid > 0 ? xch[((t + 1) & 1) * NT + tid - 1] : make_float2(NEG, NEG);
+    float2 nb;
+    float nG1 = NEG, nB2 = NEG, nI2 = NEG;      // OPT: G of the left thread's last slot, B and I of the slot before it
+    if constexpr (OPT) {
+      const float* xp = xo + ((t + 1) & 1) * XN * NT + tid - 1;
+      nb = tid > 0 ? make_float2(xp[0], xp[NT]) : make_float2(NEG, NEG);
+      if (tid > 0) { nG1 = xp[2 * NT]; nB2 = xp[3 * NT]; nI2 = xp[4 * NT]; }
+      nG1 -= sub;
+      nB2 -= sub;
+      nI2 -= sub;
+    } else {
+      nb = tid > 0 ? xch[((t + 1) & 1) * NT + tid - 1] : make_float2(NEG, NEG);
+    }
     nb.x -= sub;
     nb.y -= sub;
     unsigned bits[K::WPT];
@@ -181,6 +267,18 @@ __global__ __launch_bounds__(NT) void align_kernel(AlignLaunch a) {
       unsigned cg = 0;
       if (pI1 > m) { m = pI1; cg = 1; }
       if (pB1 > m) { m = pB1; cg = 2; }
+      float mb = m;                            // B_k: G_k's three, then the skip arcs over token k - 1
+      unsigned cb = cg;
+      if constexpr (OPT) {
+        if ((om >> r) & 1u) {
+          const float sG = (r ? G[r > 0 ? r - 1 : 0] : nG1) - lam;
+          const float sI = (r >= 2 ? I[r > 1 ? r - 2 : 0] : r == 1 ? nb.y : nI2) - lam;
+          const float sB = (r >= 2 ? B[r > 1 ? r - 2 : 0] : r == 1 ? nb.x : nB2) - lam;
+          if (sG > mb) { mb = sG; cb = 3; }
+          if (sI > mb) { mb = sI; cb = 4; }
+          if (sB > mb) { mb = sB; cb = 5; }
+        }
+      }
       float mi = I[r];
       unsigned ci = 0;
       float x = B[r];                          // what I_k is entered from
@@ -194,13 +292,26 @@ __global__ __launch_bounds__(NT) void align_kernel(AlignLaunch a) {
       if constexpr (WIN) eb = win_mask(eb, t, wn[r]);
       G[r] = k <= N ? m + eg : NEG;
       if constexpr (MIND) chain_shift(H[r], B[r], ei, dm[r]);
-      B[r] = m + eb;
+      if constexpr (OPT) B[r] = mb + eb;
+      else B[r] = m + eb;
       I[r] = mi + ei;
       bits[(6 * r) >> 5] |= cg << ((6 * r) & 31);
-      bits[(6 * r + 2) >> 5] |= cg << ((6 * r + 2) & 31);
-      bits[(6 * r + 4) >> 5] |= ci << ((6 * r + 4) & 31);
+      if constexpr (OPT) {                     // 2 bits G, 3 bits B, 1 bit I: no field straddles a word (6 r + 2 .. 6 r + 4 never holds bit 32)
+        bits[(6 * r + 2) >> 5] |= cb << ((6 * r + 2) & 31);
+        bits[(6 * r + 5) >> 5] |= ci << ((6 * r + 5) & 31);
+      } else {
+        bits[(6 * r + 2) >> 5] |= cg << ((6 * r + 2) & 31);
+        bits[(6 * r + 4) >> 5] |= ci << ((6 * r + 4) & 31);
+      }
     }
-    if constexpr (MIND) xch[(t & 1) * NT + tid] = make_float2(dm[R - 1] > 1 ? NEG : B[R - 1], I[R - 1]);
+    if constexpr (OPT) {
+      float* xq = xo + (t & 1) * XN * NT + tid;
+      xq[0] = B[R - 1];
+      xq[NT] = I[R - 1];
+      xq[2 * NT] = G[R - 1];
+      xq[3 * NT] = B[R - 2];
+      xq[4 * NT] = I[R - 2];
+    } else if constexpr (MIND) xch[(t & 1) * NT + tid] = make_float2(dm[R - 1] > 1 ? NEG : B[R - 1], I[R - 1]);
     else xch[(t & 1) * NT + tid] = make_float2(B[R - 1], I[R - 1]);
     unsigned* bw = bp + ((long)t * NT + tid) * K::WPT;
 #pragma unroll
@@ -244,6 +355,15 @@ __global__ __launch_bounds__(NT) void align_kernel(AlignLaunch a) {
     for (int r = 0; r < R; ++r)
       if (tid * R + r == N - 1 && dm[r] > 1) fin[2] = NEG;
   }
+  if constexpr (OPT) {                          // the ends that skip token N - 1: fin[3] = G_{N-1}, fin[4] = I_{N-2}, fin[5] = B_{N-2}
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+      const int k = tid * R + r;
+      if (k == N - 1) fin[3] = G[r];
+      if (k == N - 2) { fin[4] = I[r]; fin[5] = B[r]; }
+    }
+    if (tid == 0) misc[3] = N >= 1 ? a.tok_opt[cl.tok_off + N - 1] : 0;
+  }
   __syncthreads();
   float best = 0.f;
   if (tid == 0) {
@@ -253,16 +373,31 @@ __global__ __launch_bounds__(NT) void align_kernel(AlignLaunch a) {
       if (fin[1] > best) { best = fin[1]; s = 3 * N - 1; }
       if (fin[2] > best) { best = fin[2]; s = 3 * N - 2; }
     }
+    if constexpr (OPT) {
+      if (N >= 1 && misc[3]) {
+        if (fin[3] - lam > best) { best = fin[3] - lam; s = 3 * N - 3; }
+        if (N >= 2) {
+          if (fin[4] - lam > best) { best = fin[4] - lam; s = 3 * N - 4; }
+          if (fin[5] - lam > best) { best = fin[5] - lam; s = 3 * N - 5; }
+        }
+      }
+    }
     misc[1] = s;
-    if constexpr (WIN || MIND) misc[2] = best == NEG;
+    if constexpr (WIN || MIND || OPT) misc[2] = best == NEG;
   }
   __syncthreads();
-  if constexpr (WIN || MIND) {
-    if (misc[2]) {                              // no path meets every window and duration: status 1, the backpointers never walked
-      for (int t = tid; t < T; t += NT) { ids[t] = a.o_id; tokp[t] = -1; }
+  if constexpr (WIN || MIND || OPT) {
+    if (misc[2]) {                              // no path meets every window and duration (OPT: or too few frames): status 1, the
+      for (int t = tid; t < T; t += NT) { ids[t] = a.o_id; tokp[t] = -1; }            // backpointers never walked
+      if constexpr (OPT) {
+        for (int k = tid; k < N; k += NT) a.skipped[cl.tok_off + k] = 0;
+      }
       if (tid == 0) { a.score[cl.clip] = 0.f; a.status[cl.clip] = 1; }
       return;
     }
+  }
+  if constexpr (OPT) {                          // every token skipped, until a frame of the path carries it (the last pass, behind barriers)
+    for (int k = tid; k < N; k += NT) a.skipped[cl.tok_off + k] = 1;
   }
 
   // ---- backtrace, ALIGN_W frames per window
@@ -272,7 +407,7 @@ __global__ __launch_bounds__(NT) void align_kernel(AlignLaunch a) {
     const int tlo = max(1, thi - ALIGN_W + 1);
     const int nf = thi - tlo + 1;
     const int k_hi = min(max(s / 3, 0), N);
-    const int k_lo = max(0, k_hi - nf);
+    const int k_lo = max(0, k_hi - (OPT ? 2 * nf : nf));      // (OPT: a frame may step back two tokens)
     const int th_lo = k_lo / R, th_hi = k_hi / R;
     const int nw = (th_hi - th_lo + 1) * K::WPT;
     for (int e = tid; e < nf * nw; e += NT) {
@@ -291,16 +426,17 @@ __global__ __launch_bounds__(NT) void align_kernel(AlignLaunch a) {
         }
         const int k = s / 3, j = s - 3 * k;
         const int th = k / R, r = k - th * R;
-        const int pos = 2 * (3 * r + j);
+        const int pos = OPT ? 6 * r + (j == 0 ? 0 : j == 1 ? 2 : 5) : 2 * (3 * r + j);
+        const unsigned field = OPT ? (j == 0 ? 3u : j == 1 ? 7u : 1u) : 3u;
         const int wi = (t - tlo) * nw + (th - th_lo) * K::WPT + (pos >> 5);
-        const unsigned ch = (wi >= 0 && wi < nf * nw) ? (win[wi] >> (pos & 31)) & 3u : 0u;
+        const unsigned ch = (wi >= 0 && wi < nf * nw) ? (win[wi] >> (pos & 31)) & field : 0u;
         if constexpr (MIND) {
           if (j == 2 && ch == 1 && k < N) {     // I_k entered at t: from B_k for D_k <= 2, else through D_k - 2 chain frames
             const int d = a.tok_min[cl.tok_off + k];
             if (d >= 3) { chain = d - 2; continue; }
           }
         }
-        s = j == 2 ? s - (int)ch : 3 * k - (int)ch;
+        s = j == 2 ? s - (int)ch : 3 * k - (int)ch;      // (OPT: B_k's 3, 4, 5 are G_{k-1}, I_{k-2}, B_{k-2} = 3 k - 3, - 4, - 5)
         s = max(s, 0);
       }
       misc[1] = s;
@@ -335,6 +471,9 @@ __global__ __launch_bounds__(NT) void align_kernel(AlignLaunch a) {
     }
     ids[t] = id;
     tokp[t] = tk;
+    if constexpr (OPT) {
+      if (tk >= 0) a.skipped[cl.tok_off + tk] = 0;
+    }
   }
   lsum = wave_sum(lsum);
   if (lane == 0) red[wave] = lsum;
@@ -355,6 +494,14 @@ long clip_words(int T, int N) {
   return round64((long)T * per_frame);      // (256-byte aligned)
 }
 
+// the same for wfl_align_optional: a clip with fewer frames than tokens may still have a path (it skips tokens), so it has its words
+long clip_words_opt(int T, int N) {
+  const int c = cfg_of(N);
+  if (c == NCFG || T <= 0) return 0;
+  const int per_frame = dispatch_cfg(c, [](auto sh) { return decltype(sh)::NT * Cfg<decltype(sh)::NT, decltype(sh)::R>::WPT; });
+  return round64((long)T * per_frame);      // (wfl_align's own figure wherever T >= N)
+}
+
 }  // namespace
 
 extern "C" {
@@ -363,40 +510,51 @@ int64_t wfl_align_workspace_bytes(const int32_t* n_frames_host, const int32_t* n
   return clips_workspace_bytes(n_frames_host, n_tok_host, n_clips, clip_words);
 }
 
+int64_t wfl_align_optional_workspace_bytes(const int32_t* n_frames_host, const int32_t* n_tok_host, int32_t n_clips) {
+  return clips_workspace_bytes(n_frames_host, n_tok_host, n_clips, clip_words_opt);
+}
+
 }  // extern "C"
 
 namespace {
 
-// wfl_align (WIN false), wfl_align_windowed and wfl_align_min_duration (MIND, with or without windows): one host path
-template <bool WIN, bool MIND>
+// wfl_align (WIN false), wfl_align_windowed, wfl_align_min_duration (MIND, with or without windows) and wfl_align_optional (OPT, with or
+// without windows; tok_opt, skipped and skip_penalty are its alone): one host path
+template <bool WIN, bool MIND, bool OPT = false>
 int align_batch(const char* fn, const float* logits, int64_t ldl, int32_t C, int32_t o_id, const int64_t* frame_off_host,
                 const int32_t* n_frames_host, const int32_t* tok_off_host, const int32_t* n_tok_host, const int32_t* tok_cls,
                 const int32_t* tok_win, const int32_t* tok_min, const int32_t* gap_cls, int32_t n_clips, void* workspace,
-                int64_t workspace_bytes, int32_t* ids, int32_t* tok, float* score, int32_t* status, void* stream) {
-  const int64_t need = wfl_align_workspace_bytes(n_frames_host, n_tok_host, n_clips);
+                int64_t workspace_bytes, int32_t* ids, int32_t* tok, float* score, int32_t* status, void* stream,
+                const int32_t* tok_opt = nullptr, float skip_penalty = 0.f, int32_t* skipped = nullptr) {
+  const int64_t need = OPT ? wfl_align_optional_workspace_bytes(n_frames_host, n_tok_host, n_clips)
+                           : wfl_align_workspace_bytes(n_frames_host, n_tok_host, n_clips);
   bool any_tok = false, any_frame = false;
   int rc = check_clip_args(fn, C, o_id, ldl, frame_off_host, n_frames_host, tok_off_host, n_tok_host, n_clips, need, any_tok, any_frame);
-  if (rc || n_clips == 0) return rc;
-  if (!score || !status || !gap_cls || (any_tok && (!tok_cls || (WIN && !tok_win) || (MIND && !tok_min))) ||
+  if (rc) return rc;
+  if (OPT && !(skip_penalty >= 0.f && skip_penalty <= 3.0e38f)) return fail(fn, -1, "skip_penalty must be a finite number >= 0");
+  if (n_clips == 0) return 0;
+  if (!score || !status || !gap_cls || (any_tok && (!tok_cls || (WIN && !tok_win) || (MIND && !tok_min) || (OPT && (!tok_opt || !skipped)))) ||
       (any_frame && (!logits || !ids || !tok)))
     return fail(fn, -1, "null device pointer");
   if ((rc = check_workspace(fn, need, workspace, workspace_bytes))) return rc;
   hipStream_t s = (hipStream_t)stream;
-  AlignLaunch a{};
+  std::conditional_t<OPT, AlignLaunchOpt, AlignLaunch> a{};
   a.logits = logits; a.ldl = ldl; a.C = C; a.o_id = o_id; a.tok_cls = tok_cls; a.gap_cls = gap_cls; a.tok_win = tok_win; a.tok_min = tok_min;
   a.bp = (unsigned*)workspace; a.ids = ids; a.tok = tok; a.score = score; a.status = status;
+  if constexpr (OPT) { a.tok_opt = tok_opt; a.skipped = skipped; a.lambda = skip_penalty; }
   return launch_clips<NCFG>(
       a, n_clips,
       [&](int b, long off, LatClip& c, int& cfg) {
         const int T = n_frames_host[b], N = n_tok_host[b];
         c = LatClip{(long)frame_off_host[b], off, T, tok_off_host[b], N, b};
         cfg = cfg_of(N) < NCFG ? cfg_of(N) : 0;   // over the cap: every kernel reports status 2 before it touches the workspace; the smallest
-        return clip_words(T, N);
+        return OPT ? clip_words_opt(T, N) : clip_words(T, N);
       },
-      [&](int cfg, const AlignLaunch& a) {
+      [&](int cfg, const auto& a) {
         return dispatch_cfg(cfg, [&](auto sh) {
           constexpr int NT = decltype(sh)::NT, R = decltype(sh)::R;
-          return launch_cfg<align_kernel<NT, R, WIN, MIND>, NT, Cfg<NT, R>::LDS>(fn, a, s);
+          using K = std::conditional_t<OPT, CfgOpt<NT, R>, Cfg<NT, R>>;
+          return launch_cfg<align_kernel<NT, R, WIN, MIND, OPT>, NT, K::LDS>(fn, a, s);
         });
       });
 }
@@ -429,6 +587,20 @@ int32_t wfl_align_min_duration(const float* logits, int64_t ldl, int32_t C, int3
                                            tok_min, gap_cls, n_clips, workspace, workspace_bytes, ids, tok, score, status, stream)
                  : align_batch<false, true>(fn, logits, ldl, C, o_id, frame_off_host, n_frames_host, tok_off_host, n_tok_host, tok_cls,
                                             nullptr, tok_min, gap_cls, n_clips, workspace, workspace_bytes, ids, tok, score, status, stream);
+}
+
+int32_t wfl_align_optional(const float* logits, int64_t ldl, int32_t C, int32_t o_id, const int64_t* frame_off_host,
+                           const int32_t* n_frames_host, const int32_t* tok_off_host, const int32_t* n_tok_host, const int32_t* tok_cls,
+                           const int32_t* tok_win, const int32_t* gap_cls, int32_t n_clips, const int32_t* tok_opt, float skip_penalty,
+                           void* workspace, int64_t workspace_bytes, int32_t* ids, int32_t* tok, float* score, int32_t* skipped,
+                           int32_t* status, void* stream) {
+  const char* fn = "wfl_align_optional";
+  return tok_win ? align_batch<true, false, true>(fn, logits, ldl, C, o_id, frame_off_host, n_frames_host, tok_off_host, n_tok_host, tok_cls,
+                                                  tok_win, nullptr, gap_cls, n_clips, workspace, workspace_bytes, ids, tok, score, status,
+                                                  stream, tok_opt, skip_penalty, skipped)
+                 : align_batch<false, false, true>(fn, logits, ldl, C, o_id, frame_off_host, n_frames_host, tok_off_host, n_tok_host,
+                                                   tok_cls, nullptr, nullptr, gap_cls, n_clips, workspace, workspace_bytes, ids, tok, score,
+                                                   status, stream, tok_opt, skip_penalty, skipped);
 }
 
 }  // extern "C"

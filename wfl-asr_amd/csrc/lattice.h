@@ -194,13 +194,14 @@ static __device__ __forceinline__ void chain_shift_back(float (&c)[CHAIN_BACK], 
 
 // ---- lattice setup of a clip -> status: 2 over the cap (of the ABI or of this configuration), 1 fewer frames than tokens, 4 a class id
 // out of range / a token without alternative / no gap class, 0: alt[] (LDS, visible to the block) and g[] (-1 unused) hold the lattice.
-// `flag`: one LDS word.  The status is the same in every thread.
-template <int NT, int R>
+// `flag`: one LDS word.  The status is the same in every thread.  ANY_T (wfl_align_optional alone, whose paths may skip tokens): fewer
+// frames than tokens is no status here, only "tokens and no frame" is; the search itself finds a clip without path.
+template <int NT, int R, bool ANY_T = false>
 static __device__ __forceinline__ int lattice_setup(const LatClip& cl, int C, const int* tok_cls, const int* gap_cls, int4* alt, int* flag,
                                                     int (&g)[NGAP]) {
   const int tid = threadIdx.x, N = cl.N;
   if (N > NT * R - 1 || N > MAX_TOKENS) return 2;
-  if (cl.T < N) return 1;
+  if (ANY_T ? (cl.T == 0 && N > 0) : cl.T < N) return 1;
   if (tid == 0) *flag = 0;
   __syncthreads();
   bool bad = false;

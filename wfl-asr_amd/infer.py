@@ -32,7 +32,7 @@ from . import decode as DC
 from . import native_post as npost
 from . import postprocess as pp
 from ._lib import back_to_back
-from .options import ALIGN_MODES, DECODE_MODES, PostOptions, parse_min_duration, resolve
+from .options import ALIGN_MODES, DECODE_MODES, PostOptions, parse_min_duration, resolve, unknown_optional_tokens
 from .tagger import BIOPhonemeTagger, raise_on_status
 
 frame_duration = pp.FRAME_DURATION
@@ -423,10 +423,10 @@ class Labeler:
     def label_files(self, audio_paths, lang_id=None, confidence_threshold=0.0, verbose=True, align=None, align_scores=None,
                     decode=None, switch_penalty=None, decode_scores=None, phoneme_bigram=None, bigram_weight=None, align_draft=None,
                     draft_tolerance=None, align_edits=None, align_insertions=None, min_duration=None, duration_scores=None,
-                    bigram_scores=None):
+                    optional_tokens=None, skip_penalty=None, bigram_scores=None):
         """-> list (per file) of [(start_s, end_s, phoneme)] after merge + forced alignment; with align_scores, duration_scores,
         decode_scores or bigram_scores, (that list, scores); with align_edits the tuple goes on with one more list, edits, and with
-        align_insertions it ends with one more, insertions.
+        align_insertions it ends with one more, insertions; with optional_tokens it ends with the list skipped.
 
         align: "greedy" -- a `{audio}.txt` transcript is matched onto the freely decoded segments (infer.py:30-60, 312-319);
         "viterbi" -- files with a transcript are aligned by a search over their frame logits on the GPU (align.py: one segment
@@ -492,29 +492,45 @@ class Labeler:
         duration_scores (with a min_duration only; None: config postprocess.duration_scores, else off): align_scores for an
         alignment under minimum durations -- the same scores[i] (align.FileScore), from align.duration_posteriors over the
         minimum-duration lattice of the search, on the PackedClips it ran on.  A file whose durations were dropped is scored by
-        align.alignment_posteriors, over the lattice without them it was searched on, and one line says so."""
+        align.alignment_posteriors, over the lattice without them it was searched on, and one line says so.
+
+        optional_tokens (with align "viterbi" only; None: config postprocess.optional_tokens, else none): a list of token names
+        (output names, as a transcript spells them), or "*" for every token -- the transcript tokens a path may leave out, at most
+        one between two kept ones (align.viterbi_align_optional), each at skip_penalty nats (>= 0; None: config
+        postprocess.skip_penalty, else 0).  The segments of such a file lack the skipped tokens, one line says how many, and
+        skipped[i] is one align.SkippedToken per token left out (None for a file that was not aligned that way).  It combines with
+        align_draft (the names are the draft's labels; kept tokens hold their windows); min_duration and the scoring options beside
+        it are refused.  A name that is no output name of the label set is refused by name."""
         opts = self.options(align=align, align_scores=align_scores, decode=decode, switch_penalty=switch_penalty,
                             decode_scores=decode_scores, phoneme_bigram=phoneme_bigram, bigram_weight=bigram_weight,
                             bigram_scores=bigram_scores, align_draft=align_draft, draft_tolerance=draft_tolerance,
                             align_edits=align_edits, align_insertions=align_insertions, min_duration=min_duration,
-                            duration_scores=duration_scores)
+                            duration_scores=duration_scores, optional_tokens=optional_tokens, skip_penalty=skip_penalty)
         edits = {} if opts.align_edits else None
         insertions = {} if opts.align_insertions else None
+        skipped = {} if opts.optional_tokens is not None else None
         final, scores = self._label_scored(audio_paths, opts, lang_id, confidence_threshold, verbose, edits=edits,
-                                           insertions=insertions)
+                                           insertions=insertions, skipped=skipped)
         out = (final, scores) if opts.scored else (final,)
         if opts.align_edits:
             out += ([edits.get(fi) for fi in range(len(audio_paths))],)
         if opts.align_insertions:
             out += ([insertions.get(fi) for fi in range(len(audio_paths))],)
+        if skipped is not None:
+            out += ([skipped.get(fi) for fi in range(len(audio_paths))],)
         return out if len(out) > 1 else final
 
-    def _label_scored(self, audio_paths, opts, lang_id, confidence_threshold, verbose, moves=None, edits=None, insertions=None):
+    def _label_scored(self, audio_paths, opts, lang_id, confidence_threshold, verbose, moves=None, edits=None, insertions=None,
+                      skipped=None):
         """label_files for the resolved options `opts`, always -> (segments, scores): the files are split once into those a transcript is
         Viterbi-aligned to, those the grammar search decodes and those left to the argmax decode, and each subset's results go back to
         its files' places.  moves: a dict that takes {file index: [DraftMove]} for the files aligned inside their draft's windows.
         edits (opts.align_edits): a dict that takes {file index: [TokenEdit]} for the files that were Viterbi-aligned; insertions
-        (opts.align_insertions): the same with [PlaceInsertion]."""
+        (opts.align_insertions): the same with [PlaceInsertion]; skipped (opts.optional_tokens): the same with [SkippedToken]."""
+        unknown = (unknown_optional_tokens(opts.optional_tokens, self._names_for(self._lang_name(lang_id))[1])
+                   if opts.optional_tokens not in (None, "*") else [])
+        if unknown:
+            raise ValueError(f"optional_tokens: {', '.join(repr(n) for n in unknown)} is no output name of this model's label set")
         trans = self._bigram_table(opts.phoneme_bigram, opts.switch_penalty, opts.bigram_weight) if opts.phoneme_bigram else None
         if opts.decode == "viterbi" and int(self.config["postprocess"].get("median_filter", 0)) > 1:
             print("decode: viterbi -- postprocess.median_filter is not applied (the switch penalty takes its place)")
@@ -551,7 +567,7 @@ class Labeler:
                                       confidence_threshold, verbose)
             for fi, rec in zip(with_t, got):
                 final[fi], scores[fi] = rec.segments, rec.score
-                for into, value in ((moves, rec.moves), (edits, rec.edits), (insertions, rec.insertions)):
+                for into, value in ((moves, rec.moves), (edits, rec.edits), (insertions, rec.insertions), (skipped, rec.skipped)):
                     if into is not None and value is not None:
                         into[fi] = value
         return final, scores
@@ -852,10 +868,11 @@ class Labeler:
                 paths = [audio_paths[fi] for fi in run]
                 frames, lg = self._file_rows(rows, by_file, run)
                 chunks = [self._chunk_plan(rows, by_file[fi], fi) for fi in run]
+                flags = _clip_flags([transcripts[fi] for fi in run], opts)
                 wins, mins = _clip_constraints(paths, frames, chunks, [transcripts[fi] for fi in run],
-                                               [drafts[fi] for fi in run], opts)
+                                               [drafts[fi] for fi in run], opts, flags)
                 batch = AL.AlignBatch.of(lg, frames, [plans[fi] for fi in run], [AL.gap_classes(self.labels, transcripts[fi]) for fi in run],
-                                         self.labels.index("O"), wins, mins)
+                                         self.labels.index("O"), wins, mins, flags)
                 found = _search(batch, paths, opts)
                 scored = _score(found, opts, sub_pairs)
                 for b, fi in enumerate(run):
@@ -894,15 +911,27 @@ class Labeler:
         """Stage 5: clip b of a searched wave -> its file's ViterbiLabel, or None (with a line) for a clip the search did not align."""
         batch = found.batch
         n, pos = batch.frames[b], int(batch.f0[b])
+        flags = batch.opts[b] if batch.opts is not None else None
         if found.status[b] != AL.STATUS_OK:
-            why = {AL.STATUS_INFEASIBLE: f"{len(tr)} tokens for {n} frames",
+            infeasible = f"{len(tr)} tokens for {n} frames"
+            if flags is not None:
+                infeasible = f"{len(tr)} tokens need {AL.min_frames_needed(flags)} frames with their optional ones skipped, for {n} frames"
+            why = {AL.STATUS_INFEASIBLE: infeasible,
                    AL.STATUS_OVER_CAP: f"{len(tr)} tokens, over the cap of {AL.MAX_TOKENS}"}.get(int(found.status[b]),
                                                                                                f"status {int(found.status[b])}")
             print(f"{found.paths[b]}: viterbi alignment not possible ({why}); using the greedy alignment")
             return None
         tok = found.tok[pos:pos + n]
-        segs = AL.path_segments(found.ids[pos:pos + n], tok, *chunk_plan, self._table, batch.alts[b], tr, frame_duration)
-        moves = draft_moves(draft, segs, tok, batch.wins[b]) if batch.wins[b] is not None else None
+        left_out = skipped = None
+        if flags is not None:                             # the clip was searched with skip arcs: which tokens the path left out
+            k0 = sum(len(a) for a in batch.alts[:b])
+            left_out = found.skipped[k0:k0 + len(tr)]
+        segs = AL.path_segments(found.ids[pos:pos + n], tok, *chunk_plan, self._table, batch.alts[b], tr, frame_duration,
+                                skipped=left_out)
+        if flags is not None:
+            skipped = AL.skipped_tokens(left_out, segs, tr)
+            print(f"{found.paths[b]}: {len(skipped)} of {int(sum(flags))} optional tokens skipped")
+        moves = draft_moves(draft, segs, tok, batch.wins[b], left_out) if batch.wins[b] is not None else None
         score = None
         if b in scored.raw:
             score = AL.file_score(scored.raw[b][0], scored.raw[b][1], n, *scored.raw[b][2:], segs, frame_duration)
@@ -911,7 +940,7 @@ class Labeler:
             print(f"{found.paths[b]}: no alignment scores ({entry} status {code})")
         return ViterbiLabel(AL.with_end_pauses(free_segs, segs, tr), score, moves,
                             AL.token_edits(scored.edits[b], segs, sub_out) if b in scored.edits else None,
-                            AL.place_insertions(scored.insertions[b], segs, sub_out) if b in scored.insertions else None)
+                            AL.place_insertions(scored.insertions[b], segs, sub_out) if b in scored.insertions else None, skipped)
 
 
 class ViterbiLabel(NamedTuple):
@@ -921,6 +950,7 @@ class ViterbiLabel(NamedTuple):
     moves: list = None              # [DraftMove], a file aligned inside its draft's windows
     edits: list = None              # [TokenEdit] (opts.align_edits), a file that was aligned
     insertions: list = None         # [PlaceInsertion] (opts.align_insertions), the same
+    skipped: list = None            # [SkippedToken] (opts.optional_tokens), a file aligned with optional tokens
 
 
 class _Searched(NamedTuple):
@@ -933,6 +963,7 @@ class _Searched(NamedTuple):
     d_tok: torch.Tensor             # ... and tok / score on the device, for the scoring calls
     d_score: torch.Tensor
     packed: AL.PackedClips          # what the search ran on; None: packed inside viterbi_align, or a fallback round dropped constraints
+    skipped: np.ndarray = None      # viterbi_align_optional's flags of the batch's tokens, clip after clip; None: no clip has optional tokens
 
     @property
     def ok(self):
@@ -947,15 +978,26 @@ class _Scored(NamedTuple):
     insertions: dict                # the clip's rows of insertion_scores' ins
 
 
-def _clip_constraints(paths, frames, chunks, transcripts, drafts, opts):
+def _clip_flags(transcripts, opts):
+    """Stage 2 -> per clip the optional flags of its tokens (opts.optional_tokens), None for a clip without any; None: no clip has."""
+    if opts.optional_tokens is None:
+        return None
+    flags = [AL.optional_flags(tr, opts.optional_tokens) for tr in transcripts]
+    flags = [f if any(f) else None for f in flags]
+    return flags if any(f is not None for f in flags) else None
+
+
+def _clip_constraints(paths, frames, chunks, transcripts, drafts, opts, flags=None):
     """Stage 2 -> (wins, mins): per clip its draft's start windows and its opts.min_duration in frames, each None where there is
-    none or where the host rule align.windows_feasible finds no path (the durations inside the windows), with one line."""
+    none or where the host rule align.windows_feasible finds no path (the durations inside the windows), with one line.  flags
+    (_clip_flags): a clip with optional tokens keeps its windows whatever that rule says -- it knows no skips; the search's own
+    status 1 and _search's safety net decide."""
     wins, mins = [None] * len(paths), [None] * len(paths)
     for b, draft in enumerate(drafts):
         if draft is not None:
             cf, _, cc = chunks[b]
             w = AL.draft_windows(draft, cf, cc, opts.draft_tolerance, frame_duration)
-            if AL.windows_feasible(frames[b], w):
+            if (flags is not None and flags[b] is not None) or AL.windows_feasible(frames[b], w):
                 wins[b] = w
             else:
                 print(f"{paths[b]}: {DRAFT_INFEASIBLE}")
@@ -976,7 +1018,13 @@ def _search(batch, paths, opts) -> _Searched:
     the kernel found no path for inside its constraints is searched again, first without its durations, then without its windows."""
     scoring = opts.align_scores or opts.align_edits or opts.align_insertions
     packed = batch.pack(opts.duration_scores) if scoring or (opts.duration_scores and batch.min_frames is not None) else None
-    d_ids, d_tok, d_score, d_st = AL.viterbi_align(*batch.args(), packed=packed, windows=batch.windows, min_frames=batch.min_frames)
+    d_skip = None
+    if batch.optional is not None:                        # (the options refuse durations and scores beside optional tokens)
+        d_ids, d_tok, d_score, d_st, d_skip = AL.viterbi_align_optional(*batch.args(), batch.optional, opts.skip_penalty,
+                                                                        windows=batch.windows)
+        k0 = np.concatenate([[0], np.cumsum([len(a) for a in batch.alts])]).astype(np.int64)
+    else:
+        d_ids, d_tok, d_score, d_st = AL.viterbi_align(*batch.args(), packed=packed, windows=batch.windows, min_frames=batch.min_frames)
     status = d_st.cpu().numpy()
     for _ in range(2):
         again = [b for b in range(len(paths))
@@ -990,15 +1038,24 @@ def _search(batch, paths, opts) -> _Searched:
             else:
                 print(f"{paths[b]}: {DRAFT_INFEASIBLE}")
                 batch.wins[b] = None
-        sub = batch.select(again)
-        r_ids, r_tok, r_score, r_st = AL.viterbi_align(*sub.args(), frame_offsets=sub.f0, windows=sub.windows)
+        sub = batch.select(again)                         # (its clips keep their optional flags when they drop their windows)
+        if sub.optional is not None:
+            r_ids, r_tok, r_score, r_st, r_skip = AL.viterbi_align_optional(*sub.args(), sub.optional, opts.skip_penalty,
+                                                                            frame_offsets=sub.f0, windows=sub.windows)
+            j0 = 0
+            for b in again:
+                d_skip[int(k0[b]):int(k0[b + 1])] = r_skip[j0:j0 + int(k0[b + 1] - k0[b])]
+                j0 += int(k0[b + 1] - k0[b])
+        else:
+            r_ids, r_tok, r_score, r_st = AL.viterbi_align(*sub.args(), frame_offsets=sub.f0, windows=sub.windows)
         for j, b in enumerate(again):
             rows_b = slice(int(batch.f0[b]), int(batch.f0[b]) + batch.frames[b])
             d_ids[rows_b], d_tok[rows_b] = r_ids[rows_b], r_tok[rows_b]
             d_score[b], d_st[b] = r_score[j], r_st[j]
         status = d_st.cpu().numpy()
         packed = None                                     # (packed for the constraints that were dropped)
-    return _Searched(batch, paths, d_ids.cpu().numpy(), d_tok.cpu().numpy(), status, d_tok, d_score, packed)
+    return _Searched(batch, paths, d_ids.cpu().numpy(), d_tok.cpu().numpy(), status, d_tok, d_score, packed,
+                     d_skip.cpu().numpy() if d_skip is not None else None)
 
 
 def _score(found, opts, sub_pairs) -> _Scored:
@@ -1096,14 +1153,16 @@ class DraftMove(NamedTuple):
         return self.start_s - self.draft_start_s
 
 
-def draft_moves(draft, segments, tok, windows):
+def draft_moves(draft, segments, tok, windows, skipped=None):
     """Per token of a file aligned inside its draft's windows -> [DraftMove]: draft (start_s, end_s, label) and segments
-    (path_segments) one per token in order, tok the file's per-frame token index, windows the (lo, hi) rows the search was held to."""
+    (path_segments) one per token in order, tok the file's per-frame token index, windows the (lo, hi) rows the search was held to.
+    skipped (align.viterbi_align_optional's flags of the tokens; None: none): the segments are the kept tokens', and so are the rows."""
     tok = np.asarray(tok)
     opens = np.nonzero((tok >= 0) & (np.concatenate([[-1], tok[:-1]]) != tok))[0]        # one frame per token, in order
     first = {int(tok[t]): int(t) for t in opens[::-1]}
-    return [DraftMove(k, str(seg[2]), float(dr[0]), float(seg[0]), first[k] in (int(lo), int(hi)))
-            for k, (dr, seg, (lo, hi)) in enumerate(zip(draft, segments, windows))]
+    kept = [k for k in range(len(draft)) if skipped is None or not int(skipped[k])]
+    return [DraftMove(k, str(seg[2]), float(draft[k][0]), float(seg[0]), first[k] in (int(windows[k][0]), int(windows[k][1])))
+            for k, seg in zip(kept, segments)]
 
 
 def format_draft_moves_tsv(named_moves) -> str:
@@ -1270,6 +1329,16 @@ def _write_insertions(lab_path, rows):
         print(f"Transcript insertions saved to: {insertions_path(lab_path)}")
 
 
+def skipped_path(lab_path):
+    return os.path.splitext(lab_path)[0] + ".skipped.tsv"
+
+
+def _write_skipped(lab_path, rows):
+    """`{stem}.skipped.tsv` beside the .lab of a file that was aligned with optional tokens (None: no file)."""
+    if rows is not None:
+        _write_text(skipped_path(lab_path), AL.format_skipped_tsv(rows), "Skipped tokens")
+
+
 def _write_score(lab_path, segments, score):
     """The scores file of one labelled file beside its .lab, by the kind of its score (None: no file)."""
     if isinstance(score, DC.FreeScore):
@@ -1282,7 +1351,7 @@ def infer_audio(audio_path, config_path="config.yaml", checkpoint_path="best_mod
                 lang_id=None, sample=False, top_k=0, top_p=0.0, temperature=1.0, confidence_threshold=0.0, align=None,
                 align_scores=None, decode=None, switch_penalty=None, decode_scores=None, phoneme_bigram=None, bigram_weight=None,
                 align_draft=None, draft_tolerance=None, align_edits=None, align_insertions=None, min_duration=None,
-                duration_scores=None, bigram_scores=None):
+                duration_scores=None, optional_tokens=None, skip_penalty=None, bigram_scores=None):
     """align: "greedy" | "viterbi" | None (config postprocess.align, else greedy): how a `{audio}.txt` transcript is aligned
     (Labeler.label_files).  align_scores (viterbi only; None: config postprocess.align_scores): also write `{stem}.scores.tsv`
     beside the .lab when the file was Viterbi-aligned (format_scores_tsv).  decode: "argmax" | "viterbi" | None (config
@@ -1301,18 +1370,22 @@ def infer_audio(audio_path, config_path="config.yaml", checkpoint_path="best_mod
     min_duration (align viterbi only; None: config postprocess.min_duration): seconds, or {token name: seconds, "default": seconds}:
     the least time a transcript token occupies in the search (Labeler.label_files).  duration_scores (with a min_duration only; None:
     config postprocess.duration_scores): align_scores for that search, the same `{stem}.scores.tsv`, summed over the
-    minimum-duration lattice (align.duration_posteriors)."""
+    minimum-duration lattice (align.duration_posteriors).  optional_tokens / skip_penalty (align viterbi only; None: config
+    postprocess.optional_tokens / postprocess.skip_penalty): the transcript tokens a path may leave out, [NAME, ...] or "*", and the
+    nats each skipped one costs (Labeler.label_files); the .lab lacks the skipped tokens and `{stem}.skipped.tsv` lists them
+    (align.format_skipped_tsv)."""
     given = dict(align=align, align_scores=align_scores, decode=decode, switch_penalty=switch_penalty, decode_scores=decode_scores,
                  phoneme_bigram=phoneme_bigram, bigram_weight=bigram_weight, bigram_scores=bigram_scores, align_draft=align_draft,
                  draft_tolerance=draft_tolerance, align_edits=align_edits, align_insertions=align_insertions, min_duration=min_duration,
-                 duration_scores=duration_scores)
+                 duration_scores=duration_scores, optional_tokens=optional_tokens, skip_penalty=skip_penalty)
     _refuse_before_load(config_path, **given)
     lab = _labeler(config_path, checkpoint_path, device)
     opts = lab.options(**given)
     edits = {} if opts.align_edits else None
     insertions = {} if opts.align_insertions else None
+    skipped = {} if opts.optional_tokens is not None else None
     (segments,), (score,) = lab._label_scored([audio_path], opts, lang_id, confidence_threshold, True, edits=edits,
-                                              insertions=insertions)
+                                              insertions=insertions, skipped=skipped)
     if output_lab_path:
         if os.path.abspath(output_lab_path) == os.path.abspath(audio_path):
             # the reference would truncate the input WAV here (infer.py:410-411 + utils.py:77)
@@ -1323,6 +1396,8 @@ def infer_audio(audio_path, config_path="config.yaml", checkpoint_path="best_mod
             _write_edits(output_lab_path, edits.get(0))
         if insertions is not None:
             _write_insertions(output_lab_path, insertions.get(0))
+        if skipped is not None:
+            _write_skipped(output_lab_path, skipped.get(0))
     return segments
 
 
@@ -1330,11 +1405,12 @@ def infer_folder(folder_path: str, config_path: str = "config.yaml", checkpoint_
                  output_dir: str = "outputs", device: str = "cuda", lang_id: int = None, sample=False, top_k=0, top_p=0.0,
                  temperature=1.0, confidence_threshold=0.0, align=None, align_scores=None, decode=None, switch_penalty=None,
                  decode_scores=None, phoneme_bigram=None, bigram_weight=None, align_draft=None, draft_tolerance=None,
-                 align_edits=None, align_insertions=None, min_duration=None, duration_scores=None, bigram_scores=None):
+                 align_edits=None, align_insertions=None, min_duration=None, duration_scores=None, optional_tokens=None,
+                 skip_penalty=None, bigram_scores=None):
     given = dict(align=align, align_scores=align_scores, decode=decode, switch_penalty=switch_penalty, decode_scores=decode_scores,
                  phoneme_bigram=phoneme_bigram, bigram_weight=bigram_weight, bigram_scores=bigram_scores, align_draft=align_draft,
                  draft_tolerance=draft_tolerance, align_edits=align_edits, align_insertions=align_insertions, min_duration=min_duration,
-                 duration_scores=duration_scores)
+                 duration_scores=duration_scores, optional_tokens=optional_tokens, skip_penalty=skip_penalty)
     _refuse_before_load(config_path, **given)
     wav_files = sorted(f for f in os.listdir(folder_path) if f.lower().endswith(".wav"))
     os.makedirs(output_dir, exist_ok=True)
@@ -1350,7 +1426,8 @@ def infer_folder(folder_path: str, config_path: str = "config.yaml", checkpoint_
     moves = {}
     edits = {} if opts.align_edits else None
     insertions = {} if opts.align_insertions else None
-    all_segments, all_scores = (lab._label_scored(paths, opts, lang_id, confidence_threshold, True, moves, edits, insertions)
+    skipped = {} if opts.optional_tokens is not None else None
+    all_segments, all_scores = (lab._label_scored(paths, opts, lang_id, confidence_threshold, True, moves, edits, insertions, skipped)
                                 if paths else ([], []))
     for fi, (wav_file, segments, score) in enumerate(zip(wav_files, all_segments, all_scores)):
         print(f"\nInferencing: {wav_file}")
@@ -1361,6 +1438,8 @@ def infer_folder(folder_path: str, config_path: str = "config.yaml", checkpoint_
             _write_edits(lab_path, edits.get(fi))
         if insertions is not None:
             _write_insertions(lab_path, insertions.get(fi))
+        if skipped is not None:
+            _write_skipped(lab_path, skipped.get(fi))
         print("Predicted segments:")
         for start, end, ph in segments:
             print(f"({round(start, 2)}, {round(end, 2)}, {ph})")
@@ -1380,6 +1459,10 @@ def infer_folder(folder_path: str, config_path: str = "config.yaml", checkpoint_
         name = "draft_moves.tsv" if world == 1 else f"draft_moves.rank{rank}.tsv"
         _write_text(os.path.join(output_dir, name), format_draft_moves_tsv([(wav_files[fi], moves[fi]) for fi in sorted(moves)]),
                     "Draft moves")
+    if skipped is not None:
+        name = "skipped_tokens.tsv" if world == 1 else f"skipped_tokens.rank{rank}.tsv"
+        _write_text(os.path.join(output_dir, name), AL.format_folder_skipped_tsv([(wav_files[fi], skipped[fi]) for fi in sorted(skipped)]),
+                    "Skipped tokens of the folder")
     if opts.free_scores:
         name = "decode_scores.tsv" if world == 1 else f"decode_scores.rank{rank}.tsv"
         _write_text(os.path.join(output_dir, name),
@@ -1457,9 +1540,17 @@ def main(argv=None):
                   help="With --min-duration: --align-scores for the alignment under minimum durations; the same {stem}.scores.tsv "
                        "and alignment_scores.tsv, from a forward-backward pass over the minimum-duration lattice on the GPU. Default: "
                        "config postprocess.duration_scores, else off.")
+    @click.option("--optional", "optional_tokens", type=str, multiple=True,
+                  help="With --align viterbi: a transcript token name the alignment may leave out where the audio does not hold it "
+                       "(repeatable; '*' for every token), at most one between two kept tokens. The .lab lacks the skipped tokens; "
+                       "{stem}.skipped.tsv and, for a folder, skipped_tokens.tsv list them. Default: config "
+                       "postprocess.optional_tokens, else none.")
+    @click.option("--skip-penalty", "skip_penalty", type=float, default=None,
+                  help="With --optional: what a path pays per skipped token, in nats (>= 0). Default: config postprocess.skip_penalty, "
+                       "else 0.")
     def cli(path, checkpoint, config, output, lang_id, sample, top_k, top_p, temperature, device, confidence_threshold, align,
             align_scores, decode, switch_penalty, decode_scores, phoneme_bigram, bigram_weight, bigram_scores, align_draft,
-            draft_tolerance, align_edits, align_insertions, min_duration, duration_scores):
+            draft_tolerance, align_edits, align_insertions, min_duration, duration_scores, optional_tokens, skip_penalty):
         if switch_penalty is not None and not switch_penalty >= 0.0:
             raise click.UsageError("--switch-penalty must be >= 0 (nats)")
         if sample:
@@ -1493,7 +1584,8 @@ def main(argv=None):
                            decode_scores=decode_scores, phoneme_bigram=phoneme_bigram, bigram_weight=bigram_weight,
                            bigram_scores=bigram_scores, align_draft=align_draft, draft_tolerance=draft_tolerance,
                            align_edits=align_edits, align_insertions=align_insertions,
-                           min_duration=parse_min_duration(min_duration), duration_scores=duration_scores)
+                           min_duration=parse_min_duration(min_duration), duration_scores=duration_scores,
+                           optional_tokens=list(optional_tokens) or None, skip_penalty=skip_penalty)
         except ValueError as err:
             raise click.UsageError(str(err))
         output_path = inf_path if output == "." else output
@@ -1513,7 +1605,9 @@ def main(argv=None):
                   # the draft travels the same way: an empty path for "none", a tolerance only beside a draft
                   align_draft=opts.align_draft or "", draft_tolerance=opts.draft_tolerance if opts.align_draft else None,
                   align_edits=opts.align_edits, align_insertions=opts.align_insertions, min_duration=opts.min_duration,
-                  duration_scores=opts.duration_scores)
+                  duration_scores=opts.duration_scores,
+                  # a penalty only beside the tokens it prices (with none, none was given, or resolve had refused it)
+                  optional_tokens=opts.optional_tokens, skip_penalty=opts.skip_penalty if opts.optional_tokens is not None else None)
         if inf_path.is_dir():
             infer_folder(folder_path=str(inf_path), output_dir=str(output_path), **kw)
         else:

@@ -26,6 +26,15 @@ infer_folder (before any model is loaded) and the CLI all call `resolve` and car
   duration_scores off      17. needs align viterbi
                            18. needs a min_duration (it scores the minimum-duration lattice; without durations align_scores is the
                                option to ask for)
+  optional_tokens none    19. [NAME, ...] or "*": a list of token names (strings), or the string "*" for every token
+                           20. needs align viterbi (the skip arcs are arcs of that search)
+  skip_penalty    0        21. when given, a number >= 0 (nats per skipped token; no bool, no NaN)
+                           22. when given, needs optional_tokens (it is the price of skipping one)
+                           23. min_duration, align_scores, align_edits, align_insertions and duration_scores beside optional_tokens
+                               are refused (OPTIONAL_TOKENS_ERROR): their lattices have no skip arcs, and a score must speak of the
+                               lattice its search ran on
+                           (24. with the model known, Labeler.label_files: a name that is no output name of the label set is refused
+                               by name, `unknown_optional_tokens`)
 """
 from __future__ import annotations
 
@@ -47,6 +56,32 @@ MAX_MIN_FRAMES = 8                # the search's cap on a token's minimum durati
 MIN_DURATION_SCORES_ERROR = ("align_scores, align_edits and align_insertions cannot be combined with a min_duration: their passes score "
                              "the lattice without minimum durations, not the one the search ran on; drop postprocess.min_duration "
                              "(--min-duration) for the scoring run")
+
+
+OPTIONAL_TOKENS_ERROR = ("optional_tokens cannot be combined with min_duration, align_scores, align_edits, align_insertions or "
+                         "duration_scores: their lattices have no skip arcs, and a score must speak of the lattice the search ran on; "
+                         "drop postprocess.optional_tokens (--optional) for that run")
+
+
+def _optional_tokens(given):
+    """postprocess.optional_tokens -> its normalised, hashable form: None (absent, or an empty list), "*" (every token), or a sorted
+    tuple of distinct names.  Anything else breaks rule 19."""
+    if given is None:
+        return None
+    if isinstance(given, str):
+        if given == "*":
+            return "*"
+    elif isinstance(given, (list, tuple, set, frozenset)) and all(isinstance(x, str) and x for x in given):
+        return ("*" if "*" in given else tuple(sorted(set(given)))) or None
+    raise ValueError(f"optional_tokens must be a list of token names or '*', got {given!r}")
+
+
+def unknown_optional_tokens(optional_tokens, output_names):
+    """Rule 24, for the caller that knows the model: the names of `optional_tokens` that are no output name of the label set."""
+    if optional_tokens in (None, "*"):
+        return []
+    known = set(output_names)
+    return [n for n in optional_tokens if n not in known]
 
 
 def _min_duration(given):
@@ -123,16 +158,20 @@ class PostOptions(_SearchOptions):
         align_edits      False  score single substitutions and deletions of every aligned transcript
         align_insertions False  score single insertions at every place of every aligned transcript
         min_duration     None   the least time a transcript token occupies: seconds, or ((name, seconds), ...) sorted by name
-        duration_scores  False  score every alignment searched under a min_duration, over the minimum-duration lattice"""
+        duration_scores  False  score every alignment searched under a min_duration, over the minimum-duration lattice
+        optional_tokens  None   the tokens a path may leave out: "*", or a sorted tuple of names
+        skip_penalty     0.0    nats a path pays per skipped token (also stands for "not given")"""
     align_draft: Optional[str] = None
     draft_tolerance: float = DEFAULT_DRAFT_TOLERANCE
     align_edits: bool = False
     align_insertions: bool = False
     min_duration: object = None
     duration_scores: bool = False
+    optional_tokens: object = None
+    skip_penalty: float = 0.0
 
     def __new__(cls, *args, align_draft=None, draft_tolerance=DEFAULT_DRAFT_TOLERANCE, align_edits=False, align_insertions=False,
-                min_duration=None, duration_scores=False, **kw):
+                min_duration=None, duration_scores=False, optional_tokens=None, skip_penalty=0.0, **kw):
         self = super().__new__(cls, *args, **kw)
         object.__setattr__(self, "align_draft", align_draft)
         object.__setattr__(self, "draft_tolerance", draft_tolerance)
@@ -140,13 +179,16 @@ class PostOptions(_SearchOptions):
         object.__setattr__(self, "align_insertions", align_insertions)
         object.__setattr__(self, "min_duration", min_duration)
         object.__setattr__(self, "duration_scores", duration_scores)
+        object.__setattr__(self, "optional_tokens", optional_tokens)
+        object.__setattr__(self, "skip_penalty", skip_penalty)
         return self
 
     def __setattr__(self, name, value):
         raise AttributeError(f"PostOptions is read-only: cannot set {name!r}")
 
-    _KEYWORD = ("align_draft", "draft_tolerance", "align_edits", "align_insertions", "min_duration", "duration_scores")
-    _KEYWORD_DEFAULTS = (None, DEFAULT_DRAFT_TOLERANCE, False, False, None, False)
+    _KEYWORD = ("align_draft", "draft_tolerance", "align_edits", "align_insertions", "min_duration", "duration_scores",
+                "optional_tokens", "skip_penalty")
+    _KEYWORD_DEFAULTS = (None, DEFAULT_DRAFT_TOLERANCE, False, False, None, False, None, 0.0)
 
     def _draft(self):
         return self.align_draft, self.draft_tolerance
@@ -156,14 +198,15 @@ class PostOptions(_SearchOptions):
         return self.align_scores or self.free_scores or self.duration_scores
 
     def _later(self):
-        return self.align_draft, self.draft_tolerance, self.align_edits, self.align_insertions, self.min_duration, self.duration_scores
+        return tuple(getattr(self, k) for k in self._KEYWORD)
 
     # the NamedTuple helpers carry the keyword fields as well (the inherited ones know the tuple alone)
     @classmethod
     def _make(cls, iterable, align_draft=None, draft_tolerance=DEFAULT_DRAFT_TOLERANCE, align_edits=False, align_insertions=False,
-              min_duration=None, duration_scores=False):
+              min_duration=None, duration_scores=False, optional_tokens=None, skip_penalty=0.0):
         return cls(*iterable, align_draft=align_draft, draft_tolerance=draft_tolerance, align_edits=align_edits,
-                   align_insertions=align_insertions, min_duration=min_duration, duration_scores=duration_scores)
+                   align_insertions=align_insertions, min_duration=min_duration, duration_scores=duration_scores,
+                   optional_tokens=optional_tokens, skip_penalty=skip_penalty)
 
     def _replace(self, **kw):
         later = {k: kw.pop(k, getattr(self, k)) for k in self._KEYWORD}
@@ -199,7 +242,7 @@ def _number_ge0(x):
 
 def resolve(post, *, align=None, align_scores=None, decode=None, switch_penalty=None, decode_scores=None, phoneme_bigram=None,
             bigram_weight=None, bigram_scores=None, align_draft=None, draft_tolerance=None, align_edits=None,
-            align_insertions=None, min_duration=None, duration_scores=None) -> PostOptions:
+            align_insertions=None, min_duration=None, duration_scores=None, optional_tokens=None, skip_penalty=None) -> PostOptions:
     """post: the config's `postprocess` mapping (None: {}).  Per option the argument wins; None leaves it to `post[<option>]`, and a
     key that is absent (or None) to the default.  -> PostOptions, or ValueError for the first broken rule of the module's table."""
     post = post or {}
@@ -275,6 +318,19 @@ def resolve(post, *, align=None, align_scores=None, decode=None, switch_penalty=
     if duration_scores and min_duration is None:
         raise ValueError("duration_scores needs a min_duration (postprocess.min_duration): it scores the minimum-duration lattice of "
                          "that search; without durations align_scores is the option to ask for")
+    optional_tokens = _optional_tokens(pick("optional_tokens", optional_tokens))
+    if optional_tokens is not None and align != "viterbi":
+        raise ValueError("optional_tokens needs align='viterbi' (postprocess.align: viterbi): the skip arcs are arcs of the Viterbi "
+                         "search, the greedy match has none")
+    given = pick("skip_penalty", skip_penalty)
+    skip_penalty = 0.0 if given is None else _number_ge0(given)
+    if skip_penalty is None or skip_penalty == float("inf"):
+        raise ValueError(f"skip_penalty must be a number >= 0 (nats per skipped token), got {given!r}")
+    if given is not None and optional_tokens is None:
+        raise ValueError("skip_penalty needs optional_tokens (postprocess.optional_tokens): it is the price of skipping one of them")
+    if optional_tokens is not None and (min_duration is not None or align_scores or align_edits or align_insertions or duration_scores):
+        raise ValueError(OPTIONAL_TOKENS_ERROR)
     return PostOptions(align, align_scores, decode, switch_penalty, decode_scores, phoneme_bigram, bigram_weight, bigram_scores,
                        align_draft=align_draft, draft_tolerance=draft_tolerance, align_edits=align_edits,
-                       align_insertions=align_insertions, min_duration=min_duration, duration_scores=duration_scores)
+                       align_insertions=align_insertions, min_duration=min_duration, duration_scores=duration_scores,
+                       optional_tokens=optional_tokens, skip_penalty=skip_penalty)
