@@ -14,8 +14,9 @@
 // (proved against the definition by enumeration of edited transcripts in tests/test_align_edits_cpu.py).
 //
 // Phase 1, edits_fb_kernel: one workgroup per clip, configurations, slot ownership, staging, neighbour exchange and renormalisation as
-// post_kernel -- a sibling on the same lattice.h pieces, so post_kernel stays what it is.  One forward and one backward sweep, no
-// checkpoints: the planes A [T + 1][W], E [T][W], D [T][W] (W = round_up_64(N) floats a row) go to the workspace with, per frame, the
+// post_kernel, and the very same sweeps: both kernels run alpha and beta of csrc/lattice_sums.h (this one with the windows held at run
+// time and without the minimum-duration chain; A_k(t) reaches it through alpha_frame's hook).  Its own are the substitute-table check,
+// the planes and the offsets.  One forward and one backward sweep, no checkpoints: the planes A [T + 1][W], E [T][W], D [T][W] (W = round_up_64(N) floats a row) go to the workspace with, per frame, the
 // double offsets that alpha's and beta's renormalisations have subtracted so far (an absolute fp32 alpha of a long clip has no
 // resolution left).  A null tok_win is every window open.
 // Phase 2, edits_chain_kernel: one wave per (token, 64 substitutes), lanes over p: N P independent chains of T steps, two lae2 a step.
@@ -34,7 +35,7 @@
 // round64(N + 1) wide, A with slot N, F = beta(G_k) for k = 0 .. N in E's place, no D.  Phase 2 is insertions_chain_kernel, one wave
 // per (place, 64 substitutes) on the chain of edits_chain_kernel (edit_chain): (N + 1) P chains and no deletion column.  Frames before
 // j and after min(T - 1 - (N - j), hi_j - 1) contribute exact zeros and are skipped; nothing else is.
-#include "lattice.h"
+#include "lattice_sums.h"
 #include "wfl_asr.h"
 
 namespace {
@@ -87,19 +88,6 @@ struct ECfg : LdsBase<NT, R, 2 * 2 * NT * 8> {                     // its own be
   static constexpr int LDS = OFF_MISC + 64;
 };
 
-// log(exp a + exp b [+ exp c]); -inf in, -inf out (v_exp_f32 / v_log_f32)
-__device__ __forceinline__ float lae2(float a, float b) {
-  const float m = fmaxf(a, b);
-  const float ms = m == -INFINITY ? 0.f : m;
-  return ms + __logf(__expf(a - ms) + __expf(b - ms));
-}
-
-__device__ __forceinline__ float lae3(float a, float b, float c) {
-  const float m = fmaxf(a, fmaxf(b, c));
-  const float ms = m == -INFINITY ? 0.f : m;
-  return ms + __logf(__expf(a - ms) + __expf(b - ms) + __expf(c - ms));
-}
-
 // ---- phase 1: the sweeps of the transcript's own lattice -> A, E, D, the offsets, logZ; INS: A with slot N, F in E's place, no D
 template <int NT, int R, bool INS = false>
 __global__ __launch_bounds__(NT) void edits_fb_kernel(EditLaunch a) {
@@ -116,7 +104,7 @@ __global__ __launch_bounds__(NT) void edits_fb_kernel(EditLaunch a) {
   float* fin = (float*)(misc + 4);
 
   const LatClip cl = a.clip[blockIdx.x];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int tid = threadIdx.x;
   const int T = cl.T, N = cl.N, C = a.C, P = a.P;
   const float* Z = a.logits + cl.frame_off * a.ldl;
   const float NEG = -INFINITY;
@@ -160,37 +148,15 @@ __global__ __launch_bounds__(NT) void edits_fb_kernel(EditLaunch a) {
   float* pE = ws + lay.E;
   [[maybe_unused]] float* pD = ws + lay.D;
 
-  // ---- the per-frame log-sum-exp, in fp32 for the sweeps; what its rounding loses, in double for logZ (as post_kernel)
-  double lres = 0.0;
-  for (int t = tid; t < T; t += NT) {
-    const float* z = Z + (long)t * a.ldl;
-    float m = z[0];
-    for (int q = 1; q < C; ++q) m = fmaxf(m, z[q]);
-    double se = 0.0;
-    for (int q = 0; q < C; ++q) se += (double)expf(z[q] - m);
-    const double ld = (double)m + log(se);
-    const float lf = (float)ld;
-    lse[t] = lf;
-    lres += ld - (double)lf;
-  }
-  lres = wave_sum(lres);
-  if (lane == 0) red[wave] = lres;
-  __syncthreads();                             // (and the block sees lse[])
-  lres = 0.0;
-#pragma unroll
-  for (int w = 0; w < K::NW; ++w) lres += red[w];
+  // ---- the per-frame log-sum-exp, in fp32 for the sweeps; what its rounding loses, in double for logZ
+  const double lres = frame_lse<NT>(tid, Z, a.ldl, T, C, lse, red);
 
   LogitStages<NT, K::PR> stage(Z, a.ldl, T, C, ring);
   const int F = stage.F;
   float pre_l = 0.f;
-  auto load_stage = [&](int c) {               // (the backward sweep runs one stage ahead as well, down to c = -1)
-    stage.load(c, c >= 0);
-    pre_l = (tid < F && c >= 0 && c * F + tid < T) ? lse[c * F + tid] : 0.f;
-  };
-  auto store_stage = [&](int c) {
-    stage.store(c);
-    if (tid < F) lring[(c & 1) * FMAX + tid] = pre_l;
-  };
+  int pre_t = -1;                              // (no token ring here)
+  auto load_stage = [&](int c) { stage_load<false>(tid, stage, c, lse, nullptr, pre_l, pre_t); };
+  auto store_stage = [&](int c) { stage_store<false>(tid, stage, c, lring, nullptr, pre_l, pre_t); };
 
   int4 av[R];                                   // this thread's slots' alternatives
 #pragma unroll
@@ -198,6 +164,8 @@ __global__ __launch_bounds__(NT) void edits_fb_kernel(EditLaunch a) {
   const int4 avn = tid + 1 < NT ? alt[(tid + 1) * R] : make_int4(-1, -1, -1, -1);   // the next thread's first slot
 
   // ---- the forward sweep: A_k(t) is the step's `in`, relative to what alpha's renormalisations subtracted before frame t
+  // (lattice_sums.h with WIN, the windows being held at run time and open where there are none, and without MIND)
+  NoChain no;
   float G[R], B[R], I[R];
 #pragma unroll
   for (int r = 0; r < R; ++r) G[r] = B[r] = I[r] = NEG;
@@ -205,92 +173,32 @@ __global__ __launch_bounds__(NT) void edits_fb_kernel(EditLaunch a) {
   double acc = 0.0;
   float sub = 0.f;
   {
-    xf[NT + tid] = make_float2(NEG, NEG);
+    alpha_to_right<NT, R, false>(tid, xf, 1, B, I, no.D);
     int c = 0, tin = 0;
-    __syncthreads();
-    load_stage(0);
-    store_stage(0);
-    load_stage(1);
-    __syncthreads();
+    stage_start(0, 1, load_stage, store_stage);
     for (int t = 0; t < T; ++t, ++tin) {
       if (tin == F) {
         ++c;
         tin = 0;
-        store_stage(c);
-        __syncthreads();
-        load_stage(c + 1);
+        stage_enter(c, 1, load_stage, store_stage);
       }
-      const float* row = stage.row(c, tin);
-      const float l = lring[(c & 1) * FMAX + tin];
-      const float eg = gap_emission(row, g) - l;
-      float2 nb = tid > 0 ? xf[((t + 1) & 1) * NT + tid - 1] : make_float2(NEG, NEG);
-      nb.x -= sub;
-      nb.y -= sub;
       if (tid == 0) offa[t] = acc;
-#pragma unroll
-      for (int r = R - 1; r >= 0; --r) {       // descending: slot r - 1's previous-frame values are still in place
-        const int k = tid * R + r;
-        const float pB1 = r ? B[r > 0 ? r - 1 : 0] : nb.x;
-        const float pI1 = r ? I[r > 0 ? r - 1 : 0] : nb.y;
-        const float in = lae3(G[r], pI1, pB1);
-        const float ii = lae2(I[r], B[r]);
-        float eb = NEG, ei = NEG;
-        if (INS && k == N) pA[(long)t * W + k] = in;
-        if (k < N) {
-          pA[(long)t * W + k] = in;
-          tok_emission(row, av[r], eb, ei);
-          eb -= l;
-          ei -= l;
-          eb = win_mask(eb, t, wn[r]);
-        }
-        G[r] = k <= N ? in + eg : NEG;
-        B[r] = in + eb;
-        I[r] = ii + ei;
-      }
-      xf[(t & 1) * NT + tid] = make_float2(B[R - 1], I[R - 1]);
-      const bool renorm = (t & (RENORM - 1)) == RENORM - 1;
-      if (renorm) {
-        float lm = NEG;
-#pragma unroll
-        for (int r = 0; r < R; ++r) lm = fmaxf(lm, fmaxf(G[r], fmaxf(B[r], I[r])));
-        renorm_publish(lm, wmax);
-      }
-      __syncthreads();                         // the neighbour exchange and the renormalisation share it
-      sub = 0.f;
-      if (renorm) {
-        float M = renorm_max<K::NW>(wmax);
-        if (!(M > NEG)) M = 0.f;
-#pragma unroll
-        for (int r = 0; r < R; ++r) { G[r] -= M; B[r] -= M; I[r] -= M; }
-        sub = M;
-        acc += (double)M;
-      }
+      alpha_frame<NT, R, true, false>(tid, stage.row(c, tin), lring[(c & 1) * FMAX + tin], g, av, N, t, xf, wmax, sub, acc, G, B, I, no.H, no.D, wn, [&](int, int k, float in) {
+        if (k < N || (INS && k == N)) pA[(long)t * W + k] = in;
+      });
     }
     // row T of A: what ends the clip in front of token k (the deletion of the last token reads A_{N-1}(T)); no insertion reads it
     if constexpr (!INS) {
-      float2 nb = tid > 0 ? xf[((T + 1) & 1) * NT + tid - 1] : make_float2(NEG, NEG);
-      nb.x -= sub;
-      nb.y -= sub;
+      const float2 nb = alpha_from_left<NT>(tid, xf, T, sub);
       if (tid == 0) offa[T] = acc;
 #pragma unroll
-      for (int r = 0; r < R; ++r) {
-        const int k = tid * R + r;
-        const float pB1 = r ? B[r > 0 ? r - 1 : 0] : nb.x;
-        const float pI1 = r ? I[r > 0 ? r - 1 : 0] : nb.y;
-        if (k < N) pA[(long)T * W + k] = lae3(G[r], pI1, pB1);
-      }
+      for (int r = 0; r < R; ++r)
+        if (tid * R + r < N) pA[(long)T * W + tid * R + r] = alpha_enter<R, false>(r, G, B, I, nb, no.D);
     }
   }
   publish_end_states<R>(N, G, B, I, fin);
   __syncthreads();
-  if (tid == 0) {
-    const int ne = N >= 1 ? 3 : 1;
-    double m = -INFINITY;
-    for (int i = 0; i < ne; ++i) m = fmax(m, (double)fin[i]);
-    double s = 0.0;
-    for (int i = 0; i < ne; ++i) s += exp((double)fin[i] - m);
-    red[0] = m == -INFINITY ? -INFINITY : m + log(s) + acc;   // -inf: no path opens every token inside its window
-  }
+  if (tid == 0) red[0] = end_logz<true>(fin, N, acc);   // -inf: no path opens every token inside its window
   __syncthreads();
   const double logZ = red[0];                  // on the fp32 log-sum-exps; the clip's logZ is logZ - lres
   if (logZ == -INFINITY) {                     // status 1 and zeros, as every clip with a status
@@ -307,87 +215,33 @@ __global__ __launch_bounds__(NT) void edits_fb_kernel(EditLaunch a) {
     bG[r] = k == N ? 0.f : NEG;
     bX[r] = k == N - 1 ? 0.f : NEG;
   }
-  xb[(T & 1) * NT + tid] = make_float2(bG[0], bX[0]);
+  beta_to_left<NT, R, false>(tid, xb, T, bG, bX, no.C, no.D);
   double accb = 0.0;
   float subb = 0.f;
   {
     int c = (T - 1) / F, tin = (T - 1) - c * F;
-    __syncthreads();
-    load_stage(c);
-    store_stage(c);
-    load_stage(c - 1);
-    __syncthreads();
+    stage_start(c, -1, load_stage, store_stage);
     for (int t = T - 1; t >= 0; --t, --tin) {
       if (tin < 0) {
         --c;
         tin = F - 1;
-        store_stage(c);
-        __syncthreads();
-        load_stage(c - 1);
+        stage_enter(c, -1, load_stage, store_stage);
       }
-      const float* row = stage.row(c, tin);
-      const float l = lring[(c & 1) * FMAX + tin];
-      const float eg = gap_emission(row, g) - l;
-      float eb[R], ei[R];
+      float eg, eb[R], ei[R], ebn;
+      beta_emissions<NT, R, true>(tid, stage.row(c, tin), lring[(c & 1) * FMAX + tin], g, av, avn, N, t, wn, wnn, eg, eb, ei, ebn);
       if (tid == 0) offb[t] = accb;
 #pragma unroll
       for (int r = 0; r < R; ++r) {
         const int k = tid * R + r;
-        eb[r] = ei[r] = NEG;
-        if (k < N) {
-          tok_emission(row, av[r], eb[r], ei[r]);
-          eb[r] -= l;
-          ei[r] -= l;
-          eb[r] = win_mask(eb[r], t, wn[r]);
-          if constexpr (!INS) pD[(long)t * W + k] = bX[r] + eb[r];
-        }
         if constexpr (INS) {
           if (k <= N) pE[(long)t * W + k] = bG[r];
         } else {
+          if (k < N) pD[(long)t * W + k] = bX[r] + eb[r];
           if (k >= 1 && k <= N) pE[(long)t * W + k - 1] = bG[r];
         }
       }
       if (t == 0) break;
-      // beta_{t-1}
-      float ebn = NEG;
-      if ((tid + 1) * R < N && tid + 1 < NT) {
-        float ein;
-        tok_emission(row, avn, ebn, ein);
-        ebn -= l;
-        ebn = win_mask(ebn, t, wnn);
-      }
-      float2 nb = tid + 1 < NT ? xb[((t + 1) & 1) * NT + tid + 1] : make_float2(NEG, NEG);
-      nb.x -= subb;
-      nb.y -= subb;
-#pragma unroll
-      for (int r = 0; r < R; ++r) {            // ascending: slot r + 1's values of frame t are still in place
-        const int k = tid * R + r;
-        const float nG = r + 1 < R ? bG[r + 1 < R ? r + 1 : 0] : nb.x;
-        const float nX = r + 1 < R ? bX[r + 1 < R ? r + 1 : 0] : nb.y;
-        const float nE = r + 1 < R ? eb[r + 1 < R ? r + 1 : 0] : ebn;
-        const float x = lae3(bX[r] + ei[r], nG + eg, nX + nE);
-        const float y = lae2(bG[r] + eg, bX[r] + eb[r]);
-        bG[r] = k <= N ? y : NEG;
-        bX[r] = k < N ? x : NEG;
-      }
-      xb[(t & 1) * NT + tid] = make_float2(bG[0], bX[0]);
-      const bool renorm = (t & (RENORM - 1)) == 0;
-      if (renorm) {
-        float lm = NEG;
-#pragma unroll
-        for (int r = 0; r < R; ++r) lm = fmaxf(lm, fmaxf(bG[r], bX[r]));
-        renorm_publish(lm, wmax);
-      }
-      __syncthreads();
-      subb = 0.f;
-      if (renorm) {
-        float M = renorm_max<K::NW>(wmax);
-        if (!(M > NEG)) M = 0.f;
-#pragma unroll
-        for (int r = 0; r < R; ++r) { bG[r] -= M; bX[r] -= M; }
-        subb = M;
-        accb += (double)M;
-      }
+      beta_frame<NT, R, false>(tid, N, t, eg, eb, ei, ebn, xb, wmax, subb, accb, bG, bX, no.B, no.C, no.D);
     }
   }
   if (tid == 0) {

@@ -4,8 +4,10 @@
 //
 // Lattice, emissions, start / end states and caps are wfl_align's, and so is their code: csrc/lattice.h holds the caps, the
 // configurations, the shared LDS layout, lattice setup with its status codes, the logits stage ring, the emission gathers, the
-// renormalisation halves and the host side of a ragged batch.  Here: the sum-product sweeps, the status-8 check of `tok`, the
-// checkpoint workspace and the per-token outputs.  States G_k = 3k, B_k = 3k + 1, I_k = 3k + 2:
+// renormalisation halves and the host side of a ragged batch.  csrc/lattice_sums.h holds the sum-product sweeps -- one frame of alpha
+// and of beta over a thread's slots, their renormalisation, the per-frame log-sum-exp, the staged ring's side rings, logZ -- which
+// csrc/align_edits.hip runs as well.  Here is what is this kernel's own: the status-8 check of `tok`, the checkpoints and the block
+// buffer, the gammas and the per-token moments.  States G_k = 3k, B_k = 3k + 1, I_k = 3k + 2:
 //   alpha_t(G_k) = EG_t + lse(alpha_{t-1}(G_k), alpha_{t-1}(I_{k-1}), alpha_{t-1}(B_{k-1}))      alpha_t(B_k): the same sum + EB_t(k)
 //   alpha_t(I_k) = EI_t(k) + lse(alpha_{t-1}(I_k), alpha_{t-1}(B_k))
 //   beta_{t-1}(G_k) = lse(beta_t(G_k) + EG_t, beta_t(B_k) + EB_t(k))
@@ -44,7 +46,7 @@
 // translation unit of its own because those are compiled without the SLP vectoriser (build.py), which must not reach the others.
 // Everything here is in an unnamed namespace: each of the two files has its own copy, and instantiates only its own kernels.
 #pragma once
-#include "lattice.h"
+#include "lattice_sums.h"
 #include "wfl_asr.h"
 
 #include <limits.h>
@@ -103,22 +105,9 @@ struct PCfg : LdsBase<NT, R, NT * R * 4 + 2 * 2 * NT * 8> {       // its own bet
   static constexpr int LDS = OFF_MISC + 64;
 };
 
-// log(exp a + exp b [+ exp c]); -inf in, -inf out (v_exp_f32 / v_log_f32)
-__device__ __forceinline__ float lae2(float a, float b) {
-  const float m = fmaxf(a, b);
-  const float ms = m == -INFINITY ? 0.f : m;
-  return ms + __logf(__expf(a - ms) + __expf(b - ms));
-}
-
-__device__ __forceinline__ float lae3(float a, float b, float c) {
-  const float m = fmaxf(a, fmaxf(b, c));
-  const float ms = m == -INFINITY ? 0.f : m;
-  return ms + __logf(__expf(a - ms) + __expf(b - ms) + __expf(c - ms));
-}
-
-// WIN: the start windows of wfl_align_posterior_windowed (lattice.h win_mask); false is wfl_align_posterior's kernel, instruction for
-// instruction
-// MIND: the minimum durations of wfl_align_min_duration_posterior (lattice.h chain_*); false leaves the two kernels above as they were
+// WIN: the start windows of wfl_align_posterior_windowed (lattice.h win_mask); false is wfl_align_posterior's kernel
+// MIND: the minimum durations of wfl_align_min_duration_posterior (lattice.h chain_*); false leaves the two kernels above without a
+// trace of the chain (lattice_sums.h takes both as template values)
 template <int NT, int R, bool WIN, bool MIND>
 __global__ __launch_bounds__(NT) void post_kernel(PostLaunch a) {
   using K = PCfg<NT, R>;
@@ -137,7 +126,7 @@ __global__ __launch_bounds__(NT) void post_kernel(PostLaunch a) {
   float* fin = (float*)(misc + 4);
 
   const LatClip cl = a.clip[blockIdx.x];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int tid = threadIdx.x;
   const int T = cl.T, N = cl.N, C = a.C;
   const float* Z = a.logits + cl.frame_off * a.ldl;
   const int* tokp = a.tok + cl.frame_off;
@@ -243,45 +232,24 @@ __global__ __launch_bounds__(NT) void post_kernel(PostLaunch a) {
   float* ckpt = ws + lay.ckpt;
   float* blk = ws + lay.blk;
 
-  // ---- the per-frame log-sum-exp, in fp32 for the sweeps; what its rounding loses, in double for logZ
-  double lres = 0.0;
-  // (a thread per row; a wave per row with coalesced loads and wave reductions was measured 4 % slower for the whole kernel)
-  for (int t = tid; t < T; t += NT) {
-    const float* z = Z + (long)t * a.ldl;
-    float m = z[0];
-    for (int q = 1; q < C; ++q) m = fmaxf(m, z[q]);
-    double se = 0.0;
-    for (int q = 0; q < C; ++q) se += (double)expf(z[q] - m);
-    const double ld = (double)m + log(se);
-    const float lf = (float)ld;
-    lse[t] = lf;
-    lres += ld - (double)lf;
-  }
-  lres = wave_sum(lres);
-  if (lane == 0) red[wave] = lres;
-  __syncthreads();                             // (and the block sees lse[])
-  lres = 0.0;
-#pragma unroll
-  for (int w = 0; w < K::NW; ++w) lres += red[w];
+  // the thread index lattice_sums.h's pieces get.  Measured, five alternating rounds against the build before the pieces were shared
+  // (profiles/sumproduct_sweeps_ab.txt): handed `tid`, the 256 x 2 kernel with the chain is 0.6 to 0.8 % slower and the one with
+  // windows alone level; handed a fresh read in every piece, the other way round.  Same value, another schedule; each gets its own.
+  auto me = [&]() -> int {
+    if constexpr (MIND) return threadIdx.x;
+    else return tid;
+  };
 
-  // ---- staging of the logits rows, with their log-sum-exp and Viterbi token
+  // ---- the per-frame log-sum-exp, in fp32 for the sweeps; what its rounding loses, in double for logZ
+  const double lres = frame_lse<NT>(me(), Z, a.ldl, T, C, lse, red);
+
+  // ---- staging of the logits rows, with their log-sum-exp and Viterbi token (the backward sweep runs one stage ahead as well)
   LogitStages<NT, K::PR> stage(Z, a.ldl, T, C, ring);
   const int F = stage.F;
   float pre_l = 0.f;
   int pre_t = -1;
-  auto load_stage = [&](int c) {               // (the backward sweep runs one stage ahead as well, down to c = -1)
-    stage.load(c, c >= 0);
-    const bool in = tid < F && c >= 0 && c * F + tid < T;
-    pre_l = in ? lse[c * F + tid] : 0.f;
-    pre_t = in ? tokp[c * F + tid] : -1;
-  };
-  auto store_stage = [&](int c) {
-    stage.store(c);
-    if (tid < F) {
-      lring[(c & 1) * FMAX + tid] = pre_l;
-      tring[(c & 1) * FMAX + tid] = pre_t;
-    }
-  };
+  auto load_stage = [&](int c) { stage_load<true>(me(), stage, c, lse, tokp, pre_l, pre_t); };
+  auto store_stage = [&](int c) { stage_store<true>(me(), stage, c, lring, tring, pre_l, pre_t); };
 
   int4 av[R];                                   // this thread's slots' alternatives
 #pragma unroll
@@ -320,79 +288,17 @@ __global__ __launch_bounds__(NT) void post_kernel(PostLaunch a) {
       }
       acc = ckacc[t0 / POST_W];
     }
-    // (with durations the left token is left from its I alone where its D > 1: B is masked by its owner, as in csrc/align.hip)
-    if constexpr (MIND) xf[((t0 + 1) & 1) * NT + tid] = make_float2(dm[R - 1] > 1 ? NEG : B[R - 1], I[R - 1]);
-    else xf[((t0 + 1) & 1) * NT + tid] = make_float2(B[R - 1], I[R - 1]);
+    alpha_to_right<NT, R, MIND>(me(), xf, t0 + 1, B, I, dm);
     float sub = 0.f;
     int c = t0 / F, tin = t0 - c * F;
-    __syncthreads();                           // the ring's last readers are done
-    load_stage(c);
-    store_stage(c);
-    load_stage(c + 1);
-    __syncthreads();
+    stage_start(c, 1, load_stage, store_stage);
     for (int t = t0; t < t1; ++t, ++tin) {
       if (tin == F) {
         ++c;
         tin = 0;
-        store_stage(c);
-        __syncthreads();
-        load_stage(c + 1);
+        stage_enter(c, 1, load_stage, store_stage);
       }
-      const float* row = stage.row(c, tin);
-      const float l = lring[(c & 1) * FMAX + tin];
-      const float eg = gap_emission(row, g) - l;
-      float2 nb = tid > 0 ? xf[((t + 1) & 1) * NT + tid - 1] : make_float2(NEG, NEG);
-      nb.x -= sub;
-      nb.y -= sub;
-#pragma unroll
-      for (int r = R - 1; r >= 0; --r) {       // descending: slot r - 1's previous-frame values are still in place
-        const int k = tid * R + r;
-        float pB1 = r ? B[r > 0 ? r - 1 : 0] : nb.x;
-        if constexpr (MIND) {
-          if (r && dm[r > 0 ? r - 1 : 0] > 1) pB1 = NEG;
-        }
-        const float pI1 = r ? I[r > 0 ? r - 1 : 0] : nb.y;
-        const float in = lae3(G[r], pI1, pB1);
-        float x = B[r];                        // what I_k is entered from
-        if constexpr (MIND) x = chain_out(B[r], H[r], dm[r]);
-        const float ii = lae2(I[r], x);
-        float eb = NEG, ei = NEG;
-        if (k < N) {
-          tok_emission(row, av[r], eb, ei);
-          eb -= l;
-          ei -= l;
-          if constexpr (WIN) eb = win_mask(eb, t, wn[r]);
-        }
-        G[r] = k <= N ? in + eg : NEG;
-        if constexpr (MIND) chain_shift(H[r], B[r], ei, dm[r]);
-        B[r] = in + eb;
-        I[r] = ii + ei;
-      }
-      if constexpr (MIND) xf[(t & 1) * NT + tid] = make_float2(dm[R - 1] > 1 ? NEG : B[R - 1], I[R - 1]);
-      else xf[(t & 1) * NT + tid] = make_float2(B[R - 1], I[R - 1]);
-      const bool renorm = (t & (RENORM - 1)) == RENORM - 1;
-      if (renorm) {
-        float lm = NEG;
-#pragma unroll
-        for (int r = 0; r < R; ++r) lm = fmaxf(lm, fmaxf(G[r], fmaxf(B[r], I[r])));
-        renorm_publish(lm, wmax);
-      }
-      __syncthreads();                         // the neighbour exchange and the renormalisation share it
-      sub = 0.f;
-      if (renorm) {
-        float M = renorm_max<K::NW>(wmax);
-        if (!(M > NEG)) M = 0.f;               // every state -inf (or a NaN): subtract nothing (wfl_align's search takes M as it is)
-#pragma unroll
-        for (int r = 0; r < R; ++r) { G[r] -= M; B[r] -= M; I[r] -= M; }
-        if constexpr (MIND) {                  // (the offset is common to every state; the maximum is G's, B's and I's as before)
-#pragma unroll
-          for (int r = 0; r < R; ++r)
-#pragma unroll
-            for (int j = 0; j < CHAIN; ++j) H[r][j] -= M;
-        }
-        sub = M;
-        acc += (double)M;
-      }
+      alpha_frame<NT, R, WIN, MIND>(me(), stage.row(c, tin), lring[(c & 1) * FMAX + tin], g, av, N, t, xf, wmax, sub, acc, G, B, I, H, dm, wn);
       if (keep) {                              // the block's alpha, for the backward sweep of the same thread
         float* o = blk + (long)(t - t0) * K::S;
 #pragma unroll
@@ -430,17 +336,7 @@ __global__ __launch_bounds__(NT) void post_kernel(PostLaunch a) {
       if (tid * R + r == N - 1 && dm[r] > 1) fin[2] = NEG;
   }
   __syncthreads();
-  if (tid == 0) {
-    const int ne = N >= 1 ? 3 : 1;
-    double m = -INFINITY;
-    for (int i = 0; i < ne; ++i) m = fmax(m, (double)fin[i]);
-    double s = 0.0;
-    for (int i = 0; i < ne; ++i) s += exp((double)fin[i] - m);
-    red[0] = m + log(s) + acc;
-    if constexpr (WIN || MIND) {
-      if (m == -INFINITY) red[0] = -INFINITY;   // no path opens every token inside its window (meets every duration)
-    }
-  }
+  if (tid == 0) red[0] = end_logz<WIN || MIND>(fin, N, acc);   // -inf: no path opens every token inside its window (meets every duration)
   __syncthreads();                             // (ckacc[] of thread 0 is visible to the block as well)
   const double logZ = red[0];                  // on the fp32 log-sum-exps; the clip's logZ is logZ - lres
   if constexpr (WIN || MIND) {
@@ -480,21 +376,15 @@ __global__ __launch_bounds__(NT) void post_kernel(PostLaunch a) {
     for (int r = 0; r < R; ++r)
 #pragma unroll
       for (int j = 0; j < CHAIN_BACK; ++j) bC[r][j] = NEG;
-    xb[(T & 1) * NT + tid] = make_float2(bG[0], chain_in(bX[0], bC[0], dm[0]));
-  } else {
-    xb[(T & 1) * NT + tid] = make_float2(bG[0], bX[0]);
   }
+  beta_to_left<NT, R, MIND>(me(), xb, T, bG, bX, bC, dm);
   double accb = 0.0;                           // what beta's renormalisations subtracted
   float subb = 0.f;
   for (int j = lay.nblk - 1; j >= 0; --j) {
     const int t_lo = j * POST_W, t_hi = min(T, t_lo + POST_W) - 1;
     forward(t_lo, t_hi + 1, true);
     int c = t_hi / F, tin = t_hi - c * F;
-    __syncthreads();
-    load_stage(c);
-    store_stage(c);
-    load_stage(c - 1);
-    __syncthreads();
+    stage_start(c, -1, load_stage, store_stage);
     float an[R][3], ac[R][3];
     auto load_alpha = [&](int f) {
       const float* o = blk + (long)f * K::S;
@@ -510,9 +400,7 @@ __global__ __launch_bounds__(NT) void post_kernel(PostLaunch a) {
       if (tin < 0) {
         --c;
         tin = F - 1;
-        store_stage(c);
-        __syncthreads();
-        load_stage(c - 1);
+        stage_enter(c, -1, load_stage, store_stage);
       }
       const float* row = stage.row(c, tin);
       const float l = lring[(c & 1) * FMAX + tin];
@@ -552,68 +440,9 @@ __global__ __launch_bounds__(NT) void post_kernel(PostLaunch a) {
       }
       if (t == 0) break;
       // beta_{t-1}
-      const float eg = gap_emission(row, g) - l;
-      float eb[R], ei[R];
-#pragma unroll
-      for (int r = 0; r < R; ++r) {
-        eb[r] = ei[r] = NEG;
-        if (tid * R + r < N) {
-          tok_emission(row, av[r], eb[r], ei[r]);
-          eb[r] -= l;
-          ei[r] -= l;
-          if constexpr (WIN) eb[r] = win_mask(eb[r], t, wn[r]);
-        }
-      }
-      float ebn = NEG;
-      if ((tid + 1) * R < N && tid + 1 < NT) {
-        float ein;
-        tok_emission(row, avn, ebn, ein);
-        ebn -= l;
-        if constexpr (WIN) ebn = win_mask(ebn, t, wnn);
-      }
-      float2 nb = tid + 1 < NT ? xb[((t + 1) & 1) * NT + tid + 1] : make_float2(NEG, NEG);
-      nb.x -= subb;
-      nb.y -= subb;
-#pragma unroll
-      for (int r = 0; r < R; ++r) {            // ascending: slot r + 1's values of frame t are still in place
-        const int k = tid * R + r;
-        const float nG = r + 1 < R ? bG[r + 1 < R ? r + 1 : 0] : nb.x;
-        float nX = r + 1 < R ? bX[r + 1 < R ? r + 1 : 0] : nb.y;
-        if constexpr (MIND) nX = r + 1 < R ? bB[r + 1 < R ? r + 1 : 0] : nb.y;   // the next token is entered through its B
-        const float nE = r + 1 < R ? eb[r + 1 < R ? r + 1 : 0] : ebn;
-        const float x = lae3(bX[r] + ei[r], nG + eg, nX + nE);
-        float bb = bX[r];
-        if constexpr (MIND) bb = bB[r];
-        const float y = lae2(bG[r] + eg, bb + eb[r]);
-        if constexpr (MIND) chain_shift_back(bC[r], bX[r], ei[r]);
-        bG[r] = k <= N ? y : NEG;
-        bX[r] = k < N ? x : NEG;
-      }
-      if constexpr (MIND) xb[(t & 1) * NT + tid] = make_float2(bG[0], chain_in(bX[0], bC[0], dm[0]));
-      else xb[(t & 1) * NT + tid] = make_float2(bG[0], bX[0]);
-      const bool renorm = (t & (RENORM - 1)) == 0;
-      if (renorm) {
-        float lm = NEG;
-#pragma unroll
-        for (int r = 0; r < R; ++r) lm = fmaxf(lm, fmaxf(bG[r], bX[r]));
-        renorm_publish(lm, wmax);
-      }
-      __syncthreads();
-      subb = 0.f;
-      if (renorm) {
-        float M = renorm_max<K::NW>(wmax);
-        if (!(M > NEG)) M = 0.f;
-#pragma unroll
-        for (int r = 0; r < R; ++r) { bG[r] -= M; bX[r] -= M; }
-        if constexpr (MIND) {
-#pragma unroll
-          for (int r = 0; r < R; ++r)
-#pragma unroll
-            for (int j = 0; j < CHAIN_BACK; ++j) bC[r][j] -= M;
-        }
-        subb = M;
-        accb += (double)M;
-      }
+      float eg, eb[R], ei[R], ebn;
+      beta_emissions<NT, R, WIN>(me(), row, l, g, av, avn, N, t, wn, wnn, eg, eb, ei, ebn);
+      beta_frame<NT, R, MIND>(me(), N, t, eg, eb, ei, ebn, xb, wmax, subb, accb, bG, bX, bB, bC, dm);
     }
   }
 

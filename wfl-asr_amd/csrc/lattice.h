@@ -2,7 +2,9 @@
 // the sum-product sweeps) and wfl_align_edits (csrc/align_edits.hip: the same sweeps once more, kept per frame, and from them the
 // score of every single substitution and deletion of the transcript, and wfl_align_insertions beside it: of every single insertion),
 // defined ONCE: a change made here reaches all of them, so the posterior and the edit scores always speak of the lattice the search
-// ran on.
+// ran on.  The sweeps themselves follow the same rule: the max-product step is csrc/align.hip's own, and the sum-product sweeps --
+// alpha, beta, their renormalisation, the per-frame log-sum-exp, logZ -- are written once in csrc/lattice_sums.h, on the pieces below,
+// for post_kernel and edits_fb_kernel both (csrc/align.hip does not include that header).
 //
 //   device  caps and constants, the per-clip record, the wave reductions, the (threads, slots per thread) configurations and their
 //           dispatch, the shared part of the LDS layout, lattice setup (status 0 / 1 / 2 / 4, the alternatives in LDS, the gap classes in
