@@ -460,6 +460,39 @@ int32_t wfl_align_min_duration_posterior(const float* logits, int64_t ldl, int32
                                          int32_t n_clips, const int32_t* tok, void* workspace, int64_t workspace_bytes, float* logz,
                                          float* tok_post, float* start_mean, float* start_sd, int32_t* status, void* stream);
 
+/* ---- wfl_align_posterior over the skip lattice of wfl_align_optional (`postprocess.optional_scores`; wfl-asr_amd/align.py
+ * optional_posteriors).  wfl_align_posterior_windowed's arguments (tok_win may be null: no windows) plus tok_opt and skip_penalty =
+ * lambda, the table and the penalty the search was given; tok is wfl_align_optional's output.  A path weighs
+ * exp(sum_t e_t - lambda * its skipped tokens), emissions normalised per frame as in wfl_align_posterior.  With
+ * in_k(t) = lse(alpha_{t-1}(G_k), alpha_{t-1}(I_{k-1}), alpha_{t-1}(B_{k-1})):
+ *     alpha_t(G_k) = EG_t + in_k(t),    alpha_t(I_k) as wfl_align_posterior's,
+ *     alpha_t(B_k) = EB_t(k) + lse(in_k(t), in_{k-1}(t) - lambda where tok_opt[k-1]);
+ *     beta_{t-1}(G_k) = lse(beta_t(G_k) + EG_t, beta_t(B_k) + EB_t(k), beta_t(B_{k+1}) + EB_t(k+1) - lambda where tok_opt[k]),
+ *     beta_{t-1}(B_k) = beta_{t-1}(I_k) = lse(wfl_align_posterior's three, beta_t(B_{k+2}) + EB_t(k+2) - lambda where tok_opt[k+1]);
+ * start and end states are wfl_align_optional's (where tok_opt[N-1]: also G_{N-1}, I_{N-2}, B_{N-2}, each at -lambda).  Windows mask EB
+ * wherever it is gathered; a skipped token's window is never consulted.
+ * Outputs (device, float32; the per-token ones rows as tok_cls):
+ *   keep_post[k]   sum_t gamma_t(B_k), clamped to [0, 1].  Every labelling is exactly one path and a path enters B_k at most once, so
+ *                  this is the posterior probability that token k is present (on wfl_align_posterior's lattice: the constant 1);
+ *   tok_post[k]    as wfl_align_posterior's, the occupancy of the run Viterbi gave the token; 0 for a token tok does not hold;
+ *   start_mean[k], start_sd[k]   moments of gamma_.(B_k) divided by their sum, i.e. conditional on the token being kept: relative to
+ *                  Viterbi's start for a token tok holds, to frame 0 for one it does not; zeros where the sum is 0;
+ *   logz[b]        log of the summed weight of every path of the skip lattice, wfl_align_posterior's convention.
+ * status[b]: wfl_align_posterior's codes; 1 "no path": too few frames (wfl_align_optional's rule) or windows that cannot be met
+ * (logZ = -inf, never a NaN); 4 also for a flag other than 0 | 1; 8 tok is not a path of this lattice: a value outside -1 .. N - 1, a
+ * missing token that is not optional, two adjacent tokens both missing, a kept token that opens outside its window.  1 comes before 8:
+ * a clip without any path is status 1 whatever tok holds (wfl_align_optional writes tok = -1 for it).  A clip with status != 0 gets zeros.  Host-side negative returns as wfl_align_optional's (a null tok_opt, a negative, infinite or NaN
+ * skip_penalty), and a null keep_post with any token present.
+ * Workspace: wfl_align_posterior's layout and figure (a clip with 0 < T < N, which may have a path here, has its floats there too).
+ * With every flag 0 the outputs are wfl_align_posterior's (wfl_align_posterior_windowed's) up to rounding and keep_post is 1. */
+int64_t wfl_align_optional_posterior_workspace_bytes(const int32_t* n_frames_host, const int32_t* n_tok_host, int32_t n_clips);
+int32_t wfl_align_optional_posterior(const float* logits, int64_t ldl, int32_t C, int32_t o_id, const int64_t* frame_off_host,
+                                     const int32_t* n_frames_host, const int32_t* tok_off_host, const int32_t* n_tok_host,
+                                     const int32_t* tok_cls, const int32_t* tok_win, const int32_t* gap_cls, int32_t n_clips,
+                                     const int32_t* tok_opt, float skip_penalty, const int32_t* tok, void* workspace,
+                                     int64_t workspace_bytes, float* logz, float* keep_post, float* tok_post, float* start_mean,
+                                     float* start_sd, int32_t* status, void* stream);
+
 /* ---- Single-edit scores of an aligned transcript (`postprocess.align_edits`; wfl-asr_amd/align.py, csrc/align_edits.hip).  No
  * counterpart in the reference.  The arguments are wfl_align_posterior_windowed's without tok; tok_win may be null: the unwindowed
  * lattice.  sub_cls (device, [n_sub][2] int32 = (B class, I class)) is a table of P = n_sub substitutes, 0 <= P <= 512.  With logZ(.)

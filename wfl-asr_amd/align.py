@@ -16,6 +16,10 @@ token gets one contiguous, time-ordered run of frames, none is dropped.
                         `postprocess.optional_tokens`), each at `skip_penalty` nats -> viterbi_align's four and `skipped` per token
   optional_flags / min_frames_needed   `postprocess.optional_tokens` -> a flag per transcript token; the frames such a transcript needs
   skipped_tokens / format_skipped_tsv / format_folder_skipped_tsv   one file's SkippedToken rows, {stem}.skipped.tsv, the folder's list
+  optional_posteriors   forward-backward over that skip lattice (`wfl_align_optional_posterior`; `postprocess.optional_scores`):
+                        alignment_posteriors' outputs and keep_post, per token the posterior probability that it is present
+  optional_token_scores / format_optional_tsv / format_folder_optional_tsv   one file's OptionalTokenScore rows (kept | skipped, the
+                        keep posterior, the `doubt` flag), {stem}.optional.tsv, the folder's list, least confident decision first
   min_frames_for        `postprocess.min_duration` (seconds, or seconds per token name) -> frames per transcript token
   alignment_posteriors  forward-backward over the same lattice (csrc/align_posterior.h, `wfl_align_posterior`; of a batch packed with
                         windows, `wfl_align_posterior_windowed`): logZ, and per token
@@ -80,6 +84,10 @@ def workspace_bytes(n_frames, n_tokens) -> int:
 
 def optional_workspace_bytes(n_frames, n_tokens) -> int:
     return _workspace_bytes("wfl_align_optional_workspace_bytes", n_frames, n_tokens)
+
+
+def optional_posterior_workspace_bytes(n_frames, n_tokens) -> int:
+    return _workspace_bytes("wfl_align_optional_posterior_workspace_bytes", n_frames, n_tokens)
 
 
 def posterior_workspace_bytes(n_frames, n_tokens) -> int:
@@ -313,6 +321,7 @@ _ENTRIES = {
     "wfl_align_min_duration": ("wfl_align", True, True), "wfl_align_optional": ("wfl_align_optional", True, False),
     "wfl_align_min_duration_posterior": ("wfl_align_min_duration_posterior", True, True),
     "wfl_align_edits": ("wfl_align_edits", True, False), "wfl_align_insertions": ("wfl_align_insertions", True, False),
+    "wfl_align_optional_posterior": ("wfl_align_optional_posterior", True, False),
 }
 
 
@@ -410,6 +419,48 @@ def viterbi_align_optional(logits, n_frames, token_classes, gap_classes, o_id, o
     skipped = torch.empty(max(ntok, 1), dtype=torch.int32, device=dev)
     _call("wfl_align_optional", logits, o_id, packed, (d_opt, lam), (ids, tok, score, skipped, status), stream, temporaries=(d_opt,))
     return ids, tok, score[:nb], status[:nb], skipped[:ntok]
+
+
+def _optional_call_args(optional, skip_penalty, packed, logits, what):
+    """The flags and the penalty as viterbi_align_optional judges them -> (d_opt, lam)."""
+    if packed.d_min is not None:
+        raise ValueError(f"{what} has no minimum durations: this batch was packed with min_frames")
+    lam = float(skip_penalty)
+    if not (0.0 <= lam < float("inf")):
+        raise ValueError("skip_penalty must be a number of nats >= 0")
+    ntok, dev = int(packed.N.sum()), logits.device
+    d_opt = optional if isinstance(optional, torch.Tensor) else upload_optional(optional, packed.N, dev)
+    if d_opt.device != dev or d_opt.dtype != torch.int32 or d_opt.dim() != 1 or d_opt.stride(0) != 1 or d_opt.shape[0] != max(ntok, 1):
+        raise ValueError("uploaded optional flags must be upload_optional's [tokens] int32 tensor for this batch")
+    return d_opt, lam
+
+
+def optional_posteriors(logits, n_frames, token_classes, gap_classes, o_id, optional, tok, skip_penalty=0.0, frame_offsets=None,
+                        stream=None, packed=None, windows=None):
+    """alignment_posteriors over the skip lattice of viterbi_align_optional, for the same ragged batch of clips (same arguments,
+    the same `optional` and `skip_penalty`), given its `tok` (wfl_align_optional_posterior).  A path weighs
+    exp(sum of its emissions - skip_penalty per skipped token).
+
+    optional  as viterbi_align_optional's: per clip a list of bools per token (or None), or upload_optional's tensor
+    windows   as viterbi_align_optional's; with `packed` -- the PackedClips the search ran on -- the ones packed there.  A batch
+              packed with `min_frames` is refused
+    -> (logz, keep_post, tok_post, start_mean, start_sd, status): alignment_posteriors' tensors and keep_post [tokens] float32, the
+    sum over the frames of gamma(B_k).  Every labelling is exactly one path of this lattice and a path enters B_k at most once, so
+    keep_post is the posterior probability that the token is present (1 for a token that is not optional and has no optional
+    neighbour to be traded against).  tok_post is 0 for a token `tok` does not hold; start_mean / start_sd are conditional on the
+    token being kept, relative to Viterbi's start for a token in `tok` and to the clip's frame 0 for a skipped one.
+    STATUS_NOT_A_PATH: `tok` misses a token that is not optional, or two neighbours, or opens a token outside its window."""
+    if packed is None:
+        packed = pack_clips(logits, n_frames, token_classes, gap_classes, frame_offsets, windows)
+    d_opt, lam = _optional_call_args(optional, skip_penalty, packed, logits, "optional_posteriors")
+    _check_tok(tok, logits)
+    nb, ntok, dev = packed.nb, int(packed.N.sum()), logits.device
+    logz = torch.empty(max(nb, 1), dtype=torch.float32, device=dev)
+    per_tok = torch.empty((4, max(ntok, 1)), dtype=torch.float32, device=dev)
+    status = torch.empty(max(nb, 1), dtype=torch.int32, device=dev)
+    _call("wfl_align_optional_posterior", logits, o_id, packed, (d_opt, lam, tok),
+          (logz, per_tok[0], per_tok[1], per_tok[2], per_tok[3], status), stream, temporaries=(d_opt,))
+    return logz[:nb], per_tok[0, :ntok], per_tok[1, :ntok], per_tok[2, :ntok], per_tok[3, :ntok], status[:nb]
 
 
 def _without_min_frames(packed, what):
@@ -977,4 +1028,71 @@ def format_folder_skipped_tsv(per_file) -> str:
     """skipped_tokens.tsv: [(file name, [SkippedToken])] -> every skipped token, the file's name in front of the token's own
     columns, in the files' and the tokens' order."""
     lines = ["file\t" + SKIPPED_HEADER] + ["\t".join([name] + _skipped_cells(r)) for name, rows in per_file for r in rows]
+    return "".join(line + "\n" for line in lines)
+
+
+# ------------------------------------------------------------------------------------------------------- optional tokens' scores
+class OptionalTokenScore(NamedTuple):
+    index: int              # the token's index in the transcript
+    token: str
+    kept: bool              # the best path holds the token
+    keep_posterior: float   # optional_posteriors' keep_post: the posterior probability that the token is present
+    start_s: float          # a kept token's segment; for a skipped one both are the place's time (SkippedToken.at_s)
+    end_s: float
+
+    @property
+    def confidence(self) -> float:
+        """The posterior mass behind the decision the best path took."""
+        return self.keep_posterior if self.kept else 1.0 - self.keep_posterior
+
+    @property
+    def doubt(self) -> bool:
+        """The opposite decision has more posterior mass than the one the best path took."""
+        return self.confidence < 0.5
+
+
+def optional_token_scores(optional, skipped, keep_post, segments, transcript):
+    """One file's OptionalTokenScore rows, one per optional token of the transcript in order: the transcript's flags
+    (optional_flags), the path's `skipped` flags and optional_posteriors' keep_post for the file (host values, one per transcript
+    token) and its aligned segments, one per kept token (as skipped_tokens takes them)."""
+    keep_post = np.asarray(keep_post, np.float64).reshape(-1)
+    flags = [int(f) for f in skipped]
+    if not len(optional) == len(flags) == len(keep_post) == len(transcript):
+        raise ValueError("one optional flag, one skipped flag and one keep posterior per transcript token")
+    at = {r.index: r.at_s for r in skipped_tokens(flags, segments, transcript)}
+    rows, j = [], 0
+    for k, f in enumerate(flags):
+        if f:
+            start, end = at[k], at[k]
+        else:
+            start, end = float(segments[j][0]), float(segments[j][1])
+            j += 1
+        if optional[k]:
+            rows.append(OptionalTokenScore(k, str(transcript[k]), not f, float(keep_post[k]), start, end))
+    return rows
+
+
+OPTIONAL_HEADER = "index\ttoken\tdecision\tkeep_posterior\tstart_s\tend_s\tdoubt"
+
+
+def _optional_cells(r: OptionalTokenScore):
+    return [str(r.index), r.token, "kept" if r.kept else "skipped", f"{r.keep_posterior:.6f}", f"{r.start_s:.7f}", f"{r.end_s:.7f}",
+            "1" if r.doubt else "0"]
+
+
+def format_optional_tsv(rows) -> str:
+    """{stem}.optional.tsv: one line per optional token of the transcript, in the transcript's order."""
+    return "".join("\t".join(c) + "\n" for c in [OPTIONAL_HEADER.split("\t")] + [_optional_cells(r) for r in rows])
+
+
+def folder_optional_rows(per_file):
+    """[(file name, [OptionalTokenScore])] -> [(file name, row)], the least confident decision first; ties in the files' and the
+    tokens' order."""
+    flat = [(name, r) for name, rows in per_file for r in rows]
+    return sorted(flat, key=lambda nr: nr[1].confidence)
+
+
+def format_folder_optional_tsv(per_file) -> str:
+    """optional_scores.tsv: every optional token of every file, the file's name in front of the token's own columns."""
+    lines = ["file\t" + OPTIONAL_HEADER] + ["\t".join([name] + _optional_cells(r)) for name, r in folder_optional_rows(per_file)]
     return "".join(line + "\n" for line in lines)

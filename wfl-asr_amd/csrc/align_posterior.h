@@ -38,13 +38,25 @@
 // the overlap of [t, t + D_k - 2] with the run; only the checkpoints hold the chain (PCfg::SM).  A D_k outside 1 .. 8 is status 4, a run
 // shorter than its D_k status 8, and a clip without any path status 1 before its tok is judged.
 //
+// wfl_align_optional_posterior is the kernel instantiated with OPT (with and without WIN, never with MIND): the sums over the skip
+// lattice of wfl_align_optional, a path weighing exp(sum_t e_t - lambda * its skipped tokens).  With in_k(t) = alpha_enter of token k,
+//   alpha_t(B_k) = EB_t(k) + lse(in_k(t), in_{k-1}(t) - lambda where tok_opt[k-1])                       (G_k, I_k as above)
+//   beta_{t-1}(G_k) gains beta_t(B_{k+1}) + EB_t(k+1) - lambda where tok_opt[k], beta_{t-1}(B_k) = beta_{t-1}(I_k) gains
+//   beta_t(B_{k+2}) + EB_t(k+2) - lambda where tok_opt[k+1]; where tok_opt[N-1] the ends G_{N-1}, I_{N-2}, B_{N-2} count at -lambda.
+// The exchanges widen to five floats forward (the search's: B, I, G of the last slot, B, I of the one before) and three backward
+// (beta(G), beta(B) of slot 0, beta(B) of slot 1; EB of that second slot is gathered by the reader: avn2, wnn2), still one barrier per
+// frame.  Every labelling is one path and a path enters B_k at most once, so m0 = sum_t gamma_t(B_k) is the posterior that token k is
+// present: keep_post.  A tok that misses a token that is not optional, or two neighbours, is status 8 -- after sweep 1, as with
+// durations: a clip without any path is status 1 first.
+//
 // The per-frame log-sum-exp of the logits is computed once (double, expf), stored in fp32 and subtracted from the gathered logits;
 // what the fp32 rounding of it loses is summed in double and given back to logZ (it is common to every path).
 //
 // This header holds the kernel and the host path every entry shares.  csrc/align_posterior.hip instantiates wfl_align_posterior and
 // wfl_align_posterior_windowed from it, csrc/align_min_duration_posterior.hip the kernels with the minimum-duration chain (MIND) -- a
 // translation unit of its own because those are compiled without the SLP vectoriser (build.py), which must not reach the others.
-// Everything here is in an unnamed namespace: each of the two files has its own copy, and instantiates only its own kernels.
+// csrc/align_optional_posterior.hip instantiates the kernels with the skip arcs (OPT), so that the other objects keep their code.
+// Everything here is in an unnamed namespace: each of the three files has its own copy, and instantiates only its own kernels.
 #pragma once
 #include "lattice_sums.h"
 #include "wfl_asr.h"
@@ -91,13 +103,22 @@ struct PostLayout {
   }
 };
 
-template <int NT, int R>
-struct PCfg : LdsBase<NT, R, NT * R * 4 + 2 * 2 * NT * 8> {       // its own between alt and wmax: first[] and the two neighbour exchanges
+// the kernel arguments of wfl_align_optional_posterior: PostLaunch (which stays the record it was for the other entries) and, behind
+// it, the optional tokens
+struct PostLaunchOpt : PostLaunch {
+  const int* tok_opt;  // [total tokens] 0 | 1
+  float* keep_post;    // [total tokens]
+  float lambda;        // the skip penalty, nats
+};
+
+// OPT: the exchanges of the skip lattice, [2][XF_OPT][NT] and [2][XB_OPT][NT] floats instead of [2][NT] float2 each
+template <int NT, int R, bool OPT = false>
+struct PCfg : LdsBase<NT, R, NT * R * 4 + (OPT ? 2 * (XF_OPT + XB_OPT) * NT * 4 : 2 * 2 * NT * 8)> {   // its own between alt and wmax: first[] and the two neighbour exchanges
   static constexpr long S = (long)NT * R * 3;            // floats of one frame's alpha (and of one checkpoint)
   static constexpr long SM = (long)NT * R * (3 + CHAIN); // floats of one checkpoint with the minimum-duration chain
   static constexpr int OFF_FIRST = PCfg::OFF_X;                    // first frame of every token's Viterbi run
   static constexpr int OFF_XF = OFF_FIRST + NT * R * 4;            // forward neighbour exchange: [2][NT] float2
-  static constexpr int OFF_XB = OFF_XF + 2 * NT * 8;               // backward neighbour exchange
+  static constexpr int OFF_XB = OFF_XF + (OPT ? 2 * XF_OPT * NT * 4 : 2 * NT * 8);   // backward neighbour exchange
   static constexpr int OFF_OFFA = PCfg::OFF_OWN;                   // alpha's offset of every frame of the block (double)
   static constexpr int OFF_LRING = OFF_OFFA + POST_W * 8;          // staged rows' log-sum-exp
   static constexpr int OFF_TRING = OFF_LRING + 2 * FMAX * 4;       // staged rows' Viterbi token
@@ -108,9 +129,13 @@ struct PCfg : LdsBase<NT, R, NT * R * 4 + 2 * 2 * NT * 8> {       // its own bet
 // WIN: the start windows of wfl_align_posterior_windowed (lattice.h win_mask); false is wfl_align_posterior's kernel
 // MIND: the minimum durations of wfl_align_min_duration_posterior (lattice.h chain_*); false leaves the two kernels above without a
 // trace of the chain (lattice_sums.h takes both as template values)
-template <int NT, int R, bool WIN, bool MIND>
-__global__ __launch_bounds__(NT) void post_kernel(PostLaunch a) {
-  using K = PCfg<NT, R>;
+// OPT: the skip arcs of wfl_align_optional_posterior (lattice_sums.h OPT), never with MIND; keep_post[k] = sum_t gamma_t(B_k), the
+// posterior of the paths that hold token k (a path enters B_k at most once).  Without OPT the kernels keep their arguments (PostLaunch)
+// and their code; only their names carry one template value more.
+template <int NT, int R, bool WIN, bool MIND, bool OPT>
+__global__ __launch_bounds__(NT) void post_kernel(std::conditional_t<OPT, PostLaunchOpt, PostLaunch> a) {
+  static_assert(!(OPT && MIND), "no skip arcs in the minimum-duration lattice");
+  using K = PCfg<NT, R, OPT>;
   extern __shared__ __attribute__((aligned(16))) char lds[];
   float* ring = (float*)lds;
   int4* alt = (int4*)(lds + K::OFF_ALT);
@@ -133,13 +158,39 @@ __global__ __launch_bounds__(NT) void post_kernel(PostLaunch a) {
   const float NEG = -INFINITY;
 
   int g[NGAP];
-  int st = lattice_setup<NT, R>(cl, C, a.tok_cls, a.gap_cls, alt, misc, g);
+  int st;
+  SkipArcs sk;
+  if constexpr (OPT) {
+    // the clip's flags first, as csrc/align.hip's OPT search judges them: a value other than 0 | 1 is status 4; a clip without any flag
+    // and with fewer frames than tokens is wfl_align_posterior's status 1, whatever its classes are
+    if (tid == 0) { misc[2] = 0; misc[3] = 0; }
+    __syncthreads();
+    bool any = false, badf = false;
+    for (int k = tid; k < N; k += NT) {
+      const int f = a.tok_opt[cl.tok_off + k];
+      any |= f != 0;
+      badf |= f != 0 && f != 1;
+    }
+    if (any) misc[2] = 1;
+    if (badf) misc[3] = 1;
+    __syncthreads();
+    const bool none = misc[2] == 0, bad_flag = misc[3] != 0;
+    __syncthreads();                            // (lattice_setup writes misc[0])
+    if (N <= NT * R - 1 && N <= MAX_TOKENS && T < N && none) st = 1;
+    else st = lattice_setup<NT, R, true>(cl, C, a.tok_cls, a.gap_cls, alt, misc, g);
+    if (st == 0 && bad_flag) st = 4;
+    if (st == 0) sk = load_skip_arcs<R>(tid, a.tok_opt, cl.tok_off, N, a.lambda);
+  } else {
+    st = lattice_setup<NT, R>(cl, C, a.tok_cls, a.gap_cls, alt, misc, g);
+  }
   int2 wn[WIN ? R : 1];                        // this thread's slots' start windows, in registers, and the next thread's first slot's
   int2 wnn = make_int2(0, WIN_OPEN_HI);
+  int2 wnn2 = make_int2(0, WIN_OPEN_HI);       // OPT: and its second slot's
   if constexpr (WIN) {
     if (st == 0) {
       load_windows<R>(a.tok_win, cl.tok_off, N, wn);
       wnn = load_window(a.tok_win, cl.tok_off, (tid + 1) * R, N);
+      if constexpr (OPT) wnn2 = load_window(a.tok_win, cl.tok_off, (tid + 1) * R + 1, N);
     }
   }
   int dm[MIND ? R : 1];                        // this thread's slots' minimum durations, in registers
@@ -179,14 +230,24 @@ __global__ __launch_bounds__(NT) void post_kernel(PostLaunch a) {
     for (int r = 0; r < R; ++r)
       if (tid * R + r < N) {
         const int f = first[tid * R + r];
-        if (f == INT_MAX) misc[0] = 1;
-        if constexpr (WIN) {
-          if (f < wn[r].x || f > wn[r].y) misc[0] = 1;   // a token opens outside its window: not a path of this lattice either
+        if constexpr (OPT) {
+          // a token tok does not hold: a path only where it is optional and the next one is held (one skip between two kept tokens);
+          // its window is never consulted
+          if (f == INT_MAX) {
+            if (!sk.opt(r + 1) || (tid * R + r + 1 < N && first[tid * R + r + 1] == INT_MAX)) misc[0] = 1;
+          } else if constexpr (WIN) {
+            if (f < wn[r].x || f > wn[r].y) misc[0] = 1;
+          }
+        } else {
+          if (f == INT_MAX) misc[0] = 1;
+          if constexpr (WIN) {
+            if (f < wn[r].x || f > wn[r].y) misc[0] = 1;   // a token opens outside its window: not a path of this lattice either
+          }
         }
       }
     __syncthreads();
     if (misc[0]) {
-      if constexpr (MIND) notpath = true;
+      if constexpr (MIND || OPT) notpath = true;   // (OPT: the search writes tok = -1 for a clip without path, too: 1 comes before 8)
       else st = 8;
     }
     if constexpr (MIND) {
@@ -219,6 +280,7 @@ __global__ __launch_bounds__(NT) void post_kernel(PostLaunch a) {
       a.tok_post[cl.tok_off + k] = 0.f;
       a.start_mean[cl.tok_off + k] = 0.f;
       a.start_sd[cl.tok_off + k] = 0.f;
+      if constexpr (OPT) a.keep_post[cl.tok_off + k] = 0.f;
     }
     if (tid == 0) { a.logz[cl.clip] = 0.f; a.status[cl.clip] = st; }
     return;
@@ -255,6 +317,10 @@ __global__ __launch_bounds__(NT) void post_kernel(PostLaunch a) {
 #pragma unroll
   for (int r = 0; r < R; ++r) av[r] = alt[tid * R + r];
   const int4 avn = tid + 1 < NT ? alt[(tid + 1) * R] : make_int4(-1, -1, -1, -1);   // the next thread's first slot
+  int4 avn2 = make_int4(-1, -1, -1, -1);                                            // OPT: and its second
+  if constexpr (OPT) {
+    if (tid + 1 < NT) avn2 = alt[(tid + 1) * R + 1];
+  }
 
   // ---- the forward sweep over frames t0 .. t1 - 1, from the clip's start (t0 = 0) or from checkpoint t0 / POST_W
   float G[R], B[R], I[R];
@@ -288,7 +354,8 @@ __global__ __launch_bounds__(NT) void post_kernel(PostLaunch a) {
       }
       acc = ckacc[t0 / POST_W];
     }
-    alpha_to_right<NT, R, MIND>(me(), xf, t0 + 1, B, I, dm);
+    if constexpr (OPT) alpha_to_right_opt<NT, R>(me(), (float*)xf, t0 + 1, G, B, I);
+    else alpha_to_right<NT, R, MIND>(me(), xf, t0 + 1, B, I, dm);
     float sub = 0.f;
     int c = t0 / F, tin = t0 - c * F;
     stage_start(c, 1, load_stage, store_stage);
@@ -298,7 +365,11 @@ __global__ __launch_bounds__(NT) void post_kernel(PostLaunch a) {
         tin = 0;
         stage_enter(c, 1, load_stage, store_stage);
       }
-      alpha_frame<NT, R, WIN, MIND>(me(), stage.row(c, tin), lring[(c & 1) * FMAX + tin], g, av, N, t, xf, wmax, sub, acc, G, B, I, H, dm, wn);
+      if constexpr (OPT)
+        alpha_frame<NT, R, WIN, MIND, NoHook, true>(me(), stage.row(c, tin), lring[(c & 1) * FMAX + tin], g, av, N, t, xf, wmax, sub, acc, G, B, I, H, dm, wn,
+                                                    NoHook(), sk);
+      else
+        alpha_frame<NT, R, WIN, MIND>(me(), stage.row(c, tin), lring[(c & 1) * FMAX + tin], g, av, N, t, xf, wmax, sub, acc, G, B, I, H, dm, wn);
       if (keep) {                              // the block's alpha, for the backward sweep of the same thread
         float* o = blk + (long)(t - t0) * K::S;
 #pragma unroll
@@ -335,20 +406,33 @@ __global__ __launch_bounds__(NT) void post_kernel(PostLaunch a) {
     for (int r = 0; r < R; ++r)
       if (tid * R + r == N - 1 && dm[r] > 1) fin[2] = NEG;
   }
+  if constexpr (OPT) {                          // the ends that skip token N - 1: fin[3] = G_{N-1}, fin[4] = I_{N-2}, fin[5] = B_{N-2}
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+      const int k = tid * R + r;
+      if (k == N - 1) fin[3] = G[r];
+      if (k == N - 2) { fin[4] = I[r]; fin[5] = B[r]; }
+    }
+  }
   __syncthreads();
-  if (tid == 0) red[0] = end_logz<WIN || MIND>(fin, N, acc);   // -inf: no path opens every token inside its window (meets every duration)
+  if constexpr (OPT) {                          // -inf: too few frames for the tokens that may not be skipped, or windows that cannot be met
+    if (tid == 0) red[0] = end_logz_opt(fin, N, acc, N >= 1 && a.tok_opt[cl.tok_off + (N >= 1 ? N - 1 : 0)] != 0, sk.lam);
+  } else {
+    if (tid == 0) red[0] = end_logz<WIN || MIND>(fin, N, acc);   // -inf: no path opens every token inside its window (meets every duration)
+  }
   __syncthreads();                             // (ckacc[] of thread 0 is visible to the block as well)
   const double logZ = red[0];                  // on the fp32 log-sum-exps; the clip's logZ is logZ - lres
-  if constexpr (WIN || MIND) {
-    if (logZ == -INFINITY || (MIND && notpath)) {   // status 1 (with durations 8: paths exist, tok is none of them) and zeros
+  if constexpr (WIN || MIND || OPT) {
+    if (logZ == -INFINITY || ((MIND || OPT) && notpath)) {   // status 1 (with durations or skip arcs 8: paths exist, tok is none of them) and zeros
       int code = 1;
-      if constexpr (MIND) {
+      if constexpr (MIND || OPT) {
         if (logZ != -INFINITY) code = 8;
       }
       for (int k = tid; k < N; k += NT) {
         a.tok_post[cl.tok_off + k] = 0.f;
         a.start_mean[cl.tok_off + k] = 0.f;
         a.start_sd[cl.tok_off + k] = 0.f;
+        if constexpr (OPT) a.keep_post[cl.tok_off + k] = 0.f;
       }
       if (tid == 0) { a.logz[cl.clip] = 0.f; a.status[cl.clip] = code; }
       return;
@@ -368,6 +452,13 @@ __global__ __launch_bounds__(NT) void post_kernel(PostLaunch a) {
     bX[r] = k == N - 1 ? 0.f : NEG;
     if constexpr (MIND) f0[r] = fst[r];
     else f0[r] = k < N ? first[k] : 0;
+    if constexpr (OPT) {
+      // where token N - 1 is optional the clip also ends in G_{N-1}, I_{N-2}, B_{N-2}, at -lam; a token tok does not hold has its
+      // start moments about frame 0
+      if (sk.opt(r + 1) && k == N - 1) bG[r] = -sk.lam;
+      if (sk.opt(r + 2) && k == N - 2) bX[r] = -sk.lam;
+      if (f0[r] == INT_MAX) f0[r] = 0;
+    }
     cnt[r] = 0;
     occ[r] = m0[r] = m1[r] = m2[r] = 0.0;
   }
@@ -377,7 +468,8 @@ __global__ __launch_bounds__(NT) void post_kernel(PostLaunch a) {
 #pragma unroll
       for (int j = 0; j < CHAIN_BACK; ++j) bC[r][j] = NEG;
   }
-  beta_to_left<NT, R, MIND>(me(), xb, T, bG, bX, bC, dm);
+  if constexpr (OPT) beta_to_left_opt<NT, R>(me(), (float*)xb, T, bG, bX);
+  else beta_to_left<NT, R, MIND>(me(), xb, T, bG, bX, bC, dm);
   double accb = 0.0;                           // what beta's renormalisations subtracted
   float subb = 0.f;
   for (int j = lay.nblk - 1; j >= 0; --j) {
@@ -441,8 +533,14 @@ __global__ __launch_bounds__(NT) void post_kernel(PostLaunch a) {
       if (t == 0) break;
       // beta_{t-1}
       float eg, eb[R], ei[R], ebn;
-      beta_emissions<NT, R, WIN>(me(), row, l, g, av, avn, N, t, wn, wnn, eg, eb, ei, ebn);
-      beta_frame<NT, R, MIND>(me(), N, t, eg, eb, ei, ebn, xb, wmax, subb, accb, bG, bX, bB, bC, dm);
+      if constexpr (OPT) {
+        float ebn2;
+        beta_emissions<NT, R, WIN, true>(me(), row, l, g, av, avn, N, t, wn, wnn, eg, eb, ei, ebn, avn2, wnn2, &ebn2);
+        beta_frame<NT, R, MIND, true>(me(), N, t, eg, eb, ei, ebn, xb, wmax, subb, accb, bG, bX, bB, bC, dm, ebn2, sk);
+      } else {
+        beta_emissions<NT, R, WIN>(me(), row, l, g, av, avn, N, t, wn, wnn, eg, eb, ei, ebn);
+        beta_frame<NT, R, MIND>(me(), N, t, eg, eb, ei, ebn, xb, wmax, subb, accb, bG, bX, bB, bC, dm);
+      }
     }
   }
 
@@ -456,6 +554,7 @@ __global__ __launch_bounds__(NT) void post_kernel(PostLaunch a) {
       a.tok_post[cl.tok_off + k] = cnt[r] > 0 ? fminf((float)(occ[r] / (double)cnt[r]), 1.f) : 0.f;
       a.start_mean[cl.tok_off + k] = (float)mean;
       a.start_sd[cl.tok_off + k] = (float)sqrt(fmax(var, 0.0));
+      if constexpr (OPT) a.keep_post[cl.tok_off + k] = fminf(fmaxf((float)m0[r], 0.f), 1.f);
     }
   }
   if (tid == 0) {
@@ -489,24 +588,28 @@ namespace {
 
 // wfl_align_posterior (WIN false), wfl_align_posterior_windowed and wfl_align_min_duration_posterior (MIND, with or without windows): one
 // host path
-template <bool WIN, bool MIND>
+// and wfl_align_optional_posterior (OPT, with or without windows; tok_opt, skip_penalty and keep_post are its alone)
+template <bool WIN, bool MIND, bool OPT = false>
 int posterior_batch(const char* fn, const float* logits, int64_t ldl, int32_t C, int32_t o_id, const int64_t* frame_off_host,
                     const int32_t* n_frames_host, const int32_t* tok_off_host, const int32_t* n_tok_host, const int32_t* tok_cls,
                     const int32_t* tok_win, const int32_t* tok_min, const int32_t* gap_cls, int32_t n_clips, const int32_t* tok,
                     void* workspace, int64_t workspace_bytes, float* logz, float* tok_post, float* start_mean, float* start_sd,
-                    int32_t* status, void* stream) {
-  const int64_t need = MIND ? wfl_align_min_duration_posterior_workspace_bytes(n_frames_host, n_tok_host, n_clips)
-                            : wfl_align_posterior_workspace_bytes(n_frames_host, n_tok_host, n_clips);
+                    int32_t* status, void* stream, const int32_t* tok_opt = nullptr, float skip_penalty = 0.f, float* keep_post = nullptr) {
+  const int64_t need = OPT    ? wfl_align_optional_posterior_workspace_bytes(n_frames_host, n_tok_host, n_clips)
+                       : MIND ? wfl_align_min_duration_posterior_workspace_bytes(n_frames_host, n_tok_host, n_clips)
+                              : wfl_align_posterior_workspace_bytes(n_frames_host, n_tok_host, n_clips);
   bool any_tok = false, any_frame = false;
   int rc = check_clip_args(fn, C, o_id, ldl, frame_off_host, n_frames_host, tok_off_host, n_tok_host, n_clips, need, any_tok, any_frame);
   if (rc || n_clips == 0) return rc;
+  if (OPT && !(skip_penalty >= 0.f && skip_penalty <= 3.0e38f)) return fail(fn, -1, "skip_penalty must be a finite number >= 0");
   if (!logz || !status || !gap_cls ||
-      (any_tok && (!tok_cls || (WIN && !tok_win) || (MIND && !tok_min) || !tok_post || !start_mean || !start_sd)) ||
+      (any_tok && (!tok_cls || (WIN && !tok_win) || (MIND && !tok_min) || (OPT && (!tok_opt || !keep_post)) || !tok_post || !start_mean || !start_sd)) ||
       (any_frame && (!logits || !tok)))
     return fail(fn, -1, "null device pointer");
   if ((rc = check_workspace(fn, need, workspace, workspace_bytes))) return rc;
   hipStream_t s = (hipStream_t)stream;
-  PostLaunch a{};
+  std::conditional_t<OPT, PostLaunchOpt, PostLaunch> a{};
+  if constexpr (OPT) { a.tok_opt = tok_opt; a.keep_post = keep_post; a.lambda = skip_penalty; }
   a.logits = logits; a.ldl = ldl; a.C = C; a.tok_cls = tok_cls; a.gap_cls = gap_cls; a.tok = tok; a.tok_win = tok_win; a.tok_min = tok_min;
   a.ws = (float*)workspace; a.logz = logz; a.tok_post = tok_post; a.start_mean = start_mean; a.start_sd = start_sd; a.status = status;
   return launch_clips<NCFG>(
@@ -517,10 +620,10 @@ int posterior_batch(const char* fn, const float* logits, int64_t ldl, int32_t C,
         cfg = post_cfg(N);
         return MIND ? clip_floats_min(T, N) : clip_floats(T, N);
       },
-      [&](int cfg, const PostLaunch& a) {
+      [&](int cfg, const auto& a) {
         return dispatch_cfg(cfg, [&](auto sh) {
           constexpr int NT = decltype(sh)::NT, R = decltype(sh)::R;
-          return launch_cfg<post_kernel<NT, R, WIN, MIND>, NT, PCfg<NT, R>::LDS>(fn, a, s);
+          return launch_cfg<post_kernel<NT, R, WIN, MIND, OPT>, NT, PCfg<NT, R, OPT>::LDS>(fn, a, s);
         });
       });
 }

@@ -16,6 +16,9 @@
 // windows where it has none).  MIND: the minimum-duration chain, H beside G, B, I for alpha and the delay line bC for beta; without it
 // the chain arguments are arrays of one element that nothing reads (NoChain).  Every piece takes the kernel's own `tid`: a thread index
 // read again inside the pieces costs post_kernel a register.
+// OPT: the skip arcs of wfl_align_optional (include/wfl_asr.h), never with MIND: B_k is also entered from what may enter token k - 1,
+// at -lam, where token k - 1 is optional.  Everything of it stands under `if constexpr (OPT)`; the wider neighbour exchanges are the
+// *_opt siblings of the exchange pieces, and the flags travel as a bit mask per thread (SkipArcs).
 #pragma once
 #include "lattice.h"
 
@@ -129,6 +132,66 @@ static __device__ __forceinline__ float alpha_enter(int r, const float (&G)[R], 
   return lae3(G[r], pI1, pB1);
 }
 
+// ---- OPT.  The flags of the tokens a thread's recurrences look at, and the penalty: bit j of `om` = "token tid R + j - 1 is optional",
+// j = 0 .. R + 1 (a slot outside 0 .. N - 1: 0).  Alpha asks for token k - 1 (bit r), beta for tokens k and k + 1 (bits r + 1, r + 2).
+// Without OPT a kernel hands over SkipArcs() and nothing reads it.
+struct SkipArcs {
+  unsigned om = 0;
+  float lam = 0.f;
+  __device__ __forceinline__ bool opt(int j) const { return (om >> j) & 1u; }
+};
+
+template <int R>
+static __device__ __forceinline__ SkipArcs load_skip_arcs(const int tid, const int* tok_opt, int tok_off, int N, float lam) {
+  SkipArcs sk;
+  sk.lam = lam;
+#pragma unroll
+  for (int j = 0; j < R + 2; ++j) {
+    const int k = tid * R + j - 1;
+    if (k >= 0 && k < N && tok_opt[tok_off + k] != 0) sk.om |= 1u << j;
+  }
+  return sk;
+}
+
+// the forward exchange with skip arcs: what csrc/align.hip's OPT search exchanges, [2][XF_OPT][NT] floats -- B, I, G of the thread's last
+// slot, B, I of the one before it (every configuration has R >= 2).  All five carry the same `sub`.
+constexpr int XF_OPT = 5;
+struct LeftOpt {
+  float2 nb;           // (alpha(B), alpha(I)) of slot R - 1, as alpha_from_left's
+  float G1, B2, I2;    // alpha(G) of slot R - 1, alpha(B), alpha(I) of slot R - 2
+};
+
+template <int NT, int R>
+static __device__ __forceinline__ void alpha_to_right_opt(const int tid, float* xf, int t, const float (&G)[R], const float (&B)[R], const float (&I)[R]) {
+  static_assert(R >= 2, "the widened exchange takes a thread's last TWO slots");
+  float* xq = xf + (t & 1) * XF_OPT * NT + tid;
+  xq[0] = B[R - 1];
+  xq[NT] = I[R - 1];
+  xq[2 * NT] = G[R - 1];
+  xq[3 * NT] = B[R - 2];
+  xq[4 * NT] = I[R - 2];
+}
+
+template <int NT>
+static __device__ __forceinline__ LeftOpt alpha_from_left_opt(const int tid, const float* xf, int t, float sub) {
+  LeftOpt l;
+  l.nb = make_float2(-INFINITY, -INFINITY);
+  l.G1 = l.B2 = l.I2 = -INFINITY;
+  if (tid > 0) {
+    const float* xp = xf + ((t + 1) & 1) * XF_OPT * NT + tid - 1;
+    l.nb = make_float2(xp[0], xp[NT]);
+    l.G1 = xp[2 * NT];
+    l.B2 = xp[3 * NT];
+    l.I2 = xp[4 * NT];
+  }
+  l.nb.x -= sub;
+  l.nb.y -= sub;
+  l.G1 -= sub;
+  l.B2 -= sub;
+  l.I2 -= sub;
+  return l;
+}
+
 // the chain arguments of a kernel that runs the sweeps without MIND: one element each, which nothing reads
 struct NoChain {
   float H[1][CHAIN], C[1][CHAIN_BACK], B[1];
@@ -146,16 +209,38 @@ struct NoHook {
 // subtracted (wfl_align's search takes M as it is).  hook(r, k, in) sees alpha_enter of every slot.
 // (Frame and tail are ONE function on purpose: as two, with sub going into one by value and out of the other by reference, post_kernel
 // needs a register more and wfl_align_posterior_windowed was measured 0.4 to 0.8 % slower; profiles/sumproduct_sweeps_ab.txt.)
-template <int NT, int R, bool WIN, bool MIND, class Hook = NoHook>
+// OPT: xf is the [2][XF_OPT][NT] exchange, and B_k is also entered from in_{k-1} - lam where token k - 1 is optional: the slot
+// below's alpha_enter, taken before that slot is written (of slot 0: from the left thread's G[R-1], I[R-2], B[R-2]).
+template <int NT, int R, bool WIN, bool MIND, class Hook = NoHook, bool OPT = false>
 static __device__ __forceinline__ void alpha_frame(const int tid, const float* row, float l, const int (&g)[NGAP], const int4 (&av)[R], int N, int t, float2* xf,
                                                    float* wmax, float& sub, double& acc, float (&G)[R], float (&B)[R], float (&I)[R], float (&H)[MIND ? R : 1][CHAIN],
-                                                   const int (&dm)[MIND ? R : 1], const int2 (&wn)[WIN ? R : 1], Hook hook = Hook()) {
+                                                   const int (&dm)[MIND ? R : 1], const int2 (&wn)[WIN ? R : 1], Hook hook = Hook(),
+                                                   const SkipArcs sk = SkipArcs()) {
+  static_assert(!(OPT && MIND), "no skip arcs in the minimum-duration lattice");
   const float eg = gap_emission(row, g) - l;
-  const float2 nb = alpha_from_left<NT>(tid, xf, t, sub);
+  float2 nb;
+  float inl = -INFINITY, inr = -INFINITY;      // OPT: alpha_enter of the slot below (of the left thread's last slot), of this slot
+  if constexpr (OPT) {
+    const LeftOpt lf = alpha_from_left_opt<NT>(tid, (const float*)xf, t, sub);
+    nb = lf.nb;
+    inl = lae3(lf.G1, lf.I2, lf.B2);
+    inr = alpha_enter<R, MIND>(R - 1, G, B, I, nb, dm);
+  } else {
+    nb = alpha_from_left<NT>(tid, xf, t, sub);
+  }
 #pragma unroll
   for (int r = R - 1; r >= 0; --r) {           // descending: slot r - 1's previous-frame values are still in place
     const int k = tid * R + r;
-    const float in = alpha_enter<R, MIND>(r, G, B, I, nb, dm);
+    float in;
+    float inb;                                 // what B_k is entered from
+    if constexpr (OPT) {
+      in = inr;
+      inr = r ? alpha_enter<R, MIND>(r > 0 ? r - 1 : 0, G, B, I, nb, dm) : inl;
+      inb = sk.opt(r) ? lae2(in, inr - sk.lam) : in;
+    } else {
+      in = alpha_enter<R, MIND>(r, G, B, I, nb, dm);
+      inb = in;
+    }
     float x = B[r];                            // what I_k is entered from
     if constexpr (MIND) x = chain_out(B[r], H[r], dm[r]);
     const float ii = lae2(I[r], x);
@@ -169,10 +254,11 @@ static __device__ __forceinline__ void alpha_frame(const int tid, const float* r
     }
     G[r] = k <= N ? in + eg : -INFINITY;
     if constexpr (MIND) chain_shift(H[r], B[r], ei, dm[r]);
-    B[r] = in + eb;
+    B[r] = inb + eb;
     I[r] = ii + ei;
   }
-  alpha_to_right<NT, R, MIND>(tid, xf, t, B, I, dm);
+  if constexpr (OPT) alpha_to_right_opt<NT, R>(tid, (float*)xf, t, G, B, I);
+  else alpha_to_right<NT, R, MIND>(tid, xf, t, B, I, dm);
   const bool renorm = (t & (RENORM - 1)) == RENORM - 1;
   if (renorm) {
     float lm = -INFINITY;
@@ -211,6 +297,25 @@ static __device__ __forceinline__ double end_logz(const float* fin, int N, doubl
   return m + log(s) + acc;
 }
 
+// the same over the skip lattice: where token N - 1 is optional (last), the ends that skip it as well, each at -lam --
+// fin[3] = G_{N-1}, fin[4] = I_{N-2}, fin[5] = B_{N-2} (the last two only for N >= 2).  No path at all is -inf.
+static __device__ __forceinline__ double end_logz_opt(const float* fin, int N, double acc, bool last, float lam) {
+  double v[6];
+  int ne = 0;
+  v[ne++] = (double)fin[0];
+  if (N >= 1) { v[ne++] = (double)fin[1]; v[ne++] = (double)fin[2]; }
+  if (N >= 1 && last) {
+    v[ne++] = (double)fin[3] - (double)lam;
+    if (N >= 2) { v[ne++] = (double)fin[4] - (double)lam; v[ne++] = (double)fin[5] - (double)lam; }
+  }
+  double m = -INFINITY;
+  for (int i = 0; i < ne; ++i) m = fmax(m, v[i]);
+  if (m == -INFINITY) return -INFINITY;
+  double s = 0.0;
+  for (int i = 0; i < ne; ++i) s += exp(v[i] - m);
+  return m + log(s) + acc;
+}
+
 // ---- beta.  bG = beta(G_k), bX = beta(I_k) (= beta(B_k) without durations; with them beta(B_k) comes out of the slot's delay line bC).
 // Thread i hands (beta(G), beta(B)) of its first slot to thread i - 1 through xb[2][NT].
 template <int NT, int R, bool MIND>
@@ -221,12 +326,25 @@ static __device__ __forceinline__ void beta_to_left(const int tid, float2* xb, i
   xb[(t & 1) * NT + tid] = make_float2(bG[0], b);
 }
 
+// the backward exchange with skip arcs, [2][XB_OPT][NT] floats: beta(G), beta(B) of the thread's first slot and beta(B) of its second
+constexpr int XB_OPT = 3;
+template <int NT, int R>
+static __device__ __forceinline__ void beta_to_left_opt(const int tid, float* xb, int t, const float (&bG)[R], const float (&bX)[R]) {
+  static_assert(R >= 2, "the widened exchange takes a thread's first TWO slots");
+  float* xq = xb + (t & 1) * XB_OPT * NT + tid;
+  xq[0] = bG[0];
+  xq[NT] = bX[0];
+  xq[2 * NT] = bX[1];
+}
+
 // the emissions of frame t that beta_{t-1} needs: the gap's, EB / EI of this thread's slots, and EB of the next thread's first slot
 // (avn, wnn), which this thread gathers itself from the staged row
-template <int NT, int R, bool WIN>
+// OPT: EB of the next thread's SECOND slot as well (avn2, wnn2 -> ebn2): a skip arc over the next thread's first token ends there
+template <int NT, int R, bool WIN, bool OPT = false>
 static __device__ __forceinline__ void beta_emissions(const int tid, const float* row, float l, const int (&g)[NGAP], const int4 (&av)[R], const int4& avn, int N,
                                                       int t, const int2 (&wn)[WIN ? R : 1], const int2& wnn, float& eg, float (&eb)[R],
-                                                      float (&ei)[R], float& ebn) {
+                                                      float (&ei)[R], float& ebn, const int4& avn2 = int4(), const int2& wnn2 = int2(),
+                                                      float* ebn2 = nullptr) {
   eg = gap_emission(row, g) - l;
 #pragma unroll
   for (int r = 0; r < R; ++r) {
@@ -245,21 +363,64 @@ static __device__ __forceinline__ void beta_emissions(const int tid, const float
     ebn -= l;
     if constexpr (WIN) ebn = win_mask(ebn, t, wnn);
   }
+  if constexpr (OPT) {
+    float e2 = -INFINITY;
+    if ((tid + 1) * R + 1 < N && tid + 1 < NT) {
+      float ein;
+      tok_emission(row, avn2, e2, ein);
+      e2 -= l;
+      if constexpr (WIN) e2 = win_mask(e2, t, wnn2);
+    }
+    *ebn2 = e2;
+  }
 }
 
 // one frame back, beta_t -> beta_{t-1}, over this thread's slots: the neighbour's values in, the recurrences, this thread's first slot
 // out, the step's barrier and, where t is a multiple of RENORM, beta's renormalisation (as alpha_frame's).  bB (MIND): beta_t(B_k) of
 // every slot, chain_in of the state before this call.
-template <int NT, int R, bool MIND>
+// OPT: xb is the [2][XB_OPT][NT] exchange; G_k also goes to B_{k+1} where token k is optional, B_k / I_k to B_{k+2} where token k + 1
+// is, each at -lam.  vB[j] = beta_t(B) + EB_t of slot j, j = 0 .. R + 1 (the next thread's first two behind this thread's own), of frame t.
+template <int NT, int R, bool MIND, bool OPT = false>
 static __device__ __forceinline__ void beta_frame(const int tid, int N, int t, float eg, const float (&eb)[R], const float (&ei)[R], float ebn, float2* xb,
                                                   float* wmax, float& subb, double& accb, float (&bG)[R], float (&bX)[R], const float (&bB)[MIND ? R : 1],
-                                                  float (&bC)[MIND ? R : 1][CHAIN_BACK], const int (&dm)[MIND ? R : 1]) {
-  float2 nb = tid + 1 < NT ? xb[((t + 1) & 1) * NT + tid + 1] : make_float2(-INFINITY, -INFINITY);
-  nb.x -= subb;
-  nb.y -= subb;
+                                                  float (&bC)[MIND ? R : 1][CHAIN_BACK], const int (&dm)[MIND ? R : 1], float ebn2 = 0.f,
+                                                  const SkipArcs sk = SkipArcs()) {
+  static_assert(!(OPT && MIND), "no skip arcs in the minimum-duration lattice");
+  float2 nb;
+  float vB[OPT ? R + 2 : 1];
+  if constexpr (OPT) {
+    nb = make_float2(-INFINITY, -INFINITY);
+    float nX1 = -INFINITY;
+    if (tid + 1 < NT) {
+      const float* xp = (const float*)xb + ((t + 1) & 1) * XB_OPT * NT + tid + 1;
+      nb = make_float2(xp[0], xp[NT]);
+      nX1 = xp[2 * NT];
+    }
+    nb.x -= subb;
+    nb.y -= subb;
+    nX1 -= subb;
+#pragma unroll
+    for (int r = 0; r < R; ++r) vB[r] = bX[r] + eb[r];
+    vB[R] = nb.y + ebn;
+    vB[R + 1] = nX1 + ebn2;
+  } else {
+    nb = tid + 1 < NT ? xb[((t + 1) & 1) * NT + tid + 1] : make_float2(-INFINITY, -INFINITY);
+    nb.x -= subb;
+    nb.y -= subb;
+  }
 #pragma unroll
   for (int r = 0; r < R; ++r) {                // ascending: slot r + 1's values of frame t are still in place
     const int k = tid * R + r;
+    if constexpr (OPT) {
+      const float nG = r + 1 < R ? bG[r + 1 < R ? r + 1 : 0] : nb.x;
+      float x = lae3(bX[r] + ei[r], nG + eg, vB[r + 1]);
+      if (sk.opt(r + 2)) x = lae2(x, vB[r + 2] - sk.lam);
+      float y = lae2(bG[r] + eg, vB[r]);
+      if (sk.opt(r + 1)) y = lae2(y, vB[r + 1] - sk.lam);
+      bG[r] = k <= N ? y : -INFINITY;
+      bX[r] = k < N ? x : -INFINITY;
+      continue;
+    }
     const float nG = r + 1 < R ? bG[r + 1 < R ? r + 1 : 0] : nb.x;
     float nX = r + 1 < R ? bX[r + 1 < R ? r + 1 : 0] : nb.y;
     if constexpr (MIND) nX = r + 1 < R ? bB[r + 1 < R ? r + 1 : 0] : nb.y;   // the next token is entered through its B
@@ -272,7 +433,8 @@ static __device__ __forceinline__ void beta_frame(const int tid, int N, int t, f
     bG[r] = k <= N ? y : -INFINITY;
     bX[r] = k < N ? x : -INFINITY;
   }
-  beta_to_left<NT, R, MIND>(tid, xb, t, bG, bX, bC, dm);
+  if constexpr (OPT) beta_to_left_opt<NT, R>(tid, (float*)xb, t, bG, bX);
+  else beta_to_left<NT, R, MIND>(tid, xb, t, bG, bX, bC, dm);
   const bool renorm = (t & (RENORM - 1)) == 0;
   if (renorm) {
     float lm = -INFINITY;

@@ -423,7 +423,7 @@ class Labeler:
     def label_files(self, audio_paths, lang_id=None, confidence_threshold=0.0, verbose=True, align=None, align_scores=None,
                     decode=None, switch_penalty=None, decode_scores=None, phoneme_bigram=None, bigram_weight=None, align_draft=None,
                     draft_tolerance=None, align_edits=None, align_insertions=None, min_duration=None, duration_scores=None,
-                    optional_tokens=None, skip_penalty=None, bigram_scores=None):
+                    optional_tokens=None, skip_penalty=None, optional_scores=None, bigram_scores=None):
         """-> list (per file) of [(start_s, end_s, phoneme)] after merge + forced alignment; with align_scores, duration_scores,
         decode_scores or bigram_scores, (that list, scores); with align_edits the tuple goes on with one more list, edits, and with
         align_insertions it ends with one more, insertions; with optional_tokens it ends with the list skipped.
@@ -500,17 +500,24 @@ class Labeler:
         postprocess.skip_penalty, else 0).  The segments of such a file lack the skipped tokens, one line says how many, and
         skipped[i] is one align.SkippedToken per token left out (None for a file that was not aligned that way).  It combines with
         align_draft (the names are the draft's labels; kept tokens hold their windows); min_duration and the scoring options beside
-        it are refused.  A name that is no output name of the label set is refused by name."""
+        it are refused.  A name that is no output name of the label set is refused by name.
+        optional_scores (with optional_tokens only; None: config postprocess.optional_scores, else off): align_scores for that
+        search, summed over its skip lattice (align.optional_posteriors): scores[i] is an align.FileScore over the kept tokens, and
+        the result ends with one more list, optional: per file one align.OptionalTokenScore per optional token of its transcript --
+        kept or skipped, the posterior probability that the token is present, and `doubt` where the other decision has more
+        posterior mass (None for a file that was not scored that way)."""
         opts = self.options(align=align, align_scores=align_scores, decode=decode, switch_penalty=switch_penalty,
                             decode_scores=decode_scores, phoneme_bigram=phoneme_bigram, bigram_weight=bigram_weight,
                             bigram_scores=bigram_scores, align_draft=align_draft, draft_tolerance=draft_tolerance,
                             align_edits=align_edits, align_insertions=align_insertions, min_duration=min_duration,
-                            duration_scores=duration_scores, optional_tokens=optional_tokens, skip_penalty=skip_penalty)
+                            duration_scores=duration_scores, optional_tokens=optional_tokens, skip_penalty=skip_penalty,
+                            optional_scores=optional_scores)
         edits = {} if opts.align_edits else None
         insertions = {} if opts.align_insertions else None
         skipped = {} if opts.optional_tokens is not None else None
+        optional = {} if opts.optional_scores else None
         final, scores = self._label_scored(audio_paths, opts, lang_id, confidence_threshold, verbose, edits=edits,
-                                           insertions=insertions, skipped=skipped)
+                                           insertions=insertions, skipped=skipped, optional=optional)
         out = (final, scores) if opts.scored else (final,)
         if opts.align_edits:
             out += ([edits.get(fi) for fi in range(len(audio_paths))],)
@@ -518,15 +525,18 @@ class Labeler:
             out += ([insertions.get(fi) for fi in range(len(audio_paths))],)
         if skipped is not None:
             out += ([skipped.get(fi) for fi in range(len(audio_paths))],)
+        if optional is not None:
+            out += ([optional.get(fi) for fi in range(len(audio_paths))],)
         return out if len(out) > 1 else final
 
     def _label_scored(self, audio_paths, opts, lang_id, confidence_threshold, verbose, moves=None, edits=None, insertions=None,
-                      skipped=None):
+                      skipped=None, optional=None):
         """label_files for the resolved options `opts`, always -> (segments, scores): the files are split once into those a transcript is
         Viterbi-aligned to, those the grammar search decodes and those left to the argmax decode, and each subset's results go back to
         its files' places.  moves: a dict that takes {file index: [DraftMove]} for the files aligned inside their draft's windows.
         edits (opts.align_edits): a dict that takes {file index: [TokenEdit]} for the files that were Viterbi-aligned; insertions
-        (opts.align_insertions): the same with [PlaceInsertion]; skipped (opts.optional_tokens): the same with [SkippedToken]."""
+        (opts.align_insertions): the same with [PlaceInsertion]; skipped (opts.optional_tokens): the same with [SkippedToken]; optional
+        (opts.optional_scores): the same with [OptionalTokenScore]."""
         unknown = (unknown_optional_tokens(opts.optional_tokens, self._names_for(self._lang_name(lang_id))[1])
                    if opts.optional_tokens not in (None, "*") else [])
         if unknown:
@@ -567,7 +577,8 @@ class Labeler:
                                       confidence_threshold, verbose)
             for fi, rec in zip(with_t, got):
                 final[fi], scores[fi] = rec.segments, rec.score
-                for into, value in ((moves, rec.moves), (edits, rec.edits), (insertions, rec.insertions), (skipped, rec.skipped)):
+                for into, value in ((moves, rec.moves), (edits, rec.edits), (insertions, rec.insertions), (skipped, rec.skipped),
+                                    (optional, rec.optional)):
                     if into is not None and value is not None:
                         into[fi] = value
         return final, scores
@@ -881,6 +892,8 @@ class Labeler:
                         aligned[fi] = got
             for fi in sel:
                 out.append(aligned.get(fi, ViterbiLabel(greedy[fi])))
+                if opts.optional_scores and fi not in aligned:
+                    print(f"{audio_paths[fi]}: no optional-token scores (the file was not Viterbi-aligned)")
                 if opts.align_edits and fi not in aligned:
                     print(f"{audio_paths[fi]}: no transcript edits (the file was not Viterbi-aligned)")
                 if opts.align_insertions and fi not in aligned:
@@ -932,15 +945,22 @@ class Labeler:
             skipped = AL.skipped_tokens(left_out, segs, tr)
             print(f"{found.paths[b]}: {len(skipped)} of {int(sum(flags))} optional tokens skipped")
         moves = draft_moves(draft, segs, tok, batch.wins[b], left_out) if batch.wins[b] is not None else None
-        score = None
+        score = optional = None
         if b in scored.raw:
-            score = AL.file_score(scored.raw[b][0], scored.raw[b][1], n, *scored.raw[b][2:], segs, frame_duration)
-        elif opts.align_scores or opts.duration_scores:      # (the scoring entry refused the path the search gave it)
+            per_tok = scored.raw[b][2:]
+            if left_out is not None:                      # the scores of the kept tokens, one per segment
+                per_tok = tuple(a[np.asarray(left_out) == 0] for a in per_tok)
+            score = AL.file_score(scored.raw[b][0], scored.raw[b][1], n, *per_tok, segs, frame_duration)
+            if b in scored.keep:                          # (scored over the skip lattice: its optional tokens' decisions)
+                no_flag = [0] * len(tr)
+                optional = AL.optional_token_scores(flags if flags is not None else no_flag, left_out if left_out is not None else no_flag,
+                                                    scored.keep[b], segs, tr)
+        elif opts.align_scores or opts.duration_scores or opts.optional_scores:      # (the scoring entry refused the path the search gave it)
             entry, code = scored.refused.get(b, ("wfl_align_posterior", None))
             print(f"{found.paths[b]}: no alignment scores ({entry} status {code})")
         return ViterbiLabel(AL.with_end_pauses(free_segs, segs, tr), score, moves,
                             AL.token_edits(scored.edits[b], segs, sub_out) if b in scored.edits else None,
-                            AL.place_insertions(scored.insertions[b], segs, sub_out) if b in scored.insertions else None, skipped)
+                            AL.place_insertions(scored.insertions[b], segs, sub_out) if b in scored.insertions else None, skipped, optional)
 
 
 class ViterbiLabel(NamedTuple):
@@ -951,6 +971,7 @@ class ViterbiLabel(NamedTuple):
     edits: list = None              # [TokenEdit] (opts.align_edits), a file that was aligned
     insertions: list = None         # [PlaceInsertion] (opts.align_insertions), the same
     skipped: list = None            # [SkippedToken] (opts.optional_tokens), a file aligned with optional tokens
+    optional: list = None           # [OptionalTokenScore] (opts.optional_scores), a file scored over the skip lattice
 
 
 class _Searched(NamedTuple):
@@ -976,6 +997,7 @@ class _Scored(NamedTuple):
     refused: dict                   # (entry, status) of one it refused
     edits: dict                     # the clip's rows of edit_scores' edits
     insertions: dict                # the clip's rows of insertion_scores' ins
+    keep: dict                      # optional_posteriors' keep_post of a clip it accepted (opts.optional_scores)
 
 
 def _clip_flags(transcripts, opts):
@@ -1061,7 +1083,7 @@ def _search(batch, paths, opts) -> _Searched:
 def _score(found, opts, sub_pairs) -> _Scored:
     """Stage 4: edits, insertions, posteriors, duration posteriors of the clips the search aligned, each call on a sub-batch and on
     the lattice its clips were searched on (AlignBatch.scored_on: the search's PackedClips or tables packed again)."""
-    scored = _Scored({}, {}, {}, {})
+    scored = _Scored({}, {}, {}, {}, {})
     ok = found.ok
     if not ok:
         return scored
@@ -1089,6 +1111,25 @@ def _score(found, opts, sub_pairs) -> _Scored:
             d_post = (AL.duration_posteriors if with_min else AL.alignment_posteriors)(*sub.args(), found.d_tok, frame_offsets=sub.f0,
                                                                                      packed=packed)
             _take_posteriors(found, part, d_post, "wfl_align_min_duration_posterior" if with_min else "wfl_align_posterior", scored)
+    if opts.optional_scores:
+        # the clips searched with flags, over the skip lattice and on the windows they ended the search with (after _search's
+        # fallback has dropped any); a batch none of whose clips has a flag was searched by wfl_align, and is scored on that lattice
+        sub = found.batch.select(ok)
+        packed = sub.pack(False)
+        if found.batch.optional is not None:
+            d = AL.optional_posteriors(*sub.args(), sub.opts, found.d_tok, opts.skip_penalty, frame_offsets=sub.f0, packed=packed)
+            _take_posteriors(found, ok, (d[0], d[2], d[3], d[4], d[5]), "wfl_align_optional_posterior", scored)
+            h_keep, k0 = d[1].cpu().numpy(), 0
+            for b in ok:
+                if b in scored.raw:
+                    scored.keep[b] = h_keep[k0:k0 + len(found.batch.alts[b])]
+                k0 += len(found.batch.alts[b])
+        else:
+            d_post = AL.alignment_posteriors(*sub.args(), found.d_tok, frame_offsets=sub.f0, packed=packed)
+            _take_posteriors(found, ok, d_post, "wfl_align_posterior", scored)
+            for b in ok:
+                if b in scored.raw:
+                    scored.keep[b] = np.ones(len(found.batch.alts[b]), np.float32)
     return scored
 
 
@@ -1339,6 +1380,16 @@ def _write_skipped(lab_path, rows):
         _write_text(skipped_path(lab_path), AL.format_skipped_tsv(rows), "Skipped tokens")
 
 
+def optional_path(lab_path):
+    return os.path.splitext(lab_path)[0] + ".optional.tsv"
+
+
+def _write_optional(lab_path, rows):
+    """`{stem}.optional.tsv` beside the .lab of a file that was scored over the skip lattice (None: no file)."""
+    if rows is not None:
+        _write_text(optional_path(lab_path), AL.format_optional_tsv(rows), "Optional-token scores")
+
+
 def _write_score(lab_path, segments, score):
     """The scores file of one labelled file beside its .lab, by the kind of its score (None: no file)."""
     if isinstance(score, DC.FreeScore):
@@ -1351,7 +1402,7 @@ def infer_audio(audio_path, config_path="config.yaml", checkpoint_path="best_mod
                 lang_id=None, sample=False, top_k=0, top_p=0.0, temperature=1.0, confidence_threshold=0.0, align=None,
                 align_scores=None, decode=None, switch_penalty=None, decode_scores=None, phoneme_bigram=None, bigram_weight=None,
                 align_draft=None, draft_tolerance=None, align_edits=None, align_insertions=None, min_duration=None,
-                duration_scores=None, optional_tokens=None, skip_penalty=None, bigram_scores=None):
+                duration_scores=None, optional_tokens=None, skip_penalty=None, optional_scores=None, bigram_scores=None):
     """align: "greedy" | "viterbi" | None (config postprocess.align, else greedy): how a `{audio}.txt` transcript is aligned
     (Labeler.label_files).  align_scores (viterbi only; None: config postprocess.align_scores): also write `{stem}.scores.tsv`
     beside the .lab when the file was Viterbi-aligned (format_scores_tsv).  decode: "argmax" | "viterbi" | None (config
@@ -1373,19 +1424,23 @@ def infer_audio(audio_path, config_path="config.yaml", checkpoint_path="best_mod
     minimum-duration lattice (align.duration_posteriors).  optional_tokens / skip_penalty (align viterbi only; None: config
     postprocess.optional_tokens / postprocess.skip_penalty): the transcript tokens a path may leave out, [NAME, ...] or "*", and the
     nats each skipped one costs (Labeler.label_files); the .lab lacks the skipped tokens and `{stem}.skipped.tsv` lists them
-    (align.format_skipped_tsv)."""
+    (align.format_skipped_tsv).  optional_scores (with optional_tokens only; None: config postprocess.optional_scores): also write
+    `{stem}.scores.tsv` for the kept tokens, summed over the skip lattice, and `{stem}.optional.tsv`, one row per optional token of
+    the transcript with the posterior probability that it is present (align.optional_posteriors, align.format_optional_tsv)."""
     given = dict(align=align, align_scores=align_scores, decode=decode, switch_penalty=switch_penalty, decode_scores=decode_scores,
                  phoneme_bigram=phoneme_bigram, bigram_weight=bigram_weight, bigram_scores=bigram_scores, align_draft=align_draft,
                  draft_tolerance=draft_tolerance, align_edits=align_edits, align_insertions=align_insertions, min_duration=min_duration,
-                 duration_scores=duration_scores, optional_tokens=optional_tokens, skip_penalty=skip_penalty)
+                 duration_scores=duration_scores, optional_tokens=optional_tokens, skip_penalty=skip_penalty,
+                 optional_scores=optional_scores)
     _refuse_before_load(config_path, **given)
     lab = _labeler(config_path, checkpoint_path, device)
     opts = lab.options(**given)
     edits = {} if opts.align_edits else None
     insertions = {} if opts.align_insertions else None
     skipped = {} if opts.optional_tokens is not None else None
+    optional = {} if opts.optional_scores else None
     (segments,), (score,) = lab._label_scored([audio_path], opts, lang_id, confidence_threshold, True, edits=edits,
-                                              insertions=insertions, skipped=skipped)
+                                              insertions=insertions, skipped=skipped, optional=optional)
     if output_lab_path:
         if os.path.abspath(output_lab_path) == os.path.abspath(audio_path):
             # the reference would truncate the input WAV here (infer.py:410-411 + utils.py:77)
@@ -1398,6 +1453,8 @@ def infer_audio(audio_path, config_path="config.yaml", checkpoint_path="best_mod
             _write_insertions(output_lab_path, insertions.get(0))
         if skipped is not None:
             _write_skipped(output_lab_path, skipped.get(0))
+        if optional is not None:
+            _write_optional(output_lab_path, optional.get(0))
     return segments
 
 
@@ -1406,11 +1463,12 @@ def infer_folder(folder_path: str, config_path: str = "config.yaml", checkpoint_
                  temperature=1.0, confidence_threshold=0.0, align=None, align_scores=None, decode=None, switch_penalty=None,
                  decode_scores=None, phoneme_bigram=None, bigram_weight=None, align_draft=None, draft_tolerance=None,
                  align_edits=None, align_insertions=None, min_duration=None, duration_scores=None, optional_tokens=None,
-                 skip_penalty=None, bigram_scores=None):
+                 skip_penalty=None, optional_scores=None, bigram_scores=None):
     given = dict(align=align, align_scores=align_scores, decode=decode, switch_penalty=switch_penalty, decode_scores=decode_scores,
                  phoneme_bigram=phoneme_bigram, bigram_weight=bigram_weight, bigram_scores=bigram_scores, align_draft=align_draft,
                  draft_tolerance=draft_tolerance, align_edits=align_edits, align_insertions=align_insertions, min_duration=min_duration,
-                 duration_scores=duration_scores, optional_tokens=optional_tokens, skip_penalty=skip_penalty)
+                 duration_scores=duration_scores, optional_tokens=optional_tokens, skip_penalty=skip_penalty,
+                 optional_scores=optional_scores)
     _refuse_before_load(config_path, **given)
     wav_files = sorted(f for f in os.listdir(folder_path) if f.lower().endswith(".wav"))
     os.makedirs(output_dir, exist_ok=True)
@@ -1427,7 +1485,9 @@ def infer_folder(folder_path: str, config_path: str = "config.yaml", checkpoint_
     edits = {} if opts.align_edits else None
     insertions = {} if opts.align_insertions else None
     skipped = {} if opts.optional_tokens is not None else None
-    all_segments, all_scores = (lab._label_scored(paths, opts, lang_id, confidence_threshold, True, moves, edits, insertions, skipped)
+    optional = {} if opts.optional_scores else None
+    all_segments, all_scores = (lab._label_scored(paths, opts, lang_id, confidence_threshold, True, moves, edits, insertions, skipped,
+                                                  optional)
                                 if paths else ([], []))
     for fi, (wav_file, segments, score) in enumerate(zip(wav_files, all_segments, all_scores)):
         print(f"\nInferencing: {wav_file}")
@@ -1440,10 +1500,12 @@ def infer_folder(folder_path: str, config_path: str = "config.yaml", checkpoint_
             _write_insertions(lab_path, insertions.get(fi))
         if skipped is not None:
             _write_skipped(lab_path, skipped.get(fi))
+        if optional is not None:
+            _write_optional(lab_path, optional.get(fi))
         print("Predicted segments:")
         for start, end, ph in segments:
             print(f"({round(start, 2)}, {round(end, 2)}, {ph})")
-    if opts.align_scores or opts.duration_scores:
+    if opts.align_scores or opts.duration_scores or opts.optional_scores:
         name = "alignment_scores.tsv" if world == 1 else f"alignment_scores.rank{rank}.tsv"
         _write_text(os.path.join(output_dir, name),
                     format_review_tsv([(f, sc) for f, sc in zip(wav_files, all_scores) if isinstance(sc, AL.FileScore)]), "Review list")
@@ -1463,6 +1525,10 @@ def infer_folder(folder_path: str, config_path: str = "config.yaml", checkpoint_
         name = "skipped_tokens.tsv" if world == 1 else f"skipped_tokens.rank{rank}.tsv"
         _write_text(os.path.join(output_dir, name), AL.format_folder_skipped_tsv([(wav_files[fi], skipped[fi]) for fi in sorted(skipped)]),
                     "Skipped tokens of the folder")
+    if optional is not None:
+        name = "optional_scores.tsv" if world == 1 else f"optional_scores.rank{rank}.tsv"
+        _write_text(os.path.join(output_dir, name), AL.format_folder_optional_tsv([(wav_files[fi], optional[fi]) for fi in sorted(optional)]),
+                    "Optional-token scores of the folder")
     if opts.free_scores:
         name = "decode_scores.tsv" if world == 1 else f"decode_scores.rank{rank}.tsv"
         _write_text(os.path.join(output_dir, name),
@@ -1548,9 +1614,16 @@ def main(argv=None):
     @click.option("--skip-penalty", "skip_penalty", type=float, default=None,
                   help="With --optional: what a path pays per skipped token, in nats (>= 0). Default: config postprocess.skip_penalty, "
                        "else 0.")
+    @click.option("--optional-scores", "optional_scores", is_flag=True, default=None,
+                  help="With --optional: --align-scores for that alignment, from a forward-backward pass over the skip lattice on the "
+                       "GPU: {stem}.scores.tsv for the kept tokens and {stem}.optional.tsv, per optional token whether it was kept, "
+                       "the posterior probability that it is present and a doubt flag; for a folder also alignment_scores.tsv and "
+                       "optional_scores.tsv, the least confident decision first. Default: config postprocess.optional_scores, else "
+                       "off.")
     def cli(path, checkpoint, config, output, lang_id, sample, top_k, top_p, temperature, device, confidence_threshold, align,
             align_scores, decode, switch_penalty, decode_scores, phoneme_bigram, bigram_weight, bigram_scores, align_draft,
-            draft_tolerance, align_edits, align_insertions, min_duration, duration_scores, optional_tokens, skip_penalty):
+            draft_tolerance, align_edits, align_insertions, min_duration, duration_scores, optional_tokens, skip_penalty,
+            optional_scores):
         if switch_penalty is not None and not switch_penalty >= 0.0:
             raise click.UsageError("--switch-penalty must be >= 0 (nats)")
         if sample:
@@ -1585,7 +1658,7 @@ def main(argv=None):
                            bigram_scores=bigram_scores, align_draft=align_draft, draft_tolerance=draft_tolerance,
                            align_edits=align_edits, align_insertions=align_insertions,
                            min_duration=parse_min_duration(min_duration), duration_scores=duration_scores,
-                           optional_tokens=list(optional_tokens) or None, skip_penalty=skip_penalty)
+                           optional_tokens=list(optional_tokens) or None, skip_penalty=skip_penalty, optional_scores=optional_scores)
         except ValueError as err:
             raise click.UsageError(str(err))
         output_path = inf_path if output == "." else output
@@ -1607,7 +1680,8 @@ def main(argv=None):
                   align_edits=opts.align_edits, align_insertions=opts.align_insertions, min_duration=opts.min_duration,
                   duration_scores=opts.duration_scores,
                   # a penalty only beside the tokens it prices (with none, none was given, or resolve had refused it)
-                  optional_tokens=opts.optional_tokens, skip_penalty=opts.skip_penalty if opts.optional_tokens is not None else None)
+                  optional_tokens=opts.optional_tokens, skip_penalty=opts.skip_penalty if opts.optional_tokens is not None else None,
+                  optional_scores=opts.optional_scores)
         if inf_path.is_dir():
             infer_folder(folder_path=str(inf_path), output_dir=str(output_path), **kw)
         else:

@@ -35,6 +35,9 @@ infer_folder (before any model is loaded) and the CLI all call `resolve` and car
                                lattice its search ran on
                            (24. with the model known, Labeler.label_files: a name that is no output name of the label set is refused
                                by name, `unknown_optional_tokens`)
+  optional_scores off      25. needs align viterbi
+                           26. needs optional_tokens (it scores the skip lattice of that search: per optional token the posterior
+                               that it is present; without optional tokens align_scores is the option to ask for)
 """
 from __future__ import annotations
 
@@ -160,7 +163,8 @@ class PostOptions(_SearchOptions):
         min_duration     None   the least time a transcript token occupies: seconds, or ((name, seconds), ...) sorted by name
         duration_scores  False  score every alignment searched under a min_duration, over the minimum-duration lattice
         optional_tokens  None   the tokens a path may leave out: "*", or a sorted tuple of names
-        skip_penalty     0.0    nats a path pays per skipped token (also stands for "not given")"""
+        skip_penalty     0.0    nats a path pays per skipped token (also stands for "not given")
+        optional_scores  False  score every alignment searched with optional_tokens, over the skip lattice"""
     align_draft: Optional[str] = None
     draft_tolerance: float = DEFAULT_DRAFT_TOLERANCE
     align_edits: bool = False
@@ -169,9 +173,10 @@ class PostOptions(_SearchOptions):
     duration_scores: bool = False
     optional_tokens: object = None
     skip_penalty: float = 0.0
+    optional_scores: bool = False
 
     def __new__(cls, *args, align_draft=None, draft_tolerance=DEFAULT_DRAFT_TOLERANCE, align_edits=False, align_insertions=False,
-                min_duration=None, duration_scores=False, optional_tokens=None, skip_penalty=0.0, **kw):
+                min_duration=None, duration_scores=False, optional_tokens=None, skip_penalty=0.0, optional_scores=False, **kw):
         self = super().__new__(cls, *args, **kw)
         object.__setattr__(self, "align_draft", align_draft)
         object.__setattr__(self, "draft_tolerance", draft_tolerance)
@@ -181,21 +186,22 @@ class PostOptions(_SearchOptions):
         object.__setattr__(self, "duration_scores", duration_scores)
         object.__setattr__(self, "optional_tokens", optional_tokens)
         object.__setattr__(self, "skip_penalty", skip_penalty)
+        object.__setattr__(self, "optional_scores", optional_scores)
         return self
 
     def __setattr__(self, name, value):
         raise AttributeError(f"PostOptions is read-only: cannot set {name!r}")
 
     _KEYWORD = ("align_draft", "draft_tolerance", "align_edits", "align_insertions", "min_duration", "duration_scores",
-                "optional_tokens", "skip_penalty")
-    _KEYWORD_DEFAULTS = (None, DEFAULT_DRAFT_TOLERANCE, False, False, None, False, None, 0.0)
+                "optional_tokens", "skip_penalty", "optional_scores")
+    _KEYWORD_DEFAULTS = (None, DEFAULT_DRAFT_TOLERANCE, False, False, None, False, None, 0.0, False)
 
     def _draft(self):
         return self.align_draft, self.draft_tolerance
 
     @property
     def scored(self) -> bool:
-        return self.align_scores or self.free_scores or self.duration_scores
+        return self.align_scores or self.free_scores or self.duration_scores or self.optional_scores
 
     def _later(self):
         return tuple(getattr(self, k) for k in self._KEYWORD)
@@ -203,10 +209,10 @@ class PostOptions(_SearchOptions):
     # the NamedTuple helpers carry the keyword fields as well (the inherited ones know the tuple alone)
     @classmethod
     def _make(cls, iterable, align_draft=None, draft_tolerance=DEFAULT_DRAFT_TOLERANCE, align_edits=False, align_insertions=False,
-              min_duration=None, duration_scores=False, optional_tokens=None, skip_penalty=0.0):
+              min_duration=None, duration_scores=False, optional_tokens=None, skip_penalty=0.0, optional_scores=False):
         return cls(*iterable, align_draft=align_draft, draft_tolerance=draft_tolerance, align_edits=align_edits,
                    align_insertions=align_insertions, min_duration=min_duration, duration_scores=duration_scores,
-                   optional_tokens=optional_tokens, skip_penalty=skip_penalty)
+                   optional_tokens=optional_tokens, skip_penalty=skip_penalty, optional_scores=optional_scores)
 
     def _replace(self, **kw):
         later = {k: kw.pop(k, getattr(self, k)) for k in self._KEYWORD}
@@ -242,7 +248,8 @@ def _number_ge0(x):
 
 def resolve(post, *, align=None, align_scores=None, decode=None, switch_penalty=None, decode_scores=None, phoneme_bigram=None,
             bigram_weight=None, bigram_scores=None, align_draft=None, draft_tolerance=None, align_edits=None,
-            align_insertions=None, min_duration=None, duration_scores=None, optional_tokens=None, skip_penalty=None) -> PostOptions:
+            align_insertions=None, min_duration=None, duration_scores=None, optional_tokens=None, skip_penalty=None,
+            optional_scores=None) -> PostOptions:
     """post: the config's `postprocess` mapping (None: {}).  Per option the argument wins; None leaves it to `post[<option>]`, and a
     key that is absent (or None) to the default.  -> PostOptions, or ValueError for the first broken rule of the module's table."""
     post = post or {}
@@ -330,7 +337,14 @@ def resolve(post, *, align=None, align_scores=None, decode=None, switch_penalty=
         raise ValueError("skip_penalty needs optional_tokens (postprocess.optional_tokens): it is the price of skipping one of them")
     if optional_tokens is not None and (min_duration is not None or align_scores or align_edits or align_insertions or duration_scores):
         raise ValueError(OPTIONAL_TOKENS_ERROR)
+    optional_scores = bool(pick("optional_scores", optional_scores, False))
+    if optional_scores and align != "viterbi":
+        raise ValueError("optional_scores needs align='viterbi' (postprocess.align: viterbi) and optional_tokens: the greedy match has "
+                         "no lattice to score")
+    if optional_scores and optional_tokens is None:
+        raise ValueError("optional_scores needs optional_tokens (postprocess.optional_tokens): it scores the skip lattice of that "
+                         "search; without optional tokens align_scores is the option to ask for")
     return PostOptions(align, align_scores, decode, switch_penalty, decode_scores, phoneme_bigram, bigram_weight, bigram_scores,
                        align_draft=align_draft, draft_tolerance=draft_tolerance, align_edits=align_edits,
                        align_insertions=align_insertions, min_duration=min_duration, duration_scores=duration_scores,
-                       optional_tokens=optional_tokens, skip_penalty=skip_penalty)
+                       optional_tokens=optional_tokens, skip_penalty=skip_penalty, optional_scores=optional_scores)
