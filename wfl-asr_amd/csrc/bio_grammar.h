@@ -4,15 +4,16 @@
 // (csrc/decode_bigram_posterior.hip, the sum-product sweeps under the table); wfl_decode_bigram_counts (csrc/decode_bigram_counts.hip, the
 // same sweeps summed into expected successions) is the fifth -- defined ONCE: a change made here reaches all of them, so a
 // posterior always scores the grammar and the forced frames its search ran on.  A .hip file keeps its chain kernel, the head of its workspace and its
-// own fields of the launch struct; everything else of an entry is here.
+// own fields of the launch struct; everything else of an entry is here, but for what only some entries share: the path posteriors'
+// csrc/path_posterior.h and the bigram sum-product chain's csrc/bigram_sumproduct.h.
 //
 //   device  the per-clip record and the launch fields every kernel takes, a clip's workspace ([the kernel's head] [a statistic per
 //           frame] [a forced flag per frame]), a frame's row maximum / sum of exponentials and its forced-to-O rule, the ONE pre-pass
 //           kernel that writes them, what a refused clip looks like (per output shape) and the ONE fill kernel, the class table in LDS
-//           and registers with its validation (status 4)
-//   host    the slot configurations by n_pairs and their dispatch, the argument checks the ABI entries share, the status a whole call
-//           is refused with, the *_workspace_bytes rule, and the driver of an entry after its own pointer checks: workspace check,
-//           clip records, fill or pre-pass + chain launches
+//           and registers with its validation (status 4), the logZ tail of the three sum-product kernels
+//   host    the slot configurations by n_pairs and their dispatch, the launch struct's common fields (launch_of), the argument checks
+//           the ABI entries share, the status a whole call is refused with, the *_workspace_bytes rule, and the driver of an entry
+//           after its own pointer checks: workspace check, clip records, fill or pre-pass + chain launches
 //
 // From csrc/lattice.h (the alignment kernels' header) come the class cap, the clips-per-launch constant, round64, the wave reductions
 // and the host's clip-table batching, workspace check, error strings and once-per-device LDS reservation.
@@ -33,7 +34,7 @@ struct Clip {
   int T, clip;
 };
 
-// what the kernels of all three entries take; an entry's launch struct is this plus its own fields, passed by value
+// what the kernels of all five entries take; an entry's launch struct is this plus its own fields, passed by value
 struct Launch {
   const float* logits;
   long ldl;
@@ -46,6 +47,14 @@ struct Launch {
   int n, fill_status;
   Clip clip[CLIPS_PER_LAUNCH];
 };
+
+// (host) an entry's launch struct L with the fields the ABI hands every entry; ws, fill_status and the clips are run()'s
+template <class L>
+L launch_of(const float* logits, long ldl, int C, int o_id, const int* pairs, int n_pairs, float threshold, int* status) {
+  L a{};
+  a.logits = logits; a.ldl = ldl; a.C = C; a.o_id = o_id; a.pairs = pairs; a.n_pairs = n_pairs; a.threshold = threshold; a.status = status;
+  return a;
+}
 
 // ---- workspace of a clip, in words: [head: the kernel's own, `head` words, a multiple of 64] [a float per frame: its log-sum-exp or
 // its row maximum] [forced flag per frame], the last two rounded up to 64 words.  tail_stat / tail_forced: where the last two begin
@@ -110,6 +119,20 @@ __global__ __launch_bounds__(256) void pre_kernel(L a, Head head) {
     unsigned* w = a.ws + cl.ws_off;
     ((float*)(w + tail_stat(head(cl.T))))[t] = LSE ? m + logf(se) : m;
     w[tail_forced(head(cl.T), cl.T) + t] = forced_to_o(se, a.threshold);
+  }
+}
+
+// ---- the end of a sum-product kernel, by one wave: logZ = log of the scaled sum, its exponent KA, and what the emissions left out (the
+// row maxima; O's logit on a forced frame); status 0
+template <class L>
+static __device__ __forceinline__ void write_logz(const L& a, const Clip& cl, int lane, const float* Z, const float* rowmax,
+                                                  const unsigned* forced, double zsum, long KA) {
+  double ls = 0.0;
+  for (int t = lane; t < cl.T; t += 64) ls += forced[t] ? (double)Z[(long)t * a.ldl + a.o_id] : (double)rowmax[t];
+  ls = lattice::wave_sum(ls);
+  if (lane == 0) {
+    a.logz[cl.clip] = (float)(log(zsum) + (double)KA * 0.69314718055994530942 + ls);
+    a.status[cl.clip] = 0;
   }
 }
 
@@ -185,7 +208,7 @@ inline int refused_status(int C, int n_pairs, bool over_own_cap = false) {
   return C > MAX_CLASSES ? 2 : (n_pairs > C ? 4 : (over_own_cap ? 2 : 0));
 }
 
-// the arguments the three entries share -> 0 or the error.  any_frame comes back for the caller's check of its device pointers (only
+// the arguments the five entries share -> 0 or the error.  any_frame comes back for the caller's check of its device pointers (only
 // when n_clips > 0).
 inline int check_args(const char* fn, int C, int o_id, int64_t ldl, const int64_t* frame_off_host, const int32_t* n_frames_host, int n_clips,
                       int n_pairs, float lambda, float threshold, bool& any_frame) {

@@ -259,8 +259,7 @@ int32_t wfl_decode(const float* logits, int64_t ldl, int32_t C, int32_t o_id, co
   if (const int rc = bio::check_args(fn, C, o_id, ldl, frame_off_host, n_frames_host, n_clips, n_pairs, lambda, threshold, any_frame)) return rc;
   if (n_clips == 0) return 0;
   if (!score || !status || (n_pairs > 0 && !pairs) || (any_frame && (!logits || !ids))) return lattice::fail(fn, -1, "null device pointer");
-  DecodeLaunch a{};
-  a.logits = logits; a.ldl = ldl; a.C = C; a.o_id = o_id; a.pairs = pairs; a.n_pairs = n_pairs; a.threshold = threshold; a.status = status;
+  auto a = bio::launch_of<DecodeLaunch>(logits, ldl, C, o_id, pairs, n_pairs, threshold, status);
   a.lambda = lambda; a.ids = ids; a.score = score;
   const int S = bio::slots_of(n_pairs);
   return bio::run<true>(fn, a, false, frame_off_host, n_frames_host, n_clips, workspace, workspace_bytes, stream, BpWords{S},

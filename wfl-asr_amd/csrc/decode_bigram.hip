@@ -17,8 +17,7 @@
 //   - every 16 frames the maximum of end[] is subtracted from all states and carried in a double (wfl_decode's scheme)
 // Backtrace: thread 0 walks windows of BIGRAM_W frames of backpointers staged into the LDS the table no longer needs.  The state a
 // run was opened from is the better of the predecessor symbol's two states; that is the I bit of the same frame's record.
-#include "bio_grammar.h"
-#include "wfl_asr.h"
+#include "bigram_sumproduct.h"
 
 namespace {
 
@@ -27,13 +26,14 @@ using lattice::MAX_CLASSES;
 using bio::NO_CLASS;
 using BigramClip = bio::Clip;
 
-constexpr int MAX_SYMBOLS = WFL_DECODE_BIGRAM_MAX_SYMBOLS;
-constexpr int NT = 256;                      // threads per clip
-constexpr int NW = NT / 64;                  // predecessor slices
-constexpr int JT = (MAX_SYMBOLS + 63) / 64;  // targets per lane
+// the workgroup's shape is the sum-product chain's (csrc/bigram_sumproduct.h): NT threads per clip, NW predecessor slices, JT targets per lane
+using bigram_sp::JT;
+using bigram_sp::MAX_SYMBOLS;
+using bigram_sp::NT;
+using bigram_sp::NW;
 constexpr int D = 8;                         // frames per emission group
 constexpr int BIGRAM_W = 32;                 // backtrace window, frames
-static_assert(MAX_SYMBOLS <= NT && MAX_SYMBOLS <= 256, "one owner thread per symbol, 8-bit predecessors");
+static_assert(MAX_SYMBOLS <= 256, "8-bit predecessors");
 
 struct BigramLaunch : bio::Launch {
   const float* trans;  // [N][N], rows the previous symbol
@@ -284,8 +284,7 @@ int32_t wfl_decode_bigram(const float* logits, int64_t ldl, int32_t C, int32_t o
   const int N = n_pairs + 1;
   const bool over = N > MAX_SYMBOLS;
   if (any_frame && !trans && !bio::refused_status(C, n_pairs, over)) return lattice::fail(fn, -1, "null device pointer");
-  BigramLaunch a{};
-  a.logits = logits; a.ldl = ldl; a.C = C; a.o_id = o_id; a.pairs = pairs; a.n_pairs = n_pairs; a.threshold = threshold; a.status = status;
+  auto a = bio::launch_of<BigramLaunch>(logits, ldl, C, o_id, pairs, n_pairs, threshold, status);
   a.trans = trans; a.ids = ids; a.score = score;
   return bio::run<true>(fn, a, over, frame_off_host, n_frames_host, n_clips, workspace, workspace_bytes, stream, BpWords{N},
                         [&](const BigramLaunch& a, hipStream_t s) {

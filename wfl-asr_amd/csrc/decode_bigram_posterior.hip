@@ -44,27 +44,21 @@
 // Before the sweeps the workgroup checks in parallel that ids is a path of the grammar (status 8): a class of the table, I-p only after
 // B-p / I-p, O on a forced frame, and no run opened through a succession whose W is 0.  Workspace per clip, in words: [alpha records
 // 3 T] [pair | kind << 16 per frame T] [row maxima T] [forced flags T], each rounded up to 64: wfl_decode_posterior's.
+//
+// The chain itself -- LDS layout, staging, owner columns, emissions, the frame of either sweep, logZ -- is csrc/bigram_sumproduct.h's,
+// shared with csrc/decode_bigram_counts.hip; what this entry shares with wfl_decode_posterior is csrc/path_posterior.h's.  This file
+// keeps the path check's succession test, the loops over the groups, the records and gamma.
 #include "bigram_sumproduct.h"
+#include "path_posterior.h"
 
 namespace {
 
-using namespace bigram_sp;   // the workgroup's shape, the table in LDS, the scale: shared with csrc/decode_bigram_counts.hip
-using bio::NO_CLASS;
+using namespace bigram_sp;
 using lattice::MAX_CLASSES;
-using lattice::round64;
+struct HeadWords : bio::PathHead {};   // (a type of this file: bio::pre_kernel<L, HeadWords, LSE> keeps its name)
 
-constexpr int D = 8;                         // frames per emission group
-
-struct BigramPostLaunch : bio::Launch {
+struct BigramPostLaunch : bio::PathLaunch {
   const float* trans;  // [N][N], rows the previous symbol
-  const int* ids;
-  float *logz, *post, *cls_post;
-};
-
-// head of a clip's workspace, in words: the alpha records, then the path's (pair, kind) per frame
-__host__ __device__ inline long off_sel(int T) { return round64(3L * T); }
-struct HeadWords {
-  __host__ __device__ long operator()(int T) const { return off_sel(T) + round64(T); }
 };
 
 __global__ __launch_bounds__(NT) void bigram_post_chain_kernel(BigramPostLaunch a) {
@@ -73,259 +67,117 @@ __global__ __launch_bounds__(NT) void bigram_post_chain_kernel(BigramPostLaunch 
   __shared__ int info[MAX_CLASSES];    // class -> pair | kind << 16 (kind 0 O, 1 B, 2 I); -1 never chosen
 
   const bio::Clip cl = a.clip[blockIdx.x];
-  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-  const int T = cl.T, C = a.C, o_id = a.o_id, N = a.n_pairs + 1, LD = row_stride(N);
-  const int* ids = a.ids + cl.frame_off;
+  const int tid = threadIdx.x;
+  const int T = cl.T, N = a.n_pairs + 1;
   float* post = a.post + cl.frame_off;
   float* cls_post = a.cls_post + cl.frame_off;
-
-  float* tab = (float*)lds;
-  float* pv = (float*)(lds + table_bytes(N));   // [NW][MAX_SYMBOLS]
-  float* endv = pv + NW * MAX_SYMBOLS;          // end[] going forward, u[] going backward
-  int* symB = (int*)(endv + MAX_SYMBOLS);
-  int* symI = symB + MAX_SYMBOLS;
+  Chain<JT> ch(lds, tid, tid >> 6, T, N, (N + 63) / 64);
 
   // ---- the class table: thread p owns phoneme p here (one slot per thread); a bad one is status 4
   int cB[1], cI[1];
-  if (bio::class_table<1, NT>(a.pairs, a.n_pairs, C, o_id, used, info, cB, cI)) { bio::refuse<NT>(a, cl, 4); return; }
+  if (bio::class_table<1, NT>(a.pairs, a.n_pairs, a.C, a.o_id, used, info, cB, cI)) { bio::refuse<NT>(a, cl, 4); return; }
   if (T == 0) {
     if (tid == 0) { a.logz[cl.clip] = 0.f; a.status[cl.clip] = 0; }
     return;
   }
-  if (tid < a.n_pairs) { symB[tid + 1] = cB[0]; symI[tid + 1] = cI[0]; }
-  if (tid == 0) { symB[0] = o_id; symI[0] = NO_CLASS; }
-  stage_table(a.trans, N, tab);
-  if (tid < MAX_SYMBOLS) endv[tid] = tid == 0 ? 1.f : 0.f;   // the virtual O frame
-  __syncthreads();
+  ch.stage(a.trans, a.n_pairs, a.o_id, cB[0], cI[0]);
 
   unsigned* w0 = a.ws + cl.ws_off;
   float* rec = (float*)w0;                                     // [T][3]: alpha(B-p) or alpha(O), alpha(I-p) or 0, scale exponent
-  int* sel = (int*)(w0 + off_sel(T));
-  const float* rowmax = (const float*)(w0 + bio::tail_stat(HeadWords{}(T)));
+  int* sel = (int*)(w0 + bio::off_sel(T));
   const unsigned* forced = w0 + bio::tail_forced(HeadWords{}(T), T);
-  const float* Z = a.logits + cl.frame_off * a.ldl;
 
-  // ---- is ids a path of this grammar?  Every frame on its own: a class of the table, I-p only after B-p / I-p, O on a forced frame,
-  // and a run (every B-q frame, every O frame after a phoneme) opened only through a succession the table allows.
+  // ---- is ids a path of this grammar?  Every frame on its own; here also: a run (every B-q frame, every O frame after a phoneme) is
+  // opened only through a succession the table allows
   bool bad = false;
-  for (int t = tid; t < T; t += NT) {
-    const int c = ids[t];
-    const int in = (c >= 0 && c < C) ? info[c] : -1;
-    const int pc = t ? ids[t - 1] : o_id;
-    const int pin = (pc >= 0 && pc < C) ? info[pc] : -1;
-    if (in < 0) bad = true;
-    else if (pin >= 0) {                                       // (a bad previous class is found at its own frame)
-      const int kind = in >> 16, pkind = pin >> 16;
-      const int sy = kind ? (in & 0xffff) + 1 : 0, psy = pkind ? (pin & 0xffff) + 1 : 0;
-      if (kind == 2) {
-        if (pkind == 0 || psy != sy) bad = true;
-      } else if (kind == 1 || psy != 0) {
-        if (!(tab[psy * LD + sy] > 0.f)) bad = true;
-      }
-    }
-    if (in > 0 && forced[t]) bad = true;                       // (in == 0 is O)
-    sel[t] = in < 0 ? 0 : in;
-  }
+  for (int t = tid; t < T; t += NT)
+    bad |= bio::path_step_bad(a.ids + cl.frame_off, t, a.C, a.o_id, info, forced, sel, [&](int in, int pin) {
+      const int sy = (in >> 16) ? (in & 0xffff) + 1 : 0, psy = (pin >> 16) ? (pin & 0xffff) + 1 : 0;
+      return ((in >> 16) == 1 || psy != 0) && !(ch.tab[psy * ch.LD + sy] > 0.f);
+    });
   if (__syncthreads_or(bad ? 1 : 0)) { bio::refuse<NT>(a, cl, 8); return; }
   __threadfence_block();
   __syncthreads();                                             // sel[] is read back by every thread below
 
-  // ---- thread q < N owns symbol q: x0 = O's state (q = 0) or B-q's, x1 = I-q's (0 for O and for a phoneme without an I class)
-  const bool owner = tid < N;
-  const int myB = owner ? symB[tid] : o_id, myI = owner ? symI[tid] : NO_CLASS;
-  const bool hasI = myI != NO_CLASS;
-  const int col0 = myB, col1 = hasI ? myI : o_id;              // (a state that does not exist reads O's column and gets emission 0)
-
-  // a group of D frames from t0 on: the raw logits, the row maxima, the forced flags, the path's (pair, kind)
-  auto load_group = [&](int t0, float (&o0)[D], float (&o1)[D], float (&om)[D], unsigned (&of)[D], int (&os)[D]) {
-#pragma unroll
-    for (int f = 0; f < D; ++f) {
-      const int t = min(t0 + f, T - 1);          // (the tail of the last group re-reads the last row; it is never used)
-      const float* z = Z + (long)t * a.ldl;
-      o0[f] = z[col0];
-      o1[f] = z[col1];
-      om[f] = rowmax[t];
-      of[f] = forced[t];
-      os[f] = sel[t];
-    }
-  };
-  // ... turned into emissions in place, off the chain
-  auto to_emissions = [&](float (&o0)[D], float (&o1)[D], const float (&om)[D], const unsigned (&of)[D]) {
-#pragma unroll
-    for (int f = 0; f < D; ++f) {
-      const bool frc = of[f] != 0;
-      const float x = expf(o0[f] - om[f]);
-      o0[f] = tid == 0 ? (frc ? 1.f : fmaxf(x, W_MIN)) : (frc ? 0.f : x);
-      o1[f] = (frc || !hasI) ? 0.f : expf(o1[f] - om[f]);
-    }
-  };
-
-  // this thread's slice of the summed-over symbols and its output symbols
-  const int NS = (N + NW - 1) / NW;
-  const int s_lo = min(wv * NS, N), s_hi = min(s_lo + NS, N);
-  int tq[JT];
-#pragma unroll
-  for (int j = 0; j < JT; ++j) tq[j] = min(lane + 64 * j, N - 1);   // (a lane past N repeats the last symbol and writes nothing)
-  const int nj = (N + 63) / 64;
-  const float* mine = pv + tid;
-
-  float e0[D], e1[D], mx[D];
-  unsigned fc[D];
-  int sl[D];
+  ch.own(a.logits + cl.frame_off * a.ldl, a.ldl, (const float*)(w0 + bio::tail_stat(HeadWords{}(T))), forced);
+  Group g;
+  int sl[D];                                                   // the path's (pair, kind) of the group's frames
+  const auto owns = [&](int se) { return tid == ((se >> 16) ? (se & 0xffff) + 1 : 0); };
 
   // ================================================================================================================ forward sweep
-  float x0 = tid == 0 ? 1.f : 0.f, x1 = 0.f;     // the virtual O frame
-  long KA = 0;                                   // true alpha = x 2^KA (the same in every thread)
-  load_group(0, e0, e1, mx, fc, sl);
-  to_emissions(e0, e1, mx, fc);
+  ch.start_forward();
+  ch.load_group(0, g, [&](int f, int t) { sl[f] = sel[t]; });
+  ch.to_emissions(g);
   for (int t0 = 0; t0 < T; t0 += D) {
-    float n0[D], n1[D], nm[D];
-    unsigned nf[D];
+    Group n;
     int ns[D];
     const bool more = t0 + D < T;
-    if (more) load_group(t0 + D, n0, n1, nm, nf, ns);
+    if (more) ch.load_group(t0 + D, n, [&](int f, int t) { ns[f] = sel[t]; });
 #pragma unroll
     for (int f = 0; f < D; ++f) {
       const int t = t0 + f;
-      if (t < T) {                               // (uniform)
-        float m = 0.f;
-#pragma unroll
-        for (int j = 0; j < JT; ++j) m = fmaxf(m, endv[tq[j]]);
-        int ex;
-        const float sc = unscale(wave_largest(m), ex);
-        KA += ex;
-        // partial sums over this wave's predecessors
-        float acc[JT];
-#pragma unroll
-        for (int j = 0; j < JT; ++j) acc[j] = 0.f;
-#pragma unroll 4
-        for (int s = s_lo; s < s_hi; ++s) {
-          const float e = endv[s] * sc;
-          const float* row = tab + s * LD;
-#pragma unroll
-          for (int j = 0; j < JT; ++j)
-            if (j < nj) acc[j] = fmaf(e, row[tq[j]], acc[j]);   // (uniform)
-        }
-#pragma unroll
-        for (int j = 0; j < JT; ++j)
-          if (lane + 64 * j < N) pv[wv * MAX_SYMBOLS + lane + 64 * j] = acc[j];
-        __syncthreads();
-        if (owner) {
-          const float in = (mine[0] + mine[MAX_SYMBOLS]) + (mine[2 * MAX_SYMBOLS] + mine[3 * MAX_SYMBOLS]);
-          const float both = (x0 + x1) * sc;     // what I-q continues from
-          x1 = e1[f] * both;                     // (O: e1 is 0)
-          x0 = e0[f] * in;
-          endv[tid] = x0 + x1;
-          // the path's own symbol, by the thread that owns it
-          const int se = sl[f];
-          if (tid == ((se >> 16) ? (se & 0xffff) + 1 : 0)) {
+      if (t < T)                                 // (uniform)
+        ch.forward_frame(g.e0[f], g.e1[f], [](float) {}, [&] {
+          if (owns(sl[f])) {                     // the path's own symbol, by the thread that owns it
             float* r = rec + 3L * t;
-            r[0] = x0;
-            r[1] = x1;
-            r[2] = __int_as_float((int)KA);      // (the low 32 bits: the backward sweep needs only differences of exponents)
+            r[0] = ch.x0;
+            r[1] = ch.x1;
+            r[2] = __int_as_float((int)ch.KA);   // (the low 32 bits: the backward sweep needs only differences of exponents)
           }
-        }
-        __syncthreads();
-      }
+        });
     }
     if (more) {
-      to_emissions(n0, n1, nm, nf);
+      ch.to_emissions(n);
+      g.take(n);
 #pragma unroll
-      for (int f = 0; f < D; ++f) { e0[f] = n0[f]; e1[f] = n1[f]; sl[f] = ns[f]; }
+      for (int f = 0; f < D; ++f) sl[f] = ns[f];
     }
   }
-  // Z = zsum 2^KA, every state may end the clip (every thread computes the same sum)
-  double zs = 0.0;
-#pragma unroll
-  for (int j = 0; j < JT; ++j)
-    if (lane + 64 * j < N) zs += (double)endv[lane + 64 * j];
-  const double zsum = lattice::wave_sum(zs);
-  const double inv_zm = 1.0 / zsum;
-  const int ka_end = (int)KA;
-  __threadfence_block();
-  __syncthreads();                               // the records are read back below, and end[] becomes u[]
+  ch.end_forward();
 
   // =============================================================================================================== backward sweep
-  float bX = 1.f;                                // beta(O), or beta(B-q) = beta(I-q): the same successors
-  int KB = 0;                                    // true beta = b 2^KB (low 32 bits)
   float r0[D], r1[D], r2[D];
-  auto load_rec = [&](int t0, float (&o0)[D], float (&o1)[D], float (&o2)[D]) {
-#pragma unroll
-    for (int f = 0; f < D; ++f) {
-      const float* r = rec + 3L * min(t0 + f, T - 1);
-      o0[f] = r[0];
-      o1[f] = r[1];
-      o2[f] = r[2];
-    }
-  };
   const int tl = (T - 1) / D * D;                // the last group
-  load_group(tl, e0, e1, mx, fc, sl);
-  load_rec(tl, r0, r1, r2);
-  to_emissions(e0, e1, mx, fc);
+  ch.load_group(tl, g, [&](int f, int t) { sl[f] = sel[t]; });
+  bio::load_rec(rec, tl, T, r0, r1, r2);
+  ch.to_emissions(g);
   for (int t0 = tl; t0 >= 0; t0 -= D) {
-    float n0[D], n1[D], nm[D], m0[D], m1[D], m2[D];
-    unsigned nf[D];
+    Group n;
+    float m0[D], m1[D], m2[D];
     int ns[D];
     const bool more = t0 > 0;
     if (more) {
-      load_group(t0 - D, n0, n1, nm, nf, ns);
-      load_rec(t0 - D, m0, m1, m2);
+      ch.load_group(t0 - D, n, [&](int f, int t) { ns[f] = sel[t]; });
+      bio::load_rec(rec, t0 - D, T, m0, m1, m2);
     }
 #pragma unroll
     for (int f = D - 1; f >= 0; --f) {
       const int t = t0 + f;
       if (t < T) {                               // (uniform)
         // gamma of the path's class at t, by the thread that owns its symbol
-        const int se = sl[f];
-        const int kind = se >> 16;
-        if (tid == (kind ? (se & 0xffff) + 1 : 0)) {
-          const int sh = __float_as_int(r2[f]) + KB - ka_end;            // (wraps to the true, small difference)
-          const double k = ldexp((double)bX * inv_zm, sh);
-          double gp = (double)(r0[f] + r1[f]) * k, gc = (double)(kind == 2 ? r1[f] : r0[f]) * k;
-          gp = gp >= 0.0 ? fmin(gp, 1.0) : 0.0;                          // (a NaN of an overflowed clip is reported as 0)
-          gc = gc >= 0.0 ? fmin(gc, 1.0) : 0.0;
-          post[t] = (float)gp;
-          cls_post[t] = (float)gc;
-        }
+        if (owns(sl[f])) bio::write_gamma(r0[f], r1[f], r2[f], sl[f] >> 16, ch.bX, ch.inv_zm, ch.KB, ch.ka_end, post + t, cls_post + t);
         if (t > 0) {                             // (uniform)
-          float pI = 0.f;
-          if (owner) {
-            endv[tid] = e0[f] * bX;              // u[q]
-            pI = e1[f] * bX;
-          }
-          __syncthreads();
-          float m = 0.f;
-#pragma unroll
-          for (int j = 0; j < JT; ++j) m = fmaxf(m, endv[tq[j]]);
-          int ex;
-          const float sc = unscale(wave_largest(m), ex);
-          KB += ex;
-          // partial sums over this wave's successors: lane l holds the rows l, l + 64, l + 128
-          float acc[JT];
+          float pI, acc[JT];
+          const float sc = ch.backward_publish(g.e0[f], g.e1[f], pI);
 #pragma unroll
           for (int j = 0; j < JT; ++j) acc[j] = 0.f;
 #pragma unroll 4
-          for (int q = s_lo; q < s_hi; ++q) {
-            const float u = endv[q] * sc;
-            const float* col = tab + q;
+          for (int q = ch.s_lo; q < ch.s_hi; ++q) {
+            const float u = ch.endv[q] * sc;
+            const float* col = ch.tab + q;
 #pragma unroll
             for (int j = 0; j < JT; ++j)
-              if (j < nj) acc[j] = fmaf(col[tq[j] * LD], u, acc[j]);     // (uniform)
+              if (j < ch.nj) acc[j] = fmaf(col[ch.tq[j] * ch.LD], u, acc[j]);   // (uniform)
           }
-#pragma unroll
-          for (int j = 0; j < JT; ++j)
-            if (lane + 64 * j < N) pv[wv * MAX_SYMBOLS + lane + 64 * j] = acc[j];
-          __syncthreads();
-          if (owner) bX = ((mine[0] + mine[MAX_SYMBOLS]) + (mine[2 * MAX_SYMBOLS] + mine[3 * MAX_SYMBOLS])) + pI * sc;
+          ch.backward_update(acc, pI, sc);
         }
       }
     }
     if (more) {
-      to_emissions(n0, n1, nm, nf);
+      ch.to_emissions(n);
+      g.take(n);
 #pragma unroll
       for (int f = 0; f < D; ++f) {
-        e0[f] = n0[f];
-        e1[f] = n1[f];
         sl[f] = ns[f];
         r0[f] = m0[f];
         r1[f] = m1[f];
@@ -333,17 +185,7 @@ __global__ __launch_bounds__(NT) void bigram_post_chain_kernel(BigramPostLaunch 
       }
     }
   }
-
-  // ---- logZ: the mantissa, the exponents, and what the emissions left out (the row maxima; O's logit on a forced frame)
-  if (wv == 0) {
-    double ls = 0.0;
-    for (int t = lane; t < T; t += 64) ls += forced[t] ? (double)Z[(long)t * a.ldl + o_id] : (double)rowmax[t];
-    ls = lattice::wave_sum(ls);
-    if (lane == 0) {
-      a.logz[cl.clip] = (float)(log(zsum) + (double)KA * 0.69314718055994530942 + ls);
-      a.status[cl.clip] = 0;
-    }
-  }
+  ch.write_logz(a, cl);
 }
 
 }  // namespace
@@ -359,22 +201,18 @@ int32_t wfl_decode_bigram_posterior(const float* logits, int64_t ldl, int32_t C,
                                     const float* trans, float threshold, const int32_t* ids, void* workspace, int64_t workspace_bytes,
                                     float* logz, float* post, float* cls_post, int32_t* status, void* stream) {
   const char* fn = "wfl_decode_bigram_posterior";
-  bool any_frame;
+  bool any_frame, over;
   if (const int rc = bio::check_args(fn, C, o_id, ldl, frame_off_host, n_frames_host, n_clips, n_pairs, 0.f, threshold, any_frame)) return rc;
   if (n_clips == 0) return 0;
-  if (!logz || !status || (n_pairs > 0 && !pairs) || (any_frame && (!logits || !ids || !post || !cls_post)))
+  if (bio::path_pointer_missing(logits, pairs, n_pairs, ids, logz, post, cls_post, status, any_frame) ||
+      table_missing(trans, any_frame, C, n_pairs, over))
     return lattice::fail(fn, -1, "null device pointer");
-  // over the symbol cap: status 2, as over the class cap; the table is read only when the clips are scored
-  const int N = n_pairs + 1;
-  const bool over = N > MAX_SYMBOLS;
-  if (any_frame && !trans && !bio::refused_status(C, n_pairs, over)) return lattice::fail(fn, -1, "null device pointer");
-  BigramPostLaunch a{};
-  a.logits = logits; a.ldl = ldl; a.C = C; a.o_id = o_id; a.pairs = pairs; a.n_pairs = n_pairs; a.threshold = threshold; a.status = status;
+  auto a = bio::launch_of<BigramPostLaunch>(logits, ldl, C, o_id, pairs, n_pairs, threshold, status);
   a.trans = trans; a.ids = ids; a.logz = logz; a.post = post; a.cls_post = cls_post;
   return bio::run<false>(fn, a, over, frame_off_host, n_frames_host, n_clips, workspace, workspace_bytes, stream, HeadWords{},
                          [&](const BigramPostLaunch& a, hipStream_t s) {
                            if (const int rc = lattice::reserve_lds<bigram_post_chain_kernel, MAX_LDS>(fn)) return rc;
-                           hipLaunchKernelGGL(bigram_post_chain_kernel, dim3(a.n), dim3(NT), lds_bytes(N), s, a);
+                           hipLaunchKernelGGL(bigram_post_chain_kernel, dim3(a.n), dim3(NT), lds_bytes(n_pairs + 1), s, a);
                            return 0;
                          });
 }

@@ -34,26 +34,19 @@
 // Before the sweeps the wave checks in parallel that ids is a path of the grammar (status 8) and leaves class -> (pair, kind) per frame.
 // Workspace per clip, in words: [alpha records 3 T] [pair | kind << 16 per frame T] [row maxima T] [forced flags T], each rounded up to 64;
 // the first two are this file's head, the last two the tail of csrc/bio_grammar.h.  That header holds everything this entry shares with
-// wfl_decode and wfl_decode_bigram; this file holds the chain kernel and the entry's own pointer checks.
-#include "bio_grammar.h"
+// wfl_decode and wfl_decode_bigram, csrc/path_posterior.h what it shares with wfl_decode_bigram_posterior (the path's launch fields, this
+// head, the per-frame path check, the records' loads, gamma); this file holds the chain kernel's frame.
+#include "path_posterior.h"
 #include "wfl_asr.h"
 
 namespace {
 
 using bio::NO_CLASS;
 using lattice::MAX_CLASSES;
-using lattice::round64;
+struct HeadWords : bio::PathHead {};   // (a type of this file: bio::pre_kernel<L, HeadWords, LSE> keeps its name)
 
-struct PostLaunch : bio::Launch {
+struct PostLaunch : bio::PathLaunch {
   float lambda;
-  const int* ids;
-  float *logz, *post, *cls_post;
-};
-
-// head of a clip's workspace, in words: the alpha records, then the path's (pair, kind) per frame
-__host__ __device__ inline long off_sel(int T) { return round64(3L * T); }
-struct HeadWords {
-  __host__ __device__ long operator()(int T) const { return off_sel(T) + round64(T); }
 };
 
 constexpr float TINY = 0x1p-60f;   // floor of an O emission and of exp(-lambda)
@@ -91,7 +84,6 @@ __global__ __launch_bounds__(64) void decode_post_chain_kernel(PostLaunch a) {
   const bio::Clip cl = a.clip[blockIdx.x];
   const int lane = threadIdx.x;
   const int T = cl.T, C = a.C, o_id = a.o_id;
-  const int* ids = a.ids + cl.frame_off;
   float* post = a.post + cl.frame_off;
   float* cls_post = a.cls_post + cl.frame_off;
 
@@ -104,25 +96,15 @@ __global__ __launch_bounds__(64) void decode_post_chain_kernel(PostLaunch a) {
 
   unsigned* w0 = a.ws + cl.ws_off;
   float* rec = (float*)w0;                                     // [T][3]: alpha(B-p) or alpha(O), alpha(I-p) or 0, scale exponent
-  int* sel = (int*)(w0 + off_sel(T));
+  int* sel = (int*)(w0 + bio::off_sel(T));
   const float* rowmax = (const float*)(w0 + bio::tail_stat(HeadWords{}(T)));
   const unsigned* forced = w0 + bio::tail_forced(HeadWords{}(T), T);
   const float* Z = a.logits + cl.frame_off * a.ldl;
 
-  // ---- is ids a path of this grammar?  Every frame on its own: a class of the table, I-p only after B-p / I-p, O on a forced frame.
+  // ---- is ids a path of this grammar?  Every frame on its own; any run may be opened here.
   bool bad = false;
-  for (int t = lane; t < T; t += 64) {
-    const int c = ids[t];
-    const int in = (c >= 0 && c < C) ? info[c] : -1;
-    if (in < 0) bad = true;
-    else if ((in >> 16) == 2) {
-      const int pc = t ? ids[t - 1] : o_id;
-      const int pin = (pc >= 0 && pc < C) ? info[pc] : -1;
-      if (pin < 0 || (pin >> 16) == 0 || (pin & 0xffff) != (in & 0xffff)) bad = true;
-    }
-    if (in > 0 && forced[t]) bad = true;                       // (in == 0 is O)
-    sel[t] = in < 0 ? 0 : in;
-  }
+  for (int t = lane; t < T; t += 64)
+    bad |= bio::path_step_bad(a.ids + cl.frame_off, t, C, o_id, info, forced, sel, [](int, int) { return false; });
   if (__any(bad)) { bio::refuse<64>(a, cl, 8); return; }
   __threadfence_block();
   __syncthreads();                                             // sel[] is read back by every lane below
@@ -256,18 +238,9 @@ __global__ __launch_bounds__(64) void decode_post_chain_kernel(PostLaunch a) {
   for (int s = 0; s < S; ++s) bX[s] = 1.f;
   int KB = 0;                                  // true beta = b 2^KB (low 32 bits)
   float r0[D], r1[D], r2[D];
-  auto load_rec = [&](int t0, float (&o0)[D], float (&o1)[D], float (&o2)[D]) {
-#pragma unroll
-    for (int f = 0; f < D; ++f) {
-      const float* r = rec + 3L * min(t0 + f, T - 1);
-      o0[f] = r[0];
-      o1[f] = r[1];
-      o2[f] = r[2];
-    }
-  };
   const int tl = (T - 1) / D * D;              // the last group
   load_group(tl, eb, ei, eo, mx, fc, sl);
-  load_rec(tl, r0, r1, r2);
+  bio::load_rec(rec, tl, T, r0, r1, r2);
   to_emissions(eb, ei, eo, mx, fc);
   for (int t0 = tl; t0 >= 0; t0 -= D) {
     float nb[D][S], ni[D][S], no[D], nm[D], n0[D], n1[D], n2[D];
@@ -276,7 +249,7 @@ __global__ __launch_bounds__(64) void decode_post_chain_kernel(PostLaunch a) {
     const bool more = t0 > 0;
     if (more) {
       load_group(t0 - D, nb, ni, no, nm, nf, ns);
-      load_rec(t0 - D, n0, n1, n2);
+      bio::load_rec(rec, t0 - D, T, n0, n1, n2);
     }
 #pragma unroll
     for (int f = D - 1; f >= 0; --f) {
@@ -291,15 +264,7 @@ __global__ __launch_bounds__(64) void decode_post_chain_kernel(PostLaunch a) {
           for (int s = 0; s < S; ++s)
             if (slot == s) bs = bX[s];
         }
-        if (lane == (se & 63)) {
-          const int sh = __float_as_int(r2[f]) + KB - ka_end;          // (wraps to the true, small difference)
-          const double k = ldexp((double)bs * inv_zm, sh);
-          double gp = (double)(r0[f] + r1[f]) * k, gc = (double)(kind == 2 ? r1[f] : r0[f]) * k;
-          gp = gp >= 0.0 ? fmin(gp, 1.0) : 0.0;                        // (a NaN of an overflowed clip is reported as 0)
-          gc = gc >= 0.0 ? fmin(gc, 1.0) : 0.0;
-          post[t] = (float)gp;
-          cls_post[t] = (float)gc;
-        }
+        if (lane == (se & 63)) bio::write_gamma(r0[f], r1[f], r2[f], kind, bs, inv_zm, KB, ka_end, post + t, cls_post + t);
         if (t > 0) {
           float part[S], pI[S];
 #pragma unroll
@@ -340,13 +305,7 @@ __global__ __launch_bounds__(64) void decode_post_chain_kernel(PostLaunch a) {
   }
 
   // ---- logZ: the mantissa, the exponents, and what the emissions left out (the row maxima; O's logit on a forced frame)
-  double ls = 0.0;
-  for (int t = lane; t < T; t += 64) ls += forced[t] ? (double)Z[(long)t * a.ldl + o_id] : (double)rowmax[t];
-  ls = lattice::wave_sum(ls);
-  if (lane == 0) {
-    a.logz[cl.clip] = (float)(log((double)zsum) + (double)KA * 0.69314718055994530942 + ls);
-    a.status[cl.clip] = 0;
-  }
+  bio::write_logz(a, cl, lane, Z, rowmax, forced, (double)zsum, KA);
 }
 
 }  // namespace
@@ -365,10 +324,9 @@ int32_t wfl_decode_posterior(const float* logits, int64_t ldl, int32_t C, int32_
   bool any_frame;
   if (const int rc = bio::check_args(fn, C, o_id, ldl, frame_off_host, n_frames_host, n_clips, n_pairs, lambda, threshold, any_frame)) return rc;
   if (n_clips == 0) return 0;
-  if (!logz || !status || (n_pairs > 0 && !pairs) || (any_frame && (!logits || !ids || !post || !cls_post)))
+  if (bio::path_pointer_missing(logits, pairs, n_pairs, ids, logz, post, cls_post, status, any_frame))
     return lattice::fail(fn, -1, "null device pointer");
-  PostLaunch a{};
-  a.logits = logits; a.ldl = ldl; a.C = C; a.o_id = o_id; a.pairs = pairs; a.n_pairs = n_pairs; a.threshold = threshold; a.status = status;
+  auto a = bio::launch_of<PostLaunch>(logits, ldl, C, o_id, pairs, n_pairs, threshold, status);
   a.lambda = lambda; a.ids = ids; a.logz = logz; a.post = post; a.cls_post = cls_post;
   const int S = bio::slots_of(n_pairs);
   return bio::run<false>(fn, a, false, frame_off_host, n_frames_host, n_clips, workspace, workspace_bytes, stream, HeadWords{},
