@@ -391,6 +391,27 @@ int32_t wfl_align_optional(const float* logits, int64_t ldl, int32_t C, int32_t 
                            void* workspace, int64_t workspace_bytes, int32_t* ids, int32_t* tok, float* score, int32_t* skipped,
                            int32_t* status, void* stream);
 
+/* ---- wfl_align with filler tokens: a token that matches anything, for a stretch of audio the transcript does not spell
+ * (`postprocess.filler_token`; wfl-asr_amd/align.py).  wfl_align_windowed's arguments (tok_win may be null: no windows) plus tok_fill
+ * (device), [total tokens] int32 0 | 1, rows as tok_cls, and filler_penalty = phi >= 0 in nats per frame.  The states, arcs and tie rules
+ * are wfl_align's; only the emission of a flagged token differs:
+ *     EB_t(k) = EI_t(k) = max_{0 <= c < C} z_t[c] - phi        where tok_fill[k] == 1
+ * the maximum over ALL classes, the gap classes included, so a frame goes to a filler instead of a neighbouring token only where that
+ * token's class is more than phi below the frame's best class.  Windows mask EB of a filler like any token's.  A flagged token's tok_cls
+ * row must still hold one valid pair (the host writes (o_id, o_id)); it is never read for emissions.  With every flag 0 every output is
+ * wfl_align's (null tok_win) or wfl_align_windowed's, bit for bit, for any phi.
+ * Outputs: in a filler's frames tok[t] = k and ids[t] is the frame's first arg-max class over all C (the lowest index on a tie);
+ * everywhere else ids, tok as wfl_align's; score[b] = sum e_t - sum lse_t as wfl_align's.  status[b]: wfl_align's codes (1: T < N, or
+ * windows no path meets; 2 over the cap); 4 also for a flag other than 0 | 1.  A clip with status != 0 gets ids = o_id, tok = -1, score 0.
+ * Host-side negative returns as wfl_align's, and: a null tok_fill with any token present, a negative, infinite or NaN filler_penalty.
+ * Workspace: wfl_align's own figure (wfl_align_filler_workspace_bytes returns wfl_align_workspace_bytes' sum). */
+int64_t wfl_align_filler_workspace_bytes(const int32_t* n_frames_host, const int32_t* n_tok_host, int32_t n_clips);
+int32_t wfl_align_filler(const float* logits, int64_t ldl, int32_t C, int32_t o_id, const int64_t* frame_off_host,
+                         const int32_t* n_frames_host, const int32_t* tok_off_host, const int32_t* n_tok_host, const int32_t* tok_cls,
+                         const int32_t* tok_win, const int32_t* gap_cls, int32_t n_clips, const int32_t* tok_fill, float filler_penalty,
+                         void* workspace, int64_t workspace_bytes, int32_t* ids, int32_t* tok, float* score, int32_t* status,
+                         void* stream);
+
 /* ---- Posteriors of a Viterbi alignment by forward-backward on the GPU (`postprocess.align_scores`; wfl-asr_amd/align.py).  No
  * counterpart in the reference, which reports no confidence for its string match.  The lattice, emissions EB / EI / EG, start and end
  * states, caps (C <= 1024, N <= 4096) and argument conventions are wfl_align's.  The weight of a path is exp(sum_t e_t(state_t));

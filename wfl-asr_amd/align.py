@@ -6,7 +6,7 @@ posteriors: a missed, inserted or mislabelled phoneme shifts every later token o
 the frame logits for the best path that spells exactly the transcript, in order (csrc/align.hip, include/wfl_asr.h `wfl_align`): every
 token gets one contiguous, time-ordered run of frames, none is dropped.
 
-  _call                 the one call path of the nine entries below: workspace, argument order, stream, check (as decode._call)
+  _call                 the one call path of the entries below: workspace, argument order, stream, check (as decode._call)
   AlignBatch            a wave's ragged batch as the Labeler holds it: `windows` / `min_frames`, `select`, `pack`, `args`
   reuses_packed         whether a scoring call runs on the search's PackedClips or on tables packed again for its clips
   viterbi_align         the C ABI on CUDA tensors: a ragged batch of clips in one call; with `windows`, every token may open only
@@ -14,6 +14,11 @@ token gets one contiguous, time-ordered run of frames, none is dropped.
                         every token occupies at least that many frames (`wfl_align_min_duration`, `postprocess.min_duration`)
   viterbi_align_optional  the same search where a path may leave out the tokens the caller marks (`wfl_align_optional`,
                         `postprocess.optional_tokens`), each at `skip_penalty` nats -> viterbi_align's four and `skipped` per token
+  viterbi_align_filler  the same search where the tokens the caller marks are fillers: they match anything, every frame of their run
+                        scoring the frame's best class minus `filler_penalty` (`wfl_align_filler`, `postprocess.filler_token`)
+  filler_flags / collapse_fillers / filler_segments   `postprocess.filler_token` -> a flag per transcript token; runs of fillers merged;
+                        the free segments a filler's span holds, clipped to it
+  FillerSpan / format_fillers_tsv / format_folder_fillers_tsv   one file's filler rows, {stem}.fillers.tsv, the folder's list
   optional_flags / min_frames_needed   `postprocess.optional_tokens` -> a flag per transcript token; the frames such a transcript needs
   skipped_tokens / format_skipped_tsv / format_folder_skipped_tsv   one file's SkippedToken rows, {stem}.skipped.tsv, the folder's list
   optional_posteriors   forward-backward over that skip lattice (`wfl_align_optional_posterior`; `postprocess.optional_scores`):
@@ -84,6 +89,10 @@ def workspace_bytes(n_frames, n_tokens) -> int:
 
 def optional_workspace_bytes(n_frames, n_tokens) -> int:
     return _workspace_bytes("wfl_align_optional_workspace_bytes", n_frames, n_tokens)
+
+
+def filler_workspace_bytes(n_frames, n_tokens) -> int:
+    return _workspace_bytes("wfl_align_filler_workspace_bytes", n_frames, n_tokens)
 
 
 def optional_posterior_workspace_bytes(n_frames, n_tokens) -> int:
@@ -209,6 +218,27 @@ def _pack_optional(optional, N):
     return out.astype(np.int32)
 
 
+def _pack_fillers(fillers, N):
+    """Per clip a list of flags per token (bools, or ints 0 | 1), or None for a clip without fillers -> [max(tokens, 1)] int32, rows as
+    the token table's.  The values are not judged here: a flag other than 0 | 1 is the kernel's STATUS_BAD_CLASS for its clip."""
+    if len(fillers) != len(N):
+        raise ValueError("fillers needs one entry per clip (None: no filler)")
+    out = np.zeros(max(int(N.sum()), 1), np.int64)
+    k0 = 0
+    for f, n in zip(fillers, N):
+        if f is not None:
+            if any(not isinstance(x, (bool, np.bool_, int, np.integer)) for x in f):
+                raise ValueError("filler flags are bools")
+            f = np.asarray(f, np.int64).reshape(-1)
+            if len(f) != n:
+                raise ValueError(f"a clip with {n} tokens needs {n} filler flags, got {len(f)}")
+            out[k0:k0 + n] = f
+        k0 += int(n)
+    if out.min() < -2 ** 31 or out.max() > 2 ** 31 - 1:
+        raise ValueError("filler flags are int32")
+    return out.astype(np.int32)
+
+
 def pack_clips(logits, n_frames, token_classes, gap_classes, frame_offsets=None, windows=None, min_frames=None) -> PackedClips:
     """Validate a ragged batch and upload its token and gap tables once; pass the result as `packed=` to viterbi_align and to
     alignment_posteriors of the same batch (the packing is host work that grows with the token count).  windows: per clip a list of
@@ -256,12 +286,13 @@ class AlignBatch(NamedTuple):
     mins: list            # per clip its tokens' minimum frames; None: none (all 1)
     o_id: int
     opts: list = None     # per clip its tokens' optional flags; None (the field or an entry): no token may be skipped
+    fills: list = None    # per clip its tokens' filler flags; None (the field or an entry): no token is a filler
 
     @classmethod
-    def of(cls, lg, frames, alts, gaps, o_id, wins=None, mins=None, opts=None):
+    def of(cls, lg, frames, alts, gaps, o_id, wins=None, mins=None, opts=None, fills=None):
         none = [None] * len(frames)                       # (the clips' rows one after the other in `lg`)
         return cls(lg, list(frames), back_to_back(frames), list(alts), list(gaps), list(wins or none), list(mins or none), o_id,
-                   list(opts or none))
+                   list(opts or none), list(fills) if fills is not None else None)
 
     @property
     def windows(self):
@@ -277,10 +308,17 @@ class AlignBatch(NamedTuple):
         flags = self.opts or []
         return list(flags) if any(f is not None and any(f) for f in flags) else None
 
+    @property
+    def fillers(self):
+        """The per-clip filler flags where any clip has a flag set, else None (the entries without a filler emission)."""
+        flags = self.fills or []
+        return list(flags) if any(f is not None and any(f) for f in flags) else None
+
     def select(self, idx):
         """The sub-batch of the clips `idx`, in that order, on the same logits."""
         idx = [int(b) for b in idx]
-        fields = ("frames", "alts", "gaps", "wins", "mins") + (("opts",) if self.opts is not None else ())
+        fields = ("frames", "alts", "gaps", "wins", "mins") + (("opts",) if self.opts is not None else ()) \
+            + (("fills",) if self.fills is not None else ())
         return self._replace(f0=self.f0[idx], **{k: [getattr(self, k)[b] for b in idx] for k in fields})
 
     def pack(self, with_min) -> PackedClips:
@@ -322,6 +360,7 @@ _ENTRIES = {
     "wfl_align_min_duration_posterior": ("wfl_align_min_duration_posterior", True, True),
     "wfl_align_edits": ("wfl_align_edits", True, False), "wfl_align_insertions": ("wfl_align_insertions", True, False),
     "wfl_align_optional_posterior": ("wfl_align_optional_posterior", True, False),
+    "wfl_align_filler": ("wfl_align_filler", True, False),
 }
 
 
@@ -419,6 +458,47 @@ def viterbi_align_optional(logits, n_frames, token_classes, gap_classes, o_id, o
     skipped = torch.empty(max(ntok, 1), dtype=torch.int32, device=dev)
     _call("wfl_align_optional", logits, o_id, packed, (d_opt, lam), (ids, tok, score, skipped, status), stream, temporaries=(d_opt,))
     return ids, tok, score[:nb], status[:nb], skipped[:ntok]
+
+
+def upload_filler(fillers, n_tokens, device):
+    """viterbi_align_filler's flags (per clip a list of bools per token, or None) packed and uploaded once -> [max(tokens, 1)] int32
+    tensor on `device`, for its `fillers` argument.  n_tokens: tokens per clip (PackedClips.N)."""
+    return torch.from_numpy(_pack_fillers(fillers, np.asarray(n_tokens, np.int32).reshape(-1))).to(device)
+
+
+def viterbi_align_filler(logits, n_frames, token_classes, gap_classes, o_id, fillers, filler_penalty=1.0, frame_offsets=None,
+                         stream=None, packed=None, windows=None):
+    """viterbi_align where the tokens marked as fillers match anything (wfl_align_filler): a filler is a token like any other -- one
+    contiguous run of at least one frame, in order, gaps possible on both sides -- and in every frame of its run it scores the frame's
+    largest logit over all classes minus `filler_penalty`.
+
+    fillers         per clip a list of bools per token, or None for a clip without fillers.  The flags travel beside `packed`, not in
+                    it: the same PackedClips serves viterbi_align and this call.  Or upload_filler(...) of such a list.  A filler's
+                    entry of token_classes is a placeholder, one valid pair ((o_id, o_id); token_alternatives writes it): never read
+    filler_penalty  nats >= 0 per frame: a frame goes to a filler instead of a neighbouring token only where that token's class is
+                    more than this below the frame's best class (1.0 is a value to start from, not a measured optimum)
+    windows         as viterbi_align's; a filler's window masks its opening like any token's.  With `packed`, the ones packed there.
+                    A batch packed with `min_frames` is refused
+    -> (ids, tok, score, status): viterbi_align's four.  In a filler's frames tok is the filler's index and ids the frame's first
+    arg-max class over all classes.  STATUS_BAD_CLASS also for a flag other than 0 | 1.  With no flag set every output is
+    viterbi_align's."""
+    if packed is None:
+        packed = pack_clips(logits, n_frames, token_classes, gap_classes, frame_offsets, windows)
+    if packed.d_min is not None:
+        raise ValueError("viterbi_align_filler has no minimum durations: this batch was packed with min_frames")
+    phi = float(filler_penalty)
+    if not (0.0 <= phi < float("inf")):
+        raise ValueError("filler_penalty must be a number of nats >= 0")
+    dev, rows, nb, ntok = logits.device, logits.shape[0], packed.nb, int(packed.N.sum())
+    d_fill = fillers if isinstance(fillers, torch.Tensor) else upload_filler(fillers, packed.N, dev)
+    if d_fill.device != dev or d_fill.dtype != torch.int32 or d_fill.dim() != 1 or d_fill.stride(0) != 1 or d_fill.shape[0] != max(ntok, 1):
+        raise ValueError("uploaded filler flags must be upload_filler's [tokens] int32 tensor for this batch")
+    ids = torch.empty(rows, dtype=torch.int32, device=dev)
+    tok = torch.empty(rows, dtype=torch.int32, device=dev)
+    score = torch.empty(max(nb, 1), dtype=torch.float32, device=dev)
+    status = torch.empty(max(nb, 1), dtype=torch.int32, device=dev)
+    _call("wfl_align_filler", logits, o_id, packed, (d_fill, phi), (ids, tok, score, status), stream, temporaries=(d_fill,))
+    return ids, tok, score[:nb], status[:nb]
 
 
 def _optional_call_args(optional, skip_penalty, packed, logits, what):
@@ -615,10 +695,11 @@ def class_pairs(label_list):
     return {ph: (b[ph], i[ph]) for ph in b if ph in i}
 
 
-def token_alternatives(transcript, table: npost.LabelTable, remap, names, label_list):
+def token_alternatives(transcript, table: npost.LabelTable, remap, names, label_list, filler=None):
     """Per transcript token, the (B, I) class pairs of every phoneme whose OUTPUT name (the merge-map back-mapping `remap` / `names`
     that Labeler._names_for builds) equals the token.  -> (alternatives, None), or (None, reason) when a token matches no phoneme
-    or more than MAX_ALTERNATIVES of them."""
+    or more than MAX_ALTERNATIVES of them.  filler (`postprocess.filler_token`; None: none): a token of that name gets the placeholder
+    pair (O, O) that wfl_align_filler asks for in a filler's row."""
     pairs = class_pairs(label_list)
     by_name = {}
     for p, ph in enumerate(table.names):
@@ -626,6 +707,9 @@ def token_alternatives(transcript, table: npost.LabelTable, remap, names, label_
             by_name.setdefault(names[int(remap[p])], []).append(pairs[ph])
     out = []
     for tokn in transcript:
+        if filler is not None and tokn == filler:
+            out.append([(label_list.index("O"),) * 2])
+            continue
         alts = by_name.get(tokn)
         if not alts:
             return None, f"token {tokn!r} matches no phoneme of the label set"
@@ -649,11 +733,14 @@ def gap_classes(label_list, transcript):
 
 
 def path_segments(ids, tok, chunk_frames, chunk_offsets, chunk_clock, table: npost.LabelTable, alternatives, transcript,
-                  frame_duration, skipped=None):
+                  frame_duration, fillers=None, skipped=None):
     """A path over a file's chunks (ids / tok concatenated, chunk_frames[c] valid frames each) -> [(start_s, end_s, token)], exactly
     one per transcript token, in transcript order.  skipped (viterbi_align_optional's flags of this transcript's tokens; None: no
     token may be missing): the segments are then exactly the tokens whose flag is 0, in order -- a path that lacks a token without
-    the flag, or holds one with it, is the RuntimeError a path that does not spell the transcript always was.
+    the flag, or holds one with it, is the RuntimeError a path that does not spell the transcript always was.  fillers
+    (viterbi_align_filler's flags of this transcript's tokens; None: none): a filler yields exactly one (start, end, name) span like
+    any token's run -- its start from its first frame's offset, its end capped by the next segment -- whatever classes its frames
+    carry: they are decoded as one run of a stand-in phoneme, B on the run's first frame.
 
     Each chunk goes through the native BIO decoder (no median filter) with that chunk's offsets and is shifted by its clock offset,
     as the free decode of Labeler.label_files.  Within a token the ids are first mapped to the token's first alternative (all of
@@ -664,6 +751,16 @@ def path_segments(ids, tok, chunk_frames, chunk_offsets, chunk_clock, table: npo
     tok = np.asarray(tok, np.int32)
     b0 = np.array([a[0][0] for a in alternatives] or [0], np.int32)
     i0 = np.array([a[0][1] for a in alternatives] or [0], np.int32)
+    fill = None
+    if fillers is not None and any(fillers):
+        if len(fillers) != len(transcript):
+            raise ValueError("one filler flag per transcript token")
+        fill = np.asarray([bool(f) for f in fillers] or [False])
+        stand_in = next(((int(b), int(i)) for b in np.nonzero(table.kind == 1)[0]
+                         for i in np.nonzero((table.kind == 2) & (table.phon == table.phon[b]))[0]), None)
+        if stand_in is None:
+            raise ValueError("the label set has no phoneme with both tags")
+        b0[fill[:len(b0)]], i0[fill[:len(i0)]] = stand_in
     segs = []                                            # [start, end, token index]
     pos = 0
     for Tc, offs, t0 in zip(chunk_frames, chunk_offsets, chunk_clock):
@@ -672,6 +769,9 @@ def path_segments(ids, tok, chunk_frames, chunk_offsets, chunk_clock, table: npo
         pos += Tc
         on = tkc >= 0
         is_b = table.kind[idc] == 1
+        if fill is not None:                             # a filler's frames: B where its run opens (not where it goes on over a seam)
+            opens = np.concatenate([[-1 if not (segs and Tc and segs[-1][2] == tkc[0]) else tkc[0]], tkc[:-1]]) != tkc
+            is_b = np.where(on & fill[np.maximum(tkc, 0)], opens, is_b)
         canon = idc.copy()
         canon[on] = np.where(is_b[on], b0[tkc[on]], i0[tkc[on]])
         s, e, _ = npost.decode_bio_ids(canon, table, frame_duration, offs, median=0)
@@ -728,6 +828,25 @@ def optional_flags(transcript, spec):
         return [True] * len(transcript)
     names = set(spec)
     return [t in names for t in transcript]
+
+
+def filler_flags(transcript, name):
+    """`postprocess.filler_token` -> a bool per transcript token for viterbi_align_filler: the tokens equal to `name`."""
+    return [t == name for t in transcript]
+
+
+def collapse_fillers(transcript, name):
+    """-> (the transcript with every run of adjacent fillers merged into one, how many tokens that took away)."""
+    out = [t for j, t in enumerate(transcript) if not (t == name and j and transcript[j - 1] == name)]
+    return out, len(transcript) - len(out)
+
+
+def filler_segments(span, free_segments):
+    """What a filler's span (start_s, end_s, ...) holds of the file's own free decode: every free segment that overlaps the span by
+    more than nothing, clipped to it, in time order.  A span without any is empty."""
+    a, b = float(span[0]), float(span[1])
+    out = [(max(float(s), a), min(float(e), b), ph) for s, e, ph in free_segments if min(float(e), b) - max(float(s), a) > 0.0]
+    return sorted(out, key=lambda g: (g[0], g[1]))
 
 
 def min_frames_needed(flags) -> int:
@@ -1095,4 +1214,32 @@ def folder_optional_rows(per_file):
 def format_folder_optional_tsv(per_file) -> str:
     """optional_scores.tsv: every optional token of every file, the file's name in front of the token's own columns."""
     lines = ["file\t" + OPTIONAL_HEADER] + ["\t".join([name] + _optional_cells(r)) for name, r in folder_optional_rows(per_file)]
+    return "".join(line + "\n" for line in lines)
+
+
+# --------------------------------------------------------------------------------------------------------------- filler tokens
+class FillerSpan(NamedTuple):
+    index: int              # the filler's index in the transcript (after collapse_fillers)
+    start_s: float          # its span on the .lab clock
+    end_s: float
+    frames: int             # the frames of its run
+    names: tuple            # the names of the free segments the span holds (filler_segments), in time order
+
+
+FILLERS_HEADER = "index\tstart_s\tend_s\tframes\tnames"
+
+
+def _filler_cells(r: FillerSpan):
+    return [str(r.index), f"{r.start_s:.7f}", f"{r.end_s:.7f}", str(r.frames), " ".join(str(n) for n in r.names)]
+
+
+def format_fillers_tsv(rows) -> str:
+    """{stem}.fillers.tsv: one line per filler of the transcript."""
+    return "".join("\t".join(c) + "\n" for c in [FILLERS_HEADER.split("\t")] + [_filler_cells(r) for r in rows])
+
+
+def format_folder_fillers_tsv(per_file) -> str:
+    """filler_spans.tsv: [(file name, [FillerSpan])] -> every filler of every file, the file's name in front of the span's own
+    columns, in the files' and the tokens' order."""
+    lines = ["file\t" + FILLERS_HEADER] + ["\t".join([name] + _filler_cells(r)) for name, rows in per_file for r in rows]
     return "".join(line + "\n" for line in lines)

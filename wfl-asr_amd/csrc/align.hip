@@ -47,6 +47,13 @@
 // `skipped` is filled with 1 for the clip's tokens once a path is known to exist, and the last pass stores 0 from every frame that
 // carries a token.  A clip may now have a path with fewer frames than tokens, so it has backpointer words then too
 // (wfl_align_optional_workspace_bytes; wfl_align's figure wherever T >= N), and "no path" is found as the windowed kernels find it.
+//
+// wfl_align_filler is the kernel instantiated with FILL (with and without WIN, never with MIND or OPT): the states, arcs and tie rules
+// are wfl_align's, only the emission of a flagged token differs -- EB = EI = the frame's largest logit over all C classes minus the filler
+// penalty.  Once per stage of the logits ring the block computes that value for every staged row (groups of lanes share a row in LDS; one
+// more barrier per stage) into [2][FMAX] floats (CfgFill), so a frame reads one LDS float; a clip without a flag skips it.  The last pass
+// already scans all C classes per frame for the log-sum-exp and tracks the first arg-max there: a filler frame's id.  The backpointers,
+// the backtrace and the workspace are wfl_align's own.
 #include "lattice.h"
 #include "wfl_asr.h"
 
@@ -102,14 +109,36 @@ struct AlignLaunchOpt : AlignLaunch {
   float lambda;        // the skip penalty, nats
 };
 
+// wfl_align_filler's layout: Cfg's, and in front of the backtrace window the filler emission of every staged frame -- the row's maximum
+// over all C classes minus the penalty -- [2][FMAX] floats, one half per stage of the ring
+template <int NT, int R>
+struct CfgFill : LdsBase<NT, R, 2 * NT * 8> {
+  static constexpr int WPT = Cfg<NT, R>::WPT;
+  static constexpr int WIN = Cfg<NT, R>::WIN;
+  static constexpr int OFF_FILL = CfgFill::OFF_OWN;
+  static constexpr int OFF_WIN = OFF_FILL + 2 * FMAX * 4;
+  static constexpr int OFF_MISC = OFF_WIN + WIN * 4;
+  static constexpr int LDS = OFF_MISC + 64;
+};
+
+// the kernel arguments of wfl_align_filler: AlignLaunch and the filler tokens
+struct AlignLaunchFill : AlignLaunch {
+  const int* tok_fill;  // [total tokens] 0 | 1
+  float phi;            // the filler penalty, nats per frame
+};
+
 // WIN: the start windows of wfl_align_windowed (lattice.h win_mask); false is wfl_align's kernel, instruction for instruction
 // MIND: the minimum durations of wfl_align_min_duration (lattice.h chain_*); false leaves the two kernels above as they were
 // OPT: the skip arcs of wfl_align_optional (B_k also from G_{k-1}, I_{k-2}, B_{k-2} where token k - 1 is optional); false leaves the
 // kernels above as they were.  Never with MIND.
-template <int NT, int R, bool WIN, bool MIND, bool OPT>
-__global__ __launch_bounds__(NT) void align_kernel(std::conditional_t<OPT, AlignLaunchOpt, AlignLaunch> a) {
+// FILL: the filler tokens of wfl_align_filler (EB = EI = the frame's largest logit minus the penalty where the token is flagged); false
+// leaves the kernels above as they were.  Never with MIND or OPT.
+template <int NT, int R, bool WIN, bool MIND, bool OPT, bool FILL = false>
+__global__ __launch_bounds__(NT) void align_kernel(
+    std::conditional_t<OPT, AlignLaunchOpt, std::conditional_t<FILL, AlignLaunchFill, AlignLaunch>> a) {
   static_assert(!(OPT && MIND), "no skip arcs in the minimum-duration lattice");
-  using K = std::conditional_t<OPT, CfgOpt<NT, R>, Cfg<NT, R>>;
+  static_assert(!(FILL && (MIND || OPT)), "no filler emission in the minimum-duration and skip lattices");
+  using K = std::conditional_t<OPT, CfgOpt<NT, R>, std::conditional_t<FILL, CfgFill<NT, R>, Cfg<NT, R>>>;
   extern __shared__ __attribute__((aligned(16))) char lds[];
   float* ring = (float*)lds;
   int4* alt = (int4*)(lds + K::OFF_ALT);
@@ -130,6 +159,8 @@ __global__ __launch_bounds__(NT) void align_kernel(std::conditional_t<OPT, Align
 
   int g[NGAP];
   int st;
+  unsigned fm = 0;                              // FILL: bit r = "this thread's slot r is a filler"
+  bool anyfill = false;                         // FILL: the clip has a filler (the same in every thread)
   unsigned om = 0;                              // OPT: bit r = "token k - 1 is optional", k this thread's slot r: B_k has skip arcs
   if constexpr (OPT) {
     // the clip's flags, before anything else: a value other than 0 | 1 is status 4; a clip without any flag and with fewer frames than
@@ -155,6 +186,32 @@ __global__ __launch_bounds__(NT) void align_kernel(std::conditional_t<OPT, Align
       for (int r = 0; r < R; ++r) {
         const int k1 = tid * R + r - 1;        // (never below 0 or past the tokens: such a slot has no skip arc)
         if (k1 >= 0 && k1 < N && a.tok_opt[cl.tok_off + k1] != 0) om |= 1u << r;
+      }
+    }
+  } else if constexpr (FILL) {
+    // the clip's flags, as OPT reads its own: a value other than 0 | 1 is status 4 (after wfl_align's 2 and 1); a clip without any flag
+    // never computes a row maximum
+    if (tid == 0) { misc[2] = 0; misc[3] = 0; }
+    __syncthreads();
+    bool any = false, bad = false;
+    for (int k = tid; k < N; k += NT) {
+      const int f = a.tok_fill[cl.tok_off + k];
+      any |= f != 0;
+      bad |= f != 0 && f != 1;
+    }
+    if (any) misc[2] = 1;
+    if (bad) misc[3] = 1;
+    __syncthreads();
+    anyfill = misc[2] != 0;
+    const bool badf = misc[3] != 0;
+    __syncthreads();                            // (lattice_setup writes misc[0]; misc[2] is written again at the end states)
+    st = lattice_setup<NT, R>(cl, C, a.tok_cls, a.gap_cls, alt, misc, g);
+    if (st == 0 && badf) st = 4;
+    if (st == 0) {
+#pragma unroll
+      for (int r = 0; r < R; ++r) {
+        const int k = tid * R + r;
+        if (k < N && a.tok_fill[cl.tok_off + k] != 0) fm |= 1u << r;
       }
     }
   } else {
@@ -188,6 +245,8 @@ __global__ __launch_bounds__(NT) void align_kernel(std::conditional_t<OPT, Align
   // ---- forward pass
   LogitStages<NT, K::PR> stage(Z, a.ldl, T, C, ring);
   const int F = stage.F;
+  float a_phi = 0.f;                           // FILL: the penalty
+  if constexpr (FILL) a_phi = a.phi;
 
   float G[R], B[R], I[R];
 #pragma unroll
@@ -213,6 +272,31 @@ __global__ __launch_bounds__(NT) void align_kernel(std::conditional_t<OPT, Align
   stage.store(0);
   stage.load(1);
   __syncthreads();
+  // FILL: the filler emission of every row of a stage, once per stage and behind a barrier of its own: FG threads share a row (FG the
+  // largest power of two <= NT / F, at most a wave: 8 at C = 141), each takes every FG-th class of it in LDS and log2(FG) exchanges
+  // inside the group end it, so no thread scans a whole row and the frame loop reads one float per frame.  A clip without a filler
+  // (the same in every thread) does none of it.
+  float* fem = nullptr;
+  if constexpr (FILL) fem = (float*)(lds + K::OFF_FILL);
+  int FG = 1;
+  if constexpr (FILL) {
+    FG = 64;
+    while (FG * F > NT) FG >>= 1;               // (F <= FMAX = 32 <= NT / 2: FG >= 2; a group never straddles a wave)
+  }
+  auto fill_stage = [&](int cs) {
+    const int f = tid / FG, sub = tid - f * FG;
+    float mx = NEG;
+    if (f < F) {
+      const float* rw = stage.row(cs, f);
+      for (int q = sub; q < C; q += FG) mx = fmaxf(mx, rw[q]);
+    }
+    for (int o = FG >> 1; o >= 1; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o));
+    if (f < F && sub == 0) fem[(cs & 1) * FMAX + f] = mx - a_phi;
+    __syncthreads();
+  };
+  if constexpr (FILL) {
+    if (anyfill) fill_stage(0);
+  }
 
   // this thread's slots' alternatives, for the whole forward pass.  (512 x 9 with the chain: 4 R registers too many, it would spill --
   // that one configuration reads them from LDS every frame)
@@ -235,9 +319,16 @@ __global__ __launch_bounds__(NT) void align_kernel(std::conditional_t<OPT, Align
       stage.store(c);
       __syncthreads();
       stage.load(c + 1);
+      if constexpr (FILL) {
+        if (anyfill) fill_stage(c);
+      }
     }
     const float* row = stage.row(c, tin);
     const float eg = gap_emission(row, g);
+    float ef = 0.f;                             // FILL: what a filler emits at this frame
+    if constexpr (FILL) {
+      if (anyfill) ef = fem[(c & 1) * FMAX + tin];
+    }
     float2 nb;
     float nG1 = NEG, nB2 = NEG, nI2 = NEG;      // OPT: G of the left thread's last slot, B and I of the slot before it
     if constexpr (OPT) {
@@ -288,6 +379,9 @@ __global__ __launch_bounds__(NT) void align_kernel(std::conditional_t<OPT, Align
       if (k < N) {
         if constexpr (AVR) tok_emission(row, av[r], eb, ei);
         else tok_emission(row, alt[k], eb, ei);
+      }
+      if constexpr (FILL) {
+        if ((fm >> r) & 1u) eb = ei = ef;
       }
       if constexpr (WIN) eb = win_mask(eb, t, wn[r]);
       G[r] = k <= N ? m + eg : NEG;
@@ -453,7 +547,13 @@ __global__ __launch_bounds__(NT) void align_kernel(std::conditional_t<OPT, Align
   for (int t = tid; t < T; t += NT) {
     const float* z = Z + (long)t * a.ldl;
     float m = z[0];
-    for (int q = 1; q < C; ++q) m = fmaxf(m, z[q]);
+    int am = 0;                                 // FILL: the first arg-max class over all C, a filler frame's id
+    if constexpr (FILL) {
+      for (int q = 1; q < C; ++q)
+        if (z[q] > m) { m = z[q]; am = q; }
+    } else {
+      for (int q = 1; q < C; ++q) m = fmaxf(m, z[q]);
+    }
     float se = 0.f;
     for (int q = 0; q < C; ++q) se += __expf(z[q] - m);
     lsum += (double)m + log((double)se);
@@ -468,6 +568,9 @@ __global__ __launch_bounds__(NT) void align_kernel(std::conditional_t<OPT, Align
         if (q == 0 || x > bv) { bv = x; id = col; }
       });
       tk = k;
+      if constexpr (FILL) {
+        if (a.tok_fill[cl.tok_off + k] != 0) id = am;
+      }
     }
     ids[t] = id;
     tokp[t] = tk;
@@ -514,34 +617,43 @@ int64_t wfl_align_optional_workspace_bytes(const int32_t* n_frames_host, const i
   return clips_workspace_bytes(n_frames_host, n_tok_host, n_clips, clip_words_opt);
 }
 
+int64_t wfl_align_filler_workspace_bytes(const int32_t* n_frames_host, const int32_t* n_tok_host, int32_t n_clips) {
+  return clips_workspace_bytes(n_frames_host, n_tok_host, n_clips, clip_words);      // (the same backpointer words: wfl_align's own figure)
+}
+
 }  // extern "C"
 
 namespace {
 
-// wfl_align (WIN false), wfl_align_windowed, wfl_align_min_duration (MIND, with or without windows) and wfl_align_optional (OPT, with or
-// without windows; tok_opt, skipped and skip_penalty are its alone): one host path
-template <bool WIN, bool MIND, bool OPT = false>
+// wfl_align (WIN false), wfl_align_windowed, wfl_align_min_duration (MIND, with or without windows), wfl_align_optional (OPT, with or
+// without windows; tok_opt, skipped and skip_penalty are its alone) and wfl_align_filler (FILL, with or without windows; tok_fill and
+// filler_penalty are its alone): one host path
+template <bool WIN, bool MIND, bool OPT = false, bool FILL = false>
 int align_batch(const char* fn, const float* logits, int64_t ldl, int32_t C, int32_t o_id, const int64_t* frame_off_host,
                 const int32_t* n_frames_host, const int32_t* tok_off_host, const int32_t* n_tok_host, const int32_t* tok_cls,
                 const int32_t* tok_win, const int32_t* tok_min, const int32_t* gap_cls, int32_t n_clips, void* workspace,
                 int64_t workspace_bytes, int32_t* ids, int32_t* tok, float* score, int32_t* status, void* stream,
-                const int32_t* tok_opt = nullptr, float skip_penalty = 0.f, int32_t* skipped = nullptr) {
+                const int32_t* tok_opt = nullptr, float skip_penalty = 0.f, int32_t* skipped = nullptr, const int32_t* tok_fill = nullptr,
+                float filler_penalty = 0.f) {
   const int64_t need = OPT ? wfl_align_optional_workspace_bytes(n_frames_host, n_tok_host, n_clips)
                            : wfl_align_workspace_bytes(n_frames_host, n_tok_host, n_clips);
   bool any_tok = false, any_frame = false;
   int rc = check_clip_args(fn, C, o_id, ldl, frame_off_host, n_frames_host, tok_off_host, n_tok_host, n_clips, need, any_tok, any_frame);
   if (rc) return rc;
   if (OPT && !(skip_penalty >= 0.f && skip_penalty <= 3.0e38f)) return fail(fn, -1, "skip_penalty must be a finite number >= 0");
+  if (FILL && !(filler_penalty >= 0.f && filler_penalty <= 3.0e38f)) return fail(fn, -1, "filler_penalty must be a finite number >= 0");
   if (n_clips == 0) return 0;
-  if (!score || !status || !gap_cls || (any_tok && (!tok_cls || (WIN && !tok_win) || (MIND && !tok_min) || (OPT && (!tok_opt || !skipped)))) ||
+  if (!score || !status || !gap_cls ||
+      (any_tok && (!tok_cls || (WIN && !tok_win) || (MIND && !tok_min) || (OPT && (!tok_opt || !skipped)) || (FILL && !tok_fill))) ||
       (any_frame && (!logits || !ids || !tok)))
     return fail(fn, -1, "null device pointer");
   if ((rc = check_workspace(fn, need, workspace, workspace_bytes))) return rc;
   hipStream_t s = (hipStream_t)stream;
-  std::conditional_t<OPT, AlignLaunchOpt, AlignLaunch> a{};
+  std::conditional_t<OPT, AlignLaunchOpt, std::conditional_t<FILL, AlignLaunchFill, AlignLaunch>> a{};
   a.logits = logits; a.ldl = ldl; a.C = C; a.o_id = o_id; a.tok_cls = tok_cls; a.gap_cls = gap_cls; a.tok_win = tok_win; a.tok_min = tok_min;
   a.bp = (unsigned*)workspace; a.ids = ids; a.tok = tok; a.score = score; a.status = status;
   if constexpr (OPT) { a.tok_opt = tok_opt; a.skipped = skipped; a.lambda = skip_penalty; }
+  if constexpr (FILL) { a.tok_fill = tok_fill; a.phi = filler_penalty; }
   return launch_clips<NCFG>(
       a, n_clips,
       [&](int b, long off, LatClip& c, int& cfg) {
@@ -553,8 +665,8 @@ int align_batch(const char* fn, const float* logits, int64_t ldl, int32_t C, int
       [&](int cfg, const auto& a) {
         return dispatch_cfg(cfg, [&](auto sh) {
           constexpr int NT = decltype(sh)::NT, R = decltype(sh)::R;
-          using K = std::conditional_t<OPT, CfgOpt<NT, R>, Cfg<NT, R>>;
-          return launch_cfg<align_kernel<NT, R, WIN, MIND, OPT>, NT, K::LDS>(fn, a, s);
+          using K = std::conditional_t<OPT, CfgOpt<NT, R>, std::conditional_t<FILL, CfgFill<NT, R>, Cfg<NT, R>>>;
+          return launch_cfg<align_kernel<NT, R, WIN, MIND, OPT, FILL>, NT, K::LDS>(fn, a, s);
         });
       });
 }
@@ -601,6 +713,20 @@ int32_t wfl_align_optional(const float* logits, int64_t ldl, int32_t C, int32_t 
                  : align_batch<false, false, true>(fn, logits, ldl, C, o_id, frame_off_host, n_frames_host, tok_off_host, n_tok_host,
                                                    tok_cls, nullptr, nullptr, gap_cls, n_clips, workspace, workspace_bytes, ids, tok, score,
                                                    status, stream, tok_opt, skip_penalty, skipped);
+}
+
+int32_t wfl_align_filler(const float* logits, int64_t ldl, int32_t C, int32_t o_id, const int64_t* frame_off_host,
+                         const int32_t* n_frames_host, const int32_t* tok_off_host, const int32_t* n_tok_host, const int32_t* tok_cls,
+                         const int32_t* tok_win, const int32_t* gap_cls, int32_t n_clips, const int32_t* tok_fill, float filler_penalty,
+                         void* workspace, int64_t workspace_bytes, int32_t* ids, int32_t* tok, float* score, int32_t* status,
+                         void* stream) {
+  const char* fn = "wfl_align_filler";
+  return tok_win ? align_batch<true, false, false, true>(fn, logits, ldl, C, o_id, frame_off_host, n_frames_host, tok_off_host, n_tok_host,
+                                                         tok_cls, tok_win, nullptr, gap_cls, n_clips, workspace, workspace_bytes, ids, tok,
+                                                         score, status, stream, nullptr, 0.f, nullptr, tok_fill, filler_penalty)
+                 : align_batch<false, false, false, true>(fn, logits, ldl, C, o_id, frame_off_host, n_frames_host, tok_off_host, n_tok_host,
+                                                          tok_cls, nullptr, nullptr, gap_cls, n_clips, workspace, workspace_bytes, ids, tok,
+                                                          score, status, stream, nullptr, 0.f, nullptr, tok_fill, filler_penalty);
 }
 
 }  // extern "C"

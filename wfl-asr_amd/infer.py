@@ -32,7 +32,8 @@ from . import decode as DC
 from . import native_post as npost
 from . import postprocess as pp
 from ._lib import back_to_back
-from .options import ALIGN_MODES, DECODE_MODES, PostOptions, parse_min_duration, resolve, unknown_optional_tokens
+from .options import (ALIGN_MODES, DECODE_MODES, PostOptions, filler_token_collision, parse_min_duration, resolve,
+                      unknown_optional_tokens)
 from .tagger import BIOPhonemeTagger, raise_on_status
 
 frame_duration = pp.FRAME_DURATION
@@ -423,10 +424,12 @@ class Labeler:
     def label_files(self, audio_paths, lang_id=None, confidence_threshold=0.0, verbose=True, align=None, align_scores=None,
                     decode=None, switch_penalty=None, decode_scores=None, phoneme_bigram=None, bigram_weight=None, align_draft=None,
                     draft_tolerance=None, align_edits=None, align_insertions=None, min_duration=None, duration_scores=None,
-                    optional_tokens=None, skip_penalty=None, optional_scores=None, bigram_scores=None):
+                    optional_tokens=None, skip_penalty=None, optional_scores=None, filler_token=None, filler_penalty=None,
+                    bigram_scores=None):
         """-> list (per file) of [(start_s, end_s, phoneme)] after merge + forced alignment; with align_scores, duration_scores,
         decode_scores or bigram_scores, (that list, scores); with align_edits the tuple goes on with one more list, edits, and with
-        align_insertions it ends with one more, insertions; with optional_tokens it ends with the list skipped.
+        align_insertions it ends with one more, insertions; with optional_tokens it ends with the list skipped; with a filler_token
+        it ends with the list fillers.
 
         align: "greedy" -- a `{audio}.txt` transcript is matched onto the freely decoded segments (infer.py:30-60, 312-319);
         "viterbi" -- files with a transcript are aligned by a search over their frame logits on the GPU (align.py: one segment
@@ -505,19 +508,31 @@ class Labeler:
         search, summed over its skip lattice (align.optional_posteriors): scores[i] is an align.FileScore over the kept tokens, and
         the result ends with one more list, optional: per file one align.OptionalTokenScore per optional token of its transcript --
         kept or skipped, the posterior probability that the token is present, and `doubt` where the other decision has more
-        posterior mass (None for a file that was not scored that way)."""
+        posterior mass (None for a file that was not scored that way).
+
+        filler_token (with align "viterbi" only; None: config postprocess.filler_token, else none): a name; a transcript token equal
+        to it is a filler, a token like any other (one contiguous run of at least one frame, in order, gaps possible on both sides)
+        that matches anything: every frame of its run scores the frame's largest logit over all classes minus filler_penalty nats
+        (>= 0; None: config postprocess.filler_penalty, else 1.0 -- a value to start from, not a measured optimum), so a frame goes to
+        the filler instead of a neighbouring token only where that token's class is more than the penalty below the frame's best
+        class (align.viterbi_align_filler).  Runs of adjacent fillers are collapsed into one, with a line.  In the segments a
+        filler's span holds what the file's own free decode found there (align.filler_segments), and fillers[i] is one
+        align.FillerSpan per filler (None for a file that was not aligned that way).  The greedy match a file falls back to gets
+        the transcript without its fillers.  A filler_token that is an output name of the label set is refused by name; align_draft,
+        min_duration, optional_tokens and the scoring options beside it are refused."""
         opts = self.options(align=align, align_scores=align_scores, decode=decode, switch_penalty=switch_penalty,
                             decode_scores=decode_scores, phoneme_bigram=phoneme_bigram, bigram_weight=bigram_weight,
                             bigram_scores=bigram_scores, align_draft=align_draft, draft_tolerance=draft_tolerance,
                             align_edits=align_edits, align_insertions=align_insertions, min_duration=min_duration,
                             duration_scores=duration_scores, optional_tokens=optional_tokens, skip_penalty=skip_penalty,
-                            optional_scores=optional_scores)
+                            optional_scores=optional_scores, filler_token=filler_token, filler_penalty=filler_penalty)
         edits = {} if opts.align_edits else None
         insertions = {} if opts.align_insertions else None
         skipped = {} if opts.optional_tokens is not None else None
         optional = {} if opts.optional_scores else None
+        fillers = {} if opts.filler_token is not None else None
         final, scores = self._label_scored(audio_paths, opts, lang_id, confidence_threshold, verbose, edits=edits,
-                                           insertions=insertions, skipped=skipped, optional=optional)
+                                           insertions=insertions, skipped=skipped, optional=optional, fillers=fillers)
         out = (final, scores) if opts.scored else (final,)
         if opts.align_edits:
             out += ([edits.get(fi) for fi in range(len(audio_paths))],)
@@ -527,16 +542,20 @@ class Labeler:
             out += ([skipped.get(fi) for fi in range(len(audio_paths))],)
         if optional is not None:
             out += ([optional.get(fi) for fi in range(len(audio_paths))],)
+        if fillers is not None:
+            out += ([fillers.get(fi) for fi in range(len(audio_paths))],)
         return out if len(out) > 1 else final
 
     def _label_scored(self, audio_paths, opts, lang_id, confidence_threshold, verbose, moves=None, edits=None, insertions=None,
-                      skipped=None, optional=None):
+                      skipped=None, optional=None, fillers=None):
         """label_files for the resolved options `opts`, always -> (segments, scores): the files are split once into those a transcript is
         Viterbi-aligned to, those the grammar search decodes and those left to the argmax decode, and each subset's results go back to
         its files' places.  moves: a dict that takes {file index: [DraftMove]} for the files aligned inside their draft's windows.
         edits (opts.align_edits): a dict that takes {file index: [TokenEdit]} for the files that were Viterbi-aligned; insertions
         (opts.align_insertions): the same with [PlaceInsertion]; skipped (opts.optional_tokens): the same with [SkippedToken]; optional
-        (opts.optional_scores): the same with [OptionalTokenScore]."""
+        (opts.optional_scores): the same with [OptionalTokenScore]; fillers (opts.filler_token): the same with [FillerSpan]."""
+        if filler_token_collision(opts.filler_token, self._names_for(self._lang_name(lang_id))[1]) is not None:
+            raise ValueError(f"filler_token: {opts.filler_token!r} is an output name of this model's label set")
         unknown = (unknown_optional_tokens(opts.optional_tokens, self._names_for(self._lang_name(lang_id))[1])
                    if opts.optional_tokens not in (None, "*") else [])
         if unknown:
@@ -553,6 +572,12 @@ class Labeler:
             forced = [_read_forced(p, verbose) for p in audio_paths]
             drafts = [_read_draft(p, opts.align_draft, forced[fi]) if opts.align_draft else None for fi, p in enumerate(audio_paths)]
             forced = [tr if dr is None else [s[2] for s in dr] for tr, dr in zip(forced, drafts)]
+            if opts.filler_token is not None:             # runs of adjacent fillers are one filler
+                for fi, tr in enumerate(forced):
+                    if tr:
+                        forced[fi], merged = AL.collapse_fillers(tr, opts.filler_token)
+                        if merged:
+                            print(f"{audio_paths[fi]}: {merged} adjacent filler tokens collapsed")
             with_t = [fi for fi in free if forced[fi] is not None]
             free = [fi for fi in free if forced[fi] is None]
 
@@ -578,7 +603,7 @@ class Labeler:
             for fi, rec in zip(with_t, got):
                 final[fi], scores[fi] = rec.segments, rec.score
                 for into, value in ((moves, rec.moves), (edits, rec.edits), (insertions, rec.insertions), (skipped, rec.skipped),
-                                    (optional, rec.optional)):
+                                    (optional, rec.optional), (fillers, rec.fillers)):
                     if into is not None and value is not None:
                         into[fi] = value
         return final, scores
@@ -872,7 +897,8 @@ class Labeler:
         out = []
         for sel, by_file in self._file_waves(audio_paths, verbose):     # a wave's chunks are forwarded and aligned together
             free, rows = self._forward_with_logits(sel, by_file, lang_id, threshold)
-            greedy, free_segs, plans = self._greedy_and_plans(sel, by_file, free, audio_paths, transcripts, lang_name)
+            greedy, free_segs, plans = self._greedy_and_plans(sel, by_file, free, audio_paths, transcripts, lang_name,
+                                                              opts.filler_token)
             aligned = {}
             run = [fi for fi in sel if fi in plans]          # one ragged search over the files that can be aligned
             if run:
@@ -880,10 +906,11 @@ class Labeler:
                 frames, lg = self._file_rows(rows, by_file, run)
                 chunks = [self._chunk_plan(rows, by_file[fi], fi) for fi in run]
                 flags = _clip_flags([transcripts[fi] for fi in run], opts)
+                fills = _clip_fillers([transcripts[fi] for fi in run], opts)
                 wins, mins = _clip_constraints(paths, frames, chunks, [transcripts[fi] for fi in run],
                                                [drafts[fi] for fi in run], opts, flags)
                 batch = AL.AlignBatch.of(lg, frames, [plans[fi] for fi in run], [AL.gap_classes(self.labels, transcripts[fi]) for fi in run],
-                                         self.labels.index("O"), wins, mins, flags)
+                                         self.labels.index("O"), wins, mins, flags, fills)
                 found = _search(batch, paths, opts)
                 scored = _score(found, opts, sub_pairs)
                 for b, fi in enumerate(run):
@@ -900,9 +927,10 @@ class Labeler:
                     print(f"{audio_paths[fi]}: no transcript insertions (the file was not Viterbi-aligned)")
         return out
 
-    def _greedy_and_plans(self, sel, by_file, free, audio_paths, transcripts, lang_name):
+    def _greedy_and_plans(self, sel, by_file, free, audio_paths, transcripts, lang_name, filler=None):
         """Stage 1, per file of a wave -> (its greedy result: free decode, merge, string match, as _label_files_greedy computes it;
-        its merged free segments; the token alternatives of a file whose transcript can be aligned, one line for one that cannot)."""
+        its merged free segments; the token alternatives of a file whose transcript can be aligned, one line for one that cannot).
+        filler (opts.filler_token): the greedy match gets the transcript without its fillers, a filler the placeholder pair."""
         remap, names = self._names_for(lang_name)
         greedy, free_segs, plans = {}, {}, {}
         for fi in sel:
@@ -912,8 +940,9 @@ class Labeler:
                 clock += len(x) / self.sr
             segs = free_segs[fi] = self._file_segments(parts, lang_name)
             tr = transcripts[fi]
-            greedy[fi] = AL.with_end_pauses(segs, pp.align_phoneme_list(segs, tr), tr)
-            alts, why = AL.token_alternatives(tr, self._table, remap, names, self.labels) if tr else (None, None)
+            spelt = tr if filler is None or not tr else [t for t in tr if t != filler]
+            greedy[fi] = AL.with_end_pauses(segs, pp.align_phoneme_list(segs, spelt), spelt)
+            alts, why = AL.token_alternatives(tr, self._table, remap, names, self.labels, filler=filler) if tr else (None, None)
             if alts is not None:
                 plans[fi] = alts
             elif tr:
@@ -939,8 +968,9 @@ class Labeler:
         if flags is not None:                             # the clip was searched with skip arcs: which tokens the path left out
             k0 = sum(len(a) for a in batch.alts[:b])
             left_out = found.skipped[k0:k0 + len(tr)]
+        fill = batch.fills[b] if batch.fills is not None else None
         segs = AL.path_segments(found.ids[pos:pos + n], tok, *chunk_plan, self._table, batch.alts[b], tr, frame_duration,
-                                skipped=left_out)
+                                fillers=fill, skipped=left_out)
         if flags is not None:
             skipped = AL.skipped_tokens(left_out, segs, tr)
             print(f"{found.paths[b]}: {len(skipped)} of {int(sum(flags))} optional tokens skipped")
@@ -958,9 +988,17 @@ class Labeler:
         elif opts.align_scores or opts.duration_scores or opts.optional_scores:      # (the scoring entry refused the path the search gave it)
             entry, code = scored.refused.get(b, ("wfl_align_posterior", None))
             print(f"{found.paths[b]}: no alignment scores ({entry} status {code})")
-        return ViterbiLabel(AL.with_end_pauses(free_segs, segs, tr), score, moves,
+        lab, spans = segs, None
+        if fill is not None:                              # a filler's span holds what the file's own free decode found there
+            held = {k: AL.filler_segments(g, free_segs) for k, g in enumerate(segs) if fill[k]}
+            lab = [x for k, g in enumerate(segs) for x in (held[k] if k in held else [g])]
+            spans = [AL.FillerSpan(k, float(segs[k][0]), float(segs[k][1]), int((tok == k).sum()), tuple(x[2] for x in held[k]))
+                     for k in sorted(held)]
+            print(f"{found.paths[b]}: {len(spans)} filler{'s' if len(spans) != 1 else ''} in the transcript")
+        return ViterbiLabel(AL.with_end_pauses(free_segs, lab, tr), score, moves,
                             AL.token_edits(scored.edits[b], segs, sub_out) if b in scored.edits else None,
-                            AL.place_insertions(scored.insertions[b], segs, sub_out) if b in scored.insertions else None, skipped, optional)
+                            AL.place_insertions(scored.insertions[b], segs, sub_out) if b in scored.insertions else None, skipped, optional,
+                            spans)
 
 
 class ViterbiLabel(NamedTuple):
@@ -972,6 +1010,7 @@ class ViterbiLabel(NamedTuple):
     insertions: list = None         # [PlaceInsertion] (opts.align_insertions), the same
     skipped: list = None            # [SkippedToken] (opts.optional_tokens), a file aligned with optional tokens
     optional: list = None           # [OptionalTokenScore] (opts.optional_scores), a file scored over the skip lattice
+    fillers: list = None            # [FillerSpan] (opts.filler_token), a file aligned with a filler in its transcript
 
 
 class _Searched(NamedTuple):
@@ -1009,6 +1048,15 @@ def _clip_flags(transcripts, opts):
     return flags if any(f is not None for f in flags) else None
 
 
+def _clip_fillers(transcripts, opts):
+    """Stage 2 -> per clip the filler flags of its tokens (opts.filler_token), None for a clip without any; None: no clip has."""
+    if opts.filler_token is None:
+        return None
+    flags = [AL.filler_flags(tr, opts.filler_token) for tr in transcripts]
+    flags = [f if any(f) else None for f in flags]
+    return flags if any(f is not None for f in flags) else None
+
+
 def _clip_constraints(paths, frames, chunks, transcripts, drafts, opts, flags=None):
     """Stage 2 -> (wins, mins): per clip its draft's start windows and its opts.min_duration in frames, each None where there is
     none or where the host rule align.windows_feasible finds no path (the durations inside the windows), with one line.  flags
@@ -1041,7 +1089,9 @@ def _search(batch, paths, opts) -> _Searched:
     scoring = opts.align_scores or opts.align_edits or opts.align_insertions
     packed = batch.pack(opts.duration_scores) if scoring or (opts.duration_scores and batch.min_frames is not None) else None
     d_skip = None
-    if batch.optional is not None:                        # (the options refuse durations and scores beside optional tokens)
+    if batch.fillers is not None:                         # (the options refuse drafts, durations, optional tokens and scores beside a
+        d_ids, d_tok, d_score, d_st = AL.viterbi_align_filler(*batch.args(), batch.fillers, opts.filler_penalty)     # filler: one call)
+    elif batch.optional is not None:                      # (the options refuse durations and scores beside optional tokens)
         d_ids, d_tok, d_score, d_st, d_skip = AL.viterbi_align_optional(*batch.args(), batch.optional, opts.skip_penalty,
                                                                         windows=batch.windows)
         k0 = np.concatenate([[0], np.cumsum([len(a) for a in batch.alts])]).astype(np.int64)
@@ -1390,6 +1440,16 @@ def _write_optional(lab_path, rows):
         _write_text(optional_path(lab_path), AL.format_optional_tsv(rows), "Optional-token scores")
 
 
+def fillers_path(lab_path):
+    return os.path.splitext(lab_path)[0] + ".fillers.tsv"
+
+
+def _write_fillers(lab_path, rows):
+    """`{stem}.fillers.tsv` beside the .lab of a file that was aligned with a filler in its transcript (None: no file)."""
+    if rows is not None:
+        _write_text(fillers_path(lab_path), AL.format_fillers_tsv(rows), "Filler spans")
+
+
 def _write_score(lab_path, segments, score):
     """The scores file of one labelled file beside its .lab, by the kind of its score (None: no file)."""
     if isinstance(score, DC.FreeScore):
@@ -1402,7 +1462,8 @@ def infer_audio(audio_path, config_path="config.yaml", checkpoint_path="best_mod
                 lang_id=None, sample=False, top_k=0, top_p=0.0, temperature=1.0, confidence_threshold=0.0, align=None,
                 align_scores=None, decode=None, switch_penalty=None, decode_scores=None, phoneme_bigram=None, bigram_weight=None,
                 align_draft=None, draft_tolerance=None, align_edits=None, align_insertions=None, min_duration=None,
-                duration_scores=None, optional_tokens=None, skip_penalty=None, optional_scores=None, bigram_scores=None):
+                duration_scores=None, optional_tokens=None, skip_penalty=None, optional_scores=None, filler_token=None,
+                filler_penalty=None, bigram_scores=None):
     """align: "greedy" | "viterbi" | None (config postprocess.align, else greedy): how a `{audio}.txt` transcript is aligned
     (Labeler.label_files).  align_scores (viterbi only; None: config postprocess.align_scores): also write `{stem}.scores.tsv`
     beside the .lab when the file was Viterbi-aligned (format_scores_tsv).  decode: "argmax" | "viterbi" | None (config
@@ -1426,12 +1487,15 @@ def infer_audio(audio_path, config_path="config.yaml", checkpoint_path="best_mod
     nats each skipped one costs (Labeler.label_files); the .lab lacks the skipped tokens and `{stem}.skipped.tsv` lists them
     (align.format_skipped_tsv).  optional_scores (with optional_tokens only; None: config postprocess.optional_scores): also write
     `{stem}.scores.tsv` for the kept tokens, summed over the skip lattice, and `{stem}.optional.tsv`, one row per optional token of
-    the transcript with the posterior probability that it is present (align.optional_posteriors, align.format_optional_tsv)."""
+    the transcript with the posterior probability that it is present (align.optional_posteriors, align.format_optional_tsv).
+    filler_token / filler_penalty (align viterbi only; None: config postprocess.filler_token / postprocess.filler_penalty): the
+    transcript token that matches anything and the nats it pays per frame (Labeler.label_files); in the .lab its span holds what
+    the free decode found there, and `{stem}.fillers.tsv` lists the spans (align.format_fillers_tsv)."""
     given = dict(align=align, align_scores=align_scores, decode=decode, switch_penalty=switch_penalty, decode_scores=decode_scores,
                  phoneme_bigram=phoneme_bigram, bigram_weight=bigram_weight, bigram_scores=bigram_scores, align_draft=align_draft,
                  draft_tolerance=draft_tolerance, align_edits=align_edits, align_insertions=align_insertions, min_duration=min_duration,
                  duration_scores=duration_scores, optional_tokens=optional_tokens, skip_penalty=skip_penalty,
-                 optional_scores=optional_scores)
+                 optional_scores=optional_scores, filler_token=filler_token, filler_penalty=filler_penalty)
     _refuse_before_load(config_path, **given)
     lab = _labeler(config_path, checkpoint_path, device)
     opts = lab.options(**given)
@@ -1439,8 +1503,9 @@ def infer_audio(audio_path, config_path="config.yaml", checkpoint_path="best_mod
     insertions = {} if opts.align_insertions else None
     skipped = {} if opts.optional_tokens is not None else None
     optional = {} if opts.optional_scores else None
+    fillers = {} if opts.filler_token is not None else None
     (segments,), (score,) = lab._label_scored([audio_path], opts, lang_id, confidence_threshold, True, edits=edits,
-                                              insertions=insertions, skipped=skipped, optional=optional)
+                                              insertions=insertions, skipped=skipped, optional=optional, fillers=fillers)
     if output_lab_path:
         if os.path.abspath(output_lab_path) == os.path.abspath(audio_path):
             # the reference would truncate the input WAV here (infer.py:410-411 + utils.py:77)
@@ -1455,6 +1520,8 @@ def infer_audio(audio_path, config_path="config.yaml", checkpoint_path="best_mod
             _write_skipped(output_lab_path, skipped.get(0))
         if optional is not None:
             _write_optional(output_lab_path, optional.get(0))
+        if fillers is not None:
+            _write_fillers(output_lab_path, fillers.get(0))
     return segments
 
 
@@ -1463,12 +1530,12 @@ def infer_folder(folder_path: str, config_path: str = "config.yaml", checkpoint_
                  temperature=1.0, confidence_threshold=0.0, align=None, align_scores=None, decode=None, switch_penalty=None,
                  decode_scores=None, phoneme_bigram=None, bigram_weight=None, align_draft=None, draft_tolerance=None,
                  align_edits=None, align_insertions=None, min_duration=None, duration_scores=None, optional_tokens=None,
-                 skip_penalty=None, optional_scores=None, bigram_scores=None):
+                 skip_penalty=None, optional_scores=None, filler_token=None, filler_penalty=None, bigram_scores=None):
     given = dict(align=align, align_scores=align_scores, decode=decode, switch_penalty=switch_penalty, decode_scores=decode_scores,
                  phoneme_bigram=phoneme_bigram, bigram_weight=bigram_weight, bigram_scores=bigram_scores, align_draft=align_draft,
                  draft_tolerance=draft_tolerance, align_edits=align_edits, align_insertions=align_insertions, min_duration=min_duration,
                  duration_scores=duration_scores, optional_tokens=optional_tokens, skip_penalty=skip_penalty,
-                 optional_scores=optional_scores)
+                 optional_scores=optional_scores, filler_token=filler_token, filler_penalty=filler_penalty)
     _refuse_before_load(config_path, **given)
     wav_files = sorted(f for f in os.listdir(folder_path) if f.lower().endswith(".wav"))
     os.makedirs(output_dir, exist_ok=True)
@@ -1486,8 +1553,9 @@ def infer_folder(folder_path: str, config_path: str = "config.yaml", checkpoint_
     insertions = {} if opts.align_insertions else None
     skipped = {} if opts.optional_tokens is not None else None
     optional = {} if opts.optional_scores else None
+    fillers = {} if opts.filler_token is not None else None
     all_segments, all_scores = (lab._label_scored(paths, opts, lang_id, confidence_threshold, True, moves, edits, insertions, skipped,
-                                                  optional)
+                                                  optional, fillers)
                                 if paths else ([], []))
     for fi, (wav_file, segments, score) in enumerate(zip(wav_files, all_segments, all_scores)):
         print(f"\nInferencing: {wav_file}")
@@ -1502,6 +1570,8 @@ def infer_folder(folder_path: str, config_path: str = "config.yaml", checkpoint_
             _write_skipped(lab_path, skipped.get(fi))
         if optional is not None:
             _write_optional(lab_path, optional.get(fi))
+        if fillers is not None:
+            _write_fillers(lab_path, fillers.get(fi))
         print("Predicted segments:")
         for start, end, ph in segments:
             print(f"({round(start, 2)}, {round(end, 2)}, {ph})")
@@ -1529,6 +1599,10 @@ def infer_folder(folder_path: str, config_path: str = "config.yaml", checkpoint_
         name = "optional_scores.tsv" if world == 1 else f"optional_scores.rank{rank}.tsv"
         _write_text(os.path.join(output_dir, name), AL.format_folder_optional_tsv([(wav_files[fi], optional[fi]) for fi in sorted(optional)]),
                     "Optional-token scores of the folder")
+    if fillers is not None:
+        name = "filler_spans.tsv" if world == 1 else f"filler_spans.rank{rank}.tsv"
+        _write_text(os.path.join(output_dir, name), AL.format_folder_fillers_tsv([(wav_files[fi], fillers[fi]) for fi in sorted(fillers)]),
+                    "Filler spans of the folder")
     if opts.free_scores:
         name = "decode_scores.tsv" if world == 1 else f"decode_scores.rank{rank}.tsv"
         _write_text(os.path.join(output_dir, name),
@@ -1620,10 +1694,18 @@ def main(argv=None):
                        "the posterior probability that it is present and a doubt flag; for a folder also alignment_scores.tsv and "
                        "optional_scores.tsv, the least confident decision first. Default: config postprocess.optional_scores, else "
                        "off.")
+    @click.option("--filler-token", "filler_token", type=str, default=None,
+                  help="With --align viterbi: a transcript token of this name is a filler -- it stands for a stretch of audio the "
+                       "transcript does not spell and matches anything, every frame at the frame's best class minus "
+                       "--filler-penalty. In the .lab its span holds what the free decode found there; {stem}.fillers.tsv and, for "
+                       "a folder, filler_spans.tsv list the spans. Default: config postprocess.filler_token, else none.")
+    @click.option("--filler-penalty", "filler_penalty", type=float, default=None,
+                  help="With --filler-token: what a filler pays per frame of its run, in nats (>= 0). Default: config "
+                       "postprocess.filler_penalty, else 1.0 (a value to start from, not a measured optimum).")
     def cli(path, checkpoint, config, output, lang_id, sample, top_k, top_p, temperature, device, confidence_threshold, align,
             align_scores, decode, switch_penalty, decode_scores, phoneme_bigram, bigram_weight, bigram_scores, align_draft,
             draft_tolerance, align_edits, align_insertions, min_duration, duration_scores, optional_tokens, skip_penalty,
-            optional_scores):
+            optional_scores, filler_token, filler_penalty):
         if switch_penalty is not None and not switch_penalty >= 0.0:
             raise click.UsageError("--switch-penalty must be >= 0 (nats)")
         if sample:
@@ -1658,7 +1740,8 @@ def main(argv=None):
                            bigram_scores=bigram_scores, align_draft=align_draft, draft_tolerance=draft_tolerance,
                            align_edits=align_edits, align_insertions=align_insertions,
                            min_duration=parse_min_duration(min_duration), duration_scores=duration_scores,
-                           optional_tokens=list(optional_tokens) or None, skip_penalty=skip_penalty, optional_scores=optional_scores)
+                           optional_tokens=list(optional_tokens) or None, skip_penalty=skip_penalty, optional_scores=optional_scores,
+                           filler_token=filler_token, filler_penalty=filler_penalty)
         except ValueError as err:
             raise click.UsageError(str(err))
         output_path = inf_path if output == "." else output
@@ -1681,7 +1764,8 @@ def main(argv=None):
                   duration_scores=opts.duration_scores,
                   # a penalty only beside the tokens it prices (with none, none was given, or resolve had refused it)
                   optional_tokens=opts.optional_tokens, skip_penalty=opts.skip_penalty if opts.optional_tokens is not None else None,
-                  optional_scores=opts.optional_scores)
+                  optional_scores=opts.optional_scores,
+                  filler_token=opts.filler_token, filler_penalty=opts.filler_penalty if opts.filler_token is not None else None)
         if inf_path.is_dir():
             infer_folder(folder_path=str(inf_path), output_dir=str(output_path), **kw)
         else:

@@ -38,6 +38,16 @@ infer_folder (before any model is loaded) and the CLI all call `resolve` and car
   optional_scores off      25. needs align viterbi
                            26. needs optional_tokens (it scores the skip lattice of that search: per optional token the posterior
                                that it is present; without optional tokens align_scores is the option to ask for)
+  filler_token    none    27. NAME: a non-empty string without whitespace; a transcript token equal to it matches anything
+                           28. needs align viterbi (the filler is a token of that search)
+  filler_penalty  1.0      29. when given, a finite number >= 0 (nats per frame of a filler's run; no bool, no NaN).  The default of 1.0
+                               is a value to start from, not a measured optimum
+                           30. when given, needs a filler_token (it is the price per frame of that token)
+                           31. align_draft, min_duration, optional_tokens, align_scores, align_edits, align_insertions,
+                               duration_scores and optional_scores beside a filler_token are refused (FILLER_TOKEN_ERROR): their
+                               lattices have no filler emission, and a score must speak of the lattice its search ran on
+                           (32. with the model known, Labeler.label_files: a filler_token that is an output name of the label set is
+                               refused by name, `filler_token_collision`)
 """
 from __future__ import annotations
 
@@ -64,6 +74,26 @@ MIN_DURATION_SCORES_ERROR = ("align_scores, align_edits and align_insertions can
 OPTIONAL_TOKENS_ERROR = ("optional_tokens cannot be combined with min_duration, align_scores, align_edits, align_insertions or "
                          "duration_scores: their lattices have no skip arcs, and a score must speak of the lattice the search ran on; "
                          "drop postprocess.optional_tokens (--optional) for that run")
+
+
+DEFAULT_FILLER_PENALTY = 1.0      # nats per frame; a value to start from, not a measured optimum
+FILLER_TOKEN_ERROR = ("filler_token cannot be combined with align_draft, min_duration, optional_tokens, align_scores, align_edits, "
+                      "align_insertions, duration_scores or optional_scores: their lattices have no filler emission, and a score must "
+                      "speak of the lattice the search ran on; drop postprocess.filler_token (--filler-token) for that run")
+
+
+def _filler_token(given):
+    """postprocess.filler_token -> None (absent) or the name; anything but a non-empty string without whitespace breaks rule 27."""
+    if given is None:
+        return None
+    if isinstance(given, str) and given and not any(ch.isspace() for ch in given):
+        return given
+    raise ValueError(f"filler_token must be a non-empty string without whitespace, got {given!r}")
+
+
+def filler_token_collision(filler_token, output_names):
+    """Rule 32, for the caller that knows the model: the filler_token when it is an output name of the label set, else None."""
+    return filler_token if filler_token is not None and filler_token in set(output_names) else None
 
 
 def _optional_tokens(given):
@@ -164,7 +194,9 @@ class PostOptions(_SearchOptions):
         duration_scores  False  score every alignment searched under a min_duration, over the minimum-duration lattice
         optional_tokens  None   the tokens a path may leave out: "*", or a sorted tuple of names
         skip_penalty     0.0    nats a path pays per skipped token (also stands for "not given")
-        optional_scores  False  score every alignment searched with optional_tokens, over the skip lattice"""
+        optional_scores  False  score every alignment searched with optional_tokens, over the skip lattice
+        filler_token     None   the transcript token that matches anything
+        filler_penalty   1.0    nats a filler pays per frame of its run (also stands for "not given")"""
     align_draft: Optional[str] = None
     draft_tolerance: float = DEFAULT_DRAFT_TOLERANCE
     align_edits: bool = False
@@ -174,9 +206,12 @@ class PostOptions(_SearchOptions):
     optional_tokens: object = None
     skip_penalty: float = 0.0
     optional_scores: bool = False
+    filler_token: Optional[str] = None
+    filler_penalty: float = DEFAULT_FILLER_PENALTY
 
     def __new__(cls, *args, align_draft=None, draft_tolerance=DEFAULT_DRAFT_TOLERANCE, align_edits=False, align_insertions=False,
-                min_duration=None, duration_scores=False, optional_tokens=None, skip_penalty=0.0, optional_scores=False, **kw):
+                min_duration=None, duration_scores=False, optional_tokens=None, skip_penalty=0.0, optional_scores=False,
+                filler_token=None, filler_penalty=DEFAULT_FILLER_PENALTY, **kw):
         self = super().__new__(cls, *args, **kw)
         object.__setattr__(self, "align_draft", align_draft)
         object.__setattr__(self, "draft_tolerance", draft_tolerance)
@@ -187,14 +222,16 @@ class PostOptions(_SearchOptions):
         object.__setattr__(self, "optional_tokens", optional_tokens)
         object.__setattr__(self, "skip_penalty", skip_penalty)
         object.__setattr__(self, "optional_scores", optional_scores)
+        object.__setattr__(self, "filler_token", filler_token)
+        object.__setattr__(self, "filler_penalty", filler_penalty)
         return self
 
     def __setattr__(self, name, value):
         raise AttributeError(f"PostOptions is read-only: cannot set {name!r}")
 
     _KEYWORD = ("align_draft", "draft_tolerance", "align_edits", "align_insertions", "min_duration", "duration_scores",
-                "optional_tokens", "skip_penalty", "optional_scores")
-    _KEYWORD_DEFAULTS = (None, DEFAULT_DRAFT_TOLERANCE, False, False, None, False, None, 0.0, False)
+                "optional_tokens", "skip_penalty", "optional_scores", "filler_token", "filler_penalty")
+    _KEYWORD_DEFAULTS = (None, DEFAULT_DRAFT_TOLERANCE, False, False, None, False, None, 0.0, False, None, DEFAULT_FILLER_PENALTY)
 
     def _draft(self):
         return self.align_draft, self.draft_tolerance
@@ -209,10 +246,12 @@ class PostOptions(_SearchOptions):
     # the NamedTuple helpers carry the keyword fields as well (the inherited ones know the tuple alone)
     @classmethod
     def _make(cls, iterable, align_draft=None, draft_tolerance=DEFAULT_DRAFT_TOLERANCE, align_edits=False, align_insertions=False,
-              min_duration=None, duration_scores=False, optional_tokens=None, skip_penalty=0.0, optional_scores=False):
+              min_duration=None, duration_scores=False, optional_tokens=None, skip_penalty=0.0, optional_scores=False,
+              filler_token=None, filler_penalty=DEFAULT_FILLER_PENALTY):
         return cls(*iterable, align_draft=align_draft, draft_tolerance=draft_tolerance, align_edits=align_edits,
                    align_insertions=align_insertions, min_duration=min_duration, duration_scores=duration_scores,
-                   optional_tokens=optional_tokens, skip_penalty=skip_penalty, optional_scores=optional_scores)
+                   optional_tokens=optional_tokens, skip_penalty=skip_penalty, optional_scores=optional_scores,
+                   filler_token=filler_token, filler_penalty=filler_penalty)
 
     def _replace(self, **kw):
         later = {k: kw.pop(k, getattr(self, k)) for k in self._KEYWORD}
@@ -249,7 +288,7 @@ def _number_ge0(x):
 def resolve(post, *, align=None, align_scores=None, decode=None, switch_penalty=None, decode_scores=None, phoneme_bigram=None,
             bigram_weight=None, bigram_scores=None, align_draft=None, draft_tolerance=None, align_edits=None,
             align_insertions=None, min_duration=None, duration_scores=None, optional_tokens=None, skip_penalty=None,
-            optional_scores=None) -> PostOptions:
+            optional_scores=None, filler_token=None, filler_penalty=None) -> PostOptions:
     """post: the config's `postprocess` mapping (None: {}).  Per option the argument wins; None leaves it to `post[<option>]`, and a
     key that is absent (or None) to the default.  -> PostOptions, or ValueError for the first broken rule of the module's table."""
     post = post or {}
@@ -344,7 +383,21 @@ def resolve(post, *, align=None, align_scores=None, decode=None, switch_penalty=
     if optional_scores and optional_tokens is None:
         raise ValueError("optional_scores needs optional_tokens (postprocess.optional_tokens): it scores the skip lattice of that "
                          "search; without optional tokens align_scores is the option to ask for")
+    filler_token = _filler_token(pick("filler_token", filler_token))
+    if filler_token is not None and align != "viterbi":
+        raise ValueError("filler_token needs align='viterbi' (postprocess.align: viterbi): the filler is a token of the Viterbi search, "
+                         "the greedy match has none")
+    given = pick("filler_penalty", filler_penalty)
+    filler_penalty = DEFAULT_FILLER_PENALTY if given is None else _number_ge0(given)
+    if filler_penalty is None or filler_penalty == float("inf"):
+        raise ValueError(f"filler_penalty must be a finite number >= 0 (nats per frame of a filler), got {given!r}")
+    if given is not None and filler_token is None:
+        raise ValueError("filler_penalty needs a filler_token (postprocess.filler_token): it is the price per frame of that token")
+    if filler_token is not None and (align_draft or min_duration is not None or optional_tokens is not None or align_scores or align_edits
+                                     or align_insertions or duration_scores or optional_scores):
+        raise ValueError(FILLER_TOKEN_ERROR)
     return PostOptions(align, align_scores, decode, switch_penalty, decode_scores, phoneme_bigram, bigram_weight, bigram_scores,
                        align_draft=align_draft, draft_tolerance=draft_tolerance, align_edits=align_edits,
                        align_insertions=align_insertions, min_duration=min_duration, duration_scores=duration_scores,
-                       optional_tokens=optional_tokens, skip_penalty=skip_penalty, optional_scores=optional_scores)
+                       optional_tokens=optional_tokens, skip_penalty=skip_penalty, optional_scores=optional_scores,
+                       filler_token=filler_token, filler_penalty=filler_penalty)
