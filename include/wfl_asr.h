@@ -514,6 +514,43 @@ int32_t wfl_align_optional_posterior(const float* logits, int64_t ldl, int32_t C
                                      int64_t workspace_bytes, float* logz, float* keep_post, float* tok_post, float* start_mean,
                                      float* start_sd, int32_t* status, void* stream);
 
+/* ---- wfl_align_posterior over the filler lattice of wfl_align_filler (`postprocess.filler_scores`; wfl-asr_amd/align.py
+ * filler_posteriors).  wfl_align_posterior_windowed's arguments (tok_win may be null: no windows) plus tok_fill and filler_penalty =
+ * phi, the table and the penalty the search was given; tok is wfl_align_filler's output.  States, arcs, start and end states and the
+ * recurrences are wfl_align_posterior's, emissions normalised per frame (z - lse) as there; the one difference is that a flagged token
+ * emits
+ *     EB_t(k) = EI_t(k) = (max_c z_t[c] - lse_t) - phi,     the maximum over all C classes, as in the search;
+ * windows mask EB of a filler like any token's.  A path weighs exp(sum_t e_t): every frame of a filler carries -phi.
+ * Outputs (device, float32; the per-token ones rows as tok_cls):
+ *   logz[b], tok_post[k], start_mean[k], start_sd[k]   as wfl_align_posterior_windowed defines them; for a filler tok_post is the mean
+ *                  over Viterbi's run of gamma_t(B_k) + gamma_t(I_k), the posterior that those frames belong to the filler;
+ *   end_mean[k], end_sd[k]   for EVERY token: with last[k] the last frame tok gives token k and
+ *                      omega_t(k) = exp(lse(alpha_t(B_k), alpha_t(I_k)) + leave_k(t+1) - logZ),
+ *                      leave_k(t+1) = lse(beta_{t+1}(G_{k+1}) + EG_{t+1}, beta_{t+1}(B_{k+1}) + EB_{t+1}(k+1))   for t < T - 1
+ *                                     (the B term absent for k = N - 1; EB masked by the window),
+ *                                   = 0 for k = N - 1 and -inf for k < N - 1 at t = T - 1,
+ *                  the posterior that token k's run ends on frame t: mean and standard deviation of t - last[k] under omega_.(k) divided
+ *                  by its own sum, accumulated in double; zeros where the sum is 0.  omega is summed from alpha and leave directly (no
+ *                  difference of gammas), and leave crosses the boundaries of the checkpointed sweep with beta.
+ * status[b]: wfl_align_posterior_windowed's codes: 2 over the cap; 1 T < N, or windows no path meets (logZ = -inf, never a NaN); 4 a bad
+ * class, and also a flag other than 0 | 1; 8 tok is not a path of this lattice.  1 comes before 8: a clip without any path is status 1
+ * whatever tok holds (wfl_align_filler writes tok = -1 for it).  A clip with status != 0 gets zeros in all seven outputs.
+ * Host-side negative returns as wfl_align_posterior_windowed's, and: a null tok_fill, end_mean or end_sd with any token present; a
+ * negative, infinite or NaN filler_penalty; a workspace that is too small.
+ * The row maximum is taken once per frame, in the pass that takes the log-sum-exp, and kept in the workspace: inside the frame loops a
+ * thread reads one value per frame and never scans a logits row.  A clip without a flag skips all of it.
+ * Workspace: wfl_align_posterior's and the filler emission of every frame behind it: per clip, in 4-byte words (0 for T = 0),
+ *     round_up_64(T) + round_up_64(2 nblk) + 3 (nblk + 128) * slots(N) + round_up_64(T),   nblk = ceil(T / 128);
+ * the end moments' sums live in registers.  With every flag 0, logz, tok_post, start_mean and start_sd are wfl_align_posterior's
+ * (wfl_align_posterior_windowed's) up to rounding, for any phi. */
+int64_t wfl_align_filler_posterior_workspace_bytes(const int32_t* n_frames_host, const int32_t* n_tok_host, int32_t n_clips);
+int32_t wfl_align_filler_posterior(const float* logits, int64_t ldl, int32_t C, int32_t o_id, const int64_t* frame_off_host,
+                                   const int32_t* n_frames_host, const int32_t* tok_off_host, const int32_t* n_tok_host,
+                                   const int32_t* tok_cls, const int32_t* tok_win, const int32_t* gap_cls, int32_t n_clips,
+                                   const int32_t* tok_fill, float filler_penalty, const int32_t* tok, void* workspace,
+                                   int64_t workspace_bytes, float* logz, float* tok_post, float* start_mean, float* start_sd,
+                                   float* end_mean, float* end_sd, int32_t* status, void* stream);
+
 /* ---- Single-edit scores of an aligned transcript (`postprocess.align_edits`; wfl-asr_amd/align.py, csrc/align_edits.hip).  No
  * counterpart in the reference.  The arguments are wfl_align_posterior_windowed's without tok; tok_win may be null: the unwindowed
  * lattice.  sub_cls (device, [n_sub][2] int32 = (B class, I class)) is a table of P = n_sub substitutes, 0 <= P <= 512.  With logZ(.)

@@ -1,0 +1,238 @@
+"""CPU (-m "not gpu"): the definition of the posteriors over the filler lattice -- tests/filler_posterior_ref.py against the enumeration
+of every legal path (logz, the per-frame gammas, the end distribution omega), against tests/posterior_ref.py where no token is
+flagged, and the monotony of logz in the penalty -- the option rules of `postprocess.filler_scores`, the .tsv text and the ABI
+declaration.  Exact properties only."""
+import ctypes
+import inspect
+import itertools
+import os
+import re
+
+import numpy as np
+import pytest
+
+import filler_posterior_ref as FP
+import posterior_ref as P
+import viterbi_filler_ref as R
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+F = "<fill>"
+
+
+@pytest.fixture(scope="module")
+def AL():
+    import __graft_entry__  # noqa: F401
+    from wfl_asr_amd import align
+    return align
+
+
+# ------------------------------------------------------------------------------------------------ 1. the definition
+def test_reference_equals_enumeration_with_every_flag_pattern():
+    """Every T <= 6, N <= 3, every flag pattern, phi in {0, 0.5, 2}, with and without a window: logz, gamma of every state at every
+    frame, and omega, which sums to 1 per token (every path leaves every token exactly once)."""
+    rng = np.random.default_rng(17)
+    C, gaps = 9, [0, 7]
+    cases = 0
+    for T, N in itertools.product(range(1, 7), range(0, 4)):
+        alts = [[(1 + 2 * k, 2 + 2 * k)] for k in range(N)]
+        z = (rng.standard_normal((T, C)) * 2).astype(np.float32)
+        for fill in itertools.product((0, 1), repeat=N):
+            for phi in (0.0, 0.5, 2.0):
+                for win in ((None, [(1, 3)] * N) if N else (None,)):
+                    r = FP.forward_backward(z, alts, gaps, fill, phi, windows=win, full=True)
+                    e = FP.enumerate_paths(z, alts, gaps, fill, phi, win)
+                    if e is None:
+                        assert r is None
+                        continue
+                    cases += 1
+                    assert r is not None and abs(r["logz"] - e["logz"]) <= 1e-12
+                    g = np.zeros((T, 3 * N + 1))
+                    g[:, 0::3], g[:, 1::3], g[:, 2::3] = r["gamma_g"], r["gamma_b"], r["gamma_i"]
+                    assert np.abs(g - e["gamma"]).max() <= 1e-12 and np.abs(g.sum(1) - 1).max() <= 1e-12
+                    if N:
+                        assert np.abs(r["omega"] - e["omega"]).max() <= 1e-12
+                        assert np.abs(e["omega"].sum(0) - 1).max() <= 1e-12 and np.abs(r["omega"].sum(0) - 1).max() <= 1e-12
+    assert cases > 300
+
+
+def test_the_float32_restatement_is_the_same_code():
+    rng = np.random.default_rng(3)
+    alts = [[(1 + 2 * k, 2 + 2 * k)] for k in range(5)]
+    z, st = R.plant(40, 5, 12, alts, [0, 11], rng, fill=[0, 1, 0, 0, 1], margin=2.0)
+    _, tok = R.outputs(st, z, alts, 0, [0, 1, 0, 0, 1])
+    a = FP.forward_backward(z, alts, [0, 11], [0, 1, 0, 0, 1], 0.7, tok=tok)
+    b = FP.forward_backward(z, alts, [0, 11], [0, 1, 0, 0, 1], 0.7, tok=tok, dtype=np.float32)
+    for k in FP.OUTPUTS:
+        assert np.abs(np.asarray(a[k]) - np.asarray(b[k])).max() < 1e-3, k
+    assert a["end_mean"].shape == (5,) and (a["end_sd"] >= 0).all()
+
+
+def test_with_no_flag_it_is_posterior_refs():
+    rng = np.random.default_rng(5)
+    for T, N in ((30, 4), (12, 12), (50, 1), (9, 0)):
+        alts = [[(1 + 2 * k, 2 + 2 * k)] for k in range(N)]
+        z = P.planted_logits(T, N, 2 * N + 3, alts, [0, 2 * N + 2], rng, 2.0)
+        st, _ = R.viterbi(z, alts, [0, 2 * N + 2])
+        _, tok = R.outputs(st, z, alts, 0)
+        mine = FP.forward_backward(z, alts, [0, 2 * N + 2], None, 1.7, tok=tok)
+        theirs = P.forward_backward(z, alts, [0, 2 * N + 2], tok=tok)
+        for k in ("logz", "tok_post", "start_mean", "start_sd"):
+            assert np.abs(np.atleast_1d(mine[k]) - np.atleast_1d(theirs[k])).max(initial=0.0) <= 1e-12, (T, N, k)
+
+
+def test_logz_does_not_increase_with_the_penalty():
+    rng = np.random.default_rng(6)
+    alts = [[(1 + 2 * k, 2 + 2 * k)] for k in range(4)]
+    z = rng.standard_normal((20, 11)).astype(np.float32)
+    lz = [FP.forward_backward(z, alts, [0, 10], [0, 1, 0, 1], phi)["logz"] for phi in (0.0, 0.5, 2.0, 50.0)]
+    assert all(a > b for a, b in zip(lz, lz[1:]))
+    flat = [FP.forward_backward(z, alts, [0, 10], [0, 0, 0, 0], phi)["logz"] for phi in (0.0, 2.0)]
+    assert flat[0] == flat[1]                               # without a filler the penalty is never read
+
+
+# ------------------------------------------------------------------------------------------------ 2. the option
+def test_option_rules_33_and_34():
+    from wfl_asr_amd.options import FILLER_SCORES_ERROR, FILLER_TOKEN_ERROR, PostOptions, resolve
+    import wfl_asr_amd.options as OPT
+    assert resolve({}).filler_scores is False and resolve({"align": "viterbi", "filler_token": F}).filler_scores is False
+    a = resolve({"align": "viterbi", "filler_token": F, "filler_scores": True})
+    assert a.filler_scores is True and a.scored and a.filler_token == F
+    assert resolve({"align": "viterbi", "filler_token": F}, filler_scores=True) == a
+    assert resolve({"align": "viterbi", "filler_token": F, "filler_scores": True}, filler_scores=False).filler_scores is False
+    for bad in (1, 0, "yes", "true", 1.0, [True]):                                                             # rule 33
+        with pytest.raises(ValueError, match="filler_scores must be true or false"):
+            resolve({"align": "viterbi", "filler_token": F}, filler_scores=bad)
+    with pytest.raises(ValueError) as e:                                                                        # rule 34
+        resolve({"align": "viterbi"}, filler_scores=True)
+    assert str(e.value) == FILLER_SCORES_ERROR and "align_scores is the option to ask for" in FILLER_SCORES_ERROR
+    with pytest.raises(ValueError, match="filler_scores needs a filler_token"):
+        resolve({}, filler_scores=True)
+    # rule 31 stays: align_scores beside a filler_token is refused, with filler_scores or without, and comes before 33 and 34
+    for extra in ({}, {"filler_scores": True}, {"filler_scores": "yes"}):
+        with pytest.raises(ValueError) as e:
+            resolve({"align": "viterbi", "filler_token": F, "align_scores": True, **extra})
+        assert str(e.value) == FILLER_TOKEN_ERROR
+    with pytest.raises(ValueError, match="filler_penalty needs a filler_token"):                                # 30 before 34
+        resolve({"align": "viterbi"}, filler_penalty=1.0, filler_scores=True)
+    with pytest.raises(ValueError, match="filler_scores must be"):                                              # 33 before 34
+        resolve({"align": "viterbi"}, filler_scores="yes")
+    doc = " ".join(OPT.__doc__.split())
+    assert "33." in doc and "34." in doc and "filler_scores" in doc
+    # the record
+    plain = resolve({"align": "viterbi", "filler_token": F})
+    assert "filler_scores" in PostOptions._KEYWORD and a != plain and hash(a) != hash(plain)
+    assert "filler_scores=True" in repr(a) and "filler_scores=False" in repr(plain)
+    assert a._replace(filler_scores=False) == plain and a._asdict()["filler_scores"] is True
+    assert PostOptions._make(tuple(a), filler_scores=True).filler_scores is True
+    with pytest.raises(AttributeError):
+        a.filler_scores = False
+
+
+def test_the_option_is_refused_before_any_model_is_loaded(monkeypatch, tmp_path):
+    import __graft_entry__  # noqa: F401
+    from wfl_asr_amd import infer as I
+
+    def no_load(*a, **k):
+        raise AssertionError("a model was loaded before the options were refused")
+    for f in (I.infer_audio, I.infer_folder, I.Labeler.label_files):
+        assert inspect.signature(f).parameters["filler_scores"].default is None
+    monkeypatch.setattr(I, "_labeler", no_load)
+    monkeypatch.setattr(I, "Labeler", no_load)
+    with pytest.raises(ValueError, match="filler_scores needs a filler_token"):
+        I.infer_audio("x.wav", align="viterbi", filler_scores=True)
+    cfg = tmp_path / "config.yaml"
+    cfg.write_text("postprocess:\n  align: viterbi\n  filler_scores: true\n")
+    with pytest.raises(ValueError, match="filler_scores needs a filler_token"):                        # from the config file
+        I.infer_folder("some_folder", config_path=str(cfg))
+    seen = {}
+
+    def record(*a, **k):
+        seen.update(k)
+        raise SystemExit(0)
+    monkeypatch.setattr(I.torch.cuda, "is_available", lambda: True)     # (the CLI turns away a machine without a device first)
+    monkeypatch.setattr(I, "infer_audio", record)
+    monkeypatch.setattr(I, "infer_folder", record)
+    wav, ckpt = tmp_path / "x.wav", tmp_path / "m.pt"
+    wav.write_bytes(b"")
+    ckpt.write_bytes(b"")
+    cfg.write_text("postprocess:\n  align: viterbi\n")
+    base = [str(wav), "-ckpt", str(ckpt), "-c", str(cfg)]
+    for extra in (["--filler-scores"], ["--filler-scores", "--align-scores"], ["--filler-token", F, "--filler-scores", "--align-scores"]):
+        with pytest.raises(SystemExit) as e:
+            I.main(base + extra)
+        assert e.value.code == 2, extra
+    with pytest.raises(SystemExit) as e:
+        I.main(base + ["--filler-token", F, "--filler-scores"])
+    assert e.value.code == 0 and seen["filler_scores"] is True and seen["filler_token"] == F
+    seen.clear()
+    with pytest.raises(SystemExit) as e:
+        I.main(base + ["--filler-token", F])
+    assert e.value.code == 0 and seen["filler_scores"] is False
+
+
+# ------------------------------------------------------------------------------------------------ 3. the .tsv text
+def test_filler_score_rows_and_their_text(AL):
+    spans = [AL.FillerSpan(2, 0.5, 0.9, 20, ("a", "b")), AL.FillerSpan(5, 1.5, 1.7, 10, ())]
+    tp = [1, 1, 0.75, 1, 1, 0.25, 1]
+    rows = AL.filler_scores(spans, tp, [0, 0, -1.5, 0, 0, 2, 0], [0, 0, 0.5, 0, 0, 1, 0], [0, 0, 3, 0, 0, -1, 0], [0, 0, 2, 0, 0, 0.25, 0], 0.02)
+    assert rows == [AL.FillerScore(2, 0.5, 0.9, 20, 0.75, -0.03, 0.01, 0.06, 0.04), AL.FillerScore(5, 1.5, 1.7, 10, 0.25, 0.04, 0.02, -0.02, 0.005)]
+    text = AL.format_filler_scores_tsv(rows)
+    assert text.splitlines() == [
+        "index\tstart_s\tend_s\tframes\tposterior\tstart_shift_s\tstart_sd_s\tend_shift_s\tend_sd_s",
+        "2\t0.5000000\t0.9000000\t20\t0.750000\t-0.0300000\t0.0100000\t0.0600000\t0.0400000",
+        "5\t1.5000000\t1.7000000\t10\t0.250000\t0.0400000\t0.0200000\t-0.0200000\t0.0050000"] and text.endswith("\n")
+    assert AL.format_filler_scores_tsv([]) == AL.FILLER_SCORES_HEADER + "\n"
+    folder = AL.format_folder_filler_scores_tsv([("a.wav", rows), ("b.wav", []), ("c.wav", [rows[0]._replace(posterior=0.25)])])
+    lines = folder.splitlines()
+    assert lines[0] == "file\t" + AL.FILLER_SCORES_HEADER and len(lines) == 4
+    assert [ln.split("\t")[0] for ln in lines[1:]] == ["a.wav", "c.wav", "a.wav"]        # the lowest occupancy first, ties in the files' order
+    assert [ln.split("\t")[5] for ln in lines[1:]] == ["0.250000", "0.250000", "0.750000"]
+    assert "flag" not in folder and "doubt" not in folder
+    with pytest.raises(ValueError):
+        AL.filler_scores(spans, tp, [0] * 7, [0] * 7, [0] * 6, [0] * 7, 0.02)
+    with pytest.raises(ValueError):
+        AL.filler_scores([AL.FillerSpan(9, 0, 1, 3, ())], tp, [0] * 7, [0] * 7, [0] * 7, [0] * 7, 0.02)
+
+
+# ------------------------------------------------------------------------------------------------ 4. the ABI
+def test_the_abi_declaration(AL):
+    from wfl_asr_amd import _lib
+    src = open(os.path.join(ROOT, "include", "wfl_asr.h")).read()
+    code = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
+    for name in ("wfl_align_filler_posterior", "wfl_align_filler_posterior_workspace_bytes"):
+        assert re.search(r"\b" + name + r"\s*\(", code) and name in _lib.SIGNATURES
+    proto = re.search(r"int32_t\s+wfl_align_filler_posterior\s*\((.*?)\)\s*;", code, flags=re.S).group(1)
+    params = [p.strip() for p in proto.split(",")]
+    res, args = _lib.SIGNATURES["wfl_align_filler_posterior"]
+    assert res is ctypes.c_int32 and len(args) == len(params) == 25
+    assert [p.split()[-1].lstrip("*") for p in params][12:25] == ["tok_fill", "filler_penalty", "tok", "workspace", "workspace_bytes", "logz",
+                                                                  "tok_post", "start_mean", "start_sd", "end_mean", "end_sd", "status", "stream"]
+    for p, a in zip(params, args):
+        want = ctypes.c_void_p if "*" in p else {"int64_t": ctypes.c_int64, "int32_t": ctypes.c_int32, "float": ctypes.c_float}[p.split()[-2]]
+        assert a is want, (p, a)
+    assert _lib.SIGNATURES["wfl_align_filler_posterior_workspace_bytes"] == _lib.SIGNATURES["wfl_align_posterior_workspace_bytes"]
+    lib = _lib.load()
+    assert hasattr(lib, "wfl_align_filler_posterior") and hasattr(lib, "wfl_align_filler_posterior_workspace_bytes")
+    # the workspace: wfl_align_posterior's and one float per frame, rounded up to 64, per clip with frames
+    T, N = [200, 50, 700, 0, 1], [100, 20, 600, 5, 1]
+    extra = sum((t + 63) // 64 * 64 * 4 for t in T)
+    assert AL.filler_posterior_workspace_bytes(T, N) == AL.posterior_workspace_bytes(T, N) + extra
+    assert AL.filler_posterior_workspace_bytes([], []) == 0
+    sig = list(inspect.signature(AL.filler_posteriors).parameters)
+    assert sig == ["logits", "n_frames", "token_classes", "gap_classes", "o_id", "fillers", "tok", "filler_penalty", "frame_offsets", "stream",
+                   "packed", "windows"]
+    assert inspect.signature(AL.filler_posteriors).parameters["filler_penalty"].default == 1.0
+    # the entry's host-side checks, without a GPU: nothing is launched for a refused call
+    i32 = lambda *v: np.array(v, np.int32)                   # noqa: E731
+    F0, T1, K0, N1 = np.array([0], np.int64), i32(10), i32(0), i32(3)
+    hp = _lib.host_ptr
+    one = ctypes.c_void_p(64)                                # a pointer that is never dereferenced on the host
+    def call(phi=1.0, fill=one, end_mean=one, ws_bytes=None):
+        need = AL.filler_posterior_workspace_bytes([10], [3])
+        return lib.wfl_align_filler_posterior(one, 20, 20, 0, hp(F0), hp(T1), hp(K0), hp(N1), one, None, one, 1, fill, ctypes.c_float(phi), one,
+                                              one, need if ws_bytes is None else ws_bytes, one, one, one, one, end_mean, one, one, None)
+    assert call(fill=None) == -1 and b"null device pointer" in lib.wfl_last_error()
+    assert call(end_mean=None) == -1
+    assert call(phi=float("nan")) == -1 and b"filler_penalty" in lib.wfl_last_error()
+    assert call(phi=-1.0) == -1 and call(phi=float("inf")) == -1
+    assert call(ws_bytes=AL.filler_posterior_workspace_bytes([10], [3]) - 1) == -1 and b"workspace too small" in lib.wfl_last_error()

@@ -89,6 +89,9 @@ SIGNATURES = {
     "wfl_align_optional_posterior_workspace_bytes": (_L, [_P, _P, _I]),
     "wfl_align_optional_posterior": (_I, [_P, _L, _I, _I, _P, _P, _P, _P, _P, _P, _P, _I, _P, _F, _P, _P, _L, _P, _P, _P, _P, _P, _P,
                                           _P]),
+    "wfl_align_filler_posterior_workspace_bytes": (_L, [_P, _P, _I]),
+    "wfl_align_filler_posterior": (_I, [_P, _L, _I, _I, _P, _P, _P, _P, _P, _P, _P, _I, _P, _F, _P, _P, _L, _P, _P, _P, _P, _P, _P,
+                                        _P, _P]),
     "wfl_align_edits_workspace_bytes": (_L, [_P, _P, _I]),
     "wfl_align_edits": (_I, [_P, _L, _I, _I, _P, _P, _P, _P, _P, _P, _P, _I, _P, _I, _P, _L, _P, _P, _P, _P]),
     "wfl_align_insertions_workspace_bytes": (_L, [_P, _P, _I]),

@@ -99,6 +99,10 @@ def optional_posterior_workspace_bytes(n_frames, n_tokens) -> int:
     return _workspace_bytes("wfl_align_optional_posterior_workspace_bytes", n_frames, n_tokens)
 
 
+def filler_posterior_workspace_bytes(n_frames, n_tokens) -> int:
+    return _workspace_bytes("wfl_align_filler_posterior_workspace_bytes", n_frames, n_tokens)
+
+
 def posterior_workspace_bytes(n_frames, n_tokens) -> int:
     return _workspace_bytes("wfl_align_posterior_workspace_bytes", n_frames, n_tokens)
 
@@ -361,6 +365,7 @@ _ENTRIES = {
     "wfl_align_edits": ("wfl_align_edits", True, False), "wfl_align_insertions": ("wfl_align_insertions", True, False),
     "wfl_align_optional_posterior": ("wfl_align_optional_posterior", True, False),
     "wfl_align_filler": ("wfl_align_filler", True, False),
+    "wfl_align_filler_posterior": ("wfl_align_filler_posterior", True, False),
 }
 
 
@@ -499,6 +504,39 @@ def viterbi_align_filler(logits, n_frames, token_classes, gap_classes, o_id, fil
     status = torch.empty(max(nb, 1), dtype=torch.int32, device=dev)
     _call("wfl_align_filler", logits, o_id, packed, (d_fill, phi), (ids, tok, score, status), stream, temporaries=(d_fill,))
     return ids, tok, score[:nb], status[:nb]
+
+
+def filler_posteriors(logits, n_frames, token_classes, gap_classes, o_id, fillers, tok, filler_penalty=1.0, frame_offsets=None,
+                      stream=None, packed=None, windows=None):
+    """alignment_posteriors over the filler lattice of viterbi_align_filler, for the same ragged batch of clips (same arguments, the
+    same `fillers` and `filler_penalty`), given its `tok` (wfl_align_filler_posterior).  A flagged token emits, in every frame, the
+    frame's largest log-probability over all classes minus `filler_penalty`; everything else is alignment_posteriors' lattice.
+
+    fillers  as viterbi_align_filler's: per clip a list of bools per token (or None), or upload_filler's tensor
+    windows  as viterbi_align_filler's; with `packed` -- the PackedClips the search ran on -- the ones packed there.  A batch packed
+             with `min_frames` is refused
+    -> (logz, tok_post, start_mean, start_sd, end_mean, end_sd, status): alignment_posteriors' tensors and, per token, end_mean /
+    end_sd [tokens] float32: mean (relative to the last frame Viterbi gave the token) and standard deviation of the frame the
+    token's run ends on, in frames.  For a filler tok_post is the posterior that the frames of its span belong to the filler.
+    STATUS_BAD_CLASS also for a flag other than 0 | 1; a clip with status != 0 gets zeros."""
+    if packed is None:
+        packed = pack_clips(logits, n_frames, token_classes, gap_classes, frame_offsets, windows)
+    if packed.d_min is not None:
+        raise ValueError("filler_posteriors has no minimum durations: this batch was packed with min_frames")
+    phi = float(filler_penalty)
+    if not (0.0 <= phi < float("inf")):
+        raise ValueError("filler_penalty must be a number of nats >= 0")
+    _check_tok(tok, logits)
+    nb, ntok, dev = packed.nb, int(packed.N.sum()), logits.device
+    d_fill = fillers if isinstance(fillers, torch.Tensor) else upload_filler(fillers, packed.N, dev)
+    if d_fill.device != dev or d_fill.dtype != torch.int32 or d_fill.dim() != 1 or d_fill.stride(0) != 1 or d_fill.shape[0] != max(ntok, 1):
+        raise ValueError("uploaded filler flags must be upload_filler's [tokens] int32 tensor for this batch")
+    logz = torch.empty(max(nb, 1), dtype=torch.float32, device=dev)
+    per_tok = torch.empty((5, max(ntok, 1)), dtype=torch.float32, device=dev)
+    status = torch.empty(max(nb, 1), dtype=torch.int32, device=dev)
+    _call("wfl_align_filler_posterior", logits, o_id, packed, (d_fill, phi, tok),
+          (logz, per_tok[0], per_tok[1], per_tok[2], per_tok[3], per_tok[4], status), stream, temporaries=(d_fill,))
+    return (logz[:nb], per_tok[0, :ntok], per_tok[1, :ntok], per_tok[2, :ntok], per_tok[3, :ntok], per_tok[4, :ntok], status[:nb])
 
 
 def _optional_call_args(optional, skip_penalty, packed, logits, what):
@@ -1242,4 +1280,55 @@ def format_folder_fillers_tsv(per_file) -> str:
     """filler_spans.tsv: [(file name, [FillerSpan])] -> every filler of every file, the file's name in front of the span's own
     columns, in the files' and the tokens' order."""
     lines = ["file\t" + FILLERS_HEADER] + ["\t".join([name] + _filler_cells(r)) for name, rows in per_file for r in rows]
+    return "".join(line + "\n" for line in lines)
+
+
+# ------------------------------------------------------------------------------------------------------- filler tokens' scores
+class FillerScore(NamedTuple):
+    index: int              # the filler's index in the transcript (after collapse_fillers)
+    start_s: float          # its span on the .lab clock
+    end_s: float
+    frames: int             # the frames of its run
+    posterior: float        # filler_posteriors' tok_post: the posterior that the span's frames belong to the filler
+    start_shift_s: float    # posterior mean of the span's start minus Viterbi's, seconds on the .lab clock
+    start_sd_s: float       # posterior standard deviation of the start, seconds
+    end_shift_s: float      # the same for the span's end (filler_posteriors' end_mean / end_sd)
+    end_sd_s: float
+
+
+def filler_scores(spans, tok_post, start_mean, start_sd, end_mean, end_sd, frame_duration):
+    """One file's FillerScore rows, one per FillerSpan in order, from filler_posteriors' outputs for the file (host values, one per
+    transcript token).  frame_duration: the .lab clock that turns the frame figures into seconds."""
+    cols = [np.asarray(a, np.float64).reshape(-1) for a in (tok_post, start_mean, start_sd, end_mean, end_sd)]
+    if len({len(c) for c in cols}) != 1:
+        raise ValueError("one posterior and one pair of start and end moments per transcript token")
+    rows = []
+    for sp in spans:
+        if not 0 <= sp.index < len(cols[0]):
+            raise ValueError("a filler span's index lies outside the transcript")
+        p, smu, ssd, emu, esd = (float(c[sp.index]) for c in cols)
+        rows.append(FillerScore(sp.index, sp.start_s, sp.end_s, sp.frames, p, smu * frame_duration, ssd * frame_duration,
+                                emu * frame_duration, esd * frame_duration))
+    return rows
+
+
+FILLER_SCORES_HEADER = "index\tstart_s\tend_s\tframes\tposterior\tstart_shift_s\tstart_sd_s\tend_shift_s\tend_sd_s"
+
+
+def _filler_score_cells(r: FillerScore):
+    return [str(r.index), f"{r.start_s:.7f}", f"{r.end_s:.7f}", str(r.frames), f"{r.posterior:.6f}", f"{r.start_shift_s:.7f}",
+            f"{r.start_sd_s:.7f}", f"{r.end_shift_s:.7f}", f"{r.end_sd_s:.7f}"]
+
+
+def format_filler_scores_tsv(rows) -> str:
+    """{stem}.filler_scores.tsv: one line per filler of the transcript, in the transcript's order."""
+    return "".join("\t".join(c) + "\n" for c in [FILLER_SCORES_HEADER.split("\t")] + [_filler_score_cells(r) for r in rows])
+
+
+def format_folder_filler_scores_tsv(per_file) -> str:
+    """filler_scores.tsv: [(file name, [FillerScore])] -> every filler of every file, the file's name in front of the filler's own
+    columns, the lowest occupancy posterior first; ties in the files' and the tokens' order.  No flag, no threshold: the order is
+    the list to check."""
+    flat = sorted(((name, r) for name, rows in per_file for r in rows), key=lambda nr: nr[1].posterior)
+    lines = ["file\t" + FILLER_SCORES_HEADER] + ["\t".join([name] + _filler_score_cells(r)) for name, r in flat]
     return "".join(line + "\n" for line in lines)

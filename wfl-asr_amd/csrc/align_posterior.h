@@ -49,6 +49,17 @@
 // present: keep_post.  A tok that misses a token that is not optional, or two neighbours, is status 8 -- after sweep 1, as with
 // durations: a clip without any path is status 1 first.
 //
+// wfl_align_filler_posterior is the kernel instantiated with FILL (with and without WIN, never with MIND or OPT): the sums over the
+// lattice of wfl_align_filler.  States and arcs are wfl_align_posterior's; a flagged token emits EB = EI = (max_c z_t[c] - lse_t) - phi.
+// frame_lse, which takes every row's maximum anyway, keeps that value per frame in the clip's workspace (fem[T], behind the block
+// buffer); it travels through the stage rings beside the log-sum-exp (fring), so a frame of either sweep reads one float and never
+// scans a row.  A clip without a flag (the same in every thread) computes, stages and reads none of it.  New here as well: the moments
+// of every token's END.  omega_t(k) = exp(lse(alpha_t(B_k), alpha_t(I_k)) + leave_k(t+1) - logZ), leave_k(t+1) what follows the token
+// at frame t + 1 -- beta_frame hands it out (two of the three terms of beta_t(B_k)) on the scale of beta_t, and it is CARRIED into the
+// next iteration of the backward loop, where alpha_t is in hand: so it crosses the boundary of a recomputed block like beta itself
+// (alpha of frame t_lo - 1 is not in the block that produced leave(t_lo)).  At T - 1 leave is 0 for token N - 1 and -inf elsewhere:
+// beta's own start values.  The last frame of every Viterbi run comes through first[] as with durations.
+//
 // The per-frame log-sum-exp of the logits is computed once (double, expf), stored in fp32 and subtracted from the gathered logits;
 // what the fp32 rounding of it loses is summed in double and given back to logZ (it is common to every path).
 //
@@ -56,7 +67,8 @@
 // wfl_align_posterior_windowed from it, csrc/align_min_duration_posterior.hip the kernels with the minimum-duration chain (MIND) -- a
 // translation unit of its own because those are compiled without the SLP vectoriser (build.py), which must not reach the others.
 // csrc/align_optional_posterior.hip instantiates the kernels with the skip arcs (OPT), so that the other objects keep their code.
-// Everything here is in an unnamed namespace: each of the three files has its own copy, and instantiates only its own kernels.
+// csrc/align_filler_posterior.hip instantiates the kernels with the filler emission (FILL), for the same reason.
+// Everything here is in an unnamed namespace: each of the files has its own copy, and instantiates only its own kernels.
 #pragma once
 #include "lattice_sums.h"
 #include "wfl_asr.h"
@@ -111,8 +123,17 @@ struct PostLaunchOpt : PostLaunch {
   float lambda;        // the skip penalty, nats
 };
 
+// the kernel arguments of wfl_align_filler_posterior: PostLaunch and, behind it, the filler tokens and the end moments
+struct PostLaunchFill : PostLaunch {
+  const int* tok_fill;  // [total tokens] 0 | 1
+  float* end_mean;      // [total tokens]
+  float* end_sd;        // [total tokens]
+  float phi;            // the filler penalty, nats per frame
+};
+
 // OPT: the exchanges of the skip lattice, [2][XF_OPT][NT] and [2][XB_OPT][NT] floats instead of [2][NT] float2 each
-template <int NT, int R, bool OPT = false>
+// FILL: one side ring more, the staged rows' filler emission, behind everything else
+template <int NT, int R, bool OPT = false, bool FILL = false>
 struct PCfg : LdsBase<NT, R, NT * R * 4 + (OPT ? 2 * (XF_OPT + XB_OPT) * NT * 4 : 2 * 2 * NT * 8)> {   // its own between alt and wmax: first[] and the two neighbour exchanges
   static constexpr long S = (long)NT * R * 3;            // floats of one frame's alpha (and of one checkpoint)
   static constexpr long SM = (long)NT * R * (3 + CHAIN); // floats of one checkpoint with the minimum-duration chain
@@ -123,7 +144,8 @@ struct PCfg : LdsBase<NT, R, NT * R * 4 + (OPT ? 2 * (XF_OPT + XB_OPT) * NT * 4 
   static constexpr int OFF_LRING = OFF_OFFA + POST_W * 8;          // staged rows' log-sum-exp
   static constexpr int OFF_TRING = OFF_LRING + 2 * FMAX * 4;       // staged rows' Viterbi token
   static constexpr int OFF_MISC = OFF_TRING + 2 * FMAX * 4;
-  static constexpr int LDS = OFF_MISC + 64;
+  static constexpr int OFF_FRING = OFF_MISC + 64;                  // FILL: staged rows' filler emission
+  static constexpr int LDS = OFF_FRING + (FILL ? 2 * FMAX * 4 : 0);
 };
 
 // WIN: the start windows of wfl_align_posterior_windowed (lattice.h win_mask); false is wfl_align_posterior's kernel
@@ -132,10 +154,14 @@ struct PCfg : LdsBase<NT, R, NT * R * 4 + (OPT ? 2 * (XF_OPT + XB_OPT) * NT * 4 
 // OPT: the skip arcs of wfl_align_optional_posterior (lattice_sums.h OPT), never with MIND; keep_post[k] = sum_t gamma_t(B_k), the
 // posterior of the paths that hold token k (a path enters B_k at most once).  Without OPT the kernels keep their arguments (PostLaunch)
 // and their code; only their names carry one template value more.
-template <int NT, int R, bool WIN, bool MIND, bool OPT>
-__global__ __launch_bounds__(NT) void post_kernel(std::conditional_t<OPT, PostLaunchOpt, PostLaunch> a) {
+// FILL: the filler emission of wfl_align_filler_posterior (lattice_sums.h FILL), never with MIND or OPT, and the end moments
+// end_mean / end_sd of every token.  Without FILL the kernels keep their arguments and their code.
+template <int NT, int R, bool WIN, bool MIND, bool OPT, bool FILL = false>
+__global__ __launch_bounds__(NT) void post_kernel(
+    std::conditional_t<OPT, PostLaunchOpt, std::conditional_t<FILL, PostLaunchFill, PostLaunch>> a) {
   static_assert(!(OPT && MIND), "no skip arcs in the minimum-duration lattice");
-  using K = PCfg<NT, R, OPT>;
+  static_assert(!(FILL && (MIND || OPT)), "no filler emission in the minimum-duration and skip lattices");
+  using K = PCfg<NT, R, OPT, FILL>;
   extern __shared__ __attribute__((aligned(16))) char lds[];
   float* ring = (float*)lds;
   int4* alt = (int4*)(lds + K::OFF_ALT);
@@ -160,7 +186,34 @@ __global__ __launch_bounds__(NT) void post_kernel(std::conditional_t<OPT, PostLa
   int g[NGAP];
   int st;
   SkipArcs sk;
-  if constexpr (OPT) {
+  unsigned fm = 0;                             // FILL: bit r = "this thread's slot r is a filler", bit R = the next thread's first slot
+  bool anyfill = false;                        // FILL: the clip has a filler (the same in every thread)
+  if constexpr (FILL) {
+    // the clip's flags, as csrc/align.hip's FILL search judges them: a value other than 0 | 1 is status 4, after setup's 2 and 1
+    if (tid == 0) { misc[2] = 0; misc[3] = 0; }
+    __syncthreads();
+    bool any = false, badf = false;
+    for (int k = tid; k < N; k += NT) {
+      const int f = a.tok_fill[cl.tok_off + k];
+      any |= f != 0;
+      badf |= f != 0 && f != 1;
+    }
+    if (any) misc[2] = 1;
+    if (badf) misc[3] = 1;
+    __syncthreads();
+    anyfill = misc[2] != 0;
+    const bool bad_flag = misc[3] != 0;
+    __syncthreads();                            // (lattice_setup writes misc[0])
+    st = lattice_setup<NT, R>(cl, C, a.tok_cls, a.gap_cls, alt, misc, g);
+    if (st == 0 && bad_flag) st = 4;
+    if (st == 0) {
+#pragma unroll
+      for (int r = 0; r <= R; ++r) {
+        const int k = tid * R + r;
+        if (k < N && (r < R || tid + 1 < NT) && a.tok_fill[cl.tok_off + k] != 0) fm |= 1u << r;
+      }
+    }
+  } else if constexpr (OPT) {
     // the clip's flags first, as csrc/align.hip's OPT search judges them: a value other than 0 | 1 is status 4; a clip without any flag
     // and with fewer frames than tokens is wfl_align_posterior's status 1, whatever its classes are
     if (tid == 0) { misc[2] = 0; misc[3] = 0; }
@@ -194,7 +247,7 @@ __global__ __launch_bounds__(NT) void post_kernel(std::conditional_t<OPT, PostLa
     }
   }
   int dm[MIND ? R : 1];                        // this thread's slots' minimum durations, in registers
-  int fst[MIND ? R : 1], lst[MIND ? R : 1];    // first and last frame of their Viterbi runs
+  int fst[(MIND || FILL) ? R : 1], lst[(MIND || FILL) ? R : 1];    // first and last frame of their Viterbi runs (FILL: the end moments' origin)
   // with durations a tok that is no path is reported only after sweep 1: a clip that has no path at all is status 1 first (the search
   // writes tok = -1 for such a clip, and its status is the one to pass on)
   bool notpath = false;
@@ -247,10 +300,10 @@ __global__ __launch_bounds__(NT) void post_kernel(std::conditional_t<OPT, PostLa
       }
     __syncthreads();
     if (misc[0]) {
-      if constexpr (MIND || OPT) notpath = true;   // (OPT: the search writes tok = -1 for a clip without path, too: 1 comes before 8)
+      if constexpr (MIND || OPT || FILL) notpath = true;   // (OPT, FILL: the search writes tok = -1 for a clip without path, too: 1 comes before 8)
       else st = 8;
     }
-    if constexpr (MIND) {
+    if constexpr (MIND || FILL) {
       // the last frame of every run, through the same LDS words (the chain's share of a run's occupancy needs both ends before the
       // backward sweep reaches the run); a run shorter than its D_k is not a path of this lattice
       if (st == 0 && !notpath) {               // (the same in every thread; misc[0] is still 0)
@@ -268,10 +321,14 @@ __global__ __launch_bounds__(NT) void post_kernel(std::conditional_t<OPT, PostLa
 #pragma unroll
         for (int r = 0; r < R; ++r) {
           lst[r] = tid * R + r < N ? first[tid * R + r] : 0;
-          if (tid * R + r < N && lst[r] - fst[r] + 1 < dm[r]) misc[0] = 1;
+          if constexpr (MIND) {
+            if (tid * R + r < N && lst[r] - fst[r] + 1 < dm[r]) misc[0] = 1;
+          }
         }
-        __syncthreads();
-        if (misc[0]) notpath = true;
+        if constexpr (MIND) {
+          __syncthreads();
+          if (misc[0]) notpath = true;
+        }
       }
     }
   }
@@ -281,6 +338,7 @@ __global__ __launch_bounds__(NT) void post_kernel(std::conditional_t<OPT, PostLa
       a.start_mean[cl.tok_off + k] = 0.f;
       a.start_sd[cl.tok_off + k] = 0.f;
       if constexpr (OPT) a.keep_post[cl.tok_off + k] = 0.f;
+      if constexpr (FILL) { a.end_mean[cl.tok_off + k] = 0.f; a.end_sd[cl.tok_off + k] = 0.f; }
     }
     if (tid == 0) { a.logz[cl.clip] = 0.f; a.status[cl.clip] = st; }
     return;
@@ -303,15 +361,41 @@ __global__ __launch_bounds__(NT) void post_kernel(std::conditional_t<OPT, PostLa
   };
 
   // ---- the per-frame log-sum-exp, in fp32 for the sweeps; what its rounding loses, in double for logZ
-  const double lres = frame_lse<NT>(me(), Z, a.ldl, T, C, lse, red);
+  // FILL: and the filler emission of every frame, behind the block buffer; a clip without a filler has none
+  float* fem = nullptr;
+  float* fring = nullptr;
+  if constexpr (FILL) {
+    if (anyfill) fem = ws + lay.total;
+    fring = (float*)(lds + K::OFF_FRING);
+  }
+  double lres;
+  if constexpr (FILL) lres = frame_lse<NT, true>(me(), Z, a.ldl, T, C, lse, red, fem, a.phi);
+  else lres = frame_lse<NT>(me(), Z, a.ldl, T, C, lse, red);
 
   // ---- staging of the logits rows, with their log-sum-exp and Viterbi token (the backward sweep runs one stage ahead as well)
   LogitStages<NT, K::PR> stage(Z, a.ldl, T, C, ring);
   const int F = stage.F;
   float pre_l = 0.f;
   int pre_t = -1;
-  auto load_stage = [&](int c) { stage_load<true>(me(), stage, c, lse, tokp, pre_l, pre_t); };
-  auto store_stage = [&](int c) { stage_store<true>(me(), stage, c, lring, tring, pre_l, pre_t); };
+  float pre_f = 0.f;                           // FILL: the stage's filler emissions, beside pre_l
+  auto load_stage = [&](int c) {
+    stage_load<true>(me(), stage, c, lse, tokp, pre_l, pre_t);
+    if constexpr (FILL) {
+      if (anyfill) pre_f = (tid < F && c >= 0 && c * F + tid < T) ? fem[c * F + tid] : 0.f;
+    }
+  };
+  auto store_stage = [&](int c) {
+    stage_store<true>(me(), stage, c, lring, tring, pre_l, pre_t);
+    if constexpr (FILL) {
+      if (anyfill && tid < F) fring[(c & 1) * FMAX + tid] = pre_f;
+    }
+  };
+  auto filler_emission = [&](int c, int tin) -> float {   // FILL: what a filler emits at the staged frame; one LDS read
+    if constexpr (FILL) {
+      if (anyfill) return fring[(c & 1) * FMAX + tin];
+    }
+    return 0.f;
+  };
 
   int4 av[R];                                   // this thread's slots' alternatives
 #pragma unroll
@@ -365,7 +449,10 @@ __global__ __launch_bounds__(NT) void post_kernel(std::conditional_t<OPT, PostLa
         tin = 0;
         stage_enter(c, 1, load_stage, store_stage);
       }
-      if constexpr (OPT)
+      if constexpr (FILL)
+        alpha_frame<NT, R, WIN, MIND, NoHook, false, true>(me(), stage.row(c, tin), lring[(c & 1) * FMAX + tin], g, av, N, t, xf, wmax, sub, acc, G, B, I, H, dm,
+                                                           wn, NoHook(), SkipArcs(), fm, filler_emission(c, tin));
+      else if constexpr (OPT)
         alpha_frame<NT, R, WIN, MIND, NoHook, true>(me(), stage.row(c, tin), lring[(c & 1) * FMAX + tin], g, av, N, t, xf, wmax, sub, acc, G, B, I, H, dm, wn,
                                                     NoHook(), sk);
       else
@@ -418,14 +505,14 @@ __global__ __launch_bounds__(NT) void post_kernel(std::conditional_t<OPT, PostLa
   if constexpr (OPT) {                          // -inf: too few frames for the tokens that may not be skipped, or windows that cannot be met
     if (tid == 0) red[0] = end_logz_opt(fin, N, acc, N >= 1 && a.tok_opt[cl.tok_off + (N >= 1 ? N - 1 : 0)] != 0, sk.lam);
   } else {
-    if (tid == 0) red[0] = end_logz<WIN || MIND>(fin, N, acc);   // -inf: no path opens every token inside its window (meets every duration)
+    if (tid == 0) red[0] = end_logz<WIN || MIND || FILL>(fin, N, acc);   // -inf: no path opens every token inside its window (meets every duration)
   }
   __syncthreads();                             // (ckacc[] of thread 0 is visible to the block as well)
   const double logZ = red[0];                  // on the fp32 log-sum-exps; the clip's logZ is logZ - lres
-  if constexpr (WIN || MIND || OPT) {
-    if (logZ == -INFINITY || ((MIND || OPT) && notpath)) {   // status 1 (with durations or skip arcs 8: paths exist, tok is none of them) and zeros
+  if constexpr (WIN || MIND || OPT || FILL) {   // (FILL without windows: a penalty that takes every path to -inf)
+    if (logZ == -INFINITY || ((MIND || OPT || FILL) && notpath)) {   // status 1 (with durations, skip arcs or fillers 8: paths exist, tok is none of them) and zeros
       int code = 1;
-      if constexpr (MIND || OPT) {
+      if constexpr (MIND || OPT || FILL) {
         if (logZ != -INFINITY) code = 8;
       }
       for (int k = tid; k < N; k += NT) {
@@ -433,6 +520,7 @@ __global__ __launch_bounds__(NT) void post_kernel(std::conditional_t<OPT, PostLa
         a.start_mean[cl.tok_off + k] = 0.f;
         a.start_sd[cl.tok_off + k] = 0.f;
         if constexpr (OPT) a.keep_post[cl.tok_off + k] = 0.f;
+        if constexpr (FILL) { a.end_mean[cl.tok_off + k] = 0.f; a.end_sd[cl.tok_off + k] = 0.f; }
       }
       if (tid == 0) { a.logz[cl.clip] = 0.f; a.status[cl.clip] = code; }
       return;
@@ -445,13 +533,21 @@ __global__ __launch_bounds__(NT) void post_kernel(std::conditional_t<OPT, PostLa
   float bC[MIND ? R : 1][CHAIN_BACK], bB[MIND ? R : 1];
   int f0[R], cnt[R];
   double occ[R], m0[R], m1[R], m2[R];
+  // FILL: what follows token k after the frame in hand (leave_k(t + 1), on beta_t's scale), carried from the iteration before --
+  // across block boundaries too -- and the end moments' sums
+  float lv[FILL ? R : 1];
+  double e0[FILL ? R : 1], e1[FILL ? R : 1], e2[FILL ? R : 1];
 #pragma unroll
   for (int r = 0; r < R; ++r) {
     const int k = tid * R + r;
     bG[r] = k == N ? 0.f : NEG;
     bX[r] = k == N - 1 ? 0.f : NEG;
-    if constexpr (MIND) f0[r] = fst[r];
+    if constexpr (MIND || FILL) f0[r] = fst[r];
     else f0[r] = k < N ? first[k] : 0;
+    if constexpr (FILL) {                       // at T - 1 only token N - 1 ends, into the clip's end
+      lv[r] = k == N - 1 ? 0.f : NEG;
+      e0[r] = e1[r] = e2[r] = 0.0;
+    }
     if constexpr (OPT) {
       // where token N - 1 is optional the clip also ends in G_{N-1}, I_{N-2}, B_{N-2}, at -lam; a token tok does not hold has its
       // start moments about frame 0
@@ -518,6 +614,15 @@ __global__ __launch_bounds__(NT) void post_kernel(std::conditional_t<OPT, PostLa
           m0[r] += (double)gb;
           m1[r] += (double)gb * d;
           m2[r] += (double)gb * d * d;
+          if constexpr (FILL) {
+            // omega_t(k): in B_k or I_k at t and out of the token at t + 1 (summed as two terms, no difference of gammas)
+            const double dl = (double)lv[r] + cst;
+            const float w = __expf((float)((double)ac[r][1] + dl)) + __expf((float)((double)ac[r][2] + dl));
+            const double de = (double)(t - lst[r]);
+            e0[r] += (double)w;
+            e1[r] += (double)w * de;
+            e2[r] += (double)w * de * de;
+          }
           if constexpr (MIND) {
             // gamma_t(H_k^j) = gamma_{t-j+1}(B_k): a path in B_k at t is in the token's B / chain states at t .. t + max(D_k - 2, 0),
             // so gamma_t(B_k) counts once for every such frame inside Viterbi's run -- the block buffer needs no chain
@@ -533,7 +638,10 @@ __global__ __launch_bounds__(NT) void post_kernel(std::conditional_t<OPT, PostLa
       if (t == 0) break;
       // beta_{t-1}
       float eg, eb[R], ei[R], ebn;
-      if constexpr (OPT) {
+      if constexpr (FILL) {
+        beta_emissions<NT, R, WIN, false, true>(me(), row, l, g, av, avn, N, t, wn, wnn, eg, eb, ei, ebn, int4(), int2(), nullptr, fm, filler_emission(c, tin));
+        beta_frame<NT, R, MIND, false, true>(me(), N, t, eg, eb, ei, ebn, xb, wmax, subb, accb, bG, bX, bB, bC, dm, 0.f, SkipArcs(), lv);
+      } else if constexpr (OPT) {
         float ebn2;
         beta_emissions<NT, R, WIN, true>(me(), row, l, g, av, avn, N, t, wn, wnn, eg, eb, ei, ebn, avn2, wnn2, &ebn2);
         beta_frame<NT, R, MIND, true>(me(), N, t, eg, eb, ei, ebn, xb, wmax, subb, accb, bG, bX, bB, bC, dm, ebn2, sk);
@@ -555,6 +663,12 @@ __global__ __launch_bounds__(NT) void post_kernel(std::conditional_t<OPT, PostLa
       a.start_mean[cl.tok_off + k] = (float)mean;
       a.start_sd[cl.tok_off + k] = (float)sqrt(fmax(var, 0.0));
       if constexpr (OPT) a.keep_post[cl.tok_off + k] = fminf(fmaxf((float)m0[r], 0.f), 1.f);
+      if constexpr (FILL) {
+        const double em = e0[r] > 0.0 ? e1[r] / e0[r] : 0.0;
+        const double ev = e0[r] > 0.0 ? e2[r] / e0[r] - em * em : 0.0;
+        a.end_mean[cl.tok_off + k] = (float)em;
+        a.end_sd[cl.tok_off + k] = (float)sqrt(fmax(ev, 0.0));
+      }
     }
   }
   if (tid == 0) {
@@ -573,6 +687,12 @@ long clip_floats(int T, int N) {
   return round64(PostLayout(T, S, S).total);  // (256-byte aligned)
 }
 
+// with fillers: wfl_align_posterior's floats and, behind them, the filler emission of every frame
+long clip_floats_fill(int T, int N) {
+  if (T <= 0) return 0;
+  return clip_floats(T, N) + round64(T);
+}
+
 // with minimum durations: the checkpoints hold the chain as well, the block does not (post_kernel's note at occ)
 long clip_floats_min(int T, int N) {
   if (T <= 0) return 0;
@@ -589,27 +709,33 @@ namespace {
 // wfl_align_posterior (WIN false), wfl_align_posterior_windowed and wfl_align_min_duration_posterior (MIND, with or without windows): one
 // host path
 // and wfl_align_optional_posterior (OPT, with or without windows; tok_opt, skip_penalty and keep_post are its alone)
-template <bool WIN, bool MIND, bool OPT = false>
+// and wfl_align_filler_posterior (FILL, with or without windows; tok_fill, filler_penalty, end_mean and end_sd are its alone)
+template <bool WIN, bool MIND, bool OPT = false, bool FILL = false>
 int posterior_batch(const char* fn, const float* logits, int64_t ldl, int32_t C, int32_t o_id, const int64_t* frame_off_host,
                     const int32_t* n_frames_host, const int32_t* tok_off_host, const int32_t* n_tok_host, const int32_t* tok_cls,
                     const int32_t* tok_win, const int32_t* tok_min, const int32_t* gap_cls, int32_t n_clips, const int32_t* tok,
                     void* workspace, int64_t workspace_bytes, float* logz, float* tok_post, float* start_mean, float* start_sd,
-                    int32_t* status, void* stream, const int32_t* tok_opt = nullptr, float skip_penalty = 0.f, float* keep_post = nullptr) {
-  const int64_t need = OPT    ? wfl_align_optional_posterior_workspace_bytes(n_frames_host, n_tok_host, n_clips)
+                    int32_t* status, void* stream, const int32_t* tok_opt = nullptr, float skip_penalty = 0.f, float* keep_post = nullptr,
+                    const int32_t* tok_fill = nullptr, float filler_penalty = 0.f, float* end_mean = nullptr, float* end_sd = nullptr) {
+  const int64_t need = FILL   ? wfl_align_filler_posterior_workspace_bytes(n_frames_host, n_tok_host, n_clips)
+                       : OPT  ? wfl_align_optional_posterior_workspace_bytes(n_frames_host, n_tok_host, n_clips)
                        : MIND ? wfl_align_min_duration_posterior_workspace_bytes(n_frames_host, n_tok_host, n_clips)
                               : wfl_align_posterior_workspace_bytes(n_frames_host, n_tok_host, n_clips);
   bool any_tok = false, any_frame = false;
   int rc = check_clip_args(fn, C, o_id, ldl, frame_off_host, n_frames_host, tok_off_host, n_tok_host, n_clips, need, any_tok, any_frame);
   if (rc || n_clips == 0) return rc;
   if (OPT && !(skip_penalty >= 0.f && skip_penalty <= 3.0e38f)) return fail(fn, -1, "skip_penalty must be a finite number >= 0");
+  if (FILL && !(filler_penalty >= 0.f && filler_penalty <= 3.0e38f)) return fail(fn, -1, "filler_penalty must be a finite number >= 0");
   if (!logz || !status || !gap_cls ||
-      (any_tok && (!tok_cls || (WIN && !tok_win) || (MIND && !tok_min) || (OPT && (!tok_opt || !keep_post)) || !tok_post || !start_mean || !start_sd)) ||
+      (any_tok && (!tok_cls || (WIN && !tok_win) || (MIND && !tok_min) || (OPT && (!tok_opt || !keep_post)) ||
+                   (FILL && (!tok_fill || !end_mean || !end_sd)) || !tok_post || !start_mean || !start_sd)) ||
       (any_frame && (!logits || !tok)))
     return fail(fn, -1, "null device pointer");
   if ((rc = check_workspace(fn, need, workspace, workspace_bytes))) return rc;
   hipStream_t s = (hipStream_t)stream;
-  std::conditional_t<OPT, PostLaunchOpt, PostLaunch> a{};
+  std::conditional_t<OPT, PostLaunchOpt, std::conditional_t<FILL, PostLaunchFill, PostLaunch>> a{};
   if constexpr (OPT) { a.tok_opt = tok_opt; a.keep_post = keep_post; a.lambda = skip_penalty; }
+  if constexpr (FILL) { a.tok_fill = tok_fill; a.end_mean = end_mean; a.end_sd = end_sd; a.phi = filler_penalty; }
   a.logits = logits; a.ldl = ldl; a.C = C; a.tok_cls = tok_cls; a.gap_cls = gap_cls; a.tok = tok; a.tok_win = tok_win; a.tok_min = tok_min;
   a.ws = (float*)workspace; a.logz = logz; a.tok_post = tok_post; a.start_mean = start_mean; a.start_sd = start_sd; a.status = status;
   return launch_clips<NCFG>(
@@ -618,12 +744,12 @@ int posterior_batch(const char* fn, const float* logits, int64_t ldl, int32_t C,
         const int T = n_frames_host[b], N = n_tok_host[b];
         c = LatClip{(long)frame_off_host[b], off, T, tok_off_host[b], N, b};
         cfg = post_cfg(N);
-        return MIND ? clip_floats_min(T, N) : clip_floats(T, N);
+        return FILL ? clip_floats_fill(T, N) : MIND ? clip_floats_min(T, N) : clip_floats(T, N);
       },
       [&](int cfg, const auto& a) {
         return dispatch_cfg(cfg, [&](auto sh) {
           constexpr int NT = decltype(sh)::NT, R = decltype(sh)::R;
-          return launch_cfg<post_kernel<NT, R, WIN, MIND, OPT>, NT, PCfg<NT, R, OPT>::LDS>(fn, a, s);
+          return launch_cfg<post_kernel<NT, R, WIN, MIND, OPT, FILL>, NT, PCfg<NT, R, OPT, FILL>::LDS>(fn, a, s);
         });
       });
 }

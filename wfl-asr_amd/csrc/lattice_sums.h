@@ -19,6 +19,10 @@
 // OPT: the skip arcs of wfl_align_optional (include/wfl_asr.h), never with MIND: B_k is also entered from what may enter token k - 1,
 // at -lam, where token k - 1 is optional.  Everything of it stands under `if constexpr (OPT)`; the wider neighbour exchanges are the
 // *_opt siblings of the exchange pieces, and the flags travel as a bit mask per thread (SkipArcs).
+// FILL: the filler emission of wfl_align_filler (include/wfl_asr.h), never with MIND or OPT: a flagged token emits EB = EI = ef, the
+// frame's (largest logit - log-sum-exp) - phi, which frame_lse keeps per frame beside lse[]; the flags travel as a bit mask per thread
+// (bit r: this thread's slot r, bit R: the next thread's first slot), and beta_frame hands out what leaves every token (leave).
+// Everything of it stands under `if constexpr (FILL)`.
 #pragma once
 #include "lattice.h"
 
@@ -40,8 +44,10 @@ static __device__ __forceinline__ float lae3(float a, float b, float c) {
 // ---- the per-frame log-sum-exp of the logits (double, expf) -> lse[T] in fp32, for the sweeps; returns what the fp32 rounding loses,
 // summed over the clip in double (the same in every thread): it is common to every path and goes back into logZ.  red: a double per wave.
 // (a thread per row; a wave per row with coalesced loads and wave reductions was measured 4 % slower for the whole posterior kernel)
-template <int NT>
-static __device__ __forceinline__ double frame_lse(const int tid, const float* Z, long ldl, int T, int C, float* lse, double* red) {
+// FILL: fem[t] = (the row's maximum - lse[t]) - phi as well, what a filler emits at frame t; fem null: a clip without a filler, nothing more
+template <int NT, bool FILL = false>
+static __device__ __forceinline__ double frame_lse(const int tid, const float* Z, long ldl, int T, int C, float* lse, double* red,
+                                                   float* fem = nullptr, float phi = 0.f) {
   double lres = 0.0;
   for (int t = tid; t < T; t += NT) {
     const float* z = Z + (long)t * ldl;
@@ -52,6 +58,9 @@ static __device__ __forceinline__ double frame_lse(const int tid, const float* Z
     const double ld = (double)m + log(se);
     const float lf = (float)ld;
     lse[t] = lf;
+    if constexpr (FILL) {
+      if (fem) fem[t] = (m - lf) - phi;
+    }
     lres += ld - (double)lf;
   }
   lres = wave_sum(lres);
@@ -211,12 +220,14 @@ struct NoHook {
 // needs a register more and wfl_align_posterior_windowed was measured 0.4 to 0.8 % slower; profiles/sumproduct_sweeps_ab.txt.)
 // OPT: xf is the [2][XF_OPT][NT] exchange, and B_k is also entered from in_{k-1} - lam where token k - 1 is optional: the slot
 // below's alpha_enter, taken before that slot is written (of slot 0: from the left thread's G[R-1], I[R-2], B[R-2]).
-template <int NT, int R, bool WIN, bool MIND, class Hook = NoHook, bool OPT = false>
+// FILL: a slot whose bit of fm is set emits ef for B and I (B still through its window).
+template <int NT, int R, bool WIN, bool MIND, class Hook = NoHook, bool OPT = false, bool FILL = false>
 static __device__ __forceinline__ void alpha_frame(const int tid, const float* row, float l, const int (&g)[NGAP], const int4 (&av)[R], int N, int t, float2* xf,
                                                    float* wmax, float& sub, double& acc, float (&G)[R], float (&B)[R], float (&I)[R], float (&H)[MIND ? R : 1][CHAIN],
                                                    const int (&dm)[MIND ? R : 1], const int2 (&wn)[WIN ? R : 1], Hook hook = Hook(),
-                                                   const SkipArcs sk = SkipArcs()) {
+                                                   const SkipArcs sk = SkipArcs(), const unsigned fm = 0, const float ef = 0.f) {
   static_assert(!(OPT && MIND), "no skip arcs in the minimum-duration lattice");
+  static_assert(!(FILL && (MIND || OPT)), "no filler emission in the minimum-duration and skip lattices");
   const float eg = gap_emission(row, g) - l;
   float2 nb;
   float inl = -INFINITY, inr = -INFINITY;      // OPT: alpha_enter of the slot below (of the left thread's last slot), of this slot
@@ -250,6 +261,9 @@ static __device__ __forceinline__ void alpha_frame(const int tid, const float* r
       tok_emission(row, av[r], eb, ei);
       eb -= l;
       ei -= l;
+      if constexpr (FILL) {
+        if ((fm >> r) & 1u) eb = ei = ef;
+      }
       if constexpr (WIN) eb = win_mask(eb, t, wn[r]);
     }
     G[r] = k <= N ? in + eg : -INFINITY;
@@ -340,11 +354,12 @@ static __device__ __forceinline__ void beta_to_left_opt(const int tid, float* xb
 // the emissions of frame t that beta_{t-1} needs: the gap's, EB / EI of this thread's slots, and EB of the next thread's first slot
 // (avn, wnn), which this thread gathers itself from the staged row
 // OPT: EB of the next thread's SECOND slot as well (avn2, wnn2 -> ebn2): a skip arc over the next thread's first token ends there
-template <int NT, int R, bool WIN, bool OPT = false>
+// FILL: flagged slots emit ef (fm bit r: this thread's slot r, bit R: the next thread's first slot)
+template <int NT, int R, bool WIN, bool OPT = false, bool FILL = false>
 static __device__ __forceinline__ void beta_emissions(const int tid, const float* row, float l, const int (&g)[NGAP], const int4 (&av)[R], const int4& avn, int N,
                                                       int t, const int2 (&wn)[WIN ? R : 1], const int2& wnn, float& eg, float (&eb)[R],
                                                       float (&ei)[R], float& ebn, const int4& avn2 = int4(), const int2& wnn2 = int2(),
-                                                      float* ebn2 = nullptr) {
+                                                      float* ebn2 = nullptr, const unsigned fm = 0, const float ef = 0.f) {
   eg = gap_emission(row, g) - l;
 #pragma unroll
   for (int r = 0; r < R; ++r) {
@@ -353,6 +368,9 @@ static __device__ __forceinline__ void beta_emissions(const int tid, const float
       tok_emission(row, av[r], eb[r], ei[r]);
       eb[r] -= l;
       ei[r] -= l;
+      if constexpr (FILL) {
+        if ((fm >> r) & 1u) eb[r] = ei[r] = ef;
+      }
       if constexpr (WIN) eb[r] = win_mask(eb[r], t, wn[r]);
     }
   }
@@ -361,6 +379,9 @@ static __device__ __forceinline__ void beta_emissions(const int tid, const float
     float ein;
     tok_emission(row, avn, ebn, ein);
     ebn -= l;
+    if constexpr (FILL) {
+      if ((fm >> R) & 1u) ebn = ef;
+    }
     if constexpr (WIN) ebn = win_mask(ebn, t, wnn);
   }
   if constexpr (OPT) {
@@ -380,12 +401,16 @@ static __device__ __forceinline__ void beta_emissions(const int tid, const float
 // every slot, chain_in of the state before this call.
 // OPT: xb is the [2][XB_OPT][NT] exchange; G_k also goes to B_{k+1} where token k is optional, B_k / I_k to B_{k+2} where token k + 1
 // is, each at -lam.  vB[j] = beta_t(B) + EB_t of slot j, j = 0 .. R + 1 (the next thread's first two behind this thread's own), of frame t.
-template <int NT, int R, bool MIND, bool OPT = false>
+// FILL: leave[r] = lse(beta_t(G_{k+1}) + EG_t, beta_t(B_{k+1}) + EB_t(k+1)), what follows token k's last frame -- two of the three
+// terms of beta_{t-1}(B_k), summed first and on their own; it comes back on the scale of beta_{t-1} (this call's renormalisation taken
+// off it as well), so the caller's one offset serves both.
+template <int NT, int R, bool MIND, bool OPT = false, bool FILL = false>
 static __device__ __forceinline__ void beta_frame(const int tid, int N, int t, float eg, const float (&eb)[R], const float (&ei)[R], float ebn, float2* xb,
                                                   float* wmax, float& subb, double& accb, float (&bG)[R], float (&bX)[R], const float (&bB)[MIND ? R : 1],
                                                   float (&bC)[MIND ? R : 1][CHAIN_BACK], const int (&dm)[MIND ? R : 1], float ebn2 = 0.f,
-                                                  const SkipArcs sk = SkipArcs()) {
+                                                  const SkipArcs sk = SkipArcs(), float* leave = nullptr) {
   static_assert(!(OPT && MIND), "no skip arcs in the minimum-duration lattice");
+  static_assert(!(FILL && (MIND || OPT)), "no filler emission in the minimum-duration and skip lattices");
   float2 nb;
   float vB[OPT ? R + 2 : 1];
   if constexpr (OPT) {
@@ -425,7 +450,14 @@ static __device__ __forceinline__ void beta_frame(const int tid, int N, int t, f
     float nX = r + 1 < R ? bX[r + 1 < R ? r + 1 : 0] : nb.y;
     if constexpr (MIND) nX = r + 1 < R ? bB[r + 1 < R ? r + 1 : 0] : nb.y;   // the next token is entered through its B
     const float nE = r + 1 < R ? eb[r + 1 < R ? r + 1 : 0] : ebn;
-    const float x = lae3(bX[r] + ei[r], nG + eg, nX + nE);
+    float x;
+    if constexpr (FILL) {
+      const float lv = lae2(nG + eg, nX + nE);
+      leave[r] = k < N ? lv : -INFINITY;
+      x = lae2(bX[r] + ei[r], lv);
+    } else {
+      x = lae3(bX[r] + ei[r], nG + eg, nX + nE);
+    }
     float bb = bX[r];
     if constexpr (MIND) bb = bB[r];
     const float y = lae2(bG[r] + eg, bb + eb[r]);
@@ -449,6 +481,10 @@ static __device__ __forceinline__ void beta_frame(const int tid, int N, int t, f
     if (!(M > -INFINITY)) M = 0.f;
 #pragma unroll
     for (int r = 0; r < R; ++r) { bG[r] -= M; bX[r] -= M; }
+    if constexpr (FILL) {
+#pragma unroll
+      for (int r = 0; r < R; ++r) leave[r] -= M;
+    }
     if constexpr (MIND) {
 #pragma unroll
       for (int r = 0; r < R; ++r)

@@ -425,11 +425,11 @@ class Labeler:
                     decode=None, switch_penalty=None, decode_scores=None, phoneme_bigram=None, bigram_weight=None, align_draft=None,
                     draft_tolerance=None, align_edits=None, align_insertions=None, min_duration=None, duration_scores=None,
                     optional_tokens=None, skip_penalty=None, optional_scores=None, filler_token=None, filler_penalty=None,
-                    bigram_scores=None):
+                    filler_scores=None, bigram_scores=None):
         """-> list (per file) of [(start_s, end_s, phoneme)] after merge + forced alignment; with align_scores, duration_scores,
         decode_scores or bigram_scores, (that list, scores); with align_edits the tuple goes on with one more list, edits, and with
         align_insertions it ends with one more, insertions; with optional_tokens it ends with the list skipped; with a filler_token
-        it ends with the list fillers.
+        it ends with the list fillers, and with filler_scores with one more, filler_scores.
 
         align: "greedy" -- a `{audio}.txt` transcript is matched onto the freely decoded segments (infer.py:30-60, 312-319);
         "viterbi" -- files with a transcript are aligned by a search over their frame logits on the GPU (align.py: one segment
@@ -519,20 +519,29 @@ class Labeler:
         filler's span holds what the file's own free decode found there (align.filler_segments), and fillers[i] is one
         align.FillerSpan per filler (None for a file that was not aligned that way).  The greedy match a file falls back to gets
         the transcript without its fillers.  A filler_token that is an output name of the label set is refused by name; align_draft,
-        min_duration, optional_tokens and the scoring options beside it are refused."""
+        min_duration, optional_tokens and the scoring options beside it are refused.
+
+        filler_scores (with a filler_token only; None: config postprocess.filler_scores, else off): scores[i] is the align.FileScore
+        of a file that was aligned, from a forward-backward pass over the lattice the file was searched on -- the filler lattice
+        (align.filler_posteriors, the same flags and penalty) for a file with a filler, wfl_align_posterior's for one without, with
+        one line -- and filler_scores[i] one align.FillerScore per filler: the posterior that its span's frames belong to it and the
+        mean shift and spread of both its ends (None for a file that was not aligned or not scored)."""
         opts = self.options(align=align, align_scores=align_scores, decode=decode, switch_penalty=switch_penalty,
                             decode_scores=decode_scores, phoneme_bigram=phoneme_bigram, bigram_weight=bigram_weight,
                             bigram_scores=bigram_scores, align_draft=align_draft, draft_tolerance=draft_tolerance,
                             align_edits=align_edits, align_insertions=align_insertions, min_duration=min_duration,
                             duration_scores=duration_scores, optional_tokens=optional_tokens, skip_penalty=skip_penalty,
-                            optional_scores=optional_scores, filler_token=filler_token, filler_penalty=filler_penalty)
+                            optional_scores=optional_scores, filler_token=filler_token, filler_penalty=filler_penalty,
+                            filler_scores=filler_scores)
         edits = {} if opts.align_edits else None
         insertions = {} if opts.align_insertions else None
         skipped = {} if opts.optional_tokens is not None else None
         optional = {} if opts.optional_scores else None
         fillers = {} if opts.filler_token is not None else None
+        fscores = {} if opts.filler_scores else None
         final, scores = self._label_scored(audio_paths, opts, lang_id, confidence_threshold, verbose, edits=edits,
-                                           insertions=insertions, skipped=skipped, optional=optional, fillers=fillers)
+                                           insertions=insertions, skipped=skipped, optional=optional, fillers=fillers,
+                                           filler_scores=fscores)
         out = (final, scores) if opts.scored else (final,)
         if opts.align_edits:
             out += ([edits.get(fi) for fi in range(len(audio_paths))],)
@@ -544,16 +553,19 @@ class Labeler:
             out += ([optional.get(fi) for fi in range(len(audio_paths))],)
         if fillers is not None:
             out += ([fillers.get(fi) for fi in range(len(audio_paths))],)
+        if fscores is not None:
+            out += ([fscores.get(fi) for fi in range(len(audio_paths))],)
         return out if len(out) > 1 else final
 
     def _label_scored(self, audio_paths, opts, lang_id, confidence_threshold, verbose, moves=None, edits=None, insertions=None,
-                      skipped=None, optional=None, fillers=None):
+                      skipped=None, optional=None, fillers=None, filler_scores=None):
         """label_files for the resolved options `opts`, always -> (segments, scores): the files are split once into those a transcript is
         Viterbi-aligned to, those the grammar search decodes and those left to the argmax decode, and each subset's results go back to
         its files' places.  moves: a dict that takes {file index: [DraftMove]} for the files aligned inside their draft's windows.
         edits (opts.align_edits): a dict that takes {file index: [TokenEdit]} for the files that were Viterbi-aligned; insertions
         (opts.align_insertions): the same with [PlaceInsertion]; skipped (opts.optional_tokens): the same with [SkippedToken]; optional
-        (opts.optional_scores): the same with [OptionalTokenScore]; fillers (opts.filler_token): the same with [FillerSpan]."""
+        (opts.optional_scores): the same with [OptionalTokenScore]; fillers (opts.filler_token): the same with [FillerSpan]; filler_scores
+        (opts.filler_scores): the same with [FillerScore]."""
         if filler_token_collision(opts.filler_token, self._names_for(self._lang_name(lang_id))[1]) is not None:
             raise ValueError(f"filler_token: {opts.filler_token!r} is an output name of this model's label set")
         unknown = (unknown_optional_tokens(opts.optional_tokens, self._names_for(self._lang_name(lang_id))[1])
@@ -598,8 +610,11 @@ class Labeler:
         for fi, segs in searched.items():
             final[fi] = self._match_forced(audio_paths[fi], segs, verbose)
         if with_t:
+            fscores = {} if filler_scores is not None else None       # (by the file's place among with_t)
             got = self._label_viterbi(paths(with_t), [forced[fi] for fi in with_t], [drafts[fi] for fi in with_t], opts, lang_id,
-                                      confidence_threshold, verbose)
+                                      confidence_threshold, verbose, fscores)
+            for j, rows in (fscores or {}).items():
+                filler_scores[with_t[j]] = rows
             for fi, rec in zip(with_t, got):
                 final[fi], scores[fi] = rec.segments, rec.score
                 for into, value in ((moves, rec.moves), (edits, rec.edits), (insertions, rec.insertions), (skipped, rec.skipped),
@@ -880,14 +895,15 @@ class Labeler:
                 n_frames += int(frames[b])
         return total, total_logz, total_lse, n_frames, skipped
 
-    def _label_viterbi(self, audio_paths, transcripts, drafts, opts, lang_id, threshold, verbose):
+    def _label_viterbi(self, audio_paths, transcripts, drafts, opts, lang_id, threshold, verbose, filler_scores=None):
         """Files with a transcript, align="viterbi" -> one ViterbiLabel per file.  Their chunks are forwarded with logits (kept on
         the device); the free decode of the same forward gives the greedy result, which the pause rule at the ends needs and which a
         file falls back to (with a message) when its transcript cannot be aligned.  Each file's chunks' valid logits rows are
         concatenated on the device, so one search covers the whole file; the files of a wave are one ragged batch (align.AlignBatch)
         that goes through the stages -- _greedy_and_plans, _clip_constraints, _search, _score, _clip_label -- and only ids / tok /
         score / status and the scoring calls' small tables come back to the host.  drafts: per file its draft segments or None
-        (opts.align_draft; the transcript is then the draft's labels)."""
+        (opts.align_draft; the transcript is then the draft's labels).  filler_scores (opts.filler_scores): a dict that takes
+        {file index: [FillerScore]} for the files that were aligned and scored."""
         lang_name = self._lang_name(lang_id)
         drafts = drafts if drafts is not None else [None] * len(audio_paths)
         sub_pairs = sub_out = None
@@ -917,10 +933,16 @@ class Labeler:
                     got = self._clip_label(found, scored, b, chunks[b], transcripts[fi], drafts[fi], free_segs[fi], opts, sub_out)
                     if got is not None:
                         aligned[fi] = got
+                        if opts.filler_scores and filler_scores is not None and b in scored.raw:
+                            # one row per filler; a scored file without a filler has none
+                            filler_scores[fi] = (AL.filler_scores(got.fillers, *scored.raw[b][2:], *scored.ends[b], frame_duration)
+                                                 if got.fillers else [])
             for fi in sel:
                 out.append(aligned.get(fi, ViterbiLabel(greedy[fi])))
                 if opts.optional_scores and fi not in aligned:
                     print(f"{audio_paths[fi]}: no optional-token scores (the file was not Viterbi-aligned)")
+                if opts.filler_scores and fi not in aligned:
+                    print(f"{audio_paths[fi]}: no filler scores (the file was not Viterbi-aligned)")
                 if opts.align_edits and fi not in aligned:
                     print(f"{audio_paths[fi]}: no transcript edits (the file was not Viterbi-aligned)")
                 if opts.align_insertions and fi not in aligned:
@@ -985,7 +1007,7 @@ class Labeler:
                 no_flag = [0] * len(tr)
                 optional = AL.optional_token_scores(flags if flags is not None else no_flag, left_out if left_out is not None else no_flag,
                                                     scored.keep[b], segs, tr)
-        elif opts.align_scores or opts.duration_scores or opts.optional_scores:      # (the scoring entry refused the path the search gave it)
+        elif opts.align_scores or opts.duration_scores or opts.optional_scores or opts.filler_scores:      # (the scoring entry refused the path the search gave it)
             entry, code = scored.refused.get(b, ("wfl_align_posterior", None))
             print(f"{found.paths[b]}: no alignment scores ({entry} status {code})")
         lab, spans = segs, None
@@ -1037,6 +1059,7 @@ class _Scored(NamedTuple):
     edits: dict                     # the clip's rows of edit_scores' edits
     insertions: dict                # the clip's rows of insertion_scores' ins
     keep: dict                      # optional_posteriors' keep_post of a clip it accepted (opts.optional_scores)
+    ends: dict                      # filler_posteriors' (end_mean, end_sd) of a clip it accepted (opts.filler_scores)
 
 
 def _clip_flags(transcripts, opts):
@@ -1133,7 +1156,7 @@ def _search(batch, paths, opts) -> _Searched:
 def _score(found, opts, sub_pairs) -> _Scored:
     """Stage 4: edits, insertions, posteriors, duration posteriors of the clips the search aligned, each call on a sub-batch and on
     the lattice its clips were searched on (AlignBatch.scored_on: the search's PackedClips or tables packed again)."""
-    scored = _Scored({}, {}, {}, {}, {})
+    scored = _Scored({}, {}, {}, {}, {}, {})
     ok = found.ok
     if not ok:
         return scored
@@ -1180,6 +1203,30 @@ def _score(found, opts, sub_pairs) -> _Scored:
             for b in ok:
                 if b in scored.raw:
                     scored.keep[b] = np.ones(len(found.batch.alts[b]), np.float32)
+    if opts.filler_scores:
+        # every clip on the lattice it was searched on: a clip with a filler over the filler lattice, with the flags and the penalty of
+        # its search; a clip without one was searched on wfl_align's lattice (wfl_align_filler's with no flag set) and is scored there
+        fills = found.batch.fills or [None] * len(found.paths)
+        for with_fill in (True, False):
+            part = [b for b in ok if (fills[b] is not None and any(fills[b])) == with_fill]
+            if not part:
+                continue
+            sub = found.batch.select(part)
+            packed = sub.pack(False)
+            if with_fill:
+                d = AL.filler_posteriors(*sub.args(), sub.fills, found.d_tok, opts.filler_penalty, frame_offsets=sub.f0, packed=packed)
+                _take_posteriors(found, part, (d[0], d[1], d[2], d[3], d[6]), "wfl_align_filler_posterior", scored)
+                h_end, k0 = torch.stack([d[4], d[5]]).cpu().numpy(), 0
+                for b in part:
+                    n = len(found.batch.alts[b])
+                    if b in scored.raw:
+                        scored.ends[b] = (h_end[0, k0:k0 + n], h_end[1, k0:k0 + n])
+                    k0 += n
+            else:
+                for b in part:
+                    print(f"{found.paths[b]}: {FILLER_SCORES_PLAIN}")
+                d_post = AL.alignment_posteriors(*sub.args(), found.d_tok, frame_offsets=sub.f0, packed=packed)
+                _take_posteriors(found, part, d_post, "wfl_align_posterior", scored)
     return scored
 
 
@@ -1228,6 +1275,8 @@ MIN_DURATION_INFEASIBLE = ("no path gives every token its minimum duration (post
                            "for the draft's windows); aligning the transcript without minimum durations")
 DURATION_SCORES_PLAIN = ("scored without minimum durations (postprocess.duration_scores: the file was searched without them, and a "
                          "score speaks of the lattice its search ran on)")
+FILLER_SCORES_PLAIN = ("scored by wfl_align_posterior (postprocess.filler_scores: the transcript has no filler, so the file was searched "
+                       "on the lattice without a filler emission, and a score speaks of the lattice its search ran on)")
 DRAFT_INFEASIBLE = ("no path opens every token inside its draft window (two starts on one frame, or more tokens than frames in between); "
                     "aligning the draft's transcript without windows")
 
@@ -1450,6 +1499,16 @@ def _write_fillers(lab_path, rows):
         _write_text(fillers_path(lab_path), AL.format_fillers_tsv(rows), "Filler spans")
 
 
+def filler_scores_path(lab_path):
+    return os.path.splitext(lab_path)[0] + ".filler_scores.tsv"
+
+
+def _write_filler_scores(lab_path, rows):
+    """`{stem}.filler_scores.tsv` beside the .lab of a file that was scored over the lattice of its filler search (None: no file)."""
+    if rows is not None:
+        _write_text(filler_scores_path(lab_path), AL.format_filler_scores_tsv(rows), "Filler scores")
+
+
 def _write_score(lab_path, segments, score):
     """The scores file of one labelled file beside its .lab, by the kind of its score (None: no file)."""
     if isinstance(score, DC.FreeScore):
@@ -1463,7 +1522,7 @@ def infer_audio(audio_path, config_path="config.yaml", checkpoint_path="best_mod
                 align_scores=None, decode=None, switch_penalty=None, decode_scores=None, phoneme_bigram=None, bigram_weight=None,
                 align_draft=None, draft_tolerance=None, align_edits=None, align_insertions=None, min_duration=None,
                 duration_scores=None, optional_tokens=None, skip_penalty=None, optional_scores=None, filler_token=None,
-                filler_penalty=None, bigram_scores=None):
+                filler_penalty=None, filler_scores=None, bigram_scores=None):
     """align: "greedy" | "viterbi" | None (config postprocess.align, else greedy): how a `{audio}.txt` transcript is aligned
     (Labeler.label_files).  align_scores (viterbi only; None: config postprocess.align_scores): also write `{stem}.scores.tsv`
     beside the .lab when the file was Viterbi-aligned (format_scores_tsv).  decode: "argmax" | "viterbi" | None (config
@@ -1490,12 +1549,17 @@ def infer_audio(audio_path, config_path="config.yaml", checkpoint_path="best_mod
     the transcript with the posterior probability that it is present (align.optional_posteriors, align.format_optional_tsv).
     filler_token / filler_penalty (align viterbi only; None: config postprocess.filler_token / postprocess.filler_penalty): the
     transcript token that matches anything and the nats it pays per frame (Labeler.label_files); in the .lab its span holds what
-    the free decode found there, and `{stem}.fillers.tsv` lists the spans (align.format_fillers_tsv)."""
+    the free decode found there, and `{stem}.fillers.tsv` lists the spans (align.format_fillers_tsv).  filler_scores (with a
+    filler_token only; None: config postprocess.filler_scores): also write `{stem}.scores.tsv`, one row per transcript token summed
+    over the lattice the file was searched on, and `{stem}.filler_scores.tsv`, one row per filler with the posterior of its span and
+    the mean shift and spread of both its ends (align.filler_posteriors, align.format_filler_scores_tsv); the .lab and
+    `{stem}.fillers.tsv` are what they are without it."""
     given = dict(align=align, align_scores=align_scores, decode=decode, switch_penalty=switch_penalty, decode_scores=decode_scores,
                  phoneme_bigram=phoneme_bigram, bigram_weight=bigram_weight, bigram_scores=bigram_scores, align_draft=align_draft,
                  draft_tolerance=draft_tolerance, align_edits=align_edits, align_insertions=align_insertions, min_duration=min_duration,
                  duration_scores=duration_scores, optional_tokens=optional_tokens, skip_penalty=skip_penalty,
-                 optional_scores=optional_scores, filler_token=filler_token, filler_penalty=filler_penalty)
+                 optional_scores=optional_scores, filler_token=filler_token, filler_penalty=filler_penalty,
+                 filler_scores=filler_scores)
     _refuse_before_load(config_path, **given)
     lab = _labeler(config_path, checkpoint_path, device)
     opts = lab.options(**given)
@@ -1504,8 +1568,10 @@ def infer_audio(audio_path, config_path="config.yaml", checkpoint_path="best_mod
     skipped = {} if opts.optional_tokens is not None else None
     optional = {} if opts.optional_scores else None
     fillers = {} if opts.filler_token is not None else None
+    fscores = {} if opts.filler_scores else None
     (segments,), (score,) = lab._label_scored([audio_path], opts, lang_id, confidence_threshold, True, edits=edits,
-                                              insertions=insertions, skipped=skipped, optional=optional, fillers=fillers)
+                                              insertions=insertions, skipped=skipped, optional=optional, fillers=fillers,
+                                              filler_scores=fscores)
     if output_lab_path:
         if os.path.abspath(output_lab_path) == os.path.abspath(audio_path):
             # the reference would truncate the input WAV here (infer.py:410-411 + utils.py:77)
@@ -1522,6 +1588,8 @@ def infer_audio(audio_path, config_path="config.yaml", checkpoint_path="best_mod
             _write_optional(output_lab_path, optional.get(0))
         if fillers is not None:
             _write_fillers(output_lab_path, fillers.get(0))
+        if fscores is not None:
+            _write_filler_scores(output_lab_path, fscores.get(0))
     return segments
 
 
@@ -1530,12 +1598,14 @@ def infer_folder(folder_path: str, config_path: str = "config.yaml", checkpoint_
                  temperature=1.0, confidence_threshold=0.0, align=None, align_scores=None, decode=None, switch_penalty=None,
                  decode_scores=None, phoneme_bigram=None, bigram_weight=None, align_draft=None, draft_tolerance=None,
                  align_edits=None, align_insertions=None, min_duration=None, duration_scores=None, optional_tokens=None,
-                 skip_penalty=None, optional_scores=None, filler_token=None, filler_penalty=None, bigram_scores=None):
+                 skip_penalty=None, optional_scores=None, filler_token=None, filler_penalty=None, filler_scores=None,
+                 bigram_scores=None):
     given = dict(align=align, align_scores=align_scores, decode=decode, switch_penalty=switch_penalty, decode_scores=decode_scores,
                  phoneme_bigram=phoneme_bigram, bigram_weight=bigram_weight, bigram_scores=bigram_scores, align_draft=align_draft,
                  draft_tolerance=draft_tolerance, align_edits=align_edits, align_insertions=align_insertions, min_duration=min_duration,
                  duration_scores=duration_scores, optional_tokens=optional_tokens, skip_penalty=skip_penalty,
-                 optional_scores=optional_scores, filler_token=filler_token, filler_penalty=filler_penalty)
+                 optional_scores=optional_scores, filler_token=filler_token, filler_penalty=filler_penalty,
+                 filler_scores=filler_scores)
     _refuse_before_load(config_path, **given)
     wav_files = sorted(f for f in os.listdir(folder_path) if f.lower().endswith(".wav"))
     os.makedirs(output_dir, exist_ok=True)
@@ -1554,8 +1624,9 @@ def infer_folder(folder_path: str, config_path: str = "config.yaml", checkpoint_
     skipped = {} if opts.optional_tokens is not None else None
     optional = {} if opts.optional_scores else None
     fillers = {} if opts.filler_token is not None else None
+    fscores = {} if opts.filler_scores else None
     all_segments, all_scores = (lab._label_scored(paths, opts, lang_id, confidence_threshold, True, moves, edits, insertions, skipped,
-                                                  optional, fillers)
+                                                  optional, fillers, fscores)
                                 if paths else ([], []))
     for fi, (wav_file, segments, score) in enumerate(zip(wav_files, all_segments, all_scores)):
         print(f"\nInferencing: {wav_file}")
@@ -1572,10 +1643,12 @@ def infer_folder(folder_path: str, config_path: str = "config.yaml", checkpoint_
             _write_optional(lab_path, optional.get(fi))
         if fillers is not None:
             _write_fillers(lab_path, fillers.get(fi))
+        if fscores is not None:
+            _write_filler_scores(lab_path, fscores.get(fi))
         print("Predicted segments:")
         for start, end, ph in segments:
             print(f"({round(start, 2)}, {round(end, 2)}, {ph})")
-    if opts.align_scores or opts.duration_scores or opts.optional_scores:
+    if opts.align_scores or opts.duration_scores or opts.optional_scores or opts.filler_scores:
         name = "alignment_scores.tsv" if world == 1 else f"alignment_scores.rank{rank}.tsv"
         _write_text(os.path.join(output_dir, name),
                     format_review_tsv([(f, sc) for f, sc in zip(wav_files, all_scores) if isinstance(sc, AL.FileScore)]), "Review list")
@@ -1603,6 +1676,10 @@ def infer_folder(folder_path: str, config_path: str = "config.yaml", checkpoint_
         name = "filler_spans.tsv" if world == 1 else f"filler_spans.rank{rank}.tsv"
         _write_text(os.path.join(output_dir, name), AL.format_folder_fillers_tsv([(wav_files[fi], fillers[fi]) for fi in sorted(fillers)]),
                     "Filler spans of the folder")
+    if fscores is not None:
+        name = "filler_scores.tsv" if world == 1 else f"filler_scores.rank{rank}.tsv"
+        _write_text(os.path.join(output_dir, name), AL.format_folder_filler_scores_tsv([(wav_files[fi], fscores[fi]) for fi in sorted(fscores)]),
+                    "Filler scores of the folder")
     if opts.free_scores:
         name = "decode_scores.tsv" if world == 1 else f"decode_scores.rank{rank}.tsv"
         _write_text(os.path.join(output_dir, name),
@@ -1702,10 +1779,16 @@ def main(argv=None):
     @click.option("--filler-penalty", "filler_penalty", type=float, default=None,
                   help="With --filler-token: what a filler pays per frame of its run, in nats (>= 0). Default: config "
                        "postprocess.filler_penalty, else 1.0 (a value to start from, not a measured optimum).")
+    @click.option("--filler-scores", "filler_scores", is_flag=True, default=None,
+                  help="With --filler-token: --align-scores for that alignment, from a forward-backward pass over the filler lattice "
+                       "on the GPU: {stem}.scores.tsv, one row per transcript token, and {stem}.filler_scores.tsv, per filler the "
+                       "posterior that its span belongs to it and the mean shift and spread of its start and of its end; for a "
+                       "folder also alignment_scores.tsv and filler_scores.tsv, the lowest posterior first. Default: config "
+                       "postprocess.filler_scores, else off.")
     def cli(path, checkpoint, config, output, lang_id, sample, top_k, top_p, temperature, device, confidence_threshold, align,
             align_scores, decode, switch_penalty, decode_scores, phoneme_bigram, bigram_weight, bigram_scores, align_draft,
             draft_tolerance, align_edits, align_insertions, min_duration, duration_scores, optional_tokens, skip_penalty,
-            optional_scores, filler_token, filler_penalty):
+            optional_scores, filler_token, filler_penalty, filler_scores):
         if switch_penalty is not None and not switch_penalty >= 0.0:
             raise click.UsageError("--switch-penalty must be >= 0 (nats)")
         if sample:
@@ -1741,7 +1824,7 @@ def main(argv=None):
                            align_edits=align_edits, align_insertions=align_insertions,
                            min_duration=parse_min_duration(min_duration), duration_scores=duration_scores,
                            optional_tokens=list(optional_tokens) or None, skip_penalty=skip_penalty, optional_scores=optional_scores,
-                           filler_token=filler_token, filler_penalty=filler_penalty)
+                           filler_token=filler_token, filler_penalty=filler_penalty, filler_scores=filler_scores)
         except ValueError as err:
             raise click.UsageError(str(err))
         output_path = inf_path if output == "." else output
@@ -1765,7 +1848,8 @@ def main(argv=None):
                   # a penalty only beside the tokens it prices (with none, none was given, or resolve had refused it)
                   optional_tokens=opts.optional_tokens, skip_penalty=opts.skip_penalty if opts.optional_tokens is not None else None,
                   optional_scores=opts.optional_scores,
-                  filler_token=opts.filler_token, filler_penalty=opts.filler_penalty if opts.filler_token is not None else None)
+                  filler_token=opts.filler_token, filler_penalty=opts.filler_penalty if opts.filler_token is not None else None,
+                  filler_scores=opts.filler_scores)
         if inf_path.is_dir():
             infer_folder(folder_path=str(inf_path), output_dir=str(output_path), **kw)
         else:

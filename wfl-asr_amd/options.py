@@ -48,6 +48,9 @@ infer_folder (before any model is loaded) and the CLI all call `resolve` and car
                                lattices have no filler emission, and a score must speak of the lattice its search ran on
                            (32. with the model known, Labeler.label_files: a filler_token that is an output name of the label set is
                                refused by name, `filler_token_collision`)
+  filler_scores   off      33. a bool (true / false; no number, no string)
+                           34. needs a filler_token (it scores the filler lattice of that search: per filler the posterior of its
+                               span and the spread of both its ends; without a filler_token align_scores is the option to ask for)
 """
 from __future__ import annotations
 
@@ -80,6 +83,10 @@ DEFAULT_FILLER_PENALTY = 1.0      # nats per frame; a value to start from, not a
 FILLER_TOKEN_ERROR = ("filler_token cannot be combined with align_draft, min_duration, optional_tokens, align_scores, align_edits, "
                       "align_insertions, duration_scores or optional_scores: their lattices have no filler emission, and a score must "
                       "speak of the lattice the search ran on; drop postprocess.filler_token (--filler-token) for that run")
+
+
+FILLER_SCORES_ERROR = ("filler_scores needs a filler_token (postprocess.filler_token, --filler-token): it scores the filler lattice of "
+                       "that search; without a filler_token align_scores is the option to ask for")
 
 
 def _filler_token(given):
@@ -196,7 +203,8 @@ class PostOptions(_SearchOptions):
         skip_penalty     0.0    nats a path pays per skipped token (also stands for "not given")
         optional_scores  False  score every alignment searched with optional_tokens, over the skip lattice
         filler_token     None   the transcript token that matches anything
-        filler_penalty   1.0    nats a filler pays per frame of its run (also stands for "not given")"""
+        filler_penalty   1.0    nats a filler pays per frame of its run (also stands for "not given")
+        filler_scores    False  score every alignment searched with a filler_token, over the filler lattice"""
     align_draft: Optional[str] = None
     draft_tolerance: float = DEFAULT_DRAFT_TOLERANCE
     align_edits: bool = False
@@ -208,10 +216,11 @@ class PostOptions(_SearchOptions):
     optional_scores: bool = False
     filler_token: Optional[str] = None
     filler_penalty: float = DEFAULT_FILLER_PENALTY
+    filler_scores: bool = False
 
     def __new__(cls, *args, align_draft=None, draft_tolerance=DEFAULT_DRAFT_TOLERANCE, align_edits=False, align_insertions=False,
                 min_duration=None, duration_scores=False, optional_tokens=None, skip_penalty=0.0, optional_scores=False,
-                filler_token=None, filler_penalty=DEFAULT_FILLER_PENALTY, **kw):
+                filler_token=None, filler_penalty=DEFAULT_FILLER_PENALTY, filler_scores=False, **kw):
         self = super().__new__(cls, *args, **kw)
         object.__setattr__(self, "align_draft", align_draft)
         object.__setattr__(self, "draft_tolerance", draft_tolerance)
@@ -224,21 +233,24 @@ class PostOptions(_SearchOptions):
         object.__setattr__(self, "optional_scores", optional_scores)
         object.__setattr__(self, "filler_token", filler_token)
         object.__setattr__(self, "filler_penalty", filler_penalty)
+        object.__setattr__(self, "filler_scores", filler_scores)
         return self
 
     def __setattr__(self, name, value):
         raise AttributeError(f"PostOptions is read-only: cannot set {name!r}")
 
     _KEYWORD = ("align_draft", "draft_tolerance", "align_edits", "align_insertions", "min_duration", "duration_scores",
-                "optional_tokens", "skip_penalty", "optional_scores", "filler_token", "filler_penalty")
-    _KEYWORD_DEFAULTS = (None, DEFAULT_DRAFT_TOLERANCE, False, False, None, False, None, 0.0, False, None, DEFAULT_FILLER_PENALTY)
+                "optional_tokens", "skip_penalty", "filler_scores", "optional_scores", "filler_token", "filler_penalty")
+    # (filler_scores, the latest, stands in front of optional_scores: the record's last fields are the filler's own two)
+    _KEYWORD_DEFAULTS = (None, DEFAULT_DRAFT_TOLERANCE, False, False, None, False, None, 0.0, False, False, None,
+                         DEFAULT_FILLER_PENALTY)
 
     def _draft(self):
         return self.align_draft, self.draft_tolerance
 
     @property
     def scored(self) -> bool:
-        return self.align_scores or self.free_scores or self.duration_scores or self.optional_scores
+        return self.align_scores or self.free_scores or self.duration_scores or self.optional_scores or self.filler_scores
 
     def _later(self):
         return tuple(getattr(self, k) for k in self._KEYWORD)
@@ -247,11 +259,11 @@ class PostOptions(_SearchOptions):
     @classmethod
     def _make(cls, iterable, align_draft=None, draft_tolerance=DEFAULT_DRAFT_TOLERANCE, align_edits=False, align_insertions=False,
               min_duration=None, duration_scores=False, optional_tokens=None, skip_penalty=0.0, optional_scores=False,
-              filler_token=None, filler_penalty=DEFAULT_FILLER_PENALTY):
+              filler_token=None, filler_penalty=DEFAULT_FILLER_PENALTY, filler_scores=False):
         return cls(*iterable, align_draft=align_draft, draft_tolerance=draft_tolerance, align_edits=align_edits,
                    align_insertions=align_insertions, min_duration=min_duration, duration_scores=duration_scores,
                    optional_tokens=optional_tokens, skip_penalty=skip_penalty, optional_scores=optional_scores,
-                   filler_token=filler_token, filler_penalty=filler_penalty)
+                   filler_token=filler_token, filler_penalty=filler_penalty, filler_scores=filler_scores)
 
     def _replace(self, **kw):
         later = {k: kw.pop(k, getattr(self, k)) for k in self._KEYWORD}
@@ -288,7 +300,7 @@ def _number_ge0(x):
 def resolve(post, *, align=None, align_scores=None, decode=None, switch_penalty=None, decode_scores=None, phoneme_bigram=None,
             bigram_weight=None, bigram_scores=None, align_draft=None, draft_tolerance=None, align_edits=None,
             align_insertions=None, min_duration=None, duration_scores=None, optional_tokens=None, skip_penalty=None,
-            optional_scores=None, filler_token=None, filler_penalty=None) -> PostOptions:
+            optional_scores=None, filler_token=None, filler_penalty=None, filler_scores=None) -> PostOptions:
     """post: the config's `postprocess` mapping (None: {}).  Per option the argument wins; None leaves it to `post[<option>]`, and a
     key that is absent (or None) to the default.  -> PostOptions, or ValueError for the first broken rule of the module's table."""
     post = post or {}
@@ -396,8 +408,13 @@ def resolve(post, *, align=None, align_scores=None, decode=None, switch_penalty=
     if filler_token is not None and (align_draft or min_duration is not None or optional_tokens is not None or align_scores or align_edits
                                      or align_insertions or duration_scores or optional_scores):
         raise ValueError(FILLER_TOKEN_ERROR)
+    filler_scores = pick("filler_scores", filler_scores, False)
+    if not isinstance(filler_scores, bool):
+        raise ValueError(f"filler_scores must be true or false, got {filler_scores!r}")
+    if filler_scores and filler_token is None:
+        raise ValueError(FILLER_SCORES_ERROR)
     return PostOptions(align, align_scores, decode, switch_penalty, decode_scores, phoneme_bigram, bigram_weight, bigram_scores,
                        align_draft=align_draft, draft_tolerance=draft_tolerance, align_edits=align_edits,
                        align_insertions=align_insertions, min_duration=min_duration, duration_scores=duration_scores,
                        optional_tokens=optional_tokens, skip_penalty=skip_penalty, optional_scores=optional_scores,
-                       filler_token=filler_token, filler_penalty=filler_penalty)
+                       filler_token=filler_token, filler_penalty=filler_penalty, filler_scores=filler_scores)
