@@ -412,6 +412,42 @@ int32_t wfl_align_filler(const float* logits, int64_t ldl, int32_t C, int32_t o_
                          void* workspace, int64_t workspace_bytes, int32_t* ids, int32_t* tok, float* score, int32_t* status,
                          void* stream);
 
+/* ---- wfl_align with a duration prior per token: an explicit-duration (semi-Markov) Viterbi search (`postprocess.duration_prior`;
+ * wfl-asr_amd/align.py viterbi_align_duration_prior, csrc/align_duration_prior.hip).  wfl_align_windowed's arguments up to n_clips
+ * (tok_win may be null: no windows), then the prior: dur (device), [n_rows][D + 1] fp32, 1 <= D <= 32 -- columns 0 .. D - 1 are
+ * L(1) .. L(D), column D is `tail`; every entry finite or -inf, never NaN or +inf, tail <= 0 or -inf (the caller's contract, as for
+ * wfl_decode_bigram's trans) -- and tok_dur (device), [total tokens] int32, rows as tok_cls: the row of token k, -1 for no prior
+ * (L = 0, tail = 0).  A run of d frames of token k (one B frame, d - 1 I frames) with row r adds
+ *     L_k(d) = dur[r][d-1]                          1 <= d <= D
+ *            = dur[r][D-1] + (d - D) * dur[r][D]    d >  D
+ * to the path's score (gaps carry no prior), so hard minimum and maximum durations are rows with -inf entries.  Frame by frame, every
+ * quantity of frame t - 1 on the right:
+ *     Ent_k(t) = max(G_k(t-1), X_{k-1}(t-1))          Ent_0(0) = 0, every other Ent_k(0) = -inf; G first on a tie
+ *     G_k(t)   = Ent_k(t) + EG_t
+ *     R_k^1(t) = Ent_k(t) + EB_t(k)                   (EB through the window where tok_win is given)
+ *     R_k^j(t) = R_k^{j-1}(t-1) + EI_t(k)             2 <= j <= D: a run of exactly j frames, prior not yet added
+ *     Y_k(t)   = max(Y_k(t-1), R_k^D(t-1) + L_k(D)) + EI_t(k) + tail_k      a run longer than D; Y first on a tie
+ *     X_k(t)   = max(max_j R_k^j(t) + L_k(j), Y_k(t))      frame t is the last frame of token k; shortest j first, Y last on a tie
+ *     end      = max(G_N(T-1), X_{N-1}(T-1))          G first
+ * Emissions, alternatives, gap classes and windows are wfl_align_windowed's; the search decides on the raw logits and no expression
+ * forms inf - inf.  Outputs: ids and tok as wfl_align's (a run's first frame carries its arg-max alternative's B class, every later
+ * frame that frame's arg-max alternative's I class); score[b] the path's sum of e_t plus the sum of L_k(d_k).  status[b]: wfl_align's
+ * codes; 1 "no path of finite score": T < N, or the table or the windows forbid every path; 2 N above 4096; 4 also a tok_dur outside
+ * -1 .. n_rows - 1.  A clip with status != 0 gets ids = o_id, tok = -1, score 0 and does not disturb its batch; one workgroup per clip,
+ * a clip aligned alone equals the same clip inside any batch, bit for bit.  Host-side negative returns: wfl_align's, and a null tok_dur
+ * with any token present, a null dur with n_rows > 0, n_rows < 0, D outside 1 .. 32, a workspace that is too small.
+ * Workspace: one backpointer byte per token slot and frame, and the history of the D run scores of every slot where the workgroup's LDS
+ * does not hold it: per clip, in 4-byte words (0 for a clip with T < N, T = 0 or N > 4096),
+ *     round_up_64(T * words(N)) + ring(N, D),   words(N) = 64 (N <= 127), 256 (N <= 1023), 512 (N <= 2047), 1536 (N <= 4096),
+ *     ring(N, D) = 0 for N <= 511; round_up_64(slots(N) * D) where D > 23 (N <= 1023), D > 9 (N <= 2047), D > 1 (N <= 4096), else 0,
+ *     slots(N) = 1024 (N <= 1023), 2048 (N <= 2047), 4608 (N <= 4096). */
+int64_t wfl_align_duration_prior_workspace_bytes(const int32_t* n_frames_host, const int32_t* n_tok_host, int32_t n_clips, int32_t D);
+int32_t wfl_align_duration_prior(const float* logits, int64_t ldl, int32_t C, int32_t o_id, const int64_t* frame_off_host,
+                                 const int32_t* n_frames_host, const int32_t* tok_off_host, const int32_t* n_tok_host,
+                                 const int32_t* tok_cls, const int32_t* tok_win, const int32_t* gap_cls, int32_t n_clips,
+                                 const int32_t* tok_dur, const float* dur, int32_t n_rows, int32_t D, void* workspace,
+                                 int64_t workspace_bytes, int32_t* ids, int32_t* tok, float* score, int32_t* status, void* stream);
+
 /* ---- Posteriors of a Viterbi alignment by forward-backward on the GPU (`postprocess.align_scores`; wfl-asr_amd/align.py).  No
  * counterpart in the reference, which reports no confidence for its string match.  The lattice, emissions EB / EI / EG, start and end
  * states, caps (C <= 1024, N <= 4096) and argument conventions are wfl_align's.  The weight of a path is exp(sum_t e_t(state_t));

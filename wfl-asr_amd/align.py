@@ -26,6 +26,9 @@ token gets one contiguous, time-ordered run of frames, none is dropped.
   optional_token_scores / format_optional_tsv / format_folder_optional_tsv   one file's OptionalTokenScore rows (kept | skipped, the
                         keep posterior, the `doubt` flag), {stem}.optional.tsv, the folder's list, least confident decision first
   min_frames_for        `postprocess.min_duration` (seconds, or seconds per token name) -> frames per transcript token
+  viterbi_align_duration_prior  the search with a duration prior per token: a run of d frames adds its table row's L(d)
+                        (`wfl_align_duration_prior`, `postprocess.duration_prior`); upload_durations packs the rows once
+  duration_rows         a durations.DurationPrior -> the table row of every transcript token (-1: none)
   alignment_posteriors  forward-backward over the same lattice (csrc/align_posterior.h, `wfl_align_posterior`; of a batch packed with
                         windows, `wfl_align_posterior_windowed`): logZ, and per token
                         the posterior of the run Viterbi chose and the spread of its start (`postprocess.align_scores`)
@@ -63,6 +66,7 @@ MAX_TOKENS = 4096          # wfl_align's token cap per clip (status 2 above it)
 MAX_ALTERNATIVES = 4       # (B, I) pairs per token
 MAX_GAP = 8                # gap classes per clip
 MAX_MIN_FRAMES = 8         # wfl_align_min_duration's cap on a token's minimum duration, frames (csrc/lattice.h)
+MAX_PRIOR_FRAMES = 32      # wfl_align_duration_prior's cap on D, the longest explicit duration of its table (csrc/align_duration_prior.hip)
 PAUSES = ("SP", "AP")
 
 STATUS_OK, STATUS_INFEASIBLE, STATUS_OVER_CAP, STATUS_BAD_CLASS = 0, 1, 2, 4
@@ -74,12 +78,12 @@ MAX_SUBSTITUTES = 512      # wfl_align_edits' table cap
 EDITS_WORKSPACE_LIMIT = 1 << 30
 
 
-def _workspace_bytes(symbol, n_frames, n_tokens) -> int:
+def _workspace_bytes(symbol, n_frames, n_tokens, *more) -> int:
     T = np.ascontiguousarray(n_frames, np.int32)
     N = np.ascontiguousarray(n_tokens, np.int32)
-    n = int(getattr(_lib.load(), symbol)(_hp(T), _hp(N), T.size))
+    n = int(getattr(_lib.load(), symbol)(_hp(T), _hp(N), T.size, *more))
     if n < 0:
-        raise _lib.WflError(f"{symbol}: negative frame or token count")
+        raise _lib.WflError(f"{symbol}: negative frame or token count" + (f", or an argument out of range {more}" if more else ""))
     return n
 
 
@@ -93,6 +97,11 @@ def optional_workspace_bytes(n_frames, n_tokens) -> int:
 
 def filler_workspace_bytes(n_frames, n_tokens) -> int:
     return _workspace_bytes("wfl_align_filler_workspace_bytes", n_frames, n_tokens)
+
+
+def duration_prior_workspace_bytes(n_frames, n_tokens, max_frames) -> int:
+    """max_frames: D, the table's longest explicit duration (its rows have D + 1 columns), 1 .. MAX_PRIOR_FRAMES."""
+    return _workspace_bytes("wfl_align_duration_prior_workspace_bytes", n_frames, n_tokens, int(max_frames))
 
 
 def optional_posterior_workspace_bytes(n_frames, n_tokens) -> int:
@@ -291,12 +300,13 @@ class AlignBatch(NamedTuple):
     o_id: int
     opts: list = None     # per clip its tokens' optional flags; None (the field or an entry): no token may be skipped
     fills: list = None    # per clip its tokens' filler flags; None (the field or an entry): no token is a filler
+    durs: list = None     # per clip its tokens' rows of the duration table (-1: none); None: the searches without a duration prior
 
     @classmethod
-    def of(cls, lg, frames, alts, gaps, o_id, wins=None, mins=None, opts=None, fills=None):
+    def of(cls, lg, frames, alts, gaps, o_id, wins=None, mins=None, opts=None, fills=None, durs=None):
         none = [None] * len(frames)                       # (the clips' rows one after the other in `lg`)
         return cls(lg, list(frames), back_to_back(frames), list(alts), list(gaps), list(wins or none), list(mins or none), o_id,
-                   list(opts or none), list(fills) if fills is not None else None)
+                   list(opts or none), list(fills) if fills is not None else None, list(durs) if durs is not None else None)
 
     @property
     def windows(self):
@@ -322,7 +332,7 @@ class AlignBatch(NamedTuple):
         """The sub-batch of the clips `idx`, in that order, on the same logits."""
         idx = [int(b) for b in idx]
         fields = ("frames", "alts", "gaps", "wins", "mins") + (("opts",) if self.opts is not None else ()) \
-            + (("fills",) if self.fills is not None else ())
+            + (("fills",) if self.fills is not None else ()) + (("durs",) if self.durs is not None else ())
         return self._replace(f0=self.f0[idx], **{k: [getattr(self, k)[b] for b in idx] for k in fields})
 
     def pack(self, with_min) -> PackedClips:
@@ -366,19 +376,21 @@ _ENTRIES = {
     "wfl_align_optional_posterior": ("wfl_align_optional_posterior", True, False),
     "wfl_align_filler": ("wfl_align_filler", True, False),
     "wfl_align_filler_posterior": ("wfl_align_filler_posterior", True, False),
+    "wfl_align_duration_prior": ("wfl_align_duration_prior", True, False),
 }
 
 
-def _call(entry, logits, o_id, packed, middle, outputs, stream, temporaries=()):
+def _call(entry, logits, o_id, packed, middle, outputs, stream, temporaries=(), sized_by=()):
     """What the entries share after the packing: the workspace, the call on `stream` (default: the current one) and its check.  Every
     entry takes  logits .. token table, [windows], [minimum durations], gap table, clips, *middle, workspace, its bytes, *outputs,
     stream  (_ENTRIES; windows that were not packed go as a null pointer).  middle: a tensor goes as its pointer, anything else as
-    it is; temporaries: tensors made for this call alone, kept for the stream beside the workspace and the packed tables."""
+    it is; temporaries: tensors made for this call alone, kept for the stream beside the workspace and the packed tables; sized_by:
+    what the entry's workspace rule takes after the clip count (wfl_align_duration_prior: D)."""
     lib = _lib.load()
     sized_as, takes_win, takes_min = _ENTRIES[entry]
     nb, T, N, F0, K0, d_tc, d_gc, d_win, d_min = packed
     dev = logits.device
-    ws_n = _workspace_bytes(sized_as + "_workspace_bytes", T, N)
+    ws_n = _workspace_bytes(sized_as + "_workspace_bytes", T, N, *sized_by)
     ws = torch.empty(max(ws_n, 1), dtype=torch.uint8, device=dev)
     with torch.cuda.device(dev):
         st = stream if stream is not None else torch.cuda.current_stream(dev)
@@ -463,6 +475,87 @@ def viterbi_align_optional(logits, n_frames, token_classes, gap_classes, o_id, o
     skipped = torch.empty(max(ntok, 1), dtype=torch.int32, device=dev)
     _call("wfl_align_optional", logits, o_id, packed, (d_opt, lam), (ids, tok, score, skipped, status), stream, temporaries=(d_opt,))
     return ids, tok, score[:nb], status[:nb], skipped[:ntok]
+
+
+def _pack_durations(tok_rows, N):
+    """Per clip a list of table rows per token (ints; -1: the token has no prior), or None for a clip without any -> [max(tokens, 1)]
+    int32, rows as the token table's.  The values are not judged here: a row outside -1 .. n_rows - 1 is the kernel's
+    STATUS_BAD_CLASS for its clip."""
+    if len(tok_rows) != len(N):
+        raise ValueError("tok_rows needs one entry per clip (None: no token has a prior)")
+    out = np.full(max(int(N.sum()), 1), -1, np.int64)
+    k0 = 0
+    for d, n in zip(tok_rows, N):
+        if d is not None:
+            if any(isinstance(x, (bool, np.bool_)) or not isinstance(x, (int, np.integer)) for x in d):
+                raise ValueError("tok_rows are ints (rows of the duration table, -1 for none)")
+            d = np.asarray(d, np.int64).reshape(-1)
+            if len(d) != n:
+                raise ValueError(f"a clip with {n} tokens needs {n} table rows, got {len(d)}")
+            out[k0:k0 + n] = d
+        k0 += int(n)
+    if out.min() < -2 ** 31 or out.max() > 2 ** 31 - 1:
+        raise ValueError("tok_rows are int32")
+    return out.astype(np.int32)
+
+
+def upload_durations(tok_rows, n_tokens, device):
+    """viterbi_align_duration_prior's rows (per clip a list of ints per token, or None) packed and uploaded once -> [max(tokens, 1)]
+    int32 tensor on `device`, for its `tok_rows` argument.  n_tokens: tokens per clip (PackedClips.N)."""
+    return torch.from_numpy(_pack_durations(tok_rows, np.asarray(n_tokens, np.int32).reshape(-1))).to(device)
+
+
+def duration_rows(transcript, prior):
+    """The duration table's row of every transcript token (`postprocess.duration_prior`) -> [int] for viterbi_align_duration_prior's
+    tok_rows.  prior: durations.DurationPrior; names are the transcript's own tokens, i.e. output names, as min_frames_for's.  A token
+    the prior does not hold, or holds without any sample (`log_prob` null), gets -1: no prior."""
+    row = {name: i for i, name in enumerate(prior.phonemes) if prior.log_prob[i] is not None}
+    return [row.get(t, -1) for t in transcript]
+
+
+def viterbi_align_duration_prior(logits, n_frames, token_classes, gap_classes, o_id, tok_rows, table, frame_offsets=None, stream=None,
+                                 packed=None, windows=None):
+    """viterbi_align with a duration prior: an explicit-duration search in which a run of d frames of a token adds its row's L(d) to
+    the path's score (wfl_align_duration_prior).
+
+    tok_rows  per clip a list of ints per token -- the token's row of `table`, -1 for a token without prior -- or None for a clip
+              without any; or upload_durations(...) of such a list.  The rows travel beside `packed`, not in it
+    table     [rows, D + 1] float32 (numpy, or a CUDA tensor already on the device; durations.table): columns 0 .. D - 1 are
+              L(1) .. L(D), column D the tail, added once per frame past D.  Entries are finite or -inf (-inf forbids the duration),
+              never NaN or +inf; the tail is <= 0 or -inf.  1 <= D <= MAX_PRIOR_FRAMES
+    windows   as viterbi_align's.  With `packed`, the ones packed there.  A batch packed with `min_frames` is refused
+    -> (ids, tok, score, status): viterbi_align's four; the score is the path's sum of log posteriors plus its runs' L.
+    STATUS_INFEASIBLE: fewer frames than tokens, or the table (and the windows) forbid every path; STATUS_BAD_CLASS also for a row
+    outside -1 .. rows - 1."""
+    if packed is None:
+        packed = pack_clips(logits, n_frames, token_classes, gap_classes, frame_offsets, windows)
+    if packed.d_min is not None:
+        raise ValueError("viterbi_align_duration_prior has no minimum durations: this batch was packed with min_frames")
+    dev, rows, nb, ntok = logits.device, logits.shape[0], packed.nb, int(packed.N.sum())
+    if isinstance(table, torch.Tensor):
+        d_tab = table
+        if d_tab.device != dev or d_tab.dtype != torch.float32 or d_tab.dim() != 2 or not d_tab.is_contiguous():
+            raise ValueError("an uploaded duration table must be a contiguous [rows, D + 1] float32 tensor on the logits' device")
+    else:
+        tab = np.ascontiguousarray(table, np.float32)
+        if tab.ndim != 2:
+            raise ValueError("the duration table is [rows, D + 1]")
+        if np.isnan(tab).any() or np.isposinf(tab).any():
+            raise ValueError("duration table entries are finite or -inf")
+        d_tab = torch.from_numpy(tab if tab.size else np.zeros((1, max(tab.shape[1], 2)), np.float32)).to(dev)
+    n_rows, D = int(table.shape[0]), int(table.shape[1]) - 1
+    if not 1 <= D <= MAX_PRIOR_FRAMES:
+        raise ValueError(f"the duration table needs 2 to {MAX_PRIOR_FRAMES + 1} columns (D + 1), got {D + 1}")
+    d_dur = tok_rows if isinstance(tok_rows, torch.Tensor) else upload_durations(tok_rows, packed.N, dev)
+    if d_dur.device != dev or d_dur.dtype != torch.int32 or d_dur.dim() != 1 or d_dur.stride(0) != 1 or d_dur.shape[0] != max(ntok, 1):
+        raise ValueError("uploaded table rows must be upload_durations' [tokens] int32 tensor for this batch")
+    ids = torch.empty(rows, dtype=torch.int32, device=dev)
+    tok = torch.empty(rows, dtype=torch.int32, device=dev)
+    score = torch.empty(max(nb, 1), dtype=torch.float32, device=dev)
+    status = torch.empty(max(nb, 1), dtype=torch.int32, device=dev)
+    _call("wfl_align_duration_prior", logits, o_id, packed, (d_dur, d_tab, n_rows, D), (ids, tok, score, status), stream,
+          temporaries=(d_dur, d_tab), sized_by=(D,))
+    return ids, tok, score[:nb], status[:nb]
 
 
 def upload_filler(fillers, n_tokens, device):

@@ -421,11 +421,22 @@ class Labeler:
             self._bigram_cache[key] = PH.transition_table(PH.load(key[0]), self._decode_table, self.labels, switch_penalty, weight)
         return self._bigram_cache[key]
 
+    def _duration_prior(self, path, weight, lang_name):
+        """-> (durations.DurationPrior, its float32 table at `weight`) of the file `path` (absolute, or relative to the working
+        directory), checked against the frame clock and the label set's output names."""
+        from . import durations as DU
+        key = ("durations", os.path.abspath(path), float(weight), lang_name)
+        if key not in self._bigram_cache:
+            prior = DU.load(key[1])
+            DU.check(prior, self._names_for(lang_name)[1], frame_duration, path=str(path))
+            self._bigram_cache[key] = (prior, DU.table(prior, weight))
+        return self._bigram_cache[key]
+
     def label_files(self, audio_paths, lang_id=None, confidence_threshold=0.0, verbose=True, align=None, align_scores=None,
                     decode=None, switch_penalty=None, decode_scores=None, phoneme_bigram=None, bigram_weight=None, align_draft=None,
                     draft_tolerance=None, align_edits=None, align_insertions=None, min_duration=None, duration_scores=None,
                     optional_tokens=None, skip_penalty=None, optional_scores=None, filler_token=None, filler_penalty=None,
-                    filler_scores=None, bigram_scores=None):
+                    filler_scores=None, duration_prior=None, duration_prior_weight=None, bigram_scores=None):
         """-> list (per file) of [(start_s, end_s, phoneme)] after merge + forced alignment; with align_scores, duration_scores,
         decode_scores or bigram_scores, (that list, scores); with align_edits the tuple goes on with one more list, edits, and with
         align_insertions it ends with one more, insertions; with optional_tokens it ends with the list skipped; with a filler_token
@@ -525,14 +536,23 @@ class Labeler:
         of a file that was aligned, from a forward-backward pass over the lattice the file was searched on -- the filler lattice
         (align.filler_posteriors, the same flags and penalty) for a file with a filler, wfl_align_posterior's for one without, with
         one line -- and filler_scores[i] one align.FillerScore per filler: the posterior that its span's frames belong to it and the
-        mean shift and spread of both its ends (None for a file that was not aligned or not scored)."""
+        mean shift and spread of both its ends (None for a file that was not aligned or not scored).
+
+        duration_prior (with align "viterbi" only; None: config postprocess.duration_prior, else none): a phoneme_durations.json
+        (python -m wfl_asr_amd.durations): a file with a transcript is aligned by the explicit-duration search
+        (align.viterbi_align_duration_prior), in which a run of d frames of a token adds duration_prior_weight (>= 0; None: config
+        postprocess.duration_prior_weight, else 1.0 -- a value to start from, not a measured optimum) times the log probability the
+        prior gives d frames of that phoneme; the row is the one of the token's output name as the transcript spells it, a token the
+        prior does not hold has none.  A file the prior leaves no path for falls back, with a line, to the plain alignment of the same
+        transcript.  A prior counted on another frame duration, or one that holds a phoneme that is no output name of the label set,
+        is refused by name; align_draft, min_duration, optional_tokens, filler_token and the scoring options beside it are refused."""
         opts = self.options(align=align, align_scores=align_scores, decode=decode, switch_penalty=switch_penalty,
                             decode_scores=decode_scores, phoneme_bigram=phoneme_bigram, bigram_weight=bigram_weight,
                             bigram_scores=bigram_scores, align_draft=align_draft, draft_tolerance=draft_tolerance,
                             align_edits=align_edits, align_insertions=align_insertions, min_duration=min_duration,
                             duration_scores=duration_scores, optional_tokens=optional_tokens, skip_penalty=skip_penalty,
                             optional_scores=optional_scores, filler_token=filler_token, filler_penalty=filler_penalty,
-                            filler_scores=filler_scores)
+                            filler_scores=filler_scores, duration_prior=duration_prior, duration_prior_weight=duration_prior_weight)
         edits = {} if opts.align_edits else None
         insertions = {} if opts.align_insertions else None
         skipped = {} if opts.optional_tokens is not None else None
@@ -573,6 +593,8 @@ class Labeler:
         if unknown:
             raise ValueError(f"optional_tokens: {', '.join(repr(n) for n in unknown)} is no output name of this model's label set")
         trans = self._bigram_table(opts.phoneme_bigram, opts.switch_penalty, opts.bigram_weight) if opts.phoneme_bigram else None
+        prior = (self._duration_prior(opts.duration_prior, opts.duration_prior_weight, self._lang_name(lang_id))
+                 if opts.duration_prior else None)
         if opts.decode == "viterbi" and int(self.config["postprocess"].get("median_filter", 0)) > 1:
             print("decode: viterbi -- postprocess.median_filter is not applied (the switch penalty takes its place)")
         if lang_id is not None and self.lang2id and lang_id > max(self.lang2id.values()):
@@ -612,7 +634,7 @@ class Labeler:
         if with_t:
             fscores = {} if filler_scores is not None else None       # (by the file's place among with_t)
             got = self._label_viterbi(paths(with_t), [forced[fi] for fi in with_t], [drafts[fi] for fi in with_t], opts, lang_id,
-                                      confidence_threshold, verbose, fscores)
+                                      confidence_threshold, verbose, fscores, prior)
             for j, rows in (fscores or {}).items():
                 filler_scores[with_t[j]] = rows
             for fi, rec in zip(with_t, got):
@@ -895,7 +917,7 @@ class Labeler:
                 n_frames += int(frames[b])
         return total, total_logz, total_lse, n_frames, skipped
 
-    def _label_viterbi(self, audio_paths, transcripts, drafts, opts, lang_id, threshold, verbose, filler_scores=None):
+    def _label_viterbi(self, audio_paths, transcripts, drafts, opts, lang_id, threshold, verbose, filler_scores=None, prior=None):
         """Files with a transcript, align="viterbi" -> one ViterbiLabel per file.  Their chunks are forwarded with logits (kept on
         the device); the free decode of the same forward gives the greedy result, which the pause rule at the ends needs and which a
         file falls back to (with a message) when its transcript cannot be aligned.  Each file's chunks' valid logits rows are
@@ -903,7 +925,8 @@ class Labeler:
         that goes through the stages -- _greedy_and_plans, _clip_constraints, _search, _score, _clip_label -- and only ids / tok /
         score / status and the scoring calls' small tables come back to the host.  drafts: per file its draft segments or None
         (opts.align_draft; the transcript is then the draft's labels).  filler_scores (opts.filler_scores): a dict that takes
-        {file index: [FillerScore]} for the files that were aligned and scored."""
+        {file index: [FillerScore]} for the files that were aligned and scored.  prior (opts.duration_prior): _duration_prior's
+        pair; the search is then the explicit-duration one."""
         lang_name = self._lang_name(lang_id)
         drafts = drafts if drafts is not None else [None] * len(audio_paths)
         sub_pairs = sub_out = None
@@ -926,8 +949,9 @@ class Labeler:
                 wins, mins = _clip_constraints(paths, frames, chunks, [transcripts[fi] for fi in run],
                                                [drafts[fi] for fi in run], opts, flags)
                 batch = AL.AlignBatch.of(lg, frames, [plans[fi] for fi in run], [AL.gap_classes(self.labels, transcripts[fi]) for fi in run],
-                                         self.labels.index("O"), wins, mins, flags, fills)
-                found = _search(batch, paths, opts)
+                                         self.labels.index("O"), wins, mins, flags, fills,
+                                         [AL.duration_rows(transcripts[fi], prior[0]) for fi in run] if prior is not None else None)
+                found = _search(batch, paths, opts, prior[1] if prior is not None else None)
                 scored = _score(found, opts, sub_pairs)
                 for b, fi in enumerate(run):
                     got = self._clip_label(found, scored, b, chunks[b], transcripts[fi], drafts[fi], free_segs[fi], opts, sub_out)
@@ -1105,10 +1129,27 @@ def _clip_constraints(paths, frames, chunks, transcripts, drafts, opts, flags=No
     return wins, mins
 
 
-def _search(batch, paths, opts) -> _Searched:
+def _search(batch, paths, opts, dur_table=None) -> _Searched:
     """Stage 3: the search over the whole batch, packed here when scores or edits are to run on the same tables (the durations only
     with opts.duration_scores; without, they go to viterbi_align beside a PackedClips that has none), then the safety net: a clip
-    the kernel found no path for inside its constraints is searched again, first without its durations, then without its windows."""
+    the kernel found no path for inside its constraints is searched again, first without its durations, then without its windows.
+    dur_table (opts.duration_prior): the prior's table; the batch's clips (their rows in batch.durs) go through the explicit-duration
+    search, and a clip it has no path for is aligned again by the plain search, with one line."""
+    if batch.durs is not None:                            # (the options refuse drafts, durations, optional tokens, fillers and scores
+        d_ids, d_tok, d_score, d_st = AL.viterbi_align_duration_prior(*batch.args(), batch.durs, dur_table)       # beside a prior)
+        status = d_st.cpu().numpy()
+        again = [b for b in range(len(paths)) if status[b] != AL.STATUS_OK]
+        if again:
+            for b in again:
+                print(f"{paths[b]}: {DURATION_PRIOR_INFEASIBLE}")
+            sub = batch.select(again)
+            r_ids, r_tok, r_score, r_st = AL.viterbi_align(*sub.args(), frame_offsets=sub.f0)
+            for j, b in enumerate(again):
+                rows_b = slice(int(batch.f0[b]), int(batch.f0[b]) + batch.frames[b])
+                d_ids[rows_b], d_tok[rows_b] = r_ids[rows_b], r_tok[rows_b]
+                d_score[b], d_st[b] = r_score[j], r_st[j]
+            status = d_st.cpu().numpy()
+        return _Searched(batch, paths, d_ids.cpu().numpy(), d_tok.cpu().numpy(), status, d_tok, d_score, None)
     scoring = opts.align_scores or opts.align_edits or opts.align_insertions
     packed = batch.pack(opts.duration_scores) if scoring or (opts.duration_scores and batch.min_frames is not None) else None
     d_skip = None
@@ -1273,6 +1314,8 @@ def _clip_lse(lg, starts, ends):
 
 MIN_DURATION_INFEASIBLE = ("no path gives every token its minimum duration (postprocess.min_duration: too many tokens for the frames, or "
                            "for the draft's windows); aligning the transcript without minimum durations")
+DURATION_PRIOR_INFEASIBLE = ("no path of finite score under the duration prior (postprocess.duration_prior: the table forbids every "
+                             "segmentation of these frames, or the search refused the clip); aligning the transcript without the prior")
 DURATION_SCORES_PLAIN = ("scored without minimum durations (postprocess.duration_scores: the file was searched without them, and a "
                          "score speaks of the lattice its search ran on)")
 FILLER_SCORES_PLAIN = ("scored by wfl_align_posterior (postprocess.filler_scores: the transcript has no filler, so the file was searched "
@@ -1522,7 +1565,7 @@ def infer_audio(audio_path, config_path="config.yaml", checkpoint_path="best_mod
                 align_scores=None, decode=None, switch_penalty=None, decode_scores=None, phoneme_bigram=None, bigram_weight=None,
                 align_draft=None, draft_tolerance=None, align_edits=None, align_insertions=None, min_duration=None,
                 duration_scores=None, optional_tokens=None, skip_penalty=None, optional_scores=None, filler_token=None,
-                filler_penalty=None, filler_scores=None, bigram_scores=None):
+                filler_penalty=None, filler_scores=None, duration_prior=None, duration_prior_weight=None, bigram_scores=None):
     """align: "greedy" | "viterbi" | None (config postprocess.align, else greedy): how a `{audio}.txt` transcript is aligned
     (Labeler.label_files).  align_scores (viterbi only; None: config postprocess.align_scores): also write `{stem}.scores.tsv`
     beside the .lab when the file was Viterbi-aligned (format_scores_tsv).  decode: "argmax" | "viterbi" | None (config
@@ -1553,13 +1596,15 @@ def infer_audio(audio_path, config_path="config.yaml", checkpoint_path="best_mod
     filler_token only; None: config postprocess.filler_scores): also write `{stem}.scores.tsv`, one row per transcript token summed
     over the lattice the file was searched on, and `{stem}.filler_scores.tsv`, one row per filler with the posterior of its span and
     the mean shift and spread of both its ends (align.filler_posteriors, align.format_filler_scores_tsv); the .lab and
-    `{stem}.fillers.tsv` are what they are without it."""
+    `{stem}.fillers.tsv` are what they are without it.  duration_prior / duration_prior_weight (align viterbi only; None: config
+    postprocess.duration_prior / postprocess.duration_prior_weight): the phoneme duration prior of the explicit-duration search and
+    what its log probabilities are multiplied by (Labeler.label_files)."""
     given = dict(align=align, align_scores=align_scores, decode=decode, switch_penalty=switch_penalty, decode_scores=decode_scores,
                  phoneme_bigram=phoneme_bigram, bigram_weight=bigram_weight, bigram_scores=bigram_scores, align_draft=align_draft,
                  draft_tolerance=draft_tolerance, align_edits=align_edits, align_insertions=align_insertions, min_duration=min_duration,
                  duration_scores=duration_scores, optional_tokens=optional_tokens, skip_penalty=skip_penalty,
                  optional_scores=optional_scores, filler_token=filler_token, filler_penalty=filler_penalty,
-                 filler_scores=filler_scores)
+                 filler_scores=filler_scores, duration_prior=duration_prior, duration_prior_weight=duration_prior_weight)
     _refuse_before_load(config_path, **given)
     lab = _labeler(config_path, checkpoint_path, device)
     opts = lab.options(**given)
@@ -1599,13 +1644,13 @@ def infer_folder(folder_path: str, config_path: str = "config.yaml", checkpoint_
                  decode_scores=None, phoneme_bigram=None, bigram_weight=None, align_draft=None, draft_tolerance=None,
                  align_edits=None, align_insertions=None, min_duration=None, duration_scores=None, optional_tokens=None,
                  skip_penalty=None, optional_scores=None, filler_token=None, filler_penalty=None, filler_scores=None,
-                 bigram_scores=None):
+                 duration_prior=None, duration_prior_weight=None, bigram_scores=None):
     given = dict(align=align, align_scores=align_scores, decode=decode, switch_penalty=switch_penalty, decode_scores=decode_scores,
                  phoneme_bigram=phoneme_bigram, bigram_weight=bigram_weight, bigram_scores=bigram_scores, align_draft=align_draft,
                  draft_tolerance=draft_tolerance, align_edits=align_edits, align_insertions=align_insertions, min_duration=min_duration,
                  duration_scores=duration_scores, optional_tokens=optional_tokens, skip_penalty=skip_penalty,
                  optional_scores=optional_scores, filler_token=filler_token, filler_penalty=filler_penalty,
-                 filler_scores=filler_scores)
+                 filler_scores=filler_scores, duration_prior=duration_prior, duration_prior_weight=duration_prior_weight)
     _refuse_before_load(config_path, **given)
     wav_files = sorted(f for f in os.listdir(folder_path) if f.lower().endswith(".wav"))
     os.makedirs(output_dir, exist_ok=True)
@@ -1785,10 +1830,17 @@ def main(argv=None):
                        "posterior that its span belongs to it and the mean shift and spread of its start and of its end; for a "
                        "folder also alignment_scores.tsv and filler_scores.tsv, the lowest posterior first. Default: config "
                        "postprocess.filler_scores, else off.")
+    @click.option("--duration-prior", "duration_prior", type=str, default=None,
+                  help="With --align viterbi: a phoneme_durations.json (python -m wfl_asr_amd.durations); a run of d frames of a "
+                       "transcript token then adds duration_prior_weight * log P(d | phoneme) to the path's score, in an "
+                       "explicit-duration search on the GPU. Default: config postprocess.duration_prior, else none.")
+    @click.option("--duration-prior-weight", "duration_prior_weight", type=float, default=None,
+                  help="With --duration-prior: what the prior's log probabilities are multiplied by (>= 0). Default: config "
+                       "postprocess.duration_prior_weight, else 1.0 (a value to start from, not a measured optimum).")
     def cli(path, checkpoint, config, output, lang_id, sample, top_k, top_p, temperature, device, confidence_threshold, align,
             align_scores, decode, switch_penalty, decode_scores, phoneme_bigram, bigram_weight, bigram_scores, align_draft,
             draft_tolerance, align_edits, align_insertions, min_duration, duration_scores, optional_tokens, skip_penalty,
-            optional_scores, filler_token, filler_penalty, filler_scores):
+            optional_scores, filler_token, filler_penalty, filler_scores, duration_prior, duration_prior_weight):
         if switch_penalty is not None and not switch_penalty >= 0.0:
             raise click.UsageError("--switch-penalty must be >= 0 (nats)")
         if sample:
@@ -1824,7 +1876,8 @@ def main(argv=None):
                            align_edits=align_edits, align_insertions=align_insertions,
                            min_duration=parse_min_duration(min_duration), duration_scores=duration_scores,
                            optional_tokens=list(optional_tokens) or None, skip_penalty=skip_penalty, optional_scores=optional_scores,
-                           filler_token=filler_token, filler_penalty=filler_penalty, filler_scores=filler_scores)
+                           filler_token=filler_token, filler_penalty=filler_penalty, filler_scores=filler_scores,
+                           duration_prior=duration_prior, duration_prior_weight=duration_prior_weight)
         except ValueError as err:
             raise click.UsageError(str(err))
         output_path = inf_path if output == "." else output
@@ -1849,7 +1902,10 @@ def main(argv=None):
                   optional_tokens=opts.optional_tokens, skip_penalty=opts.skip_penalty if opts.optional_tokens is not None else None,
                   optional_scores=opts.optional_scores,
                   filler_token=opts.filler_token, filler_penalty=opts.filler_penalty if opts.filler_token is not None else None,
-                  filler_scores=opts.filler_scores)
+                  filler_scores=opts.filler_scores,
+                  # the prior travels as the bigram does: an empty path for "none", a weight only beside a prior
+                  duration_prior=opts.duration_prior or "",
+                  duration_prior_weight=opts.duration_prior_weight if opts.duration_prior else None)
         if inf_path.is_dir():
             infer_folder(folder_path=str(inf_path), output_dir=str(output_path), **kw)
         else:

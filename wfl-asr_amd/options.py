@@ -51,6 +51,17 @@ infer_folder (before any model is loaded) and the CLI all call `resolve` and car
   filler_scores   off      33. a bool (true / false; no number, no string)
                            34. needs a filler_token (it scores the filler lattice of that search: per filler the posterior of its
                                span and the spread of both its ends; without a filler_token align_scores is the option to ask for)
+  duration_prior  none    35. PATH of a phoneme_durations.json (python -m wfl_asr_amd.durations); needs align viterbi (the prior is a
+                               term of that search's path score)
+  duration_prior_weight 1.0  36. when given, a finite number >= 0 (no bool, no NaN): the table is weight * log P.  The default of 1.0 is
+                               a value to start from, not a measured optimum
+                           37. when given, needs a duration_prior (it scales that prior)
+                           38. align_draft, min_duration, optional_tokens, filler_token, align_scores, align_edits,
+                               align_insertions, duration_scores, optional_scores and filler_scores beside a duration_prior are
+                               refused (DURATION_PRIOR_ERROR): their lattices carry no duration term, and a search or a score must
+                               speak of one lattice
+                           (39. with the model known, Labeler.label_files: a file counted on another frame duration, or one that
+                               holds a phoneme that is no output name of the label set, is refused by name, durations.check)
 """
 from __future__ import annotations
 
@@ -87,6 +98,13 @@ FILLER_TOKEN_ERROR = ("filler_token cannot be combined with align_draft, min_dur
 
 FILLER_SCORES_ERROR = ("filler_scores needs a filler_token (postprocess.filler_token, --filler-token): it scores the filler lattice of "
                        "that search; without a filler_token align_scores is the option to ask for")
+
+
+DEFAULT_DURATION_PRIOR_WEIGHT = 1.0   # a value to start from, not a measured optimum
+DURATION_PRIOR_ERROR = ("duration_prior cannot be combined with align_draft, min_duration, optional_tokens, filler_token, align_scores, "
+                        "align_edits, align_insertions, duration_scores, optional_scores or filler_scores: their lattices carry no "
+                        "duration term, and a search or a score must speak of one lattice; drop postprocess.duration_prior "
+                        "(--duration-prior) for that run")
 
 
 def _filler_token(given):
@@ -204,7 +222,9 @@ class PostOptions(_SearchOptions):
         optional_scores  False  score every alignment searched with optional_tokens, over the skip lattice
         filler_token     None   the transcript token that matches anything
         filler_penalty   1.0    nats a filler pays per frame of its run (also stands for "not given")
-        filler_scores    False  score every alignment searched with a filler_token, over the filler lattice"""
+        filler_scores    False  score every alignment searched with a filler_token, over the filler lattice
+        duration_prior   None   path of a phoneme_durations.json: the duration prior of the explicit-duration search
+        duration_prior_weight  1.0  what the prior's log probabilities are multiplied by (also stands for "not given")"""
     align_draft: Optional[str] = None
     draft_tolerance: float = DEFAULT_DRAFT_TOLERANCE
     align_edits: bool = False
@@ -217,10 +237,13 @@ class PostOptions(_SearchOptions):
     filler_token: Optional[str] = None
     filler_penalty: float = DEFAULT_FILLER_PENALTY
     filler_scores: bool = False
+    duration_prior: Optional[str] = None
+    duration_prior_weight: float = DEFAULT_DURATION_PRIOR_WEIGHT
 
     def __new__(cls, *args, align_draft=None, draft_tolerance=DEFAULT_DRAFT_TOLERANCE, align_edits=False, align_insertions=False,
                 min_duration=None, duration_scores=False, optional_tokens=None, skip_penalty=0.0, optional_scores=False,
-                filler_token=None, filler_penalty=DEFAULT_FILLER_PENALTY, filler_scores=False, **kw):
+                filler_token=None, filler_penalty=DEFAULT_FILLER_PENALTY, filler_scores=False, duration_prior=None,
+                duration_prior_weight=DEFAULT_DURATION_PRIOR_WEIGHT, **kw):
         self = super().__new__(cls, *args, **kw)
         object.__setattr__(self, "align_draft", align_draft)
         object.__setattr__(self, "draft_tolerance", draft_tolerance)
@@ -234,16 +257,19 @@ class PostOptions(_SearchOptions):
         object.__setattr__(self, "filler_token", filler_token)
         object.__setattr__(self, "filler_penalty", filler_penalty)
         object.__setattr__(self, "filler_scores", filler_scores)
+        object.__setattr__(self, "duration_prior", duration_prior)
+        object.__setattr__(self, "duration_prior_weight", duration_prior_weight)
         return self
 
     def __setattr__(self, name, value):
         raise AttributeError(f"PostOptions is read-only: cannot set {name!r}")
 
     _KEYWORD = ("align_draft", "draft_tolerance", "align_edits", "align_insertions", "min_duration", "duration_scores",
-                "optional_tokens", "skip_penalty", "filler_scores", "optional_scores", "filler_token", "filler_penalty")
-    # (filler_scores, the latest, stands in front of optional_scores: the record's last fields are the filler's own two)
-    _KEYWORD_DEFAULTS = (None, DEFAULT_DRAFT_TOLERANCE, False, False, None, False, None, 0.0, False, False, None,
-                         DEFAULT_FILLER_PENALTY)
+                "optional_tokens", "skip_penalty", "duration_prior", "duration_prior_weight", "filler_scores", "optional_scores",
+                "filler_token", "filler_penalty")
+    # (the later options stand in front of optional_scores: the record's last fields are the filler's own two)
+    _KEYWORD_DEFAULTS = (None, DEFAULT_DRAFT_TOLERANCE, False, False, None, False, None, 0.0, None, DEFAULT_DURATION_PRIOR_WEIGHT,
+                         False, False, None, DEFAULT_FILLER_PENALTY)
 
     def _draft(self):
         return self.align_draft, self.draft_tolerance
@@ -259,11 +285,13 @@ class PostOptions(_SearchOptions):
     @classmethod
     def _make(cls, iterable, align_draft=None, draft_tolerance=DEFAULT_DRAFT_TOLERANCE, align_edits=False, align_insertions=False,
               min_duration=None, duration_scores=False, optional_tokens=None, skip_penalty=0.0, optional_scores=False,
-              filler_token=None, filler_penalty=DEFAULT_FILLER_PENALTY, filler_scores=False):
+              filler_token=None, filler_penalty=DEFAULT_FILLER_PENALTY, filler_scores=False, duration_prior=None,
+              duration_prior_weight=DEFAULT_DURATION_PRIOR_WEIGHT):
         return cls(*iterable, align_draft=align_draft, draft_tolerance=draft_tolerance, align_edits=align_edits,
                    align_insertions=align_insertions, min_duration=min_duration, duration_scores=duration_scores,
                    optional_tokens=optional_tokens, skip_penalty=skip_penalty, optional_scores=optional_scores,
-                   filler_token=filler_token, filler_penalty=filler_penalty, filler_scores=filler_scores)
+                   filler_token=filler_token, filler_penalty=filler_penalty, filler_scores=filler_scores,
+                   duration_prior=duration_prior, duration_prior_weight=duration_prior_weight)
 
     def _replace(self, **kw):
         later = {k: kw.pop(k, getattr(self, k)) for k in self._KEYWORD}
@@ -300,7 +328,8 @@ def _number_ge0(x):
 def resolve(post, *, align=None, align_scores=None, decode=None, switch_penalty=None, decode_scores=None, phoneme_bigram=None,
             bigram_weight=None, bigram_scores=None, align_draft=None, draft_tolerance=None, align_edits=None,
             align_insertions=None, min_duration=None, duration_scores=None, optional_tokens=None, skip_penalty=None,
-            optional_scores=None, filler_token=None, filler_penalty=None, filler_scores=None) -> PostOptions:
+            optional_scores=None, filler_token=None, filler_penalty=None, filler_scores=None, duration_prior=None,
+            duration_prior_weight=None) -> PostOptions:
     """post: the config's `postprocess` mapping (None: {}).  Per option the argument wins; None leaves it to `post[<option>]`, and a
     key that is absent (or None) to the default.  -> PostOptions, or ValueError for the first broken rule of the module's table."""
     post = post or {}
@@ -413,8 +442,23 @@ def resolve(post, *, align=None, align_scores=None, decode=None, switch_penalty=
         raise ValueError(f"filler_scores must be true or false, got {filler_scores!r}")
     if filler_scores and filler_token is None:
         raise ValueError(FILLER_SCORES_ERROR)
+    duration_prior = pick("duration_prior", duration_prior)
+    duration_prior = str(duration_prior) if duration_prior else None
+    if duration_prior and align != "viterbi":
+        raise ValueError("duration_prior needs align='viterbi' (postprocess.align: viterbi): the prior is a term of the Viterbi search's "
+                         "path score, the greedy match has none")
+    given = pick("duration_prior_weight", duration_prior_weight)
+    duration_prior_weight = DEFAULT_DURATION_PRIOR_WEIGHT if given is None else _number_ge0(given)
+    if duration_prior_weight is None or duration_prior_weight == float("inf"):
+        raise ValueError(f"duration_prior_weight must be a finite number >= 0, got {given!r}")
+    if given is not None and not duration_prior:
+        raise ValueError("duration_prior_weight needs a duration_prior (postprocess.duration_prior): it scales that prior")
+    if duration_prior and (align_draft or min_duration is not None or optional_tokens is not None or filler_token is not None
+                           or align_scores or align_edits or align_insertions or duration_scores or optional_scores or filler_scores):
+        raise ValueError(DURATION_PRIOR_ERROR)
     return PostOptions(align, align_scores, decode, switch_penalty, decode_scores, phoneme_bigram, bigram_weight, bigram_scores,
                        align_draft=align_draft, draft_tolerance=draft_tolerance, align_edits=align_edits,
                        align_insertions=align_insertions, min_duration=min_duration, duration_scores=duration_scores,
                        optional_tokens=optional_tokens, skip_penalty=skip_penalty, optional_scores=optional_scores,
-                       filler_token=filler_token, filler_penalty=filler_penalty, filler_scores=filler_scores)
+                       filler_token=filler_token, filler_penalty=filler_penalty, filler_scores=filler_scores,
+                       duration_prior=duration_prior, duration_prior_weight=duration_prior_weight)
