@@ -210,6 +210,62 @@ int32_t wfl_op_gemm_ln(const void* A, int64_t lda, const void* W, int32_t M, int
 int32_t wfl_op_attention(const void* QK, int64_t ldqk, int64_t lead, const void* V, int64_t ldv, void* O, int64_t ldo, int32_t B,
                          int32_t T, int32_t P, int32_t heads, int32_t d, void* stream);
 
+/* The same attention with every optional field of csrc/common.h's AttnArgs passed through (null = absent):
+ *   bias [heads][2T-1] fp32 + gate [B][heads][T] fp32   WavLM's gated relative position bias (HF modeling_wavlm.py:167-180), in log2 units:
+ *                                                       score(q, k) += gate[b][h][q] * bias[h][k - q + T - 1]; head_dim 32 / 64
+ *   clip_T [B]                                          valid frames per clip: keys and queries >= clip_T[b] do not exist, their rows of O
+ *                                                       are not written; bias and gate stay laid out for the batch-wide T
+ *   QK_lo, V_lo (both or neither)                       `model.precision: high`: the operands' low halves, same layout; head_dim 32 / 64
+ *                                                       (with or without bias), 128, 256
+ *   O_lo                                                the context's low half, bf16(o - O)
+ *   O8 (+ O8_lo), ldo8, o8_scale, status                instead of O: e4m3(o * o8_scale) bytes (+ e4m3(16 (o * o8_scale - hi))); an element
+ *                                                       that saturates is stored as +-448 and ORs 2 into *status; head_dim 64, no bias,
+ *                                                       no QK_lo / V_lo / O_lo
+ * A combination attention.hip has no kernel for is an error status: nothing is launched. */
+int32_t wfl_op_attention_ex(const void* QK, const void* QK_lo, int64_t ldqk, int64_t lead, const void* V, const void* V_lo, int64_t ldv,
+                            void* O, void* O_lo, int64_t ldo, int32_t B, int32_t T, int32_t P, int32_t heads, int32_t d, const float* bias,
+                            const float* gate, const int32_t* clip_T, void* O8, void* O8_lo, int64_t ldo8, float o8_scale, int32_t* status,
+                            void* stream);
+
+/* WavLM's relative position table (HF modeling_wavlm.py:243-271, gathered once per forward):
+ *   table[h][delta + T - 1] = rel_emb[bucket_of_delta[delta + max_t - 1]][h],  delta = key - query in [-(T-1), T-1];  T <= max_t.
+ * rel_emb [buckets][heads] fp32, bucket_of_delta [2 max_t - 1] int32, table [heads][2T-1] fp32. */
+int32_t wfl_op_relpos_table(const float* rel_emb, const int32_t* bucket_of_delta, int32_t max_t, int32_t heads, int32_t T, float* table,
+                            void* stream);
+
+/* The gate of that bias (HF modeling_wavlm.py:167-180): with (ga, gb) = sigmoid((w8 x_head + b8).view(2, 4).sum(-1)),
+ *   gate[b][h][t] = ga * (gb * cst[h] - 1) + 2.
+ * x (+ x_lo when given) bf16 frame rows, head h at column h * hd; w8 [8][hd], b8 [8], cst [heads] fp32; hd % 8 == 0, hd <= 128. */
+int32_t wfl_op_relpos_gate(const void* x, const void* x_lo, int64_t ldx, int64_t lead, int32_t B, int32_t P, int32_t T, int32_t heads,
+                           int32_t hd, const float* w8, const float* b8, const float* cst, float* gate, void* stream);
+
+/* Frame rows x [R][d] -> xg [groups][R][64]: channels g * cpg .. + cpg of every valid frame (t < T, and < clip_T[b] when given), zero in
+ * the padding channels and in every other row: the positional conv's operand.  cpg % 8 == 0, cpg <= 64, groups * cpg == d. */
+int32_t wfl_op_regroup(const void* x, int32_t d, int32_t groups, int32_t cpg, int64_t R, int64_t lead, int32_t B, int32_t P, int32_t T,
+                       const int32_t* clip_T, void* xg, void* stream);
+
+/* WavLM's positional convolution on regrouped rows (csrc/posconv.hip; HF modeling_wavlm.py:48-90):
+ *   out = res (+ res_lo) + gelu( grouped conv1d(x, taps, padding taps / 2)[..., :-1] + bias ),  out_lo = bf16(out - bf16(out)) when given.
+ * w [groups][64][ldw] bf16, element (o, tap * 64 + c), zero beyond cpg in o and c -- all 64 rows of a group are read; bias [groups][64] fp32;
+ * res / out rows of `ld` channels, group g at column g * cpg.  groups <= 16, cpg % 8 == 0, taps even in 4 .. 128, ldw >= 64 taps,
+ * lead >= taps / 2 and at least taps / 2 zero rows between clips.  A shape the kernel does not take is an error status. */
+int32_t wfl_op_posconv(const void* xg, int64_t R, int64_t lead, int32_t B, int32_t P, int32_t T, int32_t groups, int32_t cpg, int32_t taps,
+                       const void* w, int64_t ldw, const float* bias, const void* res, const void* res_lo, void* out, void* out_lo,
+                       int64_t ld, const int32_t* clip_T, void* stream);
+
+/* LayerNorm with everything csrc/norm.hip's launcher takes: input and output as bf16 pairs (x_lo, y_lo: optional), statistics over the
+ * first n_div channels (0: C; the columns beyond carry zeros and gamma = beta = 0), exact-erf GELU after the affine (gelu != 0), per-clip
+ * frame counts (rows t >= clip_T[b] are left alone).  y may be x. */
+int32_t wfl_op_layernorm_act(const void* x, const void* x_lo, int64_t ldx, void* y, void* y_lo, int64_t ldy, const float* gamma,
+                             const float* beta, float eps, int64_t lead, int32_t B, int32_t P, int32_t T, int32_t C, int32_t n_div,
+                             int32_t gelu, const int32_t* clip_T, void* stream);
+
+/* y1 = LN1(x), y2 = LN2(y1) in one pass over the rows, bit for bit what two wfl_op_layernorm_act launches write.  y2 may be x; y1 may
+ * be neither x nor y2. */
+int32_t wfl_op_layernorm_pair(const void* x, const void* x_lo, void* y1, void* y1_lo, void* y2, void* y2_lo, int64_t ld, const float* gamma1,
+                              const float* beta1, const float* gamma2, const float* beta2, float eps, int64_t lead, int32_t B, int32_t P,
+                              int32_t T, int32_t C, int32_t n_div, const int32_t* clip_T, void* stream);
+
 /* fp8 x fp8 GEMM on the block-scaled MFMA (csrc/gemm_mx.hip, round 4; the encoder GEMMs of an fp8-weight model, HF modeling_whisper.py:
  * 309-354, 391-407 via /root/reference/model.py:155-156):
  *   C[row(b,t)][n] = res + alpha * act( w_scale[n] * sa(m) * sum_k a(m, k) W8[n][k] + bias[n] )

@@ -88,3 +88,53 @@ def tag_decide(logits, thr, o_id):
     mp = torch.empty(rows, dtype=torch.float32, device=logits.device)
     _lib.check(lib().wfl_op_tag_decide(ptr(logits), Cn, rows, Cn, float(thr), o_id, ptr(ids), ptr(arg), ptr(mp), stream()), "wfl_op_tag_decide")
     return ids, arg, mp
+
+
+def _i32(v):
+    """list of ints -> int32 device tensor (None stays None)."""
+    return None if v is None else torch.tensor(list(v), dtype=torch.int32, device="cuda")
+
+
+def attention_ex(QK, ldqk, lead, V, v_off, ldv, O, ldo, B, T, P, heads, d, QK_lo=None, V_lo=None, O_lo=None, bias=None, gate=None,
+                 clip_T=None, O8=None, O8_lo=None, ldo8=0, o8_scale=1.0, status=None, check=True):
+    """wfl_op_attention_ex; clip_T an int32 device tensor.  -> the status code (check: raise on an error status)."""
+    rc = lib().wfl_op_attention_ex(ptr(QK), ptr(QK_lo), ldqk, lead, ptr(V, v_off), ptr(V_lo, v_off) if V_lo is not None else ptr(None), ldv,
+                                   ptr(O), ptr(O_lo), ldo, B, T, P, heads, d, ptr(bias), ptr(gate), ptr(clip_T), ptr(O8), ptr(O8_lo), ldo8,
+                                   float(o8_scale), ptr(status), stream())
+    if check:
+        _lib.check(rc, "wfl_op_attention_ex")
+    return rc
+
+
+def relpos_table(rel_emb, bucket_of_delta, max_t, heads, T, table, check=True):
+    rc = lib().wfl_op_relpos_table(ptr(rel_emb), ptr(bucket_of_delta), max_t, heads, T, ptr(table), stream())
+    if check:
+        _lib.check(rc, "wfl_op_relpos_table")
+    return rc
+
+
+def relpos_gate(x, x_lo, ldx, lead, B, P, T, heads, hd, w8, b8, cst, gate):
+    _lib.check(lib().wfl_op_relpos_gate(ptr(x), ptr(x_lo), ldx, lead, B, P, T, heads, hd, ptr(w8), ptr(b8), ptr(cst), ptr(gate), stream()),
+               "wfl_op_relpos_gate")
+
+
+def regroup(x, d, groups, cpg, R, lead, B, P, T, xg, clip_T=None):
+    _lib.check(lib().wfl_op_regroup(ptr(x), d, groups, cpg, R, lead, B, P, T, ptr(clip_T), ptr(xg), stream()), "wfl_op_regroup")
+
+
+def posconv(xg, R, lead, B, P, T, groups, cpg, taps, w, ldw, bias, res, res_lo, out, out_lo, ld, clip_T=None, check=True):
+    rc = lib().wfl_op_posconv(ptr(xg), R, lead, B, P, T, groups, cpg, taps, ptr(w), ldw, ptr(bias), ptr(res), ptr(res_lo), ptr(out),
+                              ptr(out_lo), ld, ptr(clip_T), stream())
+    if check:
+        _lib.check(rc, "wfl_op_posconv")
+    return rc
+
+
+def layernorm_act(x, x_lo, y, y_lo, g, b, eps, lead, B, P, T, Cn, n_div=0, gelu=0, clip_T=None):
+    _lib.check(lib().wfl_op_layernorm_act(ptr(x), ptr(x_lo), Cn, ptr(y), ptr(y_lo), Cn, ptr(g), ptr(b), float(eps), lead, B, P, T, Cn, n_div,
+                                          gelu, ptr(clip_T), stream()), "wfl_op_layernorm_act")
+
+
+def layernorm_pair(x, x_lo, y1, y1_lo, y2, y2_lo, g1, b1, g2, b2, eps, lead, B, P, T, Cn, n_div=0, clip_T=None):
+    _lib.check(lib().wfl_op_layernorm_pair(ptr(x), ptr(x_lo), ptr(y1), ptr(y1_lo), ptr(y2), ptr(y2_lo), Cn, ptr(g1), ptr(b1), ptr(g2), ptr(b2),
+                                           float(eps), lead, B, P, T, Cn, n_div, ptr(clip_T), stream()), "wfl_op_layernorm_pair")

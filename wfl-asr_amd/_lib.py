@@ -59,6 +59,13 @@ SIGNATURES = {
     "wfl_op_gemm_mx": (_I, [_P, _P, _L, _P, _P, _P, _F, _I, _I, _I, _I, _I, _P, _L, _L, _I, _P, _P, _P, _P, _F, _I, _P, _P, _L, _F, _P, _P]),
     "wfl_op_rows_fp8": (_I, [_P, _L, _P, _P, _P, _F, _L, _I, _I, _I, _I, _P, _P, _L, _P, _P]),
     "wfl_op_attention": (_I, [_P, _L, _L, _P, _L, _P, _L, _I, _I, _I, _I, _I, _P]),
+    "wfl_op_attention_ex": (_I, [_P, _P, _L, _L, _P, _P, _L, _P, _P, _L, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _L, _F, _P, _P]),
+    "wfl_op_relpos_table": (_I, [_P, _P, _I, _I, _I, _P, _P]),
+    "wfl_op_relpos_gate": (_I, [_P, _P, _L, _L, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P]),
+    "wfl_op_regroup": (_I, [_P, _I, _I, _I, _L, _L, _I, _I, _I, _P, _P, _P]),
+    "wfl_op_posconv": (_I, [_P, _L, _L, _I, _I, _I, _I, _I, _I, _P, _L, _P, _P, _P, _P, _P, _L, _P, _P]),
+    "wfl_op_layernorm_act": (_I, [_P, _P, _L, _P, _P, _L, _P, _P, _F, _L, _I, _I, _I, _I, _I, _I, _P, _P]),
+    "wfl_op_layernorm_pair": (_I, [_P, _P, _P, _P, _P, _P, _L, _P, _P, _P, _P, _F, _L, _I, _I, _I, _I, _I, _P, _P]),
     "wfl_op_layernorm": (_I, [_P, _L, _P, _L, _P, _P, _F, _L, _I, _I, _I, _I, _P]),
     "wfl_op_tag_decide": (_I, [_P, _L, _I, _I, _F, _I, _P, _P, _P, _P]),
     "wfl_host_median_filter": (_I, [_P, _I, _I, _P]),

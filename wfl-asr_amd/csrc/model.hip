@@ -2227,6 +2227,85 @@ int32_t wfl_op_attention(const void* QK, int64_t ldqk, int64_t lead, const void*
   return r ? fail(r, "wfl_op_attention: invalid arguments, unsupported head_dim or launch failure (" + std::to_string(r) + ")") : 0;
 }
 
+int32_t wfl_op_attention_ex(const void* QK, const void* QK_lo, int64_t ldqk, int64_t lead, const void* V, const void* V_lo, int64_t ldv,
+                            void* O, void* O_lo, int64_t ldo, int32_t B, int32_t T, int32_t P, int32_t heads, int32_t d, const float* bias,
+                            const float* gate, const int32_t* clip_T, void* O8, void* O8_lo, int64_t ldo8, float o8_scale, int32_t* status,
+                            void* stream) {
+  if (!QK || !V || (!O && !O8)) return fail(-1, "wfl_op_attention_ex: null argument");
+  if (!QK_lo != !V_lo) return fail(-1, "wfl_op_attention_ex: QK_lo and V_lo go together");
+  if ((O_lo && !O) || (O8_lo && !O8)) return fail(-1, "wfl_op_attention_ex: a low half without its high half");
+  if (B <= 0 || T <= 0 || heads <= 0 || d % heads) return fail(-1, "wfl_op_attention_ex: empty batch or d not a whole number of heads");
+  // (fields the dispatch would pass over without a word: the fp8 context has no split-precision or bf16-low-half form, the split kernels
+  //  exist for four head sizes)
+  if (O8 && (QK_lo || O_lo)) return fail(-4, "wfl_op_attention_ex: the fp8 context takes no QK_lo / V_lo / O_lo");
+  if (QK_lo && d / heads != 32 && d / heads != 64 && d / heads != 128 && d / heads != 256)
+    return fail(-4, "wfl_op_attention_ex: split precision at head_dim 32, 64, 128, 256 only");
+  AttnArgs a{};
+  a.QK = (const bf16_t*)QK; a.ldqk = ldqk; a.lead = lead; a.V = (const bf16_t*)V; a.ldv = ldv; a.O = (bf16_t*)O; a.ldo = ldo;
+  a.B = B; a.T = T; a.P = P; a.heads = heads; a.d = d;
+  a.bias = bias; a.gate = gate; a.clip_T = clip_T; a.O_lo = (bf16_t*)O_lo; a.QK_lo = (const bf16_t*)QK_lo; a.V_lo = (const bf16_t*)V_lo;
+  a.O8 = (unsigned char*)O8; a.O8_lo = (unsigned char*)O8_lo; a.ldo8 = ldo8; a.o8_scale = o8_scale; a.err = (unsigned*)status;
+  const int r = wfl_launch_attention(a, (hipStream_t)stream);
+  return r ? fail(r, "wfl_op_attention_ex: invalid arguments, a combination attention.hip has no kernel for, or launch failure (" +
+                         std::to_string(r) + ")") : 0;
+}
+
+int32_t wfl_op_relpos_table(const float* rel_emb, const int32_t* bucket_of_delta, int32_t max_t, int32_t heads, int32_t T, float* table,
+                            void* stream) {
+  if (!rel_emb || !bucket_of_delta || !table || heads <= 0 || T <= 0) return fail(-1, "wfl_op_relpos_table: bad argument");
+  const int r = wfl_launch_relpos_table(rel_emb, bucket_of_delta, max_t, heads, T, table, (hipStream_t)stream);
+  return r ? fail(r, "wfl_op_relpos_table: T > max_t or launch failure (" + std::to_string(r) + ")") : 0;
+}
+
+int32_t wfl_op_relpos_gate(const void* x, const void* x_lo, int64_t ldx, int64_t lead, int32_t B, int32_t P, int32_t T, int32_t heads,
+                           int32_t hd, const float* w8, const float* b8, const float* cst, float* gate, void* stream) {
+  if (!x || !w8 || !b8 || !cst || !gate || B <= 0 || T <= 0 || heads <= 0 || hd <= 0) return fail(-1, "wfl_op_relpos_gate: bad argument");
+  const int r = wfl_launch_relpos_gate((const bf16_t*)x, ldx, lead, B, P, T, heads, hd, w8, b8, cst, gate, (hipStream_t)stream,
+                                       (const bf16_t*)x_lo);
+  return r ? fail(r, "wfl_op_relpos_gate: head_dim or leading dimension not taken, or launch failure (" + std::to_string(r) + ")") : 0;
+}
+
+int32_t wfl_op_regroup(const void* x, int32_t d, int32_t groups, int32_t cpg, int64_t R, int64_t lead, int32_t B, int32_t P, int32_t T,
+                       const int32_t* clip_T, void* xg, void* stream) {
+  if (!x || !xg || groups <= 0 || cpg <= 0 || R <= 0 || B <= 0 || P <= 0) return fail(-1, "wfl_op_regroup: bad argument");
+  const int r = wfl_launch_regroup((const bf16_t*)x, d, groups, cpg, R, lead, B, P, T, (bf16_t*)xg, (hipStream_t)stream, clip_T);
+  return r ? fail(r, "wfl_op_regroup: channel split not taken or launch failure (" + std::to_string(r) + ")") : 0;
+}
+
+int32_t wfl_op_posconv(const void* xg, int64_t R, int64_t lead, int32_t B, int32_t P, int32_t T, int32_t groups, int32_t cpg, int32_t taps,
+                       const void* w, int64_t ldw, const float* bias, const void* res, const void* res_lo, void* out, void* out_lo,
+                       int64_t ld, const int32_t* clip_T, void* stream) {
+  if (!xg || !w || !bias || !res || !out || R <= 0 || B <= 0 || P <= 0) return fail(-1, "wfl_op_posconv: bad argument");
+  if (groups <= 0 || groups > 16) return fail(-1, "wfl_op_posconv: 1 .. 16 groups");
+  PosConvArgs pc{};
+  pc.xg = (const bf16_t*)xg; pc.R = R; pc.lead = lead; pc.B = B; pc.P = P; pc.T = T; pc.groups = groups; pc.cpg = cpg; pc.taps = taps;
+  for (int gi = 0; gi < groups; ++gi) { pc.w[gi] = (const bf16_t*)w + (long)gi * 64 * ldw; pc.bias[gi] = bias + gi * 64; }
+  pc.ldw = ldw;
+  pc.res = (const bf16_t*)res; pc.res_lo = (const bf16_t*)res_lo; pc.out = (bf16_t*)out; pc.out_lo = (bf16_t*)out_lo; pc.ld = ld;
+  pc.clip_T = clip_T;
+  const int r = wfl_launch_posconv(pc, (hipStream_t)stream);
+  if (r == 1) return fail(-1, "wfl_op_posconv: shape not taken by posconv.hip (cpg % 8, even taps 4 .. 128, ldw >= 64 taps, lead >= taps / 2)");
+  return r ? fail(r, "wfl_op_posconv: launch failure (" + std::to_string(r) + ")") : 0;
+}
+
+int32_t wfl_op_layernorm_act(const void* x, const void* x_lo, int64_t ldx, void* y, void* y_lo, int64_t ldy, const float* gamma,
+                             const float* beta, float eps, int64_t lead, int32_t B, int32_t P, int32_t T, int32_t C, int32_t n_div,
+                             int32_t gelu, const int32_t* clip_T, void* stream) {
+  if (!x || !y || !gamma || !beta || B <= 0 || T <= 0) return fail(-1, "wfl_op_layernorm_act: bad argument");
+  const int r = wfl_launch_layernorm_act((const bf16_t*)x, ldx, (bf16_t*)y, ldy, gamma, beta, eps, lead, B, P, T, C, gelu, (hipStream_t)stream,
+                                         (const bf16_t*)x_lo, (bf16_t*)y_lo, n_div, clip_T);
+  return r ? fail(r, "wfl_op_layernorm_act: invalid arguments or launch failure (" + std::to_string(r) + ")") : 0;
+}
+
+int32_t wfl_op_layernorm_pair(const void* x, const void* x_lo, void* y1, void* y1_lo, void* y2, void* y2_lo, int64_t ld, const float* gamma1,
+                              const float* beta1, const float* gamma2, const float* beta2, float eps, int64_t lead, int32_t B, int32_t P,
+                              int32_t T, int32_t C, int32_t n_div, const int32_t* clip_T, void* stream) {
+  if (!x || !y1 || !y2 || !gamma1 || !beta1 || !gamma2 || !beta2 || B <= 0 || T <= 0) return fail(-1, "wfl_op_layernorm_pair: bad argument");
+  const int r = wfl_launch_layernorm_pair((const bf16_t*)x, (const bf16_t*)x_lo, (bf16_t*)y1, (bf16_t*)y1_lo, (bf16_t*)y2, (bf16_t*)y2_lo, ld,
+                                          gamma1, beta1, gamma2, beta2, eps, lead, B, P, T, C, n_div, clip_T, (hipStream_t)stream);
+  return r ? fail(r, "wfl_op_layernorm_pair: invalid arguments, aliased y1 or launch failure (" + std::to_string(r) + ")") : 0;
+}
+
 int32_t wfl_op_layernorm(const void* x, int64_t ldx, void* y, int64_t ldy, const float* gamma, const float* beta, float eps,
                          int64_t lead, int32_t B, int32_t P, int32_t T, int32_t C, void* stream) {
   const int r = wfl_launch_layernorm((const bf16_t*)x, ldx, (bf16_t*)y, ldy, gamma, beta, eps, lead, B, P, T, C, (hipStream_t)stream);
