@@ -643,6 +643,61 @@ int32_t wfl_align_filler_posterior(const float* logits, int64_t ldl, int32_t C, 
                                    int64_t workspace_bytes, float* logz, float* tok_post, float* start_mean, float* start_sd,
                                    float* end_mean, float* end_sd, int32_t* status, void* stream);
 
+/* ---- Posteriors over the explicit-duration lattice of wfl_align_duration_prior (`postprocess.duration_prior_scores`;
+ * wfl-asr_amd/align.py duration_prior_posteriors, csrc/align_duration_prior_posterior.hip).  The arguments up to D are
+ * wfl_align_duration_prior's, under the same table contract (every entry finite or -inf, never NaN; tail <= 0 or -inf; 1 <= D <= 32);
+ * tok is that search's output for the same clips.  Emissions EB / EI / EG are wfl_align_posterior's (z_t - lse_t, EB through the window
+ * where tok_win is given), L_k(d) and tail_k the search's, and a path weighs exp(sum_t e_t + sum_k L_k(d_k)).  Forward, the search's
+ * recurrence with log-sum-exp for max:
+ *     ent_k(t)  = lse(aG_k(t-1), aX_{k-1}(t-1))                ent_0(0) = 0, every other ent_k(0) = -inf
+ *     aG_k(t)   = ent_k(t) + EG_t
+ *     aR_k^1(t) = ent_k(t) + EB_t(k);    aR_k^j(t) = aR_k^{j-1}(t-1) + EI_t(k)     2 <= j <= D
+ *     aY_k(t)   = lse(aY_k(t-1), aR_k^D(t-1) + L_k(D)) + EI_t(k) + tail_k
+ *     aX_k(t)   = lse(aR_k^1(t) + L_k(1), .., aR_k^D(t) + L_k(D), aY_k(t))          frame t is the last frame of token k
+ *     logZ      = lse(aG_N(T-1), aX_{N-1}(T-1))
+ * Backward: bE_k(t) stands for beta(G_k) and beta(X_{k-1}) (the same successors); W_k^j(t) is the suffix weight when frame t is the
+ * j-th frame of a run of token k, V_k(t) when the run is already longer than D:
+ *     bE_N(T-1) = 0, every other bE_k(T-1) = -inf;   the terms "at t+1" are absent at t = T - 1
+ *     V_k(t)    = lse(bE_{k+1}(t), EI_{t+1}(k) + tail_k + V_k(t+1))
+ *     W_k^j(t)  = lse(L_k(j) + bE_{k+1}(t), EI_{t+1}(k) + W_k^{j+1}(t+1))   1 <= j < D;      W_k^D(t) = L_k(D) + V_k(t)
+ *     bE_k(t-1) = lse(bE_k(t) + EG_t, EB_t(k) + W_k^1(t))                    (second term absent for k = N)
+ *     start_k(t) = exp(ent_k(t) + EB_t(k) + W_k^1(t) - logZ),     end_k(t) = exp(aX_k(t) + bE_{k+1}(t) - logZ)
+ *     occ_k(t)   = sum_{s <= t} start_k(s) - sum_{e < t} end_k(e)            the posterior that frame t belongs to token k
+ * Outputs (device, float32; the per-token ones rows as tok_cls), with [first_k, last_k] the frames tok gives token k:
+ *   logz[b]        logZ; the fp32 rounding residue of the frames' log-sum-exp is given back in double, as in wfl_align_posterior;
+ *   tok_post[k]    the mean of occ_k(t) over first_k .. last_k, clamped to [0, 1]; accumulated in double by the thread that owns the
+ *                  token as  sum_s start_k(s) #{t in run: t >= s} - sum_e end_k(e) #{t in run: t > e};
+ *   start_mean[k], start_sd[k]   moments of t - first_k under start_k(.) divided by its own sum (wfl_align_posterior's definition);
+ *   end_mean[k], end_sd[k]       moments of t - last_k under end_k(.) divided by its own sum (wfl_align_filler_posterior's); zeros where
+ *                  the sum is 0.
+ * status[b]: wfl_align_posterior_windowed's codes: 2 N above 4096; 1 T < N, or table and windows leave no path (logZ = -inf; never a
+ * NaN in any output); 4 a bad class, or a tok_dur outside -1 .. n_rows - 1; 8 tok is not a path of this lattice: a value outside
+ * -1 .. N - 1, a token missing, twice or out of order, a token opening outside its window, a run whose length d has L_k(d) = -inf.
+ * 1 comes before 8.  A clip with status != 0 gets zeros in all six float outputs and does not disturb its batch; one workgroup per
+ * clip, a clip scored alone equals the same clip inside any batch, bit for bit.
+ * Host-side negative returns: wfl_align_duration_prior's, and a null tok while any frame is present, a null per-token output while any
+ * token is present, a workspace that is too small.  Nothing is launched after a refusal.
+ * Workspace.  Alpha is never stored per frame: a checkpoint of G, X, Y and the D ring entries of every slot every 128 frames, and one
+ * block of 128 frames of (aR^1, aX), the two values of alpha that meet beta.  The two rings (alpha's aR^1 .. aR^D, beta's W^1 .. W^D;
+ * D floats per slot each) live in the workgroup's LDS where they fit beside its other areas, alpha's first, and in the workspace where
+ * they do not.  With eight or nine slots per thread (N > 1023) the seven double sums of every slot and the two ends of its run are kept
+ * in the workspace as well, not in registers.  Per clip, in 4-byte words (0 for T = 0), with nblk = ceil(T / 128):
+ *     round_up_64(T) + round_up_64(2 nblk) + nblk (3 + D) slots(N) + 256 slots(N) + sums(N)
+ *         + (2 - lds_rings(N, D)) round_up_64(slots(N) D),
+ *     slots(N) = 128 (N <= 127), 512 (N <= 511), 1024 (N <= 1023), 2048 (N <= 2047), 4608 (above);   sums(N) = 16 slots(N) for
+ *     N > 1023, else 0;   lds_rings(N, D) = min(2, floor(room(N) / (4 slots(N) D))),   room(N) = 148992, 112128, 99840, 75264, 9728
+ *     bytes in that order
+ * (so N <= 127 keeps both rings in LDS at every D; N <= 511 both up to D = 27, one above; N <= 1023 both up to D = 12, one up to
+ * D = 24, none above; N <= 2047 both up to D = 4, one up to D = 9, none above; above that none at any D). */
+int64_t wfl_align_duration_prior_posterior_workspace_bytes(const int32_t* n_frames_host, const int32_t* n_tok_host, int32_t n_clips,
+                                                           int32_t D);
+int32_t wfl_align_duration_prior_posterior(const float* logits, int64_t ldl, int32_t C, int32_t o_id, const int64_t* frame_off_host,
+                                           const int32_t* n_frames_host, const int32_t* tok_off_host, const int32_t* n_tok_host,
+                                           const int32_t* tok_cls, const int32_t* tok_win, const int32_t* gap_cls, int32_t n_clips,
+                                           const int32_t* tok_dur, const float* dur, int32_t n_rows, int32_t D, const int32_t* tok,
+                                           void* workspace, int64_t workspace_bytes, float* logz, float* tok_post, float* start_mean,
+                                           float* start_sd, float* end_mean, float* end_sd, int32_t* status, void* stream);
+
 /* ---- Single-edit scores of an aligned transcript (`postprocess.align_edits`; wfl-asr_amd/align.py, csrc/align_edits.hip).  No
  * counterpart in the reference.  The arguments are wfl_align_posterior_windowed's without tok; tok_win may be null: the unwindowed
  * lattice.  sub_cls (device, [n_sub][2] int32 = (B class, I class)) is a table of P = n_sub substitutes, 0 <= P <= 512.  With logZ(.)

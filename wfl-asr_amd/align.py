@@ -29,6 +29,10 @@ token gets one contiguous, time-ordered run of frames, none is dropped.
   viterbi_align_duration_prior  the search with a duration prior per token: a run of d frames adds its table row's L(d)
                         (`wfl_align_duration_prior`, `postprocess.duration_prior`); upload_durations packs the rows once
   duration_rows         a durations.DurationPrior -> the table row of every transcript token (-1: none)
+  duration_prior_posteriors  forward-backward over that explicit-duration lattice (`wfl_align_duration_prior_posterior`;
+                        `postprocess.duration_prior_scores`): alignment_posteriors' outputs and the moments of every token's end
+  token_durations / format_durations_tsv / format_folder_durations_tsv   one file's TokenDuration rows, {stem}.durations.tsv, the
+                        folder's list, the least probable length first
   alignment_posteriors  forward-backward over the same lattice (csrc/align_posterior.h, `wfl_align_posterior`; of a batch packed with
                         windows, `wfl_align_posterior_windowed`): logZ, and per token
                         the posterior of the run Viterbi chose and the spread of its start (`postprocess.align_scores`)
@@ -102,6 +106,11 @@ def filler_workspace_bytes(n_frames, n_tokens) -> int:
 def duration_prior_workspace_bytes(n_frames, n_tokens, max_frames) -> int:
     """max_frames: D, the table's longest explicit duration (its rows have D + 1 columns), 1 .. MAX_PRIOR_FRAMES."""
     return _workspace_bytes("wfl_align_duration_prior_workspace_bytes", n_frames, n_tokens, int(max_frames))
+
+
+def duration_prior_posterior_workspace_bytes(n_frames, n_tokens, max_frames) -> int:
+    """max_frames: D, as duration_prior_workspace_bytes'."""
+    return _workspace_bytes("wfl_align_duration_prior_posterior_workspace_bytes", n_frames, n_tokens, int(max_frames))
 
 
 def optional_posterior_workspace_bytes(n_frames, n_tokens) -> int:
@@ -377,6 +386,7 @@ _ENTRIES = {
     "wfl_align_filler": ("wfl_align_filler", True, False),
     "wfl_align_filler_posterior": ("wfl_align_filler_posterior", True, False),
     "wfl_align_duration_prior": ("wfl_align_duration_prior", True, False),
+    "wfl_align_duration_prior_posterior": ("wfl_align_duration_prior_posterior", True, False),
 }
 
 
@@ -385,7 +395,7 @@ def _call(entry, logits, o_id, packed, middle, outputs, stream, temporaries=(), 
     entry takes  logits .. token table, [windows], [minimum durations], gap table, clips, *middle, workspace, its bytes, *outputs,
     stream  (_ENTRIES; windows that were not packed go as a null pointer).  middle: a tensor goes as its pointer, anything else as
     it is; temporaries: tensors made for this call alone, kept for the stream beside the workspace and the packed tables; sized_by:
-    what the entry's workspace rule takes after the clip count (wfl_align_duration_prior: D)."""
+    what the entry's workspace rule takes after the clip count (wfl_align_duration_prior and its posterior: D)."""
     lib = _lib.load()
     sized_as, takes_win, takes_min = _ENTRIES[entry]
     nb, T, N, F0, K0, d_tc, d_gc, d_win, d_min = packed
@@ -532,6 +542,21 @@ def viterbi_align_duration_prior(logits, n_frames, token_classes, gap_classes, o
     if packed.d_min is not None:
         raise ValueError("viterbi_align_duration_prior has no minimum durations: this batch was packed with min_frames")
     dev, rows, nb, ntok = logits.device, logits.shape[0], packed.nb, int(packed.N.sum())
+    d_tab, n_rows, D = _upload_duration_table(table, dev)
+    d_dur = tok_rows if isinstance(tok_rows, torch.Tensor) else upload_durations(tok_rows, packed.N, dev)
+    if d_dur.device != dev or d_dur.dtype != torch.int32 or d_dur.dim() != 1 or d_dur.stride(0) != 1 or d_dur.shape[0] != max(ntok, 1):
+        raise ValueError("uploaded table rows must be upload_durations' [tokens] int32 tensor for this batch")
+    ids = torch.empty(rows, dtype=torch.int32, device=dev)
+    tok = torch.empty(rows, dtype=torch.int32, device=dev)
+    score = torch.empty(max(nb, 1), dtype=torch.float32, device=dev)
+    status = torch.empty(max(nb, 1), dtype=torch.int32, device=dev)
+    _call("wfl_align_duration_prior", logits, o_id, packed, (d_dur, d_tab, n_rows, D), (ids, tok, score, status), stream,
+          temporaries=(d_dur, d_tab), sized_by=(D,))
+    return ids, tok, score[:nb], status[:nb]
+
+
+def _upload_duration_table(table, dev):
+    """viterbi_align_duration_prior's and duration_prior_posteriors' `table` -> (d_tab on `dev`, n_rows, D)."""
     if isinstance(table, torch.Tensor):
         d_tab = table
         if d_tab.device != dev or d_tab.dtype != torch.float32 or d_tab.dim() != 2 or not d_tab.is_contiguous():
@@ -546,16 +571,52 @@ def viterbi_align_duration_prior(logits, n_frames, token_classes, gap_classes, o
     n_rows, D = int(table.shape[0]), int(table.shape[1]) - 1
     if not 1 <= D <= MAX_PRIOR_FRAMES:
         raise ValueError(f"the duration table needs 2 to {MAX_PRIOR_FRAMES + 1} columns (D + 1), got {D + 1}")
+    return d_tab, n_rows, D
+
+
+def duration_prior_posteriors(logits, n_frames, token_classes, gap_classes, o_id, tok_rows, table, tok, frame_offsets=None, stream=None,
+                              packed=None, windows=None):
+    """alignment_posteriors over the explicit-duration lattice of viterbi_align_duration_prior, for the same ragged batch of clips (same
+    arguments, the same `tok_rows` and `table`), given its `tok` (wfl_align_duration_prior_posterior).  A path weighs
+    exp(sum of its frames' log posteriors + sum of its runs' L(d)).
+
+    tok_rows, table  as viterbi_align_duration_prior's
+    windows          as viterbi_align_duration_prior's; with `packed` -- the PackedClips the search ran on -- the ones packed there.  A
+                     batch packed with `min_frames` is refused
+    -> (logz, tok_post, start_mean, start_sd, end_mean, end_sd, status): per clip logz [clips] float32 and status [clips] int32; per
+    token, in the order of the clips' tokens, tok_post (the posterior that the frames the search gave the token belong to it, their
+    mean, in [0, 1]), start_mean / start_sd and end_mean / end_sd (mean relative to the first / last frame the search gave the token,
+    and standard deviation, of the frame its run opens / ends on, in frames).  STATUS_INFEASIBLE: fewer frames than tokens, or the
+    table (and the windows) leave no path; STATUS_BAD_CLASS also for a row outside -1 .. rows - 1; STATUS_NOT_A_PATH: `tok` is not a
+    path of this lattice (a run of a length the table forbids included).  A clip with status != 0 gets zeros.  Large batches run in
+    groups whose workspace stays under EDITS_WORKSPACE_LIMIT (edit_groups), each clip's outputs the same as in one call."""
+    if packed is None:
+        packed = pack_clips(logits, n_frames, token_classes, gap_classes, frame_offsets, windows)
+    if packed.d_min is not None:
+        raise ValueError("duration_prior_posteriors has no minimum durations: this batch was packed with min_frames")
+    _check_tok(tok, logits)
+    nb, ntok, dev = packed.nb, int(packed.N.sum()), logits.device
+    d_tab, n_rows, D = _upload_duration_table(table, dev)
     d_dur = tok_rows if isinstance(tok_rows, torch.Tensor) else upload_durations(tok_rows, packed.N, dev)
     if d_dur.device != dev or d_dur.dtype != torch.int32 or d_dur.dim() != 1 or d_dur.stride(0) != 1 or d_dur.shape[0] != max(ntok, 1):
         raise ValueError("uploaded table rows must be upload_durations' [tokens] int32 tensor for this batch")
-    ids = torch.empty(rows, dtype=torch.int32, device=dev)
-    tok = torch.empty(rows, dtype=torch.int32, device=dev)
-    score = torch.empty(max(nb, 1), dtype=torch.float32, device=dev)
+    logz = torch.empty(max(nb, 1), dtype=torch.float32, device=dev)
+    per_tok = torch.empty((5, max(ntok, 1)), dtype=torch.float32, device=dev)
     status = torch.empty(max(nb, 1), dtype=torch.int32, device=dev)
-    _call("wfl_align_duration_prior", logits, o_id, packed, (d_dur, d_tab, n_rows, D), (ids, tok, score, status), stream,
-          temporaries=(d_dur, d_tab), sized_by=(D,))
-    return ids, tok, score[:nb], status[:nb]
+    groups = edit_groups(packed.T, packed.N, workspace_bytes=lambda t, n: duration_prior_posterior_workspace_bytes(t, n, D))
+    for grp in groups or [[]]:
+        # a group is a run of consecutive clips: the host arrays are sliced, the device tables and the outputs stay whole (the token
+        # offsets K0 and the clip index of gap_classes / logz / status are rebased by pointer arithmetic on the tensors' views)
+        if len(groups) <= 1:
+            sub, lo = packed, 0
+        else:
+            lo, hi = grp[0], grp[-1] + 1
+            sub = packed._replace(nb=hi - lo, T=packed.T[lo:hi], N=packed.N[lo:hi], F0=packed.F0[lo:hi], K0=packed.K0[lo:hi],
+                                  d_gc=packed.d_gc[lo:hi])
+        _call("wfl_align_duration_prior_posterior", logits, o_id, sub, (d_dur, d_tab, n_rows, D, tok),
+              (logz[lo:], per_tok[0], per_tok[1], per_tok[2], per_tok[3], per_tok[4], status[lo:]), stream,
+              temporaries=(d_dur, d_tab), sized_by=(D,))
+    return (logz[:nb], per_tok[0, :ntok], per_tok[1, :ntok], per_tok[2, :ntok], per_tok[3, :ntok], per_tok[4, :ntok], status[:nb])
 
 
 def upload_filler(fillers, n_tokens, device):
@@ -1424,4 +1485,66 @@ def format_folder_filler_scores_tsv(per_file) -> str:
     the list to check."""
     flat = sorted(((name, r) for name, rows in per_file for r in rows), key=lambda nr: nr[1].posterior)
     lines = ["file\t" + FILLER_SCORES_HEADER] + ["\t".join([name] + _filler_score_cells(r)) for name, r in flat]
+    return "".join(line + "\n" for line in lines)
+
+
+# ---------------------------------------------------------------------------------------- token durations under a duration prior
+class TokenDuration(NamedTuple):
+    index: int              # the token's index in the transcript
+    token: str
+    start_s: float          # its run on the .lab clock
+    end_s: float
+    frames: int             # the frames of its run
+    log_prior: float        # the table's L(frames) of the token's row: weight * log P(frames | phoneme); None for a token without a row
+    posterior: float        # duration_prior_posteriors' tok_post: the posterior that the run's frames belong to the token
+    start_shift_s: float    # posterior mean of the run's start minus the search's, seconds on the .lab clock
+    start_sd_s: float       # posterior standard deviation of the start, seconds
+    end_shift_s: float      # the same for the run's end
+    end_sd_s: float
+    expected_frames: float  # frames + end_mean - start_mean: the posterior mean of the token's length (exact, by linearity)
+
+
+def token_durations(tokens, frames, rows, table, tok_post, start_mean, start_sd, end_mean, end_sd, frame_duration):
+    """One file's TokenDuration rows, one per transcript token in order, from duration_prior_posteriors' outputs for the file (host
+    values, one per token).  tokens: the file's TokenScore rows (file_score); frames: the frames of every token's run; rows, table:
+    the tokens' rows of the duration table and the table ([rows, D + 1], as viterbi_align_duration_prior's); frame_duration: the .lab
+    clock that turns the frame figures into seconds."""
+    cols = [np.asarray(a, np.float64).reshape(-1) for a in (tok_post, start_mean, start_sd, end_mean, end_sd)]
+    if len({len(c) for c in cols} | {len(tokens), len(frames), len(rows)}) != 1:
+        raise ValueError("one token, run length, table row, posterior and pair of start and end moments per transcript token")
+    table = np.asarray(table, np.float64)
+    D = table.shape[1] - 1
+    out = []
+    for k, (t, d, r) in enumerate(zip(tokens, frames, rows)):
+        d, r = int(d), int(r)
+        prior = None
+        if r >= 0:
+            prior = float(table[r, d - 1]) if d <= D else float(table[r, D - 1]) + (d - D) * float(table[r, D])
+        p, smu, ssd, emu, esd = (float(c[k]) for c in cols)
+        out.append(TokenDuration(k, t.token, t.start_s, t.end_s, d, prior, p, smu * frame_duration, ssd * frame_duration,
+                                 emu * frame_duration, esd * frame_duration, d + emu - smu))
+    return out
+
+
+DURATIONS_HEADER = ("index\ttoken\tstart_s\tend_s\tframes\tlog_prior\tposterior\tstart_shift_s\tstart_sd_s\tend_shift_s\tend_sd_s"
+                    "\texpected_frames")
+
+
+def _duration_cells(r: TokenDuration):
+    return [str(r.index), r.token, f"{r.start_s:.7f}", f"{r.end_s:.7f}", str(r.frames),
+            "none" if r.log_prior is None else f"{r.log_prior:.6f}", f"{r.posterior:.6f}", f"{r.start_shift_s:.7f}", f"{r.start_sd_s:.7f}",
+            f"{r.end_shift_s:.7f}", f"{r.end_sd_s:.7f}", f"{r.expected_frames:.4f}"]
+
+
+def format_durations_tsv(rows) -> str:
+    """{stem}.durations.tsv: one line per transcript token, in the transcript's order."""
+    return "".join("\t".join(c) + "\n" for c in [DURATIONS_HEADER.split("\t")] + [_duration_cells(r) for r in rows])
+
+
+def format_folder_durations_tsv(per_file) -> str:
+    """token_durations.tsv: [(file name, [TokenDuration])] -> every token that has a prior row, of every file, the file's name in front
+    of the token's own columns, the lowest log_prior first (the length the prior finds least probable); ties in the files' and the
+    tokens' order.  No flag, no threshold: the order is the list to check."""
+    flat = sorted(((name, r) for name, rows in per_file for r in rows if r.log_prior is not None), key=lambda nr: nr[1].log_prior)
+    lines = ["file\t" + DURATIONS_HEADER] + ["\t".join([name] + _duration_cells(r)) for name, r in flat]
     return "".join(line + "\n" for line in lines)

@@ -436,11 +436,13 @@ class Labeler:
                     decode=None, switch_penalty=None, decode_scores=None, phoneme_bigram=None, bigram_weight=None, align_draft=None,
                     draft_tolerance=None, align_edits=None, align_insertions=None, min_duration=None, duration_scores=None,
                     optional_tokens=None, skip_penalty=None, optional_scores=None, filler_token=None, filler_penalty=None,
-                    filler_scores=None, duration_prior=None, duration_prior_weight=None, bigram_scores=None):
+                    filler_scores=None, duration_prior=None, duration_prior_weight=None, duration_prior_scores=None,
+                    bigram_scores=None):
         """-> list (per file) of [(start_s, end_s, phoneme)] after merge + forced alignment; with align_scores, duration_scores,
         decode_scores or bigram_scores, (that list, scores); with align_edits the tuple goes on with one more list, edits, and with
         align_insertions it ends with one more, insertions; with optional_tokens it ends with the list skipped; with a filler_token
-        it ends with the list fillers, and with filler_scores with one more, filler_scores.
+        it ends with the list fillers, and with filler_scores with one more, filler_scores; with duration_prior_scores it ends with the
+        list durations.
 
         align: "greedy" -- a `{audio}.txt` transcript is matched onto the freely decoded segments (infer.py:30-60, 312-319);
         "viterbi" -- files with a transcript are aligned by a search over their frame logits on the GPU (align.py: one segment
@@ -545,23 +547,33 @@ class Labeler:
         prior gives d frames of that phoneme; the row is the one of the token's output name as the transcript spells it, a token the
         prior does not hold has none.  A file the prior leaves no path for falls back, with a line, to the plain alignment of the same
         transcript.  A prior counted on another frame duration, or one that holds a phoneme that is no output name of the label set,
-        is refused by name; align_draft, min_duration, optional_tokens, filler_token and the scoring options beside it are refused."""
+        is refused by name; align_draft, min_duration, optional_tokens, filler_token and the scoring options beside it are refused.
+
+        duration_prior_scores (with a duration_prior only; None: config postprocess.duration_prior_scores, else off): scores[i] is the
+        align.FileScore of a file that was aligned, from a forward-backward pass over the lattice the file was searched on -- the
+        explicit-duration lattice (align.duration_prior_posteriors, the rows, the table and the weight of the search) for a file
+        searched under the prior, wfl_align_posterior's, with one line, for one the prior left no path for -- and durations[i] one
+        align.TokenDuration per transcript token of a file scored under the prior: its run, the prior's log probability of that
+        length, the posterior of the run, the mean shift and spread of both its ends and the expected length (None for a file that
+        was not aligned, or was searched without the prior).  The segments are the same with and without."""
         opts = self.options(align=align, align_scores=align_scores, decode=decode, switch_penalty=switch_penalty,
                             decode_scores=decode_scores, phoneme_bigram=phoneme_bigram, bigram_weight=bigram_weight,
                             bigram_scores=bigram_scores, align_draft=align_draft, draft_tolerance=draft_tolerance,
                             align_edits=align_edits, align_insertions=align_insertions, min_duration=min_duration,
                             duration_scores=duration_scores, optional_tokens=optional_tokens, skip_penalty=skip_penalty,
                             optional_scores=optional_scores, filler_token=filler_token, filler_penalty=filler_penalty,
-                            filler_scores=filler_scores, duration_prior=duration_prior, duration_prior_weight=duration_prior_weight)
+                            filler_scores=filler_scores, duration_prior=duration_prior, duration_prior_weight=duration_prior_weight,
+                            duration_prior_scores=duration_prior_scores)
         edits = {} if opts.align_edits else None
         insertions = {} if opts.align_insertions else None
         skipped = {} if opts.optional_tokens is not None else None
         optional = {} if opts.optional_scores else None
         fillers = {} if opts.filler_token is not None else None
         fscores = {} if opts.filler_scores else None
+        durations = {} if opts.duration_prior_scores else None
         final, scores = self._label_scored(audio_paths, opts, lang_id, confidence_threshold, verbose, edits=edits,
                                            insertions=insertions, skipped=skipped, optional=optional, fillers=fillers,
-                                           filler_scores=fscores)
+                                           filler_scores=fscores, durations=durations)
         out = (final, scores) if opts.scored else (final,)
         if opts.align_edits:
             out += ([edits.get(fi) for fi in range(len(audio_paths))],)
@@ -575,17 +587,19 @@ class Labeler:
             out += ([fillers.get(fi) for fi in range(len(audio_paths))],)
         if fscores is not None:
             out += ([fscores.get(fi) for fi in range(len(audio_paths))],)
+        if durations is not None:
+            out += ([durations.get(fi) for fi in range(len(audio_paths))],)
         return out if len(out) > 1 else final
 
     def _label_scored(self, audio_paths, opts, lang_id, confidence_threshold, verbose, moves=None, edits=None, insertions=None,
-                      skipped=None, optional=None, fillers=None, filler_scores=None):
+                      skipped=None, optional=None, fillers=None, filler_scores=None, durations=None):
         """label_files for the resolved options `opts`, always -> (segments, scores): the files are split once into those a transcript is
         Viterbi-aligned to, those the grammar search decodes and those left to the argmax decode, and each subset's results go back to
         its files' places.  moves: a dict that takes {file index: [DraftMove]} for the files aligned inside their draft's windows.
         edits (opts.align_edits): a dict that takes {file index: [TokenEdit]} for the files that were Viterbi-aligned; insertions
         (opts.align_insertions): the same with [PlaceInsertion]; skipped (opts.optional_tokens): the same with [SkippedToken]; optional
         (opts.optional_scores): the same with [OptionalTokenScore]; fillers (opts.filler_token): the same with [FillerSpan]; filler_scores
-        (opts.filler_scores): the same with [FillerScore]."""
+        (opts.filler_scores): the same with [FillerScore]; durations (opts.duration_prior_scores): the same with [TokenDuration]."""
         if filler_token_collision(opts.filler_token, self._names_for(self._lang_name(lang_id))[1]) is not None:
             raise ValueError(f"filler_token: {opts.filler_token!r} is an output name of this model's label set")
         unknown = (unknown_optional_tokens(opts.optional_tokens, self._names_for(self._lang_name(lang_id))[1])
@@ -633,10 +647,13 @@ class Labeler:
             final[fi] = self._match_forced(audio_paths[fi], segs, verbose)
         if with_t:
             fscores = {} if filler_scores is not None else None       # (by the file's place among with_t)
+            durs = {} if durations is not None else None
             got = self._label_viterbi(paths(with_t), [forced[fi] for fi in with_t], [drafts[fi] for fi in with_t], opts, lang_id,
-                                      confidence_threshold, verbose, fscores, prior)
+                                      confidence_threshold, verbose, fscores, prior, durs)
             for j, rows in (fscores or {}).items():
                 filler_scores[with_t[j]] = rows
+            for j, rows in (durs or {}).items():
+                durations[with_t[j]] = rows
             for fi, rec in zip(with_t, got):
                 final[fi], scores[fi] = rec.segments, rec.score
                 for into, value in ((moves, rec.moves), (edits, rec.edits), (insertions, rec.insertions), (skipped, rec.skipped),
@@ -917,7 +934,8 @@ class Labeler:
                 n_frames += int(frames[b])
         return total, total_logz, total_lse, n_frames, skipped
 
-    def _label_viterbi(self, audio_paths, transcripts, drafts, opts, lang_id, threshold, verbose, filler_scores=None, prior=None):
+    def _label_viterbi(self, audio_paths, transcripts, drafts, opts, lang_id, threshold, verbose, filler_scores=None, prior=None,
+                       durations=None):
         """Files with a transcript, align="viterbi" -> one ViterbiLabel per file.  Their chunks are forwarded with logits (kept on
         the device); the free decode of the same forward gives the greedy result, which the pause rule at the ends needs and which a
         file falls back to (with a message) when its transcript cannot be aligned.  Each file's chunks' valid logits rows are
@@ -926,7 +944,8 @@ class Labeler:
         score / status and the scoring calls' small tables come back to the host.  drafts: per file its draft segments or None
         (opts.align_draft; the transcript is then the draft's labels).  filler_scores (opts.filler_scores): a dict that takes
         {file index: [FillerScore]} for the files that were aligned and scored.  prior (opts.duration_prior): _duration_prior's
-        pair; the search is then the explicit-duration one."""
+        pair; the search is then the explicit-duration one.  durations (opts.duration_prior_scores): a dict that takes {file index:
+        [TokenDuration]} for the files that were searched and scored under the prior."""
         lang_name = self._lang_name(lang_id)
         drafts = drafts if drafts is not None else [None] * len(audio_paths)
         sub_pairs = sub_out = None
@@ -952,7 +971,7 @@ class Labeler:
                                          self.labels.index("O"), wins, mins, flags, fills,
                                          [AL.duration_rows(transcripts[fi], prior[0]) for fi in run] if prior is not None else None)
                 found = _search(batch, paths, opts, prior[1] if prior is not None else None)
-                scored = _score(found, opts, sub_pairs)
+                scored = _score(found, opts, sub_pairs, prior[1] if prior is not None else None)
                 for b, fi in enumerate(run):
                     got = self._clip_label(found, scored, b, chunks[b], transcripts[fi], drafts[fi], free_segs[fi], opts, sub_out)
                     if got is not None:
@@ -961,12 +980,19 @@ class Labeler:
                             # one row per filler; a scored file without a filler has none
                             filler_scores[fi] = (AL.filler_scores(got.fillers, *scored.raw[b][2:], *scored.ends[b], frame_duration)
                                                  if got.fillers else [])
+                        if opts.duration_prior_scores and durations is not None and b in scored.ends:
+                            pos, rows_b = int(found.batch.f0[b]), found.batch.durs[b]
+                            tok_b = found.tok[pos:pos + found.batch.frames[b]]
+                            durations[fi] = AL.token_durations(got.score.tokens, np.bincount(tok_b[tok_b >= 0], minlength=len(rows_b)),
+                                                               rows_b, prior[1], *scored.raw[b][2:], *scored.ends[b], frame_duration)
             for fi in sel:
                 out.append(aligned.get(fi, ViterbiLabel(greedy[fi])))
                 if opts.optional_scores and fi not in aligned:
                     print(f"{audio_paths[fi]}: no optional-token scores (the file was not Viterbi-aligned)")
                 if opts.filler_scores and fi not in aligned:
                     print(f"{audio_paths[fi]}: no filler scores (the file was not Viterbi-aligned)")
+                if opts.duration_prior_scores and fi not in aligned:
+                    print(f"{audio_paths[fi]}: no duration-prior scores (the file was not Viterbi-aligned)")
                 if opts.align_edits and fi not in aligned:
                     print(f"{audio_paths[fi]}: no transcript edits (the file was not Viterbi-aligned)")
                 if opts.align_insertions and fi not in aligned:
@@ -1031,7 +1057,8 @@ class Labeler:
                 no_flag = [0] * len(tr)
                 optional = AL.optional_token_scores(flags if flags is not None else no_flag, left_out if left_out is not None else no_flag,
                                                     scored.keep[b], segs, tr)
-        elif opts.align_scores or opts.duration_scores or opts.optional_scores or opts.filler_scores:      # (the scoring entry refused the path the search gave it)
+        elif (opts.align_scores or opts.duration_scores or opts.optional_scores or opts.filler_scores
+              or opts.duration_prior_scores):             # (the scoring entry refused the path the search gave it)
             entry, code = scored.refused.get(b, ("wfl_align_posterior", None))
             print(f"{found.paths[b]}: no alignment scores ({entry} status {code})")
         lab, spans = segs, None
@@ -1070,6 +1097,7 @@ class _Searched(NamedTuple):
     d_score: torch.Tensor
     packed: AL.PackedClips          # what the search ran on; None: packed inside viterbi_align, or a fallback round dropped constraints
     skipped: np.ndarray = None      # viterbi_align_optional's flags of the batch's tokens, clip after clip; None: no clip has optional tokens
+    plain: tuple = ()               # the clips a duration prior left no path for: searched again by wfl_align (opts.duration_prior)
 
     @property
     def ok(self):
@@ -1083,7 +1111,8 @@ class _Scored(NamedTuple):
     edits: dict                     # the clip's rows of edit_scores' edits
     insertions: dict                # the clip's rows of insertion_scores' ins
     keep: dict                      # optional_posteriors' keep_post of a clip it accepted (opts.optional_scores)
-    ends: dict                      # filler_posteriors' (end_mean, end_sd) of a clip it accepted (opts.filler_scores)
+    ends: dict                      # filler_posteriors' (end_mean, end_sd) of a clip it accepted (opts.filler_scores), or
+                                    # duration_prior_posteriors' (opts.duration_prior_scores)
 
 
 def _clip_flags(transcripts, opts):
@@ -1149,7 +1178,7 @@ def _search(batch, paths, opts, dur_table=None) -> _Searched:
                 d_ids[rows_b], d_tok[rows_b] = r_ids[rows_b], r_tok[rows_b]
                 d_score[b], d_st[b] = r_score[j], r_st[j]
             status = d_st.cpu().numpy()
-        return _Searched(batch, paths, d_ids.cpu().numpy(), d_tok.cpu().numpy(), status, d_tok, d_score, None)
+        return _Searched(batch, paths, d_ids.cpu().numpy(), d_tok.cpu().numpy(), status, d_tok, d_score, None, plain=tuple(again))
     scoring = opts.align_scores or opts.align_edits or opts.align_insertions
     packed = batch.pack(opts.duration_scores) if scoring or (opts.duration_scores and batch.min_frames is not None) else None
     d_skip = None
@@ -1194,9 +1223,10 @@ def _search(batch, paths, opts, dur_table=None) -> _Searched:
                      d_skip.cpu().numpy() if d_skip is not None else None)
 
 
-def _score(found, opts, sub_pairs) -> _Scored:
+def _score(found, opts, sub_pairs, dur_table=None) -> _Scored:
     """Stage 4: edits, insertions, posteriors, duration posteriors of the clips the search aligned, each call on a sub-batch and on
-    the lattice its clips were searched on (AlignBatch.scored_on: the search's PackedClips or tables packed again)."""
+    the lattice its clips were searched on (AlignBatch.scored_on: the search's PackedClips or tables packed again).  dur_table
+    (opts.duration_prior): the table of the explicit-duration search, for opts.duration_prior_scores."""
     scored = _Scored({}, {}, {}, {}, {}, {})
     ok = found.ok
     if not ok:
@@ -1268,6 +1298,29 @@ def _score(found, opts, sub_pairs) -> _Scored:
                     print(f"{found.paths[b]}: {FILLER_SCORES_PLAIN}")
                 d_post = AL.alignment_posteriors(*sub.args(), found.d_tok, frame_offsets=sub.f0, packed=packed)
                 _take_posteriors(found, part, d_post, "wfl_align_posterior", scored)
+    if opts.duration_prior_scores and found.batch.durs is not None:
+        # every clip on the lattice it was searched on: under the prior over the explicit-duration lattice, with the rows and the table
+        # of its search; a clip the prior left no path for was searched by wfl_align and is scored there
+        for with_prior in (True, False):
+            part = [b for b in ok if (b not in found.plain) == with_prior]
+            if not part:
+                continue
+            sub = found.batch.select(part)
+            packed = sub.pack(False)
+            if with_prior:
+                d = AL.duration_prior_posteriors(*sub.args(), sub.durs, dur_table, found.d_tok, frame_offsets=sub.f0, packed=packed)
+                _take_posteriors(found, part, (d[0], d[1], d[2], d[3], d[6]), "wfl_align_duration_prior_posterior", scored)
+                h_end, k0 = torch.stack([d[4], d[5]]).cpu().numpy(), 0
+                for b in part:
+                    n = len(found.batch.alts[b])
+                    if b in scored.raw:
+                        scored.ends[b] = (h_end[0, k0:k0 + n], h_end[1, k0:k0 + n])
+                    k0 += n
+            else:
+                for b in part:
+                    print(f"{found.paths[b]}: {DURATION_PRIOR_SCORES_PLAIN}")
+                d_post = AL.alignment_posteriors(*sub.args(), found.d_tok, frame_offsets=sub.f0, packed=packed)
+                _take_posteriors(found, part, d_post, "wfl_align_posterior", scored)
     return scored
 
 
@@ -1318,6 +1371,8 @@ DURATION_PRIOR_INFEASIBLE = ("no path of finite score under the duration prior (
                              "segmentation of these frames, or the search refused the clip); aligning the transcript without the prior")
 DURATION_SCORES_PLAIN = ("scored without minimum durations (postprocess.duration_scores: the file was searched without them, and a "
                          "score speaks of the lattice its search ran on)")
+DURATION_PRIOR_SCORES_PLAIN = ("scored by wfl_align_posterior (postprocess.duration_prior_scores: the prior left the file no path, so it "
+                               "was searched without the prior, and a score speaks of the lattice its search ran on)")
 FILLER_SCORES_PLAIN = ("scored by wfl_align_posterior (postprocess.filler_scores: the transcript has no filler, so the file was searched "
                        "on the lattice without a filler emission, and a score speaks of the lattice its search ran on)")
 DRAFT_INFEASIBLE = ("no path opens every token inside its draft window (two starts on one frame, or more tokens than frames in between); "
@@ -1552,6 +1607,16 @@ def _write_filler_scores(lab_path, rows):
         _write_text(filler_scores_path(lab_path), AL.format_filler_scores_tsv(rows), "Filler scores")
 
 
+def durations_path(lab_path):
+    return os.path.splitext(lab_path)[0] + ".durations.tsv"
+
+
+def _write_durations(lab_path, rows):
+    """`{stem}.durations.tsv` beside the .lab of a file that was scored over the explicit-duration lattice (None: no file)."""
+    if rows is not None:
+        _write_text(durations_path(lab_path), AL.format_durations_tsv(rows), "Token durations")
+
+
 def _write_score(lab_path, segments, score):
     """The scores file of one labelled file beside its .lab, by the kind of its score (None: no file)."""
     if isinstance(score, DC.FreeScore):
@@ -1565,7 +1630,8 @@ def infer_audio(audio_path, config_path="config.yaml", checkpoint_path="best_mod
                 align_scores=None, decode=None, switch_penalty=None, decode_scores=None, phoneme_bigram=None, bigram_weight=None,
                 align_draft=None, draft_tolerance=None, align_edits=None, align_insertions=None, min_duration=None,
                 duration_scores=None, optional_tokens=None, skip_penalty=None, optional_scores=None, filler_token=None,
-                filler_penalty=None, filler_scores=None, duration_prior=None, duration_prior_weight=None, bigram_scores=None):
+                filler_penalty=None, filler_scores=None, duration_prior=None, duration_prior_weight=None,
+                duration_prior_scores=None, bigram_scores=None):
     """align: "greedy" | "viterbi" | None (config postprocess.align, else greedy): how a `{audio}.txt` transcript is aligned
     (Labeler.label_files).  align_scores (viterbi only; None: config postprocess.align_scores): also write `{stem}.scores.tsv`
     beside the .lab when the file was Viterbi-aligned (format_scores_tsv).  decode: "argmax" | "viterbi" | None (config
@@ -1598,13 +1664,18 @@ def infer_audio(audio_path, config_path="config.yaml", checkpoint_path="best_mod
     the mean shift and spread of both its ends (align.filler_posteriors, align.format_filler_scores_tsv); the .lab and
     `{stem}.fillers.tsv` are what they are without it.  duration_prior / duration_prior_weight (align viterbi only; None: config
     postprocess.duration_prior / postprocess.duration_prior_weight): the phoneme duration prior of the explicit-duration search and
-    what its log probabilities are multiplied by (Labeler.label_files)."""
+    what its log probabilities are multiplied by (Labeler.label_files).  duration_prior_scores (with a duration_prior only; None:
+    config postprocess.duration_prior_scores): also write `{stem}.scores.tsv`, one row per transcript token summed over the lattice
+    the file was searched on, and, for a file searched under the prior, `{stem}.durations.tsv`, one row per token with its length,
+    the prior's log probability of it, the posterior of its run, the shift and spread of both its ends and its expected length
+    (align.duration_prior_posteriors, align.format_durations_tsv); the .lab is what it is without it."""
     given = dict(align=align, align_scores=align_scores, decode=decode, switch_penalty=switch_penalty, decode_scores=decode_scores,
                  phoneme_bigram=phoneme_bigram, bigram_weight=bigram_weight, bigram_scores=bigram_scores, align_draft=align_draft,
                  draft_tolerance=draft_tolerance, align_edits=align_edits, align_insertions=align_insertions, min_duration=min_duration,
                  duration_scores=duration_scores, optional_tokens=optional_tokens, skip_penalty=skip_penalty,
                  optional_scores=optional_scores, filler_token=filler_token, filler_penalty=filler_penalty,
-                 filler_scores=filler_scores, duration_prior=duration_prior, duration_prior_weight=duration_prior_weight)
+                 filler_scores=filler_scores, duration_prior=duration_prior, duration_prior_weight=duration_prior_weight,
+                 duration_prior_scores=duration_prior_scores)
     _refuse_before_load(config_path, **given)
     lab = _labeler(config_path, checkpoint_path, device)
     opts = lab.options(**given)
@@ -1614,9 +1685,10 @@ def infer_audio(audio_path, config_path="config.yaml", checkpoint_path="best_mod
     optional = {} if opts.optional_scores else None
     fillers = {} if opts.filler_token is not None else None
     fscores = {} if opts.filler_scores else None
+    durations = {} if opts.duration_prior_scores else None
     (segments,), (score,) = lab._label_scored([audio_path], opts, lang_id, confidence_threshold, True, edits=edits,
                                               insertions=insertions, skipped=skipped, optional=optional, fillers=fillers,
-                                              filler_scores=fscores)
+                                              filler_scores=fscores, durations=durations)
     if output_lab_path:
         if os.path.abspath(output_lab_path) == os.path.abspath(audio_path):
             # the reference would truncate the input WAV here (infer.py:410-411 + utils.py:77)
@@ -1635,6 +1707,8 @@ def infer_audio(audio_path, config_path="config.yaml", checkpoint_path="best_mod
             _write_fillers(output_lab_path, fillers.get(0))
         if fscores is not None:
             _write_filler_scores(output_lab_path, fscores.get(0))
+        if durations is not None:
+            _write_durations(output_lab_path, durations.get(0))
     return segments
 
 
@@ -1644,13 +1718,14 @@ def infer_folder(folder_path: str, config_path: str = "config.yaml", checkpoint_
                  decode_scores=None, phoneme_bigram=None, bigram_weight=None, align_draft=None, draft_tolerance=None,
                  align_edits=None, align_insertions=None, min_duration=None, duration_scores=None, optional_tokens=None,
                  skip_penalty=None, optional_scores=None, filler_token=None, filler_penalty=None, filler_scores=None,
-                 duration_prior=None, duration_prior_weight=None, bigram_scores=None):
+                 duration_prior=None, duration_prior_weight=None, duration_prior_scores=None, bigram_scores=None):
     given = dict(align=align, align_scores=align_scores, decode=decode, switch_penalty=switch_penalty, decode_scores=decode_scores,
                  phoneme_bigram=phoneme_bigram, bigram_weight=bigram_weight, bigram_scores=bigram_scores, align_draft=align_draft,
                  draft_tolerance=draft_tolerance, align_edits=align_edits, align_insertions=align_insertions, min_duration=min_duration,
                  duration_scores=duration_scores, optional_tokens=optional_tokens, skip_penalty=skip_penalty,
                  optional_scores=optional_scores, filler_token=filler_token, filler_penalty=filler_penalty,
-                 filler_scores=filler_scores, duration_prior=duration_prior, duration_prior_weight=duration_prior_weight)
+                 filler_scores=filler_scores, duration_prior=duration_prior, duration_prior_weight=duration_prior_weight,
+                 duration_prior_scores=duration_prior_scores)
     _refuse_before_load(config_path, **given)
     wav_files = sorted(f for f in os.listdir(folder_path) if f.lower().endswith(".wav"))
     os.makedirs(output_dir, exist_ok=True)
@@ -1670,8 +1745,9 @@ def infer_folder(folder_path: str, config_path: str = "config.yaml", checkpoint_
     optional = {} if opts.optional_scores else None
     fillers = {} if opts.filler_token is not None else None
     fscores = {} if opts.filler_scores else None
+    durations = {} if opts.duration_prior_scores else None
     all_segments, all_scores = (lab._label_scored(paths, opts, lang_id, confidence_threshold, True, moves, edits, insertions, skipped,
-                                                  optional, fillers, fscores)
+                                                  optional, fillers, fscores, durations)
                                 if paths else ([], []))
     for fi, (wav_file, segments, score) in enumerate(zip(wav_files, all_segments, all_scores)):
         print(f"\nInferencing: {wav_file}")
@@ -1690,10 +1766,12 @@ def infer_folder(folder_path: str, config_path: str = "config.yaml", checkpoint_
             _write_fillers(lab_path, fillers.get(fi))
         if fscores is not None:
             _write_filler_scores(lab_path, fscores.get(fi))
+        if durations is not None:
+            _write_durations(lab_path, durations.get(fi))
         print("Predicted segments:")
         for start, end, ph in segments:
             print(f"({round(start, 2)}, {round(end, 2)}, {ph})")
-    if opts.align_scores or opts.duration_scores or opts.optional_scores or opts.filler_scores:
+    if opts.align_scores or opts.duration_scores or opts.optional_scores or opts.filler_scores or opts.duration_prior_scores:
         name = "alignment_scores.tsv" if world == 1 else f"alignment_scores.rank{rank}.tsv"
         _write_text(os.path.join(output_dir, name),
                     format_review_tsv([(f, sc) for f, sc in zip(wav_files, all_scores) if isinstance(sc, AL.FileScore)]), "Review list")
@@ -1725,6 +1803,11 @@ def infer_folder(folder_path: str, config_path: str = "config.yaml", checkpoint_
         name = "filler_scores.tsv" if world == 1 else f"filler_scores.rank{rank}.tsv"
         _write_text(os.path.join(output_dir, name), AL.format_folder_filler_scores_tsv([(wav_files[fi], fscores[fi]) for fi in sorted(fscores)]),
                     "Filler scores of the folder")
+    if durations is not None:
+        name = "token_durations.tsv" if world == 1 else f"token_durations.rank{rank}.tsv"
+        _write_text(os.path.join(output_dir, name),
+                    AL.format_folder_durations_tsv([(wav_files[fi], durations[fi]) for fi in sorted(durations)]),
+                    "Token durations of the folder")
     if opts.free_scores:
         name = "decode_scores.tsv" if world == 1 else f"decode_scores.rank{rank}.tsv"
         _write_text(os.path.join(output_dir, name),
@@ -1837,10 +1920,17 @@ def main(argv=None):
     @click.option("--duration-prior-weight", "duration_prior_weight", type=float, default=None,
                   help="With --duration-prior: what the prior's log probabilities are multiplied by (>= 0). Default: config "
                        "postprocess.duration_prior_weight, else 1.0 (a value to start from, not a measured optimum).")
+    @click.option("--duration-prior-scores", "duration_prior_scores", is_flag=True, default=None,
+                  help="With --duration-prior: score every aligned file by a forward-backward pass over the explicit-duration "
+                       "lattice of its search on the GPU: {stem}.scores.tsv, one row per transcript token, and {stem}.durations.tsv, "
+                       "per token its length, the prior's log probability of it, the posterior of its run, the shift and spread "
+                       "of both its ends and its expected length; for a folder also alignment_scores.tsv and token_durations.tsv, "
+                       "the least probable length first. Default: config postprocess.duration_prior_scores, else off.")
     def cli(path, checkpoint, config, output, lang_id, sample, top_k, top_p, temperature, device, confidence_threshold, align,
             align_scores, decode, switch_penalty, decode_scores, phoneme_bigram, bigram_weight, bigram_scores, align_draft,
             draft_tolerance, align_edits, align_insertions, min_duration, duration_scores, optional_tokens, skip_penalty,
-            optional_scores, filler_token, filler_penalty, filler_scores, duration_prior, duration_prior_weight):
+            optional_scores, filler_token, filler_penalty, filler_scores, duration_prior, duration_prior_weight,
+            duration_prior_scores):
         if switch_penalty is not None and not switch_penalty >= 0.0:
             raise click.UsageError("--switch-penalty must be >= 0 (nats)")
         if sample:
@@ -1877,7 +1967,8 @@ def main(argv=None):
                            min_duration=parse_min_duration(min_duration), duration_scores=duration_scores,
                            optional_tokens=list(optional_tokens) or None, skip_penalty=skip_penalty, optional_scores=optional_scores,
                            filler_token=filler_token, filler_penalty=filler_penalty, filler_scores=filler_scores,
-                           duration_prior=duration_prior, duration_prior_weight=duration_prior_weight)
+                           duration_prior=duration_prior, duration_prior_weight=duration_prior_weight,
+                           duration_prior_scores=duration_prior_scores)
         except ValueError as err:
             raise click.UsageError(str(err))
         output_path = inf_path if output == "." else output
@@ -1905,7 +1996,8 @@ def main(argv=None):
                   filler_scores=opts.filler_scores,
                   # the prior travels as the bigram does: an empty path for "none", a weight only beside a prior
                   duration_prior=opts.duration_prior or "",
-                  duration_prior_weight=opts.duration_prior_weight if opts.duration_prior else None)
+                  duration_prior_weight=opts.duration_prior_weight if opts.duration_prior else None,
+                  duration_prior_scores=opts.duration_prior_scores)
         if inf_path.is_dir():
             infer_folder(folder_path=str(inf_path), output_dir=str(output_path), **kw)
         else:

@@ -62,6 +62,10 @@ infer_folder (before any model is loaded) and the CLI all call `resolve` and car
                                speak of one lattice
                            (39. with the model known, Labeler.label_files: a file counted on another frame duration, or one that
                                holds a phoneme that is no output name of the label set, is refused by name, durations.check)
+  duration_prior_scores off 40. a bool (true / false; no number, no string)
+                           41. needs a duration_prior (it scores the explicit-duration lattice of that search: per token the
+                               posterior of its run, the spread of both its ends and its expected length; without a prior
+                               align_scores is the option to ask for)
 """
 from __future__ import annotations
 
@@ -105,6 +109,10 @@ DURATION_PRIOR_ERROR = ("duration_prior cannot be combined with align_draft, min
                         "align_edits, align_insertions, duration_scores, optional_scores or filler_scores: their lattices carry no "
                         "duration term, and a search or a score must speak of one lattice; drop postprocess.duration_prior "
                         "(--duration-prior) for that run")
+
+
+DURATION_PRIOR_SCORES_ERROR = ("duration_prior_scores needs a duration_prior (postprocess.duration_prior, --duration-prior): it scores "
+                               "the explicit-duration lattice of that search; without a prior align_scores is the option to ask for")
 
 
 def _filler_token(given):
@@ -224,7 +232,8 @@ class PostOptions(_SearchOptions):
         filler_penalty   1.0    nats a filler pays per frame of its run (also stands for "not given")
         filler_scores    False  score every alignment searched with a filler_token, over the filler lattice
         duration_prior   None   path of a phoneme_durations.json: the duration prior of the explicit-duration search
-        duration_prior_weight  1.0  what the prior's log probabilities are multiplied by (also stands for "not given")"""
+        duration_prior_weight  1.0  what the prior's log probabilities are multiplied by (also stands for "not given")
+        duration_prior_scores  False  score every alignment searched under a duration_prior, over the explicit-duration lattice"""
     align_draft: Optional[str] = None
     draft_tolerance: float = DEFAULT_DRAFT_TOLERANCE
     align_edits: bool = False
@@ -239,11 +248,12 @@ class PostOptions(_SearchOptions):
     filler_scores: bool = False
     duration_prior: Optional[str] = None
     duration_prior_weight: float = DEFAULT_DURATION_PRIOR_WEIGHT
+    duration_prior_scores: bool = False
 
     def __new__(cls, *args, align_draft=None, draft_tolerance=DEFAULT_DRAFT_TOLERANCE, align_edits=False, align_insertions=False,
                 min_duration=None, duration_scores=False, optional_tokens=None, skip_penalty=0.0, optional_scores=False,
                 filler_token=None, filler_penalty=DEFAULT_FILLER_PENALTY, filler_scores=False, duration_prior=None,
-                duration_prior_weight=DEFAULT_DURATION_PRIOR_WEIGHT, **kw):
+                duration_prior_weight=DEFAULT_DURATION_PRIOR_WEIGHT, duration_prior_scores=False, **kw):
         self = super().__new__(cls, *args, **kw)
         object.__setattr__(self, "align_draft", align_draft)
         object.__setattr__(self, "draft_tolerance", draft_tolerance)
@@ -259,24 +269,26 @@ class PostOptions(_SearchOptions):
         object.__setattr__(self, "filler_scores", filler_scores)
         object.__setattr__(self, "duration_prior", duration_prior)
         object.__setattr__(self, "duration_prior_weight", duration_prior_weight)
+        object.__setattr__(self, "duration_prior_scores", duration_prior_scores)
         return self
 
     def __setattr__(self, name, value):
         raise AttributeError(f"PostOptions is read-only: cannot set {name!r}")
 
     _KEYWORD = ("align_draft", "draft_tolerance", "align_edits", "align_insertions", "min_duration", "duration_scores",
-                "optional_tokens", "skip_penalty", "duration_prior", "duration_prior_weight", "filler_scores", "optional_scores",
-                "filler_token", "filler_penalty")
+                "optional_tokens", "skip_penalty", "duration_prior", "duration_prior_weight", "filler_scores", "duration_prior_scores",
+                "optional_scores", "filler_token", "filler_penalty")
     # (the later options stand in front of optional_scores: the record's last fields are the filler's own two)
     _KEYWORD_DEFAULTS = (None, DEFAULT_DRAFT_TOLERANCE, False, False, None, False, None, 0.0, None, DEFAULT_DURATION_PRIOR_WEIGHT,
-                         False, False, None, DEFAULT_FILLER_PENALTY)
+                         False, False, False, None, DEFAULT_FILLER_PENALTY)
 
     def _draft(self):
         return self.align_draft, self.draft_tolerance
 
     @property
     def scored(self) -> bool:
-        return self.align_scores or self.free_scores or self.duration_scores or self.optional_scores or self.filler_scores
+        return (self.align_scores or self.free_scores or self.duration_scores or self.optional_scores or self.filler_scores
+                or self.duration_prior_scores)
 
     def _later(self):
         return tuple(getattr(self, k) for k in self._KEYWORD)
@@ -286,12 +298,13 @@ class PostOptions(_SearchOptions):
     def _make(cls, iterable, align_draft=None, draft_tolerance=DEFAULT_DRAFT_TOLERANCE, align_edits=False, align_insertions=False,
               min_duration=None, duration_scores=False, optional_tokens=None, skip_penalty=0.0, optional_scores=False,
               filler_token=None, filler_penalty=DEFAULT_FILLER_PENALTY, filler_scores=False, duration_prior=None,
-              duration_prior_weight=DEFAULT_DURATION_PRIOR_WEIGHT):
+              duration_prior_weight=DEFAULT_DURATION_PRIOR_WEIGHT, duration_prior_scores=False):
         return cls(*iterable, align_draft=align_draft, draft_tolerance=draft_tolerance, align_edits=align_edits,
                    align_insertions=align_insertions, min_duration=min_duration, duration_scores=duration_scores,
                    optional_tokens=optional_tokens, skip_penalty=skip_penalty, optional_scores=optional_scores,
                    filler_token=filler_token, filler_penalty=filler_penalty, filler_scores=filler_scores,
-                   duration_prior=duration_prior, duration_prior_weight=duration_prior_weight)
+                   duration_prior=duration_prior, duration_prior_weight=duration_prior_weight,
+                   duration_prior_scores=duration_prior_scores)
 
     def _replace(self, **kw):
         later = {k: kw.pop(k, getattr(self, k)) for k in self._KEYWORD}
@@ -329,7 +342,7 @@ def resolve(post, *, align=None, align_scores=None, decode=None, switch_penalty=
             bigram_weight=None, bigram_scores=None, align_draft=None, draft_tolerance=None, align_edits=None,
             align_insertions=None, min_duration=None, duration_scores=None, optional_tokens=None, skip_penalty=None,
             optional_scores=None, filler_token=None, filler_penalty=None, filler_scores=None, duration_prior=None,
-            duration_prior_weight=None) -> PostOptions:
+            duration_prior_weight=None, duration_prior_scores=None) -> PostOptions:
     """post: the config's `postprocess` mapping (None: {}).  Per option the argument wins; None leaves it to `post[<option>]`, and a
     key that is absent (or None) to the default.  -> PostOptions, or ValueError for the first broken rule of the module's table."""
     post = post or {}
@@ -456,9 +469,15 @@ def resolve(post, *, align=None, align_scores=None, decode=None, switch_penalty=
     if duration_prior and (align_draft or min_duration is not None or optional_tokens is not None or filler_token is not None
                            or align_scores or align_edits or align_insertions or duration_scores or optional_scores or filler_scores):
         raise ValueError(DURATION_PRIOR_ERROR)
+    duration_prior_scores = pick("duration_prior_scores", duration_prior_scores, False)
+    if not isinstance(duration_prior_scores, bool):
+        raise ValueError(f"duration_prior_scores must be true or false, got {duration_prior_scores!r}")
+    if duration_prior_scores and not duration_prior:
+        raise ValueError(DURATION_PRIOR_SCORES_ERROR)
     return PostOptions(align, align_scores, decode, switch_penalty, decode_scores, phoneme_bigram, bigram_weight, bigram_scores,
                        align_draft=align_draft, draft_tolerance=draft_tolerance, align_edits=align_edits,
                        align_insertions=align_insertions, min_duration=min_duration, duration_scores=duration_scores,
                        optional_tokens=optional_tokens, skip_penalty=skip_penalty, optional_scores=optional_scores,
                        filler_token=filler_token, filler_penalty=filler_penalty, filler_scores=filler_scores,
-                       duration_prior=duration_prior, duration_prior_weight=duration_prior_weight)
+                       duration_prior=duration_prior, duration_prior_weight=duration_prior_weight,
+                       duration_prior_scores=duration_prior_scores)
