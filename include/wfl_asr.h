@@ -698,6 +698,44 @@ int32_t wfl_align_duration_prior_posterior(const float* logits, int64_t ldl, int
                                            void* workspace, int64_t workspace_bytes, float* logz, float* tok_post, float* start_mean,
                                            float* start_sd, float* end_mean, float* end_sd, int32_t* status, void* stream);
 
+/* ---- Expected run-length counts over the same explicit-duration lattice: the E-step of a duration prior's re-estimation from audio and
+ * transcripts alone (wfl-asr_amd/align.py duration_prior_expected_counts, `python -m wfl_asr_amd.adapt_durations`; the counts
+ * instantiations of csrc/align_duration_prior_posterior.hip).  The arguments are wfl_align_duration_prior_posterior's without tok: the
+ * sums run over all paths, no search is needed.  With d_k the length of token k's run under the path posterior, outputs (device, float32):
+ *   logz[b]          as wfl_align_duration_prior_posterior's;
+ *   dur_post[k][j]   (rows as tok_cls, D + 1 columns: the layout of a table row)
+ *                      j = 0 .. D - 2   P(d_k = j + 1)
+ *                      j = D - 1        P(d_k >= D)
+ *                      j = D            E[max(d_k - D, 0)]
+ *                    the statistics wfl-asr_amd/durations.py estimate() counts in .lab files (c[d], c_ge, excess).
+ * The posterior that token k opens at frame t and lasts exactly d < D frames is
+ *     p_k(t, d) = exp(aR_k^1(t) + L_k(d) + Q_k^{t+d-1}(t) - logZ)
+ *     Q_k^e(t)  = EI_{t+1}(k) + .. + EI_e(k) + bE_{k+1}(e),    Q_k^t(t) = bE_{k+1}(t),    Q_k^e(t-1) = EI_t(k) + Q_k^e(t)
+ * (a third ring of D - 1 floats per slot carried by the backward sweep beside W, renormalised with it and part of beta's maximum), and
+ *     P(d_k = d)         = sum_t p_k(t, d)                                     d < D, only where start_k(t) != 0 in fp32: p <= start
+ *     P(d_k >= D)        = sum_t exp(aR_k^D(t) + L_k(D) + V_k(t) - logZ)       frame t the D-th frame of the run: once per such run
+ *     E[max(d_k - D, 0)] = sum_t exp(aY_k(t) + V_k(t) - logZ)                  frame t in the tail: once per frame past the D-th
+ * each a sum of non-negative terms in double by the thread that owns the token; nothing is formed as a difference.  An entry the table
+ * forbids (L = -inf) is exactly 0.0; at D = 1 there is no ring and column 0 is P(d >= 1).  A token with tok_dur -1 is computed like any
+ * other, with L = 0 and tail 0.
+ * status[b]: wfl_align_duration_prior_posterior's codes without 8.  A clip with status != 0 gets zeros in logz and in its dur_post rows
+ * and does not disturb its batch; a clip alone equals the same clip inside any batch, bit for bit.  Host-side negative returns:
+ * wfl_align_duration_prior's, a null dur_post while any token is present, a workspace that is too small.
+ * Workspace, per clip in 4-byte words (0 for T = 0), in the notation of wfl_align_duration_prior_posterior_workspace_bytes:
+ *     round_up_64(T) + round_up_64(2 nblk) + nblk (3 + D) slots(N) + 384 slots(N) + 2 (D + 1) slots(N)
+ *         + (2 - min(2, r)) round_up_64(slots(N) D) + (r < 3 ? round_up_64(slots(N) (D - 1)) : 0)
+ * (the block holds aR^1, aY and aR^D, three floats per slot and frame; the D + 1 double sums of a slot are always in the workspace),
+ * r = count_rings(N, D) how many of alpha's ring, W and Q, in that order, fit room(N): 3 where slots(N) (3 D - 1) words fit, else 2 where
+ * 2 slots(N) D fit, else 1 where slots(N) D fit, else 0 -- N <= 127: 3 at every D; N <= 511: 3 up to D = 18, 2 up to 27, 1 above;
+ * N <= 1023: 3 up to D = 8, 2 up to 12, 1 up to 24, 0 above; N <= 2047: 3 up to D = 3, 2 at D = 4, 1 up to 9, 0 above; above that 0. */
+int64_t wfl_align_duration_prior_counts_workspace_bytes(const int32_t* n_frames_host, const int32_t* n_tok_host, int32_t n_clips,
+                                                        int32_t D);
+int32_t wfl_align_duration_prior_counts(const float* logits, int64_t ldl, int32_t C, int32_t o_id, const int64_t* frame_off_host,
+                                        const int32_t* n_frames_host, const int32_t* tok_off_host, const int32_t* n_tok_host,
+                                        const int32_t* tok_cls, const int32_t* tok_win, const int32_t* gap_cls, int32_t n_clips,
+                                        const int32_t* tok_dur, const float* dur, int32_t n_rows, int32_t D, void* workspace,
+                                        int64_t workspace_bytes, float* logz, float* dur_post, int32_t* status, void* stream);
+
 /* ---- Single-edit scores of an aligned transcript (`postprocess.align_edits`; wfl-asr_amd/align.py, csrc/align_edits.hip).  No
  * counterpart in the reference.  The arguments are wfl_align_posterior_windowed's without tok; tok_win may be null: the unwindowed
  * lattice.  sub_cls (device, [n_sub][2] int32 = (B class, I class)) is a table of P = n_sub substitutes, 0 <= P <= 512.  With logZ(.)

@@ -93,6 +93,8 @@ SIGNATURES = {
     "wfl_align_duration_prior_posterior_workspace_bytes": (_L, [_P, _P, _I, _I]),
     "wfl_align_duration_prior_posterior": (_I, [_P, _L, _I, _I, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _I, _I, _P, _P, _L,
                                                  _P, _P, _P, _P, _P, _P, _P, _P]),
+    "wfl_align_duration_prior_counts_workspace_bytes": (_L, [_P, _P, _I, _I]),
+    "wfl_align_duration_prior_counts": (_I, [_P, _L, _I, _I, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _I, _I, _P, _L, _P, _P, _P, _P]),
     "wfl_align_posterior_workspace_bytes": (_L, [_P, _P, _I]),
     "wfl_align_posterior": (_I, [_P, _L, _I, _I, _P, _P, _P, _P, _P, _P, _I, _P, _P, _L, _P, _P, _P, _P, _P, _P]),
     "wfl_align_posterior_windowed": (_I, [_P, _L, _I, _I, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _L, _P, _P, _P, _P, _P, _P]),

@@ -33,6 +33,8 @@ token gets one contiguous, time-ordered run of frames, none is dropped.
                         `postprocess.duration_prior_scores`): alignment_posteriors' outputs and the moments of every token's end
   token_durations / format_durations_tsv / format_folder_durations_tsv   one file's TokenDuration rows, {stem}.durations.tsv, the
                         folder's list, the least probable length first
+  duration_prior_expected_counts  every token's run-length posterior over that lattice (`wfl_align_duration_prior_counts`): the
+                        E-step of durations.reestimate, `python -m wfl_asr_amd.adapt_durations`
   alignment_posteriors  forward-backward over the same lattice (csrc/align_posterior.h, `wfl_align_posterior`; of a batch packed with
                         windows, `wfl_align_posterior_windowed`): logZ, and per token
                         the posterior of the run Viterbi chose and the spread of its start (`postprocess.align_scores`)
@@ -111,6 +113,11 @@ def duration_prior_workspace_bytes(n_frames, n_tokens, max_frames) -> int:
 def duration_prior_posterior_workspace_bytes(n_frames, n_tokens, max_frames) -> int:
     """max_frames: D, as duration_prior_workspace_bytes'."""
     return _workspace_bytes("wfl_align_duration_prior_posterior_workspace_bytes", n_frames, n_tokens, int(max_frames))
+
+
+def duration_prior_counts_workspace_bytes(n_frames, n_tokens, max_frames) -> int:
+    """max_frames: D, as duration_prior_workspace_bytes'."""
+    return _workspace_bytes("wfl_align_duration_prior_counts_workspace_bytes", n_frames, n_tokens, int(max_frames))
 
 
 def optional_posterior_workspace_bytes(n_frames, n_tokens) -> int:
@@ -387,6 +394,7 @@ _ENTRIES = {
     "wfl_align_filler_posterior": ("wfl_align_filler_posterior", True, False),
     "wfl_align_duration_prior": ("wfl_align_duration_prior", True, False),
     "wfl_align_duration_prior_posterior": ("wfl_align_duration_prior_posterior", True, False),
+    "wfl_align_duration_prior_counts": ("wfl_align_duration_prior_counts", True, False),
 }
 
 
@@ -617,6 +625,46 @@ def duration_prior_posteriors(logits, n_frames, token_classes, gap_classes, o_id
               (logz[lo:], per_tok[0], per_tok[1], per_tok[2], per_tok[3], per_tok[4], status[lo:]), stream,
               temporaries=(d_dur, d_tab), sized_by=(D,))
     return (logz[:nb], per_tok[0, :ntok], per_tok[1, :ntok], per_tok[2, :ntok], per_tok[3, :ntok], per_tok[4, :ntok], status[:nb])
+
+
+def duration_prior_expected_counts(logits, n_frames, token_classes, gap_classes, o_id, tok_rows, table, frame_offsets=None, stream=None,
+                                   packed=None, windows=None):
+    """The posterior distribution of every token's run length over the explicit-duration lattice of viterbi_align_duration_prior, for
+    the same ragged batch of clips (same arguments, the same `tok_rows` and `table`; no `tok`: the sums run over all paths) -- the
+    E-step of durations.reestimate (wfl_align_duration_prior_counts).
+
+    tok_rows, table  as viterbi_align_duration_prior's
+    windows          as viterbi_align_duration_prior's; with `packed`, the ones packed there.  A batch packed with `min_frames` is
+                     refused
+    -> (logz [clips] float32, dur_post [tokens, D + 1] float32, status [clips] int32): a token's row, in the order of the clips'
+    tokens, has the layout of a table row -- columns 0 .. D - 2 are P(d = 1) .. P(d = D - 1), column D - 1 is P(d >= D), column D is
+    E[max(d - D, 0)]: what durations.estimate counts in `.lab` files.  An entry the table forbids is exactly 0.  A token whose row is
+    -1 is computed like any other, with L = 0 and tail 0.  STATUS_INFEASIBLE: fewer frames than tokens, or the table (and the windows)
+    leave no path; STATUS_BAD_CLASS also for a row outside -1 .. rows - 1.  A clip with status != 0 gets zeros.  Large batches run in
+    groups whose workspace stays under EDITS_WORKSPACE_LIMIT (edit_groups), each clip's outputs the same as in one call."""
+    if packed is None:
+        packed = pack_clips(logits, n_frames, token_classes, gap_classes, frame_offsets, windows)
+    if packed.d_min is not None:
+        raise ValueError("duration_prior_expected_counts has no minimum durations: this batch was packed with min_frames")
+    nb, ntok, dev = packed.nb, int(packed.N.sum()), logits.device
+    d_tab, n_rows, D = _upload_duration_table(table, dev)
+    d_dur = tok_rows if isinstance(tok_rows, torch.Tensor) else upload_durations(tok_rows, packed.N, dev)
+    if d_dur.device != dev or d_dur.dtype != torch.int32 or d_dur.dim() != 1 or d_dur.stride(0) != 1 or d_dur.shape[0] != max(ntok, 1):
+        raise ValueError("uploaded table rows must be upload_durations' [tokens] int32 tensor for this batch")
+    logz = torch.empty(max(nb, 1), dtype=torch.float32, device=dev)
+    dur_post = torch.empty((max(ntok, 1), D + 1), dtype=torch.float32, device=dev)
+    status = torch.empty(max(nb, 1), dtype=torch.int32, device=dev)
+    groups = edit_groups(packed.T, packed.N, workspace_bytes=lambda t, n: duration_prior_counts_workspace_bytes(t, n, D))
+    for grp in groups or [[]]:
+        if len(groups) <= 1:                 # (groups of consecutive clips, as duration_prior_posteriors')
+            sub, lo = packed, 0
+        else:
+            lo, hi = grp[0], grp[-1] + 1
+            sub = packed._replace(nb=hi - lo, T=packed.T[lo:hi], N=packed.N[lo:hi], F0=packed.F0[lo:hi], K0=packed.K0[lo:hi],
+                                  d_gc=packed.d_gc[lo:hi])
+        _call("wfl_align_duration_prior_counts", logits, o_id, sub, (d_dur, d_tab, n_rows, D), (logz[lo:], dur_post, status[lo:]),
+              stream, temporaries=(d_dur, d_tab), sized_by=(D,))
+    return logz[:nb], dur_post[:ntok], status[:nb]
 
 
 def upload_filler(fillers, n_tokens, device):

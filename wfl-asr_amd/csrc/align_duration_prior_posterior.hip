@@ -39,6 +39,20 @@
 //
 // Every RENORM frames the block's maximum over G, X, Y and the ring (bE, V and the ring) is taken off all of them, alpha and beta
 // separately, into a double: nothing is summed over the clip in fp32, a ring entry is at most D frames old.
+//
+// The counts side (wfl_align_duration_prior_counts; dpp_kernel's CNT = true): the same three sweeps without tok, and per token the
+// posterior distribution of its run's length in the layout of a table row -- P(d = 1) .. P(d = D - 1), P(d >= D), E[max(d - D, 0)].
+// The posterior that token k opens at t and lasts exactly d < D frames:
+//   p_k(t, d) = exp(aR_k^1(t) + L_k(d) + Q_k^{t+d-1}(t) - logZ)
+//   Q_k^e(t)  = EI_{t+1}(k) + .. + EI_e(k) + bE_{k+1}(e)   e = t .. t + D - 2;   Q_k^t(t) = bE_{k+1}(t),  Q_k^e(t-1) = EI_t(k) + Q_k^e(t)
+// Q is beta's third ring, D - 1 floats per slot, entry e in word e mod (D - 1), updated in place (the entry of frame t takes the word
+// of the one D - 1 frames later), renormalised with W and part of beta's maximum.  W^1(t) is the log-sum of L(d) + Q^{t+d-1}(t) over
+// d < D joined with the D / tail term: p(t, d) <= start(t), and a start gamma of 0 skips the D - 1 exponentials.  The two tail
+// statistics are sums of non-negative terms as well, no differences: P(d >= D) = sum_t exp(aR^D(t) + L(D) + V(t) - logZ), frame t the
+// D-th frame of the run, and E[max(d - D, 0)] = sum_t exp(aY(t) + V(t) - logZ), frame t in the tail; so the block buffer holds
+// (aR^1, aY, aR^D), three floats per slot and frame.  The D + 1 double sums of a slot live in the clip's workspace.  Up to three rings
+// go to LDS, alpha's, W, Q in that order: count_rings_in_lds().  What is the posterior side's alone: tok, first[] / last[], the run
+// validation, the seven moment sums; its instantiations are the code they were before the switch.
 #include "lattice_sums.h"
 #include "wfl_asr.h"
 
@@ -52,6 +66,7 @@ constexpr int POST_W = 128;                 // frames per recomputed block
 static_assert(POST_W % RENORM == 0, "a block ends on a renormalisation");
 constexpr int MAX_D = 32;
 constexpr int LDS_CAP = 160 * 1024;
+constexpr double COUNT_SHIFT = 64 * 0.69314718055994530942;   // 64 ln 2: the scale of the counts side's gammas
 
 struct DppLaunch {
   const float* logits;
@@ -63,10 +78,10 @@ struct DppLaunch {
   const int* tok_dur;  // [total tokens] row of `dur`, -1 none
   const float* dur;    // [n_rows][D + 1]
   int n_rows, D;
-  const int* tok;      // the search's output
+  const int* tok;      // the search's output (the counts side: null, never read)
   float* ws;           // LatClip::ws_off: the clip's workspace, in floats
   float* logz;
-  float* tok_post;
+  float* tok_post;     // (the counts side: dur_post [total tokens][D + 1]; the four below unused)
   float* start_mean;
   float* start_sd;
   float* end_mean;
@@ -103,14 +118,28 @@ struct CfgDpp : LdsBase<NT, R, 2 * NT * R * 4 + 4 * NT * 4> {   // its own betwe
   // windows in LDS, in the words of first[] and last[] once tok has been judged
   static constexpr bool ACC_MEM = R >= 8;
   static constexpr long ACC = ACC_MEM ? SLOTS * (7 * 2 + 2) : 0;         // floats
+  // ---- the counts side (wfl_align_duration_prior_counts): a third ring, beta's Q, D - 1 floats per slot, placed behind the other two
+  static constexpr long qring_words(int D) { return SLOTS * (D - 1); }
+  static constexpr int count_rings_in_lds(int D) {                       // alpha's, W, Q, in that order: how many of them fit
+    const long room = (LDS_CAP - OFF_RING) / 4, rw = ring_words(D);
+    return 2 * rw + qring_words(D) <= room ? 3 : 2 * rw <= room ? 2 : rw <= room ? 1 : 0;
+  }
+  static constexpr int COUNT_MAX_RINGS = count_rings_in_lds(1), COUNT_MIN_RINGS = count_rings_in_lds(32);
+  static constexpr int count_lds_bytes(int D) {
+    const int n = count_rings_in_lds(D);
+    return OFF_RING + (int)((n >= 2 ? 2 : n) * ring_words(D) + (n >= 3 ? qring_words(D) : 0)) * 4;
+  }
+  static constexpr long COUNT_BLK = SLOTS * 3;                            // aR^1, aY and aR^D of every slot, one frame
+  static constexpr long count_acc(int D) { return SLOTS * (D + 1) * 2; }  // a row of D + 1 double sums per slot, always in the workspace
 };
 
 // a clip's workspace in floats: [lse: round64(T)] [checkpoint offsets: round64(2 nblk)] [checkpoints: nblk SC] [block: POST_W BLK]
 // [the sums where they are not in registers: ACC] [alpha's ring: round64(RW) unless in LDS] [beta's ring: the same]
+// [the counts side's Q ring: round64(RQ) unless in LDS; RQ = 0 on the posterior side]
 struct DppLayout {
-  long ckacc, ckpt, blk, sums, ringf, ringb, total;
+  long ckacc, ckpt, blk, sums, ringf, ringb, ringq, total;
   int nblk;
-  __host__ __device__ DppLayout(int T, long SC, long BLK, long ACC, long RW, int in_lds) {
+  __host__ __device__ DppLayout(int T, long SC, long BLK, long ACC, long RW, int in_lds, long RQ = 0) {
     nblk = (T + POST_W - 1) / POST_W;
     ckacc = round64(T);
     ckpt = ckacc + round64(2L * nblk);
@@ -118,12 +147,16 @@ struct DppLayout {
     sums = blk + (long)POST_W * BLK;
     ringf = sums + ACC;
     ringb = ringf + (in_lds >= 1 ? 0 : round64(RW));
-    total = ringb + (in_lds >= 2 ? 0 : round64(RW));
+    ringq = ringb + (in_lds >= 2 ? 0 : round64(RW));
+    total = ringq + (in_lds >= 3 ? 0 : round64(RQ));
   }
 };
 
-// HL: how many of the two rings are in LDS (0 | 1: alpha's | 2: both)
-template <int NT, int R, int HL>
+// HL: how many of the rings are in LDS (0 | 1: alpha's | 2: beta's W as well | 3, the counts side alone: its Q too)
+// CNT: false the posteriors of wfl_align_duration_prior_posterior (tok, first / last, the run validation, the seven moment sums);
+// true the expected length counts of wfl_align_duration_prior_counts (no tok; the Q ring and a histogram row per slot), which writes
+// its dur_post through the launch's tok_post pointer
+template <int NT, int R, int HL, bool CNT>
 __global__ __launch_bounds__(NT) void dpp_kernel(DppLaunch a) {
   using K = CfgDpp<NT, R>;
   extern __shared__ __attribute__((aligned(16))) char lds[];
@@ -144,11 +177,13 @@ __global__ __launch_bounds__(NT) void dpp_kernel(DppLaunch a) {
   const int tid = threadIdx.x;
   const int T = cl.T, N = cl.N, C = a.C, D = a.D, D1 = a.D + 1;
   const float* Z = a.logits + cl.frame_off * a.ldl;
-  const int* tokp = a.tok + cl.frame_off;
+  const int* tokp = a.tok + cl.frame_off;      // (CNT: never read)
   const float NEG = -INFINITY;
 
   auto zeros = [&](int code) {
-    for (int k = tid; k < N; k += NT) {
+    if constexpr (CNT) {
+      for (long w = tid; w < (long)N * D1; w += NT) a.tok_post[(long)cl.tok_off * D1 + w] = 0.f;
+    } else for (int k = tid; k < N; k += NT) {
       a.tok_post[cl.tok_off + k] = 0.f;
       a.start_mean[cl.tok_off + k] = 0.f;
       a.start_sd[cl.tok_off + k] = 0.f;
@@ -197,13 +232,25 @@ __global__ __launch_bounds__(NT) void dpp_kernel(DppLaunch a) {
   int fst[R], lst[R];
   bool notpath;
   const long SC = K::ckpt_floats(D);
-  const DppLayout lay(T, SC, K::BLK, K::ACC, K::ring_words(D), HL);
+  const DppLayout lay = CNT ? DppLayout(T, SC, K::COUNT_BLK, K::count_acc(D), K::ring_words(D), HL, K::qring_words(D))
+                            : DppLayout(T, SC, K::BLK, K::ACC, K::ring_words(D), HL);
+  constexpr int BW = CNT ? 3 : 2;               // floats per slot and frame of the block buffer
   float* ws = a.ws + cl.ws_off;
   // (what a thread keeps for itself in the workspace lies together, thread by thread: one base address and immediate offsets, where
   // an interleaved layout makes the compiler keep an address per slot in registers)
   double* gsum = (double*)(ws + lay.sums) + tid * (7 * R);             // ACC_MEM: sum i of slot r at gsum[7 r + i]
   int* gends = (int*)(ws + lay.sums + K::SLOTS * 14) + tid * (2 * R);  // and its (first, last) at gends[2 r], gends[2 r + 1]
-  {
+  double* hsum = (double*)(ws + lay.sums) + tid * (R * D1);            // CNT: entry j of slot r's row at hsum[r D1 + j]
+  if constexpr (CNT) {                          // no tok to judge: the windows go to their LDS words at once (a thread's own words)
+    if constexpr (AM) {
+#pragma unroll
+      for (int r = 0; r < R; ++r) {
+        first[r * NT + tid] = wn[r].x;
+        last[r * NT + tid] = wn[r].y;
+      }
+    }
+    notpath = false;
+  } else {
 #pragma unroll
     for (int r = 0; r < R; ++r) { first[tid * R + r] = INT_MAX; last[tid * R + r] = -1; }
     __syncthreads();                            // (and every thread has read misc[3] before misc[0] is raised)
@@ -273,6 +320,18 @@ __global__ __launch_bounds__(NT) void dpp_kernel(DppLaunch a) {
   auto bi = [&](int q, int r) -> unsigned {
     if constexpr (HL >= 2) return (q * R + r) * NT + tid;
     else return (tid * D + q) * R + r;
+  };
+  // CNT: beta's Q ring, DQ = D - 1 words per slot, entry e (the run's last frame) in word e mod DQ
+  const int DQ = D - 1;
+  float* qring = HL >= 3 ? lrings + 2 * K::ring_words(D) : ws + lay.ringq;
+  auto qi = [&](int q, int r) -> unsigned {
+    if constexpr (HL >= 3) return (q * R + r) * NT + tid;
+    else return (tid * DQ + q) * R + r;
+  };
+  auto each_q = [&](auto&& f) {
+    for (int q = 0; q < DQ; ++q)
+#pragma unroll
+      for (int r = 0; r < R; ++r) f(qi(q, r));
   };
   // f(word) over every entry of this thread's part of a ring
   auto each_f = [&](auto&& f) {
@@ -355,7 +414,7 @@ __global__ __launch_bounds__(NT) void dpp_kernel(DppLaunch a) {
       const float nb = (tid > 0 ? xf[((t + 1) & 1) * NT + tid - 1] : NEG) - sub;
       // aR^1 goes to the block buffer as it is made, on the scale of BEFORE this frame's renormalisation (offa[0][]), aX after it, on
       // the scale of after (offa[1][]): no aR^1 stays in a register across the slots
-      float* o = blk + (long)(t - t0) * K::BLK + tid * (2 * R);        // [thread][slot](aR^1, aX)
+      float* o = blk + (long)(t - t0) * (K::SLOTS * BW) + tid * (BW * R);   // [thread][slot](aR^1, aX), CNT: (aR^1, aY, aR^D)
       if (keep && tid == 0) offa[t - t0] = acc;
 #pragma unroll
       for (int r = R - 1; r >= 0; --r) {        // descending: slot r - 1's previous-frame X is still in place
@@ -373,7 +432,7 @@ __global__ __launch_bounds__(NT) void dpp_kernel(DppLaunch a) {
           Y[r] = (lae2(Y[r], old + Ld(lb, has, D - 1)) + ei) + Ld(lb, has, D);
           const float r1 = ent + eb;
           fring[fi(p, r)] = r1;
-          if (keep) o[r * 2 + 0] = r1;
+          if (keep) o[r * BW + 0] = r1;
           // pass 1: the runs that began at t - j + 1 gain EI_t; the maximum of the D + 1 candidates
           float m = fmaxf(r1 + Ld(lb, has, 0), Y[r]);
           for (int j = 2; j <= D; ++j) {
@@ -418,7 +477,14 @@ __global__ __launch_bounds__(NT) void dpp_kernel(DppLaunch a) {
       }
       if (keep) {                               // what of the block's alpha meets beta, for the backward sweep of the same thread
 #pragma unroll
-        for (int r = 0; r < R; ++r) o[r * 2 + 1] = X[r];
+        for (int r = 0; r < R; ++r) {
+          if constexpr (CNT) {                  // (p is (t + 1) mod D by now: the word of the run that is D frames old, aR^D(t))
+            o[r * BW + 1] = Y[r];
+            o[r * BW + 2] = fring[fi(p, r)];
+          } else {
+            o[r * BW + 1] = X[r];
+          }
+        }
         if (tid == 0) offa[POST_W + t - t0] = acc;
       } else if ((t + 1) % POST_W == 0 && t + 1 < T) {   // (a block ends on a renormalisation: sub is spent)
         float* o = ckpt + (long)((t + 1) / POST_W) * SC;
@@ -465,13 +531,19 @@ __global__ __launch_bounds__(NT) void dpp_kernel(DppLaunch a) {
     bE[r] = tid * R + r == N ? 0.f : NEG;
     V[r] = NEG;
     eip[r] = 0.f;
+    if constexpr (CNT) {
+      for (int j = 0; j < D1; ++j) hsum[r * D1 + j] = 0.0;
+    } else {
 #pragma unroll
-    for (int i = 0; i < 7; ++i) {
-      if constexpr (AM) gsum[r * 7 + i] = 0.0;
-      else sums[r][i] = 0.0;
+      for (int i = 0; i < 7; ++i) {
+        if constexpr (AM) gsum[r * 7 + i] = 0.0;
+        else sums[r][i] = 0.0;
+      }
     }
   }
   each_b([&](unsigned w, int, int) { bring[w] = NEG; });
+  if constexpr (CNT) each_q([&](unsigned w) { qring[w] = NEG; });
+  int pq = DQ > 0 ? (T - 1) % DQ : 0;           // CNT: t mod DQ, the word of Q^t(t)
   xb[(T & 1) * NT + tid] = bE[0];
   double accb = 0.0;                            // what beta's renormalisations subtracted
   float subb = 0.f;
@@ -489,7 +561,7 @@ __global__ __launch_bounds__(NT) void dpp_kernel(DppLaunch a) {
       }
       const float nbE = (tid + 1 < NT ? xb[((t + 1) & 1) * NT + tid + 1] : NEG) - subb;     // bE(t) of the next thread's first slot
       const double cst1 = offa[t - t_lo] + accb - logZ, cst = offa[POST_W + t - t_lo] + accb - logZ;     // for aR^1, for aX
-      const float* ab = blk + (long)(t - t_lo) * K::BLK + tid * (2 * R);
+      const float* ab = blk + (long)(t - t_lo) * (K::SLOTS * BW) + tid * (BW * R);
       float W1[R];
       const int q1 = pb + 1 >= D ? pb + 1 - D : pb + 1;
 #pragma unroll
@@ -511,6 +583,33 @@ __global__ __launch_bounds__(NT) void dpp_kernel(DppLaunch a) {
           bring[bi(pb, r)] = Ld(lb, has, D - 1) + V[r];
           W1[r] = bring[bi(q1, r)];
           // the gammas of frame t
+          if constexpr (CNT) {
+            // Q(t) from bE_{k+1}(t) and Q(t+1): the run that ends on t takes the word of the one that ended on t + D - 1
+            for (int q = 0; q < DQ; ++q)
+              if (q != pq) qring[qi(q, r)] = ep + qring[qi(q, r)];
+            if (DQ > 0) qring[qi(pq, r)] = nE;
+            double* h = hsum + r * D1;
+            // The counts' gammas are formed 2^64 times their size and the row is scaled back in double at the end: an fp32
+            // exponential is 0 below 2^-126 (or a denormal of a few bits), and a length that takes 1e-40 of the mass in each of a
+            // thousand frames is still an output fp32 can write; on this scale a term counts down to 2^-190.  (A posterior is at
+            // most 1: 2^64 times it is far inside fp32.)
+            const double c1 = cst1 + COUNT_SHIFT, c2 = cst + COUNT_SHIFT;
+            // a run of exactly d < D frames from t: p(t, d) <= start(t), so a start gamma of 0 has nothing to add
+            if (__expf((float)((double)ab[r * BW + 0] + (double)W1[r] + c1)) != 0.f) {
+              int q = pq;
+              for (int d = 1; d < D; ++d) {
+                const float pd = __expf((float)((double)ab[r * BW + 0] + (double)(Ld(lb, has, d - 1) + qring[qi(q, r)]) + c1));
+                if (pd != 0.f) h[d - 1] += (double)pd;
+                q = q + 1 == DQ ? 0 : q + 1;
+              }
+            }
+            // frame t as the D-th frame of a run (every run of D frames or more has exactly one), and as a frame of the tail
+            const float gd = __expf((float)((double)ab[r * BW + 2] + (double)(Ld(lb, has, D - 1) + V[r]) + c2));
+            const float gy = __expf((float)((double)ab[r * BW + 1] + (double)V[r] + c2));
+            if (gd != 0.f) h[D - 1] += (double)gd;
+            if (gy != 0.f) h[D] += (double)gy;
+            continue;
+          }
           const float gs = __expf((float)((double)ab[r * 2 + 0] + (double)W1[r] + cst1));
           const float ge = __expf((float)((double)ab[r * 2 + 1] + (double)nE + cst));
           // occ summed over the run [f, l]: a start at s counts for the run's frames >= s, an end at e against those > e
@@ -535,6 +634,7 @@ __global__ __launch_bounds__(NT) void dpp_kernel(DppLaunch a) {
         }
       }
       pb = pb + 1 == D ? 0 : pb + 1;            // (-(t - 1)) mod D
+      pq = pq == 0 ? max(DQ - 1, 0) : pq - 1;   // (t - 1) mod DQ
       if (t == 0) break;
       // bE(t - 1)
       const float* rowz = stage.row(c, tin);
@@ -555,6 +655,7 @@ __global__ __launch_bounds__(NT) void dpp_kernel(DppLaunch a) {
 #pragma unroll
         for (int r = 0; r < R; ++r) lm = fmaxf(lm, fmaxf(bE[r], V[r]));
         each_b([&](unsigned w, int, int) { lm = fmaxf(lm, bring[w]); });
+        if constexpr (CNT) each_q([&](unsigned w) { lm = fmaxf(lm, qring[w]); });
         renorm_publish(lm, wmax);
       }
       __syncthreads();
@@ -565,6 +666,7 @@ __global__ __launch_bounds__(NT) void dpp_kernel(DppLaunch a) {
 #pragma unroll
         for (int r = 0; r < R; ++r) { bE[r] -= M; V[r] -= M; }
         each_b([&](unsigned w, int, int) { bring[w] -= M; });
+        if constexpr (CNT) each_q([&](unsigned w) { qring[w] -= M; });
         subb = M;
         accb += (double)M;
       }
@@ -575,6 +677,11 @@ __global__ __launch_bounds__(NT) void dpp_kernel(DppLaunch a) {
 #pragma unroll
   for (int r = 0; r < R; ++r) {
     const int k = tid * R + r;
+    if constexpr (CNT) {
+      if (k < N)
+        for (int j = 0; j < D1; ++j) a.tok_post[(long)(cl.tok_off + k) * D1 + j] = (float)ldexp(hsum[r * D1 + j], -64);
+      continue;
+    }
     if (k < N) {
       double sm[7];
 #pragma unroll
@@ -605,12 +712,51 @@ __global__ __launch_bounds__(NT) void dpp_kernel(DppLaunch a) {
 // over the cap the kernel reports status 2; such a clip is sized (and launched) as the cap's configuration (csrc/align_posterior.h)
 int dpp_cfg(int N) { return std::min(cfg_of(N), NCFG - 1); }
 
-long clip_floats(int T, int N, int D) {
+long clip_floats(int T, int N, int D, bool counts = false) {
   if (T <= 0) return 0;
   return dispatch_cfg(dpp_cfg(N), [&](auto sh) {
     using K = CfgDpp<decltype(sh)::NT, decltype(sh)::R>;
+    if (counts)
+      return round64(DppLayout(T, K::ckpt_floats(D), K::COUNT_BLK, K::count_acc(D), K::ring_words(D), K::count_rings_in_lds(D),
+                               K::qring_words(D)).total);
     return round64(DppLayout(T, K::ckpt_floats(D), K::BLK, K::ACC, K::ring_words(D), K::rings_in_lds(D)).total);
   });
+}
+
+// the launches of both entries: the clips by configuration, each with the ring placement its D reaches
+template <bool CNT>
+int launch_all(const char* fn, DppLaunch& a, int n_clips, const int64_t* frame_off_host, const int32_t* n_frames_host,
+               const int32_t* tok_off_host, const int32_t* n_tok_host, int D, hipStream_t s) {
+  return launch_clips<NCFG>(
+      a, n_clips,
+      [&](int b, long off, LatClip& c, int& cfg) {
+        const int T = n_frames_host[b], N = n_tok_host[b];
+        c = LatClip{(long)frame_off_host[b], off, T, tok_off_host[b], N, b};
+        cfg = dpp_cfg(N);
+        return clip_floats(T, N, D, CNT);
+      },
+      [&](int cfg, DppLaunch& a) {
+        return dispatch_cfg(cfg, [&](auto sh) {
+          constexpr int NT = decltype(sh)::NT, R = decltype(sh)::R;
+          using K = CfgDpp<NT, R>;
+          constexpr int HI = CNT ? K::COUNT_MAX_RINGS : K::MAX_RINGS, LO = CNT ? K::COUNT_MIN_RINGS : K::MIN_RINGS;
+          auto launch = [&](auto hl_tag) {
+            constexpr int HL = decltype(hl_tag)::value;
+            if constexpr (HL <= HI && HL >= LO) {                          // (only the placements some D reaches are instantiated)
+              if (const int rc = reserve_lds<dpp_kernel<NT, R, HL, CNT>, LDS_CAP>(fn)) return rc;     // (the most any D asks for)
+              hipLaunchKernelGGL((dpp_kernel<NT, R, HL, CNT>), dim3(a.n), dim3(NT), CNT ? K::count_lds_bytes(D) : K::lds_bytes(D), s, a);
+              return hipGetLastError() == hipSuccess ? 0 : fail(fn, -3, "launch failed");
+            } else {
+              return fail(fn, -3, "no such ring placement");
+            }
+          };
+          const int hl = CNT ? K::count_rings_in_lds(D) : K::rings_in_lds(D);
+          if (hl == 3) return launch(std::integral_constant<int, 3>());
+          if (hl == 2) return launch(std::integral_constant<int, 2>());
+          if (hl == 1) return launch(std::integral_constant<int, 1>());
+          return launch(std::integral_constant<int, 0>());
+        });
+      });
 }
 
 }  // namespace
@@ -644,40 +790,44 @@ int32_t wfl_align_duration_prior_posterior(const float* logits, int64_t ldl, int
       (any_tok && (!tok_cls || !tok_post || !start_mean || !start_sd || !end_mean || !end_sd)) || (any_frame && (!logits || !tok)))
     return fail(fn, -1, "null device pointer");
   if ((rc = check_workspace(fn, need, workspace, workspace_bytes))) return rc;
-  hipStream_t s = (hipStream_t)stream;
   DppLaunch a{};
   a.logits = logits; a.ldl = ldl; a.C = C; a.tok_cls = tok_cls; a.gap_cls = gap_cls; a.tok_win = tok_win;
   a.tok_dur = tok_dur; a.dur = dur; a.n_rows = n_rows; a.D = D; a.tok = tok;
   a.ws = (float*)workspace; a.logz = logz; a.tok_post = tok_post; a.start_mean = start_mean; a.start_sd = start_sd;
   a.end_mean = end_mean; a.end_sd = end_sd; a.status = status;
-  return launch_clips<NCFG>(
-      a, n_clips,
-      [&](int b, long off, LatClip& c, int& cfg) {
-        const int T = n_frames_host[b], N = n_tok_host[b];
-        c = LatClip{(long)frame_off_host[b], off, T, tok_off_host[b], N, b};
-        cfg = dpp_cfg(N);
-        return clip_floats(T, N, D);
-      },
-      [&](int cfg, DppLaunch& a) {
-        return dispatch_cfg(cfg, [&](auto sh) {
-          constexpr int NT = decltype(sh)::NT, R = decltype(sh)::R;
-          using K = CfgDpp<NT, R>;
-          auto launch = [&](auto hl_tag) {
-            constexpr int HL = decltype(hl_tag)::value;
-            if constexpr (HL <= K::MAX_RINGS && HL >= K::MIN_RINGS) {      // (only the placements some D reaches are instantiated)
-              if (const int rc = reserve_lds<dpp_kernel<NT, R, HL>, LDS_CAP>(fn)) return rc;     // (the most any D asks for)
-              hipLaunchKernelGGL((dpp_kernel<NT, R, HL>), dim3(a.n), dim3(NT), K::lds_bytes(D), s, a);
-              return hipGetLastError() == hipSuccess ? 0 : fail(fn, -3, "launch failed");
-            } else {
-              return fail(fn, -3, "no such ring placement");
-            }
-          };
-          const int hl = K::rings_in_lds(D);
-          if (hl == 2) return launch(std::integral_constant<int, 2>());
-          if (hl == 1) return launch(std::integral_constant<int, 1>());
-          return launch(std::integral_constant<int, 0>());
-        });
-      });
+  return launch_all<false>(fn, a, n_clips, frame_off_host, n_frames_host, tok_off_host, n_tok_host, D, (hipStream_t)stream);
+}
+
+int64_t wfl_align_duration_prior_counts_workspace_bytes(const int32_t* n_frames_host, const int32_t* n_tok_host, int32_t n_clips,
+                                                        int32_t D) {
+  if (D < 1 || D > MAX_D) return -1;
+  return clips_workspace_bytes(n_frames_host, n_tok_host, n_clips, [D](int T, int N) { return clip_floats(T, N, D, true); });
+}
+
+int32_t wfl_align_duration_prior_counts(const float* logits, int64_t ldl, int32_t C, int32_t o_id, const int64_t* frame_off_host,
+                                        const int32_t* n_frames_host, const int32_t* tok_off_host, const int32_t* n_tok_host,
+                                        const int32_t* tok_cls, const int32_t* tok_win, const int32_t* gap_cls, int32_t n_clips,
+                                        const int32_t* tok_dur, const float* dur, int32_t n_rows, int32_t D, void* workspace,
+                                        int64_t workspace_bytes, float* logz, float* dur_post, int32_t* status, void* stream) {
+  const char* fn = "wfl_align_duration_prior_counts";
+  if (D < 1 || D > MAX_D) return fail(fn, -1, "D must be 1 .. 32");
+  if (n_rows < 0) return fail(fn, -1, "n_rows < 0");
+  const int64_t need = wfl_align_duration_prior_counts_workspace_bytes(n_frames_host, n_tok_host, n_clips, D);
+  bool any_tok = false, any_frame = false;
+  int rc = check_clip_args(fn, C, o_id, ldl, frame_off_host, n_frames_host, tok_off_host, n_tok_host, n_clips, need, any_tok, any_frame);
+  if (rc) return rc;
+  if (n_rows > 0 && !dur) return fail(fn, -1, "null dur with n_rows > 0");
+  if ((int64_t)n_rows * (D + 1) > INT_MAX) return fail(fn, -1, "a table of 2^31 values or more");
+  if (n_clips == 0) return 0;
+  if (any_tok && !tok_dur) return fail(fn, -1, "null tok_dur");
+  if (!logz || !status || !gap_cls || (any_tok && (!tok_cls || !dur_post)) || (any_frame && !logits))
+    return fail(fn, -1, "null device pointer");
+  if ((rc = check_workspace(fn, need, workspace, workspace_bytes))) return rc;
+  DppLaunch a{};
+  a.logits = logits; a.ldl = ldl; a.C = C; a.tok_cls = tok_cls; a.gap_cls = gap_cls; a.tok_win = tok_win;
+  a.tok_dur = tok_dur; a.dur = dur; a.n_rows = n_rows; a.D = D;
+  a.ws = (float*)workspace; a.logz = logz; a.tok_post = dur_post; a.status = status;
+  return launch_all<true>(fn, a, n_clips, frame_off_host, n_frames_host, tok_off_host, n_tok_host, D, (hipStream_t)stream);
 }
 
 }  // extern "C"

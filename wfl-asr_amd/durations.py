@@ -6,6 +6,9 @@ P(D + i) = P(D) rho^i.  The search adds, for a run of d frames, log P(d) = log_p
 (d - D) log_tail beyond.
 
   estimate     HTK `.lab` files -> DurationPrior (counts, natural-log probabilities)
+  flat         a prior that forbids nothing and prefers nothing below D: where `python -m wfl_asr_amd.adapt_durations` starts
+  reestimate   expected counts [n, D + 1] (align.duration_prior_expected_counts, summed per phoneme) -> DurationPrior: estimate's
+               formula on fractional counts, the M-step of that command
   save / load  the JSON file {"frame_duration", "max_frames", "phonemes": [...], "log_prob": [[D values] | null, ...], "log_tail":
                [...]}; a `null` value is a forbidden duration, a `null` row a phoneme without any sample: no prior
   check        a loaded prior against the label set's output names and the frame clock (ValueError, by name)
@@ -42,6 +45,25 @@ def frames_of(start_s, end_s, frame_duration) -> int:
 
 def _log(p):
     return math.log(p) if p > 0.0 else -math.inf
+
+
+def _row(c, c_ge, excess, D, K, allowed=None):
+    """One phoneme's (log_prob [D], log_tail) from its statistics: c[d - 1] the count of d frames for d < D, c_ge the count of
+    d >= D, excess the sum of d - D over those (estimate's docstring has the formula).  allowed: None, or (entries [D] bool, tail
+    bool) -- what a prior leaves open: a forbidden entry gets no count and no smoothing and stays -inf, a forbidden tail stays -inf."""
+    ok = [True] * D if allowed is None else [bool(x) for x in allowed[0]]
+    tail_ok = True if allowed is None else bool(allowed[1])
+    c = [c[d] if ok[d] else 0.0 for d in range(D - 1)]
+    c_ge = c_ge if ok[D - 1] else 0.0
+    n_tot = sum(c) + c_ge
+    den = n_tot + K * sum(ok)
+    if not den > 0.0:
+        return None
+    big_m = (c_ge + K) / den if ok[D - 1] else 0.0
+    m = (excess + K) / (c_ge + K) if tail_ok and ok[D - 1] and c_ge + K > 0.0 else 0.0
+    rho = m / (1.0 + m)
+    row = [_log((c[d] + K) / den) if ok[d] else -math.inf for d in range(D - 1)] + [_log(big_m * (1.0 - rho))]
+    return np.array(row, np.float64), _log(rho)
 
 
 def estimate(lab_paths, symbols=None, max_frames=32, smoothing=1.0, frame_duration=0.02) -> DurationPrior:
@@ -88,16 +110,84 @@ def estimate(lab_paths, symbols=None, max_frames=32, smoothing=1.0, frame_durati
             log_prob.append(None)
             log_tail.append(-math.inf)
             continue
-        den = n_tot + K * D
         c_ge = sum(c for d, c in h.items() if d >= D)
         excess = sum((d - D) * c for d, c in h.items() if d >= D)
-        big_m = (c_ge + K) / den
-        m = (excess + K) / (c_ge + K) if c_ge + K > 0.0 else 0.0
-        rho = m / (1.0 + m)
-        row = [_log((h.get(d, 0) + K) / den) for d in range(1, D)] + [_log(big_m * (1.0 - rho))]
-        log_prob.append(np.array(row, np.float64))
-        log_tail.append(_log(rho))
+        row, tail = _row([h.get(d, 0) for d in range(1, D)], c_ge, excess, D, K)
+        log_prob.append(row)
+        log_tail.append(tail)
     return DurationPrior(float(frame_duration), D, list(names), log_prob, np.array(log_tail, np.float64), counts)
+
+
+def flat(phonemes, max_frames, frame_duration=0.02) -> DurationPrior:
+    """Every phoneme the same row: P(d) = 1 / (D + 1) for d < D, P(>= D) = 2 / (D + 1) with rho = 1 / 2.  It sums to 1 and forbids
+    nothing."""
+    D = int(max_frames)
+    if not 1 <= D <= MAX_FRAMES:
+        raise ValueError(f"max_frames must be 1 .. {MAX_FRAMES}, got {max_frames!r}")
+    names = list(dict.fromkeys(phonemes))
+    row = np.full(D, -math.log(D + 1.0), np.float64)          # P(D) = M (1 - rho) = 1 / (D + 1) as well
+    return DurationPrior(float(frame_duration), D, names, [row.copy() for _ in names], np.full(len(names), math.log(0.5), np.float64))
+
+
+def reestimate(counts, phonemes, max_frames, prior=None, prior_count=0.0, smoothing=0.0, frame_duration=0.02) -> DurationPrior:
+    """estimate's formula on expected counts: the M-step of `python -m wfl_asr_amd.adapt_durations`.
+
+    counts       float64 [n, D + 1], a row per phoneme in the layout of align.duration_prior_expected_counts' rows: columns 0 .. D - 2
+                 the (expected) count of runs of 1 .. D - 1 frames, column D - 1 of runs of D frames or more, column D the sum of
+                 d - D over those.  Negative or non-finite counts, or another shape: ValueError
+    prior        a DurationPrior over the same phonemes and D, or None.  With it a row receives `prior_count` pseudo-runs spread as
+                 the prior's own distribution in the same statistics -- P(d) for d < D, M = P(D) / (1 - rho), excess
+                 M rho / (1 - rho) -- and whatever the prior forbids (a null entry, a null tail) stays forbidden, whatever the counts
+                 and the smoothing: a forbidden entry takes no count and no smoothing
+    smoothing    K of estimate, added to every entry that is not forbidden
+    A row whose counts sum to 0 keeps the prior's row; without a prior it is None: no prior.  With integer counts, no prior and the
+    same K this is estimate, to the bit."""
+    D, K, pc = int(max_frames), float(smoothing), float(prior_count)
+    if not 1 <= D <= MAX_FRAMES:
+        raise ValueError(f"max_frames must be 1 .. {MAX_FRAMES}, got {max_frames!r}")
+    if not (K >= 0.0 and K < math.inf):
+        raise ValueError(f"smoothing must be a finite number >= 0, got {smoothing!r}")
+    if not (pc >= 0.0 and pc < math.inf):
+        raise ValueError(f"prior_count must be a finite number >= 0, got {prior_count!r}")
+    if not (float(frame_duration) > 0.0 and float(frame_duration) < math.inf):
+        raise ValueError(f"frame_duration must be a positive number of seconds, got {frame_duration!r}")
+    names = list(phonemes)
+    if len(set(names)) != len(names):
+        raise ValueError("phonemes must be distinct")
+    cnt = np.asarray(counts, np.float64)
+    if cnt.shape != (len(names), D + 1):
+        raise ValueError(f"counts must be [{len(names)}, {D + 1}] (phonemes, D + 1), got {list(cnt.shape)}")
+    if not np.isfinite(cnt).all() or (cnt < 0).any():
+        raise ValueError("counts must be finite and >= 0")
+    if prior is not None and (list(prior.phonemes) != names or int(prior.max_frames) != D):
+        raise ValueError("the prior must hold the same phonemes in the same order and the same max_frames as the counts")
+    if prior is None and pc > 0.0:
+        raise ValueError("prior_count needs a prior")
+    log_prob, log_tail = [], []
+    for i in range(len(names)):
+        pr = None if prior is None else prior.log_prob[i]
+        c, c_ge, excess = [float(v) for v in cnt[i, :D - 1]], float(cnt[i, D - 1]), float(cnt[i, D])
+        out = None
+        if sum(c) + c_ge > 0.0:
+            allowed = None
+            if pr is not None:
+                lt = float(prior.log_tail[i])
+                allowed = (np.isfinite(pr), np.isfinite(lt))
+                if pc > 0.0:
+                    rho = math.exp(lt)
+                    if not rho < 1.0:
+                        raise ValueError(f"{names[i]}: the prior's tail is rho = 1, no distribution to spread prior_count by")
+                    big_m = math.exp(pr[D - 1]) / (1.0 - rho)
+                    c = [v + pc * math.exp(pr[d]) for d, v in enumerate(c)]
+                    c_ge, excess = c_ge + pc * big_m, excess + pc * big_m * rho / (1.0 - rho)
+            out = _row(c, c_ge, excess, D, K, allowed)
+        if out is None:                            # no count (or none on an entry the prior leaves open): the prior's row
+            log_prob.append(None if pr is None else np.array(pr, np.float64))
+            log_tail.append(-math.inf if pr is None else float(prior.log_tail[i]))
+        else:
+            log_prob.append(out[0])
+            log_tail.append(out[1])
+    return DurationPrior(float(frame_duration), D, names, log_prob, np.array(log_tail, np.float64))
 
 
 def save(prior: DurationPrior, path):

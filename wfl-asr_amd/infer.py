@@ -934,6 +934,59 @@ class Labeler:
                 n_frames += int(frames[b])
         return total, total_logz, total_lse, n_frames, skipped
 
+    def expected_durations(self, audio_paths, transcripts, prior, weight=1.0, lang_id=None, confidence_threshold=0.0, verbose=True):
+        """One E-step of a duration prior's re-estimation over files with transcripts and no timed labels, under `prior`
+        (durations.DurationPrior) at `weight`: -> (counts float64 [len(prior.phonemes), D + 1]: per phoneme the expected number of
+        runs of 1 .. D - 1 frames, of D frames or more, and the expected frames past D of those -- the statistics durations.estimate
+        counts, for durations.reestimate; total_logz; n_frames; n_tokens; skipped: the paths left out).  transcripts: per file its
+        token list, or None.  The files are forwarded and laid out as _label_viterbi lays them out -- a file is one clip across its
+        30 s seams, the token alternatives and gap classes are the search's, a token's table row is align.duration_rows' -- and the
+        files of a wave go to wfl_align_duration_prior_counts as one ragged batch (align.duration_prior_expected_counts).  Each
+        token's row of length posteriors is added, in float64 on the host, to its phoneme's row; a token without a row (-1) goes
+        nowhere.  The kernel's logz is on log posteriors already.  A file without a transcript, one whose transcript cannot be
+        aligned, or one whose status is not 0 is skipped with one line."""
+        from . import durations as DU
+        lang_name = self._lang_name(lang_id)
+        DU.check(prior, self._names_for(lang_name)[1], frame_duration)
+        table = DU.table(prior, weight)
+        total = np.zeros((len(prior.phonemes), int(prior.max_frames) + 1), np.float64)
+        total_logz, n_frames, n_tokens, skipped = 0.0, 0, 0, []
+        for sel, by_file in self._file_waves(audio_paths, verbose):
+            sel = [fi for fi in sel if fi in by_file]
+            if not sel:
+                continue
+            free, rows = self._forward_with_logits(sel, by_file, lang_id, confidence_threshold)
+            for fi in sel:
+                if not transcripts[fi]:
+                    print(f"{audio_paths[fi]}: no expected durations (no transcript); skipped")
+                    skipped.append(audio_paths[fi])
+            with_tr = [fi for fi in sel if transcripts[fi]]
+            _, _, plans = self._greedy_and_plans(with_tr, by_file, free, audio_paths, transcripts, lang_name)
+            skipped += [audio_paths[fi] for fi in with_tr if fi not in plans]      # (its line: _greedy_and_plans')
+            run = [fi for fi in with_tr if fi in plans]
+            if not run:
+                continue
+            frames, lg = self._file_rows(rows, by_file, run)
+            durs = [AL.duration_rows(transcripts[fi], prior) for fi in run]
+            batch = AL.AlignBatch.of(lg, frames, [plans[fi] for fi in run], [AL.gap_classes(self.labels, transcripts[fi]) for fi in run],
+                                     self.labels.index("O"), durs=durs)
+            d_logz, d_post, d_st = AL.duration_prior_expected_counts(*batch.args(), batch.durs, table)
+            h_logz, h_post, h_st = d_logz.double().cpu().numpy(), d_post.cpu().numpy().astype(np.float64), d_st.cpu().numpy()
+            k0 = 0
+            for b, fi in enumerate(run):
+                n = len(durs[b])
+                if int(h_st[b]) != AL.STATUS_OK:
+                    print(f"{audio_paths[fi]}: no expected durations (wfl_align_duration_prior_counts status {int(h_st[b])}); skipped")
+                    skipped.append(audio_paths[fi])
+                else:
+                    r = np.asarray(durs[b], np.int64)
+                    np.add.at(total, r[r >= 0], h_post[k0:k0 + n][r >= 0])
+                    total_logz += float(h_logz[b])
+                    n_frames += int(frames[b])
+                    n_tokens += n
+                k0 += n
+        return total, total_logz, n_frames, n_tokens, skipped
+
     def _label_viterbi(self, audio_paths, transcripts, drafts, opts, lang_id, threshold, verbose, filler_scores=None, prior=None,
                        durations=None):
         """Files with a transcript, align="viterbi" -> one ViterbiLabel per file.  Their chunks are forwarded with logits (kept on
