@@ -174,7 +174,8 @@ int32_t wfl_check(wfl_model* m, void* workspace, int64_t workspace_bytes, int32_
 /* ---- single stages, exported for unit parity tests and profiling ---- */
 
 /* Replaces WhisperFeatureExtractor.__call__ at model.py:153-154 (HF feature_extraction_whisper.py:135-168).
- * out [B][n_mels][2*max_positions] fp32, the reference's layout. */
+ * out [B][n_mels][2*max_positions] fp32, the reference's layout.  wav and out must not be null and L must be at least 1 (B > 0,
+ * ldw >= L), as for wfl_forward: anything else is an error status and nothing is launched.  lens[b] may be 0 (the clip is silence). */
 int32_t wfl_logmel(wfl_model* m, const float* wav, int64_t ldw, const int32_t* lens, int32_t B, int32_t L,
                    float* out, void* workspace, int64_t workspace_bytes, void* stream);
 
@@ -243,6 +244,31 @@ int32_t wfl_op_relpos_gate(const void* x, const void* x_lo, int64_t ldx, int64_t
  * the padding channels and in every other row: the positional conv's operand.  cpg % 8 == 0, cpg <= 64, groups * cpg == d. */
 int32_t wfl_op_regroup(const void* x, int32_t d, int32_t groups, int32_t cpg, int64_t R, int64_t lead, int32_t B, int32_t P, int32_t T,
                        const int32_t* clip_T, void* xg, void* stream);
+
+/* Waveform statistics of Wav2Vec2FeatureExtractor's do_normalize (csrc/wavlm.hip): stats[2b] = sum, stats[2b + 1] = sum of squares of
+ * the first lens[b] (null: L) samples of clip b, accumulated in float64 in a fixed order.  wav [B][ldw] fp32, stats [2 B] double. */
+int32_t wfl_op_wav_stats(const float* wav, int64_t ldw, const int32_t* lens, int32_t B, int32_t L, double* stats, void* stream);
+
+/* Frames per clip at every level of a conv stack without padding: t = clamp(lens[b], 0, L), below min_len no frames at any level, then
+ * per level t <- t >= kernel[i] ? (t - kernel[i]) / stride[i] + 1 : 0; out[i * B + b].  lens and out are device arrays, kernel and
+ * stride HOST arrays of n entries, 1 <= n <= 8, stride > 0.  (kernel 0, stride hop, min_len 201: the mel front-end's 1 + len / hop.) */
+int32_t wfl_op_clip_frames(const int32_t* lens, int32_t B, int32_t L, int32_t n, const int32_t* kernel, const int32_t* stride,
+                           int32_t min_len, int32_t* out, void* stream);
+
+/* Level 0 of WavLM's feature encoder (csrc/wavlm.hip; HF modeling_wavlm.py:675-744): every field of csrc/common.h's Conv0Args.
+ *   x = (wav - mean) / sqrt(var + 1e-7) from wstats (wfl_op_wav_stats' output over the clip's own lens[b] samples; null: x = wav),
+ *   y[t][c] = sum_j w[c][j] x[5 t + j]   (k = 10, stride 5, no padding; T0 frames, a clip with lens has (lens[b] - 10) / 5 + 1, none below 10)
+ *   group_norm != 0: out = gelu(gamma (y - mean_c) rstd_c + beta), statistics per (clip, channel) over the clip's own frames, eps 1e-5.
+ *                    The conv bias is NOT read in this mode: per-channel GroupNorm removes a per-channel constant.  Needs `scratch`:
+ *                    16-byte aligned, wfl_op_conv0_scratch_bytes(B, T0, C) bytes, overwritten.
+ *   group_norm == 0: out = gelu(LayerNorm_C(y + bias)), eps 1e-5 (bias null: none); scratch is not used.
+ * out (+ out_lo = bf16(value - out) when given): bf16 frame rows of C channels, row lead + b P + t; rows at t >= the clip's own frame
+ * count are not written.  w [C][10], bias / gamma / beta [C] fp32.  C % 8 == 0, C <= 512, 0 < T0 <= (L - 10) / 5 + 1, P >= T0;
+ * lens[b] <= L is the caller's to keep.  An argument error is an error status and nothing is launched. */
+int64_t wfl_op_conv0_scratch_bytes(int32_t B, int32_t T0, int32_t C);
+int32_t wfl_op_conv0(const float* wav, int64_t ldw, const int32_t* lens, int32_t B, int32_t L, const double* wstats, const float* w,
+                     const float* bias, const float* gamma, const float* beta, int32_t C, int32_t T0, void* out, void* out_lo,
+                     int64_t lead, int32_t P, int32_t group_norm, void* scratch, int64_t scratch_bytes, void* stream);
 
 /* WavLM's positional convolution on regrouped rows (csrc/posconv.hip; HF modeling_wavlm.py:48-90):
  *   out = res (+ res_lo) + gelu( grouped conv1d(x, taps, padding taps / 2)[..., :-1] + bias ),  out_lo = bf16(out - bf16(out)) when given.

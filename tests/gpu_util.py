@@ -138,3 +138,37 @@ def layernorm_act(x, x_lo, y, y_lo, g, b, eps, lead, B, P, T, Cn, n_div=0, gelu=
 def layernorm_pair(x, x_lo, y1, y1_lo, y2, y2_lo, g1, b1, g2, b2, eps, lead, B, P, T, Cn, n_div=0, clip_T=None):
     _lib.check(lib().wfl_op_layernorm_pair(ptr(x), ptr(x_lo), ptr(y1), ptr(y1_lo), ptr(y2), ptr(y2_lo), Cn, ptr(g1), ptr(b1), ptr(g2), ptr(b2),
                                            float(eps), lead, B, P, T, Cn, n_div, ptr(clip_T), stream()), "wfl_op_layernorm_pair")
+
+
+def wav_stats(wav, ldw, B, L, stats, lens=None, check=True):
+    """wfl_op_wav_stats: wav fp32 [B][ldw], stats float64 [2 B], lens int32 device tensor or None.  -> the status code."""
+    rc = lib().wfl_op_wav_stats(ptr(wav), ldw, ptr(lens), B, L, ptr(stats), stream())
+    if check:
+        _lib.check(rc, "wfl_op_wav_stats")
+    return rc
+
+
+def clip_frames(lens, B, L, kernel, stride, min_len, out, n=None, check=True):
+    """wfl_op_clip_frames: lens / out int32 device tensors, kernel / stride host lists (n: the level count passed, default their length)."""
+    k = (C.c_int32 * max(len(kernel), 1))(*kernel)
+    s = (C.c_int32 * max(len(stride), 1))(*stride)
+    rc = lib().wfl_op_clip_frames(ptr(lens), B, L, len(kernel) if n is None else n, C.cast(k, C.c_void_p), C.cast(s, C.c_void_p), min_len,
+                                  ptr(out), stream())
+    if check:
+        _lib.check(rc, "wfl_op_clip_frames")
+    return rc
+
+
+def conv0_scratch_bytes(B, T0, Cn):
+    return int(lib().wfl_op_conv0_scratch_bytes(B, T0, Cn))
+
+
+def conv0(wav, ldw, B, L, w, gamma, beta, Cn, T0, out, lead, P, group_norm, lens=None, wstats=None, bias=None, out_lo=None, scratch=None,
+          scratch_bytes=None, check=True):
+    """wfl_op_conv0; scratch a uint8 device tensor (group mode) or None.  -> the status code."""
+    nbytes = (scratch.numel() if scratch is not None else 0) if scratch_bytes is None else scratch_bytes
+    rc = lib().wfl_op_conv0(ptr(wav), ldw, ptr(lens), B, L, ptr(wstats), ptr(w), ptr(bias), ptr(gamma), ptr(beta), Cn, T0, ptr(out), ptr(out_lo),
+                            lead, P, int(group_norm), ptr(scratch), nbytes, stream())
+    if check:
+        _lib.check(rc, "wfl_op_conv0")
+    return rc

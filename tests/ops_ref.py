@@ -1,6 +1,8 @@
 """Plain float64 references of the WavLM-path kernels and of attention's bias / ragged / split modes, and the seeded inputs of the
 operator tests (tests/test_gpu_ops_wavlm.py runs the kernels on them, tests/test_ops_ref_cpu.py checks the references themselves and
-that each test's bound separates a right reference from a wrong one).  Everything here runs on the CPU.
+that each test's bound separates a right reference from a wrong one), and -- in the second half -- the same for the front-end kernels
+(Whisper log-mel, WavLM waveform statistics, conv level 0 and frame counts: tests/test_gpu_ops_frontend.py).  Everything here runs on
+the CPU.
 
 The references take the operand VALUES as the kernels read them -- bf16 values, or hi + lo sums of bf16 pairs -- so operand rounding
 is no part of any error; what is left is the kernel's own arithmetic and the rounding of what it stores."""
@@ -289,3 +291,440 @@ def split_case(hd, bias):
 
 def posconv_case(groups, cpg, taps, pair):
     return posconv_inputs(groups, cpg, taps, POSCONV_B, POSCONV_T, pair, seed=groups + taps)
+
+
+# =================================================================================================== the front-end kernels
+# (tests/test_gpu_ops_frontend.py; the references take the fp32 input VALUES in float64, so operand rounding is no part of any error)
+U24 = 2.0 ** -24                         # fp32 unit roundoff
+
+
+# ------------------------------------------------------------------------------------------------------------ Whisper log-mel
+def mel_bank(n_mels, htk=False):
+    """[201, n_mels] float64 VALUES of the fp32 bank the model uploads (the oracle's float64 Slaney bank rounded to fp32)."""
+    from oracle import wfl_oracle as O
+    fb = O.mel_filter_bank_htk(n_mels) if htk else O.mel_filter_bank(n_mels)
+    return torch.from_numpy(fb).to(torch.float32).double()
+
+
+def mel_maxw(fb):
+    """The widest triangle of the bank in bins: the longest fp32 sum of the sparse mel projection."""
+    nz = fb != 0
+    k = torch.arange(fb.shape[0])[:, None]
+    first = torch.where(nz, k, fb.shape[0]).amin(0)
+    last = torch.where(nz, k, -1).amax(0)
+    return int((last - first + 1).clamp(min=1).max())
+
+
+def hann400(periodic=True):
+    return 0.5 - 0.5 * torch.cos(2.0 * math.pi * torch.arange(400, dtype=F64) / (400.0 if periodic else 399.0))
+
+
+def _dft_tables():
+    nk = (torch.arange(400)[:, None] * torch.arange(201)[None, :]) % 400                 # exact angle reduction
+    ang = 2.0 * math.pi * nk.double() / 400.0
+    return torch.cos(ang), -torch.sin(ang)
+
+
+def logmel_ref(wav, lens, n_mels, n_samples, pad="reflect", window=None, fold200=1.0, frame_shift=0, bank=None, batch_max=False,
+               reflect_about_L=False):
+    """wav [B, L] fp32 values, lens list of B lengths or None.  Truncate / zero-pad to n_samples, reflect-pad 200, periodic Hann of 400,
+    hop 160, drop the last frame, power, fp32-rounded Slaney bank, log10 with a clamp at 1e-10, per-clip floor max - 8, (x + 4) / 4.
+    -> dict: out [B, n_mels, frames]; absX [B, frames, 201]; P [B, frames, n_mels] mel power; E [B, frames] = sum |x_n w_n| of the
+    windowed frame; fb.  The keyword arguments are the WRONG readings of the CPU controls (tests/test_ops_ref_cpu.py): symmetric
+    padding, another window, sample 200 of every frame weighted fold200 (the fold's forgotten 1/2: 2.0), frames shifted, another bank,
+    one maximum for the whole batch, and the end reflected about L - 1 with the samples beyond n_samples read, not cut."""
+    x = wav.double()
+    B, L = x.shape
+    if lens is not None:
+        keep = torch.arange(L)[None, :] < torch.tensor(list(lens))[:, None]
+        x = torch.where(keep, x, torch.zeros((), dtype=F64))                    # (where, not a product: NaN may stand beyond a length)
+    nf = n_samples // 160
+    if reflect_about_L and L > n_samples:
+        pass                                                                   # wrong: the tail stays, the reflection is about L - 1
+    elif L >= n_samples:
+        x = x[:, :n_samples]
+    else:
+        x = F.pad(x, (0, n_samples - L))
+    n = x.shape[1]
+    if pad == "reflect":
+        left, right = x[:, 1:201].flip(1), x[:, n - 201:n - 1].flip(1)
+    else:                                                                      # symmetric: the edge sample is repeated
+        left, right = x[:, 0:200].flip(1), x[:, n - 200:n].flip(1)
+    xp = torch.cat([left, x, right], 1)
+    frames = xp.unfold(1, 400, 160)[:, frame_shift:frame_shift + nf]          # [B, nf, 400]
+    w = hann400() if window is None else window
+    fw = frames * w
+    if fold200 != 1.0:
+        fw = fw.clone()
+        fw[..., 200] *= fold200
+    cos, msin = _dft_tables()
+    re, im = fw @ cos, fw @ msin
+    power = re * re + im * im
+    fb = mel_bank(n_mels) if bank is None else bank
+    P = power @ fb
+    lg = torch.log10(P.clamp(min=1e-10))
+    mx = lg.amax(dim=(1, 2), keepdim=True)
+    if batch_max:
+        mx = mx.amax(dim=0, keepdim=True).expand(B, 1, 1)
+    out = (torch.maximum(lg, mx - 8.0) + 4.0) / 4.0
+    return {"out": out.transpose(1, 2).contiguous(), "absX": power.sqrt(), "P": P, "E": fw.abs().sum(-1), "fb": fb, "lg": lg, "mx": mx}
+
+
+# The kernel's DFT (csrc/logmel.hip): Re X_k = sum_{j=1..200} (x_j + x_{400-j}) Wc[j][k], Im likewise with x_j - x_{400-j} and Ws, the
+# window folded into fp32-rounded tables, accumulated as a 200-term fp32 fma chain.  Each term carries the fold's rounding and the
+# table entry's (2 u, u = 2^-24), the chain at most 200 u of the sum of the terms' magnitudes: (1 + u)^202 - 1 <= 204 u.  With
+# m_j = (|x_j| + |x_{400-j}|) w_j >= both folds' magnitudes times the window, the error vector (d Re, d Im) is at most
+# gamma sum_j m_j |(cos, sin)| = gamma E in length, E = sum_n |x_n w_n|: |dX_k| <= gamma E, worst case, for this arithmetic.
+LOGMEL_GAMMA = 204 * U24
+LOGMEL_STORE = 4 * 2.0 ** -23            # the fp32 floor, affine and store of values of order 1
+LOGMEL_UNINFORMATIVE = 1e-2              # an element whose bound is wider than this (output units) says nothing
+
+
+def logmel_bound(r):
+    """r: logmel_ref's dict -> the bound [B, n_mels, frames] of |kernel - r["out"]|.
+    Power domain: d|X_k|^2 <= 2 |X_k| gamma E + (gamma E)^2, so dP_m = sum_k fb[k][m] (2 |X_k| gamma E + (gamma E)^2) + c_mel u P_m with
+    c_mel = mel_maxw + 8 for the fp32 power, the mel sum of at most mel_maxw terms and log10f.  dP goes through log10 exactly (both sides,
+    with the 1e-10 clamp); the floor max - 8 moves by the log's error at the reference's arg-max element; max(log, floor) is then bounded
+    from both sides; / 4 and the store."""
+    fb, P = r["fb"], r["P"]
+    gE = (LOGMEL_GAMMA * r["E"])[..., None]                                     # [B, nf, 1]
+    dP = (2.0 * r["absX"] * gE + gE * gE) @ fb + (mel_maxw(fb) + 8) * U24 * P
+    lg, mx = r["lg"], r["mx"]
+    lg_hi = torch.log10((P + dP).clamp(min=1e-10))
+    lg_lo = torch.log10((P - dP).clamp(min=1e-10))
+    B = P.shape[0]
+    flat = lg.reshape(B, -1)
+    at = flat.argmax(1)
+    ar = torch.arange(B)
+    d_floor = torch.maximum(lg_hi.reshape(B, -1)[ar, at] - flat[ar, at], flat[ar, at] - lg_lo.reshape(B, -1)[ar, at])[:, None, None]
+    floor = mx - 8.0
+    ref = torch.maximum(lg, floor)
+    up = torch.maximum(lg_hi, floor + d_floor) - ref
+    down = ref - torch.maximum(lg_lo, floor - d_floor)
+    return (torch.maximum(up, down) / 4.0 + LOGMEL_STORE).transpose(1, 2).contiguous()
+
+
+LOGMEL_MODELS = [(80, 16), (80, 100), (128, 16), (128, 100)]                    # (n_mels, max_positions): 32 or 200 frames
+LOGMEL_KINDS = ["noise", "dc_noise", "impulses", "tone", "silence"]
+LOGMEL_BROADBAND = ["noise", "dc_noise", "impulses"]                            # the kinds the informative-share condition holds on
+LOGMEL_SHAPES = ["exact", "longer", "short", "pitch", "ragged"]
+LOGMEL_TAIL = 777
+
+
+def logmel_ragged_lens(n_samples):
+    return [n_samples, 5000, 201, 200, 1, 0]
+
+
+def logmel_signal(kind, n, seed):
+    """One clip of n samples (fp32): white noise at 0.1; DC 0.3 + noise at 0.01; unit impulses at 0, 1, 199, 200, 201, n - 201, n - 2,
+    n - 1; a tone at 1013.7 Hz over noise 60 dB down; silence."""
+    g = _gen(5000 + seed)
+    noise = torch.randn(n, generator=g)
+    if kind == "noise":
+        return 0.1 * noise
+    if kind == "dc_noise":
+        return 0.3 + 0.01 * noise
+    if kind == "impulses":
+        x = torch.zeros(n)
+        for i in (0, 1, 199, 200, 201, n - 201, n - 2, n - 1):
+            if 0 <= i < n:
+                x[i] = 1.0
+        return x
+    if kind == "tone":
+        return 0.5 * torch.sin(2.0 * math.pi * 1013.7 / 16000.0 * torch.arange(n, dtype=F64)).float() + 0.5e-3 * noise
+    return torch.zeros(n)
+
+
+def logmel_case(n_samples, shape, fill=float("nan")):
+    """The batch of one GPU case -> (wav [B, ldw] fp32, L, lens or None, kinds).  `fill` stands wherever the kernel must not read: the
+    row padding behind L ("pitch") and the samples behind each clip's length ("ragged"); the CPU control of an ignored `lens` passes
+    None and gets the clips' own continuation there instead.  "longer": 777 samples of 50.0 behind n_samples."""
+    if shape == "ragged":
+        lens = logmel_ragged_lens(n_samples)
+        kinds = ["noise", "dc_noise", "impulses", "tone", "noise", "noise"]
+        wav = torch.stack([logmel_signal(k, n_samples, 10 + i) for i, k in enumerate(kinds)])
+        if fill is not None:
+            for b, n in enumerate(lens):
+                wav[b, n:] = fill
+        return wav, n_samples, lens, kinds
+    kinds = list(LOGMEL_KINDS)
+    n = 5000 if shape == "short" else n_samples
+    wav = torch.stack([logmel_signal(k, n, i) for i, k in enumerate(kinds)])
+    if shape == "longer":
+        wav = torch.cat([wav, torch.full((len(kinds), LOGMEL_TAIL), 50.0)], 1)
+    if shape == "pitch":
+        wav = torch.cat([wav, torch.full((len(kinds), 13), float("nan") if fill is None else fill)], 1)
+    return wav, (wav.shape[1] - 13 if shape == "pitch" else wav.shape[1]), None, kinds
+
+
+# ----------------------------------------------------------------------------------------------------------------- wav_stats
+def wav_stats_ref(wav, lens=None):
+    """-> (stats [B, 2] float64: sum v, sum v^2 over the first lens[b] samples, exactly rounded; bound [B, 2]).
+    Any order of float64 additions of n terms is within (n - 1) 2^-53 sum |terms| of the exact sum (the squares of fp32 values are
+    exact in float64): L 2^-53 sum |v| and L 2^-53 sum v^2."""
+    B, L = wav.shape
+    st, bd = torch.zeros(B, 2, dtype=F64), torch.zeros(B, 2, dtype=F64)
+    for b in range(B):
+        n = L if lens is None else int(lens[b])
+        v = wav[b, :n].double()
+        st[b, 0], st[b, 1] = math.fsum(v.tolist()), math.fsum((v * v).tolist())
+        bd[b, 0], bd[b, 1] = L * 2.0 ** -53 * math.fsum(v.abs().tolist()), L * 2.0 ** -53 * float(st[b, 1])
+    return st, bd
+
+
+WAV_STATS_L = [1, 1023, 1024, 1025, 70001]
+
+
+def wav_stats_case(L):
+    """-> (wav [4, L + 5] fp32 with NaN behind each length and in the row padding, lens).  Noise at 0.1 on a DC of 0.25."""
+    g = _gen(6000 + L)
+    wav = 0.25 + 0.1 * torch.randn(4, L + 5, generator=g)
+    lens = [L, (L + 1) // 2, 0, min(L, 1)]
+    for b, n in enumerate(lens):
+        wav[b, n:] = float("nan")
+    return wav, lens
+
+
+# --------------------------------------------------------------------------------------------------------------- clip_frames
+def clip_frames_ref(lens, L, kernel, stride, min_len):
+    """-> [levels][B] ints: t = clamp(lens[b], 0, L), nothing below min_len, then t <- (t - k) // s + 1 if t >= k else 0 per level."""
+    out = [[0] * len(lens) for _ in kernel]
+    for b, n in enumerate(lens):
+        t = min(max(int(n), 0), L)
+        alive = t >= min_len
+        for i, (k, s) in enumerate(zip(kernel, stride)):
+            t = ((t - k) // s + 1) if (alive and t >= k) else 0
+            out[i][b] = t
+    return out
+
+
+WAVLM_STACK = ((10, 3, 3, 3, 3, 2, 2), (5, 2, 2, 2, 2, 2, 2))
+CLIP_FRAMES_L, CLIP_FRAMES_B = 32000, 300
+
+
+def clip_frames_lens():
+    L = CLIP_FRAMES_L
+    edge = [-3, 0, 9, 10, 200, 201, 399, 400, 401, L, L + 5]
+    g = _gen(7000)
+    rest = torch.randint(0, L + 1, (CLIP_FRAMES_B - len(edge),), generator=g).tolist()
+    return rest[:250] + edge + rest[250:]                                        # the edges in the second block of 256 clips
+
+
+# --------------------------------------------------------------------------------------------------------------- WavLM conv0
+def conv0_frames(n):
+    return (n - 10) // 5 + 1 if n >= 10 else 0
+
+
+def gelu_tanh(x):
+    return 0.5 * x * (1.0 + torch.tanh(math.sqrt(2.0 / math.pi) * (x + 0.044715 * x ** 3)))
+
+
+def conv0_ref(wav, lens, normalize, w, bias, gamma, beta, mode, with_scale=False, reverse_taps=False, unbiased=False, gn_eps=1e-5,
+              stats_T=None, mean_over_L=False, ln_div=None, tanh=False):
+    """Level 0 of WavLM's feature encoder in float64.  wav [B, L] fp32 values; lens list or None; normalize: (x - mean) / sqrt(var + 1e-7)
+    with the biased variance over the clip's own lens[b] samples; conv1d k = 10, stride 5, no padding, tap 0 at the earliest sample;
+    mode "group": per-(clip, channel) statistics over the clip's own frames, eps 1e-5 (a bias, when given, is added -- and cancels);
+    mode "layer": + bias, LayerNorm over the C channels, eps 1e-5; exact-erf GELU.
+    -> out [B, T0, C] (T0 from L; rows beyond a clip's own frames zero), and with_scale: what an fp32 error scales with,
+       |gamma| r (|y - mu| + |mu| + 1 / r + A) + |beta|,  A = sum_j |w_j x_j|  (conv0_bound).
+    The other keyword arguments are the controls' WRONG readings: taps reversed, unbiased GroupNorm variance, another GroupNorm eps,
+    GroupNorm sums divided by stats_T frames instead of the clip's, waveform sums divided by L instead of lens[b], the LayerNorm
+    divisor ln_div instead of C, tanh-GELU."""
+    B, L = wav.shape
+    C = w.shape[0]
+    T0 = conv0_frames(L)
+    wd = w.double().flip(-1) if reverse_taps else w.double()
+    g, bt = gamma.double(), beta.double()
+    out = torch.zeros(B, T0, C, dtype=F64)
+    scale = torch.zeros(B, T0, C, dtype=F64)
+    for b in range(B):
+        n = L if lens is None else int(lens[b])
+        Tb = conv0_frames(n)
+        if Tb == 0:
+            continue
+        x = wav[b, :n].double()
+        if normalize:
+            div = L if mean_over_L else n
+            m = x.sum() / div
+            var = (x * x).sum() / div - m * m if mean_over_L else ((x - m) ** 2).sum() / n
+            x = (x - m) / torch.sqrt(var.clamp(min=0.0) + 1e-7)
+        win = x.unfold(0, 10, 5)[:Tb]                                            # [Tb, 10]
+        y = win @ wd.T                                                           # [Tb, C]
+        A = win.abs() @ wd.abs().T
+        if bias is not None:
+            y = y + bias.double()
+        if mode == "group":
+            div = Tb if stats_T is None else stats_T
+            mu = y.sum(0, keepdim=True) / div
+            if stats_T is None:
+                var = ((y - mu) ** 2).sum(0, keepdim=True) / ((Tb - 1) if unbiased else Tb)
+            else:
+                var = ((y * y).sum(0, keepdim=True) / div - mu * mu).clamp(min=0.0)
+            r = (var + gn_eps) ** -0.5
+        else:
+            div = C if ln_div is None else ln_div
+            mu = y.sum(1, keepdim=True) / div
+            var = ((y - mu) ** 2).sum(1, keepdim=True) / C if ln_div is None else ((y * y).sum(1, keepdim=True) / div - mu * mu).clamp(min=0.0)
+            r = (var + 1e-5) ** -0.5
+        v = g * (y - mu) * r + bt
+        out[b, :Tb] = gelu_tanh(v) if tanh else F.gelu(v)
+        scale[b, :Tb] = g.abs() * r * ((y - mu).abs() + mu.abs() + 1.0 / r + A) + bt.abs()
+    return (out, scale) if with_scale else out
+
+
+def _fma32(a, b, c):
+    """fmaf on fp32 tensors: the product of two fp32 values is exact in float64; one float64 addition, then the rounding to fp32."""
+    return (a.double() * b.double() + c.double()).float()
+
+
+def gelu_f32(x):
+    """csrc/common.h's gelu_erf in fp32: max(x, 0) - |x| 2^q(|x|), q the degree-5 fit of log2 Phi(-t)."""
+    t = x.abs()
+    f = lambda c: torch.full_like(t, c)                                         # noqa: E731
+    q = _fma32(f(-4.732937668e-04), t, f(7.084457669e-03))
+    for c in (-5.182715505e-02, -4.599926770e-01, -1.150787711e+00, -1.000037670e+00):
+        q = _fma32(q, t, f(c))
+    return _fma32(-t, torch.exp2(q), x.clamp(min=0.0))
+
+
+def conv0_f32(wav, lens, normalize, w, bias, gamma, beta, mode):
+    """A float32 restatement of csrc/wavlm.hip's arithmetic on the CPU, for the measurement of CONV0_LAMBDA only: the waveform statistics
+    in float64 and mean / rstd rounded to fp32, (x - mean) * rstd in fp32, the ten taps as an fma chain with tap 0 first; group mode:
+    fp32 sums of y and y^2 in frame order per block of 512 frames, the blocks added in float64, var = E[y^2] - m^2 in float64, the affine
+    folded into y * sc + sh; layer mode: the chain starts at the bias, eight channels per lane summed in order and the 64 lanes by an
+    xor butterfly, the variance centred; the polynomial GELU of common.h.  -> the fp32 values before the bf16 store, [B, T0, C]."""
+    B, L = wav.shape
+    C = w.shape[0]
+    T0 = conv0_frames(L)
+    wf, gm, bt = w.float(), gamma.float(), beta.float()
+    out = torch.zeros(B, T0, C, dtype=torch.float32)
+    for b in range(B):
+        n = L if lens is None else int(lens[b])
+        Tb = conv0_frames(n)
+        if Tb == 0:
+            continue
+        x = wav[b, :n].float()
+        if normalize:
+            s, q = x.double().sum(), (x.double() ** 2).sum()
+            m = s / n
+            var = q / n - m * m
+            x = (x - m.float()) * (1.0 / torch.sqrt(var.clamp(min=0.0) + 1e-7)).float()
+        win = x.unfold(0, 10, 5)[:Tb]                                            # [Tb, 10]
+        y = (bias.float()[None, :].expand(Tb, C) if (bias is not None and mode == "layer") else torch.zeros(Tb, C)).contiguous()
+        for j in range(10):
+            y = _fma32(wf[None, :, j].expand(Tb, C), win[:, j:j + 1].expand(Tb, C), y)
+        if mode == "group":
+            S, Q = torch.zeros(C, dtype=F64), torch.zeros(C, dtype=F64)
+            for t0 in range(0, Tb, 512):
+                sa, qa = torch.zeros(C), torch.zeros(C)
+                for t in range(t0, min(t0 + 512, Tb)):
+                    sa = sa + y[t]
+                    qa = _fma32(y[t], y[t], qa)
+                S, Q = S + sa.double(), Q + qa.double()
+            m = S / Tb
+            var = Q / Tb - m * m
+            sc = (1.0 / torch.sqrt(var.clamp(min=0.0) + 1e-5)).float() * gm
+            sh = _fma32(-m.float(), sc, bt)
+            v = _fma32(y, sc[None, :].expand(Tb, C), sh[None, :].expand(Tb, C))
+        else:
+            def lanes(z):                                                        # [Tb, C] -> the wave's sum: 8 per lane in order, butterfly
+                zl = F.pad(z, (0, 512 - C)).view(Tb, 64, 8)
+                acc = torch.zeros(Tb, 64)
+                for e in range(8):
+                    acc = acc + zl[:, :, e]
+                idx = torch.arange(64)
+                for o in (32, 16, 8, 4, 2, 1):
+                    acc = acc + acc[:, idx ^ o]
+                return acc[:, :1]
+            mu = lanes(y) / C
+            d = y - mu
+            zl = F.pad(d, (0, 512 - C)).view(Tb, 64, 8)
+            acc = torch.zeros(Tb, 64)
+            for e in range(8):
+                acc = _fma32(zl[:, :, e], zl[:, :, e], acc)
+            idx = torch.arange(64)
+            for o in (32, 16, 8, 4, 2, 1):
+                acc = acc + acc[:, idx ^ o]
+            rs = 1.0 / torch.sqrt(acc[:, :1] / C + 1e-5)
+            v = _fma32(d * rs, gm[None, :].expand(Tb, C), bt[None, :].expand(Tb, C))
+        out[b, :Tb] = gelu_f32(v)
+    return out
+
+
+# (mode, C, T0, r, ragged, wstats, bias, pair): L = 5 (T0 - 1) + 10 + r; ragged: lens = [L, 5 * 199 + 13, 9]; T0 = 8200: the layer
+# kernel's grid-stride path (its grid stops at 2048 blocks of four frames).  Group mode does not read the bias: one case passes one.
+CONV0_CASES = [
+    ("group", 8, 1, 0, False, True, False, False), ("group", 8, 3, 4, False, False, False, True),
+    ("group", 32, 3, 0, False, True, False, True), ("group", 32, 511, 4, True, True, False, False),
+    ("group", 32, 512, 0, True, False, False, True), ("group", 32, 513, 4, False, True, False, True),
+    ("group", 8, 513, 0, True, True, False, False), ("group", 512, 1, 4, False, True, False, True),
+    ("group", 512, 513, 0, True, True, False, True), ("group", 512, 1030, 4, True, True, False, False),
+    ("group", 32, 1030, 0, False, False, False, True), ("group", 512, 512, 4, False, True, True, False),
+    ("group", 8, 1030, 0, True, False, False, True),
+    ("layer", 8, 1, 0, False, True, True, False), ("layer", 8, 3, 4, False, False, False, True),
+    ("layer", 32, 3, 0, False, True, True, True), ("layer", 32, 511, 4, True, True, True, True),
+    ("layer", 32, 512, 0, False, True, False, False), ("layer", 8, 513, 4, True, False, True, True),
+    ("layer", 512, 1, 0, False, True, True, True), ("layer", 512, 513, 4, True, True, True, False),
+    ("layer", 512, 1030, 0, True, True, True, True), ("layer", 32, 1030, 4, False, False, True, False),
+    ("layer", 512, 3, 4, False, True, True, False), ("layer", 32, 8200, 0, True, True, True, True),
+    ("layer", 32, 8200, 4, False, True, False, False),
+]
+CONV0_RAGGED_LEN = 5 * 199 + 13
+CONV0_LOWVAR = 2                          # channel with weights 100 x smaller: conv variance ~1e-5, where GroupNorm's eps matters
+
+
+def conv0_id(case):
+    mode, C, T0, r, ragged, ws, bias, pair = case
+    return f"{mode}_C{C}_T{T0}_r{r}_ragged{int(ragged)}_ws{int(ws)}_bias{int(bias)}_pair{int(pair)}"
+
+
+def conv0_inputs(case, fill=float("nan")):
+    """-> dict.  wav [3, L]: noise at 0.1 + DC 0.02 + a slow sine, clip 2 all zero; ragged: `fill` behind each length.  Weights N(0, 0.1),
+    channel 0 all positive, channel 1 all zero (variance 0: the output is gelu(beta) in group mode), channel 2 scaled by 0.01."""
+    mode, C, T0, r, ragged, ws, bias, pair = case
+    L = 5 * (T0 - 1) + 10 + r
+    g = _gen(8000 + C + 7 * T0 + r)
+    t = torch.arange(L, dtype=F64)
+    wav = 0.1 * torch.randn(3, L, generator=g) + 0.02 + (0.05 * torch.sin(2.0 * math.pi * t / 3000.0)).float()[None, :]
+    wav[2] = 0.0
+    lens = [L, CONV0_RAGGED_LEN, 9] if ragged else None
+    if ragged and fill is not None:
+        for b, n in enumerate(lens):
+            wav[b, n:] = fill
+    w = 0.1 * torch.randn(C, 10, generator=g)
+    w[0] = w[0].abs() + 0.01
+    w[1] = 0.0
+    w[CONV0_LOWVAR] *= 0.01
+    return {"mode": mode, "C": C, "T0": T0, "L": L, "lens": lens, "normalize": ws, "pair": pair, "wav": wav, "w": w,
+            "bias": 0.2 * torch.randn(C, generator=g) if bias else None, "gamma": 1.0 + 0.1 * torch.randn(C, generator=g),
+            "beta": 0.1 * torch.randn(C, generator=g)}
+
+
+def conv0_case_ref(c, **wrong):
+    return conv0_ref(c["wav"], c["lens"], c["normalize"], c["w"], c["bias"], c["gamma"], c["beta"], c["mode"], with_scale=True, **wrong)
+
+
+def conv0_valid(c):
+    n = torch.tensor([c["T0"]] * 3 if c["lens"] is None else [conv0_frames(x) for x in c["lens"]])
+    return torch.arange(c["T0"])[None, :] < n[:, None]
+
+
+# bound: the store -- 2^-8 |ref| for hi alone, as posconv_bound's bf16 store, 2^-15 |ref| for a hi + lo pair -- plus CONV0_LAMBDA * scale,
+# scale = |gamma| r (|y - mu| + |mu| + 1 / r + A) + |beta|: layernorm_bound's form with the conv's own magnitude A = sum_j |w_j x_j| added.
+# CONV0_LAMBDA = 4 x the largest err / scale of conv0_f32 (the CPU restatement of the kernel's fp32 arithmetic, before the store) against
+# conv0_ref over CONV0_CASES; the 4 covers what the device's exp2, rsqrt and reciprocal do differently by a few ulp.  It is never fitted
+# to the kernel's output.  tests/test_ops_ref_cpu.py::test_conv0_lambda_is_the_restatements recomputes the measurement.
+# Measured on the CPU: 2.5e-7 .. 5.2229e-7 over the 26 cases; the largest at group_C512_T1_r4_ragged0_ws1_bias0_pair1 -- one frame, so
+# y = mu and the affine y * sc + sh cancels two numbers of size |mu| r |gamma| ~ 100 (the |mu| term of the scale), on top of the
+# polynomial GELU's own 6.4e-7.  (What the kernel itself came to on MI355X: the table in tests/test_gpu_ops_frontend.py.)
+CONV0_LAMBDA_MEASURED = 5.2229e-7
+CONV0_LAMBDA = 4 * CONV0_LAMBDA_MEASURED
+
+
+def conv0_bound(ref, scale, pair):
+    return (2.0 ** -15 if pair else 2.0 ** -8) * ref.abs() + CONV0_LAMBDA * scale
+
+
+def frac_outside_nan(wrong, right, bound, factor=2.0):
+    """frac_outside, with a wrong reference that is not finite counted as outside (no finite output can be near it)."""
+    return float((((wrong - right).abs() > factor * bound) | ~torch.isfinite(wrong)).double().mean())

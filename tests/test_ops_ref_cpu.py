@@ -174,3 +174,202 @@ def test_control_layernorm_low_halves_dropped(C, n_div, offset):
     ref, scale = R.layernorm_ref(c["x_hi"].double() + c["x_lo"].double(), c["gamma"], c["beta"], 1e-5, n_div, False, with_scale=True)
     wrong = R.layernorm_ref(c["x_hi"].double(), c["gamma"], c["beta"], 1e-5, n_div, False)
     assert R.frac_outside(wrong, ref, R.layernorm_bound(ref, scale, True)) >= MIN_SHARE
+
+
+# ====================================================================================================== the front-end kernels
+# (tests/test_gpu_ops_frontend.py runs the kernels on the same seeded inputs)
+from types import SimpleNamespace
+
+
+def _report(what, share):
+    print(f"control {what}: {share:.3f} of the reachable elements beyond twice the bound")
+    return share
+
+
+# ------------------------------------------------------------------------------------------------- agreement with the oracle
+@pytest.mark.parametrize("n_mels", [80, 128])
+def test_logmel_reference_agrees_with_the_oracle(n_mels):
+    """oracle/wfl_oracle.py, whisper_log_mel (torch.stft in fp32): shorter than, equal to and longer than n_samples, and `lens` as explicit
+    zero padding.  Tolerance: the fp32 transform's own error on broadband input (5.5e-5 at most on the inputs tried), 1e-4."""
+    g = torch.Generator().manual_seed(4)
+    n = 32000
+    for L in (n, 5000, n + 777):
+        wav = 0.1 * torch.randn(2, L, generator=g)
+        want = O.whisper_log_mel(wav, n_mels, n).double()
+        r = R.logmel_ref(wav, None, n_mels, n)
+        assert r["out"].shape == want.shape and float((r["out"] - want).abs().max()) <= 1e-4
+        # ... and that fp32 path lies inside the bound, with room: a right output passes
+        assert float(((r["out"] - want).abs() / R.logmel_bound(r)).max()) <= 0.5
+    wav = 0.1 * torch.randn(3, n, generator=g)
+    lens = [n, 7001, 0]
+    padded = wav.clone()
+    for b, k in enumerate(lens):
+        padded[b, k:] = 0.0
+    wav[1, 7001:] = float("nan")
+    assert torch.equal(R.logmel_ref(wav, lens, n_mels, n)["out"], R.logmel_ref(padded, None, n_mels, n)["out"])
+    assert bool((R.logmel_ref(wav, lens, n_mels, n)["out"][2] == -1.5).all())          # no sample at all: the clamp, floored by itself
+
+
+@pytest.mark.parametrize("mode", ["group", "layer"])
+@pytest.mark.parametrize("normalize", [False, True])
+def test_conv0_reference_agrees_with_the_oracle(mode, normalize):
+    """oracle/wfl_oracle.py: level 0 of wavlm_feature_encoder after wavlm_normalize (F.conv1d, F.group_norm / F.layer_norm, F.gelu in fp32)."""
+    g = torch.Generator().manual_seed(5)
+    C, L = 24, 1234
+    wav = 0.1 * torch.randn(2, L, generator=g) + 0.03
+    w = 0.1 * torch.randn(C, 10, generator=g)
+    bias = 0.2 * torch.randn(C, generator=g) if mode == "layer" else None
+    gamma, beta = 1.0 + 0.1 * torch.randn(C, generator=g), 0.1 * torch.randn(C, generator=g)
+    p = "encoder.feature_extractor.conv_layers.0."
+    sd = {p + "conv.weight": w[:, None, :], p + "layer_norm.weight": gamma, p + "layer_norm.bias": beta}
+    if bias is not None:
+        sd[p + "conv.bias"] = bias
+    arch = SimpleNamespace(conv_kernel=(10,), conv_stride=(5,), feat_extract_norm=mode)
+    want = O.wavlm_feature_encoder(O.wavlm_normalize(wav, normalize), sd, arch).double()
+    got = R.conv0_ref(wav, None, normalize, w, bias, gamma, beta, mode)
+    assert got.shape == want.shape == (2, O.wavlm_num_frames(L, arch), C)
+    assert float((got - want).abs().max()) <= 1e-5
+    # a shorter clip is the clip alone, and nothing beyond its own frames
+    got2 = R.conv0_ref(wav, [L, 509], normalize, w, bias, gamma, beta, mode)
+    alone = R.conv0_ref(wav[1:, :509], None, normalize, w, bias, gamma, beta, mode)
+    assert torch.equal(got2[0], got[0]) and torch.equal(got2[1, :100], alone[0]) and bool((got2[1, 100:] == 0).all())
+
+
+def test_conv0_lambda_is_the_restatements():
+    """ops_ref.CONV0_LAMBDA is four times what the float32 restatement of the kernel's arithmetic (conv0_f32) measures against conv0_ref
+    over every case of the GPU test, on the CPU -- recomputed here, so the constant cannot drift from its provenance."""
+    worst, at = 0.0, None
+    for case in R.CONV0_CASES:
+        c = R.conv0_inputs(case)
+        ref, scale = R.conv0_case_ref(c)
+        v = R.conv0_f32(c["wav"], c["lens"], c["normalize"], c["w"], c["bias"], c["gamma"], c["beta"], c["mode"]).double()
+        m = R.conv0_valid(c)
+        assert bool((v[~m] == 0).all()) and bool((scale[m] > 0).all())
+        ratio = float(((v - ref).abs() / scale)[m].max())
+        if ratio > worst:
+            worst, at = ratio, R.conv0_id(case)
+    print(f"conv0 restatement: max err / scale {worst:.4e} at {at}")
+    assert abs(worst - R.CONV0_LAMBDA_MEASURED) <= 1e-3 * R.CONV0_LAMBDA_MEASURED, (worst, at)
+    assert R.CONV0_LAMBDA == 4 * R.CONV0_LAMBDA_MEASURED
+
+
+def test_wav_stats_and_clip_frames_references():
+    wav, lens = R.wav_stats_case(1025)
+    st, bd = R.wav_stats_ref(wav, lens)
+    for b, n in enumerate(lens):
+        v = wav[b, :n].double()
+        assert abs(float(st[b, 0] - v.sum())) <= float(bd[b, 0]) and abs(float(st[b, 1] - (v * v).sum())) <= float(bd[b, 1])
+    assert st[2].tolist() == [0.0, 0.0] and bd[2].tolist() == [0.0, 0.0]
+    # clip_frames: the oracle's frame count at every level, zero below a kernel, min_len, the clamp to [0, L]
+    arch = SimpleNamespace(conv_kernel=R.WAVLM_STACK[0], conv_stride=R.WAVLM_STACK[1])
+    out = R.clip_frames_ref([32000, 400, 399, 9, -3, 40000], 32000, *R.WAVLM_STACK, 0)
+    assert out[-1][0] == O.wavlm_num_frames(32000, arch) == 99 and out[-1][1] == O.wavlm_num_frames(400, arch) == 1
+    assert out[-1][2] == 0 and [lv[3] for lv in out] == [0] * 7 and [lv[4] for lv in out] == [0] * 7 and out[-1][5] == 99
+    assert R.clip_frames_ref([200, 201, 32000, 32005], 32000, (0,), (160,), 201) == [[0, 2, 201, 201]]
+
+
+# ------------------------------------------------------------------------------------------------- log-mel controls
+def _lm(n_mels, mp, shape, fill=float("nan"), **wrong):
+    n = 2 * mp * 160
+    wav, L, lens, kinds = R.logmel_case(n, shape, fill)
+    return R.logmel_ref(wav[:, :L], lens, n_mels, n, **wrong), kinds
+
+
+def _clips(kinds, names):
+    return [b for b, k in enumerate(kinds) if k in names]
+
+
+@pytest.mark.parametrize("n_mels,mp", R.LOGMEL_MODELS)
+def test_control_logmel(n_mels, mp):
+    """Each wrong reading of the log-mel definition, on the GPU test's own batches, counted over the elements it can reach:
+      symmetric padding                    the first two and last two frames of the clips with energy at their edges (noise, DC + noise, impulses)
+      symmetric Hann, the fold's missing 1/2 at sample 200, frames shifted by one, the bank shifted by one bin, the HTK bank
+                                           every element of the noise and DC + noise clips (a silent frame of the impulse clip sits at the
+                                           floor under any of them; on a pure tone only 2-6 % of the elements move)
+      one maximum for the whole batch      the silent clip: its floor comes from another clip's maximum
+      reflection about L - 1               the last frame of every clip of the "longer" batch -- the only one whose window passes n_samples
+      lens ignored                         the clips of the ragged batch shorter than n_samples."""
+    r, kinds = _lm(n_mels, mp, "exact")
+    ref, bound = r["out"], R.logmel_bound(r)
+    nf = ref.shape[2]
+
+    def share(wrong, clips, frames=None):
+        f = torch.arange(nf) if frames is None else torch.tensor(frames)
+        ix = (torch.tensor(clips)[:, None, None], torch.arange(n_mels)[None, :, None], f[None, None, :])
+        return R.frac_outside(wrong[ix], ref[ix], bound[ix])
+
+    edgy, broad = _clips(kinds, R.LOGMEL_BROADBAND), _clips(kinds, ["noise", "dc_noise"])
+    shares = {
+        "symmetric padding": share(_lm(n_mels, mp, "exact", pad="symmetric")[0]["out"], edgy, [0, 1, nf - 2, nf - 1]),
+        "symmetric Hann": share(_lm(n_mels, mp, "exact", window=R.hann400(periodic=False))[0]["out"], broad),
+        "fold without 1/2": share(_lm(n_mels, mp, "exact", fold200=2.0)[0]["out"], broad),
+        "frames shifted": share(_lm(n_mels, mp, "exact", frame_shift=1)[0]["out"], broad),
+        "bank shifted": share(_lm(n_mels, mp, "exact", bank=torch.roll(R.mel_bank(n_mels), 1, dims=0))[0]["out"], broad),
+        "HTK bank": share(_lm(n_mels, mp, "exact", bank=R.mel_bank(n_mels, htk=True))[0]["out"], broad),
+        "batch-wide maximum": share(_lm(n_mels, mp, "exact", batch_max=True)[0]["out"], _clips(kinds, ["silence"])),
+    }
+    # L > n_samples: the tail of 50.0 must be cut before the reflection
+    r2, kinds2 = _lm(n_mels, mp, "longer")
+    assert torch.equal(r2["out"], ref)
+    wrong = _lm(n_mels, mp, "longer", reflect_about_L=True)[0]["out"]
+    shares["reflection about L - 1"] = share(wrong, list(range(len(kinds2))), [nf - 1])
+    # lens: the ragged batch against the same clips read to their end
+    r3, kinds3 = _lm(n_mels, mp, "ragged")
+    wav, L, lens, _ = R.logmel_case(2 * mp * 160, "ragged", fill=None)
+    wrong = R.logmel_ref(wav, None, n_mels, 2 * mp * 160)["out"]
+    b3 = R.logmel_bound(r3)
+    short = [b for b, k in enumerate(lens) if k < 2 * mp * 160]
+    shares["lens ignored"] = R.frac_outside(wrong[short], r3["out"][short], b3[short])
+    for what, s in shares.items():
+        assert _report(f"log-mel {n_mels} x {nf}, {what}", s) >= MIN_SHARE, what
+    # the informative share the GPU test relies on: at most 1 % of a broadband clip's elements have a bound wider than 1e-2
+    for b in edgy:
+        assert float((bound[b] > R.LOGMEL_UNINFORMATIVE).double().mean()) <= 0.01
+
+
+# ------------------------------------------------------------------------------------------------- conv0 controls
+def _conv0_share(c, wrong, ref, scale, m):
+    return R.frac_outside_nan(wrong[m], ref[m], R.conv0_bound(ref, scale, c["pair"])[m])
+
+
+@pytest.mark.parametrize("case", R.CONV0_CASES, ids=R.conv0_id)
+def test_control_conv0(case):
+    """Each wrong reading of level 0, on the GPU case's own inputs (finite junk instead of NaN behind the lengths), counted over what it can reach:
+      taps reversed                              every valid element; not the group cases of one frame, where y = mu and the output is
+                                                 gelu(beta) under any taps
+      unbiased GroupNorm variance                group cases with T0 <= 3 (at one frame it is 0 / 0: no finite output matches)
+      GroupNorm eps 1e-7                         the low-variance channel of the group cases with T0 >= 511, clips with a signal
+      statistics over the batch-wide T0          the shorter clip of the ragged group cases
+      waveform mean over L, not lens[b]          the shorter clip of the ragged layer cases with normalisation (GroupNorm is blind to a
+                                                 per-clip scale and offset of the waveform, so group mode cannot see it)
+      LayerNorm divisor 512                      layer cases with C < 512
+      tanh GELU                                  cases that store a hi + lo pair; bf16 alone (2^-8) is coarser than the two GELUs' distance
+                                                 (4.7e-4 at most), so the hi-only cases cannot see it.  Nor can a group case of one
+                                                 frame: its argument is beta ~ 0.1, where the two GELUs differ by 1e-6, and its bound
+                                                 carries the cancellation of y sc against mu sc (lambda |mu| r ~ 2e-4)."""
+    mode, C, T0, _, ragged, ws, _, pair = case
+    c = R.conv0_inputs(case, fill=0.37)
+    ref, scale = R.conv0_case_ref(c)
+    m = R.conv0_valid(c)
+    assert torch.equal(ref, R.conv0_case_ref(R.conv0_inputs(case))[0])                  # nothing behind a length is read
+    shares = {}
+    if not (mode == "group" and T0 == 1):
+        shares["taps reversed"] = _conv0_share(c, R.conv0_case_ref(c, reverse_taps=True)[0], ref, scale, m)
+    if mode == "group" and T0 <= 3:
+        shares["unbiased variance"] = _conv0_share(c, R.conv0_case_ref(c, unbiased=True)[0], ref, scale, m)
+    if mode == "group" and T0 >= 511:
+        mm = torch.zeros_like(ref, dtype=torch.bool)
+        mm[:2, :, R.CONV0_LOWVAR] = True                                               # (clip 2 is silence: y = mu under any eps)
+        shares["GroupNorm eps 1e-7"] = _conv0_share(c, R.conv0_case_ref(c, gn_eps=1e-7)[0], ref, scale, mm & m[..., None])
+    one = torch.zeros_like(m)
+    one[1] = True
+    if mode == "group" and ragged:
+        shares["batch-wide T0"] = _conv0_share(c, R.conv0_case_ref(c, stats_T=T0)[0], ref, scale, m & one)
+    if mode == "layer" and ragged and ws:
+        shares["waveform mean over L"] = _conv0_share(c, R.conv0_case_ref(c, mean_over_L=True)[0], ref, scale, m & one)
+    if mode == "layer" and C < 512:
+        shares["LayerNorm divisor 512"] = _conv0_share(c, R.conv0_case_ref(c, ln_div=512)[0], ref, scale, m)
+    if pair and not (mode == "group" and T0 == 1):
+        shares["tanh GELU"] = _conv0_share(c, R.conv0_case_ref(c, tanh=True)[0], ref, scale, m)
+    for what, s in shares.items():
+        assert _report(f"conv0 {R.conv0_id(case)}, {what}", s) >= MIN_SHARE, what

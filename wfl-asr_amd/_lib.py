@@ -63,6 +63,10 @@ SIGNATURES = {
     "wfl_op_relpos_table": (_I, [_P, _P, _I, _I, _I, _P, _P]),
     "wfl_op_relpos_gate": (_I, [_P, _P, _L, _L, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P]),
     "wfl_op_regroup": (_I, [_P, _I, _I, _I, _L, _L, _I, _I, _I, _P, _P, _P]),
+    "wfl_op_wav_stats": (_I, [_P, _L, _P, _I, _I, _P, _P]),
+    "wfl_op_clip_frames": (_I, [_P, _I, _I, _I, _P, _P, _I, _P, _P]),
+    "wfl_op_conv0_scratch_bytes": (_L, [_I, _I, _I]),
+    "wfl_op_conv0": (_I, [_P, _L, _P, _I, _I, _P, _P, _P, _P, _P, _I, _I, _P, _P, _L, _I, _I, _P, _L, _P]),
     "wfl_op_posconv": (_I, [_P, _L, _L, _I, _I, _I, _I, _I, _I, _P, _L, _P, _P, _P, _P, _P, _L, _P, _P]),
     "wfl_op_layernorm_act": (_I, [_P, _P, _L, _P, _P, _L, _P, _P, _F, _L, _I, _I, _I, _I, _I, _I, _P, _P]),
     "wfl_op_layernorm_pair": (_I, [_P, _P, _P, _P, _P, _P, _L, _P, _P, _P, _P, _F, _L, _I, _I, _I, _I, _I, _P, _P]),

@@ -8,6 +8,7 @@
 #include "../../include/wfl_asr.h"
 
 #include <cmath>
+#include <cstdint>
 #include <cstdio>
 #include <cstring>
 #include <map>
@@ -1594,7 +1595,9 @@ int32_t wfl_logmel(wfl_model* m, const float* wav, int64_t ldw, const int32_t* l
                    void* workspace, int64_t workspace_bytes, void* stream) {
   if (!m || !m->finalized) return fail(-1, "wfl_logmel: model not finalized");
   if (m->a.encoder_type != WFL_ENC_WHISPER) return fail(-1, "wfl_logmel: not a Whisper model");
-  if (B <= 0 || L < 0 || ldw < L) return fail(-1, "wfl_logmel: bad shape");
+  // (L == 0 would make the staging loads of logmel_power_kernel clamp their index to L - 1 = -1: rejected here, as wfl_forward does)
+  if (!wav || !out) return fail(-1, "wfl_logmel: null wav or out");
+  if (B <= 0 || L <= 0 || ldw < L) return fail(-1, "wfl_logmel: bad shape (B > 0, L > 0, ldw >= L)");
   if (int r = check_device(m, "wfl_logmel")) return r;
   const Plan p = make_plan(m, B, L);
   if (workspace_bytes < p.total) return fail(-1, "wfl_logmel: workspace too small");
@@ -2270,6 +2273,52 @@ int32_t wfl_op_regroup(const void* x, int32_t d, int32_t groups, int32_t cpg, in
   if (!x || !xg || groups <= 0 || cpg <= 0 || R <= 0 || B <= 0 || P <= 0) return fail(-1, "wfl_op_regroup: bad argument");
   const int r = wfl_launch_regroup((const bf16_t*)x, d, groups, cpg, R, lead, B, P, T, (bf16_t*)xg, (hipStream_t)stream, clip_T);
   return r ? fail(r, "wfl_op_regroup: channel split not taken or launch failure (" + std::to_string(r) + ")") : 0;
+}
+
+int32_t wfl_op_wav_stats(const float* wav, int64_t ldw, const int32_t* lens, int32_t B, int32_t L, double* stats, void* stream) {
+  if (!wav || !stats) return fail(-1, "wfl_op_wav_stats: null argument");
+  if (B <= 0 || L <= 0 || ldw < L) return fail(-1, "wfl_op_wav_stats: bad shape (B > 0, L > 0, ldw >= L)");
+  const int r = wfl_launch_wav_stats(wav, ldw, B, L, stats, (hipStream_t)stream, lens);
+  return r ? fail(r, "wfl_op_wav_stats: launch failure (" + std::to_string(r) + ")") : 0;
+}
+
+int32_t wfl_op_clip_frames(const int32_t* lens, int32_t B, int32_t L, int32_t n, const int32_t* kernel, const int32_t* stride,
+                           int32_t min_len, int32_t* out, void* stream) {
+  if (!lens || !kernel || !stride || !out) return fail(-1, "wfl_op_clip_frames: null argument");
+  if (B <= 0 || L < 0) return fail(-1, "wfl_op_clip_frames: bad shape (B > 0, L >= 0)");
+  if (n < 1 || n > 8) return fail(-1, "wfl_op_clip_frames: 1 .. 8 levels");
+  for (int i = 0; i < n; ++i)
+    if (kernel[i] < 0 || stride[i] <= 0) return fail(-1, "wfl_op_clip_frames: kernel >= 0 and stride > 0 at every level");
+  const int r = wfl_launch_clip_frames(lens, B, L, n, kernel, stride, min_len, out, (hipStream_t)stream);
+  return r ? fail(r, "wfl_op_clip_frames: launch failure (" + std::to_string(r) + ")") : 0;
+}
+
+// scratch of wfl_op_conv0's group mode: cstats [B][C][2] double, then cpart [B][time blocks of 512 frames][C][2] float
+int64_t wfl_op_conv0_scratch_bytes(int32_t B, int32_t T0, int32_t C) {
+  if (B <= 0 || T0 <= 0 || C <= 0) return 0;
+  const int64_t nblk = ((int64_t)T0 + 511) / 512;
+  return (int64_t)B * C * 2 * (int64_t)sizeof(double) + (int64_t)B * nblk * C * 2 * (int64_t)sizeof(float);
+}
+
+int32_t wfl_op_conv0(const float* wav, int64_t ldw, const int32_t* lens, int32_t B, int32_t L, const double* wstats, const float* w,
+                     const float* bias, const float* gamma, const float* beta, int32_t C, int32_t T0, void* out, void* out_lo,
+                     int64_t lead, int32_t P, int32_t group_norm, void* scratch, int64_t scratch_bytes, void* stream) {
+  if (!wav || !w || !gamma || !beta || !out) return fail(-1, "wfl_op_conv0: null argument");
+  if (B <= 0 || L < 10 || ldw < L) return fail(-1, "wfl_op_conv0: bad shape (B > 0, L >= 10, ldw >= L)");
+  if (C <= 0 || C % 8 || C > 512) return fail(-1, "wfl_op_conv0: C a multiple of 8, at most 512");
+  if (T0 <= 0 || T0 > (L - 10) / 5 + 1 || P < T0 || lead < 0) return fail(-1, "wfl_op_conv0: 0 < T0 <= (L - 10) / 5 + 1, P >= T0, lead >= 0");
+  Conv0Args c{};
+  c.wav = wav; c.ldw = ldw; c.L = L; c.wstats = wstats; c.w = w; c.bias = bias; c.gamma = gamma; c.beta = beta;
+  c.B = B; c.T0 = T0; c.C = C; c.lens = lens;
+  c.out = (bf16_t*)out; c.out_lo = (bf16_t*)out_lo; c.lead = lead; c.P = P;
+  if (group_norm) {
+    if (!scratch || ((uintptr_t)scratch & 15) || scratch_bytes < wfl_op_conv0_scratch_bytes(B, T0, C))
+      return fail(-1, "wfl_op_conv0: group mode needs 16-byte aligned scratch of wfl_op_conv0_scratch_bytes(B, T0, C)");
+    c.cstats = (double*)scratch;
+    c.cpart = (float*)((char*)scratch + (size_t)B * C * 2 * sizeof(double));
+  }
+  const int r = wfl_launch_conv0(c, group_norm, (hipStream_t)stream);
+  return r ? fail(r, "wfl_op_conv0: launch failure (" + std::to_string(r) + ")") : 0;
 }
 
 int32_t wfl_op_posconv(const void* xg, int64_t R, int64_t lead, int32_t B, int32_t P, int32_t T, int32_t groups, int32_t cpg, int32_t taps,
