@@ -953,6 +953,47 @@ int32_t wfl_decode_bigram_counts(const float* logits, int64_t ldl, int32_t C, in
                                  float threshold, void* workspace, int64_t workspace_bytes, float* logz, float* counts, int32_t* status,
                                  void* stream);
 
+/* ---- BIO-grammar Viterbi decode with a phone-bigram prior AND a duration prior per phoneme on the GPU: the free decode as an
+ * explicit-duration (semi-Markov) search (`postprocess.decode_duration_prior`; wfl-asr_amd/decode.py, wfl-asr_amd/durations.py).  No
+ * counterpart in the reference.  Clips, logits, pairs, o_id, trans, threshold, ids, score, the symbols (0 is O, 1 + p is phoneme p;
+ * N = n_pairs + 1), the states, the legality rule, the forced-to-O rule, the virtual O frame before frame 0 and "any state may end the
+ * clip" are wfl_decode_bigram's.  sym_dur (device), [n_pairs] int32: the row of `dur` of phoneme p, -1 for no prior.  dur (device) is
+ * wfl_align_duration_prior's table, [n_rows][D + 1] fp32, 1 <= D <= 32: columns L(1) .. L(D), then the per-frame `tail`; entries finite
+ * or -inf, never NaN or +inf; tail <= 0 or -inf.  A run of phoneme q is one B-q frame and then zero or more I-q frames (exactly one frame
+ * for a phoneme without an I class); B-q after B-q / I-q opens a new run of q.  The path maximises
+ *     sum_t z[t][c_t] + sum over opened runs trans[previous symbol][opened symbol] + sum over phoneme runs L_q(d),
+ *     L_q(d) = dur[r][d - 1] for d <= D,  dur[r][D - 1] + (d - D) dur[r][D] for d > D,  r = sym_dur[q - 1];  L = 0 for r = -1.
+ * O runs carry no prior; the run in progress at the clip's last frame ends there and pays its L.  Frame by frame, everything of frame
+ * t - 1 on the right, for phoneme q (zB, zI its B and I logits; -inf on a forced frame, zI -inf without an I class):
+ *     In_q(t)  = max_s (end_s(t-1) + trans[s][q])                                the lowest s on a tie
+ *     R_q^1(t) = In_q(t) + zB_t(q)
+ *     R_q^j(t) = R_q^{j-1}(t-1) + zI_t(q)             2 <= j <= D
+ *     Y_q(t)   = max(Y_q(t-1), R_q^D(t-1) + L_q(D)) + zI_t(q) + tail_q           Y first on a tie
+ *     end_q(t) = max(max_j R_q^j(t) + L_q(j), Y_q(t))                            the shortest j first, Y last on a tie
+ *     O        : z + max(d[O], max_{p != O} (end_p(t-1) + trans[p][O]))          wfl_decode_bigram's line
+ * -inf only ever adds: no expression forms inf - inf.  The end state is the best `end` of the last frame, the lowest symbol on a tie.
+ * score[b] is the objective minus the frames' log-sum-exp.  With every sym_dur = -1, or an all-zero table, the objective is
+ * wfl_decode_bigram's.
+ * status[b]: 0 ok; 2 C above 1024 or N above WFL_DECODE_BIGRAM_MAX_SYMBOLS (whatever D); 4 a bad class table, as wfl_decode, or a sym_dur
+ * outside -1 .. n_rows - 1.  All-O is always a path, so there is no status 1.  A clip with status != 0 gets ids = o_id and score 0.
+ * Host-side errors (negative return) are wfl_decode_bigram's, and: a null sym_dur with n_pairs > 0 and frames present, a null dur with
+ * n_rows > 0, n_rows < 0, D outside 1 .. 32, a workspace below wfl_decode_duration_workspace_bytes.
+ * One workgroup per clip: a clip decoded alone equals the same clip inside any batch, bit for bit.  fp32 scores; every 16 frames the
+ * largest end[] is taken off every state and every entry of the run history (offset in double), and a history entry is at most D
+ * frames old, so nothing grows with the clip's length.
+ * Workspace, per clip with T > 0, in 4-byte words: round_up_64(T ceil(N / 2)) + H + 2 round_up_64(T)  (per frame and symbol 16 bits:
+ * the winning predecessor symbol | the winning duration 1 .. D, D + 1 for the tail, << 8 | the tail's stay / enter bit << 14 | O's bit
+ * << 15; H; the frames' log-sum-exp; their forced flags).  H holds the run history and the symbols' rows of dur where one CU's LDS does
+ * not hold them beside the trans table: with HS = round_up_64(N), H = 0 when
+ *     16 ceil(max(4 N N, 128 ceil(N / 2)) / 16) + 8448 + 4 (2 D + 1) HS <= 163840 - 4416
+ * (every D at N <= 141; at the cap of 192 symbols D = 1 only), else H = round_up_64((2 D + 1) HS).  0 above the symbol cap;
+ * wfl_decode_duration_workspace_bytes returns -1 for D outside 1 .. 32. */
+int64_t wfl_decode_duration_workspace_bytes(const int32_t* n_frames_host, int32_t n_clips, int32_t n_pairs, int32_t D);
+int32_t wfl_decode_duration(const float* logits, int64_t ldl, int32_t C, int32_t o_id, const int64_t* frame_off_host,
+                            const int32_t* n_frames_host, int32_t n_clips, const int32_t* pairs, int32_t n_pairs, const float* trans,
+                            const int32_t* sym_dur, const float* dur, int32_t n_rows, int32_t D, float threshold, void* workspace,
+                            int64_t workspace_bytes, int32_t* ids, float* score, int32_t* status, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

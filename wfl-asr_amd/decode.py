@@ -11,6 +11,8 @@ follows `B-p` or `I-p`, and every run that is opened costs `switch_penalty` nats
   bio_viterbi         the C ABI on CUDA tensors: a ragged batch of clips in one call
   bio_viterbi_bigram  the same search with a phone-bigram prior: a table of transition weights per (previous symbol, opened symbol)
                       in place of the flat switch penalty (csrc/decode_bigram.hip, `wfl_decode_bigram`; phonotactics.py makes the table)
+  bio_viterbi_duration  the bigram search with a duration prior per phoneme: an explicit-duration (semi-Markov) search
+                      (csrc/decode_duration.hip, `wfl_decode_duration`; durations.py makes the table, duration_symbol_rows the rows)
   decode_posteriors   forward-backward over the same grammar (csrc/decode_posterior.hip, `wfl_decode_posterior`): logZ, and per frame
                       the posterior of the phoneme and of the exact class the path chose (`postprocess.decode_scores`)
   decode_posteriors_bigram  the same over the grammar of bio_viterbi_bigram, the table included (csrc/decode_bigram_posterior.hip,
@@ -57,11 +59,12 @@ def class_table(label_list) -> ClassTable:
     return ClassTable(label_list.index("O"), np.array(pairs, np.int32).reshape(-1, 2))
 
 
-def _workspace_bytes(symbol, n_frames, n_pairs) -> int:
+def _workspace_bytes(symbol, n_frames, n_pairs, *more) -> int:
+    """`more`: what the entry's size function takes after n_pairs (wfl_decode_duration's D)."""
     T = np.ascontiguousarray(n_frames, np.int32)
-    n = int(getattr(_lib.load(), symbol)(_hp(T), T.size, int(n_pairs)))
+    n = int(getattr(_lib.load(), symbol)(_hp(T), T.size, int(n_pairs), *more))
     if n < 0:
-        raise _lib.WflError(f"{symbol}: negative frame or pair count")
+        raise _lib.WflError(f"{symbol}: negative frame or pair count" + (f", or a bad {more!r}" if more else ""))
     return n
 
 
@@ -83,6 +86,10 @@ def bigram_posterior_workspace_bytes(n_frames, n_pairs) -> int:
 
 def bigram_counts_workspace_bytes(n_frames, n_pairs) -> int:
     return _workspace_bytes("wfl_decode_bigram_counts_workspace_bytes", n_frames, n_pairs)
+
+
+def duration_workspace_bytes(n_frames, n_pairs, D) -> int:
+    return _workspace_bytes("wfl_decode_duration_workspace_bytes", n_frames, n_pairs, int(D))
 
 
 def _check_clips(logits, n_frames, table, switch_penalty, threshold, frame_offsets):
@@ -109,14 +116,15 @@ def _check_clips(logits, n_frames, table, switch_penalty, threshold, frame_offse
     return int(o_id), pairs, nb, T, F0
 
 
-def _call(entry, logits, clips, middle, outputs, stream):
+def _call(entry, logits, clips, middle, outputs, stream, ws_more=()):
     """What the three entries share after _check_clips (`clips`: its result): `entry`'s workspace, the class pairs on the device, the
     call on `stream` (default: the current one) and its check.  middle: the arguments between n_pairs and the workspace, outputs: the
-    tensors after it; a float goes as it is, a tensor as its pointer, a numpy array is uploaded for the call."""
+    tensors after it; a float or an int goes as it is, a tensor as its pointer, a numpy array is uploaded for the call.  ws_more: what
+    the entry's size function takes after n_pairs."""
     o_id, pairs, nb, T, F0 = clips
     lib = _lib.load()
     dev = logits.device
-    ws_n = _workspace_bytes(entry + "_workspace_bytes", T, len(pairs)) if logits.shape[1] <= MAX_CLASSES else 0
+    ws_n = _workspace_bytes(entry + "_workspace_bytes", T, len(pairs), *ws_more) if logits.shape[1] <= MAX_CLASSES else 0
     ws = torch.empty(max(ws_n, 1), dtype=torch.uint8, device=dev)
     d_pairs = torch.from_numpy(pairs if len(pairs) else np.full((1, 2), -1, np.int32)).to(dev)
     temporaries = [ws, d_pairs]
@@ -196,6 +204,80 @@ def bio_viterbi_bigram(logits, n_frames, table, trans, threshold, frame_offsets=
     status = torch.empty(max(nb, 1), dtype=torch.int32, device=logits.device)
     _call("wfl_decode_bigram", logits, clips, (w, float(threshold)), (ids, score, status), stream)
     return ids, score[:nb], status[:nb]
+
+
+MAX_DURATION = 32          # wfl_decode_duration's longest explicit duration D (wfl_align_duration_prior's)
+
+
+def check_duration_table(dur) -> np.ndarray:
+    """A table of run-length scores for bio_viterbi_duration -> contiguous float32 [rows, D + 1], 1 <= D <= 32: columns L(1) .. L(D), then
+    the per-frame tail (durations.table builds it).  Entries are finite or -inf (a forbidden duration): never NaN, never +inf; a tail is
+    <= 0 or -inf."""
+    if isinstance(dur, torch.Tensor):
+        dur = dur.detach().cpu().numpy()
+    d = np.asarray(dur)
+    if d.dtype != np.float32:
+        raise ValueError(f"dur must be float32, got {d.dtype}")
+    if d.ndim != 2 or not 2 <= d.shape[1] <= MAX_DURATION + 1:
+        raise ValueError(f"dur must be a [rows, D + 1] table with 1 <= D <= {MAX_DURATION}, got {list(d.shape)}")
+    if np.isnan(d).any():
+        raise ValueError("dur holds a NaN")
+    if np.isposinf(d).any():
+        raise ValueError("dur holds +inf (entries are finite, or -inf for a forbidden duration)")
+    if (d[:, -1] > 0).any():
+        raise ValueError("a tail of dur is > 0 (the last column is the per-frame score past D frames: <= 0 or -inf)")
+    return np.ascontiguousarray(d)
+
+
+def check_symbol_rows(sym_dur, n_pairs, rows) -> np.ndarray:
+    """The phonemes' rows of the duration table for bio_viterbi_duration -> contiguous int32 [n_pairs], every entry in -1 .. rows - 1."""
+    if isinstance(sym_dur, torch.Tensor):
+        sym_dur = sym_dur.detach().cpu().numpy()
+    r = np.asarray(sym_dur)
+    if r.dtype != np.int32:
+        raise ValueError(f"sym_dur must be int32, got {r.dtype}")
+    if r.shape != (int(n_pairs),):
+        raise ValueError(f"sym_dur must hold one row per phoneme of the class table ([{int(n_pairs)}]), got {list(r.shape)}")
+    if r.size and (int(r.min()) < -1 or int(r.max()) >= int(rows)):
+        raise ValueError(f"sym_dur must lie in -1 .. {int(rows) - 1} (the rows of dur; -1: no prior)")
+    return np.ascontiguousarray(r)
+
+
+def bio_viterbi_duration(logits, n_frames, table, trans, dur, sym_dur, threshold, frame_offsets=None, stream=None):
+    """bio_viterbi_bigram with a duration prior per phoneme: an explicit-duration (semi-Markov) search (csrc/decode_duration.hip,
+    `wfl_decode_duration`).  A run of d frames of phoneme p adds L(d) of row sym_dur[p] of `dur`.  Arguments and results are
+    bio_viterbi_bigram's, but:
+
+    dur      float32 [rows, D + 1], 1 <= D <= 32: L(1) .. L(D), then the per-frame tail of every frame past D (check_duration_table;
+             durations.table builds it from a duration prior); -inf forbids a duration.
+    sym_dur  int32 [phonemes of `table`]: each phoneme's row of `dur`, -1 for no prior (duration_symbol_rows).
+    O runs carry no prior.  With every sym_dur = -1, or an all-zero `dur`, the objective is bio_viterbi_bigram's."""
+    clips = _check_clips(logits, n_frames, table, 0.0, threshold, frame_offsets)
+    w = check_transitions(trans, len(clips[1]))
+    d = check_duration_table(dur)
+    r = check_symbol_rows(sym_dur, len(clips[1]), d.shape[0])
+    nb = clips[2]
+    ids = torch.empty(logits.shape[0], dtype=torch.int32, device=logits.device)
+    score = torch.empty(max(nb, 1), dtype=torch.float32, device=logits.device)
+    status = torch.empty(max(nb, 1), dtype=torch.int32, device=logits.device)
+    D = d.shape[1] - 1
+    r_up = r if r.size else np.full(1, -1, np.int32)
+    d_up = d if d.size else np.zeros((1, D + 1), np.float32)
+    _call("wfl_decode_duration", logits, clips, (w, r_up, d_up, int(d.shape[0]), D, float(threshold)), (ids, score, status), stream,
+          ws_more=(D,))
+    return ids, score[:nb], status[:nb]
+
+
+def duration_symbol_rows(prior, table, labels, output_names=None) -> np.ndarray:
+    """The sym_dur of bio_viterbi_duration: for each phoneme of the class table `table` (class_table(labels)) the row of the duration
+    prior `prior` (durations.DurationPrior) that its OUTPUT name has -- the naming rule of align.duration_rows, whose tokens are output
+    names.  output_names: a mapping from a phoneme's label name (the `x` of `B-x`) to the name it is written under (the merge map's
+    back-mapping); None, or a name it lacks: the label name itself.  Two phonemes with one output name share its row.  A name the
+    prior lacks, or whose row is null (no sample), gives -1: no prior."""
+    row = {name: i for i, name in enumerate(prior.phonemes) if prior.log_prob[i] is not None}
+    names = [str(labels[int(b)])[2:] for b, _ in np.asarray(table[1], np.int32).reshape(-1, 2)]
+    out = output_names or {}
+    return np.array([row.get(out.get(n, n), -1) for n in names], np.int32)
 
 
 def decode_posteriors(logits, n_frames, table, switch_penalty, threshold, ids, frame_offsets=None, stream=None):

@@ -432,12 +432,28 @@ class Labeler:
             self._bigram_cache[key] = (prior, DU.table(prior, weight))
         return self._bigram_cache[key]
 
+    def _decode_duration_prior(self, path, weight, switch_penalty, trans, lang_name):
+        """The free decode's duration prior (opts.decode_duration_prior) -> (trans, dur, sym_dur) for decode.bio_viterbi_duration (a label
+        set over the search's symbol cap is reported by the search, status 2, as the bigram's is).  trans: the phoneme
+        bigram's table, or None: the flat table -switch_penalty, wfl_decode's objective.  The prior is _duration_prior's (loaded, checked
+        against the frame clock and the output names, scaled by `weight`); a phoneme's row is the one of its output name."""
+        prior, dur = self._duration_prior(path, weight, lang_name)
+        if self._decode_table is None:
+            self._decode_table = DC.class_table(self.labels)
+        table = self._decode_table
+        n = len(table[1]) + 1
+        if trans is None:
+            trans = np.full((n, n), -float(switch_penalty), np.float32)
+        remap, names = self._names_for(lang_name)
+        out = {ph: names[int(remap[i])] for i, ph in enumerate(self._table.names)}
+        return trans, dur, DC.duration_symbol_rows(prior, table, self.labels, out)
+
     def label_files(self, audio_paths, lang_id=None, confidence_threshold=0.0, verbose=True, align=None, align_scores=None,
                     decode=None, switch_penalty=None, decode_scores=None, phoneme_bigram=None, bigram_weight=None, align_draft=None,
                     draft_tolerance=None, align_edits=None, align_insertions=None, min_duration=None, duration_scores=None,
                     optional_tokens=None, skip_penalty=None, optional_scores=None, filler_token=None, filler_penalty=None,
                     filler_scores=None, duration_prior=None, duration_prior_weight=None, duration_prior_scores=None,
-                    bigram_scores=None):
+                    decode_duration_prior=None, decode_duration_prior_weight=None, bigram_scores=None):
         """-> list (per file) of [(start_s, end_s, phoneme)] after merge + forced alignment; with align_scores, duration_scores,
         decode_scores or bigram_scores, (that list, scores); with align_edits the tuple goes on with one more list, edits, and with
         align_insertions it ends with one more, insertions; with optional_tokens it ends with the list skipped; with a filler_token
@@ -555,7 +571,17 @@ class Labeler:
         searched under the prior, wfl_align_posterior's, with one line, for one the prior left no path for -- and durations[i] one
         align.TokenDuration per transcript token of a file scored under the prior: its run, the prior's log probability of that
         length, the posterior of the run, the mean shift and spread of both its ends and the expected length (None for a file that
-        was not aligned, or was searched without the prior).  The segments are the same with and without."""
+        was not aligned, or was searched without the prior).  The segments are the same with and without.
+
+        decode_duration_prior (with decode "viterbi" only; None: config postprocess.decode_duration_prior, else none): a
+        phoneme_durations.json for the FREE decode: every file the grammar search decodes is searched by the explicit-duration search
+        (decode.bio_viterbi_duration, wfl_decode_duration), in which a run of d frames of a phoneme adds decode_duration_prior_weight
+        (>= 0; None: config postprocess.decode_duration_prior_weight, else 1.0 -- a value to start from, not a measured optimum)
+        times the log probability the prior gives d frames of the phoneme's output name; a phoneme the prior does not hold has none, and
+        O runs carry none.  Opened runs cost what they cost without the prior: the phoneme_bigram's table where one is given, else the
+        flat switch penalty.  A file's chunks are one clip, so a run that crosses a chunk seam is one run and pays one prior.  The
+        file is checked as a duration_prior is; decode_scores and bigram_scores beside it are refused.  `duration_prior` keeps meaning
+        the transcript alignment's prior."""
         opts = self.options(align=align, align_scores=align_scores, decode=decode, switch_penalty=switch_penalty,
                             decode_scores=decode_scores, phoneme_bigram=phoneme_bigram, bigram_weight=bigram_weight,
                             bigram_scores=bigram_scores, align_draft=align_draft, draft_tolerance=draft_tolerance,
@@ -563,7 +589,8 @@ class Labeler:
                             duration_scores=duration_scores, optional_tokens=optional_tokens, skip_penalty=skip_penalty,
                             optional_scores=optional_scores, filler_token=filler_token, filler_penalty=filler_penalty,
                             filler_scores=filler_scores, duration_prior=duration_prior, duration_prior_weight=duration_prior_weight,
-                            duration_prior_scores=duration_prior_scores)
+                            duration_prior_scores=duration_prior_scores, decode_duration_prior=decode_duration_prior,
+                            decode_duration_prior_weight=decode_duration_prior_weight)
         edits = {} if opts.align_edits else None
         insertions = {} if opts.align_insertions else None
         skipped = {} if opts.optional_tokens is not None else None
@@ -609,6 +636,8 @@ class Labeler:
         trans = self._bigram_table(opts.phoneme_bigram, opts.switch_penalty, opts.bigram_weight) if opts.phoneme_bigram else None
         prior = (self._duration_prior(opts.duration_prior, opts.duration_prior_weight, self._lang_name(lang_id))
                  if opts.duration_prior else None)
+        free_prior = (self._decode_duration_prior(opts.decode_duration_prior, opts.decode_duration_prior_weight, opts.switch_penalty,
+                                                  trans, self._lang_name(lang_id)) if opts.decode_duration_prior else None)
         if opts.decode == "viterbi" and int(self.config["postprocess"].get("median_filter", 0)) > 1:
             print("decode: viterbi -- postprocess.median_filter is not applied (the switch penalty takes its place)")
         if lang_id is not None and self.lang2id and lang_id > max(self.lang2id.values()):
@@ -636,7 +665,7 @@ class Labeler:
         if opts.decode == "viterbi":
             # the free decode by the grammar search; a file it could not decode (with a message) takes the argmax decode
             got, free_scores = self._decode_viterbi(paths(free), lang_id, confidence_threshold, verbose, opts.switch_penalty,
-                                                    opts.free_scores, trans)
+                                                    opts.free_scores, trans, free_prior)
             searched = {free[j]: segs for j, segs in got.items()}
             for j, sc in free_scores.items():
                 scores[free[j]] = sc
@@ -832,7 +861,7 @@ class Labeler:
             clock += len(x) / self.sr
         return cf, co, cc
 
-    def _decode_viterbi(self, audio_paths, lang_id, threshold, verbose, switch_penalty, want_scores=False, trans=None):
+    def _decode_viterbi(self, audio_paths, lang_id, threshold, verbose, switch_penalty, want_scores=False, trans=None, free_prior=None):
         """decode="viterbi": the free decode of files by the BIO-grammar search (decode.py, wfl_decode) -> ({file index: segments
         [(start_s, end_s, phoneme)] after the merge-map names and merge_segments, before any string match}, {file index: FreeScore}).  The files' chunks are
         forwarded with logits (kept on the device); each file's chunks' valid logits rows are concatenated on the device, so one
@@ -841,7 +870,8 @@ class Labeler:
         by argmax.  want_scores: right after the search, one wfl_decode_posterior call per wave over the clips it decoded (same
         logits, the device `ids`; wfl_decode_bigram_posterior with the same table when the search was the bigram's) and one log-sum-exp reduction over the wave's logits, the per-frame arrays back in one more copy; without, the second dict stays empty and the calls are
         the search's alone.  trans: the transition table of a phoneme bigram (_bigram_table); the search is then wfl_decode_bigram's,
-        everything around it the same."""
+        everything around it the same.  free_prior: _decode_duration_prior's triple; the search is then wfl_decode_duration's under its
+        table (never with want_scores: options.DECODE_DURATION_PRIOR_ERROR)."""
         lang_name = self._lang_name(lang_id)
         remap, names = self._names_for(lang_name)
         if self._decode_table is None:
@@ -855,7 +885,9 @@ class Labeler:
                 continue
             _, rows = self._forward_with_logits(sel, by_file, lang_id, threshold)
             frames, lg = self._file_rows(rows, by_file, sel)
-            if trans is None:
+            if free_prior is not None:
+                d_ids, d_score, d_st = DC.bio_viterbi_duration(lg, frames, table, *free_prior, threshold)
+            elif trans is None:
                 d_ids, d_score, d_st = DC.bio_viterbi(lg, frames, table, switch_penalty, threshold)
             else:
                 d_ids, d_score, d_st = DC.bio_viterbi_bigram(lg, frames, table, trans, threshold)
@@ -881,7 +913,7 @@ class Labeler:
             for b, fi in enumerate(sel):
                 n = frames[b]
                 if st_all[b] != DC.STATUS_OK:
-                    fn = "wfl_decode" if trans is None else "wfl_decode_bigram"
+                    fn = "wfl_decode_duration" if free_prior is not None else ("wfl_decode" if trans is None else "wfl_decode_bigram")
                     print(f"{audio_paths[fi]}: viterbi decode not possible ({fn} status {int(st_all[b])}); using the argmax decode")
                 else:
                     plan = self._chunk_plan(rows, by_file[fi], fi)
@@ -907,7 +939,7 @@ class Labeler:
         if self._decode_table is None:
             self._decode_table = DC.class_table(self.labels)
         table = self._decode_table
-        n = len(table.pairs) + 1
+        n = len(table[1]) + 1
         total = np.zeros((n, n), np.float64)
         total_logz = total_lse = 0.0
         n_frames, skipped = 0, []
@@ -1684,7 +1716,7 @@ def infer_audio(audio_path, config_path="config.yaml", checkpoint_path="best_mod
                 align_draft=None, draft_tolerance=None, align_edits=None, align_insertions=None, min_duration=None,
                 duration_scores=None, optional_tokens=None, skip_penalty=None, optional_scores=None, filler_token=None,
                 filler_penalty=None, filler_scores=None, duration_prior=None, duration_prior_weight=None,
-                duration_prior_scores=None, bigram_scores=None):
+                duration_prior_scores=None, decode_duration_prior=None, decode_duration_prior_weight=None, bigram_scores=None):
     """align: "greedy" | "viterbi" | None (config postprocess.align, else greedy): how a `{audio}.txt` transcript is aligned
     (Labeler.label_files).  align_scores (viterbi only; None: config postprocess.align_scores): also write `{stem}.scores.tsv`
     beside the .lab when the file was Viterbi-aligned (format_scores_tsv).  decode: "argmax" | "viterbi" | None (config
@@ -1721,14 +1753,18 @@ def infer_audio(audio_path, config_path="config.yaml", checkpoint_path="best_mod
     config postprocess.duration_prior_scores): also write `{stem}.scores.tsv`, one row per transcript token summed over the lattice
     the file was searched on, and, for a file searched under the prior, `{stem}.durations.tsv`, one row per token with its length,
     the prior's log probability of it, the posterior of its run, the shift and spread of both its ends and its expected length
-    (align.duration_prior_posteriors, align.format_durations_tsv); the .lab is what it is without it."""
+    (align.duration_prior_posteriors, align.format_durations_tsv); the .lab is what it is without it.  decode_duration_prior /
+    decode_duration_prior_weight (decode viterbi only; None: config postprocess.decode_duration_prior /
+    postprocess.decode_duration_prior_weight): the phoneme duration prior of the FREE decode's explicit-duration search and what its log
+    probabilities are multiplied by (Labeler.label_files)."""
     given = dict(align=align, align_scores=align_scores, decode=decode, switch_penalty=switch_penalty, decode_scores=decode_scores,
                  phoneme_bigram=phoneme_bigram, bigram_weight=bigram_weight, bigram_scores=bigram_scores, align_draft=align_draft,
                  draft_tolerance=draft_tolerance, align_edits=align_edits, align_insertions=align_insertions, min_duration=min_duration,
                  duration_scores=duration_scores, optional_tokens=optional_tokens, skip_penalty=skip_penalty,
                  optional_scores=optional_scores, filler_token=filler_token, filler_penalty=filler_penalty,
                  filler_scores=filler_scores, duration_prior=duration_prior, duration_prior_weight=duration_prior_weight,
-                 duration_prior_scores=duration_prior_scores)
+                 duration_prior_scores=duration_prior_scores, decode_duration_prior=decode_duration_prior,
+                 decode_duration_prior_weight=decode_duration_prior_weight)
     _refuse_before_load(config_path, **given)
     lab = _labeler(config_path, checkpoint_path, device)
     opts = lab.options(**given)
@@ -1771,14 +1807,16 @@ def infer_folder(folder_path: str, config_path: str = "config.yaml", checkpoint_
                  decode_scores=None, phoneme_bigram=None, bigram_weight=None, align_draft=None, draft_tolerance=None,
                  align_edits=None, align_insertions=None, min_duration=None, duration_scores=None, optional_tokens=None,
                  skip_penalty=None, optional_scores=None, filler_token=None, filler_penalty=None, filler_scores=None,
-                 duration_prior=None, duration_prior_weight=None, duration_prior_scores=None, bigram_scores=None):
+                 duration_prior=None, duration_prior_weight=None, duration_prior_scores=None,
+                 decode_duration_prior=None, decode_duration_prior_weight=None, bigram_scores=None):
     given = dict(align=align, align_scores=align_scores, decode=decode, switch_penalty=switch_penalty, decode_scores=decode_scores,
                  phoneme_bigram=phoneme_bigram, bigram_weight=bigram_weight, bigram_scores=bigram_scores, align_draft=align_draft,
                  draft_tolerance=draft_tolerance, align_edits=align_edits, align_insertions=align_insertions, min_duration=min_duration,
                  duration_scores=duration_scores, optional_tokens=optional_tokens, skip_penalty=skip_penalty,
                  optional_scores=optional_scores, filler_token=filler_token, filler_penalty=filler_penalty,
                  filler_scores=filler_scores, duration_prior=duration_prior, duration_prior_weight=duration_prior_weight,
-                 duration_prior_scores=duration_prior_scores)
+                 duration_prior_scores=duration_prior_scores, decode_duration_prior=decode_duration_prior,
+                 decode_duration_prior_weight=decode_duration_prior_weight)
     _refuse_before_load(config_path, **given)
     wav_files = sorted(f for f in os.listdir(folder_path) if f.lower().endswith(".wav"))
     os.makedirs(output_dir, exist_ok=True)
@@ -1979,11 +2017,19 @@ def main(argv=None):
                        "per token its length, the prior's log probability of it, the posterior of its run, the shift and spread "
                        "of both its ends and its expected length; for a folder also alignment_scores.tsv and token_durations.tsv, "
                        "the least probable length first. Default: config postprocess.duration_prior_scores, else off.")
+    @click.option("--decode-duration-prior", "decode_duration_prior", type=str, default=None,
+                  help="With --decode viterbi: a phoneme_durations.json (python -m wfl_asr_amd.durations) for the free decode; a run of "
+                       "d frames of a phoneme then adds decode_duration_prior_weight * log P(d | phoneme) to the path's score, in an "
+                       "explicit-duration search on the GPU (under the --phoneme-bigram table where one is given, else the flat "
+                       "switch penalty). Default: config postprocess.decode_duration_prior, else none.")
+    @click.option("--decode-duration-prior-weight", "decode_duration_prior_weight", type=float, default=None,
+                  help="With --decode-duration-prior: what the prior's log probabilities are multiplied by (>= 0). Default: config "
+                       "postprocess.decode_duration_prior_weight, else 1.0 (a value to start from, not a measured optimum).")
     def cli(path, checkpoint, config, output, lang_id, sample, top_k, top_p, temperature, device, confidence_threshold, align,
             align_scores, decode, switch_penalty, decode_scores, phoneme_bigram, bigram_weight, bigram_scores, align_draft,
             draft_tolerance, align_edits, align_insertions, min_duration, duration_scores, optional_tokens, skip_penalty,
             optional_scores, filler_token, filler_penalty, filler_scores, duration_prior, duration_prior_weight,
-            duration_prior_scores):
+            duration_prior_scores, decode_duration_prior, decode_duration_prior_weight):
         if switch_penalty is not None and not switch_penalty >= 0.0:
             raise click.UsageError("--switch-penalty must be >= 0 (nats)")
         if sample:
@@ -2021,7 +2067,8 @@ def main(argv=None):
                            optional_tokens=list(optional_tokens) or None, skip_penalty=skip_penalty, optional_scores=optional_scores,
                            filler_token=filler_token, filler_penalty=filler_penalty, filler_scores=filler_scores,
                            duration_prior=duration_prior, duration_prior_weight=duration_prior_weight,
-                           duration_prior_scores=duration_prior_scores)
+                           duration_prior_scores=duration_prior_scores, decode_duration_prior=decode_duration_prior,
+                           decode_duration_prior_weight=decode_duration_prior_weight)
         except ValueError as err:
             raise click.UsageError(str(err))
         output_path = inf_path if output == "." else output
@@ -2050,7 +2097,9 @@ def main(argv=None):
                   # the prior travels as the bigram does: an empty path for "none", a weight only beside a prior
                   duration_prior=opts.duration_prior or "",
                   duration_prior_weight=opts.duration_prior_weight if opts.duration_prior else None,
-                  duration_prior_scores=opts.duration_prior_scores)
+                  duration_prior_scores=opts.duration_prior_scores,
+                  decode_duration_prior=opts.decode_duration_prior or "",
+                  decode_duration_prior_weight=opts.decode_duration_prior_weight if opts.decode_duration_prior else None)
         if inf_path.is_dir():
             infer_folder(folder_path=str(inf_path), output_dir=str(output_path), **kw)
         else:

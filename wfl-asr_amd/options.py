@@ -66,6 +66,17 @@ infer_folder (before any model is loaded) and the CLI all call `resolve` and car
                            41. needs a duration_prior (it scores the explicit-duration lattice of that search: per token the
                                posterior of its run, the spread of both its ends and its expected length; without a prior
                                align_scores is the option to ask for)
+  decode_duration_prior none 42. PATH of a phoneme_durations.json; a decode_duration_prior or a given decode_duration_prior_weight needs
+                               decode viterbi (the prior is a term of the free decode's path score: the explicit-duration search
+                               wfl_decode_duration, under the phoneme_bigram's table where one is given, else the flat switch
+                               penalty).  `duration_prior` stays the transcript alignment's prior
+  decode_duration_prior_weight 1.0  43. when given, a finite number >= 0 (no bool, no NaN): the table is weight * log P.  The default of
+                               1.0 is a value to start from, not a measured optimum
+                           44. when given, needs a decode_duration_prior (it scales that prior)
+                           45. decode_scores and bigram_scores beside a decode_duration_prior are refused
+                               (DECODE_DURATION_PRIOR_ERROR): their sweeps carry no duration term, and a posterior must score the
+                               grammar its search ran on
+                           (46. with the model known, Labeler.label_files: durations.check, as rule 39)
 """
 from __future__ import annotations
 
@@ -113,6 +124,11 @@ DURATION_PRIOR_ERROR = ("duration_prior cannot be combined with align_draft, min
 
 DURATION_PRIOR_SCORES_ERROR = ("duration_prior_scores needs a duration_prior (postprocess.duration_prior, --duration-prior): it scores "
                                "the explicit-duration lattice of that search; without a prior align_scores is the option to ask for")
+
+
+DECODE_DURATION_PRIOR_ERROR = ("decode_duration_prior cannot be combined with decode_scores or bigram_scores: their forward-backward "
+                               "sweeps carry no duration term, and a posterior must score the grammar the search ran on; drop "
+                               "postprocess.decode_duration_prior (--decode-duration-prior) for the scoring run")
 
 
 def _filler_token(given):
@@ -233,7 +249,9 @@ class PostOptions(_SearchOptions):
         filler_scores    False  score every alignment searched with a filler_token, over the filler lattice
         duration_prior   None   path of a phoneme_durations.json: the duration prior of the explicit-duration search
         duration_prior_weight  1.0  what the prior's log probabilities are multiplied by (also stands for "not given")
-        duration_prior_scores  False  score every alignment searched under a duration_prior, over the explicit-duration lattice"""
+        duration_prior_scores  False  score every alignment searched under a duration_prior, over the explicit-duration lattice
+        decode_duration_prior  None  path of a phoneme_durations.json: the duration prior of the free decode (decode viterbi)
+        decode_duration_prior_weight  1.0  what that prior's log probabilities are multiplied by (also stands for "not given")"""
     align_draft: Optional[str] = None
     draft_tolerance: float = DEFAULT_DRAFT_TOLERANCE
     align_edits: bool = False
@@ -249,11 +267,14 @@ class PostOptions(_SearchOptions):
     duration_prior: Optional[str] = None
     duration_prior_weight: float = DEFAULT_DURATION_PRIOR_WEIGHT
     duration_prior_scores: bool = False
+    decode_duration_prior: Optional[str] = None
+    decode_duration_prior_weight: float = DEFAULT_DURATION_PRIOR_WEIGHT
 
     def __new__(cls, *args, align_draft=None, draft_tolerance=DEFAULT_DRAFT_TOLERANCE, align_edits=False, align_insertions=False,
                 min_duration=None, duration_scores=False, optional_tokens=None, skip_penalty=0.0, optional_scores=False,
                 filler_token=None, filler_penalty=DEFAULT_FILLER_PENALTY, filler_scores=False, duration_prior=None,
-                duration_prior_weight=DEFAULT_DURATION_PRIOR_WEIGHT, duration_prior_scores=False, **kw):
+                duration_prior_weight=DEFAULT_DURATION_PRIOR_WEIGHT, duration_prior_scores=False, decode_duration_prior=None,
+                decode_duration_prior_weight=DEFAULT_DURATION_PRIOR_WEIGHT, **kw):
         self = super().__new__(cls, *args, **kw)
         object.__setattr__(self, "align_draft", align_draft)
         object.__setattr__(self, "draft_tolerance", draft_tolerance)
@@ -270,17 +291,19 @@ class PostOptions(_SearchOptions):
         object.__setattr__(self, "duration_prior", duration_prior)
         object.__setattr__(self, "duration_prior_weight", duration_prior_weight)
         object.__setattr__(self, "duration_prior_scores", duration_prior_scores)
+        object.__setattr__(self, "decode_duration_prior", decode_duration_prior)
+        object.__setattr__(self, "decode_duration_prior_weight", decode_duration_prior_weight)
         return self
 
     def __setattr__(self, name, value):
         raise AttributeError(f"PostOptions is read-only: cannot set {name!r}")
 
     _KEYWORD = ("align_draft", "draft_tolerance", "align_edits", "align_insertions", "min_duration", "duration_scores",
-                "optional_tokens", "skip_penalty", "duration_prior", "duration_prior_weight", "filler_scores", "duration_prior_scores",
-                "optional_scores", "filler_token", "filler_penalty")
+                "optional_tokens", "skip_penalty", "duration_prior", "duration_prior_weight", "decode_duration_prior",
+                "decode_duration_prior_weight", "filler_scores", "duration_prior_scores", "optional_scores", "filler_token", "filler_penalty")
     # (the later options stand in front of optional_scores: the record's last fields are the filler's own two)
     _KEYWORD_DEFAULTS = (None, DEFAULT_DRAFT_TOLERANCE, False, False, None, False, None, 0.0, None, DEFAULT_DURATION_PRIOR_WEIGHT,
-                         False, False, False, None, DEFAULT_FILLER_PENALTY)
+                         None, DEFAULT_DURATION_PRIOR_WEIGHT, False, False, False, None, DEFAULT_FILLER_PENALTY)
 
     def _draft(self):
         return self.align_draft, self.draft_tolerance
@@ -298,13 +321,15 @@ class PostOptions(_SearchOptions):
     def _make(cls, iterable, align_draft=None, draft_tolerance=DEFAULT_DRAFT_TOLERANCE, align_edits=False, align_insertions=False,
               min_duration=None, duration_scores=False, optional_tokens=None, skip_penalty=0.0, optional_scores=False,
               filler_token=None, filler_penalty=DEFAULT_FILLER_PENALTY, filler_scores=False, duration_prior=None,
-              duration_prior_weight=DEFAULT_DURATION_PRIOR_WEIGHT, duration_prior_scores=False):
+              duration_prior_weight=DEFAULT_DURATION_PRIOR_WEIGHT, duration_prior_scores=False, decode_duration_prior=None,
+              decode_duration_prior_weight=DEFAULT_DURATION_PRIOR_WEIGHT):
         return cls(*iterable, align_draft=align_draft, draft_tolerance=draft_tolerance, align_edits=align_edits,
                    align_insertions=align_insertions, min_duration=min_duration, duration_scores=duration_scores,
                    optional_tokens=optional_tokens, skip_penalty=skip_penalty, optional_scores=optional_scores,
                    filler_token=filler_token, filler_penalty=filler_penalty, filler_scores=filler_scores,
                    duration_prior=duration_prior, duration_prior_weight=duration_prior_weight,
-                   duration_prior_scores=duration_prior_scores)
+                   duration_prior_scores=duration_prior_scores, decode_duration_prior=decode_duration_prior,
+                   decode_duration_prior_weight=decode_duration_prior_weight)
 
     def _replace(self, **kw):
         later = {k: kw.pop(k, getattr(self, k)) for k in self._KEYWORD}
@@ -339,7 +364,7 @@ def _number_ge0(x):
 
 
 def resolve(post, *, align=None, align_scores=None, decode=None, switch_penalty=None, decode_scores=None, phoneme_bigram=None,
-            bigram_weight=None, bigram_scores=None, align_draft=None, draft_tolerance=None, align_edits=None,
+            bigram_weight=None, bigram_scores=None, decode_duration_prior=None, decode_duration_prior_weight=None, align_draft=None, draft_tolerance=None, align_edits=None,
             align_insertions=None, min_duration=None, duration_scores=None, optional_tokens=None, skip_penalty=None,
             optional_scores=None, filler_token=None, filler_penalty=None, filler_scores=None, duration_prior=None,
             duration_prior_weight=None, duration_prior_scores=None) -> PostOptions:
@@ -474,10 +499,25 @@ def resolve(post, *, align=None, align_scores=None, decode=None, switch_penalty=
         raise ValueError(f"duration_prior_scores must be true or false, got {duration_prior_scores!r}")
     if duration_prior_scores and not duration_prior:
         raise ValueError(DURATION_PRIOR_SCORES_ERROR)
+    decode_duration_prior = pick("decode_duration_prior", decode_duration_prior)
+    decode_duration_prior = str(decode_duration_prior) if decode_duration_prior else None
+    given = pick("decode_duration_prior_weight", decode_duration_prior_weight)
+    if (decode_duration_prior or given is not None) and decode != "viterbi":
+        raise ValueError("decode_duration_prior / decode_duration_prior_weight need decode='viterbi' (postprocess.decode: viterbi): the "
+                         "argmax decode has no search to weigh")
+    decode_duration_prior_weight = DEFAULT_DURATION_PRIOR_WEIGHT if given is None else _number_ge0(given)
+    if decode_duration_prior_weight is None or decode_duration_prior_weight == float("inf"):
+        raise ValueError(f"decode_duration_prior_weight must be a finite number >= 0, got {given!r}")
+    if given is not None and not decode_duration_prior:
+        raise ValueError("decode_duration_prior_weight needs a decode_duration_prior (postprocess.decode_duration_prior): it scales that "
+                         "prior")
+    if decode_duration_prior and (decode_scores or bigram_scores):
+        raise ValueError(DECODE_DURATION_PRIOR_ERROR)
     return PostOptions(align, align_scores, decode, switch_penalty, decode_scores, phoneme_bigram, bigram_weight, bigram_scores,
                        align_draft=align_draft, draft_tolerance=draft_tolerance, align_edits=align_edits,
                        align_insertions=align_insertions, min_duration=min_duration, duration_scores=duration_scores,
                        optional_tokens=optional_tokens, skip_penalty=skip_penalty, optional_scores=optional_scores,
                        filler_token=filler_token, filler_penalty=filler_penalty, filler_scores=filler_scores,
                        duration_prior=duration_prior, duration_prior_weight=duration_prior_weight,
-                       duration_prior_scores=duration_prior_scores)
+                       duration_prior_scores=duration_prior_scores, decode_duration_prior=decode_duration_prior,
+                       decode_duration_prior_weight=decode_duration_prior_weight)
