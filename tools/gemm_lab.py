@@ -1,6 +1,8 @@
 #!/usr/bin/env python3
 """Diagnostic (not product): A/B builds of the GEMM translation units with extra -D flags, timed on the config-2 shapes in
 ONE process (interleaved rounds).  Usage: gemm_lab.py name=-DFLAG1,-DFLAG2 name2= ...   (empty flag list = stock build)
+A "flag" of the form env:NAME=VALUE is not passed to the compiler: it is set in the environment around that variant's launches (switches
+that the library reads at every launch, e.g. blocked=env:WFL_CONV_ROTATE=0 next to stock=: one library file per name all the same).
 Every build carries -DWFL_GEMM_STAMPS so the K-loop time per block (stamps 1 -> 2) is reported next to the wall time."""
 import ctypes as C
 import os
@@ -46,11 +48,33 @@ SHAPES = [("out_proj+res", 512, 512, 0, True), ("qkv-like", 512, 1536, 0, False)
           ("fc2+res", 2048, 512, 0, True), ("k31 conv gelu", 15872, 512, 1, False), ("ff1_b", 1024, 512, 0, True)]
 
 
+ENVS = {}
+
+
+class _env:
+    """the variant's env: settings, for the duration of its launches"""
+
+    def __init__(self, lib):
+        self.kv = ENVS.get(lib._lab_name, {})
+
+    def __enter__(self):
+        self.old = {k: os.environ.get(k) for k in self.kv}
+        os.environ.update(self.kv)
+
+    def __exit__(self, *a):
+        for k, v in self.old.items():
+            if v is None:
+                os.environ.pop(k, None)
+            else:
+                os.environ[k] = v
+
+
 def main():
     variants = []
     for a in sys.argv[1:] or ["stock="]:
         name, _, fl = a.partition("=")
-        variants.append((name, [f for f in fl.split(",") if f]))
+        variants.append((name, [f for f in fl.split(",") if f and not f.startswith("env:")]))
+        ENVS[name] = dict(f[4:].split("=", 1) for f in fl.split(",") if f.startswith("env:"))
     if os.environ.get("LAB_BUILD_ONLY"):
         for name, fl in variants:
             print(build(name, fl))
@@ -64,6 +88,7 @@ def main():
         lib.diag_gemm.argtypes = [C.c_void_p, C.c_long, C.c_int, C.c_long, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                   C.c_void_p, C.c_long, C.c_long, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        lib._lab_name = name
         libs[name] = lib
     B, T, P, lead = (32 if os.environ.get("LAB_CFG5") else 16), 1500, 1520, 16
     w8 = bool(os.environ.get("LAB_W8"))                # e4m3 weights + per-channel scales (gemm_stream's W8 instantiations)
@@ -98,6 +123,10 @@ def main():
         ln_s = W.float().sum(1).contiguous()
 
         def run(lib, with_stamps):
+            with _env(lib):
+                return _run(lib, with_stamps)
+
+        def _run(lib, with_stamps):
             return lib.diag_gemm(C.c_void_p(A.data_ptr() + aoff), lda, 512 if tapped else 0, 512 if tapped else 0, C.c_void_p((W8b if w8 else W).data_ptr()), M, N, K, P, T,
                                  C.c_void_p(Cb.data_ptr()), N, lead, C.c_void_p(bias.data_ptr()),
                                  C.c_void_p(Rs.data_ptr()) if res else None, act,

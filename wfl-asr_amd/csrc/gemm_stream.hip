@@ -63,6 +63,14 @@ static __device__ __forceinline__ int sswz(int row) { return (-(row >> 2)) & 3; 
 // the eight 16-byte-chunk XORs that keep 16 consecutive rows from any start conflict-free for ds_read_b128 (exhaustive search
 // over the functions of (row >> 2) & 3; the aligned-only sswz above costs 2-way conflicts on 3 taps of 4: +0.10 us per K step).
 static __device__ __forceinline__ int xswz(int row) { return ((row >> 2) & 1) << 1; }
+// ROT image of the CONV extended frame tile: four planes, one per 16-byte chunk g of a row, each 223 rows x 16 bytes, back to back: chunk g
+// of row r lives at (223 g + r) * 16 (rows 0 .. 222 are all a tile reads: 96 + 31 taps + 95).  Linear in the row, so the fragments of a tap
+// sit at constant offsets from one address.  A ROT fragment read takes rows r0 + 6 c: in each of ds_read_b128's four lane groups
+// ({0-3, 12-15, 20-27}, ...) the eight lanes of one g have 6 c mod 16 = the eight even residues, and 223 = -1 mod 16 puts the other g's eight
+// on the odd ones: 16 different 16-byte slots of the 256-byte bank row for every r0 (tools/conv_rotate_lds_image.py enumerates it).
+// The LDS-DMA writes lane l's 16 bytes to slot 64 p + l of the image (p: the 1 KiB piece), so that lane FETCHES chunk (64 p + l) / 223 of
+// row (64 p + l) % 223; the last four slots of the 14 KiB are padding.
+#define XROT_ROWS 223
 template <int N>
 static __device__ __forceinline__ void wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
 
@@ -96,9 +104,17 @@ static __device__ __forceinline__ void wait_vm() { asm volatile("s_waitcnt vmcnt
 //   OUT8: the epilogue writes e4m3 (GemmArgs::c8) instead of bf16 -- fc1's GELU output, the next GEMM's fp8 operand.
 // NOLO: a CONV launch without a low-half buffer (GemmArgs::c_lo == null: every conv of the default precision) -- the low half is neither
 //   computed nor sent to the scratch line: 12 fewer 16-byte stores per wave and tile, and the second conversion with them.
-template <int ACT, int MT, bool RES, int LNF, bool STATS, bool CONV, bool W8 = false, bool A8 = false, bool OUT8 = false, bool NOLO = false>
+// ROT: the CONV mode with a wave's six frame fragments INTERLEAVED instead of blocked: fragment u, lane column c, tap t holds row
+//   wm + t + u + 6 c of the extended tile (blocked: wm + t + 16 u + c), so fragment u at tap t + 1 IS fragment u + 1 at tap t.  Going to the
+//   next tap moves fragments 1 .. 5 down one register (copies among the 24 MFMAs of the step) and reads ONE new fragment -- the old
+//   fragment 5 one row on: 6 + (taps - 1) frame fragment reads per channel chunk instead of 6 taps.  Same MFMAs, same operands per output
+//   element, same K order: the outputs are bit-identical to the blocked form's; lane column c of acc[u][] now belongs to frame
+//   m0 + wm + u + 6 c (the epilogue's row index).
+//   The extended tile's LDS image changes with it (XROT_ROWS above).  !ROT is the blocked form, kept selectable (WFL_CONV_ROTATE=0).
+template <int ACT, int MT, bool RES, int LNF, bool STATS, bool CONV, bool W8 = false, bool A8 = false, bool OUT8 = false, bool NOLO = false, bool ROT = false>
 __global__ __launch_bounds__(512) void gemm_stream_kernel(GemmArgs p) {
   static_assert(!NOLO || CONV, "only the conv mode has an optional low half");
+  static_assert(!ROT || CONV, "only the conv mode rotates frame fragments");
   static_assert(!CONV || (MT == 6 && !RES && LNF == 0 && !STATS), "conv mode: 192-row tiles, plain epilogue");
   static_assert(!W8 || (!CONV && MT == 6), "fp8 weights: plain 192-row mode");
   static_assert(!A8 || (!W8 && !CONV && MT == 6 && LNF == 0 && !STATS), "fp8 x fp8: the plain 192-row mode, no LayerNorm folding");
@@ -172,11 +188,13 @@ __global__ __launch_bounds__(512) void gemm_stream_kernel(GemmArgs p) {
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
       const int wrow = (wid * 2 + i) * 16 + (lane >> 2);
-      const int xrow = (xg0 + i) * 16 + (lane >> 2);
+      const int xslot = (xg0 + i) * 64 + lane;                                                    // ROT: slot of the image
+      const int xch = (xslot >= XROT_ROWS) + (xslot >= 2 * XROT_ROWS) + (xslot >= 3 * XROT_ROWS);   //   its chunk (padding: chunk 3, rows past 222)
+      const int xrow = ROT ? xslot - XROT_ROWS * xch : (xg0 + i) * 16 + (lane >> 2);
       int am = m0 + xrow;
       const int am_max = CONV ? p.M - 1 + ntaps - 1 : p.M - 1;     // (conv: row m + tap of the caller's buffer, as in gemm.hip)
       am = am < am_max ? am : am_max;
-      a_src[i] = p.A + (long)am * p.lda + ((lane & 3) ^ (CONV ? xswz(xrow) : sswz(xrow))) * 8;
+      a_src[i] = p.A + (long)am * p.lda + (ROT ? xch : (lane & 3) ^ (CONV ? xswz(xrow) : sswz(xrow))) * 8;
       w_src[i] = p.W + (long)(n0 + wrow) * p.K + ((lane & 3) ^ sswz(wrow)) * 8;
     }
     if (W8) {
@@ -319,7 +337,8 @@ __global__ __launch_bounds__(512) void gemm_stream_kernel(GemmArgs p) {
     // the K loop, and keeps them in registers across it -- registers this kernel does not have, so they spill, and a spill's reload inside
     // the epilogue is an `s_waitcnt vmcnt(0)`: a wait for the operand DMA in flight AND for every store issued so far, in the one place
     // built around never waiting for a store.  Computed here from values the compiler cannot see through, they cost one add each.
-    int mrow0 = m0 + wm + c;
+    constexpr int FCOL = ROT ? MT : 1, FROW = ROT ? 1 : 16;     // frame of acc[u][], lane column c: m0 + wm + FROW u + FCOL c
+    int mrow0 = m0 + wm + FCOL * c;
     int sidx_w = (((grp * 4 + wq) * (MT * 16)) + c) * 2, sidx_g = ((grp * 4 * (MT * 16)) + c) * 2, sidx_l = (grp * (MT * 16) + c) * 2;
     asm volatile("" : "+v"(mrow0), "+v"(sidx_w), "+v"(sidx_g), "+v"(sidx_l));
     f32x4 bj[4], sj[4], cj[(W8 || A8) ? 4 : 1];
@@ -341,7 +360,7 @@ __global__ __launch_bounds__(512) void gemm_stream_kernel(GemmArgs p) {
     if (A8) {
 #pragma unroll
       for (int u = 0; u < MT; ++u) {
-        int m = mrow0 + 16 * u;
+        int m = mrow0 + FROW * u;
         m = m < p.M ? m : p.M - 1;
         sa[u] = p.a8_scale ? p.a8_scale[p.a8_lead + m] : p.a8_static;
       }
@@ -354,7 +373,7 @@ __global__ __launch_bounds__(512) void gemm_stream_kernel(GemmArgs p) {
     int orow[MT];                                   // output row index, or -1 for rows that are not stored
 #pragma unroll
     for (int u = 0; u < MT; ++u) {
-      const int m = mrow0 + 16 * u;
+      const int m = mrow0 + FROW * u;
       int b = (int)((float)m * invP);
       int t = m - b * P_;
       if (t < 0) { t += P_; --b; }
@@ -365,7 +384,7 @@ __global__ __launch_bounds__(512) void gemm_stream_kernel(GemmArgs p) {
 #pragma unroll                                      // the expression above they cost the LayerNorm-folded launches 2 us each)
       for (int u = 0; u < MT; ++u)
         if (orow[u] >= 0) {
-          const int m = mrow0 + 16 * u;             // (clip and frame once more from the row index: an integer division by c_pitch
+          const int m = mrow0 + FROW * u;             // (clip and frame once more from the row index: an integer division by c_pitch
           int b = (int)((float)m * invP);           //  would keep its magic reciprocal in a register across the K loop)
           int t = m - b * P_;
           if (t < 0) { t += P_; --b; }
@@ -410,7 +429,7 @@ __global__ __launch_bounds__(512) void gemm_stream_kernel(GemmArgs p) {
       f32x4 sp[MT][2];
 #pragma unroll
       for (int u = 0; u < MT; ++u) {
-        int m = mrow0 + 16 * u;
+        int m = mrow0 + FROW * u;
         m = m < p.M ? m : p.M - 1;
         const f32x4* q = (const f32x4*)(p.stats_in + (p.stats_lead + m) * (2 * SROW));
         sp[u][0] = q[0];
@@ -559,7 +578,10 @@ __global__ __launch_bounds__(512) void gemm_stream_kernel(GemmArgs p) {
   int s = 0;                                         // global K-step counter
   int rslot = 0;                                     // its ring slot (= s % SNST)
   int ctap = 0, ccg = 0;                              // CONV: tap of the step being computed; chunks finished (buffer parity)
-  auto read_frags = [&]() __attribute__((always_inline)) {
+  // carry (ROT): fragments 0 .. 4 of this tap are in fx[] already, moved down by the previous step's mma_all, unless the tap is the first of
+  // a channel chunk.  Only the steady loop carries them, from its second step on: carried through the general steps they would be live across
+  // the tile change's address arithmetic and the epilogue, registers this kernel does not have (they spilled INTO the steady loop).
+  auto read_frags = [&](bool carry) __attribute__((always_inline)) {
     const char* sb = smem + rslot * STB;
     if (W8 && WFL_W8_CVT_IN_C) {
 #pragma unroll
@@ -576,7 +598,19 @@ __global__ __launch_bounds__(512) void gemm_stream_kernel(GemmArgs p) {
       }
     } else {
 #pragma unroll
-      for (int v = 0; v < 4; ++v) fw[v] = *(const bf16x8*)(sb + w_off[v]);
+      // (ROT: rows 32 apart share sswz, so column tiles 2 / 3 sit 2 KiB behind 0 / 1 -- an immediate offset, two address registers fewer)
+      for (int v = 0; v < 4; ++v) fw[v] = ROT ? *(const bf16x8*)(sb + w_off[v & 1] + (v >> 1) * 2048) : *(const bf16x8*)(sb + w_off[v]);
+    }
+    if (ROT) {
+      const char* ab = smem + AOFF + (ccg & 1) * AEXT;
+      const int xb = (XROT_ROWS * g + wm + MT * c + ctap) * 16;      // fragment u: row wm + ctap + 6 c + u, 16 u bytes on
+      if (!carry || ctap == 0) {                     // fragments 0 .. 4 too (wave-uniform)
+#pragma unroll
+        for (int u = 0; u < MT - 1; ++u) fx[u] = *(const bf16x8*)(ab + xb + u * 16);
+      }                                              // the one new fragment:
+      fx[MT - 1] = *(const bf16x8*)(ab + xb + (MT - 1) * 16);
+      if (++ctap == ntaps) { ctap = 0; ++ccg; }
+      return;
     }
     if (CONV) {
       const char* ab = smem + AOFF + (ccg & 1) * AEXT;
@@ -611,6 +645,14 @@ __global__ __launch_bounds__(512) void gemm_stream_kernel(GemmArgs p) {
           acc[u][v] = __builtin_amdgcn_mfma_f32_16x16x32_fp8_fp8(a[0], b[0], acc[u][v], 0, 0, 0);
           acc[u][v] = __builtin_amdgcn_mfma_f32_16x16x32_fp8_fp8(a[1], b[1], acc[u][v], 0, 0, 0);
         } else acc[u][v] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fw[v], fx[u], acc[u][v], 0, 0, 0);
+      }
+      if (ROT && u + 1 < MT) {
+        // fragment u + 1 of this tap is fragment u of the next: copied down behind fragment u's last MFMA, in the MFMAs' shadow.  (The empty
+        // asm pins the copy here: left alone it becomes the loop's phi copies, or sinks into read_frags' carry branch -- the L slot either way.)
+        typedef __attribute__((ext_vector_type(4))) int i32x4;
+        i32x4 t = __builtin_bit_cast(i32x4, fx[u + 1]);
+        asm volatile("" : "+v"(t));
+        fx[u] = __builtin_bit_cast(bf16x8, t);
       }
       if (NDC >= 1 && u == 1) { __builtin_amdgcn_sched_barrier(0); issue_deferred(0, ndc_c); __builtin_amdgcn_sched_barrier(0); }
       if (NDC >= 2 && u == 3) { __builtin_amdgcn_sched_barrier(0); issue_deferred(1, ndc_c); __builtin_amdgcn_sched_barrier(0); }
@@ -658,7 +700,7 @@ __global__ __launch_bounds__(512) void gemm_stream_kernel(GemmArgs p) {
     // or ends).
     auto step_general = [&](int kt, auto first_c) __attribute__((always_inline)) {
       if (decltype(first_c)::value && have_prev) epilogue(pm0, pn0);
-      read_frags();
+      read_frags(false);
       prefetch_one();
       if (grp) wait_stage(s + 1, have_prev && kt < SNST - 2);
       __builtin_amdgcn_s_waitcnt(0xC07F);            // lgkmcnt(0)
@@ -687,7 +729,7 @@ __global__ __launch_bounds__(512) void gemm_stream_kernel(GemmArgs p) {
       const std::integral_constant<int, NDC> ndc_c{};
       for (int kt = SNST - 2; kt <= nk - SNST - 1; ++kt) {
 #ifndef WFL_ABL_NOLDS          // diagnostic builds (tools/gemm_lab.py): no fragment reads / no operand DMA in the steady loop
-        read_frags();
+        read_frags(ROT && kt > SNST - 2);
 #endif
 #ifndef WFL_ABL_NOSTAGE
         if (CONV) issue_stage(); else issue_stage_split(ndc_c);
@@ -724,7 +766,7 @@ __global__ __launch_bounds__(512) void gemm_stream_kernel(GemmArgs p) {
 #undef SSB
 }
 
-template <int ACT, int MT, bool RES, int LNF, bool STATS, bool CONV = false, bool W8 = false, bool A8 = false, bool OUT8 = false, bool NOLO = false>
+template <int ACT, int MT, bool RES, int LNF, bool STATS, bool CONV = false, bool W8 = false, bool A8 = false, bool OUT8 = false, bool NOLO = false, bool ROT = false>
 static int launch_stream(const GemmArgs& a, hipStream_t s) {
   constexpr int BMV = MT * 32;
 #ifdef WFL_LAB_STB32
@@ -733,7 +775,7 @@ static int launch_stream(const GemmArgs& a, hipStream_t s) {
   constexpr int lds = (CONV ? SNST * 256 * SBK * 2 + 2 * 224 * SBK * 2 : SNST * (BMV * SBK * 2 + 256 * SBK * (W8 ? 1 : 2))) + 8 * (MT * 16) * 2 * 4 + 64;
 #endif
   const int tiles = ((a.M + BMV - 1) / BMV) * (a.N / 256);
-  auto k = gemm_stream_kernel<ACT, MT, RES, LNF, STATS, CONV, W8, A8, OUT8, NOLO>;
+  auto k = gemm_stream_kernel<ACT, MT, RES, LNF, STATS, CONV, W8, A8, OUT8, NOLO, ROT>;
   static WflOncePerDevice attr_once;
   if (attr_once.need()) {
     if (hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess) return -2;
@@ -773,6 +815,24 @@ static bool wfl_gemm_stream_conv(const GemmArgs& a) {
 }
 
 bool wfl_gemm_stream_conv_takes(const GemmArgs& a);
+
+template <bool ROT>
+static int launch_conv(const GemmArgs& g, hipStream_t s) {
+  if (!g.c_lo) {                                       // no low half asked for: the instantiation that does not compute one
+    switch (g.act) {
+      case WFL_ACT_NONE: return launch_stream<WFL_ACT_NONE, 6, false, 0, false, true, false, false, false, true, ROT>(g, s);
+      case WFL_ACT_GELU: return launch_stream<WFL_ACT_GELU, 6, false, 0, false, true, false, false, false, true, ROT>(g, s);
+      case WFL_ACT_RELU: return launch_stream<WFL_ACT_RELU, 6, false, 0, false, true, false, false, false, true, ROT>(g, s);
+    }
+    return 1;
+  }
+  switch (g.act) {
+    case WFL_ACT_NONE: return launch_stream<WFL_ACT_NONE, 6, false, 0, false, true, false, false, false, false, ROT>(g, s);
+    case WFL_ACT_GELU: return launch_stream<WFL_ACT_GELU, 6, false, 0, false, true, false, false, false, false, ROT>(g, s);
+    case WFL_ACT_RELU: return launch_stream<WFL_ACT_RELU, 6, false, 0, false, true, false, false, false, false, ROT>(g, s);
+  }
+  return 1;
+}
 // The launches this kernel takes (everything else stays with gemm256 / gemm).
 bool wfl_gemm_stream_takes(const GemmArgs& a) {
   static int off = -1;
@@ -858,20 +918,10 @@ int wfl_launch_gemm_stream(const GemmArgs& a, hipStream_t s) {
     return 1;
   }
   if (wfl_gemm_stream_conv(g)) {
-    if (!g.c_lo) {                                     // no low half asked for: the instantiation that does not compute one
-      switch (g.act) {
-        case WFL_ACT_NONE: return launch_stream<WFL_ACT_NONE, 6, false, 0, false, true, false, false, false, true>(g, s);
-        case WFL_ACT_GELU: return launch_stream<WFL_ACT_GELU, 6, false, 0, false, true, false, false, false, true>(g, s);
-        case WFL_ACT_RELU: return launch_stream<WFL_ACT_RELU, 6, false, 0, false, true, false, false, false, true>(g, s);
-      }
-      return 1;
-    }
-    switch (g.act) {
-      case WFL_ACT_NONE: return launch_stream<WFL_ACT_NONE, 6, false, 0, false, true>(g, s);
-      case WFL_ACT_GELU: return launch_stream<WFL_ACT_GELU, 6, false, 0, false, true>(g, s);
-      case WFL_ACT_RELU: return launch_stream<WFL_ACT_RELU, 6, false, 0, false, true>(g, s);
-    }
-    return 1;
+    // WFL_CONV_ROTATE=0: the blocked-fragment form (A/B; read at every launch, so one process can run both -- the two are bit-identical)
+    const char* e = getenv("WFL_CONV_ROTATE");
+    const bool rot = !(e && e[0] == '0' && !e[1]);
+    return rot ? launch_conv<true>(g, s) : launch_conv<false>(g, s);
   }
   if (g.res) return g.stats_out ? launch_stream_mt<WFL_ACT_NONE, true, 0, true>(g, s) : launch_stream_mt<WFL_ACT_NONE, true, 0>(g, s);
   switch (g.act) {
