@@ -234,6 +234,7 @@ def test_the_abi_entry_checks_its_arguments_and_sizes_its_workspace(AL):
 
 
 def test_the_rows_and_the_formatters(AL):
+    from wfl_asr_amd import reports as RP
     toks = [AL.TokenScore("a", 0.0, 0.06, 0.9, 0.01, 0.0), AL.TokenScore("SP", 0.06, 0.08, 0.5, 0.0, 0.0),
             AL.TokenScore("b", 0.08, 0.2, 0.7, 0.02, -0.01)]
     table = np.array([[-1.0, -2.0, -0.5], [NEG, -3.0, NEG]])
@@ -249,15 +250,15 @@ def test_the_rows_and_the_formatters(AL):
         AL.token_durations(toks, [3, 1], [0, -1, 1], table, [0.9, 0.5, 0.7], [0] * 3, [0] * 3, [0] * 3, [0] * 3, 0.02)
     head = ["index", "token", "start_s", "end_s", "frames", "log_prior", "posterior", "start_shift_s", "start_sd_s", "end_shift_s",
             "end_sd_s", "expected_frames"]
-    assert AL.DURATIONS_HEADER.split("\t") == head and AL.TokenDuration._fields == tuple(head)
-    lines = AL.format_durations_tsv(rows).split("\n")
+    assert RP.REPORTS["durations"].header.split("\t") == head and AL.TokenDuration._fields == tuple(head)
+    lines = RP.file_text("durations", rows).split("\n")
     assert lines[0].split("\t") == head and len(lines) == 5 and lines[-1] == ""
     assert lines[1].split("\t") == ["0", "a", "0.0000000", "0.0600000", "3", "-2.500000", "0.900000", "0.0100000", "0.0200000",
                                     "0.0050000", "0.0100000", "2.7500"]
     assert lines[2].split("\t")[5] == "none" and lines[3].split("\t")[5] == "-inf"
-    assert AL.format_durations_tsv([]) == "\t".join(head) + "\n"
+    assert RP.file_text("durations", []) == "\t".join(head) + "\n"
     other = AL.token_durations(toks[:1], [1], [0], table, [0.4], [0], [0], [0], [0], 0.02)
-    folder = AL.format_folder_durations_tsv([("x.wav", rows), ("y.wav", other)]).split("\n")
+    folder = RP.folder_text("durations", [("x.wav", rows), ("y.wav", other)]).split("\n")
     assert folder[0] == "file\t" + "\t".join(head) and len(folder) == 5            # the token without a row is left out
     assert [ln.split("\t")[0] for ln in folder[1:4]] == ["x.wav", "x.wav", "y.wav"]
     assert [float(ln.split("\t")[6]) for ln in folder[1:4]] == [NEG, -2.5, -1.0]   # the lowest log_prior first
@@ -314,6 +315,7 @@ def test_option_rules_40_and_41_and_their_order():
 
 
 def test_the_option_is_refused_before_any_model_is_loaded(monkeypatch, tmp_path):
+    from wfl_asr_amd import reports as RP
     import __graft_entry__  # noqa: F401
     from wfl_asr_amd import infer as I
 
@@ -333,5 +335,5 @@ def test_the_option_is_refused_before_any_model_is_loaded(monkeypatch, tmp_path)
     cfg.write_text("postprocess:\n  align: viterbi\n  duration_prior_scores: true\n")
     with pytest.raises(ValueError, match="duration_prior_scores needs a duration_prior"):              # from the config file
         I.infer_audio("x.wav", config_path=str(cfg))
-    assert I.durations_path("out/x.lab") == os.path.join("out", "x.durations.tsv")
+    assert RP.file_path("durations", "out/x.lab") == os.path.join("out", "x.durations.tsv")
     assert "wfl_align_posterior" in I.DURATION_PRIOR_SCORES_PLAIN

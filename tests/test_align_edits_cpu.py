@@ -255,22 +255,23 @@ def test_best_and_second_substitute_through_a_merge_map():
 
 def test_the_tsv_writers_and_the_folder_files_order(tmp_path):
     from wfl_asr_amd import align as AL
+    from wfl_asr_amd import reports as RP
     mk = lambda i, best, dele: AL.TokenEdit(i, "t", 0.1 * i, 0.1 * i + 0.1, "x", best, "y", best - 1, dele, int(max(best, dele) > 0))  # noqa: E731
     a = [mk(0, -1.0, -2.0), mk(1, 3.0, -1.0), mk(2, -1.0, 0.5)]
     b = [mk(0, 0.25, 7.0), mk(1, -np.inf, -np.inf)]
-    AL.write_edits_tsv(tmp_path / "a.edits.tsv", a)
+    (tmp_path / "a.edits.tsv").write_text(RP.file_text("edits", a))
     lines = (tmp_path / "a.edits.tsv").read_text().split("\n")
-    assert lines[0] == AL.EDITS_HEADER and lines[0].split("\t") == ["index", "token", "start_s", "end_s", "best", "best_log_ratio",
+    assert lines[0] == RP.REPORTS["edits"].header and lines[0].split("\t") == ["index", "token", "start_s", "end_s", "best", "best_log_ratio",
                                                                      "second", "second_log_ratio", "deletion_log_ratio", "flag"]
     assert len(lines) == 5 and lines[4] == ""
     assert lines[2].split("\t") == ["1", "t", "0.1000000", "0.2000000", "x", "3", "y", "2", "-1", "1"]
-    assert [r.index for _, r in AL.folder_edit_rows([("a.wav", a), ("b.wav", b)])] == [0, 1, 2]
-    assert [n for n, _ in AL.folder_edit_rows([("a.wav", a), ("b.wav", b)])] == ["b.wav", "a.wav", "a.wav"]
-    AL.write_folder_edits(tmp_path / "transcript_edits.tsv", [("a.wav", a), ("b.wav", b)])
+    assert [r.index for _, r in RP.folder_rows("edits", [("a.wav", a), ("b.wav", b)])] == [0, 1, 2]
+    assert [n for n, _ in RP.folder_rows("edits", [("a.wav", a), ("b.wav", b)])] == ["b.wav", "a.wav", "a.wav"]
+    (tmp_path / "transcript_edits.tsv").write_text(RP.folder_text("edits", [("a.wav", a), ("b.wav", b)]))
     lines = (tmp_path / "transcript_edits.tsv").read_text().split("\n")
-    assert lines[0] == "file\t" + AL.EDITS_HEADER and [ln.split("\t")[0] for ln in lines[1:4]] == ["b.wav", "a.wav", "a.wav"]
+    assert lines[0] == "file\t" + RP.REPORTS["edits"].header and [ln.split("\t")[0] for ln in lines[1:4]] == ["b.wav", "a.wav", "a.wav"]
     assert lines[1].split("\t")[-2:] == ["7", "1"] and len(lines) == 5
-    AL.write_edits_tsv(tmp_path / "e.edits.tsv", [b[1]])
+    (tmp_path / "e.edits.tsv").write_text(RP.file_text("edits", [b[1]]))
     assert (tmp_path / "e.edits.tsv").read_text().split("\n")[1].split("\t")[5:] == ["-inf", "y", "-inf", "-inf", "0"]
 
 

@@ -110,12 +110,13 @@ def test_filler_flags_collapse_and_segments(AL):
 
 
 def test_the_tsv_texts(AL):
+    from wfl_asr_amd import reports as RP
     rows = [AL.FillerSpan(1, 0.3, 0.7, 20, ("a", "AP", "b")), AL.FillerSpan(4, 1.25, 1.5, 12, ())]
     assert AL.FillerSpan._fields == ("index", "start_s", "end_s", "frames", "names")
-    assert AL.format_fillers_tsv(rows) == ("index\tstart_s\tend_s\tframes\tnames\n1\t0.3000000\t0.7000000\t20\ta AP b\n"
+    assert RP.file_text("fillers", rows) == ("index\tstart_s\tend_s\tframes\tnames\n1\t0.3000000\t0.7000000\t20\ta AP b\n"
                                            "4\t1.2500000\t1.5000000\t12\t\n")
-    assert AL.format_fillers_tsv([]) == "index\tstart_s\tend_s\tframes\tnames\n"
-    folder = AL.format_folder_fillers_tsv([("x.wav", rows), ("y.wav", []), ("z.wav", rows[1:])])
+    assert RP.file_text("fillers", []) == "index\tstart_s\tend_s\tframes\tnames\n"
+    folder = RP.folder_text("fillers", [("x.wav", rows), ("y.wav", []), ("z.wav", rows[1:])])
     assert folder.splitlines() == ["file\tindex\tstart_s\tend_s\tframes\tnames", "x.wav\t1\t0.3000000\t0.7000000\t20\ta AP b",
                                    "x.wav\t4\t1.2500000\t1.5000000\t12\t", "z.wav\t4\t1.2500000\t1.5000000\t12\t"]
 
@@ -315,7 +316,7 @@ def test_the_options_are_refused_before_any_model_is_loaded(monkeypatch, tmp_pat
     for f in (I.infer_audio, I.infer_folder, I.Labeler.label_files):
         p = inspect.signature(f).parameters
         assert p["filler_token"].default is None and p["filler_penalty"].default is None
-    assert I.ViterbiLabel._fields[-1] == "fillers" and I.ViterbiLabel([]).fillers is None
+    assert I.ViterbiLabel._fields[-1] == "rows" and I.ViterbiLabel([]).rows.get("fillers") is None
     monkeypatch.setattr(I, "_labeler", no_load)
     monkeypatch.setattr(I, "Labeler", no_load)
     with pytest.raises(ValueError, match="filler_token needs align='viterbi'"):

@@ -172,19 +172,20 @@ def test_the_option_is_refused_before_any_model_is_loaded(monkeypatch, tmp_path)
 
 # ------------------------------------------------------------------------------------------------ 3. the .tsv text
 def test_filler_score_rows_and_their_text(AL):
+    from wfl_asr_amd import reports as RP
     spans = [AL.FillerSpan(2, 0.5, 0.9, 20, ("a", "b")), AL.FillerSpan(5, 1.5, 1.7, 10, ())]
     tp = [1, 1, 0.75, 1, 1, 0.25, 1]
     rows = AL.filler_scores(spans, tp, [0, 0, -1.5, 0, 0, 2, 0], [0, 0, 0.5, 0, 0, 1, 0], [0, 0, 3, 0, 0, -1, 0], [0, 0, 2, 0, 0, 0.25, 0], 0.02)
     assert rows == [AL.FillerScore(2, 0.5, 0.9, 20, 0.75, -0.03, 0.01, 0.06, 0.04), AL.FillerScore(5, 1.5, 1.7, 10, 0.25, 0.04, 0.02, -0.02, 0.005)]
-    text = AL.format_filler_scores_tsv(rows)
+    text = RP.file_text("filler_scores", rows)
     assert text.splitlines() == [
         "index\tstart_s\tend_s\tframes\tposterior\tstart_shift_s\tstart_sd_s\tend_shift_s\tend_sd_s",
         "2\t0.5000000\t0.9000000\t20\t0.750000\t-0.0300000\t0.0100000\t0.0600000\t0.0400000",
         "5\t1.5000000\t1.7000000\t10\t0.250000\t0.0400000\t0.0200000\t-0.0200000\t0.0050000"] and text.endswith("\n")
-    assert AL.format_filler_scores_tsv([]) == AL.FILLER_SCORES_HEADER + "\n"
-    folder = AL.format_folder_filler_scores_tsv([("a.wav", rows), ("b.wav", []), ("c.wav", [rows[0]._replace(posterior=0.25)])])
+    assert RP.file_text("filler_scores", []) == RP.REPORTS["filler_scores"].header + "\n"
+    folder = RP.folder_text("filler_scores", [("a.wav", rows), ("b.wav", []), ("c.wav", [rows[0]._replace(posterior=0.25)])])
     lines = folder.splitlines()
-    assert lines[0] == "file\t" + AL.FILLER_SCORES_HEADER and len(lines) == 4
+    assert lines[0] == "file\t" + RP.REPORTS["filler_scores"].header and len(lines) == 4
     assert [ln.split("\t")[0] for ln in lines[1:]] == ["a.wav", "c.wav", "a.wav"]        # the lowest occupancy first, ties in the files' order
     assert [ln.split("\t")[5] for ln in lines[1:]] == ["0.250000", "0.250000", "0.750000"]
     assert "flag" not in folder and "doubt" not in folder

@@ -201,24 +201,25 @@ def test_place_insertions_through_a_merge_map():
 
 def test_the_tsv_writers_and_the_folder_files_order(tmp_path):
     from wfl_asr_amd import align as AL
+    from wfl_asr_amd import reports as RP
     mk = lambda i, best: AL.PlaceInsertion(i, "p", "q", 0.1 * i, "x", best, "y", best - 1, int(best > 0))      # noqa: E731
     a = [mk(0, -1.0), mk(1, 3.0), mk(2, 0.5)]
     b = [mk(0, 3.0), mk(1, -np.inf), mk(2, 7.0)]
-    AL.write_insertions_tsv(tmp_path / "a.insertions.tsv", a)
+    (tmp_path / "a.insertions.tsv").write_text(RP.file_text("insertions", a))
     lines = (tmp_path / "a.insertions.tsv").read_text().split("\n")
-    assert lines[0] == AL.INSERTIONS_HEADER and lines[0].split("\t") == ["index", "after", "before", "at_s", "best", "best_log_ratio",
+    assert lines[0] == RP.REPORTS["insertions"].header and lines[0].split("\t") == ["index", "after", "before", "at_s", "best", "best_log_ratio",
                                                                          "second", "second_log_ratio", "flag"]
     assert len(lines) == 5 and lines[4] == ""
     assert lines[2].split("\t") == ["1", "p", "q", "0.1000000", "x", "3", "y", "2", "1"]
-    rows = AL.folder_insertion_rows([("a.wav", a), ("b.wav", b)])
+    rows = RP.folder_rows("insertions", [("a.wav", a), ("b.wav", b)])
     # the flagged places, largest ratio first; the tie at 3.0 in file order
     assert [(n, r.index) for n, r in rows] == [("b.wav", 2), ("a.wav", 1), ("b.wav", 0), ("a.wav", 2)]
-    assert [(n, r.index) for n, r in AL.folder_insertion_rows([("a.wav", [mk(0, 2.0), mk(1, 2.0)])])] == [("a.wav", 0), ("a.wav", 1)]
-    AL.write_folder_insertions(tmp_path / "transcript_insertions.tsv", [("a.wav", a), ("b.wav", b)])
+    assert [(n, r.index) for n, r in RP.folder_rows("insertions", [("a.wav", [mk(0, 2.0), mk(1, 2.0)])])] == [("a.wav", 0), ("a.wav", 1)]
+    (tmp_path / "transcript_insertions.tsv").write_text(RP.folder_text("insertions", [("a.wav", a), ("b.wav", b)]))
     lines = (tmp_path / "transcript_insertions.tsv").read_text().split("\n")
-    assert lines[0] == "file\t" + AL.INSERTIONS_HEADER and [ln.split("\t")[0] for ln in lines[1:5]] == ["b.wav", "a.wav", "b.wav", "a.wav"]
+    assert lines[0] == "file\t" + RP.REPORTS["insertions"].header and [ln.split("\t")[0] for ln in lines[1:5]] == ["b.wav", "a.wav", "b.wav", "a.wav"]
     assert lines[1].split("\t")[-4:] == ["7", "y", "6", "1"] and len(lines) == 6
-    AL.write_insertions_tsv(tmp_path / "e.insertions.tsv", [b[1]])
+    (tmp_path / "e.insertions.tsv").write_text(RP.file_text("insertions", [b[1]]))
     assert (tmp_path / "e.insertions.tsv").read_text().split("\n")[1].split("\t")[4:] == ["x", "-inf", "y", "-inf", "0"]
     assert f"{float('-inf'):.6g}" == str(float("-inf"))    # (-inf as written by Python)
 

@@ -151,6 +151,7 @@ def test_pack_optional_and_the_batch_record(AL):
 
 
 def test_segments_of_a_path_that_lacks_tokens(AL, table):  # noqa: F811
+    from wfl_asr_amd import reports as RP
     tr = ["a", "b", "a", "b"]
     remap, names = _names(table)
     alts, why = AL.token_alternatives(tr, table, remap, names, LABELS)
@@ -180,10 +181,10 @@ def test_segments_of_a_path_that_lacks_tokens(AL, table):  # noqa: F811
     assert AL.skipped_tokens([0, 0, 0, 0], [(0, 1, x) for x in tr], tr) == [] and AL.skipped_tokens([1], [], ["a"])[0].at_s == 0.0
     with pytest.raises(ValueError, match="one segment per kept token"):
         AL.skipped_tokens([0, 1, 0, 1], segs[:1], tr)
-    text = AL.format_skipped_tsv(first)
+    text = RP.file_text("skipped", first)
     assert text == "index\ttoken\tafter\tbefore\tat_s\n0\ta\t\tb\t0.1000000\n2\ta\tb\tb\t0.3000000\n"
-    assert AL.format_skipped_tsv([]) == "index\ttoken\tafter\tbefore\tat_s\n"
-    folder = AL.format_folder_skipped_tsv([("x.wav", first), ("y.wav", []), ("z.wav", first[:1])])
+    assert RP.file_text("skipped", []) == "index\ttoken\tafter\tbefore\tat_s\n"
+    folder = RP.folder_text("skipped", [("x.wav", first), ("y.wav", []), ("z.wav", first[:1])])
     assert folder.splitlines() == ["file\tindex\ttoken\tafter\tbefore\tat_s", "x.wav\t0\ta\t\tb\t0.1000000", "x.wav\t2\ta\tb\tb\t0.3000000",
                                    "z.wav\t0\ta\t\tb\t0.1000000"]
 

@@ -11,6 +11,7 @@ import posterior_ref as P
 import viterbi_ref as V
 from wfl_asr_amd import align as AL
 from wfl_asr_amd import options as OPT
+from wfl_asr_amd import reports as RP
 
 C = 12
 GAPS = [0, 11]
@@ -136,18 +137,18 @@ def test_optional_token_scores_rows_and_the_doubt_rule():
 
 def test_the_tsv_writers_and_the_folder_order():
     rows = _rows()
-    text = AL.format_optional_tsv(rows)
+    text = RP.file_text("optional", rows)
     lines = text.split("\n")
     assert lines[0] == "index\ttoken\tdecision\tkeep_posterior\tstart_s\tend_s\tdoubt"
     assert lines[1] == "1\tcl\tskipped\t0.700000\t0.2000000\t0.2000000\t1"
     assert lines[2] == "3\tq\tkept\t0.900000\t0.3000000\t0.3500000\t0"
     assert len(lines) == 5 and lines[-1] == ""
-    assert AL.format_optional_tsv([]) == lines[0] + "\n"
+    assert RP.file_text("optional", []) == lines[0] + "\n"
     other = [AL.OptionalTokenScore(0, "cl", True, 0.55, 0.0, 0.1)]
-    folder = AL.format_folder_optional_tsv([("a.wav", rows), ("b.wav", other)]).split("\n")
+    folder = RP.folder_text("optional", [("a.wav", rows), ("b.wav", other)]).split("\n")
     assert folder[0] == "file\t" + lines[0]
     assert [ln.split("\t")[0:2] for ln in folder[1:-1]] == [["a.wav", "1"], ["b.wav", "0"], ["a.wav", "5"], ["a.wav", "3"]]
-    conf = [r.confidence for _, r in AL.folder_optional_rows([("a.wav", rows), ("b.wav", other)])]
+    conf = [r.confidence for _, r in RP.folder_rows("optional", [("a.wav", rows), ("b.wav", other)])]
     assert conf == sorted(conf)
 
 

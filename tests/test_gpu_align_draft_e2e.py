@@ -22,6 +22,7 @@ from wfl_asr_amd import audio as A
 from wfl_asr_amd import infer as I
 from wfl_asr_amd import native_post as npost
 from wfl_asr_amd import postprocess as pp
+from wfl_asr_amd import reports as RP
 
 pytestmark = pytest.mark.gpu
 FD = pp.FRAME_DURATION
@@ -180,9 +181,10 @@ def test_a_long_files_tokens_find_their_chunk_either_side_of_the_seams(whisper, 
     _write_draft(d, "long", base)
     try:
         capsys.readouterr()
-        moves = {}
         opts = lab.options(align="viterbi", align_draft=str(d / "drafts"), draft_tolerance=0.1)
-        got, _ = lab._label_scored([plain_p, long_p], opts, None, CT, False, moves)
+        reports = RP.Reports.for_options(opts)
+        got, _ = lab._label_scored([plain_p, long_p], opts, None, CT, False, reports)
+        moves = reports.moves
         assert I.DRAFT_INFEASIBLE not in capsys.readouterr().out
     finally:
         os.remove(str(d / "drafts" / "long.lab"))

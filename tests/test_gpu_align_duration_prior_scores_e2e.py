@@ -13,6 +13,7 @@ from test_gpu_align_duration_prior_e2e import CT, FD, NAMES, NEG, _prior, _trans
 from test_gpu_align_e2e import _write_tr
 from wfl_asr_amd import align as AL
 from wfl_asr_amd import infer as I
+from wfl_asr_amd import reports as RP
 
 pytestmark = pytest.mark.gpu
 
@@ -63,7 +64,7 @@ def test_the_reports_and_both_fallbacks(whisper, tmp_path, capsys):  # noqa: F81
         assert float(lines[0].split("\t")[0].split("=")[1]) <= 1e-3 * 350            # score <= logz, within the search's own bound
     # {stem}.durations.tsv
     lines = open(tmp_path / "with" / "a.durations.tsv").read().split("\n")
-    assert lines[0] == AL.DURATIONS_HEADER and len(lines) == len(tr_a) + 2 and lines[-1] == ""
+    assert lines[0] == RP.REPORTS["durations"].header and len(lines) == len(tr_a) + 2 and lines[-1] == ""
     rows = [ln.split("\t") for ln in lines[1:-1]]
     assert [r[1] for r in rows] == tr_a and [int(r[0]) for r in rows] == list(range(len(tr_a)))
     frames = np.array([int(r[4]) for r in rows])
@@ -82,7 +83,7 @@ def test_the_reports_and_both_fallbacks(whisper, tmp_path, capsys):  # noqa: F81
     review = open(tmp_path / "with" / "alignment_scores.tsv").read().split("\n")
     assert review[0].startswith("# file\tmin_posterior") and sorted(ln.split("\t")[0] for ln in review[1:-1]) == ["a.wav", "b.wav"]
     lines = open(tmp_path / "with" / "token_durations.tsv").read().split("\n")
-    assert lines[0] == "file\t" + AL.DURATIONS_HEADER
+    assert lines[0] == "file\t" + RP.REPORTS["durations"].header
     listed = [ln.split("\t") for ln in lines[1:-1]]
     assert len(listed) == sum(t in ("p00", "p01", "p02") for t in tr_a) and {r[0] for r in listed} == {"a.wav"}
     priors = [float(r[6]) for r in listed]
@@ -117,7 +118,7 @@ def test_label_files_returns_the_rows_and_one_file_gets_its_files(whisper, tmp_p
     I.infer_audio(paths[0], config_path=str(d / "config.yaml"), checkpoint_path=str(d / "best_model.pt"),
                   output_lab_path=str(tmp_path / "one" / "a.lab"), confidence_threshold=CT, align="viterbi", duration_prior=pr_path, duration_prior_scores=True)
     assert sorted(os.listdir(tmp_path / "one")) == ["a.durations.tsv", "a.lab", "a.scores.tsv"]
-    assert open(tmp_path / "one" / "a.durations.tsv").read() == AL.format_durations_tsv(durations[0])
+    assert open(tmp_path / "one" / "a.durations.tsv").read() == RP.file_text("durations", durations[0])
     # the CLI flag reaches infer_folder; without a prior it is refused before a model is loaded
     seen = {}
     real = I.infer_folder

@@ -17,6 +17,7 @@ from wfl_asr_amd import audio as A
 from wfl_asr_amd import infer as I
 from wfl_asr_amd import native_post as npost
 from wfl_asr_amd import postprocess as pp
+from wfl_asr_amd import reports as RP
 
 pytestmark = pytest.mark.gpu
 CT = 0.3
@@ -61,7 +62,7 @@ def _direct(lab, path, tr, segments, windows_of=None):
     logz, edits, st = AL.edit_scores(lg, [tv], [alts], [gaps], LABELS.index("O"), pairs, packed=packed)
     assert int(st[0]) == 0 and edits.shape == (len(tr), len(pairs) + 1)
     rows = AL.token_edits(edits.cpu().numpy(), segments, out_names)
-    return [AL._edit_cells(r) for r in rows], out_names
+    return [RP.REPORTS["edits"].cells(r) for r in rows], out_names
 
 
 def test_edits_leave_the_segments_alone_and_equal_a_direct_call(whisper, capsys):
@@ -83,7 +84,7 @@ def test_edits_leave_the_segments_alone_and_equal_a_direct_call(whisper, capsys)
     assert [(r.start_s, r.end_s, r.token) for r in rows] == core and [r.token for r in rows] == tr
     assert [r.index for r in rows] == list(range(len(tr)))
     want, out_names = _direct(lab, path, tr, core)
-    assert [AL._edit_cells(r) for r in rows] == want
+    assert [RP.REPORTS["edits"].cells(r) for r in rows] == want
     for r in rows:                                        # a token's own name is never its substitute; best and second differ
         assert r.best != r.token and r.second != r.token and r.best != r.second and r.best in out_names and r.second in out_names
         assert r.best_ratio >= r.second_ratio and r.flag == int(max(r.best_ratio, r.deletion_ratio) > 0)
@@ -110,7 +111,7 @@ def test_with_a_draft_the_windowed_lattice_is_the_one_scored(whisper):
     assert npost.format_lab_tuples(segs[0]) == npost.format_lab_tuples(base)
     windowed, _ = _direct(lab, path, tr, segs[0], lambda tv: AL.draft_windows(draft, [tv], [0.0], 0.06, pp.FRAME_DURATION))
     open_, _ = _direct(lab, path, tr, segs[0])
-    got = [AL._edit_cells(r) for r in edits[0]]
+    got = [RP.REPORTS["edits"].cells(r) for r in edits[0]]
     assert got == windowed
     assert got != open_                                   # (inside +-0.06 s windows fewer boundaries are summed: other ratios)
 
@@ -144,7 +145,7 @@ def test_folder_writes_the_edit_files_and_the_flagged_rows_in_order(whisper, tmp
     flagged = []
     for i in (0, 1):
         lines = open(out / f"f{i}.edits.tsv").read().split("\n")
-        assert lines[0] == AL.EDITS_HEADER and lines[-1] == ""
+        assert lines[0] == RP.REPORTS["edits"].header and lines[-1] == ""
         rows = [ln.split("\t") for ln in lines[1:-1]]
         assert [r[1] for r in rows] == trs[i] and [int(r[0]) for r in rows] == list(range(len(trs[i])))
         lab_lines = [ln.split() for ln in open(out / f"f{i}.lab").read().split("\n") if ln and ln.split()[2] not in ("SP", "AP")]
@@ -154,7 +155,7 @@ def test_folder_writes_the_edit_files_and_the_flagged_rows_in_order(whisper, tmp
             assert int(r[9]) == int(max(float(r[5]), float(r[7]), float(r[8])) > 0)
         flagged += [[f"f{i}.wav"] + r for r in rows if r[9] == "1"]
     lines = open(out / "transcript_edits.tsv").read().split("\n")
-    assert lines[0] == "file\t" + AL.EDITS_HEADER and lines[-1] == ""
+    assert lines[0] == "file\t" + RP.REPORTS["edits"].header and lines[-1] == ""
     got = [ln.split("\t") for ln in lines[1:-1]]
     assert sorted(got) == sorted(flagged) and len(flagged) > 0, "no token is flagged (test setup)"
     largest = [max(float(r[6]), float(r[8]), float(r[9])) for r in got]

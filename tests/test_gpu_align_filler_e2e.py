@@ -16,6 +16,7 @@ from test_gpu_align_e2e import LABELS, _write_tr
 from test_gpu_align_min_duration_e2e import CT, FD, _bytes, _transcript, whisper  # noqa: F401  (the module's fixture, built once here)
 from wfl_asr_amd import align as AL
 from wfl_asr_amd import infer as I
+from wfl_asr_amd import reports as RP
 
 pytestmark = pytest.mark.gpu
 F = "<unk>"
@@ -109,7 +110,7 @@ def test_a_filler_gives_the_host_dp_and_holds_the_free_segments(whisper, spy, ca
     assert all(a <= s < e <= b for s, e, _ in held) and held == AL.filler_segments(spans[30], free)
     assert all(x[1] <= y[0] + 1e-9 for x, y in zip(got, got[1:]))
     assert fillers == [AL.FillerSpan(30, a, b, int((rtok == 30).sum()), tuple(ph for _, _, ph in held))] and fillers[0].frames >= 1
-    assert AL.format_fillers_tsv(fillers).count("\n") == 2
+    assert RP.file_text("fillers", fillers).count("\n") == 2
     # a larger price: the reference's again, and a shorter (or equal) run
     spans5, rtok5 = _host_reference(lab, path, tr, 5.0)
     got5, fillers5 = _label(lab, path, tr, filler_token=F, filler_penalty=5.0)
@@ -161,9 +162,9 @@ def test_the_config_key_and_the_cli_flags_reach_infer_folder(whisper, tmp_path, 
         I.main(args + ["-o", str(tmp_path / "out"), "--filler-token", F, "--filler-penalty", "0.5"])
     assert e.value.code == 0 and seen["filler_token"] == F and seen["filler_penalty"] == 0.5
     assert open(tmp_path / "out" / "a.lab", "rb").read() == _bytes(ref)
-    want = AL.format_fillers_tsv(fillers)
+    want = RP.file_text("fillers", fillers)
     assert open(tmp_path / "out" / "a.fillers.tsv", encoding="utf-8").read() == want and want.count("\n") == 2
-    assert open(tmp_path / "out" / "filler_spans.tsv", encoding="utf-8").read() == AL.format_folder_fillers_tsv([("a.wav", fillers)])
+    assert open(tmp_path / "out" / "filler_spans.tsv", encoding="utf-8").read() == RP.folder_text("fillers", [("a.wav", fillers)])
     assert sorted(os.listdir(tmp_path / "out")) == ["a.fillers.tsv", "a.lab", "filler_spans.tsv"]
     with pytest.raises(SystemExit) as e:                  # the default price
         I.main(args + ["-o", str(tmp_path / "out1"), "--filler-token", F])

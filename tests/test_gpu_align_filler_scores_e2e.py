@@ -14,6 +14,7 @@ from test_gpu_align_min_duration_e2e import CT, _transcript, whisper  # noqa: F4
 from wfl_asr_amd import align as AL
 from wfl_asr_amd import infer as I
 from wfl_asr_amd import options as O
+from wfl_asr_amd import reports as RP
 
 pytestmark = pytest.mark.gpu
 
@@ -66,16 +67,16 @@ def test_the_new_files_and_their_columns(folders):
     assert sorted(os.listdir(outs["scored"])) == ["a.filler_scores.tsv", "a.fillers.tsv", "a.lab", "a.scores.tsv", "alignment_scores.tsv",
                                                   "b.filler_scores.tsv", "b.lab", "b.scores.tsv", "filler_scores.tsv", "filler_spans.tsv"]
     rows = _read(outs["scored"] / "a.filler_scores.tsv").decode().splitlines()
-    assert rows[0] == AL.FILLER_SCORES_HEADER and rows[0].split("\t") == ["index", "start_s", "end_s", "frames", "posterior", "start_shift_s",
+    assert rows[0] == RP.REPORTS["filler_scores"].header and rows[0].split("\t") == ["index", "start_s", "end_s", "frames", "posterior", "start_shift_s",
                                                                           "start_sd_s", "end_shift_s", "end_sd_s"]
     assert len(rows) == 2                                     # one filler in the transcript
     cells = rows[1].split("\t")
     span = _read(outs["scored"] / "a.fillers.tsv").decode().splitlines()[1].split("\t")
     assert cells[:4] == span[:4] and cells[0] == "30" and int(cells[3]) >= 1
     assert 0.0 <= float(cells[4]) <= 1.0 and float(cells[6]) >= 0.0 and float(cells[8]) >= 0.0
-    assert _read(outs["scored"] / "b.filler_scores.tsv").decode().splitlines() == [AL.FILLER_SCORES_HEADER]      # no filler, no row
+    assert _read(outs["scored"] / "b.filler_scores.tsv").decode().splitlines() == [RP.REPORTS["filler_scores"].header]      # no filler, no row
     folder_rows = _read(outs["scored"] / "filler_scores.tsv").decode().splitlines()
-    assert folder_rows == ["file\t" + AL.FILLER_SCORES_HEADER, "a.wav\t" + rows[1]]
+    assert folder_rows == ["file\t" + RP.REPORTS["filler_scores"].header, "a.wav\t" + rows[1]]
     # {stem}.scores.tsv: align_scores' format, one row per transcript token, the filler's row under its NAME with its span
     tr = _with_filler(_transcript(90))
     sc = [r.split("\t") for r in _read(outs["scored"] / "a.scores.tsv").decode().splitlines() if not r.startswith("#")]

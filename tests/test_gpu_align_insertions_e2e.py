@@ -17,6 +17,7 @@ from wfl_asr_amd import align as AL
 from wfl_asr_amd import infer as I
 from wfl_asr_amd import native_post as npost
 from wfl_asr_amd import postprocess as pp
+from wfl_asr_amd import reports as RP
 
 pytestmark = pytest.mark.gpu
 
@@ -43,7 +44,7 @@ def _direct(lab, path, tr, segments, windows_of=None):
     logz, ins, st = AL.insertion_scores(lg, [tv], [alts], [gaps], LABELS.index("O"), pairs, packed=packed)
     assert int(st[0]) == 0 and ins.shape == (len(tr) + 1, len(pairs))
     rows = AL.place_insertions(ins.cpu().numpy(), segments, out_names)
-    return [AL._insertion_cells(r) for r in rows], out_names
+    return [RP.REPORTS["insertions"].cells(r) for r in rows], out_names
 
 
 def test_insertions_leave_segments_and_edits_alone_and_equal_a_direct_call(whisper):  # noqa: F811
@@ -68,7 +69,7 @@ def test_insertions_leave_segments_and_edits_alone_and_equal_a_direct_call(whisp
     assert [r.before for r in rows] == tr + [""] and [r.after for r in rows] == [""] + tr
     assert [r.at_s for r in rows] == [core[0][0]] + [e for _, e, _ in core]
     want, out_names = _direct(lab, path, tr, core)
-    assert [AL._insertion_cells(r) for r in rows] == want
+    assert [RP.REPORTS["insertions"].cells(r) for r in rows] == want
     for r in rows:
         assert r.best != r.second and r.best in out_names and r.second in out_names
         assert r.best_ratio >= r.second_ratio and r.flag == int(r.best_ratio > 0)
@@ -95,7 +96,7 @@ def test_with_a_draft_the_windowed_lattice_is_the_one_scored(whisper):  # noqa: 
     assert npost.format_lab_tuples(segs[0]) == npost.format_lab_tuples(base)
     windowed, _ = _direct(lab, path, tr, segs[0], lambda tv: AL.draft_windows(draft, [tv], [0.0], 0.06, pp.FRAME_DURATION))
     open_, _ = _direct(lab, path, tr, segs[0])
-    got = [AL._insertion_cells(r) for r in ins[0]]
+    got = [RP.REPORTS["insertions"].cells(r) for r in ins[0]]
     assert got == windowed
     assert got != open_                                   # (inside +-0.06 s windows fewer boundaries are summed: other ratios)
 
@@ -139,7 +140,7 @@ def test_folder_writes_the_insertion_files_and_the_flagged_rows_in_order(whisper
     flagged = []
     for i in (0, 1):
         lines = open(out / f"f{i}.insertions.tsv").read().split("\n")
-        assert lines[0] == AL.INSERTIONS_HEADER and lines[-1] == ""
+        assert lines[0] == RP.REPORTS["insertions"].header and lines[-1] == ""
         rows = [ln.split("\t") for ln in lines[1:-1]]
         n = len(trs[i])
         assert len(rows) == n + 1 and [int(r[0]) for r in rows] == list(range(n + 1))
@@ -151,7 +152,7 @@ def test_folder_writes_the_insertion_files_and_the_flagged_rows_in_order(whisper
             assert int(r[8]) == int(float(r[5]) > 0) and float(r[5]) >= float(r[7]) and r[4] != r[6]
         flagged += [[f"f{i}.wav"] + r for r in rows if r[8] == "1"]
     lines = open(out / "transcript_insertions.tsv").read().split("\n")
-    assert lines[0] == "file\t" + AL.INSERTIONS_HEADER and lines[-1] == ""
+    assert lines[0] == "file\t" + RP.REPORTS["insertions"].header and lines[-1] == ""
     got = [ln.split("\t") for ln in lines[1:-1]]
     assert sorted(got) == sorted(flagged) and len(flagged) > 0, "no place is flagged (test setup)"
     best = [float(r[6]) for r in got]

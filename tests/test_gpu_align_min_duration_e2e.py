@@ -20,6 +20,7 @@ from wfl_asr_amd import audio as A
 from wfl_asr_amd import infer as I
 from wfl_asr_amd import native_post as npost
 from wfl_asr_amd import postprocess as pp
+from wfl_asr_amd import reports as RP
 
 pytestmark = pytest.mark.gpu
 FD = pp.FRAME_DURATION
@@ -153,9 +154,10 @@ def test_a_long_file_with_a_draft_carries_a_run_across_the_seam(whisper, spy, ca
         f.write(_bytes(base))
     try:
         capsys.readouterr()
-        moves = {}
         opts = lab.options(align="viterbi", align_draft=str(d / "drafts"), draft_tolerance=0.02, min_duration=0.16)
-        got, _ = lab._label_scored([long_p], opts, None, CT, False, moves)
+        reports = RP.Reports.for_options(opts)
+        got, _ = lab._label_scored([long_p], opts, None, CT, False, reports)
+        moves = reports.moves
         out = capsys.readouterr().out
     finally:
         os.remove(str(d / "drafts" / "long.lab"))

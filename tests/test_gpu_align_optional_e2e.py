@@ -16,6 +16,7 @@ from test_gpu_align_e2e import LABELS, _write_tr
 from test_gpu_align_min_duration_e2e import CT, FD, _bytes, _transcript, whisper  # noqa: F401  (the module's fixture, built once here)
 from wfl_asr_amd import align as AL
 from wfl_asr_amd import infer as I
+from wfl_asr_amd import reports as RP
 
 pytestmark = pytest.mark.gpu
 
@@ -133,9 +134,9 @@ def test_the_config_key_and_the_cli_flags_reach_infer_folder(whisper, tmp_path, 
         I.main(args + ["-o", str(tmp_path / "out"), "--optional", "p03", "--optional", "p01", "--skip-penalty", "0.5"])
     assert e.value.code == 0 and seen["optional_tokens"] == ("p01", "p03") and seen["skip_penalty"] == 0.5
     assert open(tmp_path / "out" / "a.lab", "rb").read() == _bytes(ref)
-    want = AL.format_skipped_tsv(skipped)
+    want = RP.file_text("skipped", skipped)
     assert open(tmp_path / "out" / "a.skipped.tsv", encoding="utf-8").read() == want and want.count("\n") == len(skipped) + 1
-    assert open(tmp_path / "out" / "skipped_tokens.tsv", encoding="utf-8").read() == AL.format_folder_skipped_tsv([("a.wav", skipped)])
+    assert open(tmp_path / "out" / "skipped_tokens.tsv", encoding="utf-8").read() == RP.folder_text("skipped", [("a.wav", skipped)])
     # '*' from the command line; the key from the config file
     with pytest.raises(SystemExit) as e:
         I.main(args + ["-o", str(tmp_path / "out_all"), "--optional", "*"])
@@ -171,9 +172,10 @@ def test_with_a_draft_kept_tokens_hold_their_windows(whisper, spy, capsys):  # n
         f.write(_bytes(base))
     try:
         capsys.readouterr()
-        moves, skipped = {}, {}
         opts = lab.options(align="viterbi", align_draft=str(d / "drafts"), draft_tolerance=0.1, optional_tokens="*", skip_penalty=0.0)
-        got, _ = lab._label_scored([long_p], opts, None, CT, False, moves, skipped=skipped)
+        reports = RP.Reports.for_options(opts)
+        got, _ = lab._label_scored([long_p], opts, None, CT, False, reports)
+        moves, skipped = reports.moves, reports.rows["skipped"]
         out = capsys.readouterr().out
     finally:
         os.remove(str(d / "drafts" / "long.lab"))
@@ -207,9 +209,10 @@ def test_the_safety_net_keeps_the_flags_when_it_drops_the_windows(whisper, spy, 
         f.write(_bytes(base))
     try:
         capsys.readouterr()
-        moves, skipped = {}, {}
         opts = lab.options(align="viterbi", align_draft=str(d / "drafts"), draft_tolerance=0.0, optional_tokens=["p01"])
-        got, _ = lab._label_scored([p], opts, None, CT, False, moves, skipped=skipped)
+        reports = RP.Reports.for_options(opts)
+        got, _ = lab._label_scored([p], opts, None, CT, False, reports)
+        moves, skipped = reports.moves, reports.rows["skipped"]
         out = capsys.readouterr().out
     finally:
         os.remove(str(d / "drafts" / "a.lab"))

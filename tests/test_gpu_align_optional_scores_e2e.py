@@ -13,6 +13,7 @@ from test_gpu_align_e2e import _write_tr
 from test_gpu_align_min_duration_e2e import CT, _bytes, _transcript, whisper  # noqa: F401  (the module's fixture, built once here)
 from wfl_asr_amd import align as AL
 from wfl_asr_amd import infer as I
+from wfl_asr_amd import reports as RP
 
 pytestmark = pytest.mark.gpu
 
@@ -100,7 +101,7 @@ def test_the_files_of_a_folder(whisper, tmp_path, monkeypatch, capsys):  # noqa:
         assert [r[0] for r in rows if r[2] == "skipped"] == left_out and all(r[2] in ("kept", "skipped") for r in rows)
         assert all((float(r[3]) if r[2] == "kept" else 1 - float(r[3])) < 0.5 for r in rows if r[6] == "1")
     lines = open(w / "optional_scores.tsv", encoding="utf-8").read().split("\n")
-    assert lines[0] == "file\t" + AL.OPTIONAL_HEADER and lines[-1] == ""
+    assert lines[0] == "file\t" + RP.REPORTS["optional"].header and lines[-1] == ""
     body = [ln.split("\t") for ln in lines[1:-1]]
     conf = [float(r[4]) if r[3] == "kept" else 1.0 - float(r[4]) for r in body]
     assert {r[0] for r in body} == {"a.wav", "b.wav"} and all(x <= y + 1e-6 for x, y in zip(conf, conf[1:]))   # least confident first

@@ -18,21 +18,18 @@ token gets one contiguous, time-ordered run of frames, none is dropped.
                         scoring the frame's best class minus `filler_penalty` (`wfl_align_filler`, `postprocess.filler_token`)
   filler_flags / collapse_fillers / filler_segments   `postprocess.filler_token` -> a flag per transcript token; runs of fillers merged;
                         the free segments a filler's span holds, clipped to it
-  FillerSpan / format_fillers_tsv / format_folder_fillers_tsv   one file's filler rows, {stem}.fillers.tsv, the folder's list
   optional_flags / min_frames_needed   `postprocess.optional_tokens` -> a flag per transcript token; the frames such a transcript needs
-  skipped_tokens / format_skipped_tsv / format_folder_skipped_tsv   one file's SkippedToken rows, {stem}.skipped.tsv, the folder's list
+  skipped_tokens        one file's SkippedToken rows
   optional_posteriors   forward-backward over that skip lattice (`wfl_align_optional_posterior`; `postprocess.optional_scores`):
                         alignment_posteriors' outputs and keep_post, per token the posterior probability that it is present
-  optional_token_scores / format_optional_tsv / format_folder_optional_tsv   one file's OptionalTokenScore rows (kept | skipped, the
-                        keep posterior, the `doubt` flag), {stem}.optional.tsv, the folder's list, least confident decision first
+  optional_token_scores one file's OptionalTokenScore rows (kept | skipped, the keep posterior, the `doubt` flag)
   min_frames_for        `postprocess.min_duration` (seconds, or seconds per token name) -> frames per transcript token
   viterbi_align_duration_prior  the search with a duration prior per token: a run of d frames adds its table row's L(d)
                         (`wfl_align_duration_prior`, `postprocess.duration_prior`); upload_durations packs the rows once
   duration_rows         a durations.DurationPrior -> the table row of every transcript token (-1: none)
   duration_prior_posteriors  forward-backward over that explicit-duration lattice (`wfl_align_duration_prior_posterior`;
                         `postprocess.duration_prior_scores`): alignment_posteriors' outputs and the moments of every token's end
-  token_durations / format_durations_tsv / format_folder_durations_tsv   one file's TokenDuration rows, {stem}.durations.tsv, the
-                        folder's list, the least probable length first
+  filler_scores / token_durations   one file's FillerScore / TokenDuration rows from those outputs
   duration_prior_expected_counts  every token's run-length posterior over that lattice (`wfl_align_duration_prior_counts`): the
                         E-step of durations.reestimate, `python -m wfl_asr_amd.adapt_durations`
   alignment_posteriors  forward-backward over the same lattice (csrc/align_posterior.h, `wfl_align_posterior`; of a batch packed with
@@ -44,10 +41,10 @@ token gets one contiguous, time-ordered run of frames, none is dropped.
                         (csrc/align_edits.hip, `wfl_align_edits`; `postprocess.align_edits`), on the same lattice, windows included
   substitute_table      the (B, I) pairs of a label set, the table edit_scores takes
   edit_groups           clips -> groups whose edit_scores workspace stays under EDITS_WORKSPACE_LIMIT
-  token_edits / write_edits_tsv / write_folder_edits   one file's rows of {stem}.edits.tsv, the file itself, the folder's list
+  token_edits           one file's TokenEdit rows
   insertion_scores      per place (in front of every token, and behind the last) the log likelihood ratio of inserting every phoneme
                         of a table there (csrc/align_edits.hip, `wfl_align_insertions`; `postprocess.align_insertions`)
-  place_insertions / write_insertions_tsv / write_folder_insertions   the same three for {stem}.insertions.tsv
+  place_insertions      one file's PlaceInsertion rows
   file_score            those outputs + viterbi_align's score -> FileScore / TokenScore records
   token_alternatives    transcript tokens -> (B, I) class pairs of every phoneme whose output name is the token
   gap_classes           the classes a gap between tokens may take (O, and SP / AP unless the transcript spells them)
@@ -55,6 +52,9 @@ token gets one contiguous, time-ordered run of frames, none is dropped.
   windows_feasible      the host rule that predicts the windowed search's status 1
   draft_windows         a draft's start times -> per-token windows on the file's rows, through the chunk clock
   read_draft            the draft .lab of a file (phonotactics.read_lab, the HTK reader the bigram estimate uses)
+
+The records of those rows (TokenEdit, PlaceInsertion, SkippedToken, OptionalTokenScore, FillerSpan, FillerScore, TokenDuration) and
+the files they are written to are reports.py's; the records are imported here, so align.TokenEdit and the others name them too.
 """
 from __future__ import annotations
 
@@ -67,6 +67,8 @@ import torch
 from . import _lib
 from . import native_post as npost
 from ._lib import back_to_back, host_ptr as _hp, ptr as _ptr
+from .reports import (FillerScore, FillerSpan, OptionalTokenScore, PlaceInsertion, SkippedToken, TokenDuration,  # noqa: F401
+                      TokenEdit)
 
 MAX_TOKENS = 4096          # wfl_align's token cap per clip (status 2 above it)
 MAX_ALTERNATIVES = 4       # (B, I) pairs per token
@@ -1198,23 +1200,6 @@ def file_score(score, logz, n_frames, tok_post, start_mean, start_sd, segments, 
 
 
 # ------------------------------------------------------------------------------------------------------------- transcript edits
-class TokenEdit(NamedTuple):
-    index: int
-    token: str
-    start_s: float
-    end_s: float
-    best: str               # output name of the best substitute ("" when the table holds none for this token)
-    best_ratio: float       # its log likelihood ratio against the transcript as written (-inf: none)
-    second: str
-    second_ratio: float
-    deletion_ratio: float   # the same for the transcript without the token
-    flag: int               # 1 when the largest of the three ratios is > 0: an edit explains the audio better
-
-    @property
-    def largest(self) -> float:
-        return max(self.best_ratio, self.second_ratio, self.deletion_ratio)
-
-
 def substitute_output_names(sub_names, table: npost.LabelTable, remap, names):
     """The output name of every substitute of substitute_table, through the merge-map back-mapping (`remap` / `names` of
     Labeler._names_for) that token_alternatives uses."""
@@ -1243,50 +1228,7 @@ def token_edits(edits, segments, sub_out_names):
     return rows
 
 
-EDITS_HEADER = "index\ttoken\tstart_s\tend_s\tbest\tbest_log_ratio\tsecond\tsecond_log_ratio\tdeletion_log_ratio\tflag"
-
-
-def _edit_cells(r: TokenEdit):
-    return [str(r.index), r.token, f"{r.start_s:.7f}", f"{r.end_s:.7f}", r.best, f"{r.best_ratio:.6g}", r.second,
-            f"{r.second_ratio:.6g}", f"{r.deletion_ratio:.6g}", str(r.flag)]
-
-
-def write_edits_tsv(path, rows):
-    """{stem}.edits.tsv: one line per transcript token."""
-    with open(path, "w", encoding="utf-8") as f:
-        f.write(EDITS_HEADER + "\n")
-        for r in rows:
-            f.write("\t".join(_edit_cells(r)) + "\n")
-
-
-def folder_edit_rows(per_file):
-    """per_file: [(file name, [TokenEdit])] -> every flagged token as (file name, TokenEdit), by its largest ratio, descending (ties
-    keep the files' and the tokens' order)."""
-    flagged = [(name, r) for name, rows in per_file for r in rows if r.flag]
-    return sorted(flagged, key=lambda x: -x[1].largest)
-
-
-def write_folder_edits(path, per_file):
-    """transcript_edits.tsv: folder_edit_rows, the file's name in front of the token's own columns."""
-    with open(path, "w", encoding="utf-8") as f:
-        f.write("file\t" + EDITS_HEADER + "\n")
-        for name, r in folder_edit_rows(per_file):
-            f.write("\t".join([name] + _edit_cells(r)) + "\n")
-
-
 # -------------------------------------------------------------------------------------------------------- transcript insertions
-class PlaceInsertion(NamedTuple):
-    index: int              # the place: 0 .. N, in front of token `index` (N: behind the last token)
-    after: str              # the neighbour tokens' names, "" at the ends
-    before: str
-    at_s: float             # the boundary of the Viterbi path there: the end of token index - 1, for index 0 the start of token 0
-    best: str               # output name of the best phoneme to insert ("" when the table is empty)
-    best_ratio: float       # its log likelihood ratio against the transcript as written (-inf: none, or no path)
-    second: str
-    second_ratio: float
-    flag: int               # 1 when best_ratio > 0: a token inserted here explains the audio better
-
-
 def place_insertions(ins, segments, sub_out_names):
     """One file's PlaceInsertion rows from its N + 1 rows of insertion_scores' `ins` (host values) and its N aligned segments
     [(start_s, end_s, token)].  Of several substitutes with one output name (a merge map) the best one stands for the name, so best
@@ -1309,46 +1251,7 @@ def place_insertions(ins, segments, sub_out_names):
     return rows
 
 
-INSERTIONS_HEADER = "index\tafter\tbefore\tat_s\tbest\tbest_log_ratio\tsecond\tsecond_log_ratio\tflag"
-
-
-def _insertion_cells(r: PlaceInsertion):
-    return [str(r.index), r.after, r.before, f"{r.at_s:.7f}", r.best, f"{r.best_ratio:.6g}", r.second, f"{r.second_ratio:.6g}",
-            str(r.flag)]
-
-
-def write_insertions_tsv(path, rows):
-    """{stem}.insertions.tsv: one line per place of the transcript."""
-    with open(path, "w", encoding="utf-8") as f:
-        f.write(INSERTIONS_HEADER + "\n")
-        for r in rows:
-            f.write("\t".join(_insertion_cells(r)) + "\n")
-
-
-def folder_insertion_rows(per_file):
-    """per_file: [(file name, [PlaceInsertion])] -> every flagged place as (file name, PlaceInsertion), by its best ratio, descending
-    (ties keep the files' and the places' order)."""
-    flagged = [(name, r) for name, rows in per_file for r in rows if r.flag]
-    return sorted(flagged, key=lambda x: -x[1].best_ratio)
-
-
-def write_folder_insertions(path, per_file):
-    """transcript_insertions.tsv: folder_insertion_rows, the file's name in front of the place's own columns."""
-    with open(path, "w", encoding="utf-8") as f:
-        f.write("file\t" + INSERTIONS_HEADER + "\n")
-        for name, r in folder_insertion_rows(per_file):
-            f.write("\t".join([name] + _insertion_cells(r)) + "\n")
-
-
 # -------------------------------------------------------------------------------------------------------------- skipped tokens
-class SkippedToken(NamedTuple):
-    index: int              # the token's index in the transcript
-    token: str
-    after: str              # the kept tokens around the place, "" at the ends
-    before: str
-    at_s: float             # the place: the start of the next kept token's segment, the end of the last segment when nothing follows
-
-
 def skipped_tokens(skipped, segments, transcript):
     """One file's SkippedToken rows from its tokens' `skipped` flags (viterbi_align_optional; host values) and its aligned segments
     [(start_s, end_s, token)], one per kept token in order (path_segments with the same flags)."""
@@ -1371,45 +1274,7 @@ def skipped_tokens(skipped, segments, transcript):
     return rows
 
 
-SKIPPED_HEADER = "index\ttoken\tafter\tbefore\tat_s"
-
-
-def _skipped_cells(r: SkippedToken):
-    return [str(r.index), r.token, r.after, r.before, f"{r.at_s:.7f}"]
-
-
-def format_skipped_tsv(rows) -> str:
-    """{stem}.skipped.tsv: one line per token the path left out."""
-    return "".join("\t".join(c) + "\n" for c in [SKIPPED_HEADER.split("\t")] + [_skipped_cells(r) for r in rows])
-
-
-def format_folder_skipped_tsv(per_file) -> str:
-    """skipped_tokens.tsv: [(file name, [SkippedToken])] -> every skipped token, the file's name in front of the token's own
-    columns, in the files' and the tokens' order."""
-    lines = ["file\t" + SKIPPED_HEADER] + ["\t".join([name] + _skipped_cells(r)) for name, rows in per_file for r in rows]
-    return "".join(line + "\n" for line in lines)
-
-
 # ------------------------------------------------------------------------------------------------------- optional tokens' scores
-class OptionalTokenScore(NamedTuple):
-    index: int              # the token's index in the transcript
-    token: str
-    kept: bool              # the best path holds the token
-    keep_posterior: float   # optional_posteriors' keep_post: the posterior probability that the token is present
-    start_s: float          # a kept token's segment; for a skipped one both are the place's time (SkippedToken.at_s)
-    end_s: float
-
-    @property
-    def confidence(self) -> float:
-        """The posterior mass behind the decision the best path took."""
-        return self.keep_posterior if self.kept else 1.0 - self.keep_posterior
-
-    @property
-    def doubt(self) -> bool:
-        """The opposite decision has more posterior mass than the one the best path took."""
-        return self.confidence < 0.5
-
-
 def optional_token_scores(optional, skipped, keep_post, segments, transcript):
     """One file's OptionalTokenScore rows, one per optional token of the transcript in order: the transcript's flags
     (optional_flags), the path's `skipped` flags and optional_posteriors' keep_post for the file (host values, one per transcript
@@ -1431,73 +1296,7 @@ def optional_token_scores(optional, skipped, keep_post, segments, transcript):
     return rows
 
 
-OPTIONAL_HEADER = "index\ttoken\tdecision\tkeep_posterior\tstart_s\tend_s\tdoubt"
-
-
-def _optional_cells(r: OptionalTokenScore):
-    return [str(r.index), r.token, "kept" if r.kept else "skipped", f"{r.keep_posterior:.6f}", f"{r.start_s:.7f}", f"{r.end_s:.7f}",
-            "1" if r.doubt else "0"]
-
-
-def format_optional_tsv(rows) -> str:
-    """{stem}.optional.tsv: one line per optional token of the transcript, in the transcript's order."""
-    return "".join("\t".join(c) + "\n" for c in [OPTIONAL_HEADER.split("\t")] + [_optional_cells(r) for r in rows])
-
-
-def folder_optional_rows(per_file):
-    """[(file name, [OptionalTokenScore])] -> [(file name, row)], the least confident decision first; ties in the files' and the
-    tokens' order."""
-    flat = [(name, r) for name, rows in per_file for r in rows]
-    return sorted(flat, key=lambda nr: nr[1].confidence)
-
-
-def format_folder_optional_tsv(per_file) -> str:
-    """optional_scores.tsv: every optional token of every file, the file's name in front of the token's own columns."""
-    lines = ["file\t" + OPTIONAL_HEADER] + ["\t".join([name] + _optional_cells(r)) for name, r in folder_optional_rows(per_file)]
-    return "".join(line + "\n" for line in lines)
-
-
-# --------------------------------------------------------------------------------------------------------------- filler tokens
-class FillerSpan(NamedTuple):
-    index: int              # the filler's index in the transcript (after collapse_fillers)
-    start_s: float          # its span on the .lab clock
-    end_s: float
-    frames: int             # the frames of its run
-    names: tuple            # the names of the free segments the span holds (filler_segments), in time order
-
-
-FILLERS_HEADER = "index\tstart_s\tend_s\tframes\tnames"
-
-
-def _filler_cells(r: FillerSpan):
-    return [str(r.index), f"{r.start_s:.7f}", f"{r.end_s:.7f}", str(r.frames), " ".join(str(n) for n in r.names)]
-
-
-def format_fillers_tsv(rows) -> str:
-    """{stem}.fillers.tsv: one line per filler of the transcript."""
-    return "".join("\t".join(c) + "\n" for c in [FILLERS_HEADER.split("\t")] + [_filler_cells(r) for r in rows])
-
-
-def format_folder_fillers_tsv(per_file) -> str:
-    """filler_spans.tsv: [(file name, [FillerSpan])] -> every filler of every file, the file's name in front of the span's own
-    columns, in the files' and the tokens' order."""
-    lines = ["file\t" + FILLERS_HEADER] + ["\t".join([name] + _filler_cells(r)) for name, rows in per_file for r in rows]
-    return "".join(line + "\n" for line in lines)
-
-
 # ------------------------------------------------------------------------------------------------------- filler tokens' scores
-class FillerScore(NamedTuple):
-    index: int              # the filler's index in the transcript (after collapse_fillers)
-    start_s: float          # its span on the .lab clock
-    end_s: float
-    frames: int             # the frames of its run
-    posterior: float        # filler_posteriors' tok_post: the posterior that the span's frames belong to the filler
-    start_shift_s: float    # posterior mean of the span's start minus Viterbi's, seconds on the .lab clock
-    start_sd_s: float       # posterior standard deviation of the start, seconds
-    end_shift_s: float      # the same for the span's end (filler_posteriors' end_mean / end_sd)
-    end_sd_s: float
-
-
 def filler_scores(spans, tok_post, start_mean, start_sd, end_mean, end_sd, frame_duration):
     """One file's FillerScore rows, one per FillerSpan in order, from filler_posteriors' outputs for the file (host values, one per
     transcript token).  frame_duration: the .lab clock that turns the frame figures into seconds."""
@@ -1514,44 +1313,7 @@ def filler_scores(spans, tok_post, start_mean, start_sd, end_mean, end_sd, frame
     return rows
 
 
-FILLER_SCORES_HEADER = "index\tstart_s\tend_s\tframes\tposterior\tstart_shift_s\tstart_sd_s\tend_shift_s\tend_sd_s"
-
-
-def _filler_score_cells(r: FillerScore):
-    return [str(r.index), f"{r.start_s:.7f}", f"{r.end_s:.7f}", str(r.frames), f"{r.posterior:.6f}", f"{r.start_shift_s:.7f}",
-            f"{r.start_sd_s:.7f}", f"{r.end_shift_s:.7f}", f"{r.end_sd_s:.7f}"]
-
-
-def format_filler_scores_tsv(rows) -> str:
-    """{stem}.filler_scores.tsv: one line per filler of the transcript, in the transcript's order."""
-    return "".join("\t".join(c) + "\n" for c in [FILLER_SCORES_HEADER.split("\t")] + [_filler_score_cells(r) for r in rows])
-
-
-def format_folder_filler_scores_tsv(per_file) -> str:
-    """filler_scores.tsv: [(file name, [FillerScore])] -> every filler of every file, the file's name in front of the filler's own
-    columns, the lowest occupancy posterior first; ties in the files' and the tokens' order.  No flag, no threshold: the order is
-    the list to check."""
-    flat = sorted(((name, r) for name, rows in per_file for r in rows), key=lambda nr: nr[1].posterior)
-    lines = ["file\t" + FILLER_SCORES_HEADER] + ["\t".join([name] + _filler_score_cells(r)) for name, r in flat]
-    return "".join(line + "\n" for line in lines)
-
-
 # ---------------------------------------------------------------------------------------- token durations under a duration prior
-class TokenDuration(NamedTuple):
-    index: int              # the token's index in the transcript
-    token: str
-    start_s: float          # its run on the .lab clock
-    end_s: float
-    frames: int             # the frames of its run
-    log_prior: float        # the table's L(frames) of the token's row: weight * log P(frames | phoneme); None for a token without a row
-    posterior: float        # duration_prior_posteriors' tok_post: the posterior that the run's frames belong to the token
-    start_shift_s: float    # posterior mean of the run's start minus the search's, seconds on the .lab clock
-    start_sd_s: float       # posterior standard deviation of the start, seconds
-    end_shift_s: float      # the same for the run's end
-    end_sd_s: float
-    expected_frames: float  # frames + end_mean - start_mean: the posterior mean of the token's length (exact, by linearity)
-
-
 def token_durations(tokens, frames, rows, table, tok_post, start_mean, start_sd, end_mean, end_sd, frame_duration):
     """One file's TokenDuration rows, one per transcript token in order, from duration_prior_posteriors' outputs for the file (host
     values, one per token).  tokens: the file's TokenScore rows (file_score); frames: the frames of every token's run; rows, table:
@@ -1572,27 +1334,3 @@ def token_durations(tokens, frames, rows, table, tok_post, start_mean, start_sd,
         out.append(TokenDuration(k, t.token, t.start_s, t.end_s, d, prior, p, smu * frame_duration, ssd * frame_duration,
                                  emu * frame_duration, esd * frame_duration, d + emu - smu))
     return out
-
-
-DURATIONS_HEADER = ("index\ttoken\tstart_s\tend_s\tframes\tlog_prior\tposterior\tstart_shift_s\tstart_sd_s\tend_shift_s\tend_sd_s"
-                    "\texpected_frames")
-
-
-def _duration_cells(r: TokenDuration):
-    return [str(r.index), r.token, f"{r.start_s:.7f}", f"{r.end_s:.7f}", str(r.frames),
-            "none" if r.log_prior is None else f"{r.log_prior:.6f}", f"{r.posterior:.6f}", f"{r.start_shift_s:.7f}", f"{r.start_sd_s:.7f}",
-            f"{r.end_shift_s:.7f}", f"{r.end_sd_s:.7f}", f"{r.expected_frames:.4f}"]
-
-
-def format_durations_tsv(rows) -> str:
-    """{stem}.durations.tsv: one line per transcript token, in the transcript's order."""
-    return "".join("\t".join(c) + "\n" for c in [DURATIONS_HEADER.split("\t")] + [_duration_cells(r) for r in rows])
-
-
-def format_folder_durations_tsv(per_file) -> str:
-    """token_durations.tsv: [(file name, [TokenDuration])] -> every token that has a prior row, of every file, the file's name in front
-    of the token's own columns, the lowest log_prior first (the length the prior finds least probable); ties in the files' and the
-    tokens' order.  No flag, no threshold: the order is the list to check."""
-    flat = sorted(((name, r) for name, rows in per_file for r in rows if r.log_prior is not None), key=lambda nr: nr[1].log_prior)
-    lines = ["file\t" + DURATIONS_HEADER] + ["\t".join([name] + _duration_cells(r)) for name, r in flat]
-    return "".join(line + "\n" for line in lines)

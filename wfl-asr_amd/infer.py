@@ -31,6 +31,7 @@ from . import audio as A
 from . import decode as DC
 from . import native_post as npost
 from . import postprocess as pp
+from . import reports as R
 from ._lib import back_to_back
 from .options import (ALIGN_MODES, DECODE_MODES, PostOptions, filler_token_collision, parse_min_duration, resolve,
                       unknown_optional_tokens)
@@ -591,42 +592,18 @@ class Labeler:
                             filler_scores=filler_scores, duration_prior=duration_prior, duration_prior_weight=duration_prior_weight,
                             duration_prior_scores=duration_prior_scores, decode_duration_prior=decode_duration_prior,
                             decode_duration_prior_weight=decode_duration_prior_weight)
-        edits = {} if opts.align_edits else None
-        insertions = {} if opts.align_insertions else None
-        skipped = {} if opts.optional_tokens is not None else None
-        optional = {} if opts.optional_scores else None
-        fillers = {} if opts.filler_token is not None else None
-        fscores = {} if opts.filler_scores else None
-        durations = {} if opts.duration_prior_scores else None
-        final, scores = self._label_scored(audio_paths, opts, lang_id, confidence_threshold, verbose, edits=edits,
-                                           insertions=insertions, skipped=skipped, optional=optional, fillers=fillers,
-                                           filler_scores=fscores, durations=durations)
+        reports = R.Reports.for_options(opts)
+        final, scores = self._label_scored(audio_paths, opts, lang_id, confidence_threshold, verbose, reports)
         out = (final, scores) if opts.scored else (final,)
-        if opts.align_edits:
-            out += ([edits.get(fi) for fi in range(len(audio_paths))],)
-        if opts.align_insertions:
-            out += ([insertions.get(fi) for fi in range(len(audio_paths))],)
-        if skipped is not None:
-            out += ([skipped.get(fi) for fi in range(len(audio_paths))],)
-        if optional is not None:
-            out += ([optional.get(fi) for fi in range(len(audio_paths))],)
-        if fillers is not None:
-            out += ([fillers.get(fi) for fi in range(len(audio_paths))],)
-        if fscores is not None:
-            out += ([fscores.get(fi) for fi in range(len(audio_paths))],)
-        if durations is not None:
-            out += ([durations.get(fi) for fi in range(len(audio_paths))],)
+        for by_file in reports.rows.values():             # (the enabled kinds, in reports.REPORTS' order)
+            out += ([by_file.get(fi) for fi in range(len(audio_paths))],)
         return out if len(out) > 1 else final
 
-    def _label_scored(self, audio_paths, opts, lang_id, confidence_threshold, verbose, moves=None, edits=None, insertions=None,
-                      skipped=None, optional=None, fillers=None, filler_scores=None, durations=None):
+    def _label_scored(self, audio_paths, opts, lang_id, confidence_threshold, verbose, reports=None):
         """label_files for the resolved options `opts`, always -> (segments, scores): the files are split once into those a transcript is
         Viterbi-aligned to, those the grammar search decodes and those left to the argmax decode, and each subset's results go back to
-        its files' places.  moves: a dict that takes {file index: [DraftMove]} for the files aligned inside their draft's windows.
-        edits (opts.align_edits): a dict that takes {file index: [TokenEdit]} for the files that were Viterbi-aligned; insertions
-        (opts.align_insertions): the same with [PlaceInsertion]; skipped (opts.optional_tokens): the same with [SkippedToken]; optional
-        (opts.optional_scores): the same with [OptionalTokenScore]; fillers (opts.filler_token): the same with [FillerSpan]; filler_scores
-        (opts.filler_scores): the same with [FillerScore]; durations (opts.duration_prior_scores): the same with [TokenDuration]."""
+        its files' places.  reports (reports.Reports.for_options(opts); None: nothing is kept): takes the draft moves and, per enabled
+        kind of side report, the rows of every file that was Viterbi-aligned that way, by file index."""
         if filler_token_collision(opts.filler_token, self._names_for(self._lang_name(lang_id))[1]) is not None:
             raise ValueError(f"filler_token: {opts.filler_token!r} is an output name of this model's label set")
         unknown = (unknown_optional_tokens(opts.optional_tokens, self._names_for(self._lang_name(lang_id))[1])
@@ -675,20 +652,12 @@ class Labeler:
         for fi, segs in searched.items():
             final[fi] = self._match_forced(audio_paths[fi], segs, verbose)
         if with_t:
-            fscores = {} if filler_scores is not None else None       # (by the file's place among with_t)
-            durs = {} if durations is not None else None
             got = self._label_viterbi(paths(with_t), [forced[fi] for fi in with_t], [drafts[fi] for fi in with_t], opts, lang_id,
-                                      confidence_threshold, verbose, fscores, prior, durs)
-            for j, rows in (fscores or {}).items():
-                filler_scores[with_t[j]] = rows
-            for j, rows in (durs or {}).items():
-                durations[with_t[j]] = rows
+                                      confidence_threshold, verbose, prior)
             for fi, rec in zip(with_t, got):
                 final[fi], scores[fi] = rec.segments, rec.score
-                for into, value in ((moves, rec.moves), (edits, rec.edits), (insertions, rec.insertions), (skipped, rec.skipped),
-                                    (optional, rec.optional), (fillers, rec.fillers)):
-                    if into is not None and value is not None:
-                        into[fi] = value
+                if reports is not None:
+                    reports.take(fi, rec.rows, rec.moves)
         return final, scores
 
     def _label_files_greedy(self, audio_paths, lang_id, confidence_threshold, verbose):
@@ -1019,18 +988,15 @@ class Labeler:
                 k0 += n
         return total, total_logz, n_frames, n_tokens, skipped
 
-    def _label_viterbi(self, audio_paths, transcripts, drafts, opts, lang_id, threshold, verbose, filler_scores=None, prior=None,
-                       durations=None):
+    def _label_viterbi(self, audio_paths, transcripts, drafts, opts, lang_id, threshold, verbose, prior=None):
         """Files with a transcript, align="viterbi" -> one ViterbiLabel per file.  Their chunks are forwarded with logits (kept on
         the device); the free decode of the same forward gives the greedy result, which the pause rule at the ends needs and which a
         file falls back to (with a message) when its transcript cannot be aligned.  Each file's chunks' valid logits rows are
         concatenated on the device, so one search covers the whole file; the files of a wave are one ragged batch (align.AlignBatch)
         that goes through the stages -- _greedy_and_plans, _clip_constraints, _search, _score, _clip_label -- and only ids / tok /
         score / status and the scoring calls' small tables come back to the host.  drafts: per file its draft segments or None
-        (opts.align_draft; the transcript is then the draft's labels).  filler_scores (opts.filler_scores): a dict that takes
-        {file index: [FillerScore]} for the files that were aligned and scored.  prior (opts.duration_prior): _duration_prior's
-        pair; the search is then the explicit-duration one.  durations (opts.duration_prior_scores): a dict that takes {file index:
-        [TokenDuration]} for the files that were searched and scored under the prior."""
+        (opts.align_draft; the transcript is then the draft's labels).  prior (opts.duration_prior): _duration_prior's pair; the
+        search is then the explicit-duration one."""
         lang_name = self._lang_name(lang_id)
         drafts = drafts if drafts is not None else [None] * len(audio_paths)
         sub_pairs = sub_out = None
@@ -1058,30 +1024,16 @@ class Labeler:
                 found = _search(batch, paths, opts, prior[1] if prior is not None else None)
                 scored = _score(found, opts, sub_pairs, prior[1] if prior is not None else None)
                 for b, fi in enumerate(run):
-                    got = self._clip_label(found, scored, b, chunks[b], transcripts[fi], drafts[fi], free_segs[fi], opts, sub_out)
+                    got = self._clip_label(found, scored, b, chunks[b], transcripts[fi], drafts[fi], free_segs[fi], opts, sub_out,
+                                           prior[1] if prior is not None else None)
                     if got is not None:
                         aligned[fi] = got
-                        if opts.filler_scores and filler_scores is not None and b in scored.raw:
-                            # one row per filler; a scored file without a filler has none
-                            filler_scores[fi] = (AL.filler_scores(got.fillers, *scored.raw[b][2:], *scored.ends[b], frame_duration)
-                                                 if got.fillers else [])
-                        if opts.duration_prior_scores and durations is not None and b in scored.ends:
-                            pos, rows_b = int(found.batch.f0[b]), found.batch.durs[b]
-                            tok_b = found.tok[pos:pos + found.batch.frames[b]]
-                            durations[fi] = AL.token_durations(got.score.tokens, np.bincount(tok_b[tok_b >= 0], minlength=len(rows_b)),
-                                                               rows_b, prior[1], *scored.raw[b][2:], *scored.ends[b], frame_duration)
             for fi in sel:
                 out.append(aligned.get(fi, ViterbiLabel(greedy[fi])))
-                if opts.optional_scores and fi not in aligned:
-                    print(f"{audio_paths[fi]}: no optional-token scores (the file was not Viterbi-aligned)")
-                if opts.filler_scores and fi not in aligned:
-                    print(f"{audio_paths[fi]}: no filler scores (the file was not Viterbi-aligned)")
-                if opts.duration_prior_scores and fi not in aligned:
-                    print(f"{audio_paths[fi]}: no duration-prior scores (the file was not Viterbi-aligned)")
-                if opts.align_edits and fi not in aligned:
-                    print(f"{audio_paths[fi]}: no transcript edits (the file was not Viterbi-aligned)")
-                if opts.align_insertions and fi not in aligned:
-                    print(f"{audio_paths[fi]}: no transcript insertions (the file was not Viterbi-aligned)")
+                if fi not in aligned:
+                    for key in NOT_ALIGNED_LINES:
+                        if R.REPORTS[key].enabled(opts):
+                            print(f"{audio_paths[fi]}: {R.REPORTS[key].missing} (the file was not Viterbi-aligned)")
         return out
 
     def _greedy_and_plans(self, sel, by_file, free, audio_paths, transcripts, lang_name, filler=None):
@@ -1106,8 +1058,9 @@ class Labeler:
                 print(f"{audio_paths[fi]}: viterbi alignment not possible ({why}); using the greedy alignment")
         return greedy, free_segs, plans
 
-    def _clip_label(self, found, scored, b, chunk_plan, tr, draft, free_segs, opts, sub_out):
-        """Stage 5: clip b of a searched wave -> its file's ViterbiLabel, or None (with a line) for a clip the search did not align."""
+    def _clip_label(self, found, scored, b, chunk_plan, tr, draft, free_segs, opts, sub_out, dur_table=None):
+        """Stage 5: clip b of a searched wave -> its file's ViterbiLabel, or None (with a line) for a clip the search did not align.
+        dur_table (opts.duration_prior): the table the clip was searched with."""
         batch = found.batch
         n, pos = batch.frames[b], int(batch.f0[b])
         flags = batch.opts[b] if batch.opts is not None else None
@@ -1121,7 +1074,7 @@ class Labeler:
             print(f"{found.paths[b]}: viterbi alignment not possible ({why}); using the greedy alignment")
             return None
         tok = found.tok[pos:pos + n]
-        left_out = skipped = None
+        left_out, rows = None, {}                         # rows: the clip's side reports, by kind (reports.REPORTS)
         if flags is not None:                             # the clip was searched with skip arcs: which tokens the path left out
             k0 = sum(len(a) for a in batch.alts[:b])
             left_out = found.skipped[k0:k0 + len(tr)]
@@ -1129,10 +1082,10 @@ class Labeler:
         segs = AL.path_segments(found.ids[pos:pos + n], tok, *chunk_plan, self._table, batch.alts[b], tr, frame_duration,
                                 fillers=fill, skipped=left_out)
         if flags is not None:
-            skipped = AL.skipped_tokens(left_out, segs, tr)
-            print(f"{found.paths[b]}: {len(skipped)} of {int(sum(flags))} optional tokens skipped")
+            rows["skipped"] = AL.skipped_tokens(left_out, segs, tr)
+            print(f"{found.paths[b]}: {len(rows['skipped'])} of {int(sum(flags))} optional tokens skipped")
         moves = draft_moves(draft, segs, tok, batch.wins[b], left_out) if batch.wins[b] is not None else None
-        score = optional = None
+        score = None
         if b in scored.raw:
             per_tok = scored.raw[b][2:]
             if left_out is not None:                      # the scores of the kept tokens, one per segment
@@ -1140,8 +1093,8 @@ class Labeler:
             score = AL.file_score(scored.raw[b][0], scored.raw[b][1], n, *per_tok, segs, frame_duration)
             if b in scored.keep:                          # (scored over the skip lattice: its optional tokens' decisions)
                 no_flag = [0] * len(tr)
-                optional = AL.optional_token_scores(flags if flags is not None else no_flag, left_out if left_out is not None else no_flag,
-                                                    scored.keep[b], segs, tr)
+                rows["optional"] = AL.optional_token_scores(flags if flags is not None else no_flag,
+                                                            left_out if left_out is not None else no_flag, scored.keep[b], segs, tr)
         elif (opts.align_scores or opts.duration_scores or opts.optional_scores or opts.filler_scores
               or opts.duration_prior_scores):             # (the scoring entry refused the path the search gave it)
             entry, code = scored.refused.get(b, ("wfl_align_posterior", None))
@@ -1150,13 +1103,23 @@ class Labeler:
         if fill is not None:                              # a filler's span holds what the file's own free decode found there
             held = {k: AL.filler_segments(g, free_segs) for k, g in enumerate(segs) if fill[k]}
             lab = [x for k, g in enumerate(segs) for x in (held[k] if k in held else [g])]
-            spans = [AL.FillerSpan(k, float(segs[k][0]), float(segs[k][1]), int((tok == k).sum()), tuple(x[2] for x in held[k]))
-                     for k in sorted(held)]
+            spans = rows["fillers"] = [AL.FillerSpan(k, float(segs[k][0]), float(segs[k][1]), int((tok == k).sum()),
+                                                     tuple(x[2] for x in held[k])) for k in sorted(held)]
             print(f"{found.paths[b]}: {len(spans)} filler{'s' if len(spans) != 1 else ''} in the transcript")
-        return ViterbiLabel(AL.with_end_pauses(free_segs, lab, tr), score, moves,
-                            AL.token_edits(scored.edits[b], segs, sub_out) if b in scored.edits else None,
-                            AL.place_insertions(scored.insertions[b], segs, sub_out) if b in scored.insertions else None, skipped, optional,
-                            spans)
+        if b in scored.edits:
+            rows["edits"] = AL.token_edits(scored.edits[b], segs, sub_out)
+        if b in scored.insertions:
+            rows["insertions"] = AL.place_insertions(scored.insertions[b], segs, sub_out)
+        if opts.filler_scores and b in scored.raw:        # one row per filler; a scored file without a filler has none
+            rows["filler_scores"] = AL.filler_scores(spans, *scored.raw[b][2:], *scored.ends[b], frame_duration) if spans else []
+        if opts.duration_prior_scores and b in scored.ends:
+            frames = np.bincount(tok[tok >= 0], minlength=len(batch.durs[b]))
+            rows["durations"] = AL.token_durations(score.tokens, frames, batch.durs[b], dur_table, *scored.raw[b][2:], *scored.ends[b],
+                                                   frame_duration)
+        return ViterbiLabel(AL.with_end_pauses(free_segs, lab, tr), score, moves, rows)
+
+
+NOT_ALIGNED_LINES = ("optional", "filler_scores", "durations", "edits", "insertions")   # the order a file's lines are printed in
 
 
 class ViterbiLabel(NamedTuple):
@@ -1164,11 +1127,7 @@ class ViterbiLabel(NamedTuple):
     segments: list
     score: AL.FileScore = None      # opts.align_scores / duration_scores, a file that was aligned and scored
     moves: list = None              # [DraftMove], a file aligned inside its draft's windows
-    edits: list = None              # [TokenEdit] (opts.align_edits), a file that was aligned
-    insertions: list = None         # [PlaceInsertion] (opts.align_insertions), the same
-    skipped: list = None            # [SkippedToken] (opts.optional_tokens), a file aligned with optional tokens
-    optional: list = None           # [OptionalTokenScore] (opts.optional_scores), a file scored over the skip lattice
-    fillers: list = None            # [FillerSpan] (opts.filler_token), a file aligned with a filler in its transcript
+    rows: dict = {}                 # the file's side reports, {kind: rows} (reports.REPORTS), of the kinds that apply to the file
 
 
 class _Searched(NamedTuple):
@@ -1630,76 +1589,11 @@ def decode_scores_path(lab_path):
     return os.path.splitext(lab_path)[0] + ".decode_scores.tsv"
 
 
-def edits_path(lab_path):
-    return os.path.splitext(lab_path)[0] + ".edits.tsv"
-
-
-def _write_edits(lab_path, rows):
-    """`{stem}.edits.tsv` beside the .lab of a file that was Viterbi-aligned (None: no file)."""
-    if rows is not None:
-        AL.write_edits_tsv(edits_path(lab_path), rows)
-        print(f"Transcript edits saved to: {edits_path(lab_path)}")
-
-
-def insertions_path(lab_path):
-    return os.path.splitext(lab_path)[0] + ".insertions.tsv"
-
-
-def _write_insertions(lab_path, rows):
-    """`{stem}.insertions.tsv` beside the .lab of a file that was Viterbi-aligned (None: no file)."""
-    if rows is not None:
-        AL.write_insertions_tsv(insertions_path(lab_path), rows)
-        print(f"Transcript insertions saved to: {insertions_path(lab_path)}")
-
-
-def skipped_path(lab_path):
-    return os.path.splitext(lab_path)[0] + ".skipped.tsv"
-
-
-def _write_skipped(lab_path, rows):
-    """`{stem}.skipped.tsv` beside the .lab of a file that was aligned with optional tokens (None: no file)."""
-    if rows is not None:
-        _write_text(skipped_path(lab_path), AL.format_skipped_tsv(rows), "Skipped tokens")
-
-
-def optional_path(lab_path):
-    return os.path.splitext(lab_path)[0] + ".optional.tsv"
-
-
-def _write_optional(lab_path, rows):
-    """`{stem}.optional.tsv` beside the .lab of a file that was scored over the skip lattice (None: no file)."""
-    if rows is not None:
-        _write_text(optional_path(lab_path), AL.format_optional_tsv(rows), "Optional-token scores")
-
-
-def fillers_path(lab_path):
-    return os.path.splitext(lab_path)[0] + ".fillers.tsv"
-
-
-def _write_fillers(lab_path, rows):
-    """`{stem}.fillers.tsv` beside the .lab of a file that was aligned with a filler in its transcript (None: no file)."""
-    if rows is not None:
-        _write_text(fillers_path(lab_path), AL.format_fillers_tsv(rows), "Filler spans")
-
-
-def filler_scores_path(lab_path):
-    return os.path.splitext(lab_path)[0] + ".filler_scores.tsv"
-
-
-def _write_filler_scores(lab_path, rows):
-    """`{stem}.filler_scores.tsv` beside the .lab of a file that was scored over the lattice of its filler search (None: no file)."""
-    if rows is not None:
-        _write_text(filler_scores_path(lab_path), AL.format_filler_scores_tsv(rows), "Filler scores")
-
-
-def durations_path(lab_path):
-    return os.path.splitext(lab_path)[0] + ".durations.tsv"
-
-
-def _write_durations(lab_path, rows):
-    """`{stem}.durations.tsv` beside the .lab of a file that was scored over the explicit-duration lattice (None: no file)."""
-    if rows is not None:
-        _write_text(durations_path(lab_path), AL.format_durations_tsv(rows), "Token durations")
+def _write_reports(lab_path, reports, fi):
+    """File fi's side reports beside its .lab, one file per enabled kind the file has rows of, in reports.REPORTS' order."""
+    for key, by_file in reports.rows.items():
+        if by_file.get(fi) is not None:
+            _write_text(R.file_path(key, lab_path), R.file_text(key, by_file[fi]), R.REPORTS[key].what)
 
 
 def _write_score(lab_path, segments, score):
@@ -1729,31 +1623,31 @@ def infer_audio(audio_path, config_path="config.yaml", checkpoint_path="best_mod
     config postprocess.align_draft / postprocess.draft_tolerance): refine the draft DIR/{stem}.lab inside per-token start windows
     (Labeler.label_files).  align_edits (align viterbi only; None: config postprocess.align_edits): also write `{stem}.edits.tsv`
     beside the .lab when the file was Viterbi-aligned: per token the best and second-best substitute, the deletion, their log
-    likelihood ratios and a flag (align.write_edits_tsv).  align_insertions (align viterbi only; None: config
+    likelihood ratios and a flag (reports.REPORTS["edits"]).  align_insertions (align viterbi only; None: config
     postprocess.align_insertions): also write `{stem}.insertions.tsv` beside the .lab when the file was Viterbi-aligned: per place of
-    the transcript the best and second-best phoneme to insert, their log likelihood ratios and a flag (align.write_insertions_tsv).
+    the transcript the best and second-best phoneme to insert, their log likelihood ratios and a flag (reports.REPORTS["insertions"]).
     min_duration (align viterbi only; None: config postprocess.min_duration): seconds, or {token name: seconds, "default": seconds}:
     the least time a transcript token occupies in the search (Labeler.label_files).  duration_scores (with a min_duration only; None:
     config postprocess.duration_scores): align_scores for that search, the same `{stem}.scores.tsv`, summed over the
     minimum-duration lattice (align.duration_posteriors).  optional_tokens / skip_penalty (align viterbi only; None: config
     postprocess.optional_tokens / postprocess.skip_penalty): the transcript tokens a path may leave out, [NAME, ...] or "*", and the
     nats each skipped one costs (Labeler.label_files); the .lab lacks the skipped tokens and `{stem}.skipped.tsv` lists them
-    (align.format_skipped_tsv).  optional_scores (with optional_tokens only; None: config postprocess.optional_scores): also write
+    (reports.REPORTS["skipped"]).  optional_scores (with optional_tokens only; None: config postprocess.optional_scores): also write
     `{stem}.scores.tsv` for the kept tokens, summed over the skip lattice, and `{stem}.optional.tsv`, one row per optional token of
-    the transcript with the posterior probability that it is present (align.optional_posteriors, align.format_optional_tsv).
+    the transcript with the posterior probability that it is present (align.optional_posteriors, reports.REPORTS["optional"]).
     filler_token / filler_penalty (align viterbi only; None: config postprocess.filler_token / postprocess.filler_penalty): the
     transcript token that matches anything and the nats it pays per frame (Labeler.label_files); in the .lab its span holds what
-    the free decode found there, and `{stem}.fillers.tsv` lists the spans (align.format_fillers_tsv).  filler_scores (with a
+    the free decode found there, and `{stem}.fillers.tsv` lists the spans (reports.REPORTS["fillers"]).  filler_scores (with a
     filler_token only; None: config postprocess.filler_scores): also write `{stem}.scores.tsv`, one row per transcript token summed
     over the lattice the file was searched on, and `{stem}.filler_scores.tsv`, one row per filler with the posterior of its span and
-    the mean shift and spread of both its ends (align.filler_posteriors, align.format_filler_scores_tsv); the .lab and
+    the mean shift and spread of both its ends (align.filler_posteriors, reports.REPORTS["filler_scores"]); the .lab and
     `{stem}.fillers.tsv` are what they are without it.  duration_prior / duration_prior_weight (align viterbi only; None: config
     postprocess.duration_prior / postprocess.duration_prior_weight): the phoneme duration prior of the explicit-duration search and
     what its log probabilities are multiplied by (Labeler.label_files).  duration_prior_scores (with a duration_prior only; None:
     config postprocess.duration_prior_scores): also write `{stem}.scores.tsv`, one row per transcript token summed over the lattice
     the file was searched on, and, for a file searched under the prior, `{stem}.durations.tsv`, one row per token with its length,
     the prior's log probability of it, the posterior of its run, the shift and spread of both its ends and its expected length
-    (align.duration_prior_posteriors, align.format_durations_tsv); the .lab is what it is without it.  decode_duration_prior /
+    (align.duration_prior_posteriors, reports.REPORTS["durations"]); the .lab is what it is without it.  decode_duration_prior /
     decode_duration_prior_weight (decode viterbi only; None: config postprocess.decode_duration_prior /
     postprocess.decode_duration_prior_weight): the phoneme duration prior of the FREE decode's explicit-duration search and what its log
     probabilities are multiplied by (Labeler.label_files)."""
@@ -1768,36 +1662,15 @@ def infer_audio(audio_path, config_path="config.yaml", checkpoint_path="best_mod
     _refuse_before_load(config_path, **given)
     lab = _labeler(config_path, checkpoint_path, device)
     opts = lab.options(**given)
-    edits = {} if opts.align_edits else None
-    insertions = {} if opts.align_insertions else None
-    skipped = {} if opts.optional_tokens is not None else None
-    optional = {} if opts.optional_scores else None
-    fillers = {} if opts.filler_token is not None else None
-    fscores = {} if opts.filler_scores else None
-    durations = {} if opts.duration_prior_scores else None
-    (segments,), (score,) = lab._label_scored([audio_path], opts, lang_id, confidence_threshold, True, edits=edits,
-                                              insertions=insertions, skipped=skipped, optional=optional, fillers=fillers,
-                                              filler_scores=fscores, durations=durations)
+    reports = R.Reports.for_options(opts)
+    (segments,), (score,) = lab._label_scored([audio_path], opts, lang_id, confidence_threshold, True, reports)
     if output_lab_path:
         if os.path.abspath(output_lab_path) == os.path.abspath(audio_path):
             # the reference would truncate the input WAV here (infer.py:410-411 + utils.py:77)
             output_lab_path = os.path.splitext(audio_path)[0] + ".lab"
         _write_lab(output_lab_path, segments)
         _write_score(output_lab_path, segments, score)
-        if edits is not None:
-            _write_edits(output_lab_path, edits.get(0))
-        if insertions is not None:
-            _write_insertions(output_lab_path, insertions.get(0))
-        if skipped is not None:
-            _write_skipped(output_lab_path, skipped.get(0))
-        if optional is not None:
-            _write_optional(output_lab_path, optional.get(0))
-        if fillers is not None:
-            _write_fillers(output_lab_path, fillers.get(0))
-        if fscores is not None:
-            _write_filler_scores(output_lab_path, fscores.get(0))
-        if durations is not None:
-            _write_durations(output_lab_path, durations.get(0))
+        _write_reports(output_lab_path, reports, 0)
     return segments
 
 
@@ -1829,81 +1702,38 @@ def infer_folder(folder_path: str, config_path: str = "config.yaml", checkpoint_
     lab = _labeler(config_path, checkpoint_path, device)
     paths = [os.path.join(folder_path, f) for f in wav_files]
     opts = lab.options(**given)
-    moves = {}
-    edits = {} if opts.align_edits else None
-    insertions = {} if opts.align_insertions else None
-    skipped = {} if opts.optional_tokens is not None else None
-    optional = {} if opts.optional_scores else None
-    fillers = {} if opts.filler_token is not None else None
-    fscores = {} if opts.filler_scores else None
-    durations = {} if opts.duration_prior_scores else None
-    all_segments, all_scores = (lab._label_scored(paths, opts, lang_id, confidence_threshold, True, moves, edits, insertions, skipped,
-                                                  optional, fillers, fscores, durations)
-                                if paths else ([], []))
+    reports = R.Reports.for_options(opts)
+    all_segments, all_scores = lab._label_scored(paths, opts, lang_id, confidence_threshold, True, reports) if paths else ([], [])
     for fi, (wav_file, segments, score) in enumerate(zip(wav_files, all_segments, all_scores)):
         print(f"\nInferencing: {wav_file}")
         lab_path = os.path.join(output_dir, os.path.splitext(wav_file)[0] + ".lab")
         _write_lab(lab_path, segments)
         _write_score(lab_path, segments, score)
-        if edits is not None:
-            _write_edits(lab_path, edits.get(fi))
-        if insertions is not None:
-            _write_insertions(lab_path, insertions.get(fi))
-        if skipped is not None:
-            _write_skipped(lab_path, skipped.get(fi))
-        if optional is not None:
-            _write_optional(lab_path, optional.get(fi))
-        if fillers is not None:
-            _write_fillers(lab_path, fillers.get(fi))
-        if fscores is not None:
-            _write_filler_scores(lab_path, fscores.get(fi))
-        if durations is not None:
-            _write_durations(lab_path, durations.get(fi))
+        _write_reports(lab_path, reports, fi)
         print("Predicted segments:")
         for start, end, ph in segments:
             print(f"({round(start, 2)}, {round(end, 2)}, {ph})")
+    def write_folder(stem, text, what):
+        _write_text(os.path.join(output_dir, f"{stem}.tsv" if world == 1 else f"{stem}.rank{rank}.tsv"), text, what)
+
+    def write_folder_reports(keys):
+        for key in keys:
+            if key in reports.rows:
+                write_folder(R.REPORTS[key].stem, R.folder_text(key, reports.named(key, wav_files)), R.REPORTS[key].what + " of the folder")
+
+    first = ("edits", "insertions")                       # draft_moves.tsv keeps its place between these two kinds and the later ones
+
     if opts.align_scores or opts.duration_scores or opts.optional_scores or opts.filler_scores or opts.duration_prior_scores:
-        name = "alignment_scores.tsv" if world == 1 else f"alignment_scores.rank{rank}.tsv"
-        _write_text(os.path.join(output_dir, name),
-                    format_review_tsv([(f, sc) for f, sc in zip(wav_files, all_scores) if isinstance(sc, AL.FileScore)]), "Review list")
-    if opts.align_edits:
-        name = "transcript_edits.tsv" if world == 1 else f"transcript_edits.rank{rank}.tsv"
-        AL.write_folder_edits(os.path.join(output_dir, name), [(wav_files[fi], edits[fi]) for fi in sorted(edits)])
-        print(f"Transcript edits of the folder saved to: {os.path.join(output_dir, name)}")
-    if opts.align_insertions:
-        name = "transcript_insertions.tsv" if world == 1 else f"transcript_insertions.rank{rank}.tsv"
-        AL.write_folder_insertions(os.path.join(output_dir, name), [(wav_files[fi], insertions[fi]) for fi in sorted(insertions)])
-        print(f"Transcript insertions of the folder saved to: {os.path.join(output_dir, name)}")
+        write_folder("alignment_scores", format_review_tsv([(f, sc) for f, sc in zip(wav_files, all_scores) if isinstance(sc, AL.FileScore)]),
+                     "Review list")
+    write_folder_reports(first)
     if opts.align_draft:
-        name = "draft_moves.tsv" if world == 1 else f"draft_moves.rank{rank}.tsv"
-        _write_text(os.path.join(output_dir, name), format_draft_moves_tsv([(wav_files[fi], moves[fi]) for fi in sorted(moves)]),
-                    "Draft moves")
-    if skipped is not None:
-        name = "skipped_tokens.tsv" if world == 1 else f"skipped_tokens.rank{rank}.tsv"
-        _write_text(os.path.join(output_dir, name), AL.format_folder_skipped_tsv([(wav_files[fi], skipped[fi]) for fi in sorted(skipped)]),
-                    "Skipped tokens of the folder")
-    if optional is not None:
-        name = "optional_scores.tsv" if world == 1 else f"optional_scores.rank{rank}.tsv"
-        _write_text(os.path.join(output_dir, name), AL.format_folder_optional_tsv([(wav_files[fi], optional[fi]) for fi in sorted(optional)]),
-                    "Optional-token scores of the folder")
-    if fillers is not None:
-        name = "filler_spans.tsv" if world == 1 else f"filler_spans.rank{rank}.tsv"
-        _write_text(os.path.join(output_dir, name), AL.format_folder_fillers_tsv([(wav_files[fi], fillers[fi]) for fi in sorted(fillers)]),
-                    "Filler spans of the folder")
-    if fscores is not None:
-        name = "filler_scores.tsv" if world == 1 else f"filler_scores.rank{rank}.tsv"
-        _write_text(os.path.join(output_dir, name), AL.format_folder_filler_scores_tsv([(wav_files[fi], fscores[fi]) for fi in sorted(fscores)]),
-                    "Filler scores of the folder")
-    if durations is not None:
-        name = "token_durations.tsv" if world == 1 else f"token_durations.rank{rank}.tsv"
-        _write_text(os.path.join(output_dir, name),
-                    AL.format_folder_durations_tsv([(wav_files[fi], durations[fi]) for fi in sorted(durations)]),
-                    "Token durations of the folder")
+        write_folder("draft_moves", format_draft_moves_tsv([(wav_files[fi], reports.moves[fi]) for fi in sorted(reports.moves)]),
+                     "Draft moves")
+    write_folder_reports([key for key in R.REPORTS if key not in first])
     if opts.free_scores:
-        name = "decode_scores.tsv" if world == 1 else f"decode_scores.rank{rank}.tsv"
-        _write_text(os.path.join(output_dir, name),
-                    format_decode_review_tsv([(f, sc) for f, sc in zip(wav_files, all_scores) if isinstance(sc, DC.FreeScore)]),
-                    "Decode review list")
+        write_folder("decode_scores", format_decode_review_tsv([(f, sc) for f, sc in zip(wav_files, all_scores) if isinstance(sc, DC.FreeScore)]),
+                     "Decode review list")
     return all_segments
 
 
