@@ -2,7 +2,7 @@
 // Replaces HF modeling_whisper.py:215-238 / SDPA (Whisper, head_dim 64) and nn.MultiheadAttention inside the
 // Conformer block (/root/reference/model.py:26, 42; head_dim = d / conformer_heads = 256 for Whisper-base).
 //
-// One workgroup = 4 waves = one (clip, head, block of query frames); each wave owns QT tiles of 16 query frames.
+// One workgroup = NW waves (4; 8 or 12 at head_dim 256) = one (clip, head, block of query frames); each wave owns QT tiles of 16 query frames.
 // K tiles and V tiles (64 keys x HD, both row-major exactly as the packed q|k|v projection wrote them) are staged in
 // LDS.  Scores are computed TRANSPOSED, S^T = K . Q^T with MFMA 16x16x32 (A = K rows, B = Q rows), so every
 // lane holds scores of ONE query frame (column lane&15) and the row max/sum need only two cross-lane steps; the
@@ -44,8 +44,18 @@ typedef __attribute__((address_space(3))) void* attn_lptr_t;
 // (one output-channel tile each) of a row XORed so that the 8 key rows x 32 bytes one half of a ds_read_b64_tr_b16 touches fall into 8
 // different windows of the 256-byte bank row
 template <int HD>
-static __host__ __device__ constexpr bool attn_dma(bool prefetch) {
-  return WFL_ATTN_DMA && ((prefetch && (HD == 32 || HD == 64 || HD == 128)) || (!prefetch && HD == 256));
+static __host__ __device__ constexpr bool attn_dma(bool prefetch, int nw = 4) {
+  return WFL_ATTN_DMA && ((prefetch && (HD == 32 || HD == 64 || HD == 128 || (HD == 256 && nw > 4))) || (!prefetch && HD == 256));
+}
+// The wide head_dim 256 kernels (more than four waves, two tile buffers) issue their LDS-DMA from an asm statement: behind the builtin hipcc
+// waits vmcnt(0) in front of the first ds_read_b64_tr_b16 that follows (it cannot tell that the V reads touch the other buffer), which ends
+// the overlap halfway through a tile.  hipcc does not count an asm load: the kernel's own vmcnt(0) in front of the tile's barrier does.
+// M0 (the destination base) is the compiler's: saved and restored inside the statement.
+static __device__ __forceinline__ void attn_glds16_asm(const void* gsrc, const char* dst) {
+  unsigned keep;
+  const unsigned ldst = __builtin_amdgcn_readfirstlane((unsigned)(__UINTPTR_TYPE__)(attn_lptr_t)dst);
+  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
+               : "=&s"(keep) : "v"(gsrc), "s"(ldst) : "memory");
 }
 template <int HD>
 static __device__ __forceinline__ int v_swz(int row) {
@@ -65,7 +75,7 @@ static __device__ __forceinline__ int k_swz(int row) {
 #ifndef WFL_ATTN_SPLIT_P
 #define WFL_ATTN_SPLIT_P 1   // 0: P stays ONE bf16 value (five MFMA passes instead of six).  Measured (round 4): 1 % of the precision-high step, and the
 #endif                       //   goldens' logits error grows from 0.0004 to 0.003-0.006, held-out raw mismatches from 3-4 to 11 of 96 000, 62 -> 58 identical clips: kept split
-template <int HD, int QT, bool PREFETCH, bool BIAS, bool OUT8 = false, bool SPLIT = false>
+template <int HD, int QT, bool PREFETCH, bool BIAS, bool OUT8 = false, bool SPLIT = false, int NW = 4>
 // (Four waves per SIMD instead of three -- __launch_bounds__(256, 4) -- measured slower twice: 99 us against 90 at 139 registers / 7
 //  spilled, 93 against 91 at 129 registers / 5 spilled: a fourth workgroup per CU adds more LDS and L2 contention than latency hiding.
 //  A software-pipelined loop -- the scores of tile kt + 1 issued before the softmax of tile kt, K staged one tile ahead of V -- was built
@@ -74,10 +84,11 @@ template <int HD, int QT, bool PREFETCH, bool BIAS, bool OUT8 = false, bool SPLI
 //  Round 4: an eight-wave workgroup whose two wave groups alternate between the matrix pipe and the softmax / fragment reads, barriers
 //  between the phases (attention_pp.hip in the history), was built, equal in output, and 17-30 % SLOWER: one wave per SIMD issuing
 //  v_mfma_f32_16x16x32 leaves the other wave 8 of every 16 issue cycles, its softmax needs more -- profiles/round4_attn_pp_dead_end.txt.)
-__global__ __launch_bounds__(256) void attn_kernel(AttnArgs p) {
+__global__ __launch_bounds__(64 * NW) void attn_kernel(AttnArgs p) {
   static_assert(!SPLIT || !OUT8, "split precision: bf16 output");
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  constexpr bool DMA = attn_dma<HD>(PREFETCH);
+  constexpr bool DMA = attn_dma<HD>(PREFETCH, NW);
+  static_assert(NW == 4 || (DMA && !BIAS), "more than four waves: LDS-DMA staging only (no staging registers), no bias table");
   constexpr int VPITCH = DMA ? HD * 2 : HD * 2 + 32;
   constexpr int TILE1 = KT * HD * 2 + KT * VPITCH;          // K tile [KT][HD] (16-byte chunks XOR-swizzled) + V tile [KT][VPITCH]
   constexpr int TILE_BYTES = SPLIT ? 2 * TILE1 : TILE1;     // SPLIT: the low halves' images behind the high ones
@@ -86,7 +97,8 @@ __global__ __launch_bounds__(256) void attn_kernel(AttnArgs p) {
   char* Ks = smem;
   char* Vs = smem + KT * HD * 2;
   constexpr int CPR = HD / 8;
-  constexpr int KCH = KT * CPR / 256;    // K (and V) chunks per thread per tile
+  constexpr int KCH = KT * CPR / (64 * NW);    // K (and V) chunks per thread per tile (register staging)
+  static_assert(DMA || KT * CPR % (64 * NW) == 0, "register staging: the tile's chunks divide evenly among the threads");
   constexpr int KS = HD / 32;            // k-steps over head_dim
   constexpr int DT = HD / 16;            // output channel tiles
 
@@ -95,7 +107,8 @@ __global__ __launch_bounds__(256) void attn_kernel(AttnArgs p) {
   // XCD-aware order: blocks i and i+8 share an XCD (and its L2).  All query blocks of one (clip, head) read the
   // same K / V^T, so give each XCD a contiguous run of logical blocks ordered (clip, head, query block): K/V are
   // then fetched from HBM once per (clip, head) instead of once per XCD (PMC: 419 MB -> algorithmic 74 MB per launch).
-  const int nqb = (p.T + 4 * QT * 16 - 1) / (4 * QT * 16);     // (grid geometry: the batch-wide frame count)
+  constexpr int NQW = NW * QT * 16;                       // queries per workgroup
+  const int nqb = (p.T + NQW - 1) / NQW;                  // (grid geometry: the batch-wide frame count)
   const int nblk = nqb * p.heads * p.B;
   int bid = blockIdx.x;
   {
@@ -108,8 +121,8 @@ __global__ __launch_bounds__(256) void attn_kernel(AttnArgs p) {
   // a batch of clips of different lengths (AttnArgs::clip_T): this block's clip has its own frame count; keys and queries beyond it
   // do not exist -- exactly the clip labelled alone
   const int T = p.clip_T ? p.clip_T[b] : p.T;
-  if (qb * (4 * QT * 16) >= T) return;                          // (block-uniform: before any barrier)
-  const int q0 = qb * (4 * QT * 16) + wid * (QT * 16);
+  if (qb * NQW >= T) return;                              // (block-uniform: before any barrier)
+  const int q0 = qb * NQW + wid * (QT * 16);             // (a wave whose q0 >= T has no query to store; it still stages and arrives at barriers)
   const long row0 = p.lead + (long)b * p.P;
   const bf16_t* Kg = p.QK + p.d + h * HD;                 // + row * ldqk
   const bf16_t* Vg = p.V + h * HD;                        // + row * ldv
@@ -165,7 +178,7 @@ __global__ __launch_bounds__(256) void attn_kernel(AttnArgs p) {
   int koff[KCH], voff[KCH];
 #pragma unroll
   for (int i = 0; i < KCH; ++i) {
-    const int ch = tid + 256 * i;
+    const int ch = tid + 64 * NW * i;
     const int r = ch / CPR, cc = ch % CPR;
     koff[i] = r * (int)p.ldqk + cc * 8;
     voff[i] = r * (int)p.ldv + cc * 8;
@@ -191,7 +204,7 @@ __global__ __launch_bounds__(256) void attn_kernel(AttnArgs p) {
   auto store_tile = [&]() {
 #pragma unroll
     for (int i = 0; i < KCH; ++i) {
-      const int ch = tid + 256 * i;
+      const int ch = tid + 64 * NW * i;
       const int r = ch / CPR, cc = ch % CPR;
       *(bf16x8*)(Ks + r * (HD * 2) + ((cc ^ k_swz<HD>(r)) << 4)) = kreg[i];
       *(bf16x8*)(Vs + r * VPITCH + cc * 16) = vreg[i];
@@ -211,7 +224,7 @@ __global__ __launch_bounds__(256) void attn_kernel(AttnArgs p) {
     }
 #pragma unroll
     for (int i = 0; i < KCH; ++i) {
-      const int ch = tid + 256 * i;
+      const int ch = tid + 64 * NW * i;
       const int r = ch / CPR, cc = ch % CPR;
       *(bf16x8*)(Ks + TILE1 + r * (HD * 2) + ((cc ^ k_swz<HD>(r)) << 4)) = kreg[i];
       *(bf16x8*)(Vs + TILE1 + r * VPITCH + cc * 16) = vreg[i];
@@ -220,41 +233,61 @@ __global__ __launch_bounds__(256) void attn_kernel(AttnArgs p) {
 
   // DMA staging: a wave's instruction j covers 1 KiB of the tile image (rows of HD * 2 bytes); lane l fetches the 16-byte chunk that
   // belongs at its LDS position under the K / V swizzles
-  constexpr int NDI = DMA ? KT * HD * 2 / 1024 / 4 : 1;   // instructions per wave and image
+  // The KT * HD * 2 / 1024 one-KiB pieces of an image are dealt to the first NWI waves, NDI each: all of them where that divides (8 pieces
+  // per wave at four waves and head_dim 256, 4 at eight), else the first eight (twelve waves: waves 8-11 stage nothing, and wait and
+  // arrive at the barriers like the others)
+  constexpr int PIECES = KT * HD * 2 / 1024;
+  constexpr int NWI = PIECES % NW == 0 ? NW : 8;          // waves that issue
+  static_assert(!DMA || (NWI <= NW && PIECES % NWI == 0), "LDS-DMA staging: the image's pieces divide evenly among the issuing waves");
+  constexpr int NDI = DMA ? PIECES / NWI : 1;             // instructions per issuing wave and image
+  // (twelve waves leave 168 registers per lane: the offsets are worked out again for every tile, from a lane number the compiler cannot
+  //  see through, instead of living in 2 * NDI registers across the loop)
+  constexpr bool DOFF_LIVE = NW <= 8;
   int kdoff[NDI], vdoff[NDI];
-  if (DMA) {
+  auto dma_offsets = [&](int ln) {
 #pragma unroll
     for (int j = 0; j < NDI; ++j) {
-      const int byte = (wid * NDI + j) * 1024 + lane * 16;
+      const int byte = (wid * NDI + j) * 1024 + ln * 16;
       const int r = byte / (HD * 2), pos = (byte % (HD * 2)) >> 4;
       kdoff[j] = r * (int)p.ldqk + ((pos ^ k_swz<HD>(r)) << 3);
       vdoff[j] = r * (int)p.ldv + (((((pos >> 1) ^ v_swz<HD>(r)) << 1) | (pos & 1)) << 3);
     }
-  }
+  };
+  if (DMA && DOFF_LIVE) dma_offsets(lane);
+  constexpr bool ASM_DMA = NW > 4 && PREFETCH;           // (attn_glds16_asm above)
+  auto glds = [&](const bf16_t* src, char* to) {
+    if (ASM_DMA) attn_glds16_asm(src, to);
+    else __builtin_amdgcn_global_load_lds((attn_gptr_t)src, (attn_lptr_t)to, 16, 0, 0);
+  };
   auto dma_tile = [&](int kt, int buf) {
+    if (NWI < NW && wid >= NWI) return;                   // (wave-uniform)
+    if (!DOFF_LIVE) {
+      int ln = lane;
+      asm volatile("" : "+v"(ln));
+      dma_offsets(ln);
+    }
     const bf16_t* kb = Kg + (row0 + (long)kt * KT) * p.ldqk;
     const bf16_t* vb = Vg + (row0 + (long)kt * KT) * p.ldv;
     char* dst = smem + buf * TILE_BYTES + wid * NDI * 1024;
 #pragma unroll
     for (int j = 0; j < NDI; ++j) {
-      __builtin_amdgcn_global_load_lds((attn_gptr_t)(kb + kdoff[j]), (attn_lptr_t)(dst + j * 1024), 16, 0, 0);
-      __builtin_amdgcn_global_load_lds((attn_gptr_t)(vb + vdoff[j]), (attn_lptr_t)(dst + KT * HD * 2 + j * 1024), 16, 0, 0);
+      glds(kb + kdoff[j], dst + j * 1024);
+      glds(vb + vdoff[j], dst + KT * HD * 2 + j * 1024);
     }
     if (SPLIT) {
       const bf16_t* kl = Kgl + (row0 + (long)kt * KT) * p.ldqk;
       const bf16_t* vl = Vgl + (row0 + (long)kt * KT) * p.ldv;
 #pragma unroll
       for (int j = 0; j < NDI; ++j) {
-        __builtin_amdgcn_global_load_lds((attn_gptr_t)(kl + kdoff[j]), (attn_lptr_t)(dst + TILE1 + j * 1024), 16, 0, 0);
-        __builtin_amdgcn_global_load_lds((attn_gptr_t)(vl + vdoff[j]), (attn_lptr_t)(dst + TILE1 + KT * HD * 2 + j * 1024), 16, 0, 0);
+        glds(kl + kdoff[j], dst + TILE1 + j * 1024);
+        glds(vl + vdoff[j], dst + TILE1 + KT * HD * 2 + j * 1024);
       }
     }
   };
 
-  // BIAS: the slice of the relative-position table a key tile needs -- offsets key - query for this workgroup's 4 * QT * 16 queries
-  // and the tile's 64 keys, 64 + 4 * QT * 16 - 1 entries -- is staged in LDS one tile ahead (it rides on the tile's barrier); round 1
+  // BIAS: the slice of the relative-position table a key tile needs -- offsets key - query for this workgroup's NQW queries
+  // and the tile's 64 keys, 64 + NQW - 1 entries -- is staged in LDS one tile ahead (it rides on the tile's barrier); round 1
   // gathered every score's entry from global memory inside the loop (the BIAS kernel ran at half the plain kernel's rate)
-  constexpr int NQW = 4 * QT * 16;                       // queries per workgroup
   constexpr int BT = KT + NQW;                           // table entries per tile (one spare)
   float* btab = (float*)(smem + (PREFETCH ? 2 : 1) * TILE_BYTES);   // [2][BT]
   const int qwg0 = qb * NQW;
@@ -535,19 +568,20 @@ __global__ __launch_bounds__(256) void attn_kernel(AttnArgs p) {
   }
 }
 
-template <int HD, int QT, bool PREFETCH, bool BIAS, bool OUT8 = false, bool SPLIT = false>
+template <int HD, int QT, bool PREFETCH, bool BIAS, bool OUT8 = false, bool SPLIT = false, int NW = 4>
 static int launch_attn(const AttnArgs& a, hipStream_t s) {
   static_assert(!BIAS || PREFETCH, "the bias table slice is staged on the prefetch barrier");
-  constexpr int lds = (PREFETCH ? 2 : 1) * (SPLIT ? 2 : 1) * (KT * HD * 2 + KT * (attn_dma<HD>(PREFETCH) ? HD * 2 : HD * 2 + 32)) +
-                      (BIAS ? 2 * (KT + 4 * QT * 16) * 4 : 0);
-  auto k = attn_kernel<HD, QT, PREFETCH, BIAS, OUT8, SPLIT>;
+  constexpr int lds = (PREFETCH ? 2 : 1) * (SPLIT ? 2 : 1) * (KT * HD * 2 + KT * (attn_dma<HD>(PREFETCH, NW) ? HD * 2 : HD * 2 + 32)) +
+                      (BIAS ? 2 * (KT + NW * QT * 16) * 4 : 0);
+  static_assert(lds <= 160 * 1024, "the tile buffers fit a CU's LDS");
+  auto k = attn_kernel<HD, QT, PREFETCH, BIAS, OUT8, SPLIT, NW>;
   static WflOncePerDevice attr_once;
   if (attr_once.need()) {
     if (hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess) return -2;
   }
-  const int qb = 4 * QT * 16;
+  const int qb = NW * QT * 16;
   dim3 grid(((a.T + qb - 1) / qb) * a.heads * a.B);
-  hipLaunchKernelGGL(k, grid, dim3(256), lds, s, a);
+  hipLaunchKernelGGL(k, grid, dim3(64 * NW), lds, s, a);
   return hipGetLastError() == hipSuccess ? 0 : -3;
 }
 
@@ -558,6 +592,13 @@ static int attn_variant() {
   static int v = -1;
   if (v < 0) { const char* e = getenv("WFL_ATTN_VARIANT"); v = e ? atoi(e) : 0; }
   return v;
+}
+
+// WFL_ATTN_WAVES=4 / 8 / 12: waves per workgroup of the head_dim 256 kernel (A/B runs and the tests; read at every launch, so one process
+// can run all of them -- their outputs are bit-identical).  Unset: the default form
+static int attn_waves() {
+  const char* e = getenv("WFL_ATTN_WAVES");
+  return e ? atoi(e) : 0;
 }
 
 int wfl_launch_attention(const AttnArgs& a, hipStream_t s) {
@@ -574,7 +615,10 @@ int wfl_launch_attention(const AttnArgs& a, hipStream_t s) {
     if (!a.bias && hd == 32) return launch_attn<32, 2, true, false, false, true>(a, s);
     if (!a.bias && hd == 64) return launch_attn<64, 2, true, false, false, true>(a, s);
     if (!a.bias && hd == 128) return launch_attn<128, 2, true, false, false, true>(a, s);
-    if (!a.bias && hd == 256) return launch_attn<256, 1, false, false, false, true>(a, s);
+    // head_dim 256: four image tiles = 128 KiB, one buffer, one workgroup per CU either way: eight waves (254 registers, no scratch) share
+    // it -- the precision-high step of cfg2 8.73 -> 8.33 ms (profiles/attn_wide_ab.txt); WFL_ATTN_WAVES=4: the four-wave form (266 registers)
+    if (!a.bias && hd == 256)
+      return attn_waves() == 4 ? launch_attn<256, 1, false, false, false, true>(a, s) : launch_attn<256, 1, false, false, false, true, 8>(a, s);
   }
   if (a.bias) {
     if (!a.gate) return -1;
@@ -595,7 +639,21 @@ int wfl_launch_attention(const AttnArgs& a, hipStream_t s) {
     case 128: return launch_attn<128, 2, true, false>(a, s);
     // head_dim 256, measured at cfg2 size (tools/attn_bench.py): <256, 1, no prefetch> 125 us (two workgroups per CU hide each other's
     // tile loads); <256, 2, prefetch> 166; <256, 2, no prefetch> 168; <256, 1, prefetch> 212 (one workgroup per CU each)
-    case 256: return launch_attn<256, 1, false, false>(a, s);
+    // More waves per workgroup, each wave as it was (NW; two 64 KiB tile buffers filled by LDS-DMA, one workgroup per CU): a staged tile
+    // serves 8 or 12 waves instead of 4, 1.15 GB -> 0.58 / 0.38 GB through L2 -> LDS per launch.  tools/attn_bench.py --waves 4,8,12, one
+    // process, interleaved: 112.1 / 109.1 / 83.8 us at 16 clips (8 waves: 384 workgroups, one and a half rounds; 12: 256, one round),
+    // 415.9 / 352.0 / 325.8 us at 64; in the model 116.0 -> 82.9 us per launch, the step 3.576 -> 3.519 ms (profiles/attn_wide_ab.txt).
+    // Registers 234 / 221 / 168, no scratch (12 waves: the DMA offsets are worked out per tile).  FETCH_SIZE per launch 87 / 87 / 75 MB: it counts
+    // behind L2, where the block order already held the bytes near q, k, v once.  Twelve is the default at this head size whatever the
+    // batch or T; WFL_ATTN_WAVES=4 / 8 select the others, bit-identical.  What bounds it now: each wave still reads the whole tile from LDS
+    // (12 x 64 KiB per tile and CU, ~3 100 LDS cycles beside ~3 200 matrix-pipe cycles).
+    case 256:
+      switch (attn_waves()) {
+        case 4: return launch_attn<256, 1, false, false>(a, s);
+        case 8: return launch_attn<256, 1, true, false, false, false, 8>(a, s);
+        case 0: case 12: return launch_attn<256, 1, true, false, false, false, 12>(a, s);
+      }
+      return -1;
     // head_dim 384 (Whisper-small's Conformer heads): 32 queries per wave with Q in registers (506 VGPRs, one wave per SIMD) halves the
     // K / V tile traffic per query against attention_big's 16: 845 vs 2 635 us at 64 x 1500 frames (tools/attn_bench.py)
     case 384: return attn_variant() == 1 ? wfl_launch_attention_big(a, s) : launch_attn<384, 2, false, false>(a, s);
