@@ -994,6 +994,54 @@ int32_t wfl_decode_duration(const float* logits, int64_t ldl, int32_t C, int32_t
                             const int32_t* sym_dur, const float* dur, int32_t n_rows, int32_t D, float threshold, void* workspace,
                             int64_t workspace_bytes, int32_t* ids, float* score, int32_t* status, void* stream);
 
+/* ---- Posteriors of a duration-prior decode by forward-backward on the GPU (`postprocess.decode_duration_scores`;
+ * wfl-asr_amd/decode.py).  The sum-product counterpart of wfl_decode_duration, as wfl_decode_bigram_posterior is wfl_decode_bigram's: a
+ * semi-Markov forward-backward over the BIO grammar.  Clips, logits, pairs, o_id, trans, sym_dur, dur, n_rows, D, threshold, the
+ * symbols, the states, the legality rule, the forced-to-O rule, the virtual O frame, "any state may end the clip", L_q(d) with its
+ * tail and "the run in progress at the last frame ends there and pays its L" are wfl_decode_duration's; ids (the path
+ * wfl_decode_duration returned for the same clips), logz, post, cls_post and what they mean are wfl_decode_posterior's.  The weight of
+ * a legal path is
+ *     exp(sum_t z[t][c_t] + sum over opened runs trans[previous symbol][opened symbol] + sum over phoneme runs L_q(d)).
+ * With W = exp(trans), W[O][O] = 1, lambda_q(j) = exp(L_q(j)), tau_q = exp(tail_q) (-inf -> exactly 0; all 1 for a phoneme without a
+ * row), e a frame's emissions (e(B) = e(I) = 0 on a forced frame, e(I) = 0 without an I class), everything of frame t - 1 on the right
+ * and end(-1) = (1, 0, ...):
+ *     forward    In_q(t) = sum_s end_s(t-1) W[s][q];    R_q^1(t) = e_t(B-q) In_q(t);    R_q^j(t) = e_t(I-q) R_q^{j-1}(t-1)  2 <= j <= D
+ *                Y_q(t) = e_t(I-q) tau_q (Y_q(t-1) + lambda_q(D) R_q^D(t-1));    end_q(t) = sum_j lambda_q(j) R_q^j(t) + Y_q(t)
+ *                O(t) = e_t(O) sum_s end_s(t-1) W[s][O]   (end_O = O);    Z = sum_s end_s(T-1)
+ *     backward   bE_q(t): the suffix weight after a run of q ends at t; Wr_q^j(t): when t is the j-th frame of a run; V_q(t): inside the
+ *                tail.  At T - 1: bO = bE = V = 1, Wr^j = lambda(j).    u_t[O] = e_t(O) bO(t),  u_t[q] = e_t(B-q) Wr_q^1(t)
+ *                (bO, bE_1 .. bE_P)(t-1) = W u_t;    V_q(t-1) = bE_q(t-1) + e_t(I-q) tau_q V_q(t)
+ *                Wr_q^j(t-1) = lambda_q(j) bE_q(t-1) + e_t(I-q) Wr_q^{j+1}(t)  j < D;    Wr_q^D(t-1) = lambda_q(D) V_q(t-1)
+ * logz[b] = log Z.  For ids[t] in {B-p, I-p}: post[t] = (sum_j R_p^j(t) Wr_p^j(t) + Y_p(t) V_p(t)) / Z, the posterior that frame t
+ * belongs to phoneme p at all; for ids[t] = O: post[t] = O(t) bO(t) / Z.  cls_post[t] is the posterior of the exact class: on a B frame
+ * R^1 Wr^1 / Z (a run opens exactly here), on an I frame the j >= 2 terms plus the tail term, on O post.  0 <= cls_post <= post <= 1.
+ * With every sym_dur = -1, or an all-zero table, every output equals wfl_decode_bigram_posterior's.
+ * status[b]: 0 ok; 2 C above 1024 or N above WFL_DECODE_BIGRAM_MAX_SYMBOLS (whatever D); 4 a bad class table, or a sym_dur outside
+ * -1 .. n_rows - 1; 8 ids is not a path of this grammar: wfl_decode_bigram_posterior's cases, or a phoneme run of ids whose length has
+ * L = -inf, the run the clip ends in included (wfl_decode_duration never returns such a path).  A clip with status != 0 gets logz = 0
+ * and post = cls_post = 0; T = 0 is ok, logz 0, and writes nothing per frame.  Host-side errors (negative return) are
+ * wfl_decode_duration's and wfl_decode_bigram_posterior's.
+ * One workgroup per clip: a clip scored alone equals the same clip inside any batch, bit for bit.  Scaled linear-domain fp32 states,
+ * every frame rescaled by a power of two taken from the largest value alive in the previous frame -- the states, the tail states and
+ * every entry of the run history, not the states alone: under a hard minimum a history entry does not show in the states for D - 1
+ * frames -- the exponents summed in integers; the posteriors are sums of non-negative products added in double.  Guards: an O emission
+ * counts as at least 2^-60 of its frame's largest, finite entries of trans, and finite lambda and tau, are clamped to +-60 ln 2; no
+ * intermediate is inf or NaN whatever the logits, the tables and the clip's length.  What is below 2^-122 of its frame's largest alive
+ * value underflows and is reported as 0.
+ * Workspace, per clip with T > 0, in 4-byte words: round_up_64(T (D + 2)) + round_up_64(T) + H + 2 round_up_64(T)  (per frame the run
+ * history, the tail state and the scale exponent of the path's own symbol; the path's (pair, kind); H; the row maxima; the forced
+ * flags).  H holds the run history and the symbols' rows of dur where one CU's LDS does not hold them beside the trans table: with
+ * HS = round_up_64(N), H = 0 when
+ *     16 ceil(4 N (N | 1) / 16) + 6912 + 4 (2 D + 1) HS <= 163840 - 4608
+ * (every D at N <= 159; at the cap of 192 symbols D <= 2), else H = round_up_64((2 D + 1) HS).  0 above the symbol cap;
+ * wfl_decode_duration_posterior_workspace_bytes returns -1 for D outside 1 .. 32. */
+int64_t wfl_decode_duration_posterior_workspace_bytes(const int32_t* n_frames_host, int32_t n_clips, int32_t n_pairs, int32_t D);
+int32_t wfl_decode_duration_posterior(const float* logits, int64_t ldl, int32_t C, int32_t o_id, const int64_t* frame_off_host,
+                                      const int32_t* n_frames_host, int32_t n_clips, const int32_t* pairs, int32_t n_pairs,
+                                      const float* trans, const int32_t* sym_dur, const float* dur, int32_t n_rows, int32_t D,
+                                      float threshold, const int32_t* ids, void* workspace, int64_t workspace_bytes, float* logz,
+                                      float* post, float* cls_post, int32_t* status, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -2,7 +2,9 @@
 // (csrc/decode_bigram_posterior.hip, the posteriors of a path; its header comment is the definition of the recurrences, the guards and
 // the scaling) and bigram_counts_chain_kernel (csrc/decode_bigram_counts.hip, the expected successions).  A guard, a scale rule or a
 // forced-frame rule changed here is changed for both.  The grammar, the pre-pass, the logZ tail and the host driver are
-// csrc/bio_grammar.h's.
+// csrc/bio_grammar.h's.  duration_post_chain_kernel (csrc/decode_duration_posterior.hip, the posteriors under a duration prior) uses
+// Chain's carve-up, stage, own, load_group / to_emissions, exchange / summed, unscale and wave_largest as they are and writes its own
+// two frames: its owner carries a run history, and its scale is taken from everything alive in the owners, not from end[] alone.
 //
 // Pieces, in the order a kernel uses them:
 //   the workgroup's shape (also that of csrc/decode_bigram.hip, the max-product search, which takes the four constants from here and

@@ -3,7 +3,8 @@
 // (csrc/decode_posterior.hip, the sum-product sweeps under the flat penalty) and wfl_decode_bigram_posterior
 // (csrc/decode_bigram_posterior.hip, the sum-product sweeps under the table); wfl_decode_bigram_counts (csrc/decode_bigram_counts.hip, the
 // same sweeps summed into expected successions) is the fifth; wfl_decode_duration (csrc/decode_duration.hip, the bigram search with a
-// duration prior per phoneme) uses the same pieces as they are -- defined ONCE: a change made here reaches all of them, so a
+// duration prior per phoneme) and wfl_decode_duration_posterior (csrc/decode_duration_posterior.hip, the sum-product sweeps under that
+// prior) use the same pieces as they are -- defined ONCE: a change made here reaches all of them, so a
 // posterior always scores the grammar and the forced frames its search ran on.  A .hip file keeps its chain kernel, the head of its workspace and its
 // own fields of the launch struct; everything else of an entry is here, but for what only some entries share: the path posteriors'
 // csrc/path_posterior.h and the bigram sum-product chain's csrc/bigram_sumproduct.h.

@@ -1,7 +1,9 @@
 // What the two entries that score a decoded path share -- wfl_decode_posterior (csrc/decode_posterior.hip) and
 // wfl_decode_bigram_posterior (csrc/decode_bigram_posterior.hip) -- defined ONCE: the launch fields of the path and its outputs, the head
 // of a clip's workspace, the per-frame part of the check that ids is a path, the alpha records read back a group ahead, and gamma of the
-// path's class from a record and the owner's beta.  Included by those two files only; the sweeps are each file's own.
+// path's class from a record and the owner's beta.  The sweeps are each file's own.  wfl_decode_duration_posterior
+// (csrc/decode_duration_posterior.hip) takes the launch fields, path_step_bad and path_pointer_missing from here; its records, its
+// workspace head and its gamma are its own (a record there is a ring column, not two states).
 #pragma once
 #include "bio_grammar.h"
 

@@ -17,6 +17,8 @@ follows `B-p` or `I-p`, and every run that is opened costs `switch_penalty` nats
                       the posterior of the phoneme and of the exact class the path chose (`postprocess.decode_scores`)
   decode_posteriors_bigram  the same over the grammar of bio_viterbi_bigram, the table included (csrc/decode_bigram_posterior.hip,
                       `wfl_decode_bigram_posterior`; `postprocess.bigram_scores`)
+  decode_posteriors_duration  the same over the explicit-duration grammar of bio_viterbi_duration, the table and the duration prior
+                      included (csrc/decode_duration_posterior.hip, `wfl_decode_duration_posterior`; `postprocess.decode_duration_scores`)
   bigram_expected_counts  the expected successions of a batch of clips under bio_viterbi_bigram's path distribution, one [N, N] table
                       per clip (csrc/decode_bigram_counts.hip, `wfl_decode_bigram_counts`): the E-step of adapt_bigram.py
   path_segments_free  the path's ids of a file, chunk by chunk, -> segments; a run that crosses a chunk seam is one segment
@@ -39,7 +41,7 @@ from .options import DECODE_MODES  # noqa: F401  (decode.DECODE_MODES stays impo
 MAX_CLASSES = 1024         # wfl_decode's class cap (status 2 above it)
 MAX_BIGRAM_SYMBOLS = 192   # wfl_decode_bigram's symbol cap, O + 191 phonemes (WFL_DECODE_BIGRAM_MAX_SYMBOLS; status 2 above it)
 STATUS_OK, STATUS_OVER_CAP, STATUS_BAD_CLASS = 0, 2, 4
-STATUS_NOT_A_PATH = 8      # the two posterior entries alone: `ids` is not a path of the grammar
+STATUS_NOT_A_PATH = 8      # the posterior entries alone: `ids` is not a path of the grammar
 
 
 class ClassTable(NamedTuple):
@@ -90,6 +92,10 @@ def bigram_counts_workspace_bytes(n_frames, n_pairs) -> int:
 
 def duration_workspace_bytes(n_frames, n_pairs, D) -> int:
     return _workspace_bytes("wfl_decode_duration_workspace_bytes", n_frames, n_pairs, int(D))
+
+
+def duration_posterior_workspace_bytes(n_frames, n_pairs, D) -> int:
+    return _workspace_bytes("wfl_decode_duration_posterior_workspace_bytes", n_frames, n_pairs, int(D))
 
 
 def _check_clips(logits, n_frames, table, switch_penalty, threshold, frame_offsets):
@@ -293,8 +299,8 @@ def decode_posteriors(logits, n_frames, table, switch_penalty, threshold, ids, f
     return _posteriors("wfl_decode_posterior", logits, clips, (float(switch_penalty), float(threshold)), ids, stream)
 
 
-def _posteriors(entry, logits, clips, middle, ids, stream):
-    """What the two posterior entries share after their own checks: the check of `ids`, the outputs and the call."""
+def _posteriors(entry, logits, clips, middle, ids, stream, ws_more=()):
+    """What the posterior entries share after their own checks: the check of `ids`, the outputs and the call.  ws_more: _call's."""
     dev = logits.device
     if not isinstance(ids, torch.Tensor) or not ids.is_cuda or ids.device != dev or ids.dtype != torch.int32 or ids.dim() != 1 \
             or (ids.numel() and ids.stride(0) != 1) or ids.shape[0] != logits.shape[0]:
@@ -303,7 +309,7 @@ def _posteriors(entry, logits, clips, middle, ids, stream):
     per_frame = torch.empty((2, max(rows, 1)), dtype=torch.float32, device=dev)
     logz = torch.empty(max(nb, 1), dtype=torch.float32, device=dev)
     status = torch.empty(max(nb, 1), dtype=torch.int32, device=dev)
-    _call(entry, logits, clips, (*middle, ids), (logz, per_frame[0], per_frame[1], status), stream)
+    _call(entry, logits, clips, (*middle, ids), (logz, per_frame[0], per_frame[1], status), stream, ws_more=ws_more)
     return logz[:nb], per_frame[0, :rows], per_frame[1, :rows], status[:nb]
 
 
@@ -318,6 +324,28 @@ def decode_posteriors_bigram(logits, n_frames, table, trans, threshold, ids, fra
     clips = _check_clips(logits, n_frames, table, 0.0, threshold, frame_offsets)
     w = check_transitions(trans, len(clips[1]))
     return _posteriors("wfl_decode_bigram_posterior", logits, clips, (w, float(threshold)), ids, stream)
+
+
+def decode_posteriors_duration(logits, n_frames, table, trans, dur, sym_dur, threshold, ids, frame_offsets=None, stream=None):
+    """Forward-backward over the explicit-duration grammar of bio_viterbi_duration, for the same ragged batch of clips (same
+    arguments), given its `ids`: decode_posteriors_bigram with the duration table `dur` (check_duration_table) and the phonemes' rows
+    `sym_dur` (check_symbol_rows) beside the table `trans` (csrc/decode_duration_posterior.hip, `wfl_decode_duration_posterior`).
+
+    -> (logz [clips], post [rows], cls_post [rows], status [clips]) as decode_posteriors; logz is the log of the summed weight
+    exp(sum of the logits on the path + sum of trans over the runs opened + sum of L(d) over the phoneme runs) of every legal path.
+    post: the posterior that the frame belongs to the path's phoneme at all; cls_post on a run's first frame: that a run opens exactly
+    there.  A clip with status != 0 gets zeros (STATUS_OVER_CAP also above MAX_BIGRAM_SYMBOLS; STATUS_NOT_A_PATH also for a run
+    opened through a -inf entry of `trans` and for a run whose length has L = -inf).  With every sym_dur = -1, or an all-zero `dur`,
+    the results are decode_posteriors_bigram's."""
+    clips = _check_clips(logits, n_frames, table, 0.0, threshold, frame_offsets)
+    w = check_transitions(trans, len(clips[1]))
+    d = check_duration_table(dur)
+    r = check_symbol_rows(sym_dur, len(clips[1]), d.shape[0])
+    D = d.shape[1] - 1
+    r_up = r if r.size else np.full(1, -1, np.int32)
+    d_up = d if d.size else np.zeros((1, D + 1), np.float32)
+    return _posteriors("wfl_decode_duration_posterior", logits, clips, (w, r_up, d_up, int(d.shape[0]), D, float(threshold)), ids, stream,
+                       ws_more=(D,))
 
 
 def bigram_expected_counts(logits, n_frames, table, trans, threshold, frame_offsets=None, stream=None):

@@ -454,9 +454,9 @@ class Labeler:
                     draft_tolerance=None, align_edits=None, align_insertions=None, min_duration=None, duration_scores=None,
                     optional_tokens=None, skip_penalty=None, optional_scores=None, filler_token=None, filler_penalty=None,
                     filler_scores=None, duration_prior=None, duration_prior_weight=None, duration_prior_scores=None,
-                    decode_duration_prior=None, decode_duration_prior_weight=None, bigram_scores=None):
+                    decode_duration_prior=None, decode_duration_prior_weight=None, decode_duration_scores=None, bigram_scores=None):
         """-> list (per file) of [(start_s, end_s, phoneme)] after merge + forced alignment; with align_scores, duration_scores,
-        decode_scores or bigram_scores, (that list, scores); with align_edits the tuple goes on with one more list, edits, and with
+        decode_scores, bigram_scores or decode_duration_scores, (that list, scores); with align_edits the tuple goes on with one more list, edits, and with
         align_insertions it ends with one more, insertions; with optional_tokens it ends with the list skipped; with a filler_token
         it ends with the list fillers, and with filler_scores with one more, filler_scores; with duration_prior_scores it ends with the
         list durations.
@@ -581,8 +581,14 @@ class Labeler:
         times the log probability the prior gives d frames of the phoneme's output name; a phoneme the prior does not hold has none, and
         O runs carry none.  Opened runs cost what they cost without the prior: the phoneme_bigram's table where one is given, else the
         flat switch penalty.  A file's chunks are one clip, so a run that crosses a chunk seam is one run and pays one prior.  The
-        file is checked as a duration_prior is; decode_scores and bigram_scores beside it are refused.  `duration_prior` keeps meaning
-        the transcript alignment's prior."""
+        file is checked as a duration_prior is; decode_scores and bigram_scores beside it are refused: decode_duration_scores is their
+        counterpart there.  `duration_prior` keeps meaning the transcript alignment's prior.
+
+        decode_duration_scores (with a decode_duration_prior only; None: config postprocess.decode_duration_scores, else off):
+        decode_scores for a duration-prior decode -- the same scores[i] records, from a semi-Markov forward-backward pass over the
+        grammar with the search's transition table and duration table (decode.decode_posteriors_duration,
+        wfl_decode_duration_posterior), so the posterior scores the grammar the search ran on.  The segments are the same with and
+        without."""
         opts = self.options(align=align, align_scores=align_scores, decode=decode, switch_penalty=switch_penalty,
                             decode_scores=decode_scores, phoneme_bigram=phoneme_bigram, bigram_weight=bigram_weight,
                             bigram_scores=bigram_scores, align_draft=align_draft, draft_tolerance=draft_tolerance,
@@ -591,7 +597,7 @@ class Labeler:
                             optional_scores=optional_scores, filler_token=filler_token, filler_penalty=filler_penalty,
                             filler_scores=filler_scores, duration_prior=duration_prior, duration_prior_weight=duration_prior_weight,
                             duration_prior_scores=duration_prior_scores, decode_duration_prior=decode_duration_prior,
-                            decode_duration_prior_weight=decode_duration_prior_weight)
+                            decode_duration_prior_weight=decode_duration_prior_weight, decode_duration_scores=decode_duration_scores)
         reports = R.Reports.for_options(opts)
         final, scores = self._label_scored(audio_paths, opts, lang_id, confidence_threshold, verbose, reports)
         out = (final, scores) if opts.scored else (final,)
@@ -837,10 +843,11 @@ class Labeler:
         search covers the whole file and a run may cross a chunk seam; the files of a wave go to wfl_decode as one ragged batch and
         only ids / status come back to the host.  A file whose status is not 0 is left out (with a message): the caller decodes it
         by argmax.  want_scores: right after the search, one wfl_decode_posterior call per wave over the clips it decoded (same
-        logits, the device `ids`; wfl_decode_bigram_posterior with the same table when the search was the bigram's) and one log-sum-exp reduction over the wave's logits, the per-frame arrays back in one more copy; without, the second dict stays empty and the calls are
+        logits, the device `ids`; wfl_decode_bigram_posterior with the same table when the search was the bigram's,
+        wfl_decode_duration_posterior with the same tables when it was the duration prior's) and one log-sum-exp reduction over the wave's logits, the per-frame arrays back in one more copy; without, the second dict stays empty and the calls are
         the search's alone.  trans: the transition table of a phoneme bigram (_bigram_table); the search is then wfl_decode_bigram's,
         everything around it the same.  free_prior: _decode_duration_prior's triple; the search is then wfl_decode_duration's under its
-        table (never with want_scores: options.DECODE_DURATION_PRIOR_ERROR)."""
+        tables."""
         lang_name = self._lang_name(lang_id)
         remap, names = self._names_for(lang_name)
         if self._decode_table is None:
@@ -865,7 +872,10 @@ class Labeler:
             raw = {}                                          # clip -> (score, logz, sum lse, post, cls_post, posterior status)
             ok = [b for b in range(len(sel)) if st_all[b] == DC.STATUS_OK]
             if want_scores and ok:
-                if trans is None:
+                if free_prior is not None:
+                    d_logz, d_post, d_cls, d_pst = DC.decode_posteriors_duration(lg, [frames[b] for b in ok], table, *free_prior, threshold,
+                                                                                 d_ids, frame_offsets=f0[ok])
+                elif trans is None:
                     d_logz, d_post, d_cls, d_pst = DC.decode_posteriors(lg, [frames[b] for b in ok], table, switch_penalty, threshold,
                                                                         d_ids, frame_offsets=f0[ok])
                 else:
@@ -892,7 +902,8 @@ class Labeler:
                         scored[fi] = DC.free_score(*raw[b][:5], ids_all[pos:pos + n], *plan, self._table, frame_duration,
                                                    names=[names[int(r)] for r in remap[:len(self._table.names)]])
                     elif want_scores:                         # (the posterior entry refused the path the search gave it)
-                        fn = "wfl_decode_posterior" if trans is None else "wfl_decode_bigram_posterior"
+                        fn = ("wfl_decode_duration_posterior" if free_prior is not None
+                              else ("wfl_decode_posterior" if trans is None else "wfl_decode_bigram_posterior"))
                         print(f"{audio_paths[fi]}: no decode scores ({fn} status {raw[b][5] if b in raw else None})")
                 pos += n
         return out, scored
@@ -1610,7 +1621,8 @@ def infer_audio(audio_path, config_path="config.yaml", checkpoint_path="best_mod
                 align_draft=None, draft_tolerance=None, align_edits=None, align_insertions=None, min_duration=None,
                 duration_scores=None, optional_tokens=None, skip_penalty=None, optional_scores=None, filler_token=None,
                 filler_penalty=None, filler_scores=None, duration_prior=None, duration_prior_weight=None,
-                duration_prior_scores=None, decode_duration_prior=None, decode_duration_prior_weight=None, bigram_scores=None):
+                duration_prior_scores=None, decode_duration_prior=None, decode_duration_prior_weight=None,
+                decode_duration_scores=None, bigram_scores=None):
     """align: "greedy" | "viterbi" | None (config postprocess.align, else greedy): how a `{audio}.txt` transcript is aligned
     (Labeler.label_files).  align_scores (viterbi only; None: config postprocess.align_scores): also write `{stem}.scores.tsv`
     beside the .lab when the file was Viterbi-aligned (format_scores_tsv).  decode: "argmax" | "viterbi" | None (config
@@ -1650,7 +1662,9 @@ def infer_audio(audio_path, config_path="config.yaml", checkpoint_path="best_mod
     (align.duration_prior_posteriors, reports.REPORTS["durations"]); the .lab is what it is without it.  decode_duration_prior /
     decode_duration_prior_weight (decode viterbi only; None: config postprocess.decode_duration_prior /
     postprocess.decode_duration_prior_weight): the phoneme duration prior of the FREE decode's explicit-duration search and what its log
-    probabilities are multiplied by (Labeler.label_files)."""
+    probabilities are multiplied by (Labeler.label_files).  decode_duration_scores (with a decode_duration_prior only; None: config
+    postprocess.decode_duration_scores): decode_scores for the duration-prior decode -- the same `{stem}.decode_scores.tsv`, from
+    decode.decode_posteriors_duration over the explicit-duration grammar of that search."""
     given = dict(align=align, align_scores=align_scores, decode=decode, switch_penalty=switch_penalty, decode_scores=decode_scores,
                  phoneme_bigram=phoneme_bigram, bigram_weight=bigram_weight, bigram_scores=bigram_scores, align_draft=align_draft,
                  draft_tolerance=draft_tolerance, align_edits=align_edits, align_insertions=align_insertions, min_duration=min_duration,
@@ -1658,7 +1672,7 @@ def infer_audio(audio_path, config_path="config.yaml", checkpoint_path="best_mod
                  optional_scores=optional_scores, filler_token=filler_token, filler_penalty=filler_penalty,
                  filler_scores=filler_scores, duration_prior=duration_prior, duration_prior_weight=duration_prior_weight,
                  duration_prior_scores=duration_prior_scores, decode_duration_prior=decode_duration_prior,
-                 decode_duration_prior_weight=decode_duration_prior_weight)
+                 decode_duration_prior_weight=decode_duration_prior_weight, decode_duration_scores=decode_duration_scores)
     _refuse_before_load(config_path, **given)
     lab = _labeler(config_path, checkpoint_path, device)
     opts = lab.options(**given)
@@ -1681,7 +1695,7 @@ def infer_folder(folder_path: str, config_path: str = "config.yaml", checkpoint_
                  align_edits=None, align_insertions=None, min_duration=None, duration_scores=None, optional_tokens=None,
                  skip_penalty=None, optional_scores=None, filler_token=None, filler_penalty=None, filler_scores=None,
                  duration_prior=None, duration_prior_weight=None, duration_prior_scores=None,
-                 decode_duration_prior=None, decode_duration_prior_weight=None, bigram_scores=None):
+                 decode_duration_prior=None, decode_duration_prior_weight=None, decode_duration_scores=None, bigram_scores=None):
     given = dict(align=align, align_scores=align_scores, decode=decode, switch_penalty=switch_penalty, decode_scores=decode_scores,
                  phoneme_bigram=phoneme_bigram, bigram_weight=bigram_weight, bigram_scores=bigram_scores, align_draft=align_draft,
                  draft_tolerance=draft_tolerance, align_edits=align_edits, align_insertions=align_insertions, min_duration=min_duration,
@@ -1689,7 +1703,7 @@ def infer_folder(folder_path: str, config_path: str = "config.yaml", checkpoint_
                  optional_scores=optional_scores, filler_token=filler_token, filler_penalty=filler_penalty,
                  filler_scores=filler_scores, duration_prior=duration_prior, duration_prior_weight=duration_prior_weight,
                  duration_prior_scores=duration_prior_scores, decode_duration_prior=decode_duration_prior,
-                 decode_duration_prior_weight=decode_duration_prior_weight)
+                 decode_duration_prior_weight=decode_duration_prior_weight, decode_duration_scores=decode_duration_scores)
     _refuse_before_load(config_path, **given)
     wav_files = sorted(f for f in os.listdir(folder_path) if f.lower().endswith(".wav"))
     os.makedirs(output_dir, exist_ok=True)
@@ -1855,11 +1869,15 @@ def main(argv=None):
     @click.option("--decode-duration-prior-weight", "decode_duration_prior_weight", type=float, default=None,
                   help="With --decode-duration-prior: what the prior's log probabilities are multiplied by (>= 0). Default: config "
                        "postprocess.decode_duration_prior_weight, else 1.0 (a value to start from, not a measured optimum).")
+    @click.option("--decode-duration-scores", "decode_duration_scores", is_flag=True, default=None,
+                  help="With --decode-duration-prior: --decode-scores for the duration-prior decode; the same {stem}.decode_scores.tsv "
+                       "and decode_scores.tsv, from a semi-Markov forward-backward pass over the grammar with the search's tables on "
+                       "the GPU. Default: config postprocess.decode_duration_scores, else off.")
     def cli(path, checkpoint, config, output, lang_id, sample, top_k, top_p, temperature, device, confidence_threshold, align,
             align_scores, decode, switch_penalty, decode_scores, phoneme_bigram, bigram_weight, bigram_scores, align_draft,
             draft_tolerance, align_edits, align_insertions, min_duration, duration_scores, optional_tokens, skip_penalty,
             optional_scores, filler_token, filler_penalty, filler_scores, duration_prior, duration_prior_weight,
-            duration_prior_scores, decode_duration_prior, decode_duration_prior_weight):
+            duration_prior_scores, decode_duration_prior, decode_duration_prior_weight, decode_duration_scores):
         if switch_penalty is not None and not switch_penalty >= 0.0:
             raise click.UsageError("--switch-penalty must be >= 0 (nats)")
         if sample:
@@ -1898,7 +1916,8 @@ def main(argv=None):
                            filler_token=filler_token, filler_penalty=filler_penalty, filler_scores=filler_scores,
                            duration_prior=duration_prior, duration_prior_weight=duration_prior_weight,
                            duration_prior_scores=duration_prior_scores, decode_duration_prior=decode_duration_prior,
-                           decode_duration_prior_weight=decode_duration_prior_weight)
+                           decode_duration_prior_weight=decode_duration_prior_weight,
+                           decode_duration_scores=decode_duration_scores)
         except ValueError as err:
             raise click.UsageError(str(err))
         output_path = inf_path if output == "." else output
@@ -1929,7 +1948,8 @@ def main(argv=None):
                   duration_prior_weight=opts.duration_prior_weight if opts.duration_prior else None,
                   duration_prior_scores=opts.duration_prior_scores,
                   decode_duration_prior=opts.decode_duration_prior or "",
-                  decode_duration_prior_weight=opts.decode_duration_prior_weight if opts.decode_duration_prior else None)
+                  decode_duration_prior_weight=opts.decode_duration_prior_weight if opts.decode_duration_prior else None,
+                  decode_duration_scores=opts.decode_duration_scores)
         if inf_path.is_dir():
             infer_folder(folder_path=str(inf_path), output_dir=str(output_path), **kw)
         else:

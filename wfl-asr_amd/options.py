@@ -77,6 +77,11 @@ infer_folder (before any model is loaded) and the CLI all call `resolve` and car
                                (DECODE_DURATION_PRIOR_ERROR): their sweeps carry no duration term, and a posterior must score the
                                grammar its search ran on
                            (46. with the model known, Labeler.label_files: durations.check, as rule 39)
+  decode_duration_scores off 47. a bool (true / false; no number, no string)
+                           48. needs decode viterbi
+                           49. needs a decode_duration_prior (it scores the explicit-duration grammar of that search,
+                               wfl_decode_duration_posterior: the same records as decode_scores; without a prior decode_scores, or
+                               bigram_scores beside a phoneme_bigram, is the option to ask for)
 """
 from __future__ import annotations
 
@@ -127,8 +132,14 @@ DURATION_PRIOR_SCORES_ERROR = ("duration_prior_scores needs a duration_prior (po
 
 
 DECODE_DURATION_PRIOR_ERROR = ("decode_duration_prior cannot be combined with decode_scores or bigram_scores: their forward-backward "
-                               "sweeps carry no duration term, and a posterior must score the grammar the search ran on; drop "
-                               "postprocess.decode_duration_prior (--decode-duration-prior) for the scoring run")
+                               "sweeps carry no duration term, and a posterior must score the grammar the search ran on; ask for "
+                               "decode_duration_scores (postprocess.decode_duration_scores, --decode-duration-scores) instead, which "
+                               "scores the explicit-duration grammar of that search")
+
+
+DECODE_DURATION_SCORES_ERROR = ("decode_duration_scores needs a decode_duration_prior (postprocess.decode_duration_prior, "
+                                "--decode-duration-prior): it scores the explicit-duration grammar of that search; without a prior "
+                                "decode_scores (or bigram_scores beside a phoneme_bigram) is the option to ask for")
 
 
 def _filler_token(given):
@@ -251,7 +262,8 @@ class PostOptions(_SearchOptions):
         duration_prior_weight  1.0  what the prior's log probabilities are multiplied by (also stands for "not given")
         duration_prior_scores  False  score every alignment searched under a duration_prior, over the explicit-duration lattice
         decode_duration_prior  None  path of a phoneme_durations.json: the duration prior of the free decode (decode viterbi)
-        decode_duration_prior_weight  1.0  what that prior's log probabilities are multiplied by (also stands for "not given")"""
+        decode_duration_prior_weight  1.0  what that prior's log probabilities are multiplied by (also stands for "not given")
+        decode_duration_scores  False  score every file decoded under a decode_duration_prior, over the explicit-duration grammar"""
     align_draft: Optional[str] = None
     draft_tolerance: float = DEFAULT_DRAFT_TOLERANCE
     align_edits: bool = False
@@ -269,12 +281,13 @@ class PostOptions(_SearchOptions):
     duration_prior_scores: bool = False
     decode_duration_prior: Optional[str] = None
     decode_duration_prior_weight: float = DEFAULT_DURATION_PRIOR_WEIGHT
+    decode_duration_scores: bool = False
 
     def __new__(cls, *args, align_draft=None, draft_tolerance=DEFAULT_DRAFT_TOLERANCE, align_edits=False, align_insertions=False,
                 min_duration=None, duration_scores=False, optional_tokens=None, skip_penalty=0.0, optional_scores=False,
                 filler_token=None, filler_penalty=DEFAULT_FILLER_PENALTY, filler_scores=False, duration_prior=None,
                 duration_prior_weight=DEFAULT_DURATION_PRIOR_WEIGHT, duration_prior_scores=False, decode_duration_prior=None,
-                decode_duration_prior_weight=DEFAULT_DURATION_PRIOR_WEIGHT, **kw):
+                decode_duration_prior_weight=DEFAULT_DURATION_PRIOR_WEIGHT, decode_duration_scores=False, **kw):
         self = super().__new__(cls, *args, **kw)
         object.__setattr__(self, "align_draft", align_draft)
         object.__setattr__(self, "draft_tolerance", draft_tolerance)
@@ -293,6 +306,7 @@ class PostOptions(_SearchOptions):
         object.__setattr__(self, "duration_prior_scores", duration_prior_scores)
         object.__setattr__(self, "decode_duration_prior", decode_duration_prior)
         object.__setattr__(self, "decode_duration_prior_weight", decode_duration_prior_weight)
+        object.__setattr__(self, "decode_duration_scores", decode_duration_scores)
         return self
 
     def __setattr__(self, name, value):
@@ -300,13 +314,18 @@ class PostOptions(_SearchOptions):
 
     _KEYWORD = ("align_draft", "draft_tolerance", "align_edits", "align_insertions", "min_duration", "duration_scores",
                 "optional_tokens", "skip_penalty", "duration_prior", "duration_prior_weight", "decode_duration_prior",
-                "decode_duration_prior_weight", "filler_scores", "duration_prior_scores", "optional_scores", "filler_token", "filler_penalty")
+                "decode_duration_prior_weight", "decode_duration_scores", "filler_scores", "duration_prior_scores", "optional_scores", "filler_token", "filler_penalty")
     # (the later options stand in front of optional_scores: the record's last fields are the filler's own two)
     _KEYWORD_DEFAULTS = (None, DEFAULT_DRAFT_TOLERANCE, False, False, None, False, None, 0.0, None, DEFAULT_DURATION_PRIOR_WEIGHT,
-                         None, DEFAULT_DURATION_PRIOR_WEIGHT, False, False, False, None, DEFAULT_FILLER_PENALTY)
+                         None, DEFAULT_DURATION_PRIOR_WEIGHT, False, False, False, False, None, DEFAULT_FILLER_PENALTY)
 
     def _draft(self):
         return self.align_draft, self.draft_tolerance
+
+    @property
+    def free_scores(self) -> bool:
+        """Scores of the grammar search's path are asked for, of any of the three kinds."""
+        return self.decode_scores or self.bigram_scores or self.decode_duration_scores
 
     @property
     def scored(self) -> bool:
@@ -322,14 +341,14 @@ class PostOptions(_SearchOptions):
               min_duration=None, duration_scores=False, optional_tokens=None, skip_penalty=0.0, optional_scores=False,
               filler_token=None, filler_penalty=DEFAULT_FILLER_PENALTY, filler_scores=False, duration_prior=None,
               duration_prior_weight=DEFAULT_DURATION_PRIOR_WEIGHT, duration_prior_scores=False, decode_duration_prior=None,
-              decode_duration_prior_weight=DEFAULT_DURATION_PRIOR_WEIGHT):
+              decode_duration_prior_weight=DEFAULT_DURATION_PRIOR_WEIGHT, decode_duration_scores=False):
         return cls(*iterable, align_draft=align_draft, draft_tolerance=draft_tolerance, align_edits=align_edits,
                    align_insertions=align_insertions, min_duration=min_duration, duration_scores=duration_scores,
                    optional_tokens=optional_tokens, skip_penalty=skip_penalty, optional_scores=optional_scores,
                    filler_token=filler_token, filler_penalty=filler_penalty, filler_scores=filler_scores,
                    duration_prior=duration_prior, duration_prior_weight=duration_prior_weight,
                    duration_prior_scores=duration_prior_scores, decode_duration_prior=decode_duration_prior,
-                   decode_duration_prior_weight=decode_duration_prior_weight)
+                   decode_duration_prior_weight=decode_duration_prior_weight, decode_duration_scores=decode_duration_scores)
 
     def _replace(self, **kw):
         later = {k: kw.pop(k, getattr(self, k)) for k in self._KEYWORD}
@@ -364,7 +383,8 @@ def _number_ge0(x):
 
 
 def resolve(post, *, align=None, align_scores=None, decode=None, switch_penalty=None, decode_scores=None, phoneme_bigram=None,
-            bigram_weight=None, bigram_scores=None, decode_duration_prior=None, decode_duration_prior_weight=None, align_draft=None, draft_tolerance=None, align_edits=None,
+            bigram_weight=None, bigram_scores=None, decode_duration_prior=None, decode_duration_prior_weight=None, decode_duration_scores=None,
+            align_draft=None, draft_tolerance=None, align_edits=None,
             align_insertions=None, min_duration=None, duration_scores=None, optional_tokens=None, skip_penalty=None,
             optional_scores=None, filler_token=None, filler_penalty=None, filler_scores=None, duration_prior=None,
             duration_prior_weight=None, duration_prior_scores=None) -> PostOptions:
@@ -513,6 +533,14 @@ def resolve(post, *, align=None, align_scores=None, decode=None, switch_penalty=
                          "prior")
     if decode_duration_prior and (decode_scores or bigram_scores):
         raise ValueError(DECODE_DURATION_PRIOR_ERROR)
+    decode_duration_scores = pick("decode_duration_scores", decode_duration_scores, False)
+    if not isinstance(decode_duration_scores, bool):
+        raise ValueError(f"decode_duration_scores must be true or false, got {decode_duration_scores!r}")
+    if decode_duration_scores and decode != "viterbi":
+        raise ValueError("decode_duration_scores needs decode='viterbi' (postprocess.decode: viterbi) and a decode_duration_prior: the "
+                         "argmax decode has no lattice to score")
+    if decode_duration_scores and not decode_duration_prior:
+        raise ValueError(DECODE_DURATION_SCORES_ERROR)
     return PostOptions(align, align_scores, decode, switch_penalty, decode_scores, phoneme_bigram, bigram_weight, bigram_scores,
                        align_draft=align_draft, draft_tolerance=draft_tolerance, align_edits=align_edits,
                        align_insertions=align_insertions, min_duration=min_duration, duration_scores=duration_scores,
@@ -520,4 +548,4 @@ def resolve(post, *, align=None, align_scores=None, decode=None, switch_penalty=
                        filler_token=filler_token, filler_penalty=filler_penalty, filler_scores=filler_scores,
                        duration_prior=duration_prior, duration_prior_weight=duration_prior_weight,
                        duration_prior_scores=duration_prior_scores, decode_duration_prior=decode_duration_prior,
-                       decode_duration_prior_weight=decode_duration_prior_weight)
+                       decode_duration_prior_weight=decode_duration_prior_weight, decode_duration_scores=decode_duration_scores)
