@@ -1042,6 +1042,49 @@ int32_t wfl_decode_duration_posterior(const float* logits, int64_t ldl, int32_t 
                                       float threshold, const int32_t* ids, void* workspace, int64_t workspace_bytes, float* logz,
                                       float* post, float* cls_post, int32_t* status, void* stream);
 
+/* ---- Expected run lengths and successions of a duration-prior decode on the GPU: one E-step over the explicit-duration grammar of
+ * wfl_decode_duration, to learn the free decode's duration prior (and its bigram) from audio without labels
+ * (`python -m wfl_asr_amd.adapt_decode_durations`; wfl-asr_amd/decode.py).  Clips, logits, pairs, o_id, trans, sym_dur, dur, n_rows, D,
+ * threshold, the symbols, the states, the legality rule, the forced-to-O rule, the virtual O frame, "any state may end the clip",
+ * L_q(d) with its tail, "the run in progress at the last frame ends there and pays its L", the path weight, W, lambda, tau, the
+ * recurrences (R, Y, end, bE, bO, Wr, V, u), the guards and clamps and logz are wfl_decode_duration_posterior's; there is no path
+ * argument: the sums run over every legal path.  Outputs (device, fp32):
+ *     succ[b][s][q] = (1 / Z) sum_t end_s(t-1) W[s][q] u_t[q]    (s, q) != (O, O);  succ[b][O][O] = 0
+ * one [N][N] table per clip, rows the PREVIOUS symbol: wfl_decode_bigram_counts' table on this grammar; an entry whose trans is -inf is
+ * exactly 0.  dur_counts[b][p][j], [n_pairs][D + 1] per clip, indexed by phoneme SYMBOL p (not by table row; the host adds symbols
+ * that share a row), in the layout of a row of dur:
+ *     j = 0 .. D - 2   (1 / Z) sum_t R_p^{j+1}(t) lambda_p(j+1) bE_p(t)    expected runs of p of exactly j + 1 frames (t: the last frame)
+ *     j = D - 1        (1 / Z) sum_t R_p^D(t) lambda_p(D) V_p(t)            expected runs of D frames or more (t: the D-th frame)
+ *     j = D            (1 / Z) sum_t Y_p(t) V_p(t)                          expected frames past the D-th
+ * At the last frame bE = V = 1: a run the clip cuts off counts with its cut length, as the search charges it.  Every entry is a sum of
+ * non-negative products (nothing is formed as a difference); an entry the table forbids (lambda = 0; tau = 0 for j = D) is exactly 0.0; a
+ * phoneme without a row (sym_dur = -1) is counted like any other, lambda = tau = 1.  At D = 1 column 0 is the number of runs.
+ * Identities, by construction: sum_{j <= D-1} dur_counts[p][j] = sum_s succ[s][1 + p] (every run is opened once);
+ * sum_{j <= D-2} (j + 1) dc[p][j] + D dc[p][D-1] + dc[p][D] is the posterior number of frames of p, and those summed over p are <= T;
+ * with every sym_dur = -1, or an all-zero table, succ and logz are wfl_decode_bigram_counts'; dur_counts[p][.] and succ are the partial
+ * derivatives of log Z with respect to p's row of dur and to trans, which is why they are the E-step.
+ * status[b]: 0 ok; 2 C above 1024 or N above WFL_DECODE_BIGRAM_MAX_SYMBOLS (whatever D); 4 a bad class table, or a sym_dur outside
+ * -1 .. n_rows - 1.  A clip with status != 0 gets logz = 0 and all-zero tables; so does T = 0, with status 0.  Host-side errors
+ * (negative return) are wfl_decode_duration_posterior's, and a null logz, succ, status or (n_pairs > 0) dur_counts when n_clips > 0.
+ * One workgroup per clip: a clip alone equals the same clip inside any batch, bit for bit.  Three sweeps: forward and backward as in
+ * wfl_decode_duration_posterior (succ is summed in the backward sweep, in registers, fp32, a frame adds at most 1), then the owner
+ * thread of each phoneme walks forward again over its recorded R^1, bE and V and adds the run-length shares, in double.  A frame's
+ * share is multiplied by 2^(exponents) / Z formed in double and clamped to 2^126; no intermediate is inf or NaN whatever the logits,
+ * the tables and the clip's length.
+ * Workspace, per clip with T > 0, in 4-byte words: round_up_64(T (4 N + 2)) + H + 2 round_up_64(T)  (per frame the scaled end(t-1),
+ * R^1(t), bE(t), V(t) of every symbol and the two scale exponents; H; the row maxima; the forced flags).  H holds the run history,
+ * the symbols' rows of dur and the (D + 1) double sums per symbol where one CU's LDS does not hold them beside the trans table: with
+ * HS = round_up_64(N), H = 0 when
+ *     16 ceil(4 N (N | 1) / 16) + 6912 + 4 (4 D + 3) HS <= 163840 - 4608
+ * (every D at N <= 128; at N = 141 D <= 22; never at the cap of 192 symbols), else H = round_up_64((4 D + 3) HS).  0 above the symbol cap;
+ * wfl_decode_duration_counts_workspace_bytes returns -1 for D outside 1 .. 32. */
+int64_t wfl_decode_duration_counts_workspace_bytes(const int32_t* n_frames_host, int32_t n_clips, int32_t n_pairs, int32_t D);
+int32_t wfl_decode_duration_counts(const float* logits, int64_t ldl, int32_t C, int32_t o_id, const int64_t* frame_off_host,
+                                   const int32_t* n_frames_host, int32_t n_clips, const int32_t* pairs, int32_t n_pairs,
+                                   const float* trans, const int32_t* sym_dur, const float* dur, int32_t n_rows, int32_t D,
+                                   float threshold, void* workspace, int64_t workspace_bytes, float* logz, float* succ,
+                                   float* dur_counts, int32_t* status, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -128,6 +128,8 @@ SIGNATURES = {
     "wfl_decode_duration": (_I, [_P, _L, _I, _I, _P, _P, _I, _P, _I, _P, _P, _P, _I, _I, _F, _P, _L, _P, _P, _P, _P]),
     "wfl_decode_duration_posterior_workspace_bytes": (_L, [_P, _I, _I, _I]),
     "wfl_decode_duration_posterior": (_I, [_P, _L, _I, _I, _P, _P, _I, _P, _I, _P, _P, _P, _I, _I, _F, _P, _P, _L, _P, _P, _P, _P, _P]),
+    "wfl_decode_duration_counts_workspace_bytes": (_L, [_P, _I, _I, _I]),
+    "wfl_decode_duration_counts": (_I, [_P, _L, _I, _I, _P, _P, _I, _P, _I, _P, _P, _P, _I, _I, _F, _P, _L, _P, _P, _P, _P, _P]),
     "wfl_gemm_profile_enable":(_I, [_P, _I]),
     "wfl_gemm_profile_read": (_I, [_P, _I, _P, _P, _P, _P, _P, _I]),
 }

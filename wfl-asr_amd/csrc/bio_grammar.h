@@ -140,7 +140,7 @@ static __device__ __forceinline__ void write_logz(const L& a, const Clip& cl, in
 
 // ---- what a clip that is not searched / scored looks like, written by a block of NT threads; the shape is chosen by the outputs the
 // launch struct has.  A search (ids, score): O everywhere, score 0.  A posterior (logz, post, cls_post): zeros.  Expected successions
-// (logz, counts [clips][N][N]): logz 0 and an all-zero table.
+// (logz, counts [clips][N][N]): logz 0 and an all-zero table.  Expected run lengths: below.
 template <int NT, class L>
 static __device__ __forceinline__ auto refuse(const L& a, const Clip& cl, int status) -> decltype((void)a.score) {
   int* ids = a.ids + cl.frame_off;
@@ -159,6 +159,17 @@ static __device__ __forceinline__ auto refuse(const L& a, const Clip& cl, int st
   const long nn = (long)(a.n_pairs + 1) * (a.n_pairs + 1);
   float* c = a.counts + cl.clip * nn;
   for (long e = threadIdx.x; e < nn; e += NT) c[e] = 0.f;
+  if (threadIdx.x == 0) { a.logz[cl.clip] = 0.f; a.status[cl.clip] = status; }
+}
+
+// expected run lengths (logz, succ [clips][N][N], dur_counts [clips][n_pairs][D + 1]): logz 0 and two all-zero tables
+template <int NT, class L>
+static __device__ __forceinline__ auto refuse(const L& a, const Clip& cl, int status) -> decltype((void)a.dur_counts) {
+  const long nn = (long)(a.n_pairs + 1) * (a.n_pairs + 1), nd = (long)a.n_pairs * (a.D + 1);
+  float* c = a.succ + cl.clip * nn;
+  float* d = a.dur_counts + cl.clip * nd;
+  for (long e = threadIdx.x; e < nn; e += NT) c[e] = 0.f;
+  for (long e = threadIdx.x; e < nd; e += NT) d[e] = 0.f;
   if (threadIdx.x == 0) { a.logz[cl.clip] = 0.f; a.status[cl.clip] = status; }
 }
 

@@ -21,6 +21,9 @@ follows `B-p` or `I-p`, and every run that is opened costs `switch_penalty` nats
                       included (csrc/decode_duration_posterior.hip, `wfl_decode_duration_posterior`; `postprocess.decode_duration_scores`)
   bigram_expected_counts  the expected successions of a batch of clips under bio_viterbi_bigram's path distribution, one [N, N] table
                       per clip (csrc/decode_bigram_counts.hip, `wfl_decode_bigram_counts`): the E-step of adapt_bigram.py
+  duration_expected_counts  the expected run lengths [phonemes, D + 1] and successions [N, N] per clip under bio_viterbi_duration's
+                      path distribution (csrc/decode_duration_counts.hip, `wfl_decode_duration_counts`): the E-step of
+                      adapt_decode_durations.py
   path_segments_free  the path's ids of a file, chunk by chunk, -> segments; a run that crosses a chunk seam is one segment
   free_score          those outputs + bio_viterbi's score -> FreeScore / RunScore records, run j being segment j of the path
 """
@@ -96,6 +99,10 @@ def duration_workspace_bytes(n_frames, n_pairs, D) -> int:
 
 def duration_posterior_workspace_bytes(n_frames, n_pairs, D) -> int:
     return _workspace_bytes("wfl_decode_duration_posterior_workspace_bytes", n_frames, n_pairs, int(D))
+
+
+def duration_counts_workspace_bytes(n_frames, n_pairs, D) -> int:
+    return _workspace_bytes("wfl_decode_duration_counts_workspace_bytes", n_frames, n_pairs, int(D))
 
 
 def _check_clips(logits, n_frames, table, switch_penalty, threshold, frame_offsets):
@@ -366,6 +373,36 @@ def bigram_expected_counts(logits, n_frames, table, trans, threshold, frame_offs
     status = torch.empty(max(nb, 1), dtype=torch.int32, device=dev)
     _call("wfl_decode_bigram_counts", logits, clips, (w, float(threshold)), (logz, counts, status), stream)
     return logz[:nb], counts[:nb], status[:nb]
+
+
+def duration_expected_counts(logits, n_frames, table, trans, dur, sym_dur, threshold, frame_offsets=None, stream=None):
+    """The expected run lengths and successions of a ragged batch of clips under the explicit-duration grammar of bio_viterbi_duration
+    (same arguments): one E-step over the duration table `dur` and the table `trans` (csrc/decode_duration_counts.hip,
+    `wfl_decode_duration_counts`).
+
+    -> (logz [clips] float32, succ [clips, N, N] float32, dur_counts [clips, phonemes, D + 1] float32, status [clips] int32), CUDA
+    tensors.  succ is bigram_expected_counts' table on this grammar (rows the PREVIOUS symbol).  dur_counts[b][p] is indexed by the
+    phoneme of the class table, NOT by the row of `dur` (add the phonemes that share a row on the host), and has the layout of a row
+    of `dur`: columns 0 .. D - 2 the expected number of runs of exactly 1 .. D - 1 frames, column D - 1 the expected number of runs of
+    D frames or more, column D the expected number of frames past the D-th -- the statistics durations.reestimate takes.  An entry
+    whose `trans` or `dur` is -inf is exactly 0.  logz is decode_posteriors_duration's.  A clip with status != 0 (STATUS_OVER_CAP also
+    above MAX_BIGRAM_SYMBOLS; STATUS_BAD_CLASS) gets logz 0 and all-zero tables; so does an empty clip, with status 0."""
+    clips = _check_clips(logits, n_frames, table, 0.0, threshold, frame_offsets)
+    w = check_transitions(trans, len(clips[1]))
+    d = check_duration_table(dur)
+    r = check_symbol_rows(sym_dur, len(clips[1]), d.shape[0])
+    D = d.shape[1] - 1
+    nb, n = clips[2], len(clips[1]) + 1
+    dev = logits.device
+    logz = torch.empty(max(nb, 1), dtype=torch.float32, device=dev)
+    succ = torch.empty((max(nb, 1), n, n), dtype=torch.float32, device=dev)
+    dur_counts = torch.empty((max(nb, 1), max(n - 1, 1), D + 1), dtype=torch.float32, device=dev)
+    status = torch.empty(max(nb, 1), dtype=torch.int32, device=dev)
+    r_up = r if r.size else np.full(1, -1, np.int32)
+    d_up = d if d.size else np.zeros((1, D + 1), np.float32)
+    _call("wfl_decode_duration_counts", logits, clips, (w, r_up, d_up, int(d.shape[0]), D, float(threshold)),
+          (logz, succ, dur_counts, status), stream, ws_more=(D,))
+    return logz[:nb], succ[:nb], dur_counts[:nb, :n - 1], status[:nb]
 
 
 def path_segments_free(ids, chunk_frames, chunk_offsets, chunk_clock, table: npost.LabelTable, frame_duration):

@@ -999,6 +999,61 @@ class Labeler:
                 k0 += n
         return total, total_logz, n_frames, n_tokens, skipped
 
+    def expected_free_durations(self, audio_paths, trans, prior, weight=1.0, lang_id=None, confidence_threshold=0.0, verbose=True):
+        """One E-step over files WITHOUT labels or transcripts, under the explicit-duration grammar of the free decode
+        (opts.decode_duration_prior): the transition table `trans` ([N, N] float32, phonotactics.transition_table; None: the flat
+        table -postprocess.switch_penalty) and `prior` (durations.DurationPrior) at `weight`.  -> (dur_counts float64
+        [len(prior.phonemes), D + 1]: per phoneme the expected number of runs of 1 .. D - 1 frames, of D frames or more, and the
+        expected frames past D -- durations.reestimate's statistics; succ float64 [N, N]: expected_successions' table on this
+        grammar; total_logz; total_lse; n_frames; skipped).  The files are forwarded and laid out as expected_successions does it: a
+        file is one clip across its 30 s seams, the files of a wave one ragged batch (decode.duration_expected_counts,
+        wfl_decode_duration_counts).  The tables follow _decode_duration_prior's rule: a symbol's row is the row of its output name, so
+        the symbols that share an output name add into one row (float64, on the host); a symbol whose output name the prior lacks
+        goes nowhere, one whose row is null is counted under no prior.  A file whose status is not 0 is skipped with one line."""
+        from . import durations as DU
+        lang_name = self._lang_name(lang_id)
+        remap, names = self._names_for(lang_name)
+        DU.check(prior, names, frame_duration)
+        dur = DU.table(prior, weight)
+        if self._decode_table is None:
+            self._decode_table = DC.class_table(self.labels)
+        table = self._decode_table
+        n, D = len(table[1]) + 1, int(prior.max_frames)
+        if trans is None:
+            trans = np.full((n, n), -float(self.options().switch_penalty), np.float32)
+        out = {ph: names[int(remap[i])] for i, ph in enumerate(self._table.names)}
+        sym_dur = DC.duration_symbol_rows(prior, table, self.labels, out)
+        row_of = {name: i for i, name in enumerate(prior.phonemes)}
+        sym_names = [str(self.labels[int(b)])[2:] for b, _ in np.asarray(table[1], np.int32).reshape(-1, 2)]
+        acc_row = np.array([row_of.get(out.get(s, s), -1) for s in sym_names], np.int64)
+        total = np.zeros((len(prior.phonemes), D + 1), np.float64)
+        succ = np.zeros((n, n), np.float64)
+        total_logz = total_lse = 0.0
+        n_frames, skipped = 0, []
+        for files, by_file in self._file_waves(audio_paths, verbose):
+            sel = [fi for fi in files if fi in by_file]
+            if not sel:
+                continue
+            _, rows = self._forward_with_logits(sel, by_file, lang_id, confidence_threshold)
+            frames, lg = self._file_rows(rows, by_file, sel)
+            d_logz, d_succ, d_dur, d_st = DC.duration_expected_counts(lg, frames, table, trans, dur, sym_dur, confidence_threshold)
+            f0 = back_to_back(frames)
+            d_lse = _clip_lse(lg, f0, f0 + np.asarray(frames, np.int64))
+            h = torch.cat([d_logz.double(), d_lse, d_st.double()]).cpu().numpy()
+            h_succ, h_dur = d_succ.cpu().numpy(), d_dur.cpu().numpy()
+            nb = len(sel)
+            for b, fi in enumerate(sel):
+                if int(h[2 * nb + b]) != DC.STATUS_OK:
+                    print(f"{audio_paths[fi]}: no expected run lengths (wfl_decode_duration_counts status {int(h[2 * nb + b])}); skipped")
+                    skipped.append(audio_paths[fi])
+                    continue
+                np.add.at(total, acc_row[acc_row >= 0], h_dur[b].astype(np.float64)[acc_row >= 0])
+                succ += h_succ[b].astype(np.float64)
+                total_logz += float(h[b])
+                total_lse += float(h[nb + b])
+                n_frames += int(frames[b])
+        return total, succ, total_logz, total_lse, n_frames, skipped
+
     def _label_viterbi(self, audio_paths, transcripts, drafts, opts, lang_id, threshold, verbose, prior=None):
         """Files with a transcript, align="viterbi" -> one ViterbiLabel per file.  Their chunks are forwarded with logits (kept on
         the device); the free decode of the same forward gives the greedy result, which the pause rule at the ends needs and which a
