@@ -206,6 +206,42 @@ int32_t wfl_op_gemm_ln(const void* A, int64_t lda, const void* W, int32_t M, int
                        int32_t T, void* C, int64_t ldc, int64_t c_lead, int32_t c_pitch, const float* bias, const float* ln_s,
                        float ln_eps, int32_t act, void* stream);
 
+/* One GEMM launch with every optional field of csrc/common.h's GemmArgs passed through (null / 0 = absent), for per-mode parity tests:
+ *   v      = sa(m) * w8_scale[n] * sum_k a(m, k) W[n][k]             (sa, w8_scale: 1 when absent)
+ *   v      = rstd_m * (v - mean_m * ln_s[n])                          with ln_s (W = gamma o W, bias = b + W beta; see wfl_op_gemm_ln)
+ *   v      = act( v + bias[n] + clip_bias[clip_idx[b]][n] ) + pos[t][n]
+ *   out    = res (+ res_lo) + alpha * v       (no res: out = v);      out_f32 + acc_f32: out += C
+ *   C      = bf16(out) (fp32 with out_f32),  c_lo = bf16(out - C);    stored iff t < T, t < clip_T[b] and n < n_valid
+ *   W        bf16 [N][K], or -- w8_scale given -- OCP e4m3 bytes [N][K] with one fp32 scale per output channel
+ *   a8 == 1  A holds e4m3 bytes too (lda in bytes, one tap); sa(m) = a8_scale[a8_lead + m], or a8_static when a8_scale is null;
+ *            needs w8_scale.  (The block-scaled forms a8 == 2, 3 stay with wfl_op_gemm_mx.)
+ *   c8       with a8: instead of C, e4m3(out * c8_inv_scale) bytes (ldc8 per row, C's row mapping); a stored element that saturates
+ *            (|out| * c8_inv_scale > 448) or is NaN is stored clamped and ORs 2 into *status
+ *   stats_out  (residual launches of the streaming kernel, N <= 1024) per C row r and 256-column tile j, the sum and the sum of squares
+ *            of the bf16 values stored in C: stats_out[(r * 4 + j) * 2 + {0, 1}]
+ *   stats_in   with ln_s: mean_m / rstd_m from a producer's stats_out -- row stats_lead + m, its first stats_nsl (1 .. 4) tile slots
+ *            added up, over K columns -- instead of from the A row itself
+ *   pos [>= T][ldpos] bf16, clip_bias [rows][clip_ld] fp32 with clip_idx [clips] int32, clip_T [clips] int32.
+ * *kernel_id (optional) receives the kernel that ran: 1 / 5 the streaming kernel (192- / 256-row tiles), 2 / 3 gemm256, 4 the 128-tile
+ * kernel, 6 the streaming kernel's conv mode, 7 its fp8 forms; 0 when nothing was launched.
+ * What the dispatch would pass over without a word is an error status and nothing is launched: struct_bytes != sizeof(wfl_gemm_ex_args),
+ * res_lo without res, c8 without a8, a8 outside {0, 1} or without w8_scale, stats_in without ln_s, acc_f32 without out_f32, and
+ * stats_out / stats_in on a launch the streaming kernel does not take (no other kernel reads or writes them). */
+typedef struct wfl_gemm_ex_args {
+  int64_t struct_bytes;       /* sizeof(wfl_gemm_ex_args) */
+  const void* A; int64_t lda; int64_t tap_stride; int32_t cin; int32_t a8;          /* as wfl_op_gemm (cin <= 0: K) */
+  const void* W; const float* w8_scale; const float* a8_scale; int64_t a8_lead; float a8_static;
+  int32_t M, N, K, n_valid, P, T, c_pitch;
+  void* C; void* c_lo; int64_t ldc; int64_t c_lead;
+  const float* bias; const float* clip_bias; const int32_t* clip_idx; const int32_t* clip_T; int32_t clip_ld; int32_t act;
+  const void* res; const void* res_lo; int64_t ldres; float alpha; int32_t glu; int32_t out_f32; int32_t acc_f32;
+  const void* pos; int64_t ldpos;
+  const float* ln_s; float ln_eps; int32_t stats_nsl; float* stats_out; const float* stats_in; int64_t stats_lead;
+  void* c8; int64_t ldc8; float c8_inv_scale; int32_t reserved;
+  int32_t* status;            /* -> GemmArgs::err */
+} wfl_gemm_ex_args;
+int32_t wfl_op_gemm_ex(const wfl_gemm_ex_args* args, int32_t* kernel_id, void* stream);
+
 /* softmax(q k^T) v per (clip, head); QK rows hold [q | k] (q pre-scaled by hd^-1/2 * log2 e), V rows (ld = ldv, same row
  * indexing) hold v; normally all three are columns of one packed q|k|v projection output. */
 int32_t wfl_op_attention(const void* QK, int64_t ldqk, int64_t lead, const void* V, int64_t ldv, void* O, int64_t ldo, int32_t B,
@@ -299,7 +335,8 @@ int32_t wfl_op_layernorm_pair(const void* x, const void* x_lo, void* y1, void* y
  * (an e4m3 PAIR: lo = e4m3(16 (x / sa - hi))); sa(m) = a_scale[m] or a_static when a_scale is null.  N % 256 == 0, K % 128 == 0, K >= 512.
  * res / res_lo / c_lo are bf16 rows with C's leading dimension and row mapping.
  * Output: bf16 rows C (+ the low half c_lo with a residual), or -- c8 given -- e4m3(out * c8_inv_scale) into c8 and, c8_lo given, the
- * remainder e4m3(16 (out * c8_inv_scale - hi)) into c8_lo (ldc8 bytes per row); an e4m3 store that saturates ORs 2 into *status. */
+ * remainder e4m3(16 (out * c8_inv_scale - hi)) into c8_lo (ldc8 bytes per row); a stored element that saturates or is NaN ORs 2 into
+ * *status (elements that are not stored -- rows t >= T -- are not judged). */
 int32_t wfl_op_gemm_mx(const void* A8, const void* A8_lo, int64_t lda, const void* W8, const float* w_scale, const float* a_scale,
                        float a_static, int32_t M, int32_t N, int32_t K, int32_t P, int32_t T, void* C, int64_t ldc, int64_t c_lead,
                        int32_t c_pitch, const float* bias, const void* res, const void* res_lo, void* c_lo, float alpha, int32_t act,

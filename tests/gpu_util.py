@@ -73,6 +73,26 @@ def gemm_ln(A, a_off, lda, Wp, M, n_valid, P, T, Cout, c_ld, c_lead, c_pitch, bi
     _lib.check(rc, "wfl_op_gemm_ln")
 
 
+_GEMM_EX_POINTERS = {n for n, t in _lib.WflGemmExArgs._fields_ if t is C.c_void_p}
+
+
+def gemm_ex(check=True, **fields):
+    """wfl_op_gemm_ex: the fields of include/wfl_asr.h's wfl_gemm_ex_args by name.  Pointer fields take a device tensor, a
+    (tensor, element offset) pair or None; everything else a number.  -> (status code, kernel id)."""
+    a = _lib.WflGemmExArgs()
+    for k, v in fields.items():
+        if k in _GEMM_EX_POINTERS:
+            v = ptr(*v) if isinstance(v, tuple) else ptr(v)
+        elif k not in {n for n, _ in _lib.WflGemmExArgs._fields_}:
+            raise TypeError(f"wfl_gemm_ex_args has no field {k}")
+        setattr(a, k, v)
+    kid = C.c_int32(-1)
+    rc = lib().wfl_op_gemm_ex(C.byref(a), C.byref(kid), stream())
+    if check:
+        _lib.check(rc, "wfl_op_gemm_ex")
+    return rc, kid.value
+
+
 def attention(QK, ldqk, lead, V, v_off, ldv, O, ldo, B, T, P, heads, d):
     _lib.check(lib().wfl_op_attention(ptr(QK), ldqk, lead, ptr(V, v_off), ldv, ptr(O), ldo, B, T, P, heads, d, stream()), "wfl_op_attention")
 

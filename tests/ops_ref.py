@@ -728,3 +728,130 @@ def conv0_bound(ref, scale, pair):
 def frac_outside_nan(wrong, right, bound, factor=2.0):
     """frac_outside, with a wrong reference that is not finite counted as outside (no finite output can be near it)."""
     return float((((wrong - right).abs() > factor * bound) | ~torch.isfinite(wrong)).double().mean())
+
+
+# ------------------------------------------------------------------------------------------------------------------ GEMM modes
+# Float64 references of what one GemmArgs launch computes (csrc/common.h; include/wfl_asr.h, wfl_op_gemm_ex), piece by piece, for
+# tests/test_gpu_ops_gemm_modes.py.  Every function takes the operand VALUES the kernel reads (bf16 values, e4m3 bytes decoded, fp32
+# scales) as float64 matrices of the VALID rows only -- gathering rows out of the frame-row buffers is the test's business -- and
+# returns the value together with `mag`, the same expression with every term replaced by its absolute value: the scale an fp32
+# accumulation error is proportional to, and what the tests' tolerances hang on.
+def e4m3_decode(b):
+    """uint8 tensor of OCP e4m3 (fn) bytes -> float64, by the format's definition: 1 sign, 4 exponent (bias 7), 3 mantissa bits, no
+    infinities, S.1111.111 = NaN, exponent 0 subnormal."""
+    b = b.to(torch.int64)
+    s, e, m = b >> 7, (b >> 3) & 15, b & 7
+    v = torch.where(e == 0, m.double() / 8 * 2.0 ** -6, (1 + m.double() / 8) * torch.exp2((e - 7).double()))
+    v = torch.where((e == 15) & (m == 7), torch.full_like(v, math.nan), v)
+    return torch.where(s == 1, -v, v)
+
+
+def gemm_ref(a, w, bias=None, row_scale=None, col_scale=None):
+    """a [M, K], w [N, K] values; row_scale [M] (fp8 activations' per-row scale), col_scale [N] (fp8 weights' per-channel scale).
+    -> (v, mag) [M, N]:  v = rs_m cs_n sum_k a w + bias,  mag = |rs_m| |cs_n| sum_k |a| |w| + |bias|."""
+    a, w = a.to(F64), w.to(F64)
+    v, mag = a @ w.T, a.abs() @ w.abs().T
+    if col_scale is not None:
+        v, mag = v * col_scale.to(F64)[None, :], mag * col_scale.to(F64).abs()[None, :]
+    if row_scale is not None:
+        v, mag = v * row_scale.to(F64)[:, None], mag * row_scale.to(F64).abs()[:, None]
+    if bias is not None:
+        v, mag = v + bias.to(F64), mag + bias.to(F64).abs()
+    return v, mag
+
+
+def gemm_table_terms(v, mag, B, T, clip_bias=None, clip_idx=None, act=None, pos=None):
+    """The per-clip bias row (before the activation) and the positional table (after it) of a [B * T, N] result:
+         v = act(v + clip_bias[clip_idx[b]][n]) + pos[t][n].
+    clip_bias [rows, >= N], clip_idx list of B rows, pos [>= T, >= N]; act None / "gelu" / "relu".  mag follows (an activation with
+    Lipschitz constant L leaves at most L mag: the caller applies its factor)."""
+    N = v.shape[1]
+    v, mag = v.view(B, T, N).clone(), mag.view(B, T, N).clone()
+    if clip_bias is not None:
+        cb = clip_bias.to(F64)[torch.as_tensor(list(clip_idx), dtype=torch.long)][:, None, :N]
+        v, mag = v + cb, mag + cb.abs()
+    if act == "gelu":
+        v = F.gelu(v)
+    elif act == "relu":
+        v = F.relu(v)
+    elif act is not None:
+        raise ValueError(act)
+    if pos is not None:
+        pt = pos.to(F64)[None, :T, :N]
+        v, mag = v + pt, mag + pt.abs()
+    return v.reshape(B * T, N), mag.reshape(B * T, N)
+
+
+def residual_pair_ref(v, mag, res_hi, res_lo=None, alpha=1.0):
+    """out = res_hi + res_lo + alpha v  (the residual stream as a bf16 pair, GemmArgs::res / res_lo / alpha)."""
+    out, m = res_hi.to(F64) + alpha * v, res_hi.to(F64).abs() + abs(alpha) * mag
+    if res_lo is not None:
+        out, m = out + res_lo.to(F64), m + res_lo.to(F64).abs()
+    return out, m
+
+
+def ragged_mask(B, T, clip_T=None):
+    """bool [B, T]: the frames a launch stores -- t < T and t < clip_T[b]."""
+    n = torch.tensor([T] * B if clip_T is None else [min(int(x), T) for x in clip_T])
+    return torch.arange(T)[None, :] < n[:, None]
+
+
+def tile_stats_ref(c):
+    """The statistics producer (GemmArgs::stats_out): c [M, N] the bf16 values stored in C, N % 256 == 0.
+    -> (stats [M, N / 256, 2], scale [M, N / 256, 2]): per row and 256-column tile (sum, sum of squares), and the absolute sums
+    (sum |x|, sum x^2) a 256-term fp32 summation's error is proportional to."""
+    M, N = c.shape
+    t = c.to(F64).view(M, N // 256, 256)
+    sq = (t * t).sum(-1)
+    return torch.stack([t.sum(-1), sq], -1), torch.stack([t.abs().sum(-1), sq], -1)
+
+
+def row_stats_slots(a, nsl):
+    """What a producer leaves for a consumer whose K = 256 nsl: a [M, K] -> fp32 [M, 4, 2], slot j < nsl = (sum, sum of squares) of columns
+    256 j .. 256 j + 255 (summed in float64, rounded once); the unused slots hold NaN -- a consumer must not read them."""
+    M, K = a.shape
+    assert K == 256 * nsl and 1 <= nsl <= 4
+    st, _ = tile_stats_ref(a)
+    out = torch.full((M, 4, 2), math.nan, dtype=torch.float32, device=a.device)
+    out[:, :nsl] = st.float()
+    return out
+
+
+def ln_fold_ref(a, w, bias, stats, nsl, eps=1e-5, ln_s=None):
+    """LayerNorm folded into the consuming GEMM, statistics given (GemmArgs::ln_s + stats_in):
+         mean = sum_j stats[m, j, 0] / K,  var = sum_j stats[m, j, 1] / K - mean^2,  rstd = (var + eps)^-1/2,
+         v = rstd (a w^T - mean ln_s) + bias,        ln_s[n] = sum_k w[n][k] unless given.
+    a [M, K], w [N, K] (gamma already folded in), stats [M, >= nsl, 2].
+    -> (v, mag, cancel): mag = rstd (sum |a||w| + |mean| sum |w|) (the bias is added once, exactly: no part of it);  cancel = (E[x^2] / var) |v - bias|, the factor by which the
+    one-pass variance E[x^2] - mean^2 amplifies a relative error of its two terms, times the part of v that rstd multiplies."""
+    a, w = a.to(F64), w.to(F64)
+    K = a.shape[1]
+    s = stats.to(F64)[:, :nsl].sum(1)
+    mean, ex2 = s[:, 0] / K, s[:, 1] / K
+    var = (ex2 - mean * mean).clamp_min(0)
+    rstd = (var + eps) ** -0.5
+    ls = w.sum(1) if ln_s is None else ln_s.to(F64)
+    core = rstd[:, None] * (a @ w.T - mean[:, None] * ls[None, :])
+    mag = rstd[:, None] * (a.abs() @ w.abs().T + mean.abs()[:, None] * w.abs().sum(1)[None, :])
+    b = 0.0 if bias is None else bias.to(F64)[None, :]
+    cancel = (ex2 / var.clamp_min(1e-300))[:, None] * core.abs()
+    return core + b, mag, cancel
+
+
+# Tolerances of the GEMM-mode tests: derived from the number formats, never from what a kernel gives.
+GELU_LIPSCHITZ = 1.2          # max |gelu'| = 1.13
+
+
+def tol_bf16(ref, mag, K, lip=1.0):
+    """one bf16 rounding of the stored value + an fp32 accumulation over K terms"""
+    return 2.0 ** -8 * ref.abs() + lip * K * 2.0 ** -24 * mag
+
+
+def tol_pair(ref, mag, K):
+    """a hi + lo pair keeps sixteen significant bits of the sum"""
+    return 2.0 ** -15 * ref.abs() + K * 2.0 ** -24 * mag
+
+
+def tol_ln_fold(ref, mag, cancel, K, lip=1.0):
+    """tol_bf16 + the one-pass variance's cancellation: fp32 sums carry ~2^-23 each, two of them, amplified by E[x^2] / var"""
+    return 2.0 ** -8 * ref.abs() + lip * (K * 2.0 ** -24 * mag + 2.0 ** -22 * cancel)

@@ -168,3 +168,42 @@ def test_gemm_split_validates_its_arguments_without_gpu(libpath):
     # K that is not a whole number of taps
     rc = lib.wfl_op_gemm_split(a, a, 512, 96, 96, a, 16, 256, 512, 256, 16, 8, a, a, 256, 0, 16, None, None, None, 0, 1.0, 0, 0, None)
     assert rc != 0 and b"taps" in lib.wfl_last_error()
+
+
+def test_gemm_ex_validates_its_arguments_without_gpu(libpath):
+    """wfl_op_gemm_ex (every GemmArgs field at the operator level): what the dispatch would pass over without a word comes back as a
+    status and a message, *kernel_id stays 0, and nothing is launched (no GPU exists here: a launch would fail differently)."""
+    from wfl_asr_amd import _lib
+    lib = _lib.load()
+    assert ctypes.sizeof(_lib.WflGemmExArgs) % 8 == 0
+    buf = (ctypes.c_char * 64)()
+    a = ctypes.cast(buf, ctypes.c_void_p)
+
+    def call(**kw):
+        base = dict(A=a, W=a, C=a, lda=512, M=16, N=256, K=512, n_valid=256, P=16, T=8, ldc=256, c_pitch=16, alpha=1.0)
+        base.update(kw)
+        x = _lib.WflGemmExArgs(**base)
+        kid = ctypes.c_int32(-1)
+        rc = lib.wfl_op_gemm_ex(ctypes.byref(x), ctypes.byref(kid), None)
+        return rc, kid.value, lib.wfl_last_error()
+
+    for kw, word in ((dict(struct_bytes=ctypes.sizeof(_lib.WflGemmExArgs) - 8), b"struct_bytes"),
+                     (dict(struct_bytes=0), b"struct_bytes"),
+                     (dict(A=None), b"null"),
+                     (dict(res_lo=a), b"res_lo without res"),
+                     (dict(c8=a), b"c8 without a8"),
+                     (dict(a8=2, w8_scale=a), b"a8 is 0 or 1"),
+                     (dict(a8=-1, w8_scale=a), b"a8 is 0 or 1"),
+                     (dict(a8=1), b"a8 without w8_scale"),
+                     (dict(stats_in=a, stats_nsl=2), b"stats_in without ln_s"),
+                     (dict(acc_f32=1), b"acc_f32 without out_f32"),
+                     (dict(clip_bias=a), b"clip_bias without clip_idx"),
+                     # row statistics on launches the streaming kernel does not take: no residual; N / 256 > 4; a table beside them
+                     (dict(stats_out=a), b"streaming kernel does not take"),
+                     (dict(stats_out=a, res=a, ldres=1280, N=1280, n_valid=1280, ldc=1280), b"streaming kernel does not take"),
+                     (dict(stats_in=a, stats_nsl=2, ln_s=a, pos=a, ldpos=256), b"streaming kernel does not take"),
+                     (dict(stats_in=a, stats_nsl=5, ln_s=a), b"streaming kernel does not take"),
+                     # and what the dispatch itself refuses still is an error status
+                     (dict(P=12), b"wfl_op_gemm_ex")):
+        rc, kid, msg = call(**kw)
+        assert rc != 0 and kid == 0 and word in msg, (kw, rc, kid, msg)

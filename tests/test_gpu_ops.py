@@ -96,7 +96,8 @@ def test_gemm_conv_stride2_and_pos():
     wp, bp = G.pad_weight(w.permute(0, 2, 1).reshape(N, 3 * C), bias)
     pos = _rand(T, N, seed=16).to(torch.bfloat16)
     lib = G.lib()
-    # pos is not part of wfl_op_gemm's surface; emulate with the residual input (same add, alpha = 1)
+    # wfl_op_gemm has no `pos` argument: here the table goes in as the residual input (the same add, alpha = 1).  GemmArgs::pos itself is
+    # tested behind this conv in test_gpu_ops_gemm_modes.py::test_positional_table_behind_the_stride2_conv (wfl_op_gemm_ex)
     posrows = G.Rows(B, T, N, halo=18, lead=16).set(pos.float().expand(B, T, N))
     G.gemm(a.buf, (a.lead - 1) * C, 2 * C, wp, B * out.P, N, out.P, T, out.buf, N, out.lead, out.P, bias=bp, act=1,
            res=posrows.buf, ldres=N, alpha=1.0)

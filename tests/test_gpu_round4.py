@@ -103,7 +103,21 @@ def test_rows_fp8_pair_carries_eight_significant_bits(norm):
 @pytest.mark.parametrize("pair", [False, True])
 @pytest.mark.parametrize("mode", ["plain", "residual", "gelu_e4m3"])
 def test_gemm_mx_against_a_float64_product_of_its_own_bytes(pair, mode):
-    B, T, K, N = 3, 410, 1280, 768                       # 1290 rows: nine 160-row / seven 192-row tiles x 3 column tiles, tiles straddle clips
+    _gemm_mx_case(pair, mode, 3, 410, 1280, 768)         # 1290 rows: nine 160-row / seven 192-row tiles x 3 column tiles, tiles straddle clips
+
+
+@pytest.mark.parametrize("pair,mode,K,N", [(p, m, 512, 1024) for m in ("plain", "residual", "gelu_e4m3") for p in (False, True)] +
+                         [(True, "residual", 1280, 1280)])
+def test_gemm_mx_with_more_tiles_than_persistent_workgroups(pair, mode, K, N):
+    """25 clips of 480 frames (pitch 496, 12 400 rows): 78 row tiles of 160 (single) / 65 of 192 (pair) x N / 256 column tiles -- more than
+    the 256 persistent workgroups and no multiple of them, so the tile-boundary pre-issue, group 1's early epilogue, the vmcnt accounting
+    with the previous tile's stores in flight and have_prev all run, some workgroups taking one tile more than others.  K = 512 is the
+    shortest K loop the kernel takes (4 stages single, 8 pair, against a ring of 3): where an accounting error at the tile change has
+    the least room to hide.  Same bounds as the small case."""
+    _gemm_mx_case(pair, mode, 25, 480, K, N)
+
+
+def _gemm_mx_case(pair, mode, B, T, K, N):
     g = torch.Generator().manual_seed(11 + pair)
     x = G.Rows(B, T, K).set((torch.randn(B, T, K, generator=g) * 0.7).cuda())
     hi, lo, sc = _rows_fp8(x, pair=pair)
@@ -155,12 +169,12 @@ def test_gemm_mx_against_a_float64_product_of_its_own_bytes(pair, mode):
         ref = ref + res.get().reshape(-1, N).double() + res_lo.get().reshape(-1, N).double()
         got = out.get().reshape(-1, N).double() + c_lo.get().reshape(-1, N).double()
         err = (got - ref).abs()
-        _note(f"gemm_mx_op_residual_pair{int(pair)}", err_over_mag_max=(err / mag).max(), err_max=err.max())
+        _note(f"gemm_mx_op_residual_pair{int(pair)}_B{B}_K{K}_N{N}", err_over_mag_max=(err / mag).max(), err_max=err.max())
         assert bool((err <= 2 ** -15 * ref.abs() + 2e-5 * mag).all()), float((err / mag).max())     # hi + lo: sixteen significant bits of the sum
     else:
         got = out.get().reshape(-1, N).double()
         err = (got - ref).abs()
-        _note(f"gemm_mx_op_plain_pair{int(pair)}", err_over_mag_max=(err / mag).max(), err_max=err.max())
+        _note(f"gemm_mx_op_plain_pair{int(pair)}_B{B}_K{K}_N{N}", err_over_mag_max=(err / mag).max(), err_max=err.max())
         assert bool((err <= 2 ** -8 * ref.abs() + 2e-5 * mag).all()), float((err / mag).max())      # one bf16 rounding + the accumulation
     assert out.halo_is_zero()
 

@@ -373,3 +373,129 @@ def test_control_conv0(case):
         shares["tanh GELU"] = _conv0_share(c, R.conv0_case_ref(c, tanh=True)[0], ref, scale, m)
     for what, s in shares.items():
         assert _report(f"conv0 {R.conv0_id(case)}, {what}", s) >= MIN_SHARE, what
+
+
+# ------------------------------------------------------------------------------------------------- GEMM-mode references
+def _bf(x):
+    return x.to(torch.bfloat16).double()
+
+
+def test_e4m3_decode_is_torch_float8_e4m3fn():
+    b = torch.arange(256, dtype=torch.uint8)
+    mine, theirs = R.e4m3_decode(b), b.view(torch.float8_e4m3fn).double()
+    assert torch.equal(torch.isnan(mine), torch.isnan(theirs)) and int(torch.isnan(mine).sum()) == 2
+    ok = ~torch.isnan(mine)
+    assert torch.equal(mine[ok], theirs[ok]) and float(mine[ok].max()) == 448.0
+    assert torch.equal(torch.signbit(mine[ok]), torch.signbit(theirs[ok]))
+
+
+def test_gemm_reference_and_its_scales():
+    g = torch.Generator().manual_seed(1)
+    a, w, bias = _bf(torch.randn(37, 64, generator=g)), _bf(torch.randn(24, 64, generator=g)), torch.randn(24, generator=g).double()
+    rs, cs = torch.rand(37, generator=g).double() + 0.5, -(torch.rand(24, generator=g).double() + 0.5)
+    v, mag = R.gemm_ref(a, w, bias, rs, cs)
+    want = F.linear(a * rs[:, None], w * cs[:, None], bias)
+    assert torch.allclose(v, want, rtol=1e-12, atol=1e-12)
+    assert bool((mag >= v.abs() - 1e-12).all()) and bool((mag > 0).all())
+    assert torch.allclose(mag, F.linear((a * rs[:, None]).abs(), (w * cs[:, None]).abs(), bias.abs()), rtol=1e-12)
+    # the bytes' product "of the very bytes given": e4m3 weights x per-channel scale
+    wb = torch.randint(0, 256, (24, 64), generator=g, dtype=torch.uint8)
+    wb[(wb & 0x7F) == 0x7F] = 0x3C
+    v8, _ = R.gemm_ref(a, R.e4m3_decode(wb), None, None, cs)
+    assert torch.allclose(v8, a @ (wb.view(torch.float8_e4m3fn).double() * cs[:, None]).T, rtol=1e-12, atol=1e-12)
+
+
+def test_residual_pair_reference():
+    g = torch.Generator().manual_seed(2)
+    x = torch.randn(9, 16, generator=g) * 3
+    hi, lo = R.split(x)
+    v, mag = torch.randn(9, 16, generator=g).double(), torch.rand(9, 16, generator=g).double() + 1
+    out, m = R.residual_pair_ref(v, mag, hi.double(), lo.double(), alpha=0.5)
+    assert torch.allclose(out, hi.double() + lo.double() + 0.5 * v, rtol=0, atol=1e-15)
+    assert float((hi.double() + lo.double() - x.double()).abs().max()) <= 2.0 ** -16 * float(x.abs().max())
+    assert torch.allclose(m, hi.double().abs() + lo.double().abs() + 0.5 * mag)
+    out1, _ = R.residual_pair_ref(v, mag, hi.double(), None, alpha=1.0)
+    assert torch.equal(out1, hi.double() + v)
+
+
+@pytest.mark.parametrize("nsl", [1, 2, 3, 4])
+def test_statistics_slots_are_the_256_column_sums(nsl):
+    g = torch.Generator().manual_seed(3 + nsl)
+    x = _bf(torch.randn(11, 256 * nsl, generator=g) + 0.3)
+    st, sc = R.tile_stats_ref(x)
+    assert torch.allclose(st[..., 0], x.view(11, nsl, 256).sum(-1), rtol=1e-13, atol=1e-13)
+    assert torch.allclose(st[..., 1], (x * x).view(11, nsl, 256).sum(-1), rtol=1e-13)
+    assert torch.allclose(sc[..., 0], x.abs().view(11, nsl, 256).sum(-1), rtol=1e-13)
+    slots = R.row_stats_slots(x, nsl)
+    assert slots.dtype == torch.float32 and slots.shape == (11, 4, 2)
+    assert torch.equal(slots[:, :nsl], st.float()) and bool(torch.isnan(slots[:, nsl:]).all())
+    # a column moved across a tile border changes two slots and leaves their sum alone: the slot order is visible, the row total is not
+    y = x.clone()
+    if nsl > 1:
+        y[:, [255, 256]] = x[:, [256, 255]]
+        st2, _ = R.tile_stats_ref(y)
+        assert not torch.allclose(st2[:, 0], st[:, 0]) and torch.allclose(st2.sum(1), st.sum(1), rtol=1e-12)
+
+
+@pytest.mark.parametrize("K,kind", [(256, "normal"), (512, "normal"), (768, "offset"), (1024, "outlier")])
+def test_layernorm_fold_reference_is_layer_norm_then_linear(K, kind):
+    g = torch.Generator().manual_seed(K)
+    x = torch.randn(23, K, generator=g)
+    if kind == "offset":
+        x = x + 30
+    if kind == "outlier":
+        x[:, 5] *= 100
+    x = _bf(x)
+    gamma, beta = torch.randn(K, generator=g).double() * 0.2 + 1, torch.randn(K, generator=g).double() * 0.1
+    w, b = torch.randn(40, K, generator=g).double() / K ** 0.5, torch.randn(40, generator=g).double()
+    wf, bf_ = w * gamma[None, :], b + w @ beta                       # the fold: W' = gamma o W, bias = b + W beta
+    stats, _ = R.tile_stats_ref(x)
+    v, mag, cancel = R.ln_fold_ref(x, wf, bf_, stats, K // 256, eps=1e-5)
+    want = F.layer_norm(x, (K,), gamma, beta, 1e-5) @ w.T + b
+    assert torch.allclose(v, want, rtol=1e-9, atol=1e-9), float((v - want).abs().max())
+    assert bool((mag + bf_.abs() >= v.abs() - 1e-9).all()) and bool((cancel >= 0).all())
+    ratio = (x * x).mean(1) / x.var(1, unbiased=False)
+    assert torch.allclose(cancel, ratio[:, None] * (v - bf_).abs(), rtol=1e-6)
+    # controls: statistics of another row, an unfolded bias, a slot forgotten -- all far outside the bound.  (Not the first two on the
+    # common-offset rows: there the bound itself is wide, |mean| sum |w'| K 2^-24 ~ 0.04, and rows differ by less.)
+    tol = R.tol_ln_fold(v, mag, cancel, K)
+    if kind != "offset":
+        shifted, _, _ = R.ln_fold_ref(x, wf, bf_, stats.roll(1, 0), K // 256)
+        assert float(((shifted - v).abs() > 2 * tol).double().mean()) > 0.5
+        nobeta, _, _ = R.ln_fold_ref(x, wf, b, stats, K // 256)
+        assert float(((nobeta - v).abs() > 2 * tol).double().mean()) > 0.5
+    one_slot_short, _, _ = R.ln_fold_ref(x, wf, bf_, stats, max(K // 256 - 1, 1))
+    if K > 256:
+        assert float(((one_slot_short - v).abs() > 2 * tol).double().mean()) > 0.5
+
+
+def test_table_clip_bias_and_ragged_references():
+    g = torch.Generator().manual_seed(9)
+    B, T, N = 3, 7, 16
+    v0, mag0 = torch.randn(B * T, N, generator=g).double(), torch.rand(B * T, N, generator=g).double() + 1
+    table = torch.randn(4, N + 8, generator=g).double()               # clip_ld > N
+    idx = [2, 0, 2]
+    pos = torch.randn(T + 5, N, generator=g).double()
+    v, mag = R.gemm_table_terms(v0, mag0, B, T, table, idx, "gelu", pos)
+    for b in range(B):
+        for t in range(T):
+            want = F.gelu(v0[b * T + t] + table[idx[b], :N]) + pos[t]
+            assert torch.allclose(v[b * T + t], want, rtol=1e-13, atol=1e-13)
+    assert torch.allclose(mag, (mag0.view(B, T, N) + table[idx][:, None, :N].abs() + pos[None, :T].abs()).reshape(B * T, N))
+    # a table read one row off is a different result on every frame
+    off, _ = R.gemm_table_terms(v0, mag0, B, T, None, None, None, pos[1:])
+    plain, _ = R.gemm_table_terms(v0, mag0, B, T, None, None, None, pos)
+    assert float(((off - plain).abs() > 1e-3).double().mean()) > 0.95
+    m = R.ragged_mask(4, 10, [0, 1, 10, 6])
+    assert m.sum(1).tolist() == [0, 1, 10, 6] and bool(m[3, :6].all()) and not bool(m[3, 6:].any())
+    assert bool(R.ragged_mask(2, 5).all())
+
+
+def test_gemm_tolerances_are_the_formats():
+    ref, mag = torch.tensor([1.0, -3.0]).double(), torch.tensor([2.0, 8.0]).double()
+    assert torch.equal(R.tol_bf16(ref, mag, 512), 2.0 ** -8 * ref.abs() + 512 * 2.0 ** -24 * mag)
+    assert torch.equal(R.tol_bf16(ref, mag, 512, R.GELU_LIPSCHITZ), 2.0 ** -8 * ref.abs() + 1.2 * 512 * 2.0 ** -24 * mag)
+    assert torch.equal(R.tol_pair(ref, mag, 256), 2.0 ** -15 * ref.abs() + 256 * 2.0 ** -24 * mag)
+    x = torch.linspace(-6, 6, 20001, dtype=torch.float64, requires_grad=True)
+    (d,) = torch.autograd.grad(F.gelu(x).sum(), x)
+    assert 1.12 < float(d.abs().max()) < R.GELU_LIPSCHITZ

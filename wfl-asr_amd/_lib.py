@@ -35,6 +35,28 @@ _I = C.c_int32
 _L = C.c_int64
 _F = C.c_float
 
+
+class WflGemmExArgs(C.Structure):
+    """include/wfl_asr.h's wfl_gemm_ex_args, field for field (struct_bytes is filled in by the constructor)."""
+    _fields_ = [
+        ("struct_bytes", _L),
+        ("A", _P), ("lda", _L), ("tap_stride", _L), ("cin", _I), ("a8", _I),
+        ("W", _P), ("w8_scale", _P), ("a8_scale", _P), ("a8_lead", _L), ("a8_static", _F),
+        ("M", _I), ("N", _I), ("K", _I), ("n_valid", _I), ("P", _I), ("T", _I), ("c_pitch", _I),
+        ("C", _P), ("c_lo", _P), ("ldc", _L), ("c_lead", _L),
+        ("bias", _P), ("clip_bias", _P), ("clip_idx", _P), ("clip_T", _P), ("clip_ld", _I), ("act", _I),
+        ("res", _P), ("res_lo", _P), ("ldres", _L), ("alpha", _F), ("glu", _I), ("out_f32", _I), ("acc_f32", _I),
+        ("pos", _P), ("ldpos", _L),
+        ("ln_s", _P), ("ln_eps", _F), ("stats_nsl", _I), ("stats_out", _P), ("stats_in", _P), ("stats_lead", _L),
+        ("c8", _P), ("ldc8", _L), ("c8_inv_scale", _F), ("reserved", _I),
+        ("status", _P),
+    ]
+
+    def __init__(self, **kw):
+        super().__init__(**kw)
+        if "struct_bytes" not in kw:
+            self.struct_bytes = C.sizeof(WflGemmExArgs)
+
 # name -> (restype, argtypes); exactly the declarations of include/wfl_asr.h
 SIGNATURES = {
     "wfl_last_error": (C.c_char_p, []),
@@ -54,6 +76,7 @@ SIGNATURES = {
     "wfl_check": (_I, [_P, _P, _L, _I, _I, _P]),
     "wfl_logmel": (_I, [_P, _P, _L, _P, _I, _I, _P, _P, _L, _P]),
     "wfl_op_gemm": (_I, [_P, _L, _I, _L, _P, _I, _I, _I, _I, _I, _I, _P, _L, _L, _I, _P, _P, _L, _F, _I, _I, _I, _P]),
+    "wfl_op_gemm_ex": (_I, [C.POINTER(WflGemmExArgs), C.POINTER(_I), _P]),
     "wfl_op_gemm_split": (_I, [_P, _P, _L, _I, _L, _P, _I, _I, _I, _I, _I, _I, _P, _P, _L, _L, _I, _P, _P, _P, _L, _F, _I, _I, _P]),
     "wfl_op_gemm_ln": (_I, [_P, _L, _P, _I, _I, _I, _I, _I, _I, _P, _L, _L, _I, _P, _P, _F, _I, _P]),
     "wfl_op_gemm_mx": (_I, [_P, _P, _L, _P, _P, _P, _F, _I, _I, _I, _I, _I, _P, _L, _L, _I, _P, _P, _P, _P, _F, _I, _P, _P, _L, _F, _P, _P]),

@@ -72,8 +72,8 @@ struct GemmArgs {
   unsigned char* c8_lo;     // gemm_mx.hip: the output as an e4m3 pair -- e4m3(16 (out * c8_inv_scale - hi)) goes here (ld = ldc8)
   long ldc8;
   float c8_inv_scale;
-  unsigned* err;            // the forward's error word or null: an e4m3 output that saturates (|x| * c8_inv_scale > 448, or NaN) ORs bit 1
-                            //   into it -- a fixed output scale never clips silently (round 4)
+  unsigned* err;            // the forward's error word or null: an e4m3 output that saturates (|x| * c8_inv_scale > 448, or NaN) ORs the value 2
+                            //   (bit 1 of the mask as wfl_asr.h numbers `status`: bit 0 is 1, bit 1 is 2) into it -- a fixed output scale never clips silently (round 4)
   float alpha;              // out = res + alpha * act(v)
   const bf16_t* pos;        // [T][ldpos] added after the activation (positional table) or null
   long ldpos;
@@ -120,7 +120,7 @@ struct AttnArgs {
   unsigned char* O8_lo;   // round 4: the context as an e4m3 PAIR -- e4m3(16 (context * o8_scale - hi)) goes here (ld = ldo8), or null
   long ldo8;
   float o8_scale;
-  unsigned* err;          // the forward's error word or null: a context element that saturates e4m3 (or is NaN) ORs bit 1 into it
+  unsigned* err;          // the forward's error word or null: a context element that saturates e4m3 (or is NaN) ORs the value 2 (bit 1) into it
 };
 
 // One BiLSTM layer's recurrence (lstm.hip)

@@ -288,7 +288,10 @@ __global__ __launch_bounds__(512) void gemm_mx_kernel(GemmArgs p) {
 #else
 #define MX_KEEP(k) (k)
 #endif
-    float amax8 = 0.f;                               // e4m3 output: largest stored |x| * scale (above 448 it did not fit)
+    // e4m3 output: the largest stored |x| * scale as the float's BIT PATTERN (unsigned order = numeric order for non-negative floats, every
+    // NaN above +Inf): above 448.0's pattern the element did not fit or was NaN.  (A float maximum dropped a NaN, and the clamp stored it
+    // as a finite byte without a word.)
+    unsigned amax8 = 0u;
 #pragma unroll
     for (int u = 0; u < MT; ++u) {
       __builtin_amdgcn_sched_barrier(0);
@@ -308,13 +311,15 @@ __global__ __launch_bounds__(512) void gemm_mx_kernel(GemmArgs p) {
           }
         const bool keep = orow[u] >= 0 && nb + 32 * h < p.n_valid;
         if (OUT != 0) {
-          const float keepf = keep ? 1.f : 0.f;
+          const unsigned keepm = keep ? 0x7fffffffu : 0u;
           int wv[2] = {0, 0}, lv[2] = {0, 0};        // e4m3 bytes of the run of 8 channels: hi plane, lo plane
 #pragma unroll
           for (int e = 0; e < 8; e += 2) {           // two values at a time: a packed hi word half, then what its rounding left behind
             typedef __attribute__((ext_vector_type(2))) float f32x2_;
             const float t0 = x[e] * p.c8_inv_scale, t1 = x[e + 1] * p.c8_inv_scale;
-            amax8 = fmaxf(amax8, fmaxf(fabsf(t0), fabsf(t1)) * keepf);
+            const unsigned b0 = __builtin_bit_cast(unsigned, t0) & keepm, b1 = __builtin_bit_cast(unsigned, t1) & keepm;
+            amax8 = amax8 > b0 ? amax8 : b0;
+            amax8 = amax8 > b1 ? amax8 : b1;
             const float y0 = fminf(fmaxf(t0, -448.f), 448.f), y1 = fminf(fmaxf(t1, -448.f), 448.f);
             const bool up = (e & 2) != 0;
             wv[e >> 2] = up ? __builtin_amdgcn_cvt_pk_fp8_f32(y0, y1, wv[e >> 2], true) : __builtin_amdgcn_cvt_pk_fp8_f32(y0, y1, wv[e >> 2], false);
@@ -403,7 +408,7 @@ __global__ __launch_bounds__(512) void gemm_mx_kernel(GemmArgs p) {
       if (RES && u + RING < MT) load_res(u + RING, u % RING);
     }
     if (OUT != 0 && p.err) {
-      if (__builtin_amdgcn_ballot_w64(amax8 > 448.f) && lane == 0) atomicOr(p.err, 2u);
+      if (__builtin_amdgcn_ballot_w64(amax8 > 0x43e00000u /* 448.0f */) && lane == 0) atomicOr(p.err, 2u);
     }
   };
 

@@ -457,7 +457,10 @@ __global__ __launch_bounds__(512) void gemm_stream_kernel(GemmArgs p) {
 #define WFL_KEEP(k) (k)
 #endif
     float t1 = 0.f, t2 = 0.f;
-    float amax8 = 0.f;                               // OUT8: largest stored |x| * scale (above 448 it did not fit e4m3)
+    // OUT8: the largest stored |x| * scale, as the BIT PATTERN of the float (for non-negative floats the unsigned order is the numeric one,
+    // and every NaN pattern lies above +Inf's): above 448.0's pattern the element did not fit e4m3 or was NaN.  (A float maximum -- v_max_f32
+    // returns the operand that is a number -- dropped a NaN, which the clamp below then stored as a finite byte without a word.)
+    unsigned amax8 = 0u;
 #pragma unroll
     for (int u = 0; u < MT; ++u) {
       __builtin_amdgcn_sched_barrier(0);            // one 16-frame tile at a time: keeps the register footprint bounded
@@ -490,11 +493,12 @@ __global__ __launch_bounds__(512) void gemm_stream_kernel(GemmArgs p) {
         const bool keep = orow[u] >= 0 && nb + 32 * h < p.n_valid;
         if (OUT8) {                                  // e4m3 (saturating at +-448) instead of bf16: 8 bytes per run of 8 channels
           int w0 = 0, w1 = 0;
-          const float keepf = keep ? 1.f : 0.f;
+          const unsigned keepm = keep ? 0x7fffffffu : 0u;
 #pragma unroll
           for (int e = 0; e < 8; ++e) {
             const float y = x[e] * p.c8_inv_scale;
-            amax8 = fmaxf(amax8, fabsf(y) * keepf);
+            const unsigned yb = __builtin_bit_cast(unsigned, y) & keepm;
+            amax8 = amax8 > yb ? amax8 : yb;
             x[e] = fminf(fmaxf(y, -448.f), 448.f);
           }
           w0 = __builtin_amdgcn_cvt_pk_fp8_f32(x[0], x[1], w0, false); w0 = __builtin_amdgcn_cvt_pk_fp8_f32(x[2], x[3], w0, true);
@@ -531,7 +535,7 @@ __global__ __launch_bounds__(512) void gemm_stream_kernel(GemmArgs p) {
       if (RES && u + RING < MT) load_res(u + RING, u % RING);
     }
     if (OUT8 && p.err) {                             // (only elements that were stored are judged: halo rows and padding columns are not)
-      if (__builtin_amdgcn_ballot_w64(amax8 > 448.f) && lane == 0) atomicOr(p.err, 2u);
+      if (__builtin_amdgcn_ballot_w64(amax8 > 0x43e00000u /* 448.0f */) && lane == 0) atomicOr(p.err, 2u);
     }
     if (STATS) {
       // The last of the group's four waves to get here adds the four partials of every row in a fixed order (bit-exact

@@ -2221,6 +2221,40 @@ int32_t wfl_op_gemm_split(const void* A_hi, const void* A_lo, int64_t lda, int32
   return r ? fail(r, "wfl_op_gemm_split: invalid arguments or launch failure (" + std::to_string(r) + ")") : 0;
 }
 
+int32_t wfl_op_gemm_ex(const wfl_gemm_ex_args* x, int32_t* kernel_id, void* stream) {
+  if (kernel_id) *kernel_id = 0;
+  if (!x || x->struct_bytes != (int64_t)sizeof(wfl_gemm_ex_args)) return fail(-1, "wfl_op_gemm_ex: struct_bytes is not the size of wfl_gemm_ex_args");
+  if (!x->A || !x->W || (!x->C && !x->c8)) return fail(-1, "wfl_op_gemm_ex: null argument");
+  // (fields the dispatch would pass over without a word)
+  if (x->res_lo && !x->res) return fail(-1, "wfl_op_gemm_ex: res_lo without res");
+  if (x->a8 != 0 && x->a8 != 1) return fail(-1, "wfl_op_gemm_ex: a8 is 0 or 1 here (2 / 3: wfl_op_gemm_mx)");
+  if (x->a8 && !x->w8_scale) return fail(-1, "wfl_op_gemm_ex: a8 without w8_scale");
+  if (x->c8 && !x->a8) return fail(-1, "wfl_op_gemm_ex: c8 without a8");
+  if (x->stats_in && !x->ln_s) return fail(-1, "wfl_op_gemm_ex: stats_in without ln_s");
+  if (x->acc_f32 && !x->out_f32) return fail(-1, "wfl_op_gemm_ex: acc_f32 without out_f32");
+  if (x->clip_bias && !x->clip_idx) return fail(-1, "wfl_op_gemm_ex: clip_bias without clip_idx");
+  GemmArgs g{};
+  g.A = (const bf16_t*)x->A; g.lda = x->lda; g.cin = x->cin > 0 ? x->cin : x->K; g.tap_stride = x->tap_stride;
+  g.W = (const bf16_t*)x->W; g.M = x->M; g.N = x->N; g.K = x->K; g.n_valid = x->n_valid; g.P = x->P; g.T = x->T;
+  g.C = x->C; g.c_lo = (bf16_t*)x->c_lo; g.ldc = x->ldc; g.c_lead = x->c_lead; g.c_pitch = x->c_pitch;
+  g.bias = x->bias; g.clip_bias = x->clip_bias; g.clip_idx = x->clip_idx; g.clip_ld = x->clip_ld; g.clip_T = x->clip_T;
+  g.res = (const bf16_t*)x->res; g.res_lo = (const bf16_t*)x->res_lo; g.ldres = x->ldres; g.alpha = x->alpha;
+  g.act = x->act; g.glu = x->glu; g.out_f32 = x->out_f32; g.acc_f32 = x->acc_f32;
+  g.pos = (const bf16_t*)x->pos; g.ldpos = x->ldpos;
+  g.ln_s = x->ln_s; g.ln_eps = x->ln_eps; g.stats_out = x->stats_out; g.stats_in = x->stats_in; g.stats_nsl = x->stats_nsl;
+  g.stats_lead = x->stats_lead;
+  g.w8_scale = x->w8_scale; g.a8 = x->a8; g.a8_scale = x->a8_scale; g.a8_lead = x->a8_lead; g.a8_static = x->a8_static;
+  g.c8 = (unsigned char*)x->c8; g.ldc8 = x->ldc8; g.c8_inv_scale = x->c8_inv_scale; g.err = (unsigned*)x->status;
+  // only the streaming kernel writes or reads row statistics: gemm256 / the 128-tile kernel would run and ignore them
+  if ((g.stats_out || g.stats_in) && !wfl_gemm_stream_takes(g))
+    return fail(-4, "wfl_op_gemm_ex: stats_out / stats_in on a launch the streaming kernel does not take");
+  g_wfl_gemm_kernel_id = 0;
+  const int r = wfl_launch_gemm(g, (hipStream_t)stream);
+  if (r) return fail(r, "wfl_op_gemm_ex: invalid arguments, a combination no kernel takes, or launch failure (" + std::to_string(r) + ")");
+  if (kernel_id) *kernel_id = g_wfl_gemm_kernel_id;
+  return 0;
+}
+
 int32_t wfl_op_attention(const void* QK, int64_t ldqk, int64_t lead, const void* V, int64_t ldv, void* O, int64_t ldo, int32_t B, int32_t T,
                          int32_t P, int32_t heads, int32_t d, void* stream) {
   AttnArgs a{};
