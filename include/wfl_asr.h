@@ -510,6 +510,35 @@ int32_t wfl_align_optional(const float* logits, int64_t ldl, int32_t C, int32_t 
                            void* workspace, int64_t workspace_bytes, int32_t* ids, int32_t* tok, float* score, int32_t* skipped,
                            int32_t* status, void* stream);
 
+/* ---- wfl_align over a transcript GRAPH: pronunciation variants, several spellings of a stretch of the transcript, chosen jointly by the
+ * search (`postprocess.transcript_variants`; wfl-asr_amd/align.py, csrc/align_graph.hip).  Clip b has N = n_slots_host[b] slots in
+ * topological order (rows slot_off_host[b] .. of tok_cls, slot_pred, slot_final and taken).  Slot k carries tok_cls exactly as a wfl_align
+ * token does, a predecessor list slot_pred[k][0..7] (int32, the used entries first: -1 = START, -2 = unused, otherwise a clip-local slot
+ * j with k - 255 <= j < k) and slot_final[k] in {0, 1}.  States G_k, B_k, I_k per slot and one end gap G_end:
+ *     m_k(t)   = max{ G_k, then for p in pred(k) in list order: I_p, B_p }  of frame t - 1      (the first listed wins an exact tie)
+ *     G_k(t)   = m_k(t) + EG_t        B_k(t) = m_k(t) + EB_t(k)        I_k(t) = max{I_k, B_k}(t-1) + EI_t(k)
+ *     G_end(t) = max{ G_end, then for final f in slot order: I_f, B_f }(t-1) + EG_t
+ *     start: frame 0 is G_k or B_k of a slot that lists START (G_end when N == 0)
+ *     end:   G_end | I_f | B_f over the final slots, in that order
+ * Emissions, gap classes, the decisions on the raw logits, the renormalisation every 16 frames and the meaning of score are wfl_align's.
+ * With pred(k) = {k - 1}, START for slot 0 and slot N - 1 alone final this is wfl_align's lattice state for state (G_k its G_k, G_end its
+ * G_N), and ids, tok and status are wfl_align's.
+ * Outputs (device): ids and tok per frame as wfl_align writes them, tok the clip-local slot or -1 in a gap; score[b]; taken[k] ([total
+ * slots] int32) 1 for a slot the path visits, else 0.  status[b]: 0 ok; 1 no path (the best end state is -inf, found as the windowed
+ * kernels find it: every way through the graph needs more frames than T, or no slot lists START); 2 N > 2047; 4 a bad class or no gap
+ * class, a slot without a predecessor, a predecessor >= k, < -2 or more than 255 slots back, a used entry behind an unused one, a
+ * slot_final other than 0 | 1, N > 0 and no final slot.  A clip with status != 0 gets ids = o_id, tok = -1, taken = 0, score 0; its
+ * backpointers are never walked.  Clips are independent (one workgroup each): a clip aligned alone equals the same clip inside any
+ * batch, bit for bit.  Host-side negative returns as wfl_align's, and: a null slot_pred, slot_final or taken with any slot present.
+ * Workspace: 8 bits per slot and frame (4 the choice of m_k, 1 I_k's, 1 "X_k = max{I_k, B_k} was B_k") in wfl_align's words per thread,
+ * and one word per frame for G_end's choice: per clip round_up(T * (words(N) + 1), 64) 4-byte words, words(N) = 64 (N <= 127), 256
+ * (N <= 1023), 512 (N <= 2047); 0 for a clip with T == 0 or N > 2047.  wfl_align_graph_workspace_bytes returns that sum in bytes. */
+int64_t wfl_align_graph_workspace_bytes(const int32_t* n_frames_host, const int32_t* n_slots_host, int32_t n_clips);
+int32_t wfl_align_graph(const float* logits, int64_t ldl, int32_t C, int32_t o_id, const int64_t* frame_off_host,
+                        const int32_t* n_frames_host, const int32_t* slot_off_host, const int32_t* n_slots_host, const int32_t* tok_cls,
+                        const int32_t* gap_cls, int32_t n_clips, const int32_t* slot_pred, const int32_t* slot_final, void* workspace,
+                        int64_t workspace_bytes, int32_t* ids, int32_t* tok, float* score, int32_t* taken, int32_t* status, void* stream);
+
 /* ---- wfl_align with filler tokens: a token that matches anything, for a stretch of audio the transcript does not spell
  * (`postprocess.filler_token`; wfl-asr_amd/align.py).  wfl_align_windowed's arguments (tok_win may be null: no windows) plus tok_fill
  * (device), [total tokens] int32 0 | 1, rows as tok_cls, and filler_penalty = phi >= 0 in nats per frame.  The states, arcs and tie rules

@@ -115,6 +115,8 @@ SIGNATURES = {
     "wfl_align_optional": (_I, [_P, _L, _I, _I, _P, _P, _P, _P, _P, _P, _P, _I, _P, _F, _P, _L, _P, _P, _P, _P, _P, _P]),
     "wfl_align_filler_workspace_bytes": (_L, [_P, _P, _I]),
     "wfl_align_filler": (_I, [_P, _L, _I, _I, _P, _P, _P, _P, _P, _P, _P, _I, _P, _F, _P, _L, _P, _P, _P, _P, _P]),
+    "wfl_align_graph_workspace_bytes": (_L, [_P, _P, _I]),
+    "wfl_align_graph": (_I, [_P, _L, _I, _I, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _L, _P, _P, _P, _P, _P, _P]),
     "wfl_align_duration_prior_workspace_bytes": (_L, [_P, _P, _I, _I]),
     "wfl_align_duration_prior": (_I, [_P, _L, _I, _I, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _I, _I, _P, _L, _P, _P, _P, _P, _P]),
     "wfl_align_duration_prior_posterior_workspace_bytes": (_L, [_P, _P, _I, _I]),

@@ -52,8 +52,15 @@ token gets one contiguous, time-ordered run of frames, none is dropped.
   windows_feasible      the host rule that predicts the windowed search's status 1
   draft_windows         a draft's start times -> per-token windows on the file's rows, through the chunk clock
   read_draft            the draft .lab of a file (phonotactics.read_lab, the HTK reader the bigram estimate uses)
+  parse_variants / compile_graph   `postprocess.transcript_variants`: the `( a | b c | )` groups of a `.txt` -> its elements -> the
+                        slots, predecessors and finals of a transcript graph (TranscriptGraph)
+  viterbi_align_graph   the search over such graphs, choosing among the variants jointly (`wfl_align_graph`, csrc/align_graph.hip)
+                        -> viterbi_align's four and `taken` per slot; chain_graph: a plain transcript as a graph; pack_graph: the
+                        tables of a batch, packed and uploaded once
+  variant_choices       one file's VariantChoice rows
 
-The records of those rows (TokenEdit, PlaceInsertion, SkippedToken, OptionalTokenScore, FillerSpan, FillerScore, TokenDuration) and
+The records of those rows (TokenEdit, PlaceInsertion, SkippedToken, OptionalTokenScore, FillerSpan, FillerScore, TokenDuration,
+VariantChoice) and
 the files they are written to are reports.py's; the records are imported here, so align.TokenEdit and the others name them too.
 """
 from __future__ import annotations
@@ -68,7 +75,7 @@ from . import _lib
 from . import native_post as npost
 from ._lib import back_to_back, host_ptr as _hp, ptr as _ptr
 from .reports import (FillerScore, FillerSpan, OptionalTokenScore, PlaceInsertion, SkippedToken, TokenDuration,  # noqa: F401
-                      TokenEdit)
+                      TokenEdit, VariantChoice)
 
 MAX_TOKENS = 4096          # wfl_align's token cap per clip (status 2 above it)
 MAX_ALTERNATIVES = 4       # (B, I) pairs per token
@@ -397,6 +404,7 @@ _ENTRIES = {
     "wfl_align_duration_prior": ("wfl_align_duration_prior", True, False),
     "wfl_align_duration_prior_posterior": ("wfl_align_duration_prior_posterior", True, False),
     "wfl_align_duration_prior_counts": ("wfl_align_duration_prior_counts", True, False),
+    "wfl_align_graph": ("wfl_align_graph", False, False),
 }
 
 
@@ -1334,3 +1342,252 @@ def token_durations(tokens, frames, rows, table, tok_post, start_mean, start_sd,
         out.append(TokenDuration(k, t.token, t.start_s, t.end_s, d, prior, p, smu * frame_duration, ssd * frame_duration,
                                  emu * frame_duration, esd * frame_duration, d + emu - smu))
     return out
+
+
+# ------------------------------------------------------------------------------------------------------- pronunciation variants
+VARIANT_CHARS = "(|)"       # syntax of a `{audio}.txt` under `postprocess.transcript_variants`, wherever they occur
+MAX_VARIANTS = 4            # variants per group
+MAX_SLOTS = 2047            # wfl_align_graph's slot cap per clip (status 2 above it)
+MAX_PREDECESSORS = 8        # predecessors per slot
+MAX_SPAN = 255              # a predecessor is at most this many slots back
+START, UNUSED = -1, -2      # slot_pred's values that are no slot
+
+
+def graph_workspace_bytes(n_frames, n_slots) -> int:
+    return _workspace_bytes("wfl_align_graph_workspace_bytes", n_frames, n_slots)
+
+
+def has_variants(tokens) -> bool:
+    """Whether a transcript's tokens (the whitespace-separated words of a `.txt`) hold any of the three syntax characters."""
+    return any(ch in tok for tok in tokens for ch in VARIANT_CHARS)
+
+
+def variant_name_collisions(output_names):
+    """The output names of a label set that hold one of the three syntax characters: with transcript_variants on they could not be
+    spelled, so the caller that knows the model refuses them by name."""
+    return sorted({n for n in output_names if any(ch in n for ch in VARIANT_CHARS)})
+
+
+def parse_variants(tokens, notes=None):
+    """The words of a `.txt` -> its elements, in order: a plain token is a str, a group a tuple of 2 to MAX_VARIANTS variants, each a
+    tuple of tokens (the empty tuple: the group may be left out); the first variant is the transcript as written.  `(`, `|` and `)`
+    are syntax wherever they occur, attached to a name or alone.  A ValueError names the place (the 1-based word) of: nesting, an
+    unbalanced parenthesis, a `|` outside a group, a group with fewer than 2 distinct variants, one with more than MAX_VARIANTS.
+    Duplicate variants inside a group collapse (the first stays); `notes` (a list) receives one line for each such group."""
+    elements, group, current, opened = [], None, None, 0
+    for place, word in enumerate(tokens, 1):
+        name = ""
+        for ch in list(word) + [" "]:
+            if ch not in VARIANT_CHARS and ch != " ":
+                name += ch
+                continue
+            if name:
+                (current if group is not None else elements).append(name)
+                name = ""
+            if ch == "(":
+                if group is not None:
+                    raise ValueError(f"word {place}: a group inside the group opened at word {opened} (variants do not nest)")
+                group, current, opened = [], [], place
+            elif ch == "|":
+                if group is None:
+                    raise ValueError(f"word {place}: '|' outside a group")
+                group.append(tuple(current))
+                current = []
+            elif ch == ")":
+                if group is None:
+                    raise ValueError(f"word {place}: ')' without a '('")
+                group.append(tuple(current))
+                if len(group) > MAX_VARIANTS:
+                    raise ValueError(f"word {place}: the group opened at word {opened} has {len(group)} variants (at most {MAX_VARIANTS})")
+                distinct = list(dict.fromkeys(group))
+                if len(distinct) < 2:
+                    raise ValueError(f"word {place}: the group opened at word {opened} needs at least 2 distinct variants")
+                if len(distinct) < len(group) and notes is not None:
+                    notes.append(f"the group opened at word {opened} repeats a variant: {len(group) - len(distinct)} dropped")
+                elements.append(tuple(distinct))
+                group, current = None, None
+    if group is not None:
+        raise ValueError(f"word {opened}: '(' is never closed")
+    return elements
+
+
+class TranscriptGraph(NamedTuple):
+    """compile_graph's record of a transcript with variants."""
+    slots: list       # the token name of every slot, in topological order: element by element, a group's variants one after the other
+    preds: list       # per slot its predecessors, in order: START (-1) or earlier slots
+    final: list       # per slot 0 | 1: the path may end there
+    groups: list      # per group, in order: per variant its (first slot, one past its last slot); an empty variant is (k, k)
+    elements: list    # parse_variants' elements
+
+    @property
+    def first(self):
+        """The slots of the first-variant expansion, the transcript as written."""
+        out, k, gi = [], 0, 0
+        for el in self.elements:
+            if isinstance(el, str):
+                out.append(k)
+                k += 1
+            else:
+                a, b = self.groups[gi][0]
+                out.extend(range(a, b))
+                k = self.groups[gi][-1][1]
+                gi += 1
+        return out
+
+    def spelling(self, gi, v) -> str:
+        a, b = self.groups[gi][v]
+        return " ".join(self.slots[a:b])
+
+
+def compile_graph(elements) -> TranscriptGraph:
+    """parse_variants' elements -> the slots of wfl_align_graph.  A plain token's predecessors are the current frontier (at first:
+    START) and it becomes the frontier; every non-empty variant of a group opens from the frontier and chains inside, and the new
+    frontier is the variants' last slots, plus the old frontier for an empty variant -- order kept, entries deduplicated.  The finals
+    are the last frontier.  ValueError: a transcript whose every element is a group with an empty variant (it could spell nothing),
+    a slot that would need more than MAX_PREDECESSORS predecessors (runs of adjacent optional groups), a group of more than MAX_SPAN
+    slots, a predecessor more than MAX_SPAN slots back."""
+    if all(not isinstance(el, str) and () in el for el in elements):
+        raise ValueError("every element of the transcript is a group with an empty variant: it could spell nothing")
+    slots, preds, groups = [], [], []
+    frontier = [START]
+
+    def add(name, pr, where):
+        if len(pr) > MAX_PREDECESSORS:
+            raise ValueError(f"{where}: token {name!r} would need {len(pr)} predecessors (at most {MAX_PREDECESSORS}): too many adjacent "
+                             "optional groups in front of it")
+        k = len(slots)
+        if any(p != START and k - p > MAX_SPAN for p in pr):
+            raise ValueError(f"{where}: token {name!r} would follow a token more than {MAX_SPAN} slots back")
+        slots.append(name)
+        preds.append(list(pr))
+        return k
+
+    for ei, el in enumerate(elements, 1):
+        where = f"element {ei}"
+        if isinstance(el, str):
+            frontier = [add(el, frontier, where)]
+            continue
+        if sum(len(v) for v in el) > MAX_SPAN:
+            raise ValueError(f"{where}: a group of {sum(len(v) for v in el)} slots (at most {MAX_SPAN})")
+        ranges, new = [], []
+        for var in el:
+            a = len(slots)
+            if not var:
+                new.extend(frontier)
+            else:
+                last = None
+                for name in var:
+                    last = add(name, frontier if last is None else [last], where)
+                new.append(last)
+            ranges.append((a, len(slots)))
+        groups.append(ranges)
+        frontier = list(dict.fromkeys(new))
+    final = [0] * len(slots)
+    for k in frontier:
+        if k != START:
+            final[k] = 1
+    return TranscriptGraph(slots, preds, final, groups, list(elements))
+
+
+def chain_graph(n):
+    """(preds, final) of the chain of n slots: wfl_align's lattice as a graph."""
+    return [[START if k == 0 else k - 1] for k in range(n)], [int(k == n - 1) for k in range(n)]
+
+
+def _pack_graph(slot_preds, slot_final, N):
+    """Per clip the predecessor lists and the final flags of its slots -> ([max(slots, 1), 8] int32, unused entries -2, and
+    [max(slots, 1)] int32), rows as the token table's.  The values are not judged here: the kernel's STATUS_BAD_CLASS is."""
+    if len(slot_preds) != len(N) or len(slot_final) != len(N):
+        raise ValueError("slot_preds and slot_final need one entry per clip")
+    total = max(int(N.sum()), 1)
+    pr = np.full((total, MAX_PREDECESSORS), UNUSED, np.int64)
+    fn = np.zeros(total, np.int64)
+    k0 = 0
+    for p, f, n in zip(slot_preds, slot_final, N):
+        if len(p) != n or len(f) != n:
+            raise ValueError(f"a clip with {n} slots needs {n} predecessor lists and {n} final flags")
+        for k, row in enumerate(p):
+            row = list(row)
+            if len(row) > MAX_PREDECESSORS:
+                raise ValueError(f"a slot has at most {MAX_PREDECESSORS} predecessors, got {len(row)}")
+            pr[k0 + k, :len(row)] = row
+        fn[k0:k0 + n] = np.asarray(f, np.int64).reshape(-1) if n else 0
+        k0 += int(n)
+    if min(pr.min(), fn.min()) < -2 ** 31 or max(pr.max(), fn.max()) > 2 ** 31 - 1:
+        raise ValueError("predecessors and final flags are int32")
+    return pr.astype(np.int32), fn.astype(np.int32)
+
+
+class PackedGraph(NamedTuple):
+    """pack_graph's result: the PackedClips of the slots and the uploaded predecessor and final tables of a ragged batch."""
+    clips: PackedClips
+    d_pred: torch.Tensor      # [max(slots, 1), 8] int32
+    d_final: torch.Tensor     # [max(slots, 1)] int32
+
+
+def pack_graph(logits, n_frames, slot_classes, slot_preds, slot_final, gap_classes, frame_offsets=None) -> PackedGraph:
+    """Validate a ragged batch of transcript graphs and upload its tables once; pass the result as `packed=` to viterbi_align_graph
+    calls over the same batch."""
+    nb, T, N, F0, K0, tc, gc = _pack_clips(logits, n_frames, slot_classes, gap_classes, frame_offsets)
+    pr, fn = _pack_graph(slot_preds, slot_final, N)
+    dev = logits.device
+    return PackedGraph(PackedClips(nb, T, N, F0, K0, torch.from_numpy(tc).to(dev), torch.from_numpy(gc).to(dev)),
+                       torch.from_numpy(pr).to(dev), torch.from_numpy(fn).to(dev))
+
+
+def viterbi_align_graph(logits, n_frames, slot_classes, slot_preds, slot_final, gap_classes, o_id, frame_offsets=None, stream=None,
+                        packed=None):
+    """Forced alignment of a ragged batch of transcript GRAPHS on the GPU (wfl_align_graph): the search chooses among the variants.
+
+    slot_classes  per clip, per slot: 1..4 (B, I) class pairs, as viterbi_align's token_classes
+    slot_preds    per clip, per slot: its predecessors in order of preference, START (-1) or clip-local slots k - MAX_SPAN <= j < k,
+                  at most MAX_PREDECESSORS (compile_graph's preds; chain_graph's for a plain transcript)
+    slot_final    per clip, per slot: 0 | 1, the path may end in the slot
+    packed        pack_graph(...) of these same arguments, to pack and upload the tables once for several calls (default: packed here)
+    the others    as viterbi_align's
+    -> (ids, tok, score, status, taken): viterbi_align's four, tok the clip-local slot, and taken [slots] int32, 1 for a slot the
+    path visits, in the order of the clips' slots.  STATUS_INFEASIBLE: no path through the graph fits the frames; STATUS_OVER_CAP:
+    more than MAX_SLOTS slots; STATUS_BAD_CLASS also for a malformed graph (include/wfl_asr.h).  A clip with status != 0 has
+    taken = 0.  On chain_graph's lists ids, tok and status are viterbi_align's."""
+    if packed is None:
+        packed = pack_graph(logits, n_frames, slot_classes, slot_preds, slot_final, gap_classes, frame_offsets)
+    clips, d_pr, d_fn = packed
+    dev, rows, nb, ntok = logits.device, logits.shape[0], clips.nb, int(clips.N.sum())
+    ids = torch.empty(rows, dtype=torch.int32, device=dev)
+    tok = torch.empty(rows, dtype=torch.int32, device=dev)
+    score = torch.empty(max(nb, 1), dtype=torch.float32, device=dev)
+    status = torch.empty(max(nb, 1), dtype=torch.int32, device=dev)
+    taken = torch.empty(max(ntok, 1), dtype=torch.int32, device=dev)
+    _call("wfl_align_graph", logits, o_id, clips, (d_pr, d_fn), (ids, tok, score, taken, status), stream, temporaries=(d_pr, d_fn))
+    return ids, tok, score[:nb], status[:nb], taken[:ntok]
+
+
+def variant_choices(graph: TranscriptGraph, taken, segments, gain=None):
+    """One file's VariantChoice rows, one per group in order, from the path's `taken` flags (host values, one per slot) and its
+    segments [(start_s, end_s, token)], one per taken slot in order (path_segments with skipped = 1 - taken).  The chosen variant is
+    the one whose slots are taken -- the empty one where none is; its time is its first segment's start to its last segment's end,
+    for an empty one the time of the place: the start of the next taken slot's segment, the end of the last segment when nothing
+    follows.  gain: the file's gain in nats (None: the transcript as written has no path of its own)."""
+    flags = [int(f) for f in taken]
+    if len(flags) != len(graph.slots) or len(segments) != sum(flags):
+        raise ValueError("one flag per slot and one segment per taken slot")
+    seg_of, j = {}, 0
+    for k, f in enumerate(flags):
+        if f:
+            seg_of[k] = segments[j]
+            j += 1
+    rows = []
+    for gi, ranges in enumerate(graph.groups):
+        chosen = [v for v, (a, b) in enumerate(ranges) if b > a and all(flags[a:b])]
+        empty = [v for v, (a, b) in enumerate(ranges) if b == a]
+        if len(chosen) > 1 or (not chosen and (not empty or any(flags[ranges[0][0]:ranges[-1][1]]))):
+            raise ValueError(f"group {gi}: the taken slots are not one variant")
+        v = chosen[0] if chosen else empty[0]
+        a, b = ranges[v]
+        if b > a:
+            start, end = float(seg_of[a][0]), float(seg_of[b - 1][1])
+        else:
+            nxt = min((q for q in seg_of if q >= ranges[-1][1]), default=None)
+            start = end = float(seg_of[nxt][0]) if nxt is not None else (float(segments[-1][1]) if segments else 0.0)
+        rows.append(VariantChoice(gi, start, end, v, graph.spelling(gi, v), graph.spelling(gi, 0), gain))
+    return rows

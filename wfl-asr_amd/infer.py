@@ -454,7 +454,8 @@ class Labeler:
                     draft_tolerance=None, align_edits=None, align_insertions=None, min_duration=None, duration_scores=None,
                     optional_tokens=None, skip_penalty=None, optional_scores=None, filler_token=None, filler_penalty=None,
                     filler_scores=None, duration_prior=None, duration_prior_weight=None, duration_prior_scores=None,
-                    decode_duration_prior=None, decode_duration_prior_weight=None, decode_duration_scores=None, bigram_scores=None):
+                    decode_duration_prior=None, decode_duration_prior_weight=None, decode_duration_scores=None,
+                    transcript_variants=None, bigram_scores=None):
         """-> list (per file) of [(start_s, end_s, phoneme)] after merge + forced alignment; with align_scores, duration_scores,
         decode_scores, bigram_scores or decode_duration_scores, (that list, scores); with align_edits the tuple goes on with one more list, edits, and with
         align_insertions it ends with one more, insertions; with optional_tokens it ends with the list skipped; with a filler_token
@@ -588,7 +589,16 @@ class Labeler:
         decode_scores for a duration-prior decode -- the same scores[i] records, from a semi-Markov forward-backward pass over the
         grammar with the search's transition table and duration table (decode.decode_posteriors_duration,
         wfl_decode_duration_posterior), so the posterior scores the grammar the search ran on.  The segments are the same with and
-        without."""
+        without.
+
+        transcript_variants (with align "viterbi" only; None: config postprocess.transcript_variants, else off): `(`, `|` and `)` in
+        a `{audio}.txt` are syntax -- `k a ( t | d ) o ( N | ) ( ts u | s u )` offers 2 to 4 spellings of a stretch, the first the
+        transcript as written, an empty one making the stretch optional -- and a file whose transcript holds such a group is
+        searched over the graph of all of them (align.viterbi_align_graph, wfl_align_graph): the variants are chosen jointly.  Its
+        segments are the chosen slots'; the tuple ends with the list variants, per such file its align.VariantChoice rows.  A file
+        without a group is searched by exactly the calls it is searched by without the option.  The greedy fallback and the
+        end-pause rule take the transcript as written.  A malformed transcript is refused, naming the file and the place; the
+        options whose lattices are chains are refused beside it, each by name."""
         opts = self.options(align=align, align_scores=align_scores, decode=decode, switch_penalty=switch_penalty,
                             decode_scores=decode_scores, phoneme_bigram=phoneme_bigram, bigram_weight=bigram_weight,
                             bigram_scores=bigram_scores, align_draft=align_draft, draft_tolerance=draft_tolerance,
@@ -597,7 +607,8 @@ class Labeler:
                             optional_scores=optional_scores, filler_token=filler_token, filler_penalty=filler_penalty,
                             filler_scores=filler_scores, duration_prior=duration_prior, duration_prior_weight=duration_prior_weight,
                             duration_prior_scores=duration_prior_scores, decode_duration_prior=decode_duration_prior,
-                            decode_duration_prior_weight=decode_duration_prior_weight, decode_duration_scores=decode_duration_scores)
+                            decode_duration_prior_weight=decode_duration_prior_weight, decode_duration_scores=decode_duration_scores,
+                            transcript_variants=transcript_variants)
         reports = R.Reports.for_options(opts)
         final, scores = self._label_scored(audio_paths, opts, lang_id, confidence_threshold, verbose, reports)
         out = (final, scores) if opts.scored else (final,)
@@ -627,7 +638,7 @@ class Labeler:
             raise ValueError(f"Error: Language ID ({lang_id}) is higher than the latest ID ({max(self.lang2id.values())}) "
                              f"of this model.\n Languages and Codes available: {self.lang2id}")
         final, scores = [None] * len(audio_paths), [None] * len(audio_paths)
-        free, with_t = list(range(len(audio_paths))), []
+        free, with_t, graphs = list(range(len(audio_paths))), [], {}
         if opts.align == "viterbi":
             forced = [_read_forced(p, verbose) for p in audio_paths]
             drafts = [_read_draft(p, opts.align_draft, forced[fi]) if opts.align_draft else None for fi, p in enumerate(audio_paths)]
@@ -638,6 +649,8 @@ class Labeler:
                         forced[fi], merged = AL.collapse_fillers(tr, opts.filler_token)
                         if merged:
                             print(f"{audio_paths[fi]}: {merged} adjacent filler tokens collapsed")
+            if opts.transcript_variants:                  # a transcript with groups: its graph; the file goes on as written
+                graphs = _read_variants(audio_paths, forced, self._names_for(self._lang_name(lang_id))[1])
             with_t = [fi for fi in free if forced[fi] is not None]
             free = [fi for fi in free if forced[fi] is None]
 
@@ -659,7 +672,8 @@ class Labeler:
             final[fi] = self._match_forced(audio_paths[fi], segs, verbose)
         if with_t:
             got = self._label_viterbi(paths(with_t), [forced[fi] for fi in with_t], [drafts[fi] for fi in with_t], opts, lang_id,
-                                      confidence_threshold, verbose, prior)
+                                      confidence_threshold, verbose, prior,
+                                      **({"graphs": {j: graphs[fi] for j, fi in enumerate(with_t) if fi in graphs}} if graphs else {}))
             for fi, rec in zip(with_t, got):
                 final[fi], scores[fi] = rec.segments, rec.score
                 if reports is not None:
@@ -1054,7 +1068,7 @@ class Labeler:
                 n_frames += int(frames[b])
         return total, succ, total_logz, total_lse, n_frames, skipped
 
-    def _label_viterbi(self, audio_paths, transcripts, drafts, opts, lang_id, threshold, verbose, prior=None):
+    def _label_viterbi(self, audio_paths, transcripts, drafts, opts, lang_id, threshold, verbose, prior=None, graphs=None):
         """Files with a transcript, align="viterbi" -> one ViterbiLabel per file.  Their chunks are forwarded with logits (kept on
         the device); the free decode of the same forward gives the greedy result, which the pause rule at the ends needs and which a
         file falls back to (with a message) when its transcript cannot be aligned.  Each file's chunks' valid logits rows are
@@ -1062,8 +1076,11 @@ class Labeler:
         that goes through the stages -- _greedy_and_plans, _clip_constraints, _search, _score, _clip_label -- and only ids / tok /
         score / status and the scoring calls' small tables come back to the host.  drafts: per file its draft segments or None
         (opts.align_draft; the transcript is then the draft's labels).  prior (opts.duration_prior): _duration_prior's pair; the
-        search is then the explicit-duration one."""
+        search is then the explicit-duration one.  graphs (opts.transcript_variants; None: none): {file: its align.TranscriptGraph}
+        for the files whose transcript holds groups -- `transcripts` has their first-variant expansion, for the greedy result and the
+        end-pause rule -- which are searched by _search_variants instead; every other file goes through the stages as without."""
         lang_name = self._lang_name(lang_id)
+        graphs = graphs or {}
         drafts = drafts if drafts is not None else [None] * len(audio_paths)
         sub_pairs = sub_out = None
         if opts.align_edits or opts.align_insertions:
@@ -1075,7 +1092,10 @@ class Labeler:
             greedy, free_segs, plans = self._greedy_and_plans(sel, by_file, free, audio_paths, transcripts, lang_name,
                                                               opts.filler_token)
             aligned = {}
-            run = [fi for fi in sel if fi in plans]          # one ragged search over the files that can be aligned
+            run = [fi for fi in sel if fi in plans and fi not in graphs]     # one ragged search over the files that can be aligned
+            grun = [fi for fi in sel if fi in plans and fi in graphs]
+            if grun:                                         # the files with variants: one ragged search over their graphs
+                aligned.update(self._search_variants(grun, graphs, rows, by_file, audio_paths, transcripts, free_segs, lang_name))
             if run:
                 paths = [audio_paths[fi] for fi in run]
                 frames, lg = self._file_rows(rows, by_file, run)
@@ -1100,6 +1120,52 @@ class Labeler:
                     for key in NOT_ALIGNED_LINES:
                         if R.REPORTS[key].enabled(opts):
                             print(f"{audio_paths[fi]}: {R.REPORTS[key].missing} (the file was not Viterbi-aligned)")
+        return out
+
+    def _search_variants(self, grun, graphs, rows, by_file, audio_paths, transcripts, free_segs, lang_name):
+        """The files of a wave whose transcripts hold groups -> {file: ViterbiLabel} for those the graph search aligned; one line for
+        every other (it keeps its greedy result).  Two calls over the same rows: align.viterbi_align_graph over the graphs, and
+        align.viterbi_align over the transcripts as written, whose score the gain is measured against.  Both see the gap classes of
+        every slot's name, so SP / AP spelled in any variant count as spelled."""
+        remap, names = self._names_for(lang_name)
+        slot_alts = {}
+        for fi in grun:
+            alts, why = AL.token_alternatives(graphs[fi].slots, self._table, remap, names, self.labels)
+            if alts is None:
+                print(f"{audio_paths[fi]}: viterbi alignment not possible ({why}); using the greedy alignment")
+            else:
+                slot_alts[fi] = alts
+        grun = [fi for fi in grun if fi in slot_alts]
+        if not grun:
+            return {}
+        frames, lg = self._file_rows(rows, by_file, grun)
+        gaps = [AL.gap_classes(self.labels, graphs[fi].slots) for fi in grun]
+        o_id = self.labels.index("O")
+        d_ids, d_tok, d_score, d_st, d_taken = AL.viterbi_align_graph(lg, frames, [slot_alts[fi] for fi in grun],
+                                                                      [graphs[fi].preds for fi in grun],
+                                                                      [graphs[fi].final for fi in grun], gaps, o_id)
+        _, _, w_score, w_st = AL.viterbi_align(lg, frames, [[slot_alts[fi][k] for k in graphs[fi].first] for fi in grun], gaps, o_id)
+        ids, tok, taken = d_ids.cpu().numpy(), d_tok.cpu().numpy(), d_taken.cpu().numpy()
+        score, status, w_score, w_st = (t.cpu().numpy() for t in (d_score, d_st, w_score, w_st))
+        f0 = back_to_back(frames)
+        k0 = np.concatenate([[0], np.cumsum([len(graphs[fi].slots) for fi in grun])]).astype(np.int64)
+        out = {}
+        for b, fi in enumerate(grun):
+            g, n, pos = graphs[fi], frames[b], int(f0[b])
+            if status[b] != AL.STATUS_OK:
+                why = {AL.STATUS_INFEASIBLE: f"no way through the {len(g.groups)} groups' variants fits {n} frames",
+                       AL.STATUS_OVER_CAP: f"{len(g.slots)} slots, over the cap of {AL.MAX_SLOTS}"}.get(int(status[b]),
+                                                                                                        f"status {int(status[b])}")
+                print(f"{audio_paths[fi]}: viterbi alignment not possible ({why}); using the greedy alignment")
+                continue
+            tk = taken[int(k0[b]):int(k0[b + 1])]
+            segs = AL.path_segments(ids[pos:pos + n], tok[pos:pos + n], *self._chunk_plan(rows, by_file[fi], fi), self._table,
+                                    slot_alts[fi], g.slots, frame_duration, skipped=1 - tk)
+            gain = float(score[b]) - float(w_score[b]) if w_st[b] == AL.STATUS_OK else None
+            choices = AL.variant_choices(g, tk, segs, gain)
+            print(f"{audio_paths[fi]}: {len(choices)} groups, {sum(r.choice != 0 for r in choices)} not as written, gain "
+                  f"{'none' if gain is None else format(gain, '.3f')} nats")
+            out[fi] = ViterbiLabel(AL.with_end_pauses(free_segs[fi], segs, transcripts[fi]), None, None, {"variants": choices})
         return out
 
     def _greedy_and_plans(self, sel, by_file, free, audio_paths, transcripts, lang_name, filler=None):
@@ -1540,6 +1606,30 @@ def _read_draft(audio_path, draft_dir, forced):
     return draft
 
 
+def _read_variants(audio_paths, forced, output_names):
+    """opts.transcript_variants: the files whose transcript holds a group -> {file: its align.TranscriptGraph}; forced[fi] of such a
+    file becomes its first-variant expansion, the transcript as written.  A malformed transcript is a ValueError that names the
+    file and the place; so is an output name of the label set that holds a syntax character."""
+    clash = AL.variant_name_collisions(output_names)
+    if clash:
+        raise ValueError(f"transcript_variants: {', '.join(repr(n) for n in clash)} of this model's label set holds one of "
+                         f"{' '.join(AL.VARIANT_CHARS)}, which are syntax with the option on")
+    graphs = {}
+    for fi, tr in enumerate(forced):
+        if tr and AL.has_variants(tr):
+            txt = audio_paths[fi].replace(".wav", ".txt")
+            notes = []
+            try:
+                g = AL.compile_graph(AL.parse_variants(tr, notes))
+            except ValueError as err:
+                raise ValueError(f"{txt}: {err}") from None
+            for line in notes:
+                print(f"{txt}: {line}")
+            graphs[fi] = g
+            forced[fi] = [g.slots[k] for k in g.first]
+    return graphs
+
+
 def _read_forced(audio_path, verbose):
     """`{audio}.txt` forced phoneme list (infer.py:193, 210-215)."""
     txt = audio_path.replace(".wav", ".txt")
@@ -1659,7 +1749,7 @@ def _write_reports(lab_path, reports, fi):
     """File fi's side reports beside its .lab, one file per enabled kind the file has rows of, in reports.REPORTS' order."""
     for key, by_file in reports.rows.items():
         if by_file.get(fi) is not None:
-            _write_text(R.file_path(key, lab_path), R.file_text(key, by_file[fi]), R.REPORTS[key].what)
+            _write_text(R.file_path(key, lab_path), R.file_text(key, by_file[fi]), R.KINDS[key].what)
 
 
 def _write_score(lab_path, segments, score):
@@ -1677,7 +1767,7 @@ def infer_audio(audio_path, config_path="config.yaml", checkpoint_path="best_mod
                 duration_scores=None, optional_tokens=None, skip_penalty=None, optional_scores=None, filler_token=None,
                 filler_penalty=None, filler_scores=None, duration_prior=None, duration_prior_weight=None,
                 duration_prior_scores=None, decode_duration_prior=None, decode_duration_prior_weight=None,
-                decode_duration_scores=None, bigram_scores=None):
+                decode_duration_scores=None, transcript_variants=None, bigram_scores=None):
     """align: "greedy" | "viterbi" | None (config postprocess.align, else greedy): how a `{audio}.txt` transcript is aligned
     (Labeler.label_files).  align_scores (viterbi only; None: config postprocess.align_scores): also write `{stem}.scores.tsv`
     beside the .lab when the file was Viterbi-aligned (format_scores_tsv).  decode: "argmax" | "viterbi" | None (config
@@ -1727,7 +1817,8 @@ def infer_audio(audio_path, config_path="config.yaml", checkpoint_path="best_mod
                  optional_scores=optional_scores, filler_token=filler_token, filler_penalty=filler_penalty,
                  filler_scores=filler_scores, duration_prior=duration_prior, duration_prior_weight=duration_prior_weight,
                  duration_prior_scores=duration_prior_scores, decode_duration_prior=decode_duration_prior,
-                 decode_duration_prior_weight=decode_duration_prior_weight, decode_duration_scores=decode_duration_scores)
+                 decode_duration_prior_weight=decode_duration_prior_weight, decode_duration_scores=decode_duration_scores,
+                 transcript_variants=transcript_variants)
     _refuse_before_load(config_path, **given)
     lab = _labeler(config_path, checkpoint_path, device)
     opts = lab.options(**given)
@@ -1750,7 +1841,8 @@ def infer_folder(folder_path: str, config_path: str = "config.yaml", checkpoint_
                  align_edits=None, align_insertions=None, min_duration=None, duration_scores=None, optional_tokens=None,
                  skip_penalty=None, optional_scores=None, filler_token=None, filler_penalty=None, filler_scores=None,
                  duration_prior=None, duration_prior_weight=None, duration_prior_scores=None,
-                 decode_duration_prior=None, decode_duration_prior_weight=None, decode_duration_scores=None, bigram_scores=None):
+                 decode_duration_prior=None, decode_duration_prior_weight=None, decode_duration_scores=None,
+                 transcript_variants=None, bigram_scores=None):
     given = dict(align=align, align_scores=align_scores, decode=decode, switch_penalty=switch_penalty, decode_scores=decode_scores,
                  phoneme_bigram=phoneme_bigram, bigram_weight=bigram_weight, bigram_scores=bigram_scores, align_draft=align_draft,
                  draft_tolerance=draft_tolerance, align_edits=align_edits, align_insertions=align_insertions, min_duration=min_duration,
@@ -1758,7 +1850,8 @@ def infer_folder(folder_path: str, config_path: str = "config.yaml", checkpoint_
                  optional_scores=optional_scores, filler_token=filler_token, filler_penalty=filler_penalty,
                  filler_scores=filler_scores, duration_prior=duration_prior, duration_prior_weight=duration_prior_weight,
                  duration_prior_scores=duration_prior_scores, decode_duration_prior=decode_duration_prior,
-                 decode_duration_prior_weight=decode_duration_prior_weight, decode_duration_scores=decode_duration_scores)
+                 decode_duration_prior_weight=decode_duration_prior_weight, decode_duration_scores=decode_duration_scores,
+                 transcript_variants=transcript_variants)
     _refuse_before_load(config_path, **given)
     wav_files = sorted(f for f in os.listdir(folder_path) if f.lower().endswith(".wav"))
     os.makedirs(output_dir, exist_ok=True)
@@ -1788,7 +1881,7 @@ def infer_folder(folder_path: str, config_path: str = "config.yaml", checkpoint_
     def write_folder_reports(keys):
         for key in keys:
             if key in reports.rows:
-                write_folder(R.REPORTS[key].stem, R.folder_text(key, reports.named(key, wav_files)), R.REPORTS[key].what + " of the folder")
+                write_folder(R.KINDS[key].stem, R.folder_text(key, reports.named(key, wav_files)), R.KINDS[key].what + " of the folder")
 
     first = ("edits", "insertions")                       # draft_moves.tsv keeps its place between these two kinds and the later ones
 
@@ -1799,7 +1892,7 @@ def infer_folder(folder_path: str, config_path: str = "config.yaml", checkpoint_
     if opts.align_draft:
         write_folder("draft_moves", format_draft_moves_tsv([(wav_files[fi], reports.moves[fi]) for fi in sorted(reports.moves)]),
                      "Draft moves")
-    write_folder_reports([key for key in R.REPORTS if key not in first])
+    write_folder_reports([key for key in R.KINDS if key not in first])
     if opts.free_scores:
         write_folder("decode_scores", format_decode_review_tsv([(f, sc) for f, sc in zip(wav_files, all_scores) if isinstance(sc, DC.FreeScore)]),
                      "Decode review list")
@@ -1928,11 +2021,17 @@ def main(argv=None):
                   help="With --decode-duration-prior: --decode-scores for the duration-prior decode; the same {stem}.decode_scores.tsv "
                        "and decode_scores.tsv, from a semi-Markov forward-backward pass over the grammar with the search's tables on "
                        "the GPU. Default: config postprocess.decode_duration_scores, else off.")
+    @click.option("--transcript-variants", "transcript_variants", is_flag=True, default=None,
+                  help="With --align viterbi: '(', '|' and ')' in a {audio}.txt are syntax, 'k a ( t | d ) o ( N | )': 2 to 4 spellings "
+                       "of a stretch, the first the transcript as written, an empty one making it optional. The search chooses among "
+                       "them jointly on the GPU; {stem}.variants.tsv lists every group's choice and, for a folder, "
+                       "transcript_variants.tsv the choices that are not as written. Default: config "
+                       "postprocess.transcript_variants, else off.")
     def cli(path, checkpoint, config, output, lang_id, sample, top_k, top_p, temperature, device, confidence_threshold, align,
             align_scores, decode, switch_penalty, decode_scores, phoneme_bigram, bigram_weight, bigram_scores, align_draft,
             draft_tolerance, align_edits, align_insertions, min_duration, duration_scores, optional_tokens, skip_penalty,
             optional_scores, filler_token, filler_penalty, filler_scores, duration_prior, duration_prior_weight,
-            duration_prior_scores, decode_duration_prior, decode_duration_prior_weight, decode_duration_scores):
+            duration_prior_scores, decode_duration_prior, decode_duration_prior_weight, decode_duration_scores, transcript_variants):
         if switch_penalty is not None and not switch_penalty >= 0.0:
             raise click.UsageError("--switch-penalty must be >= 0 (nats)")
         if sample:
@@ -1972,7 +2071,7 @@ def main(argv=None):
                            duration_prior=duration_prior, duration_prior_weight=duration_prior_weight,
                            duration_prior_scores=duration_prior_scores, decode_duration_prior=decode_duration_prior,
                            decode_duration_prior_weight=decode_duration_prior_weight,
-                           decode_duration_scores=decode_duration_scores)
+                           decode_duration_scores=decode_duration_scores, transcript_variants=transcript_variants)
         except ValueError as err:
             raise click.UsageError(str(err))
         output_path = inf_path if output == "." else output
@@ -2004,7 +2103,7 @@ def main(argv=None):
                   duration_prior_scores=opts.duration_prior_scores,
                   decode_duration_prior=opts.decode_duration_prior or "",
                   decode_duration_prior_weight=opts.decode_duration_prior_weight if opts.decode_duration_prior else None,
-                  decode_duration_scores=opts.decode_duration_scores)
+                  decode_duration_scores=opts.decode_duration_scores, transcript_variants=opts.transcript_variants)
         if inf_path.is_dir():
             infer_folder(folder_path=str(inf_path), output_dir=str(output_path), **kw)
         else:

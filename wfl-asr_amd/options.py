@@ -82,6 +82,14 @@ infer_folder (before any model is loaded) and the CLI all call `resolve` and car
                            49. needs a decode_duration_prior (it scores the explicit-duration grammar of that search,
                                wfl_decode_duration_posterior: the same records as decode_scores; without a prior decode_scores, or
                                bigram_scores beside a phoneme_bigram, is the option to ask for)
+  transcript_variants off  50. a bool (true / false; no number, no string)
+                           51. needs align viterbi (the variants are arcs of that search: the transcript graph of wfl_align_graph)
+                           52. align_draft, min_duration, optional_tokens, filler_token, duration_prior, align_scores, align_edits,
+                               align_insertions, duration_scores, optional_scores, filler_scores and duration_prior_scores beside
+                               transcript_variants are refused, each by name (transcript_variants_error): their lattices are chains,
+                               and a search or a score must speak of the lattice the search ran on -- search first, scores later
+                           (53. with the model known, Labeler.label_files: an output name of the label set that holds one of `(`,
+                               `|`, `)` is refused by name, align.variant_name_collisions)
 """
 from __future__ import annotations
 
@@ -140,6 +148,17 @@ DECODE_DURATION_PRIOR_ERROR = ("decode_duration_prior cannot be combined with de
 DECODE_DURATION_SCORES_ERROR = ("decode_duration_scores needs a decode_duration_prior (postprocess.decode_duration_prior, "
                                 "--decode-duration-prior): it scores the explicit-duration grammar of that search; without a prior "
                                 "decode_scores (or bigram_scores beside a phoneme_bigram) is the option to ask for")
+
+
+# the options whose lattices are chains: refused beside transcript_variants, each by name
+CHAIN_ONLY_OPTIONS = ("align_draft", "min_duration", "optional_tokens", "filler_token", "duration_prior", "align_scores", "align_edits",
+                      "align_insertions", "duration_scores", "optional_scores", "filler_scores", "duration_prior_scores")
+
+
+def transcript_variants_error(names):
+    return (f"transcript_variants cannot be combined with {', '.join(names)}: their lattices are chains, the variants' is a graph, and "
+            "a search or a score must speak of the lattice the search ran on; drop postprocess.transcript_variants "
+            "(--transcript-variants) for that run, or search with the variants first and score the chosen transcript later")
 
 
 def _filler_token(given):
@@ -263,7 +282,8 @@ class PostOptions(_SearchOptions):
         duration_prior_scores  False  score every alignment searched under a duration_prior, over the explicit-duration lattice
         decode_duration_prior  None  path of a phoneme_durations.json: the duration prior of the free decode (decode viterbi)
         decode_duration_prior_weight  1.0  what that prior's log probabilities are multiplied by (also stands for "not given")
-        decode_duration_scores  False  score every file decoded under a decode_duration_prior, over the explicit-duration grammar"""
+        decode_duration_scores  False  score every file decoded under a decode_duration_prior, over the explicit-duration grammar
+        transcript_variants  False  `( a | b )` groups of a transcript are variants the search chooses among (wfl_align_graph)"""
     align_draft: Optional[str] = None
     draft_tolerance: float = DEFAULT_DRAFT_TOLERANCE
     align_edits: bool = False
@@ -282,12 +302,13 @@ class PostOptions(_SearchOptions):
     decode_duration_prior: Optional[str] = None
     decode_duration_prior_weight: float = DEFAULT_DURATION_PRIOR_WEIGHT
     decode_duration_scores: bool = False
+    transcript_variants: bool = False
 
     def __new__(cls, *args, align_draft=None, draft_tolerance=DEFAULT_DRAFT_TOLERANCE, align_edits=False, align_insertions=False,
                 min_duration=None, duration_scores=False, optional_tokens=None, skip_penalty=0.0, optional_scores=False,
                 filler_token=None, filler_penalty=DEFAULT_FILLER_PENALTY, filler_scores=False, duration_prior=None,
                 duration_prior_weight=DEFAULT_DURATION_PRIOR_WEIGHT, duration_prior_scores=False, decode_duration_prior=None,
-                decode_duration_prior_weight=DEFAULT_DURATION_PRIOR_WEIGHT, decode_duration_scores=False, **kw):
+                decode_duration_prior_weight=DEFAULT_DURATION_PRIOR_WEIGHT, decode_duration_scores=False, transcript_variants=False, **kw):
         self = super().__new__(cls, *args, **kw)
         object.__setattr__(self, "align_draft", align_draft)
         object.__setattr__(self, "draft_tolerance", draft_tolerance)
@@ -307,6 +328,7 @@ class PostOptions(_SearchOptions):
         object.__setattr__(self, "decode_duration_prior", decode_duration_prior)
         object.__setattr__(self, "decode_duration_prior_weight", decode_duration_prior_weight)
         object.__setattr__(self, "decode_duration_scores", decode_duration_scores)
+        object.__setattr__(self, "transcript_variants", transcript_variants)
         return self
 
     def __setattr__(self, name, value):
@@ -314,10 +336,10 @@ class PostOptions(_SearchOptions):
 
     _KEYWORD = ("align_draft", "draft_tolerance", "align_edits", "align_insertions", "min_duration", "duration_scores",
                 "optional_tokens", "skip_penalty", "duration_prior", "duration_prior_weight", "decode_duration_prior",
-                "decode_duration_prior_weight", "decode_duration_scores", "filler_scores", "duration_prior_scores", "optional_scores", "filler_token", "filler_penalty")
+                "decode_duration_prior_weight", "decode_duration_scores", "transcript_variants", "filler_scores", "duration_prior_scores", "optional_scores", "filler_token", "filler_penalty")
     # (the later options stand in front of optional_scores: the record's last fields are the filler's own two)
     _KEYWORD_DEFAULTS = (None, DEFAULT_DRAFT_TOLERANCE, False, False, None, False, None, 0.0, None, DEFAULT_DURATION_PRIOR_WEIGHT,
-                         None, DEFAULT_DURATION_PRIOR_WEIGHT, False, False, False, False, None, DEFAULT_FILLER_PENALTY)
+                         None, DEFAULT_DURATION_PRIOR_WEIGHT, False, False, False, False, False, None, DEFAULT_FILLER_PENALTY)
 
     def _draft(self):
         return self.align_draft, self.draft_tolerance
@@ -341,14 +363,15 @@ class PostOptions(_SearchOptions):
               min_duration=None, duration_scores=False, optional_tokens=None, skip_penalty=0.0, optional_scores=False,
               filler_token=None, filler_penalty=DEFAULT_FILLER_PENALTY, filler_scores=False, duration_prior=None,
               duration_prior_weight=DEFAULT_DURATION_PRIOR_WEIGHT, duration_prior_scores=False, decode_duration_prior=None,
-              decode_duration_prior_weight=DEFAULT_DURATION_PRIOR_WEIGHT, decode_duration_scores=False):
+              decode_duration_prior_weight=DEFAULT_DURATION_PRIOR_WEIGHT, decode_duration_scores=False, transcript_variants=False):
         return cls(*iterable, align_draft=align_draft, draft_tolerance=draft_tolerance, align_edits=align_edits,
                    align_insertions=align_insertions, min_duration=min_duration, duration_scores=duration_scores,
                    optional_tokens=optional_tokens, skip_penalty=skip_penalty, optional_scores=optional_scores,
                    filler_token=filler_token, filler_penalty=filler_penalty, filler_scores=filler_scores,
                    duration_prior=duration_prior, duration_prior_weight=duration_prior_weight,
                    duration_prior_scores=duration_prior_scores, decode_duration_prior=decode_duration_prior,
-                   decode_duration_prior_weight=decode_duration_prior_weight, decode_duration_scores=decode_duration_scores)
+                   decode_duration_prior_weight=decode_duration_prior_weight, decode_duration_scores=decode_duration_scores,
+                   transcript_variants=transcript_variants)
 
     def _replace(self, **kw):
         later = {k: kw.pop(k, getattr(self, k)) for k in self._KEYWORD}
@@ -384,7 +407,7 @@ def _number_ge0(x):
 
 def resolve(post, *, align=None, align_scores=None, decode=None, switch_penalty=None, decode_scores=None, phoneme_bigram=None,
             bigram_weight=None, bigram_scores=None, decode_duration_prior=None, decode_duration_prior_weight=None, decode_duration_scores=None,
-            align_draft=None, draft_tolerance=None, align_edits=None,
+            transcript_variants=None, align_draft=None, draft_tolerance=None, align_edits=None,
             align_insertions=None, min_duration=None, duration_scores=None, optional_tokens=None, skip_penalty=None,
             optional_scores=None, filler_token=None, filler_penalty=None, filler_scores=None, duration_prior=None,
             duration_prior_weight=None, duration_prior_scores=None) -> PostOptions:
@@ -541,6 +564,20 @@ def resolve(post, *, align=None, align_scores=None, decode=None, switch_penalty=
                          "argmax decode has no lattice to score")
     if decode_duration_scores and not decode_duration_prior:
         raise ValueError(DECODE_DURATION_SCORES_ERROR)
+    transcript_variants = pick("transcript_variants", transcript_variants, False)
+    if not isinstance(transcript_variants, bool):
+        raise ValueError(f"transcript_variants must be true or false, got {transcript_variants!r}")
+    if transcript_variants and align != "viterbi":
+        raise ValueError("transcript_variants needs align='viterbi' (postprocess.align: viterbi): the variants are arcs of the Viterbi "
+                         "search, the greedy match has none")
+    if transcript_variants:
+        given = {"align_draft": align_draft, "min_duration": min_duration is not None, "optional_tokens": optional_tokens is not None,
+                 "filler_token": filler_token is not None, "duration_prior": duration_prior, "align_scores": align_scores,
+                 "align_edits": align_edits, "align_insertions": align_insertions, "duration_scores": duration_scores,
+                 "optional_scores": optional_scores, "filler_scores": filler_scores, "duration_prior_scores": duration_prior_scores}
+        beside = [k for k in CHAIN_ONLY_OPTIONS if given[k]]
+        if beside:
+            raise ValueError(transcript_variants_error(beside))
     return PostOptions(align, align_scores, decode, switch_penalty, decode_scores, phoneme_bigram, bigram_weight, bigram_scores,
                        align_draft=align_draft, draft_tolerance=draft_tolerance, align_edits=align_edits,
                        align_insertions=align_insertions, min_duration=min_duration, duration_scores=duration_scores,
@@ -548,4 +585,5 @@ def resolve(post, *, align=None, align_scores=None, decode=None, switch_penalty=
                        filler_token=filler_token, filler_penalty=filler_penalty, filler_scores=filler_scores,
                        duration_prior=duration_prior, duration_prior_weight=duration_prior_weight,
                        duration_prior_scores=duration_prior_scores, decode_duration_prior=decode_duration_prior,
-                       decode_duration_prior_weight=decode_duration_prior_weight, decode_duration_scores=decode_duration_scores)
+                       decode_duration_prior_weight=decode_duration_prior_weight, decode_duration_scores=decode_duration_scores,
+                       transcript_variants=transcript_variants)

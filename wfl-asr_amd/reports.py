@@ -1,11 +1,12 @@
 """The side reports of a Viterbi-aligned labelling run: the files written beside the .lab files, `{stem}{suffix}` per labelled file and
-`{folder stem}.tsv` per folder.  REPORTS is the one table of their kinds; everything a kind needs is in its entry, and the callers
-(infer.py) loop over the table.  A kind's rows are computed in align.py (token_edits, place_insertions, skipped_tokens,
-optional_token_scores, filler_scores, token_durations; the FillerSpan rows in Labeler._clip_label) and travel from the search to the
-writer in a Reports.
+`{folder stem}.tsv` per folder.  KINDS is the one table of their kinds -- REPORTS, the seven kinds that report on a chain lattice,
+and behind them the kinds that came later (`variants`, of the transcript graph); everything a kind needs is in its entry, and the
+callers (infer.py) loop over the table.  A kind's rows are computed in align.py (token_edits, place_insertions, skipped_tokens,
+optional_token_scores, filler_scores, token_durations, variant_choices; the FillerSpan rows in Labeler._clip_label) and travel from
+the search to the writer in a Reports.
 
-A new kind: its row record and an entry of REPORTS here, its row builder in align.py, and one line of Labeler._clip_label that puts
-the rows under the kind's key."""
+A new kind: its row record and an entry of KINDS here, its row builder in align.py, and one line of the Labeler stage that puts the
+rows under the kind's key (Labeler._clip_label; Labeler._search_variants for `variants`)."""
 import os
 from typing import Callable, NamedTuple
 
@@ -102,6 +103,16 @@ class TokenDuration(NamedTuple):
     expected_frames: float  # frames + end_mean - start_mean: the posterior mean of the token's length (exact, by linearity)
 
 
+class VariantChoice(NamedTuple):
+    index: int              # the group's index among the transcript's groups
+    start_s: float          # the chosen variant on the .lab clock; for an empty one both are the time of the place
+    end_s: float
+    choice: int             # the chosen variant's number, 0 the transcript as written
+    spelling: str           # its tokens ("" for the empty variant)
+    written: str            # the first variant's tokens
+    gain: float             # the file's gain in nats: the graph's score minus the score of the transcript as written (None: that has no path)
+
+
 # ------------------------------------------------------------------------------------------------------------- a row's cells, as text
 def _edit_cells(r: TokenEdit):
     return [str(r.index), r.token, f"{r.start_s:.7f}", f"{r.end_s:.7f}", r.best, f"{r.best_ratio:.6g}", r.second,
@@ -135,6 +146,11 @@ def _duration_cells(r: TokenDuration):
     return [str(r.index), r.token, f"{r.start_s:.7f}", f"{r.end_s:.7f}", str(r.frames),
             "none" if r.log_prior is None else f"{r.log_prior:.6f}", f"{r.posterior:.6f}", f"{r.start_shift_s:.7f}", f"{r.start_sd_s:.7f}",
             f"{r.end_shift_s:.7f}", f"{r.end_sd_s:.7f}", f"{r.expected_frames:.4f}"]
+
+
+def _variant_cells(r: VariantChoice):
+    return [str(r.index), f"{r.start_s:.7f}", f"{r.end_s:.7f}", str(r.choice), r.spelling, r.written,
+            "none" if r.gain is None else f"{r.gain:.6g}"]
 
 
 # ------------------------------------------------------------------------------------------------------------------------ the table
@@ -182,29 +198,39 @@ REPORTS = {k.key: k for k in (
          _duration_cells, keep=lambda r: r.log_prior is not None, order=lambda r: r.log_prior, missing="no duration-prior scores"),
 )}
 
+# REPORTS is the table of the seven kinds that report on a chain lattice; KINDS is the whole table, those and the kinds that came
+# after them.  Everything below, and every caller, looks a kind up in KINDS.
+KINDS = {**REPORTS, **{k.key: k for k in (
+    # per group of a transcript with variants; the folder file: every group whose choice is not the transcript as written, the file
+    # with the largest gain first (a file without a gain last)
+    Kind("variants", lambda o: getattr(o, "transcript_variants", False), ".variants.tsv", "transcript_variants", "Transcript variants",
+         "index\tstart_s\tend_s\tvariant\tspelling\twritten\tgain_nats", _variant_cells,
+         keep=lambda r: r.choice != 0, order=lambda r: float("inf") if r.gain is None else -r.gain),
+)}}
+
 
 def file_text(key, rows) -> str:
     """`{stem}{suffix}` of one file: the header, then one line per row (an empty report is its header alone)."""
-    kind = REPORTS[key]
+    kind = KINDS[key]
     return "".join(line + "\n" for line in [kind.header] + ["\t".join(kind.cells(r)) for r in rows])
 
 
 def folder_rows(key, per_file):
     """per_file: [(file name, rows)] -> the rows of the kind's folder file as [(file name, row)]: Kind.keep, Kind.order."""
-    kind = REPORTS[key]
+    kind = KINDS[key]
     flat = [(name, r) for name, rows in per_file for r in rows if kind.keep is None or kind.keep(r)]
     return flat if kind.order is None else sorted(flat, key=lambda nr: kind.order(nr[1]))      # (stable: the descending ones negate)
 
 
 def folder_text(key, per_file) -> str:
     """`{folder stem}.tsv`: folder_rows, the file's name in front of the row's own columns."""
-    kind = REPORTS[key]
+    kind = KINDS[key]
     lines = ["file\t" + kind.header] + ["\t".join([name] + kind.cells(r)) for name, r in folder_rows(key, per_file)]
     return "".join(line + "\n" for line in lines)
 
 
 def file_path(key, lab_path) -> str:
-    return os.path.splitext(lab_path)[0] + REPORTS[key].suffix
+    return os.path.splitext(lab_path)[0] + KINDS[key].suffix
 
 
 class Reports:
@@ -218,7 +244,7 @@ class Reports:
 
     @classmethod
     def for_options(cls, opts):
-        return cls(key for key, kind in REPORTS.items() if kind.enabled(opts))
+        return cls(key for key, kind in KINDS.items() if kind.enabled(opts))
 
     def take(self, fi, rows_of, moves=None):
         """File fi's rows by kind (a kind that is not enabled is dropped) and its draft moves (None: none)."""
