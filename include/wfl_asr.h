@@ -355,6 +355,30 @@ int32_t wfl_op_layernorm(const void* x, int64_t ldx, void* y, int64_t ldy, const
 int32_t wfl_op_tag_decide(const float* logits, int64_t ldl, int32_t rows, int32_t C, float threshold, int32_t o_id,
                           int32_t* ids, int32_t* argmax, float* maxprob, void* stream);
 
+/* One BiLSTM layer's recurrence (csrc/lstm.hip; nn.LSTM at model.py:104-111 behind its input projection), every field of csrc/common.h's
+ * LstmArgs:   gates_t = gx_t + W_hh h_(t-1),  c_t = f c_(t-1) + i g,  h_t = o tanh(c_t),  zero initial state, both directions in one launch.
+ *   gx      fp32 frame rows (row lead + b P + t, ldgx floats per row): the input projection x W_ih^T + b_ih + b_hh of both directions,
+ *           column dir * 4H + 4 * unit + gate (gate 0 .. 3 = i, f, g, o; dir 0 forward, 1 backward)
+ *   out     bf16 frame rows (same row mapping, ldo per row): column dir * H + unit.  Rows t >= T (>= clip_T[b] when given), the rows
+ *           between clips and the columns beyond 2H are not written.  A clip's rows do not depend on the other clips of the batch.
+ *   whh     wfl_op_lstm_pack_whh's hi output on the device, packed for the U passed here
+ *   whh_lo + out_lo (both or neither)   `model.precision: high`: W_hh and h as bf16 pairs hi + lo, three MFMA passes; out_lo = bf16(h - out)
+ *   clip_T  [B] int32 on the device or null: frames per clip, 0 <= clip_T[b] <= T; the backward direction of clip b starts at its own last frame
+ *   U       hidden units per workgroup: a multiple of 8, at most 32, dividing H, H / U <= 64; <= 0: the default for H
+ *   exchange   device scratch through which the workgroups of a direction hand h to each other, 16-byte aligned, at least
+ *           wfl_op_lstm_exchange_bytes(H, B) bytes; the launch clears it itself, so any content may be passed and it may be reused
+ *   status  device error word, required: a hand-off wait that gives up ORs 1 into it (the output is invalid then); never cleared here
+ * H is one of 32, 64, 128, 192, 256, 384, 512, 640.  ldgx % 4 == 0, ldgx >= 8H, ldo % 8 == 0, ldo >= 2H, P >= T >= 1, B >= 1.  Anything
+ * else is an error status with a wfl_last_error() text, and nothing is launched.
+ * wfl_op_lstm_pack_whh (host only): weight_hh of both directions, [2][4H][H] fp32 in PyTorch's row order (blocks i | f | g | o of H rows)
+ * -> the slice-major [2][H / U][4U][H] bf16 high halves (row 4 * u_local + gate of slice unit / U) and, lo_host not null, the low halves
+ * bf16(w - hi) in the same layout.  The model loader packs with this function. */
+int64_t wfl_op_lstm_exchange_bytes(int32_t H, int32_t B);
+int32_t wfl_op_lstm_pack_whh(const float* whh_host, int32_t H, int32_t U, uint16_t* hi_host, uint16_t* lo_host);
+int32_t wfl_op_lstm(const float* gx, int64_t ldgx, const void* whh, const void* whh_lo, void* out, void* out_lo, int64_t ldo,
+                    int64_t lead, int32_t B, int32_t T, int32_t P, int32_t H, int32_t U, const int32_t* clip_T,
+                    void* exchange, int64_t exchange_bytes, int32_t* status, void* stream);
+
 /* Per-kernel timing hook for bench.py's roofline: when enabled, wfl_forward brackets every GEMM launch with
  * hipEvents on `stream`.  wfl_gemm_profile_read synchronises on them and returns, per GEMM kernel variant
  * (key = act | glu<<2 | out_f32<<3 | res<<4 | kernel<<5 | ln_fold<<8 | stats<<10, one template instantiation = one

@@ -192,3 +192,28 @@ def conv0(wav, ldw, B, L, w, gamma, beta, Cn, T0, out, lead, P, group_norm, lens
     if check:
         _lib.check(rc, "wfl_op_conv0")
     return rc
+
+
+def lstm_exchange_bytes(H, B):
+    return int(lib().wfl_op_lstm_exchange_bytes(H, B))
+
+
+def lstm_pack_whh(whh, H, U=0, lo=True):
+    """wfl_op_lstm_pack_whh: weight_hh of both directions [2, 4H, H] fp32 (CPU) -> the packed bf16 (hi, lo or None) on the device."""
+    w = whh.detach().float().contiguous().numpy()
+    hi = torch.empty(2 * 4 * H * H, dtype=torch.int16)
+    lo_t = torch.empty_like(hi) if lo else None
+    rc = lib().wfl_op_lstm_pack_whh(_lib.host_ptr(w), H, U, C.c_void_p(hi.data_ptr()), C.c_void_p(lo_t.data_ptr()) if lo else None)
+    _lib.check(rc, "wfl_op_lstm_pack_whh")
+    return hi.view(torch.bfloat16).cuda(), (lo_t.view(torch.bfloat16).cuda() if lo else None)
+
+
+def lstm(gx, ldgx, whh, out, ldo, lead, B, T, P, H, exchange, status, U=0, whh_lo=None, out_lo=None, clip_T=None, exchange_bytes=None, check=True):
+    """wfl_op_lstm: gx fp32 / out bf16 frame rows, whh (+ whh_lo) from lstm_pack_whh, clip_T an int32 device tensor or None, exchange a
+    uint8 device tensor, status an int32 device tensor of one element.  -> the status code."""
+    nbytes = exchange.numel() * exchange.element_size() if exchange_bytes is None else exchange_bytes
+    rc = lib().wfl_op_lstm(ptr(gx), ldgx, ptr(whh), ptr(whh_lo), ptr(out), ptr(out_lo), ldo, lead, B, T, P, H, U, ptr(clip_T), ptr(exchange),
+                           nbytes, ptr(status), stream())
+    if check:
+        _lib.check(rc, "wfl_op_lstm")
+    return rc

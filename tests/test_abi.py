@@ -207,3 +207,85 @@ def test_gemm_ex_validates_its_arguments_without_gpu(libpath):
                      (dict(P=12), b"wfl_op_gemm_ex")):
         rc, kid, msg = call(**kw)
         assert rc != 0 and kid == 0 and word in msg, (kw, rc, kid, msg)
+
+
+def _lstm_call(lib, **kw):
+    """wfl_op_lstm on made-up addresses (aligned; nothing is dereferenced before the checks pass and nothing launches here)"""
+    a = ctypes.c_void_p(0x10000)
+    f = dict(gx=a, ldgx=8 * 64, whh=a, whh_lo=None, out=a, out_lo=None, ldo=2 * 64, lead=8, B=3, T=5, P=16, H=64, U=0, clip_T=None, exchange=a,
+             exchange_bytes=lib.wfl_op_lstm_exchange_bytes(64, 3), status=a)
+    f.update(kw)
+    rc = lib.wfl_op_lstm(f["gx"], f["ldgx"], f["whh"], f["whh_lo"], f["out"], f["out_lo"], f["ldo"], f["lead"], f["B"], f["T"], f["P"], f["H"],
+                         f["U"], f["clip_T"], f["exchange"], f["exchange_bytes"], f["status"], None)
+    return rc, lib.wfl_last_error()
+
+
+def test_lstm_op_validates_its_arguments_without_gpu(libpath):
+    """wfl_op_lstm (the BiLSTM recurrence at the operator level): every refusal the header lists comes back as a negative status and a
+    message before anything is launched (no GPU exists here: a launch would fail differently, with "launch failure")."""
+    from wfl_asr_amd import _lib
+    lib = _lib.load()
+    a = ctypes.c_void_p(0x10000)
+    assert lib.wfl_op_lstm_exchange_bytes(64, 3) > 0
+    assert lib.wfl_op_lstm_exchange_bytes(256, 17) == 2 * lib.wfl_op_lstm_exchange_bytes(256, 16) - 64      # two clip groups
+    assert lib.wfl_op_lstm_exchange_bytes(96, 3) < 0 and b"96" in lib.wfl_last_error()
+    for kw, word in ((dict(gx=None), b"null"), (dict(whh=None), b"null"), (dict(out=None), b"null"), (dict(exchange=None), b"null"),
+                     (dict(status=None), b"null"),
+                     (dict(whh_lo=a), b"go together"), (dict(out_lo=a), b"go together"),
+                     (dict(H=96), b"hidden size 96"), (dict(H=768), b"hidden size 768"), (dict(H=0), b"hidden size 0"),
+                     (dict(U=12), b"U must"), (dict(U=40), b"U must"), (dict(U=24), b"U must"), (dict(H=640, ldgx=8 * 640, ldo=1280, U=8), b"U must"),
+                     (dict(ldgx=8 * 64 + 2), b"ldgx"), (dict(ldgx=8 * 64 - 4), b"ldgx"),
+                     (dict(ldo=2 * 64 + 4), b"ldo"), (dict(ldo=2 * 64 - 8), b"ldo"),
+                     (dict(P=4), b"P >= T"), (dict(T=0), b"T >= 1"), (dict(B=0), b"B >= 1"),
+                     (dict(exchange_bytes=lib.wfl_op_lstm_exchange_bytes(64, 3) - 1), b"exchange_bytes"),
+                     (dict(B=17), b"exchange_bytes")):
+        rc, msg = _lstm_call(lib, **kw)
+        assert rc < 0 and b"wfl_op_lstm" in msg and word in msg and b"launch failure" not in msg, (kw, rc, msg)
+
+
+def test_lstm_pack_whh_is_the_documented_layout(libpath):
+    """wfl_op_lstm_pack_whh (what the model loader packs W_hh with) against a numpy restatement of the header's layout:
+    [2][H / U][4U][H], row 4 * u_local + gate of slice unit / U, from PyTorch's blocks i | f | g | o; hi = bf16(w), lo = bf16(w - hi)."""
+    import numpy as np
+    from wfl_asr_amd import _lib
+    lib = _lib.load()
+
+    def bf16_bits(x):
+        u = np.ascontiguousarray(x, np.float32).view(np.uint32).astype(np.uint64)
+        return (((u + 0x7FFF + ((u >> 16) & 1)) >> 16) & 0xFFFF).astype(np.uint16)
+
+    rng = np.random.RandomState(3)
+    for H, U in ((32, 0), (32, 8), (64, 16), (192, 8), (128, 0)):
+        w = (rng.uniform(-1, 1, (2, 4 * H, H)) * H ** -0.5).astype(np.float32)
+        hi, lo = np.full((2, 4 * H, H), 0xFFFF, np.uint16), np.full((2, 4 * H, H), 0xFFFF, np.uint16)
+        assert lib.wfl_op_lstm_pack_whh(_lib.host_ptr(w), H, U, _lib.host_ptr(hi), _lib.host_ptr(lo)) == 0, lib.wfl_last_error()
+        Ue = U if U > 0 else 32
+        # [dir][gate][unit][k] -> [dir][slice][u_local][gate][k]
+        want = w.reshape(2, 4, H // Ue, Ue, H).transpose(0, 2, 3, 1, 4).reshape(2, 4 * H, H)
+        want_hi = bf16_bits(want)
+        back = (want_hi.astype(np.uint32) << 16).view(np.float32)
+        assert np.array_equal(hi, want_hi), (H, U)
+        assert np.array_equal(lo, bf16_bits(want - back)), (H, U)
+        hi2 = np.zeros_like(hi)
+        assert lib.wfl_op_lstm_pack_whh(_lib.host_ptr(w), H, U, _lib.host_ptr(hi2), None) == 0 and np.array_equal(hi2, hi)
+    assert lib.wfl_op_lstm_pack_whh(_lib.host_ptr(w), 96, 0, _lib.host_ptr(hi), None) < 0 and b"96" in lib.wfl_last_error()
+    assert lib.wfl_op_lstm_pack_whh(_lib.host_ptr(w), 128, 12, _lib.host_ptr(hi), None) < 0 and b"U must" in lib.wfl_last_error()
+    assert lib.wfl_op_lstm_pack_whh(None, 128, 0, _lib.host_ptr(hi), None) < 0 and b"null" in lib.wfl_last_error()
+
+
+def test_finalize_refuses_an_unsupported_bilstm_hidden_size_without_gpu(libpath):
+    """A BiLSTM whose hidden size d / 2 the recurrence has no kernel for (768: a slice width exists, an instantiation does not) is refused
+    by wfl_finalize with the size named -- it used to load and fail in the first forward with "lstm launch failed (-4)"."""
+    from wfl_asr_amd import _lib
+    lib = _lib.load()
+    for d, ok in ((1536, False), (192, False), (512, True)):
+        a = _lib.WflArch()
+        a.abi_version = _lib.ABI_VERSION
+        a.d_model, a.enc_layers, a.enc_heads, a.enc_ffn, a.n_mels, a.max_positions = d, 1, 4, 4 * d, 80, 100
+        a.num_classes, a.o_id, a.enable_bilstm, a.bilstm_layers = 5, 4, 1, 1
+        h = ctypes.c_void_p(0)
+        assert lib.wfl_create(ctypes.byref(a), ctypes.byref(h)) == 0 and h.value, lib.wfl_last_error()
+        rc, msg = lib.wfl_finalize(h), lib.wfl_last_error()
+        lib.wfl_destroy(h)
+        assert rc != 0
+        assert (f"BiLSTM hidden size {d // 2} is not supported".encode() in msg) == (not ok), (d, msg)

@@ -95,6 +95,9 @@ SIGNATURES = {
     "wfl_op_layernorm_pair": (_I, [_P, _P, _P, _P, _P, _P, _L, _P, _P, _P, _P, _F, _L, _I, _I, _I, _I, _I, _P, _P]),
     "wfl_op_layernorm": (_I, [_P, _L, _P, _L, _P, _P, _F, _L, _I, _I, _I, _I, _P]),
     "wfl_op_tag_decide": (_I, [_P, _L, _I, _I, _F, _I, _P, _P, _P, _P]),
+    "wfl_op_lstm_exchange_bytes": (_L, [_I, _I]),
+    "wfl_op_lstm_pack_whh": (_I, [_P, _I, _I, _P, _P]),
+    "wfl_op_lstm": (_I, [_P, _L, _P, _P, _P, _P, _L, _L, _I, _I, _I, _I, _I, _P, _P, _L, _P, _P]),
     "wfl_host_median_filter": (_I, [_P, _I, _I, _P]),
     "wfl_host_decode_bio": (_I, [_P, _I, _P, _I, _P, _P, _I, C.c_double, _P, _P, _P, _I]),
     "wfl_host_merge_segments": (_I, [_P, _P, _P, _I, _I]),

@@ -453,6 +453,13 @@ static int launch_lstm_t(const LstmArgs& a, int groups, hipStream_t s) {
 
 bool wfl_lstm_split_precision_supported(int H) { return H <= 640; }
 
+// The hidden sizes (per direction) the recurrence is instantiated for: the cases of wfl_launch_lstm's switch, asked by the launcher
+// itself, by the operator entry (wfl_op_lstm) and by the loader (wfl_finalize), so that a size without a kernel is refused where the
+// model is built and not by the first forward.
+bool wfl_lstm_hidden_supported(int H) {
+  return H == 32 || H == 64 || H == 128 || H == 192 || H == 256 || H == 384 || H == 512 || H == 640;
+}
+
 // Units per WG: 32 (four waves x one pair of 16-row tiles) when it divides H, else the largest multiple of 8 below that does.
 // Measured at H = 256, 16 clips (tools/micro/lstm_bench.hip): 64 units per WG (4 WGs per direction) 2.14 us per step, 32 units
 // (8 WGs) 1.76 us, 16 units 1.77 us -- the step is hand-off latency plus one WG's own MFMA + cell update, so halving the slice
@@ -478,6 +485,7 @@ long wfl_lstm_exchange_bytes(int H, int B) {
 int wfl_launch_lstm(LstmArgs a, void* exchange, hipStream_t s) {
   if (a.U <= 0 || a.U % 8 || a.U > 32 || a.H % a.U || a.H % 32 || a.ldgx % 4 || a.ldo % 8 || a.T <= 0 || a.B <= 0) return -1;
   if (!a.error) return -1;                 // the forward's error word (ORed into, never cleared here)
+  if (!wfl_lstm_hidden_supported(a.H)) return -4;
   a.G = a.H / a.U;
   const int groups = (a.B + 15) / 16;
   if (2 * a.G > 128) return -5;

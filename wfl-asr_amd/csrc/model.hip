@@ -45,6 +45,7 @@ int wfl_launch_layernorm_pair(const bf16_t* x, const bf16_t* x_lo, bf16_t* y1, b
 int wfl_lstm_units_per_wg(int H);
 long wfl_lstm_exchange_bytes(int H, int B);
 bool wfl_lstm_split_precision_supported(int H);
+bool wfl_lstm_hidden_supported(int H);
 int wfl_launch_rows_fp8(const bf16_t* x, long ldx, const bf16_t* x_lo, const float* g, const float* b, float eps, long lead, int B, int P,
                         int T, int C, unsigned char* y8, long ldy8, float* scale, hipStream_t s, unsigned char* y8_lo = nullptr);          // norm.hip
 int wfl_launch_axpy(float* dst, const float* src, long n, float alpha, int init, hipStream_t s);
@@ -73,6 +74,40 @@ static inline uint16_t f32_to_bf16_bits(float f) {
 }
 
 static inline long round_up(long x, long m) { return (x + m - 1) / m * m; }
+
+static std::string lstm_hidden_refusal(int H) {
+  return "BiLSTM hidden size " + std::to_string(H) + " is not supported (32, 64, 128, 192, 256, 384, 512 or 640 per direction)";
+}
+
+// the launcher's rules for the slice width (wfl_launch_lstm): a multiple of 8, at most 32, dividing H, at most 64 slices per direction
+static bool lstm_units_ok(int H, int U) { return U >= 8 && U % 8 == 0 && U <= 32 && H % U == 0 && H / U <= 64; }
+
+// nn.LSTM's weight_hh of both directions -> the recurrence kernel's operand (lstm.hip): slice-major [dir][slice][4 * u_local + gate][H],
+// so that the workgroup of slice s reads one contiguous 4U x H block whose rows hold the four gates of a unit side by side.
+int32_t wfl_op_lstm_pack_whh(const float* whh_host, int32_t H, int32_t U, uint16_t* hi_host, uint16_t* lo_host) {
+  if (!whh_host || !hi_host) return fail(-1, "wfl_op_lstm_pack_whh: null argument");
+  if (!wfl_lstm_hidden_supported(H)) return fail(-4, "wfl_op_lstm_pack_whh: " + lstm_hidden_refusal(H));
+  if (U <= 0) U = wfl_lstm_units_per_wg(H);
+  if (!lstm_units_ok(H, U)) return fail(-1, "wfl_op_lstm_pack_whh: U must be a multiple of 8, at most 32, divide H and leave at most 64 slices");
+  const int G = H / U;
+  for (int dir = 0; dir < 2; ++dir)
+    for (int u = 0; u < H; ++u)
+      for (int gate = 0; gate < 4; ++gate) {
+        const size_t src = (size_t)dir * 4 * H + (size_t)gate * H + u;       // PyTorch's row order: blocks i | f | g | o of H rows
+        const int sl = u / U, ul = u % U;
+        const size_t wrow = ((size_t)(dir * G + sl) * 4 * U) + 4 * ul + gate;
+        for (int k = 0; k < H; ++k) {
+          const float x = whh_host[src * H + k];
+          const uint16_t hb = f32_to_bf16_bits(x);
+          const uint32_t u32 = (uint32_t)hb << 16;
+          float xh;
+          memcpy(&xh, &u32, 4);
+          hi_host[wrow * H + k] = hb;
+          if (lo_host) lo_host[wrow * H + k] = f32_to_bf16_bits(x - xh);
+        }
+      }
+  return 0;
+}
 #define WAVLM_MAX_T 4096   // frames per clip the relative-position bucket table covers (81 s of audio)
 
 struct HostTensor {
@@ -859,11 +894,10 @@ static int finalize_head(wfl_model* m, Packer& P) {
     // unit-major / gate-minor for the recurrence kernel (lstm.hip); b_ih + b_hh fold into the projection bias.
     const int H = d / 2;
     m->lstm_U = wfl_lstm_units_per_wg(H);
-    if (m->lstm_U <= 0 && P.err.empty()) P.err = "BiLSTM hidden size " + std::to_string(H) + " is not supported";
-    const int U = std::max(m->lstm_U, 1), G = H / U;
+    if ((m->lstm_U <= 0 || !wfl_lstm_hidden_supported(H)) && P.err.empty()) P.err = lstm_hidden_refusal(H);
     for (int layer = 0; layer < a.bilstm_layers && P.err.empty(); ++layer) {
       const int din = d;      // layer 0: encoder width d; deeper layers: 2H = d
-      std::vector<float> rows((size_t)8 * H * din), bias((size_t)8 * H);
+      std::vector<float> rows((size_t)8 * H * din), bias((size_t)8 * H), whh_f((size_t)2 * 4 * H * H);
       std::vector<uint16_t> whh((size_t)2 * 4 * H * H), whh_lo((size_t)2 * 4 * H * H);
       for (int dir = 0; dir < 2; ++dir) {
         const std::string suf = "_l" + std::to_string(layer) + (dir ? "_reverse" : "");
@@ -878,21 +912,11 @@ static int finalize_head(wfl_model* m, Packer& P) {
             const size_t dst = (size_t)dir * 4 * H + 4 * u + gate;
             memcpy(&rows[dst * din], &wih->data[(size_t)src * din], sizeof(float) * din);
             bias[dst] = bih->data[src] + bhh->data[src];
-            // slice-major packing: [dir][slice][4*u_local + gate][H]
-            const int sl = u / U, ul = u % U;
-            const size_t wrow = ((size_t)(dir * G + sl) * 4 * U) + 4 * ul + gate;
-            for (int k = 0; k < H; ++k) {
-              const float x = whh_t->data[(size_t)src * H + k];
-              const uint16_t hb = f32_to_bf16_bits(x);
-              const uint32_t u32 = (uint32_t)hb << 16;
-              float xh;
-              memcpy(&xh, &u32, 4);
-              whh[wrow * H + k] = hb;
-              whh_lo[wrow * H + k] = f32_to_bf16_bits(x - xh);
-            }
           }
+        memcpy(&whh_f[(size_t)dir * 4 * H * H], whh_t->data.data(), sizeof(float) * 4 * H * H);
       }
       if (!P.err.empty()) break;
+      if (wfl_op_lstm_pack_whh(whh_f.data(), H, m->lstm_U, whh.data(), whh_lo.data())) { P.err = g_err; break; }
       m->lstm_in.push_back(P.pack(rows, 8 * H, din, &bias));
       m->lstm_whh.push_back((bf16_t*)P.upload(whh));
       m->lstm_whh_lo.push_back((a.precision && wfl_lstm_split_precision_supported(H)) ? (bf16_t*)P.upload(whh_lo) : nullptr);
@@ -1021,6 +1045,8 @@ static int finalize_head(wfl_model* m, Packer& P) {
 int32_t wfl_finalize(wfl_model* m) {
   if (!m) return fail(-1, "wfl_finalize: null model");
   if (m->finalized) return fail(-1, "wfl_finalize: already finalized");
+  // a hidden size the recurrence has no kernel for is refused here, by name, and not by the first forward (before any device call)
+  if (m->a.enable_bilstm && !wfl_lstm_hidden_supported(m->a.d_model / 2)) return fail(-2, "wfl_finalize: " + lstm_hidden_refusal(m->a.d_model / 2));
   Packer P{m};
   if (hipGetDevice(&m->device) != hipSuccess) return fail(-10, "wfl_finalize: hipGetDevice failed");
   if (m->a.encoder_type == WFL_ENC_WHISPER) finalize_whisper(m, P);
@@ -2403,6 +2429,34 @@ int32_t wfl_op_tag_decide(const float* logits, int64_t ldl, int32_t rows, int32_
   t.ids = ids; t.argmax = argmax; t.maxprob = maxprob;
   const int r = wfl_launch_tag_decide(t, (hipStream_t)stream);
   return r ? fail(r, "wfl_op_tag_decide: launch failure") : 0;
+}
+
+int64_t wfl_op_lstm_exchange_bytes(int32_t H, int32_t B) {
+  if (!wfl_lstm_hidden_supported(H) || B < 1) return fail(-1, "wfl_op_lstm_exchange_bytes: " + (B < 1 ? std::string("B < 1") : lstm_hidden_refusal(H)));
+  return wfl_lstm_exchange_bytes(H, B);
+}
+
+int32_t wfl_op_lstm(const float* gx, int64_t ldgx, const void* whh, const void* whh_lo, void* out, void* out_lo, int64_t ldo, int64_t lead,
+                    int32_t B, int32_t T, int32_t P, int32_t H, int32_t U, const int32_t* clip_T, void* exchange, int64_t exchange_bytes,
+                    int32_t* status, void* stream) {
+  if (!gx || !whh || !out || !exchange || !status) return fail(-1, "wfl_op_lstm: null argument (gx, whh, out, exchange and status are required)");
+  if (!whh_lo != !out_lo) return fail(-1, "wfl_op_lstm: whh_lo and out_lo go together");
+  if (!wfl_lstm_hidden_supported(H)) return fail(-4, "wfl_op_lstm: " + lstm_hidden_refusal(H));
+  if (U <= 0) U = wfl_lstm_units_per_wg(H);
+  if (!lstm_units_ok(H, U)) return fail(-1, "wfl_op_lstm: U must be a multiple of 8, at most 32, divide H and leave at most 64 slices");
+  if (B < 1 || T < 1 || P < T || lead < 0) return fail(-1, "wfl_op_lstm: bad shape (B >= 1, T >= 1, P >= T, lead >= 0)");
+  if (ldgx % 4 || ldgx < 8L * H) return fail(-1, "wfl_op_lstm: ldgx must be a multiple of 4 and at least 8 H");
+  if (ldo % 8 || ldo < 2L * H) return fail(-1, "wfl_op_lstm: ldo must be a multiple of 8 and at least 2 H");
+  // the kernel's access widths: 16-byte gx, W_hh and granule loads, 4-byte stores of two hidden values
+  if ((((uintptr_t)gx | (uintptr_t)whh | (uintptr_t)whh_lo | (uintptr_t)exchange) & 15) || (((uintptr_t)out | (uintptr_t)out_lo) & 3))
+    return fail(-1, "wfl_op_lstm: gx, whh, whh_lo and exchange must be 16-byte aligned, out and out_lo 4-byte aligned");
+  if (exchange_bytes < wfl_lstm_exchange_bytes(H, B))
+    return fail(-1, "wfl_op_lstm: exchange_bytes is below wfl_op_lstm_exchange_bytes(H, B) = " + std::to_string(wfl_lstm_exchange_bytes(H, B)));
+  LstmArgs la{};
+  la.gx = gx; la.ldgx = ldgx; la.whh = (const bf16_t*)whh; la.whh_lo = (const bf16_t*)whh_lo; la.out = (bf16_t*)out; la.out_lo = (bf16_t*)out_lo;
+  la.ldo = ldo; la.lead = lead; la.B = B; la.T = T; la.P = P; la.H = H; la.U = U; la.error = (unsigned*)status; la.clip_T = clip_T;
+  const int r = wfl_launch_lstm(la, exchange, (hipStream_t)stream);
+  return r ? fail(r, "wfl_op_lstm: launch failure (" + std::to_string(r) + ")") : 0;
 }
 
 int32_t wfl_gemm_profile_enable(wfl_model* m, int32_t on) {

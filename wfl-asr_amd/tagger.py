@@ -174,7 +174,8 @@ class BIOPhonemeTagger:
         return int(self._lib.wfl_num_frames(self._handle, int(L)))
 
     def effective_precision(self) -> str:
-        """What `model.precision` turned into for this model (a wide BiLSTM under `precision: high` keeps a bf16 recurrence, by request)."""
+        """What `model.precision` turned into for this model.  Under `precision: high` every product runs in split precision, the
+        BiLSTM recurrence included at every hidden size up to 640 (above 256 in its four-wave form); wider is refused by the constructor."""
         return self.precision_note
 
     def batches_in_flight(self) -> int:
